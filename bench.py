@@ -44,6 +44,11 @@ one-GPU box can rehearse).  `device_ms.effective_mhz` is the clock the headline 
 measured inside a stamped build of it (ta_clock_probe) right after the timed region;
 `roofline.model_ceiling` is what this transform structure can reach under the package power
 limit.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0), as a caller of the path
+receives it, to DIR/<name>.npy in float64: `timeseries` and, with --by-particle,
+`vacf_by_particle` / `visc_by_particle` (this rank's particles; a fixed seeded column sample when
+the array exceeds the 64 MB budget).  The inputs depend on the arguments alone, so two builds can
+be compared output for output.
 """
 import argparse
 import hashlib
@@ -101,7 +106,49 @@ def parse():
     ap.add_argument("--full-json", default="",
                     help="also write the JSON line, indented, to this file (tools/profile_bench.sh: profiles/rNN_bench_full.json)")
     ap.add_argument("--no-clock-probe", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy: the "
+                         "timeseries and, with --by-particle, a fixed seeded column sample of the by-particle array "
+                         f"({DUMP_BYTES // 10**6} MB at most in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64 * 10**6
+DUMP_SEED = 20250825
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: 1-d or 2-d array} as dirname/<name>.npy in float64 within DUMP_BYTES in all.  A 2-d array
+    (frames x particles) that does not fit is written as a fixed seeded sample of its columns (sorted, the same
+    for every run of the same shape), and, should one column still be too long, of its rows.  Device tensors are
+    sampled on the device: only what is written crosses to the host."""
+    import numpy as np
+
+    def take(a, idx, axis):
+        if hasattr(a, "cpu"):  # torch tensor
+            import torch
+
+            return a.index_select(axis, torch.as_tensor(idx, device=a.device))
+        return np.take(a, idx, axis=axis)
+
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_BYTES // 8 - 1024 * len(arrays)  # elements, less room for the .npy headers
+    for name, a in arrays.items():
+        rng = np.random.default_rng(DUMP_SEED)  # per array: its sample depends on its shape alone
+        rows = a.shape[0]
+        size = int(np.prod(a.shape))
+        if len(a.shape) == 2 and size > budget:
+            cols = max(1, min(a.shape[1], budget // rows))
+            a = take(a, np.sort(rng.choice(a.shape[1], cols, replace=False)), 1)
+            size = rows * cols
+        if size > budget:
+            a = take(a, np.sort(rng.choice(rows, max(1, budget * rows // size), replace=False)), 0)
+        a = np.ascontiguousarray((a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)).astype(np.float64))
+        budget -= a.size
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 # Ceiling of this transform structure under the package power limit (DESIGN.md section 6,
@@ -200,6 +247,8 @@ def single_process(args):
     for _ in range(args.steps):
         ts, _ = fn(by_particle=False)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"timeseries": ts})
     members = member_rooflines(g, T, D, args.steps)
     slowest = min(members, key=lambda m: m["GBps"])
     # what the call adds to the slowest member's kernels: the reduce, the (n_frames,) copy to the host, the waits
@@ -723,6 +772,8 @@ def cpu_rehearsal(args, world, rank):
     if grouped:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"timeseries": result["ts"]})
     per_rank = [{"rank": rank, "atoms": A, "atom_range": [lo, hi]}]
     collective = None
     if grouped:
@@ -856,6 +907,11 @@ def main():
             result["ts"] = reduce_lagsum(case.lagsum, a_total)
 
     elapsed = timed(torch, dist, world if grouped else 1, args.steps, args.warmup, step)
+    if args.dump_outputs and rank == 0:  # before anything below runs the path again
+        outs = {"timeseries": result["ts"]}
+        if case.bp is not None:  # this rank's particles
+            outs["visc_by_particle" if args.mode == "helfand" else "vacf_by_particle"] = case.bp
+        dump_outputs(args.dump_outputs, outs)
     reduce_us = None
     if red_events:
         torch.cuda.synchronize()

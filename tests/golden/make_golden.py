@@ -159,6 +159,24 @@ def _docstring_vector(path, after, n):
     return vals
 
 
+def digest(path):
+    """SHA-256 of a stored array's content: the .npy file's bytes; for an .npz (whose zip container
+    need not be byte-stable) every member's name, dtype, shape and data, in name order."""
+    import hashlib
+
+    h = hashlib.sha256()
+    if path.endswith(".npz"):
+        with np.load(path) as z:
+            for k in sorted(z.files):
+                a = np.ascontiguousarray(z[k])
+                h.update(f"{k}|{a.dtype.str}|{a.shape}|".encode())
+                h.update(a.tobytes())
+    else:
+        with open(path, "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
 def main():
     manifest = {}
     ref_tests = os.path.join(REF, "transport_analysis", "tests")
@@ -277,6 +295,9 @@ def main():
         json.dump(constants, fh, indent=1)
     with open(os.path.join(OUT, "manifest.json"), "w") as fh:
         json.dump(manifest, fh, indent=1, sort_keys=True)
+    # the arrays' digests: tests/test_oracle.py pins the committed fixtures with them (no reference needed)
+    with open(os.path.join(OUT, "sha256.json"), "w") as fh:
+        json.dump({n: digest(os.path.join(OUT, n)) for n in manifest}, fh, indent=1, sort_keys=True)
     print("wrote", len(manifest), "arrays")
 
 
