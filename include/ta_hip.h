@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -180,6 +180,14 @@ int ta_vacf_fft(ta_ctx *ctx, double *h_timeseries, double *h_by_particle);
 int ta_vacf_direct(ta_ctx *ctx, double *h_timeseries, double *h_by_particle);
 int ta_helfand_msd(ta_ctx *ctx, const double *h_masses, double scale, double *h_timeseries,
                    double *h_by_particle);
+/* ta_msd          : MDAnalysis.analysis.msd.EinsteinMSD (_conclude_fft / _conclude_simple) on slab 0 = the
+ *                   positions of the msd_type's columns: by_particle[k, n] = mean over t < n_frames - k of
+ *                   sum_d (x[t+k,n,d] - x[t,n,d])^2, row 0 exactly 0; no masses, no division by dim.  fft = 1: up to 64
+ *                   frames the exact register-resident kernel, beyond that S1 - 2 S2 on x - x[t=0] (n_frames <=
+ *                   163840, else the direct form); fft = 0: the direct squared-difference forms.  fft other than 0 / 1:
+ *                   TA_E_INVALID.  CPU backend: fft = 1 by zero-padded transforms of x - x[t=0], fft = 0 directly.
+ *                   Float32 device slabs ("stage_device_f32") are widened to float64 first; "direct_f32" is ignored. */
+int ta_msd(ta_ctx *ctx, int fft, double *h_timeseries, double *h_by_particle);
 
 /* ---- compute on caller-provided device memory (asynchronous) -----------
  * Same arithmetic as above on a device-resident FRAME-MAJOR shard: d_vel / d_pos are
@@ -199,6 +207,8 @@ int ta_helfand_msd_dev(ta_ctx *ctx, const double *d_vel, const double *d_pos,
                        const double *d_masses, int64_t n_frames, int64_t n_atoms, int dim,
                        int64_t ld_row, double scale, double *d_lagsum,
                        double *d_by_particle, int64_t ld_bp, void *stream);
+int ta_msd_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row,
+               int fft, double *d_lagsum, double *d_by_particle, int64_t ld_bp, void *stream);
 
 /* ---- compute on the staged (pair-major) slabs, device outputs, asynchronous on `stream` ----
  * Same arithmetic and outputs as the *_dev calls, on the slabs of ta_stage_alloc*: no
@@ -209,6 +219,7 @@ int ta_vacf_direct_staged(ta_ctx *ctx, double *d_lagsum, double *d_by_particle, 
                           void *stream);
 int ta_helfand_msd_staged(ta_ctx *ctx, const double *d_masses, double scale, double *d_lagsum,
                           double *d_by_particle, int64_t ld_bp, void *stream);
+int ta_msd_staged(ta_ctx *ctx, int fft, double *d_lagsum, double *d_by_particle, int64_t ld_bp, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns
@@ -234,7 +245,7 @@ int ta_helfand_msd_staged(ta_ctx *ctx, const double *d_masses, double scale, dou
  *                      one-GPU box can execute;  "force_rccl" 1 = "reduce_mode" 2.
  * h_slabs of ta_group_stage_alloc: n_dev * n_slabs pointers, member i's slab s at [i * n_slabs + s]
  * (NULL for a member without atoms: more devices than atoms), each (n_frames, hi_i - lo_i, dim).
- * h_masses of ta_group_helfand_msd: all n_atoms.  Options go to every member.                */
+ * h_masses of ta_group_helfand_msd: all n_atoms.  ta_group_msd: ta_msd on every member's slab 0.  Options go to every member.                */
 typedef struct ta_group ta_group;
 int ta_group_create(const int *device_ids, int n_dev, ta_group **out);
 int ta_group_destroy(ta_group *g);
@@ -260,6 +271,7 @@ int ta_group_vacf_fft(ta_group *g, double *h_timeseries, double *h_by_particle);
 int ta_group_vacf_direct(ta_group *g, double *h_timeseries, double *h_by_particle);
 int ta_group_helfand_msd(ta_group *g, const double *h_masses, double scale, double *h_timeseries,
                          double *h_by_particle);
+int ta_group_msd(ta_group *g, int fft, double *h_timeseries, double *h_by_particle);
 
 /* ---- instrumentation ----------------------------------------------------
  * Device time of the last *_dev / host-facing compute call on this context,
@@ -338,7 +350,7 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      cap the atoms a workgroup works on at once (0 = automatic);
  *   "mid_max" n      : trajectories of 97 ... n frames (default and maximum 512; 0 = never) take k_mid (mid_kernels.hpp: a
  *                      lane per column and pair of 16-lag blocks, a sliding window in registers) for the windowed VACF, and
- *                      for the Einstein-Helfand sums up to 128 frames, under "direct_mfma" 1 and float64 arithmetic;
+ *                      for the Einstein-Helfand sums up to 128 frames (the Einstein MSD: 65 ... 512 frames), under "direct_mfma" 1 and float64 arithmetic;
  *                      "mid_all" 1: wherever the kernel can run (65 ... 512 frames, both quantities); "mid_ncl" 3..6:
  *                      log2 of the lanes per pair of lag blocks, i.e. the columns per tile (tools/mid_shapes.py; 0: by length);
  *   "direct_subwave" 1|0 : the vector kernel's column groups may be 8, 16 or 32 lanes where a column has that few

@@ -182,3 +182,39 @@ def stage_frame_native(ctx, slab, frame, ts, attr, cols, rows):
         return False
     ctx.stage_frame(slab, frame, src, cols, rows[0])
     return True
+
+
+def pop_device_options(kwargs):
+    """The placement keywords every analysis class takes, popped from its **kwargs:
+    ``distributed`` (one process per GPU under torch.distributed), ``devices=[...]`` (several GPUs
+    behind one object, exclusive with ``distributed``) and ``device`` (a GPU index or "cpu"; default
+    the first of ``devices``, else this rank's device when distributed, else ``$TA_AMD_DEVICE`` or 0).
+    Returns (distributed, devices or None, device index)."""
+    import os
+
+    from . import _lib
+
+    distributed = bool(kwargs.pop("distributed", False))
+    devices = kwargs.pop("devices", None)
+    devices = None if devices is None else [int(d) for d in devices]
+    if devices is not None and distributed:
+        raise ValueError("devices=[...] (one process, several GPUs) and distributed=True "
+                         "(one process per GPU) are exclusive")
+    device = kwargs.pop("device", None)
+    if device is None and devices:
+        device = devices[0]
+    if device is None:
+        if distributed:  # one process per GPU: this rank's own device
+            from .dist import default_device
+
+            device = default_device()
+        else:
+            device = os.environ.get("TA_AMD_DEVICE", 0)
+    return distributed, devices, _lib.device_index(device)
+
+
+def open_context(devices, device):
+    """The library handle of an analysis object: a ta_group for devices=[...], else one context."""
+    from . import _lib
+
+    return _lib.Group(devices) if devices is not None else _lib.Context(device)

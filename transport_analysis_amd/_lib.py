@@ -32,6 +32,7 @@ EXPORTS = (
     "ta_group_shard", "ta_group_reduce_kind", "ta_group_reduce_note", "ta_group_rccl_ranks", "ta_group_set_option", "ta_group_stage_alloc",
     "ta_group_stage_commit", "ta_group_stage_frame", "ta_group_stage_free", "ta_group_stage_alloc_device", "ta_group_stage_synth", "ta_group_vacf_fft", "ta_group_vacf_direct",
     "ta_group_helfand_msd",
+    "ta_msd", "ta_msd_dev", "ta_msd_staged", "ta_group_msd",
 )
 
 
@@ -150,6 +151,10 @@ def lib():
     L.ta_group_vacf_fft.argtypes = [vp, vp, vp]
     L.ta_group_vacf_direct.argtypes = [vp, vp, vp]
     L.ta_group_helfand_msd.argtypes = [vp, vp, dbl, vp, vp]
+    L.ta_msd.argtypes = [vp, ci, vp, vp]
+    L.ta_msd_dev.argtypes = [vp, vp, i64, i64, ci, i64, ci, vp, vp, i64, vp]
+    L.ta_msd_staged.argtypes = [vp, ci, vp, vp, i64, vp]
+    L.ta_group_msd.argtypes = [vp, ci, vp, vp]
     for name in EXPORTS:
         if name not in ("ta_last_error", "ta_group_last_error", "ta_group_reduce_kind", "ta_group_reduce_note"):
             getattr(L, name).restype = ci
@@ -445,6 +450,10 @@ class Context:
         m = np.ascontiguousarray(masses, dtype=np.float64)
         return self._host(lib().ta_helfand_msd, by_particle, _ptr(m), ctypes.c_double(scale), out=out)
 
+    def msd(self, fft, by_particle=False, out=None):
+        """Einstein MSD of slab 0 (the positions): (timeseries, by_particle or None)."""
+        return self._host(lib().ta_msd, by_particle, int(fft), out=out)
+
     # -- device-pointer compute (asynchronous) --------------------------
     def vacf_fft_dev(self, d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._check(lib().ta_vacf_fft_dev(self._h, d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum,
@@ -460,6 +469,10 @@ class Context:
                                              ld_row, scale, d_lagsum, d_bp or None, ld_bp,
                                              stream or None))
 
+    def msd_dev(self, d_pos, n_frames, n_atoms, dim, ld_row, fft, d_lagsum, d_bp=0, ld_bp=0, stream=0):
+        self._check(lib().ta_msd_dev(self._h, d_pos, n_frames, n_atoms, dim, ld_row, int(fft), d_lagsum,
+                                     d_bp or None, ld_bp, stream or None))
+
     # -- compute on the staged slabs, device outputs (asynchronous) ------
     def vacf_fft_staged(self, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._check(lib().ta_vacf_fft_staged(self._h, d_lagsum, d_bp or None, ld_bp, stream or None))
@@ -470,6 +483,9 @@ class Context:
     def helfand_msd_staged(self, d_masses, scale, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._check(lib().ta_helfand_msd_staged(self._h, d_masses, scale, d_lagsum, d_bp or None, ld_bp,
                                                 stream or None))
+
+    def msd_staged(self, fft, d_lagsum, d_bp=0, ld_bp=0, stream=0):
+        self._check(lib().ta_msd_staged(self._h, int(fft), d_lagsum, d_bp or None, ld_bp, stream or None))
 
     def timing_history(self, max_n=64):
         """[(total_ms, main_kernel_ms)] of the last compute calls, oldest first."""
@@ -663,3 +679,5 @@ class Group:
         m = np.ascontiguousarray(masses, dtype=np.float64)
         return self._host(lib().ta_group_helfand_msd, by_particle, _ptr(m), ctypes.c_double(scale), out=out)
 
+    def msd(self, fft, by_particle=False, out=None):
+        return self._host(lib().ta_group_msd, by_particle, int(fft), out=out)

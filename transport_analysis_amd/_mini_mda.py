@@ -6,7 +6,7 @@ build in-memory trajectories with ``mda.Universe.empty(..., velocities=True)``
 (/root/reference/transport_analysis/tests/test_velocityautocorr.py:46-57).  It
 provides exactly what the hooks touch: ``atomgroup.universe.trajectory``,
 ``len(atomgroup)``, ``.velocities`` / ``.positions`` (fresh float32 copies),
-``.masses``, and per-frame ``ts.has_velocities``, ``ts.has_positions``,
+``.masses``, ``select_atoms("all" | "index i:j" | "index i")``, and per-frame ``ts.has_velocities``, ``ts.has_positions``,
 ``ts.volume``, ``ts.frame``, ``ts.time``.
 """
 from __future__ import annotations
@@ -122,6 +122,24 @@ class AtomGroup:
     def masses(self):
         return np.array(self.universe._masses[self.indices], dtype=np.float64)
 
+    def select_atoms(self, selection):
+        """The atoms of this group that `selection` names: "all", or "index i:j" (inclusive, as in
+        MDAnalysis) / "index i" on the universe's atom indices -- the subset of MDAnalysis' selection
+        language the in-memory stand-in understands."""
+        words = selection.split()
+        if words == ["all"]:
+            return AtomGroup(self.universe, self.indices)
+        if len(words) == 2 and words[0] == "index":
+            lo, _, hi = words[1].partition(":")
+            try:
+                lo = int(lo)
+                hi = int(hi) if hi else lo
+            except ValueError:
+                raise ValueError(f"unsupported selection: {selection!r}") from None
+            keep = (self.indices >= lo) & (self.indices <= hi)
+            return AtomGroup(self.universe, self.indices[keep])
+        raise ValueError(f"unsupported selection: {selection!r} (the stand-in knows 'all' and 'index i:j')")
+
 
 class ArrayUniverse:
     """``positions`` / ``velocities``: (n_frames, n_atoms, 3) arrays or None."""
@@ -145,3 +163,10 @@ class ArrayUniverse:
                         else np.asarray(masses, dtype=np.float64))
         self.trajectory = MemoryTrajectory(positions, velocities, dimensions, dt)
         self.atoms = AtomGroup(self, np.arange(self._n_atoms))
+
+    @property
+    def universe(self):
+        return self
+
+    def select_atoms(self, selection):
+        return self.atoms.select_atoms(selection)

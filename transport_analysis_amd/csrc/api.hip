@@ -259,15 +259,17 @@ int mid_impl(ta_ctx* ctx, int mode, const double* d_vel, const double* d_pos, co
 int direct_impl(ta_ctx* ctx, int mode, const void* d_vel, const void* d_pos,
                 const double* d_masses, int64_t T, int64_t A, int D, int64_t pitch, double scale,
                 double* d_lagsum, double* d_bp, int64_t ld_bp, hipStream_t st, bool src_f32 = false) {
-    const bool f32 = ctx->opt_direct_f32 != 0;  // src_f32 only comes with it (compute_pm)
+    const bool f32 = ctx->opt_direct_f32 != 0 && mode != MODE_MSD;  // src_f32 only comes with it (compute_pm); MSD: float64
     if (!f32 && !src_f32 && ctx->opt_direct_mfma == 1 && short_applies(ctx, T))  // ("direct_mfma" 0 / 3 force a form)
         return short_impl(ctx, mode, (const double*)d_vel, (const double*)d_pos, d_masses, T, A, D, pitch, scale, d_lagsum, d_bp,
                           ld_bp, st);
     // k_mid where it wins (profiles/r06_direct_mid_sweep.txt): the windowed VACF from 97 to 512 frames (9.4 against 16.5 ms per
     // 12 GB at 128 frames with the by-particle array, 21.9 against 25.8 at 512), Helfand from 97 to 128 (18 against 23);
-    // "mid_max" 0: never; "mid_all" 1: wherever the kernel can run (65 ... 512 frames, both quantities: the parity tests)
+    // "mid_max" 0: never; "mid_all" 1: wherever the kernel can run (65 ... 512 frames, both quantities: the parity tests).
+    // The Einstein MSD (no product stage) from 65 to 512 frames: 14 - 38 ms against the vector kernel's 21 - 44 per 12 GB
+    // with the by-particle array, within 8 % where it loses (160 frames; tools/sweep_msd.py)
     if (!f32 && !src_f32 && ctx->opt_direct_mfma == 1 && T > 64 && T <= ctx->opt_mid_max && T <= mid_max_frames() &&
-        (ctx->opt_mid_all || (T >= 97 && (mode == MODE_VACF || T <= 128))))
+        (ctx->opt_mid_all || mode == MODE_MSD || (T >= 97 && (mode == MODE_VACF || T <= 128))))
         return mid_impl(ctx, mode, (const double*)d_vel, (const double*)d_pos, d_masses, T, A, D, pitch, scale, d_lagsum, d_bp, ld_bp,
                         st);
     // The O(T^2) correlators run on the matrix cores wherever that wins: FP64 (bandbp_kernels.hpp) and, for the float32
@@ -632,7 +634,53 @@ int helfand_impl(ta_ctx* ctx, const double* pm_vel, const double* pm_pos, const 
                        ld_bp, st);
 }
 
-enum { W_FFT = 0, W_DIRECT = 1, W_HELFAND = 2 };
+// Einstein MSD (MDAnalysis.analysis.msd.EinsteinMSD) on the position slab alone.  fft: up to short_max frames k_short
+// (exact, and faster there, as for the VACF); beyond, S1 - 2 S2 on P = x - x[t=0] (msd.hip, helfand_fft.hip's combine
+// kernels with factor 1) wherever wfft_choose has a plan.  !fft, and fft beyond the largest plan: the direct forms under
+// direct_impl's thresholds (k_short up to 64 frames, k_mid 65 ... 512: re-measured for MSD, k_direct beyond).
+int msd_impl(ta_ctx* ctx, bool fft, const double* pm_pos, int64_t pitch, int64_t T, int64_t A, int D, double* d_lagsum,
+             double* d_bp, int64_t ld_bp, hipStream_t st) {
+    int rc;
+    int r0 = 0, ro = 0;
+    const bool fft_form = fft && T >= 2 && !(ctx->opt_direct_mfma == 1 && short_applies(ctx, T)) &&
+                          wfft_choose((long)T, &r0, &ro);
+    if (!fft_form)
+        return direct_impl(ctx, MODE_MSD, pm_pos, nullptr, nullptr, T, A, D, pitch, 1.0, d_lagsum, d_bp, ld_bp, st);
+    const int64_t n_cols = A * D, n_pairs = (n_cols + 1) / 2;
+    if ((rc = ensure(ctx, ctx->helf_p, pm_bytes(T, n_cols)))) return rc;
+    double* P = (double*)ctx->helf_p.p;
+    if (!d_bp) {
+        const int n_parts = (int)std::min<int64_t>(1024, n_pairs);
+        if ((rc = ensure(ctx, ctx->helf_small, sizeof(double) * ((size_t)n_parts * T + 3 * (size_t)T + 1)))) return rc;
+        double* Qpart = (double*)ctx->helf_small.p;
+        double* Q = Qpart + (size_t)n_parts * T;
+        double* S2 = Q + T;
+        double* C = S2 + T;
+        tl_mark(ctx, "k_msd_prepare", st);
+        TA_HIP_TRY(ctx, launch_msd_prepare(pm_pos, pitch, T, n_cols, P, Qpart, n_parts, st));
+        tl_mark(ctx, "k_sum_partials", st);
+        TA_HIP_TRY(ctx, launch_sum_partials(Qpart, n_parts, T, Q, st));
+        if ((rc = fft_impl(ctx, P, pitch, T, A, D, S2, nullptr, 0, st))) return rc;
+        tl_mark(ctx, "k_helfand_combine", st);
+        TA_HIP_TRY(ctx, launch_helfand_combine(Q, S2, C, (int)T, 1.0, d_lagsum, st));
+        return TA_OK;
+    }
+    if ((rc = ensure(ctx, ctx->helf_small, sizeof(double) * ((size_t)T + 1) * A))) return rc;
+    double* Ca = (double*)ctx->helf_small.p;
+    if (n_cols & 1)  // the unpaired last column's partner is never written by the prepare kernel
+        TA_HIP_TRY(ctx, hipMemsetAsync(P + (size_t)(n_pairs - 1) * pitch * 2, 0, (size_t)pitch * 16, st));
+    tl_mark(ctx, "k_msd_prepare", st);
+    TA_HIP_TRY(ctx, launch_msd_prepare_bp(pm_pos, pitch, T, A, D, P, Ca, st));
+    if ((rc = fft_impl(ctx, P, pitch, T, A, D, d_lagsum, d_bp, ld_bp, st))) return rc;
+    tl_mark(ctx, "k_helfand_combine", st);
+    TA_HIP_TRY(ctx, launch_helfand_combine_bp(Ca, A, (int)T, 1.0, d_bp, ld_bp, st));
+    tl_mark(ctx, "k_row_sums", st);
+    TA_HIP_TRY(ctx, launch_row_sums(d_bp, T, A, ld_bp, d_lagsum, st));
+    return TA_OK;
+}
+
+enum { W_FFT = 0, W_DIRECT = 1, W_HELFAND = 2, W_MSD_FFT = 3, W_MSD_DIRECT = 4 };
+inline bool is_msd(int which) { return which == W_MSD_FFT || which == W_MSD_DIRECT; }
 
 // one compute call on pair-major slabs, bracketed by the timing events
 int compute_pm(ta_ctx* ctx, int which, const void* pm_vel_any, const void* pm_pos_any, const double* d_masses,
@@ -672,6 +720,8 @@ int compute_pm(ta_ctx* ctx, int which, const void* pm_vel_any, const void* pm_po
     else if (which == W_DIRECT)
         rc = direct_impl(ctx, MODE_VACF, pm_vel_any, nullptr, nullptr, T, A, D, pitch, 1.0, d_lagsum, d_bp, ld_bp, st,
                          direct_on_f32);
+    else if (is_msd(which))
+        rc = msd_impl(ctx, which == W_MSD_FFT, pm_vel, pitch, T, A, D, d_lagsum, d_bp, ld_bp, st);
     else if (direct_on_f32)
         rc = direct_impl(ctx, MODE_HELFAND, pm_vel_any, pm_pos_any, d_masses, T, A, D, pitch, scale, d_lagsum, d_bp,
                          ld_bp, st, true);
@@ -1387,6 +1437,30 @@ int ta_helfand_msd_staged(ta_ctx* ctx, const double* d_masses, double scale, dou
     });
 }
 
+// Einstein MSD: slab 0 / d_pos holds the positions (the vel argument of the shared paths)
+static int msd_which(ta_ctx* ctx, int fft, int* which) {
+    if (fft != 0 && fft != 1) return fail(ctx, TA_E_INVALID, "fft must be 0 or 1");
+    *which = fft ? W_MSD_FFT : W_MSD_DIRECT;
+    return TA_OK;
+}
+
+int ta_msd_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int fft, double* d_lagsum,
+               double* d_bp, int64_t ld_bp, void* stream) {
+    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    int which = 0;
+    if (int rc = msd_which(ctx, fft, &which)) return rc;
+    return dev_entry(ctx, which, d_pos, nullptr, nullptr, T, A, D, ld_row, 1.0, d_lagsum, d_bp, ld_bp, stream);
+    });
+}
+
+int ta_msd_staged(ta_ctx* ctx, int fft, double* d_lagsum, double* d_bp, int64_t ld_bp, void* stream) {
+    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    int which = 0;
+    if (int rc = msd_which(ctx, fft, &which)) return rc;
+    return staged_entry(ctx, which, nullptr, 1.0, d_lagsum, d_bp, ld_bp, stream);
+    });
+}
+
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
     if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
@@ -1615,6 +1689,7 @@ static int host_compute(ta_ctx* ctx, int which, const double* h_masses, double s
         if (which == W_HELFAND && !h_masses) return fail(ctx, TA_E_INVALID, "h_masses is NULL");
         const int rc = which == W_FFT      ? ta::cpu::vacf_fft(ctx->cpu, h_ts, h_bp)
                        : which == W_DIRECT ? ta::cpu::vacf_direct(ctx->cpu, h_ts, h_bp)
+                       : is_msd(which)     ? ta::cpu::msd(ctx->cpu, which == W_MSD_FFT, h_ts, h_bp)
                                            : ta::cpu::helfand(ctx->cpu, h_masses, scale, h_ts, h_bp);
         if (rc) return fail(ctx, rc, "CPU backend: out of host memory");
         const double n_at = (double)ctx->st_A;  // mean over atoms (velocityautocorr.py:214,237; viscosity.py:233)
@@ -1637,6 +1712,10 @@ int ta_vacf_fft(ta_ctx* ctx, double* h_ts, double* h_bp) { return host_compute(c
 int ta_vacf_direct(ta_ctx* ctx, double* h_ts, double* h_bp) { return host_compute(ctx, W_DIRECT, nullptr, 1.0, h_ts, h_bp); }
 int ta_helfand_msd(ta_ctx* ctx, const double* h_masses, double scale, double* h_ts, double* h_bp) {
     return host_compute(ctx, W_HELFAND, h_masses, scale, h_ts, h_bp);
+}
+int ta_msd(ta_ctx* ctx, int fft, double* h_ts, double* h_bp) {
+    if (fft != 0 && fft != 1) return fail(ctx, TA_E_INVALID, "fft must be 0 or 1");
+    return host_compute(ctx, fft ? W_MSD_FFT : W_MSD_DIRECT, nullptr, 1.0, h_ts, h_bp);
 }
 
 }  // extern "C"

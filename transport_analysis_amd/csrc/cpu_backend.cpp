@@ -15,6 +15,10 @@
 //   windowed VACF velocityautocorr.py:217-238: the same sums, lag by lag, products then sum (k = 0 .. T - 1);
 //   Helfand       viscosity.py:201-233: P = (m v) x, H[k, n] = scale / D / (T - k) sum_i sum_d (P[i] - P[i+k])^2,
 //                 difference first, like the reference; H[0, n] = 0.
+//   Einstein MSD  MDAnalysis.analysis.msd.EinsteinMSD: M[k, n] = 1 / (T - k) sum_i sum_d (x[i] - x[i+k])^2, M[0, n] = 0;
+//                 fft = false difference first (the Helfand loop without masses and 1 / D), fft = true by the transforms
+//                 of the FFT VACF on P = x - x[0] and S1 - 2 S2 (P's autocorrelation, prefix sums of sum_d P^2), as on
+//                 the GPU (msd.hip).
 // timeseries[k] = sum over atoms (the caller divides by n_atoms, as for the GPU path).  Atoms are processed in
 // blocks of 8 by OpenMP threads; a block's lag sums are added in block order afterwards, so results do not depend on
 // the number of threads.
@@ -148,11 +152,13 @@ inline double elem(const void* slab, size_t idx) {
 }
 
 struct Work {  // per-thread buffers
-    std::vector<double> a, b, c, d, pr[2], cols, prod, out;
+    std::vector<double> a, b, c, d, pr[2], cq[2], cols, prod, out;
 };
 
+// msd: the Einstein MSD of the slab instead of its autocorrelation (the columns shifted by their first frame, the
+// prefix sums cq[h][t] = sum_{i<t} sum_d P[i]^2 of the atom, and the S1 - 2 S2 combination per lag)
 template <class E>
-int vacf_fft_t(const State& s, double* ts, double* bp) {
+int vacf_fft_t(const State& s, double* ts, double* bp, bool msd = false) {
     const int64_t T = s.T, A = s.A;
     const int D = s.D;
     int L = 2;
@@ -167,6 +173,8 @@ int vacf_fft_t(const State& s, double* ts, double* bp) {
         Work w;
         try {
             for (auto* v : {&w.a, &w.b, &w.c, &w.d, &w.pr[0], &w.pr[1]}) v->assign((size_t)L, 0.0);
+            if (msd)
+                for (auto* v : {&w.cq[0], &w.cq[1]}) v->assign((size_t)T + 1, 0.0);
             w.out.assign((size_t)T * kBlock, 0.0);
         } catch (const std::bad_alloc&) {
 #pragma omp atomic write
@@ -186,6 +194,7 @@ int vacf_fft_t(const State& s, double* ts, double* bp) {
                         const int64_t atom = a0 + j + h;
                         double* P = w.pr[h].data();
                         std::memset(P, 0, sizeof(double) * L);
+                        if (msd) std::memset(w.cq[h].data(), 0, sizeof(double) * (T + 1));
                         for (int d0 = 0; d0 < D; d0 += 2) {
                             const bool two = d0 + 1 < D;
                             double *xr = w.a.data(), *xi = w.b.data();
@@ -194,11 +203,24 @@ int vacf_fft_t(const State& s, double* ts, double* bp) {
                                 xr[t] = elem<E>(slab, base);
                                 xi[t] = two ? elem<E>(slab, base + 1) : 0.0;
                             }
+                            if (msd) {
+                                const double x0 = xr[0], y0 = xi[0];
+                                double* q = w.cq[h].data() + 1;
+                                for (int64_t t = 0; t < T; ++t) {
+                                    xr[t] -= x0;
+                                    xi[t] -= y0;
+                                    q[t] += xr[t] * xr[t] + xi[t] * xi[t];
+                                }
+                            }
                             std::memset(xr + T, 0, sizeof(double) * (L - T));
                             std::memset(xi + T, 0, sizeof(double) * (L - T));
                             const Split z = fft(plan, xr, xi, w.c.data(), w.d.data());
 #pragma omp simd
                             for (int k = 0; k < L; ++k) P[k] += z.r[k] * z.r[k] + z.i[k] * z.i[k];
+                        }
+                        if (msd) {  // cq[h][t + 1] = Q[t] -> exclusive prefix sums C[0 .. T]
+                            double* C = w.cq[h].data();
+                            for (int64_t t = 1; t <= T; ++t) C[t] += C[t - 1];
                         }
                     }
                     // one transform of P_0 + i P_1 (both real: G[n] + conj G[L - n] = 2 F_0[n], the imaginary parts F_1)
@@ -210,9 +232,14 @@ int vacf_fft_t(const State& s, double* ts, double* bp) {
                     for (int64_t n = 0; n < T; ++n) {
                         const int64_t mir = n == 0 ? 0 : L - n;
                         const double norm = (double)L * (double)(T - n);  // < 2^53: exact
-                        const double f0 = 0.5 * (g.r[n] + g.r[mir]) / norm, f1 = 0.5 * (g.i[n] + g.i[mir]) / norm;
-                        w.out[(size_t)n * kBlock + j] = f0;
-                        if (n2 == 2) w.out[(size_t)n * kBlock + j + 1] = f1;
+                        double f[2] = {0.5 * (g.r[n] + g.r[mir]) / norm, 0.5 * (g.i[n] + g.i[mir]) / norm};
+                        if (msd)
+                            for (int h = 0; h < n2; ++h) {  // (C[T - n] + C[T] - C[n]) / (T - n) - 2 S2 / (T - n)
+                                const double* C = w.cq[h].data();
+                                f[h] = n == 0 ? 0.0 : (C[T - n] + (C[T] - C[n])) / (double)(T - n) - 2.0 * f[h];
+                            }
+                        w.out[(size_t)n * kBlock + j] = f[0];
+                        if (n2 == 2) w.out[(size_t)n * kBlock + j + 1] = f[1];
                     }
                 }
                 for (int64_t n = 0; n < T; ++n) {
@@ -234,9 +261,10 @@ int vacf_fft_t(const State& s, double* ts, double* bp) {
     return TA_OK;
 }
 
-// windowed VACF (helfand == false) and Einstein-Helfand (helfand == true) share the O(T^2) loop over lags
+// windowed VACF (helfand == false), Einstein-Helfand (helfand == true) and the Einstein MSD (msd == true: slab 0 = the
+// positions, differences as Helfand without masses and 1 / D) share the O(T^2) loop over lags
 template <class E>
-int direct_t(const State& s, bool helfand, const double* masses, double scale, double* ts, double* bp) {
+int direct_t(const State& s, bool helfand, const double* masses, double scale, double* ts, double* bp, bool msd = false) {
     const int64_t T = s.T, A = s.A;
     const int D = s.D;
     const int64_t n_blocks = (A + kBlock - 1) / kBlock;
@@ -270,11 +298,11 @@ int direct_t(const State& s, bool helfand, const double* masses, double scale, d
                         }
                     for (int64_t k = 0; k < T; ++k) {
                         double acc = 0.0;
-                        if (!(helfand && k == 0)) {
+                        if (!((helfand || msd) && k == 0)) {
                             for (int d = 0; d < D; ++d) {
                                 const double *p0 = c + (size_t)d * T, *p1 = p0 + k;
                                 double sd = 0.0;
-                                if (helfand) {
+                                if (helfand || msd) {
 #pragma omp simd reduction(+ : sd)
                                     for (int64_t i = 0; i < T - k; ++i) {
                                         const double df = p0[i] - p1[i];
@@ -352,6 +380,11 @@ int vacf_direct(const State& s, double* ts, double* bp) {
 }
 int helfand(const State& s, const double* masses, double scale, double* ts, double* bp) {
     return s.dtype == TA_F32 ? direct_t<float>(s, true, masses, scale, ts, bp) : direct_t<double>(s, true, masses, scale, ts, bp);
+}
+int msd(const State& s, bool fft, double* ts, double* bp) {
+    if (fft) return s.dtype == TA_F32 ? vacf_fft_t<float>(s, ts, bp, true) : vacf_fft_t<double>(s, ts, bp, true);
+    return s.dtype == TA_F32 ? direct_t<float>(s, false, nullptr, 1.0, ts, bp, true)
+                             : direct_t<double>(s, false, nullptr, 1.0, ts, bp, true);
 }
 
 }  // namespace cpu

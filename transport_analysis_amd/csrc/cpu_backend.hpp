@@ -20,6 +20,8 @@ void synth(const State& s, int slab, unsigned long long seed, int64_t col_offset
 int vacf_fft(const State& s, double* timeseries, double* by_particle);
 int vacf_direct(const State& s, double* timeseries, double* by_particle);
 int helfand(const State& s, const double* masses, double scale, double* timeseries, double* by_particle);
+// Einstein MSD of slab 0 (the positions): fft = true by transforms of x - x[0] (S1 - 2 S2), false difference first
+int msd(const State& s, bool fft, double* timeseries, double* by_particle);
 
 }  // namespace cpu
 }  // namespace ta

@@ -48,12 +48,17 @@ static const void* direct_kernel(int mode, bool f32, int L, bool gs, bool src_f3
     if (src_f32) return gs ? TA_K(M, LL, true, float, float) : TA_K(M, LL, false, float, float);      \
     if (f32) return gs ? TA_K(M, LL, true, float, double) : TA_K(M, LL, false, float, double);        \
     return gs ? TA_K(M, LL, true, double, double) : TA_K(M, LL, false, double, double);
-#define TA_X(LL)                                  \
-    if (L == LL) {                                \
-        if (mode == MODE_VACF) {                  \
-            TA_PICK(MODE_VACF, LL)                \
-        }                                         \
-        TA_PICK(MODE_HELFAND, LL)                 \
+// (MODE_MSD: float64 slabs and arithmetic only)
+#define TA_X(LL)                                                                         \
+    if (L == LL) {                                                                       \
+        if (mode == MODE_VACF) {                                                         \
+            TA_PICK(MODE_VACF, LL)                                                       \
+        }                                                                                \
+        if (mode == MODE_MSD) {                                                          \
+            if (f32 || src_f32) return nullptr;                                          \
+            return gs ? TA_K(MODE_MSD, LL, true, double, double) : TA_K(MODE_MSD, LL, false, double, double); \
+        }                                                                                \
+        TA_PICK(MODE_HELFAND, LL)                                                        \
     }
     TA_DIRECT_CHUNKS(TA_X)
 #undef TA_X

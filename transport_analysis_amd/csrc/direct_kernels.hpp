@@ -8,6 +8,9 @@
 //                P = (m*v)*x ; H[k,n] = scale/(D (T-k)) sum_i sum_d (P[i]-P[i+k])^2,
 //                k = 1..T-1, H[0,n] = 0.  The difference is formed first, exactly as
 //                the reference does (no prefix-sum expansion: SURVEY.md 7.3-5).
+// MODE_MSD     : MDAnalysis.analysis.msd.EinsteinMSD (the direct form of its fft=False loop)
+//                M[k,n] = 1/(T-k) sum_i sum_d (x[i]-x[i+k])^2 on the position slab alone
+//                (`vel` carries the positions; no masses, no division by D), M[0,n] = 0.
 //
 // One workgroup takes one atom at a time.  For each of its D columns the whole
 // time series (T float64, P formed on the fly for Helfand) is staged in LDS; a
@@ -25,7 +28,10 @@
 
 namespace ta {
 
-enum { MODE_VACF = 0, MODE_HELFAND = 1 };
+enum { MODE_VACF = 0, MODE_HELFAND = 1, MODE_MSD = 2 };
+
+// the squared-difference quantities (Helfand, MSD) against the products of the VACF
+constexpr bool mode_diff(int mode) { return mode != MODE_VACF; }
 
 // Staged column layout: groups of L values padded to a stride of 4 (mod 8) dwords: groups
 // stay 16-byte aligned for ds_read_b128 and the 16 lanes a b128 read services together
@@ -122,7 +128,7 @@ __device__ __forceinline__ void chunk_accumulate(const double* __restrict__ s, i
         ++blk;
     }
 #undef TA_TILE_F64
-    if (MODE == MODE_HELFAND) {
+    if (mode_diff(MODE)) {
         // ragged end of the chunk (at most two blocks): a pair (i+b, i+b+k) only counts
         // while i+b+k < T.  Straight from the staged column, rolled over b: small code.
         for (; blk < nblk; ++blk) {
@@ -226,7 +232,7 @@ __device__ __forceinline__ void chunk_accumulate(const float* __restrict__ s, in
         ++blk;
     }
     flush();
-    if (MODE == MODE_HELFAND) {
+    if (mode_diff(MODE)) {
         for (; blk < nblk; ++blk) {  // ragged end, as in the float64 version
             const int i = blk * L;
 #pragma unroll 1
@@ -315,6 +321,7 @@ __global__ void __launch_bounds__(1024)
                         if (k < T) {
                             double val = (h ? acc2[a] : acc1[a]) / (double)(T - k);
                             if (MODE == MODE_HELFAND) val = (k == 0) ? 0.0 : (val / (double)D) * scale;
+                            if (MODE == MODE_MSD && k == 0) val = 0.0;
                             // atom-major scratch (ld_bp = row pitch >= T), transposed afterwards
                             if (by_particle) by_particle[(long)atom * ld_bp + k] = val;
                             ts_out[k] += val;

@@ -554,5 +554,9 @@ int ta_group_helfand_msd(ta_group* g, const double* h_masses, double scale, doub
     return group_compute(g, 2, h_masses, scale, h_ts, h_bp);
     });
 }
+int ta_group_msd(ta_group* g, int fft, double* h_ts, double* h_bp) {
+    if (fft != 0 && fft != 1) return gfail(g, TA_E_INVALID, "fft must be 0 or 1");
+    return group_compute(g, fft ? 3 : 4, nullptr, 1.0, h_ts, h_bp);
+}
 
 }  // extern "C"

@@ -23,6 +23,7 @@ MidShape mid_shape(int T, int D, int ncl_log2) {
 }
 
 static const void* mid_kernel(int mode) {
+    if (mode == MODE_MSD) return reinterpret_cast<const void*>(k_mid<MODE_MSD>);
     return mode == MODE_VACF ? reinterpret_cast<const void*>(k_mid<MODE_VACF>) : reinterpret_cast<const void*>(k_mid<MODE_HELFAND>);
 }
 

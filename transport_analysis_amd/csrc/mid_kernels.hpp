@@ -9,7 +9,8 @@
 //
 // A workgroup stages a tile of NC adjacent columns (a multiple of dim: whole particles) from the pair-major slab into the
 // LDS (xs[column][TS], zero padded to the next multiple of 16 plus 16: out-of-range products of the windowed VACF vanish;
-// Helfand forms P = (m v) x on the way in and masks its out-of-range terms in a block's last groups), lanes = (column,
+// Helfand forms P = (m v) x on the way in and masks its out-of-range terms in a block's last groups; MODE_MSD stages the
+// position slab as it is and masks like Helfand), lanes = (column,
 // pair of blocks); then the accumulators go back through the LDS: by_particle[lag, atom] (the sum over the particle's dim
 // columns) is stored straight into the caller's (n_frames, ld) array, and thread k adds up lag k over the tile's columns in
 // a register that lives across the tiles: partial[workgroup][lag], added in a fixed order by k_sum_partials.
@@ -36,7 +37,7 @@ __device__ __forceinline__ void mid_group(const double (&xi)[kMidLB], const doub
 #pragma unroll
         for (int u = 0; u < LB; ++u) {
             const double wv = s + u < LB ? wa[s + u] : wb[s + u - LB];
-            if (MODE == MODE_HELFAND) {
+            if (mode_diff(MODE)) {
                 double df = xi[s] - wv;
                 if (MASKED) df = (s + u < nvalid) ? df : 0.0;
                 acc[u] = __builtin_fma(df, df, acc[u]);
@@ -83,7 +84,7 @@ __device__ __forceinline__ void mid_block(const double* __restrict__ xc, int T, 
             mid_group<MODE, M>(xi, w1, w0, acc, T - (i0 + LB + k0));
         }
     };
-    if (MODE == MODE_HELFAND) {
+    if (mode_diff(MODE)) {
         for (; i0 + 2 * LB <= n_full * LB; i0 += 2 * LB) pair(std::false_type{});
         for (; i0 < T - k0; i0 += 2 * LB) pair(std::true_type{});
     } else {
@@ -170,7 +171,7 @@ __global__ void __launch_bounds__(kMidThreads) __attribute__((amdgpu_waves_per_e
         for (int u = 0; u < LB; ++u) acc1[u] = acc2[u] = 0.0;
         const bool active = j < ncv && bpi < NP;
         int nf1 = 0, nf2 = 0;
-        if (MODE == MODE_HELFAND) {  // (outside the divergent part: the lane exchanges want every lane)
+        if (mode_diff(MODE)) {  // (outside the divergent part: the lane exchanges want every lane)
             nf1 = active ? mid_full_groups(T, b1 * LB) : 1 << 30;
             nf2 = active && b2 > b1 ? mid_full_groups(T, b2 * LB) : 1 << 30;
 #pragma unroll
@@ -202,7 +203,7 @@ __global__ void __launch_bounds__(kMidThreads) __attribute__((amdgpu_waves_per_e
                 const int k = (int)(((unsigned long long)idx * inv) >> 32), a = idx - k * na;
                 double v = 0.0;
                 for (int d = 0; d < D; ++d) v += xs[(a * D + d) * TS + k];
-                if (MODE == MODE_HELFAND && k == 0) v = 0.0;
+                if (mode_diff(MODE) && k == 0) v = 0.0;
                 bp[(long)k * ld_bp + atom0 + a] = v * rn[k];
             }
         }
@@ -235,7 +236,7 @@ __global__ void __launch_bounds__(kMidThreads) __attribute__((amdgpu_waves_per_e
         }
     }
     double* prow = partial + (long)blockIdx.x * T;
-    if (tid < T) prow[tid] = (MODE == MODE_HELFAND && tid == 0) ? 0.0 : tot0 * rn[tid];
+    if (tid < T) prow[tid] = (mode_diff(MODE) && tid == 0) ? 0.0 : tot0 * rn[tid];
     if (tid + nt < T) prow[tid + nt] = tot1 * rn[tid + nt];
 }
 

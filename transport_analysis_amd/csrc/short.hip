@@ -15,6 +15,7 @@ template <int TMAX, bool BP>
 ShortFn short_kernel(int mode, int D) {
 #define TA_K(M, DD) ShortFn{reinterpret_cast<const void*>(k_short<TMAX, M, DD, BP>), ShortCfg<TMAX, BP>::kLds}
     if (mode == MODE_VACF) return D == 1 ? TA_K(MODE_VACF, 1) : D == 2 ? TA_K(MODE_VACF, 2) : TA_K(MODE_VACF, 3);
+    if (mode == MODE_MSD) return D == 1 ? TA_K(MODE_MSD, 1) : D == 2 ? TA_K(MODE_MSD, 2) : TA_K(MODE_MSD, 3);
     return D == 1 ? TA_K(MODE_HELFAND, 1) : D == 2 ? TA_K(MODE_HELFAND, 2) : TA_K(MODE_HELFAND, 3);
 #undef TA_K
 }

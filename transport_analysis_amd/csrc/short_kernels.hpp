@@ -54,7 +54,9 @@ struct ShortCfg {
 template <int D>
 constexpr int short_cols_per_wave() { return D == 3 ? 63 : 64; }
 
-// partial: [gridDim.x * kShortWaves][T]; bp: (T, ld_bp) with BP; factor: 1 (VACF) or scale / D (Helfand)
+// partial: [gridDim.x * kShortWaves][T]; bp: (T, ld_bp) with BP; factor: 1 (VACF, MSD) or scale / D (Helfand).
+// MODE_MSD reads `vel` (the position slab) as the VACF does and forms differences as Helfand does: lag 0 is a sum of nothing
+// (i == j is skipped), i.e. exactly 0
 template <int TMAX, int MODE, int D, bool BP>
 __global__ void __launch_bounds__(64 * kShortWaves)
     __attribute__((amdgpu_waves_per_eu(ShortCfg<TMAX, BP>::WAVES_PER_SIMD, ShortCfg<TMAX, BP>::WAVES_PER_SIMD)))
@@ -122,7 +124,7 @@ __global__ void __launch_bounds__(64 * kShortWaves)
                         for (int i = 0; i <= j; ++i) {
                             const int k = j - i - k0;  // lag within the block
                             if (k < 0 || k >= LB) continue;
-                            if (MODE == MODE_HELFAND) {
+                            if (mode_diff(MODE)) {
                                 if (i == j) continue;
                                 const double df = x[i] - x[j];
                                 acc[k] = __builtin_fma(df, df, acc[k]);

@@ -45,7 +45,8 @@ int guard(Report&& report, Body&& body) noexcept {
 }
 
 // api.hip, for group.hip (several contexts driven by one host thread): one context's share of a
-// host-facing call queued on its streams (which: 0 FFT VACF, 1 windowed VACF, 2 Helfand), the sum
+// host-facing call queued on its streams (which: 0 FFT VACF, 1 windowed VACF, 2 Helfand, 3 / 4 Einstein MSD by the FFT /
+// direct form), the sum
 // over its atoms left on the device; host_wait blocks until that work and its copies are done
 int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, double* h_bp, int64_t ld_host,
                 double** d_total);
@@ -135,6 +136,14 @@ hipError_t launch_helfand_product_bp(const double* vel, const double* pos, const
                                      hipStream_t st);  // Ca: (T+1, n_atoms)
 hipError_t launch_helfand_combine_bp(double* Ca, long n_atoms, int T, double factor, double* bp,
                                      long ld_bp, hipStream_t st);
+
+// msd.hip: the FFT form of the Einstein MSD.  P = x - x[t=0] per column into a pair-major slab (the unpaired last column's
+// partner written as 0); Qpart [n_parts][T] written in full (lag sums) or Ca rows 1..T of (T+1, n_atoms) (by particle); the
+// helfand_combine kernels above finish with factor 1
+hipError_t launch_msd_prepare(const double* pos, long pitch, long T, long n_cols, double* P, double* Qpart, int n_parts,
+                              hipStream_t st);
+hipError_t launch_msd_prepare_bp(const double* pos, long pitch, long T, long n_atoms, int D, double* P, double* Ca,
+                                 hipStream_t st);
 
 hipError_t launch_widen_f32(const float* in, double* out, long n, hipStream_t st);
 

@@ -98,10 +98,10 @@ def uses_device_reduce():
 
 
 def staged_timeseries_on_device(ctx, which, n_frames, n_local, n_atoms_total, device, masses=None,
-                                scale=1.0, by_particle=False):
+                                scale=1.0, by_particle=False, fft=True):
     """This rank's staged block -> lag sums (device) -> ONE all-reduce over RCCL -> mean over
     ALL atoms.  The (n_frames,) float64 sums never leave the GPU before the reduce.
-    which: "fft" | "direct" | "helfand".  Returns (timeseries ndarray, by_particle ndarray|None)."""
+    which: "fft" | "direct" | "helfand" | "msd" (the Einstein MSD of the position slab, by the FFT form when `fft`).  Returns (timeseries ndarray, by_particle ndarray|None)."""
     import torch
 
     dev = torch.device("cuda", device)
@@ -115,6 +115,8 @@ def staged_timeseries_on_device(ctx, which, n_frames, n_local, n_atoms_total, de
                 ctx.vacf_fft_staged(lag.data_ptr(), d_bp, n_local, stream)
             elif which == "direct":
                 ctx.vacf_direct_staged(lag.data_ptr(), d_bp, n_local, stream)
+            elif which == "msd":
+                ctx.msd_staged(fft, lag.data_ptr(), d_bp, n_local, stream)
             else:
                 m = torch.as_tensor(np.ascontiguousarray(masses, dtype=np.float64), device=dev)
                 ctx.helfand_msd_staged(m.data_ptr(), float(scale), lag.data_ptr(), d_bp, n_local, stream)

@@ -9,13 +9,10 @@ CPU fallback.
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 
-from . import _lib
-from ._base import (stage_columns, AnalysisBase, NoDataError, UpdatingAtomGroup, native_rows, parse_dim_type,
-                    stage_frame_native)
+from ._base import (stage_columns, AnalysisBase, NoDataError, UpdatingAtomGroup, native_rows, open_context, parse_dim_type,
+                    pop_device_options, stage_frame_native)
 
 #: frames staged on the host before an asynchronous host->device copy is queued
 _COMMIT_BYTES = 32 << 20
@@ -84,25 +81,9 @@ class VelocityAutocorr(AnalysisBase):
 
     def __init__(self, atomgroup, dim_type="xyz", fft=True, **kwargs):
         self._want_by_particle = bool(kwargs.pop("by_particle", True))
-        self._distributed = bool(kwargs.pop("distributed", False))
         self._stage_dtype = kwargs.pop("stage_dtype", None)
         self._device_f32 = kwargs.pop("device_float32", None)
-        devices = kwargs.pop("devices", None)
-        self._devices = None if devices is None else [int(d) for d in devices]
-        if self._devices is not None and self._distributed:
-            raise ValueError("devices=[...] (one process, several GPUs) and distributed=True "
-                             "(one process per GPU) are exclusive")
-        device = kwargs.pop("device", None)
-        if device is None and self._devices:
-            device = self._devices[0]
-        if device is None:
-            if self._distributed:  # one process per GPU: this rank's own device
-                from .dist import default_device
-
-                device = default_device()
-            else:
-                device = os.environ.get("TA_AMD_DEVICE", 0)
-        self._device = _lib.device_index(device)
+        self._distributed, self._devices, self._device = pop_device_options(kwargs)
         super().__init__(atomgroup.universe.trajectory, **kwargs)
 
         if isinstance(atomgroup, UpdatingAtomGroup):
@@ -143,7 +124,7 @@ class VelocityAutocorr(AnalysisBase):
     def _prepare(self):
         """Pinned host slab + device slab instead of ``np.zeros`` (:142-153)."""
         if self._ctx is None:
-            self._ctx = _lib.Group(self._devices) if self._devices is not None else _lib.Context(self._device)
+            self._ctx = open_context(self._devices, self._device)
         self._lo, self._hi = 0, self.n_particles
         self._source = self.atomgroup  # whose velocities a frame is read from
         if self._distributed:

@@ -6,13 +6,10 @@ hand-written HIP kernel; the fit (:235-245) stays on the host.  No CPU fallback.
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 
-from . import _lib
 from ._base import (stage_columns, BOLTZMANN, AnalysisBase, NoDataError, UpdatingAtomGroup, native_rows,
-                    parse_dim_type, stage_frame_native)
+                    open_context, parse_dim_type, pop_device_options, stage_frame_native)
 
 _COMMIT_BYTES = 32 << 20
 
@@ -64,24 +61,8 @@ class ViscosityHelfand(AnalysisBase):
     def __init__(self, atomgroup, temp_avg=300.0, dim_type="xyz", linear_fit_window=None,
                  **kwargs):
         self._want_by_particle = bool(kwargs.pop("by_particle", True))
-        self._distributed = bool(kwargs.pop("distributed", False))
         self._stage_dtype = kwargs.pop("stage_dtype", None)
-        devices = kwargs.pop("devices", None)
-        self._devices = None if devices is None else [int(d) for d in devices]
-        if self._devices is not None and self._distributed:
-            raise ValueError("devices=[...] (one process, several GPUs) and distributed=True "
-                             "(one process per GPU) are exclusive")
-        device = kwargs.pop("device", None)
-        if device is None and self._devices:
-            device = self._devices[0]
-        if device is None:
-            if self._distributed:  # one process per GPU: this rank's own device
-                from .dist import default_device
-
-                device = default_device()
-            else:
-                device = os.environ.get("TA_AMD_DEVICE", 0)
-        self._device = _lib.device_index(device)
+        self._distributed, self._devices, self._device = pop_device_options(kwargs)
         self._float32 = bool(kwargs.pop("float32", False))
         self._fft = bool(kwargs.pop("fft", False))
         if self._fft and self._float32:
@@ -124,7 +105,7 @@ class ViscosityHelfand(AnalysisBase):
     def _prepare(self):
         """Two pinned slabs (velocities, positions) + volumes + masses (:111-142)."""
         if self._ctx is None:
-            self._ctx = _lib.Group(self._devices) if self._devices is not None else _lib.Context(self._device)
+            self._ctx = open_context(self._devices, self._device)
         self._ctx.set_option("direct_f32", int(self._float32))
         self._ctx.set_option("helfand_fft", int(self._fft))
         # float32 path: the device slabs keep float32 staging as float32 (half the footprint; the
