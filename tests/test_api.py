@@ -416,3 +416,18 @@ def test_devices_more_gpus_than_atoms_and_exclusive_with_distributed(backend):
     with pytest.raises(ValueError, match="exclusive"):
         VH(u.atoms, devices=[0], distributed=True)
 
+
+
+# private hooks of MDAnalysis >= 2.8's AnalysisBase that its run() calls (e.g.
+# self._compute(indexed_frames, verbose=..., progressbar_kwargs=...)): an analysis class that
+# defines one of them replaces MDAnalysis' own and breaks run() there
+_MDA_RUN_HOOKS = ("_compute", "_configure_backend", "_setup_computation_groups", "_get_aggregator",
+                  "_define_run_frames", "_prepare_sliced_trajectory")
+
+
+def test_classes_do_not_shadow_mdanalysis_run_hooks():
+    from transport_analysis_amd import EinsteinMSD
+
+    for cls in (VACF, VH, EinsteinMSD):
+        own = [k for c in cls.__mro__[:cls.__mro__.index(_base.AnalysisBase)] for k in vars(c)]
+        assert not set(own) & set(_MDA_RUN_HOOKS), cls.__name__

@@ -73,8 +73,9 @@ def test_classes_distributed_two_ranks_one_gpu(tmp_path, T, A):
 
 def _worker_nccl(rank, world, port, T, A, out_dir):
     """One rank, nccl (= RCCL) process group: the branch every real multi-GPU run of the classes
-    takes -- lag sums produced into a device tensor on torch's stream
-    (dist.staged_timeseries_on_device), all-reduced on the device, by-particle block copied back."""
+    takes -- lag sums produced into a device tensor on torch's stream by the class's staged call
+    (dist.staged_timeseries_on_device(launch, ...)), all-reduced on the device, by-particle block
+    copied back."""
     import torch
     import torch.distributed as dist
 

@@ -112,18 +112,22 @@ _DIM_KEYS = {
 }
 
 
-def parse_dim_type(dim_str):
+#: frames staged on the host before an asynchronous host->device copy is queued
+_COMMIT_BYTES = 32 << 20
+
+
+def parse_dim_type(dim_str, what="dim_type"):
     """Column indices and dimensionality factor for a (lower-cased) dim_type.
 
     Same table and error text as the reference
-    (velocityautocorr.py:155-176, viscosity.py:144-165); order matters, so
-    "yx" is invalid."""
+    (velocityautocorr.py:155-176, viscosity.py:144-165; MDAnalysis' EinsteinMSD with
+    ``what="msd_type"``); order matters, so "yx" is invalid."""
     try:
         cols = _DIM_KEYS[dim_str]
     except KeyError:
         raise ValueError(
-            "invalid dim_type: {} specified, please specify one of xyz, "
-            "xy, xz, yz, x, y, z".format(dim_str)
+            "invalid {}: {} specified, please specify one of xyz, "
+            "xy, xz, yz, x, y, z".format(what, dim_str)
         )
     return list(cols), len(cols)
 
@@ -218,3 +222,135 @@ def open_context(devices, device):
     from . import _lib
 
     return _lib.Group(devices) if devices is not None else _lib.Context(device)
+
+
+class StagedAnalysis(AnalysisBase):
+    """The run logic the analysis classes share: the frames' columns of ``_stage_arrays`` go into
+    pinned host slabs (one per array, in that order) and on to the device during the frame loop,
+    then ONE library call evaluates them.  The placement keywords (``device`` / ``devices`` /
+    ``distributed``), ``by_particle`` and ``stage_dtype`` are handled here; under ``distributed=True``
+    the lag sums are reduced over ranks, on the device when the process group is nccl (RCCL).
+
+    A subclass sets ``self._group`` (the analysed AtomGroup), ``self.n_particles`` and ``self._dim`` /
+    ``self.dim_fac``, names its by-particle result, gives the frame check of ``_has_data`` and
+    implements ``_set_options`` (context options, set before the slabs are allocated) and
+    ``_evaluate`` (one ``_run_kernels`` call with its host and staged entry points); its own keywords
+    it pops in ``_pop_options``.
+
+    No method here may take a name of MDAnalysis' ``AnalysisBase`` hooks: from 2.8 on its ``run()``
+    calls ``self._compute(indexed_frames, ...)``, so ``_compute`` is theirs."""
+
+    _stage_arrays = ()          # Timestep arrays staged, in slab order
+    _by_particle_key = None     # results.<key>: the (n_frames, n_particles) array or None
+    _no_data_message = None     # NoDataError text of a frame _has_data rejects
+
+    def __init__(self, group, **kwargs):
+        self._want_by_particle = bool(kwargs.pop("by_particle", True))
+        self._stage_dtype = kwargs.pop("stage_dtype", None)
+        self._distributed, self._devices, self._device = pop_device_options(kwargs)
+        self._pop_options(kwargs)
+        super().__init__(group.universe.trajectory, **kwargs)
+        self._ctx = None
+
+    def _pop_options(self, kwargs):
+        """Pop (and check) the subclass's own keywords before AnalysisBase sees the rest."""
+
+    def _pick_stage_dtype(self):
+        """float32 when the trajectory hands out every staged array in float32 (MDAnalysis does):
+        lossless, half the PCIe bytes of the reference's float64 slab; the arithmetic is float64."""
+        if self._stage_dtype is not None:
+            return np.dtype(self._stage_dtype)
+        try:
+            f32 = all(np.asarray(getattr(self._group, a)).dtype == np.float32 for a in self._stage_arrays)
+        except Exception:  # missing data: _single_frame raises NoDataError, as the reference does
+            return np.dtype(np.float64)
+        return np.dtype(np.float32) if f32 else np.dtype(np.float64)
+
+    def _prepare(self):
+        """Pinned host slabs + device slabs instead of the reference's ``np.zeros`` arrays."""
+        if self._ctx is None:
+            self._ctx = open_context(self._devices, self._device)
+        self._lo, self._hi = 0, self.n_particles
+        self._source = self._group  # whose arrays a frame is read from
+        self._rccl = False  # the lag sums stay on the GPU through the reduce
+        if self._distributed:
+            from .dist import shard_of_this_rank, uses_device_reduce
+
+            _, _, self._lo, self._hi = shard_of_this_rank(self.n_particles)
+            self.results.particle_range = (self._lo, self._hi)
+            # this rank's block only: the trajectory gathers hi - lo atoms per frame, not all of them
+            self._source = self._group[self._lo:self._hi]
+            self._rccl = uses_device_reduce()
+        self._n_local = self._hi - self._lo
+        dtype = self._pick_stage_dtype()
+        self._set_options(dtype)
+        n_slabs = len(self._stage_arrays)
+        if self._devices is not None:
+            # one pinned slab per array and GPU, each holding that GPU's column block; filled in ONE frame loop
+            slabs = self._ctx.stage_alloc(self.n_frames, self.n_particles, self.dim_fac, n_slabs=n_slabs, dtype=dtype)
+            self._targets = [(views, lo, hi) for *views, (lo, hi) in zip(*slabs, self._ctx.shards) if hi > lo]
+            self.results.device_ranges = list(self._ctx.shards)
+        else:
+            slabs = self._ctx.stage_alloc(self.n_frames, max(self._n_local, 1), self.dim_fac, n_slabs=n_slabs,
+                                          dtype=dtype)
+            # columns of the source group: the distributed source is the block itself
+            self._targets = [(slabs, 0, self._n_local)]
+        for attr, slab in zip(self._stage_arrays, slabs):
+            setattr(self, "_" + attr, slab)
+        self._fills = tuple(enumerate(self._stage_arrays))  # (slab, Timestep array) pairs of the frame loop
+        # the per-frame fill reads the Timestep's own arrays natively (ta_stage_frame) where it can
+        self._rows = native_rows(self._source) if self._n_local else None
+        frame_bytes = max(1, n_slabs * self._n_local * self.dim_fac * dtype.itemsize)
+        self._commit_every = max(1, _COMMIT_BYTES // frame_bytes)
+        self._committed = 0
+        setattr(self.results, self._by_particle_key, None)
+        # the (n_frames, n_particles) result array lives in pinned host memory, page-locked on a
+        # helper thread while the frames are staged
+        self._bp_home = None
+        if self._want_by_particle and self._n_local and not self._rccl:
+            self._bp_home = self._ctx.result_home((self.n_frames, self._n_local))
+
+    def _single_frame(self):
+        """Stage the selected columns of one frame's arrays."""
+        ts = self._ts
+        if not self._has_data(ts):
+            raise NoDataError(self._no_data_message)
+        i = self._frame_index
+        if self._n_local:
+            for slab, attr in self._fills:
+                if not stage_frame_native(self._ctx, slab, i, ts, attr, self._dim, self._rows):
+                    src = np.asarray(getattr(self._source, attr))
+                    for views, lo, hi in self._targets:
+                        stage_columns(views[slab][i], src, lo, hi, self._dim)
+        if i + 1 - self._committed >= self._commit_every:
+            self._ctx.stage_commit(self._committed, i + 1)
+            self._committed = i + 1
+
+    def _conclude(self):
+        if self._committed < self.n_frames:
+            self._ctx.stage_commit(self._committed, self.n_frames)
+            self._committed = self.n_frames
+        self._evaluate()
+
+    def _run_kernels(self, host, launch):
+        """results.timeseries and the by-particle result of the staged slabs.  host(by_particle=, out=)
+        -> (timeseries, by-particle or None) is the library call; launch(d_lagsum, d_bp, ld_bp, stream)
+        its staged twin, which only the RCCL path calls (see dist.staged_timeseries_on_device) -- so it
+        looks the context's ``*_staged`` method up when called: a device group has none."""
+        if self._rccl:
+            from .dist import staged_timeseries_on_device
+
+            ts, bp = staged_timeseries_on_device(launch, self.n_frames, self._n_local, self.n_particles,
+                                                 self._device, by_particle=self._want_by_particle)
+        else:
+            home = self._bp_home.get() if self._bp_home is not None else None
+            self._bp_home = None
+            ts, bp = host(by_particle=self._want_by_particle, out=home)
+            if self._distributed:
+                from .dist import allreduce_mean_over_atoms
+
+                if self._n_local == 0:  # more ranks than atoms: this rank contributes nothing
+                    ts, bp = np.zeros(self.n_frames), (None if bp is None else bp[:, :0])
+                ts = allreduce_mean_over_atoms(ts, self._n_local, self.n_particles, self._device)
+        setattr(self.results, self._by_particle_key, bp)
+        self.results.timeseries = ts

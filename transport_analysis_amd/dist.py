@@ -97,11 +97,12 @@ def uses_device_reduce():
     return dist.is_available() and dist.is_initialized() and dist.get_backend() == "nccl"
 
 
-def staged_timeseries_on_device(ctx, which, n_frames, n_local, n_atoms_total, device, masses=None,
-                                scale=1.0, by_particle=False, fft=True):
+def staged_timeseries_on_device(launch, n_frames, n_local, n_atoms_total, device, by_particle=False):
     """This rank's staged block -> lag sums (device) -> ONE all-reduce over RCCL -> mean over
     ALL atoms.  The (n_frames,) float64 sums never leave the GPU before the reduce.
-    which: "fft" | "direct" | "helfand" | "msd" (the Einstein MSD of the position slab, by the FFT form when `fft`).  Returns (timeseries ndarray, by_particle ndarray|None)."""
+    launch(d_lagsum, d_bp, ld_bp, stream) is the context's staged call (``Context.vacf_fft_staged`` and
+    its siblings), made inside this device's scope; what it returns is kept alive until the results are
+    on the host.  Returns (timeseries ndarray, by_particle ndarray|None)."""
     import torch
 
     dev = torch.device("cuda", device)
@@ -110,21 +111,12 @@ def staged_timeseries_on_device(ctx, which, n_frames, n_local, n_atoms_total, de
         lag = torch.zeros(n_frames, dtype=torch.float64, device=dev)
         bp = torch.empty((n_frames, max(n_local, 1)), dtype=torch.float64, device=dev) if by_particle else None
         d_bp = bp.data_ptr() if bp is not None else 0
-        if n_local:  # more ranks than atoms: this rank contributes zeros
-            if which == "fft":
-                ctx.vacf_fft_staged(lag.data_ptr(), d_bp, n_local, stream)
-            elif which == "direct":
-                ctx.vacf_direct_staged(lag.data_ptr(), d_bp, n_local, stream)
-            elif which == "msd":
-                ctx.msd_staged(fft, lag.data_ptr(), d_bp, n_local, stream)
-            else:
-                m = torch.as_tensor(np.ascontiguousarray(masses, dtype=np.float64), device=dev)
-                ctx.helfand_msd_staged(m.data_ptr(), float(scale), lag.data_ptr(), d_bp, n_local, stream)
+        held = launch(lag.data_ptr(), d_bp, n_local, stream) if n_local else None  # more ranks than atoms: zeros
         ts = reduce_lagsum(lag, n_atoms_total)
         out_bp = None
         if bp is not None:
             out_bp = bp.cpu().numpy() if n_local else np.zeros((n_frames, 0))
-        return ts.cpu().numpy(), out_bp
+        return ts.cpu().numpy(), out_bp  # (`held` lives until here)
 
 
 def allreduce_mean_over_atoms(ts_local, n_local, n_atoms_total, device=None):

@@ -11,14 +11,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._base import (stage_columns, AnalysisBase, NoDataError, UpdatingAtomGroup, native_rows, open_context, parse_dim_type,
-                    pop_device_options, stage_frame_native)
-
-#: frames staged on the host before an asynchronous host->device copy is queued
-_COMMIT_BYTES = 32 << 20
+from ._base import StagedAnalysis, UpdatingAtomGroup, parse_dim_type
 
 
-class VelocityAutocorr(AnalysisBase):
+class VelocityAutocorr(StagedAnalysis):
     r"""Velocity autocorrelation function (VACF) of an AtomGroup.
 
     Parameters
@@ -79,12 +75,12 @@ class VelocityAutocorr(AnalysisBase):
     dim_fac, n_frames, n_particles, times, frames, start, stop, step
     """
 
+    _stage_arrays = ("velocities",)
+    _by_particle_key = "vacf_by_particle"
+    _no_data_message = "VACF computation requires velocities in the trajectory"
+
     def __init__(self, atomgroup, dim_type="xyz", fft=True, **kwargs):
-        self._want_by_particle = bool(kwargs.pop("by_particle", True))
-        self._stage_dtype = kwargs.pop("stage_dtype", None)
-        self._device_f32 = kwargs.pop("device_float32", None)
-        self._distributed, self._devices, self._device = pop_device_options(kwargs)
-        super().__init__(atomgroup.universe.trajectory, **kwargs)
+        super().__init__(atomgroup, **kwargs)
 
         if isinstance(atomgroup, UpdatingAtomGroup):
             raise TypeError("UpdatingAtomGroups are not valid for VACF computation")
@@ -93,10 +89,12 @@ class VelocityAutocorr(AnalysisBase):
         self._dim, self.dim_fac = parse_dim_type(self.dim_type)
         self.fft = fft
 
-        self.atomgroup = atomgroup
+        self.atomgroup = self._group = atomgroup
         self.n_particles = len(self.atomgroup)
         self._run_called = False
-        self._ctx = None
+
+    def _pop_options(self, kwargs):
+        self._device_f32 = kwargs.pop("device_float32", None)
 
     _parse_dim_type = staticmethod(parse_dim_type)
 
@@ -109,125 +107,31 @@ class VelocityAutocorr(AnalysisBase):
     def get_supported_backends(cls):
         return ("serial",)
 
-    def _pick_stage_dtype(self):
-        """float32 when the trajectory hands out float32 (MDAnalysis always does); the
-        reference upcasts into a float64 slab (:150-152,192-194), which the device slab is."""
-        if self._stage_dtype is not None:
-            return np.dtype(self._stage_dtype)
-        try:
-            dt = np.asarray(self.atomgroup.velocities).dtype
-        except Exception:  # no velocities: _single_frame raises NoDataError, as the reference does
-            return np.dtype(np.float64)
-        return np.dtype(np.float32) if dt == np.float32 else np.dtype(np.float64)
-
     # ------------------------------------------------------------ hooks
-    def _prepare(self):
-        """Pinned host slab + device slab instead of ``np.zeros`` (:142-153)."""
-        if self._ctx is None:
-            self._ctx = open_context(self._devices, self._device)
-        self._lo, self._hi = 0, self.n_particles
-        self._source = self.atomgroup  # whose velocities a frame is read from
-        if self._distributed:
-            from .dist import shard_of_this_rank
+    # _prepare (:142-153; results.timeseries is not set there) and _single_frame (:178-194) are
+    # StagedAnalysis': the velocity columns go into a pinned host slab and on to the device.
+    @staticmethod
+    def _has_data(ts):
+        return ts.has_velocities
 
-            _, _, self._lo, self._hi = shard_of_this_rank(self.n_particles)
-            self.results.particle_range = (self._lo, self._hi)
-            # this rank's block only: the trajectory gathers hi - lo atoms per frame, not all of them
-            self._source = self.atomgroup[self._lo:self._hi]
-        self._n_local = self._hi - self._lo
-        dtype = self._pick_stage_dtype()
+    def _set_options(self, dtype):
         dev32 = self._device_f32
         if dev32 is None:  # float32 staging stays float32 on the device where the FFT kernels read it as it is
             dev32 = dtype == np.float32 and bool(self.fft) and 512 < self.n_frames <= 10240
         self._ctx.set_option("stage_device_f32", int(bool(dev32) and dtype == np.float32))
-        if self._devices is not None:
-            # one pinned slab per GPU, each holding that GPU's column block; filled in ONE frame loop
-            (views,) = self._ctx.stage_alloc(self.n_frames, self.n_particles, self.dim_fac, n_slabs=1, dtype=dtype)
-            self._velocities = views
-            self._targets = [(v, lo, hi) for v, (lo, hi) in zip(views, self._ctx.shards) if hi > lo]
-            self.results.device_ranges = list(self._ctx.shards)
-        else:
-            (self._velocities,) = self._ctx.stage_alloc(
-                self.n_frames, max(self._n_local, 1), self.dim_fac, n_slabs=1, dtype=dtype)
-            # (columns of the source group: the distributed source is the block itself)
-            self._targets = [(self._velocities, 0, self._n_local)] if self._distributed else \
-                [(self._velocities, self._lo, self._hi)]
-        # the per-frame fill reads the Timestep's own array natively (ta_stage_frame) where it can
-        self._rows = native_rows(self._source) if self._n_local else None
-        frame_bytes = max(1, self._n_local * self.dim_fac * dtype.itemsize)
-        self._commit_every = max(1, _COMMIT_BYTES // frame_bytes)
-        self._committed = 0
-        self.results.vacf_by_particle = None
-        # the (n_frames, n_particles) result array (:145-147) lives in pinned host memory, page-locked
-        # on a helper thread while the frames are staged
-        self._bp_home = None
-        if self._want_by_particle and self._n_local and not self._device_reduce():
-            self._bp_home = self._ctx.result_home((self.n_frames, self._n_local))
-        # results.timeseries is not set here (reference: :153)
 
-    def _single_frame(self):
-        """Stage one frame of the selected velocity columns (:178-194)."""
-        if not self._ts.has_velocities:
-            raise NoDataError("VACF computation requires velocities in the trajectory")
-        i = self._frame_index
-        if self._n_local and not stage_frame_native(self._ctx, 0, i, self._ts, "velocities", self._dim, self._rows):
-            vel = np.asarray(self._source.velocities)
-            for view, lo, hi in self._targets:
-                stage_columns(view[i], vel, lo, hi, self._dim)
-        if i + 1 - self._committed >= self._commit_every:
-            self._ctx.stage_commit(self._committed, i + 1)
-            self._committed = i + 1
-
-    def _conclude(self):
-        if self._committed < self.n_frames:
-            self._ctx.stage_commit(self._committed, self.n_frames)
-            self._committed = self.n_frames
+    def _evaluate(self):
         if self.fft:
             self._conclude_fft()
         else:
             self._conclude_simple()
+        self._run_called = True
 
     def _conclude_fft(self):
-        self._compute("fft")
+        self._run_kernels(self._ctx.vacf_fft, lambda *a: self._ctx.vacf_fft_staged(*a))
 
     def _conclude_simple(self):
-        self._compute("direct")
-
-    def _device_reduce(self):
-        if not self._distributed:
-            return False
-        from .dist import uses_device_reduce
-
-        return uses_device_reduce()
-
-    def _compute(self, which):
-        if self._distributed:
-            from .dist import staged_timeseries_on_device
-
-            if self._device_reduce():  # RCCL: the lag sums stay on the GPU through the reduce
-                ts, bp = staged_timeseries_on_device(self._ctx, which, self.n_frames, self._n_local,
-                                                     self.n_particles, self._device,
-                                                     by_particle=self._want_by_particle)
-                self.results.vacf_by_particle = bp
-                self.results.timeseries = ts
-                self._run_called = True
-                return
-        fn = self._ctx.vacf_fft if which == "fft" else self._ctx.vacf_direct
-        home = self._bp_home.get() if self._bp_home is not None else None
-        self._bp_home = None
-        ts, bp = fn(by_particle=self._want_by_particle, out=home)
-        self._store(ts, bp)
-
-    def _store(self, ts, bp):
-        if self._distributed:
-            from .dist import allreduce_mean_over_atoms
-
-            if self._n_local == 0:  # more ranks than atoms: this rank contributes nothing
-                ts, bp = np.zeros(self.n_frames), (None if bp is None else bp[:, :0])
-            ts = allreduce_mean_over_atoms(ts, self._n_local, self.n_particles, self._device)
-        self.results.vacf_by_particle = bp
-        self.results.timeseries = ts
-        self._run_called = True
+        self._run_kernels(self._ctx.vacf_direct, lambda *a: self._ctx.vacf_direct_staged(*a))
 
     # --------------------------------------------- post-processing (host)
     def _window(self, start, stop, step):

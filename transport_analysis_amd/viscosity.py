@@ -6,15 +6,14 @@ hand-written HIP kernel; the fit (:235-245) stays on the host.  No CPU fallback.
 """
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
-from ._base import (stage_columns, BOLTZMANN, AnalysisBase, NoDataError, UpdatingAtomGroup, native_rows,
-                    open_context, parse_dim_type, pop_device_options, stage_frame_native)
-
-_COMMIT_BYTES = 32 << 20
+from ._base import BOLTZMANN, StagedAnalysis, UpdatingAtomGroup, parse_dim_type
 
 
-class ViscosityHelfand(AnalysisBase):
+class ViscosityHelfand(StagedAnalysis):
     r"""Viscosity function via the Einstein-Helfand method.
 
     Parameters
@@ -58,16 +57,14 @@ class ViscosityHelfand(AnalysisBase):
     results.viscosity : slope of the linear fit (only with linear_fit_window).
     """
 
+    _stage_arrays = ("velocities", "positions")
+    _by_particle_key = "visc_by_particle"
+    _no_data_message = ("Helfand viscosity computation requires "
+                        "velocities, positions, and box volume in the trajectory")
+
     def __init__(self, atomgroup, temp_avg=300.0, dim_type="xyz", linear_fit_window=None,
                  **kwargs):
-        self._want_by_particle = bool(kwargs.pop("by_particle", True))
-        self._stage_dtype = kwargs.pop("stage_dtype", None)
-        self._distributed, self._devices, self._device = pop_device_options(kwargs)
-        self._float32 = bool(kwargs.pop("float32", False))
-        self._fft = bool(kwargs.pop("fft", False))
-        if self._fft and self._float32:
-            raise ValueError("fft=True and float32=True are exclusive")
-        super().__init__(atomgroup.universe.trajectory, **kwargs)
+        super().__init__(atomgroup, **kwargs)
 
         if isinstance(atomgroup, UpdatingAtomGroup):
             raise TypeError("UpdatingAtomGroups are not valid for viscosity computation")
@@ -77,9 +74,14 @@ class ViscosityHelfand(AnalysisBase):
         self.linear_fit_window = linear_fit_window
         self._dim, self.dim_fac = parse_dim_type(self.dim_type)
 
-        self.atomgroup = atomgroup
+        self.atomgroup = self._group = atomgroup
         self.n_particles = len(self.atomgroup)
-        self._ctx = None
+
+    def _pop_options(self, kwargs):
+        self._float32 = bool(kwargs.pop("float32", False))
+        self._fft = bool(kwargs.pop("fft", False))
+        if self._fft and self._float32:
+            raise ValueError("fft=True and float32=True are exclusive")
 
     _parse_dim_type = staticmethod(parse_dim_type)
 
@@ -90,123 +92,45 @@ class ViscosityHelfand(AnalysisBase):
     def get_supported_backends(cls):
         return ("serial",)
 
-    def _pick_stage_dtype(self):
-        """float32 when the trajectory hands out float32 velocities AND positions (MDAnalysis
-        does): lossless, half the PCIe bytes; the device slabs are float64 (:128-134)."""
-        if self._stage_dtype is not None:
-            return np.dtype(self._stage_dtype)
-        try:
-            f32 = (np.asarray(self.atomgroup.velocities).dtype == np.float32
-                   and np.asarray(self.atomgroup.positions).dtype == np.float32)
-        except Exception:  # missing data: _single_frame raises NoDataError, as the reference does
-            return np.dtype(np.float64)
-        return np.dtype(np.float32) if f32 else np.dtype(np.float64)
-
-    def _prepare(self):
-        """Two pinned slabs (velocities, positions) + volumes + masses (:111-142)."""
-        if self._ctx is None:
-            self._ctx = open_context(self._devices, self._device)
+    def _set_options(self, dtype):
         self._ctx.set_option("direct_f32", int(self._float32))
         self._ctx.set_option("helfand_fft", int(self._fft))
         # float32 path: the device slabs keep float32 staging as float32 (half the footprint; the
         # kernels round the staged value to float32 anyway, so the results do not change)
         self._ctx.set_option("stage_device_f32", int(self._float32))
-        self._lo, self._hi = 0, self.n_particles
-        self._source = self.atomgroup  # whose velocities / positions a frame is read from
-        if self._distributed:
-            from .dist import shard_of_this_rank
 
-            _, _, self._lo, self._hi = shard_of_this_rank(self.n_particles)
-            self.results.particle_range = (self._lo, self._hi)
-            # this rank's block only: the trajectory gathers hi - lo atoms per frame, not all of them
-            self._source = self.atomgroup[self._lo:self._hi]
-        self._n_local = self._hi - self._lo
-        dtype = self._pick_stage_dtype()
-        if self._devices is not None:
-            # one pair of pinned slabs per GPU (its column block); filled in ONE frame loop
-            vviews, xviews = self._ctx.stage_alloc(self.n_frames, self.n_particles, self.dim_fac, n_slabs=2,
-                                                   dtype=dtype)
-            self._velocities, self._positions = vviews, xviews
-            self._targets = [(v, x, lo, hi) for v, x, (lo, hi) in zip(vviews, xviews, self._ctx.shards) if hi > lo]
-            self.results.device_ranges = list(self._ctx.shards)
-        else:
-            self._velocities, self._positions = self._ctx.stage_alloc(
-                self.n_frames, max(self._n_local, 1), self.dim_fac, n_slabs=2, dtype=dtype)
-            self._targets = [(self._velocities, self._positions, 0, self._n_local)] if self._distributed else \
-                [(self._velocities, self._positions, self._lo, self._hi)]
+    def _prepare(self):
+        """Two pinned slabs (velocities, positions) + volumes + masses (:111-142)."""
+        super()._prepare()
         self._volumes = np.zeros(self.n_frames)
         self._masses = np.asarray(self.atomgroup.masses, dtype=np.float64)[self._lo:self._hi]
         if self._n_local == 0:
             self._masses = np.ones(1)
         self.boltzmann = BOLTZMANN
-        frame_bytes = max(1, 2 * self._n_local * self.dim_fac * dtype.itemsize)
-        self._commit_every = max(1, _COMMIT_BYTES // frame_bytes)
-        # the per-frame fill reads the Timestep's own arrays natively (ta_stage_frame) where it can
-        self._rows = native_rows(self._source) if self._n_local else None
-        self._committed = 0
-        self.results.visc_by_particle = None
-        # pinned home of the (n_frames, n_particles) result (:117-119), page-locked on a helper thread
-        self._bp_home = None
-        if self._want_by_particle and self._n_local:
-            device_reduce = False
-            if self._distributed:
-                from .dist import uses_device_reduce
 
-                device_reduce = uses_device_reduce()
-            if not device_reduce:
-                self._bp_home = self._ctx.result_home((self.n_frames, self._n_local))
+    @staticmethod
+    def _has_data(ts):
+        return ts.has_velocities and ts.has_positions and ts.volume != 0
 
     def _single_frame(self):
         """Stage volume, velocities and positions of one frame (:167-199)."""
-        ts = self._ts
-        if not (ts.has_velocities and ts.has_positions and ts.volume != 0):
-            raise NoDataError(
-                "Helfand viscosity computation requires "
-                "velocities, positions, and box volume in the trajectory"
-            )
-        i = self._frame_index
-        self._volumes[i] = ts.volume
-        if self._n_local:
-            if not stage_frame_native(self._ctx, 0, i, ts, "velocities", self._dim, self._rows):
-                vel = np.asarray(self._source.velocities)
-                for vview, xview, lo, hi in self._targets:
-                    stage_columns(vview[i], vel, lo, hi, self._dim)
-            if not stage_frame_native(self._ctx, 1, i, ts, "positions", self._dim, self._rows):
-                pos = np.asarray(self._source.positions)
-                for vview, xview, lo, hi in self._targets:
-                    stage_columns(xview[i], pos, lo, hi, self._dim)
-        if i + 1 - self._committed >= self._commit_every:
-            self._ctx.stage_commit(self._committed, i + 1)
-            self._committed = i + 1
+        super()._single_frame()
+        self._volumes[self._frame_index] = self._ts.volume
 
-    def _conclude(self):
-        if self._committed < self.n_frames:
-            self._ctx.stage_commit(self._committed, self.n_frames)
-            self._committed = self.n_frames
+    def _evaluate(self):
         self._vol_avg = np.average(self._volumes)
         # everything is divided by 2 kB <V> T (:229-231)
         scale = 1.0 / (2 * self.boltzmann * self._vol_avg * self.temp_avg)
-        device_reduce = False
-        if self._distributed:
-            from .dist import staged_timeseries_on_device, uses_device_reduce
 
-            device_reduce = uses_device_reduce()
-        if device_reduce:  # RCCL: the lag sums stay on the GPU through the reduce
-            ts, bp = staged_timeseries_on_device(self._ctx, "helfand", self.n_frames, self._n_local,
-                                                 self.n_particles, self._device, masses=self._masses,
-                                                 scale=scale, by_particle=self._want_by_particle)
-        else:
-            home = self._bp_home.get() if self._bp_home is not None else None
-            self._bp_home = None
-            ts, bp = self._ctx.helfand_msd(self._masses, scale, by_particle=self._want_by_particle, out=home)
-        if self._distributed and not device_reduce:
-            from .dist import allreduce_mean_over_atoms
+        def launch(d_lagsum, d_bp, ld_bp, stream):
+            import torch
 
-            if self._n_local == 0:
-                ts, bp = np.zeros(self.n_frames), (None if bp is None else bp[:, :0])
-            ts = allreduce_mean_over_atoms(ts, self._n_local, self.n_particles, self._device)
-        self.results.visc_by_particle = bp
-        self.results.timeseries = ts
+            m = torch.as_tensor(np.ascontiguousarray(self._masses, dtype=np.float64),
+                                device=torch.device("cuda", self._device))
+            self._ctx.helfand_msd_staged(m.data_ptr(), float(scale), d_lagsum, d_bp, ld_bp, stream)
+            return m  # kept alive until the results are back on the host
+
+        self._run_kernels(functools.partial(self._ctx.helfand_msd, self._masses, scale), launch)
 
         if self.linear_fit_window is not None:
             # the reference fits against lagtimes = arange(1, n_frames): its x axis
