@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -147,8 +147,10 @@ int ta_stage_synth(ta_ctx *ctx, int slab, uint64_t seed, int64_t col_offset, int
  * until this call or ta_ctx_destroy: partial spectra (<= 42 MB), with a by-particle array the
  * atom-major scratch (n_atoms * n_frames * 8 bytes) and the power spectra of one block of atoms
  * (2.5 GiB unless "bp_spec_atoms" says otherwise), the pair-major copies of frame-major *_dev
- * inputs (the input's size, twice for Helfand), the 64 MiB landing buffer of ta_stage_commit
- * and the product slab of the "helfand_fft" option (the input's size).                        */
+ * inputs (the input's size, twice for Helfand), the 64 MiB landing buffer of ta_stage_commit,
+ * the product slab of the "helfand_fft" option and of the Einstein MSD's FFT form (the input's size),
+ * and for ta_conductivity* the moment's partial sums (<= 1024 * n_frames * dim * 8 bytes) and, with
+ * the self term, the weighted slab (the input's size).                                        */
 int ta_trim(ta_ctx *ctx);
 
 /* ---- pinned host memory for result arrays ---------------------------------
@@ -188,6 +190,21 @@ int ta_helfand_msd(ta_ctx *ctx, const double *h_masses, double scale, double *h_
  *                   TA_E_INVALID.  CPU backend: fft = 1 by zero-padded transforms of x - x[t=0], fft = 0 directly.
  *                   Float32 device slabs ("stage_device_f32") are widened to float64 first; "direct_f32" is ignored. */
 int ta_msd(ta_ctx *ctx, int fft, double *h_timeseries, double *h_by_particle);
+/* ta_conductivity : Einstein-Helfand ionic conductivity (no reference: a new analysis, ConductivityHelfand) on slab 0 = the
+ *                   positions of the dim_type's columns and h_charges = the n_atoms charges q_n:
+ *                     h_moment[t * dim + d] = M[t, d] = sum_n q_n (x[t,n,d] - x[0,n,d])          ((n_frames, dim), required)
+ *                     h_collective[k] = Phi(k) = 1 / (n_frames - k) sum_{i < n_frames - k} sum_d (M[i+k,d] - M[i,d])^2
+ *                     h_self_lagsum[k] = sum_n q_n^2 MSD_n(k), MSD_n as in ta_msd (the Nernst-Einstein self term)
+ *                   h_collective / h_self_lagsum NULL: skipped (without the self term no weighted slab is written).  One
+ *                   pass over the slab forms M as fixed-order partial sums (no atomics: the same bits from run to run)
+ *                   and, for the self term, the weighted slab q (x - x[0]) in the context's scratch (one slab of
+ *                   n_frames * n_atoms * dim * 8 bytes, kept as ta_trim says); Phi and the self term are the lag sums of
+ *                   ta_msd with the same fft (0 / 1, else TA_E_INVALID) on a one-atom copy of M and on the weighted slab
+ *                   (the FFT form adds ta_msd's own product slab).  NULL h_charges / h_moment: TA_E_INVALID; nothing
+ *                   staged: TA_E_STATE.  CPU backend: the same in C++/OpenMP.  Timings: the moment pass is the main
+ *                   kernel unless an FFT evaluation follows it (ta_kernel_timeline names it k_cond_moment).          */
+int ta_conductivity(ta_ctx *ctx, int fft, const double *h_charges, double *h_moment, double *h_collective,
+                    double *h_self_lagsum);
 
 /* ---- compute on caller-provided device memory (asynchronous) -----------
  * Same arithmetic as above on a device-resident FRAME-MAJOR shard: d_vel / d_pos are
@@ -209,6 +226,12 @@ int ta_helfand_msd_dev(ta_ctx *ctx, const double *d_vel, const double *d_pos,
                        double *d_by_particle, int64_t ld_bp, void *stream);
 int ta_msd_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row,
                int fft, double *d_lagsum, double *d_by_particle, int64_t ld_bp, void *stream);
+/* d_charges: (n_atoms,) device array; d_moment (n_frames, dim) required, d_collective / d_self_lagsum (n_frames,) or NULL.
+ * A shard's moment and self lag sum add up over shards; Phi does not (reduce the moments, then ta_msd_dev with
+ * n_atoms = 1, ld_row = dim on the sum).                                                                            */
+int ta_conductivity_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row,
+                        int fft, const double *d_charges, double *d_moment, double *d_collective,
+                        double *d_self_lagsum, void *stream);
 
 /* ---- compute on the staged (pair-major) slabs, device outputs, asynchronous on `stream` ----
  * Same arithmetic and outputs as the *_dev calls, on the slabs of ta_stage_alloc*: no
@@ -220,6 +243,8 @@ int ta_vacf_direct_staged(ta_ctx *ctx, double *d_lagsum, double *d_by_particle, 
 int ta_helfand_msd_staged(ta_ctx *ctx, const double *d_masses, double scale, double *d_lagsum,
                           double *d_by_particle, int64_t ld_bp, void *stream);
 int ta_msd_staged(ta_ctx *ctx, int fft, double *d_lagsum, double *d_by_particle, int64_t ld_bp, void *stream);
+int ta_conductivity_staged(ta_ctx *ctx, int fft, const double *d_charges, double *d_moment, double *d_collective,
+                           double *d_self_lagsum, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns
@@ -272,6 +297,11 @@ int ta_group_vacf_direct(ta_group *g, double *h_timeseries, double *h_by_particl
 int ta_group_helfand_msd(ta_group *g, const double *h_masses, double scale, double *h_timeseries,
                          double *h_by_particle);
 int ta_group_msd(ta_group *g, int fft, double *h_timeseries, double *h_by_particle);
+/* ta_group_conductivity: ta_conductivity on every member (h_charges: all n_atoms); the members' moments and self lag sums
+ * are SUMMED on the host in member order, then ONE collective MSD of the summed moment runs on the first member that holds
+ * atoms.  h_collective is required here.                                                                             */
+int ta_group_conductivity(ta_group *g, int fft, const double *h_charges, double *h_moment, double *h_collective,
+                          double *h_self_lagsum);
 
 /* ---- instrumentation ----------------------------------------------------
  * Device time of the last *_dev / host-facing compute call on this context,

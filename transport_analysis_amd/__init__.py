@@ -1,7 +1,8 @@
 """transport_analysis_amd — MI355X-native time-correlation kernels behind the
-transport-analysis API (VelocityAutocorr, ViscosityHelfand) and MDAnalysis' EinsteinMSD."""
+transport-analysis API (VelocityAutocorr, ViscosityHelfand), MDAnalysis' EinsteinMSD and ConductivityHelfand."""
 __version__ = "0.1.0"
 
 from .velocityautocorr import VelocityAutocorr  # noqa: F401
 from .viscosity import ViscosityHelfand  # noqa: F401
 from .msd import EinsteinMSD  # noqa: F401
+from .conductivity import ConductivityHelfand  # noqa: F401

@@ -303,7 +303,8 @@ class StagedAnalysis(AnalysisBase):
         frame_bytes = max(1, n_slabs * self._n_local * self.dim_fac * dtype.itemsize)
         self._commit_every = max(1, _COMMIT_BYTES // frame_bytes)
         self._committed = 0
-        setattr(self.results, self._by_particle_key, None)
+        if self._by_particle_key is not None:
+            setattr(self.results, self._by_particle_key, None)
         # the (n_frames, n_particles) result array lives in pinned host memory, page-locked on a
         # helper thread while the frames are staged
         self._bp_home = None

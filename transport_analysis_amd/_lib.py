@@ -33,6 +33,7 @@ EXPORTS = (
     "ta_group_stage_commit", "ta_group_stage_frame", "ta_group_stage_free", "ta_group_stage_alloc_device", "ta_group_stage_synth", "ta_group_vacf_fft", "ta_group_vacf_direct",
     "ta_group_helfand_msd",
     "ta_msd", "ta_msd_dev", "ta_msd_staged", "ta_group_msd",
+    "ta_conductivity", "ta_conductivity_dev", "ta_conductivity_staged", "ta_group_conductivity",
 )
 
 
@@ -155,6 +156,10 @@ def lib():
     L.ta_msd_dev.argtypes = [vp, vp, i64, i64, ci, i64, ci, vp, vp, i64, vp]
     L.ta_msd_staged.argtypes = [vp, ci, vp, vp, i64, vp]
     L.ta_group_msd.argtypes = [vp, ci, vp, vp]
+    L.ta_conductivity.argtypes = [vp, ci, vp, vp, vp, vp]
+    L.ta_conductivity_dev.argtypes = [vp, vp, i64, i64, ci, i64, ci, vp, vp, vp, vp, vp]
+    L.ta_conductivity_staged.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    L.ta_group_conductivity.argtypes = [vp, ci, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("ta_last_error", "ta_group_last_error", "ta_group_reduce_kind", "ta_group_reduce_note"):
             getattr(L, name).restype = ci
@@ -454,6 +459,32 @@ class Context:
         """Einstein MSD of slab 0 (the positions): (timeseries, by_particle or None)."""
         return self._host(lib().ta_msd, by_particle, int(fft), out=out)
 
+    def _conductivity(self, fn, fft, charges, self_term, collective):
+        T, A, D = getattr(self, "shape", None) or (1, 1, 1)  # unstaged: the library reports it
+        q = np.ascontiguousarray(charges, dtype=np.float64).ravel()
+        if q.size != A:
+            raise ValueError(f"charges: {q.size} values for {A} atoms")
+        moment = np.empty((T, D), dtype=np.float64)
+        phi = np.empty(T, dtype=np.float64) if collective else None
+        self_ls = np.empty(T, dtype=np.float64) if self_term else None
+        self._check(fn(self._h, int(fft), _ptr(q), _ptr(moment), _ptr(phi), _ptr(self_ls)))
+        return moment, phi, self_ls
+
+    def conductivity(self, fft, charges, self_term=False, collective=True):
+        """Einstein-Helfand conductivity of slab 0 (the positions) with one charge per staged atom:
+        (moment (n_frames, dim), Phi (n_frames,) or None, self lag sum sum_n q_n^2 MSD_n (n_frames,) or None)."""
+        return self._conductivity(lib().ta_conductivity, fft, charges, self_term, collective)
+
+    def moment_msd(self, moment, fft):
+        """Phi(k) of a (n_frames, dim) moment, e.g. the sum of several shards' moments: the moment is staged as a
+        one-atom slab (replacing this context's slabs) whose conductivity with charge 1 is that moment's MSD."""
+        moment = np.asarray(moment, dtype=np.float64)
+        T, D = moment.shape
+        (view,) = self.stage_alloc(T, 1, D)
+        view[:, 0, :] = moment
+        self.stage_commit(0, T)
+        return self.conductivity(fft, np.ones(1))[1]
+
     # -- device-pointer compute (asynchronous) --------------------------
     def vacf_fft_dev(self, d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._check(lib().ta_vacf_fft_dev(self._h, d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum,
@@ -474,6 +505,11 @@ class Context:
                                      d_bp or None, ld_bp, stream or None))
 
     # -- compute on the staged slabs, device outputs (asynchronous) ------
+    def conductivity_dev(self, d_pos, n_frames, n_atoms, dim, ld_row, fft, d_charges, d_moment, d_collective=0,
+                         d_self=0, stream=0):
+        self._check(lib().ta_conductivity_dev(self._h, d_pos, n_frames, n_atoms, dim, ld_row, int(fft), d_charges,
+                                              d_moment, d_collective or None, d_self or None, stream or None))
+
     def vacf_fft_staged(self, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._check(lib().ta_vacf_fft_staged(self._h, d_lagsum, d_bp or None, ld_bp, stream or None))
 
@@ -486,6 +522,10 @@ class Context:
 
     def msd_staged(self, fft, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._check(lib().ta_msd_staged(self._h, int(fft), d_lagsum, d_bp or None, ld_bp, stream or None))
+
+    def conductivity_staged(self, fft, d_charges, d_moment, d_collective=0, d_self=0, stream=0):
+        self._check(lib().ta_conductivity_staged(self._h, int(fft), d_charges, d_moment, d_collective or None,
+                                                 d_self or None, stream or None))
 
     def timing_history(self, max_n=64):
         """[(total_ms, main_kernel_ms)] of the last compute calls, oldest first."""
@@ -681,3 +721,10 @@ class Group:
 
     def msd(self, fft, by_particle=False, out=None):
         return self._host(lib().ta_group_msd, by_particle, int(fft), out=out)
+
+    def conductivity(self, fft, charges, self_term=False, collective=True):
+        """As Context.conductivity, charges of all atoms; the members' moments and self lag sums are summed, then ONE
+        collective MSD runs (collective=False is not available here)."""
+        if not collective:
+            raise ValueError("a device group always evaluates the collective term")
+        return Context._conductivity(self, lib().ta_group_conductivity, fft, charges, self_term, True)

@@ -6,8 +6,8 @@ build in-memory trajectories with ``mda.Universe.empty(..., velocities=True)``
 (/root/reference/transport_analysis/tests/test_velocityautocorr.py:46-57).  It
 provides exactly what the hooks touch: ``atomgroup.universe.trajectory``,
 ``len(atomgroup)``, ``.velocities`` / ``.positions`` (fresh float32 copies),
-``.masses``, ``select_atoms("all" | "index i:j" | "index i")``, and per-frame ``ts.has_velocities``, ``ts.has_positions``,
-``ts.volume``, ``ts.frame``, ``ts.time``.
+``.masses``, ``.charges`` (when the universe has them), ``select_atoms("all" | "index i:j" | "index i")``, and
+per-frame ``ts.has_velocities``, ``ts.has_positions``, ``ts.volume``, ``ts.frame``, ``ts.time``.
 """
 from __future__ import annotations
 
@@ -122,6 +122,15 @@ class AtomGroup:
     def masses(self):
         return np.array(self.universe._masses[self.indices], dtype=np.float64)
 
+    @property
+    def charges(self):
+        """partial charges (e); a universe made without ``charges=`` has no such topology attribute"""
+        if self.universe._charges is None:
+            from ._base import NoDataError
+
+            raise NoDataError("This Universe does not contain charges information")
+        return np.array(self.universe._charges[self.indices], dtype=np.float64)
+
     def select_atoms(self, selection):
         """The atoms of this group that `selection` names: "all", or "index i:j" (inclusive, as in
         MDAnalysis) / "index i" on the universe's atom indices -- the subset of MDAnalysis' selection
@@ -142,10 +151,10 @@ class AtomGroup:
 
 
 class ArrayUniverse:
-    """``positions`` / ``velocities``: (n_frames, n_atoms, 3) arrays or None."""
+    """``positions`` / ``velocities``: (n_frames, n_atoms, 3) arrays or None; ``charges``: (n_atoms,) or None."""
 
     def __init__(self, positions=None, velocities=None, masses=None, dimensions=None, dt=1.0,
-                 n_atoms=None, n_frames=None):
+                 n_atoms=None, n_frames=None, charges=None):
         # like an MDAnalysis Timestep, the trajectory holds float32 coordinates: ts.velocities / ts.positions
         # and AtomGroup.velocities / .positions hand out the same values (no copy when float32 came in)
         if positions is not None:
@@ -161,6 +170,7 @@ class ArrayUniverse:
         self._n_atoms = ref.shape[1]
         self._masses = (np.ones(self._n_atoms) if masses is None
                         else np.asarray(masses, dtype=np.float64))
+        self._charges = None if charges is None else np.asarray(charges, dtype=np.float64)
         self.trajectory = MemoryTrajectory(positions, velocities, dimensions, dt)
         self.atoms = AtomGroup(self, np.arange(self._n_atoms))
 

@@ -1,0 +1,150 @@
+"""Einstein-Helfand ionic conductivity on MI355X, from positions.
+
+The transport-analysis reference has no conductivity class; this one follows its ``ViscosityHelfand`` in
+shape (constructor, ``run()``, a lag-index fit window).  Conductivity is a collective quantity: it is the
+mean squared displacement of ONE sum over all atoms, the translational dipole
+
+    M(t) = sum_n q_n (x_n(t) - x_n(0))
+
+and not a mean of per-particle series.  The pass over the position slab that forms M (and, for the
+Nernst-Einstein estimate, the weighted slab q (x - x[0])) runs in hand-written HIP (``k_cond_moment``
+behind ``ta_conductivity`` of ``include/ta_hip.h``); both MSDs run on the library's Einstein MSD paths.
+Positions only, like ``EinsteinMSD``: XTC / DCD trajectories qualify.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ._base import StagedAnalysis, UpdatingAtomGroup, parse_dim_type
+
+#: CODATA 2018 (exact SI values): elementary charge (C) and Boltzmann constant (J/K)
+ELEMENTARY_CHARGE = 1.602176634e-19
+BOLTZMANN_J_PER_K = 1.380649e-23
+
+
+class ConductivityHelfand(StagedAnalysis):
+    r"""Ionic conductivity by the Einstein-Helfand relation.
+
+    .. math:: \Phi(k) = \frac{1}{T - k} \sum_{i < T - k} \sum_d (M_{i+k, d} - M_{i, d})^2, \qquad
+              M_{t, d} = \sum_n q_n (x_{t, n, d} - x_{0, n, d})
+
+    summed over the dimensions of ``dim_type``; :math:`\sigma` = slope of :math:`\Phi` against lag time
+    / (2 D k_B <V> T_avg), with D the number of those dimensions.  In units:
+
+        sigma [S/m] = e^2 10^22 / k_B[J/K] * slope[e^2 A^2 / ps] / (2 D <V>[A^3] T_avg[K])
+
+    with CODATA e and k_B (e^2 A^2 / ps = e^2 10^-8 C^2 m^2 / s and A^3 = 10^-30 m^3).
+
+    Parameters
+    ----------
+    atomgroup : AtomGroup — positions should be unwrapped, as for ``EinsteinMSD``.
+    temp_avg : float — average temperature (K), default 300.
+    dim_type : {'xyz', 'xy', 'yz', 'xz', 'x', 'y', 'z'}
+    linear_fit_window : (int, int) or None — lag indices [lo, hi) of the slope fit.  The fit is against
+        lag time k * dt (ps; dt = the spacing of the analysed frames' times), not lag index.
+    fft : bool — ``True``: the Einstein MSD's FFT form for both MSDs (up to 64 frames the exact direct
+        kernel); ``False``: the direct forms.
+    charges : array, keyword-only — one charge (e) per atom of ``atomgroup``; default ``atomgroup.charges``
+        (a topology without charges raises MDAnalysis' missing-attribute error).
+    nernst_einstein : bool, keyword-only, default False — also compute the self term
+        sum_n q_n^2 MSD_n(k) (``results.timeseries_self``) and its conductivity: the Nernst-Einstein
+        estimate, whose ratio to ``results.conductivity`` is the Haven ratio.  Costs one more
+        slab-sized scratch on the device and an Einstein MSD lag-sum evaluation.
+    device, devices, distributed, stage_dtype : keyword-only — as for ``EinsteinMSD``.  Under
+        ``distributed=True`` every rank forms the moment and self term of its block of atoms; the moments
+        are summed over ranks BEFORE the collective MSD (the MSD of a sum is not the sum of the MSDs).
+
+    Attributes
+    ----------
+    results.moment : (n_frames, D) float64 — M (e A).
+    results.timeseries : (n_frames,) float64 — Phi (e^2 A^2), lag 0 exactly 0.
+    results.timeseries_self : (n_frames,) float64 or None — sum_n q_n^2 MSD_n (e^2 A^2).
+    results.conductivity, results.conductivity_self : S/m (only with ``linear_fit_window``).
+    """
+
+    _stage_arrays = ("positions",)
+    _no_data_message = ("Helfand conductivity computation requires "
+                        "positions and box volume in the trajectory")
+
+    def __init__(self, atomgroup, temp_avg=300.0, dim_type="xyz", linear_fit_window=None, fft=True, *,
+                 charges=None, nernst_einstein=False, **kwargs):
+        if isinstance(atomgroup, UpdatingAtomGroup):
+            raise TypeError("UpdatingAtomGroups are not valid for conductivity computation")
+        if kwargs.pop("by_particle", False):
+            raise TypeError("ConductivityHelfand has no per-particle result: conductivity is collective "
+                            "(by_particle=True is not supported)")
+        super().__init__(atomgroup, by_particle=False, **kwargs)
+
+        self.temp_avg = temp_avg
+        self.dim_type = dim_type.lower()
+        self._dim, self.dim_fac = parse_dim_type(self.dim_type)
+        self.linear_fit_window = linear_fit_window
+        self.fft = fft
+        self.nernst_einstein = bool(nernst_einstein)
+
+        self.atomgroup = self._group = atomgroup
+        self.n_particles = len(self.atomgroup)
+        q = atomgroup.charges if charges is None else charges
+        self.charges = np.asarray(q, dtype=np.float64).ravel()
+        if self.charges.size != self.n_particles:
+            raise ValueError(f"charges: {self.charges.size} values for {self.n_particles} atoms")
+
+    # see EinsteinMSD: atoms, not frames, are this path's parallel axis
+    _analysis_algorithm_is_parallelizable = False
+
+    @classmethod
+    def get_supported_backends(cls):
+        return ("serial",)
+
+    def _set_options(self, dtype):
+        self._ctx.set_option("stage_device_f32", 0)
+
+    def _prepare(self):
+        super()._prepare()
+        self._volumes = np.zeros(self.n_frames)
+        for key in ("conductivity", "conductivity_self"):  # a fit of an earlier run
+            self.results.pop(key, None)
+        self.results.moment = self.results.timeseries = self.results.timeseries_self = None
+
+    @staticmethod
+    def _has_data(ts):
+        return ts.has_positions and ts.volume != 0
+
+    def _single_frame(self):
+        super()._single_frame()
+        self._volumes[self._frame_index] = self._ts.volume
+
+    def _evaluate(self):
+        fft, want_self = bool(self.fft), self.nernst_einstein
+        if self._distributed:
+            from .dist import allreduce_sum
+
+            if self._n_local:
+                moment, _, self_ls = self._ctx.conductivity(fft, self.charges[self._lo:self._hi], self_term=want_self,
+                                                            collective=False)
+            else:  # more ranks than atoms: this rank contributes nothing
+                moment, self_ls = np.zeros((self.n_frames, self.dim_fac)), np.zeros(self.n_frames)
+            moment = allreduce_sum(moment, self._device)
+            self_ls = allreduce_sum(self_ls, self._device) if want_self else None
+            phi = self._ctx.moment_msd(moment, fft)
+        else:
+            moment, phi, self_ls = self._ctx.conductivity(fft, self.charges, self_term=want_self)
+        self.results.moment = moment
+        self.results.timeseries = phi
+        self.results.timeseries_self = self_ls
+        self._vol_avg = np.average(self._volumes)
+        if self.linear_fit_window is not None:
+            self.results.conductivity = self._sigma(phi)
+            if self_ls is not None:
+                self.results.conductivity_self = self._sigma(self_ls)
+
+    def lag_times(self):
+        """Lag times k * dt (ps) of the timeseries, dt the spacing of the analysed frames' times."""
+        dt = float(self.times[1] - self.times[0]) if self.n_frames > 1 else 0.0
+        return np.arange(self.n_frames) * dt
+
+    def _sigma(self, series):
+        lo, hi = self.linear_fit_window[0], self.linear_fit_window[1]
+        slope = np.polyfit(self.lag_times()[lo:hi], series[lo:hi], 1)[0]
+        return (ELEMENTARY_CHARGE ** 2 * 1e22 / BOLTZMANN_J_PER_K * slope
+                / (2 * self.dim_fac * self._vol_avg * self.temp_avg))

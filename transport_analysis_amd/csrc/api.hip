@@ -50,6 +50,9 @@ struct ta_ctx {
     DevBuf bp_scratch;  // atom-major by-particle results before the transposition
     DevBuf bp_spec;     // per-atom power spectra of one block of atoms (two-kernel by-particle path)
     DevBuf unit_counter;  // k_band_bp_vacf's work counter
+    // conductivity (cond_pm): the moment's partial sums, the weighted slab of the self term (the input's size), the
+    // charges and outputs of host-facing calls, the pair-major copy of the (n_frames, dim) moment
+    DevBuf cond_part, cond_w, cond_q, cond_out, cond_mpm;
     // staging: pinned host slabs keep the reference's (n_frames, n_atoms, dim) layout, the
     // device slabs are pair-major (layout.hip) with st_pitch rows per column pair
     int64_t st_T = 0, st_A = 0, st_pitch = 0;
@@ -792,6 +795,71 @@ int staged_entry(ta_ctx* ctx, int which, const double* d_masses, double scale, d
                       (hipStream_t)stream, true, ctx->st_dev_f32);
 }
 
+
+// ---- Einstein-Helfand conductivity (conductivity.hip) ---------------------------------------------------------------
+// Phi(k) of the (n_frames, dim) frame-major moment at d_moment: its pair-major copy is a one-atom slab, and its MSD lag
+// sum (msd_impl, the EinsteinMSD dispatch) is Phi.
+int cond_collective(ta_ctx* ctx, bool fft, const double* d_moment, int64_t T, int D, double* d_coll, hipStream_t st) {
+    int rc = ensure(ctx, ctx->cond_mpm, pm_bytes(T, D));
+    if (rc) return rc;
+    tl_mark(ctx, "k_relayout", st);
+    TA_HIP_TRY(ctx, launch_relayout(d_moment, false, D, D, T, ctx->cond_mpm.p, false, pm_pitch(T), 0, st));
+    return msd_impl(ctx, fft, (const double*)ctx->cond_mpm.p, pm_pitch(T), T, 1, D, d_coll, nullptr, 0, st);
+}
+
+// One conductivity call on a pair-major position slab, bracketed by the timing events: the moment pass (and with
+// d_self the weighted slab W = q (x - x[0])), the fixed-order sum of its partials into d_moment, then the self term =
+// the MSD lag sum of W (sum_n q_n^2 MSD_n: the MSD is invariant under the shift and |d(q x)|^2 = q^2 |dx|^2) and the
+// collective Phi of the moment, each by msd_impl.  d_coll / d_self NULL: skipped.  ev[1] / ev[2] bracket the moment
+// pass, unless an FFT evaluation after it records its own forward kernel there.
+int cond_pm(ta_ctx* ctx, bool fft, const void* pm_any, bool pm_f32, int64_t pitch, int64_t T, int64_t A, int D,
+            const double* d_q, double* d_moment, double* d_coll, double* d_self, hipStream_t st, bool record_start) {
+    int rc;
+    ctx->timing_valid = false;
+    if (record_start) {
+        ctx->ev = ctx->ring[ctx->n_calls % ta_ctx::kRing];
+        TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
+        tl_reset(ctx);
+    }
+    const int64_t n_cols = A * D;
+    const double* pm = (const double*)pm_any;
+    if (pm_f32) {  // float32 device slabs: a float64 copy first, as for every other evaluation but the float32 kernels
+        const size_t n_el = (size_t)((n_cols + 1) / 2) * (size_t)pitch * 2;
+        if ((rc = ensure(ctx, ctx->pm_in[0], n_el * sizeof(double)))) return rc;
+        tl_mark(ctx, "k_widen_f32", st);
+        TA_HIP_TRY(ctx, launch_widen_f32((const float*)pm_any, (double*)ctx->pm_in[0].p, (long)n_el, st));
+        pm = (const double*)ctx->pm_in[0].p;
+    }
+    const int n_parts = cond_moment_parts(ctx->n_cu, (long)T, (long)n_cols);
+    if ((rc = ensure(ctx, ctx->cond_part, sizeof(double) * (size_t)n_parts * T * D))) return rc;
+    double* W = nullptr;
+    if (d_self) {
+        if ((rc = ensure(ctx, ctx->cond_w, pm_bytes(T, n_cols)))) return rc;
+        W = (double*)ctx->cond_w.p;
+    }
+    tl_mark(ctx, "k_cond_moment", st);
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
+    TA_HIP_TRY(ctx, launch_cond_moment(pm, (long)pitch, (long)T, (long)n_cols, D, d_q, (double*)ctx->cond_part.p, n_parts,
+                                       W, st));
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
+    tl_mark(ctx, "k_sum_partials", st);
+    TA_HIP_TRY(ctx, launch_sum_partials((const double*)ctx->cond_part.p, n_parts, (long)(T * D), d_moment, st));
+    if (d_self && (rc = msd_impl(ctx, fft, W, pitch, T, A, D, d_self, nullptr, 0, st))) return rc;
+    if (d_coll && (rc = cond_collective(ctx, fft, d_moment, T, D, d_coll, st))) return rc;
+    tl_mark(ctx, "end", st);
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[3], st));
+    ctx->timing_valid = true;
+    ++ctx->n_calls;
+    return TA_OK;
+}
+
+int cond_args(ta_ctx* ctx, int fft, const void* charges, const void* moment) {
+    if (fft != 0 && fft != 1) return fail(ctx, TA_E_INVALID, "fft must be 0 or 1");
+    if (!charges) return fail(ctx, TA_E_INVALID, "charges are NULL");
+    if (!moment) return fail(ctx, TA_E_INVALID, "moment output is NULL");
+    return TA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -910,7 +978,8 @@ int ta_ctx_destroy(ta_ctx* ctx) {
     for (DevBuf* b : {&ctx->partial, &ctx->spec, &ctx->ts_partial, &ctx->out_lagsum, &ctx->out_bp,
                       &ctx->masses, &ctx->bounce, &ctx->stage_buf, &ctx->helf_p,
                       &ctx->helf_small, &ctx->pm_in[0], &ctx->pm_in[1], &ctx->bp_scratch, &ctx->bp_spec,
-                      &ctx->bounce2, &ctx->unit_counter})
+                      &ctx->bounce2, &ctx->unit_counter, &ctx->cond_part, &ctx->cond_w, &ctx->cond_q, &ctx->cond_out,
+                      &ctx->cond_mpm})
         if (b->p) hipFree(b->p);
     for (auto& q : ctx->ring)
         for (auto& ev : q)
@@ -938,7 +1007,7 @@ int ta_trim(ta_ctx* ctx) {
     hipDeviceSynchronize();
     for (DevBuf* b : {&ctx->partial, &ctx->spec, &ctx->ts_partial, &ctx->out_bp, &ctx->bounce, &ctx->bounce2, &ctx->stage_buf,
                       &ctx->helf_p, &ctx->helf_small, &ctx->pm_in[0], &ctx->pm_in[1],
-                      &ctx->bp_scratch, &ctx->bp_spec})
+                      &ctx->bp_scratch, &ctx->bp_spec, &ctx->cond_part, &ctx->cond_w, &ctx->cond_mpm})
         if (b->p) {
             hipFree(b->p);
             b->p = nullptr;
@@ -1461,6 +1530,43 @@ int ta_msd_staged(ta_ctx* ctx, int fft, double* d_lagsum, double* d_bp, int64_t 
     });
 }
 
+// Einstein-Helfand conductivity: slab 0 / d_pos holds the positions
+int ta_conductivity_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int fft,
+                        const double* d_charges, double* d_moment, double* d_collective, double* d_self_lagsum,
+                        void* stream) {
+    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    TA_NO_CPU(ctx);
+    int rc = check_shape(ctx, T, A, D, ld_row);
+    if (rc || (rc = cond_args(ctx, fft, d_charges, d_moment))) return rc;
+    if (!d_pos) return fail(ctx, TA_E_INVALID, "null device pointer");
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    ctx->timing_valid = false;
+    ctx->ev = ctx->ring[ctx->n_calls % ta_ctx::kRing];
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
+    tl_reset(ctx);
+    const double* px = nullptr;
+    if ((rc = relayout_input(ctx, 0, d_pos, T, A * D, ld_row, st, &px))) return rc;
+    return cond_pm(ctx, fft != 0, px, false, pm_pitch(T), T, A, D, d_charges, d_moment, d_collective, d_self_lagsum, st,
+                   false);
+    });
+}
+
+int ta_conductivity_staged(ta_ctx* ctx, int fft, const double* d_charges, double* d_moment, double* d_collective,
+                           double* d_self_lagsum, void* stream) {
+    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    TA_NO_CPU(ctx);
+    int rc = cond_args(ctx, fft, d_charges, d_moment);
+    if (rc) return rc;
+    if (ctx->st_nslabs < 1) return fail(ctx, TA_E_STATE, "slabs have not been staged");
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = order_after_staging(ctx, (hipStream_t)stream))) return rc;
+    return cond_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A, ctx->st_D,
+                   d_charges, d_moment, d_collective, d_self_lagsum, (hipStream_t)stream, true);
+    });
+}
+
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
     if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
@@ -1656,6 +1762,40 @@ int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, do
     return TA_OK;
 }
 
+// Conductivity share of a host-facing call, queued on ctx->stream and not waited for: charges (this context's atoms)
+// uploaded, the moment (and with self the self lag sum, with coll Phi) left on the device in *d_out: (T, D) moment,
+// then T values of Phi, then T of the self term.
+int cond_launch(ta_ctx* ctx, int fft, const double* h_q, bool coll, bool self, double** d_out) {
+    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    TA_NO_CPU(ctx);
+    if (ctx->st_nslabs < 1) return fail(ctx, TA_E_STATE, "slabs have not been staged");
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t T = ctx->st_T, A = ctx->st_A;
+    const int D = ctx->st_D;
+    int rc = ensure(ctx, ctx->cond_q, sizeof(double) * A);
+    if (rc || (rc = ensure(ctx, ctx->cond_out, sizeof(double) * (size_t)T * (D + 2)))) return rc;
+    double* out = (double*)ctx->cond_out.p;
+    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->cond_q.p, h_q, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = order_after_staging(ctx, ctx->stream))) return rc;
+    if ((rc = cond_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, T, A, D, (const double*)ctx->cond_q.p,
+                      out, coll ? out + T * D : nullptr, self ? out + T * (D + 1) : nullptr, ctx->stream, true)))
+        return rc;
+    *d_out = out;
+    return TA_OK;
+}
+
+// Phi of a host (T, D) moment on this context's device, blocking (the group's collective after its members' sums)
+int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T, int D, double* h_coll) {
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure(ctx, ctx->cond_out, sizeof(double) * (size_t)T * (D + 2));
+    if (rc) return rc;
+    double* out = (double*)ctx->cond_out.p;
+    TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_moment, sizeof(double) * T * D, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = cond_collective(ctx, fft != 0, out, T, D, out + T * D, ctx->stream))) return rc;
+    TA_HIP_TRY(ctx, hipMemcpyAsync(h_coll, out + T * D, sizeof(double) * T, hipMemcpyDeviceToHost, ctx->stream));
+    return host_wait(ctx);
+}
+
 int host_wait(ta_ctx* ctx) {
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     TA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1716,6 +1856,31 @@ int ta_helfand_msd(ta_ctx* ctx, const double* h_masses, double scale, double* h_
 int ta_msd(ta_ctx* ctx, int fft, double* h_ts, double* h_bp) {
     if (fft != 0 && fft != 1) return fail(ctx, TA_E_INVALID, "fft must be 0 or 1");
     return host_compute(ctx, fft ? W_MSD_FFT : W_MSD_DIRECT, nullptr, 1.0, h_ts, h_bp);
+}
+
+int ta_conductivity(ta_ctx* ctx, int fft, const double* h_charges, double* h_moment, double* h_collective,
+                    double* h_self_lagsum) {
+    return ta::guard([&](int c_, const std::string& m_) { if (ctx) (void)host_wait(ctx); return fail(ctx, c_, m_); }, [&]() -> int {
+    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    int rc = cond_args(ctx, fft, h_charges, h_moment);
+    if (rc) return rc;
+    if (ctx->st_nslabs < 1) return fail(ctx, TA_E_STATE, "slabs have not been staged");
+    if (ctx->is_cpu) {
+        if ((rc = ta::cpu::conductivity(ctx->cpu, fft != 0, h_charges, h_moment, h_collective, h_self_lagsum)))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    double* d_out = nullptr;
+    if ((rc = ta::cond_launch(ctx, fft, h_charges, h_collective != nullptr, h_self_lagsum != nullptr, &d_out))) return rc;
+    const int64_t T = ctx->st_T, D = ctx->st_D;
+    TA_HIP_TRY(ctx, hipMemcpyAsync(h_moment, d_out, sizeof(double) * T * D, hipMemcpyDeviceToHost, ctx->stream));
+    if (h_collective)
+        TA_HIP_TRY(ctx, hipMemcpyAsync(h_collective, d_out + T * D, sizeof(double) * T, hipMemcpyDeviceToHost, ctx->stream));
+    if (h_self_lagsum)
+        TA_HIP_TRY(ctx, hipMemcpyAsync(h_self_lagsum, d_out + T * (D + 1), sizeof(double) * T, hipMemcpyDeviceToHost,
+                                       ctx->stream));
+    return host_wait(ctx);
+    });
 }
 
 }  // extern "C"

@@ -19,6 +19,9 @@
 //                 fft = false difference first (the Helfand loop without masses and 1 / D), fft = true by the transforms
 //                 of the FFT VACF on P = x - x[0] and S1 - 2 S2 (P's autocorrelation, prefix sums of sum_d P^2), as on
 //                 the GPU (msd.hip).
+//   Conductivity  M[t, d] = sum_n q_n (x[t,n,d] - x[0,n,d]) (a frame per task, atoms in order); the collective MSD of M
+//                 and the self term sum_n q_n^2 MSD_n as the Einstein MSD of a one-atom slab holding M and of the
+//                 weighted slab q (x - x[0]).
 // timeseries[k] = sum over atoms (the caller divides by n_atoms, as for the GPU path).  Atoms are processed in
 // blocks of 8 by OpenMP threads; a block's lag sums are added in block order afterwards, so results do not depend on
 // the number of threads.
@@ -385,6 +388,50 @@ int msd(const State& s, bool fft, double* ts, double* bp) {
     if (fft) return s.dtype == TA_F32 ? vacf_fft_t<float>(s, ts, bp, true) : vacf_fft_t<double>(s, ts, bp, true);
     return s.dtype == TA_F32 ? direct_t<float>(s, false, nullptr, 1.0, ts, bp, true)
                              : direct_t<double>(s, false, nullptr, 1.0, ts, bp, true);
+}
+
+int conductivity(const State& s, bool fft, const double* q, double* moment, double* collective, double* self_lagsum) {
+    const int64_t T = s.T, A = s.A;
+    const int D = s.D;
+    std::vector<double> w;
+    if (self_lagsum) {
+        try {
+            w.assign((size_t)T * A * D, 0.0);
+        } catch (const std::bad_alloc&) {
+            return TA_E_NOMEM;
+        }
+    }
+    const void* slab = s.slabs[0];
+    const bool f32 = s.dtype == TA_F32;
+#pragma omp parallel for num_threads(s.threads) schedule(static)
+    for (int64_t t = 0; t < T; ++t) {
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (int64_t n = 0; n < A; ++n)
+            for (int d = 0; d < D; ++d) {
+                const size_t i0 = (size_t)n * D + d, i = (size_t)t * A * D + i0;
+                const double x = f32 ? elem<float>(slab, i) : elem<double>(slab, i);
+                const double x0 = f32 ? elem<float>(slab, i0) : elem<double>(slab, i0);
+                const double v = q[n] * (x - x0);
+                acc[d] += v;
+                if (self_lagsum) w[i] = v;
+            }
+        for (int d = 0; d < D; ++d) moment[(size_t)t * D + d] = acc[d];
+    }
+    int rc = TA_OK;
+    if (self_lagsum) {
+        State ws = s;
+        ws.dtype = TA_F64;
+        ws.slabs = {w.data()};
+        if ((rc = msd(ws, fft, self_lagsum, nullptr))) return rc;
+    }
+    if (collective) {
+        State ms = s;
+        ms.A = 1;
+        ms.dtype = TA_F64;
+        ms.slabs = {moment};
+        rc = msd(ms, fft, collective, nullptr);
+    }
+    return rc;
 }
 
 }  // namespace cpu

@@ -22,6 +22,9 @@ int vacf_direct(const State& s, double* timeseries, double* by_particle);
 int helfand(const State& s, const double* masses, double scale, double* timeseries, double* by_particle);
 // Einstein MSD of slab 0 (the positions): fft = true by transforms of x - x[0] (S1 - 2 S2), false difference first
 int msd(const State& s, bool fft, double* timeseries, double* by_particle);
+// Einstein-Helfand conductivity of slab 0: moment (n_frames, dim) = sum_n q_n (x - x[0]); collective (or NULL) = the MSD lag
+// sum of the moment; self_lagsum (or NULL) = sum_n q_n^2 MSD_n, both by msd() with the same fft
+int conductivity(const State& s, bool fft, const double* charges, double* moment, double* collective, double* self_lagsum);
 
 }  // namespace cpu
 }  // namespace ta

@@ -559,4 +559,67 @@ int ta_group_msd(ta_group* g, int fft, double* h_ts, double* h_bp) {
     return group_compute(g, fft ? 3 : 4, nullptr, 1.0, h_ts, h_bp);
 }
 
+
+// Conductivity: every member's moment (and self lag sum) of its atoms, added on the host in member order, then ONE
+// collective MSD of the summed moment on the first member that holds atoms (the MSD of a sum is not a sum of MSDs)
+int ta_group_conductivity(ta_group* g, int fft, const double* h_charges, double* h_moment, double* h_collective,
+                          double* h_self_lagsum) {
+    return ta::guard(
+        [&](int c_, const std::string& m_) {
+            if (g)
+                for (ta_ctx* c : g->ctx)
+                    if (c) (void)host_wait(c);
+            return gfail(g, c_, m_);
+        },
+        [&]() -> int {
+    if (!g) return gfail(nullptr, TA_E_INVALID, "null group");
+    if (fft != 0 && fft != 1) return gfail(g, TA_E_INVALID, "fft must be 0 or 1");
+    if (!h_charges || !h_moment || !h_collective) return gfail(g, TA_E_INVALID, "charges, moment or collective is NULL");
+    if (g->T == 0) return gfail(g, TA_E_STATE, "slabs have not been staged");
+    const int n = (int)g->ctx.size();
+    const int64_t T = g->T;
+    const int D = g->D;
+    std::vector<std::vector<double>> mom(n), slf(n);
+    std::vector<int> who;
+    int rc;
+    for (int i = 0; i < n; ++i) {
+        if (g->hi[i] == g->lo[i]) continue;
+        double* d = nullptr;
+        rc = cond_launch(g->ctx[i], fft, h_charges + g->lo[i], false, h_self_lagsum != nullptr, &d);
+        who.push_back(i);
+        if (rc) {
+            rc = mfail(g, i, rc);
+            drain_members(g, who);
+            return rc;
+        }
+        mom[i].resize((size_t)T * D);
+        hipError_t he = hipMemcpyAsync(mom[i].data(), d, sizeof(double) * T * D, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
+        if (he == hipSuccess && h_self_lagsum) {
+            slf[i].resize((size_t)T);
+            he = hipMemcpyAsync(slf[i].data(), d + T * (D + 1), sizeof(double) * T, hipMemcpyDeviceToHost,
+                                ctx_stream(g->ctx[i]));
+        }
+        if (he != hipSuccess) {
+            drain_members(g, who);
+            return gfail(g, TA_E_HIP, std::string("moment copy: ") + hipGetErrorString(he));
+        }
+    }
+    rc = TA_OK;
+    for (int i : who) {
+        const int r = host_wait(g->ctx[i]);
+        if (r && !rc) rc = mfail(g, i, r);
+    }
+    if (rc) return rc;
+    std::fill(h_moment, h_moment + T * D, 0.0);
+    if (h_self_lagsum) std::fill(h_self_lagsum, h_self_lagsum + T, 0.0);
+    for (int i : who) {
+        for (int64_t k = 0; k < T * D; ++k) h_moment[k] += mom[i][k];
+        if (h_self_lagsum)
+            for (int64_t k = 0; k < T; ++k) h_self_lagsum[k] += slf[i][k];
+    }
+    if ((rc = cond_collective_host(g->ctx[who[0]], fft, h_moment, T, D, h_collective))) return mfail(g, who[0], rc);
+    return TA_OK;
+        });
+}
+
 }  // extern "C"

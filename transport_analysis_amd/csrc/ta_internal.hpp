@@ -51,6 +51,11 @@ int guard(Report&& report, Body&& body) noexcept {
 int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, double* h_bp, int64_t ld_host,
                 double** d_total);
 int host_wait(ta_ctx* ctx);
+// api.hip, for group.hip: one context's conductivity share (ta_conductivity on its staged slab 0 with its atoms' charges
+// h_q), queued: *d_out = the (n_frames, dim) moment, then Phi (coll), then the self lag sum (self), valid after
+// host_wait; and Phi of a host (n_frames, dim) moment on the context's device, blocking
+int cond_launch(ta_ctx* ctx, int fft, const double* h_q, bool coll, bool self, double** d_out);
+int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T, int D, double* h_coll);
 hipStream_t ctx_stream(ta_ctx* ctx);
 int ctx_device(const ta_ctx* ctx);
 int64_t ctx_staged_frames(const ta_ctx* ctx);
@@ -144,6 +149,13 @@ hipError_t launch_msd_prepare(const double* pos, long pitch, long T, long n_cols
                               hipStream_t st);
 hipError_t launch_msd_prepare_bp(const double* pos, long pitch, long T, long n_atoms, int D, double* P, double* Ca,
                                  hipStream_t st);
+
+// conductivity.hip: the charge-weighted moment M[t, d] = sum_n q_n (x[t, n, d] - x[0, n, d]) of a float64 pair-major
+// slab as n_parts partial sums partial [n_parts][T][D] (written in full; k_sum_partials adds them in order), and with
+// W != NULL the weighted shifted slab W = q (x - x[0]) in the same layout (rows < T; an unpaired column's partner 0)
+int cond_moment_parts(int n_cu, long T, long n_cols);
+hipError_t launch_cond_moment(const double* pos, long pitch, long T, long n_cols, int D, const double* q, double* partial,
+                              int n_parts, double* W, hipStream_t st);
 
 hipError_t launch_widen_f32(const float* in, double* out, long n, hipStream_t st);
 

@@ -130,3 +130,16 @@ def allreduce_mean_over_atoms(ts_local, n_local, n_atoms_total, device=None):
         lagsum = lagsum.to(torch.device("cuda", device if device is not None else torch.cuda.current_device()))
     out = reduce_lagsum(lagsum, n_atoms_total)
     return out.cpu().numpy()
+
+
+def allreduce_sum(local, device=None):
+    """The element-wise sum over ranks of a small float64 array (RCCL when the group's backend is nccl, gloo on CPU):
+    for quantities that add up over atoms but are not lag sums to be averaged -- the conductivity's (n_frames, dim)
+    charge-weighted moment, whose MSD is taken only after the sum, and its self term."""
+    import torch
+    import torch.distributed as dist
+
+    t = torch.from_numpy(np.array(local, dtype=np.float64))
+    if dist.get_backend() == "nccl":
+        t = t.to(torch.device("cuda", device if device is not None else torch.cuda.current_device()))
+    return reduce_lagsum(t, 1).cpu().numpy()
