@@ -25,6 +25,9 @@ Parity pinning
 
 from __future__ import annotations
 
+import os
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 
 # MDAnalysis.units.constants["Boltzmann_constant"], kJ/(mol K).  Pinned to 12
@@ -177,6 +180,101 @@ def helfand_fit(timeseries, fit_window):
     lagtimes = np.arange(1, n_frames)
     s, e = fit_window[0], fit_window[1]
     return np.polyfit(lagtimes[s:e], timeseries[s:e], 1)[0]
+
+
+# --------------------------------------------------------------------------
+# Einstein MSD and Einstein-Helfand conductivity at chosen lags
+# --------------------------------------------------------------------------
+# Direct float64 forms (differences first, no FFT identity) that evaluate only
+# the lags asked for, so trajectories of thousands of frames and atoms can be
+# checked at the lags where the kernels change tile, block or plan.  One lag
+# is one vectorised pass; lags run on a few threads (NumPy releases the GIL
+# inside its loops).  tests/test_oracle.py ties them to the all-lag
+# restatements of tests/test_msd.py and tests/test_conductivity.py.
+def _lag_threads():
+    return max(1, min(8, os.cpu_count() or 1))
+
+
+def _per_lag(fn, lags, n_out):
+    lags = [int(k) for k in lags]
+    out = np.zeros((len(lags), n_out))
+    chunks = [range(i, len(lags), _lag_threads()) for i in range(_lag_threads())]
+
+    def work(idx):
+        for i in idx:
+            if lags[i] > 0:
+                out[i] = fn(lags[i])
+
+    with ThreadPoolExecutor(len(chunks)) as ex:
+        list(ex.map(work, chunks))
+    return out
+
+
+def msd_at_lags(x, lags):
+    """(len(lags), n_atoms): 1/(T-k) sum_{t<T-k} |x[t+k] - x[t]|^2 per atom for
+    each lag k of `lags` (0 <= k < T; lag 0 is 0).  x: (T, n_atoms, D).  The lag
+    sum of EinsteinMSD is ``.sum(axis=1)``."""
+    x = np.asarray(x, dtype=np.float64)
+    T = x.shape[0]
+    if any(not 0 <= int(k) < T for k in lags):
+        raise ValueError("lags must lie in [0, n_frames)")
+
+    def one(k):
+        d = x[k:] - x[:-k]
+        return np.einsum("tad,tad->a", d, d) / (T - k)
+
+    return _per_lag(one, lags, x.shape[1])
+
+
+def cond_moment(x, q, atom_block=64):
+    """M[t, d] = sum_n q_n (x[t, n, d] - x[0, n, d]), summed over atoms in
+    np.longdouble, and the scale S[t, d] = sum_n |q_n| |x[t, n, d] - x[0, n, d]|
+    that bounds the rounding of any float64 order of that sum (with mixed
+    signs M can be far below its terms).  Returns (M, S), both float64."""
+    x = np.asarray(x, dtype=np.float64)
+    q = np.asarray(q, dtype=np.float64)
+    T, A, D = x.shape
+    m = np.zeros((T, D), dtype=np.longdouble)
+    s = np.zeros((T, D))
+    for lo in range(0, A, atom_block):
+        dx = x[:, lo:lo + atom_block] - x[0, lo:lo + atom_block]
+        qb = q[lo:lo + atom_block, None]
+        m += (dx.astype(np.longdouble) * qb.astype(np.longdouble)).sum(axis=1)
+        s += (np.abs(dx) * np.abs(qb)).sum(axis=1)
+    return m.astype(np.float64), s
+
+
+def moment_msd(M):
+    """Phi(k) = 1/(T-k) sum_{i<T-k} |M[i+k] - M[i]|^2 of a (T, D) series at
+    every lag (Phi(0) = 0)."""
+    M = np.asarray(M, dtype=np.float64)
+    if M.ndim == 1:
+        M = M[:, None]
+    T = M.shape[0]
+    out = np.zeros(T)
+    for k in range(1, T):
+        d = M[k:] - M[:-k]
+        out[k] = np.einsum("td,td->", d, d) / (T - k)
+    return out
+
+
+def self_term_at_lags(x, q, lags):
+    """Nernst-Einstein self term sum_n q_n^2 MSD_n(k) at `lags`."""
+    q = np.asarray(q, dtype=np.float64)
+    return msd_at_lags(x, lags) @ (q * q)
+
+
+def lag_sample(T):
+    """Sorted lags of a T-frame series where the kernels change tile, block or
+    plan: 0 ... 64, both sides of every 64- and 1024-frame boundary below T, a
+    stride of about 1/64 of T, and the last 64 lags."""
+    T = int(T)
+    lags = set(range(min(65, T)))
+    for b in range(64, T, 64):
+        lags.update((b - 1, b))
+    lags.update(range(0, T, max(1, T // 64)))
+    lags.update(range(max(0, T - 64), T))
+    return np.array(sorted(k for k in lags if 0 <= k < T), dtype=np.int64)
 
 
 # --------------------------------------------------------------------------
