@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_unwrap / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -206,6 +206,25 @@ int ta_msd(ta_ctx *ctx, int fft, double *h_timeseries, double *h_by_particle);
 int ta_conductivity(ta_ctx *ctx, int fft, const double *h_charges, double *h_moment, double *h_collective,
                     double *h_self_lagsum);
 
+/* ---- periodic unwrapping of a staged position slab ---------------------------------------------------------------
+ * ta_unwrap: undo periodic wrapping of staging slab `slab` in place (MDAnalysis' NoJump), over the staged frames
+ * in order.  h_dimensions: (n_frames, 6) float64 rows [a, b, c, alpha, beta, gamma] (A, degrees; ts.dimensions).
+ * axes: `dim` entries, the box axis (0 = x, 1 = y, 2 = z) of each staged column d of an atom.
+ * Non-orthogonal frames need axes == {0, 1, 2}; lengths <= 0 / non-finite, NULL pointers, bad axes -> TA_E_INVALID;
+ * no slab -> TA_E_STATE.
+ *   H(t) = the box vectors of frame t as rows (MDAnalysis' triclinic_vectors, float64), f(t) = x(t) H(t)^-1,
+ *   n(0) = 0, n(t) = n(t-1) + rint(f(t) - f(t-1)) (an integer 3-vector per atom, round-half-even),
+ *   x_u(t) = x(t) - n(t) H(t)
+ * Frame 0 keeps its bits; a particle that moves more than half a box between two staged frames cannot be unwrapped (not
+ * detected).  A box that changes from frame to frame (NPT) is followed, as by NoJump.  Works on slabs filled by
+ * ta_stage_commit, ta_stage_commit_dev or ta_stage_synth: one in-place pass over the float64 device slab (unwrap.hip:
+ * k_unwrap_ortho when every frame is orthogonal, else k_unwrap_tric), after the queued commits, blocking; recorded as a
+ * compute call (ta_timing_history; the kernel is the main kernel, ta_kernel_timeline: box_copy, k_unwrap_*).  Float32
+ * device slabs ("stage_device_f32"): TA_E_UNSUPPORTED.  CPU backend: the same arithmetic on the host slab, written back in
+ * its element type (a TA_F32 slab holds the unwrapped positions rounded to float32, as NoJump's own output).
+ * ta_group_unwrap (below, with the device groups): every member's block, with the same boxes.                       */
+int ta_unwrap(ta_ctx *ctx, int slab, const double *h_dimensions, const int *axes);
+
 /* ---- compute on caller-provided device memory (asynchronous) -----------
  * Same arithmetic as above on a device-resident FRAME-MAJOR shard: d_vel / d_pos are
  * (n_frames, n_atoms, dim) float64 with row stride ld_row elements between
@@ -302,6 +321,8 @@ int ta_group_msd(ta_group *g, int fft, double *h_timeseries, double *h_by_partic
  * atoms.  h_collective is required here.                                                                             */
 int ta_group_conductivity(ta_group *g, int fft, const double *h_charges, double *h_moment, double *h_collective,
                           double *h_self_lagsum);
+/* ta_group_unwrap: ta_unwrap on every member's block of slab `slab` (declared with ta_unwrap above) */
+int ta_group_unwrap(ta_group *g, int slab, const double *h_dimensions, const int *axes); /* every member's block */
 
 /* ---- instrumentation ----------------------------------------------------
  * Device time of the last *_dev / host-facing compute call on this context,

@@ -12,6 +12,8 @@ per frame ``_single_frame`` (with ``_frame_index``, ``_ts``, ``frames``,
 """
 from __future__ import annotations
 
+import warnings
+
 import numpy as np
 
 try:  # pragma: no cover - exercised only where MDAnalysis exists
@@ -235,7 +237,10 @@ class StagedAnalysis(AnalysisBase):
     ``self.dim_fac``, names its by-particle result, gives the frame check of ``_has_data`` and
     implements ``_set_options`` (context options, set before the slabs are allocated) and
     ``_evaluate`` (one ``_run_kernels`` call with its host and staged entry points); its own keywords
-    it pops in ``_pop_options``.
+    it pops in ``_pop_options``.  A subclass that stages ``positions`` may set ``self._unwrap``: the
+    frame loop then records every frame's ``ts.dimensions`` and ``_conclude`` unwraps the position slab
+    on the device (MDAnalysis' ``NoJump``, ``ta_unwrap``) after the last commit and before ``_evaluate``,
+    on every placement (each rank or device member unwraps its own atoms: no communication).
 
     No method here may take a name of MDAnalysis' ``AnalysisBase`` hooks: from 2.8 on its ``run()``
     calls ``self._compute(indexed_frames, ...)``, so ``_compute`` is theirs."""
@@ -243,6 +248,7 @@ class StagedAnalysis(AnalysisBase):
     _stage_arrays = ()          # Timestep arrays staged, in slab order
     _by_particle_key = None     # results.<key>: the (n_frames, n_particles) array or None
     _no_data_message = None     # NoDataError text of a frame _has_data rejects
+    _unwrap = False             # unwrap the staged positions (NoJump) before _evaluate
 
     def __init__(self, group, **kwargs):
         self._want_by_particle = bool(kwargs.pop("by_particle", True))
@@ -307,6 +313,8 @@ class StagedAnalysis(AnalysisBase):
             setattr(self.results, self._by_particle_key, None)
         # the (n_frames, n_particles) result array lives in pinned host memory, page-locked on a
         # helper thread while the frames are staged
+        # unwrap: the box of every analysed frame, (n_frames, 6) = ts.dimensions
+        self._boxes = np.zeros((self.n_frames, 6)) if self._unwrap else None
         self._bp_home = None
         if self._want_by_particle and self._n_local and not self._rccl:
             self._bp_home = self._ctx.result_home((self.n_frames, self._n_local))
@@ -317,6 +325,8 @@ class StagedAnalysis(AnalysisBase):
         if not self._has_data(ts):
             raise NoDataError(self._no_data_message)
         i = self._frame_index
+        if self._boxes is not None:
+            self._boxes[i] = self._unwrap_box(ts)
         if self._n_local:
             for slab, attr in self._fills:
                 if not stage_frame_native(self._ctx, slab, i, ts, attr, self._dim, self._rows):
@@ -327,10 +337,32 @@ class StagedAnalysis(AnalysisBase):
             self._ctx.stage_commit(self._committed, i + 1)
             self._committed = i + 1
 
+    def _unwrap_box(self, ts):
+        """ts.dimensions as unwrapping needs it, or the ValueError of a box it cannot use."""
+        dims = ts.dimensions
+        if dims is None:
+            raise ValueError(f"unwrap=True needs the periodic box, and frame {ts.frame} has none (ts.dimensions is None)")
+        d = np.asarray(dims, dtype=np.float64).ravel()
+        if d.shape != (6,) or not np.all(np.isfinite(d)) or not np.all(d[:3] > 0):
+            raise ValueError(f"unwrap=True needs box lengths > 0: frame {ts.frame} has dimensions {list(d)}")
+        if self.dim_fac != 3 and not np.all(d[3:] == 90.0):
+            raise ValueError(f"unwrap=True with a non-orthogonal box (frame {ts.frame}: angles {list(d[3:])}) needs "
+                             "all three dimensions ('xyz'): a triclinic image shift mixes the axes")
+        return d
+
     def _conclude(self):
         if self._committed < self.n_frames:
             self._ctx.stage_commit(self._committed, self.n_frames)
             self._committed = self.n_frames
+        if self._boxes is not None:
+            frames = np.asarray(self.frames)
+            if frames.size > 1 and np.any(np.diff(frames) != 1):
+                warnings.warn("unwrap=True over frames that are not consecutive (step > 1 or a frames= list): the "
+                              "positions are unwrapped over the analysed frames only, and a particle that moves more "
+                              "than half a box between two of them is not unwrapped correctly", UserWarning,
+                              stacklevel=3)
+            if self._n_local or self._devices is not None:
+                self._ctx.unwrap(self._stage_arrays.index("positions"), self._boxes, self._dim)
         self._evaluate()
 
     def _run_kernels(self, host, launch):

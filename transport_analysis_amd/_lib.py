@@ -34,6 +34,7 @@ EXPORTS = (
     "ta_group_helfand_msd",
     "ta_msd", "ta_msd_dev", "ta_msd_staged", "ta_group_msd",
     "ta_conductivity", "ta_conductivity_dev", "ta_conductivity_staged", "ta_group_conductivity",
+    "ta_unwrap", "ta_group_unwrap",
 )
 
 
@@ -160,6 +161,8 @@ def lib():
     L.ta_conductivity_dev.argtypes = [vp, vp, i64, i64, ci, i64, ci, vp, vp, vp, vp, vp]
     L.ta_conductivity_staged.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.ta_group_conductivity.argtypes = [vp, ci, vp, vp, vp, vp]
+    L.ta_unwrap.argtypes = [vp, ci, vp, vp]
+    L.ta_group_unwrap.argtypes = [vp, ci, vp, vp]
     for name in EXPORTS:
         if name not in ("ta_last_error", "ta_group_last_error", "ta_group_reduce_kind", "ta_group_reduce_note"):
             getattr(L, name).restype = ci
@@ -314,6 +317,15 @@ class _PlainHome:
 
     def get(self):
         return np.empty(self._shape, dtype=np.float64)
+
+
+def _unwrap(owner, fn, slab, dimensions, axes):
+    T = (getattr(owner, "shape", None) or (None,))[0]
+    dims = np.ascontiguousarray(dimensions, dtype=np.float64)
+    if T is not None and dims.shape != (T, 6):
+        raise ValueError(f"dimensions: shape {dims.shape}, expected ({T}, 6) (one box per staged frame)")
+    ax = np.ascontiguousarray(axes, dtype=np.int32).ravel()
+    owner._check(fn(owner._h, int(slab), _ptr(dims), _ptr(ax)))
 
 
 class Context:
@@ -484,6 +496,12 @@ class Context:
         view[:, 0, :] = moment
         self.stage_commit(0, T)
         return self.conductivity(fft, np.ones(1))[1]
+
+    def unwrap(self, slab, dimensions, axes):
+        """Undo periodic wrapping of staged slab `slab` in place (MDAnalysis' NoJump, ta_unwrap): `dimensions` the
+        (n_frames, 6) boxes [a, b, c, alpha, beta, gamma] of the staged frames, `axes` the box axis (0, 1, 2) of each
+        staged column of an atom."""
+        return _unwrap(self, lib().ta_unwrap, slab, dimensions, axes)
 
     # -- device-pointer compute (asynchronous) --------------------------
     def vacf_fft_dev(self, d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp=0, ld_bp=0, stream=0):
@@ -721,6 +739,10 @@ class Group:
 
     def msd(self, fft, by_particle=False, out=None):
         return self._host(lib().ta_group_msd, by_particle, int(fft), out=out)
+
+    def unwrap(self, slab, dimensions, axes):
+        """As Context.unwrap, on every member's block of the slab."""
+        return _unwrap(self, lib().ta_group_unwrap, slab, dimensions, axes)
 
     def conductivity(self, fft, charges, self_term=False, collective=True):
         """As Context.conductivity, charges of all atoms; the members' moments and self lag sums are summed, then ONE

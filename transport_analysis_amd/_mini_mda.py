@@ -7,7 +7,7 @@ build in-memory trajectories with ``mda.Universe.empty(..., velocities=True)``
 provides exactly what the hooks touch: ``atomgroup.universe.trajectory``,
 ``len(atomgroup)``, ``.velocities`` / ``.positions`` (fresh float32 copies),
 ``.masses``, ``.charges`` (when the universe has them), ``select_atoms("all" | "index i:j" | "index i")``, and
-per-frame ``ts.has_velocities``, ``ts.has_positions``, ``ts.volume``, ``ts.frame``, ``ts.time``.
+per-frame ``ts.has_velocities``, ``ts.has_positions``, ``ts.dimensions``, ``ts.volume``, ``ts.frame``, ``ts.time``.
 """
 from __future__ import annotations
 
@@ -38,21 +38,31 @@ class Timestep:
 
     @property
     def dimensions(self):
-        return self._traj.dimensions
+        """[a, b, c, alpha, beta, gamma] of this frame (a per-frame table's row), or None without a box"""
+        d = self._traj.dimensions
+        if d is not None and self._traj.per_frame_box:
+            return d[self.frame]
+        return d
 
     @property
     def volume(self):
-        d = self._traj.dimensions
+        d = self.dimensions
         if d is None:
             return 0.0
-        return float(d[0] * d[1] * d[2])  # orthorhombic boxes only
+        if d[3] == 90 and d[4] == 90 and d[5] == 90:
+            return float(d[0] * d[1] * d[2])
+        # a triclinic box: the determinant of MDAnalysis' triclinic_vectors, a b c sqrt(1 - sum cos^2 + 2 prod cos)
+        ca, cb, cg = (np.cos(np.deg2rad(float(x))) for x in d[3:6])
+        return float(d[0] * d[1] * d[2] * np.sqrt(1.0 - ca * ca - cb * cb - cg * cg + 2.0 * ca * cb * cg))
 
 
 class MemoryTrajectory:
     def __init__(self, positions, velocities, dimensions, dt, time_offset=0.0):
         self._pos = positions
         self._vel = velocities
-        self.dimensions = dimensions
+        # one box for every frame, or an (n_frames, 6) table of per-frame boxes (NPT)
+        self.per_frame_box = dimensions is not None and np.ndim(dimensions) == 2
+        self.dimensions = np.asarray(dimensions, dtype=np.float64) if self.per_frame_box else dimensions
         self.dt = dt
         self.time_offset = time_offset
         ref = positions if positions is not None else velocities
@@ -151,7 +161,9 @@ class AtomGroup:
 
 
 class ArrayUniverse:
-    """``positions`` / ``velocities``: (n_frames, n_atoms, 3) arrays or None; ``charges``: (n_atoms,) or None."""
+    """``positions`` / ``velocities``: (n_frames, n_atoms, 3) arrays or None; ``charges``: (n_atoms,) or None;
+    ``dimensions``: one box [a, b, c, alpha, beta, gamma] for every frame, an (n_frames, 6) array of per-frame boxes,
+    or None."""
 
     def __init__(self, positions=None, velocities=None, masses=None, dimensions=None, dt=1.0,
                  n_atoms=None, n_frames=None, charges=None):

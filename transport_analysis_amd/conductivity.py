@@ -37,7 +37,8 @@ class ConductivityHelfand(StagedAnalysis):
 
     Parameters
     ----------
-    atomgroup : AtomGroup — positions should be unwrapped, as for ``EinsteinMSD``.
+    atomgroup : AtomGroup — positions must be unwrapped for a meaningful moment: pass ``unwrap=True`` for a
+        trajectory written wrapped into the box, or unwrap beforehand (MDAnalysis' ``NoJump``).
     temp_avg : float — average temperature (K), default 300.
     dim_type : {'xyz', 'xy', 'yz', 'xz', 'x', 'y', 'z'}
     linear_fit_window : (int, int) or None — lag indices [lo, hi) of the slope fit.  The fit is against
@@ -50,6 +51,12 @@ class ConductivityHelfand(StagedAnalysis):
         sum_n q_n^2 MSD_n(k) (``results.timeseries_self``) and its conductivity: the Nernst-Einstein
         estimate, whose ratio to ``results.conductivity`` is the Haven ratio.  Costs one more
         slab-sized scratch on the device and an Einstein MSD lag-sum evaluation.
+    unwrap : bool, keyword-only, default False — ``True``: undo the periodic wrapping of the staged positions on
+        the device before the moment is formed, as MDAnalysis' ``NoJump`` does (see ``EinsteinMSD``: one
+        crossing of the box would otherwise add q L to M).  Every analysed frame needs a box with lengths > 0, a
+        non-orthogonal box needs ``dim_type='xyz'`` (else ``ValueError``), non-consecutive analysed frames give a
+        ``UserWarning``; a particle that moves more than half a box between two analysed frames is not unwrapped
+        correctly (not detected).  Under ``distributed=True`` every rank unwraps its own atoms.
     device, devices, distributed, stage_dtype : keyword-only — as for ``EinsteinMSD``.  Under
         ``distributed=True`` every rank forms the moment and self term of its block of atoms; the moments
         are summed over ranks BEFORE the collective MSD (the MSD of a sum is not the sum of the MSDs).
@@ -67,13 +74,14 @@ class ConductivityHelfand(StagedAnalysis):
                         "positions and box volume in the trajectory")
 
     def __init__(self, atomgroup, temp_avg=300.0, dim_type="xyz", linear_fit_window=None, fft=True, *,
-                 charges=None, nernst_einstein=False, **kwargs):
+                 charges=None, nernst_einstein=False, unwrap=False, **kwargs):
         if isinstance(atomgroup, UpdatingAtomGroup):
             raise TypeError("UpdatingAtomGroups are not valid for conductivity computation")
         if kwargs.pop("by_particle", False):
             raise TypeError("ConductivityHelfand has no per-particle result: conductivity is collective "
                             "(by_particle=True is not supported)")
         super().__init__(atomgroup, by_particle=False, **kwargs)
+        self._unwrap = self.unwrap = bool(unwrap)
 
         self.temp_avg = temp_avg
         self.dim_type = dim_type.lower()

@@ -20,6 +20,7 @@
 #include "cpu_backend.hpp"
 #include "direct_kernels.hpp"
 #include "ta_internal.hpp"
+#include "unwrap_box.hpp"
 
 using namespace ta;
 
@@ -53,6 +54,7 @@ struct ta_ctx {
     // conductivity (cond_pm): the moment's partial sums, the weighted slab of the self term (the input's size), the
     // charges and outputs of host-facing calls, the pair-major copy of the (n_frames, dim) moment
     DevBuf cond_part, cond_w, cond_q, cond_out, cond_mpm;
+    DevBuf unwrap_box;  // ta_unwrap: the box table (unwrap_box.hpp) of the last call
     // staging: pinned host slabs keep the reference's (n_frames, n_atoms, dim) layout, the
     // device slabs are pair-major (layout.hip) with st_pitch rows per column pair
     int64_t st_T = 0, st_A = 0, st_pitch = 0;
@@ -979,7 +981,7 @@ int ta_ctx_destroy(ta_ctx* ctx) {
                       &ctx->masses, &ctx->bounce, &ctx->stage_buf, &ctx->helf_p,
                       &ctx->helf_small, &ctx->pm_in[0], &ctx->pm_in[1], &ctx->bp_scratch, &ctx->bp_spec,
                       &ctx->bounce2, &ctx->unit_counter, &ctx->cond_part, &ctx->cond_w, &ctx->cond_q, &ctx->cond_out,
-                      &ctx->cond_mpm})
+                      &ctx->cond_mpm, &ctx->unwrap_box})
         if (b->p) hipFree(b->p);
     for (auto& q : ctx->ring)
         for (auto& ev : q)
@@ -1007,7 +1009,7 @@ int ta_trim(ta_ctx* ctx) {
     hipDeviceSynchronize();
     for (DevBuf* b : {&ctx->partial, &ctx->spec, &ctx->ts_partial, &ctx->out_bp, &ctx->bounce, &ctx->bounce2, &ctx->stage_buf,
                       &ctx->helf_p, &ctx->helf_small, &ctx->pm_in[0], &ctx->pm_in[1],
-                      &ctx->bp_scratch, &ctx->bp_spec, &ctx->cond_part, &ctx->cond_w, &ctx->cond_mpm})
+                      &ctx->bp_scratch, &ctx->bp_spec, &ctx->cond_part, &ctx->cond_w, &ctx->cond_mpm, &ctx->unwrap_box})
         if (b->p) {
             hipFree(b->p);
             b->p = nullptr;
@@ -1796,6 +1798,34 @@ int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T
     return host_wait(ctx);
 }
 
+// One context's unwrap of staged slab `slab` (ta_unwrap, ta_group_unwrap), queued on ctx->stream behind the queued commits
+// and bracketed by the timing events: the box table's copy (box.tab must stay valid until host_wait), then the kernel
+int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes) {
+    if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
+    if (ctx->st_dev_f32) return fail(ctx, TA_E_UNSUPPORTED, "unwrap: float64 device slabs only (stage_device_f32 is on)");
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = order_after_staging(ctx, ctx->stream);
+    if (rc) return rc;
+    const size_t bytes = box.tab.size() * sizeof(double);
+    if ((rc = ensure(ctx, ctx->unwrap_box, bytes))) return rc;
+    hipStream_t st = ctx->stream;
+    ctx->timing_valid = false;
+    ctx->ev = ctx->ring[ctx->n_calls % ta_ctx::kRing];
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
+    tl_reset(ctx);
+    tl_mark(ctx, "box_copy", st);
+    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->unwrap_box.p, box.tab.data(), bytes, hipMemcpyHostToDevice, st));
+    tl_mark(ctx, box.triclinic ? "k_unwrap_tric" : "k_unwrap_ortho", st);
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
+    TA_HIP_TRY(ctx, launch_unwrap(ctx->d_slabs[slab], (long)ctx->st_pitch, (long)ctx->st_T, (long)ctx->st_A, ctx->st_D, axes,
+                                  box.triclinic, box.per_frame, (const double*)ctx->unwrap_box.p, (long)box.tpitch, st));
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
+    tl_mark(ctx, "end", st);
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[3], st));
+    ctx->timing_valid = true;
+    ++ctx->n_calls;
+    return TA_OK;
+}
 int host_wait(ta_ctx* ctx) {
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     TA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1879,6 +1909,25 @@ int ta_conductivity(ta_ctx* ctx, int fft, const double* h_charges, double* h_mom
     if (h_self_lagsum)
         TA_HIP_TRY(ctx, hipMemcpyAsync(h_self_lagsum, d_out + T * (D + 1), sizeof(double) * T, hipMemcpyDeviceToHost,
                                        ctx->stream));
+    return host_wait(ctx);
+    });
+}
+
+int ta_unwrap(ta_ctx* ctx, int slab, const double* h_dimensions, const int* axes) {
+    return ta::guard([&](int c_, const std::string& m_) { if (ctx && !ctx->is_cpu) (void)host_wait(ctx); return fail(ctx, c_, m_); }, [&]() -> int {
+    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    if (!h_dimensions || !axes) return fail(ctx, TA_E_INVALID, "dimensions or axes are NULL");
+    if (ctx->st_nslabs < 1) return fail(ctx, TA_E_STATE, "slabs have not been staged");
+    if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
+    BoxTable box;
+    const std::string why = box_table(h_dimensions, ctx->st_T, ctx->st_D, axes, 256, &box);
+    if (!why.empty()) return fail(ctx, TA_E_INVALID, "unwrap: " + why);
+    if (ctx->is_cpu) {
+        ta::cpu::unwrap(ctx->cpu, slab, box, axes);
+        return TA_OK;
+    }
+    int rc = unwrap_launch(ctx, slab, box, axes);
+    if (rc) return rc;
     return host_wait(ctx);
     });
 }

@@ -19,6 +19,9 @@
 //                 fft = false difference first (the Helfand loop without masses and 1 / D), fft = true by the transforms
 //                 of the FFT VACF on P = x - x[0] and S1 - 2 S2 (P's autocorrelation, prefix sums of sum_d P^2), as on
 //                 the GPU (msd.hip).
+//   Unwrap        MDAnalysis' NoJump in place (unwrap.hip's arithmetic): per atom, a walk along time carrying the integer
+//                 image counts n(t) = n(t-1) + rint(f(t) - f(t-1)), f = x H^-1, and writing x - n H (rounded to the slab's
+//                 element type: a float32 slab holds float32 positions, as NoJump writes them).
 //   Conductivity  M[t, d] = sum_n q_n (x[t,n,d] - x[0,n,d]) (a frame per task, atoms in order); the collective MSD of M
 //                 and the self term sum_n q_n^2 MSD_n as the Einstein MSD of a one-atom slab holding M and of the
 //                 weighted slab q (x - x[0]).
@@ -36,6 +39,7 @@
 
 #include "../../include/ta_hip.h"
 #include "cpu_backend.hpp"
+#include "unwrap_box.hpp"
 
 namespace ta {
 namespace cpu {
@@ -432,6 +436,48 @@ int conductivity(const State& s, bool fft, const double* q, double* moment, doub
         rc = msd(ms, fft, collective, nullptr);
     }
     return rc;
+}
+
+template <class E>
+void unwrap_t(const State& s, int slab, const BoxTable& box, const int* axes) {
+    const int64_t T = s.T, A = s.A, tp = box.per_frame ? box.tpitch : 0;
+    const int D = s.D;
+    E* p = static_cast<E*>(s.slabs[slab]);
+    const double* tab = box.tab.data();
+    auto at = [&](int row, int64_t t) { return tab[row * box.tpitch + (tp ? t : 0)]; };
+#pragma omp parallel for num_threads(s.threads) schedule(static)
+    for (int64_t a = 0; a < A; ++a) {
+        double prev[3] = {0.0, 0.0, 0.0};
+        int n[3] = {0, 0, 0};
+        for (int64_t t = 0; t < T; ++t) {
+            E* row = p + ((size_t)t * A + a) * D;
+            double x[3] = {0.0, 0.0, 0.0}, f[3];
+            for (int d = 0; d < D; ++d) x[d] = (double)row[d];
+            if (box.triclinic) {
+                f[0] = x[0] * at(6, t) + x[1] * at(7, t) + x[2] * at(9, t);
+                f[1] = x[1] * at(8, t) + x[2] * at(10, t);
+                f[2] = x[2] * at(11, t);
+            } else {
+                for (int d = 0; d < D; ++d) f[d] = x[d] * at(6 + diag_row(axes[d]), t);
+            }
+            if (t)
+                for (int d = 0; d < D; ++d) n[d] += (int)std::nearbyint(f[d] - prev[d]);  // (round-half-even)
+            for (int d = 0; d < D; ++d) prev[d] = f[d];
+            if (box.triclinic) {
+                const double n0 = n[0], n1 = n[1], n2 = n[2];
+                row[0] = (E)(x[0] - (n0 * at(0, t) + n1 * at(1, t) + n2 * at(3, t)));
+                row[1] = (E)(x[1] - (n1 * at(2, t) + n2 * at(4, t)));
+                row[2] = (E)(x[2] - n2 * at(5, t));
+            } else {
+                for (int d = 0; d < D; ++d) row[d] = (E)(x[d] - (double)n[d] * at(diag_row(axes[d]), t));
+            }
+        }
+    }
+}
+
+void unwrap(const State& s, int slab, const BoxTable& box, const int* axes) {
+    if (s.dtype == TA_F32) unwrap_t<float>(s, slab, box, axes);
+    else unwrap_t<double>(s, slab, box, axes);
 }
 
 }  // namespace cpu

@@ -4,6 +4,7 @@
 #include <vector>
 
 namespace ta {
+struct BoxTable;  // unwrap_box.hpp
 namespace cpu {
 
 struct State {
@@ -25,6 +26,8 @@ int msd(const State& s, bool fft, double* timeseries, double* by_particle);
 // Einstein-Helfand conductivity of slab 0: moment (n_frames, dim) = sum_n q_n (x - x[0]); collective (or NULL) = the MSD lag
 // sum of the moment; self_lagsum (or NULL) = sum_n q_n^2 MSD_n, both by msd() with the same fft
 int conductivity(const State& s, bool fft, const double* charges, double* moment, double* collective, double* self_lagsum);
+// ta_unwrap on host slab `slab` in place (box, axes checked by the caller)
+void unwrap(const State& s, int slab, const BoxTable& box, const int* axes);
 
 }  // namespace cpu
 }  // namespace ta

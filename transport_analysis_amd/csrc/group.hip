@@ -48,6 +48,7 @@ const char* ncclGetErrorString(ncclResult_t result);
 
 #include "../../include/ta_hip.h"
 #include "ta_internal.hpp"
+#include "unwrap_box.hpp"
 
 using namespace ta;
 
@@ -619,6 +620,41 @@ int ta_group_conductivity(ta_group* g, int fft, const double* h_charges, double*
     }
     if ((rc = cond_collective_host(g->ctx[who[0]], fft, h_moment, T, D, h_collective))) return mfail(g, who[0], rc);
     return TA_OK;
+        });
+}
+
+// Unwrap: every member's block of slab `slab` with the same box table, queued on all devices, then waited for
+int ta_group_unwrap(ta_group* g, int slab, const double* h_dimensions, const int* axes) {
+    std::vector<int> who;
+    return ta::guard(
+        [&](int c_, const std::string& m_) {
+            if (g) drain_members(g, who);
+            return gfail(g, c_, m_);
+        },
+        [&]() -> int {
+    if (!g) return gfail(nullptr, TA_E_INVALID, "null group");
+    if (!h_dimensions || !axes) return gfail(g, TA_E_INVALID, "dimensions or axes are NULL");
+    if (g->T == 0) return gfail(g, TA_E_STATE, "slabs have not been staged");
+    if (slab < 0 || slab >= g->n_slabs) return gfail(g, TA_E_INVALID, "no such slab");
+    BoxTable box;
+    const std::string why = box_table(h_dimensions, g->T, g->D, axes, 256, &box);
+    if (!why.empty()) return gfail(g, TA_E_INVALID, "unwrap: " + why);
+    for (int i = 0; i < (int)g->ctx.size(); ++i) {
+        if (g->hi[i] == g->lo[i]) continue;
+        const int rc = unwrap_launch(g->ctx[i], slab, box, axes);
+        if (rc) {
+            const int r = mfail(g, i, rc);
+            drain_members(g, who);
+            return r;
+        }
+        who.push_back(i);
+    }
+    int rc = TA_OK;
+    for (int i : who) {
+        const int r = host_wait(g->ctx[i]);
+        if (r && !rc) rc = mfail(g, i, r);
+    }
+    return rc;
         });
 }
 

@@ -15,6 +15,8 @@ struct ta_ctx;
 
 namespace ta {
 
+struct BoxTable;  // unwrap_box.hpp
+
 // No exception leaves an extern "C" function (every call returns an int status).  Every entry point's
 // body runs inside guard(report, body): std::bad_alloc becomes TA_E_NOMEM, anything else TA_E_HIP, the message goes
 // through `report(code, text)` -- the file's fail / gfail, which records it for ta_last_error and returns the code
@@ -56,6 +58,8 @@ int host_wait(ta_ctx* ctx);
 // host_wait; and Phi of a host (n_frames, dim) moment on the context's device, blocking
 int cond_launch(ta_ctx* ctx, int fft, const double* h_q, bool coll, bool self, double** d_out);
 int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T, int D, double* h_coll);
+// api.hip, for group.hip: one context's ta_unwrap queued on its stream (box.tab must stay valid until host_wait)
+int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes);
 hipStream_t ctx_stream(ta_ctx* ctx);
 int ctx_device(const ta_ctx* ctx);
 int64_t ctx_staged_frames(const ta_ctx* ctx);
@@ -156,6 +160,11 @@ hipError_t launch_msd_prepare_bp(const double* pos, long pitch, long T, long n_a
 int cond_moment_parts(int n_cu, long T, long n_cols);
 hipError_t launch_cond_moment(const double* pos, long pitch, long T, long n_cols, int D, const double* q, double* partial,
                               int n_parts, double* W, hipStream_t st);
+
+// unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
+// box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)
+hipError_t launch_unwrap(double* slab, long pitch, long T, long n_atoms, int D, const int* axes, bool triclinic,
+                         bool per_frame, const double* d_tab, long tpitch, hipStream_t st);
 
 hipError_t launch_widen_f32(const float* in, double* out, long n, hipStream_t st);
 

@@ -25,7 +25,8 @@ class EinsteinMSD(StagedAnalysis):
     Parameters
     ----------
     u : Universe or AtomGroup
-        Positions should be unwrapped (MDAnalysis' ``NoJump`` / ``unwrap``), as for MDAnalysis.
+        Positions must be unwrapped for a meaningful MSD: pass ``unwrap=True`` for a trajectory written
+        wrapped into the box, or unwrap beforehand (MDAnalysis' ``NoJump``).
     select : str
         Selection applied to ``u`` (``u.select_atoms(select)``).
     msd_type : {'xyz', 'xy', 'yz', 'xz', 'x', 'y', 'z'}
@@ -35,6 +36,16 @@ class EinsteinMSD(StagedAnalysis):
         first frame; up to 64 frames the exact direct kernel); ``False``: the direct form.
     by_particle : bool, keyword-only, default True
         ``False`` skips ``results.msds_by_particle`` (then ``None``) and computes the lag sums only.
+    unwrap : bool, keyword-only, default False
+        ``True``: undo the periodic wrapping of the staged positions on the device before the MSD, as
+        MDAnalysis' ``NoJump`` does (``ta_unwrap``: image counts from the jumps of the fractional
+        coordinates between consecutive analysed frames, an exact integer prefix sum along time; frame 0
+        is kept as it is; a box that changes from frame to frame is followed).  Every analysed frame needs
+        a box (``ts.dimensions``) with lengths > 0, else ``ValueError``; a non-orthogonal box needs
+        ``msd_type='xyz'``, else ``ValueError``.  Analysed frames that are not consecutive (``step > 1``,
+        ``frames=``) give a ``UserWarning`` and are unwrapped over the analysed frames.  A particle that moves
+        more than half a box between two analysed frames cannot be unwrapped (not detected).  ``False``
+        (default): the positions are used as they are.
     device, devices, distributed, stage_dtype : keyword-only
         As for ``VelocityAutocorr``: a GPU index or ``"cpu"`` (the opt-in C++/OpenMP backend),
         several GPUs behind one object, or one process per GPU under ``torch.distributed``
@@ -44,23 +55,25 @@ class EinsteinMSD(StagedAnalysis):
     ----------
     results.timeseries : (n_frames,) float64 — MSD averaged over particles (Å^2).
     results.msds_by_particle : (n_frames, n_particles) float64 or None
-    ag, n_particles, fft, msd_type, dim_fac, select
+    ag, n_particles, fft, msd_type, dim_fac, select, unwrap
     """
 
     _stage_arrays = ("positions",)
     _by_particle_key = "msds_by_particle"
     _no_data_message = "MSD computation requires positions in the trajectory"
 
-    def __init__(self, u, select="all", msd_type="xyz", fft=True, **kwargs):
+    def __init__(self, u, select="all", msd_type="xyz", fft=True, *, unwrap=False, **kwargs):
         if isinstance(u, UpdatingAtomGroup):
             raise TypeError("UpdatingAtomGroups are not valid for MSD computation")
         super().__init__(u, **kwargs)
+        self._unwrap = bool(unwrap)
 
         self.u = u
         self.msd_type = msd_type
         self._parse_msd_type()
         self.select = select
         self.fft = fft
+        self.unwrap = self._unwrap
         self.ag = self._group = u.select_atoms(self.select)
         self.n_particles = len(self.ag)
         self.results.msds_by_particle = None
