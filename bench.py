@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: FFT-VACF lag-points/s on synthetic random velocities.
 
-    python bench.py [--gpus N --steps K --warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N --steps K --warmup W] [--scaling weak|strong] [--full]
+
+A plain run does what the headline figure needs and nothing else: it stages the input, runs W warm-up
+steps and times K steps, writes --dump-outputs, and prints the line (`value`, `ms_per_step`, and the
+`roofline` of the timed steps' own kernel events).  `--full` adds what takes work of its own: the input
+check, the clock probe, the per-kernel split, `other_configs`, `staging`, the host paths and
+`cpu_baseline` (the --no-* options leave single parts of a --full run out).
 
 N > 1 runs one rank per GPU (RCCL): either the driver starts the ranks,
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -89,6 +95,10 @@ def parse():
                          "float64 arithmetic")
     ap.add_argument("--helfand-fft", action="store_true",
                     help="--mode helfand: the O(T log T) option (lag sums as S1 - 2 S2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the input check, the clock probe, the per-kernel split, the "
+                         "other configs, the staging and host paths and the CPU baseline (the --no-* options below "
+                         "leave single parts out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--no-host-path", action="store_true")
@@ -113,6 +123,10 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: nothing after the timed steps but --dump-outputs and the line
+        for extra in ("no_cpu_baseline", "no_other_configs", "no_host_path", "no_check", "no_kernel_split",
+                      "no_clock_probe"):
+            setattr(args, extra, True)
     return args
 
 

@@ -160,7 +160,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(scaling):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "2000", "--atoms", "3000",
-           "--scaling", scaling]
+           "--scaling", scaling, "--full"]
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -189,7 +189,7 @@ def test_bench_bare_gpus_2_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["TA_BENCH_ONE_GPU"] = "1"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--frames", "2000", "--atoms", "3000", "--cpu-sample-atoms", "200"]
+           "--frames", "2000", "--atoms", "3000", "--cpu-sample-atoms", "200", "--full"]
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -221,7 +221,7 @@ def test_bench_one_rank_under_rccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
            "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "2000", "--atoms", "3000",
-           "--no-cpu-baseline", "--no-other-configs", "--no-host-path"]
+           "--full", "--no-cpu-baseline", "--no-other-configs", "--no-host-path"]
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -230,6 +230,38 @@ def test_bench_one_rank_under_rccl():
     assert d["config"]["collective"]["backend"] == "nccl" and d["config"]["collective"]["ranks"] == 1
     assert len(d["config"]["rank_devices"]) == 1
     assert d["reduce_us"] > 0 and d["check"]["max_scale_rel_err_vs_torch_lags"] < 1e-10
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_rest(tmp_path):
+    """A plain `bench.py` run prints the headline line from the timed steps alone: no input check, clock probe,
+    per-kernel split or CPU baseline.  `--full` adds them, and both runs time and dump the same steps."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+            "--frames", "2000", "--atoms", "3000"]
+    lines = {}
+    for run, extra in (("plain", []), ("full", ["--full", "--no-other-configs", "--no-host-path",
+                                                "--cpu-sample-atoms", "200"])):
+        cmd = base + ["--dump-outputs", str(tmp_path / run)] + extra
+        res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        out = [ln for ln in res.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert len(out) == 1, res.stdout[-2000:]
+        lines[run] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f64"
+        assert d["value"] == pytest.approx(2000 * 3000 / (d["ms_per_step"] * 1e-3), rel=1e-9)
+        assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1
+    assert plain["check"] == {} and "kernels" not in plain["roofline"] and "clock_probe" not in plain["device_ms"]
+    assert not {"cpu_baseline", "other_configs", "staging", "host_path", "summary"} & plain.keys()
+    assert full["check"]["generator_bit_exact_vs_numpy"] and full["check"]["max_scale_rel_err_vs_torch_lags"] < 1e-10
+    assert full["roofline"]["kernels"] and "clock_probe" in full["device_ms"] and full["cpu_baseline"]["value"] > 0
+    assert np.array_equal(np.load(tmp_path / "plain" / "timeseries.npy"), np.load(tmp_path / "full" / "timeseries.npy"))
 
 
 GROUP_DRIVER = r"""
@@ -428,7 +460,8 @@ def test_bench_single_process_line_is_complete():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--single-process", "--gpus", "2", "--devices", "0,0",
-           "--steps", "2", "--warmup", "1", "--frames", "2000", "--atoms", "3000", "--cpu-sample-atoms", "200"]
+           "--steps", "2", "--warmup", "1", "--frames", "2000", "--atoms", "3000", "--cpu-sample-atoms", "200",
+           "--full"]
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
