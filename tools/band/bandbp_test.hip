@@ -254,6 +254,9 @@ static int check_one(int T, long A, int D, int nwg) {
     CK(hipDeviceSynchronize());
     std::vector<double> got((size_t)A * pitch);
     CK(hipMemcpy(got.data(), out, got.size() * 8, hipMemcpyDeviceToHost));
+    for (long a = 0; a < A; ++a)  // the lags two units share arrive undivided (the library divides them in k_bp_transpose)
+        for (int k = 0; k < T; ++k)
+            if (k % 256 >= 241) got[a * pitch + k] /= (double)(T - k);
     double worst = 0;
     long wa = -1;
     int wk = -1;

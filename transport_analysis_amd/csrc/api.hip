@@ -339,7 +339,8 @@ int direct_impl(ta_ctx* ctx, int mode, const void* d_vel, const void* d_pos,
                                                 (unsigned long long*)ctx->unit_counter.p, st));
             TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
             tl_mark(ctx, "k_bp_transpose", st);
-            TA_HIP_TRY(ctx, launch_bp_transpose((const double*)ctx->bp_scratch.p, Tp, A, T, d_bp, ld_bp, (double*)ctx->ts_partial.p, st));
+            TA_HIP_TRY(ctx, launch_bp_transpose((const double*)ctx->bp_scratch.p, Tp, A, T, d_bp, ld_bp, (double*)ctx->ts_partial.p, st,
+                                                true));
             tl_mark(ctx, "k_sum_partials", st);
             TA_HIP_TRY(ctx, launch_sum_partials((const double*)ctx->ts_partial.p, (int)n_tiles, T, d_lagsum, st));
             return TA_OK;

@@ -218,14 +218,14 @@ __global__ void __launch_bounds__(64 * NW)
                 if (d < 15 || e == 0) {
                     if (e >= 1) s += dsum[(d + 1) * 32 + e - 16 + 15];
                     out[lag] = s / (double)(T - lag);
-                } else {  // the other half is the next unit's first block lag
-                    unsafeAtomicAdd(out + lag, s / (double)(T - lag));
-                }
+                } else {  // the other half is the next unit's first block lag: the SUM, divided once by k_bp_transpose
+                    unsafeAtomicAdd(out + lag, s);  // (the halves' products may cancel: dividing each first would
+                }                                   //  leave u sum |v v| / (T - k) of rounding, not a few ulps)
             }
         }
         if (g > 0 && lane >= 1 && lane < 16) {  // ... and this unit's first block lag completes the previous unit's last 15 lags
             const long lag = 256L * g - 16 + lane;
-            if (lag < T) unsafeAtomicAdd(out + lag, dsum[lane - 16 + 15] / (double)(T - lag));
+            if (lag < T) unsafeAtomicAdd(out + lag, dsum[lane - 16 + 15]);
         }
         TA_LDS_ORDER();
     }

@@ -157,11 +157,16 @@ __global__ void __launch_bounds__(256)
 // stores); the caller's array is (n_frames, ld_bp) like results.vacf_by_particle
 // (velocityautocorr.py:145-147).  64 x 64 tiles through LDS, both sides coalesced; with
 // `partial` the tile also adds its 64 atoms per lag: partial[tile_a][lag] (the mean over atoms,
-// velocityautocorr.py:214, summed over tiles in a fixed order afterwards).
+// velocityautocorr.py:214, summed over tiles in a fixed order afterwards).  split_div: the lags 256 g + 241 ... 256 g + 255
+// arrive as undivided sums (k_band_bp_vacf: two units add their halves there) and are divided by T - lag here, once.
+__device__ __forceinline__ double split_lag_div(double v, long lag, long T) {
+    return lag % 256 >= 241 && lag < T ? v / (double)(T - lag) : v;
+}
+
 template <bool WIDE>
 __global__ void __launch_bounds__(256)
     k_bp_transpose(const double* __restrict__ src, long src_ld, long n_atoms, long T,
-                   double* __restrict__ bp, long ld_bp, double* __restrict__ partial) {
+                   double* __restrict__ bp, long ld_bp, double* __restrict__ partial, int split_div) {
     __shared__ double tile[64][65];
     const int tid = threadIdx.x;
     const long a0 = (long)blockIdx.x * 64, t0 = (long)blockIdx.y * 64;
@@ -177,6 +182,7 @@ __global__ void __launch_bounds__(256)
                 const double* p = src + (a0 + a) * src_ld + t0 + t;
                 if (t0 + t + 1 < T) v = *reinterpret_cast<const double2*>(p);
                 else if (t0 + t < T) v.x = p[0];
+                if (split_div) v = double2{split_lag_div(v.x, t0 + t, T), split_lag_div(v.y, t0 + t + 1, T)};
             }
             tile[a][t] = v.x;
             tile[a][t + 1] = v.y;
@@ -197,6 +203,7 @@ __global__ void __launch_bounds__(256)
             const int a = i * 4 + (tid >> 6), t = tid & 63;
             double v = 0.0;
             if (a0 + a < n_atoms && t0 + t < T) v = src[(a0 + a) * src_ld + t0 + t];
+            if (split_div) v = split_lag_div(v, t0 + t, T);
             tile[a][t] = v;
         }
         __syncthreads();
@@ -303,14 +310,16 @@ hipError_t launch_unlayout(const void* pm, bool pm_f32, long pitch, long n_cols,
 }
 
 hipError_t launch_bp_transpose(const double* src, long src_ld, long n_atoms, long T, double* bp, long ld_bp,
-                               double* partial, hipStream_t st) {
+                               double* partial, hipStream_t st, bool split_div) {
     if (T <= 0 || n_atoms <= 0) return hipSuccess;
     const dim3 grid((unsigned)((n_atoms + 63) / 64), (unsigned)((T + 63) / 64));
     const bool wide = src_ld % 2 == 0 && ld_bp % 2 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)bp & 15) == 0;
     if (wide)
-        hipLaunchKernelGGL(k_bp_transpose<true>, grid, dim3(256), 0, st, src, src_ld, n_atoms, T, bp, ld_bp, partial);
+        hipLaunchKernelGGL(k_bp_transpose<true>, grid, dim3(256), 0, st, src, src_ld, n_atoms, T, bp, ld_bp, partial,
+                           (int)split_div);
     else
-        hipLaunchKernelGGL(k_bp_transpose<false>, grid, dim3(256), 0, st, src, src_ld, n_atoms, T, bp, ld_bp, partial);
+        hipLaunchKernelGGL(k_bp_transpose<false>, grid, dim3(256), 0, st, src, src_ld, n_atoms, T, bp, ld_bp, partial,
+                           (int)split_div);
     return hipGetLastError();
 }
 

@@ -174,9 +174,10 @@ hipError_t launch_relayout(const void* src, bool src_f32, long ld_row, long n_co
                            void* dst, bool dst_f32, long pitch, long t_dst0, hipStream_t st);
 hipError_t launch_unlayout(const void* pm, bool pm_f32, long pitch, long n_cols, long t_count, double* dst,
                            long ld_row, hipStream_t st);
-// atom-major by-particle scratch -> (n_frames, ld_bp); partial: [ceil(n_atoms/64)][T] or NULL
+// atom-major by-particle scratch -> (n_frames, ld_bp); partial: [ceil(n_atoms/64)][T] or NULL; split_div: the lags
+// 256 g + 241 ... 256 g + 255 hold undivided sums (k_band_bp_vacf), divided by T - lag on the way
 hipError_t launch_bp_transpose(const double* src, long src_ld, long n_atoms, long T, double* bp, long ld_bp,
-                               double* partial, hipStream_t st);
+                               double* partial, hipStream_t st, bool split_div = false);
 hipError_t launch_synth(void* pm, bool pm_f32, long pitch, long n_cols, long T, unsigned long long seed,
                         long col_offset, long n_cols_total, hipStream_t st);
 
