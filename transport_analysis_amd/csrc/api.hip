@@ -225,9 +225,93 @@ int check_shape(ta_ctx* ctx, int64_t T, int64_t A, int D, int64_t ld_row) {
     return TA_OK;
 }
 
+// ---- the brackets every timed call is made of -----------------------------------------------------------------------
+// A compute call owns one event quadruple of the ring: call_begin records ev[0] and empties the timeline, call_end records
+// ev[3] and counts the call (on success only: a call that failed leaves timing_valid false).  The *_dev entries open the
+// bracket before their relayout, everyone else right before compute_pm / cond_pm, which close it.
+int call_begin(ta_ctx* ctx, hipStream_t st) {
+    ctx->timing_valid = false;
+    ctx->ev = ctx->ring[ctx->n_calls % ta_ctx::kRing];
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
+    tl_reset(ctx);
+    return TA_OK;
+}
+int call_end(ta_ctx* ctx, hipStream_t st) {
+    tl_mark(ctx, "end", st);
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[3], st));
+    ctx->timing_valid = true;
+    ++ctx->n_calls;
+    return TA_OK;
+}
+
+// one launch under its timeline name ...
+#define TA_LAUNCH(ctx, name, st, launch)                                                                                  \
+    do {                                                                                                                  \
+        tl_mark(ctx, name, st);                                                                                           \
+        TA_HIP_TRY(ctx, launch);                                                                                          \
+    } while (0)
+// ... and the call's main kernel: ev[1] / ev[2] around it are what ta_last_timing reports as the main kernel's time
+#define TA_LAUNCH_MAIN(ctx, name, st, launch)                                                                             \
+    do {                                                                                                                  \
+        tl_mark(ctx, name, st);                                                                                           \
+        TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));                                                                  \
+        TA_HIP_TRY(ctx, launch);                                                                                          \
+        TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));                                                                  \
+    } while (0)
+
+// The by-particle tail of every form whose kernel leaves atom-major lags in bp_scratch (pitch pm_pitch(T)): the
+// transposition into the caller's (n_frames, ld_bp) array, which also adds up its 64 atoms per lag into a row of ts_partial
+// (both ensured by the caller), then the sum of those tile rows.  halves: the kernel's units add undivided halves of a
+// lag, the transposition divides once (k_band_bp_vacf).
+int bp_tail(ta_ctx* ctx, int64_t T, int64_t A, double* d_lagsum, double* d_bp, int64_t ld_bp, hipStream_t st,
+            bool halves = false) {
+    const int64_t Tp = pm_pitch(T), n_tiles = (A + 63) / 64;
+    TA_LAUNCH(ctx, "k_bp_transpose", st,
+              launch_bp_transpose((const double*)ctx->bp_scratch.p, Tp, A, T, d_bp, ld_bp, (double*)ctx->ts_partial.p, st,
+                                  halves));
+    TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->ts_partial.p, (int)n_tiles, T, d_lagsum, st));
+    return TA_OK;
+}
+
+// ---- the O(T^2) forms --------------------------------------------------------------------------------------------------
+// Which kernel evaluates a direct request.  "direct_mfma": 1 = by trajectory length (the default), 3 = the matrix cores
+// always, 0 = the vector kernel always (the parity tests' second opinion); 0 / 3 leave k_short and k_mid aside too.
+// (The column-packed forms of rounds 4-5 -- "direct_mfma" 2, inline-assembly LDS-DMA -- live under tools/band/ since round 6.)
+enum Form { F_SHORT, F_MID, F_BAND_VACF64, F_BAND_HELF64, F_BAND_HELF32, F_VECTOR };
+
+// the float32 option: products and block sums in float32 (float64 accumulation); the Einstein MSD stays float64
+bool direct_f32(const ta_ctx* ctx, int mode) { return ctx->opt_direct_f32 != 0 && mode != MODE_MSD; }
+
 // Short trajectories (short_kernels.hpp): a lane per column, every lag in its registers; the by-particle array is written in
 // place, the lag sums leave as one row per wave
 bool short_applies(const ta_ctx* ctx, int64_t T) { return T <= ctx->opt_short_max && T <= short_max_frames(); }
+
+// src_f32: the slabs hold float32 elements; it only comes with the float32 option (compute_pm)
+Form direct_form(const ta_ctx* ctx, int mode, int64_t T, bool src_f32 = false) {
+    const int mf = (int)ctx->opt_direct_mfma;
+    const bool f32 = direct_f32(ctx, mode), f64 = !f32 && !src_f32;
+    if (f64 && mf == 1 && short_applies(ctx, T)) return F_SHORT;
+    // k_mid where it wins (profiles/r06_direct_mid_sweep.txt): the windowed VACF from 97 to 512 frames (9.4 against 16.5 ms per
+    // 12 GB at 128 frames with the by-particle array, 21.9 against 25.8 at 512), Helfand from 97 to 128 (18 against 23);
+    // "mid_max" 0: never; "mid_all" 1: wherever the kernel can run (65 ... 512 frames, both quantities: the parity tests).
+    // The Einstein MSD (no product stage) from 65 to 512 frames: 14 - 38 ms against the vector kernel's 21 - 44 per 12 GB
+    // with the by-particle array, within 8 % where it loses (160 frames; tools/sweep_msd.py, DESIGN.md section 4.7)
+    if (f64 && mf == 1 && T > 64 && T <= ctx->opt_mid_max && T <= mid_max_frames() &&
+        (ctx->opt_mid_all || mode == MODE_MSD || (T >= 97 && (mode == MODE_VACF || T <= 128))))
+        return F_MID;
+    // The O(T^2) correlators run on the matrix cores wherever that wins: FP64 (bandbp_kernels.hpp) and, for the float32
+    // option's Helfand forms, FP32 (band32tp_kernels.hpp: P rounded once to float32 like the float32 vector kernel's staged
+    // values, float32 products, float64 accumulation) -- the k-slots of the MFMA filled from the time axis.  These kernels
+    // pay a ring fill and an epilogue per particle (block) and lag group; the vector kernel, whose column groups are 8 - 32
+    // lanes under ~640 frames, wins the windowed VACF up to 512 frames, Helfand float64 up to 351, float32 up to 447
+    // (profiles/r06_direct_mid_sweep.txt, 12 GB of input at every length).
+    auto time_packed = [&](int64_t from_frames) { return mf == 3 || (mf == 1 && T >= from_frames); };
+    if (T >= ((int64_t)1 << 24)) return F_VECTOR;
+    if (f32 && mode == MODE_HELFAND && time_packed(448)) return F_BAND_HELF32;
+    if (f64 && mode == MODE_VACF && time_packed(513)) return F_BAND_VACF64;
+    if (f64 && mode == MODE_HELFAND && time_packed(352)) return F_BAND_HELF64;
+    return F_VECTOR;
+}
 
 int short_impl(ta_ctx* ctx, int mode, const double* d_vel, const double* d_pos, const double* d_masses, int64_t T, int64_t A,
                int D, int64_t pitch, double scale, double* d_lagsum, double* d_bp, int64_t ld_bp, hipStream_t st) {
@@ -235,13 +319,10 @@ int short_impl(ta_ctx* ctx, int mode, const double* d_vel, const double* d_pos, 
     const int rows = nwg * short_waves();
     int rc = ensure(ctx, ctx->ts_partial, sizeof(double) * (size_t)rows * T);
     if (rc) return rc;
-    tl_mark(ctx, "k_short", st);
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-    TA_HIP_TRY(ctx, launch_short(mode, nwg, d_vel, d_pos, d_masses, pitch, (int)T, A, D,
-                                 mode == MODE_HELFAND ? scale / (double)D : 1.0, d_bp, ld_bp, (double*)ctx->ts_partial.p, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-    tl_mark(ctx, "k_sum_partials", st);
-    TA_HIP_TRY(ctx, launch_sum_partials((const double*)ctx->ts_partial.p, rows, T, d_lagsum, st));
+    TA_LAUNCH_MAIN(ctx, "k_short", st,
+                   launch_short(mode, nwg, d_vel, d_pos, d_masses, pitch, (int)T, A, D, mode == MODE_HELFAND ? scale / (double)D : 1.0,
+                                d_bp, ld_bp, (double*)ctx->ts_partial.p, st));
+    TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->ts_partial.p, rows, T, d_lagsum, st));
     return TA_OK;
 }
 
@@ -251,172 +332,99 @@ int mid_impl(ta_ctx* ctx, int mode, const double* d_vel, const double* d_pos, co
     const int nwg = mid_grid(ctx->n_cu, mode, (int)T, A, D, (int)ctx->opt_mid_ncl);
     int rc = ensure(ctx, ctx->ts_partial, sizeof(double) * (size_t)nwg * T);
     if (rc) return rc;
-    tl_mark(ctx, "k_mid", st);
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-    TA_HIP_TRY(ctx, launch_mid(mode, nwg, d_vel, d_pos, d_masses, pitch, (int)T, A, D, mode == MODE_HELFAND ? scale / (double)D : 1.0,
-                               d_bp, ld_bp, (double*)ctx->ts_partial.p, (int)ctx->opt_mid_ncl, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-    tl_mark(ctx, "k_sum_partials", st);
-    TA_HIP_TRY(ctx, launch_sum_partials((const double*)ctx->ts_partial.p, nwg, T, d_lagsum, st));
+    TA_LAUNCH_MAIN(ctx, "k_mid", st,
+                   launch_mid(mode, nwg, d_vel, d_pos, d_masses, pitch, (int)T, A, D, mode == MODE_HELFAND ? scale / (double)D : 1.0,
+                              d_bp, ld_bp, (double*)ctx->ts_partial.p, (int)ctx->opt_mid_ncl, st));
+    TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->ts_partial.p, nwg, T, d_lagsum, st));
     return TA_OK;
 }
 
-int direct_impl(ta_ctx* ctx, int mode, const void* d_vel, const void* d_pos,
-                const double* d_masses, int64_t T, int64_t A, int D, int64_t pitch, double scale,
-                double* d_lagsum, double* d_bp, int64_t ld_bp, hipStream_t st, bool src_f32 = false) {
-    const bool f32 = ctx->opt_direct_f32 != 0 && mode != MODE_MSD;  // src_f32 only comes with it (compute_pm); MSD: float64
-    if (!f32 && !src_f32 && ctx->opt_direct_mfma == 1 && short_applies(ctx, T))  // ("direct_mfma" 0 / 3 force a form)
-        return short_impl(ctx, mode, (const double*)d_vel, (const double*)d_pos, d_masses, T, A, D, pitch, scale, d_lagsum, d_bp,
-                          ld_bp, st);
-    // k_mid where it wins (profiles/r06_direct_mid_sweep.txt): the windowed VACF from 97 to 512 frames (9.4 against 16.5 ms per
-    // 12 GB at 128 frames with the by-particle array, 21.9 against 25.8 at 512), Helfand from 97 to 128 (18 against 23);
-    // "mid_max" 0: never; "mid_all" 1: wherever the kernel can run (65 ... 512 frames, both quantities: the parity tests).
-    // The Einstein MSD (no product stage) from 65 to 512 frames: 14 - 38 ms against the vector kernel's 21 - 44 per 12 GB
-    // with the by-particle array, within 8 % where it loses (160 frames; tools/sweep_msd.py, DESIGN.md section 4.7)
-    if (!f32 && !src_f32 && ctx->opt_direct_mfma == 1 && T > 64 && T <= ctx->opt_mid_max && T <= mid_max_frames() &&
-        (ctx->opt_mid_all || mode == MODE_MSD || (T >= 97 && (mode == MODE_VACF || T <= 128))))
-        return mid_impl(ctx, mode, (const double*)d_vel, (const double*)d_pos, d_masses, T, A, D, pitch, scale, d_lagsum, d_bp, ld_bp,
-                        st);
-    // The O(T^2) correlators run on the matrix cores wherever that wins: FP64 (bandbp_kernels.hpp) and, for the float32
-    // option's Helfand forms, FP32 (band32tp_kernels.hpp: P rounded once to float32 like the float32 vector kernel's staged
-    // values, float32 products, float64 accumulation) -- the k-slots of the MFMA filled from the time axis.  "direct_mfma":
-    // 1 = by trajectory length (these kernels pay a ring fill and an epilogue per particle (block) and lag group; the vector
-    // kernel, whose column groups are 8 - 32 lanes under ~640 frames, wins the windowed VACF up to 512 frames, Helfand float64
-    // up to 351, float32 up to 447: profiles/r06_direct_mid_sweep.txt, 12 GB of input at every length),
-    // 3 = always, 0 = vector kernels (the parity tests' second opinion).  (The column-packed forms of rounds 4-5 --
-    // "direct_mfma" 2, inline-assembly LDS-DMA -- live under tools/band/ since round 6.)
-    const bool band_ok = !d_bp && !f32 && !src_f32 && ctx->opt_direct_mfma && T < ((int64_t)1 << 24);
-    const int mf = (int)ctx->opt_direct_mfma;
-    auto time_packed = [&](int64_t from_frames) { return mf == 3 || (mf == 1 && T >= from_frames); };
-    if (!d_bp && f32 && mode == MODE_HELFAND && time_packed(448) && T < ((int64_t)1 << 24)) {
-        const int64_t n_cols = A * D;
-        if (ensure(ctx, ctx->helf_p, pm_bytes(T, n_cols, true)) == TA_OK &&
-            ensure(ctx, ctx->bp_scratch, sizeof(double) * band_bp_helf_partial_doubles(ctx->n_cu, (int)T, A)) == TA_OK &&
-            ensure(ctx, ctx->unit_counter, 64) == TA_OK) {
-            tl_mark(ctx, "k_helfand_product32", st);
-            TA_HIP_TRY(ctx, launch_helfand_product32(d_vel, d_pos, src_f32, d_masses, pitch, T, n_cols, D, (float*)ctx->helf_p.p, st));
-            tl_mark(ctx, "k_band32_tp", st);
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-            TA_HIP_TRY(ctx, launch_band32_tp_lags(ctx->n_cu, (const float*)ctx->helf_p.p, pitch, (int)T, A, D, scale / (double)D,
-                                                  (double*)ctx->bp_scratch.p, (unsigned long long*)ctx->unit_counter.p, d_lagsum, st));
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-            return TA_OK;
-        }
-        (void)hipGetLastError();  // out of memory for the product slab: the vector kernel needs none
-    }
-    // ... and with the by-particle array
-    if (d_bp && f32 && mode == MODE_HELFAND && time_packed(448) && T < ((int64_t)1 << 24)) {
-        const int64_t n_cols = A * D, Tp = pm_pitch(T), n_tiles = (A + 63) / 64;
-        if (ensure(ctx, ctx->helf_p, pm_bytes(T, n_cols, true)) == TA_OK &&
-            ensure(ctx, ctx->bp_scratch, sizeof(double) * (size_t)A * Tp) == TA_OK &&
-            ensure(ctx, ctx->ts_partial, sizeof(double) * (size_t)n_tiles * T) == TA_OK &&
-            ensure(ctx, ctx->unit_counter, 64) == TA_OK) {
-            tl_mark(ctx, "k_helfand_product32", st);
-            TA_HIP_TRY(ctx, launch_helfand_product32(d_vel, d_pos, src_f32, d_masses, pitch, T, n_cols, D, (float*)ctx->helf_p.p, st));
-            tl_mark(ctx, "k_band32_tp", st);
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-            TA_HIP_TRY(ctx, launch_band32_tp_bp(ctx->n_cu, (const float*)ctx->helf_p.p, pitch, (int)T, A, D, scale / (double)D,
-                                                (double*)ctx->bp_scratch.p, Tp, (unsigned long long*)ctx->unit_counter.p, st));
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-            tl_mark(ctx, "k_bp_transpose", st);
-            TA_HIP_TRY(ctx, launch_bp_transpose((const double*)ctx->bp_scratch.p, Tp, A, T, d_bp, ld_bp, (double*)ctx->ts_partial.p, st));
-            tl_mark(ctx, "k_sum_partials", st);
-            TA_HIP_TRY(ctx, launch_sum_partials((const double*)ctx->ts_partial.p, (int)n_tiles, T, d_lagsum, st));
-            return TA_OK;
-        }
+// The matrix-core forms, each with and without the by-particle array.  With it the kernel leaves atom-major lags and
+// bp_tail follows; without, the kernel of the by-particle form runs with the particles of a unit summed in its
+// accumulators (work handed out by a counter: windowed VACF 51.4 ms at 5000 x 50000 x 3, Helfand 463 ms per configs[4]
+// share) and writes the lag sums itself.  The Helfand forms read the product slab P = (m v) x, made first (T*A*D*8 bytes
+// more, 4 in float32).
+struct BandForm {
+    Form form;
+    int slab_elem;    // bytes per element of the product slab helf_p (0: the kernel reads the velocities)
+    bool q_partials;  // k_helfand_product also writes its row partials, into helf_small
+    bool halves;      // bp_tail's flag
+};
+constexpr BandForm kBandForms[] = {{F_BAND_VACF64, 0, false, true},
+                                   {F_BAND_HELF64, 8, true, false},
+                                   {F_BAND_HELF32, 4, false, false}};
+
+// Queues form f.  *queued false: a buffer could not be had (not an error of the call: the vector kernel needs none of
+// them, and the caller goes on to it).
+int band_impl(ta_ctx* ctx, const BandForm& f, const void* d_vel, const void* d_pos, bool src_f32, const double* d_masses, int64_t T,
+              int64_t A, int D, int64_t pitch, double scale, double* d_lagsum, double* d_bp, int64_t ld_bp, hipStream_t st,
+              bool* queued) {
+    const int64_t n_cols = A * D, Tp = pm_pitch(T), n_tiles = (A + 63) / 64;
+    const int n_parts = (int)std::min<int64_t>(1024, (n_cols + 1) / 2);
+    const size_t scratch = d_bp ? (size_t)A * Tp : band_bp_helf_partial_doubles(ctx->n_cu, (int)T, A);
+    *queued = (!f.slab_elem || ensure(ctx, ctx->helf_p, pm_bytes(T, n_cols, f.slab_elem == 4)) == TA_OK) &&
+              (!f.q_partials || ensure(ctx, ctx->helf_small, sizeof(double) * (size_t)n_parts * T) == TA_OK) &&
+              ensure(ctx, ctx->bp_scratch, sizeof(double) * scratch) == TA_OK &&
+              (!d_bp || ensure(ctx, ctx->ts_partial, sizeof(double) * (size_t)n_tiles * T) == TA_OK) &&
+              ensure(ctx, ctx->unit_counter, 64) == TA_OK;
+    if (!*queued) {
         (void)hipGetLastError();
-    }
-    // ... and the windowed VACF with its by-particle array (the class default) on the FP64 matrix cores: the k-slots
-    // are filled from the time axis (bandbp_kernels.hpp)
-    if (d_bp && !f32 && !src_f32 && mode == MODE_VACF && time_packed(513) && T < ((int64_t)1 << 24)) {
-        const int64_t Tp = pm_pitch(T), n_tiles = (A + 63) / 64;
-        if (ensure(ctx, ctx->bp_scratch, sizeof(double) * (size_t)A * Tp) == TA_OK &&
-            ensure(ctx, ctx->ts_partial, sizeof(double) * (size_t)n_tiles * T) == TA_OK &&
-            ensure(ctx, ctx->unit_counter, 64) == TA_OK) {
-            tl_mark(ctx, "k_band_bp_vacf", st);
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-            TA_HIP_TRY(ctx, launch_band_bp_vacf(ctx->n_cu, (const double*)d_vel, pitch, (int)T, A, D, (double*)ctx->bp_scratch.p, Tp,
-                                                (unsigned long long*)ctx->unit_counter.p, st));
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-            tl_mark(ctx, "k_bp_transpose", st);
-            TA_HIP_TRY(ctx, launch_bp_transpose((const double*)ctx->bp_scratch.p, Tp, A, T, d_bp, ld_bp, (double*)ctx->ts_partial.p, st,
-                                                true));
-            tl_mark(ctx, "k_sum_partials", st);
-            TA_HIP_TRY(ctx, launch_sum_partials((const double*)ctx->ts_partial.p, (int)n_tiles, T, d_lagsum, st));
-            return TA_OK;
-        }
-        (void)hipGetLastError();
-    }
-    // ... and the Einstein-Helfand by-particle array (float64) the same way, on the product slab
-    if (d_bp && !f32 && !src_f32 && mode == MODE_HELFAND && time_packed(352) && T < ((int64_t)1 << 24)) {
-        const int64_t n_cols = A * D, n_pairs = (n_cols + 1) / 2, Tp = pm_pitch(T), n_tiles = (A + 63) / 64;
-        const int n_parts = (int)std::min<int64_t>(1024, n_pairs);
-        if (ensure(ctx, ctx->helf_p, pm_bytes(T, n_cols)) == TA_OK &&
-            ensure(ctx, ctx->helf_small, sizeof(double) * (size_t)n_parts * T) == TA_OK &&
-            ensure(ctx, ctx->bp_scratch, sizeof(double) * (size_t)A * Tp) == TA_OK &&
-            ensure(ctx, ctx->ts_partial, sizeof(double) * (size_t)n_tiles * T) == TA_OK &&
-            ensure(ctx, ctx->unit_counter, 64) == TA_OK) {
-            tl_mark(ctx, "k_helfand_product", st);
-            TA_HIP_TRY(ctx, launch_helfand_product((const double*)d_vel, (const double*)d_pos, d_masses, pitch, T, n_cols, D,
-                                                   (double*)ctx->helf_p.p, (double*)ctx->helf_small.p, n_parts, st));
-            tl_mark(ctx, "k_band_bp_helf", st);
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-            TA_HIP_TRY(ctx, launch_band_bp_helf(ctx->n_cu, (const double*)ctx->helf_p.p, pitch, (int)T, A, D, scale / (double)D,
-                                                (double*)ctx->bp_scratch.p, Tp, (unsigned long long*)ctx->unit_counter.p, st));
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-            tl_mark(ctx, "k_bp_transpose", st);
-            TA_HIP_TRY(ctx, launch_bp_transpose((const double*)ctx->bp_scratch.p, Tp, A, T, d_bp, ld_bp, (double*)ctx->ts_partial.p, st));
-            tl_mark(ctx, "k_sum_partials", st);
-            TA_HIP_TRY(ctx, launch_sum_partials((const double*)ctx->ts_partial.p, (int)n_tiles, T, d_lagsum, st));
-            return TA_OK;
-        }
-        (void)hipGetLastError();
-    }
-    // windowed VACF lag sums alone: the by-particle kernel with a unit's particles summed in its accumulators (work handed out
-    // by a counter: 51.4 ms at 5000 x 50000 x 3)
-    if (band_ok && mode == MODE_VACF && time_packed(513) &&
-        ensure(ctx, ctx->bp_scratch, sizeof(double) * band_bp_helf_partial_doubles(ctx->n_cu, (int)T, A)) == TA_OK &&
-        ensure(ctx, ctx->unit_counter, 64) == TA_OK) {
-        tl_mark(ctx, "k_band_bp_vacf", st);
-        TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-        TA_HIP_TRY(ctx, launch_band_bp_vacf_lags(ctx->n_cu, (const double*)d_vel, pitch, (int)T, A, D, (double*)ctx->bp_scratch.p,
-                                                 (unsigned long long*)ctx->unit_counter.p, d_lagsum, st));
-        TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
         return TA_OK;
     }
-    if (band_ok && mode == MODE_HELFAND && time_packed(352)) {
-        // the product slab P = (m v) x first (T*A*D*8 bytes more; without them: the vector kernel); then the kernel of the
-        // by-particle form with the particles of a unit summed in its accumulators (k-slots from the time axis: all four do
-        // arithmetic: 463 ms per configs[4] share).
-        const int64_t n_cols = A * D, n_pairs = (n_cols + 1) / 2;
-        const int n_parts = (int)std::min<int64_t>(1024, n_pairs);
-        if (ensure(ctx, ctx->helf_p, pm_bytes(T, n_cols)) == TA_OK &&
-            ensure(ctx, ctx->helf_small, sizeof(double) * (size_t)n_parts * T) == TA_OK &&
-            ensure(ctx, ctx->bp_scratch, sizeof(double) * band_bp_helf_partial_doubles(ctx->n_cu, (int)T, A)) == TA_OK &&
-            ensure(ctx, ctx->unit_counter, 64) == TA_OK) {
-            tl_mark(ctx, "k_helfand_product", st);
-            TA_HIP_TRY(ctx, launch_helfand_product((const double*)d_vel, (const double*)d_pos, d_masses, pitch, T, n_cols, D,
-                                                   (double*)ctx->helf_p.p, (double*)ctx->helf_small.p, n_parts, st));
-            tl_mark(ctx, "k_band_bp_helf", st);
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-            TA_HIP_TRY(ctx, launch_band_bp_helf_lags(ctx->n_cu, (const double*)ctx->helf_p.p, pitch, (int)T, A, D, scale / (double)D,
-                                                     (double*)ctx->bp_scratch.p, (unsigned long long*)ctx->unit_counter.p, d_lagsum, st));
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-            return TA_OK;
-        }
-        (void)hipGetLastError();  // out of memory for the product slab: not an error of the call
+    double* part = (double*)ctx->bp_scratch.p;
+    unsigned long long* counter = (unsigned long long*)ctx->unit_counter.p;
+    const double factor = scale / (double)D;
+    if (f.form == F_BAND_VACF64) {
+        const double* v = (const double*)d_vel;
+        if (d_bp)
+            TA_LAUNCH_MAIN(ctx, "k_band_bp_vacf", st,
+                           launch_band_bp_vacf(ctx->n_cu, v, pitch, (int)T, A, D, part, Tp, counter, st));
+        else
+            TA_LAUNCH_MAIN(ctx, "k_band_bp_vacf", st,
+                           launch_band_bp_vacf_lags(ctx->n_cu, v, pitch, (int)T, A, D, part, counter, d_lagsum, st));
+    } else if (f.form == F_BAND_HELF64) {
+        const double* P = (const double*)ctx->helf_p.p;
+        TA_LAUNCH(ctx, "k_helfand_product", st,
+                  launch_helfand_product((const double*)d_vel, (const double*)d_pos, d_masses, pitch, T, n_cols, D,
+                                         (double*)ctx->helf_p.p, (double*)ctx->helf_small.p, n_parts, st));
+        if (d_bp)
+            TA_LAUNCH_MAIN(ctx, "k_band_bp_helf", st,
+                           launch_band_bp_helf(ctx->n_cu, P, pitch, (int)T, A, D, factor, part, Tp, counter, st));
+        else
+            TA_LAUNCH_MAIN(ctx, "k_band_bp_helf", st,
+                           launch_band_bp_helf_lags(ctx->n_cu, P, pitch, (int)T, A, D, factor, part, counter, d_lagsum, st));
+    } else {
+        const float* P = (const float*)ctx->helf_p.p;
+        TA_LAUNCH(ctx, "k_helfand_product32", st,
+                  launch_helfand_product32(d_vel, d_pos, src_f32, d_masses, pitch, T, n_cols, D, (float*)ctx->helf_p.p, st));
+        if (d_bp)
+            TA_LAUNCH_MAIN(ctx, "k_band32_tp", st,
+                           launch_band32_tp_bp(ctx->n_cu, P, pitch, (int)T, A, D, factor, part, Tp, counter, st));
+        else
+            TA_LAUNCH_MAIN(ctx, "k_band32_tp", st,
+                           launch_band32_tp_lags(ctx->n_cu, P, pitch, (int)T, A, D, factor, part, counter, d_lagsum, st));
     }
-    // Shape of the launch.  A thread owns one chunk pair (2L lags); a column group = W waves;
-    // a workgroup = G groups working on G atoms at once, so that ONE workgroup fills a CU's
-    // 16 wave slots (G*W <= 16) and its waves are dealt evenly to the 4 SIMDs.  The column
-    // must be resident next to the compute units: in LDS when it fits (float64: <= 16376
-    // frames, float32: <= 27296), otherwise in an L2-resident per-group staging buffer
-    // (slower, any length).  L (8 or 10 lags per chunk) is the one that wastes fewer lanes
-    // and SIMD slots for this n_frames.
+    return d_bp ? bp_tail(ctx, T, A, d_lagsum, d_bp, ld_bp, st, f.halves) : TA_OK;
+}
+
+// Shape of the vector kernel's launch.  A thread owns one chunk pair (2L lags); a column group = W waves;
+// a workgroup = G groups working on G atoms at once, so that ONE workgroup fills a CU's
+// 16 wave slots (G*W <= 16) and its waves are dealt evenly to the 4 SIMDs.  The column
+// must be resident next to the compute units: in LDS when it fits (float64: <= 16376
+// frames, float32: <= 27296), otherwise in an L2-resident per-group staging buffer
+// (slower, any length).  L (8 or 10 lags per chunk) is the one that wastes fewer lanes
+// and SIMD slots for this n_frames.
+// Trajectories under ~1000 frames have fewer chunk pairs than a wave has lanes: a column group is then 16 or 32 LANES
+// ("direct_subwave" 1, the default), several groups per wave, up to 64 atoms per workgroup.
+struct Shape {
+    int L, GT, G;  // lags per chunk, threads per column group, groups per workgroup
+    size_t col;    // bytes of a resident column
+    bool gs;       // columns in the global staging buffer
+    double eff;    // < 0: no chunk size is to be had ("direct_chunk")
+};
+Shape direct_shape(const ta_ctx* ctx, int64_t T, int64_t A, bool f32) {
     const size_t lds_cap = 160 * 1024;
-    // Trajectories under ~1000 frames have fewer chunk pairs than a wave has lanes: a column group is then 16 or 32 LANES
-    // ("direct_subwave" 1, the default), several groups per wave, up to 64 atoms per workgroup.
-    struct Shape { int L, GT, G; size_t col; bool gs; double eff; } best{0, 0, 0, 0, false, -1.0};
+    Shape best{0, 0, 0, 0, false, -1.0};
     for (int L : {8, 10}) {
         if (ctx->opt_direct_chunk > 0 && L != ctx->opt_direct_chunk) continue;
         if (!direct_chunk_supported(L)) continue;
@@ -441,21 +449,41 @@ int direct_impl(ta_ctx* ctx, int mode, const void* d_vel, const void* d_pos,
             c.eff = 2.0 + (double)npairs / ((double)rounds * c.GT) * (L == 8 ? 1.0 : 0.93);
         if (c.eff > best.eff) best = c;
     }
-    if (best.eff < 0) return fail(ctx, TA_E_INVALID, "direct_chunk option: unsupported chunk size");
-    const int L = best.L, G = best.G;
-    const size_t col = best.col;
-    const bool global_stage = best.gs;
-    const int gnt = best.GT, nt = G * gnt;
-    const size_t lds = global_stage ? 0 : col * (size_t)G;
-    const int per_cu = direct_max_wg_per_cu(mode, f32, L, nt, lds, global_stage);
+    return best;
+}
+
+// One O(T^2) evaluation by the form direct_form names (the thresholds and where they were measured: there).  A matrix-core
+// form that cannot have its buffers gives way to the vector kernel.
+int direct_impl(ta_ctx* ctx, int mode, const void* d_vel, const void* d_pos,
+                const double* d_masses, int64_t T, int64_t A, int D, int64_t pitch, double scale,
+                double* d_lagsum, double* d_bp, int64_t ld_bp, hipStream_t st, bool src_f32 = false) {
+    const Form form = direct_form(ctx, mode, T, src_f32);
+    if (form == F_SHORT)
+        return short_impl(ctx, mode, (const double*)d_vel, (const double*)d_pos, d_masses, T, A, D, pitch, scale, d_lagsum, d_bp,
+                          ld_bp, st);
+    if (form == F_MID)
+        return mid_impl(ctx, mode, (const double*)d_vel, (const double*)d_pos, d_masses, T, A, D, pitch, scale, d_lagsum, d_bp, ld_bp,
+                        st);
+    int rc;
+    for (const BandForm& f : kBandForms) {
+        if (f.form != form) continue;
+        bool queued = false;
+        rc = band_impl(ctx, f, d_vel, d_pos, src_f32, d_masses, T, A, D, pitch, scale, d_lagsum, d_bp, ld_bp, st, &queued);
+        if (rc || queued) return rc;
+    }
+    const bool f32 = direct_f32(ctx, mode);
+    const Shape sh = direct_shape(ctx, T, A, f32);
+    if (sh.eff < 0) return fail(ctx, TA_E_INVALID, "direct_chunk option: unsupported chunk size");
+    const int nt = sh.G * sh.GT;
+    const size_t lds = sh.gs ? 0 : sh.col * (size_t)sh.G;
+    const int per_cu = direct_max_wg_per_cu(mode, f32, sh.L, nt, lds, sh.gs);
     int64_t nwg = ctx->opt_direct_nwg > 0 ? ctx->opt_direct_nwg : (int64_t)ctx->n_cu * per_cu;
-    nwg = std::max<int64_t>(1, std::min<int64_t>(nwg, (A + G - 1) / G));
-    const size_t rows = (size_t)nwg * G;
-    int rc = ensure(ctx, ctx->ts_partial, sizeof(double) * rows * T);
-    if (rc) return rc;
+    nwg = std::max<int64_t>(1, std::min<int64_t>(nwg, (A + sh.G - 1) / sh.G));
+    const size_t rows = (size_t)nwg * sh.G;
+    if ((rc = ensure(ctx, ctx->ts_partial, sizeof(double) * rows * T))) return rc;
     void* stage_buf = nullptr;
-    if (global_stage) {
-        if ((rc = ensure(ctx, ctx->stage_buf, col * rows))) return rc;
+    if (sh.gs) {
+        if ((rc = ensure(ctx, ctx->stage_buf, sh.col * rows))) return rc;
         stage_buf = ctx->stage_buf.p;
     }
     // by-particle values leave the kernel atom-major (contiguous stores) and are transposed
@@ -466,20 +494,12 @@ int direct_impl(ta_ctx* ctx, int mode, const void* d_vel, const void* d_pos,
         if ((rc = ensure(ctx, ctx->bp_scratch, sizeof(double) * (size_t)A * Tp))) return rc;
         bp_am = (double*)ctx->bp_scratch.p;
     }
-    tl_mark(ctx, "memset", st);
-    TA_HIP_TRY(ctx, hipMemsetAsync(ctx->ts_partial.p, 0, sizeof(double) * rows * T, st));
-    tl_mark(ctx, "k_direct", st);
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-    TA_HIP_TRY(ctx, launch_direct(mode, f32, src_f32, L, d_vel, d_pos, d_masses, pitch, (int)T, A, D, scale, bp_am,
-                                  Tp, (double*)ctx->ts_partial.p, (int)nwg, nt, lds, stage_buf,
-                                  gnt, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-    tl_mark(ctx, "k_sum_partials", st);
-    TA_HIP_TRY(ctx, launch_sum_partials((const double*)ctx->ts_partial.p, (int)rows, T, d_lagsum, st));
-    if (d_bp) {
-        tl_mark(ctx, "k_bp_transpose", st);
-        TA_HIP_TRY(ctx, launch_bp_transpose(bp_am, Tp, A, T, d_bp, ld_bp, nullptr, st));
-    }
+    TA_LAUNCH(ctx, "memset", st, hipMemsetAsync(ctx->ts_partial.p, 0, sizeof(double) * rows * T, st));
+    TA_LAUNCH_MAIN(ctx, "k_direct", st,
+                   launch_direct(mode, f32, src_f32, sh.L, d_vel, d_pos, d_masses, pitch, (int)T, A, D, scale, bp_am, Tp,
+                                 (double*)ctx->ts_partial.p, (int)nwg, nt, lds, stage_buf, sh.GT, st));
+    TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->ts_partial.p, (int)rows, T, d_lagsum, st));
+    if (d_bp) TA_LAUNCH(ctx, "k_bp_transpose", st, launch_bp_transpose(bp_am, Tp, A, T, d_bp, ld_bp, nullptr, st));
     return TA_OK;
 }
 
@@ -490,8 +510,7 @@ int direct_impl(ta_ctx* ctx, int mode, const void* d_vel, const void* d_pos,
 // it; beyond that the direct correlator (same quantity: velocityautocorr.py:217-238 == :208-215
 // mathematically).  Lag sums: forward kernel -> partial spectra per tuple of workgroups -> their
 // sum -> ONE inverse transform.  By-particle array: per block of atoms, forward kernel -> the
-// atoms' power spectra in scratch -> inverse kernel -> atom-major lags; then the transposition
-// into the caller's (n_frames, ld_bp) array, which also adds up its 64 atoms per lag.
+// atoms' power spectra in scratch -> inverse kernel -> atom-major lags; then bp_tail.
 // pm_f32: the slab holds float32 elements (fft_reads_f32 says for which lengths the kernels take it)
 bool fft_reads_f32(int64_t T) {
     int R0 = 0, R = 1;
@@ -527,34 +546,27 @@ int fft_impl(ta_ctx* ctx, const double* pm, int64_t pitch, int64_t T, int64_t A,
             const int n_parts = (int)(4 * nwg);
             if ((rc = ensure(ctx, ctx->partial, sizeof(double) * (size_t)n_parts * L))) return rc;
             if ((rc = ensure(ctx, ctx->spec, sizeof(double) * (size_t)L))) return rc;
-            tl_mark(ctx, "k_w1_accum", st);
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-            TA_HIP_TRY(ctx, launch_w1_accum((int)nwg, st, pm, pitch, (int)T, n_pairs, tw, (double*)ctx->partial.p));
-            TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-            tl_mark(ctx, "k_wf_sum+k_wf_fold+k_wf_lags", st);
-            TA_HIP_TRY(ctx, launch_wfft_finish(R0, (const double*)ctx->partial.p, n_parts, tw, (int)T,
-                                               (double*)ctx->spec.p, d_lagsum, st));
+            TA_LAUNCH_MAIN(ctx, "k_w1_accum", st,
+                           launch_w1_accum((int)nwg, st, pm, pitch, (int)T, n_pairs, tw, (double*)ctx->partial.p));
+            TA_LAUNCH(ctx, "k_wf_sum+k_wf_fold+k_wf_lags", st,
+                      launch_wfft_finish(R0, (const double*)ctx->partial.p, n_parts, tw, (int)T, (double*)ctx->spec.p, d_lagsum, st));
             return TA_OK;
         }
         const int64_t nwg = std::max<int64_t>(1, std::min(cap, (A + 3) / 4));  // a wave per atom
-        tl_mark(ctx, "k_w1_bp", st);
-        TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-        TA_HIP_TRY(ctx, launch_w1_bp((int)nwg, st, pm, pitch, (int)T, A, D, tw, (double*)ctx->bp_scratch.p, Tp));
-        TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
+        TA_LAUNCH_MAIN(ctx, "k_w1_bp", st,
+                       launch_w1_bp((int)nwg, st, pm, pitch, (int)T, A, D, tw, (double*)ctx->bp_scratch.p, Tp));
     } else if (!d_bp) {
         const int64_t nwg = forward_grid(n_pairs), n_tuples = nwg / (2 * R);
         if ((rc = ensure(ctx, ctx->partial, sizeof(double) * (size_t)n_tuples * L))) return rc;
         if ((rc = ensure(ctx, ctx->spec, sizeof(double) * (size_t)L))) return rc;
-        tl_mark(ctx, "k_wsplit_accum", st);
-        TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-        TA_HIP_TRY(ctx, launch_wfft_forward(R0, R, false, pm_f32, (int)nwg, st, pm, pitch, (int)T, n_pairs, D, tw,
-                                            (double*)ctx->partial.p));
-        TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
+        TA_LAUNCH_MAIN(ctx, "k_wsplit_accum", st,
+                       launch_wfft_forward(R0, R, false, pm_f32, (int)nwg, st, pm, pitch, (int)T, n_pairs, D, tw,
+                                           (double*)ctx->partial.p));
         // the summed spectrum -> lag sums: ONE inverse transform per launch
-        tl_mark(ctx, "k_sum_partials", st);
-        TA_HIP_TRY(ctx, launch_sum_partials((const double*)ctx->partial.p, (int)n_tuples, L, (double*)ctx->spec.p, st));
-        tl_mark(ctx, "k_winverse", st);
-        TA_HIP_TRY(ctx, launch_wfft_inverse(R0, R, 1, st, (const double*)ctx->spec.p, (int)T, 1, tw, d_lagsum, 0, 0));
+        TA_LAUNCH(ctx, "k_sum_partials", st,
+                  launch_sum_partials((const double*)ctx->partial.p, (int)n_tuples, L, (double*)ctx->spec.p, st));
+        TA_LAUNCH(ctx, "k_winverse", st,
+                  launch_wfft_inverse(R0, R, 1, st, (const double*)ctx->spec.p, (int)T, 1, tw, d_lagsum, 0, 0));
         return TA_OK;
     } else {
         // blocks of atoms sized by the spectrum scratch (2.5 GiB unless the bp_spec_atoms option
@@ -567,92 +579,41 @@ int fft_impl(ta_ctx* ctx, const double* pm, int64_t pitch, int64_t T, int64_t A,
             CA = std::min<int64_t>(CA, ((A + n_blocks - 1) / n_blocks + 1) / 2 * 2);
         }
         if ((rc = ensure(ctx, ctx->bp_spec, spec_bytes * (size_t)CA))) return rc;
+        // (the main-kernel interval spans every block's pair of launches)
         TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
         for (int64_t a0 = 0; a0 < A; a0 += CA) {
             const int64_t ca = std::min(CA, A - a0);
             const int64_t groups = D & 1 ? (ca + 1) / 2 : ca;  // a tuple of workgroups per group of atoms
-            tl_mark(ctx, "k_wsplit_accum", st);
             // (a block starts on a column-pair boundary; pairs of a float32 slab are 8-byte rows)
             const double* pm_blk = pm_f32 ? (const double*)((const float*)pm + (a0 * D / 2) * pitch * 2)
                                           : pm + (a0 * D / 2) * pitch * 2;
-            TA_HIP_TRY(ctx, launch_wfft_forward(R0, R, true, pm_f32, (int)forward_grid(groups), st, pm_blk, pitch,
-                                                (int)T, ca, D, tw, (double*)ctx->bp_spec.p));
-            tl_mark(ctx, "k_winverse", st);
-            TA_HIP_TRY(ctx, launch_wfft_inverse(R0, R, (int)std::min<int64_t>(cap, ca), st,
-                                                (const double*)ctx->bp_spec.p, (int)T, ca, tw,
-                                                (double*)ctx->bp_scratch.p + a0 * Tp, Tp, (int)ctx->opt_bp_prefetch));
+            TA_LAUNCH(ctx, "k_wsplit_accum", st,
+                      launch_wfft_forward(R0, R, true, pm_f32, (int)forward_grid(groups), st, pm_blk, pitch, (int)T, ca, D, tw,
+                                          (double*)ctx->bp_spec.p));
+            TA_LAUNCH(ctx, "k_winverse", st,
+                      launch_wfft_inverse(R0, R, (int)std::min<int64_t>(cap, ca), st, (const double*)ctx->bp_spec.p, (int)T, ca, tw,
+                                          (double*)ctx->bp_scratch.p + a0 * Tp, Tp, (int)ctx->opt_bp_prefetch));
         }
         TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
     }
-    tl_mark(ctx, "k_bp_transpose", st);
-    TA_HIP_TRY(ctx, launch_bp_transpose((const double*)ctx->bp_scratch.p, Tp, A, T, d_bp, ld_bp,
-                                        (double*)ctx->ts_partial.p, st));
-    tl_mark(ctx, "k_sum_partials", st);
-    TA_HIP_TRY(ctx, launch_sum_partials((const double*)ctx->ts_partial.p, (int)n_tiles, T, d_lagsum, st));
-    return TA_OK;
+    return bp_tail(ctx, T, A, d_lagsum, d_bp, ld_bp, st);
 }
 
-// Helfand mean squared differences (viscosity.py:201-233); the "helfand_fft" option evaluates
-// them as S1 - 2 S2 (helfand_fft.hip) where an FFT path exists for the request.
-int helfand_impl(ta_ctx* ctx, const double* pm_vel, const double* pm_pos, const double* d_masses,
-                 int64_t pitch, int64_t T, int64_t A, int D, double scale, double* d_lagsum,
-                 double* d_bp, int64_t ld_bp, hipStream_t st) {
-    int rc;
-    const int64_t n_cols = A * D, n_pairs = (n_cols + 1) / 2;
-    const bool fft_ok = ctx->opt_helfand_fft && T >= 2;
+// Mean squared differences of a prepared slab as S1 - 2 S2 (helfand_fft.hip), wherever wfft_choose has a plan: the
+// prepare kernel writes P and its squares' sums (lag sums: row partials Qpart, summed into Q; by particle: Ca per atom),
+// fft_impl gives S2 as the autocorrelation of P, the combine kernels put factor * (S1 - 2 S2) together.
+bool s1_2s2_applies(int64_t T) {
     int r0 = 0, ro = 0;
-    const bool has_fft = wfft_choose((long)T, &r0, &ro);
-    if (fft_ok && !d_bp && has_fft) {
-        const int n_parts = (int)std::min<int64_t>(1024, n_pairs);
-        if ((rc = ensure(ctx, ctx->helf_p, pm_bytes(T, n_cols)))) return rc;
-        if ((rc = ensure(ctx, ctx->helf_small, sizeof(double) * ((size_t)n_parts * T + 3 * (size_t)T + 1)))) return rc;
-        double* P = (double*)ctx->helf_p.p;
-        double* Qpart = (double*)ctx->helf_small.p;
-        double* Q = Qpart + (size_t)n_parts * T;
-        double* S2 = Q + T;
-        double* C = S2 + T;
-        tl_mark(ctx, "k_helfand_product", st);
-        TA_HIP_TRY(ctx, launch_helfand_product(pm_vel, pm_pos, d_masses, pitch, T, n_cols, D, P, Qpart, n_parts, st));
-        tl_mark(ctx, "k_sum_partials", st);
-        TA_HIP_TRY(ctx, launch_sum_partials(Qpart, n_parts, T, Q, st));
-        if ((rc = fft_impl(ctx, P, pitch, T, A, D, S2, nullptr, 0, st))) return rc;
-        tl_mark(ctx, "k_helfand_combine", st);
-        TA_HIP_TRY(ctx, launch_helfand_combine(Q, S2, C, (int)T, scale / (double)D, d_lagsum, st));
-        return TA_OK;
-    }
-    if (fft_ok && d_bp && has_fft) {
-        if ((rc = ensure(ctx, ctx->helf_p, pm_bytes(T, n_cols)))) return rc;
-        if ((rc = ensure(ctx, ctx->helf_small, sizeof(double) * ((size_t)T + 1) * A))) return rc;
-        double* P = (double*)ctx->helf_p.p;
-        double* Ca = (double*)ctx->helf_small.p;
-        if (n_cols & 1)  // the unpaired last column's partner is never written by the product kernel
-            TA_HIP_TRY(ctx, hipMemsetAsync(P + (size_t)(n_pairs - 1) * pitch * 2, 0, (size_t)pitch * 16, st));
-        tl_mark(ctx, "k_helfand_product", st);
-        TA_HIP_TRY(ctx, launch_helfand_product_bp(pm_vel, pm_pos, d_masses, pitch, T, A, D, P, Ca, st));
-        if ((rc = fft_impl(ctx, P, pitch, T, A, D, d_lagsum, d_bp, ld_bp, st))) return rc;
-        tl_mark(ctx, "k_helfand_combine", st);
-        TA_HIP_TRY(ctx, launch_helfand_combine_bp(Ca, A, (int)T, scale / (double)D, d_bp, ld_bp, st));
-        tl_mark(ctx, "k_row_sums", st);
-        TA_HIP_TRY(ctx, launch_row_sums(d_bp, T, A, ld_bp, d_lagsum, st));
-        return TA_OK;
-    }
-    return direct_impl(ctx, MODE_HELFAND, pm_vel, pm_pos, d_masses, T, A, D, pitch, scale, d_lagsum, d_bp,
-                       ld_bp, st);
+    return T >= 2 && wfft_choose((long)T, &r0, &ro);
 }
+enum Prepare { PREP_HELFAND /* P = (m v) x */, PREP_MSD /* P = x - x[t=0] (msd.hip) */ };
 
-// Einstein MSD (MDAnalysis.analysis.msd.EinsteinMSD) on the position slab alone.  fft: up to short_max frames k_short
-// (exact, and faster there, as for the VACF); beyond, S1 - 2 S2 on P = x - x[t=0] (msd.hip, helfand_fft.hip's combine
-// kernels with factor 1) wherever wfft_choose has a plan.  !fft, and fft beyond the largest plan: the direct forms under
-// direct_impl's thresholds (k_short up to 64 frames, k_mid 65 ... 512: re-measured for MSD, k_direct beyond).
-int msd_impl(ta_ctx* ctx, bool fft, const double* pm_pos, int64_t pitch, int64_t T, int64_t A, int D, double* d_lagsum,
-             double* d_bp, int64_t ld_bp, hipStream_t st) {
+// pm: the velocities (PREP_MSD: the positions, and nothing else)
+int s1_2s2_impl(ta_ctx* ctx, Prepare prep, const double* pm, const double* pm_pos, const double* d_masses, int64_t pitch, int64_t T,
+                int64_t A, int D, double factor, double* d_lagsum, double* d_bp, int64_t ld_bp, hipStream_t st) {
     int rc;
-    int r0 = 0, ro = 0;
-    const bool fft_form = fft && T >= 2 && !(ctx->opt_direct_mfma == 1 && short_applies(ctx, T)) &&
-                          wfft_choose((long)T, &r0, &ro);
-    if (!fft_form)
-        return direct_impl(ctx, MODE_MSD, pm_pos, nullptr, nullptr, T, A, D, pitch, 1.0, d_lagsum, d_bp, ld_bp, st);
     const int64_t n_cols = A * D, n_pairs = (n_cols + 1) / 2;
+    const char* name = prep == PREP_HELFAND ? "k_helfand_product" : "k_msd_prepare";
     if ((rc = ensure(ctx, ctx->helf_p, pm_bytes(T, n_cols)))) return rc;
     double* P = (double*)ctx->helf_p.p;
     if (!d_bp) {
@@ -662,43 +623,68 @@ int msd_impl(ta_ctx* ctx, bool fft, const double* pm_pos, int64_t pitch, int64_t
         double* Q = Qpart + (size_t)n_parts * T;
         double* S2 = Q + T;
         double* C = S2 + T;
-        tl_mark(ctx, "k_msd_prepare", st);
-        TA_HIP_TRY(ctx, launch_msd_prepare(pm_pos, pitch, T, n_cols, P, Qpart, n_parts, st));
-        tl_mark(ctx, "k_sum_partials", st);
-        TA_HIP_TRY(ctx, launch_sum_partials(Qpart, n_parts, T, Q, st));
+        TA_LAUNCH(ctx, name, st,
+                  prep == PREP_HELFAND ? launch_helfand_product(pm, pm_pos, d_masses, pitch, T, n_cols, D, P, Qpart, n_parts, st)
+                                       : launch_msd_prepare(pm, pitch, T, n_cols, P, Qpart, n_parts, st));
+        TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials(Qpart, n_parts, T, Q, st));
         if ((rc = fft_impl(ctx, P, pitch, T, A, D, S2, nullptr, 0, st))) return rc;
-        tl_mark(ctx, "k_helfand_combine", st);
-        TA_HIP_TRY(ctx, launch_helfand_combine(Q, S2, C, (int)T, 1.0, d_lagsum, st));
+        TA_LAUNCH(ctx, "k_helfand_combine", st, launch_helfand_combine(Q, S2, C, (int)T, factor, d_lagsum, st));
         return TA_OK;
     }
     if ((rc = ensure(ctx, ctx->helf_small, sizeof(double) * ((size_t)T + 1) * A))) return rc;
     double* Ca = (double*)ctx->helf_small.p;
     if (n_cols & 1)  // the unpaired last column's partner is never written by the prepare kernel
         TA_HIP_TRY(ctx, hipMemsetAsync(P + (size_t)(n_pairs - 1) * pitch * 2, 0, (size_t)pitch * 16, st));
-    tl_mark(ctx, "k_msd_prepare", st);
-    TA_HIP_TRY(ctx, launch_msd_prepare_bp(pm_pos, pitch, T, A, D, P, Ca, st));
+    TA_LAUNCH(ctx, name, st,
+              prep == PREP_HELFAND ? launch_helfand_product_bp(pm, pm_pos, d_masses, pitch, T, A, D, P, Ca, st)
+                                   : launch_msd_prepare_bp(pm, pitch, T, A, D, P, Ca, st));
     if ((rc = fft_impl(ctx, P, pitch, T, A, D, d_lagsum, d_bp, ld_bp, st))) return rc;
-    tl_mark(ctx, "k_helfand_combine", st);
-    TA_HIP_TRY(ctx, launch_helfand_combine_bp(Ca, A, (int)T, 1.0, d_bp, ld_bp, st));
-    tl_mark(ctx, "k_row_sums", st);
-    TA_HIP_TRY(ctx, launch_row_sums(d_bp, T, A, ld_bp, d_lagsum, st));
+    TA_LAUNCH(ctx, "k_helfand_combine", st, launch_helfand_combine_bp(Ca, A, (int)T, factor, d_bp, ld_bp, st));
+    TA_LAUNCH(ctx, "k_row_sums", st, launch_row_sums(d_bp, T, A, ld_bp, d_lagsum, st));
     return TA_OK;
+}
+
+// Helfand mean squared differences (viscosity.py:201-233); the "helfand_fft" option evaluates
+// them as S1 - 2 S2 where an FFT path exists for the request.
+int helfand_impl(ta_ctx* ctx, const double* pm_vel, const double* pm_pos, const double* d_masses,
+                 int64_t pitch, int64_t T, int64_t A, int D, double scale, double* d_lagsum,
+                 double* d_bp, int64_t ld_bp, hipStream_t st) {
+    if (ctx->opt_helfand_fft && s1_2s2_applies(T))
+        return s1_2s2_impl(ctx, PREP_HELFAND, pm_vel, pm_pos, d_masses, pitch, T, A, D, scale / (double)D, d_lagsum, d_bp,
+                           ld_bp, st);
+    return direct_impl(ctx, MODE_HELFAND, pm_vel, pm_pos, d_masses, T, A, D, pitch, scale, d_lagsum, d_bp,
+                       ld_bp, st);
+}
+
+// Einstein MSD (MDAnalysis.analysis.msd.EinsteinMSD) on the position slab alone.  fft: up to short_max frames k_short
+// (exact, and faster there, as for the VACF); beyond, S1 - 2 S2 on P = x - x[t=0] (the combine kernels with factor 1)
+// wherever wfft_choose has a plan.  !fft, and fft beyond the largest plan: the direct forms under
+// direct_form's thresholds (k_short up to 64 frames, k_mid 65 ... 512: re-measured for MSD, k_direct beyond).
+int msd_impl(ta_ctx* ctx, bool fft, const double* pm_pos, int64_t pitch, int64_t T, int64_t A, int D, double* d_lagsum,
+             double* d_bp, int64_t ld_bp, hipStream_t st) {
+    if (fft && direct_form(ctx, MODE_MSD, T) != F_SHORT && s1_2s2_applies(T))
+        return s1_2s2_impl(ctx, PREP_MSD, pm_pos, nullptr, nullptr, pitch, T, A, D, 1.0, d_lagsum, d_bp, ld_bp, st);
+    return direct_impl(ctx, MODE_MSD, pm_pos, nullptr, nullptr, T, A, D, pitch, 1.0, d_lagsum, d_bp, ld_bp, st);
 }
 
 enum { W_FFT = 0, W_DIRECT = 1, W_HELFAND = 2, W_MSD_FFT = 3, W_MSD_DIRECT = 4 };
 inline bool is_msd(int which) { return which == W_MSD_FFT || which == W_MSD_DIRECT; }
 
-// one compute call on pair-major slabs, bracketed by the timing events
+// float32 device slab -> *pm: its float64 copy (same layout) in the context's scratch slab k
+int widen_input(ta_ctx* ctx, int k, int64_t pitch, int64_t n_cols, hipStream_t st, const void** pm) {
+    const size_t n_el = (size_t)((n_cols + 1) / 2) * (size_t)pitch * 2;
+    int rc = ensure(ctx, ctx->pm_in[k], n_el * sizeof(double));
+    if (rc) return rc;
+    TA_LAUNCH(ctx, "k_widen_f32", st, launch_widen_f32((const float*)*pm, (double*)ctx->pm_in[k].p, (long)n_el, st));
+    *pm = ctx->pm_in[k].p;
+    return TA_OK;
+}
+
+// one compute call on pair-major slabs; the caller has opened the call's bracket (call_begin), it is closed here
 int compute_pm(ta_ctx* ctx, int which, const void* pm_vel_any, const void* pm_pos_any, const double* d_masses,
                int64_t pitch, int64_t T, int64_t A, int D, double scale, double* d_lagsum, double* d_bp,
-               int64_t ld_bp, hipStream_t st, bool record_start, bool pm_f32 = false) {
+               int64_t ld_bp, hipStream_t st, bool pm_f32 = false) {
     int rc;
-    ctx->timing_valid = false;
-    if (record_start) {
-        ctx->ev = ctx->ring[ctx->n_calls % ta_ctx::kRing];
-        TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
-        tl_reset(ctx);
-    }
     // float32 device slabs are read as they are by the float32 direct correlators; every other
     // evaluation works on a float64 copy (same layout) in the context's scratch slabs
     const bool direct_on_f32 = pm_f32 && ctx->opt_direct_f32 &&
@@ -706,16 +692,8 @@ int compute_pm(ta_ctx* ctx, int which, const void* pm_vel_any, const void* pm_po
     // ... and by the FFT kernels of the plans without an outer radix (513 ... 10240 frames)
     const bool fft_on_f32 = pm_f32 && which == W_FFT && fft_reads_f32(T);
     if (pm_f32 && !direct_on_f32 && !fft_on_f32) {
-        const size_t n_el = (size_t)((A * D + 1) / 2) * (size_t)pitch * 2;
-        const void* src[2] = {pm_vel_any, pm_pos_any};
-        for (int k = 0; k < 2; ++k) {
-            if (!src[k]) continue;
-            if ((rc = ensure(ctx, ctx->pm_in[k], n_el * sizeof(double)))) return rc;
-            tl_mark(ctx, "k_widen_f32", st);
-            TA_HIP_TRY(ctx, launch_widen_f32((const float*)src[k], (double*)ctx->pm_in[k].p, (long)n_el, st));
-        }
-        pm_vel_any = ctx->pm_in[0].p;
-        if (pm_pos_any) pm_pos_any = ctx->pm_in[1].p;
+        if ((rc = widen_input(ctx, 0, pitch, A * D, st, &pm_vel_any))) return rc;
+        if (pm_pos_any && (rc = widen_input(ctx, 1, pitch, A * D, st, &pm_pos_any))) return rc;
     }
     const double* pm_vel = (const double*)pm_vel_any;
     const double* pm_pos = (const double*)pm_pos_any;
@@ -732,12 +710,7 @@ int compute_pm(ta_ctx* ctx, int which, const void* pm_vel_any, const void* pm_po
         rc = direct_impl(ctx, MODE_HELFAND, pm_vel_any, pm_pos_any, d_masses, T, A, D, pitch, scale, d_lagsum, d_bp,
                          ld_bp, st, true);
     else rc = helfand_impl(ctx, pm_vel, pm_pos, d_masses, pitch, T, A, D, scale, d_lagsum, d_bp, ld_bp, st);
-    if (rc) return rc;
-    tl_mark(ctx, "end", st);
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[3], st));
-    ctx->timing_valid = true;
-    ++ctx->n_calls;
-    return TA_OK;
+    return rc ? rc : call_end(ctx, st);
 }
 
 // frame-major device input of a *_dev entry point -> the context's pair-major scratch slab
@@ -745,8 +718,7 @@ int relayout_input(ta_ctx* ctx, int k, const double* d_src, int64_t T, int64_t n
                    hipStream_t st, const double** out) {
     int rc = ensure(ctx, ctx->pm_in[k], pm_bytes(T, n_cols));
     if (rc) return rc;
-    tl_mark(ctx, "k_relayout", st);
-    TA_HIP_TRY(ctx, launch_relayout(d_src, false, ld_row, n_cols, T, ctx->pm_in[k].p, false, pm_pitch(T), 0, st));
+    TA_LAUNCH(ctx, "k_relayout", st, launch_relayout(d_src, false, ld_row, n_cols, T, ctx->pm_in[k].p, false, pm_pitch(T), 0, st));
     *out = (const double*)ctx->pm_in[k].p;
     return TA_OK;
 }
@@ -762,14 +734,11 @@ int dev_entry(ta_ctx* ctx, int which, const double* d_vel, const double* d_pos, 
     if (d_bp && ld_bp < A) return fail(ctx, TA_E_INVALID, "ld_bp smaller than n_atoms");
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;  // NULL = the legacy default stream, as for any HIP call
-    ctx->timing_valid = false;
-    ctx->ev = ctx->ring[ctx->n_calls % ta_ctx::kRing];
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
-    tl_reset(ctx);
+    if ((rc = call_begin(ctx, st))) return rc;
     const double *pv = nullptr, *px = nullptr;
     if ((rc = relayout_input(ctx, 0, d_vel, T, A * D, ld_row, st, &pv))) return rc;
     if (which == W_HELFAND && (rc = relayout_input(ctx, 1, d_pos, T, A * D, ld_row, st, &px))) return rc;
-    return compute_pm(ctx, which, pv, px, d_masses, pm_pitch(T), T, A, D, scale, d_lagsum, d_bp, ld_bp, st, false);
+    return compute_pm(ctx, which, pv, px, d_masses, pm_pitch(T), T, A, D, scale, d_lagsum, d_bp, ld_bp, st);
 }
 
 // frames committed by ta_stage_commit travel on the context's own stream: a caller's stream that
@@ -792,10 +761,10 @@ int staged_entry(ta_ctx* ctx, int which, const double* d_masses, double scale, d
     if (d_bp && ld_bp < ctx->st_A) return fail(ctx, TA_E_INVALID, "ld_bp smaller than n_atoms");
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = order_after_staging(ctx, (hipStream_t)stream);
-    if (rc) return rc;
+    if (rc || (rc = call_begin(ctx, (hipStream_t)stream))) return rc;
     return compute_pm(ctx, which, ctx->d_slabs[0], need == 2 ? ctx->d_slabs[1] : nullptr, d_masses,
                       ctx->st_pitch, ctx->st_T, ctx->st_A, ctx->st_D, scale, d_lagsum, d_bp, ld_bp,
-                      (hipStream_t)stream, true, ctx->st_dev_f32);
+                      (hipStream_t)stream, ctx->st_dev_f32);
 }
 
 
@@ -805,34 +774,22 @@ int staged_entry(ta_ctx* ctx, int which, const double* d_masses, double scale, d
 int cond_collective(ta_ctx* ctx, bool fft, const double* d_moment, int64_t T, int D, double* d_coll, hipStream_t st) {
     int rc = ensure(ctx, ctx->cond_mpm, pm_bytes(T, D));
     if (rc) return rc;
-    tl_mark(ctx, "k_relayout", st);
-    TA_HIP_TRY(ctx, launch_relayout(d_moment, false, D, D, T, ctx->cond_mpm.p, false, pm_pitch(T), 0, st));
+    TA_LAUNCH(ctx, "k_relayout", st, launch_relayout(d_moment, false, D, D, T, ctx->cond_mpm.p, false, pm_pitch(T), 0, st));
     return msd_impl(ctx, fft, (const double*)ctx->cond_mpm.p, pm_pitch(T), T, 1, D, d_coll, nullptr, 0, st);
 }
 
-// One conductivity call on a pair-major position slab, bracketed by the timing events: the moment pass (and with
-// d_self the weighted slab W = q (x - x[0])), the fixed-order sum of its partials into d_moment, then the self term =
-// the MSD lag sum of W (sum_n q_n^2 MSD_n: the MSD is invariant under the shift and |d(q x)|^2 = q^2 |dx|^2) and the
+// One conductivity call on a pair-major position slab (the caller has opened the call's bracket, it is closed here): the
+// moment pass (and with d_self the weighted slab W = q (x - x[0])), the fixed-order sum of its partials into d_moment,
+// then the self term = the MSD lag sum of W (sum_n q_n^2 MSD_n: the MSD is invariant under the shift and |d(q x)|^2 = q^2 |dx|^2) and the
 // collective Phi of the moment, each by msd_impl.  d_coll / d_self NULL: skipped.  ev[1] / ev[2] bracket the moment
 // pass, unless an FFT evaluation after it records its own forward kernel there.
 int cond_pm(ta_ctx* ctx, bool fft, const void* pm_any, bool pm_f32, int64_t pitch, int64_t T, int64_t A, int D,
-            const double* d_q, double* d_moment, double* d_coll, double* d_self, hipStream_t st, bool record_start) {
+            const double* d_q, double* d_moment, double* d_coll, double* d_self, hipStream_t st) {
     int rc;
-    ctx->timing_valid = false;
-    if (record_start) {
-        ctx->ev = ctx->ring[ctx->n_calls % ta_ctx::kRing];
-        TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
-        tl_reset(ctx);
-    }
     const int64_t n_cols = A * D;
+    // float32 device slabs: a float64 copy first, as for every other evaluation but the float32 kernels
+    if (pm_f32 && (rc = widen_input(ctx, 0, pitch, n_cols, st, &pm_any))) return rc;
     const double* pm = (const double*)pm_any;
-    if (pm_f32) {  // float32 device slabs: a float64 copy first, as for every other evaluation but the float32 kernels
-        const size_t n_el = (size_t)((n_cols + 1) / 2) * (size_t)pitch * 2;
-        if ((rc = ensure(ctx, ctx->pm_in[0], n_el * sizeof(double)))) return rc;
-        tl_mark(ctx, "k_widen_f32", st);
-        TA_HIP_TRY(ctx, launch_widen_f32((const float*)pm_any, (double*)ctx->pm_in[0].p, (long)n_el, st));
-        pm = (const double*)ctx->pm_in[0].p;
-    }
     const int n_parts = cond_moment_parts(ctx->n_cu, (long)T, (long)n_cols);
     if ((rc = ensure(ctx, ctx->cond_part, sizeof(double) * (size_t)n_parts * T * D))) return rc;
     double* W = nullptr;
@@ -840,20 +797,13 @@ int cond_pm(ta_ctx* ctx, bool fft, const void* pm_any, bool pm_f32, int64_t pitc
         if ((rc = ensure(ctx, ctx->cond_w, pm_bytes(T, n_cols)))) return rc;
         W = (double*)ctx->cond_w.p;
     }
-    tl_mark(ctx, "k_cond_moment", st);
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-    TA_HIP_TRY(ctx, launch_cond_moment(pm, (long)pitch, (long)T, (long)n_cols, D, d_q, (double*)ctx->cond_part.p, n_parts,
-                                       W, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-    tl_mark(ctx, "k_sum_partials", st);
-    TA_HIP_TRY(ctx, launch_sum_partials((const double*)ctx->cond_part.p, n_parts, (long)(T * D), d_moment, st));
+    TA_LAUNCH_MAIN(ctx, "k_cond_moment", st,
+                   launch_cond_moment(pm, (long)pitch, (long)T, (long)n_cols, D, d_q, (double*)ctx->cond_part.p, n_parts, W, st));
+    TA_LAUNCH(ctx, "k_sum_partials", st,
+              launch_sum_partials((const double*)ctx->cond_part.p, n_parts, (long)(T * D), d_moment, st));
     if (d_self && (rc = msd_impl(ctx, fft, W, pitch, T, A, D, d_self, nullptr, 0, st))) return rc;
     if (d_coll && (rc = cond_collective(ctx, fft, d_moment, T, D, d_coll, st))) return rc;
-    tl_mark(ctx, "end", st);
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[3], st));
-    ctx->timing_valid = true;
-    ++ctx->n_calls;
-    return TA_OK;
+    return call_end(ctx, st);
 }
 
 int cond_args(ta_ctx* ctx, int fft, const void* charges, const void* moment) {
@@ -889,7 +839,7 @@ const char* ta_last_error(const ta_ctx* ctx) {
 }
 
 int ta_ctx_create(int device, ta_ctx** out) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(nullptr, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, nullptr, [&]() -> int {
     if (!out) return fail(nullptr, TA_E_INVALID, "out is NULL");
     *out = nullptr;
     if (device == TA_DEVICE_CPU) {  // the opt-in CPU backend: no HIP call at all
@@ -933,7 +883,7 @@ int ta_ctx_create(int device, ta_ctx** out) {
 }
 
 int ta_stage_free(ta_ctx* ctx) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
     if (ctx->is_cpu) {
         for (auto& b : ctx->h_blocks)
@@ -965,7 +915,7 @@ int ta_stage_free(ta_ctx* ctx) {
 }
 
 int ta_ctx_destroy(ta_ctx* ctx) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx) return TA_OK;
     if (ctx->is_cpu) {
         ta_stage_free(ctx);
@@ -1002,7 +952,7 @@ int ta_ctx_destroy(ta_ctx* ctx) {
 }
 
 int ta_trim(ta_ctx* ctx) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
     if (ctx->is_cpu) return TA_OK;  // (no workspaces outlive a call)
     if (int rc = commit_flush(ctx)) return rc;
@@ -1021,7 +971,7 @@ int ta_trim(ta_ctx* ctx) {
 }
 
 int ta_set_option(ta_ctx* ctx, const char* key, int64_t value) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx || !key) return fail(ctx, TA_E_INVALID, "null argument");
     if (!strcmp(key, "fft_nwg")) ctx->opt_fft_nwg = value;
     else if (!strcmp(key, "direct_nwg")) ctx->opt_direct_nwg = value;
@@ -1063,7 +1013,7 @@ int ta_set_option(ta_ctx* ctx, const char* key, int64_t value) {
 }
 
 int ta_fft_plan_info(int64_t n_frames, int64_t* m_out, int* n_threads, int* n_stages) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(nullptr, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, nullptr, [&]() -> int {
     int R0 = 0, R = 1;
     if (!wfft_choose((long)n_frames, &R0, &R))
         return fail(nullptr, TA_E_UNSUPPORTED, "n_frames exceeds the largest FFT plan");
@@ -1089,7 +1039,7 @@ std::map<void*, size_t> g_host_blocks;  // base -> mapped length
 extern "C" {
 
 int ta_host_alloc_on(int device, int64_t n_bytes, void** h_out) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(nullptr, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, nullptr, [&]() -> int {
     if (!h_out || n_bytes < 0) return fail(nullptr, TA_E_INVALID, "bad argument");
     *h_out = nullptr;
     // the allocating thread may be a fresh helper thread whose current device is 0: bind it to the
@@ -1126,7 +1076,7 @@ int ta_host_alloc_on(int device, int64_t n_bytes, void** h_out) {
 int ta_host_alloc(int64_t n_bytes, void** h_out) { return ta_host_alloc_on(-1, n_bytes, h_out); }
 
 int ta_host_free(void* h) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(nullptr, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, nullptr, [&]() -> int {
     if (!h) return TA_OK;
     size_t len = 0;
     {
@@ -1233,14 +1183,14 @@ static int stage_alloc_common(ta_ctx* ctx, int64_t n_frames, int64_t n_atoms, in
 
 int ta_stage_alloc(ta_ctx* ctx, int64_t n_frames, int64_t n_atoms, int dim, int dtype, int n_slabs,
                    void** h_slabs) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!h_slabs) return fail(ctx, TA_E_INVALID, "h_slabs is NULL");
     return stage_alloc_common(ctx, n_frames, n_atoms, dim, dtype, n_slabs, h_slabs);
     });
 }
 
 int ta_stage_alloc_device(ta_ctx* ctx, int64_t n_frames, int64_t n_atoms, int dim, int n_slabs) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     return stage_alloc_common(ctx, n_frames, n_atoms, dim, TA_F64, n_slabs, nullptr);
     });
 }
@@ -1336,7 +1286,7 @@ static void commit_worker(ta_ctx* ctx) {
         ctx->cq_busy = true;
         lk.unlock();
         // (an exception on this thread would end the process: it becomes the queued commit's error)
-        const int rc = ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+        const int rc = ta::guarded(fail, ctx, [&]() -> int {
             const int r = job.second > job.first ? stage_commit_now(ctx, job.first, job.second) : TA_OK;  // (an empty job: lock ahead only)
             if (r == TA_OK && ctx->opt_lock_ahead) stage_lock_ahead(ctx, job.second);
             return r;
@@ -1381,7 +1331,7 @@ static void commit_stop(ta_ctx* ctx) {
 extern "C" {
 
 int ta_stage_commit(ta_ctx* ctx, int64_t frame_lo, int64_t frame_hi) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
     if (ctx->st_nslabs == 0) return fail(ctx, TA_E_STATE, "ta_stage_alloc has not been called");
     if (frame_lo < 0 || frame_hi > ctx->st_T || frame_lo > frame_hi)
@@ -1405,7 +1355,7 @@ int ta_stage_commit(ta_ctx* ctx, int64_t frame_lo, int64_t frame_hi) {
 
 int ta_stage_commit_dev(ta_ctx* ctx, int slab, const void* d_src, int dtype, int64_t ld_row,
                         int64_t frame_lo, int64_t frame_hi, void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx || !d_src) return fail(ctx, TA_E_INVALID, "null argument");
     TA_NO_CPU(ctx);
     if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
@@ -1424,7 +1374,7 @@ int ta_stage_commit_dev(ta_ctx* ctx, int slab, const void* d_src, int dtype, int
 
 int ta_stage_synth(ta_ctx* ctx, int slab, uint64_t seed, int64_t col_offset, int64_t n_cols_total,
                    void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
     if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
     if (col_offset < 0 || col_offset + ctx->st_A * ctx->st_D > n_cols_total)
@@ -1442,7 +1392,7 @@ int ta_stage_synth(ta_ctx* ctx, int slab, uint64_t seed, int64_t col_offset, int
 }
 
 int ta_stage_read_dev(ta_ctx* ctx, int slab, double* d_dst, int64_t ld_row, void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx || !d_dst) return fail(ctx, TA_E_INVALID, "null argument");
     TA_NO_CPU(ctx);
     if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
@@ -1456,7 +1406,7 @@ int ta_stage_read_dev(ta_ctx* ctx, int slab, double* d_dst, int64_t ld_row, void
 }
 
 int ta_stage_device(ta_ctx* ctx, int slab, double** d_slab, int64_t* pitch_rows, int64_t* n_pairs) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx || !d_slab) return fail(ctx, TA_E_INVALID, "null argument");
     TA_NO_CPU(ctx);
     if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
@@ -1470,14 +1420,14 @@ int ta_stage_device(ta_ctx* ctx, int slab, double** d_slab, int64_t* pitch_rows,
 /* --------------------------------------------------------- device compute */
 int ta_vacf_fft_dev(ta_ctx* ctx, const double* d_vel, int64_t T, int64_t A, int D, int64_t ld_row,
                     double* d_lagsum, double* d_bp, int64_t ld_bp, void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     return dev_entry(ctx, W_FFT, d_vel, nullptr, nullptr, T, A, D, ld_row, 1.0, d_lagsum, d_bp, ld_bp, stream);
     });
 }
 
 int ta_vacf_direct_dev(ta_ctx* ctx, const double* d_vel, int64_t T, int64_t A, int D, int64_t ld_row,
                        double* d_lagsum, double* d_bp, int64_t ld_bp, void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     return dev_entry(ctx, W_DIRECT, d_vel, nullptr, nullptr, T, A, D, ld_row, 1.0, d_lagsum, d_bp, ld_bp, stream);
     });
 }
@@ -1485,26 +1435,26 @@ int ta_vacf_direct_dev(ta_ctx* ctx, const double* d_vel, int64_t T, int64_t A, i
 int ta_helfand_msd_dev(ta_ctx* ctx, const double* d_vel, const double* d_pos, const double* d_masses,
                        int64_t T, int64_t A, int D, int64_t ld_row, double scale, double* d_lagsum,
                        double* d_bp, int64_t ld_bp, void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     return dev_entry(ctx, W_HELFAND, d_vel, d_pos, d_masses, T, A, D, ld_row, scale, d_lagsum, d_bp, ld_bp, stream);
     });
 }
 
 int ta_vacf_fft_staged(ta_ctx* ctx, double* d_lagsum, double* d_bp, int64_t ld_bp, void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     return staged_entry(ctx, W_FFT, nullptr, 1.0, d_lagsum, d_bp, ld_bp, stream);
     });
 }
 
 int ta_vacf_direct_staged(ta_ctx* ctx, double* d_lagsum, double* d_bp, int64_t ld_bp, void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     return staged_entry(ctx, W_DIRECT, nullptr, 1.0, d_lagsum, d_bp, ld_bp, stream);
     });
 }
 
 int ta_helfand_msd_staged(ta_ctx* ctx, const double* d_masses, double scale, double* d_lagsum,
                           double* d_bp, int64_t ld_bp, void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     return staged_entry(ctx, W_HELFAND, d_masses, scale, d_lagsum, d_bp, ld_bp, stream);
     });
 }
@@ -1518,7 +1468,7 @@ static int msd_which(ta_ctx* ctx, int fft, int* which) {
 
 int ta_msd_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int fft, double* d_lagsum,
                double* d_bp, int64_t ld_bp, void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     int which = 0;
     if (int rc = msd_which(ctx, fft, &which)) return rc;
     return dev_entry(ctx, which, d_pos, nullptr, nullptr, T, A, D, ld_row, 1.0, d_lagsum, d_bp, ld_bp, stream);
@@ -1526,7 +1476,7 @@ int ta_msd_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, in
 }
 
 int ta_msd_staged(ta_ctx* ctx, int fft, double* d_lagsum, double* d_bp, int64_t ld_bp, void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     int which = 0;
     if (int rc = msd_which(ctx, fft, &which)) return rc;
     return staged_entry(ctx, which, nullptr, 1.0, d_lagsum, d_bp, ld_bp, stream);
@@ -1537,41 +1487,37 @@ int ta_msd_staged(ta_ctx* ctx, int fft, double* d_lagsum, double* d_bp, int64_t 
 int ta_conductivity_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int fft,
                         const double* d_charges, double* d_moment, double* d_collective, double* d_self_lagsum,
                         void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     TA_NO_CPU(ctx);
     int rc = check_shape(ctx, T, A, D, ld_row);
     if (rc || (rc = cond_args(ctx, fft, d_charges, d_moment))) return rc;
     if (!d_pos) return fail(ctx, TA_E_INVALID, "null device pointer");
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    ctx->timing_valid = false;
-    ctx->ev = ctx->ring[ctx->n_calls % ta_ctx::kRing];
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
-    tl_reset(ctx);
+    if ((rc = call_begin(ctx, st))) return rc;
     const double* px = nullptr;
     if ((rc = relayout_input(ctx, 0, d_pos, T, A * D, ld_row, st, &px))) return rc;
-    return cond_pm(ctx, fft != 0, px, false, pm_pitch(T), T, A, D, d_charges, d_moment, d_collective, d_self_lagsum, st,
-                   false);
+    return cond_pm(ctx, fft != 0, px, false, pm_pitch(T), T, A, D, d_charges, d_moment, d_collective, d_self_lagsum, st);
     });
 }
 
 int ta_conductivity_staged(ta_ctx* ctx, int fft, const double* d_charges, double* d_moment, double* d_collective,
                            double* d_self_lagsum, void* stream) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
     TA_NO_CPU(ctx);
     int rc = cond_args(ctx, fft, d_charges, d_moment);
     if (rc) return rc;
     if (ctx->st_nslabs < 1) return fail(ctx, TA_E_STATE, "slabs have not been staged");
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = order_after_staging(ctx, (hipStream_t)stream))) return rc;
+    if ((rc = order_after_staging(ctx, (hipStream_t)stream)) || (rc = call_begin(ctx, (hipStream_t)stream))) return rc;
     return cond_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A, ctx->st_D,
-                   d_charges, d_moment, d_collective, d_self_lagsum, (hipStream_t)stream, true);
+                   d_charges, d_moment, d_collective, d_self_lagsum, (hipStream_t)stream);
     });
 }
 
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
     TA_NO_CPU(ctx);
     if (!ctx->timing_valid) return fail(ctx, TA_E_STATE, "no completed compute call to time");
@@ -1586,7 +1532,7 @@ int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
 }
 
 int ta_timing_history(ta_ctx* ctx, int max_n, float* total_ms, float* main_kernel_ms, int* n_out) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx || !n_out) return fail(ctx, TA_E_INVALID, "null argument");
     TA_NO_CPU(ctx);
     const long have = std::min<long>(ctx->n_calls, ta_ctx::kRing);
@@ -1606,7 +1552,7 @@ int ta_timing_history(ta_ctx* ctx, int max_n, float* total_ms, float* main_kerne
 }
 
 int ta_clock_probe(ta_ctx* ctx, int n_launches, double* mhz, double* cycles_per_unit_pass, double* ms_per_launch) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
     TA_NO_CPU(ctx);
     if (ctx->st_nslabs < 1) return fail(ctx, TA_E_STATE, "slabs have not been staged");
@@ -1664,7 +1610,7 @@ int ta_clock_probe(ta_ctx* ctx, int n_launches, double* mhz, double* cycles_per_
 }
 
 int ta_kernel_timeline(ta_ctx* ctx, int max_n, const char** names, float* ms, int* n_out) {
-    return ta::guard([&](int c_, const std::string& m_) { return fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx || !n_out) return fail(ctx, TA_E_INVALID, "null argument");
     TA_NO_CPU(ctx);
     *n_out = 0;
@@ -1750,8 +1696,9 @@ int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, do
         const size_t off = (size_t)pair_lo * ctx->st_pitch * (ctx->st_dev_f32 ? 8 : 16);  // bytes
         const void* v = (const char*)ctx->d_slabs[0] + off;
         const void* x = need == 2 ? (const char*)ctx->d_slabs[1] + off : nullptr;
-        if ((rc = compute_pm(ctx, which, v, x, d_m ? d_m + lo : nullptr, ctx->st_pitch, T, hi - lo, D, scale,
-                             d_ls + b * T, d_bp + lo, A, ctx->stream, true, ctx->st_dev_f32)))
+        if ((rc = call_begin(ctx, ctx->stream)) ||
+            (rc = compute_pm(ctx, which, v, x, d_m ? d_m + lo : nullptr, ctx->st_pitch, T, hi - lo, D, scale,
+                             d_ls + b * T, d_bp + lo, A, ctx->stream, ctx->st_dev_f32)))
             return rc;
         TA_HIP_TRY(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
         TA_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_stage, 0));
@@ -1779,9 +1726,9 @@ int cond_launch(ta_ctx* ctx, int fft, const double* h_q, bool coll, bool self, d
     if (rc || (rc = ensure(ctx, ctx->cond_out, sizeof(double) * (size_t)T * (D + 2)))) return rc;
     double* out = (double*)ctx->cond_out.p;
     TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->cond_q.p, h_q, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = order_after_staging(ctx, ctx->stream))) return rc;
+    if ((rc = order_after_staging(ctx, ctx->stream)) || (rc = call_begin(ctx, ctx->stream))) return rc;
     if ((rc = cond_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, T, A, D, (const double*)ctx->cond_q.p,
-                      out, coll ? out + T * D : nullptr, self ? out + T * (D + 1) : nullptr, ctx->stream, true)))
+                      out, coll ? out + T * D : nullptr, self ? out + T * (D + 1) : nullptr, ctx->stream)))
         return rc;
     *d_out = out;
     return TA_OK;
@@ -1810,22 +1757,12 @@ int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes) {
     const size_t bytes = box.tab.size() * sizeof(double);
     if ((rc = ensure(ctx, ctx->unwrap_box, bytes))) return rc;
     hipStream_t st = ctx->stream;
-    ctx->timing_valid = false;
-    ctx->ev = ctx->ring[ctx->n_calls % ta_ctx::kRing];
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
-    tl_reset(ctx);
-    tl_mark(ctx, "box_copy", st);
-    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->unwrap_box.p, box.tab.data(), bytes, hipMemcpyHostToDevice, st));
-    tl_mark(ctx, box.triclinic ? "k_unwrap_tric" : "k_unwrap_ortho", st);
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-    TA_HIP_TRY(ctx, launch_unwrap(ctx->d_slabs[slab], (long)ctx->st_pitch, (long)ctx->st_T, (long)ctx->st_A, ctx->st_D, axes,
-                                  box.triclinic, box.per_frame, (const double*)ctx->unwrap_box.p, (long)box.tpitch, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-    tl_mark(ctx, "end", st);
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[3], st));
-    ctx->timing_valid = true;
-    ++ctx->n_calls;
-    return TA_OK;
+    if ((rc = call_begin(ctx, st))) return rc;
+    TA_LAUNCH(ctx, "box_copy", st, hipMemcpyAsync(ctx->unwrap_box.p, box.tab.data(), bytes, hipMemcpyHostToDevice, st));
+    TA_LAUNCH_MAIN(ctx, box.triclinic ? "k_unwrap_tric" : "k_unwrap_ortho", st,
+                   launch_unwrap(ctx->d_slabs[slab], (long)ctx->st_pitch, (long)ctx->st_T, (long)ctx->st_A, ctx->st_D, axes,
+                                 box.triclinic, box.per_frame, (const double*)ctx->unwrap_box.p, (long)box.tpitch, st));
+    return call_end(ctx, st);
 }
 int host_wait(ta_ctx* ctx) {
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -206,7 +206,7 @@ extern "C" {
 
 int ta_stage_frame(ta_ctx* ctx, int slab, int64_t frame, const void* h_src, int src_dtype, int64_t ld_row, int col0,
                    int col_step, int n_col, int64_t atom_lo, const int64_t* h_index, int64_t n_atoms) {
-    return ta::guard([&](int c_, const std::string& m_) { return ta::ctx_fail(ctx, c_, m_); }, [&]() -> int {
+    return ta::guarded(ta::ctx_fail, ctx, [&]() -> int {
     if (!ctx) return ta::ctx_fail(nullptr, TA_E_INVALID, "null context");
     void* h = nullptr;
     int64_t T = 0, A = 0;
@@ -228,7 +228,7 @@ int ta_stage_frame(ta_ctx* ctx, int slab, int64_t frame, const void* h_src, int 
 
 int ta_group_stage_frame(ta_group* g, int slab, int64_t frame, const void* h_src, int src_dtype, int64_t ld_row, int col0,
                          int col_step, int n_col, int64_t atom_lo, const int64_t* h_index, int64_t n_atoms) {
-    return ta::guard([&](int c_, const std::string& m_) { return ta::ctx_fail(nullptr, c_, m_); }, [&]() -> int {
+    return ta::guarded(ta::ctx_fail, nullptr, [&]() -> int {
     const int n = ta_group_size(g);
     if (n < 1) return TA_E_INVALID;
     std::vector<Job> jobs;

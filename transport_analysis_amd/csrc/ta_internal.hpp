@@ -46,6 +46,13 @@ int guard(Report&& report, Body&& body) noexcept {
     }
 }
 
+// ... with the reporter nearly every entry point uses: the file's `fail(owner, code, text)` on the call's context / group
+// (NULL where there is none).  An entry point whose reporter does more (waits for queued work first) spells it out with guard.
+template <class Fail, class Owner, class Body>
+int guarded(Fail fail, Owner owner, Body&& body) noexcept {
+    return guard([&](int code, const std::string& text) { return fail(owner, code, text); }, body);
+}
+
 // api.hip, for group.hip (several contexts driven by one host thread): one context's share of a
 // host-facing call queued on its streams (which: 0 FFT VACF, 1 windowed VACF, 2 Helfand, 3 / 4 Einstein MSD by the FFT /
 // direct form), the sum
