@@ -8,6 +8,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <deque>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <new>
@@ -28,52 +29,135 @@ namespace {
 
 thread_local std::string g_tls_error;
 
+// A device workspace of a context.  Each one is a member of ta_ctx declared once, with whether ta_trim releases it; the
+// constructor enters it in the context's list, which is what ta_trim and ta_ctx_destroy walk.
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    const bool trimmed;
+    DevBuf(std::vector<DevBuf*>& list, bool trimmed_by_ta_trim) : trimmed(trimmed_by_ta_trim) { list.push_back(this); }
+    DevBuf(const DevBuf&) = delete;
+    void release() {
+        if (p) hipFree(p);
+        p = nullptr, bytes = 0;
+    }
+};
+constexpr bool kTrimmed = true, kKept = false;
+
+// ta_stage_commit hands its frame range to a worker thread that makes the HIP calls (copies in pieces, the transposition
+// launches): the caller's frame loop never waits on the runtime — which it did, for as long as another thread's
+// hipHostMalloc of the by-particle result held the runtime's lock (0.17 s of a 0.6 s loop at 10000 x 50000 x 3).
+// The rules:
+//   - the worker is the only thread that touches the slabs and the context's streams while a job is queued or running;
+//     every other entry that touches them calls flush() first (order_after_staging does);
+//   - push() never fails and never waits; a job's error is kept (the first one only) and returned ONCE, by the next
+//     flush(), with the prefix "queued ta_stage_commit: ";
+//   - the thread starts with the first push() and ends in stop(), which drains the queue first; an empty job
+//     (frame_lo == frame_hi) copies nothing and only page-locks ahead (ta_stage_alloc queues one).
+class CommitQueue {
+public:
+    explicit CommitQueue(ta_ctx* owner) : ctx_(owner) {}
+    void push(int64_t frame_lo, int64_t frame_hi);
+    int flush();  // every queued job has made its HIP calls (their work is queued on the context's streams)
+    void stop();
+
+private:
+    void run();
+    ta_ctx* ctx_;
+    std::thread thread_;
+    std::mutex m_;
+    std::condition_variable cv_;
+    std::deque<std::pair<int64_t, int64_t>> jobs_;
+    bool stop_ = false, busy_ = false;
+    int rc_ = TA_OK;
+    std::string err_;
 };
 
 }  // namespace
 
+// Every option of ta_set_option: X(key, default, hook) declares the field ctx->opt_<key> and its row of the table
+// ta_set_option looks the key up in.  A hook (NULL: a plain store) runs before the store and may reject the value.
+#define TA_OPTIONS(X)                                                                                                      \
+    X(fft_nwg, 0, nullptr)         /* workgroups of the FFT kernels (0: by the device) */                                  \
+    X(direct_nwg, 0, nullptr)      /* workgroups of k_direct (0: by the device) */                                         \
+    X(direct_f32, 0, nullptr)      /* the float32 option of the O(T^2) correlators */                                      \
+    X(direct_groups, 0, nullptr)   /* cap on k_direct's column groups per workgroup */                                     \
+    X(direct_chunk, 0, nullptr)    /* k_direct's lags per chunk: 8 or 10 (0: by n_frames) */                               \
+    X(direct_mfma, 1, opt_check_direct_mfma) /* which kernel evaluates a direct request: see direct_form */                \
+    X(helfand_fft, 0, nullptr)     /* Helfand as S1 - 2 S2 where an FFT plan exists */                                     \
+    X(bp_block, 0, nullptr)        /* atoms per block of a host-facing by-particle call (0: 16384) */                      \
+    X(bp_spec_atoms, 0, nullptr)   /* atoms per block of spectra in the two-kernel by-particle path (0: 2.5 GiB's worth) */ \
+    X(bp_prefetch, 2, nullptr)     /* k_winverse's prefetch depth */                                                       \
+    /* "short_max": trajectories of up to this many frames (<= 64) take the register-resident kernels of short_kernels.hpp \
+       wherever float64 slabs are asked for a by-particle array or an O(T^2) form (0: never); "short_lags_max": the FFT    \
+       path's lag sums alone as well, up to this many frames (per 12 GB: 2.1 against 3.9 ms at 32 frames, 3.8 against 4.6  \
+       at 48, 4.1 against 3.8 at 64: profiles/r06_short.txt) */                                                           \
+    X(short_max, 64, nullptr)                                                                                              \
+    X(short_lags_max, 48, nullptr)                                                                                         \
+    X(mid_max, 512, nullptr)       /* k_mid (mid_kernels.hpp) under "direct_mfma" 1: see direct_form */                    \
+    X(mid_all, 0, nullptr)                                                                                                 \
+    X(mid_ncl, 0, nullptr)                                                                                                 \
+    X(direct_subwave, 1, nullptr)  /* k_direct's column groups may be 16 or 32 lanes (under ~640 frames) */                \
+    X(stage_device_f32, 0, nullptr) /* device slabs hold float32 when nothing wider is coming in */                        \
+    X(timeline, 0, nullptr)        /* record the kernel timeline of every compute call (ta_kernel_timeline) */             \
+    X(async_commit, 1, opt_flush_commits) /* ta_stage_commit goes through the commit queue; flushed before it changes */   \
+    X(lock_ahead, 1, nullptr)      /* the commit worker page-locks the chunks behind the one it committed */               \
+    X(cpu_threads, 0, opt_set_cpu_threads) /* CPU backend: OpenMP team size (0: the runtime's default) */                  \
+    X(fail_alloc_after, 0, nullptr) /* test hooks of ensure(): the n-th call from now throws std::bad_alloc ... */         \
+    X(fail_throw_after, 0, nullptr) /* ... or std::runtime_error */
+
 struct ta_ctx {
     // a CPU context (ta_ctx_create(TA_DEVICE_CPU, ...): the opt-in backend of cpu_backend.cpp) owns host slabs only;
-    // no HIP call is ever made on its behalf and every device-facing entry point rejects it (TA_NO_CPU)
+    // no HIP call is ever made on its behalf and every device-facing entry point rejects it (TA_NO_CPU).  Its entry
+    // points branch to the cpu_* functions below (the seam) and nowhere else.
     bool is_cpu = false;
-    ta::cpu::State cpu;
+    int cpu_threads = 1;  // OpenMP team size of the CPU backend
     int device = 0;
     int n_cu = 256;
     hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr;  // device->host copies of by-particle blocks (host_compute)
+    hipStream_t copy_stream = nullptr;  // device->host copies of by-particle blocks (host_launch)
     std::string err;
     std::map<int, cd*> wf_tables;  // wfft.hip twiddle tables, keyed by 64 * R0 + R
-    DevBuf partial, spec, ts_partial, out_lagsum, out_bp, masses, bounce, stage_buf, helf_p, helf_small;
-    DevBuf pm_in[2];  // pair-major copies of frame-major *_dev inputs
-    DevBuf bp_scratch;  // atom-major by-particle results before the transposition
-    DevBuf bp_spec;     // per-atom power spectra of one block of atoms (two-kernel by-particle path)
-    DevBuf unit_counter;  // k_band_bp_vacf's work counter
+    // ---- device workspaces: this is the one list of them (kTrimmed: ta_trim releases it, kKept: it does not)
+    std::vector<DevBuf*> workspaces;
+    DevBuf partial{workspaces, kTrimmed}, spec{workspaces, kTrimmed}, ts_partial{workspaces, kTrimmed};
+    DevBuf out_lagsum{workspaces, kKept}, out_bp{workspaces, kTrimmed}, masses{workspaces, kKept};
+    DevBuf stage_buf{workspaces, kTrimmed}, helf_p{workspaces, kTrimmed}, helf_small{workspaces, kTrimmed};
+    DevBuf pm_in[2] = {{workspaces, kTrimmed}, {workspaces, kTrimmed}};  // pair-major copies of frame-major *_dev inputs
+    DevBuf bp_scratch{workspaces, kTrimmed};    // atom-major by-particle results before the transposition
+    DevBuf bp_spec{workspaces, kTrimmed};       // per-atom power spectra of one block of atoms (two-kernel by-particle path)
+    DevBuf unit_counter{workspaces, kKept};     // k_band_bp_vacf's work counter
     // conductivity (cond_pm): the moment's partial sums, the weighted slab of the self term (the input's size), the
     // charges and outputs of host-facing calls, the pair-major copy of the (n_frames, dim) moment
-    DevBuf cond_part, cond_w, cond_q, cond_out, cond_mpm;
-    DevBuf unwrap_box;  // ta_unwrap: the box table (unwrap_box.hpp) of the last call
-    // staging: pinned host slabs keep the reference's (n_frames, n_atoms, dim) layout, the
-    // device slabs are pair-major (layout.hip) with st_pitch rows per column pair
+    DevBuf cond_part{workspaces, kTrimmed}, cond_w{workspaces, kTrimmed}, cond_q{workspaces, kKept};
+    DevBuf cond_out{workspaces, kKept}, cond_mpm{workspaces, kTrimmed};
+    DevBuf unwrap_box{workspaces, kTrimmed};    // ta_unwrap: the box table (unwrap_box.hpp) of the last call
+    // staging: two landing buffers, so that a piece crosses PCIe while the one before it is transposed
+    DevBuf bounce{workspaces, kTrimmed}, bounce2{workspaces, kTrimmed};
+    DevBuf clock_stamps{workspaces, kTrimmed};  // ta_clock_probe: the stamps of its last launch
+    // ---- staging: pinned host slabs keep the reference's (n_frames, n_atoms, dim) layout, the device slabs are
+    // pair-major (layout.hip) with st_pitch rows per column pair.  This is the one record of the staged shape, for GPU
+    // and CPU contexts alike (a CPU context has host slabs only).
     int64_t st_T = 0, st_A = 0, st_pitch = 0;
     int st_D = 0, st_dtype = TA_F64, st_nslabs = 0;
     bool st_dev_f32 = false;  // device slabs hold float32 elements ("stage_device_f32")
     std::vector<void*> h_slabs;
     std::vector<HostBlock> h_blocks;  // the mapping behind h_slabs[i] (base == NULL: a hipHostMalloc block, the fallback)
     std::vector<double*> d_slabs;
-    // timing: a ring of event quadruples, one per compute call (start, main kernel start,
-    // main kernel end, end), so a caller can time K calls back to back and read all K
-    // durations afterwards (ta_timing_history) instead of synchronising inside its loop
+    hipStream_t relayout_stream = nullptr;  // the transpositions of ta_stage_commit
+    hipEvent_t ev_piece[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
+    CommitQueue commits{this};
+    // ---- timing: a ring of event quadruples, one per compute call (start, main kernel start, main kernel end, end), so
+    // a caller can time K calls back to back and read all K durations afterwards (ta_timing_history) instead of
+    // synchronising inside its loop
     static constexpr int kRing = 64;
     hipEvent_t ring[kRing][4] = {};
     hipEvent_t* ev = ring[0];
     hipEvent_t ev_stage = nullptr;  // orders a caller's stream behind the staging stream
     long n_calls = 0;  // compute calls completed (their events recorded)
     bool timing_valid = false;
-    // kernel timeline of the last compute call ("timeline" option): an event before every
-    // launch, a last one at the end; segment i = [mark i, mark i + 1) belongs to name i
+    // kernel timeline of the last compute call ("timeline" option): an event before every launch, a last one at the
+    // end; segment i = [mark i, mark i + 1) belongs to name i
     struct Mark {
         const char* name;
         hipEvent_t ev;
@@ -81,51 +165,11 @@ struct ta_ctx {
     std::vector<Mark> marks;
     std::vector<hipEvent_t> mark_pool;
     size_t marks_used = 0;
-    int64_t opt_timeline = 0;
-    // staging: second landing buffer + stream, so that a piece crosses PCIe while the one before
-    // it is transposed
-    DevBuf bounce2;
-    hipStream_t relayout_stream = nullptr;
-    hipEvent_t ev_piece[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
-    // options
-    int64_t opt_fft_nwg = 0;
-    int64_t opt_direct_nwg = 0;
-    int64_t opt_direct_f32 = 0;
-    int64_t opt_direct_groups = 0;
-    int64_t opt_direct_chunk = 0;
-    int64_t opt_direct_mfma = 1;  // windowed VACF lag sums without the by-particle array: matrix-core kernel
-    int64_t opt_helfand_fft = 0;
-    int64_t opt_bp_block = 0;
-    int64_t opt_bp_spec_atoms = 0;
-    int64_t opt_bp_prefetch = 2;
-    // "short_max": trajectories of up to this many frames (<= 64) take the register-resident kernels of short_kernels.hpp
-    // wherever float64 slabs are asked for a by-particle array or an O(T^2) form (0: never); "short_lags_max": the FFT
-    // path's lag sums alone as well, up to this many frames (per 12 GB: 2.1 against 3.9 ms at 32 frames, 3.8 against 4.6 at
-    // 48, 4.1 against 3.8 at 64: profiles/r06_short.txt)
-    int64_t opt_short_max = 64, opt_short_lags_max = 48;
-    int64_t opt_mid_max = 512, opt_mid_all = 0, opt_mid_ncl = 0;  // k_mid (mid_kernels.hpp) under "direct_mfma" 1: see direct_impl
-    int64_t opt_direct_subwave = 1;  // "direct_subwave": k_direct's column groups may be 16 or 32 lanes (under ~640 frames)
-    int64_t opt_stage_device_f32 = 0;
-    int64_t opt_fail_alloc_after = 0, opt_fail_throw_after = 0;  // test hooks of ensure()
-    // ta_stage_commit hands its frame range to a worker thread that makes the HIP calls (copies in pieces, the
-    // transposition launches): the caller's frame loop never waits on the runtime — which it did, for as long
-    // as another thread's hipHostMalloc of the by-particle result held the runtime's lock (0.17 s of a 0.6 s
-    // loop at 10000 x 50000 x 3).  Everything that touches the slabs or the streams joins the queue first
-    // (commit_flush); an error of a queued commit is returned there.
-    int64_t opt_async_commit = 1;
-    int64_t opt_lock_ahead = 1;  // "lock_ahead": the commit worker page-locks the chunks behind the one it committed
-    std::thread cq_thread;
-    std::mutex cq_m;
-    std::condition_variable cq_cv;
-    std::deque<std::pair<int64_t, int64_t>> cq;
-    bool cq_stop = false, cq_busy = false;
-    int cq_rc = TA_OK;
-    std::string cq_err;
+    // ---- options
+#define X(key, dflt, hook) int64_t opt_##key = dflt;
+    TA_OPTIONS(X)
+#undef X
 };
-
-int commit_flush(ta_ctx* ctx);  // (defined with ta_stage_commit)
-static void commit_stop(ta_ctx* ctx);
-static void commit_worker(ta_ctx* ctx);
 
 namespace {
 
@@ -143,10 +187,9 @@ int fail(ta_ctx* ctx, int code, const std::string& msg) noexcept {
     return code;
 }
 
-#define TA_NO_CPU(ctx)                                                                                                   \
+#define TA_CHECK(expr)                                                                                                    \
     do {                                                                                                                  \
-        if ((ctx) && (ctx)->is_cpu)                                                                                       \
-            return fail(ctx, TA_E_UNSUPPORTED, "not available on the CPU backend (device pointers, streams and kernel timings belong to GPU contexts)"); \
+        if (int rc_ = (expr)) return rc_;                                                                                 \
     } while (0)
 
 #define TA_HIP_TRY(ctx, expr)                                                                  \
@@ -157,17 +200,47 @@ int fail(ta_ctx* ctx, int code, const std::string& msg) noexcept {
                         std::string(#expr) + ": " + hipGetErrorString(_e));                    \
     } while (0)
 
+// ---- the argument and state checks of the entry points, each message written once -------------------------------------
+int need_ctx(ta_ctx* ctx) { return ctx ? TA_OK : fail(nullptr, TA_E_INVALID, "null context"); }
+int no_cpu(ta_ctx* ctx) {
+    if (ctx && ctx->is_cpu)
+        return fail(ctx, TA_E_UNSUPPORTED, "not available on the CPU backend (device pointers, streams and kernel timings belong to GPU contexts)");
+    return TA_OK;
+}
+#define TA_NO_CPU(ctx) TA_CHECK(no_cpu(ctx))
+int check_staged(ta_ctx* ctx, int n_slabs = 1) {
+    return ctx->st_nslabs >= n_slabs ? TA_OK : fail(ctx, TA_E_STATE, "slabs have not been staged");
+}
+int check_slab(ta_ctx* ctx, int slab) {
+    return slab >= 0 && slab < ctx->st_nslabs ? TA_OK : fail(ctx, TA_E_INVALID, "no such slab");
+}
+int check_frames(ta_ctx* ctx, int64_t frame_lo, int64_t frame_hi) {
+    if (frame_lo < 0 || frame_hi > ctx->st_T || frame_lo > frame_hi) return fail(ctx, TA_E_INVALID, "frame range out of bounds");
+    return TA_OK;
+}
+int check_ld_row(ta_ctx* ctx, int64_t ld_row, int64_t n_cols) {
+    return ld_row >= n_cols ? TA_OK : fail(ctx, TA_E_INVALID, "ld_row smaller than n_atoms*dim");
+}
+int check_fft(ta_ctx* ctx, int fft) { return fft == 0 || fft == 1 ? TA_OK : fail(ctx, TA_E_INVALID, "fft must be 0 or 1"); }
+int check_dtype(ta_ctx* ctx, int dtype) {
+    return dtype == TA_F32 || dtype == TA_F64 ? TA_OK : fail(ctx, TA_E_INVALID, "bad dtype");
+}
+int check_shape(ta_ctx* ctx, int64_t T, int64_t A, int D, int64_t ld_row) {
+    TA_CHECK(need_ctx(ctx));
+    if (T < 1 || A < 1 || D < 1 || D > 3)
+        return fail(ctx, TA_E_INVALID, "need n_frames >= 1, n_atoms >= 1, 1 <= dim <= 3");
+    TA_CHECK(check_ld_row(ctx, ld_row, A * D));
+    if (T > (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, "n_frames too large");
+    return TA_OK;
+}
+
 int ensure(ta_ctx* ctx, DevBuf& b, size_t bytes) {
     // test hooks ("fail_alloc_after" / "fail_throw_after" n): the n-th call from now throws what a failing host allocation /
     // any other library exception would, so that the tests can see the C boundary turn it into a status
     if (ctx->opt_fail_alloc_after > 0 && --ctx->opt_fail_alloc_after == 0) throw std::bad_alloc();
     if (ctx->opt_fail_throw_after > 0 && --ctx->opt_fail_throw_after == 0) throw std::runtime_error("fail_throw_after");
     if (b.bytes >= bytes && b.p) return TA_OK;
-    if (b.p) {
-        hipFree(b.p);
-        b.p = nullptr;
-        b.bytes = 0;
-    }
+    b.release();
     if (bytes == 0) bytes = 16;
     TA_HIP_TRY(ctx, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
@@ -213,15 +286,6 @@ int get_wf_table(ta_ctx* ctx, int R0, int R, cd** out) {
     }
     ctx->wf_tables[key] = d;
     *out = d;
-    return TA_OK;
-}
-
-int check_shape(ta_ctx* ctx, int64_t T, int64_t A, int D, int64_t ld_row) {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
-    if (T < 1 || A < 1 || D < 1 || D > 3)
-        return fail(ctx, TA_E_INVALID, "need n_frames >= 1, n_atoms >= 1, 1 <= dim <= 3");
-    if (ld_row < A * D) return fail(ctx, TA_E_INVALID, "ld_row smaller than n_atoms*dim");
-    if (T > (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, "n_frames too large");
     return TA_OK;
 }
 
@@ -667,9 +731,6 @@ int msd_impl(ta_ctx* ctx, bool fft, const double* pm_pos, int64_t pitch, int64_t
     return direct_impl(ctx, MODE_MSD, pm_pos, nullptr, nullptr, T, A, D, pitch, 1.0, d_lagsum, d_bp, ld_bp, st);
 }
 
-enum { W_FFT = 0, W_DIRECT = 1, W_HELFAND = 2, W_MSD_FFT = 3, W_MSD_DIRECT = 4 };
-inline bool is_msd(int which) { return which == W_MSD_FFT || which == W_MSD_DIRECT; }
-
 // float32 device slab -> *pm: its float64 copy (same layout) in the context's scratch slab k
 int widen_input(ta_ctx* ctx, int k, int64_t pitch, int64_t n_cols, hipStream_t st, const void** pm) {
     const size_t n_el = (size_t)((n_cols + 1) / 2) * (size_t)pitch * 2;
@@ -744,7 +805,7 @@ int dev_entry(ta_ctx* ctx, int which, const double* d_vel, const double* d_pos, 
 // frames committed by ta_stage_commit travel on the context's own stream: a caller's stream that
 // is about to touch the slabs waits for them (a no-op when nothing is pending)
 int order_after_staging(ta_ctx* ctx, hipStream_t st) {
-    if (int rc = commit_flush(ctx)) return rc;  // queued commits have made their calls on ctx->stream
+    if (int rc = ctx->commits.flush()) return rc;  // queued commits have made their calls on ctx->stream
     if (st == ctx->stream) return TA_OK;
     TA_HIP_TRY(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
     TA_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_stage, 0));
@@ -753,10 +814,10 @@ int order_after_staging(ta_ctx* ctx, hipStream_t st) {
 
 int staged_entry(ta_ctx* ctx, int which, const double* d_masses, double scale, double* d_lagsum,
                  double* d_bp, int64_t ld_bp, void* stream) {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    TA_CHECK(need_ctx(ctx));
     TA_NO_CPU(ctx);
-    const int need = which == W_HELFAND ? 2 : 1;
-    if (ctx->st_nslabs < need) return fail(ctx, TA_E_STATE, "slabs have not been staged");
+    const int need = slabs_needed(which);
+    TA_CHECK(check_staged(ctx, need));
     if (!d_lagsum || (which == W_HELFAND && !d_masses)) return fail(ctx, TA_E_INVALID, "null device pointer");
     if (d_bp && ld_bp < ctx->st_A) return fail(ctx, TA_E_INVALID, "ld_bp smaller than n_atoms");
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -807,11 +868,97 @@ int cond_pm(ta_ctx* ctx, bool fft, const void* pm_any, bool pm_f32, int64_t pitc
 }
 
 int cond_args(ta_ctx* ctx, int fft, const void* charges, const void* moment) {
-    if (fft != 0 && fft != 1) return fail(ctx, TA_E_INVALID, "fft must be 0 or 1");
+    TA_CHECK(check_fft(ctx, fft));
     if (!charges) return fail(ctx, TA_E_INVALID, "charges are NULL");
     if (!moment) return fail(ctx, TA_E_INVALID, "moment output is NULL");
     return TA_OK;
 }
+
+// ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
+// This is the seam: a CPU context's staging and host-facing calls end up in the cpu_* functions below, reached by one
+// early branch of their entry point (after the checks both kinds of context share); nothing below makes a HIP call.
+void set_staged(ta_ctx* ctx, int64_t T, int64_t A, int D, int dtype, int n_slabs, bool dev_f32) {
+    ctx->st_T = T, ctx->st_A = A, ctx->st_D = D, ctx->st_dtype = dtype, ctx->st_nslabs = n_slabs;
+    ctx->st_dev_f32 = dev_f32;
+    ctx->st_pitch = pm_pitch(T);
+}
+
+// what cpu_backend.cpp works on: the staged shape and the host slabs, read where they are
+ta::cpu::State cpu_state(const ta_ctx* ctx) {
+    ta::cpu::State s;
+    s.T = ctx->st_T, s.A = ctx->st_A, s.D = ctx->st_D, s.dtype = ctx->st_dtype, s.threads = ctx->cpu_threads;
+    s.slabs = ctx->h_slabs;
+    return s;
+}
+
+// host slabs in the reference's (n_frames, n_atoms, dim) layout, zero-filled mappings like the GPU contexts' (never
+// page-locked)
+int cpu_stage_alloc(ta_ctx* ctx, int64_t n_frames, int64_t n_atoms, int dim, int dtype, int n_slabs, void** h_slabs) {
+    if (!h_slabs) return fail(ctx, TA_E_UNSUPPORTED, "the CPU backend has no device slabs");
+    ta_stage_free(ctx);
+    const size_t bytes = (size_t)n_frames * n_atoms * dim * (dtype == TA_F32 ? 4 : 8);
+    for (int i = 0; i < n_slabs; ++i) {
+        HostBlock blk;
+        if (host_block_map(bytes, &blk) != 0) {
+            ta_stage_free(ctx);
+            return fail(ctx, TA_E_NOMEM, "staging allocation failed: no host memory for the slab");
+        }
+        ctx->h_slabs.push_back(blk.base);
+        ctx->h_blocks.push_back(blk);
+        h_slabs[i] = blk.base;
+    }
+    set_staged(ctx, n_frames, n_atoms, dim, dtype, n_slabs, false);
+    return TA_OK;
+}
+
+// the mean over atoms of a lag-indexed sum (velocityautocorr.py:214,237; viscosity.py:233)
+void atom_mean(const ta_ctx* ctx, double* h_ts) {
+    const double n_at = (double)ctx->st_A;
+    for (int64_t k = 0; k < ctx->st_T; ++k) h_ts[k] /= n_at;
+}
+
+int cpu_compute(ta_ctx* ctx, int which, const double* h_masses, double scale, double* h_ts, double* h_bp) {
+    TA_CHECK(check_staged(ctx, slabs_needed(which)));
+    if (which == W_HELFAND && !h_masses) return fail(ctx, TA_E_INVALID, "h_masses is NULL");
+    const ta::cpu::State s = cpu_state(ctx);
+    const int rc = which == W_FFT      ? ta::cpu::vacf_fft(s, h_ts, h_bp)
+                   : which == W_DIRECT ? ta::cpu::vacf_direct(s, h_ts, h_bp)
+                   : is_msd(which)     ? ta::cpu::msd(s, which == W_MSD_FFT, h_ts, h_bp)
+                                       : ta::cpu::helfand(s, h_masses, scale, h_ts, h_bp);
+    if (rc) return fail(ctx, rc, "CPU backend: out of host memory");
+    atom_mean(ctx, h_ts);
+    return TA_OK;
+}
+
+int cpu_conductivity(ta_ctx* ctx, bool fft, const double* h_charges, double* h_moment, double* h_collective,
+                     double* h_self_lagsum) {
+    if (int rc = ta::cpu::conductivity(cpu_state(ctx), fft, h_charges, h_moment, h_collective, h_self_lagsum))
+        return fail(ctx, rc, "CPU backend: out of host memory");
+    return TA_OK;
+}
+
+// ---- options: the table behind ta_set_option ------------------------------------------------------------------------
+int opt_check_direct_mfma(ta_ctx* ctx, int64_t value) {
+    if (value != 0 && value != 1 && value != 3)
+        return fail(ctx, TA_E_INVALID, "direct_mfma: 0 vector kernels, 1 by trajectory length (default), 3 matrix cores always "
+                                       "(2, the column-packed forms, left the library in round 6: tools/band/)");
+    return TA_OK;
+}
+int opt_set_cpu_threads(ta_ctx* ctx, int64_t value) {
+    if (value < 0 || value > 4096) return fail(ctx, TA_E_INVALID, "cpu_threads: 0 (default) .. 4096");
+    ctx->cpu_threads = value > 0 ? (int)value : ta::cpu::hardware_threads();
+    return TA_OK;
+}
+int opt_flush_commits(ta_ctx* ctx, int64_t) { return ctx->commits.flush(); }
+
+struct Option {
+    const char* key;
+    int64_t ta_ctx::*field;
+    int (*hook)(ta_ctx*, int64_t);
+};
+#define X(key, dflt, hook) {#key, &ta_ctx::opt_##key, hook},
+const Option kOptions[] = {TA_OPTIONS(X)};
+#undef X
 
 }  // namespace
 
@@ -849,7 +996,7 @@ int ta_ctx_create(int device, ta_ctx** out) {
         c->is_cpu = true;
         c->device = TA_DEVICE_CPU;
         c->n_cu = 0;
-        c->cpu.threads = ta::cpu::hardware_threads();
+        c->cpu_threads = ta::cpu::hardware_threads();
         *out = c;
         return TA_OK;
     }
@@ -884,28 +1031,20 @@ int ta_ctx_create(int device, ta_ctx** out) {
 
 int ta_stage_free(ta_ctx* ctx) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
-    if (ctx->is_cpu) {
-        for (auto& b : ctx->h_blocks)
-            if (b.base) host_block_unmap(b);
-        ctx->h_blocks.clear();
-        ctx->h_slabs.clear();
-        ctx->cpu.slabs.clear();
-        ctx->st_nslabs = 0;
-        ctx->st_T = ctx->st_A = ctx->st_pitch = 0;
-        return TA_OK;
+    TA_CHECK(need_ctx(ctx));
+    if (!ctx->is_cpu) {  // nothing queued may still read or write the slabs
+        (void)ctx->commits.flush();  // (an error of a commit into slabs that are going away is dropped with them)
+        hipSetDevice(ctx->device);
+        if (ctx->stream) hipStreamSynchronize(ctx->stream);
+        if (ctx->relayout_stream) hipStreamSynchronize(ctx->relayout_stream);
     }
-    (void)commit_flush(ctx);  // (an error of a commit into slabs that are going away is dropped with them)
-    hipSetDevice(ctx->device);
-    if (ctx->stream) hipStreamSynchronize(ctx->stream);
-    if (ctx->relayout_stream) hipStreamSynchronize(ctx->relayout_stream);
     for (size_t i = 0; i < ctx->h_slabs.size(); ++i) {
-        if (i < ctx->h_blocks.size() && ctx->h_blocks[i].base) host_block_unmap(ctx->h_blocks[i]);
-        else if (ctx->h_slabs[i]) hipHostFree(ctx->h_slabs[i]);
+        if (ctx->h_blocks[i].base) host_block_unmap(ctx->h_blocks[i]);
+        else if (ctx->h_slabs[i]) hipHostFree(ctx->h_slabs[i]);  // (GPU contexts only: the allocator's fallback block)
     }
-    ctx->h_blocks.clear();
     for (double* d : ctx->d_slabs)
         if (d) hipFree(d);
+    ctx->h_blocks.clear();
     ctx->h_slabs.clear();
     ctx->d_slabs.clear();
     ctx->st_nslabs = 0;
@@ -922,18 +1061,13 @@ int ta_ctx_destroy(ta_ctx* ctx) {
         delete ctx;
         return TA_OK;
     }
-    (void)commit_flush(ctx);
-    commit_stop(ctx);
+    (void)ctx->commits.flush();
+    ctx->commits.stop();
     hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     ta_stage_free(ctx);
     for (auto& kv : ctx->wf_tables) hipFree(kv.second);
-    for (DevBuf* b : {&ctx->partial, &ctx->spec, &ctx->ts_partial, &ctx->out_lagsum, &ctx->out_bp,
-                      &ctx->masses, &ctx->bounce, &ctx->stage_buf, &ctx->helf_p,
-                      &ctx->helf_small, &ctx->pm_in[0], &ctx->pm_in[1], &ctx->bp_scratch, &ctx->bp_spec,
-                      &ctx->bounce2, &ctx->unit_counter, &ctx->cond_part, &ctx->cond_w, &ctx->cond_q, &ctx->cond_out,
-                      &ctx->cond_mpm, &ctx->unwrap_box})
-        if (b->p) hipFree(b->p);
+    for (DevBuf* b : ctx->workspaces) b->release();
     for (auto& q : ctx->ring)
         for (auto& ev : q)
             if (ev) hipEventDestroy(ev);
@@ -953,19 +1087,13 @@ int ta_ctx_destroy(ta_ctx* ctx) {
 
 int ta_trim(ta_ctx* ctx) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    TA_CHECK(need_ctx(ctx));
     if (ctx->is_cpu) return TA_OK;  // (no workspaces outlive a call)
-    if (int rc = commit_flush(ctx)) return rc;
+    TA_CHECK(ctx->commits.flush());
     hipSetDevice(ctx->device);
     hipDeviceSynchronize();
-    for (DevBuf* b : {&ctx->partial, &ctx->spec, &ctx->ts_partial, &ctx->out_bp, &ctx->bounce, &ctx->bounce2, &ctx->stage_buf,
-                      &ctx->helf_p, &ctx->helf_small, &ctx->pm_in[0], &ctx->pm_in[1],
-                      &ctx->bp_scratch, &ctx->bp_spec, &ctx->cond_part, &ctx->cond_w, &ctx->cond_mpm, &ctx->unwrap_box})
-        if (b->p) {
-            hipFree(b->p);
-            b->p = nullptr;
-            b->bytes = 0;
-        }
+    for (DevBuf* b : ctx->workspaces)
+        if (b->trimmed) b->release();
     return TA_OK;
     });
 }
@@ -973,42 +1101,13 @@ int ta_trim(ta_ctx* ctx) {
 int ta_set_option(ta_ctx* ctx, const char* key, int64_t value) {
     return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx || !key) return fail(ctx, TA_E_INVALID, "null argument");
-    if (!strcmp(key, "fft_nwg")) ctx->opt_fft_nwg = value;
-    else if (!strcmp(key, "direct_nwg")) ctx->opt_direct_nwg = value;
-    else if (!strcmp(key, "direct_f32")) ctx->opt_direct_f32 = value;
-    else if (!strcmp(key, "direct_groups")) ctx->opt_direct_groups = value;
-    else if (!strcmp(key, "direct_chunk")) ctx->opt_direct_chunk = value;
-    else if (!strcmp(key, "direct_mfma")) {
-        if (value != 0 && value != 1 && value != 3)
-            return fail(ctx, TA_E_INVALID, "direct_mfma: 0 vector kernels, 1 by trajectory length (default), 3 matrix cores always "
-                                           "(2, the column-packed forms, left the library in round 6: tools/band/)");
-        ctx->opt_direct_mfma = value;
+    for (const Option& o : kOptions) {
+        if (strcmp(key, o.key)) continue;
+        if (o.hook) TA_CHECK(o.hook(ctx, value));
+        ctx->*o.field = value;
+        return TA_OK;
     }
-    else if (!strcmp(key, "helfand_fft")) ctx->opt_helfand_fft = value;
-    else if (!strcmp(key, "bp_block")) ctx->opt_bp_block = value;
-    else if (!strcmp(key, "bp_spec_atoms")) ctx->opt_bp_spec_atoms = value;
-    else if (!strcmp(key, "lock_ahead")) ctx->opt_lock_ahead = value;
-    else if (!strcmp(key, "cpu_threads")) {  // CPU backend: OpenMP team size (0: the runtime's default)
-        if (value < 0 || value > 4096) return fail(ctx, TA_E_INVALID, "cpu_threads: 0 (default) .. 4096");
-        ctx->cpu.threads = value > 0 ? (int)value : ta::cpu::hardware_threads();
-    }
-    else if (!strcmp(key, "fail_alloc_after")) ctx->opt_fail_alloc_after = value;
-    else if (!strcmp(key, "fail_throw_after")) ctx->opt_fail_throw_after = value;
-    else if (!strcmp(key, "bp_prefetch")) ctx->opt_bp_prefetch = value;
-    else if (!strcmp(key, "short_max")) ctx->opt_short_max = value;
-    else if (!strcmp(key, "direct_subwave")) ctx->opt_direct_subwave = value;
-    else if (!strcmp(key, "mid_max")) ctx->opt_mid_max = value;
-    else if (!strcmp(key, "mid_all")) ctx->opt_mid_all = value;
-    else if (!strcmp(key, "mid_ncl")) ctx->opt_mid_ncl = value;
-    else if (!strcmp(key, "short_lags_max")) ctx->opt_short_lags_max = value;
-    else if (!strcmp(key, "stage_device_f32")) ctx->opt_stage_device_f32 = value;
-    else if (!strcmp(key, "timeline")) ctx->opt_timeline = value;
-    else if (!strcmp(key, "async_commit")) {
-        if (int rc = commit_flush(ctx)) return rc;
-        ctx->opt_async_commit = value;
-    }
-    else return fail(ctx, TA_E_INVALID, std::string("unknown option ") + key);
-    return TA_OK;
+    return fail(ctx, TA_E_INVALID, std::string("unknown option ") + key);
     });
 }
 
@@ -1097,35 +1196,10 @@ int ta_host_free(void* h) {
 /* ------------------------------------------------------------------ staging */
 static int stage_alloc_common(ta_ctx* ctx, int64_t n_frames, int64_t n_atoms, int dim, int dtype,
                               int n_slabs, void** h_slabs) {
-    int rc = check_shape(ctx, n_frames, n_atoms, dim, n_atoms * dim);
-    if (rc) return rc;
+    TA_CHECK(check_shape(ctx, n_frames, n_atoms, dim, n_atoms * dim));
     if (n_slabs < 1 || n_slabs > 4) return fail(ctx, TA_E_INVALID, "bad slab count");
-    if (dtype != TA_F32 && dtype != TA_F64) return fail(ctx, TA_E_INVALID, "bad dtype");
-    if (ctx->is_cpu) {
-        // host slabs in the reference's (n_frames, n_atoms, dim) layout, zero-filled mappings like the GPU contexts' (never
-        // page-locked); the CPU backend reads them where they are
-        if (!h_slabs) return fail(ctx, TA_E_UNSUPPORTED, "the CPU backend has no device slabs");
-        ta_stage_free(ctx);
-        const size_t bytes = (size_t)n_frames * n_atoms * dim * (dtype == TA_F32 ? 4 : 8);
-        for (int i = 0; i < n_slabs; ++i) {
-            HostBlock blk;
-            if (host_block_map(bytes, &blk) != 0) {
-                ta_stage_free(ctx);
-                return fail(ctx, TA_E_NOMEM, "staging allocation failed: no host memory for the slab");
-            }
-            ctx->h_slabs.push_back(blk.base);
-            ctx->h_blocks.push_back(blk);
-            ctx->cpu.slabs.push_back(blk.base);
-            h_slabs[i] = blk.base;
-        }
-        ctx->st_T = ctx->cpu.T = n_frames;
-        ctx->st_A = ctx->cpu.A = n_atoms;
-        ctx->st_D = ctx->cpu.D = dim;
-        ctx->st_dtype = ctx->cpu.dtype = dtype;
-        ctx->st_nslabs = n_slabs;
-        ctx->st_pitch = pm_pitch(n_frames);
-        return TA_OK;
-    }
+    TA_CHECK(check_dtype(ctx, dtype));
+    if (ctx->is_cpu) return cpu_stage_alloc(ctx, n_frames, n_atoms, dim, dtype, n_slabs, h_slabs);
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     ta_stage_free(ctx);
     const size_t n = (size_t)n_frames * n_atoms * dim;
@@ -1160,24 +1234,11 @@ static int stage_alloc_common(ta_ctx* ctx, int64_t n_frames, int64_t n_atoms, in
         TA_HIP_TRY(ctx, hipMemsetAsync(d, 0, dbytes, ctx->stream));
         if (h_slabs) h_slabs[i] = h;
     }
-    ctx->st_T = n_frames;
-    ctx->st_A = n_atoms;
-    ctx->st_D = dim;
-    ctx->st_dtype = dtype;
-    ctx->st_dev_f32 = dev_f32;
-    ctx->st_nslabs = n_slabs;
-    ctx->st_pitch = pm_pitch(n_frames);
+    set_staged(ctx, n_frames, n_atoms, dim, dtype, n_slabs, dev_f32);
     // the zero fill ran on the context's stream; later fills may come on any stream
     TA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (h_slabs && ctx->opt_async_commit && ctx->opt_lock_ahead) {
-        // the worker starts page-locking the slabs' first chunks while the caller sets up its frame loop (an empty job)
-        if (!ctx->cq_thread.joinable()) ctx->cq_thread = std::thread(commit_worker, ctx);
-        {
-            std::lock_guard<std::mutex> lk(ctx->cq_m);
-            ctx->cq.emplace_back(0, 0);
-        }
-        ctx->cq_cv.notify_all();
-    }
+    // the worker starts page-locking the slabs' first chunks while the caller sets up its frame loop (an empty job)
+    if (h_slabs && ctx->opt_async_commit && ctx->opt_lock_ahead) ctx->commits.push(0, 0);
     return TA_OK;
 }
 
@@ -1197,24 +1258,19 @@ int ta_stage_alloc_device(ta_ctx* ctx, int64_t n_frames, int64_t n_atoms, int di
 
 }  // extern "C"
 
+// Frames [frame_lo, frame_hi) of every host slab -> the device slabs.  The range is not empty and has been checked by
+// ta_stage_commit, the only way here (directly, or through the commit queue).
 static int stage_commit_now(ta_ctx* ctx, int64_t frame_lo, int64_t frame_hi) {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
-    if (ctx->st_nslabs == 0) return fail(ctx, TA_E_STATE, "ta_stage_alloc has not been called");
-    if (frame_lo < 0 || frame_hi > ctx->st_T || frame_lo > frame_hi)
-        return fail(ctx, TA_E_INVALID, "frame range out of bounds");
-    if (!ctx->h_slabs[0]) return fail(ctx, TA_E_STATE, "device-only slabs: use ta_stage_commit_dev");
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t row = (size_t)ctx->st_A * ctx->st_D;
     const size_t esz = ctx->st_dtype == TA_F32 ? 4 : 8;
-    if (frame_hi == frame_lo) return TA_OK;
     // frames cross PCIe in their native width into one of two landing buffers (<= 64 MiB each) and
     // are transposed into the pair-major slab on the device (float32 widened on the way), on a
     // second stream: piece i + 1 crosses PCIe while piece i is transposed
     const int64_t per = std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / (row * esz)));
     const int64_t chunk = std::min<int64_t>(per, frame_hi - frame_lo);
-    int rc = ensure(ctx, ctx->bounce, (size_t)chunk * row * esz);
-    if (!rc) rc = ensure(ctx, ctx->bounce2, (size_t)chunk * row * esz);
-    if (rc) return rc;
+    TA_CHECK(ensure(ctx, ctx->bounce, (size_t)chunk * row * esz));
+    TA_CHECK(ensure(ctx, ctx->bounce2, (size_t)chunk * row * esz));
     if (!ctx->relayout_stream) {
         TA_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->relayout_stream, hipStreamNonBlocking));
         for (int i = 0; i < 2; ++i) {
@@ -1275,81 +1331,81 @@ static void stage_lock_ahead(ta_ctx* ctx, int64_t frame_from) {
     }
 }
 
-static void commit_worker(ta_ctx* ctx) {
-    (void)hipSetDevice(ctx->device);
-    std::unique_lock<std::mutex> lk(ctx->cq_m);
+// ---- the commit queue (rules: on the class) ------------------------------------------------------------------------
+void CommitQueue::push(int64_t frame_lo, int64_t frame_hi) {
+    if (!thread_.joinable()) thread_ = std::thread([this] { run(); });
+    {
+        std::lock_guard<std::mutex> lk(m_);
+        jobs_.emplace_back(frame_lo, frame_hi);
+    }
+    cv_.notify_all();
+}
+
+void CommitQueue::run() {
+    (void)hipSetDevice(ctx_->device);
+    std::unique_lock<std::mutex> lk(m_);
     for (;;) {
-        ctx->cq_cv.wait(lk, [&] { return ctx->cq_stop || !ctx->cq.empty(); });
-        if (ctx->cq.empty()) return;  // stop requested and nothing left
-        const auto job = ctx->cq.front();
-        ctx->cq.pop_front();
-        ctx->cq_busy = true;
+        cv_.wait(lk, [&] { return stop_ || !jobs_.empty(); });
+        if (jobs_.empty()) return;  // stop requested and nothing left
+        const auto job = jobs_.front();
+        jobs_.pop_front();
+        busy_ = true;
         lk.unlock();
         // (an exception on this thread would end the process: it becomes the queued commit's error)
-        const int rc = ta::guarded(fail, ctx, [&]() -> int {
-            const int r = job.second > job.first ? stage_commit_now(ctx, job.first, job.second) : TA_OK;  // (an empty job: lock ahead only)
-            if (r == TA_OK && ctx->opt_lock_ahead) stage_lock_ahead(ctx, job.second);
-            return r;
+        const int rc = ta::guarded(fail, ctx_, [&]() -> int {
+            TA_CHECK(job.second > job.first ? stage_commit_now(ctx_, job.first, job.second) : TA_OK);
+            if (ctx_->opt_lock_ahead) stage_lock_ahead(ctx_, job.second);
+            return TA_OK;
         });
         lk.lock();
-        if (rc && ctx->cq_rc == TA_OK) {  // the first failure is the one reported
+        if (rc && rc_ == TA_OK) {  // the first failure is the one reported
             std::lock_guard<std::mutex> el(g_err_m);
-            ctx->cq_rc = rc, ctx->cq_err = ctx->err;
+            rc_ = rc, err_ = ctx_->err;
         }
-        ctx->cq_busy = false;
-        ctx->cq_cv.notify_all();
+        busy_ = false;
+        cv_.notify_all();
     }
 }
 
-// every queued commit has made its HIP calls (their work is queued on the context's streams); returns the
-// first error one of them hit
-int commit_flush(ta_ctx* ctx) {
-    if (!ctx->cq_thread.joinable()) return TA_OK;
-    std::unique_lock<std::mutex> lk(ctx->cq_m);
-    ctx->cq_cv.wait(lk, [&] { return ctx->cq.empty() && !ctx->cq_busy; });
-    const int rc = ctx->cq_rc;
-    if (rc) {
-        const std::string msg = ctx->cq_err;
-        ctx->cq_rc = TA_OK;
-        lk.unlock();
-        return fail(ctx, rc, "queued ta_stage_commit: " + msg);
-    }
-    return TA_OK;
+int CommitQueue::flush() {
+    if (!thread_.joinable()) return TA_OK;
+    std::unique_lock<std::mutex> lk(m_);
+    cv_.wait(lk, [&] { return jobs_.empty() && !busy_; });
+    const int rc = rc_;
+    if (!rc) return TA_OK;
+    const std::string msg = err_;
+    rc_ = TA_OK;
+    lk.unlock();
+    return fail(ctx_, rc, "queued ta_stage_commit: " + msg);
 }
 
-static void commit_stop(ta_ctx* ctx) {
-    if (!ctx->cq_thread.joinable()) return;
+void CommitQueue::stop() {
+    if (!thread_.joinable()) return;
     {
-        std::lock_guard<std::mutex> lk(ctx->cq_m);
-        ctx->cq_stop = true;
+        std::lock_guard<std::mutex> lk(m_);
+        stop_ = true;
     }
-    ctx->cq_cv.notify_all();
-    ctx->cq_thread.join();
-    ctx->cq_stop = false;
+    cv_.notify_all();
+    thread_.join();
+    stop_ = false;
 }
 
 extern "C" {
 
 int ta_stage_commit(ta_ctx* ctx, int64_t frame_lo, int64_t frame_hi) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    TA_CHECK(need_ctx(ctx));
     if (ctx->st_nslabs == 0) return fail(ctx, TA_E_STATE, "ta_stage_alloc has not been called");
-    if (frame_lo < 0 || frame_hi > ctx->st_T || frame_lo > frame_hi)
-        return fail(ctx, TA_E_INVALID, "frame range out of bounds");
+    TA_CHECK(check_frames(ctx, frame_lo, frame_hi));
     if (!ctx->h_slabs[0]) return fail(ctx, TA_E_STATE, "device-only slabs: use ta_stage_commit_dev");
     if (frame_hi == frame_lo) return TA_OK;
     if (ctx->is_cpu) return TA_OK;  // the CPU backend reads the host slab in place
-    if (!ctx->opt_async_commit) {
-        if (int rc = commit_flush(ctx)) return rc;
-        return stage_commit_now(ctx, frame_lo, frame_hi);
+    if (ctx->opt_async_commit) {
+        ctx->commits.push(frame_lo, frame_hi);
+        return TA_OK;
     }
-    if (!ctx->cq_thread.joinable()) ctx->cq_thread = std::thread(commit_worker, ctx);
-    {
-        std::lock_guard<std::mutex> lk(ctx->cq_m);
-        ctx->cq.emplace_back(frame_lo, frame_hi);
-    }
-    ctx->cq_cv.notify_all();
-    return TA_OK;
+    TA_CHECK(ctx->commits.flush());
+    return stage_commit_now(ctx, frame_lo, frame_hi);
     });
 }
 
@@ -1358,13 +1414,12 @@ int ta_stage_commit_dev(ta_ctx* ctx, int slab, const void* d_src, int dtype, int
     return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx || !d_src) return fail(ctx, TA_E_INVALID, "null argument");
     TA_NO_CPU(ctx);
-    if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
-    if (dtype != TA_F32 && dtype != TA_F64) return fail(ctx, TA_E_INVALID, "bad dtype");
-    if (frame_lo < 0 || frame_hi > ctx->st_T || frame_lo > frame_hi)
-        return fail(ctx, TA_E_INVALID, "frame range out of bounds");
-    if (ld_row < ctx->st_A * ctx->st_D) return fail(ctx, TA_E_INVALID, "ld_row smaller than n_atoms*dim");
+    TA_CHECK(check_slab(ctx, slab));
+    TA_CHECK(check_dtype(ctx, dtype));
+    TA_CHECK(check_frames(ctx, frame_lo, frame_hi));
+    TA_CHECK(check_ld_row(ctx, ld_row, ctx->st_A * ctx->st_D));
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc_ = order_after_staging(ctx, (hipStream_t)stream)) return rc_;
+    TA_CHECK(order_after_staging(ctx, (hipStream_t)stream));
     TA_HIP_TRY(ctx, launch_relayout(d_src, dtype == TA_F32, ld_row, ctx->st_A * ctx->st_D, frame_hi - frame_lo,
                                     ctx->d_slabs[slab], ctx->st_dev_f32, ctx->st_pitch, frame_lo,
                                     (hipStream_t)stream));
@@ -1375,16 +1430,16 @@ int ta_stage_commit_dev(ta_ctx* ctx, int slab, const void* d_src, int dtype, int
 int ta_stage_synth(ta_ctx* ctx, int slab, uint64_t seed, int64_t col_offset, int64_t n_cols_total,
                    void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
-    if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(check_slab(ctx, slab));
     if (col_offset < 0 || col_offset + ctx->st_A * ctx->st_D > n_cols_total)
         return fail(ctx, TA_E_INVALID, "column block outside the synthetic tensor");
     if (ctx->is_cpu) {  // the same generator into the host slab
-        ta::cpu::synth(ctx->cpu, slab, seed, col_offset, n_cols_total);
+        ta::cpu::synth(cpu_state(ctx), slab, seed, col_offset, n_cols_total);
         return TA_OK;
     }
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc_ = order_after_staging(ctx, (hipStream_t)stream)) return rc_;
+    TA_CHECK(order_after_staging(ctx, (hipStream_t)stream));
     TA_HIP_TRY(ctx, launch_synth(ctx->d_slabs[slab], ctx->st_dev_f32, ctx->st_pitch, ctx->st_A * ctx->st_D, ctx->st_T, seed,
                                  col_offset, n_cols_total, (hipStream_t)stream));
     return TA_OK;
@@ -1395,10 +1450,10 @@ int ta_stage_read_dev(ta_ctx* ctx, int slab, double* d_dst, int64_t ld_row, void
     return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx || !d_dst) return fail(ctx, TA_E_INVALID, "null argument");
     TA_NO_CPU(ctx);
-    if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
-    if (ld_row < ctx->st_A * ctx->st_D) return fail(ctx, TA_E_INVALID, "ld_row smaller than n_atoms*dim");
+    TA_CHECK(check_slab(ctx, slab));
+    TA_CHECK(check_ld_row(ctx, ld_row, ctx->st_A * ctx->st_D));
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc_ = order_after_staging(ctx, (hipStream_t)stream)) return rc_;
+    TA_CHECK(order_after_staging(ctx, (hipStream_t)stream));
     TA_HIP_TRY(ctx, launch_unlayout(ctx->d_slabs[slab], ctx->st_dev_f32, ctx->st_pitch, ctx->st_A * ctx->st_D, ctx->st_T, d_dst,
                                     ld_row, (hipStream_t)stream));
     return TA_OK;
@@ -1409,7 +1464,7 @@ int ta_stage_device(ta_ctx* ctx, int slab, double** d_slab, int64_t* pitch_rows,
     return ta::guarded(fail, ctx, [&]() -> int {
     if (!ctx || !d_slab) return fail(ctx, TA_E_INVALID, "null argument");
     TA_NO_CPU(ctx);
-    if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
+    TA_CHECK(check_slab(ctx, slab));
     *d_slab = ctx->d_slabs[slab];
     if (pitch_rows) *pitch_rows = ctx->st_pitch;
     if (n_pairs) *n_pairs = (ctx->st_A * ctx->st_D + 1) / 2;
@@ -1460,26 +1515,20 @@ int ta_helfand_msd_staged(ta_ctx* ctx, const double* d_masses, double scale, dou
 }
 
 // Einstein MSD: slab 0 / d_pos holds the positions (the vel argument of the shared paths)
-static int msd_which(ta_ctx* ctx, int fft, int* which) {
-    if (fft != 0 && fft != 1) return fail(ctx, TA_E_INVALID, "fft must be 0 or 1");
-    *which = fft ? W_MSD_FFT : W_MSD_DIRECT;
-    return TA_OK;
-}
+static int msd_which(int fft) { return fft ? W_MSD_FFT : W_MSD_DIRECT; }
 
 int ta_msd_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int fft, double* d_lagsum,
                double* d_bp, int64_t ld_bp, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    int which = 0;
-    if (int rc = msd_which(ctx, fft, &which)) return rc;
-    return dev_entry(ctx, which, d_pos, nullptr, nullptr, T, A, D, ld_row, 1.0, d_lagsum, d_bp, ld_bp, stream);
+    TA_CHECK(check_fft(ctx, fft));
+    return dev_entry(ctx, msd_which(fft), d_pos, nullptr, nullptr, T, A, D, ld_row, 1.0, d_lagsum, d_bp, ld_bp, stream);
     });
 }
 
 int ta_msd_staged(ta_ctx* ctx, int fft, double* d_lagsum, double* d_bp, int64_t ld_bp, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    int which = 0;
-    if (int rc = msd_which(ctx, fft, &which)) return rc;
-    return staged_entry(ctx, which, nullptr, 1.0, d_lagsum, d_bp, ld_bp, stream);
+    TA_CHECK(check_fft(ctx, fft));
+    return staged_entry(ctx, msd_which(fft), nullptr, 1.0, d_lagsum, d_bp, ld_bp, stream);
     });
 }
 
@@ -1489,14 +1538,14 @@ int ta_conductivity_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, 
                         void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
     TA_NO_CPU(ctx);
-    int rc = check_shape(ctx, T, A, D, ld_row);
-    if (rc || (rc = cond_args(ctx, fft, d_charges, d_moment))) return rc;
+    TA_CHECK(check_shape(ctx, T, A, D, ld_row));
+    TA_CHECK(cond_args(ctx, fft, d_charges, d_moment));
     if (!d_pos) return fail(ctx, TA_E_INVALID, "null device pointer");
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = call_begin(ctx, st))) return rc;
+    TA_CHECK(call_begin(ctx, st));
     const double* px = nullptr;
-    if ((rc = relayout_input(ctx, 0, d_pos, T, A * D, ld_row, st, &px))) return rc;
+    TA_CHECK(relayout_input(ctx, 0, d_pos, T, A * D, ld_row, st, &px));
     return cond_pm(ctx, fft != 0, px, false, pm_pitch(T), T, A, D, d_charges, d_moment, d_collective, d_self_lagsum, st);
     });
 }
@@ -1504,13 +1553,13 @@ int ta_conductivity_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, 
 int ta_conductivity_staged(ta_ctx* ctx, int fft, const double* d_charges, double* d_moment, double* d_collective,
                            double* d_self_lagsum, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    TA_CHECK(need_ctx(ctx));
     TA_NO_CPU(ctx);
-    int rc = cond_args(ctx, fft, d_charges, d_moment);
-    if (rc) return rc;
-    if (ctx->st_nslabs < 1) return fail(ctx, TA_E_STATE, "slabs have not been staged");
+    TA_CHECK(cond_args(ctx, fft, d_charges, d_moment));
+    TA_CHECK(check_staged(ctx));
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = order_after_staging(ctx, (hipStream_t)stream)) || (rc = call_begin(ctx, (hipStream_t)stream))) return rc;
+    TA_CHECK(order_after_staging(ctx, (hipStream_t)stream));
+    TA_CHECK(call_begin(ctx, (hipStream_t)stream));
     return cond_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A, ctx->st_D,
                    d_charges, d_moment, d_collective, d_self_lagsum, (hipStream_t)stream);
     });
@@ -1518,7 +1567,7 @@ int ta_conductivity_staged(ta_ctx* ctx, int fft, const double* d_charges, double
 
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    TA_CHECK(need_ctx(ctx));
     TA_NO_CPU(ctx);
     if (!ctx->timing_valid) return fail(ctx, TA_E_STATE, "no completed compute call to time");
     TA_HIP_TRY(ctx, hipEventSynchronize(ctx->ev[3]));
@@ -1553,9 +1602,9 @@ int ta_timing_history(ta_ctx* ctx, int max_n, float* total_ms, float* main_kerne
 
 int ta_clock_probe(ta_ctx* ctx, int n_launches, double* mhz, double* cycles_per_unit_pass, double* ms_per_launch) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    TA_CHECK(need_ctx(ctx));
     TA_NO_CPU(ctx);
-    if (ctx->st_nslabs < 1) return fail(ctx, TA_E_STATE, "slabs have not been staged");
+    TA_CHECK(check_staged(ctx));
     if (n_launches < 1) return fail(ctx, TA_E_INVALID, "need at least one launch");
     if (ctx->st_dev_f32) return fail(ctx, TA_E_UNSUPPORTED, "clock probe: float64 device slabs only");
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1564,34 +1613,29 @@ int ta_clock_probe(ta_ctx* ctx, int n_launches, double* mhz, double* cycles_per_
     if (!wfft_choose((long)T, &R0, &R) || R != 1 || !(R0 == 8 || R0 == 10 || R0 == 12 || R0 == 16 || R0 == 20))
         return fail(ctx, TA_E_UNSUPPORTED, "clock probe: plans R0 = 8, 10, 12, 16, 20 without an outer radix only");
     cd* tw = nullptr;
-    int rc = get_wf_table(ctx, R0, R, &tw);
-    if (rc) return rc;
+    TA_CHECK(get_wf_table(ctx, R0, R, &tw));
     const int64_t cap = ctx->opt_fft_nwg > 0 ? ctx->opt_fft_nwg : (int64_t)ctx->n_cu * wfft_max_wg_per_cu(R0);
     const int64_t nwg = std::max<int64_t>(16, std::min<int64_t>(cap, 2 * n_pairs) / 16 * 16), n_tuples = nwg / 2;
     const int64_t L = 2L * R0 * 512;
-    if ((rc = ensure(ctx, ctx->partial, sizeof(double) * (size_t)n_tuples * L))) return rc;
-    DevBuf st;
-    if ((rc = ensure(ctx, st, sizeof(unsigned long long) * 16 * (size_t)nwg))) return rc;
-    if (int rc_ = order_after_staging(ctx, ctx->stream)) {
-        hipFree(st.p);
-        return rc_;
-    }
+    TA_CHECK(ensure(ctx, ctx->partial, sizeof(double) * (size_t)n_tuples * L));
+    TA_CHECK(ensure(ctx, ctx->clock_stamps, sizeof(unsigned long long) * 16 * (size_t)nwg));
+    unsigned long long* stamps = (unsigned long long*)ctx->clock_stamps.p;
+    TA_CHECK(order_after_staging(ctx, ctx->stream));
     hipEvent_t e0 = nullptr, e1 = nullptr;  // its own events: the probe is not a compute call and leaves the timing ring alone
     hipError_t e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
     if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
     for (int i = 0; i < n_launches && e == hipSuccess; ++i)
         e = launch_wfft_forward_stamp(R0, (int)nwg, ctx->stream, ctx->d_slabs[0], ctx->st_pitch, (int)T, n_pairs, tw,
-                                      (double*)ctx->partial.p, (unsigned long long*)st.p);
+                                      (double*)ctx->partial.p, stamps);
     if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
     std::vector<unsigned long long> h(16 * (size_t)nwg);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), st.p, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     float ms = 0.f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    hipFree(st.p);
     if (e != hipSuccess) return fail(ctx, TA_E_HIP, std::string("clock probe: ") + hipGetErrorString(e));
     // the last launch's stamps, wave 0 of every workgroup: [0] S1, [1] S2 cycles, [2] the kernel's span
     // in shader cycles, [3] in 100 MHz ticks
@@ -1647,10 +1691,10 @@ namespace ta {
 // on ctx->stream).  h_masses: this context's atoms.
 int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, double* h_bp, int64_t ld_host,
                 double** d_total) {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    TA_CHECK(need_ctx(ctx));
     TA_NO_CPU(ctx);
-    const int need = which == W_HELFAND ? 2 : 1;
-    if (ctx->st_nslabs < need) return fail(ctx, TA_E_STATE, "slabs have not been staged");
+    const int need = slabs_needed(which);
+    TA_CHECK(check_staged(ctx, need));
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t T = ctx->st_T, A = ctx->st_A;
     if (h_bp && ld_host < A) return fail(ctx, TA_E_INVALID, "host row stride smaller than n_atoms");
@@ -1661,24 +1705,23 @@ int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, do
     const bool blocked = h_bp && A >= 2 * CH;
     const int64_t n_blocks = blocked ? (A + CH - 1) / CH : 1;
     // rows [0, n_blocks): per-block lag sums; row n_blocks: their sum (one block: row 0 is the sum)
-    int rc = ensure(ctx, ctx->out_lagsum, sizeof(double) * T * (n_blocks + 1));
-    if (rc) return rc;
+    TA_CHECK(ensure(ctx, ctx->out_lagsum, sizeof(double) * T * (n_blocks + 1)));
     double* d_ls = (double*)ctx->out_lagsum.p;
     double* d_bp = nullptr;
     if (h_bp) {
-        if ((rc = ensure(ctx, ctx->out_bp, sizeof(double) * (size_t)T * A))) return rc;
+        TA_CHECK(ensure(ctx, ctx->out_bp, sizeof(double) * (size_t)T * A));
         d_bp = (double*)ctx->out_bp.p;
     }
     const double* d_m = nullptr;
     if (which == W_HELFAND) {
         if (!h_masses) return fail(ctx, TA_E_INVALID, "h_masses is NULL");
-        if ((rc = ensure(ctx, ctx->masses, sizeof(double) * A))) return rc;
+        TA_CHECK(ensure(ctx, ctx->masses, sizeof(double) * A));
         TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->masses.p, h_masses, sizeof(double) * A, hipMemcpyHostToDevice,
                                        ctx->stream));
         d_m = (const double*)ctx->masses.p;
     }
     if (!blocked) {
-        if ((rc = staged_entry(ctx, which, d_m, scale, d_ls, d_bp, A, (void*)ctx->stream))) return rc;
+        TA_CHECK(staged_entry(ctx, which, d_m, scale, d_ls, d_bp, A, (void*)ctx->stream));
         if (h_bp)
             TA_HIP_TRY(ctx, hipMemcpy2DAsync(h_bp, sizeof(double) * ld_host, d_bp, sizeof(double) * A,
                                              sizeof(double) * A, T, hipMemcpyDeviceToHost, ctx->stream));
@@ -1688,7 +1731,7 @@ int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, do
     if (!ctx->copy_stream) TA_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     // the blocks go to compute_pm directly (staged_entry is not on this path): join the commit worker here, or the
     // first block is queued ahead of frames whose copies the worker has not issued yet
-    if ((rc = order_after_staging(ctx, ctx->stream))) return rc;
+    TA_CHECK(order_after_staging(ctx, ctx->stream));
     const int D = ctx->st_D;
     for (int64_t b = 0; b < n_blocks; ++b) {
         const int64_t lo = b * CH, hi = std::min(A, lo + CH);
@@ -1696,10 +1739,9 @@ int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, do
         const size_t off = (size_t)pair_lo * ctx->st_pitch * (ctx->st_dev_f32 ? 8 : 16);  // bytes
         const void* v = (const char*)ctx->d_slabs[0] + off;
         const void* x = need == 2 ? (const char*)ctx->d_slabs[1] + off : nullptr;
-        if ((rc = call_begin(ctx, ctx->stream)) ||
-            (rc = compute_pm(ctx, which, v, x, d_m ? d_m + lo : nullptr, ctx->st_pitch, T, hi - lo, D, scale,
-                             d_ls + b * T, d_bp + lo, A, ctx->stream, ctx->st_dev_f32)))
-            return rc;
+        TA_CHECK(call_begin(ctx, ctx->stream));
+        TA_CHECK(compute_pm(ctx, which, v, x, d_m ? d_m + lo : nullptr, ctx->st_pitch, T, hi - lo, D, scale,
+                            d_ls + b * T, d_bp + lo, A, ctx->stream, ctx->st_dev_f32));
         TA_HIP_TRY(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
         TA_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_stage, 0));
         TA_HIP_TRY(ctx, hipMemcpy2DAsync(h_bp + lo, sizeof(double) * ld_host, d_bp + lo, sizeof(double) * A,
@@ -1716,20 +1758,20 @@ int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, do
 // uploaded, the moment (and with self the self lag sum, with coll Phi) left on the device in *d_out: (T, D) moment,
 // then T values of Phi, then T of the self term.
 int cond_launch(ta_ctx* ctx, int fft, const double* h_q, bool coll, bool self, double** d_out) {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    TA_CHECK(need_ctx(ctx));
     TA_NO_CPU(ctx);
-    if (ctx->st_nslabs < 1) return fail(ctx, TA_E_STATE, "slabs have not been staged");
+    TA_CHECK(check_staged(ctx));
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t T = ctx->st_T, A = ctx->st_A;
     const int D = ctx->st_D;
-    int rc = ensure(ctx, ctx->cond_q, sizeof(double) * A);
-    if (rc || (rc = ensure(ctx, ctx->cond_out, sizeof(double) * (size_t)T * (D + 2)))) return rc;
+    TA_CHECK(ensure(ctx, ctx->cond_q, sizeof(double) * A));
+    TA_CHECK(ensure(ctx, ctx->cond_out, sizeof(double) * (size_t)T * (D + 2)));
     double* out = (double*)ctx->cond_out.p;
     TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->cond_q.p, h_q, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = order_after_staging(ctx, ctx->stream)) || (rc = call_begin(ctx, ctx->stream))) return rc;
-    if ((rc = cond_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, T, A, D, (const double*)ctx->cond_q.p,
-                      out, coll ? out + T * D : nullptr, self ? out + T * (D + 1) : nullptr, ctx->stream)))
-        return rc;
+    TA_CHECK(order_after_staging(ctx, ctx->stream));
+    TA_CHECK(call_begin(ctx, ctx->stream));
+    TA_CHECK(cond_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, T, A, D, (const double*)ctx->cond_q.p,
+                     out, coll ? out + T * D : nullptr, self ? out + T * (D + 1) : nullptr, ctx->stream));
     *d_out = out;
     return TA_OK;
 }
@@ -1737,27 +1779,24 @@ int cond_launch(ta_ctx* ctx, int fft, const double* h_q, bool coll, bool self, d
 // Phi of a host (T, D) moment on this context's device, blocking (the group's collective after its members' sums)
 int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T, int D, double* h_coll) {
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure(ctx, ctx->cond_out, sizeof(double) * (size_t)T * (D + 2));
-    if (rc) return rc;
+    TA_CHECK(ensure(ctx, ctx->cond_out, sizeof(double) * (size_t)T * (D + 2)));
     double* out = (double*)ctx->cond_out.p;
     TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_moment, sizeof(double) * T * D, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = cond_collective(ctx, fft != 0, out, T, D, out + T * D, ctx->stream))) return rc;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(h_coll, out + T * D, sizeof(double) * T, hipMemcpyDeviceToHost, ctx->stream));
-    return host_wait(ctx);
+    TA_CHECK(cond_collective(ctx, fft != 0, out, T, D, out + T * D, ctx->stream));
+    return host_finish(ctx, {{h_coll, out + T * D, (size_t)T}});
 }
 
 // One context's unwrap of staged slab `slab` (ta_unwrap, ta_group_unwrap), queued on ctx->stream behind the queued commits
 // and bracketed by the timing events: the box table's copy (box.tab must stay valid until host_wait), then the kernel
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes) {
-    if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
+    TA_CHECK(check_slab(ctx, slab));
     if (ctx->st_dev_f32) return fail(ctx, TA_E_UNSUPPORTED, "unwrap: float64 device slabs only (stage_device_f32 is on)");
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = order_after_staging(ctx, ctx->stream);
-    if (rc) return rc;
+    TA_CHECK(order_after_staging(ctx, ctx->stream));
     const size_t bytes = box.tab.size() * sizeof(double);
-    if ((rc = ensure(ctx, ctx->unwrap_box, bytes))) return rc;
+    TA_CHECK(ensure(ctx, ctx->unwrap_box, bytes));
     hipStream_t st = ctx->stream;
-    if ((rc = call_begin(ctx, st))) return rc;
+    TA_CHECK(call_begin(ctx, st));
     TA_LAUNCH(ctx, "box_copy", st, hipMemcpyAsync(ctx->unwrap_box.p, box.tab.data(), bytes, hipMemcpyHostToDevice, st));
     TA_LAUNCH_MAIN(ctx, box.triclinic ? "k_unwrap_tric" : "k_unwrap_ortho", st,
                    launch_unwrap(ctx->d_slabs[slab], (long)ctx->st_pitch, (long)ctx->st_T, (long)ctx->st_A, ctx->st_D, axes,
@@ -1770,48 +1809,51 @@ int host_wait(ta_ctx* ctx) {
     if (ctx->copy_stream) TA_HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
     return TA_OK;
 }
+// the tail of a host-facing call: the small results (n doubles each; a NULL destination is skipped) copied back on the
+// context's stream, then everything the call queued waited for
+int host_finish(ta_ctx* ctx, std::initializer_list<HostCopy> copies) {
+    for (const HostCopy& c : copies)
+        if (c.h) TA_HIP_TRY(ctx, hipMemcpyAsync(c.h, c.d, sizeof(double) * c.n, hipMemcpyDeviceToHost, ctx->stream));
+    return host_wait(ctx);
+}
 hipStream_t ctx_stream(ta_ctx* ctx) { return ctx->stream; }
 int ctx_device(const ta_ctx* ctx) { return ctx->device; }
 int64_t ctx_staged_frames(const ta_ctx* ctx) { return ctx->st_nslabs ? ctx->st_T : 0; }
 int ctx_fail(ta_ctx* ctx, int code, const std::string& msg) { return fail(ctx, code, msg); }
 int ctx_host_slab(ta_ctx* ctx, int slab, void** h, int64_t* T, int64_t* A, int* D, int* dtype) {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
-    if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(check_slab(ctx, slab));
     if (!ctx->h_slabs[slab]) return fail(ctx, TA_E_STATE, "device-only slabs have no host side to fill");
     *h = ctx->h_slabs[slab], *T = ctx->st_T, *A = ctx->st_A, *D = ctx->st_D, *dtype = ctx->st_dtype;
     return TA_OK;
 }
 }  // namespace ta
 
+// The shape of every host-facing (blocking) entry: the body runs under a reporter that waits before it reports -- an
+// exception after the launch lets the queued kernels and the copies into the caller's arrays finish before the error
+// returns, so the caller may free its arrays at once -- and ends in host_finish.
+template <class Body>
+static int host_call(ta_ctx* ctx, Body&& body) {
+    return ta::guard(
+        [&](int code, const std::string& msg) {
+            if (ctx && !ctx->is_cpu) (void)host_wait(ctx);
+            return fail(ctx, code, msg);
+        },
+        body);
+}
+
 extern "C" {
 
 static int host_compute(ta_ctx* ctx, int which, const double* h_masses, double scale,
                         double* h_ts, double* h_bp) {
-    // (an exception after the launch: the queued kernels and copies into the caller's arrays finish before the error returns)
-    return ta::guard([&](int c_, const std::string& m_) { if (ctx) (void)host_wait(ctx); return fail(ctx, c_, m_); }, [&]() -> int {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
     if (!h_ts) return fail(ctx, TA_E_INVALID, "h_timeseries is NULL");
-    if (ctx->is_cpu) {
-        const int need = which == W_HELFAND ? 2 : 1;
-        if (ctx->st_nslabs < need) return fail(ctx, TA_E_STATE, "slabs have not been staged");
-        if (which == W_HELFAND && !h_masses) return fail(ctx, TA_E_INVALID, "h_masses is NULL");
-        const int rc = which == W_FFT      ? ta::cpu::vacf_fft(ctx->cpu, h_ts, h_bp)
-                       : which == W_DIRECT ? ta::cpu::vacf_direct(ctx->cpu, h_ts, h_bp)
-                       : is_msd(which)     ? ta::cpu::msd(ctx->cpu, which == W_MSD_FFT, h_ts, h_bp)
-                                           : ta::cpu::helfand(ctx->cpu, h_masses, scale, h_ts, h_bp);
-        if (rc) return fail(ctx, rc, "CPU backend: out of host memory");
-        const double n_at = (double)ctx->st_A;  // mean over atoms (velocityautocorr.py:214,237; viscosity.py:233)
-        for (int64_t k = 0; k < ctx->st_T; ++k) h_ts[k] /= n_at;
-        return TA_OK;
-    }
+    if (ctx->is_cpu) return cpu_compute(ctx, which, h_masses, scale, h_ts, h_bp);
     double* d_total = nullptr;
-    int rc = host_launch(ctx, which, h_masses, scale, h_bp, ctx->st_A, &d_total);
-    if (rc) return rc;
-    const int64_t T = ctx->st_T;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(h_ts, d_total, sizeof(double) * T, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = host_wait(ctx))) return rc;
-    const double n_at = (double)ctx->st_A;  // mean over atoms (velocityautocorr.py:214,237)
-    for (int64_t k = 0; k < T; ++k) h_ts[k] /= n_at;
+    TA_CHECK(host_launch(ctx, which, h_masses, scale, h_bp, ctx->st_A, &d_total));
+    TA_CHECK(host_finish(ctx, {{h_ts, d_total, (size_t)ctx->st_T}}));
+    atom_mean(ctx, h_ts);
     return TA_OK;
     });
 }
@@ -1822,50 +1864,38 @@ int ta_helfand_msd(ta_ctx* ctx, const double* h_masses, double scale, double* h_
     return host_compute(ctx, W_HELFAND, h_masses, scale, h_ts, h_bp);
 }
 int ta_msd(ta_ctx* ctx, int fft, double* h_ts, double* h_bp) {
-    if (fft != 0 && fft != 1) return fail(ctx, TA_E_INVALID, "fft must be 0 or 1");
-    return host_compute(ctx, fft ? W_MSD_FFT : W_MSD_DIRECT, nullptr, 1.0, h_ts, h_bp);
+    TA_CHECK(check_fft(ctx, fft));
+    return host_compute(ctx, msd_which(fft), nullptr, 1.0, h_ts, h_bp);
 }
 
 int ta_conductivity(ta_ctx* ctx, int fft, const double* h_charges, double* h_moment, double* h_collective,
                     double* h_self_lagsum) {
-    return ta::guard([&](int c_, const std::string& m_) { if (ctx) (void)host_wait(ctx); return fail(ctx, c_, m_); }, [&]() -> int {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
-    int rc = cond_args(ctx, fft, h_charges, h_moment);
-    if (rc) return rc;
-    if (ctx->st_nslabs < 1) return fail(ctx, TA_E_STATE, "slabs have not been staged");
-    if (ctx->is_cpu) {
-        if ((rc = ta::cpu::conductivity(ctx->cpu, fft != 0, h_charges, h_moment, h_collective, h_self_lagsum)))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
-    }
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(cond_args(ctx, fft, h_charges, h_moment));
+    TA_CHECK(check_staged(ctx));
+    if (ctx->is_cpu) return cpu_conductivity(ctx, fft != 0, h_charges, h_moment, h_collective, h_self_lagsum);
     double* d_out = nullptr;
-    if ((rc = ta::cond_launch(ctx, fft, h_charges, h_collective != nullptr, h_self_lagsum != nullptr, &d_out))) return rc;
-    const int64_t T = ctx->st_T, D = ctx->st_D;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(h_moment, d_out, sizeof(double) * T * D, hipMemcpyDeviceToHost, ctx->stream));
-    if (h_collective)
-        TA_HIP_TRY(ctx, hipMemcpyAsync(h_collective, d_out + T * D, sizeof(double) * T, hipMemcpyDeviceToHost, ctx->stream));
-    if (h_self_lagsum)
-        TA_HIP_TRY(ctx, hipMemcpyAsync(h_self_lagsum, d_out + T * (D + 1), sizeof(double) * T, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-    return host_wait(ctx);
+    TA_CHECK(ta::cond_launch(ctx, fft, h_charges, h_collective != nullptr, h_self_lagsum != nullptr, &d_out));
+    const size_t T = (size_t)ctx->st_T, D = (size_t)ctx->st_D;
+    return host_finish(ctx, {{h_moment, d_out, T * D}, {h_collective, d_out + T * D, T}, {h_self_lagsum, d_out + T * (D + 1), T}});
     });
 }
 
 int ta_unwrap(ta_ctx* ctx, int slab, const double* h_dimensions, const int* axes) {
-    return ta::guard([&](int c_, const std::string& m_) { if (ctx && !ctx->is_cpu) (void)host_wait(ctx); return fail(ctx, c_, m_); }, [&]() -> int {
-    if (!ctx) return fail(nullptr, TA_E_INVALID, "null context");
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
     if (!h_dimensions || !axes) return fail(ctx, TA_E_INVALID, "dimensions or axes are NULL");
-    if (ctx->st_nslabs < 1) return fail(ctx, TA_E_STATE, "slabs have not been staged");
-    if (slab < 0 || slab >= ctx->st_nslabs) return fail(ctx, TA_E_INVALID, "no such slab");
+    TA_CHECK(check_staged(ctx));
+    TA_CHECK(check_slab(ctx, slab));
     BoxTable box;
     const std::string why = box_table(h_dimensions, ctx->st_T, ctx->st_D, axes, 256, &box);
     if (!why.empty()) return fail(ctx, TA_E_INVALID, "unwrap: " + why);
     if (ctx->is_cpu) {
-        ta::cpu::unwrap(ctx->cpu, slab, box, axes);
+        ta::cpu::unwrap(cpu_state(ctx), slab, box, axes);
         return TA_OK;
     }
-    int rc = unwrap_launch(ctx, slab, box, axes);
-    if (rc) return rc;
+    TA_CHECK(unwrap_launch(ctx, slab, box, axes));
     return host_wait(ctx);
     });
 }

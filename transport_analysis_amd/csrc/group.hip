@@ -284,68 +284,108 @@ int reduce_members(ta_group* g, const std::vector<int>& who, std::vector<double*
     return TA_OK;
 }
 
-// everything queued so far on the members `who` has finished (their kernels and their copies into the
-// caller's host arrays): called before an error is returned, so that the caller may free those arrays
-void drain_members(ta_group* g, const std::vector<int>& who) {
-    for (int i : who) (void)host_wait(g->ctx[i]);
+// ---- the members of a call ---------------------------------------------------------------------------------------------
+// fn(i) for every member that holds atoms (all of them unless there are more devices than atoms), in member order.  A
+// member's failure ends the walk and becomes the group's, with the member's message (mfail).  who (or NULL) collects the
+// members fn was called for, the failing one included: its launch may have queued work already.
+template <class Fn>
+int for_members(ta_group* g, std::vector<int>* who, Fn&& fn) {
+    for (int i = 0; i < (int)g->ctx.size(); ++i) {
+        if (g->hi[i] == g->lo[i]) continue;
+        if (who) who->push_back(i);
+        if (const int rc = fn(i)) return mfail(g, i, rc);
+    }
+    return TA_OK;
 }
 
-int group_compute_impl(ta_group* g, int which, const double* h_masses, double scale, double* h_ts, double* h_bp) {
-    if (!g) return gfail(nullptr, TA_E_INVALID, "null group");
+// everything queued so far on the members `who` has finished (their kernels and their copies into the caller's host
+// arrays): every member is waited for, whatever an earlier one reports; the first failure is the one returned
+int wait_members(ta_group* g, const std::vector<int>& who) {
+    int rc = TA_OK;
+    for (int i : who) {
+        const int r = host_wait(g->ctx[i]);
+        if (r && !rc) rc = mfail(g, i, r);
+    }
+    return rc;
+}
+// ... before an error is returned, so that the caller may free those arrays: the error stays the one being returned
+int drained(ta_group* g, const std::vector<int>& who, int rc) {
+    for (int i : who) (void)host_wait(g->ctx[i]);
+    return rc;
+}
+
+// The shape of the host-facing group entries: the reporter drains every member, then fails -- an exception after the
+// members' launches lets their queued work finish first (the caller may free its arrays as soon as the call returns)
+template <class Body>
+int group_call(ta_group* g, Body&& body) {
+    return ta::guard(
+        [&](int code, const std::string& msg) {
+            if (g)
+                for (ta_ctx* c : g->ctx)
+                    if (c) (void)host_wait(c);
+            return gfail(g, code, msg);
+        },
+        body);
+}
+
+int check_group(ta_group* g) { return g ? TA_OK : gfail(nullptr, TA_E_INVALID, "null group"); }
+int check_staged(ta_group* g) { return g->T ? TA_OK : gfail(g, TA_E_STATE, "slabs have not been staged"); }
+int check_fft(ta_group* g, int fft) { return fft == 0 || fft == 1 ? TA_OK : gfail(g, TA_E_INVALID, "fft must be 0 or 1"); }
+#define TAG_CHECK(expr)                                                                              \
+    do {                                                                                             \
+        if (int rc_ = (expr)) return rc_;                                                            \
+    } while (0)
+
+int group_compute(ta_group* g, int which, const double* h_masses, double scale, double* h_ts, double* h_bp) {
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
     if (!h_ts) return gfail(g, TA_E_INVALID, "h_timeseries is NULL");
-    if (g->T == 0) return gfail(g, TA_E_STATE, "slabs have not been staged");
-    if (which == 2 && !h_masses) return gfail(g, TA_E_INVALID, "h_masses is NULL");
-    const int n = (int)g->ctx.size();
+    TAG_CHECK(check_staged(g));
+    if (which == W_HELFAND && !h_masses) return gfail(g, TA_E_INVALID, "h_masses is NULL");
     std::vector<double*> d_tot;
-    std::vector<int> who;  // members that hold atoms (all of them unless there are more devices than atoms)
-    int rc;
-    for (int i = 0; i < n; ++i) {
-        if (g->hi[i] == g->lo[i]) continue;
+    std::vector<int> who;
+    int rc = for_members(g, &who, [&](int i) {
         double* d = nullptr;
-        rc = host_launch(g->ctx[i], which, h_masses ? h_masses + g->lo[i] : nullptr, scale,
-                         h_bp ? h_bp + g->lo[i] : nullptr, g->A, &d);
-        who.push_back(i);  // (a failed launch may have queued work already)
-        if (rc) {
-            rc = mfail(g, i, rc);
-            drain_members(g, who);  // earlier members' copies into h_bp are in flight: not after we return
-            return rc;
-        }
-        d_tot.push_back(d);
-    }
-    if ((rc = reduce_members(g, who, d_tot))) {
-        drain_members(g, who);
-        return rc;
-    }
+        const int r = host_launch(g->ctx[i], which, h_masses ? h_masses + g->lo[i] : nullptr, scale,
+                                  h_bp ? h_bp + g->lo[i] : nullptr, g->A, &d);
+        if (!r) d_tot.push_back(d);
+        return r;
+    });
+    if (rc || (rc = reduce_members(g, who, d_tot))) return drained(g, who, rc);  // (copies into h_bp are in flight)
     const int root = who[0];
     hipError_t he = hipSetDevice(g->devices[root]);
     if (he == hipSuccess)
         he = hipMemcpyAsync(h_ts, d_tot[0], sizeof(double) * g->T, hipMemcpyDeviceToHost, ctx_stream(g->ctx[root]));
-    if (he != hipSuccess) {
-        drain_members(g, who);
-        return gfail(g, TA_E_HIP, std::string("timeseries copy: ") + hipGetErrorString(he));
-    }
-    rc = TA_OK;
-    for (int i : who) {  // every member is waited for, whatever an earlier one reports
-        const int r = host_wait(g->ctx[i]);
-        if (r && !rc) rc = mfail(g, i, r);
-    }
-    if (rc) return rc;
+    if (he != hipSuccess) return drained(g, who, gfail(g, TA_E_HIP, std::string("timeseries copy: ") + hipGetErrorString(he)));
+    TAG_CHECK(wait_members(g, who));
     const double n_at = (double)g->A;  // mean over ALL atoms (velocityautocorr.py:214,237; viscosity.py:233)
     for (int64_t k = 0; k < g->T; ++k) h_ts[k] /= n_at;
     return TA_OK;
+    });
 }
 
-// ... behind the guard of the entry points: an exception after the members' launches drains them first (the caller may
-// free its arrays as soon as the call returns)
-int group_compute(ta_group* g, int which, const double* h_masses, double scale, double* h_ts, double* h_bp) {
-    return ta::guard(
-        [&](int c_, const std::string& m_) {
-            if (g)
-                for (ta_ctx* c : g->ctx)
-                    if (c) (void)host_wait(c);
-            return gfail(g, c_, m_);
-        },
-        [&]() -> int { return group_compute_impl(g, which, h_masses, scale, h_ts, h_bp); });
+// ta_group_stage_alloc (host: pinned host slabs, their pointers into h_slabs[member * n_slabs + slab]) and
+// ta_group_stage_alloc_device
+int group_stage_alloc(ta_group* g, int64_t n_frames, int64_t n_atoms, int dim, int dtype, int n_slabs, bool host, void** h_slabs) {
+    TAG_CHECK(check_group(g));
+    if (host && !h_slabs) return gfail(g, TA_E_INVALID, "h_slabs is NULL");
+    if (n_frames < 1 || n_atoms < 1 || dim < 1 || dim > 3 || n_slabs < 1 || n_slabs > 4)
+        return gfail(g, TA_E_INVALID, "need n_frames >= 1, n_atoms >= 1, 1 <= dim <= 3, 1 <= n_slabs <= 4");
+    const int n = (int)g->ctx.size();
+    g->T = 0;
+    for (int i = 0; i < n; ++i) {
+        shard(n_atoms, i, n, &g->lo[i], &g->hi[i]);
+        for (int s = 0; host && s < n_slabs; ++s) h_slabs[i * n_slabs + s] = nullptr;
+        if (g->hi[i] == g->lo[i]) {  // more devices than atoms
+            ta_stage_free(g->ctx[i]);
+            continue;
+        }
+        const int rc = host ? ta_stage_alloc(g->ctx[i], n_frames, g->hi[i] - g->lo[i], dim, dtype, n_slabs, h_slabs + (size_t)i * n_slabs)
+                            : ta_stage_alloc_device(g->ctx[i], n_frames, g->hi[i] - g->lo[i], dim, n_slabs);
+        if (rc) return mfail(g, i, rc);
+    }
+    g->T = n_frames, g->A = n_atoms, g->D = dim, g->n_slabs = n_slabs;
+    return TA_OK;
 }
 
 }  // namespace
@@ -452,13 +492,14 @@ int ta_group_set_option(ta_group* g, const char* key, int64_t value) {
     return ta::guarded(gfail, g, [&]() -> int {
     if (!g || !key) return gfail(g, TA_E_INVALID, "null argument");
     // the group's own options; every other key goes to the members' contexts
-    if (!strcmp(key, "reduce_mode") || !strcmp(key, "force_rccl")) {
-        const int mode = !strcmp(key, "force_rccl") ? (value ? RED_RCCL : RED_AUTO) : (int)value;
+    const bool force = !strcmp(key, "force_rccl");
+    if (force || !strcmp(key, "reduce_mode")) {
+        const int mode = force ? (value ? RED_RCCL : RED_AUTO) : (int)value;
         if (mode < RED_AUTO || mode > RED_RCCL) return gfail(g, TA_E_INVALID, "reduce_mode: 0 auto, 1 peer copies, 2 RCCL");
         g->reduce_mode = mode;
         return TA_OK;
     }
-    for (size_t i = 0; i < g->ctx.size(); ++i) {
+    for (size_t i = 0; i < g->ctx.size(); ++i) {  // (every member, with or without atoms)
         const int rc = ta_set_option(g->ctx[i], key, value);
         if (rc) return mfail(g, (int)i, rc);
     }
@@ -469,148 +510,84 @@ int ta_group_set_option(ta_group* g, const char* key, int64_t value) {
 int ta_group_stage_alloc(ta_group* g, int64_t n_frames, int64_t n_atoms, int dim, int dtype, int n_slabs,
                          void** h_slabs) {
     return ta::guarded(gfail, g, [&]() -> int {
-    if (!g) return gfail(nullptr, TA_E_INVALID, "null group");
-    if (!h_slabs) return gfail(g, TA_E_INVALID, "h_slabs is NULL");
-    if (n_frames < 1 || n_atoms < 1 || dim < 1 || dim > 3 || n_slabs < 1 || n_slabs > 4)
-        return gfail(g, TA_E_INVALID, "need n_frames >= 1, n_atoms >= 1, 1 <= dim <= 3, 1 <= n_slabs <= 4");
-    const int n = (int)g->ctx.size();
-    g->T = 0;
-    for (int i = 0; i < n; ++i) {
-        shard(n_atoms, i, n, &g->lo[i], &g->hi[i]);
-        for (int s = 0; s < n_slabs; ++s) h_slabs[i * n_slabs + s] = nullptr;
-        if (g->hi[i] == g->lo[i]) {  // more devices than atoms
-            ta_stage_free(g->ctx[i]);
-            continue;
-        }
-        const int rc = ta_stage_alloc(g->ctx[i], n_frames, g->hi[i] - g->lo[i], dim, dtype, n_slabs,
-                                      h_slabs + (size_t)i * n_slabs);
-        if (rc) return mfail(g, i, rc);
-    }
-    g->T = n_frames, g->A = n_atoms, g->D = dim, g->n_slabs = n_slabs;
-    return TA_OK;
+    return group_stage_alloc(g, n_frames, n_atoms, dim, dtype, n_slabs, true, h_slabs);
     });
 }
 
 int ta_group_stage_alloc_device(ta_group* g, int64_t n_frames, int64_t n_atoms, int dim, int n_slabs) {
     return ta::guarded(gfail, g, [&]() -> int {
-    if (!g) return gfail(nullptr, TA_E_INVALID, "null group");
-    if (n_frames < 1 || n_atoms < 1 || dim < 1 || dim > 3 || n_slabs < 1 || n_slabs > 4)
-        return gfail(g, TA_E_INVALID, "need n_frames >= 1, n_atoms >= 1, 1 <= dim <= 3, 1 <= n_slabs <= 4");
-    const int n = (int)g->ctx.size();
-    g->T = 0;
-    for (int i = 0; i < n; ++i) {
-        shard(n_atoms, i, n, &g->lo[i], &g->hi[i]);
-        if (g->hi[i] == g->lo[i]) {
-            ta_stage_free(g->ctx[i]);
-            continue;
-        }
-        const int rc = ta_stage_alloc_device(g->ctx[i], n_frames, g->hi[i] - g->lo[i], dim, n_slabs);
-        if (rc) return mfail(g, i, rc);
-    }
-    g->T = n_frames, g->A = n_atoms, g->D = dim, g->n_slabs = n_slabs;
-    return TA_OK;
+    return group_stage_alloc(g, n_frames, n_atoms, dim, TA_F64, n_slabs, false, nullptr);
     });
 }
 
 int ta_group_stage_synth(ta_group* g, int slab, uint64_t seed, int64_t col_offset, int64_t n_cols_total) {
     return ta::guarded(gfail, g, [&]() -> int {
-    if (!g) return gfail(nullptr, TA_E_INVALID, "null group");
-    if (g->T == 0) return gfail(g, TA_E_STATE, "slabs have not been staged");
-    for (size_t i = 0; i < g->ctx.size(); ++i) {  // member i: its own columns of the ONE synthetic tensor
-        if (g->hi[i] == g->lo[i]) continue;
-        const int rc = ta_stage_synth(g->ctx[i], slab, seed, col_offset + g->lo[i] * g->D, n_cols_total,
-                                      (void*)ctx_stream(g->ctx[i]));
-        if (rc) return mfail(g, (int)i, rc);
-    }
-    return TA_OK;
+    TAG_CHECK(check_group(g));
+    TAG_CHECK(check_staged(g));
+    return for_members(g, nullptr, [&](int i) {  // member i: its own columns of the ONE synthetic tensor
+        return ta_stage_synth(g->ctx[i], slab, seed, col_offset + g->lo[i] * g->D, n_cols_total, (void*)ctx_stream(g->ctx[i]));
+    });
     });
 }
 
 int ta_group_stage_commit(ta_group* g, int64_t frame_lo, int64_t frame_hi) {
     return ta::guarded(gfail, g, [&]() -> int {
-    if (!g) return gfail(nullptr, TA_E_INVALID, "null group");
+    TAG_CHECK(check_group(g));
     if (g->T == 0) return gfail(g, TA_E_STATE, "ta_group_stage_alloc has not been called");
-    for (size_t i = 0; i < g->ctx.size(); ++i) {  // queued on each device's own streams: the devices overlap
-        if (g->hi[i] == g->lo[i]) continue;
-        const int rc = ta_stage_commit(g->ctx[i], frame_lo, frame_hi);
-        if (rc) return mfail(g, (int)i, rc);
-    }
-    return TA_OK;
+    // queued on each device's own streams: the devices overlap
+    return for_members(g, nullptr, [&](int i) { return ta_stage_commit(g->ctx[i], frame_lo, frame_hi); });
     });
 }
 
 int ta_group_stage_free(ta_group* g) {
     return ta::guarded(gfail, g, [&]() -> int {
-    if (!g) return gfail(nullptr, TA_E_INVALID, "null group");
+    TAG_CHECK(check_group(g));
     for (ta_ctx* c : g->ctx) ta_stage_free(c);
     g->T = g->A = 0;
     return TA_OK;
     });
 }
 
-int ta_group_vacf_fft(ta_group* g, double* h_ts, double* h_bp) { return group_compute(g, 0, nullptr, 1.0, h_ts, h_bp); }
-int ta_group_vacf_direct(ta_group* g, double* h_ts, double* h_bp) { return group_compute(g, 1, nullptr, 1.0, h_ts, h_bp); }
+int ta_group_vacf_fft(ta_group* g, double* h_ts, double* h_bp) { return group_compute(g, W_FFT, nullptr, 1.0, h_ts, h_bp); }
+int ta_group_vacf_direct(ta_group* g, double* h_ts, double* h_bp) { return group_compute(g, W_DIRECT, nullptr, 1.0, h_ts, h_bp); }
 int ta_group_helfand_msd(ta_group* g, const double* h_masses, double scale, double* h_ts, double* h_bp) {
-    return ta::guarded(gfail, g, [&]() -> int {
-    return group_compute(g, 2, h_masses, scale, h_ts, h_bp);
-    });
+    return group_compute(g, W_HELFAND, h_masses, scale, h_ts, h_bp);
 }
 int ta_group_msd(ta_group* g, int fft, double* h_ts, double* h_bp) {
-    if (fft != 0 && fft != 1) return gfail(g, TA_E_INVALID, "fft must be 0 or 1");
-    return group_compute(g, fft ? 3 : 4, nullptr, 1.0, h_ts, h_bp);
+    TAG_CHECK(check_fft(g, fft));
+    return group_compute(g, fft ? W_MSD_FFT : W_MSD_DIRECT, nullptr, 1.0, h_ts, h_bp);
 }
-
 
 // Conductivity: every member's moment (and self lag sum) of its atoms, added on the host in member order, then ONE
 // collective MSD of the summed moment on the first member that holds atoms (the MSD of a sum is not a sum of MSDs)
 int ta_group_conductivity(ta_group* g, int fft, const double* h_charges, double* h_moment, double* h_collective,
                           double* h_self_lagsum) {
-    return ta::guard(
-        [&](int c_, const std::string& m_) {
-            if (g)
-                for (ta_ctx* c : g->ctx)
-                    if (c) (void)host_wait(c);
-            return gfail(g, c_, m_);
-        },
-        [&]() -> int {
-    if (!g) return gfail(nullptr, TA_E_INVALID, "null group");
-    if (fft != 0 && fft != 1) return gfail(g, TA_E_INVALID, "fft must be 0 or 1");
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
+    TAG_CHECK(check_fft(g, fft));
     if (!h_charges || !h_moment || !h_collective) return gfail(g, TA_E_INVALID, "charges, moment or collective is NULL");
-    if (g->T == 0) return gfail(g, TA_E_STATE, "slabs have not been staged");
+    TAG_CHECK(check_staged(g));
     const int n = (int)g->ctx.size();
     const int64_t T = g->T;
     const int D = g->D;
     std::vector<std::vector<double>> mom(n), slf(n);
     std::vector<int> who;
-    int rc;
-    for (int i = 0; i < n; ++i) {
-        if (g->hi[i] == g->lo[i]) continue;
+    hipError_t he = hipSuccess;  // of a member's copies into mom / slf
+    int rc = for_members(g, &who, [&](int i) {
         double* d = nullptr;
-        rc = cond_launch(g->ctx[i], fft, h_charges + g->lo[i], false, h_self_lagsum != nullptr, &d);
-        who.push_back(i);
-        if (rc) {
-            rc = mfail(g, i, rc);
-            drain_members(g, who);
-            return rc;
-        }
+        if (const int r = cond_launch(g->ctx[i], fft, h_charges + g->lo[i], false, h_self_lagsum != nullptr, &d)) return r;
         mom[i].resize((size_t)T * D);
-        hipError_t he = hipMemcpyAsync(mom[i].data(), d, sizeof(double) * T * D, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
+        he = hipMemcpyAsync(mom[i].data(), d, sizeof(double) * T * D, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
         if (he == hipSuccess && h_self_lagsum) {
             slf[i].resize((size_t)T);
             he = hipMemcpyAsync(slf[i].data(), d + T * (D + 1), sizeof(double) * T, hipMemcpyDeviceToHost,
                                 ctx_stream(g->ctx[i]));
         }
-        if (he != hipSuccess) {
-            drain_members(g, who);
-            return gfail(g, TA_E_HIP, std::string("moment copy: ") + hipGetErrorString(he));
-        }
-    }
-    rc = TA_OK;
-    for (int i : who) {
-        const int r = host_wait(g->ctx[i]);
-        if (r && !rc) rc = mfail(g, i, r);
-    }
-    if (rc) return rc;
+        return he == hipSuccess ? TA_OK : TA_E_HIP;
+    });
+    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string("moment copy: ") + hipGetErrorString(he));  // (the group's own failure)
+    if (rc) return drained(g, who, rc);
+    TAG_CHECK(wait_members(g, who));
     std::fill(h_moment, h_moment + T * D, 0.0);
     if (h_self_lagsum) std::fill(h_self_lagsum, h_self_lagsum + T, 0.0);
     for (int i : who) {
@@ -620,42 +597,24 @@ int ta_group_conductivity(ta_group* g, int fft, const double* h_charges, double*
     }
     if ((rc = cond_collective_host(g->ctx[who[0]], fft, h_moment, T, D, h_collective))) return mfail(g, who[0], rc);
     return TA_OK;
-        });
+    });
 }
 
 // Unwrap: every member's block of slab `slab` with the same box table, queued on all devices, then waited for
 int ta_group_unwrap(ta_group* g, int slab, const double* h_dimensions, const int* axes) {
-    std::vector<int> who;
-    return ta::guard(
-        [&](int c_, const std::string& m_) {
-            if (g) drain_members(g, who);
-            return gfail(g, c_, m_);
-        },
-        [&]() -> int {
-    if (!g) return gfail(nullptr, TA_E_INVALID, "null group");
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
     if (!h_dimensions || !axes) return gfail(g, TA_E_INVALID, "dimensions or axes are NULL");
-    if (g->T == 0) return gfail(g, TA_E_STATE, "slabs have not been staged");
+    TAG_CHECK(check_staged(g));
     if (slab < 0 || slab >= g->n_slabs) return gfail(g, TA_E_INVALID, "no such slab");
     BoxTable box;
     const std::string why = box_table(h_dimensions, g->T, g->D, axes, 256, &box);
     if (!why.empty()) return gfail(g, TA_E_INVALID, "unwrap: " + why);
-    for (int i = 0; i < (int)g->ctx.size(); ++i) {
-        if (g->hi[i] == g->lo[i]) continue;
-        const int rc = unwrap_launch(g->ctx[i], slab, box, axes);
-        if (rc) {
-            const int r = mfail(g, i, rc);
-            drain_members(g, who);
-            return r;
-        }
-        who.push_back(i);
-    }
-    int rc = TA_OK;
-    for (int i : who) {
-        const int r = host_wait(g->ctx[i]);
-        if (r && !rc) rc = mfail(g, i, r);
-    }
-    return rc;
-        });
+    std::vector<int> who;
+    if (const int rc = for_members(g, &who, [&](int i) { return unwrap_launch(g->ctx[i], slab, box, axes); }))
+        return drained(g, who, rc);
+    return wait_members(g, who);
+    });
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <exception>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -53,13 +54,23 @@ int guarded(Fail fail, Owner owner, Body&& body) noexcept {
     return guard([&](int code, const std::string& text) { return fail(owner, code, text); }, body);
 }
 
-// api.hip, for group.hip (several contexts driven by one host thread): one context's share of a
-// host-facing call queued on its streams (which: 0 FFT VACF, 1 windowed VACF, 2 Helfand, 3 / 4 Einstein MSD by the FFT /
-// direct form), the sum
-// over its atoms left on the device; host_wait blocks until that work and its copies are done
+// Which quantity a compute request asks for (api.hip's dispatch, and group.hip's requests to its members)
+enum Which { W_FFT = 0, W_DIRECT = 1, W_HELFAND = 2 /* needs two slabs: velocities, positions */, W_MSD_FFT = 3, W_MSD_DIRECT = 4 };
+inline bool is_msd(int which) { return which == W_MSD_FFT || which == W_MSD_DIRECT; }
+inline int slabs_needed(int which) { return which == W_HELFAND ? 2 : 1; }
+
+// api.hip, for group.hip (several contexts driven by one host thread): one context's share of a host-facing call queued
+// on its streams, the sum over its atoms left on the device; host_wait blocks until that work and its copies are done,
+// host_finish queues the copies of small results (n doubles each; a NULL destination is skipped) first
 int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, double* h_bp, int64_t ld_host,
                 double** d_total);
 int host_wait(ta_ctx* ctx);
+struct HostCopy {
+    double* h;
+    const double* d;
+    size_t n;
+};
+int host_finish(ta_ctx* ctx, std::initializer_list<HostCopy> copies);
 // api.hip, for group.hip: one context's conductivity share (ta_conductivity on its staged slab 0 with its atoms' charges
 // h_q), queued: *d_out = the (n_frames, dim) moment, then Phi (coll), then the self lag sum (self), valid after
 // host_wait; and Phi of a host (n_frames, dim) moment on the context's device, blocking
