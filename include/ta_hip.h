@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_unwrap / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_unwrap / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -150,7 +150,10 @@ int ta_stage_synth(ta_ctx *ctx, int slab, uint64_t seed, int64_t col_offset, int
  * inputs (the input's size, twice for Helfand), the 64 MiB landing buffer of ta_stage_commit,
  * the product slab of the "helfand_fft" option and of the Einstein MSD's FFT form (the input's size),
  * and for ta_conductivity* the moment's partial sums (<= 1024 * n_frames * dim * 8 bytes) and, with
- * the self term, the weighted slab (the input's size).                                        */
+ * the self term, the weighted slab (the input's size), and for ta_onsager* the species moments' partial sums
+ * (<= 1024 * n_species * n_frames * dim * 8 bytes), the pair-major slab of the n_species^2 pseudo-particles and their
+ * by-particle MSDs (n_species^2 * n_frames * (dim + 1) * 8 bytes); the labels, weights and outputs of host-facing calls
+ * are kept.                                                                                                            */
 int ta_trim(ta_ctx *ctx);
 
 /* ---- pinned host memory for result arrays ---------------------------------
@@ -205,6 +208,34 @@ int ta_msd(ta_ctx *ctx, int fft, double *h_timeseries, double *h_by_particle);
  *                   kernel unless an FFT evaluation follows it (ta_kernel_timeline names it k_cond_moment).          */
 int ta_conductivity(ta_ctx *ctx, int fft, const double *h_charges, double *h_moment, double *h_collective,
                     double *h_self_lagsum);
+/* ta_onsager      : species-resolved Onsager transport coefficients (no reference: a new analysis, OnsagerHelfand) on slab 0 =
+ *                   the positions of the dim_type's columns, h_species = one int32 label in 0 ... n_species - 1 per atom, in
+ *                   any order (interleaved topologies), h_weights = one weight per atom (NULL: all 1),
+ *                   1 <= n_species <= TA_ONSAGER_MAX_SPECIES:
+ *                     h_moments[(s * n_frames + t) * dim + d] = M_s[t, d] = sum_{n: species[n] = s} w_n (x[t,n,d] - x[0,n,d])
+ *                                                                                  ((n_species, n_frames, dim), required)
+ *                     h_cross[(k * S + i) * S + j] = C[k, i, j] = 1 / (n_frames - k) sum_{t < n_frames - k} sum_d
+ *                                  (M_i[t+k,d] - M_i[t,d]) (M_j[t+k,d] - M_j[t,d])          ((n_frames, S, S), or NULL: skipped)
+ *                   ONE pass over the slab forms every species' moment (k_species_moment: the pass of ta_conductivity with
+ *                   the sum split by label; fixed-order partial sums, no atomics, the same bits from run to run; the shift
+ *                   by the first frame comes before the weight; a species without atoms has an exactly zero moment).  C is
+ *                   evaluated by polarisation, C_ij = 1/4 [MSD(M_i + M_j) - MSD(M_i - M_j)], C_ii = MSD(M_i), in one
+ *                   by-particle evaluation of ta_msd's dispatch with the same fft (0 / 1) on n_species^2 pseudo-particles:
+ *                   C is symmetric bit for bit, C[0] is exactly 0, and the row and column of a species whose moment is
+ *                   identically zero are exactly 0.  ACCURACY: the error of C_ij is that of the two MSDs it is the
+ *                   difference of, i.e. relative to max_k max(C_ii, C_jj) (1e-10 of it at worst, FFT form), NOT to |C_ij|:
+ *                   two nearly uncorrelated species have a C_ij far below that scale.
+ *                   NULL h_species / h_moments, fft other than 0 / 1, n_species out of range, a label outside
+ *                   0 ... n_species - 1 (checked on the host before anything is uploaded): TA_E_INVALID; nothing staged:
+ *                   TA_E_STATE.  CPU backend: the same in C++/OpenMP.  Timings: the pass is the main kernel unless an FFT
+ *                   evaluation follows it (ta_kernel_timeline names it k_species_moment).
+ * ta_onsager_cross: C (n_frames, S, S) of caller-provided moments (S, n_frames, dim) alone, e.g. the sum of several shards'
+ *                   moments (moments add up over shards, C does not).  Needs no staged slab and leaves one untouched.   */
+#define TA_ONSAGER_MAX_SPECIES 8
+int ta_onsager(ta_ctx *ctx, int fft, int n_species, const int32_t *h_species, const double *h_weights, double *h_moments,
+               double *h_cross);
+int ta_onsager_cross(ta_ctx *ctx, int fft, const double *h_moments, int n_species, int64_t n_frames, int dim,
+                     double *h_cross);
 
 /* ---- periodic unwrapping of a staged position slab ---------------------------------------------------------------
  * ta_unwrap: undo periodic wrapping of staging slab `slab` in place (MDAnalysis' NoJump), over the staged frames
@@ -251,6 +282,12 @@ int ta_msd_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_ato
 int ta_conductivity_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row,
                         int fft, const double *d_charges, double *d_moment, double *d_collective,
                         double *d_self_lagsum, void *stream);
+/* d_species: (n_atoms,) int32 device labels, NOT checked: an atom whose label is outside 0 ... n_species - 1 is left out of
+ * every moment.  d_weights: (n_atoms,) or NULL (all 1); d_moments (n_species, n_frames, dim) required; d_cross
+ * (n_frames, n_species, n_species) or NULL.  Shards' moments add up; C does not (reduce the moments, then ta_onsager_cross). */
+int ta_onsager_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row, int fft,
+                   int n_species, const int32_t *d_species, const double *d_weights, double *d_moments, double *d_cross,
+                   void *stream);
 
 /* ---- compute on the staged (pair-major) slabs, device outputs, asynchronous on `stream` ----
  * Same arithmetic and outputs as the *_dev calls, on the slabs of ta_stage_alloc*: no
@@ -264,6 +301,8 @@ int ta_helfand_msd_staged(ta_ctx *ctx, const double *d_masses, double scale, dou
 int ta_msd_staged(ta_ctx *ctx, int fft, double *d_lagsum, double *d_by_particle, int64_t ld_bp, void *stream);
 int ta_conductivity_staged(ta_ctx *ctx, int fft, const double *d_charges, double *d_moment, double *d_collective,
                            double *d_self_lagsum, void *stream);
+int ta_onsager_staged(ta_ctx *ctx, int fft, int n_species, const int32_t *d_species, const double *d_weights,
+                      double *d_moments, double *d_cross, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns
@@ -321,6 +360,11 @@ int ta_group_msd(ta_group *g, int fft, double *h_timeseries, double *h_by_partic
  * atoms.  h_collective is required here.                                                                             */
 int ta_group_conductivity(ta_group *g, int fft, const double *h_charges, double *h_moment, double *h_collective,
                           double *h_self_lagsum);
+/* ta_group_onsager: ta_onsager on every member with its slice of h_species / h_weights (all n_atoms; labels checked first)
+ * and the call's n_species; the members' moments are SUMMED on the host in member order, then ONE cross evaluation of the
+ * summed moments runs on the first member that holds atoms.  h_cross NULL: the moments alone.                          */
+int ta_group_onsager(ta_group *g, int fft, int n_species, const int32_t *h_species, const double *h_weights,
+                     double *h_moments, double *h_cross);
 /* ta_group_unwrap: ta_unwrap on every member's block of slab `slab` (declared with ta_unwrap above) */
 int ta_group_unwrap(ta_group *g, int slab, const double *h_dimensions, const int *axes); /* every member's block */
 

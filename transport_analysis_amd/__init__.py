@@ -1,8 +1,9 @@
 """transport_analysis_amd — MI355X-native time-correlation kernels behind the
-transport-analysis API (VelocityAutocorr, ViscosityHelfand), MDAnalysis' EinsteinMSD and ConductivityHelfand."""
+transport-analysis API (VelocityAutocorr, ViscosityHelfand), MDAnalysis' EinsteinMSD, ConductivityHelfand and its species-resolved form, OnsagerHelfand."""
 __version__ = "0.1.0"
 
 from .velocityautocorr import VelocityAutocorr  # noqa: F401
 from .viscosity import ViscosityHelfand  # noqa: F401
 from .msd import EinsteinMSD  # noqa: F401
 from .conductivity import ConductivityHelfand  # noqa: F401
+from .onsager import OnsagerHelfand  # noqa: F401

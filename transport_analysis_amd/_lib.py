@@ -36,6 +36,7 @@ _STAGED = _int(_vp, _vp, _vp, _i64, _vp)
 _FRAME = _int(_vp, _ci, _i64, _vp, _ci, _i64, _ci, _ci, _ci, _i64, _vp, _i64)
 _COND = _int(_vp, _ci, _vp, _vp, _vp, _vp)
 _UNWRAP = _int(_vp, _ci, _vp, _vp)
+_ONSAGER = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, fft, n_species, h_species, h_weights, h_moments, h_cross)
 
 #: every symbol include/ta_hip.h declares -> (result type, argument types): the one table EXPORTS and lib() are made of
 _API = {
@@ -52,6 +53,9 @@ _API = {
     "ta_stage_synth": _int(_vp, _ci, ctypes.c_uint64, _i64, _i64, _vp),
     "ta_vacf_fft": _HOST, "ta_vacf_direct": _HOST, "ta_helfand_msd": _int(_vp, _vp, _dbl, _vp, _vp),
     "ta_msd": _int(_vp, _ci, _vp, _vp), "ta_conductivity": _COND, "ta_unwrap": _UNWRAP,
+    "ta_onsager": _ONSAGER, "ta_onsager_cross": _int(_vp, _ci, _vp, _ci, _i64, _ci, _vp),
+    "ta_onsager_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
+    "ta_onsager_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
     "ta_helfand_msd_dev": _int(_vp, _vp, _vp, _vp, _i64, _i64, _ci, _i64, _dbl, _vp, _vp, _i64, _vp),
     "ta_msd_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _vp, _i64, _vp),
@@ -71,6 +75,7 @@ _API = {
     "ta_group_stage_synth": _int(_vp, _ci, ctypes.c_uint64, _i64, _i64),
     "ta_group_vacf_fft": _HOST, "ta_group_vacf_direct": _HOST, "ta_group_helfand_msd": _int(_vp, _vp, _dbl, _vp, _vp),
     "ta_group_msd": _int(_vp, _ci, _vp, _vp), "ta_group_conductivity": _COND, "ta_group_unwrap": _UNWRAP,
+    "ta_group_onsager": _ONSAGER,
 }
 EXPORTS = tuple(_API)
 
@@ -399,6 +404,26 @@ class _Staged:
         self._call("conductivity", int(fft), _ptr(q), _ptr(moment), _ptr(phi), _ptr(self_ls))
         return moment, phi, self_ls
 
+    def onsager(self, fft, species, n_species=None, weights=None, cross=True):
+        """Species moments and their cross MSD of slab 0 (the positions), ta_onsager: `species` one integer label in
+        0 ... n_species - 1 per staged atom, in any order (n_species: default the largest label + 1), `weights` one weight
+        per atom or None (all 1): (moments (n_species, n_frames, dim), C (n_frames, n_species, n_species) or None)."""
+        T, A, D = self.shape or (1, 1, 1)  # unstaged: the library reports it
+        lab = np.ascontiguousarray(species, dtype=np.int32).ravel()
+        if lab.size != A:
+            raise ValueError(f"species: {lab.size} labels for {A} atoms")
+        S = int(n_species) if n_species is not None else int(lab.max()) + 1
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+            if w.size != A:
+                raise ValueError(f"weights: {w.size} values for {A} atoms")
+        n = max(S, 1)
+        moments = np.empty((n, T, D), dtype=np.float64)
+        c = np.empty((T, n, n), dtype=np.float64) if cross else None
+        self._call("onsager", int(fft), S, _ptr(lab), _ptr(w), _ptr(moments), _ptr(c))
+        return moments, c
+
     def unwrap(self, slab, dimensions, axes):
         """Undo periodic wrapping of staged slab `slab` in place (MDAnalysis' NoJump, ta_unwrap; a group: on every
         member's block of the slab): `dimensions` the (n_frames, 6) boxes [a, b, c, alpha, beta, gamma] of the staged
@@ -482,6 +507,17 @@ class Context(_Staged):
         self.stage_commit(0, T)
         return self.conductivity(fft, np.ones(1))[1]
 
+    def onsager_cross(self, moments, fft):
+        """C (n_frames, S, S) of given (S, n_frames, dim) moments, e.g. the sum of several shards' moments
+        (ta_onsager_cross): needs no staged slab and leaves the context's slabs as they are."""
+        m = np.ascontiguousarray(moments, dtype=np.float64)
+        if m.ndim != 3:
+            raise ValueError(f"moments: shape {m.shape}, expected (n_species, n_frames, dim)")
+        S, T, D = m.shape
+        c = np.empty((T, S, S), dtype=np.float64)
+        self._call("onsager_cross", int(fft), _ptr(m), S, T, D, _ptr(c))
+        return c
+
     # -- device-pointer compute (asynchronous) --------------------------
     def vacf_fft_dev(self, d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._call("vacf_fft_dev", d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp or None, ld_bp, stream or None)
@@ -502,6 +538,11 @@ class Context(_Staged):
         self._call("conductivity_dev", d_pos, n_frames, n_atoms, dim, ld_row, int(fft), d_charges, d_moment,
                    d_collective or None, d_self or None, stream or None)
 
+    def onsager_dev(self, d_pos, n_frames, n_atoms, dim, ld_row, fft, n_species, d_species, d_moments, d_weights=0,
+                    d_cross=0, stream=0):
+        self._call("onsager_dev", d_pos, n_frames, n_atoms, dim, ld_row, int(fft), int(n_species), d_species,
+                   d_weights or None, d_moments, d_cross or None, stream or None)
+
     # -- compute on the staged slabs, device outputs (asynchronous) ------
     def vacf_fft_staged(self, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._call("vacf_fft_staged", d_lagsum, d_bp or None, ld_bp, stream or None)
@@ -517,6 +558,10 @@ class Context(_Staged):
 
     def conductivity_staged(self, fft, d_charges, d_moment, d_collective=0, d_self=0, stream=0):
         self._call("conductivity_staged", int(fft), d_charges, d_moment, d_collective or None, d_self or None, stream or None)
+
+    def onsager_staged(self, fft, n_species, d_species, d_moments, d_weights=0, d_cross=0, stream=0):
+        self._call("onsager_staged", int(fft), int(n_species), d_species, d_weights or None, d_moments, d_cross or None,
+                   stream or None)
 
     # -- timing ----------------------------------------------------------
     def timing_history(self, max_n=64):

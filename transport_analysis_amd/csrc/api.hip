@@ -131,6 +131,10 @@ struct ta_ctx {
     // charges and outputs of host-facing calls, the pair-major copy of the (n_frames, dim) moment
     DevBuf cond_part{workspaces, kTrimmed}, cond_w{workspaces, kTrimmed}, cond_q{workspaces, kKept};
     DevBuf cond_out{workspaces, kKept}, cond_mpm{workspaces, kTrimmed};
+    // Onsager (ons_pm, ons_cross): the species moments' partial sums, the labels and weights and the outputs of host-facing
+    // calls, the pair-major slab of the S^2 pseudo-particles, their by-particle MSDs (+ lag sums and the non-zero flags)
+    DevBuf ons_part{workspaces, kTrimmed}, ons_lab{workspaces, kKept}, ons_w{workspaces, kKept};
+    DevBuf ons_out{workspaces, kKept}, ons_pm{workspaces, kTrimmed}, ons_bp{workspaces, kTrimmed};
     DevBuf unwrap_box{workspaces, kTrimmed};    // ta_unwrap: the box table (unwrap_box.hpp) of the last call
     // staging: two landing buffers, so that a piece crosses PCIe while the one before it is transposed
     DevBuf bounce{workspaces, kTrimmed}, bounce2{workspaces, kTrimmed};
@@ -874,6 +878,69 @@ int cond_args(ta_ctx* ctx, int fft, const void* charges, const void* moment) {
     return TA_OK;
 }
 
+// ---- Onsager transport coefficients (onsager.hip) -------------------------------------------------------------------
+// C[k, i, j] of the (S, T, D) moments at d_moments into d_cross (T, S, S), by polarisation in ONE msd_impl call: the S^2
+// pseudo-particles M_i, M_i + M_j, M_i - M_j as a pair-major slab, their (T, S^2) by-particle MSDs (msd_impl: the
+// EinsteinMSD dispatch, with the call's fft), then C_ij = 1/4 (MSD(M_i + M_j) - MSD(M_i - M_j)).
+int ons_cross(ta_ctx* ctx, bool fft, const double* d_moments, int S, int64_t T, int D, double* d_cross, hipStream_t st) {
+    const int64_t P = (int64_t)S * S, pitch = pm_pitch(T);
+    if (T < 2) {  // lag 0 alone: exactly 0
+        TA_HIP_TRY(ctx, hipMemsetAsync(d_cross, 0, sizeof(double) * (size_t)(T * P), st));
+        return TA_OK;
+    }
+    TA_CHECK(ensure(ctx, ctx->ons_pm, pm_bytes(T, P * D)));
+    TA_CHECK(ensure(ctx, ctx->ons_bp, sizeof(double) * (size_t)(T * P + T) + sizeof(int) * TA_ONSAGER_MAX_SPECIES));
+    double* bp = (double*)ctx->ons_bp.p;
+    double* lagsum = bp + T * P;
+    int* nz = (int*)(lagsum + T);
+    TA_HIP_TRY(ctx, hipMemsetAsync(nz, 0, sizeof(int) * TA_ONSAGER_MAX_SPECIES, st));
+    TA_LAUNCH(ctx, "k_onsager_combos", st, launch_onsager_combos(d_moments, S, (long)T, D, (long)pitch, (double*)ctx->ons_pm.p, nz, st));
+    TA_CHECK(msd_impl(ctx, fft, (const double*)ctx->ons_pm.p, pitch, T, P, D, lagsum, bp, P, st));
+    TA_LAUNCH(ctx, "k_onsager_finish", st, launch_onsager_finish(bp, S, (long)T, nz, d_cross, st));
+    return TA_OK;
+}
+
+// One Onsager call on a pair-major position slab (the caller has opened the call's bracket, it is closed here): the one
+// pass that forms every species' moment, the fixed-order sum of its partials into d_moments (S, T, D), and with d_cross
+// the cross MSD of the moments.  ev[1] / ev[2] bracket the pass, unless an FFT evaluation after it records its own
+// forward kernel there.
+int ons_pm(ta_ctx* ctx, bool fft, const void* pm_any, bool pm_f32, int64_t pitch, int64_t T, int64_t A, int D, int S,
+           const int32_t* d_species, const double* d_w, double* d_moments, double* d_cross, hipStream_t st) {
+    const int64_t n_cols = A * D;
+    if (n_cols >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "Onsager moments: n_atoms * dim must be below 2^31");
+    // float32 device slabs: a float64 copy first, as cond_pm does
+    if (pm_f32) TA_CHECK(widen_input(ctx, 0, pitch, n_cols, st, &pm_any));
+    const int n_parts = species_moment_parts(ctx->n_cu, S, (long)T, (long)n_cols);
+    const size_t n_out = (size_t)S * T * D;
+    TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)n_parts * n_out));
+    TA_LAUNCH_MAIN(ctx, "k_species_moment", st,
+                   launch_species_moment((const double*)pm_any, (long)pitch, (long)T, (long)n_cols, D, S, d_species, d_w,
+                                         (double*)ctx->ons_part.p, n_parts, st));
+    TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)n_out, d_moments, st));
+    if (d_cross) TA_CHECK(ons_cross(ctx, fft, d_moments, S, T, D, d_cross, st));
+    return call_end(ctx, st);
+}
+
+int check_species_count(ta_ctx* ctx, int S) {
+    if (S < 1 || S > TA_ONSAGER_MAX_SPECIES)
+        return fail(ctx, TA_E_INVALID, "n_species must be 1 ... " + std::to_string(TA_ONSAGER_MAX_SPECIES));
+    return TA_OK;
+}
+int ons_args(ta_ctx* ctx, int fft, int S, const void* species, const void* moments) {
+    TA_CHECK(check_fft(ctx, fft));
+    TA_CHECK(check_species_count(ctx, S));
+    if (!species) return fail(ctx, TA_E_INVALID, "species labels are NULL");
+    if (!moments) return fail(ctx, TA_E_INVALID, "moments output is NULL");
+    return TA_OK;
+}
+int check_labels(ta_ctx* ctx, const int32_t* h_species, int64_t n, int S) {
+    for (int64_t a = 0; a < n; ++a)
+        if (h_species[a] < 0 || h_species[a] >= S)
+            return fail(ctx, TA_E_INVALID, "species label " + std::to_string(h_species[a]) + " of atom " + std::to_string(a) +
+                                               " is outside 0 ... n_species - 1");
+    return TA_OK;
+}
+
 // ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
 // This is the seam: a CPU context's staging and host-facing calls end up in the cpu_* functions below, reached by one
 // early branch of their entry point (after the checks both kinds of context share); nothing below makes a HIP call.
@@ -1565,6 +1632,39 @@ int ta_conductivity_staged(ta_ctx* ctx, int fft, const double* d_charges, double
     });
 }
 
+// Onsager transport coefficients: slab 0 / d_pos holds the positions; device labels are not checked (k_species_moment
+// skips an atom whose label is out of range)
+int ta_onsager_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int fft, int n_species,
+                   const int32_t* d_species, const double* d_weights, double* d_moments, double* d_cross, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    TA_NO_CPU(ctx);
+    TA_CHECK(check_shape(ctx, T, A, D, ld_row));
+    TA_CHECK(ons_args(ctx, fft, n_species, d_species, d_moments));
+    if (!d_pos) return fail(ctx, TA_E_INVALID, "null device pointer");
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    TA_CHECK(call_begin(ctx, st));
+    const double* px = nullptr;
+    TA_CHECK(relayout_input(ctx, 0, d_pos, T, A * D, ld_row, st, &px));
+    return ons_pm(ctx, fft != 0, px, false, pm_pitch(T), T, A, D, n_species, d_species, d_weights, d_moments, d_cross, st);
+    });
+}
+
+int ta_onsager_staged(ta_ctx* ctx, int fft, int n_species, const int32_t* d_species, const double* d_weights,
+                      double* d_moments, double* d_cross, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(ons_args(ctx, fft, n_species, d_species, d_moments));
+    TA_CHECK(check_staged(ctx));
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TA_CHECK(order_after_staging(ctx, (hipStream_t)stream));
+    TA_CHECK(call_begin(ctx, (hipStream_t)stream));
+    return ons_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A, ctx->st_D, n_species,
+                  d_species, d_weights, d_moments, d_cross, (hipStream_t)stream);
+    });
+}
+
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guarded(fail, ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
@@ -1786,6 +1886,48 @@ int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T
     return host_finish(ctx, {{h_coll, out + T * D, (size_t)T}});
 }
 
+// Onsager share of a host-facing call, queued on ctx->stream and not waited for: the labels and weights (this context's
+// atoms, labels already checked) uploaded, the (S, T, D) moments and with cross the (T, S, S) cross MSD behind them left
+// on the device in *d_out.
+int ons_launch(ta_ctx* ctx, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out) {
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(check_staged(ctx));
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t T = ctx->st_T, A = ctx->st_A;
+    const int D = ctx->st_D;
+    TA_CHECK(ensure(ctx, ctx->ons_lab, sizeof(int32_t) * A));
+    if (h_w) TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * A));
+    TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)T * S * (D + S)));
+    double* out = (double*)ctx->ons_out.p;
+    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_lab.p, h_species, sizeof(int32_t) * A, hipMemcpyHostToDevice, ctx->stream));
+    if (h_w) TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_w.p, h_w, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
+    TA_CHECK(order_after_staging(ctx, ctx->stream));
+    TA_CHECK(call_begin(ctx, ctx->stream));
+    TA_CHECK(ons_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, T, A, D, S, (const int32_t*)ctx->ons_lab.p,
+                    h_w ? (const double*)ctx->ons_w.p : nullptr, out, cross ? out + (size_t)S * T * D : nullptr, ctx->stream));
+    *d_out = out;
+    return TA_OK;
+}
+
+// The cross MSD of host (S, T, D) moments on this context's device, blocking, as a compute call of its own (ta_onsager_cross;
+// the group's ONE evaluation after its members' sums).  Needs no staged slab.
+int ons_cross_host(ta_ctx* ctx, int fft, const double* h_moments, int S, int64_t T, int D, double* h_cross) {
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TA_CHECK(ctx->commits.flush());
+    TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)T * S * (D + S)));
+    double* out = (double*)ctx->ons_out.p;
+    double* cross = out + (size_t)S * T * D;
+    hipStream_t st = ctx->stream;
+    TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_moments, sizeof(double) * (size_t)S * T * D, hipMemcpyHostToDevice, st));
+    TA_CHECK(call_begin(ctx, st));
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));  // no dominant kernel of its own, unless msd_impl records one
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
+    TA_CHECK(ons_cross(ctx, fft != 0, out, S, T, D, cross, st));
+    TA_CHECK(call_end(ctx, st));
+    return host_finish(ctx, {{h_cross, cross, (size_t)T * S * S}});
+}
+
 // One context's unwrap of staged slab `slab` (ta_unwrap, ta_group_unwrap), queued on ctx->stream behind the queued commits
 // and bracketed by the timing events: the box table's copy (box.tab must stay valid until host_wait), then the kernel
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes) {
@@ -1879,6 +2021,42 @@ int ta_conductivity(ta_ctx* ctx, int fft, const double* h_charges, double* h_mom
     TA_CHECK(ta::cond_launch(ctx, fft, h_charges, h_collective != nullptr, h_self_lagsum != nullptr, &d_out));
     const size_t T = (size_t)ctx->st_T, D = (size_t)ctx->st_D;
     return host_finish(ctx, {{h_moment, d_out, T * D}, {h_collective, d_out + T * D, T}, {h_self_lagsum, d_out + T * (D + 1), T}});
+    });
+}
+
+int ta_onsager(ta_ctx* ctx, int fft, int n_species, const int32_t* h_species, const double* h_weights, double* h_moments,
+               double* h_cross) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(ons_args(ctx, fft, n_species, h_species, h_moments));
+    TA_CHECK(check_staged(ctx));
+    TA_CHECK(check_labels(ctx, h_species, ctx->st_A, n_species));
+    if (ctx->is_cpu) {
+        if (int rc = ta::cpu::onsager(cpu_state(ctx), fft != 0, n_species, h_species, h_weights, h_moments, h_cross))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    double* d_out = nullptr;
+    TA_CHECK(ta::ons_launch(ctx, fft, n_species, h_species, h_weights, h_cross != nullptr, &d_out));
+    const size_t T = (size_t)ctx->st_T, D = (size_t)ctx->st_D, S = (size_t)n_species;
+    return host_finish(ctx, {{h_moments, d_out, S * T * D}, {h_cross, d_out + S * T * D, T * S * S}});
+    });
+}
+
+int ta_onsager_cross(ta_ctx* ctx, int fft, const double* h_moments, int n_species, int64_t n_frames, int dim, double* h_cross) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(check_fft(ctx, fft));
+    TA_CHECK(check_species_count(ctx, n_species));
+    if (!h_moments || !h_cross) return fail(ctx, TA_E_INVALID, "moments or cross output is NULL");
+    if (n_frames < 1 || dim < 1 || dim > 3 || n_frames > (int64_t)1 << 30)
+        return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30, 1 <= dim <= 3");
+    if (ctx->is_cpu) {
+        if (int rc = ta::cpu::onsager_cross(ctx->cpu_threads, fft != 0, h_moments, n_species, n_frames, dim, h_cross))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    return ta::ons_cross_host(ctx, fft, h_moments, n_species, n_frames, dim, h_cross);
     });
 }
 

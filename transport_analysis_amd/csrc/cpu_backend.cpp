@@ -438,6 +438,67 @@ int conductivity(const State& s, bool fft, const double* q, double* moment, doub
     return rc;
 }
 
+int onsager_cross(int threads, bool fft, const double* moments, int S, int64_t T, int D, double* cross) {
+    const int64_t P = (int64_t)S * S;
+    std::vector<double> pm, bp, ts;
+    try {
+        pm.assign((size_t)T * P * D, 0.0);
+        bp.assign((size_t)T * P, 0.0);
+        ts.assign((size_t)T, 0.0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    bool nz[8] = {};
+    for (int i = 0; i < S; ++i)
+        for (int64_t k = 0; k < T * D && !nz[i]; ++k) nz[i] = moments[(size_t)i * T * D + k] != 0.0;
+    for (int64_t t = 0; t < T; ++t)
+        for (int i = 0; i < S; ++i)
+            for (int j = 0; j < S; ++j)
+                for (int d = 0; d < D; ++d) {
+                    const double mi = moments[((size_t)i * T + t) * D + d], mj = moments[((size_t)j * T + t) * D + d];
+                    pm[((size_t)t * P + i * S + j) * D + d] = i == j ? mi : i < j ? mi + mj : mi - mj;
+                }
+    State ps;
+    ps.T = T, ps.A = P, ps.D = D, ps.dtype = TA_F64, ps.threads = threads;
+    ps.slabs = {pm.data()};
+    if (T >= 2)
+        if (int rc = msd(ps, fft, ts.data(), bp.data())) return rc;
+    for (int64_t k = 0; k < T; ++k)
+        for (int i = 0; i < S; ++i)
+            for (int j = 0; j < S; ++j) {
+                const int lo = i < j ? i : j, hi = i < j ? j : i;
+                const double* row = bp.data() + (size_t)k * P;
+                double c = 0.0;
+                if (k > 0 && nz[i] && nz[j]) c = i == j ? row[i * S + i] : 0.25 * (row[lo * S + hi] - row[hi * S + lo]);
+                cross[((size_t)k * S + i) * S + j] = c;
+            }
+    return TA_OK;
+}
+
+int onsager(const State& s, bool fft, int S, const int32_t* species, const double* w, double* moments, double* cross) {
+    const int64_t T = s.T, A = s.A;
+    const int D = s.D;
+    const void* slab = s.slabs[0];
+    const bool f32 = s.dtype == TA_F32;
+#pragma omp parallel for num_threads(s.threads) schedule(static)
+    for (int64_t t = 0; t < T; ++t) {
+        double acc[8][3] = {};
+        for (int64_t n = 0; n < A; ++n) {
+            const double wn = w ? w[n] : 1.0;
+            double* a = acc[species[n]];
+            for (int d = 0; d < D; ++d) {
+                const size_t i0 = (size_t)n * D + d, i = (size_t)t * A * D + i0;
+                const double x = f32 ? elem<float>(slab, i) : elem<double>(slab, i);
+                const double x0 = f32 ? elem<float>(slab, i0) : elem<double>(slab, i0);
+                a[d] += wn * (x - x0);
+            }
+        }
+        for (int sp = 0; sp < S; ++sp)
+            for (int d = 0; d < D; ++d) moments[((size_t)sp * T + t) * D + d] = acc[sp][d];
+    }
+    return cross ? onsager_cross(s.threads, fft, moments, S, T, D, cross) : TA_OK;
+}
+
 template <class E>
 void unwrap_t(const State& s, int slab, const BoxTable& box, const int* axes) {
     const int64_t T = s.T, A = s.A, tp = box.per_frame ? box.tpitch : 0;

@@ -26,6 +26,12 @@ int msd(const State& s, bool fft, double* timeseries, double* by_particle);
 // Einstein-Helfand conductivity of slab 0: moment (n_frames, dim) = sum_n q_n (x - x[0]); collective (or NULL) = the MSD lag
 // sum of the moment; self_lagsum (or NULL) = sum_n q_n^2 MSD_n, both by msd() with the same fft
 int conductivity(const State& s, bool fft, const double* charges, double* moment, double* collective, double* self_lagsum);
+// Onsager: moments (n_species, n_frames, dim) = sum_{n: species[n] = s} w_n (x - x[0]) of slab 0 (w NULL: all 1; labels
+// checked by the caller) and, with cross != NULL, onsager_cross of them
+int onsager(const State& s, bool fft, int n_species, const int32_t* species, const double* w, double* moments, double* cross);
+// cross (n_frames, S, S): C[k, i, j] = 1/4 (MSD(M_i + M_j) - MSD(M_i - M_j))[k] by ONE msd() call on the S^2 pseudo-particles
+// M_i, M_i + M_j, M_i - M_j; lag 0 and every pair with an all-zero moment exactly 0
+int onsager_cross(int threads, bool fft, const double* moments, int n_species, int64_t n_frames, int dim, double* cross);
 // ta_unwrap on host slab `slab` in place (box, axes checked by the caller)
 void unwrap(const State& s, int slab, const BoxTable& box, const int* axes);
 

@@ -76,6 +76,11 @@ int host_finish(ta_ctx* ctx, std::initializer_list<HostCopy> copies);
 // host_wait; and Phi of a host (n_frames, dim) moment on the context's device, blocking
 int cond_launch(ta_ctx* ctx, int fft, const double* h_q, bool coll, bool self, double** d_out);
 int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T, int D, double* h_coll);
+// api.hip, for group.hip: one context's ta_onsager share (its staged slab 0 with its atoms' labels h_species and weights
+// h_w or NULL, n_species the call's), queued: *d_out = the (n_species, n_frames, dim) moments, valid after host_wait; and
+// the cross MSD (n_frames, S, S) of host moments (S, n_frames, dim) on the context's device, blocking
+int ons_launch(ta_ctx* ctx, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out);
+int ons_cross_host(ta_ctx* ctx, int fft, const double* h_moments, int S, int64_t T, int D, double* h_cross);
 // api.hip, for group.hip: one context's ta_unwrap queued on its stream (box.tab must stay valid until host_wait)
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes);
 hipStream_t ctx_stream(ta_ctx* ctx);
@@ -178,6 +183,18 @@ hipError_t launch_msd_prepare_bp(const double* pos, long pitch, long T, long n_a
 int cond_moment_parts(int n_cu, long T, long n_cols);
 hipError_t launch_cond_moment(const double* pos, long pitch, long T, long n_cols, int D, const double* q, double* partial,
                               int n_parts, double* W, hipStream_t st);
+
+// onsager.hip: the species moments M[s, t, d] = sum_{n: species[n] = s} w_n (x[t, n, d] - x[0, n, d]) of a float64 pair-major
+// slab in one pass, as n_parts partial sums partial [n_parts][S][T][D] (written in full; k_sum_partials adds them in
+// order); species: (n_atoms,) int32 device labels, one outside [0, S) is skipped; w: (n_atoms,) weights or NULL (all 1).
+// combos: the pair-major slab (pitch rows per pair) of the S^2 pseudo-particles M_i, M_i + M_j, M_i - M_j of the moments
+// M (S, T, D), and nz[s] != 0 where M_s has a non-zero element (nz zeroed by the caller); finish: C (T, S, S) from their
+// (T, S^2) by-particle MSDs
+int species_moment_parts(int n_cu, int S, long T, long n_cols);
+hipError_t launch_species_moment(const double* pos, long pitch, long T, long n_cols, int D, int S, const int* species,
+                                 const double* w, double* partial, int n_parts, hipStream_t st);
+hipError_t launch_onsager_combos(const double* M, int S, long T, int D, long pitch, double* pm, int* nz, hipStream_t st);
+hipError_t launch_onsager_finish(const double* bp, int S, long T, const int* nz, double* C, hipStream_t st);
 
 // unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
 // box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)

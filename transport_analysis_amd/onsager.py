@@ -1,0 +1,171 @@
+"""Species-resolved Onsager transport coefficients on MI355X, from positions.
+
+``ConductivityHelfand`` gives the conductivity of the whole charge-weighted moment; this class resolves it by
+species (Fong, Bergstrom, McCloskey, Persson, *Macromolecules* 2020 / *AIChE J.* 2020):
+
+    L_ij = 1 / (2 D k_B T V) d/dt < dM_i(t) . dM_j(t) >,      M_s(t) = sum_{n in species s} w_n (x_n(t) - x_n(0))
+    sigma = e^2 sum_ij z_i z_j L_ij,        t_i = z_i sum_j z_j L_ij / sum_kl z_k z_l L_kl
+
+One pass over the position slab forms the moments of ALL species (``k_species_moment`` behind ``ta_onsager`` of
+``include/ta_hip.h``, hand-written HIP); the cross mean squared displacements of the moments run on the library's
+Einstein MSD paths by polarisation.  Positions only, like ``EinsteinMSD``.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ._base import StagedAnalysis, UpdatingAtomGroup, parse_dim_type
+from .conductivity import BOLTZMANN_J_PER_K, ELEMENTARY_CHARGE
+
+#: ta_hip.h: TA_ONSAGER_MAX_SPECIES
+MAX_SPECIES = 8
+
+
+class OnsagerHelfand(StagedAnalysis):
+    r"""Onsager transport coefficients of the species of a system by the Einstein-Helfand relation.
+
+    .. math:: C_{ij}(k) = \frac{1}{T - k} \sum_{t < T - k} \sum_d (M_{i; t+k, d} - M_{i; t, d}) (M_{j; t+k, d} - M_{j; t, d}),
+              \qquad M_{s; t, d} = \sum_{n \in s} w_n (x_{t, n, d} - x_{0, n, d})
+
+    summed over the dimensions of ``dim_type``; :math:`L_{ij}` = slope of :math:`C_{ij}` against lag time
+    / (2 D k_B <V> T_avg), with D the number of those dimensions.
+
+    Parameters
+    ----------
+    atomgroup : AtomGroup — positions must be unwrapped (``unwrap=True`` for a trajectory written wrapped into the box).
+    species : one label per atom of ``atomgroup`` (any sortable values, in any order: interleaved topologies are
+        fine; ``np.unique`` order defines the species index), or the name of a per-atom attribute of the group as a
+        string (``"types"``, ``"resnames"``).  At most 8 distinct labels.
+    temp_avg : float — average temperature (K), default 300.
+    dim_type : {'xyz', 'xy', 'yz', 'xz', 'x', 'y', 'z'}
+    linear_fit_window : (int, int) or None — lag indices [lo, hi) of the slope fits, against lag time k * dt (ps).
+    fft : bool — ``True``: the Einstein MSD's FFT form for the cross MSDs (up to 64 frames the exact direct kernel);
+        ``False``: the direct forms.  The error of ``C_ij`` is relative to ``max(C_ii, C_jj)``, not to ``|C_ij|``.
+    weights : array, keyword-only — one weight per atom (default 1: ``M_s`` is the species' summed displacement, and
+        charges enter through ``conductivity(z)``).  With ``weights=charges`` and one species, ``moments[0]`` and
+        ``timeseries[:, 0, 0]`` are ``ConductivityHelfand``'s moment and Phi.
+    unwrap : bool, keyword-only, default False — as for ``ConductivityHelfand``.
+    device, devices, distributed, stage_dtype : keyword-only — as for ``EinsteinMSD``.  Under ``distributed=True``
+        every rank forms the moments of its block of atoms with its slice of the labels; the moments are summed over
+        ranks BEFORE the correlation.
+
+    Attributes
+    ----------
+    results.species : the distinct labels, in species-index order.
+    results.moments : (S, n_frames, D) float64 — M (A times weight).
+    results.timeseries : (n_frames, S, S) float64 — C (A^2 times weight^2), symmetric, lag 0 exactly 0.
+    results.onsager : (S, S) float64, only with ``linear_fit_window`` — L_ij = slope x 1e22 / (2 D k_B <V> T_avg) in
+        (J m s)^-1 per particle^2 (A^2 / ps = 1e-8 m^2 / s, A^3 = 1e-30 m^3); divide by N_A^2 for mol^2 J^-1 m^-1 s^-1.
+
+    Not here: the per-species SELF terms (sum_{n in s} w_n^2 MSD_n: ``EinsteinMSD`` on the species' atoms, times their
+    number), a centre-of-mass reference frame, the Green-Kubo (velocity) form.
+    """
+
+    _stage_arrays = ("positions",)
+    _no_data_message = ("Onsager coefficient computation requires "
+                        "positions and box volume in the trajectory")
+
+    def __init__(self, atomgroup, species, temp_avg=300.0, dim_type="xyz", linear_fit_window=None, fft=True, *,
+                 weights=None, unwrap=False, **kwargs):
+        if isinstance(atomgroup, UpdatingAtomGroup):
+            raise TypeError("UpdatingAtomGroups are not valid for Onsager coefficient computation")
+        if kwargs.pop("by_particle", False):
+            raise TypeError("OnsagerHelfand has no per-particle result: the Onsager coefficients are collective "
+                            "(by_particle=True is not supported)")
+        super().__init__(atomgroup, by_particle=False, **kwargs)
+        self._unwrap = self.unwrap = bool(unwrap)
+
+        self.temp_avg = temp_avg
+        self.dim_type = dim_type.lower()
+        self._dim, self.dim_fac = parse_dim_type(self.dim_type)
+        self.linear_fit_window = linear_fit_window
+        self.fft = fft
+
+        self.atomgroup = self._group = atomgroup
+        self.n_particles = len(self.atomgroup)
+        if isinstance(species, str):
+            species = getattr(atomgroup, species)
+        labels = np.asarray(species).ravel()
+        if labels.size != self.n_particles:
+            raise ValueError(f"species: {labels.size} labels for {self.n_particles} atoms")
+        self.species, index = np.unique(labels, return_inverse=True)
+        if self.species.size > MAX_SPECIES:
+            raise ValueError(f"species: {self.species.size} distinct labels, at most {MAX_SPECIES} are supported")
+        self.species_index = np.ascontiguousarray(index, dtype=np.int32).ravel()
+        self.n_species = max(int(self.species.size), 1)
+        self.weights = None
+        if weights is not None:
+            self.weights = np.asarray(weights, dtype=np.float64).ravel()
+            if self.weights.size != self.n_particles:
+                raise ValueError(f"weights: {self.weights.size} values for {self.n_particles} atoms")
+
+    # see EinsteinMSD: atoms, not frames, are this path's parallel axis
+    _analysis_algorithm_is_parallelizable = False
+
+    @classmethod
+    def get_supported_backends(cls):
+        return ("serial",)
+
+    def _set_options(self, dtype):
+        self._ctx.set_option("stage_device_f32", 0)
+
+    def _prepare(self):
+        super()._prepare()
+        self._volumes = np.zeros(self.n_frames)
+        self.results.pop("onsager", None)  # a fit of an earlier run
+        self.results.species = self.species
+        self.results.moments = self.results.timeseries = None
+
+    @staticmethod
+    def _has_data(ts):
+        return ts.has_positions and ts.volume != 0
+
+    def _single_frame(self):
+        super()._single_frame()
+        self._volumes[self._frame_index] = self._ts.volume
+
+    def _evaluate(self):
+        fft, S = bool(self.fft), self.n_species
+        if self._distributed:
+            from .dist import allreduce_sum
+
+            if self._n_local:
+                w = None if self.weights is None else self.weights[self._lo:self._hi]
+                moments, _ = self._ctx.onsager(fft, self.species_index[self._lo:self._hi], S, w, cross=False)
+            else:  # more ranks than atoms: this rank contributes nothing
+                moments = np.zeros((S, self.n_frames, self.dim_fac))
+            moments = allreduce_sum(moments, self._device)
+            cross = self._ctx.onsager_cross(moments, fft)
+        else:
+            moments, cross = self._ctx.onsager(fft, self.species_index, S, self.weights)
+        self.results.moments = moments
+        self.results.timeseries = cross
+        self._vol_avg = np.average(self._volumes)
+        if self.linear_fit_window is not None:
+            lo, hi = self.linear_fit_window[0], self.linear_fit_window[1]
+            t = self.lag_times()[lo:hi]
+            slopes = np.array([[np.polyfit(t, cross[lo:hi, i, j], 1)[0] for j in range(S)] for i in range(S)])
+            self.results.onsager = slopes * 1e22 / (2 * self.dim_fac * BOLTZMANN_J_PER_K * self._vol_avg * self.temp_avg)
+
+    def lag_times(self):
+        """Lag times k * dt (ps) of the timeseries, dt the spacing of the analysed frames' times."""
+        dt = float(self.times[1] - self.times[0]) if self.n_frames > 1 else 0.0
+        return np.arange(self.n_frames) * dt
+
+    def _charge_weighted(self, z):
+        if "onsager" not in self.results:
+            raise ValueError("the Onsager coefficients need a fit: pass linear_fit_window=(lo, hi)")
+        z = np.asarray(z, dtype=np.float64).ravel()
+        if z.size != self.n_species:
+            raise ValueError(f"z: {z.size} charges for {self.n_species} species")
+        return z[:, None] * z[None, :] * self.results.onsager
+
+    def conductivity(self, z):
+        """sigma = e^2 sum_ij z_i z_j L_ij in S/m for one charge number per species (index order of
+        ``results.species``); with unit weights this is ``ConductivityHelfand``'s value for charges ``z[species]``."""
+        return ELEMENTARY_CHARGE ** 2 * float(self._charge_weighted(z).sum())
+
+    def transference_numbers(self, z):
+        """t_i = z_i sum_j z_j L_ij / sum_kl z_k z_l L_kl, one per species; they add up to 1."""
+        zlz = self._charge_weighted(z)
+        return zlz.sum(axis=1) / zlz.sum()
