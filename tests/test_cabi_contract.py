@@ -32,6 +32,15 @@ MFMA = ("direct_mfma: 0 vector kernels, 1 by trajectory length (default), 3 matr
 COLUMNS = "columns col0 + k col_step (k < n_col) must lie inside a source row of ld_row elements"
 GROUP_SHAPE = "need n_frames >= 1, n_atoms >= 1, 1 <= dim <= 3, 1 <= n_slabs <= 4"
 NULL_GROUP = "null group"
+SPECIES = "n_species must be 1 ... 8"
+LABELS_NULL = "species labels are NULL"
+MOMENTS_NULL = "moments output is NULL"
+CROSS_NULL = "moments or cross output is NULL"
+CROSS_SHAPE = "need 1 <= n_frames <= 2^30, 1 <= dim <= 3"
+GROUP_ONS_NULL = "species labels or moments are NULL"
+LABEL_NEG = "species label -1 of atom 0 is outside 0 ... n_species - 1"
+LABEL_HI = "species label 2 of atom 2 is outside 0 ... n_species - 1"
+S = 2
 
 # every option key of ta_set_option with a value it accepts (its default) and, where the key validates, one it rejects
 OPTIONS = [
@@ -58,6 +67,12 @@ class Bufs:
         self.mom = np.zeros((T, D))
         self.phi = np.zeros(T)
         self.slf = np.zeros(T)
+        self.lab = np.array([0, 1, 0], dtype=np.int32)
+        self.lab_neg = np.array([-1, 1, 0], dtype=np.int32)
+        self.lab_hi = np.array([0, 1, S], dtype=np.int32)
+        self.w = np.array([1.0, -0.5, 2.0])
+        self.moms = np.zeros((S, T, D))
+        self.cross = np.zeros((T, S, S))
         self.box = np.tile(np.array([10.0, 10.0, 10.0, 90.0, 90.0, 90.0]), (T, 1))
         self.badbox = np.tile(np.array([-1.0, 10.0, 10.0, 90.0, 90.0, 90.0]), (T, 1))
         self.tric = np.tile(np.array([10.0, 10.0, 10.0, 80.0, 90.0, 90.0]), (T, 1))
@@ -287,6 +302,46 @@ CTX_ROWS = [
      "moment output is NULL"),
     ("cond-good", "*_staged", lambda L, h, B: L.ta_conductivity(h, 1, B.p("q"), B.p("mom"), B.p("phi"), B.p("slf")), 0, None),
     ("cond-good-moment-only", "*_staged1", lambda L, h, B: L.ta_conductivity(h, 0, B.p("q"), B.p("mom"), None, None), 0, None),
+    # ---- host-facing: ta_onsager (the rows of ta_conductivity, the species count and the labels' range)
+    ("ons-null", "null", lambda L, h, B: L.ta_onsager(None, 1, S, B.p("lab"), None, B.p("moms"), None), INVALID, NULL_CTX),
+    ("ons-null+fft", "null", lambda L, h, B: L.ta_onsager(None, 2, S, B.p("lab"), None, B.p("moms"), None), INVALID, NULL_CTX),
+    ("ons-fft", "*_staged", lambda L, h, B: L.ta_onsager(h, 2, S, B.p("lab"), None, B.p("moms"), None), INVALID, FFT_FLAG),
+    ("ons-species-0", "*_staged", lambda L, h, B: L.ta_onsager(h, 0, 0, B.p("lab"), None, B.p("moms"), None), INVALID, SPECIES),
+    ("ons-species-9", "*_staged", lambda L, h, B: L.ta_onsager(h, 0, 9, B.p("lab"), None, B.p("moms"), None), INVALID, SPECIES),
+    ("ons-labels", "*_staged", lambda L, h, B: L.ta_onsager(h, 0, S, None, None, B.p("moms"), None), INVALID, LABELS_NULL),
+    ("ons-moments", "*_staged", lambda L, h, B: L.ta_onsager(h, 0, S, B.p("lab"), None, None, None), INVALID, MOMENTS_NULL),
+    ("ons-fft+species-count", "*_staged", lambda L, h, B: L.ta_onsager(h, 2, 0, B.p("lab"), None, B.p("moms"), None), INVALID, FFT_FLAG),
+    ("ons-fft+labels", "*_staged", lambda L, h, B: L.ta_onsager(h, 2, S, None, None, B.p("moms"), None), INVALID, FFT_FLAG),
+    ("ons-species-count+labels", "*_staged", lambda L, h, B: L.ta_onsager(h, 1, 9, None, None, B.p("moms"), None), INVALID, SPECIES),
+    ("ons-labels+moments", "*_staged", lambda L, h, B: L.ta_onsager(h, 1, S, None, None, None, None), INVALID, LABELS_NULL),
+    ("ons-fresh", "*_fresh", lambda L, h, B: L.ta_onsager(h, 1, S, B.p("lab"), None, B.p("moms"), None), STATE, NOT_STAGED),
+    ("ons-fft+fresh", "*_fresh", lambda L, h, B: L.ta_onsager(h, 2, S, B.p("lab"), None, B.p("moms"), None), INVALID, FFT_FLAG),
+    ("ons-moments+fresh", "*_fresh", lambda L, h, B: L.ta_onsager(h, 1, S, B.p("lab"), None, None, None), INVALID, MOMENTS_NULL),
+    ("ons-label-negative", "*_staged", lambda L, h, B: L.ta_onsager(h, 1, S, B.p("lab_neg"), None, B.p("moms"), None), INVALID, LABEL_NEG),
+    ("ons-label-n_species", "*_staged", lambda L, h, B: L.ta_onsager(h, 1, S, B.p("lab_hi"), None, B.p("moms"), None), INVALID, LABEL_HI),
+    ("ons-moments+label", "*_staged", lambda L, h, B: L.ta_onsager(h, 1, S, B.p("lab_neg"), None, None, None), INVALID, MOMENTS_NULL),
+    ("ons-good", "*_staged", lambda L, h, B: L.ta_onsager(h, 1, S, B.p("lab"), B.p("w"), B.p("moms"), B.p("cross")), 0, None),
+    ("ons-good-moments-only", "*_staged1", lambda L, h, B: L.ta_onsager(h, 0, S, B.p("lab"), None, B.p("moms"), None), 0, None),
+    # ---- host-facing: ta_onsager_cross (needs no slab)
+    ("ons_cross-null", "null", lambda L, h, B: L.ta_onsager_cross(None, 1, B.p("moms"), S, T, D, B.p("cross")), INVALID, NULL_CTX),
+    ("ons_cross-null+fft", "null", lambda L, h, B: L.ta_onsager_cross(None, 2, B.p("moms"), S, T, D, B.p("cross")), INVALID, NULL_CTX),
+    ("ons_cross-fft", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 2, B.p("moms"), S, T, D, B.p("cross")), INVALID, FFT_FLAG),
+    ("ons_cross-species-0", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, B.p("moms"), 0, T, D, B.p("cross")), INVALID, SPECIES),
+    ("ons_cross-species-9", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, B.p("moms"), 9, T, D, B.p("cross")), INVALID, SPECIES),
+    ("ons_cross-moments-null", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, None, S, T, D, B.p("cross")), INVALID, CROSS_NULL),
+    ("ons_cross-cross-null", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, B.p("moms"), S, T, D, None), INVALID, CROSS_NULL),
+    ("ons_cross-frames-0", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, B.p("moms"), S, 0, D, B.p("cross")), INVALID, CROSS_SHAPE),
+    ("ons_cross-dim-4", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, B.p("moms"), S, T, 4, B.p("cross")), INVALID, CROSS_SHAPE),
+    ("ons_cross-dim-0", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, B.p("moms"), S, T, 0, B.p("cross")), INVALID, CROSS_SHAPE),
+    ("ons_cross-frames-too-many", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, B.p("moms"), S, BIG, D, B.p("cross")), INVALID,
+     CROSS_SHAPE),
+    ("ons_cross-fft+species-count", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 2, B.p("moms"), 0, T, D, B.p("cross")), INVALID,
+     FFT_FLAG),
+    ("ons_cross-species-count+null-arrays", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, None, 9, T, D, None), INVALID, SPECIES),
+    ("ons_cross-null-arrays+frames", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, None, S, 0, D, None), INVALID, CROSS_NULL),
+    ("ons_cross-good", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, B.p("moms"), S, T, D, B.p("cross")), 0, None),
+    ("ons_cross-good-direct-staged", "*_staged", lambda L, h, B: L.ta_onsager_cross(h, 0, B.p("moms"), S, T, D, B.p("cross")), 0, None),
+    ("ons_cross-good-one-frame", "*_fresh", lambda L, h, B: L.ta_onsager_cross(h, 1, B.p("moms"), S, 1, D, B.p("cross")), 0, None),
     # ---- host-facing: ta_unwrap
     ("unwrap-null", "null", lambda L, h, B: L.ta_unwrap(None, 0, B.p("box"), B.p("axes")), INVALID, NULL_CTX),
     ("unwrap-dims-null", "*_staged", lambda L, h, B: L.ta_unwrap(h, 0, None, B.p("axes")), INVALID, "dimensions or axes are NULL"),
@@ -321,6 +376,10 @@ CTX_ROWS = [
     ("cond_dev-cpu", "cpu_staged", lambda L, h, B: L.ta_conductivity_dev(h, B.fake, T, A, D, A * D, 1, B.fake, B.fake, None, None, None),
      UNSUPPORTED, NO_CPU),
     ("cond_dev-cpu+fft", "cpu_staged", lambda L, h, B: L.ta_conductivity_dev(h, B.fake, T, A, D, A * D, 2, B.fake, B.fake, None, None, None),
+     UNSUPPORTED, NO_CPU),
+    ("ons_dev-cpu", "cpu_staged", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, A * D, 1, S, B.fake, None, B.fake, None, None),
+     UNSUPPORTED, NO_CPU),
+    ("ons_dev-cpu+fft", "cpu_staged", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, A * D, 2, S, B.fake, None, B.fake, None, None),
      UNSUPPORTED, NO_CPU),
     ("vacf_fft_dev-cpu+shape", "cpu_fresh", lambda L, h, B: L.ta_vacf_fft_dev(h, B.fake, 0, A, D, A * D, B.fake, None, 0, None),
      UNSUPPORTED, NO_CPU),
@@ -367,6 +426,38 @@ CTX_ROWS = [
      INVALID, NULL_DEV),
     ("cond_dev-charges+pos-null", "gpu_fresh",
      lambda L, h, B: L.ta_conductivity_dev(h, None, T, A, D, A * D, 1, None, B.fake, None, None, None), INVALID, "charges are NULL"),
+    ("ons_dev-null", "null", lambda L, h, B: L.ta_onsager_dev(None, B.fake, T, A, D, A * D, 1, S, B.fake, None, B.fake, None, None),
+     INVALID, NULL_CTX),
+    ("ons_dev-shape", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, 0, D, A * D, 1, S, B.fake, None, B.fake, None, None),
+     INVALID, SHAPE),
+    ("ons_dev-ld_row", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, 1, 1, S, B.fake, None, B.fake, None, None),
+     INVALID, LD_ROW),
+    ("ons_dev-shape+fft", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, 0, D, A * D, 2, S, B.fake, None, B.fake, None, None),
+     INVALID, SHAPE),
+    ("ons_dev-ld_row+species-count", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, 1, 1, 0, B.fake, None, B.fake, None, None),
+     INVALID, LD_ROW),
+    ("ons_dev-fft", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, A * D, 2, S, B.fake, None, B.fake, None, None),
+     INVALID, FFT_FLAG),
+    ("ons_dev-species-0", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, A * D, 1, 0, B.fake, None, B.fake, None, None),
+     INVALID, SPECIES),
+    ("ons_dev-species-9", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, A * D, 1, 9, B.fake, None, B.fake, None, None),
+     INVALID, SPECIES),
+    ("ons_dev-fft+species-count", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, A * D, 2, 9, B.fake, None, B.fake, None, None),
+     INVALID, FFT_FLAG),
+    ("ons_dev-labels", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, A * D, 1, S, None, None, B.fake, None, None),
+     INVALID, LABELS_NULL),
+    ("ons_dev-moments", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, A * D, 1, S, B.fake, None, None, None, None),
+     INVALID, MOMENTS_NULL),
+    ("ons_dev-species-count+labels", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, A * D, 1, 0, None, None, B.fake, None, None),
+     INVALID, SPECIES),
+    ("ons_dev-labels+moments", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, B.fake, T, A, D, A * D, 1, S, None, None, None, None, None),
+     INVALID, LABELS_NULL),
+    ("ons_dev-pos-null", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, None, T, A, D, A * D, 1, S, B.fake, None, B.fake, None, None),
+     INVALID, NULL_DEV),
+    ("ons_dev-labels+pos-null", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, None, T, A, D, A * D, 1, S, None, None, B.fake, None, None),
+     INVALID, LABELS_NULL),
+    ("ons_dev-moments+pos-null", "gpu_fresh", lambda L, h, B: L.ta_onsager_dev(h, None, T, A, D, A * D, 1, S, B.fake, None, None, None, None),
+     INVALID, MOMENTS_NULL),
     # ---- device-facing compute: *_staged
     ("vacf_fft_staged-null", "null", lambda L, h, B: L.ta_vacf_fft_staged(None, B.fake, None, 0, None), INVALID, NULL_CTX),
     ("vacf_fft_staged-cpu", "cpu_staged", lambda L, h, B: L.ta_vacf_fft_staged(h, B.fake, None, 0, None), UNSUPPORTED, NO_CPU),
@@ -379,6 +470,8 @@ CTX_ROWS = [
      NO_CPU),
     ("cond_staged-cpu+fft", "cpu_fresh", lambda L, h, B: L.ta_conductivity_staged(h, 2, None, None, None, None, None), UNSUPPORTED,
      NO_CPU),
+    ("ons_staged-cpu", "cpu_staged", lambda L, h, B: L.ta_onsager_staged(h, 1, S, B.fake, None, B.fake, None, None), UNSUPPORTED, NO_CPU),
+    ("ons_staged-cpu+fft", "cpu_fresh", lambda L, h, B: L.ta_onsager_staged(h, 2, 0, None, None, None, None, None), UNSUPPORTED, NO_CPU),
     ("vacf_fft_staged-cpu+fresh", "cpu_fresh", lambda L, h, B: L.ta_vacf_fft_staged(h, None, None, 0, None), UNSUPPORTED, NO_CPU),
     ("vacf_fft_staged-fresh", "gpu_fresh", lambda L, h, B: L.ta_vacf_fft_staged(h, B.fake, None, 0, None), STATE, NOT_STAGED),
     ("vacf_fft_staged-fresh+null-pointer", "gpu_fresh", lambda L, h, B: L.ta_vacf_fft_staged(h, None, None, 0, None), STATE, NOT_STAGED),
@@ -402,6 +495,18 @@ CTX_ROWS = [
     ("cond_staged-fresh", "gpu_fresh", lambda L, h, B: L.ta_conductivity_staged(h, 1, B.fake, B.fake, None, None, None), STATE, NOT_STAGED),
     ("cond_staged-charges+fresh", "gpu_fresh", lambda L, h, B: L.ta_conductivity_staged(h, 1, None, B.fake, None, None, None), INVALID,
      "charges are NULL"),
+    ("ons_staged-null", "null", lambda L, h, B: L.ta_onsager_staged(None, 1, S, B.fake, None, B.fake, None, None), INVALID, NULL_CTX),
+    ("ons_staged-fft", "gpu_staged", lambda L, h, B: L.ta_onsager_staged(h, 2, S, B.fake, None, B.fake, None, None), INVALID, FFT_FLAG),
+    ("ons_staged-species-0", "gpu_staged", lambda L, h, B: L.ta_onsager_staged(h, 1, 0, B.fake, None, B.fake, None, None), INVALID, SPECIES),
+    ("ons_staged-species-9", "gpu_staged", lambda L, h, B: L.ta_onsager_staged(h, 1, 9, B.fake, None, B.fake, None, None), INVALID, SPECIES),
+    ("ons_staged-fft+species-count", "gpu_staged", lambda L, h, B: L.ta_onsager_staged(h, 2, 0, B.fake, None, B.fake, None, None), INVALID, FFT_FLAG),
+    ("ons_staged-labels", "gpu_staged", lambda L, h, B: L.ta_onsager_staged(h, 1, S, None, None, B.fake, None, None), INVALID, LABELS_NULL),
+    ("ons_staged-moments", "gpu_staged", lambda L, h, B: L.ta_onsager_staged(h, 1, S, B.fake, None, None, None, None), INVALID, MOMENTS_NULL),
+    ("ons_staged-species-count+labels", "gpu_staged", lambda L, h, B: L.ta_onsager_staged(h, 1, 9, None, None, B.fake, None, None), INVALID, SPECIES),
+    ("ons_staged-labels+moments", "gpu_staged", lambda L, h, B: L.ta_onsager_staged(h, 1, S, None, None, None, None, None), INVALID, LABELS_NULL),
+    ("ons_staged-fresh", "gpu_fresh", lambda L, h, B: L.ta_onsager_staged(h, 1, S, B.fake, None, B.fake, None, None), STATE, NOT_STAGED),
+    ("ons_staged-labels+fresh", "gpu_fresh", lambda L, h, B: L.ta_onsager_staged(h, 1, S, None, None, B.fake, None, None), INVALID, LABELS_NULL),
+    ("ons_staged-species-count+fresh", "gpu_fresh", lambda L, h, B: L.ta_onsager_staged(h, 1, 0, B.fake, None, B.fake, None, None), INVALID, SPECIES),
 ]
 
 GROUP_ROWS = [
@@ -430,6 +535,7 @@ GROUP_ROWS = [
     ("msd-null", "gnull", lambda L, g, B: L.ta_group_msd(None, 1, B.p("ts"), None), INVALID, NULL_GROUP),
     ("msd-fft+null", "gnull", lambda L, g, B: L.ta_group_msd(None, 2, B.p("ts"), None), INVALID, FFT_FLAG),
     ("cond-null", "gnull", lambda L, g, B: L.ta_group_conductivity(None, 2, None, None, None, None), INVALID, NULL_GROUP),
+    ("ons-null", "gnull", lambda L, g, B: L.ta_group_onsager(None, 2, 0, None, None, None, None), INVALID, NULL_GROUP),
     ("unwrap-null", "gnull", lambda L, g, B: L.ta_group_unwrap(None, 0, None, None), INVALID, NULL_GROUP),
     # ---- options
     ("set_option-key-null", "g_fresh", lambda L, g, B: L.ta_group_set_option(g, None, 1), INVALID, NULL_ARG),
@@ -503,6 +609,20 @@ GROUP_ROWS = [
      "charges, moment or collective is NULL"),
     ("cond-fresh", "g_fresh", lambda L, g, B: L.ta_group_conductivity(g, 1, B.p("q"), B.p("mom"), B.p("phi"), None), STATE, NOT_STAGED),
     ("cond-good", "g_staged", lambda L, g, B: L.ta_group_conductivity(g, 0, B.p("q"), B.p("mom"), B.p("phi"), B.p("slf")), 0, None),
+    ("ons-fft", "g_staged", lambda L, g, B: L.ta_group_onsager(g, 2, S, B.p("lab"), None, B.p("moms"), None), INVALID, FFT_FLAG),
+    ("ons-fft+species-count", "g_staged", lambda L, g, B: L.ta_group_onsager(g, 2, 0, B.p("lab"), None, B.p("moms"), None), INVALID, FFT_FLAG),
+    ("ons-species-0", "g_staged", lambda L, g, B: L.ta_group_onsager(g, 1, 0, B.p("lab"), None, B.p("moms"), None), INVALID, SPECIES),
+    ("ons-species-9", "g_staged", lambda L, g, B: L.ta_group_onsager(g, 1, 9, B.p("lab"), None, B.p("moms"), None), INVALID, SPECIES),
+    ("ons-species-count+labels", "g_staged", lambda L, g, B: L.ta_group_onsager(g, 1, 9, None, None, B.p("moms"), None), INVALID, SPECIES),
+    ("ons-labels", "g_staged", lambda L, g, B: L.ta_group_onsager(g, 1, S, None, None, B.p("moms"), None), INVALID, GROUP_ONS_NULL),
+    ("ons-moments", "g_staged", lambda L, g, B: L.ta_group_onsager(g, 1, S, B.p("lab"), None, None, None), INVALID, GROUP_ONS_NULL),
+    ("ons-moments+fresh", "g_fresh", lambda L, g, B: L.ta_group_onsager(g, 1, S, B.p("lab"), None, None, None), INVALID, GROUP_ONS_NULL),
+    ("ons-fresh", "g_fresh", lambda L, g, B: L.ta_group_onsager(g, 1, S, B.p("lab"), None, B.p("moms"), None), STATE, NOT_STAGED),
+    ("ons-fresh+label", "g_fresh", lambda L, g, B: L.ta_group_onsager(g, 1, S, B.p("lab_neg"), None, B.p("moms"), None), STATE, NOT_STAGED),
+    ("ons-label-negative", "g_staged", lambda L, g, B: L.ta_group_onsager(g, 1, S, B.p("lab_neg"), None, B.p("moms"), None), INVALID, LABEL_NEG),
+    ("ons-label-n_species", "g_staged", lambda L, g, B: L.ta_group_onsager(g, 1, S, B.p("lab_hi"), None, B.p("moms"), None), INVALID, LABEL_HI),
+    ("ons-good", "g_staged", lambda L, g, B: L.ta_group_onsager(g, 0, S, B.p("lab"), B.p("w"), B.p("moms"), B.p("cross")), 0, None),
+    ("ons-good-moments-only", "g_staged", lambda L, g, B: L.ta_group_onsager(g, 1, S, B.p("lab"), None, B.p("moms"), None), 0, None),
     ("unwrap-dims-null", "g_staged", lambda L, g, B: L.ta_group_unwrap(g, 0, None, B.p("axes")), INVALID, "dimensions or axes are NULL"),
     ("unwrap-axes-null+fresh", "g_fresh", lambda L, g, B: L.ta_group_unwrap(g, 0, B.p("box"), None), INVALID,
      "dimensions or axes are NULL"),
@@ -598,11 +718,13 @@ def _fill(ctx, T_, A_, D_, n_slabs, seed):
 def _every_quantity(ctx, A_):
     m = np.linspace(1.0, 2.0, A_)
     q = np.where(np.arange(A_) % 2 == 0, 1.0, -0.5)
+    lab = np.arange(A_) % 3
     out = []
     for r in (ctx.vacf_fft(by_particle=True), ctx.vacf_fft(), ctx.vacf_direct(by_particle=True), ctx.vacf_direct(),
               ctx.helfand_msd(m, 3.0, by_particle=True), ctx.helfand_msd(m, 3.0), ctx.msd(True, by_particle=True),
               ctx.msd(False, by_particle=True), ctx.msd(True), ctx.conductivity(True, q, self_term=True),
-              ctx.conductivity(False, q, self_term=True)):
+              ctx.conductivity(False, q, self_term=True), ctx.onsager(True, lab, 3, weights=q),
+              ctx.onsager(False, lab, 3, weights=q), ctx.onsager(True, lab, 3, cross=False)):
         out += [np.array(a, copy=True) for a in r if a is not None]
     return out
 

@@ -35,6 +35,7 @@ WF_BP = ["k_wsplit_accum", "k_winverse"] + TAIL  # (one block of atoms at these 
 WIDEN = ["k_widen_f32"]
 RELAYOUT = ["k_relayout"]
 MOMENT = ["k_cond_moment", "k_sum_partials"]
+SPECIES = ["k_species_moment", "k_sum_partials"]
 
 
 def s1_2s2(prepare, fft_names, by_particle):
@@ -48,10 +49,12 @@ ROWS = []
 
 
 def row(entry, T, form, expect, via="host", atoms=(9, 70), dtype=np.float64, **opts):
-    """form: by-particle array or not; for the conductivity (self term, collective term)."""
+    """form: by-particle array or not; for the conductivity (self term, collective term); for Onsager ("S", n_species,
+    cross term)."""
     for A in atoms:
         tag = "-".join([entry, via, f"T{T}", f"A{A}",
-                        ("bp" if form else "lags") if not isinstance(form, tuple) else "self%d_coll%d" % form] +
+                        ("bp" if form else "lags") if not isinstance(form, tuple)
+                        else "S%d_cross%d" % form[1:] if form[0] == "S" else "self%d_coll%d" % form] +
                        [f"{k}{v}" for k, v in sorted(opts.items())] + (["f32"] if dtype == np.float32 else []))
         ROWS.append(pytest.param(entry, via, T, A, form, dtype, opts, list(expect), id=tag))
 
@@ -136,6 +139,16 @@ for fft, T, msd in ((0, 64, SHORT), (0, 700, VEC), (1, 64, SHORT), (1, 700, s1_2
     row(f"cond{fft}", T, (0, 1), MOMENT + RELAYOUT + msd)
     row(f"cond{fft}", T, (0, 0), MOMENT)
 
+# ---- Onsager: every species' moment in one pass, then the cross MSD = the by-particle MSDs of the S^2 pseudo-particles
+# M_i, M_i +- M_j between the combination kernel and the polarisation kernel (n_species 1, 3, 8: one per class of
+# k_species_moment)
+ONS_MSD = {(0, 64): SHORT, (0, 700): VEC_BP, (1, 64): SHORT, (1, 700): s1_2s2("k_msd_prepare", WF_BP, True)}
+for via, pre in (("host", []), ("staged", []), ("dev", RELAYOUT)):
+    for (fft, T), msd in ONS_MSD.items():
+        for S in (1, 3, 8):
+            row(f"ons{fft}", T, ("S", S, 1), pre + SPECIES + ["k_onsager_combos"] + msd + ["k_onsager_finish"], via=via)
+            row(f"ons{fft}", T, ("S", S, 0), pre + SPECIES, via=via)
+
 # ---- the staged entries and the *_dev entries (frame-major device input: relayout first)
 for via, pre in (("staged", []), ("dev", RELAYOUT)):
     row("vacf_fft", 700, False, pre + WF, via=via)
@@ -180,6 +193,8 @@ def run_host(ctx, entry, form, first, x, m, q):
         return ctx.helfand_msd(m, SCALE, by_particle=form)
     if entry in ("msd0", "msd1"):
         return ctx.msd(entry == "msd1", by_particle=form)
+    if entry in ("ons0", "ons1"):
+        return ctx.onsager(entry == "ons1", np.arange(len(q)) % form[1], form[1], weights=q, cross=bool(form[2]))
     return ctx.conductivity(entry == "cond1", q, self_term=bool(form[0]), collective=bool(form[1]))
 
 
@@ -193,7 +208,13 @@ def run_device(ctx, entry, via, form, first, x, m, q):
     ptr = lambda t: t.data_ptr() if t is not None else 0
     d_first, d_x, d_m, d_q = dev(first), dev(x), dev(m), dev(q)
     where = (d_first.data_ptr(), T, A, D, A * D) if via == "dev" else ()
-    if entry in ("cond0", "cond1"):
+    if entry in ("ons0", "ons1"):
+        S = form[1]
+        d_lab = torch.from_numpy((np.arange(A) % S).astype(np.int32)).cuda()
+        out = [zeros(S, T, D), zeros(T, S, S) if form[2] else None]
+        fn = ctx.onsager_dev if via == "dev" else ctx.onsager_staged
+        fn(*where, entry == "ons1", S, d_lab.data_ptr(), ptr(out[0]), d_q.data_ptr(), ptr(out[1]))
+    elif entry in ("cond0", "cond1"):
         out = [zeros(T, D), zeros(T) if form[1] else None, zeros(T) if form[0] else None]
         fn = ctx.conductivity_dev if via == "dev" else ctx.conductivity_staged
         fn(*where, entry == "cond1", d_q.data_ptr(), ptr(out[0]), ptr(out[1]), ptr(out[2]))

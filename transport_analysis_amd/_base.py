@@ -249,6 +249,16 @@ class StagedAnalysis(AnalysisBase):
     _by_particle_key = None     # results.<key>: the (n_frames, n_particles) array or None
     _no_data_message = None     # NoDataError text of a frame _has_data rejects
     _unwrap = False             # unwrap the staged positions (NoJump) before _evaluate
+    _record_volumes = False     # record every frame's ts.volume; _evaluate finds their mean in self._vol_avg
+
+    # MDAnalysis >= 2.8 parallel-analysis protocol: frames are staged into ONE device slab per
+    # analysis object and every lag couples all frames, so a frame-split backend cannot apply;
+    # the data-parallel axis of this path is atoms (distributed=True), not frames.
+    _analysis_algorithm_is_parallelizable = False
+
+    @classmethod
+    def get_supported_backends(cls):
+        return ("serial",)
 
     def __init__(self, group, **kwargs):
         self._want_by_particle = bool(kwargs.pop("by_particle", True))
@@ -315,6 +325,7 @@ class StagedAnalysis(AnalysisBase):
         # helper thread while the frames are staged
         # unwrap: the box of every analysed frame, (n_frames, 6) = ts.dimensions
         self._boxes = np.zeros((self.n_frames, 6)) if self._unwrap else None
+        self._volumes = np.zeros(self.n_frames) if self._record_volumes else None
         self._bp_home = None
         if self._want_by_particle and self._n_local and not self._rccl:
             self._bp_home = self._ctx.result_home((self.n_frames, self._n_local))
@@ -327,6 +338,8 @@ class StagedAnalysis(AnalysisBase):
         i = self._frame_index
         if self._boxes is not None:
             self._boxes[i] = self._unwrap_box(ts)
+        if self._volumes is not None:
+            self._volumes[i] = ts.volume
         if self._n_local:
             for slab, attr in self._fills:
                 if not stage_frame_native(self._ctx, slab, i, ts, attr, self._dim, self._rows):
@@ -363,6 +376,8 @@ class StagedAnalysis(AnalysisBase):
                               stacklevel=3)
             if self._n_local or self._devices is not None:
                 self._ctx.unwrap(self._stage_arrays.index("positions"), self._boxes, self._dim)
+        if self._volumes is not None:
+            self._vol_avg = np.average(self._volumes)
         self._evaluate()
 
     def _run_kernels(self, host, launch):
@@ -387,3 +402,72 @@ class StagedAnalysis(AnalysisBase):
                 ts = allreduce_mean_over_atoms(ts, self._n_local, self.n_particles, self._device)
         setattr(self.results, self._by_particle_key, bp)
         self.results.timeseries = ts
+
+
+class CollectiveAnalysis(StagedAnalysis):
+    """What the collective Einstein-Helfand analyses (``ConductivityHelfand``, ``OnsagerHelfand``) share.  Their quantity is
+    the mean squared displacement of sums over all atoms -- the moments -- and not a mean of per-particle series: there
+    is no by-particle result, and under ``distributed=True`` every rank forms the moments of its block of atoms, the
+    moments are summed over ranks, and ONE correlation of the sums follows (the MSD of a sum is not the sum of the MSDs).
+
+    A subclass gives the wording of the two refusals, pops nothing of its own, and implements ``_moments(fft, lo, hi,
+    correlate)`` (one library call on the atoms [lo, hi) -> (tuple of the arrays that add up over atoms, None for one
+    not asked for; their correlation or None)), ``_no_moments()`` (that tuple as zeros: a rank without atoms),
+    ``_correlate(fft, sums)`` (the correlation of summed moments) and ``_store(sums, correlation)`` (results and fit)."""
+
+    _stage_arrays = ("positions",)
+    _record_volumes = True
+    _updating_message = None     # TypeError text for an UpdatingAtomGroup
+    _by_particle_message = None  # TypeError text for by_particle=True
+
+    def __init__(self, atomgroup, temp_avg, dim_type, linear_fit_window, fft, unwrap, kwargs):
+        if isinstance(atomgroup, UpdatingAtomGroup):
+            raise TypeError(self._updating_message)
+        if kwargs.pop("by_particle", False):
+            raise TypeError(self._by_particle_message)
+        super().__init__(atomgroup, by_particle=False, **kwargs)
+        self._unwrap = self.unwrap = bool(unwrap)
+        self.temp_avg = temp_avg
+        self.dim_type = dim_type.lower()
+        self._dim, self.dim_fac = parse_dim_type(self.dim_type)
+        self.linear_fit_window = linear_fit_window
+        self.fft = fft
+        self.atomgroup = self._group = atomgroup
+        self.n_particles = len(self.atomgroup)
+
+    def _per_atom(self, values, name, unit, dtype=np.float64):
+        """One value per atom of the group as a flat array, or the ValueError that says how many there are."""
+        a = np.asarray(values, dtype=dtype).ravel()
+        if a.size != self.n_particles:
+            raise ValueError(f"{name}: {a.size} {unit} for {self.n_particles} atoms")
+        return a
+
+    def _set_options(self, dtype):
+        self._ctx.set_option("stage_device_f32", 0)
+
+    @staticmethod
+    def _has_data(ts):
+        return ts.has_positions and ts.volume != 0
+
+    def _evaluate(self):
+        fft = bool(self.fft)
+        if self._distributed:
+            from .dist import allreduce_sum
+
+            # (more ranks than atoms: a rank without atoms contributes zeros)
+            sums = self._moments(fft, self._lo, self._hi, False)[0] if self._n_local else self._no_moments()
+            sums = tuple(None if a is None else allreduce_sum(a, self._device) for a in sums)
+            correlation = self._correlate(fft, sums)
+        else:
+            sums, correlation = self._moments(fft, 0, self.n_particles, True)
+        self._store(sums, correlation)
+
+    def lag_times(self):
+        """Lag times k * dt (ps) of the timeseries, dt the spacing of the analysed frames' times."""
+        dt = float(self.times[1] - self.times[0]) if self.n_frames > 1 else 0.0
+        return np.arange(self.n_frames) * dt
+
+    def _slope(self, series):
+        """Slope of a lag-indexed series against lag time over the lag indices [lo, hi) of ``linear_fit_window``."""
+        lo, hi = self.linear_fit_window[0], self.linear_fit_window[1]
+        return np.polyfit(self.lag_times()[lo:hi], series[lo:hi], 1)[0]

@@ -362,10 +362,22 @@ class _Staged:
         self._call("stage_free")
 
     # -- host-facing compute -------------------------------------------
+    def _staged_shape(self):
+        return self.shape or (1, 1, 1)  # unstaged: the library reports it
+
+    def _per_atom(self, values, dtype, name, unit):
+        """`values` as a flat contiguous array of `dtype` with one entry per staged atom (None stays None)"""
+        if values is None:
+            return None
+        a = np.ascontiguousarray(values, dtype=dtype).ravel()
+        if a.size != self._staged_shape()[1]:
+            raise ValueError(f"{name}: {a.size} {unit} for {self._staged_shape()[1]} atoms")
+        return a
+
     def _host(self, name, by_particle, *extra, out=None):
         """by_particle: False, True (a pinned (n_frames, n_atoms) array is allocated here) or
         `out` = the caller's (n_frames, n_atoms) float64 C-contiguous array (pinned_empty)."""
-        T, A, _ = self.shape or (1, 1, 1)  # unstaged: the library reports it
+        T, A, _ = self._staged_shape()
         ts = np.empty(T, dtype=np.float64)
         bp = None
         if out is not None:
@@ -394,10 +406,8 @@ class _Staged:
     def conductivity(self, fft, charges, self_term=False, collective=True):
         """Einstein-Helfand conductivity of slab 0 (the positions) with one charge per staged atom:
         (moment (n_frames, dim), Phi (n_frames,) or None, self lag sum sum_n q_n^2 MSD_n (n_frames,) or None)."""
-        T, A, D = self.shape or (1, 1, 1)  # unstaged: the library reports it
-        q = np.ascontiguousarray(charges, dtype=np.float64).ravel()
-        if q.size != A:
-            raise ValueError(f"charges: {q.size} values for {A} atoms")
+        T, _, D = self._staged_shape()
+        q = self._per_atom(charges, np.float64, "charges", "values")
         moment = np.empty((T, D), dtype=np.float64)
         phi = np.empty(T, dtype=np.float64) if collective else None
         self_ls = np.empty(T, dtype=np.float64) if self_term else None
@@ -408,16 +418,10 @@ class _Staged:
         """Species moments and their cross MSD of slab 0 (the positions), ta_onsager: `species` one integer label in
         0 ... n_species - 1 per staged atom, in any order (n_species: default the largest label + 1), `weights` one weight
         per atom or None (all 1): (moments (n_species, n_frames, dim), C (n_frames, n_species, n_species) or None)."""
-        T, A, D = self.shape or (1, 1, 1)  # unstaged: the library reports it
-        lab = np.ascontiguousarray(species, dtype=np.int32).ravel()
-        if lab.size != A:
-            raise ValueError(f"species: {lab.size} labels for {A} atoms")
+        T, _, D = self._staged_shape()
+        lab = self._per_atom(species, np.int32, "species", "labels")
         S = int(n_species) if n_species is not None else int(lab.max()) + 1
-        w = None
-        if weights is not None:
-            w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
-            if w.size != A:
-                raise ValueError(f"weights: {w.size} values for {A} atoms")
+        w = self._per_atom(weights, np.float64, "weights", "values")
         n = max(S, 1)
         moments = np.empty((n, T, D), dtype=np.float64)
         c = np.empty((T, n, n), dtype=np.float64) if cross else None

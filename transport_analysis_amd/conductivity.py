@@ -15,14 +15,14 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._base import StagedAnalysis, UpdatingAtomGroup, parse_dim_type
+from ._base import CollectiveAnalysis
 
 #: CODATA 2018 (exact SI values): elementary charge (C) and Boltzmann constant (J/K)
 ELEMENTARY_CHARGE = 1.602176634e-19
 BOLTZMANN_J_PER_K = 1.380649e-23
 
 
-class ConductivityHelfand(StagedAnalysis):
+class ConductivityHelfand(CollectiveAnalysis):
     r"""Ionic conductivity by the Einstein-Helfand relation.
 
     .. math:: \Phi(k) = \frac{1}{T - k} \sum_{i < T - k} \sum_d (M_{i+k, d} - M_{i, d})^2, \qquad
@@ -69,90 +69,43 @@ class ConductivityHelfand(StagedAnalysis):
     results.conductivity, results.conductivity_self : S/m (only with ``linear_fit_window``).
     """
 
-    _stage_arrays = ("positions",)
     _no_data_message = ("Helfand conductivity computation requires "
                         "positions and box volume in the trajectory")
+    _updating_message = "UpdatingAtomGroups are not valid for conductivity computation"
+    _by_particle_message = ("ConductivityHelfand has no per-particle result: conductivity is collective "
+                            "(by_particle=True is not supported)")
 
     def __init__(self, atomgroup, temp_avg=300.0, dim_type="xyz", linear_fit_window=None, fft=True, *,
                  charges=None, nernst_einstein=False, unwrap=False, **kwargs):
-        if isinstance(atomgroup, UpdatingAtomGroup):
-            raise TypeError("UpdatingAtomGroups are not valid for conductivity computation")
-        if kwargs.pop("by_particle", False):
-            raise TypeError("ConductivityHelfand has no per-particle result: conductivity is collective "
-                            "(by_particle=True is not supported)")
-        super().__init__(atomgroup, by_particle=False, **kwargs)
-        self._unwrap = self.unwrap = bool(unwrap)
-
-        self.temp_avg = temp_avg
-        self.dim_type = dim_type.lower()
-        self._dim, self.dim_fac = parse_dim_type(self.dim_type)
-        self.linear_fit_window = linear_fit_window
-        self.fft = fft
+        super().__init__(atomgroup, temp_avg, dim_type, linear_fit_window, fft, unwrap, kwargs)
         self.nernst_einstein = bool(nernst_einstein)
-
-        self.atomgroup = self._group = atomgroup
-        self.n_particles = len(self.atomgroup)
-        q = atomgroup.charges if charges is None else charges
-        self.charges = np.asarray(q, dtype=np.float64).ravel()
-        if self.charges.size != self.n_particles:
-            raise ValueError(f"charges: {self.charges.size} values for {self.n_particles} atoms")
-
-    # see EinsteinMSD: atoms, not frames, are this path's parallel axis
-    _analysis_algorithm_is_parallelizable = False
-
-    @classmethod
-    def get_supported_backends(cls):
-        return ("serial",)
-
-    def _set_options(self, dtype):
-        self._ctx.set_option("stage_device_f32", 0)
+        self.charges = self._per_atom(atomgroup.charges if charges is None else charges, "charges", "values")
 
     def _prepare(self):
         super()._prepare()
-        self._volumes = np.zeros(self.n_frames)
         for key in ("conductivity", "conductivity_self"):  # a fit of an earlier run
             self.results.pop(key, None)
         self.results.moment = self.results.timeseries = self.results.timeseries_self = None
 
-    @staticmethod
-    def _has_data(ts):
-        return ts.has_positions and ts.volume != 0
+    def _moments(self, fft, lo, hi, correlate):
+        moment, phi, self_ls = self._ctx.conductivity(fft, self.charges[lo:hi], self_term=self.nernst_einstein,
+                                                      collective=correlate)
+        return (moment, self_ls), phi
 
-    def _single_frame(self):
-        super()._single_frame()
-        self._volumes[self._frame_index] = self._ts.volume
+    def _no_moments(self):
+        return np.zeros((self.n_frames, self.dim_fac)), (np.zeros(self.n_frames) if self.nernst_einstein else None)
 
-    def _evaluate(self):
-        fft, want_self = bool(self.fft), self.nernst_einstein
-        if self._distributed:
-            from .dist import allreduce_sum
+    def _correlate(self, fft, sums):
+        return self._ctx.moment_msd(sums[0], fft)
 
-            if self._n_local:
-                moment, _, self_ls = self._ctx.conductivity(fft, self.charges[self._lo:self._hi], self_term=want_self,
-                                                            collective=False)
-            else:  # more ranks than atoms: this rank contributes nothing
-                moment, self_ls = np.zeros((self.n_frames, self.dim_fac)), np.zeros(self.n_frames)
-            moment = allreduce_sum(moment, self._device)
-            self_ls = allreduce_sum(self_ls, self._device) if want_self else None
-            phi = self._ctx.moment_msd(moment, fft)
-        else:
-            moment, phi, self_ls = self._ctx.conductivity(fft, self.charges, self_term=want_self)
-        self.results.moment = moment
+    def _store(self, sums, phi):
+        self.results.moment, self.results.timeseries_self = sums
         self.results.timeseries = phi
-        self.results.timeseries_self = self_ls
-        self._vol_avg = np.average(self._volumes)
         if self.linear_fit_window is not None:
             self.results.conductivity = self._sigma(phi)
-            if self_ls is not None:
-                self.results.conductivity_self = self._sigma(self_ls)
-
-    def lag_times(self):
-        """Lag times k * dt (ps) of the timeseries, dt the spacing of the analysed frames' times."""
-        dt = float(self.times[1] - self.times[0]) if self.n_frames > 1 else 0.0
-        return np.arange(self.n_frames) * dt
+            if self.nernst_einstein:
+                self.results.conductivity_self = self._sigma(sums[1])
 
     def _sigma(self, series):
-        lo, hi = self.linear_fit_window[0], self.linear_fit_window[1]
-        slope = np.polyfit(self.lag_times()[lo:hi], series[lo:hi], 1)[0]
-        return (ELEMENTARY_CHARGE ** 2 * 1e22 / BOLTZMANN_J_PER_K * slope
+        return (ELEMENTARY_CHARGE ** 2 * 1e22 / BOLTZMANN_J_PER_K * self._slope(series)
                 / (2 * self.dim_fac * self._vol_avg * self.temp_avg))

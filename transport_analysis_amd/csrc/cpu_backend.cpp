@@ -394,48 +394,54 @@ int msd(const State& s, bool fft, double* ts, double* bp) {
                              : direct_t<double>(s, false, nullptr, 1.0, ts, bp, true);
 }
 
-int conductivity(const State& s, bool fft, const double* q, double* moment, double* collective, double* self_lagsum) {
+// moments (S, T, D) = sum_{n: species[n] = sp} w_n (x - x[0]) of slab 0, frame-parallel (species NULL: all atoms are species 0;
+// w NULL: all 1), and with wslab the weighted shifted slab w_n (x - x[0]) in the slab's layout
+static void moments_of(const State& s, int S, const int32_t* species, const double* w, double* moments, double* wslab) {
     const int64_t T = s.T, A = s.A;
     const int D = s.D;
-    std::vector<double> w;
-    if (self_lagsum) {
-        try {
-            w.assign((size_t)T * A * D, 0.0);
-        } catch (const std::bad_alloc&) {
-            return TA_E_NOMEM;
-        }
-    }
     const void* slab = s.slabs[0];
     const bool f32 = s.dtype == TA_F32;
 #pragma omp parallel for num_threads(s.threads) schedule(static)
     for (int64_t t = 0; t < T; ++t) {
-        double acc[3] = {0.0, 0.0, 0.0};
-        for (int64_t n = 0; n < A; ++n)
+        double acc[8][3] = {};
+        for (int64_t n = 0; n < A; ++n) {
+            const double wn = w ? w[n] : 1.0;
+            double* a = acc[species ? species[n] : 0];
             for (int d = 0; d < D; ++d) {
                 const size_t i0 = (size_t)n * D + d, i = (size_t)t * A * D + i0;
                 const double x = f32 ? elem<float>(slab, i) : elem<double>(slab, i);
                 const double x0 = f32 ? elem<float>(slab, i0) : elem<double>(slab, i0);
-                const double v = q[n] * (x - x0);
-                acc[d] += v;
-                if (self_lagsum) w[i] = v;
+                const double v = wn * (x - x0);
+                a[d] += v;
+                if (wslab) wslab[i] = v;
             }
-        for (int d = 0; d < D; ++d) moment[(size_t)t * D + d] = acc[d];
+        }
+        for (int sp = 0; sp < S; ++sp)
+            for (int d = 0; d < D; ++d) moments[((size_t)sp * T + t) * D + d] = acc[sp][d];
     }
-    int rc = TA_OK;
+}
+
+// a float64 (T, A, D) array as a slab of its own: what msd() reads for the weighted slab, the moment and the pseudo-particles
+static State f64_slab(int threads, int64_t T, int64_t A, int D, double* data) {
+    State v;
+    v.T = T, v.A = A, v.D = D, v.dtype = TA_F64, v.threads = threads;
+    v.slabs = {data};
+    return v;
+}
+
+int conductivity(const State& s, bool fft, const double* q, double* moment, double* collective, double* self_lagsum) {
+    std::vector<double> w;
     if (self_lagsum) {
-        State ws = s;
-        ws.dtype = TA_F64;
-        ws.slabs = {w.data()};
-        if ((rc = msd(ws, fft, self_lagsum, nullptr))) return rc;
+        try {
+            w.assign((size_t)s.T * s.A * s.D, 0.0);
+        } catch (const std::bad_alloc&) {
+            return TA_E_NOMEM;
+        }
     }
-    if (collective) {
-        State ms = s;
-        ms.A = 1;
-        ms.dtype = TA_F64;
-        ms.slabs = {moment};
-        rc = msd(ms, fft, collective, nullptr);
-    }
-    return rc;
+    moments_of(s, 1, nullptr, q, moment, self_lagsum ? w.data() : nullptr);
+    if (self_lagsum)
+        if (int rc = msd(f64_slab(s.threads, s.T, s.A, s.D, w.data()), fft, self_lagsum, nullptr)) return rc;
+    return collective ? msd(f64_slab(s.threads, s.T, 1, s.D, moment), fft, collective, nullptr) : TA_OK;
 }
 
 int onsager_cross(int threads, bool fft, const double* moments, int S, int64_t T, int D, double* cross) {
@@ -458,11 +464,8 @@ int onsager_cross(int threads, bool fft, const double* moments, int S, int64_t T
                     const double mi = moments[((size_t)i * T + t) * D + d], mj = moments[((size_t)j * T + t) * D + d];
                     pm[((size_t)t * P + i * S + j) * D + d] = i == j ? mi : i < j ? mi + mj : mi - mj;
                 }
-    State ps;
-    ps.T = T, ps.A = P, ps.D = D, ps.dtype = TA_F64, ps.threads = threads;
-    ps.slabs = {pm.data()};
     if (T >= 2)
-        if (int rc = msd(ps, fft, ts.data(), bp.data())) return rc;
+        if (int rc = msd(f64_slab(threads, T, P, D, pm.data()), fft, ts.data(), bp.data())) return rc;
     for (int64_t k = 0; k < T; ++k)
         for (int i = 0; i < S; ++i)
             for (int j = 0; j < S; ++j) {
@@ -476,27 +479,8 @@ int onsager_cross(int threads, bool fft, const double* moments, int S, int64_t T
 }
 
 int onsager(const State& s, bool fft, int S, const int32_t* species, const double* w, double* moments, double* cross) {
-    const int64_t T = s.T, A = s.A;
-    const int D = s.D;
-    const void* slab = s.slabs[0];
-    const bool f32 = s.dtype == TA_F32;
-#pragma omp parallel for num_threads(s.threads) schedule(static)
-    for (int64_t t = 0; t < T; ++t) {
-        double acc[8][3] = {};
-        for (int64_t n = 0; n < A; ++n) {
-            const double wn = w ? w[n] : 1.0;
-            double* a = acc[species[n]];
-            for (int d = 0; d < D; ++d) {
-                const size_t i0 = (size_t)n * D + d, i = (size_t)t * A * D + i0;
-                const double x = f32 ? elem<float>(slab, i) : elem<double>(slab, i);
-                const double x0 = f32 ? elem<float>(slab, i0) : elem<double>(slab, i0);
-                a[d] += wn * (x - x0);
-            }
-        }
-        for (int sp = 0; sp < S; ++sp)
-            for (int d = 0; d < D; ++d) moments[((size_t)sp * T + t) * D + d] = acc[sp][d];
-    }
-    return cross ? onsager_cross(s.threads, fft, moments, S, T, D, cross) : TA_OK;
+    moments_of(s, S, species, w, moments, nullptr);
+    return cross ? onsager_cross(s.threads, fft, moments, S, s.T, s.D, cross) : TA_OK;
 }
 
 template <class E>

@@ -84,14 +84,6 @@ class EinsteinMSD(StagedAnalysis):
         self.msd_type = self.msd_type.lower()
         self._dim, self.dim_fac = parse_dim_type(self.msd_type, "msd_type")
 
-    # frames are staged into one device slab and every lag couples all frames: atoms, not frames, are the
-    # parallel axis of this path (distributed=True)
-    _analysis_algorithm_is_parallelizable = False
-
-    @classmethod
-    def get_supported_backends(cls):
-        return ("serial",)
-
     # ------------------------------------------------------------ hooks
     def _set_options(self, dtype):
         self._ctx.set_option("stage_device_f32", 0)

@@ -14,14 +14,14 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._base import StagedAnalysis, UpdatingAtomGroup, parse_dim_type
+from ._base import CollectiveAnalysis
 from .conductivity import BOLTZMANN_J_PER_K, ELEMENTARY_CHARGE
 
 #: ta_hip.h: TA_ONSAGER_MAX_SPECIES
 MAX_SPECIES = 8
 
 
-class OnsagerHelfand(StagedAnalysis):
+class OnsagerHelfand(CollectiveAnalysis):
     r"""Onsager transport coefficients of the species of a system by the Einstein-Helfand relation.
 
     .. math:: C_{ij}(k) = \frac{1}{T - k} \sum_{t < T - k} \sum_d (M_{i; t+k, d} - M_{i; t, d}) (M_{j; t+k, d} - M_{j; t, d}),
@@ -61,96 +61,49 @@ class OnsagerHelfand(StagedAnalysis):
     number), a centre-of-mass reference frame, the Green-Kubo (velocity) form.
     """
 
-    _stage_arrays = ("positions",)
     _no_data_message = ("Onsager coefficient computation requires "
                         "positions and box volume in the trajectory")
+    _updating_message = "UpdatingAtomGroups are not valid for Onsager coefficient computation"
+    _by_particle_message = ("OnsagerHelfand has no per-particle result: the Onsager coefficients are collective "
+                            "(by_particle=True is not supported)")
 
     def __init__(self, atomgroup, species, temp_avg=300.0, dim_type="xyz", linear_fit_window=None, fft=True, *,
                  weights=None, unwrap=False, **kwargs):
-        if isinstance(atomgroup, UpdatingAtomGroup):
-            raise TypeError("UpdatingAtomGroups are not valid for Onsager coefficient computation")
-        if kwargs.pop("by_particle", False):
-            raise TypeError("OnsagerHelfand has no per-particle result: the Onsager coefficients are collective "
-                            "(by_particle=True is not supported)")
-        super().__init__(atomgroup, by_particle=False, **kwargs)
-        self._unwrap = self.unwrap = bool(unwrap)
-
-        self.temp_avg = temp_avg
-        self.dim_type = dim_type.lower()
-        self._dim, self.dim_fac = parse_dim_type(self.dim_type)
-        self.linear_fit_window = linear_fit_window
-        self.fft = fft
-
-        self.atomgroup = self._group = atomgroup
-        self.n_particles = len(self.atomgroup)
+        super().__init__(atomgroup, temp_avg, dim_type, linear_fit_window, fft, unwrap, kwargs)
         if isinstance(species, str):
             species = getattr(atomgroup, species)
-        labels = np.asarray(species).ravel()
-        if labels.size != self.n_particles:
-            raise ValueError(f"species: {labels.size} labels for {self.n_particles} atoms")
+        labels = self._per_atom(species, "species", "labels", dtype=None)
         self.species, index = np.unique(labels, return_inverse=True)
         if self.species.size > MAX_SPECIES:
             raise ValueError(f"species: {self.species.size} distinct labels, at most {MAX_SPECIES} are supported")
         self.species_index = np.ascontiguousarray(index, dtype=np.int32).ravel()
         self.n_species = max(int(self.species.size), 1)
-        self.weights = None
-        if weights is not None:
-            self.weights = np.asarray(weights, dtype=np.float64).ravel()
-            if self.weights.size != self.n_particles:
-                raise ValueError(f"weights: {self.weights.size} values for {self.n_particles} atoms")
-
-    # see EinsteinMSD: atoms, not frames, are this path's parallel axis
-    _analysis_algorithm_is_parallelizable = False
-
-    @classmethod
-    def get_supported_backends(cls):
-        return ("serial",)
-
-    def _set_options(self, dtype):
-        self._ctx.set_option("stage_device_f32", 0)
+        self.weights = None if weights is None else self._per_atom(weights, "weights", "values")
 
     def _prepare(self):
         super()._prepare()
-        self._volumes = np.zeros(self.n_frames)
         self.results.pop("onsager", None)  # a fit of an earlier run
         self.results.species = self.species
         self.results.moments = self.results.timeseries = None
 
-    @staticmethod
-    def _has_data(ts):
-        return ts.has_positions and ts.volume != 0
+    def _moments(self, fft, lo, hi, correlate):
+        w = None if self.weights is None else self.weights[lo:hi]
+        moments, cross = self._ctx.onsager(fft, self.species_index[lo:hi], self.n_species, w, cross=correlate)
+        return (moments,), cross
 
-    def _single_frame(self):
-        super()._single_frame()
-        self._volumes[self._frame_index] = self._ts.volume
+    def _no_moments(self):
+        return (np.zeros((self.n_species, self.n_frames, self.dim_fac)),)
 
-    def _evaluate(self):
-        fft, S = bool(self.fft), self.n_species
-        if self._distributed:
-            from .dist import allreduce_sum
+    def _correlate(self, fft, sums):
+        return self._ctx.onsager_cross(sums[0], fft)
 
-            if self._n_local:
-                w = None if self.weights is None else self.weights[self._lo:self._hi]
-                moments, _ = self._ctx.onsager(fft, self.species_index[self._lo:self._hi], S, w, cross=False)
-            else:  # more ranks than atoms: this rank contributes nothing
-                moments = np.zeros((S, self.n_frames, self.dim_fac))
-            moments = allreduce_sum(moments, self._device)
-            cross = self._ctx.onsager_cross(moments, fft)
-        else:
-            moments, cross = self._ctx.onsager(fft, self.species_index, S, self.weights)
-        self.results.moments = moments
+    def _store(self, sums, cross):
+        (self.results.moments,) = sums
         self.results.timeseries = cross
-        self._vol_avg = np.average(self._volumes)
         if self.linear_fit_window is not None:
-            lo, hi = self.linear_fit_window[0], self.linear_fit_window[1]
-            t = self.lag_times()[lo:hi]
-            slopes = np.array([[np.polyfit(t, cross[lo:hi, i, j], 1)[0] for j in range(S)] for i in range(S)])
+            S = self.n_species
+            slopes = np.array([[self._slope(cross[:, i, j]) for j in range(S)] for i in range(S)])
             self.results.onsager = slopes * 1e22 / (2 * self.dim_fac * BOLTZMANN_J_PER_K * self._vol_avg * self.temp_avg)
-
-    def lag_times(self):
-        """Lag times k * dt (ps) of the timeseries, dt the spacing of the analysed frames' times."""
-        dt = float(self.times[1] - self.times[0]) if self.n_frames > 1 else 0.0
-        return np.arange(self.n_frames) * dt
 
     def _charge_weighted(self, z):
         if "onsager" not in self.results:

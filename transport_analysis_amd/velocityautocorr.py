@@ -98,15 +98,6 @@ class VelocityAutocorr(StagedAnalysis):
 
     _parse_dim_type = staticmethod(parse_dim_type)
 
-    # MDAnalysis >= 2.8 parallel-analysis protocol: frames are staged into ONE device slab per
-    # analysis object and every lag couples all frames, so a frame-split backend cannot apply;
-    # the data-parallel axis of this path is atoms (distributed=True), not frames.
-    _analysis_algorithm_is_parallelizable = False
-
-    @classmethod
-    def get_supported_backends(cls):
-        return ("serial",)
-
     # ------------------------------------------------------------ hooks
     # _prepare (:142-153; results.timeseries is not set there) and _single_frame (:178-194) are
     # StagedAnalysis': the velocity columns go into a pinned host slab and on to the device.

@@ -59,6 +59,7 @@ class ViscosityHelfand(StagedAnalysis):
 
     _stage_arrays = ("velocities", "positions")
     _by_particle_key = "visc_by_particle"
+    _record_volumes = True
     _no_data_message = ("Helfand viscosity computation requires "
                         "velocities, positions, and box volume in the trajectory")
 
@@ -85,13 +86,6 @@ class ViscosityHelfand(StagedAnalysis):
 
     _parse_dim_type = staticmethod(parse_dim_type)
 
-    # see VelocityAutocorr: atoms, not frames, are this path's parallel axis
-    _analysis_algorithm_is_parallelizable = False
-
-    @classmethod
-    def get_supported_backends(cls):
-        return ("serial",)
-
     def _set_options(self, dtype):
         self._ctx.set_option("direct_f32", int(self._float32))
         self._ctx.set_option("helfand_fft", int(self._fft))
@@ -102,7 +96,6 @@ class ViscosityHelfand(StagedAnalysis):
     def _prepare(self):
         """Two pinned slabs (velocities, positions) + volumes + masses (:111-142)."""
         super()._prepare()
-        self._volumes = np.zeros(self.n_frames)
         self._masses = np.asarray(self.atomgroup.masses, dtype=np.float64)[self._lo:self._hi]
         if self._n_local == 0:
             self._masses = np.ones(1)
@@ -112,13 +105,7 @@ class ViscosityHelfand(StagedAnalysis):
     def _has_data(ts):
         return ts.has_velocities and ts.has_positions and ts.volume != 0
 
-    def _single_frame(self):
-        """Stage volume, velocities and positions of one frame (:167-199)."""
-        super()._single_frame()
-        self._volumes[self._frame_index] = self._ts.volume
-
     def _evaluate(self):
-        self._vol_avg = np.average(self._volumes)
         # everything is divided by 2 kB <V> T (:229-231)
         scale = 1.0 / (2 * self.boltzmann * self._vol_avg * self.temp_avg)
 
