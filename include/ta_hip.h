@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_unwrap / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_unwrap / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -152,8 +152,8 @@ int ta_stage_synth(ta_ctx *ctx, int slab, uint64_t seed, int64_t col_offset, int
  * and for ta_conductivity* the moment's partial sums (<= 1024 * n_frames * dim * 8 bytes) and, with
  * the self term, the weighted slab (the input's size), and for ta_onsager* the species moments' partial sums
  * (<= 1024 * n_species * n_frames * dim * 8 bytes), the pair-major slab of the n_species^2 pseudo-particles and their
- * by-particle MSDs (n_species^2 * n_frames * (dim + 1) * 8 bytes); the labels, weights and outputs of host-facing calls
- * are kept.                                                                                                            */
+ * by-particle MSDs (n_species^2 * n_frames * (dim + 1) * 8 bytes); ta_current* use the same workspaces for the currents;
+ * the labels, weights and outputs of host-facing calls are kept.                                                                                                            */
 int ta_trim(ta_ctx *ctx);
 
 /* ---- pinned host memory for result arrays ---------------------------------
@@ -237,6 +237,31 @@ int ta_onsager(ta_ctx *ctx, int fft, int n_species, const int32_t *h_species, co
 int ta_onsager_cross(ta_ctx *ctx, int fft, const double *h_moments, int n_species, int64_t n_frames, int dim,
                      double *h_cross);
 
+/* ta_current      : the Green-Kubo twin of ta_onsager (OnsagerGreenKubo, ConductivityGreenKubo) on slab 0 = the VELOCITIES of the
+ *                   dim_type's columns; h_species, h_weights, n_species as for ta_onsager:
+ *                     h_currents[(s * n_frames + t) * dim + d] = J_s[t, d] = sum_{n: species[n] = s} w_n v[t,n,d]
+ *                                                                                  ((n_species, n_frames, dim), required)
+ *                     h_cross[(k * S + i) * S + j] = C[k, i, j] = 1/2 * 1 / (n_frames - k) sum_{t < n_frames - k} sum_d
+ *                                  (J_i[t,d] J_j[t+k,d] + J_j[t,d] J_i[t+k,d])              ((n_frames, S, S), or NULL: skipped)
+ *                   Nothing is subtracted from the velocities and no term depends on frame 0; lag 0 is kept
+ *                   (C[0, i, j] = <J_i . J_j>).  The slab is read ONCE for all species, in the element type it has: a
+ *                   float32 device slab ("stage_device_f32") is read as float32 and summed in float64, never widened
+ *                   first.  The currents' partial sums per group of column pairs are added in a fixed order (no
+ *                   atomics: the same bits from run to run); a species without atoms gives exact zeros in J and in its
+ *                   row and column of C.  C is evaluated by polarisation, 1/4 (ACF(J_i + J_j) - ACF(J_i - J_j)), in ONE
+ *                   autocorrelation call on the n_species^2 pseudo-particles J_i, J_i + J_j, J_i - J_j (the evaluations of
+ *                   ta_vacf_fft with fft = 1, of ta_vacf_direct with fft = 0): symmetric bit for bit, its error relative
+ *                   to max(C_ii(0), C_jj(0)).  Errors as ta_onsager (the currents output takes the moments' place in
+ *                   the messages); n_atoms * dim must be below 2^31.  CPU backend: the same in C++/OpenMP.  Timings: the
+ *                   pass is the main kernel unless an FFT evaluation follows it (ta_kernel_timeline names it
+ *                   k_species_current).
+ * ta_current_cross: C (n_frames, S, S) of caller-provided currents (S, n_frames, dim) alone, e.g. the sum of several shards'
+ *                   currents (currents add up over shards, C does not).  Needs no staged slab and leaves one untouched.   */
+int ta_current(ta_ctx *ctx, int fft, int n_species, const int32_t *h_species, const double *h_weights, double *h_currents,
+               double *h_cross);
+int ta_current_cross(ta_ctx *ctx, int fft, const double *h_currents, int n_species, int64_t n_frames, int dim,
+                     double *h_cross);
+
 /* ---- periodic unwrapping of a staged position slab ---------------------------------------------------------------
  * ta_unwrap: undo periodic wrapping of staging slab `slab` in place (MDAnalysis' NoJump), over the staged frames
  * in order.  h_dimensions: (n_frames, 6) float64 rows [a, b, c, alpha, beta, gamma] (A, degrees; ts.dimensions).
@@ -288,6 +313,11 @@ int ta_conductivity_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int6
 int ta_onsager_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row, int fft,
                    int n_species, const int32_t *d_species, const double *d_weights, double *d_moments, double *d_cross,
                    void *stream);
+/* d_vel: frame-major float64 velocities; d_species, d_weights as for ta_onsager_dev; d_currents (n_species, n_frames, dim)
+ * required; d_cross (n_frames, n_species, n_species) or NULL.  Shards' currents add up; C does not. */
+int ta_current_dev(ta_ctx *ctx, const double *d_vel, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row, int fft,
+                   int n_species, const int32_t *d_species, const double *d_weights, double *d_currents, double *d_cross,
+                   void *stream);
 
 /* ---- compute on the staged (pair-major) slabs, device outputs, asynchronous on `stream` ----
  * Same arithmetic and outputs as the *_dev calls, on the slabs of ta_stage_alloc*: no
@@ -303,6 +333,9 @@ int ta_conductivity_staged(ta_ctx *ctx, int fft, const double *d_charges, double
                            double *d_self_lagsum, void *stream);
 int ta_onsager_staged(ta_ctx *ctx, int fft, int n_species, const int32_t *d_species, const double *d_weights,
                       double *d_moments, double *d_cross, void *stream);
+/* slab 0 holds the velocities, float64 or ("stage_device_f32") float32 elements: read as they are */
+int ta_current_staged(ta_ctx *ctx, int fft, int n_species, const int32_t *d_species, const double *d_weights,
+                      double *d_currents, double *d_cross, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns
@@ -365,6 +398,10 @@ int ta_group_conductivity(ta_group *g, int fft, const double *h_charges, double 
  * summed moments runs on the first member that holds atoms.  h_cross NULL: the moments alone.                          */
 int ta_group_onsager(ta_group *g, int fft, int n_species, const int32_t *h_species, const double *h_weights,
                      double *h_moments, double *h_cross);
+/* ta_group_current: ta_current on every member in the same way: the members' currents are SUMMED on the host in member
+ * order, then ONE cross evaluation of the summed currents runs on the first member that holds atoms.                   */
+int ta_group_current(ta_group *g, int fft, int n_species, const int32_t *h_species, const double *h_weights,
+                     double *h_currents, double *h_cross);
 /* ta_group_unwrap: ta_unwrap on every member's block of slab `slab` (declared with ta_unwrap above) */
 int ta_group_unwrap(ta_group *g, int slab, const double *h_dimensions, const int *axes); /* every member's block */
 

@@ -1,5 +1,6 @@
 """transport_analysis_amd — MI355X-native time-correlation kernels behind the
-transport-analysis API (VelocityAutocorr, ViscosityHelfand), MDAnalysis' EinsteinMSD, ConductivityHelfand and its species-resolved form, OnsagerHelfand."""
+transport-analysis API (VelocityAutocorr, ViscosityHelfand), MDAnalysis' EinsteinMSD, ConductivityHelfand and its species-resolved form, OnsagerHelfand, and their Green-Kubo
+(velocity) twins, ConductivityGreenKubo and OnsagerGreenKubo."""
 __version__ = "0.1.0"
 
 from .velocityautocorr import VelocityAutocorr  # noqa: F401
@@ -7,3 +8,4 @@ from .viscosity import ViscosityHelfand  # noqa: F401
 from .msd import EinsteinMSD  # noqa: F401
 from .conductivity import ConductivityHelfand  # noqa: F401
 from .onsager import OnsagerHelfand  # noqa: F401
+from .greenkubo import ConductivityGreenKubo, OnsagerGreenKubo  # noqa: F401

@@ -405,7 +405,9 @@ class StagedAnalysis(AnalysisBase):
 
 
 class CollectiveAnalysis(StagedAnalysis):
-    """What the collective Einstein-Helfand analyses (``ConductivityHelfand``, ``OnsagerHelfand``) share.  Their quantity is
+    """What the collective analyses share: the Einstein-Helfand ones (``ConductivityHelfand``, ``OnsagerHelfand``) and their
+    Green-Kubo twins (``greenkubo.py``: the sums are currents of the staged velocities, ``_stage_arrays``, ``_has_data``
+    and ``_set_options`` overridden).  Their quantity is
     the mean squared displacement of sums over all atoms -- the moments -- and not a mean of per-particle series: there
     is no by-particle result, and under ``distributed=True`` every rank forms the moments of its block of atoms, the
     moments are summed over ranks, and ONE correlation of the sums follows (the MSD of a sum is not the sum of the MSDs).

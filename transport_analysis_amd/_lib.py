@@ -56,6 +56,9 @@ _API = {
     "ta_onsager": _ONSAGER, "ta_onsager_cross": _int(_vp, _ci, _vp, _ci, _i64, _ci, _vp),
     "ta_onsager_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_onsager_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
+    "ta_current": _ONSAGER, "ta_current_cross": _int(_vp, _ci, _vp, _ci, _i64, _ci, _vp),
+    "ta_current_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
+    "ta_current_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
     "ta_helfand_msd_dev": _int(_vp, _vp, _vp, _vp, _i64, _i64, _ci, _i64, _dbl, _vp, _vp, _i64, _vp),
     "ta_msd_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _vp, _i64, _vp),
@@ -75,7 +78,7 @@ _API = {
     "ta_group_stage_synth": _int(_vp, _ci, ctypes.c_uint64, _i64, _i64),
     "ta_group_vacf_fft": _HOST, "ta_group_vacf_direct": _HOST, "ta_group_helfand_msd": _int(_vp, _vp, _dbl, _vp, _vp),
     "ta_group_msd": _int(_vp, _ci, _vp, _vp), "ta_group_conductivity": _COND, "ta_group_unwrap": _UNWRAP,
-    "ta_group_onsager": _ONSAGER,
+    "ta_group_onsager": _ONSAGER, "ta_group_current": _ONSAGER,
 }
 EXPORTS = tuple(_API)
 
@@ -428,6 +431,19 @@ class _Staged:
         self._call("onsager", int(fft), S, _ptr(lab), _ptr(w), _ptr(moments), _ptr(c))
         return moments, c
 
+    def current(self, fft, species, n_species=None, weights=None, cross=True):
+        """Species currents and their cross-correlation of slab 0 (the velocities), ta_current: arguments as `onsager`:
+        (currents (n_species, n_frames, dim), C (n_frames, n_species, n_species) with lag 0, or None)."""
+        T, _, D = self._staged_shape()
+        lab = self._per_atom(species, np.int32, "species", "labels")
+        S = int(n_species) if n_species is not None else int(lab.max()) + 1
+        w = self._per_atom(weights, np.float64, "weights", "values")
+        n = max(S, 1)
+        currents = np.empty((n, T, D), dtype=np.float64)
+        c = np.empty((T, n, n), dtype=np.float64) if cross else None
+        self._call("current", int(fft), S, _ptr(lab), _ptr(w), _ptr(currents), _ptr(c))
+        return currents, c
+
     def unwrap(self, slab, dimensions, axes):
         """Undo periodic wrapping of staged slab `slab` in place (MDAnalysis' NoJump, ta_unwrap; a group: on every
         member's block of the slab): `dimensions` the (n_frames, 6) boxes [a, b, c, alpha, beta, gamma] of the staged
@@ -522,6 +538,17 @@ class Context(_Staged):
         self._call("onsager_cross", int(fft), _ptr(m), S, T, D, _ptr(c))
         return c
 
+    def current_cross(self, currents, fft):
+        """C (n_frames, S, S) of given (S, n_frames, dim) currents, e.g. the sum of several shards' currents
+        (ta_current_cross): needs no staged slab and leaves the context's slabs as they are."""
+        j = np.ascontiguousarray(currents, dtype=np.float64)
+        if j.ndim != 3:
+            raise ValueError(f"currents: shape {j.shape}, expected (n_species, n_frames, dim)")
+        S, T, D = j.shape
+        c = np.empty((T, S, S), dtype=np.float64)
+        self._call("current_cross", int(fft), _ptr(j), S, T, D, _ptr(c))
+        return c
+
     # -- device-pointer compute (asynchronous) --------------------------
     def vacf_fft_dev(self, d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._call("vacf_fft_dev", d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp or None, ld_bp, stream or None)
@@ -547,6 +574,11 @@ class Context(_Staged):
         self._call("onsager_dev", d_pos, n_frames, n_atoms, dim, ld_row, int(fft), int(n_species), d_species,
                    d_weights or None, d_moments, d_cross or None, stream or None)
 
+    def current_dev(self, d_vel, n_frames, n_atoms, dim, ld_row, fft, n_species, d_species, d_currents, d_weights=0,
+                    d_cross=0, stream=0):
+        self._call("current_dev", d_vel, n_frames, n_atoms, dim, ld_row, int(fft), int(n_species), d_species,
+                   d_weights or None, d_currents, d_cross or None, stream or None)
+
     # -- compute on the staged slabs, device outputs (asynchronous) ------
     def vacf_fft_staged(self, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._call("vacf_fft_staged", d_lagsum, d_bp or None, ld_bp, stream or None)
@@ -565,6 +597,10 @@ class Context(_Staged):
 
     def onsager_staged(self, fft, n_species, d_species, d_moments, d_weights=0, d_cross=0, stream=0):
         self._call("onsager_staged", int(fft), int(n_species), d_species, d_weights or None, d_moments, d_cross or None,
+                   stream or None)
+
+    def current_staged(self, fft, n_species, d_species, d_currents, d_weights=0, d_cross=0, stream=0):
+        self._call("current_staged", int(fft), int(n_species), d_species, d_weights or None, d_currents, d_cross or None,
                    stream or None)
 
     # -- timing ----------------------------------------------------------

@@ -941,6 +941,54 @@ int check_labels(ta_ctx* ctx, const int32_t* h_species, int64_t n, int S) {
     return TA_OK;
 }
 
+// ---- Green-Kubo species currents (current.hip) ----------------------------------------------------------------------
+// C[k, i, j] of the (S, T, D) currents at d_currents into d_cross (T, S, S), by polarisation in ONE autocorrelation call:
+// the S^2 pseudo-particles J_i, J_i + J_j, J_i - J_j as a pair-major slab (k_onsager_combos, in the Onsager workspaces),
+// their (T, S^2) by-particle autocorrelations (the VACF dispatch, with the call's fft), then
+// C_ij = 1/4 (ACF(J_i + J_j) - ACF(J_i - J_j)), lag 0 included.
+int cur_cross(ta_ctx* ctx, bool fft, const double* d_currents, int S, int64_t T, int D, double* d_cross, hipStream_t st) {
+    const int64_t P = (int64_t)S * S, pitch = pm_pitch(T);
+    TA_CHECK(ensure(ctx, ctx->ons_pm, pm_bytes(T, P * D)));
+    TA_CHECK(ensure(ctx, ctx->ons_bp, sizeof(double) * (size_t)(T * P + T) + sizeof(int) * TA_ONSAGER_MAX_SPECIES));
+    double* bp = (double*)ctx->ons_bp.p;
+    double* lagsum = bp + T * P;
+    int* nz = (int*)(lagsum + T);
+    const double* pm = (const double*)ctx->ons_pm.p;
+    TA_HIP_TRY(ctx, hipMemsetAsync(nz, 0, sizeof(int) * TA_ONSAGER_MAX_SPECIES, st));
+    TA_LAUNCH(ctx, "k_onsager_combos", st, launch_onsager_combos(d_currents, S, (long)T, D, (long)pitch, (double*)ctx->ons_pm.p, nz, st));
+    if (fft) TA_CHECK(fft_impl(ctx, pm, pitch, T, P, D, lagsum, bp, P, st));
+    else TA_CHECK(direct_impl(ctx, MODE_VACF, pm, nullptr, nullptr, T, P, D, pitch, 1.0, lagsum, bp, P, st));
+    TA_LAUNCH(ctx, "k_current_finish", st, launch_current_finish(bp, S, (long)T, nz, d_cross, st));
+    return TA_OK;
+}
+
+// One current call on a pair-major velocity slab of either element type, read as it is (the caller has opened the call's
+// bracket, it is closed here): the one pass that forms every species' current, the fixed-order sum of its partials into
+// d_currents (S, T, D), and with d_cross their cross-correlation.  ev[1] / ev[2] bracket the pass, unless an FFT
+// evaluation after it records its own forward kernel there.
+int cur_pm(ta_ctx* ctx, bool fft, const void* pm_any, bool pm_f32, int64_t pitch, int64_t T, int64_t A, int D, int S,
+           const int32_t* d_species, const double* d_w, double* d_currents, double* d_cross, hipStream_t st) {
+    const int64_t n_cols = A * D;
+    if (n_cols >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "Onsager currents: n_atoms * dim must be below 2^31");
+    const int n_parts = species_moment_parts(ctx->n_cu, S, (long)T, (long)n_cols);
+    const size_t n_out = (size_t)S * T * D;
+    TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)n_parts * n_out));
+    TA_LAUNCH_MAIN(ctx, "k_species_current", st,
+                   launch_species_current(pm_any, pm_f32, (long)pitch, (long)T, (long)n_cols, D, S, d_species, d_w,
+                                          (double*)ctx->ons_part.p, n_parts, st));
+    TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)n_out, d_currents, st));
+    if (d_cross) TA_CHECK(cur_cross(ctx, fft, d_currents, S, T, D, d_cross, st));
+    return call_end(ctx, st);
+}
+
+int cur_args(ta_ctx* ctx, int fft, int S, const void* species, const void* currents) {
+    TA_CHECK(check_fft(ctx, fft));
+    TA_CHECK(check_species_count(ctx, S));
+    if (!species) return fail(ctx, TA_E_INVALID, "species labels are NULL");
+    if (!currents) return fail(ctx, TA_E_INVALID, "currents output is NULL");
+    return TA_OK;
+}
+
 // ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
 // This is the seam: a CPU context's staging and host-facing calls end up in the cpu_* functions below, reached by one
 // early branch of their entry point (after the checks both kinds of context share); nothing below makes a HIP call.
@@ -1665,6 +1713,39 @@ int ta_onsager_staged(ta_ctx* ctx, int fft, int n_species, const int32_t* d_spec
     });
 }
 
+// Green-Kubo species currents: slab 0 / d_vel holds the velocities; the staged slab is read in its own element type
+// (never widened); device labels are not checked (k_species_current skips an atom whose label is out of range)
+int ta_current_dev(ta_ctx* ctx, const double* d_vel, int64_t T, int64_t A, int D, int64_t ld_row, int fft, int n_species,
+                   const int32_t* d_species, const double* d_weights, double* d_currents, double* d_cross, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    TA_NO_CPU(ctx);
+    TA_CHECK(check_shape(ctx, T, A, D, ld_row));
+    TA_CHECK(cur_args(ctx, fft, n_species, d_species, d_currents));
+    if (!d_vel) return fail(ctx, TA_E_INVALID, "null device pointer");
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    TA_CHECK(call_begin(ctx, st));
+    const double* pv = nullptr;
+    TA_CHECK(relayout_input(ctx, 0, d_vel, T, A * D, ld_row, st, &pv));
+    return cur_pm(ctx, fft != 0, pv, false, pm_pitch(T), T, A, D, n_species, d_species, d_weights, d_currents, d_cross, st);
+    });
+}
+
+int ta_current_staged(ta_ctx* ctx, int fft, int n_species, const int32_t* d_species, const double* d_weights,
+                      double* d_currents, double* d_cross, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(cur_args(ctx, fft, n_species, d_species, d_currents));
+    TA_CHECK(check_staged(ctx));
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TA_CHECK(order_after_staging(ctx, (hipStream_t)stream));
+    TA_CHECK(call_begin(ctx, (hipStream_t)stream));
+    return cur_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A, ctx->st_D, n_species,
+                  d_species, d_weights, d_currents, d_cross, (hipStream_t)stream);
+    });
+}
+
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guarded(fail, ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
@@ -1928,6 +2009,48 @@ int ons_cross_host(ta_ctx* ctx, int fft, const double* h_moments, int S, int64_t
     return host_finish(ctx, {{h_cross, cross, (size_t)T * S * S}});
 }
 
+// Current share of a host-facing call, queued on ctx->stream and not waited for: the labels and weights (this context's
+// atoms, labels already checked) uploaded, the (S, T, D) currents and with cross the (T, S, S) cross-correlation behind
+// them left on the device in *d_out (the Onsager buffers: one call at a time uses them).
+int cur_launch(ta_ctx* ctx, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out) {
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(check_staged(ctx));
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t T = ctx->st_T, A = ctx->st_A;
+    const int D = ctx->st_D;
+    TA_CHECK(ensure(ctx, ctx->ons_lab, sizeof(int32_t) * A));
+    if (h_w) TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * A));
+    TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)T * S * (D + S)));
+    double* out = (double*)ctx->ons_out.p;
+    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_lab.p, h_species, sizeof(int32_t) * A, hipMemcpyHostToDevice, ctx->stream));
+    if (h_w) TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_w.p, h_w, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
+    TA_CHECK(order_after_staging(ctx, ctx->stream));
+    TA_CHECK(call_begin(ctx, ctx->stream));
+    TA_CHECK(cur_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, T, A, D, S, (const int32_t*)ctx->ons_lab.p,
+                    h_w ? (const double*)ctx->ons_w.p : nullptr, out, cross ? out + (size_t)S * T * D : nullptr, ctx->stream));
+    *d_out = out;
+    return TA_OK;
+}
+
+// The cross-correlation of host (S, T, D) currents on this context's device, blocking, as a compute call of its own
+// (ta_current_cross; the group's ONE evaluation after its members' sums).  Needs no staged slab.
+int cur_cross_host(ta_ctx* ctx, int fft, const double* h_currents, int S, int64_t T, int D, double* h_cross) {
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TA_CHECK(ctx->commits.flush());
+    TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)T * S * (D + S)));
+    double* out = (double*)ctx->ons_out.p;
+    double* cross = out + (size_t)S * T * D;
+    hipStream_t st = ctx->stream;
+    TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_currents, sizeof(double) * (size_t)S * T * D, hipMemcpyHostToDevice, st));
+    TA_CHECK(call_begin(ctx, st));
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));  // no dominant kernel of its own, unless the correlator records one
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
+    TA_CHECK(cur_cross(ctx, fft != 0, out, S, T, D, cross, st));
+    TA_CHECK(call_end(ctx, st));
+    return host_finish(ctx, {{h_cross, cross, (size_t)T * S * S}});
+}
+
 // One context's unwrap of staged slab `slab` (ta_unwrap, ta_group_unwrap), queued on ctx->stream behind the queued commits
 // and bracketed by the timing events: the box table's copy (box.tab must stay valid until host_wait), then the kernel
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes) {
@@ -2057,6 +2180,42 @@ int ta_onsager_cross(ta_ctx* ctx, int fft, const double* h_moments, int n_specie
         return TA_OK;
     }
     return ta::ons_cross_host(ctx, fft, h_moments, n_species, n_frames, dim, h_cross);
+    });
+}
+
+int ta_current(ta_ctx* ctx, int fft, int n_species, const int32_t* h_species, const double* h_weights, double* h_currents,
+               double* h_cross) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(cur_args(ctx, fft, n_species, h_species, h_currents));
+    TA_CHECK(check_staged(ctx));
+    TA_CHECK(check_labels(ctx, h_species, ctx->st_A, n_species));
+    if (ctx->is_cpu) {
+        if (int rc = ta::cpu::current(cpu_state(ctx), fft != 0, n_species, h_species, h_weights, h_currents, h_cross))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    double* d_out = nullptr;
+    TA_CHECK(ta::cur_launch(ctx, fft, n_species, h_species, h_weights, h_cross != nullptr, &d_out));
+    const size_t T = (size_t)ctx->st_T, D = (size_t)ctx->st_D, S = (size_t)n_species;
+    return host_finish(ctx, {{h_currents, d_out, S * T * D}, {h_cross, d_out + S * T * D, T * S * S}});
+    });
+}
+
+int ta_current_cross(ta_ctx* ctx, int fft, const double* h_currents, int n_species, int64_t n_frames, int dim, double* h_cross) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(check_fft(ctx, fft));
+    TA_CHECK(check_species_count(ctx, n_species));
+    if (!h_currents || !h_cross) return fail(ctx, TA_E_INVALID, "currents or cross output is NULL");
+    if (n_frames < 1 || dim < 1 || dim > 3 || n_frames > (int64_t)1 << 30)
+        return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30, 1 <= dim <= 3");
+    if (ctx->is_cpu) {
+        if (int rc = ta::cpu::current_cross(ctx->cpu_threads, fft != 0, h_currents, n_species, n_frames, dim, h_cross))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    return ta::cur_cross_host(ctx, fft, h_currents, n_species, n_frames, dim, h_cross);
     });
 }
 

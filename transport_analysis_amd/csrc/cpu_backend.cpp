@@ -395,8 +395,10 @@ int msd(const State& s, bool fft, double* ts, double* bp) {
 }
 
 // moments (S, T, D) = sum_{n: species[n] = sp} w_n (x - x[0]) of slab 0, frame-parallel (species NULL: all atoms are species 0;
-// w NULL: all 1), and with wslab the weighted shifted slab w_n (x - x[0]) in the slab's layout
-static void moments_of(const State& s, int S, const int32_t* species, const double* w, double* moments, double* wslab) {
+// w NULL: all 1), and with wslab the weighted shifted slab w_n (x - x[0]) in the slab's layout.  shift == false: the
+// currents sum w_n x, nothing subtracted (x - 0.0 is x: one loop, and the same bits as before for the moments)
+static void moments_of(const State& s, int S, const int32_t* species, const double* w, double* moments, double* wslab,
+                       bool shift = true) {
     const int64_t T = s.T, A = s.A;
     const int D = s.D;
     const void* slab = s.slabs[0];
@@ -410,7 +412,7 @@ static void moments_of(const State& s, int S, const int32_t* species, const doub
             for (int d = 0; d < D; ++d) {
                 const size_t i0 = (size_t)n * D + d, i = (size_t)t * A * D + i0;
                 const double x = f32 ? elem<float>(slab, i) : elem<double>(slab, i);
-                const double x0 = f32 ? elem<float>(slab, i0) : elem<double>(slab, i0);
+                const double x0 = !shift ? 0.0 : f32 ? elem<float>(slab, i0) : elem<double>(slab, i0);
                 const double v = wn * (x - x0);
                 a[d] += v;
                 if (wslab) wslab[i] = v;
@@ -481,6 +483,46 @@ int onsager_cross(int threads, bool fft, const double* moments, int S, int64_t T
 int onsager(const State& s, bool fft, int S, const int32_t* species, const double* w, double* moments, double* cross) {
     moments_of(s, S, species, w, moments, nullptr);
     return cross ? onsager_cross(s.threads, fft, moments, S, s.T, s.D, cross) : TA_OK;
+}
+
+// the Green-Kubo twin of onsager_cross: the pseudo-particles of the currents, their autocorrelations, lag 0 kept
+int current_cross(int threads, bool fft, const double* currents, int S, int64_t T, int D, double* cross) {
+    const int64_t P = (int64_t)S * S;
+    std::vector<double> pm, bp, ts;
+    try {
+        pm.assign((size_t)T * P * D, 0.0);
+        bp.assign((size_t)T * P, 0.0);
+        ts.assign((size_t)T, 0.0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    bool nz[8] = {};
+    for (int i = 0; i < S; ++i)
+        for (int64_t k = 0; k < T * D && !nz[i]; ++k) nz[i] = currents[(size_t)i * T * D + k] != 0.0;
+    for (int64_t t = 0; t < T; ++t)
+        for (int i = 0; i < S; ++i)
+            for (int j = 0; j < S; ++j)
+                for (int d = 0; d < D; ++d) {
+                    const double ji = currents[((size_t)i * T + t) * D + d], jj = currents[((size_t)j * T + t) * D + d];
+                    pm[((size_t)t * P + i * S + j) * D + d] = i == j ? ji : i < j ? ji + jj : ji - jj;
+                }
+    const State v = f64_slab(threads, T, P, D, pm.data());
+    if (int rc = fft ? vacf_fft(v, ts.data(), bp.data()) : vacf_direct(v, ts.data(), bp.data())) return rc;
+    for (int64_t k = 0; k < T; ++k)
+        for (int i = 0; i < S; ++i)
+            for (int j = 0; j < S; ++j) {
+                const int lo = i < j ? i : j, hi = i < j ? j : i;
+                const double* row = bp.data() + (size_t)k * P;
+                double c = 0.0;
+                if (nz[i] && nz[j]) c = i == j ? row[i * S + i] : 0.25 * (row[lo * S + hi] - row[hi * S + lo]);
+                cross[((size_t)k * S + i) * S + j] = c;
+            }
+    return TA_OK;
+}
+
+int current(const State& s, bool fft, int S, const int32_t* species, const double* w, double* currents, double* cross) {
+    moments_of(s, S, species, w, currents, nullptr, false);
+    return cross ? current_cross(s.threads, fft, currents, S, s.T, s.D, cross) : TA_OK;
 }
 
 template <class E>

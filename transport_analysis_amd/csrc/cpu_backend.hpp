@@ -32,6 +32,12 @@ int onsager(const State& s, bool fft, int n_species, const int32_t* species, con
 // cross (n_frames, S, S): C[k, i, j] = 1/4 (MSD(M_i + M_j) - MSD(M_i - M_j))[k] by ONE msd() call on the S^2 pseudo-particles
 // M_i, M_i + M_j, M_i - M_j; lag 0 and every pair with an all-zero moment exactly 0
 int onsager_cross(int threads, bool fft, const double* moments, int n_species, int64_t n_frames, int dim, double* cross);
+// Green-Kubo: currents (n_species, n_frames, dim) = sum_{n: species[n] = s} w_n v of slab 0 (the velocities; nothing
+// subtracted) and, with cross != NULL, current_cross of them
+int current(const State& s, bool fft, int n_species, const int32_t* species, const double* w, double* currents, double* cross);
+// cross (n_frames, S, S): C[k, i, j] = 1/4 (ACF(J_i + J_j) - ACF(J_i - J_j))[k] by ONE vacf call on the S^2 pseudo-particles;
+// lag 0 is kept; every pair with an all-zero current exactly 0
+int current_cross(int threads, bool fft, const double* currents, int n_species, int64_t n_frames, int dim, double* cross);
 // ta_unwrap on host slab `slab` in place (box, axes checked by the caller)
 void unwrap(const State& s, int slab, const BoxTable& box, const int* axes);
 

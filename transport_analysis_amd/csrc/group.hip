@@ -641,6 +641,46 @@ int ta_group_onsager(ta_group* g, int fft, int n_species, const int32_t* h_speci
     });
 }
 
+// Green-Kubo currents: every member's species currents of its atoms, added on the host in member order, then ONE
+// cross-correlation of the summed currents on the first member that holds atoms -- the rule of ta_group_onsager
+int ta_group_current(ta_group* g, int fft, int n_species, const int32_t* h_species, const double* h_weights,
+                     double* h_currents, double* h_cross) {
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
+    TAG_CHECK(check_fft(g, fft));
+    if (n_species < 1 || n_species > TA_ONSAGER_MAX_SPECIES)
+        return gfail(g, TA_E_INVALID, "n_species must be 1 ... " + std::to_string(TA_ONSAGER_MAX_SPECIES));
+    if (!h_species || !h_currents) return gfail(g, TA_E_INVALID, "species labels or currents are NULL");
+    TAG_CHECK(check_staged(g));
+    for (int64_t a = 0; a < g->A; ++a)
+        if (h_species[a] < 0 || h_species[a] >= n_species)
+            return gfail(g, TA_E_INVALID, "species label " + std::to_string(h_species[a]) + " of atom " + std::to_string(a) +
+                                              " is outside 0 ... n_species - 1");
+    const int n = (int)g->ctx.size();
+    const size_t n_out = (size_t)n_species * g->T * g->D;
+    std::vector<std::vector<double>> cur(n);
+    std::vector<int> who;
+    hipError_t he = hipSuccess;  // of a member's copy into cur
+    int rc = for_members(g, &who, [&](int i) {
+        double* d = nullptr;
+        if (const int r = cur_launch(g->ctx[i], fft, n_species, h_species + g->lo[i], h_weights ? h_weights + g->lo[i] : nullptr,
+                                     false, &d))
+            return r;
+        cur[i].resize(n_out);
+        he = hipMemcpyAsync(cur[i].data(), d, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
+        return he == hipSuccess ? TA_OK : TA_E_HIP;
+    });
+    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string("currents copy: ") + hipGetErrorString(he));  // (the group's own failure)
+    if (rc) return drained(g, who, rc);
+    TAG_CHECK(wait_members(g, who));
+    std::fill(h_currents, h_currents + n_out, 0.0);
+    for (int i : who)
+        for (size_t k = 0; k < n_out; ++k) h_currents[k] += cur[i][k];
+    if (h_cross && (rc = cur_cross_host(g->ctx[who[0]], fft, h_currents, n_species, g->T, g->D, h_cross))) return mfail(g, who[0], rc);
+    return TA_OK;
+    });
+}
+
 // Unwrap: every member's block of slab `slab` with the same box table, queued on all devices, then waited for
 int ta_group_unwrap(ta_group* g, int slab, const double* h_dimensions, const int* axes) {
     return group_call(g, [&]() -> int {

@@ -81,6 +81,10 @@ int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T
 // the cross MSD (n_frames, S, S) of host moments (S, n_frames, dim) on the context's device, blocking
 int ons_launch(ta_ctx* ctx, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out);
 int ons_cross_host(ta_ctx* ctx, int fft, const double* h_moments, int S, int64_t T, int D, double* h_cross);
+// api.hip, for group.hip: the same two for ta_current: one context's (n_species, n_frames, dim) currents of its staged
+// velocity slab 0, queued; and the cross-correlation (n_frames, S, S) of host currents on the context's device, blocking
+int cur_launch(ta_ctx* ctx, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out);
+int cur_cross_host(ta_ctx* ctx, int fft, const double* h_currents, int S, int64_t T, int D, double* h_cross);
 // api.hip, for group.hip: one context's ta_unwrap queued on its stream (box.tab must stay valid until host_wait)
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes);
 hipStream_t ctx_stream(ta_ctx* ctx);
@@ -195,6 +199,15 @@ hipError_t launch_species_moment(const double* pos, long pitch, long T, long n_c
                                  const double* w, double* partial, int n_parts, hipStream_t st);
 hipError_t launch_onsager_combos(const double* M, int S, long T, int D, long pitch, double* pm, int* nz, hipStream_t st);
 hipError_t launch_onsager_finish(const double* bp, int S, long T, const int* nz, double* C, hipStream_t st);
+
+// current.hip: the species currents J[s, t, d] = sum_{n: species[n] = s} w_n v[t, n, d] of a pair-major slab of float64 or
+// (f32) float32 elements in one pass over it as it is, as n_parts partial sums partial [n_parts][S][T][D] (written in
+// full; n_parts from species_moment_parts; k_sum_partials adds them in order); species, w as launch_species_moment.
+// finish: C (T, S, S), lag 0 included, from the (T, S^2) by-particle autocorrelations of launch_onsager_combos'
+// pseudo-particles of the currents
+hipError_t launch_species_current(const void* vel, bool f32, long pitch, long T, long n_cols, int D, int S, const int* species,
+                                  const double* w, double* partial, int n_parts, hipStream_t st);
+hipError_t launch_current_finish(const double* bp, int S, long T, const int* nz, double* C, hipStream_t st);
 
 // unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
 // box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)

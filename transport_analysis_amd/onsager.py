@@ -21,6 +21,15 @@ from .conductivity import BOLTZMANN_J_PER_K, ELEMENTARY_CHARGE
 MAX_SPECIES = 8
 
 
+def index_species(labels):
+    """(the distinct labels in ``np.unique`` order, one int32 species index per atom); more than MAX_SPECIES distinct
+    labels raise ValueError"""
+    species, index = np.unique(labels, return_inverse=True)
+    if species.size > MAX_SPECIES:
+        raise ValueError(f"species: {species.size} distinct labels, at most {MAX_SPECIES} are supported")
+    return species, np.ascontiguousarray(index, dtype=np.int32).ravel()
+
+
 class OnsagerHelfand(CollectiveAnalysis):
     r"""Onsager transport coefficients of the species of a system by the Einstein-Helfand relation.
 
@@ -58,7 +67,7 @@ class OnsagerHelfand(CollectiveAnalysis):
         (J m s)^-1 per particle^2 (A^2 / ps = 1e-8 m^2 / s, A^3 = 1e-30 m^3); divide by N_A^2 for mol^2 J^-1 m^-1 s^-1.
 
     Not here: the per-species SELF terms (sum_{n in s} w_n^2 MSD_n: ``EinsteinMSD`` on the species' atoms, times their
-    number), a centre-of-mass reference frame, the Green-Kubo (velocity) form.
+    number), a centre-of-mass reference frame.  The Green-Kubo (velocity) form is ``OnsagerGreenKubo``.
     """
 
     _no_data_message = ("Onsager coefficient computation requires "
@@ -72,11 +81,7 @@ class OnsagerHelfand(CollectiveAnalysis):
         super().__init__(atomgroup, temp_avg, dim_type, linear_fit_window, fft, unwrap, kwargs)
         if isinstance(species, str):
             species = getattr(atomgroup, species)
-        labels = self._per_atom(species, "species", "labels", dtype=None)
-        self.species, index = np.unique(labels, return_inverse=True)
-        if self.species.size > MAX_SPECIES:
-            raise ValueError(f"species: {self.species.size} distinct labels, at most {MAX_SPECIES} are supported")
-        self.species_index = np.ascontiguousarray(index, dtype=np.int32).ravel()
+        self.species, self.species_index = index_species(self._per_atom(species, "species", "labels", dtype=None))
         self.n_species = max(int(self.species.size), 1)
         self.weights = None if weights is None else self._per_atom(weights, "weights", "values")
 
