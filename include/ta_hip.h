@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_unwrap / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_unwrap / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -153,6 +153,8 @@ int ta_stage_synth(ta_ctx *ctx, int slab, uint64_t seed, int64_t col_offset, int
  * the self term, the weighted slab (the input's size), and for ta_onsager* the species moments' partial sums
  * (<= 1024 * n_species * n_frames * dim * 8 bytes), the pair-major slab of the n_species^2 pseudo-particles and their
  * by-particle MSDs (n_species^2 * n_frames * (dim + 1) * 8 bytes); ta_current* use the same workspaces for the currents;
+ * for ta_species_self* the weighted slab with each species' atoms contiguous (the input's element count * 8 bytes, plus at
+ * most one column per species) beside what the lag-sum evaluation of one species needs;
  * the labels, weights and outputs of host-facing calls are kept.                                                                                                            */
 int ta_trim(ta_ctx *ctx);
 
@@ -262,6 +264,30 @@ int ta_current(ta_ctx *ctx, int fft, int n_species, const int32_t *h_species, co
 int ta_current_cross(ta_ctx *ctx, int fft, const double *h_currents, int n_species, int64_t n_frames, int dim,
                      double *h_cross);
 
+/* ta_species_self : the per-species SELF terms of the Onsager analyses (OnsagerHelfand / OnsagerGreenKubo with self_terms=True)
+ *                   on slab 0, labels, weights and n_species as for ta_onsager:
+ *                     h_self[s * n_frames + k] = sum_{n: species[n] = s} w_n^2 f_n(k)          ((n_species, n_frames), required)
+ *                   quantity TA_SELF_MSD: slab 0 = the positions, f_n = ta_msd's by-particle series (row 0 exactly 0);
+ *                   quantity TA_SELF_VACF: slab 0 = the velocities, f_n = the VACF's by-particle series (lag 0 kept).
+ *                   h_counts (n_species) or NULL: the atoms per species.  No division by counts anywhere.  ONE pass over the
+ *                   slab, in the element type it has (a float32 device slab is read as float32 and widened in registers),
+ *                   writes the float64 slab W = w (x - x[0]) (MSD: the shift comes before the weight, as ta_conductivity's
+ *                   self term) or w v (VACF) with each species' atoms contiguous and in input order, every species' block
+ *                   starting on a column pair (k_species_sort: no atomics, one writer per element); then every species
+ *                   with atoms gets one lag-sum evaluation on its block, the one ta_msd / ta_vacf_fft (fft = 1) /
+ *                   ta_vacf_direct (fft = 0) would run on a slab of that species' weighted atoms alone -- the same bits.
+ *                   A species without atoms: exact zeros.  With one species and weights = charges, TA_SELF_MSD is
+ *                   ta_conductivity's h_self_lagsum bit for bit.  NULL h_species / h_self, quantity or fft other than
+ *                   0 / 1, n_species out of range, a label outside 0 ... n_species - 1 (checked on the host before
+ *                   anything is written): TA_E_INVALID; nothing staged: TA_E_STATE; n_atoms * dim must be below 2^31.  CPU
+ *                   backend: each species gathered and weighted on the host, then its MSD / VACF routines.  Timings: the
+ *                   pass is the main kernel unless an evaluation after it records its own (ta_kernel_timeline names it
+ *                   k_species_sort).                                                                                   */
+#define TA_SELF_MSD 0
+#define TA_SELF_VACF 1
+int ta_species_self(ta_ctx *ctx, int quantity, int fft, int n_species, const int32_t *h_species, const double *h_weights,
+                    double *h_self, int64_t *h_counts);
+
 /* ---- periodic unwrapping of a staged position slab ---------------------------------------------------------------
  * ta_unwrap: undo periodic wrapping of staging slab `slab` in place (MDAnalysis' NoJump), over the staged frames
  * in order.  h_dimensions: (n_frames, 6) float64 rows [a, b, c, alpha, beta, gamma] (A, degrees; ts.dimensions).
@@ -319,6 +345,13 @@ int ta_current_dev(ta_ctx *ctx, const double *d_vel, int64_t n_frames, int64_t n
                    int n_species, const int32_t *d_species, const double *d_weights, double *d_currents, double *d_cross,
                    void *stream);
 
+/* d_x: frame-major float64 positions (TA_SELF_MSD) or velocities (TA_SELF_VACF); h_species: HOST labels (the block sizes
+ * decide the launches; checked before anything is written); d_weights: (n_atoms,) device array or NULL (all 1); d_self
+ * (n_species, n_frames).  Shards' self terms add up. */
+int ta_species_self_dev(ta_ctx *ctx, const double *d_x, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row,
+                        int quantity, int fft, int n_species, const int32_t *h_species, const double *d_weights,
+                        double *d_self, void *stream);
+
 /* ---- compute on the staged (pair-major) slabs, device outputs, asynchronous on `stream` ----
  * Same arithmetic and outputs as the *_dev calls, on the slabs of ta_stage_alloc*: no
  * transposition, no second copy.  d_masses: (n_atoms,) float64 device array.              */
@@ -336,6 +369,10 @@ int ta_onsager_staged(ta_ctx *ctx, int fft, int n_species, const int32_t *d_spec
 /* slab 0 holds the velocities, float64 or ("stage_device_f32") float32 elements: read as they are */
 int ta_current_staged(ta_ctx *ctx, int fft, int n_species, const int32_t *d_species, const double *d_weights,
                       double *d_currents, double *d_cross, void *stream);
+
+/* h_species: HOST labels, as for ta_species_self_dev; slab 0 is read in the element type it has */
+int ta_species_self_staged(ta_ctx *ctx, int quantity, int fft, int n_species, const int32_t *h_species,
+                           const double *d_weights, double *d_self, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns
@@ -402,6 +439,10 @@ int ta_group_onsager(ta_group *g, int fft, int n_species, const int32_t *h_speci
  * order, then ONE cross evaluation of the summed currents runs on the first member that holds atoms.                   */
 int ta_group_current(ta_group *g, int fft, int n_species, const int32_t *h_species, const double *h_weights,
                      double *h_currents, double *h_cross);
+/* ta_group_species_self: ta_species_self on every member with its slice of h_species / h_weights (all n_atoms; labels checked
+ * first); the members' (n_species, n_frames) arrays and counts are SUMMED on the host in member order.               */
+int ta_group_species_self(ta_group *g, int quantity, int fft, int n_species, const int32_t *h_species,
+                          const double *h_weights, double *h_self, int64_t *h_counts);
 /* ta_group_unwrap: ta_unwrap on every member's block of slab `slab` (declared with ta_unwrap above) */
 int ta_group_unwrap(ta_group *g, int slab, const double *h_dimensions, const int *axes); /* every member's block */
 

@@ -37,6 +37,7 @@ _FRAME = _int(_vp, _ci, _i64, _vp, _ci, _i64, _ci, _ci, _ci, _i64, _vp, _i64)
 _COND = _int(_vp, _ci, _vp, _vp, _vp, _vp)
 _UNWRAP = _int(_vp, _ci, _vp, _vp)
 _ONSAGER = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, fft, n_species, h_species, h_weights, h_moments, h_cross)
+_SELF = _int(_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, quantity, fft, n_species, h_species, h_weights, h_self, h_counts)
 
 #: every symbol include/ta_hip.h declares -> (result type, argument types): the one table EXPORTS and lib() are made of
 _API = {
@@ -59,6 +60,8 @@ _API = {
     "ta_current": _ONSAGER, "ta_current_cross": _int(_vp, _ci, _vp, _ci, _i64, _ci, _vp),
     "ta_current_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_current_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
+    "ta_species_self": _SELF, "ta_species_self_staged": _int(_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp),
+    "ta_species_self_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _ci, _vp, _vp, _vp, _vp),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
     "ta_helfand_msd_dev": _int(_vp, _vp, _vp, _vp, _i64, _i64, _ci, _i64, _dbl, _vp, _vp, _i64, _vp),
     "ta_msd_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _vp, _i64, _vp),
@@ -78,7 +81,7 @@ _API = {
     "ta_group_stage_synth": _int(_vp, _ci, ctypes.c_uint64, _i64, _i64),
     "ta_group_vacf_fft": _HOST, "ta_group_vacf_direct": _HOST, "ta_group_helfand_msd": _int(_vp, _vp, _dbl, _vp, _vp),
     "ta_group_msd": _int(_vp, _ci, _vp, _vp), "ta_group_conductivity": _COND, "ta_group_unwrap": _UNWRAP,
-    "ta_group_onsager": _ONSAGER, "ta_group_current": _ONSAGER,
+    "ta_group_onsager": _ONSAGER, "ta_group_current": _ONSAGER, "ta_group_species_self": _SELF,
 }
 EXPORTS = tuple(_API)
 
@@ -273,6 +276,7 @@ class PinnedResult:
 
 
 DEVICE_CPU = -1  # ta_hip.h: TA_DEVICE_CPU
+SELF_MSD, SELF_VACF = 0, 1  # ta_hip.h: TA_SELF_MSD, TA_SELF_VACF
 
 
 def device_index(device):
@@ -444,6 +448,20 @@ class _Staged:
         self._call("current", int(fft), S, _ptr(lab), _ptr(w), _ptr(currents), _ptr(c))
         return currents, c
 
+    def species_self(self, quantity, fft, species, n_species=None, weights=None):
+        """Per-species self terms of slab 0, ta_species_self: `quantity` SELF_MSD (slab 0 = positions) or SELF_VACF
+        (velocities), the other arguments as `onsager`: (self (n_species, n_frames) = sum_{n in s} w_n^2 f_n(k), counts
+        (n_species,) int64 = the atoms per species)."""
+        T, _, _ = self._staged_shape()
+        lab = self._per_atom(species, np.int32, "species", "labels")
+        S = int(n_species) if n_species is not None else int(lab.max()) + 1
+        w = self._per_atom(weights, np.float64, "weights", "values")
+        n = max(S, 1)
+        out = np.empty((n, T), dtype=np.float64)
+        counts = np.zeros(n, dtype=np.int64)
+        self._call("species_self", int(quantity), int(fft), S, _ptr(lab), _ptr(w), _ptr(out), _ptr(counts))
+        return out, counts
+
     def unwrap(self, slab, dimensions, axes):
         """Undo periodic wrapping of staged slab `slab` in place (MDAnalysis' NoJump, ta_unwrap; a group: on every
         member's block of the slab): `dimensions` the (n_frames, 6) boxes [a, b, c, alpha, beta, gamma] of the staged
@@ -601,6 +619,21 @@ class Context(_Staged):
 
     def current_staged(self, fft, n_species, d_species, d_currents, d_weights=0, d_cross=0, stream=0):
         self._call("current_staged", int(fft), int(n_species), d_species, d_weights or None, d_currents, d_cross or None,
+                   stream or None)
+
+    def species_self_dev(self, d_x, n_frames, n_atoms, dim, ld_row, quantity, fft, n_species, species, d_self, d_weights=0,
+                         stream=0):
+        """`species`: HOST labels, one per atom (checked by the library before anything is written)"""
+        lab = np.ascontiguousarray(species, dtype=np.int32).ravel()
+        if lab.size != n_atoms:
+            raise ValueError(f"species: {lab.size} labels for {n_atoms} atoms")
+        self._call("species_self_dev", d_x, n_frames, n_atoms, dim, ld_row, int(quantity), int(fft), int(n_species), _ptr(lab),
+                   d_weights or None, d_self, stream or None)
+
+    def species_self_staged(self, quantity, fft, n_species, species, d_self, d_weights=0, stream=0):
+        """`species`: HOST labels, one per staged atom (checked by the library before anything is written)"""
+        lab = self._per_atom(species, np.int32, "species", "labels")
+        self._call("species_self_staged", int(quantity), int(fft), int(n_species), _ptr(lab), d_weights or None, d_self,
                    stream or None)
 
     # -- timing ----------------------------------------------------------

@@ -136,6 +136,12 @@ struct ta_ctx {
     DevBuf ons_part{workspaces, kTrimmed}, ons_lab{workspaces, kKept}, ons_w{workspaces, kKept};
     DevBuf ons_out{workspaces, kKept}, ons_pm{workspaces, kTrimmed}, ons_bp{workspaces, kTrimmed};
     DevBuf unwrap_box{workspaces, kTrimmed};    // ta_unwrap: the box table (unwrap_box.hpp) of the last call
+    // species self terms (species_self_pm): the weighted slab with each species' atoms contiguous (the input's element
+    // count x 8 bytes + at most one column per species), the atoms in sorted order and the output of host-facing calls.
+    // self_order_h is what the upload of the order reads: it stays until ev_order says the copy is done
+    DevBuf self_w{workspaces, kTrimmed}, self_order{workspaces, kKept}, self_out{workspaces, kKept};
+    std::vector<int32_t> self_order_h;
+    hipEvent_t ev_order = nullptr;
     // staging: two landing buffers, so that a piece crosses PCIe while the one before it is transposed
     DevBuf bounce{workspaces, kTrimmed}, bounce2{workspaces, kTrimmed};
     DevBuf clock_stamps{workspaces, kTrimmed};  // ta_clock_probe: the stamps of its last launch
@@ -941,6 +947,59 @@ int check_labels(ta_ctx* ctx, const int32_t* h_species, int64_t n, int S) {
     return TA_OK;
 }
 
+// ---- species-resolved self terms (species_self.hip) ------------------------------------------------------------------
+int self_args(ta_ctx* ctx, int quantity, int fft, int S, const void* species, const void* out) {
+    if (quantity != TA_SELF_MSD && quantity != TA_SELF_VACF)
+        return fail(ctx, TA_E_INVALID, "quantity must be TA_SELF_MSD (0) or TA_SELF_VACF (1)");
+    TA_CHECK(check_fft(ctx, fft));
+    TA_CHECK(check_species_count(ctx, S));
+    if (!species) return fail(ctx, TA_E_INVALID, "species labels are NULL");
+    if (!out) return fail(ctx, TA_E_INVALID, "self output is NULL");
+    return TA_OK;
+}
+
+// The host half of one call: the labels checked, the blocks laid out, the sorted order (one int32 per atom) queued for
+// upload on `st`.  Nothing on the device has been written when this fails.
+int self_plan(ta_ctx* ctx, int S, const int32_t* h_species, int64_t A, int D, hipStream_t st, SortPlan* plan) {
+    if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "species self terms: n_atoms * dim must be below 2^31");
+    TA_CHECK(check_labels(ctx, h_species, A, S));
+    TA_CHECK(ensure(ctx, ctx->self_order, sizeof(int32_t) * (size_t)A));
+    if (!ctx->ev_order) TA_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_order, hipEventDisableTiming));
+    else TA_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_order));  // the last call's upload has left self_order_h
+    ctx->self_order_h.resize((size_t)A);
+    species_sort_plan(h_species, A, D, S, plan, ctx->self_order_h.data());
+    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->self_order.p, ctx->self_order_h.data(), sizeof(int32_t) * (size_t)A, hipMemcpyHostToDevice, st));
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev_order, st));
+    return TA_OK;
+}
+
+// One self-term call on a pair-major slab of either element type, read as it is (the caller has opened the call's
+// bracket, it is closed here): the sort pass writes W = w (x - shift x[0]) with each species' atoms contiguous, then
+// every species with atoms gets ONE lag-sum evaluation on its block -- a pair-major slab of its own with N_s atoms -- by
+// the dispatch ta_msd_staged / ta_vacf_fft_staged / ta_vacf_direct_staged use, into d_self + s T.  A species without
+// atoms: exact zeros, no call.  ev[1] / ev[2] bracket the pass, unless an evaluation after it records its own kernel.
+int species_self_pm(ta_ctx* ctx, int quantity, bool fft, const void* pm_any, bool pm_f32, int64_t pitch, int64_t T, int64_t A,
+                    int D, const SortPlan& plan, const double* d_w, double* d_self, hipStream_t st) {
+    TA_CHECK(ensure(ctx, ctx->self_w, (size_t)plan.n_pairs * (size_t)pitch * 16));
+    double* W = (double*)ctx->self_w.p;
+    TA_LAUNCH_MAIN(ctx, "k_species_sort", st,
+                   launch_species_sort(ctx->n_cu, pm_any, pm_f32, (long)pitch, (long)T, (long)(A * D), D, plan,
+                                       (const int*)ctx->self_order.p, d_w, quantity == TA_SELF_MSD, W, st));
+    for (int s = 0; s < plan.n_species; ++s) {
+        double* out = d_self + (size_t)s * T;
+        const int64_t n = plan.count[s];
+        if (n == 0) {
+            TA_HIP_TRY(ctx, hipMemsetAsync(out, 0, sizeof(double) * (size_t)T, st));
+            continue;
+        }
+        const double* blk = W + (size_t)plan.pair0[s] * (size_t)pitch * 2;
+        if (quantity == TA_SELF_MSD) TA_CHECK(msd_impl(ctx, fft, blk, pitch, T, n, D, out, nullptr, 0, st));
+        else if (fft) TA_CHECK(fft_impl(ctx, blk, pitch, T, n, D, out, nullptr, 0, st));
+        else TA_CHECK(direct_impl(ctx, MODE_VACF, blk, nullptr, nullptr, T, n, D, pitch, 1.0, out, nullptr, 0, st));
+    }
+    return call_end(ctx, st);
+}
+
 // ---- Green-Kubo species currents (current.hip) ----------------------------------------------------------------------
 // C[k, i, j] of the (S, T, D) currents at d_currents into d_cross (T, S, S), by polarisation in ONE autocorrelation call:
 // the S^2 pseudo-particles J_i, J_i + J_j, J_i - J_j as a pair-major slab (k_onsager_combos, in the Onsager workspaces),
@@ -1187,6 +1246,10 @@ int ta_ctx_destroy(ta_ctx* ctx) {
         for (auto& ev : q)
             if (ev) hipEventDestroy(ev);
     if (ctx->ev_stage) hipEventDestroy(ctx->ev_stage);
+    if (ctx->ev_order) {
+        hipEventSynchronize(ctx->ev_order);  // (the upload may be on a caller's stream)
+        hipEventDestroy(ctx->ev_order);
+    }
     for (hipEvent_t e : ctx->mark_pool) hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) {
         if (ctx->ev_piece[i]) hipEventDestroy(ctx->ev_piece[i]);
@@ -1746,6 +1809,44 @@ int ta_current_staged(ta_ctx* ctx, int fft, int n_species, const int32_t* d_spec
     });
 }
 
+// Species self terms: slab 0 / d_x holds the positions (TA_SELF_MSD) or the velocities (TA_SELF_VACF); the staged slab
+// is read in its own element type (never widened); the labels are HOST arrays: the block sizes decide the launches
+int ta_species_self_dev(ta_ctx* ctx, const double* d_x, int64_t T, int64_t A, int D, int64_t ld_row, int quantity, int fft,
+                        int n_species, const int32_t* h_species, const double* d_weights, double* d_self, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    TA_NO_CPU(ctx);
+    TA_CHECK(check_shape(ctx, T, A, D, ld_row));
+    TA_CHECK(self_args(ctx, quantity, fft, n_species, h_species, d_self));
+    if (!d_x) return fail(ctx, TA_E_INVALID, "null device pointer");
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    SortPlan plan;
+    TA_CHECK(self_plan(ctx, n_species, h_species, A, D, st, &plan));
+    TA_CHECK(call_begin(ctx, st));
+    const double* px = nullptr;
+    TA_CHECK(relayout_input(ctx, 0, d_x, T, A * D, ld_row, st, &px));
+    return species_self_pm(ctx, quantity, fft != 0, px, false, pm_pitch(T), T, A, D, plan, d_weights, d_self, st);
+    });
+}
+
+int ta_species_self_staged(ta_ctx* ctx, int quantity, int fft, int n_species, const int32_t* h_species, const double* d_weights,
+                           double* d_self, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(self_args(ctx, quantity, fft, n_species, h_species, d_self));
+    TA_CHECK(check_staged(ctx));
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    SortPlan plan;
+    TA_CHECK(self_plan(ctx, n_species, h_species, ctx->st_A, ctx->st_D, st, &plan));
+    TA_CHECK(order_after_staging(ctx, st));
+    TA_CHECK(call_begin(ctx, st));
+    return species_self_pm(ctx, quantity, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A,
+                           ctx->st_D, plan, d_weights, d_self, st);
+    });
+}
+
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guarded(fail, ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
@@ -2051,6 +2152,32 @@ int cur_cross_host(ta_ctx* ctx, int fft, const double* h_currents, int S, int64_
     return host_finish(ctx, {{h_cross, cross, (size_t)T * S * S}});
 }
 
+// Self-term share of a host-facing call, queued on ctx->stream and not waited for: the labels (this context's atoms)
+// checked and sorted, the weights uploaded (the Onsager weight buffer: one call at a time uses it), the (S, T) lag sums
+// left on the device in *d_out; h_counts (S) or NULL: this context's atoms per species.
+int self_launch(ta_ctx* ctx, int quantity, int fft, int S, const int32_t* h_species, const double* h_w, int64_t* h_counts,
+                double** d_out) {
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(check_staged(ctx));
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t T = ctx->st_T, A = ctx->st_A;
+    const int D = ctx->st_D;
+    SortPlan plan;
+    TA_CHECK(self_plan(ctx, S, h_species, A, D, ctx->stream, &plan));
+    if (h_w) TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * A));
+    TA_CHECK(ensure(ctx, ctx->self_out, sizeof(double) * (size_t)T * S));
+    if (h_w) TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_w.p, h_w, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
+    TA_CHECK(order_after_staging(ctx, ctx->stream));
+    TA_CHECK(call_begin(ctx, ctx->stream));
+    TA_CHECK(species_self_pm(ctx, quantity, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, T, A, D, plan,
+                             h_w ? (const double*)ctx->ons_w.p : nullptr, (double*)ctx->self_out.p, ctx->stream));
+    if (h_counts)
+        for (int s = 0; s < S; ++s) h_counts[s] = plan.count[s];
+    *d_out = (double*)ctx->self_out.p;
+    return TA_OK;
+}
+
 // One context's unwrap of staged slab `slab` (ta_unwrap, ta_group_unwrap), queued on ctx->stream behind the queued commits
 // and bracketed by the timing events: the box table's copy (box.tab must stay valid until host_wait), then the kernel
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes) {
@@ -2216,6 +2343,25 @@ int ta_current_cross(ta_ctx* ctx, int fft, const double* h_currents, int n_speci
         return TA_OK;
     }
     return ta::cur_cross_host(ctx, fft, h_currents, n_species, n_frames, dim, h_cross);
+    });
+}
+
+int ta_species_self(ta_ctx* ctx, int quantity, int fft, int n_species, const int32_t* h_species, const double* h_weights,
+                    double* h_self, int64_t* h_counts) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(self_args(ctx, quantity, fft, n_species, h_species, h_self));
+    TA_CHECK(check_staged(ctx));
+    if (ctx->is_cpu) {
+        TA_CHECK(check_labels(ctx, h_species, ctx->st_A, n_species));
+        if (int rc = ta::cpu::species_self(cpu_state(ctx), quantity == TA_SELF_MSD, fft != 0, n_species, h_species, h_weights,
+                                           h_self, h_counts))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    double* d_out = nullptr;
+    TA_CHECK(ta::self_launch(ctx, quantity, fft, n_species, h_species, h_weights, h_counts, &d_out));
+    return host_finish(ctx, {{h_self, d_out, (size_t)n_species * (size_t)ctx->st_T}});
     });
 }
 

@@ -525,6 +525,46 @@ int current(const State& s, bool fft, int S, const int32_t* species, const doubl
     return cross ? current_cross(s.threads, fft, currents, S, s.T, s.D, cross) : TA_OK;
 }
 
+int species_self(const State& s, bool msd_quantity, bool fft, int S, const int32_t* species, const double* w, double* self,
+                 int64_t* counts) {
+    const int64_t T = s.T, A = s.A;
+    const int D = s.D;
+    const void* slab = s.slabs[0];
+    const bool f32 = s.dtype == TA_F32;
+    for (int sp = 0; sp < S; ++sp) {
+        std::vector<int64_t> atoms;
+        std::vector<double> ws;
+        try {
+            for (int64_t n = 0; n < A; ++n)
+                if (species[n] == sp) atoms.push_back(n);
+            ws.assign((size_t)T * atoms.size() * D, 0.0);
+        } catch (const std::bad_alloc&) {
+            return TA_E_NOMEM;
+        }
+        const int64_t N = (int64_t)atoms.size();
+        if (counts) counts[sp] = N;
+        double* out = self + (size_t)sp * T;
+        std::fill(out, out + T, 0.0);
+        if (N == 0) continue;
+#pragma omp parallel for num_threads(s.threads) schedule(static)
+        for (int64_t t = 0; t < T; ++t)
+            for (int64_t r = 0; r < N; ++r) {
+                const int64_t n = atoms[r];
+                const double wn = w ? w[n] : 1.0;
+                for (int d = 0; d < D; ++d) {
+                    const size_t i0 = (size_t)n * D + d, i = (size_t)t * A * D + i0;
+                    const double x = f32 ? elem<float>(slab, i) : elem<double>(slab, i);
+                    const double x0 = !msd_quantity ? 0.0 : f32 ? elem<float>(slab, i0) : elem<double>(slab, i0);
+                    ws[((size_t)t * N + r) * D + d] = wn * (x - x0);
+                }
+            }
+        const State v = f64_slab(s.threads, T, N, D, ws.data());
+        if (int rc = msd_quantity ? msd(v, fft, out, nullptr) : fft ? vacf_fft(v, out, nullptr) : vacf_direct(v, out, nullptr))
+            return rc;
+    }
+    return TA_OK;
+}
+
 template <class E>
 void unwrap_t(const State& s, int slab, const BoxTable& box, const int* axes) {
     const int64_t T = s.T, A = s.A, tp = box.per_frame ? box.tpitch : 0;

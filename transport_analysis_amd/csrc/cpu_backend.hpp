@@ -38,6 +38,11 @@ int current(const State& s, bool fft, int n_species, const int32_t* species, con
 // cross (n_frames, S, S): C[k, i, j] = 1/4 (ACF(J_i + J_j) - ACF(J_i - J_j))[k] by ONE vacf call on the S^2 pseudo-particles;
 // lag 0 is kept; every pair with an all-zero current exactly 0
 int current_cross(int threads, bool fft, const double* currents, int n_species, int64_t n_frames, int dim, double* cross);
+// species self terms: self (n_species, n_frames) = sum_{n: species[n] = s} w_n^2 f_n, f_n the by-particle MSD (msd_quantity) or
+// VACF of slab 0: each species' atoms gathered in input order as w (x - x[0]) or w v into a float64 slab of their own, then
+// msd() / vacf_fft() / vacf_direct() on it; counts (n_species) or NULL; a species without atoms: zeros
+int species_self(const State& s, bool msd_quantity, bool fft, int n_species, const int32_t* species, const double* w,
+                 double* self, int64_t* counts);
 // ta_unwrap on host slab `slab` in place (box, axes checked by the caller)
 void unwrap(const State& s, int slab, const BoxTable& box, const int* axes);
 

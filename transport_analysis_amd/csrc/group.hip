@@ -681,6 +681,53 @@ int ta_group_current(ta_group* g, int fft, int n_species, const int32_t* h_speci
     });
 }
 
+// Species self terms: every member's (n_species, n_frames) lag sums and counts of its atoms (its slice of the labels and
+// weights), added on the host in member order (lag sums are linear in atoms: nothing follows the sum)
+int ta_group_species_self(ta_group* g, int quantity, int fft, int n_species, const int32_t* h_species, const double* h_weights,
+                          double* h_self, int64_t* h_counts) {
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
+    if (quantity != TA_SELF_MSD && quantity != TA_SELF_VACF)
+        return gfail(g, TA_E_INVALID, "quantity must be TA_SELF_MSD (0) or TA_SELF_VACF (1)");
+    TAG_CHECK(check_fft(g, fft));
+    if (n_species < 1 || n_species > TA_ONSAGER_MAX_SPECIES)
+        return gfail(g, TA_E_INVALID, "n_species must be 1 ... " + std::to_string(TA_ONSAGER_MAX_SPECIES));
+    if (!h_species || !h_self) return gfail(g, TA_E_INVALID, "species labels or self output are NULL");
+    TAG_CHECK(check_staged(g));
+    for (int64_t a = 0; a < g->A; ++a)
+        if (h_species[a] < 0 || h_species[a] >= n_species)
+            return gfail(g, TA_E_INVALID, "species label " + std::to_string(h_species[a]) + " of atom " + std::to_string(a) +
+                                              " is outside 0 ... n_species - 1");
+    const int n = (int)g->ctx.size();
+    const size_t n_out = (size_t)n_species * g->T;
+    std::vector<std::vector<double>> slf(n);
+    std::vector<std::vector<int64_t>> cnt(n);
+    std::vector<int> who;
+    hipError_t he = hipSuccess;  // of a member's copy into slf
+    int rc = for_members(g, &who, [&](int i) {
+        double* d = nullptr;
+        cnt[i].assign(n_species, 0);
+        if (const int r = self_launch(g->ctx[i], quantity, fft, n_species, h_species + g->lo[i],
+                                      h_weights ? h_weights + g->lo[i] : nullptr, cnt[i].data(), &d))
+            return r;
+        slf[i].resize(n_out);
+        he = hipMemcpyAsync(slf[i].data(), d, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
+        return he == hipSuccess ? TA_OK : TA_E_HIP;
+    });
+    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string("self terms copy: ") + hipGetErrorString(he));  // (the group's own failure)
+    if (rc) return drained(g, who, rc);
+    TAG_CHECK(wait_members(g, who));
+    std::fill(h_self, h_self + n_out, 0.0);
+    if (h_counts) std::fill(h_counts, h_counts + n_species, (int64_t)0);
+    for (int i : who) {
+        for (size_t k = 0; k < n_out; ++k) h_self[k] += slf[i][k];
+        if (h_counts)
+            for (int s = 0; s < n_species; ++s) h_counts[s] += cnt[i][s];
+    }
+    return TA_OK;
+    });
+}
+
 // Unwrap: every member's block of slab `slab` with the same box table, queued on all devices, then waited for
 int ta_group_unwrap(ta_group* g, int slab, const double* h_dimensions, const int* axes) {
     return group_call(g, [&]() -> int {

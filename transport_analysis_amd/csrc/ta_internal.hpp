@@ -85,6 +85,11 @@ int ons_cross_host(ta_ctx* ctx, int fft, const double* h_moments, int S, int64_t
 // velocity slab 0, queued; and the cross-correlation (n_frames, S, S) of host currents on the context's device, blocking
 int cur_launch(ta_ctx* ctx, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out);
 int cur_cross_host(ta_ctx* ctx, int fft, const double* h_currents, int S, int64_t T, int D, double* h_cross);
+// api.hip, for group.hip: one context's ta_species_self share (its staged slab 0 with its atoms' labels and weights, the
+// call's n_species; labels checked here), queued: *d_out = the (n_species, n_frames) self lag sums, valid after host_wait;
+// h_counts (n_species) or NULL: its atoms per species
+int self_launch(ta_ctx* ctx, int quantity, int fft, int S, const int32_t* h_species, const double* h_w, int64_t* h_counts,
+                double** d_out);
 // api.hip, for group.hip: one context's ta_unwrap queued on its stream (box.tab must stay valid until host_wait)
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes);
 hipStream_t ctx_stream(ta_ctx* ctx);
@@ -208,6 +213,21 @@ hipError_t launch_onsager_finish(const double* bp, int S, long T, const int* nz,
 hipError_t launch_species_current(const void* vel, bool f32, long pitch, long T, long n_cols, int D, int S, const int* species,
                                   const double* w, double* partial, int n_parts, hipStream_t st);
 hipError_t launch_current_finish(const double* bp, int S, long T, const int* nz, double* C, hipStream_t st);
+
+// species_self.hip: the weighted slab W = w (x - shift x[0]) of a pair-major slab of float64 or (f32) float32 elements with
+// each species' atoms contiguous, as a float64 pair-major slab of plan.n_pairs pairs: species s's block starts at pair
+// plan.pair0[s] and is a slab of count[s] atoms of its own (a phantom last column and the rows T ... pitch - 1 written as
+// zeros).  species_sort_plan: the blocks and order (n_atoms,) = the atoms species by species, input order kept, from
+// host labels in [0, S) (checked by the caller); order goes to the device, one int32 per atom.
+struct SortPlan {
+    int n_species, n_units;  // units: two consecutive atoms of one species in sorted order
+    long n_pairs;
+    int count[TA_ONSAGER_MAX_SPECIES], pos0[TA_ONSAGER_MAX_SPECIES], unit0[TA_ONSAGER_MAX_SPECIES];
+    long pair0[TA_ONSAGER_MAX_SPECIES];
+};
+void species_sort_plan(const int32_t* h_species, int64_t n_atoms, int D, int S, SortPlan* plan, int32_t* order);
+hipError_t launch_species_sort(int n_cu, const void* x, bool f32, long pitch, long T, long n_cols, int D, const SortPlan& plan,
+                               const int* order, const double* w, bool shift, double* W, hipStream_t st);
 
 // unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
 // box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)

@@ -16,10 +16,11 @@ import numpy as np
 
 from ._base import CollectiveAnalysis, UpdatingAtomGroup
 from .conductivity import BOLTZMANN_J_PER_K, ELEMENTARY_CHARGE
-from .onsager import index_species
+from . import _lib
+from .onsager import SelfTerms, index_species
 
 
-class OnsagerGreenKubo(CollectiveAnalysis):
+class OnsagerGreenKubo(SelfTerms, CollectiveAnalysis):
     r"""Onsager transport coefficients of the species of a system by the Green-Kubo relation.
 
     .. math:: C_{ij}(k) = \frac{1}{2} \frac{1}{T - k} \sum_{t < T - k} \sum_d (J_{i; t, d} J_{j; t+k, d} + J_{j; t, d} J_{i; t+k, d}),
@@ -38,6 +39,9 @@ class OnsagerGreenKubo(CollectiveAnalysis):
     fft : bool — ``True``: ``VelocityAutocorr``'s FFT evaluation for the correlations; ``False``: the direct forms.  The
         error of ``C_ij`` is relative to ``max(C_ii(0), C_jj(0))``, not to ``|C_ij|``.
     weights : array, keyword-only — one weight per atom (default 1; charges enter through ``conductivity(z)``).
+    self_terms : bool, keyword-only, default False — also compute the self part of every species,
+        ``sum_{n in s} w_n^2 VACF_n(k)``, in one more pass over the slab (``k_species_sort`` behind ``ta_species_self``,
+        a float32 slab read as it is) and one VACF lag-sum call per species.
     device, devices, distributed, stage_dtype : keyword-only — as for ``VelocityAutocorr``.  float32 staging stays float32
         on the device at every number of frames: the current pass reads it as it is.  Under ``distributed=True`` every
         rank forms the currents of its block of atoms; they are summed over ranks BEFORE the correlation.
@@ -52,8 +56,15 @@ class OnsagerGreenKubo(CollectiveAnalysis):
     ``onsager_gk`` / ``onsager_gk_odd`` integrate over a window of lags with ``VelocityAutocorr``'s convention
     (``start=0, stop=0, step=1``; ``stop=0``: all lags).
 
-    Not here: the per-species SELF terms, a centre-of-mass reference frame, more than 8 species.
+    With ``self_terms=True``: ``results.timeseries_self`` (n_frames, S) = sum_{n in s} w_n^2 <v_n(0) . v_n(k dt)> (lag 0
+    kept), ``results.species_counts`` and ``results.species_weight2`` (S,); ``onsager_self_gk`` / ``onsager_self_gk_odd``
+    integrate it as ``onsager_gk`` does C; ``self_diffusivities``, ``conductivity_nernst_einstein(z)`` and
+    ``ionicity(z)`` read them.
+
+    Not here: a centre-of-mass reference frame, more than 8 species.
     """
+
+    _self_quantity = _lib.SELF_VACF
 
     _stage_arrays = ("velocities",)
     _no_data_message = ("Green-Kubo Onsager coefficient computation requires "
@@ -62,7 +73,8 @@ class OnsagerGreenKubo(CollectiveAnalysis):
     _by_particle_message = ("OnsagerGreenKubo has no per-particle result: the Onsager coefficients are collective "
                             "(by_particle=True is not supported)")
 
-    def __init__(self, atomgroup, species, temp_avg=300.0, dim_type="xyz", fft=True, *, weights=None, **kwargs):
+    def __init__(self, atomgroup, species, temp_avg=300.0, dim_type="xyz", fft=True, *, weights=None, self_terms=False,
+                 **kwargs):
         if "unwrap" in kwargs:
             raise TypeError(f"{type(self).__name__} reads velocities, which are not wrapped: unwrap is not accepted")
         super().__init__(atomgroup, temp_avg, dim_type, None, fft, False, kwargs)
@@ -71,7 +83,8 @@ class OnsagerGreenKubo(CollectiveAnalysis):
         self.species, self.species_index = index_species(self._per_atom(species, "species", "labels", dtype=None))
         self.n_species = max(int(self.species.size), 1)
         self.weights = None if weights is None else self._per_atom(weights, "weights", "values")
-        self._cross = None
+        self.self_terms = bool(self_terms)
+        self._cross = self._self = None
 
     def _set_options(self, dtype):
         # float32 staging stays float32 on the device, whatever the number of frames: k_species_current reads it as it is
@@ -83,8 +96,9 @@ class OnsagerGreenKubo(CollectiveAnalysis):
 
     def _prepare(self):
         super()._prepare()
-        self._cross = None
+        self._cross = self._self = None
         self._clear_results()
+        self._clear_self()
 
     def _clear_results(self):
         self.results.species = self.species
@@ -93,18 +107,24 @@ class OnsagerGreenKubo(CollectiveAnalysis):
     def _moments(self, fft, lo, hi, correlate):
         w = None if self.weights is None else self.weights[lo:hi]
         currents, cross = self._ctx.current(fft, self.species_index[lo:hi], self.n_species, w, cross=correlate)
+        if self.self_terms:
+            return (currents, self._self_sums(fft, lo, hi)), cross
         return (currents,), cross
 
     def _no_moments(self):
-        return (np.zeros((self.n_species, self.n_frames, self.dim_fac)),)
+        currents = np.zeros((self.n_species, self.n_frames, self.dim_fac))
+        return (currents, np.zeros((self.n_species, self.n_frames))) if self.self_terms else (currents,)
 
     def _correlate(self, fft, sums):
         return self._ctx.current_cross(sums[0], fft)
 
     def _store(self, sums, cross):
-        (self._currents,) = sums
+        self._currents = sums[0]
         self._cross = cross
         self._publish()
+        if self.self_terms:
+            self._self = sums[1]
+            self._store_self(self._self)
 
     def _publish(self):
         self.results.currents = self._currents
@@ -135,6 +155,47 @@ class OnsagerGreenKubo(CollectiveAnalysis):
 
         t, y = self._window(start, stop, step)
         return integrate.simpson(y=y, x=t, axis=0) * self._factor()
+
+    def _self_window(self, start, stop, step, what):
+        self._need_self(what)
+        if self._self is None:
+            raise RuntimeError("Analysis must be run prior to integrating the self terms")
+        stop = self.n_frames if stop == 0 else stop
+        sl = slice(start, stop, step)
+        return self.lag_times()[sl], self._self.T[sl]
+
+    def onsager_self_gk(self, start=0, stop=0, step=1):
+        """(S,) L_ii^self = trapezoid integral of ``timeseries_self`` over the lags ``[start:stop:step]`` x the factor of
+        ``onsager_gk``."""
+        t, y = self._self_window(start, stop, step, "onsager_self_gk()")
+        return (0.5 * (y[1:] + y[:-1]) * np.diff(t)[:, None]).sum(axis=0) * self._factor()
+
+    def onsager_self_gk_odd(self, start=0, stop=0, step=1):
+        """As ``onsager_self_gk`` by Simpson's rule."""
+        from scipy import integrate
+
+        t, y = self._self_window(start, stop, step, "onsager_self_gk_odd()")
+        return integrate.simpson(y=y, x=t, axis=0) * self._factor()
+
+    def self_diffusivities(self, start=0, stop=0, step=1, odd=False):
+        """(S,) self-diffusion coefficients in A^2 / ps: the integral of ``timeseries_self`` / (D sum_{n in s} w_n^2) --
+        with unit weights ``VelocityAutocorr.self_diffusivity_gk`` of the species' atoms; NaN for a species without
+        atoms."""
+        self._need_self("self_diffusivities()")
+        L = self.onsager_self_gk_odd(start, stop, step) if odd else self.onsager_self_gk(start, stop, step)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return L / self._factor() / (self.dim_fac * self.results.species_weight2)
+
+    def conductivity_nernst_einstein(self, z, start=0, stop=0, step=1, odd=False):
+        """sigma_NE = e^2 sum_i z_i^2 L_ii^self in S/m for one charge number per species."""
+        self._need_self("conductivity_nernst_einstein(z)")
+        L = self.onsager_self_gk_odd(start, stop, step) if odd else self.onsager_self_gk(start, stop, step)
+        return ELEMENTARY_CHARGE ** 2 * float((self._per_species(z) ** 2 * L).sum())
+
+    def ionicity(self, z, start=0, stop=0, step=1, odd=False):
+        """sigma / sigma_NE over the same window and rule."""
+        return (self.conductivity(z, start, stop, step, odd)
+                / self.conductivity_nernst_einstein(z, start, stop, step, odd))
 
     def running_integral(self):
         """(n_frames, S, S): the cumulative trapezoid integral of C over lag time in the units of ``onsager_gk`` -- the
@@ -169,7 +230,8 @@ class ConductivityGreenKubo(OnsagerGreenKubo):
     .. math:: \sigma = \frac{e^2}{D k_B <V> T_{avg}} \int <J(0) . J(t)> dt, \qquad J_{t, d} = \sum_n q_n v_{t, n, d}
 
     Parameters: ``atomgroup``, ``charges`` (one charge (e) per atom; default ``atomgroup.charges``), ``temp_avg``,
-    ``dim_type``, ``fft`` and the placement keywords, as for ``OnsagerGreenKubo``.
+    ``dim_type``, ``fft``, ``self_terms`` (``results.timeseries_self`` (n_frames, 1) = sum_n q_n^2 VACF_n: the
+    Nernst-Einstein part, ``conductivity_nernst_einstein([1])``) and the placement keywords, as for ``OnsagerGreenKubo``.
 
     Attributes
     ----------

@@ -14,11 +14,47 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _lib
 from ._base import CollectiveAnalysis
 from .conductivity import BOLTZMANN_J_PER_K, ELEMENTARY_CHARGE
 
 #: ta_hip.h: TA_ONSAGER_MAX_SPECIES
 MAX_SPECIES = 8
+
+
+class SelfTerms:
+    """What ``OnsagerHelfand`` and ``OnsagerGreenKubo`` share for ``self_terms=True``: the per-species self part
+    ``sum_{n in s} w_n^2 f_n`` (``ta_species_self``: one sorted pass over the slab, then one lag-sum call per species) as
+    a second array that adds up over atoms, beside the moments or currents."""
+
+    _self_quantity = None  # _lib.SELF_MSD or _lib.SELF_VACF
+
+    def _self_sums(self, fft, lo, hi):
+        """(S, n_frames) of the atoms [lo, hi)"""
+        w = None if self.weights is None else self.weights[lo:hi]
+        return self._ctx.species_self(self._self_quantity, fft, self.species_index[lo:hi], self.n_species, w)[0]
+
+    def _clear_self(self):
+        for key in ("timeseries_self", "species_counts", "species_weight2", "onsager_self", "onsager_distinct"):
+            self.results.pop(key, None)
+
+    def _store_self(self, self_sums):
+        """results.timeseries_self (n_frames, S), species_counts and species_weight2 = sum w^2 per species, of ALL atoms"""
+        S = self.n_species
+        w2 = np.ones(self.n_particles) if self.weights is None else self.weights ** 2
+        self.results.timeseries_self = np.ascontiguousarray(self_sums.T)
+        self.results.species_counts = np.bincount(self.species_index, minlength=S).astype(np.int64)
+        self.results.species_weight2 = np.bincount(self.species_index, weights=w2, minlength=S)
+
+    def _need_self(self, what):
+        if not self.self_terms:
+            raise ValueError(f"{what} needs the per-species self terms: pass self_terms=True")
+
+    def _per_species(self, z):
+        z = np.asarray(z, dtype=np.float64).ravel()
+        if z.size != self.n_species:
+            raise ValueError(f"z: {z.size} charges for {self.n_species} species")
+        return z
 
 
 def index_species(labels):
@@ -30,7 +66,7 @@ def index_species(labels):
     return species, np.ascontiguousarray(index, dtype=np.int32).ravel()
 
 
-class OnsagerHelfand(CollectiveAnalysis):
+class OnsagerHelfand(SelfTerms, CollectiveAnalysis):
     r"""Onsager transport coefficients of the species of a system by the Einstein-Helfand relation.
 
     .. math:: C_{ij}(k) = \frac{1}{T - k} \sum_{t < T - k} \sum_d (M_{i; t+k, d} - M_{i; t, d}) (M_{j; t+k, d} - M_{j; t, d}),
@@ -54,6 +90,9 @@ class OnsagerHelfand(CollectiveAnalysis):
         charges enter through ``conductivity(z)``).  With ``weights=charges`` and one species, ``moments[0]`` and
         ``timeseries[:, 0, 0]`` are ``ConductivityHelfand``'s moment and Phi.
     unwrap : bool, keyword-only, default False — as for ``ConductivityHelfand``.
+    self_terms : bool, keyword-only, default False — also compute the self part of every species,
+        ``sum_{n in s} w_n^2 MSD_n(k)``, in one more pass over the slab (``k_species_sort`` behind ``ta_species_self``)
+        and one MSD lag-sum call per species.
     device, devices, distributed, stage_dtype : keyword-only — as for ``EinsteinMSD``.  Under ``distributed=True``
         every rank forms the moments of its block of atoms with its slice of the labels; the moments are summed over
         ranks BEFORE the correlation.
@@ -66,9 +105,17 @@ class OnsagerHelfand(CollectiveAnalysis):
     results.onsager : (S, S) float64, only with ``linear_fit_window`` — L_ij = slope x 1e22 / (2 D k_B <V> T_avg) in
         (J m s)^-1 per particle^2 (A^2 / ps = 1e-8 m^2 / s, A^3 = 1e-30 m^3); divide by N_A^2 for mol^2 J^-1 m^-1 s^-1.
 
-    Not here: the per-species SELF terms (sum_{n in s} w_n^2 MSD_n: ``EinsteinMSD`` on the species' atoms, times their
-    number), a centre-of-mass reference frame.  The Green-Kubo (velocity) form is ``OnsagerGreenKubo``.
+    With ``self_terms=True``:
+    results.timeseries_self : (n_frames, S) float64 — sum_{n in s} w_n^2 MSD_n (A^2 times weight^2), lag 0 exactly 0.
+    results.species_counts, results.species_weight2 : (S,) — the atoms and sum w_n^2 of every species.
+    results.onsager_self : (S,) float64, only with ``linear_fit_window`` — L_ii^self, slope x the factor of ``onsager``.
+    results.onsager_distinct : (S, S) — ``onsager - diag(onsager_self)``.
+    ``self_diffusivities()``, ``conductivity_nernst_einstein(z)`` and ``ionicity(z)`` read them.
+
+    Not here: a centre-of-mass reference frame.  The Green-Kubo (velocity) form is ``OnsagerGreenKubo``.
     """
+
+    _self_quantity = _lib.SELF_MSD
 
     _no_data_message = ("Onsager coefficient computation requires "
                         "positions and box volume in the trajectory")
@@ -77,8 +124,9 @@ class OnsagerHelfand(CollectiveAnalysis):
                             "(by_particle=True is not supported)")
 
     def __init__(self, atomgroup, species, temp_avg=300.0, dim_type="xyz", linear_fit_window=None, fft=True, *,
-                 weights=None, unwrap=False, **kwargs):
+                 weights=None, unwrap=False, self_terms=False, **kwargs):
         super().__init__(atomgroup, temp_avg, dim_type, linear_fit_window, fft, unwrap, kwargs)
+        self.self_terms = bool(self_terms)
         if isinstance(species, str):
             species = getattr(atomgroup, species)
         self.species, self.species_index = index_species(self._per_atom(species, "species", "labels", dtype=None))
@@ -88,27 +136,37 @@ class OnsagerHelfand(CollectiveAnalysis):
     def _prepare(self):
         super()._prepare()
         self.results.pop("onsager", None)  # a fit of an earlier run
+        self._clear_self()
         self.results.species = self.species
         self.results.moments = self.results.timeseries = None
 
     def _moments(self, fft, lo, hi, correlate):
         w = None if self.weights is None else self.weights[lo:hi]
         moments, cross = self._ctx.onsager(fft, self.species_index[lo:hi], self.n_species, w, cross=correlate)
+        if self.self_terms:
+            return (moments, self._self_sums(fft, lo, hi)), cross
         return (moments,), cross
 
     def _no_moments(self):
-        return (np.zeros((self.n_species, self.n_frames, self.dim_fac)),)
+        moments = np.zeros((self.n_species, self.n_frames, self.dim_fac))
+        return (moments, np.zeros((self.n_species, self.n_frames))) if self.self_terms else (moments,)
 
     def _correlate(self, fft, sums):
         return self._ctx.onsager_cross(sums[0], fft)
 
     def _store(self, sums, cross):
-        (self.results.moments,) = sums
+        self.results.moments = sums[0]
         self.results.timeseries = cross
+        if self.self_terms:
+            self._store_self(sums[1])
         if self.linear_fit_window is not None:
             S = self.n_species
+            factor = 1e22 / (2 * self.dim_fac * BOLTZMANN_J_PER_K * self._vol_avg * self.temp_avg)
             slopes = np.array([[self._slope(cross[:, i, j]) for j in range(S)] for i in range(S)])
-            self.results.onsager = slopes * 1e22 / (2 * self.dim_fac * BOLTZMANN_J_PER_K * self._vol_avg * self.temp_avg)
+            self.results.onsager = slopes * factor
+            if self.self_terms:
+                self.results.onsager_self = np.array([self._slope(sums[1][s]) for s in range(S)]) * factor
+                self.results.onsager_distinct = self.results.onsager - np.diag(self.results.onsager_self)
 
     def _charge_weighted(self, z):
         if "onsager" not in self.results:
@@ -127,3 +185,27 @@ class OnsagerHelfand(CollectiveAnalysis):
         """t_i = z_i sum_j z_j L_ij / sum_kl z_k z_l L_kl, one per species; they add up to 1."""
         zlz = self._charge_weighted(z)
         return zlz.sum(axis=1) / zlz.sum()
+
+    def _fitted_self(self, what):
+        self._need_self(what)
+        if "onsager_self" not in self.results:
+            raise ValueError("the self terms need a fit: pass linear_fit_window=(lo, hi)")
+        return self.results.onsager_self
+
+    def self_diffusivities(self):
+        """(S,) self-diffusion coefficients in A^2 / ps: the slope of ``timeseries_self`` / (2 D sum_{n in s} w_n^2) --
+        with unit weights the ``EinsteinMSD`` slope / (2 D) of the species' atoms; NaN for a species without atoms."""
+        self._fitted_self("self_diffusivities()")
+        slopes = np.array([self._slope(self.results.timeseries_self[:, s]) for s in range(self.n_species)])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return slopes / (2 * self.dim_fac * self.results.species_weight2)
+
+    def conductivity_nernst_einstein(self, z):
+        """sigma_NE = e^2 sum_i z_i^2 L_ii^self in S/m for one charge number per species: with unit weights
+        ``ConductivityHelfand(nernst_einstein=True).results.conductivity_self`` for charges ``z[species]``."""
+        L = self._fitted_self("conductivity_nernst_einstein(z)")
+        return ELEMENTARY_CHARGE ** 2 * float((self._per_species(z) ** 2 * L).sum())
+
+    def ionicity(self, z):
+        """sigma / sigma_NE: 1 for uncorrelated ions, below 1 where ion pairs move together."""
+        return self.conductivity(z) / self.conductivity_nernst_einstein(z)
