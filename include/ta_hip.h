@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_unwrap / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -154,7 +154,9 @@ int ta_stage_synth(ta_ctx *ctx, int slab, uint64_t seed, int64_t col_offset, int
  * (<= 1024 * n_species * n_frames * dim * 8 bytes), the pair-major slab of the n_species^2 pseudo-particles and their
  * by-particle MSDs (n_species^2 * n_frames * (dim + 1) * 8 bytes); ta_current* use the same workspaces for the currents;
  * for ta_species_self* the weighted slab with each species' atoms contiguous (the input's element count * 8 bytes, plus at
- * most one column per species) beside what the lag-sum evaluation of one species needs;
+ * most one column per species) beside what the lag-sum evaluation of one species needs; for ta_compound its plan (12 bytes per
+ * member entry, 12 per compound) and, with frame weights, the (n_frames, dim) weighted mean and its partial sums (the
+ * ta_onsager workspace);
  * the labels, weights and outputs of host-facing calls are kept.                                                                                                            */
 int ta_trim(ta_ctx *ctx);
 
@@ -306,6 +308,35 @@ int ta_species_self(ta_ctx *ctx, int quantity, int fft, int n_species, const int
  * its element type (a TA_F32 slab holds the unwrapped positions rounded to float32, as NoJump's own output).
  * ta_group_unwrap (below, with the device groups): every member's block, with the same boxes.                       */
 int ta_unwrap(ta_ctx *ctx, int slab, const double *h_dimensions, const int *axes);
+
+/* ---- molecules instead of atoms: a staging transformation, like ta_unwrap -----------------------------------------
+ * ta_compound: replace staged slab 0, (n_frames, n_atoms, dim), by a float64 slab of (n_frames, n_compounds, dim):
+ *     out[t, c, d] = sum_{i in [h_offsets[c], h_offsets[c+1])} w_i x[t, h_members[i], d]  -  g_c F[t, d]
+ *     g_c = sum_i w_i,      F[t, d] = sum_{a < n_atoms} u_a x[t, a, d]
+ * w = h_weights, one per MEMBER ENTRY (NULL: all 1; weights that add up to 1 per compound give its weighted centre, masses /
+ * the molecule's mass its centre of mass); u = h_frame_weights, one per atom (NULL: no F term at all; masses / the total mass
+ * put the compounds into the barycentric frame of the system).  h_offsets: n_compounds + 1 entries, starting at 0, strictly
+ * increasing (no empty compound), the last one = the number of member entries, below 2^31.  Members lie in 0 ... n_atoms - 1,
+ * in any order, interleaved across compounds or not; an atom no compound names is dropped.
+ *   Afterwards the context's staged shape is that of the new slab (same pitch, float64 elements whatever the old slab
+ * held); the old device slab is freed once the call has completed and the pinned host slabs are released as by
+ * ta_stage_free.  ta_stage_frame and ta_stage_commit* return TA_E_STATE until the next ta_stage_alloc*;
+ * ta_stage_device, ta_stage_read_dev, ta_unwrap and every compute entry point see the new slab (ta_msd divides by
+ * n_compounds).  Works on slabs filled by ta_stage_commit, ta_stage_commit_dev or ta_stage_synth.
+ *   A compound's sum runs in member order in float64 (the first product as it is, every further term one fma; with F the
+ * result is fma(-g_c, F, sum)); no atomics, one writer per element: the same bits from run to run.  Without frame weights a
+ * one-member compound of weight 1 is its atom's column bit for bit.  The rows n_frames ... pitch - 1 of every pair and the
+ * phantom column of an odd n_compounds * dim are written as zeros.  ONE pass over the slab in the element type it has
+ * (k_compound, compound.hip: a float32 slab is read as float32 and widened in registers); F is formed first by
+ * k_species_current with one species and its fixed-order partial sums.
+ *   NULL h_offsets / h_members, bad offsets, a member out of range, n_compounds < 1 (checked on the host before anything is
+ * written): TA_E_INVALID; nothing staged: TA_E_STATE; more than one staged slab: TA_E_UNSUPPORTED; n_atoms * dim and
+ * n_compounds * dim must be below 2^31.  Blocking; recorded as a compute call (k_compound is the main kernel; the timeline
+ * shows k_species_current first when F is asked for).  h_out (may be NULL): on a GPU context *h_out = NULL; on the CPU
+ * backend *h_out = the new host slab, (n_frames, n_compounds, dim) float64 row-major, valid until the next ta_stage_alloc /
+ * ta_stage_free (the same arithmetic and member order, parallel over compounds).                                        */
+int ta_compound(ta_ctx *ctx, int64_t n_compounds, const int64_t *h_offsets, const int32_t *h_members,
+                const double *h_weights, const double *h_frame_weights, void **h_out);
 
 /* ---- compute on caller-provided device memory (asynchronous) -----------
  * Same arithmetic as above on a device-resident FRAME-MAJOR shard: d_vel / d_pos are

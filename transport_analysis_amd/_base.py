@@ -242,6 +242,12 @@ class StagedAnalysis(AnalysisBase):
     on the device (MDAnalysis' ``NoJump``, ``ta_unwrap``) after the last commit and before ``_evaluate``,
     on every placement (each rank or device member unwraps its own atoms: no communication).
 
+    A subclass with ``_accepts_compound`` takes ``compound``, ``compound_weights`` and ``reference_frame`` and calls
+    ``_init_compound()`` once ``self._group`` and ``self.n_particles`` are set: the frames are still staged (and unwrapped)
+    as ATOMS, then ``_conclude`` replaces the slab by the slab of the compounds' weighted centres (``ta_compound``), and
+    ``n_particles``, the by-particle result and every mean are those of the compounds.  A class without it leaves the three
+    keywords to ``AnalysisBase``, which rejects them like any unknown keyword.
+
     No method here may take a name of MDAnalysis' ``AnalysisBase`` hooks: from 2.8 on its ``run()``
     calls ``self._compute(indexed_frames, ...)``, so ``_compute`` is theirs."""
 
@@ -250,6 +256,7 @@ class StagedAnalysis(AnalysisBase):
     _no_data_message = None     # NoDataError text of a frame _has_data rejects
     _unwrap = False             # unwrap the staged positions (NoJump) before _evaluate
     _record_volumes = False     # record every frame's ts.volume; _evaluate finds their mean in self._vol_avg
+    _accepts_compound = False   # takes compound / compound_weights / reference_frame (the subclass calls _init_compound)
 
     # MDAnalysis >= 2.8 parallel-analysis protocol: frames are staged into ONE device slab per
     # analysis object and every lag couples all frames, so a frame-split backend cannot apply;
@@ -264,12 +271,75 @@ class StagedAnalysis(AnalysisBase):
         self._want_by_particle = bool(kwargs.pop("by_particle", True))
         self._stage_dtype = kwargs.pop("stage_dtype", None)
         self._distributed, self._devices, self._device = pop_device_options(kwargs)
+        self._plan = None  # (offsets, members, member weights, frame weights or None) of ta_compound
+        if self._accepts_compound:
+            # (compound_weights="mass", the default, asks for nothing by itself)
+            given = [k for k in ("compound", "compound_weights", "reference_frame")
+                     if kwargs.get(k) is not None and not (k == "compound_weights" and isinstance(kwargs[k], str) and kwargs[k] == "mass")]
+            if given and (self._devices is not None or self._distributed):
+                raise ValueError(f"{', '.join(given)}: not available with devices=[...] or distributed=True -- the atoms are "
+                                 "split over the GPUs by index, and all atoms of a molecule would have to share a shard")
+            self._compound = kwargs.pop("compound", None)
+            self._compound_weights = kwargs.pop("compound_weights", "mass")
+            self._reference_frame = kwargs.pop("reference_frame", None)
+            if self._reference_frame not in (None, "barycentric"):
+                raise ValueError(f"reference_frame: {self._reference_frame!r}, expected None or 'barycentric'")
         self._pop_options(kwargs)
         super().__init__(group.universe.trajectory, **kwargs)
         self._ctx = None
 
     def _pop_options(self, kwargs):
         """Pop (and check) the subclass's own keywords before AnalysisBase sees the rest."""
+
+    def _group_attr(self, attr, what):
+        try:
+            return np.asarray(getattr(self._group, attr))
+        except Exception as err:  # (MDAnalysis: NoDataError, an AttributeError subclass)
+            raise ValueError(f"{what} needs the group's '{attr}', and it has none ({err})") from err
+
+    def _init_compound(self):
+        """The plan of ``ta_compound`` from the three keywords; ``n_particles`` becomes the number of compounds and
+        ``_compound_index`` the compound of every atom.  Without ``compound`` and ``reference_frame`` nothing changes."""
+        self._n_atoms = self.n_particles
+        self.compound, self.reference_frame = self._compound, self._reference_frame
+        if self._compound is None and self._reference_frame is None:
+            return
+        from .compound import COMPOUND_ATTRS, compound_plan
+
+        n = self._n_atoms
+        if self._compound is None:  # every atom its own compound: the frame of reference alone
+            ids, offsets = np.arange(n), np.arange(n + 1, dtype=np.int64)
+            members, weights = np.arange(n, dtype=np.int32), None
+        else:
+            if isinstance(self._compound, str):
+                if self._compound not in COMPOUND_ATTRS:
+                    raise ValueError(f"compound: {self._compound!r}, expected one of {sorted(COMPOUND_ATTRS)} or one integer "
+                                     "label per atom")
+                labels = self._group_attr(COMPOUND_ATTRS[self._compound], f"compound={self._compound!r}")
+            else:
+                labels = np.asarray(self._compound)
+                if labels.ndim != 1 or labels.size != n or not np.issubdtype(labels.dtype, np.integer):
+                    raise ValueError(f"compound: one integer label per atom is expected ({n} atoms), got an array of shape "
+                                     f"{labels.shape} and dtype {labels.dtype}")
+            cw = self._compound_weights
+            if isinstance(cw, str):
+                if cw not in ("mass", "geometry"):
+                    raise ValueError(f"compound_weights: {cw!r}, expected 'mass', 'geometry' or one value per atom")
+                per_atom = self._group_attr("masses", "compound_weights='mass'") if cw == "mass" else np.ones(n)
+            else:
+                per_atom = np.asarray(cw, dtype=np.float64).ravel()
+            ids, offsets, members, weights = compound_plan(labels, per_atom)
+        frame = None
+        if self._reference_frame == "barycentric":
+            m = self._group_attr("masses", "reference_frame='barycentric'").astype(np.float64)
+            if m.size != n or not m.sum() > 0:
+                raise ValueError("reference_frame='barycentric' needs masses with a positive sum, one per atom")
+            frame = m / m.sum()
+        self._plan = (offsets, members, weights, frame)
+        self._compound_ids = ids
+        self._compound_index = np.empty(n, dtype=np.int64)
+        self._compound_index[members] = np.repeat(np.arange(ids.size), np.diff(offsets))
+        self.n_particles = int(ids.size)
 
     def _pick_stage_dtype(self):
         """float32 when the trajectory hands out every staged array in float32 (MDAnalysis does):
@@ -286,7 +356,9 @@ class StagedAnalysis(AnalysisBase):
         """Pinned host slabs + device slabs instead of the reference's ``np.zeros`` arrays."""
         if self._ctx is None:
             self._ctx = open_context(self._devices, self._device)
-        self._lo, self._hi = 0, self.n_particles
+        # staging is sized by the atoms, everything after ta_compound by the compounds (n_particles)
+        n_stage = self._n_atoms if self._plan is not None else self.n_particles
+        self._lo, self._hi = 0, n_stage
         self._source = self._group  # whose arrays a frame is read from
         self._rccl = False  # the lag sums stay on the GPU through the reduce
         if self._distributed:
@@ -328,7 +400,10 @@ class StagedAnalysis(AnalysisBase):
         self._volumes = np.zeros(self.n_frames) if self._record_volumes else None
         self._bp_home = None
         if self._want_by_particle and self._n_local and not self._rccl:
-            self._bp_home = self._ctx.result_home((self.n_frames, self._n_local))
+            n_out = self.n_particles if self._plan is not None else self._n_local
+            self._bp_home = self._ctx.result_home((self.n_frames, n_out))
+        if self._plan is not None:
+            self.results.compound_ids = self._compound_ids
 
     def _single_frame(self):
         """Stage the selected columns of one frame's arrays."""
@@ -378,6 +453,8 @@ class StagedAnalysis(AnalysisBase):
                 self._ctx.unwrap(self._stage_arrays.index("positions"), self._boxes, self._dim)
         if self._volumes is not None:
             self._vol_avg = np.average(self._volumes)
+        if self._plan is not None:  # after the unwrap, which must see atoms: molecules from here on
+            self._ctx.compound(*self._plan)
         self._evaluate()
 
     def _run_kernels(self, host, launch):
@@ -436,13 +513,30 @@ class CollectiveAnalysis(StagedAnalysis):
         self.fft = fft
         self.atomgroup = self._group = atomgroup
         self.n_particles = len(self.atomgroup)
+        if self._accepts_compound:
+            self._init_compound()
 
     def _per_atom(self, values, name, unit, dtype=np.float64):
-        """One value per atom of the group as a flat array, or the ValueError that says how many there are."""
+        """One value per atom of the group (with ``compound``: per compound) as a flat array, or the ValueError that says
+        how many there are."""
         a = np.asarray(values, dtype=dtype).ravel()
         if a.size != self.n_particles:
-            raise ValueError(f"{name}: {a.size} {unit} for {self.n_particles} atoms")
+            what = "atoms" if self._plan is None or self._compound is None else "compounds"
+            raise ValueError(f"{name}: {a.size} {unit} for {self.n_particles} {what}")
         return a
+
+    def _species_labels(self, species):
+        """One species label per particle: with ``compound`` one per compound, or one per atom that is the same within
+        every compound (``species="resnames"``)."""
+        # a topology attribute, or a subclass's own per-atom labels: certainly one label per atom
+        named = isinstance(species, str) or getattr(self, "_species_per_atom", False)
+        if isinstance(species, str):
+            species = getattr(self.atomgroup, species)
+        if self._plan is not None and self._compound is not None:
+            from .compound import per_compound
+
+            return per_compound(species, self._compound_index, self.n_particles, "species", per_atom=True if named else None)
+        return self._per_atom(species, "species", "labels", dtype=None)
 
     def _set_options(self, dtype):
         self._ctx.set_option("stage_device_f32", 0)

@@ -62,6 +62,7 @@ _API = {
     "ta_current_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_species_self": _SELF, "ta_species_self_staged": _int(_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp),
     "ta_species_self_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _ci, _vp, _vp, _vp, _vp),
+    "ta_compound": _int(_vp, _i64, _vp, _vp, _vp, _vp, _P(_vp)),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
     "ta_helfand_msd_dev": _int(_vp, _vp, _vp, _vp, _i64, _i64, _ci, _i64, _dbl, _vp, _vp, _i64, _vp),
     "ta_msd_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _vp, _i64, _vp),
@@ -534,6 +535,32 @@ class Context(_Staged):
 
     def trim(self):
         self._call("trim")
+
+    def compound(self, offsets, members, weights=None, frame_weights=None):
+        """Replace staged slab 0 by the float64 slab of its compounds (ta_compound): compound c = the member entries
+        [offsets[c], offsets[c + 1]) of `members` (atom indices, in any order), `weights` one per member entry or None (all
+        1), `frame_weights` one per staged atom or None: their weighted mean over all atoms is subtracted (times the
+        compound's weight sum).  The context's shape becomes (n_frames, n_compounds, dim) and the host views are dropped:
+        nothing can be staged until the next stage_alloc.  Returns the new host slab's view on a CPU context, else None."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+        mem = np.ascontiguousarray(members, dtype=np.int32).ravel()
+        n = int(off.size) - 1
+        if n >= 1 and int(off[-1]) != mem.size:
+            raise ValueError(f"compound: offsets end at {int(off[-1])}, and there are {mem.size} member entries")
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        if w is not None and w.size != mem.size:
+            raise ValueError(f"compound: {w.size} weights for {mem.size} member entries")
+        u = self._per_atom(frame_weights, np.float64, "frame_weights", "values")
+        out = ctypes.c_void_p()
+        self._call("compound", n, _ptr(off), _ptr(mem), _ptr(w), _ptr(u), ctypes.byref(out))
+        T, _, D = self._staged_shape()
+        self._drop_views()
+        self._staged(T, n, D)
+        if not out.value:
+            return None
+        view = _slab_view(out.value, np.float64, (T, n, D))
+        self._slabs = [view]  # dropped (made read-only) with the slab, like the staging views
+        return view
 
     def moment_msd(self, moment, fft):
         """Phi(k) of a (n_frames, dim) moment, e.g. the sum of several shards' moments: the moment is staged as a

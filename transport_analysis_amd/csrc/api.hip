@@ -10,6 +10,7 @@
 #include <deque>
 #include <initializer_list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <stdexcept>
@@ -142,6 +143,9 @@ struct ta_ctx {
     DevBuf self_w{workspaces, kTrimmed}, self_order{workspaces, kKept}, self_out{workspaces, kKept};
     std::vector<int32_t> self_order_h;
     hipEvent_t ev_order = nullptr;
+    // ta_compound: the plan (offsets, members, member weights, their sums per compound) and the (n_frames, dim) weighted
+    // mean F of the barycentric term; the per-atom frame weights and F's partial sums use the Onsager workspaces
+    DevBuf comp_plan{workspaces, kTrimmed}, comp_f{workspaces, kTrimmed};
     // staging: two landing buffers, so that a piece crosses PCIe while the one before it is transposed
     DevBuf bounce{workspaces, kTrimmed}, bounce2{workspaces, kTrimmed};
     DevBuf clock_stamps{workspaces, kTrimmed};  // ta_clock_probe: the stamps of its last launch
@@ -151,6 +155,7 @@ struct ta_ctx {
     int64_t st_T = 0, st_A = 0, st_pitch = 0;
     int st_D = 0, st_dtype = TA_F64, st_nslabs = 0;
     bool st_dev_f32 = false;  // device slabs hold float32 elements ("stage_device_f32")
+    bool st_compound = false;  // slab 0 is ta_compound's: nothing can be staged into it (until the next ta_stage_alloc*)
     std::vector<void*> h_slabs;
     std::vector<HostBlock> h_blocks;  // the mapping behind h_slabs[i] (base == NULL: a hipHostMalloc block, the fallback)
     std::vector<double*> d_slabs;
@@ -223,6 +228,10 @@ int check_staged(ta_ctx* ctx, int n_slabs = 1) {
 }
 int check_slab(ta_ctx* ctx, int slab) {
     return slab >= 0 && slab < ctx->st_nslabs ? TA_OK : fail(ctx, TA_E_INVALID, "no such slab");
+}
+int check_not_compound(ta_ctx* ctx) {
+    return !ctx->st_compound ? TA_OK
+                             : fail(ctx, TA_E_STATE, "the staged slab holds ta_compound's compounds: ta_stage_alloc comes before frames can be staged again");
 }
 int check_frames(ta_ctx* ctx, int64_t frame_lo, int64_t frame_hi) {
     if (frame_lo < 0 || frame_hi > ctx->st_T || frame_lo > frame_hi) return fail(ctx, TA_E_INVALID, "frame range out of bounds");
@@ -1223,6 +1232,7 @@ int ta_stage_free(ta_ctx* ctx) {
     ctx->d_slabs.clear();
     ctx->st_nslabs = 0;
     ctx->st_T = ctx->st_A = ctx->st_pitch = 0;
+    ctx->st_compound = false;
     return TA_OK;
     });
 }
@@ -1574,6 +1584,7 @@ int ta_stage_commit(ta_ctx* ctx, int64_t frame_lo, int64_t frame_hi) {
     return ta::guarded(fail, ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
     if (ctx->st_nslabs == 0) return fail(ctx, TA_E_STATE, "ta_stage_alloc has not been called");
+    TA_CHECK(check_not_compound(ctx));
     TA_CHECK(check_frames(ctx, frame_lo, frame_hi));
     if (!ctx->h_slabs[0]) return fail(ctx, TA_E_STATE, "device-only slabs: use ta_stage_commit_dev");
     if (frame_hi == frame_lo) return TA_OK;
@@ -1593,6 +1604,7 @@ int ta_stage_commit_dev(ta_ctx* ctx, int slab, const void* d_src, int dtype, int
     if (!ctx || !d_src) return fail(ctx, TA_E_INVALID, "null argument");
     TA_NO_CPU(ctx);
     TA_CHECK(check_slab(ctx, slab));
+    TA_CHECK(check_not_compound(ctx));
     TA_CHECK(check_dtype(ctx, dtype));
     TA_CHECK(check_frames(ctx, frame_lo, frame_hi));
     TA_CHECK(check_ld_row(ctx, ld_row, ctx->st_A * ctx->st_D));
@@ -2215,6 +2227,7 @@ int ctx_fail(ta_ctx* ctx, int code, const std::string& msg) { return fail(ctx, c
 int ctx_host_slab(ta_ctx* ctx, int slab, void** h, int64_t* T, int64_t* A, int* D, int* dtype) {
     TA_CHECK(need_ctx(ctx));
     TA_CHECK(check_slab(ctx, slab));
+    TA_CHECK(check_not_compound(ctx));
     if (!ctx->h_slabs[slab]) return fail(ctx, TA_E_STATE, "device-only slabs have no host side to fill");
     *h = ctx->h_slabs[slab], *T = ctx->st_T, *A = ctx->st_A, *D = ctx->st_D, *dtype = ctx->st_dtype;
     return TA_OK;
@@ -2362,6 +2375,123 @@ int ta_species_self(ta_ctx* ctx, int quantity, int fft, int n_species, const int
     double* d_out = nullptr;
     TA_CHECK(ta::self_launch(ctx, quantity, fft, n_species, h_species, h_weights, h_counts, &d_out));
     return host_finish(ctx, {{h_self, d_out, (size_t)n_species * (size_t)ctx->st_T}});
+    });
+}
+
+// The host slabs of a context go away (ta_compound: they hold atoms, the staged slab no longer does)
+static void release_host_slabs(ta_ctx* ctx) {
+    for (size_t i = 0; i < ctx->h_slabs.size(); ++i) {
+        if (ctx->h_blocks[i].base) host_block_unmap(ctx->h_blocks[i]);
+        else if (ctx->h_slabs[i]) hipHostFree(ctx->h_slabs[i]);
+        ctx->h_blocks[i] = HostBlock{};
+        ctx->h_slabs[i] = nullptr;
+    }
+}
+
+int ta_compound(ta_ctx* ctx, int64_t n_compounds, const int64_t* h_offsets, const int32_t* h_members, const double* h_weights,
+                const double* h_frame_weights, void** h_out) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    if (h_out) *h_out = nullptr;
+    if (!h_offsets || !h_members) return fail(ctx, TA_E_INVALID, "compound: offsets or members are NULL");
+    if (n_compounds < 1) return fail(ctx, TA_E_INVALID, "compound: need n_compounds >= 1");
+    TA_CHECK(check_staged(ctx));
+    if (ctx->st_nslabs != 1) return fail(ctx, TA_E_UNSUPPORTED, "compound: one staged slab only (this context holds " + std::to_string(ctx->st_nslabs) + ")");
+    const int64_t T = ctx->st_T, A = ctx->st_A, C = n_compounds;
+    const int D = ctx->st_D;
+    if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "compound: n_atoms * dim must be below 2^31");
+    if (C * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "compound: n_compounds * dim must be below 2^31");
+    if (h_offsets[0] != 0) return fail(ctx, TA_E_INVALID, "compound: offsets must start at 0");
+    for (int64_t c = 0; c < C; ++c)
+        if (h_offsets[c + 1] <= h_offsets[c] || h_offsets[c + 1] >= (int64_t)1 << 31)
+            return fail(ctx, TA_E_INVALID, "compound: offsets must be strictly increasing (no empty compound) and end below 2^31 (compound " + std::to_string(c) + ")");
+    const int64_t M = h_offsets[C];
+    for (int64_t i = 0; i < M; ++i)
+        if (h_members[i] < 0 || h_members[i] >= A)
+            return fail(ctx, TA_E_INVALID, "compound: member " + std::to_string(h_members[i]) + " (entry " + std::to_string(i) + ") is outside 0 ... n_atoms - 1");
+    const size_t out_elems = (size_t)T * (size_t)C * (size_t)D;
+    if (ctx->is_cpu) {
+        HostBlock blk;
+        if (host_block_map(out_elems * sizeof(double), &blk) != 0) return fail(ctx, TA_E_NOMEM, "compound: no host memory for the new slab");
+        if (int rc = ta::cpu::compound(cpu_state(ctx), C, h_offsets, h_members, h_weights, h_frame_weights, (double*)blk.base)) {
+            host_block_unmap(blk);
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        }
+        release_host_slabs(ctx);
+        ctx->h_slabs[0] = blk.base, ctx->h_blocks[0] = blk;
+        set_staged(ctx, T, C, D, TA_F64, 1, false);
+        ctx->st_compound = true;
+        if (h_out) *h_out = blk.base;
+        return TA_OK;
+    }
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the plan as the kernel reads it: int32 offsets and members, float64 member weights and their sums in member order
+    const size_t n_off = (size_t)C + 1, n_int = (n_off + (size_t)M + 1) / 2 * 2;
+    const size_t n_dbl = (h_weights ? (size_t)M : 0) + (size_t)C;
+    std::vector<double> plan(n_int / 2 + n_dbl);
+    int32_t* p_off = reinterpret_cast<int32_t*>(plan.data());
+    int32_t* p_mem = p_off + n_off;
+    double* p_w = plan.data() + n_int / 2;
+    double* p_g = p_w + (h_weights ? (size_t)M : 0);
+    for (size_t c = 0; c < n_off; ++c) p_off[c] = (int32_t)h_offsets[c];
+    std::copy(h_members, h_members + M, p_mem);
+    if (h_weights) std::copy(h_weights, h_weights + M, p_w);
+    for (int64_t c = 0; c < C; ++c) {
+        double g = 0.0;
+        for (int64_t i = h_offsets[c]; i < h_offsets[c + 1]; ++i) g += h_weights ? h_weights[i] : 1.0;
+        p_g[c] = g;
+    }
+    hipStream_t st = ctx->stream;
+    const int64_t pitch = ctx->st_pitch, n_cols = A * D;
+    double* d_new = nullptr;
+    TA_HIP_TRY(ctx, hipMalloc((void**)&d_new, pm_bytes(T, C * D)));
+    struct DevFree {
+        void operator()(void* p) const { hipFree(p); }
+    };
+    std::unique_ptr<void, DevFree> fresh(d_new);  // (an exception below: host_call waits, then this frees)
+    // everything queued from here on is waited for before the plan's host copy, or on failure the new slab, goes away
+    const int rc = [&]() -> int {
+        TA_CHECK(ensure(ctx, ctx->comp_plan, sizeof(double) * plan.size()));
+        TA_CHECK(order_after_staging(ctx, st));
+        TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->comp_plan.p, plan.data(), sizeof(double) * plan.size(), hipMemcpyHostToDevice, st));
+        const int* d_off = (const int*)ctx->comp_plan.p;
+        const double* d_w = (const double*)ctx->comp_plan.p + n_int / 2;
+        const double* d_F = nullptr;
+        if (h_frame_weights) {  // F = the one-species "current" of the slab with w = u: the slab read as it is
+            const int n_parts = species_moment_parts(ctx->n_cu, 1, (long)T, (long)n_cols);
+            TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)n_parts * T * D));
+            TA_CHECK(ensure(ctx, ctx->ons_lab, sizeof(int32_t) * (size_t)A));
+            TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * (size_t)A));
+            TA_CHECK(ensure(ctx, ctx->comp_f, sizeof(double) * (size_t)T * D));
+            TA_HIP_TRY(ctx, hipMemsetAsync(ctx->ons_lab.p, 0, sizeof(int32_t) * (size_t)A, st));
+            TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_w.p, h_frame_weights, sizeof(double) * (size_t)A, hipMemcpyHostToDevice, st));
+            d_F = (const double*)ctx->comp_f.p;
+        }
+        TA_CHECK(call_begin(ctx, st));
+        if (d_F) {
+            const int n_parts = species_moment_parts(ctx->n_cu, 1, (long)T, (long)n_cols);
+            TA_LAUNCH(ctx, "k_species_current", st,
+                      launch_species_current(ctx->d_slabs[0], ctx->st_dev_f32, (long)pitch, (long)T, (long)n_cols, D, 1,
+                                             (const int*)ctx->ons_lab.p, (const double*)ctx->ons_w.p, (double*)ctx->ons_part.p,
+                                             n_parts, st));
+            TA_LAUNCH(ctx, "k_sum_partials", st,
+                      launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)(T * D), (double*)ctx->comp_f.p, st));
+        }
+        TA_LAUNCH_MAIN(ctx, "k_compound", st,
+                       launch_compound(ctx->n_cu, ctx->d_slabs[0], ctx->st_dev_f32, (long)pitch, (long)T, (long)n_cols, D, (long)C,
+                                       d_off, d_off + n_off, h_weights ? d_w : nullptr, d_w + (h_weights ? (size_t)M : 0), d_F,
+                                       d_new, st));
+        return call_end(ctx, st);
+    }();
+    const int rc_wait = host_wait(ctx);
+    if (rc || rc_wait) return rc ? rc : rc_wait;
+    // the call has completed: the old device slab and the host slabs (they hold atoms) go
+    hipFree(ctx->d_slabs[0]);
+    ctx->d_slabs[0] = (double*)fresh.release();
+    release_host_slabs(ctx);
+    set_staged(ctx, T, C, D, ctx->st_dtype, 1, false);
+    ctx->st_compound = true;
+    return TA_OK;
     });
 }
 

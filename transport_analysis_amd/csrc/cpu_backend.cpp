@@ -566,6 +566,46 @@ int species_self(const State& s, bool msd_quantity, bool fft, int S, const int32
 }
 
 template <class E>
+int compound_t(const State& s, int64_t C, const int64_t* off, const int32_t* members, const double* w, const double* u,
+               double* out) {
+    const int64_t T = s.T, A = s.A;
+    const int D = s.D;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    std::vector<double> F;
+    if (u) {
+        try {
+            F.assign((size_t)T * D, 0.0);
+        } catch (const std::bad_alloc&) {
+            return TA_E_NOMEM;
+        }
+#pragma omp parallel for num_threads(s.threads) schedule(static)
+        for (int64_t t = 0; t < T; ++t)
+            for (int64_t a = 0; a < A; ++a)
+                for (int d = 0; d < D; ++d) F[(size_t)t * D + d] = std::fma(u[a], (double)x[((size_t)t * A + a) * D + d], F[(size_t)t * D + d]);
+    }
+#pragma omp parallel for num_threads(s.threads) schedule(dynamic, 16)
+    for (int64_t c = 0; c < C; ++c) {
+        double g = 0.0;
+        for (int64_t i = off[c]; i < off[c + 1]; ++i) g += w ? w[i] : 1.0;
+        for (int64_t t = 0; t < T; ++t) {
+            double acc[3] = {0.0, 0.0, 0.0};
+            for (int64_t i = off[c]; i < off[c + 1]; ++i) {
+                const double wi = w ? w[i] : 1.0;
+                const E* row = x + ((size_t)t * A + members[i]) * D;
+                for (int d = 0; d < D; ++d) acc[d] = i == off[c] ? wi * (double)row[d] : std::fma(wi, (double)row[d], acc[d]);
+            }
+            double* o = out + ((size_t)t * C + c) * D;
+            for (int d = 0; d < D; ++d) o[d] = u ? std::fma(-g, F[(size_t)t * D + d], acc[d]) : acc[d];
+        }
+    }
+    return TA_OK;
+}
+
+int compound(const State& s, int64_t C, const int64_t* off, const int32_t* members, const double* w, const double* u, double* out) {
+    return s.dtype == TA_F32 ? compound_t<float>(s, C, off, members, w, u, out) : compound_t<double>(s, C, off, members, w, u, out);
+}
+
+template <class E>
 void unwrap_t(const State& s, int slab, const BoxTable& box, const int* axes) {
     const int64_t T = s.T, A = s.A, tp = box.per_frame ? box.tpitch : 0;
     const int D = s.D;

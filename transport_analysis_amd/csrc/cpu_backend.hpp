@@ -43,6 +43,11 @@ int current_cross(int threads, bool fft, const double* currents, int n_species, 
 // msd() / vacf_fft() / vacf_direct() on it; counts (n_species) or NULL; a species without atoms: zeros
 int species_self(const State& s, bool msd_quantity, bool fft, int n_species, const int32_t* species, const double* w,
                  double* self, int64_t* counts);
+// ta_compound: out (n_frames, n_compounds, dim) float64 = sum_{i in [offsets[c], offsets[c + 1])} w_i x[t, members[i], d] -
+// g_c F[t, d] of slab 0 (g_c = sum_i w_i, F = sum_a u_a x[t, a, d]; frame_weights NULL: no such term; weights NULL: all 1),
+// the sum in member order (the first product, then fma), parallel over compounds; arguments checked by the caller
+int compound(const State& s, int64_t n_compounds, const int64_t* offsets, const int32_t* members, const double* weights,
+             const double* frame_weights, double* out);
 // ta_unwrap on host slab `slab` in place (box, axes checked by the caller)
 void unwrap(const State& s, int slab, const BoxTable& box, const int* axes);
 

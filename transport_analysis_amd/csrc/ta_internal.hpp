@@ -229,6 +229,14 @@ void species_sort_plan(const int32_t* h_species, int64_t n_atoms, int D, int S, 
 hipError_t launch_species_sort(int n_cu, const void* x, bool f32, long pitch, long T, long n_cols, int D, const SortPlan& plan,
                                const int* order, const double* w, bool shift, double* W, hipStream_t st);
 
+// compound.hip: the float64 pair-major slab of n_compounds compounds of a pair-major slab of float64 or (f32) float32 elements,
+// read as it is: out[t, D c + d] = sum_{i in [off[c], off[c + 1])} w_i x[t, D member[i] + d] - g[c] F[t, d], in member order.
+// off (n_compounds + 1), member, w (or NULL: all 1; one per member entry), g (n_compounds) and F ((T, D), or NULL: no such
+// term) are device arrays; out has (n_compounds D + 1) / 2 pairs of `pitch` rows, every one of them written.
+hipError_t launch_compound(int n_cu, const void* x, bool f32, long pitch, long T, long n_cols, int D, long n_compounds,
+                           const int* off, const int* member, const double* w, const double* g, const double* F, double* out,
+                           hipStream_t st);
+
 // unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
 // box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)
 hipError_t launch_unwrap(double* slab, long pitch, long T, long n_atoms, int D, const int* axes, bool triclinic,

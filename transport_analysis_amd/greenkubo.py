@@ -45,6 +45,10 @@ class OnsagerGreenKubo(SelfTerms, CollectiveAnalysis):
     device, devices, distributed, stage_dtype : keyword-only — as for ``VelocityAutocorr``.  float32 staging stays float32
         on the device at every number of frames: the current pass reads it as it is.  Under ``distributed=True`` every
         rank forms the currents of its block of atoms; they are summed over ranks BEFORE the correlation.
+    compound, compound_weights, reference_frame : keyword-only — as for ``OnsagerHelfand``: the currents and self terms
+        of the centre-of-mass velocities of molecules or ions, in the laboratory or the barycentric frame (the staged
+        velocities minus the mass-weighted mean velocity of the group).  ``species`` and ``weights`` are then per compound
+        (``species`` may also be given per atom, the same within every compound).  A float32 slab is read as it is.
     ``unwrap`` is not accepted: velocities are not wrapped.
 
     Attributes
@@ -61,10 +65,11 @@ class OnsagerGreenKubo(SelfTerms, CollectiveAnalysis):
     integrate it as ``onsager_gk`` does C; ``self_diffusivities``, ``conductivity_nernst_einstein(z)`` and
     ``ionicity(z)`` read them.
 
-    Not here: a centre-of-mass reference frame, more than 8 species.
+    Not here: more than 8 species.
     """
 
     _self_quantity = _lib.SELF_VACF
+    _accepts_compound = True
 
     _stage_arrays = ("velocities",)
     _no_data_message = ("Green-Kubo Onsager coefficient computation requires "
@@ -78,13 +83,14 @@ class OnsagerGreenKubo(SelfTerms, CollectiveAnalysis):
         if "unwrap" in kwargs:
             raise TypeError(f"{type(self).__name__} reads velocities, which are not wrapped: unwrap is not accepted")
         super().__init__(atomgroup, temp_avg, dim_type, None, fft, False, kwargs)
-        if isinstance(species, str):
-            species = getattr(atomgroup, species)
-        self.species, self.species_index = index_species(self._per_atom(species, "species", "labels", dtype=None))
+        self.species, self.species_index = index_species(self._species_labels(species))
         self.n_species = max(int(self.species.size), 1)
-        self.weights = None if weights is None else self._per_atom(weights, "weights", "values")
+        self.weights = None if weights is None else self._particle_weights(weights)
         self.self_terms = bool(self_terms)
         self._cross = self._self = None
+
+    def _particle_weights(self, weights):
+        return self._per_atom(weights, "weights", "values")
 
     def _set_options(self, dtype):
         # float32 staging stays float32 on the device, whatever the number of frames: k_species_current reads it as it is
@@ -232,6 +238,8 @@ class ConductivityGreenKubo(OnsagerGreenKubo):
     Parameters: ``atomgroup``, ``charges`` (one charge (e) per atom; default ``atomgroup.charges``), ``temp_avg``,
     ``dim_type``, ``fft``, ``self_terms`` (``results.timeseries_self`` (n_frames, 1) = sum_n q_n^2 VACF_n: the
     Nernst-Einstein part, ``conductivity_nernst_einstein([1])``) and the placement keywords, as for ``OnsagerGreenKubo``.
+    ``compound``, ``compound_weights``, ``reference_frame`` as for ``OnsagerGreenKubo``: ``charges`` is then one charge per
+    compound, or one per atom (the default, ``atomgroup.charges``), which are added up within every compound.
 
     Attributes
     ----------
@@ -250,9 +258,26 @@ class ConductivityGreenKubo(OnsagerGreenKubo):
             raise TypeError(self._updating_message)
         if "weights" in kwargs:
             raise TypeError("ConductivityGreenKubo takes charges, not weights")
+        self._charges_per_atom = charges is None  # the group's own charges: certainly one per atom
+        self._species_per_atom = True             # (the one species, given per atom below)
         q = atomgroup.charges if charges is None else charges
         super().__init__(atomgroup, np.zeros(len(atomgroup), dtype=np.int32), temp_avg, dim_type, fft, weights=q, **kwargs)
         self.charges = self.weights
+
+    def _particle_weights(self, charges):
+        q = np.asarray(charges, dtype=np.float64).ravel()
+        if self._plan is None or self._compound is None:
+            return super()._particle_weights(q)
+        from .compound import same_order
+
+        n, C = self._n_atoms, self.n_particles
+        if q.size == n == C and not self._charges_per_atom and not same_order(self._compound_index, C):
+            raise ValueError(f"charges: {q.size} values for {n} atoms in {C} one-atom compounds whose order (np.unique of the "
+                             "labels) is not the atoms': per atom or per compound cannot be told apart; give the compound "
+                             "labels in increasing order, or leave charges=None for the group's own")
+        if q.size == n and (self._charges_per_atom or n != C):  # per atom: a compound's charge is their sum
+            return np.bincount(self._compound_index, weights=q, minlength=C)
+        return super()._particle_weights(q)
 
     def _clear_results(self):
         self.results.current = self.results.timeseries = None

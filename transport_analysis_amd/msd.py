@@ -46,6 +46,21 @@ class EinsteinMSD(StagedAnalysis):
         ``frames=``) give a ``UserWarning`` and are unwrapped over the analysed frames.  A particle that moves
         more than half a box between two analysed frames cannot be unwrapped (not detected).  ``False``
         (default): the positions are used as they are.
+    compound : keyword-only, default None
+        ``None``: the MSD of atoms.  ``"residues"``, ``"segments"``, ``"molecules"``, ``"fragments"`` (the group's
+        ``resindices``, ``segindices``, ``molnums``, ``fragindices``) or one integer label per atom: the MSD of the
+        weighted centre of every compound.  The frames are staged (and unwrapped) as atoms; one pass on the device
+        (``k_compound`` behind ``ta_compound``) then replaces the slab by the compounds'.  ``n_particles``,
+        ``results.msds_by_particle`` and the mean are those of the compounds, ``results.compound_ids`` their labels
+        (``np.unique`` order).
+    compound_weights : keyword-only, default ``"mass"``
+        ``"mass"`` (the group's ``masses``: centres of mass), ``"geometry"`` (equal weights) or one value per atom;
+        normalised within every compound.
+    reference_frame : keyword-only, default None
+        ``"barycentric"``: positions relative to the centre of mass of all atoms of the group, frame by frame (allowed
+        with ``compound=None``: every atom is then its own compound).
+        None of the three is available with ``devices=[...]`` or ``distributed=True`` (``ValueError``): the atoms of a
+        molecule would have to share a shard.
     device, devices, distributed, stage_dtype : keyword-only
         As for ``VelocityAutocorr``: a GPU index or ``"cpu"`` (the opt-in C++/OpenMP backend),
         several GPUs behind one object, or one process per GPU under ``torch.distributed``
@@ -61,6 +76,7 @@ class EinsteinMSD(StagedAnalysis):
     _stage_arrays = ("positions",)
     _by_particle_key = "msds_by_particle"
     _no_data_message = "MSD computation requires positions in the trajectory"
+    _accepts_compound = True
 
     def __init__(self, u, select="all", msd_type="xyz", fft=True, *, unwrap=False, **kwargs):
         if isinstance(u, UpdatingAtomGroup):
@@ -76,6 +92,7 @@ class EinsteinMSD(StagedAnalysis):
         self.unwrap = self._unwrap
         self.ag = self._group = u.select_atoms(self.select)
         self.n_particles = len(self.ag)
+        self._init_compound()
         self.results.msds_by_particle = None
         self.results.timeseries = None
 

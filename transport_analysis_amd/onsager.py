@@ -93,6 +93,11 @@ class OnsagerHelfand(SelfTerms, CollectiveAnalysis):
     self_terms : bool, keyword-only, default False — also compute the self part of every species,
         ``sum_{n in s} w_n^2 MSD_n(k)``, in one more pass over the slab (``k_species_sort`` behind ``ta_species_self``)
         and one MSD lag-sum call per species.
+    compound, compound_weights, reference_frame : keyword-only — as for ``EinsteinMSD``: the moments and self terms of
+        the centres (of mass) of molecules or ions instead of atoms, in the laboratory or the barycentric frame -- the
+        quantities the papers above define.  With ``compound``, ``species`` is one label per compound, or one per atom
+        that is the same within every compound (``species="resnames"``; else ``ValueError``), and ``weights`` one value
+        per compound; ``results.compound_ids`` holds the compounds' labels, ``results.species_counts`` counts compounds.
     device, devices, distributed, stage_dtype : keyword-only — as for ``EinsteinMSD``.  Under ``distributed=True``
         every rank forms the moments of its block of atoms with its slice of the labels; the moments are summed over
         ranks BEFORE the correlation.
@@ -112,10 +117,11 @@ class OnsagerHelfand(SelfTerms, CollectiveAnalysis):
     results.onsager_distinct : (S, S) — ``onsager - diag(onsager_self)``.
     ``self_diffusivities()``, ``conductivity_nernst_einstein(z)`` and ``ionicity(z)`` read them.
 
-    Not here: a centre-of-mass reference frame.  The Green-Kubo (velocity) form is ``OnsagerGreenKubo``.
+    The Green-Kubo (velocity) form is ``OnsagerGreenKubo``.
     """
 
     _self_quantity = _lib.SELF_MSD
+    _accepts_compound = True
 
     _no_data_message = ("Onsager coefficient computation requires "
                         "positions and box volume in the trajectory")
@@ -127,9 +133,7 @@ class OnsagerHelfand(SelfTerms, CollectiveAnalysis):
                  weights=None, unwrap=False, self_terms=False, **kwargs):
         super().__init__(atomgroup, temp_avg, dim_type, linear_fit_window, fft, unwrap, kwargs)
         self.self_terms = bool(self_terms)
-        if isinstance(species, str):
-            species = getattr(atomgroup, species)
-        self.species, self.species_index = index_species(self._per_atom(species, "species", "labels", dtype=None))
+        self.species, self.species_index = index_species(self._species_labels(species))
         self.n_species = max(int(self.species.size), 1)
         self.weights = None if weights is None else self._per_atom(weights, "weights", "values")
 
