@@ -516,6 +516,68 @@ def test_group_of_eight_members_on_one_device(A):
         c.close()
 
 
+def _pair_err(c, want, diag):
+    """max over pairs (i, j) of max_k |c - want|[k, i, j] / max(diag[i], diag[j])"""
+    S = want.shape[1]
+    return max(float(np.max(np.abs(c[:, i, j] - want[:, i, j]))) / max(diag[i], diag[j]) for i in range(S) for j in range(S))
+
+
+@pytest.mark.parametrize("fft", [True, False])
+def test_group_collectives_skip_empty_members(fft):
+    """The four collective group calls share one launch / copy / wait / sum sequence (sum_members in group.hip): a group
+    over [0, 0, 0] holding 2 atoms has an empty first member, which the sequence skips, so the members called are 1 and 2
+    and the cross terms run on member 1.  70 frames, 3 dims, one atom per species; positions are a walk of steps in
+    -40 ... 40 on a 1/64 grid starting at 8 (|x| < 11 with this seed: 10 bits) and velocities lie in -40/64 ... 40/64, the weights are
+    1 and -0.5, so every moment and current is an exact float64 sum whatever its order (checked on the CPU backend: the
+    moments of the two atoms staged alone, added in order, equal the two-atom context's bit for bit).  Against a single
+    context on the same data: moments and currents bit-equal, counts equal, Phi, the self lag sum and the per-species
+    self terms within 1e-10 scale-relative, the cross terms within 1e-10 of max(C_ii, C_jj) (moments: over the lags,
+    DESIGN 4.10; currents: at lag 0); a second group call returns the same bits."""
+    from transport_analysis_amd import _lib
+
+    T, A, D, S = 70, 2, 3, 2
+    rng = np.random.default_rng(70)
+    x = (np.cumsum(rng.integers(-40, 41, size=(T, A, D)), axis=0) + 512) / 64.0
+    v = rng.integers(-40, 41, size=(T, A, D)) / 64.0
+    lab, w = np.array([0, 1], dtype=np.int32), np.array([1.0, -0.5])
+
+    def evaluate(h, views, data):
+        for view, (lo, hi) in views:
+            view[...] = data[:, lo:hi]
+        h.stage_commit(0, T)
+        if data is x:
+            return (h.conductivity(fft, w, self_term=True), h.onsager(fft, lab, S, w), h.species_self(_lib.SELF_MSD, fft, lab, S, w))
+        return (h.current(fft, lab, S, w), h.species_self(_lib.SELF_VACF, fft, lab, S, w))
+
+    c = _lib.Context(0)
+    g = _lib.Group([0, 0, 0])
+    try:
+        for data in (x, v):
+            (slab,) = c.stage_alloc(T, A, D, n_slabs=1, dtype=np.float64)
+            one = evaluate(c, [(slab, (0, A))], data)
+            (views,) = g.stage_alloc(T, A, D, n_slabs=1, dtype=np.float64)
+            assert g.shards == [(0, 0), (0, 1), (1, 2)] and views[0] is None
+            members = [(view, sh) for view, sh in zip(views, g.shards) if view is not None]
+            grp = evaluate(g, members, data)
+            again = evaluate(g, members, data)
+            for a, b in zip(grp, again):
+                assert all(np.array_equal(p, q) for p, q in zip(a, b))
+            if data is x:
+                (m1, phi1, s1), (m0, phi0, s0) = grp[0], one[0]
+                assert np.array_equal(m1, m0)
+                assert scale_rel_err(phi1, phi0) < 1e-10 and scale_rel_err(s1, s0) < 1e-10
+            (q1, c1), (q0, c0) = (grp[1], one[1]) if data is x else (grp[0], one[0])
+            assert np.array_equal(q1, q0) and np.abs(q0).max() > 0
+            diag = [float(np.max(np.abs(c0[:, i, i]))) if data is x else float(c0[0, i, i]) for i in range(S)]
+            assert _pair_err(c1, c0, diag) < 1e-10
+            (f1, n1), (f0, n0) = grp[-1], one[-1]
+            assert np.array_equal(n1, n0) and list(n0) == [1, 1]
+            assert max(scale_rel_err(f1[s], f0[s]) for s in range(S)) < 1e-10
+    finally:
+        g.close()
+        c.close()
+
+
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_four_ranks_rehearsal_on_one_gpu(scaling):
     """bench.py's N > 1 path with FOUR ranks on this box's one GPU (TA_BENCH_ONE_GPU=1; a box allows six processes

@@ -422,42 +422,37 @@ class _Staged:
         self._call("conductivity", int(fft), _ptr(q), _ptr(moment), _ptr(phi), _ptr(self_ls))
         return moment, phi, self_ls
 
+    def _species_args(self, species, n_species, weights):
+        """(labels int32, n_species as given or the largest label + 1, weights float64 or None, the outputs' species count)"""
+        lab = self._per_atom(species, np.int32, "species", "labels")
+        S = int(n_species) if n_species is not None else int(lab.max()) + 1
+        return lab, S, self._per_atom(weights, np.float64, "weights", "values"), max(S, 1)
+
+    def _species_sums(self, name, fft, species, n_species, weights, cross):
+        T, _, D = self._staged_shape()
+        lab, S, w, n = self._species_args(species, n_species, weights)
+        sums = np.empty((n, T, D), dtype=np.float64)
+        c = np.empty((T, n, n), dtype=np.float64) if cross else None
+        self._call(name, int(fft), S, _ptr(lab), _ptr(w), _ptr(sums), _ptr(c))
+        return sums, c
+
     def onsager(self, fft, species, n_species=None, weights=None, cross=True):
         """Species moments and their cross MSD of slab 0 (the positions), ta_onsager: `species` one integer label in
         0 ... n_species - 1 per staged atom, in any order (n_species: default the largest label + 1), `weights` one weight
         per atom or None (all 1): (moments (n_species, n_frames, dim), C (n_frames, n_species, n_species) or None)."""
-        T, _, D = self._staged_shape()
-        lab = self._per_atom(species, np.int32, "species", "labels")
-        S = int(n_species) if n_species is not None else int(lab.max()) + 1
-        w = self._per_atom(weights, np.float64, "weights", "values")
-        n = max(S, 1)
-        moments = np.empty((n, T, D), dtype=np.float64)
-        c = np.empty((T, n, n), dtype=np.float64) if cross else None
-        self._call("onsager", int(fft), S, _ptr(lab), _ptr(w), _ptr(moments), _ptr(c))
-        return moments, c
+        return self._species_sums("onsager", fft, species, n_species, weights, cross)
 
     def current(self, fft, species, n_species=None, weights=None, cross=True):
         """Species currents and their cross-correlation of slab 0 (the velocities), ta_current: arguments as `onsager`:
         (currents (n_species, n_frames, dim), C (n_frames, n_species, n_species) with lag 0, or None)."""
-        T, _, D = self._staged_shape()
-        lab = self._per_atom(species, np.int32, "species", "labels")
-        S = int(n_species) if n_species is not None else int(lab.max()) + 1
-        w = self._per_atom(weights, np.float64, "weights", "values")
-        n = max(S, 1)
-        currents = np.empty((n, T, D), dtype=np.float64)
-        c = np.empty((T, n, n), dtype=np.float64) if cross else None
-        self._call("current", int(fft), S, _ptr(lab), _ptr(w), _ptr(currents), _ptr(c))
-        return currents, c
+        return self._species_sums("current", fft, species, n_species, weights, cross)
 
     def species_self(self, quantity, fft, species, n_species=None, weights=None):
         """Per-species self terms of slab 0, ta_species_self: `quantity` SELF_MSD (slab 0 = positions) or SELF_VACF
         (velocities), the other arguments as `onsager`: (self (n_species, n_frames) = sum_{n in s} w_n^2 f_n(k), counts
         (n_species,) int64 = the atoms per species)."""
         T, _, _ = self._staged_shape()
-        lab = self._per_atom(species, np.int32, "species", "labels")
-        S = int(n_species) if n_species is not None else int(lab.max()) + 1
-        w = self._per_atom(weights, np.float64, "weights", "values")
-        n = max(S, 1)
+        lab, S, w, n = self._species_args(species, n_species, weights)
         out = np.empty((n, T), dtype=np.float64)
         counts = np.zeros(n, dtype=np.int64)
         self._call("species_self", int(quantity), int(fft), S, _ptr(lab), _ptr(w), _ptr(out), _ptr(counts))
@@ -572,27 +567,24 @@ class Context(_Staged):
         self.stage_commit(0, T)
         return self.conductivity(fft, np.ones(1))[1]
 
+    def _cross(self, name, noun, sums, fft):
+        a = np.ascontiguousarray(sums, dtype=np.float64)
+        if a.ndim != 3:
+            raise ValueError(f"{noun}: shape {a.shape}, expected (n_species, n_frames, dim)")
+        S, T, D = a.shape
+        c = np.empty((T, S, S), dtype=np.float64)
+        self._call(name, int(fft), _ptr(a), S, T, D, _ptr(c))
+        return c
+
     def onsager_cross(self, moments, fft):
         """C (n_frames, S, S) of given (S, n_frames, dim) moments, e.g. the sum of several shards' moments
         (ta_onsager_cross): needs no staged slab and leaves the context's slabs as they are."""
-        m = np.ascontiguousarray(moments, dtype=np.float64)
-        if m.ndim != 3:
-            raise ValueError(f"moments: shape {m.shape}, expected (n_species, n_frames, dim)")
-        S, T, D = m.shape
-        c = np.empty((T, S, S), dtype=np.float64)
-        self._call("onsager_cross", int(fft), _ptr(m), S, T, D, _ptr(c))
-        return c
+        return self._cross("onsager_cross", "moments", moments, fft)
 
     def current_cross(self, currents, fft):
         """C (n_frames, S, S) of given (S, n_frames, dim) currents, e.g. the sum of several shards' currents
         (ta_current_cross): needs no staged slab and leaves the context's slabs as they are."""
-        j = np.ascontiguousarray(currents, dtype=np.float64)
-        if j.ndim != 3:
-            raise ValueError(f"currents: shape {j.shape}, expected (n_species, n_frames, dim)")
-        S, T, D = j.shape
-        c = np.empty((T, S, S), dtype=np.float64)
-        self._call("current_cross", int(fft), _ptr(j), S, T, D, _ptr(c))
-        return c
+        return self._cross("current_cross", "currents", currents, fft)
 
     # -- device-pointer compute (asynchronous) --------------------------
     def vacf_fft_dev(self, d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp=0, ld_bp=0, stream=0):

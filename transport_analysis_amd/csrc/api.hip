@@ -132,8 +132,9 @@ struct ta_ctx {
     // charges and outputs of host-facing calls, the pair-major copy of the (n_frames, dim) moment
     DevBuf cond_part{workspaces, kTrimmed}, cond_w{workspaces, kTrimmed}, cond_q{workspaces, kKept};
     DevBuf cond_out{workspaces, kKept}, cond_mpm{workspaces, kTrimmed};
-    // Onsager (ons_pm, ons_cross): the species moments' partial sums, the labels and weights and the outputs of host-facing
-    // calls, the pair-major slab of the S^2 pseudo-particles, their by-particle MSDs (+ lag sums and the non-zero flags)
+    // Onsager moments and Green-Kubo currents (coll_pm, coll_cross; ons_*: the first of the two to use them): the species
+    // sums' partial sums, the labels and weights and the outputs of host-facing calls, the pair-major slab of the S^2
+    // pseudo-particles, their by-particle lag sums (+ lag sums and the non-zero flags)
     DevBuf ons_part{workspaces, kTrimmed}, ons_lab{workspaces, kKept}, ons_w{workspaces, kKept};
     DevBuf ons_out{workspaces, kKept}, ons_pm{workspaces, kTrimmed}, ons_bp{workspaces, kTrimmed};
     DevBuf unwrap_box{workspaces, kTrimmed};    // ta_unwrap: the box table (unwrap_box.hpp) of the last call
@@ -847,6 +848,56 @@ int staged_entry(ta_ctx* ctx, int which, const double* d_masses, double scale, d
                       (hipStream_t)stream, ctx->st_dev_f32);
 }
 
+// ---- the slab bracket of the collective quantities (conductivity, moments, currents, species self terms) ------------
+// Where a call's pair-major slab is, and the stream the call runs on
+struct Slab {
+    const void* pm;
+    bool f32;
+    int64_t pitch, T, A;
+    int D;
+    hipStream_t st;
+};
+// the frame-major device input of a *_dev entry
+struct DevSrc {
+    const double* d;
+    int64_t T, A;
+    int D;
+    int64_t ld_row;
+};
+constexpr auto no_args = []() -> int { return TA_OK; };
+constexpr auto no_pre = [](const Slab&) -> int { return TA_OK; };
+
+// One call on slab 0: of `dev` (a *_dev entry: check_shape, the call opened, then its relayout into the scratch slab) or,
+// dev NULL, the staged one (check_staged; the caller's stream ordered behind the queued commits, then the call opened).
+// args(): the entry's own argument checks, at their place among the shared ones; pre(slab): what the call queues or
+// allocates BEFORE it is opened (uploads, self_plan; slab.pm of a *_dev entry is not set yet); body(slab) closes the call.
+template <class Args, class Pre, class Body>
+int slab_entry(ta_ctx* ctx, const DevSrc* dev, void* stream, Args&& args, Pre&& pre, Body&& body) {
+    if (dev) {
+        TA_NO_CPU(ctx);
+        TA_CHECK(check_shape(ctx, dev->T, dev->A, dev->D, dev->ld_row));
+        TA_CHECK(args());
+        if (!dev->d) return fail(ctx, TA_E_INVALID, "null device pointer");
+    } else {
+        TA_CHECK(need_ctx(ctx));
+        TA_NO_CPU(ctx);
+        TA_CHECK(args());
+        TA_CHECK(check_staged(ctx));
+    }
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;  // NULL = the legacy default stream, as for any HIP call
+    Slab s = dev ? Slab{nullptr, false, pm_pitch(dev->T), dev->T, dev->A, dev->D, st}
+                 : Slab{ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A, ctx->st_D, st};
+    TA_CHECK(pre(s));
+    if (!dev) TA_CHECK(order_after_staging(ctx, st));
+    TA_CHECK(call_begin(ctx, st));
+    if (dev) {
+        const double* px = nullptr;
+        TA_CHECK(relayout_input(ctx, 0, dev->d, s.T, s.A * s.D, dev->ld_row, st, &px));
+        s.pm = px;
+    }
+    return body(s);
+}
 
 // ---- Einstein-Helfand conductivity (conductivity.hip) ---------------------------------------------------------------
 // Phi(k) of the (n_frames, dim) frame-major moment at d_moment: its pair-major copy is a one-atom slab, and its MSD lag
@@ -863,12 +914,14 @@ int cond_collective(ta_ctx* ctx, bool fft, const double* d_moment, int64_t T, in
 // then the self term = the MSD lag sum of W (sum_n q_n^2 MSD_n: the MSD is invariant under the shift and |d(q x)|^2 = q^2 |dx|^2) and the
 // collective Phi of the moment, each by msd_impl.  d_coll / d_self NULL: skipped.  ev[1] / ev[2] bracket the moment
 // pass, unless an FFT evaluation after it records its own forward kernel there.
-int cond_pm(ta_ctx* ctx, bool fft, const void* pm_any, bool pm_f32, int64_t pitch, int64_t T, int64_t A, int D,
-            const double* d_q, double* d_moment, double* d_coll, double* d_self, hipStream_t st) {
+int cond_pm(ta_ctx* ctx, bool fft, const Slab& s, const double* d_q, double* d_moment, double* d_coll, double* d_self) {
     int rc;
-    const int64_t n_cols = A * D;
+    const int64_t pitch = s.pitch, T = s.T, A = s.A, n_cols = s.A * s.D;
+    const int D = s.D;
+    hipStream_t st = s.st;
+    const void* pm_any = s.pm;
     // float32 device slabs: a float64 copy first, as for every other evaluation but the float32 kernels
-    if (pm_f32 && (rc = widen_input(ctx, 0, pitch, n_cols, st, &pm_any))) return rc;
+    if (s.f32 && (rc = widen_input(ctx, 0, pitch, n_cols, st, &pm_any))) return rc;
     const double* pm = (const double*)pm_any;
     const int n_parts = cond_moment_parts(ctx->n_cu, (long)T, (long)n_cols);
     if ((rc = ensure(ctx, ctx->cond_part, sizeof(double) * (size_t)n_parts * T * D))) return rc;
@@ -893,13 +946,54 @@ int cond_args(ta_ctx* ctx, int fft, const void* charges, const void* moment) {
     return TA_OK;
 }
 
-// ---- Onsager transport coefficients (onsager.hip) -------------------------------------------------------------------
-// C[k, i, j] of the (S, T, D) moments at d_moments into d_cross (T, S, S), by polarisation in ONE msd_impl call: the S^2
-// pseudo-particles M_i, M_i + M_j, M_i - M_j as a pair-major slab, their (T, S^2) by-particle MSDs (msd_impl: the
-// EinsteinMSD dispatch, with the call's fft), then C_ij = 1/4 (MSD(M_i + M_j) - MSD(M_i - M_j)).
-int ons_cross(ta_ctx* ctx, bool fft, const double* d_moments, int S, int64_t T, int D, double* d_cross, hipStream_t st) {
+// ---- species-collective quantities: Onsager moments (onsager.hip), Green-Kubo currents (current.hip) ----------------
+// Per-species sums over atoms Q_s[t, d] in ONE pass over the slab, and their cross-correlation C[k, i, j] by polarisation.
+// The two quantities run the same host code; Collective holds everything that differs between them.
+
+// the VACF's dispatch with msd_impl's signature (the by-particle autocorrelations of the currents, the VACF self terms)
+int acf_impl(ta_ctx* ctx, bool fft, const double* pm, int64_t pitch, int64_t T, int64_t A, int D, double* d_lagsum, double* d_bp,
+             int64_t ld_bp, hipStream_t st) {
+    if (fft) return fft_impl(ctx, pm, pitch, T, A, D, d_lagsum, d_bp, ld_bp, st);
+    return direct_impl(ctx, MODE_VACF, pm, nullptr, nullptr, T, A, D, pitch, 1.0, d_lagsum, d_bp, ld_bp, st);
+}
+// k_species_moment reads float64 slabs only: the slab type is the caller's business (widen_f32)
+hipError_t pass_species_moment(const void* pos, bool, long pitch, long T, long n_cols, int D, int S, const int* species,
+                               const double* w, double* partial, int n_parts, hipStream_t st) {
+    return launch_species_moment((const double*)pos, pitch, T, n_cols, D, S, species, w, partial, n_parts, st);
+}
+
+struct Collective {
+    const char* noun;       // of the sums, in messages
+    const char* pass_name;  // the pass that forms every species' sum: the call's main kernel
+    hipError_t (*pass)(const void* pm, bool f32, long pitch, long T, long n_cols, int D, int S, const int* species,
+                       const double* w, double* partial, int n_parts, hipStream_t st);
+    bool widen_f32;  // a float32 slab gets a float64 copy first (as cond_pm does), or the pass reads it as it is
+    // the (T, S^2) by-particle lag sums of the pseudo-particles under the polarisation step
+    int (*corr)(ta_ctx*, bool fft, const double* pm, int64_t pitch, int64_t T, int64_t A, int D, double* d_lagsum, double* d_bp,
+                int64_t ld_bp, hipStream_t st);
+    const char* finish_name;
+    hipError_t (*finish)(const double* bp, int S, long T, const int* nz, double* C, hipStream_t st);
+    bool lag0;  // C[0] is kept (<Q_i . Q_j>), or exactly 0 (a mean squared difference: one frame needs no kernel at all)
+    // the CPU backend's whole call and its cross term
+    int (*cpu)(const ta::cpu::State&, bool fft, int S, const int32_t* species, const double* w, double* sums, double* cross);
+    int (*cpu_cross)(int threads, bool fft, const double* sums, int S, int64_t T, int D, double* cross);
+};
+// indexed by ta::CollKind.  Moments: Q = w (x - x[0]), C_ij = 1/4 (MSD(M_i + M_j) - MSD(M_i - M_j)) by the EinsteinMSD
+// dispatch.  Currents: Q = w v of a slab of either element type, C_ij = 1/4 (ACF(J_i + J_j) - ACF(J_i - J_j)) by the VACF's.
+constexpr Collective kCollective[2] = {
+    {"moments", "k_species_moment", pass_species_moment, true, msd_impl, "k_onsager_finish", launch_onsager_finish, false,
+     ta::cpu::onsager, ta::cpu::onsager_cross},
+    {"currents", "k_species_current", launch_species_current, false, acf_impl, "k_current_finish", launch_current_finish, true,
+     ta::cpu::current, ta::cpu::current_cross},
+};
+
+// C[k, i, j] of the (S, T, D) sums at d_sums into d_cross (T, S, S), by polarisation in ONE q.corr call: the S^2
+// pseudo-particles Q_i, Q_i + Q_j, Q_i - Q_j as a pair-major slab (k_onsager_combos, in the Onsager workspaces), their
+// (T, S^2) by-particle lag sums with the call's fft, then q.finish.
+int coll_cross(ta_ctx* ctx, const Collective& q, bool fft, const double* d_sums, int S, int64_t T, int D, double* d_cross,
+               hipStream_t st) {
     const int64_t P = (int64_t)S * S, pitch = pm_pitch(T);
-    if (T < 2) {  // lag 0 alone: exactly 0
+    if (!q.lag0 && T < 2) {  // lag 0 alone: exactly 0
         TA_HIP_TRY(ctx, hipMemsetAsync(d_cross, 0, sizeof(double) * (size_t)(T * P), st));
         return TA_OK;
     }
@@ -909,50 +1003,39 @@ int ons_cross(ta_ctx* ctx, bool fft, const double* d_moments, int S, int64_t T, 
     double* lagsum = bp + T * P;
     int* nz = (int*)(lagsum + T);
     TA_HIP_TRY(ctx, hipMemsetAsync(nz, 0, sizeof(int) * TA_ONSAGER_MAX_SPECIES, st));
-    TA_LAUNCH(ctx, "k_onsager_combos", st, launch_onsager_combos(d_moments, S, (long)T, D, (long)pitch, (double*)ctx->ons_pm.p, nz, st));
-    TA_CHECK(msd_impl(ctx, fft, (const double*)ctx->ons_pm.p, pitch, T, P, D, lagsum, bp, P, st));
-    TA_LAUNCH(ctx, "k_onsager_finish", st, launch_onsager_finish(bp, S, (long)T, nz, d_cross, st));
+    TA_LAUNCH(ctx, "k_onsager_combos", st, launch_onsager_combos(d_sums, S, (long)T, D, (long)pitch, (double*)ctx->ons_pm.p, nz, st));
+    TA_CHECK(q.corr(ctx, fft, (const double*)ctx->ons_pm.p, pitch, T, P, D, lagsum, bp, P, st));
+    TA_LAUNCH(ctx, q.finish_name, st, q.finish(bp, S, (long)T, nz, d_cross, st));
     return TA_OK;
 }
 
-// One Onsager call on a pair-major position slab (the caller has opened the call's bracket, it is closed here): the one
-// pass that forms every species' moment, the fixed-order sum of its partials into d_moments (S, T, D), and with d_cross
-// the cross MSD of the moments.  ev[1] / ev[2] bracket the pass, unless an FFT evaluation after it records its own
-// forward kernel there.
-int ons_pm(ta_ctx* ctx, bool fft, const void* pm_any, bool pm_f32, int64_t pitch, int64_t T, int64_t A, int D, int S,
-           const int32_t* d_species, const double* d_w, double* d_moments, double* d_cross, hipStream_t st) {
-    const int64_t n_cols = A * D;
-    if (n_cols >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "Onsager moments: n_atoms * dim must be below 2^31");
-    // float32 device slabs: a float64 copy first, as cond_pm does
-    if (pm_f32) TA_CHECK(widen_input(ctx, 0, pitch, n_cols, st, &pm_any));
+// One call on a pair-major slab (the caller has opened the call's bracket, it is closed here): the one pass that forms
+// every species' sum, the fixed-order sum of its partials into d_sums (S, T, D), and with d_cross their cross term.
+// ev[1] / ev[2] bracket the pass, unless an FFT evaluation after it records its own forward kernel there.
+int coll_pm(ta_ctx* ctx, const Collective& q, bool fft, const Slab& s, int S, const int32_t* d_species, const double* d_w,
+            double* d_sums, double* d_cross) {
+    const int64_t T = s.T, n_cols = s.A * s.D;
+    if (n_cols >= (int64_t)1 << 31)
+        return fail(ctx, TA_E_INVALID, std::string("Onsager ") + q.noun + ": n_atoms * dim must be below 2^31");
+    const void* pm = s.pm;
+    const bool widen = s.f32 && q.widen_f32;
+    if (widen) TA_CHECK(widen_input(ctx, 0, s.pitch, n_cols, s.st, &pm));
     const int n_parts = species_moment_parts(ctx->n_cu, S, (long)T, (long)n_cols);
-    const size_t n_out = (size_t)S * T * D;
+    const size_t n_out = (size_t)S * T * s.D;
     TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)n_parts * n_out));
-    TA_LAUNCH_MAIN(ctx, "k_species_moment", st,
-                   launch_species_moment((const double*)pm_any, (long)pitch, (long)T, (long)n_cols, D, S, d_species, d_w,
-                                         (double*)ctx->ons_part.p, n_parts, st));
-    TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)n_out, d_moments, st));
-    if (d_cross) TA_CHECK(ons_cross(ctx, fft, d_moments, S, T, D, d_cross, st));
-    return call_end(ctx, st);
+    TA_LAUNCH_MAIN(ctx, q.pass_name, s.st,
+                   q.pass(pm, s.f32 && !widen, (long)s.pitch, (long)T, (long)n_cols, s.D, S, d_species, d_w,
+                          (double*)ctx->ons_part.p, n_parts, s.st));
+    TA_LAUNCH(ctx, "k_sum_partials", s.st, launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)n_out, d_sums, s.st));
+    if (d_cross) TA_CHECK(coll_cross(ctx, q, fft, d_sums, S, T, s.D, d_cross, s.st));
+    return call_end(ctx, s.st);
 }
 
-int check_species_count(ta_ctx* ctx, int S) {
-    if (S < 1 || S > TA_ONSAGER_MAX_SPECIES)
-        return fail(ctx, TA_E_INVALID, "n_species must be 1 ... " + std::to_string(TA_ONSAGER_MAX_SPECIES));
-    return TA_OK;
-}
-int ons_args(ta_ctx* ctx, int fft, int S, const void* species, const void* moments) {
+int coll_args(ta_ctx* ctx, const Collective& q, int fft, int S, const void* species, const void* sums) {
     TA_CHECK(check_fft(ctx, fft));
-    TA_CHECK(check_species_count(ctx, S));
+    TA_CHECK(check_species_count(fail, ctx, S));
     if (!species) return fail(ctx, TA_E_INVALID, "species labels are NULL");
-    if (!moments) return fail(ctx, TA_E_INVALID, "moments output is NULL");
-    return TA_OK;
-}
-int check_labels(ta_ctx* ctx, const int32_t* h_species, int64_t n, int S) {
-    for (int64_t a = 0; a < n; ++a)
-        if (h_species[a] < 0 || h_species[a] >= S)
-            return fail(ctx, TA_E_INVALID, "species label " + std::to_string(h_species[a]) + " of atom " + std::to_string(a) +
-                                               " is outside 0 ... n_species - 1");
+    if (!sums) return fail(ctx, TA_E_INVALID, std::string(q.noun) + " output is NULL");
     return TA_OK;
 }
 
@@ -961,7 +1044,7 @@ int self_args(ta_ctx* ctx, int quantity, int fft, int S, const void* species, co
     if (quantity != TA_SELF_MSD && quantity != TA_SELF_VACF)
         return fail(ctx, TA_E_INVALID, "quantity must be TA_SELF_MSD (0) or TA_SELF_VACF (1)");
     TA_CHECK(check_fft(ctx, fft));
-    TA_CHECK(check_species_count(ctx, S));
+    TA_CHECK(check_species_count(fail, ctx, S));
     if (!species) return fail(ctx, TA_E_INVALID, "species labels are NULL");
     if (!out) return fail(ctx, TA_E_INVALID, "self output is NULL");
     return TA_OK;
@@ -971,7 +1054,7 @@ int self_args(ta_ctx* ctx, int quantity, int fft, int S, const void* species, co
 // upload on `st`.  Nothing on the device has been written when this fails.
 int self_plan(ta_ctx* ctx, int S, const int32_t* h_species, int64_t A, int D, hipStream_t st, SortPlan* plan) {
     if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "species self terms: n_atoms * dim must be below 2^31");
-    TA_CHECK(check_labels(ctx, h_species, A, S));
+    TA_CHECK(check_labels(fail, ctx, h_species, A, S));
     TA_CHECK(ensure(ctx, ctx->self_order, sizeof(int32_t) * (size_t)A));
     if (!ctx->ev_order) TA_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_order, hipEventDisableTiming));
     else TA_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_order));  // the last call's upload has left self_order_h
@@ -987,12 +1070,15 @@ int self_plan(ta_ctx* ctx, int S, const int32_t* h_species, int64_t A, int D, hi
 // every species with atoms gets ONE lag-sum evaluation on its block -- a pair-major slab of its own with N_s atoms -- by
 // the dispatch ta_msd_staged / ta_vacf_fft_staged / ta_vacf_direct_staged use, into d_self + s T.  A species without
 // atoms: exact zeros, no call.  ev[1] / ev[2] bracket the pass, unless an evaluation after it records its own kernel.
-int species_self_pm(ta_ctx* ctx, int quantity, bool fft, const void* pm_any, bool pm_f32, int64_t pitch, int64_t T, int64_t A,
-                    int D, const SortPlan& plan, const double* d_w, double* d_self, hipStream_t st) {
+int species_self_pm(ta_ctx* ctx, int quantity, bool fft, const Slab& slab, const SortPlan& plan, const double* d_w,
+                    double* d_self) {
+    const int64_t pitch = slab.pitch, T = slab.T;
+    const int D = slab.D;
+    hipStream_t st = slab.st;
     TA_CHECK(ensure(ctx, ctx->self_w, (size_t)plan.n_pairs * (size_t)pitch * 16));
     double* W = (double*)ctx->self_w.p;
     TA_LAUNCH_MAIN(ctx, "k_species_sort", st,
-                   launch_species_sort(ctx->n_cu, pm_any, pm_f32, (long)pitch, (long)T, (long)(A * D), D, plan,
+                   launch_species_sort(ctx->n_cu, slab.pm, slab.f32, (long)pitch, (long)T, (long)(slab.A * D), D, plan,
                                        (const int*)ctx->self_order.p, d_w, quantity == TA_SELF_MSD, W, st));
     for (int s = 0; s < plan.n_species; ++s) {
         double* out = d_self + (size_t)s * T;
@@ -1002,59 +1088,9 @@ int species_self_pm(ta_ctx* ctx, int quantity, bool fft, const void* pm_any, boo
             continue;
         }
         const double* blk = W + (size_t)plan.pair0[s] * (size_t)pitch * 2;
-        if (quantity == TA_SELF_MSD) TA_CHECK(msd_impl(ctx, fft, blk, pitch, T, n, D, out, nullptr, 0, st));
-        else if (fft) TA_CHECK(fft_impl(ctx, blk, pitch, T, n, D, out, nullptr, 0, st));
-        else TA_CHECK(direct_impl(ctx, MODE_VACF, blk, nullptr, nullptr, T, n, D, pitch, 1.0, out, nullptr, 0, st));
+        TA_CHECK((quantity == TA_SELF_MSD ? msd_impl : acf_impl)(ctx, fft, blk, pitch, T, n, D, out, nullptr, 0, st));
     }
     return call_end(ctx, st);
-}
-
-// ---- Green-Kubo species currents (current.hip) ----------------------------------------------------------------------
-// C[k, i, j] of the (S, T, D) currents at d_currents into d_cross (T, S, S), by polarisation in ONE autocorrelation call:
-// the S^2 pseudo-particles J_i, J_i + J_j, J_i - J_j as a pair-major slab (k_onsager_combos, in the Onsager workspaces),
-// their (T, S^2) by-particle autocorrelations (the VACF dispatch, with the call's fft), then
-// C_ij = 1/4 (ACF(J_i + J_j) - ACF(J_i - J_j)), lag 0 included.
-int cur_cross(ta_ctx* ctx, bool fft, const double* d_currents, int S, int64_t T, int D, double* d_cross, hipStream_t st) {
-    const int64_t P = (int64_t)S * S, pitch = pm_pitch(T);
-    TA_CHECK(ensure(ctx, ctx->ons_pm, pm_bytes(T, P * D)));
-    TA_CHECK(ensure(ctx, ctx->ons_bp, sizeof(double) * (size_t)(T * P + T) + sizeof(int) * TA_ONSAGER_MAX_SPECIES));
-    double* bp = (double*)ctx->ons_bp.p;
-    double* lagsum = bp + T * P;
-    int* nz = (int*)(lagsum + T);
-    const double* pm = (const double*)ctx->ons_pm.p;
-    TA_HIP_TRY(ctx, hipMemsetAsync(nz, 0, sizeof(int) * TA_ONSAGER_MAX_SPECIES, st));
-    TA_LAUNCH(ctx, "k_onsager_combos", st, launch_onsager_combos(d_currents, S, (long)T, D, (long)pitch, (double*)ctx->ons_pm.p, nz, st));
-    if (fft) TA_CHECK(fft_impl(ctx, pm, pitch, T, P, D, lagsum, bp, P, st));
-    else TA_CHECK(direct_impl(ctx, MODE_VACF, pm, nullptr, nullptr, T, P, D, pitch, 1.0, lagsum, bp, P, st));
-    TA_LAUNCH(ctx, "k_current_finish", st, launch_current_finish(bp, S, (long)T, nz, d_cross, st));
-    return TA_OK;
-}
-
-// One current call on a pair-major velocity slab of either element type, read as it is (the caller has opened the call's
-// bracket, it is closed here): the one pass that forms every species' current, the fixed-order sum of its partials into
-// d_currents (S, T, D), and with d_cross their cross-correlation.  ev[1] / ev[2] bracket the pass, unless an FFT
-// evaluation after it records its own forward kernel there.
-int cur_pm(ta_ctx* ctx, bool fft, const void* pm_any, bool pm_f32, int64_t pitch, int64_t T, int64_t A, int D, int S,
-           const int32_t* d_species, const double* d_w, double* d_currents, double* d_cross, hipStream_t st) {
-    const int64_t n_cols = A * D;
-    if (n_cols >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "Onsager currents: n_atoms * dim must be below 2^31");
-    const int n_parts = species_moment_parts(ctx->n_cu, S, (long)T, (long)n_cols);
-    const size_t n_out = (size_t)S * T * D;
-    TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)n_parts * n_out));
-    TA_LAUNCH_MAIN(ctx, "k_species_current", st,
-                   launch_species_current(pm_any, pm_f32, (long)pitch, (long)T, (long)n_cols, D, S, d_species, d_w,
-                                          (double*)ctx->ons_part.p, n_parts, st));
-    TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)n_out, d_currents, st));
-    if (d_cross) TA_CHECK(cur_cross(ctx, fft, d_currents, S, T, D, d_cross, st));
-    return call_end(ctx, st);
-}
-
-int cur_args(ta_ctx* ctx, int fft, int S, const void* species, const void* currents) {
-    TA_CHECK(check_fft(ctx, fft));
-    TA_CHECK(check_species_count(ctx, S));
-    if (!species) return fail(ctx, TA_E_INVALID, "species labels are NULL");
-    if (!currents) return fail(ctx, TA_E_INVALID, "currents output is NULL");
-    return TA_OK;
 }
 
 // ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
@@ -1722,140 +1758,85 @@ int ta_msd_staged(ta_ctx* ctx, int fft, double* d_lagsum, double* d_bp, int64_t 
     });
 }
 
+// The *_dev / *_staged pairs of the collective quantities: one body each on slab_entry; dev NULL = the staged slab.
 // Einstein-Helfand conductivity: slab 0 / d_pos holds the positions
+static int cond_entry(ta_ctx* ctx, const DevSrc* dev, int fft, const double* d_charges, double* d_moment, double* d_collective,
+                      double* d_self_lagsum, void* stream) {
+    return slab_entry(ctx, dev, stream, [&] { return cond_args(ctx, fft, d_charges, d_moment); }, no_pre, [&](const Slab& s) {
+        return cond_pm(ctx, fft != 0, s, d_charges, d_moment, d_collective, d_self_lagsum);
+    });
+}
 int ta_conductivity_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int fft,
                         const double* d_charges, double* d_moment, double* d_collective, double* d_self_lagsum,
                         void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    TA_NO_CPU(ctx);
-    TA_CHECK(check_shape(ctx, T, A, D, ld_row));
-    TA_CHECK(cond_args(ctx, fft, d_charges, d_moment));
-    if (!d_pos) return fail(ctx, TA_E_INVALID, "null device pointer");
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    TA_CHECK(call_begin(ctx, st));
-    const double* px = nullptr;
-    TA_CHECK(relayout_input(ctx, 0, d_pos, T, A * D, ld_row, st, &px));
-    return cond_pm(ctx, fft != 0, px, false, pm_pitch(T), T, A, D, d_charges, d_moment, d_collective, d_self_lagsum, st);
+    const DevSrc src{d_pos, T, A, D, ld_row};
+    return cond_entry(ctx, &src, fft, d_charges, d_moment, d_collective, d_self_lagsum, stream);
     });
 }
-
 int ta_conductivity_staged(ta_ctx* ctx, int fft, const double* d_charges, double* d_moment, double* d_collective,
                            double* d_self_lagsum, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(cond_args(ctx, fft, d_charges, d_moment));
-    TA_CHECK(check_staged(ctx));
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    TA_CHECK(order_after_staging(ctx, (hipStream_t)stream));
-    TA_CHECK(call_begin(ctx, (hipStream_t)stream));
-    return cond_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A, ctx->st_D,
-                   d_charges, d_moment, d_collective, d_self_lagsum, (hipStream_t)stream);
+    return cond_entry(ctx, nullptr, fft, d_charges, d_moment, d_collective, d_self_lagsum, stream);
     });
 }
 
-// Onsager transport coefficients: slab 0 / d_pos holds the positions; device labels are not checked (k_species_moment
-// skips an atom whose label is out of range)
+// Onsager moments (slab 0 / d_pos holds the positions) and Green-Kubo currents (the velocities; the staged slab is read
+// in its own element type, never widened); device labels are not checked (the pass skips an atom whose label is out of range)
+static int coll_entry(ta_ctx* ctx, const Collective& q, const DevSrc* dev, int fft, int n_species, const int32_t* d_species,
+                      const double* d_weights, double* d_sums, double* d_cross, void* stream) {
+    return slab_entry(ctx, dev, stream, [&] { return coll_args(ctx, q, fft, n_species, d_species, d_sums); }, no_pre,
+                      [&](const Slab& s) { return coll_pm(ctx, q, fft != 0, s, n_species, d_species, d_weights, d_sums, d_cross); });
+}
 int ta_onsager_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int fft, int n_species,
                    const int32_t* d_species, const double* d_weights, double* d_moments, double* d_cross, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    TA_NO_CPU(ctx);
-    TA_CHECK(check_shape(ctx, T, A, D, ld_row));
-    TA_CHECK(ons_args(ctx, fft, n_species, d_species, d_moments));
-    if (!d_pos) return fail(ctx, TA_E_INVALID, "null device pointer");
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    TA_CHECK(call_begin(ctx, st));
-    const double* px = nullptr;
-    TA_CHECK(relayout_input(ctx, 0, d_pos, T, A * D, ld_row, st, &px));
-    return ons_pm(ctx, fft != 0, px, false, pm_pitch(T), T, A, D, n_species, d_species, d_weights, d_moments, d_cross, st);
+    const DevSrc src{d_pos, T, A, D, ld_row};
+    return coll_entry(ctx, kCollective[COLL_MOMENTS], &src, fft, n_species, d_species, d_weights, d_moments, d_cross, stream);
     });
 }
-
 int ta_onsager_staged(ta_ctx* ctx, int fft, int n_species, const int32_t* d_species, const double* d_weights,
                       double* d_moments, double* d_cross, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(ons_args(ctx, fft, n_species, d_species, d_moments));
-    TA_CHECK(check_staged(ctx));
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    TA_CHECK(order_after_staging(ctx, (hipStream_t)stream));
-    TA_CHECK(call_begin(ctx, (hipStream_t)stream));
-    return ons_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A, ctx->st_D, n_species,
-                  d_species, d_weights, d_moments, d_cross, (hipStream_t)stream);
+    return coll_entry(ctx, kCollective[COLL_MOMENTS], nullptr, fft, n_species, d_species, d_weights, d_moments, d_cross, stream);
     });
 }
-
-// Green-Kubo species currents: slab 0 / d_vel holds the velocities; the staged slab is read in its own element type
-// (never widened); device labels are not checked (k_species_current skips an atom whose label is out of range)
 int ta_current_dev(ta_ctx* ctx, const double* d_vel, int64_t T, int64_t A, int D, int64_t ld_row, int fft, int n_species,
                    const int32_t* d_species, const double* d_weights, double* d_currents, double* d_cross, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    TA_NO_CPU(ctx);
-    TA_CHECK(check_shape(ctx, T, A, D, ld_row));
-    TA_CHECK(cur_args(ctx, fft, n_species, d_species, d_currents));
-    if (!d_vel) return fail(ctx, TA_E_INVALID, "null device pointer");
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    TA_CHECK(call_begin(ctx, st));
-    const double* pv = nullptr;
-    TA_CHECK(relayout_input(ctx, 0, d_vel, T, A * D, ld_row, st, &pv));
-    return cur_pm(ctx, fft != 0, pv, false, pm_pitch(T), T, A, D, n_species, d_species, d_weights, d_currents, d_cross, st);
+    const DevSrc src{d_vel, T, A, D, ld_row};
+    return coll_entry(ctx, kCollective[COLL_CURRENTS], &src, fft, n_species, d_species, d_weights, d_currents, d_cross, stream);
     });
 }
-
 int ta_current_staged(ta_ctx* ctx, int fft, int n_species, const int32_t* d_species, const double* d_weights,
                       double* d_currents, double* d_cross, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(cur_args(ctx, fft, n_species, d_species, d_currents));
-    TA_CHECK(check_staged(ctx));
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    TA_CHECK(order_after_staging(ctx, (hipStream_t)stream));
-    TA_CHECK(call_begin(ctx, (hipStream_t)stream));
-    return cur_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A, ctx->st_D, n_species,
-                  d_species, d_weights, d_currents, d_cross, (hipStream_t)stream);
+    return coll_entry(ctx, kCollective[COLL_CURRENTS], nullptr, fft, n_species, d_species, d_weights, d_currents, d_cross, stream);
     });
 }
 
 // Species self terms: slab 0 / d_x holds the positions (TA_SELF_MSD) or the velocities (TA_SELF_VACF); the staged slab
-// is read in its own element type (never widened); the labels are HOST arrays: the block sizes decide the launches
+// is read in its own element type (never widened); the labels are HOST arrays: the block sizes decide the launches, and
+// self_plan runs before the call is opened
+static int self_entry(ta_ctx* ctx, const DevSrc* dev, int quantity, int fft, int n_species, const int32_t* h_species,
+                      const double* d_weights, double* d_self, void* stream) {
+    SortPlan plan;
+    return slab_entry(
+        ctx, dev, stream, [&] { return self_args(ctx, quantity, fft, n_species, h_species, d_self); },
+        [&](const Slab& s) { return self_plan(ctx, n_species, h_species, s.A, s.D, s.st, &plan); },
+        [&](const Slab& s) { return species_self_pm(ctx, quantity, fft != 0, s, plan, d_weights, d_self); });
+}
 int ta_species_self_dev(ta_ctx* ctx, const double* d_x, int64_t T, int64_t A, int D, int64_t ld_row, int quantity, int fft,
                         int n_species, const int32_t* h_species, const double* d_weights, double* d_self, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    TA_NO_CPU(ctx);
-    TA_CHECK(check_shape(ctx, T, A, D, ld_row));
-    TA_CHECK(self_args(ctx, quantity, fft, n_species, h_species, d_self));
-    if (!d_x) return fail(ctx, TA_E_INVALID, "null device pointer");
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    SortPlan plan;
-    TA_CHECK(self_plan(ctx, n_species, h_species, A, D, st, &plan));
-    TA_CHECK(call_begin(ctx, st));
-    const double* px = nullptr;
-    TA_CHECK(relayout_input(ctx, 0, d_x, T, A * D, ld_row, st, &px));
-    return species_self_pm(ctx, quantity, fft != 0, px, false, pm_pitch(T), T, A, D, plan, d_weights, d_self, st);
+    const DevSrc src{d_x, T, A, D, ld_row};
+    return self_entry(ctx, &src, quantity, fft, n_species, h_species, d_weights, d_self, stream);
     });
 }
-
 int ta_species_self_staged(ta_ctx* ctx, int quantity, int fft, int n_species, const int32_t* h_species, const double* d_weights,
                            double* d_self, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(self_args(ctx, quantity, fft, n_species, h_species, d_self));
-    TA_CHECK(check_staged(ctx));
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    SortPlan plan;
-    TA_CHECK(self_plan(ctx, n_species, h_species, ctx->st_A, ctx->st_D, st, &plan));
-    TA_CHECK(order_after_staging(ctx, st));
-    TA_CHECK(call_begin(ctx, st));
-    return species_self_pm(ctx, quantity, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A,
-                           ctx->st_D, plan, d_weights, d_self, st);
+    return self_entry(ctx, nullptr, quantity, fft, n_species, h_species, d_weights, d_self, stream);
     });
 }
 
@@ -2052,20 +2033,20 @@ int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, do
 // uploaded, the moment (and with self the self lag sum, with coll Phi) left on the device in *d_out: (T, D) moment,
 // then T values of Phi, then T of the self term.
 int cond_launch(ta_ctx* ctx, int fft, const double* h_q, bool coll, bool self, double** d_out) {
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(check_staged(ctx));
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t T = ctx->st_T, A = ctx->st_A;
-    const int D = ctx->st_D;
-    TA_CHECK(ensure(ctx, ctx->cond_q, sizeof(double) * A));
-    TA_CHECK(ensure(ctx, ctx->cond_out, sizeof(double) * (size_t)T * (D + 2)));
-    double* out = (double*)ctx->cond_out.p;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->cond_q.p, h_q, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    TA_CHECK(order_after_staging(ctx, ctx->stream));
-    TA_CHECK(call_begin(ctx, ctx->stream));
-    TA_CHECK(cond_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, T, A, D, (const double*)ctx->cond_q.p,
-                     out, coll ? out + T * D : nullptr, self ? out + T * (D + 1) : nullptr, ctx->stream));
+    double* out = nullptr;
+    TA_CHECK(slab_entry(
+        ctx, nullptr, ctx->stream, no_args,
+        [&](const Slab& s) -> int {
+            TA_CHECK(ensure(ctx, ctx->cond_q, sizeof(double) * s.A));
+            TA_CHECK(ensure(ctx, ctx->cond_out, sizeof(double) * (size_t)s.T * (s.D + 2)));
+            out = (double*)ctx->cond_out.p;
+            TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->cond_q.p, h_q, sizeof(double) * s.A, hipMemcpyHostToDevice, ctx->stream));
+            return TA_OK;
+        },
+        [&](const Slab& s) {
+            return cond_pm(ctx, fft != 0, s, (const double*)ctx->cond_q.p, out, coll ? out + s.T * s.D : nullptr,
+                           self ? out + s.T * (s.D + 1) : nullptr);
+        }));
     *d_out = out;
     return TA_OK;
 }
@@ -2080,86 +2061,44 @@ int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T
     return host_finish(ctx, {{h_coll, out + T * D, (size_t)T}});
 }
 
-// Onsager share of a host-facing call, queued on ctx->stream and not waited for: the labels and weights (this context's
-// atoms, labels already checked) uploaded, the (S, T, D) moments and with cross the (T, S, S) cross MSD behind them left
-// on the device in *d_out.
-int ons_launch(ta_ctx* ctx, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out) {
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(check_staged(ctx));
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t T = ctx->st_T, A = ctx->st_A;
-    const int D = ctx->st_D;
-    TA_CHECK(ensure(ctx, ctx->ons_lab, sizeof(int32_t) * A));
-    if (h_w) TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * A));
-    TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)T * S * (D + S)));
-    double* out = (double*)ctx->ons_out.p;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_lab.p, h_species, sizeof(int32_t) * A, hipMemcpyHostToDevice, ctx->stream));
-    if (h_w) TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_w.p, h_w, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    TA_CHECK(order_after_staging(ctx, ctx->stream));
-    TA_CHECK(call_begin(ctx, ctx->stream));
-    TA_CHECK(ons_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, T, A, D, S, (const int32_t*)ctx->ons_lab.p,
-                    h_w ? (const double*)ctx->ons_w.p : nullptr, out, cross ? out + (size_t)S * T * D : nullptr, ctx->stream));
+// Moments' / currents' share of a host-facing call, queued on ctx->stream and not waited for: the labels and weights (this
+// context's atoms, labels already checked) uploaded, the (S, T, D) sums and with cross the (T, S, S) cross term behind
+// them left on the device in *d_out (the Onsager buffers serve both quantities: one call at a time uses them).
+int coll_launch(ta_ctx* ctx, int kind, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out) {
+    double* out = nullptr;
+    TA_CHECK(slab_entry(
+        ctx, nullptr, ctx->stream, no_args,
+        [&](const Slab& s) -> int {
+            TA_CHECK(ensure(ctx, ctx->ons_lab, sizeof(int32_t) * s.A));
+            if (h_w) TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * s.A));
+            TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)s.T * S * (s.D + S)));
+            out = (double*)ctx->ons_out.p;
+            TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_lab.p, h_species, sizeof(int32_t) * s.A, hipMemcpyHostToDevice, ctx->stream));
+            if (h_w) TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_w.p, h_w, sizeof(double) * s.A, hipMemcpyHostToDevice, ctx->stream));
+            return TA_OK;
+        },
+        [&](const Slab& s) {
+            return coll_pm(ctx, kCollective[kind], fft != 0, s, S, (const int32_t*)ctx->ons_lab.p,
+                           h_w ? (const double*)ctx->ons_w.p : nullptr, out, cross ? out + (size_t)S * s.T * s.D : nullptr);
+        }));
     *d_out = out;
     return TA_OK;
 }
 
-// The cross MSD of host (S, T, D) moments on this context's device, blocking, as a compute call of its own (ta_onsager_cross;
-// the group's ONE evaluation after its members' sums).  Needs no staged slab.
-int ons_cross_host(ta_ctx* ctx, int fft, const double* h_moments, int S, int64_t T, int D, double* h_cross) {
+// The cross term of host (S, T, D) sums on this context's device, blocking, as a compute call of its own (ta_onsager_cross,
+// ta_current_cross; the group's ONE evaluation after its members' sums).  Needs no staged slab.
+int coll_cross_host(ta_ctx* ctx, int kind, int fft, const double* h_sums, int S, int64_t T, int D, double* h_cross) {
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     TA_CHECK(ctx->commits.flush());
     TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)T * S * (D + S)));
     double* out = (double*)ctx->ons_out.p;
     double* cross = out + (size_t)S * T * D;
     hipStream_t st = ctx->stream;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_moments, sizeof(double) * (size_t)S * T * D, hipMemcpyHostToDevice, st));
-    TA_CHECK(call_begin(ctx, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));  // no dominant kernel of its own, unless msd_impl records one
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-    TA_CHECK(ons_cross(ctx, fft != 0, out, S, T, D, cross, st));
-    TA_CHECK(call_end(ctx, st));
-    return host_finish(ctx, {{h_cross, cross, (size_t)T * S * S}});
-}
-
-// Current share of a host-facing call, queued on ctx->stream and not waited for: the labels and weights (this context's
-// atoms, labels already checked) uploaded, the (S, T, D) currents and with cross the (T, S, S) cross-correlation behind
-// them left on the device in *d_out (the Onsager buffers: one call at a time uses them).
-int cur_launch(ta_ctx* ctx, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out) {
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(check_staged(ctx));
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t T = ctx->st_T, A = ctx->st_A;
-    const int D = ctx->st_D;
-    TA_CHECK(ensure(ctx, ctx->ons_lab, sizeof(int32_t) * A));
-    if (h_w) TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * A));
-    TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)T * S * (D + S)));
-    double* out = (double*)ctx->ons_out.p;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_lab.p, h_species, sizeof(int32_t) * A, hipMemcpyHostToDevice, ctx->stream));
-    if (h_w) TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_w.p, h_w, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    TA_CHECK(order_after_staging(ctx, ctx->stream));
-    TA_CHECK(call_begin(ctx, ctx->stream));
-    TA_CHECK(cur_pm(ctx, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, T, A, D, S, (const int32_t*)ctx->ons_lab.p,
-                    h_w ? (const double*)ctx->ons_w.p : nullptr, out, cross ? out + (size_t)S * T * D : nullptr, ctx->stream));
-    *d_out = out;
-    return TA_OK;
-}
-
-// The cross-correlation of host (S, T, D) currents on this context's device, blocking, as a compute call of its own
-// (ta_current_cross; the group's ONE evaluation after its members' sums).  Needs no staged slab.
-int cur_cross_host(ta_ctx* ctx, int fft, const double* h_currents, int S, int64_t T, int D, double* h_cross) {
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    TA_CHECK(ctx->commits.flush());
-    TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)T * S * (D + S)));
-    double* out = (double*)ctx->ons_out.p;
-    double* cross = out + (size_t)S * T * D;
-    hipStream_t st = ctx->stream;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_currents, sizeof(double) * (size_t)S * T * D, hipMemcpyHostToDevice, st));
+    TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_sums, sizeof(double) * (size_t)S * T * D, hipMemcpyHostToDevice, st));
     TA_CHECK(call_begin(ctx, st));
     TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));  // no dominant kernel of its own, unless the correlator records one
     TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-    TA_CHECK(cur_cross(ctx, fft != 0, out, S, T, D, cross, st));
+    TA_CHECK(coll_cross(ctx, kCollective[kind], fft != 0, out, S, T, D, cross, st));
     TA_CHECK(call_end(ctx, st));
     return host_finish(ctx, {{h_cross, cross, (size_t)T * S * S}});
 }
@@ -2169,21 +2108,20 @@ int cur_cross_host(ta_ctx* ctx, int fft, const double* h_currents, int S, int64_
 // left on the device in *d_out; h_counts (S) or NULL: this context's atoms per species.
 int self_launch(ta_ctx* ctx, int quantity, int fft, int S, const int32_t* h_species, const double* h_w, int64_t* h_counts,
                 double** d_out) {
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(check_staged(ctx));
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t T = ctx->st_T, A = ctx->st_A;
-    const int D = ctx->st_D;
     SortPlan plan;
-    TA_CHECK(self_plan(ctx, S, h_species, A, D, ctx->stream, &plan));
-    if (h_w) TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * A));
-    TA_CHECK(ensure(ctx, ctx->self_out, sizeof(double) * (size_t)T * S));
-    if (h_w) TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_w.p, h_w, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    TA_CHECK(order_after_staging(ctx, ctx->stream));
-    TA_CHECK(call_begin(ctx, ctx->stream));
-    TA_CHECK(species_self_pm(ctx, quantity, fft != 0, ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, T, A, D, plan,
-                             h_w ? (const double*)ctx->ons_w.p : nullptr, (double*)ctx->self_out.p, ctx->stream));
+    TA_CHECK(slab_entry(
+        ctx, nullptr, ctx->stream, no_args,
+        [&](const Slab& s) -> int {
+            TA_CHECK(self_plan(ctx, S, h_species, s.A, s.D, ctx->stream, &plan));
+            if (h_w) TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * s.A));
+            TA_CHECK(ensure(ctx, ctx->self_out, sizeof(double) * (size_t)s.T * S));
+            if (h_w) TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_w.p, h_w, sizeof(double) * s.A, hipMemcpyHostToDevice, ctx->stream));
+            return TA_OK;
+        },
+        [&](const Slab& s) {
+            return species_self_pm(ctx, quantity, fft != 0, s, plan, h_w ? (const double*)ctx->ons_w.p : nullptr,
+                                   (double*)ctx->self_out.p);
+        }));
     if (h_counts)
         for (int s = 0; s < S; ++s) h_counts[s] = plan.count[s];
     *d_out = (double*)ctx->self_out.p;
@@ -2287,76 +2225,57 @@ int ta_conductivity(ta_ctx* ctx, int fft, const double* h_charges, double* h_mom
     });
 }
 
+// ta_onsager / ta_current, and ta_onsager_cross / ta_current_cross: one body each
+static int coll_host(ta_ctx* ctx, int kind, int fft, int n_species, const int32_t* h_species, const double* h_weights,
+                     double* h_sums, double* h_cross) {
+    return host_call(ctx, [&]() -> int {
+    const Collective& q = kCollective[kind];
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(coll_args(ctx, q, fft, n_species, h_species, h_sums));
+    TA_CHECK(check_staged(ctx));
+    TA_CHECK(check_labels(fail, ctx, h_species, ctx->st_A, n_species));
+    if (ctx->is_cpu) {
+        if (int rc = q.cpu(cpu_state(ctx), fft != 0, n_species, h_species, h_weights, h_sums, h_cross))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    double* d_out = nullptr;
+    TA_CHECK(ta::coll_launch(ctx, kind, fft, n_species, h_species, h_weights, h_cross != nullptr, &d_out));
+    const size_t T = (size_t)ctx->st_T, D = (size_t)ctx->st_D, S = (size_t)n_species;
+    return host_finish(ctx, {{h_sums, d_out, S * T * D}, {h_cross, d_out + S * T * D, T * S * S}});
+    });
+}
+static int coll_cross_call(ta_ctx* ctx, int kind, int fft, const double* h_sums, int n_species, int64_t n_frames, int dim,
+                           double* h_cross) {
+    return host_call(ctx, [&]() -> int {
+    const Collective& q = kCollective[kind];
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(check_fft(ctx, fft));
+    TA_CHECK(check_species_count(fail, ctx, n_species));
+    if (!h_sums || !h_cross) return fail(ctx, TA_E_INVALID, std::string(q.noun) + " or cross output is NULL");
+    if (n_frames < 1 || dim < 1 || dim > 3 || n_frames > (int64_t)1 << 30)
+        return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30, 1 <= dim <= 3");
+    if (ctx->is_cpu) {
+        if (int rc = q.cpu_cross(ctx->cpu_threads, fft != 0, h_sums, n_species, n_frames, dim, h_cross))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    return ta::coll_cross_host(ctx, kind, fft, h_sums, n_species, n_frames, dim, h_cross);
+    });
+}
 int ta_onsager(ta_ctx* ctx, int fft, int n_species, const int32_t* h_species, const double* h_weights, double* h_moments,
                double* h_cross) {
-    return host_call(ctx, [&]() -> int {
-    TA_CHECK(need_ctx(ctx));
-    TA_CHECK(ons_args(ctx, fft, n_species, h_species, h_moments));
-    TA_CHECK(check_staged(ctx));
-    TA_CHECK(check_labels(ctx, h_species, ctx->st_A, n_species));
-    if (ctx->is_cpu) {
-        if (int rc = ta::cpu::onsager(cpu_state(ctx), fft != 0, n_species, h_species, h_weights, h_moments, h_cross))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
-    }
-    double* d_out = nullptr;
-    TA_CHECK(ta::ons_launch(ctx, fft, n_species, h_species, h_weights, h_cross != nullptr, &d_out));
-    const size_t T = (size_t)ctx->st_T, D = (size_t)ctx->st_D, S = (size_t)n_species;
-    return host_finish(ctx, {{h_moments, d_out, S * T * D}, {h_cross, d_out + S * T * D, T * S * S}});
-    });
+    return coll_host(ctx, COLL_MOMENTS, fft, n_species, h_species, h_weights, h_moments, h_cross);
 }
-
 int ta_onsager_cross(ta_ctx* ctx, int fft, const double* h_moments, int n_species, int64_t n_frames, int dim, double* h_cross) {
-    return host_call(ctx, [&]() -> int {
-    TA_CHECK(need_ctx(ctx));
-    TA_CHECK(check_fft(ctx, fft));
-    TA_CHECK(check_species_count(ctx, n_species));
-    if (!h_moments || !h_cross) return fail(ctx, TA_E_INVALID, "moments or cross output is NULL");
-    if (n_frames < 1 || dim < 1 || dim > 3 || n_frames > (int64_t)1 << 30)
-        return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30, 1 <= dim <= 3");
-    if (ctx->is_cpu) {
-        if (int rc = ta::cpu::onsager_cross(ctx->cpu_threads, fft != 0, h_moments, n_species, n_frames, dim, h_cross))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
-    }
-    return ta::ons_cross_host(ctx, fft, h_moments, n_species, n_frames, dim, h_cross);
-    });
+    return coll_cross_call(ctx, COLL_MOMENTS, fft, h_moments, n_species, n_frames, dim, h_cross);
 }
-
 int ta_current(ta_ctx* ctx, int fft, int n_species, const int32_t* h_species, const double* h_weights, double* h_currents,
                double* h_cross) {
-    return host_call(ctx, [&]() -> int {
-    TA_CHECK(need_ctx(ctx));
-    TA_CHECK(cur_args(ctx, fft, n_species, h_species, h_currents));
-    TA_CHECK(check_staged(ctx));
-    TA_CHECK(check_labels(ctx, h_species, ctx->st_A, n_species));
-    if (ctx->is_cpu) {
-        if (int rc = ta::cpu::current(cpu_state(ctx), fft != 0, n_species, h_species, h_weights, h_currents, h_cross))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
-    }
-    double* d_out = nullptr;
-    TA_CHECK(ta::cur_launch(ctx, fft, n_species, h_species, h_weights, h_cross != nullptr, &d_out));
-    const size_t T = (size_t)ctx->st_T, D = (size_t)ctx->st_D, S = (size_t)n_species;
-    return host_finish(ctx, {{h_currents, d_out, S * T * D}, {h_cross, d_out + S * T * D, T * S * S}});
-    });
+    return coll_host(ctx, COLL_CURRENTS, fft, n_species, h_species, h_weights, h_currents, h_cross);
 }
-
 int ta_current_cross(ta_ctx* ctx, int fft, const double* h_currents, int n_species, int64_t n_frames, int dim, double* h_cross) {
-    return host_call(ctx, [&]() -> int {
-    TA_CHECK(need_ctx(ctx));
-    TA_CHECK(check_fft(ctx, fft));
-    TA_CHECK(check_species_count(ctx, n_species));
-    if (!h_currents || !h_cross) return fail(ctx, TA_E_INVALID, "currents or cross output is NULL");
-    if (n_frames < 1 || dim < 1 || dim > 3 || n_frames > (int64_t)1 << 30)
-        return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30, 1 <= dim <= 3");
-    if (ctx->is_cpu) {
-        if (int rc = ta::cpu::current_cross(ctx->cpu_threads, fft != 0, h_currents, n_species, n_frames, dim, h_cross))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
-    }
-    return ta::cur_cross_host(ctx, fft, h_currents, n_species, n_frames, dim, h_cross);
-    });
+    return coll_cross_call(ctx, COLL_CURRENTS, fft, h_currents, n_species, n_frames, dim, h_cross);
 }
 
 int ta_species_self(ta_ctx* ctx, int quantity, int fft, int n_species, const int32_t* h_species, const double* h_weights,
@@ -2366,7 +2285,7 @@ int ta_species_self(ta_ctx* ctx, int quantity, int fft, int n_species, const int
     TA_CHECK(self_args(ctx, quantity, fft, n_species, h_species, h_self));
     TA_CHECK(check_staged(ctx));
     if (ctx->is_cpu) {
-        TA_CHECK(check_labels(ctx, h_species, ctx->st_A, n_species));
+        TA_CHECK(check_labels(fail, ctx, h_species, ctx->st_A, n_species));
         if (int rc = ta::cpu::species_self(cpu_state(ctx), quantity == TA_SELF_MSD, fft != 0, n_species, h_species, h_weights,
                                            h_self, h_counts))
             return fail(ctx, rc, "CPU backend: out of host memory");

@@ -446,7 +446,10 @@ int conductivity(const State& s, bool fft, const double* q, double* moment, doub
     return collective ? msd(f64_slab(s.threads, s.T, 1, s.D, moment), fft, collective, nullptr) : TA_OK;
 }
 
-int onsager_cross(int threads, bool fft, const double* moments, int S, int64_t T, int D, double* cross) {
+// C (T, S, S) of the (S, T, D) sums Q by polarisation: the S^2 pseudo-particles Q_i, Q_i + Q_j, Q_i - Q_j, ONE by-particle
+// evaluation of them, C_ij = 1/4 (f(Q_i + Q_j) - f(Q_i - Q_j)).  acf false: f = the MSD (msd()), lag 0 exactly 0 (one frame:
+// no evaluation); acf true: f = the autocorrelation (vacf_fft / vacf_direct), lag 0 kept.  A pair with an all-zero sum: 0.
+static int cross_of(int threads, bool fft, bool acf, const double* sums, int S, int64_t T, int D, double* cross) {
     const int64_t P = (int64_t)S * S;
     std::vector<double> pm, bp, ts;
     try {
@@ -458,68 +461,41 @@ int onsager_cross(int threads, bool fft, const double* moments, int S, int64_t T
     }
     bool nz[8] = {};
     for (int i = 0; i < S; ++i)
-        for (int64_t k = 0; k < T * D && !nz[i]; ++k) nz[i] = moments[(size_t)i * T * D + k] != 0.0;
+        for (int64_t k = 0; k < T * D && !nz[i]; ++k) nz[i] = sums[(size_t)i * T * D + k] != 0.0;
     for (int64_t t = 0; t < T; ++t)
         for (int i = 0; i < S; ++i)
             for (int j = 0; j < S; ++j)
                 for (int d = 0; d < D; ++d) {
-                    const double mi = moments[((size_t)i * T + t) * D + d], mj = moments[((size_t)j * T + t) * D + d];
-                    pm[((size_t)t * P + i * S + j) * D + d] = i == j ? mi : i < j ? mi + mj : mi - mj;
+                    const double qi = sums[((size_t)i * T + t) * D + d], qj = sums[((size_t)j * T + t) * D + d];
+                    pm[((size_t)t * P + i * S + j) * D + d] = i == j ? qi : i < j ? qi + qj : qi - qj;
                 }
-    if (T >= 2)
-        if (int rc = msd(f64_slab(threads, T, P, D, pm.data()), fft, ts.data(), bp.data())) return rc;
+    const State v = f64_slab(threads, T, P, D, pm.data());
+    int rc = TA_OK;
+    if (acf) rc = fft ? vacf_fft(v, ts.data(), bp.data()) : vacf_direct(v, ts.data(), bp.data());
+    else if (T >= 2) rc = msd(v, fft, ts.data(), bp.data());
+    if (rc) return rc;
     for (int64_t k = 0; k < T; ++k)
         for (int i = 0; i < S; ++i)
             for (int j = 0; j < S; ++j) {
                 const int lo = i < j ? i : j, hi = i < j ? j : i;
                 const double* row = bp.data() + (size_t)k * P;
                 double c = 0.0;
-                if (k > 0 && nz[i] && nz[j]) c = i == j ? row[i * S + i] : 0.25 * (row[lo * S + hi] - row[hi * S + lo]);
+                if ((acf || k > 0) && nz[i] && nz[j]) c = i == j ? row[i * S + i] : 0.25 * (row[lo * S + hi] - row[hi * S + lo]);
                 cross[((size_t)k * S + i) * S + j] = c;
             }
     return TA_OK;
+}
+int onsager_cross(int threads, bool fft, const double* moments, int S, int64_t T, int D, double* cross) {
+    return cross_of(threads, fft, false, moments, S, T, D, cross);
+}
+int current_cross(int threads, bool fft, const double* currents, int S, int64_t T, int D, double* cross) {
+    return cross_of(threads, fft, true, currents, S, T, D, cross);
 }
 
 int onsager(const State& s, bool fft, int S, const int32_t* species, const double* w, double* moments, double* cross) {
     moments_of(s, S, species, w, moments, nullptr);
     return cross ? onsager_cross(s.threads, fft, moments, S, s.T, s.D, cross) : TA_OK;
 }
-
-// the Green-Kubo twin of onsager_cross: the pseudo-particles of the currents, their autocorrelations, lag 0 kept
-int current_cross(int threads, bool fft, const double* currents, int S, int64_t T, int D, double* cross) {
-    const int64_t P = (int64_t)S * S;
-    std::vector<double> pm, bp, ts;
-    try {
-        pm.assign((size_t)T * P * D, 0.0);
-        bp.assign((size_t)T * P, 0.0);
-        ts.assign((size_t)T, 0.0);
-    } catch (const std::bad_alloc&) {
-        return TA_E_NOMEM;
-    }
-    bool nz[8] = {};
-    for (int i = 0; i < S; ++i)
-        for (int64_t k = 0; k < T * D && !nz[i]; ++k) nz[i] = currents[(size_t)i * T * D + k] != 0.0;
-    for (int64_t t = 0; t < T; ++t)
-        for (int i = 0; i < S; ++i)
-            for (int j = 0; j < S; ++j)
-                for (int d = 0; d < D; ++d) {
-                    const double ji = currents[((size_t)i * T + t) * D + d], jj = currents[((size_t)j * T + t) * D + d];
-                    pm[((size_t)t * P + i * S + j) * D + d] = i == j ? ji : i < j ? ji + jj : ji - jj;
-                }
-    const State v = f64_slab(threads, T, P, D, pm.data());
-    if (int rc = fft ? vacf_fft(v, ts.data(), bp.data()) : vacf_direct(v, ts.data(), bp.data())) return rc;
-    for (int64_t k = 0; k < T; ++k)
-        for (int i = 0; i < S; ++i)
-            for (int j = 0; j < S; ++j) {
-                const int lo = i < j ? i : j, hi = i < j ? j : i;
-                const double* row = bp.data() + (size_t)k * P;
-                double c = 0.0;
-                if (nz[i] && nz[j]) c = i == j ? row[i * S + i] : 0.25 * (row[lo * S + hi] - row[hi * S + lo]);
-                cross[((size_t)k * S + i) * S + j] = c;
-            }
-    return TA_OK;
-}
-
 int current(const State& s, bool fft, int S, const int32_t* species, const double* w, double* currents, double* cross) {
     moments_of(s, S, species, w, currents, nullptr, false);
     return cross ? current_cross(s.threads, fft, currents, S, s.T, s.D, cross) : TA_OK;

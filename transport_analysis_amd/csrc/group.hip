@@ -314,6 +314,48 @@ int drained(ta_group* g, const std::vector<int>& who, int rc) {
     return rc;
 }
 
+// The sum over members of what each leaves on its device.  launch(i, &d) queues member i's share and returns its device
+// result; of that result every part (n doubles at offset off; h NULL: skipped) is copied into a host vector of the member's
+// own.  A copy's HIP error is the group's own failure ("<what> copy: ..."); any failure drains the members first.  Then
+// every member is waited for, each part's h zeroed and the members' values added in member order (who: the members called).
+struct MemberPart {
+    size_t off, n;
+    double* h;
+};
+template <class Launch>
+int sum_members(ta_group* g, std::vector<int>& who, const char* what, std::initializer_list<MemberPart> parts, Launch&& launch) {
+    std::vector<std::vector<double>> got(g->ctx.size());
+    size_t total = 0;
+    for (const MemberPart& p : parts) total += p.h ? p.n : 0;
+    hipError_t he = hipSuccess;
+    int rc = for_members(g, &who, [&](int i) {
+        double* d = nullptr;
+        if (const int r = launch(i, &d)) return r;
+        got[i].resize(total);  // (once: copies into it are in flight from here on)
+        double* dst = got[i].data();
+        for (const MemberPart& p : parts) {
+            if (!p.h || he != hipSuccess) continue;
+            he = hipMemcpyAsync(dst, d + p.off, sizeof(double) * p.n, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
+            dst += p.n;
+        }
+        return he == hipSuccess ? TA_OK : TA_E_HIP;
+    });
+    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string(what) + " copy: " + hipGetErrorString(he));
+    if (rc) return drained(g, who, rc);
+    if ((rc = wait_members(g, who))) return rc;
+    for (const MemberPart& p : parts)
+        if (p.h) std::fill(p.h, p.h + p.n, 0.0);
+    for (int i : who) {
+        const double* src = got[i].data();
+        for (const MemberPart& p : parts) {
+            if (!p.h) continue;
+            for (size_t k = 0; k < p.n; ++k) p.h[k] += src[k];
+            src += p.n;
+        }
+    }
+    return TA_OK;
+}
+
 // The shape of the host-facing group entries: the reporter drains every member, then fails -- an exception after the
 // members' launches lets their queued work finish first (the caller may free its arrays as soon as the call returns)
 template <class Body>
@@ -567,118 +609,44 @@ int ta_group_conductivity(ta_group* g, int fft, const double* h_charges, double*
     TAG_CHECK(check_fft(g, fft));
     if (!h_charges || !h_moment || !h_collective) return gfail(g, TA_E_INVALID, "charges, moment or collective is NULL");
     TAG_CHECK(check_staged(g));
-    const int n = (int)g->ctx.size();
-    const int64_t T = g->T;
-    const int D = g->D;
-    std::vector<std::vector<double>> mom(n), slf(n);
+    const size_t T = (size_t)g->T, D = (size_t)g->D;
     std::vector<int> who;
-    hipError_t he = hipSuccess;  // of a member's copies into mom / slf
-    int rc = for_members(g, &who, [&](int i) {
-        double* d = nullptr;
-        if (const int r = cond_launch(g->ctx[i], fft, h_charges + g->lo[i], false, h_self_lagsum != nullptr, &d)) return r;
-        mom[i].resize((size_t)T * D);
-        he = hipMemcpyAsync(mom[i].data(), d, sizeof(double) * T * D, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
-        if (he == hipSuccess && h_self_lagsum) {
-            slf[i].resize((size_t)T);
-            he = hipMemcpyAsync(slf[i].data(), d + T * (D + 1), sizeof(double) * T, hipMemcpyDeviceToHost,
-                                ctx_stream(g->ctx[i]));
-        }
-        return he == hipSuccess ? TA_OK : TA_E_HIP;
-    });
-    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string("moment copy: ") + hipGetErrorString(he));  // (the group's own failure)
-    if (rc) return drained(g, who, rc);
-    TAG_CHECK(wait_members(g, who));
-    std::fill(h_moment, h_moment + T * D, 0.0);
-    if (h_self_lagsum) std::fill(h_self_lagsum, h_self_lagsum + T, 0.0);
-    for (int i : who) {
-        for (int64_t k = 0; k < T * D; ++k) h_moment[k] += mom[i][k];
-        if (h_self_lagsum)
-            for (int64_t k = 0; k < T; ++k) h_self_lagsum[k] += slf[i][k];
-    }
-    if ((rc = cond_collective_host(g->ctx[who[0]], fft, h_moment, T, D, h_collective))) return mfail(g, who[0], rc);
+    TAG_CHECK(sum_members(g, who, "moment", {{0, T * D, h_moment}, {T * (D + 1), T, h_self_lagsum}}, [&](int i, double** d) {
+        return cond_launch(g->ctx[i], fft, h_charges + g->lo[i], false, h_self_lagsum != nullptr, d);
+    }));
+    if (const int rc = cond_collective_host(g->ctx[who[0]], fft, h_moment, g->T, g->D, h_collective)) return mfail(g, who[0], rc);
     return TA_OK;
     });
 }
 
-// Onsager: every member's species moments of its atoms (its slice of the labels and weights, the call's n_species), added
-// on the host in member order, then ONE cross MSD of the summed moments on the first member that holds atoms -- the rule
-// of ta_group_conductivity
+// Onsager moments / Green-Kubo currents: every member's species sums of its atoms (its slice of the labels and weights, the
+// call's n_species), added on the host in member order, then ONE cross term of the summed moments / currents on the first
+// member that holds atoms -- the rule of ta_group_conductivity
+static int group_collective(ta_group* g, int kind, const char* noun, int fft, int n_species, const int32_t* h_species,
+                            const double* h_weights, double* h_sums, double* h_cross) {
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
+    TAG_CHECK(check_fft(g, fft));
+    TAG_CHECK(check_species_count(gfail, g, n_species));
+    if (!h_species || !h_sums) return gfail(g, TA_E_INVALID, std::string("species labels or ") + noun + " are NULL");
+    TAG_CHECK(check_staged(g));
+    TAG_CHECK(check_labels(gfail, g, h_species, g->A, n_species));
+    std::vector<int> who;
+    TAG_CHECK(sum_members(g, who, noun, {{0, (size_t)n_species * g->T * g->D, h_sums}}, [&](int i, double** d) {
+        return coll_launch(g->ctx[i], kind, fft, n_species, h_species + g->lo[i], h_weights ? h_weights + g->lo[i] : nullptr, false, d);
+    }));
+    if (h_cross)
+        if (const int rc = coll_cross_host(g->ctx[who[0]], kind, fft, h_sums, n_species, g->T, g->D, h_cross)) return mfail(g, who[0], rc);
+    return TA_OK;
+    });
+}
 int ta_group_onsager(ta_group* g, int fft, int n_species, const int32_t* h_species, const double* h_weights,
                      double* h_moments, double* h_cross) {
-    return group_call(g, [&]() -> int {
-    TAG_CHECK(check_group(g));
-    TAG_CHECK(check_fft(g, fft));
-    if (n_species < 1 || n_species > TA_ONSAGER_MAX_SPECIES)
-        return gfail(g, TA_E_INVALID, "n_species must be 1 ... " + std::to_string(TA_ONSAGER_MAX_SPECIES));
-    if (!h_species || !h_moments) return gfail(g, TA_E_INVALID, "species labels or moments are NULL");
-    TAG_CHECK(check_staged(g));
-    for (int64_t a = 0; a < g->A; ++a)
-        if (h_species[a] < 0 || h_species[a] >= n_species)
-            return gfail(g, TA_E_INVALID, "species label " + std::to_string(h_species[a]) + " of atom " + std::to_string(a) +
-                                              " is outside 0 ... n_species - 1");
-    const int n = (int)g->ctx.size();
-    const size_t n_out = (size_t)n_species * g->T * g->D;
-    std::vector<std::vector<double>> mom(n);
-    std::vector<int> who;
-    hipError_t he = hipSuccess;  // of a member's copy into mom
-    int rc = for_members(g, &who, [&](int i) {
-        double* d = nullptr;
-        if (const int r = ons_launch(g->ctx[i], fft, n_species, h_species + g->lo[i], h_weights ? h_weights + g->lo[i] : nullptr,
-                                     false, &d))
-            return r;
-        mom[i].resize(n_out);
-        he = hipMemcpyAsync(mom[i].data(), d, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
-        return he == hipSuccess ? TA_OK : TA_E_HIP;
-    });
-    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string("moments copy: ") + hipGetErrorString(he));  // (the group's own failure)
-    if (rc) return drained(g, who, rc);
-    TAG_CHECK(wait_members(g, who));
-    std::fill(h_moments, h_moments + n_out, 0.0);
-    for (int i : who)
-        for (size_t k = 0; k < n_out; ++k) h_moments[k] += mom[i][k];
-    if (h_cross && (rc = ons_cross_host(g->ctx[who[0]], fft, h_moments, n_species, g->T, g->D, h_cross))) return mfail(g, who[0], rc);
-    return TA_OK;
-    });
+    return group_collective(g, COLL_MOMENTS, "moments", fft, n_species, h_species, h_weights, h_moments, h_cross);
 }
-
-// Green-Kubo currents: every member's species currents of its atoms, added on the host in member order, then ONE
-// cross-correlation of the summed currents on the first member that holds atoms -- the rule of ta_group_onsager
 int ta_group_current(ta_group* g, int fft, int n_species, const int32_t* h_species, const double* h_weights,
                      double* h_currents, double* h_cross) {
-    return group_call(g, [&]() -> int {
-    TAG_CHECK(check_group(g));
-    TAG_CHECK(check_fft(g, fft));
-    if (n_species < 1 || n_species > TA_ONSAGER_MAX_SPECIES)
-        return gfail(g, TA_E_INVALID, "n_species must be 1 ... " + std::to_string(TA_ONSAGER_MAX_SPECIES));
-    if (!h_species || !h_currents) return gfail(g, TA_E_INVALID, "species labels or currents are NULL");
-    TAG_CHECK(check_staged(g));
-    for (int64_t a = 0; a < g->A; ++a)
-        if (h_species[a] < 0 || h_species[a] >= n_species)
-            return gfail(g, TA_E_INVALID, "species label " + std::to_string(h_species[a]) + " of atom " + std::to_string(a) +
-                                              " is outside 0 ... n_species - 1");
-    const int n = (int)g->ctx.size();
-    const size_t n_out = (size_t)n_species * g->T * g->D;
-    std::vector<std::vector<double>> cur(n);
-    std::vector<int> who;
-    hipError_t he = hipSuccess;  // of a member's copy into cur
-    int rc = for_members(g, &who, [&](int i) {
-        double* d = nullptr;
-        if (const int r = cur_launch(g->ctx[i], fft, n_species, h_species + g->lo[i], h_weights ? h_weights + g->lo[i] : nullptr,
-                                     false, &d))
-            return r;
-        cur[i].resize(n_out);
-        he = hipMemcpyAsync(cur[i].data(), d, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
-        return he == hipSuccess ? TA_OK : TA_E_HIP;
-    });
-    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string("currents copy: ") + hipGetErrorString(he));  // (the group's own failure)
-    if (rc) return drained(g, who, rc);
-    TAG_CHECK(wait_members(g, who));
-    std::fill(h_currents, h_currents + n_out, 0.0);
-    for (int i : who)
-        for (size_t k = 0; k < n_out; ++k) h_currents[k] += cur[i][k];
-    if (h_cross && (rc = cur_cross_host(g->ctx[who[0]], fft, h_currents, n_species, g->T, g->D, h_cross))) return mfail(g, who[0], rc);
-    return TA_OK;
-    });
+    return group_collective(g, COLL_CURRENTS, "currents", fft, n_species, h_species, h_weights, h_currents, h_cross);
 }
 
 // Species self terms: every member's (n_species, n_frames) lag sums and counts of its atoms (its slice of the labels and
@@ -690,38 +658,20 @@ int ta_group_species_self(ta_group* g, int quantity, int fft, int n_species, con
     if (quantity != TA_SELF_MSD && quantity != TA_SELF_VACF)
         return gfail(g, TA_E_INVALID, "quantity must be TA_SELF_MSD (0) or TA_SELF_VACF (1)");
     TAG_CHECK(check_fft(g, fft));
-    if (n_species < 1 || n_species > TA_ONSAGER_MAX_SPECIES)
-        return gfail(g, TA_E_INVALID, "n_species must be 1 ... " + std::to_string(TA_ONSAGER_MAX_SPECIES));
+    TAG_CHECK(check_species_count(gfail, g, n_species));
     if (!h_species || !h_self) return gfail(g, TA_E_INVALID, "species labels or self output are NULL");
     TAG_CHECK(check_staged(g));
-    for (int64_t a = 0; a < g->A; ++a)
-        if (h_species[a] < 0 || h_species[a] >= n_species)
-            return gfail(g, TA_E_INVALID, "species label " + std::to_string(h_species[a]) + " of atom " + std::to_string(a) +
-                                              " is outside 0 ... n_species - 1");
-    const int n = (int)g->ctx.size();
-    const size_t n_out = (size_t)n_species * g->T;
-    std::vector<std::vector<double>> slf(n);
-    std::vector<std::vector<int64_t>> cnt(n);
+    TAG_CHECK(check_labels(gfail, g, h_species, g->A, n_species));
+    std::vector<std::vector<int64_t>> cnt(g->ctx.size());
     std::vector<int> who;
-    hipError_t he = hipSuccess;  // of a member's copy into slf
-    int rc = for_members(g, &who, [&](int i) {
-        double* d = nullptr;
+    TAG_CHECK(sum_members(g, who, "self terms", {{0, (size_t)n_species * g->T, h_self}}, [&](int i, double** d) {
         cnt[i].assign(n_species, 0);
-        if (const int r = self_launch(g->ctx[i], quantity, fft, n_species, h_species + g->lo[i],
-                                      h_weights ? h_weights + g->lo[i] : nullptr, cnt[i].data(), &d))
-            return r;
-        slf[i].resize(n_out);
-        he = hipMemcpyAsync(slf[i].data(), d, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
-        return he == hipSuccess ? TA_OK : TA_E_HIP;
-    });
-    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string("self terms copy: ") + hipGetErrorString(he));  // (the group's own failure)
-    if (rc) return drained(g, who, rc);
-    TAG_CHECK(wait_members(g, who));
-    std::fill(h_self, h_self + n_out, 0.0);
-    if (h_counts) std::fill(h_counts, h_counts + n_species, (int64_t)0);
-    for (int i : who) {
-        for (size_t k = 0; k < n_out; ++k) h_self[k] += slf[i][k];
-        if (h_counts)
+        return self_launch(g->ctx[i], quantity, fft, n_species, h_species + g->lo[i], h_weights ? h_weights + g->lo[i] : nullptr,
+                           cnt[i].data(), d);
+    }));
+    if (h_counts) {
+        std::fill(h_counts, h_counts + n_species, (int64_t)0);
+        for (int i : who)
             for (int s = 0; s < n_species; ++s) h_counts[s] += cnt[i][s];
     }
     return TA_OK;

@@ -76,15 +76,30 @@ int host_finish(ta_ctx* ctx, std::initializer_list<HostCopy> copies);
 // host_wait; and Phi of a host (n_frames, dim) moment on the context's device, blocking
 int cond_launch(ta_ctx* ctx, int fft, const double* h_q, bool coll, bool self, double** d_out);
 int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T, int D, double* h_coll);
-// api.hip, for group.hip: one context's ta_onsager share (its staged slab 0 with its atoms' labels h_species and weights
-// h_w or NULL, n_species the call's), queued: *d_out = the (n_species, n_frames, dim) moments, valid after host_wait; and
-// the cross MSD (n_frames, S, S) of host moments (S, n_frames, dim) on the context's device, blocking
-int ons_launch(ta_ctx* ctx, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out);
-int ons_cross_host(ta_ctx* ctx, int fft, const double* h_moments, int S, int64_t T, int D, double* h_cross);
-// api.hip, for group.hip: the same two for ta_current: one context's (n_species, n_frames, dim) currents of its staged
-// velocity slab 0, queued; and the cross-correlation (n_frames, S, S) of host currents on the context's device, blocking
-int cur_launch(ta_ctx* ctx, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out);
-int cur_cross_host(ta_ctx* ctx, int fft, const double* h_currents, int S, int64_t T, int D, double* h_cross);
+// api.hip, for group.hip: the two species-collective quantities, Onsager moments (ta_onsager*) and Green-Kubo currents
+// (ta_current*), share one host path (api.hip's Collective table, indexed by `kind`).  One context's share (its staged
+// slab 0 with its atoms' labels h_species and weights h_w or NULL, n_species the call's), queued: *d_out = the (n_species,
+// n_frames, dim) sums, valid after host_wait; and the cross term (n_frames, S, S) of host sums (S, n_frames, dim) on the
+// context's device, blocking
+enum CollKind { COLL_MOMENTS = 0, COLL_CURRENTS = 1 };
+int coll_launch(ta_ctx* ctx, int kind, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out);
+int coll_cross_host(ta_ctx* ctx, int kind, int fft, const double* h_sums, int S, int64_t T, int D, double* h_cross);
+// the species-count and host-label checks of a context (fail, ctx) or a group (gfail, g): the same messages for both; the
+// atom index is relative to h_species
+template <class Fail, class Owner>
+static int check_species_count(Fail fail, Owner* owner, int S) {
+    if (S < 1 || S > TA_ONSAGER_MAX_SPECIES)
+        return fail(owner, TA_E_INVALID, "n_species must be 1 ... " + std::to_string(TA_ONSAGER_MAX_SPECIES));
+    return TA_OK;
+}
+template <class Fail, class Owner>
+static int check_labels(Fail fail, Owner* owner, const int32_t* h_species, int64_t n, int S) {
+    for (int64_t a = 0; a < n; ++a)
+        if (h_species[a] < 0 || h_species[a] >= S)
+            return fail(owner, TA_E_INVALID, "species label " + std::to_string(h_species[a]) + " of atom " + std::to_string(a) +
+                                                 " is outside 0 ... n_species - 1");
+    return TA_OK;
+}
 // api.hip, for group.hip: one context's ta_species_self share (its staged slab 0 with its atoms' labels and weights, the
 // call's n_species; labels checked here), queued: *d_out = the (n_species, n_frames) self lag sums, valid after host_wait;
 // h_counts (n_species) or NULL: its atoms per species
