@@ -232,7 +232,8 @@ int ta_conductivity(ta_ctx *ctx, int fft, const double *h_charges, double *h_mom
  *                   NULL h_species / h_moments, fft other than 0 / 1, n_species out of range, a label outside
  *                   0 ... n_species - 1 (checked on the host before anything is uploaded): TA_E_INVALID; nothing staged:
  *                   TA_E_STATE.  CPU backend: the same in C++/OpenMP.  Timings: the pass is the main kernel unless an FFT
- *                   evaluation follows it (ta_kernel_timeline names it k_species_moment).
+ *                   evaluation follows it (ta_kernel_timeline names it k_species_moment; k_species_current of
+ *                   ta_current is the same kernel without the shift, on the slab's own element type).
  * ta_onsager_cross: C (n_frames, S, S) of caller-provided moments (S, n_frames, dim) alone, e.g. the sum of several shards'
  *                   moments (moments add up over shards, C does not).  Needs no staged slab and leaves one untouched.   */
 #define TA_ONSAGER_MAX_SPECIES 8

@@ -51,7 +51,7 @@ def n_cu():
 
 
 def current_groups(T, n_pairs, S):
-    """k_species_current's group count (onsager.hip: species_moment_parts; 4, 2, 1 frames per thread for S <= 2, 4, 8)."""
+    """k_species_current's group count (species_sum.hip: species_sum_parts; 4, 2, 1 frames per thread for S <= 2, 4, 8)."""
     rows = 4 if S <= 2 else 2 if S <= 4 else 1
     n_tb = -(-T // (256 * rows))
     return max(1, min(-(-8 * n_cu() // n_tb), n_pairs, 1024))

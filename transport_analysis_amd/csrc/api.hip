@@ -946,7 +946,7 @@ int cond_args(ta_ctx* ctx, int fft, const void* charges, const void* moment) {
     return TA_OK;
 }
 
-// ---- species-collective quantities: Onsager moments (onsager.hip), Green-Kubo currents (current.hip) ----------------
+// ---- species-collective quantities: Onsager moments, Green-Kubo currents (species_sum.hip) ---------------------------
 // Per-species sums over atoms Q_s[t, d] in ONE pass over the slab, and their cross-correlation C[k, i, j] by polarisation.
 // The two quantities run the same host code; Collective holds everything that differs between them.
 
@@ -956,23 +956,17 @@ int acf_impl(ta_ctx* ctx, bool fft, const double* pm, int64_t pitch, int64_t T, 
     if (fft) return fft_impl(ctx, pm, pitch, T, A, D, d_lagsum, d_bp, ld_bp, st);
     return direct_impl(ctx, MODE_VACF, pm, nullptr, nullptr, T, A, D, pitch, 1.0, d_lagsum, d_bp, ld_bp, st);
 }
-// k_species_moment reads float64 slabs only: the slab type is the caller's business (widen_f32)
-hipError_t pass_species_moment(const void* pos, bool, long pitch, long T, long n_cols, int D, int S, const int* species,
-                               const double* w, double* partial, int n_parts, hipStream_t st) {
-    return launch_species_moment((const double*)pos, pitch, T, n_cols, D, S, species, w, partial, n_parts, st);
-}
 
 struct Collective {
     const char* noun;       // of the sums, in messages
-    const char* pass_name;  // the pass that forms every species' sum: the call's main kernel
-    hipError_t (*pass)(const void* pm, bool f32, long pitch, long T, long n_cols, int D, int S, const int* species,
-                       const double* w, double* partial, int n_parts, hipStream_t st);
-    bool widen_f32;  // a float32 slab gets a float64 copy first (as cond_pm does), or the pass reads it as it is
+    const char* pass_name;  // the pass that forms every species' sum (k_species_sum): the call's main kernel
+    // the pass subtracts frame 0.  The shifted pass reads float64 only, so this also says that a float32 slab gets a
+    // float64 copy first (as cond_pm does); without it the pass reads the slab as it is
+    bool shift;
     // the (T, S^2) by-particle lag sums of the pseudo-particles under the polarisation step
     int (*corr)(ta_ctx*, bool fft, const double* pm, int64_t pitch, int64_t T, int64_t A, int D, double* d_lagsum, double* d_bp,
                 int64_t ld_bp, hipStream_t st);
-    const char* finish_name;
-    hipError_t (*finish)(const double* bp, int S, long T, const int* nz, double* C, hipStream_t st);
+    const char* finish_name;  // of k_cross_finish
     bool lag0;  // C[0] is kept (<Q_i . Q_j>), or exactly 0 (a mean squared difference: one frame needs no kernel at all)
     // the CPU backend's whole call and its cross term
     int (*cpu)(const ta::cpu::State&, bool fft, int S, const int32_t* species, const double* w, double* sums, double* cross);
@@ -981,15 +975,13 @@ struct Collective {
 // indexed by ta::CollKind.  Moments: Q = w (x - x[0]), C_ij = 1/4 (MSD(M_i + M_j) - MSD(M_i - M_j)) by the EinsteinMSD
 // dispatch.  Currents: Q = w v of a slab of either element type, C_ij = 1/4 (ACF(J_i + J_j) - ACF(J_i - J_j)) by the VACF's.
 constexpr Collective kCollective[2] = {
-    {"moments", "k_species_moment", pass_species_moment, true, msd_impl, "k_onsager_finish", launch_onsager_finish, false,
-     ta::cpu::onsager, ta::cpu::onsager_cross},
-    {"currents", "k_species_current", launch_species_current, false, acf_impl, "k_current_finish", launch_current_finish, true,
-     ta::cpu::current, ta::cpu::current_cross},
+    {"moments", "k_species_moment", true, msd_impl, "k_onsager_finish", false, ta::cpu::onsager, ta::cpu::onsager_cross},
+    {"currents", "k_species_current", false, acf_impl, "k_current_finish", true, ta::cpu::current, ta::cpu::current_cross},
 };
 
 // C[k, i, j] of the (S, T, D) sums at d_sums into d_cross (T, S, S), by polarisation in ONE q.corr call: the S^2
 // pseudo-particles Q_i, Q_i + Q_j, Q_i - Q_j as a pair-major slab (k_onsager_combos, in the Onsager workspaces), their
-// (T, S^2) by-particle lag sums with the call's fft, then q.finish.
+// (T, S^2) by-particle lag sums with the call's fft, then the finish.
 int coll_cross(ta_ctx* ctx, const Collective& q, bool fft, const double* d_sums, int S, int64_t T, int D, double* d_cross,
                hipStream_t st) {
     const int64_t P = (int64_t)S * S, pitch = pm_pitch(T);
@@ -1005,7 +997,7 @@ int coll_cross(ta_ctx* ctx, const Collective& q, bool fft, const double* d_sums,
     TA_HIP_TRY(ctx, hipMemsetAsync(nz, 0, sizeof(int) * TA_ONSAGER_MAX_SPECIES, st));
     TA_LAUNCH(ctx, "k_onsager_combos", st, launch_onsager_combos(d_sums, S, (long)T, D, (long)pitch, (double*)ctx->ons_pm.p, nz, st));
     TA_CHECK(q.corr(ctx, fft, (const double*)ctx->ons_pm.p, pitch, T, P, D, lagsum, bp, P, st));
-    TA_LAUNCH(ctx, q.finish_name, st, q.finish(bp, S, (long)T, nz, d_cross, st));
+    TA_LAUNCH(ctx, q.finish_name, st, launch_cross_finish(bp, S, (long)T, nz, q.lag0, d_cross, st));
     return TA_OK;
 }
 
@@ -1018,14 +1010,14 @@ int coll_pm(ta_ctx* ctx, const Collective& q, bool fft, const Slab& s, int S, co
     if (n_cols >= (int64_t)1 << 31)
         return fail(ctx, TA_E_INVALID, std::string("Onsager ") + q.noun + ": n_atoms * dim must be below 2^31");
     const void* pm = s.pm;
-    const bool widen = s.f32 && q.widen_f32;
+    const bool widen = s.f32 && q.shift;
     if (widen) TA_CHECK(widen_input(ctx, 0, s.pitch, n_cols, s.st, &pm));
-    const int n_parts = species_moment_parts(ctx->n_cu, S, (long)T, (long)n_cols);
+    const int n_parts = species_sum_parts(ctx->n_cu, S, (long)T, (long)n_cols);
     const size_t n_out = (size_t)S * T * s.D;
     TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)n_parts * n_out));
     TA_LAUNCH_MAIN(ctx, q.pass_name, s.st,
-                   q.pass(pm, s.f32 && !widen, (long)s.pitch, (long)T, (long)n_cols, s.D, S, d_species, d_w,
-                          (double*)ctx->ons_part.p, n_parts, s.st));
+                   launch_species_sum(pm, s.f32 && !widen, q.shift, (long)s.pitch, (long)T, (long)n_cols, s.D, S, d_species, d_w,
+                                      (double*)ctx->ons_part.p, n_parts, s.st));
     TA_LAUNCH(ctx, "k_sum_partials", s.st, launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)n_out, d_sums, s.st));
     if (d_cross) TA_CHECK(coll_cross(ctx, q, fft, d_sums, S, T, s.D, d_cross, s.st));
     return call_end(ctx, s.st);
@@ -2377,7 +2369,7 @@ int ta_compound(ta_ctx* ctx, int64_t n_compounds, const int64_t* h_offsets, cons
         const double* d_w = (const double*)ctx->comp_plan.p + n_int / 2;
         const double* d_F = nullptr;
         if (h_frame_weights) {  // F = the one-species "current" of the slab with w = u: the slab read as it is
-            const int n_parts = species_moment_parts(ctx->n_cu, 1, (long)T, (long)n_cols);
+            const int n_parts = species_sum_parts(ctx->n_cu, 1, (long)T, (long)n_cols);
             TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)n_parts * T * D));
             TA_CHECK(ensure(ctx, ctx->ons_lab, sizeof(int32_t) * (size_t)A));
             TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * (size_t)A));
@@ -2388,11 +2380,11 @@ int ta_compound(ta_ctx* ctx, int64_t n_compounds, const int64_t* h_offsets, cons
         }
         TA_CHECK(call_begin(ctx, st));
         if (d_F) {
-            const int n_parts = species_moment_parts(ctx->n_cu, 1, (long)T, (long)n_cols);
+            const int n_parts = species_sum_parts(ctx->n_cu, 1, (long)T, (long)n_cols);
             TA_LAUNCH(ctx, "k_species_current", st,
-                      launch_species_current(ctx->d_slabs[0], ctx->st_dev_f32, (long)pitch, (long)T, (long)n_cols, D, 1,
-                                             (const int*)ctx->ons_lab.p, (const double*)ctx->ons_w.p, (double*)ctx->ons_part.p,
-                                             n_parts, st));
+                      launch_species_sum(ctx->d_slabs[0], ctx->st_dev_f32, false, (long)pitch, (long)T, (long)n_cols, D, 1,
+                                         (const int*)ctx->ons_lab.p, (const double*)ctx->ons_w.p, (double*)ctx->ons_part.p,
+                                         n_parts, st));
             TA_LAUNCH(ctx, "k_sum_partials", st,
                       launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)(T * D), (double*)ctx->comp_f.p, st));
         }

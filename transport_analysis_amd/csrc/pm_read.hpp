@@ -1,0 +1,100 @@
+// pm_read.hpp — reading a pair-major slab in its own element type, and writing whole pairs of a float64 one: the pieces
+// shared by k_species_sum (species_sum.hip), k_species_sort (species_self.hip) and k_compound (compound.hip).
+//
+// A pair is `pitch` rows of two columns along time (pitch a multiple of 8, T <= pitch frames are live).  Every load is 16
+// bytes: row t of a float64 pair, rows 2 q, 2 q + 1 of a float32 one (8-byte rows), widened in registers.  The rules:
+//   * a load that would start at or past row T reads row 0 instead (its value is never stored, or adds a zero);
+//   * with an odd T the last float32 load's second row is row T < pitch: nothing is read outside the pair's pitch rows;
+//   * selects work on loaded VALUES with constant destinations (a select between two elements of a local array comes back
+//     from the compiler as a runtime index, and the array then lives in scratch or LDS).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <type_traits>
+
+namespace ta {
+
+constexpr int kPmThreads = 256;  // threads per workgroup of every kernel here
+constexpr int kPmFrames = 4;     // frames per thread of the kernels that walk units: a workgroup covers 1024 consecutive frames
+
+// The frame of slot i of a thread whose workgroup starts at frame tb (a multiple of 2 kPmThreads) and gives each thread F
+// slots (kPmFrames, or the species sum's ROWS).  float64: tb + tid + 256 i, one load per slot.  float32: 2 (tb / 2 + tid + 256 (i / 2)) + i % 2, one load per two
+// slots (F even), the workgroup's loads of a pair 4 KiB in a row.
+template <bool F32>
+__device__ __forceinline__ long pm_frame(long tb, int i) {
+    if constexpr (F32) return tb + 2 * ((long)threadIdx.x + kPmThreads * (i / 2)) + i % 2;
+    else return tb + threadIdx.x + kPmThreads * i;
+}
+
+// Column c + j of an atom (c its first column, odd = c & 1) is element j + odd of the source pairs (ax, ay), (bx, by) that
+// cover its D columns: one pair for D = 1, 2 (b unused), two for D = 3
+template <int D, class V>
+__device__ __forceinline__ void pm_pick(V ax, V ay, V bx, V by, bool odd, double (&out)[3]) {
+    if constexpr (D == 2) {
+        out[0] = (double)ax, out[1] = (double)ay;  // (an atom's first column is even)
+    } else {
+        out[0] = (double)(odd ? ay : ax);
+        if constexpr (D == 3) out[1] = (double)(odd ? bx : ay), out[2] = (double)(odd ? by : bx);
+    }
+}
+
+// The one or two source pairs that cover an atom's D columns (atom D < 2^31: the launchers)
+template <class E, int D>
+struct PmAtom {
+    static constexpr bool kF32 = std::is_same_v<E, float>;
+    using Row = std::conditional_t<kF32, float4, double2>;  // what one 16-byte load gives
+    const Row* src;  // the first pair
+    long next;       // loads from it to the second (D = 3)
+    bool odd;
+    __device__ __forceinline__ PmAtom(const E* __restrict__ x, long pitch, unsigned atom)
+        : next(kF32 ? pitch / 2 : pitch), odd((atom * (unsigned)D) & 1) {
+        src = reinterpret_cast<const Row*>(x) + (long)((atom * (unsigned)D) >> 1) * next;
+    }
+    // load i of both pairs, picked into one frame's columns (float64) or two consecutive frames' (float32)
+    __device__ __forceinline__ void load(long i, double (&lo)[3], double (&hi)[3]) const {
+        const Row qa = src[i], qb = D == 3 ? src[next + i] : qa;
+        pm_pick<D>(qa.x, qa.y, qb.x, qb.y, odd, lo);
+        if constexpr (kF32) pm_pick<D>(qa.z, qa.w, qb.z, qb.w, odd, hi);
+    }
+};
+
+// The D columns of one atom in the thread's frames ...
+template <class E, int D>
+__device__ __forceinline__ void pm_load(const PmAtom<E, D>& a, long T, long tb, double (&col)[kPmFrames][3]) {
+    constexpr bool kF32 = PmAtom<E, D>::kF32;
+#pragma unroll
+    for (int f = 0; f < kPmFrames; f += kF32 ? 2 : 1) {
+        const long t = pm_frame<kF32>(tb, f);  // (float32: even)
+        a.load(t < T ? (kF32 ? t / 2 : t) : 0, col[f], col[kF32 ? f + 1 : f]);
+    }
+}
+// ... and in frame 0 (one address for the whole workgroup)
+template <class E, int D>
+__device__ __forceinline__ void pm_load0(const PmAtom<E, D>& a, double (&col0)[3]) {
+    double unused[3];
+    a.load(0, col0, unused);
+}
+
+// A work unit is two consecutive items (atoms, compounds) of D columns: 2 D columns = D WHOLE destination pairs from
+// dst on, so every store is a full 16-byte row and a wave's stores of one pair are contiguous along time.  A unit that
+// holds one item (its v[D ...] are zeros) is n_out = ceil(D / 2) pairs, the phantom column of an odd D written as 0:
+// nothing behind it is touched.  This is row t < pitch of a unit: the callers write every row of their frames, those
+// >= T (live == false) as zeros.  (The loop over a thread's frames stays in the kernels: k_species_sort is at the
+// SGPR limit with its plan, and with that loop in here two of its six instantiations came out one VGPR larger.)
+template <int D>
+__device__ __forceinline__ void pm_store_row(double2* dst, long pitch, long t, bool live, int n_out, const double (&v)[2 * D]) {
+#pragma unroll
+    for (int j = 0; j < D; ++j)
+        if (j < n_out) dst[j * pitch + t] = live ? double2{v[2 * j], v[2 * j + 1]} : double2{0.0, 0.0};
+}
+
+// The grid of a kernel that walks units: (frame blocks of the pitch) x (groups of units), about sixteen workgroups per CU,
+// at most one group per unit
+inline dim3 pm_unit_grid(int n_cu, long pitch, long n_units) {
+    const long n_tb = (pitch + kPmThreads * kPmFrames - 1) / (kPmThreads * kPmFrames);
+    const long want = (16L * n_cu + n_tb - 1) / n_tb;
+    return dim3((unsigned)n_tb, (unsigned)std::max(1L, std::min({want, n_units, 65535L})));
+}
+
+}  // namespace ta

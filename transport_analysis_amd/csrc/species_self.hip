@@ -10,52 +10,26 @@
 // reused between calls.  No atomics, every destination element has one writer: the same bits from run to run.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <type_traits>
 
+#include "pm_read.hpp"
 #include "ta_internal.hpp"
 
 namespace ta {
 namespace {
 
-constexpr int kSortThreads = 256, kSortFrames = 4;  // a workgroup covers 1024 consecutive frames, a thread four of them
-
-// Column c + j of an atom (c its first column, odd = c & 1) is element j + odd of the source pairs (ax, ay), (bx, by) that
-// cover it; the selects work on loaded VALUES with constant destinations (a select between two array elements comes back
-// from the compiler as a runtime index, and the array then lives in scratch or LDS)
-template <int D, class V>
-__device__ __forceinline__ void sort_pick(V ax, V ay, V bx, V by, bool odd, double (&out)[3]) {
-    if constexpr (D == 2) {
-        out[0] = (double)ax, out[1] = (double)ay;  // (an atom's first column is even)
-    } else {
-        out[0] = (double)(odd ? ay : ax);
-        if constexpr (D == 3) out[1] = (double)(odd ? bx : ay), out[2] = (double)(odd ? by : bx);
-    }
-}
-
-// A work unit is two consecutive atoms (2 u, 2 u + 1) of one species in sorted order: 2 D columns = D WHOLE destination
-// pairs, so every store is a full 16-byte row and a wave's stores of one pair are contiguous along time.  The last
-// unit of a species with an odd count holds one atom: ceil(D / 2) pairs, the phantom column (odd D) written as 0 --
-// nothing of the next species' block is touched.  Each source atom is read as the whole source pairs that cover its D
-// columns (one pair for D = 1, 2, two for D = 3), 16-byte loads along time; the half that belongs to a neighbouring
-// atom is that atom's unit's own load a moment earlier or later (cache).
-//   float64 slab: a load = row t of a pair; the thread's frames are tb + tid + 256 i, i < 4
-//   float32 slab: a load = rows 2 q, 2 q + 1 of a pair (8-byte rows), widened in registers; q = tb / 2 + tid + 256 i, i < 2
-// Workgroup (bx, g): frames [1024 bx, 1024 bx + 1024) of the pitch (every row < pitch is written, those >= T as zeros; a
-// load that would start at or past row T reads row 0 instead), units g, g + G, ... (G = gridDim.y).  Which unit, its
-// species, atoms, weights and column parity depend on blockIdx and the loop counter only: scalar registers.
+// A work unit (pm_read.hpp) is two consecutive atoms (2 u, 2 u + 1) of one species in sorted order; the last unit of a
+// species with an odd count holds one atom, and nothing of the next species' block is touched.  Each source atom is read
+// as the whole source pairs that cover its D columns; the half that belongs to a neighbouring atom is that atom's unit's
+// own load a moment earlier or later (cache).  Workgroup (bx, g): frames [1024 bx, 1024 bx + 1024) of the pitch, units g,
+// g + G, ... (G = gridDim.y).  Which unit, its species, atoms, weights and column parity depend on blockIdx and the loop
+// counter only: scalar registers.
 template <class E, int D>
-__global__ void __launch_bounds__(kSortThreads)
+__global__ void __launch_bounds__(kPmThreads)
     k_species_sort(const E* __restrict__ x, long pitch, long T, SortPlan plan, const int* __restrict__ order,
                    const double* __restrict__ w, int shift, double* __restrict__ W) {
-    constexpr bool kF32 = std::is_same_v<E, float>;
-    constexpr int NP = D == 3 ? 2 : 1;  // source pairs per atom
-    constexpr int F = kSortFrames;
-    const long tb = (long)blockIdx.x * (kSortThreads * F);
-    auto frame = [&](int f) -> long {
-        if constexpr (kF32) return 2 * (tb / 2 + threadIdx.x + kSortThreads * (f / 2)) + f % 2;
-        else return tb + threadIdx.x + kSortThreads * f;
-    };
+    constexpr int F = kPmFrames;
+    const long tb = (long)blockIdx.x * (kPmThreads * F);
     for (int unit = blockIdx.y; unit < plan.n_units; unit += gridDim.y) {
         // the unit's species: the last one whose first unit is not past it (constant indices: the plan stays in SGPRs)
         int u0 = 0, pos0 = 0, cnt = plan.count[0];
@@ -71,33 +45,10 @@ __global__ void __launch_bounds__(kSortThreads)
         double val[F][2 * D];
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
-            const unsigned c = atom[a] * (unsigned)D;  // (n_atoms dim < 2^31: launch_species_sort)
-            const bool odd = c & 1;
-            // the D columns of the atom in every frame of the thread, and in the first frame
+            const PmAtom<E, D> src(x, pitch, atom[a]);
             double col[F][3], col0[3];
-            if constexpr (!kF32) {
-                const double2* src = reinterpret_cast<const double2*>(x) + (long)(c >> 1) * pitch;
-                const double2 a0 = src[0], b0 = NP == 2 ? src[pitch] : a0;  // (one address for the whole workgroup)
-                sort_pick<D>(a0.x, a0.y, b0.x, b0.y, odd, col0);
-#pragma unroll
-                for (int f = 0; f < F; ++f) {
-                    const long t = frame(f), i = t < T ? t : 0;
-                    const double2 qa = src[i], qb = NP == 2 ? src[pitch + i] : qa;
-                    sort_pick<D>(qa.x, qa.y, qb.x, qb.y, odd, col[f]);
-                }
-            } else {
-                const long hp = pitch / 2;
-                const float4* src = reinterpret_cast<const float4*>(x) + (long)(c >> 1) * hp;
-                const float4 a0 = src[0], b0 = NP == 2 ? src[hp] : a0;
-                sort_pick<D>(a0.x, a0.y, b0.x, b0.y, odd, col0);
-#pragma unroll
-                for (int f = 0; f < F; f += 2) {
-                    const long t = frame(f), i = t < T ? t / 2 : 0;  // t is even
-                    const float4 qa = src[i], qb = NP == 2 ? src[hp + i] : qa;
-                    sort_pick<D>(qa.x, qa.y, qb.x, qb.y, odd, col[f]);
-                    sort_pick<D>(qa.z, qa.w, qb.z, qb.w, odd, col[f + 1]);
-                }
-            }
+            pm_load0(src, col0);
+            pm_load(src, T, tb, col);
             // the shift comes before the weight (k_cond_moment's W)
 #pragma unroll
             for (int j = 0; j < D; ++j) {
@@ -106,16 +57,13 @@ __global__ void __launch_bounds__(kSortThreads)
                 for (int f = 0; f < F; ++f) val[f][a * D + j] = a == 0 || two ? wt[a] * (col[f][j] - first) : 0.0;
             }
         }
-        const int n_out = two ? D : (D + 1) / 2;  // whole pairs of this unit inside its species' block
         double2* dst = reinterpret_cast<double2*>(W) + (dp0 + (long)D * (unit - u0)) * pitch;
+        const int n_out = two ? D : (D + 1) / 2;
 #pragma unroll
         for (int f = 0; f < F; ++f) {
-            const long t = frame(f);
+            const long t = pm_frame<std::is_same_v<E, float>>(tb, f);
             if (t >= pitch) continue;
-            const bool live = t < T;
-#pragma unroll
-            for (int j = 0; j < D; ++j)
-                if (j < n_out) dst[j * pitch + t] = live ? double2{val[f][2 * j], val[f][2 * j + 1]} : double2{0.0, 0.0};
+            pm_store_row<D>(dst, pitch, t, t < T, n_out, val[f]);
         }
     }
 }
@@ -123,7 +71,7 @@ __global__ void __launch_bounds__(kSortThreads)
 template <class E, int D>
 void sort_launch(dim3 grid, hipStream_t st, const void* x, long pitch, long T, const SortPlan& plan, const int* order,
                  const double* w, int shift, double* W) {
-    hipLaunchKernelGGL((k_species_sort<E, D>), grid, dim3(kSortThreads), 0, st, (const E*)x, pitch, T, plan, order, w, shift, W);
+    hipLaunchKernelGGL((k_species_sort<E, D>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, plan, order, w, shift, W);
 }
 template <class E>
 void sort_launch_dim(int D, dim3 grid, hipStream_t st, const void* x, long pitch, long T, const SortPlan& plan, const int* order,
@@ -159,10 +107,7 @@ hipError_t launch_species_sort(int n_cu, const void* x, bool f32, long pitch, lo
                                const int* order, const double* w, bool shift, double* W, hipStream_t st) {
     if (D < 1 || D > 3 || n_cols < 1 || n_cols >= (1L << 31) || (pitch & 7) || T < 1 || T > pitch || plan.n_units < 1)
         return hipErrorInvalidValue;
-    // about sixteen workgroups per CU over the frame blocks, at most one group per unit
-    const long n_tb = (pitch + kSortThreads * kSortFrames - 1) / (kSortThreads * kSortFrames);
-    const long want = (16L * n_cu + n_tb - 1) / n_tb;
-    const dim3 grid((unsigned)n_tb, (unsigned)std::max(1L, std::min({want, (long)plan.n_units, 65535L})));
+    const dim3 grid = pm_unit_grid(n_cu, pitch, plan.n_units);
     if (f32) sort_launch_dim<float>(D, grid, st, x, pitch, T, plan, order, w, shift, W);
     else sort_launch_dim<double>(D, grid, st, x, pitch, T, plan, order, w, shift, W);
     return hipGetLastError();

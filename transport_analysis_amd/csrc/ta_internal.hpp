@@ -208,26 +208,18 @@ int cond_moment_parts(int n_cu, long T, long n_cols);
 hipError_t launch_cond_moment(const double* pos, long pitch, long T, long n_cols, int D, const double* q, double* partial,
                               int n_parts, double* W, hipStream_t st);
 
-// onsager.hip: the species moments M[s, t, d] = sum_{n: species[n] = s} w_n (x[t, n, d] - x[0, n, d]) of a float64 pair-major
-// slab in one pass, as n_parts partial sums partial [n_parts][S][T][D] (written in full; k_sum_partials adds them in
-// order); species: (n_atoms,) int32 device labels, one outside [0, S) is skipped; w: (n_atoms,) weights or NULL (all 1).
-// combos: the pair-major slab (pitch rows per pair) of the S^2 pseudo-particles M_i, M_i + M_j, M_i - M_j of the moments
-// M (S, T, D), and nz[s] != 0 where M_s has a non-zero element (nz zeroed by the caller); finish: C (T, S, S) from their
-// (T, S^2) by-particle MSDs
-int species_moment_parts(int n_cu, int S, long T, long n_cols);
-hipError_t launch_species_moment(const double* pos, long pitch, long T, long n_cols, int D, int S, const int* species,
-                                 const double* w, double* partial, int n_parts, hipStream_t st);
+// species_sum.hip: the species sums Q[s, t, d] = sum_{n: species[n] = s} w_n (x[t, n, d] - shift x[0, n, d]) of a pair-major
+// slab of float64 or (f32, without shift only) float32 elements in one pass over it as it is, as n_parts partial sums
+// partial [n_parts][S][T][D] (written in full; n_parts from species_sum_parts; k_sum_partials adds them in order);
+// species: (n_atoms,) int32 device labels, one outside [0, S) is skipped; w: (n_atoms,) weights or NULL (all 1).
+// combos: the pair-major slab (pitch rows per pair) of the S^2 pseudo-particles Q_i, Q_i + Q_j, Q_i - Q_j of the sums
+// Q (S, T, D), and nz[s] != 0 where Q_s has a non-zero element (nz zeroed by the caller); finish: C (T, S, S) from their
+// (T, S^2) by-particle lag sums, lag 0 kept (lag0) or exactly 0
+int species_sum_parts(int n_cu, int S, long T, long n_cols);
+hipError_t launch_species_sum(const void* pm, bool f32, bool shift, long pitch, long T, long n_cols, int D, int S,
+                              const int* species, const double* w, double* partial, int n_parts, hipStream_t st);
 hipError_t launch_onsager_combos(const double* M, int S, long T, int D, long pitch, double* pm, int* nz, hipStream_t st);
-hipError_t launch_onsager_finish(const double* bp, int S, long T, const int* nz, double* C, hipStream_t st);
-
-// current.hip: the species currents J[s, t, d] = sum_{n: species[n] = s} w_n v[t, n, d] of a pair-major slab of float64 or
-// (f32) float32 elements in one pass over it as it is, as n_parts partial sums partial [n_parts][S][T][D] (written in
-// full; n_parts from species_moment_parts; k_sum_partials adds them in order); species, w as launch_species_moment.
-// finish: C (T, S, S), lag 0 included, from the (T, S^2) by-particle autocorrelations of launch_onsager_combos'
-// pseudo-particles of the currents
-hipError_t launch_species_current(const void* vel, bool f32, long pitch, long T, long n_cols, int D, int S, const int* species,
-                                  const double* w, double* partial, int n_parts, hipStream_t st);
-hipError_t launch_current_finish(const double* bp, int S, long T, const int* nz, double* C, hipStream_t st);
+hipError_t launch_cross_finish(const double* bp, int S, long T, const int* nz, bool lag0, double* C, hipStream_t st);
 
 // species_self.hip: the weighted slab W = w (x - shift x[0]) of a pair-major slab of float64 or (f32) float32 elements with
 // each species' atoms contiguous, as a float64 pair-major slab of plan.n_pairs pairs: species s's block starts at pair
