@@ -222,6 +222,65 @@ struct Dft<20> {
     }
 };
 
+// ---- pass-B first stage with the twist inside the prime-factor butterfly (R0 = 18, 20) -----------
+// run(v) = Dft<R0> of v[n] W_{2 R0}^n.  With n = N2 n1 + N1 n2 - R0 w (w = 1 where the sum passes R0):
+//   W_{2 R0}^n = W_{2 N1}^{n1} (-1)^{w + n2} W_N2^{S n2},   S = (N2 + 1) / 2,
+// because W_{2 N2}^{n2} = (-1)^{n2} W_N2^{S n2}.  So the N1-point step takes the odd frequencies
+// W_{2 N1}^{n1 (2 k1 + 1)}, the signs are operand negations and the N2-point step only shifts its
+// output index by S: 19 (17) complex multiplications in front of the butterfly become 4 extra
+// operations per four-point step (none per two-point step).
+template <int R0>
+struct DftTwisted {
+    static constexpr bool kHave = false;
+};
+template <int R0>
+__device__ __forceinline__ cd wf_twist_in(const cd (&v)[R0], int n, int n2) {  // (-1)^{w + n2} v[n mod R0]
+    const cd x = v[n % R0];
+    return ((n >= R0 ? 1 : 0) + n2) & 1 ? cd{-x.x, -x.y} : x;
+}
+template <>
+struct DftTwisted<18> {
+    static constexpr bool kHave = true;
+    static __device__ __forceinline__ void run(cd (&v)[18]) {
+        cd s[2][9];
+#pragma unroll
+        for (int j2 = 0; j2 < 9; ++j2) {
+            const cd a = wf_twist_in<18>(v, 2 * j2, j2), b = wf_twist_in<18>(v, 9 + 2 * j2, j2);
+            s[0][j2] = cd{a.x + b.y, a.y - b.x};  // a - i b
+            s[1][j2] = cd{a.x - b.y, a.y + b.x};  // a + i b
+        }
+        Dft<9>::run(s[0]);
+        Dft<9>::run(s[1]);
+#pragma unroll
+        for (int q = 0; q < 18; ++q) v[q] = s[q % 2][(q % 9 + 5) % 9];
+    }
+};
+template <>
+struct DftTwisted<20> {
+    static constexpr bool kHave = true;
+    static __device__ __forceinline__ void run(cd (&v)[20]) {
+        cd s[4][5];
+#pragma unroll
+        for (int j2 = 0; j2 < 5; ++j2) {
+            const cd a = wf_twist_in<20>(v, 4 * j2, j2), b = wf_twist_in<20>(v, 5 + 4 * j2, j2);
+            const cd c = wf_twist_in<20>(v, 10 + 4 * j2, j2), d = wf_twist_in<20>(v, 15 + 4 * j2, j2);
+            // odd-frequency four-point step: (a - ic) +- W_8 (b - id), (a + ic) +- W_8^3 (b + id)
+            const cd p = cd{a.x + c.y, a.y - c.x}, m = cd{a.x - c.y, a.y + c.x};
+            const cd e = cd{b.x + d.y, b.y - d.x}, f = cd{b.x - d.y, b.y + d.x};
+            const double ex = e.x + e.y, ey = e.y - e.x;  // sqrt 2 W_8 e
+            const double fx = f.y - f.x, fy = f.x + f.y;  // sqrt 2 W_8^3 f = (fx, -fy)
+            s[0][j2] = cd{fma(kR2, ex, p.x), fma(kR2, ey, p.y)};
+            s[2][j2] = cd{fma(-kR2, ex, p.x), fma(-kR2, ey, p.y)};
+            s[1][j2] = cd{fma(kR2, fx, m.x), fma(-kR2, fy, m.y)};
+            s[3][j2] = cd{fma(-kR2, fx, m.x), fma(kR2, fy, m.y)};
+        }
+#pragma unroll
+        for (int k1 = 0; k1 < 4; ++k1) Dft<5>::run(s[k1]);
+#pragma unroll
+        for (int q = 0; q < 20; ++q) v[q] = s[q % 4][(q % 5 + 3) % 5];
+    }
+};
+
 // Twiddle table of plan (R0, R) (host side; shared by the library and tools/wfft), L = 2 R M:
 //   [0, L)            W_L^n = exp(-2 pi i n / L)
 //   [L, L + 896)      wave-local stage twiddles of the inverse kernel [14][64]: rows 0..6
@@ -804,20 +863,49 @@ __device__ __forceinline__ auto& wf_pick(A& a, B& b) {
 // widened to float64 (exactly) when the first stage picks them up; everything after is the same
 // arithmetic on the same values.  (Without an outer radix; longer trajectories are widened into a
 // float64 scratch slab first.)
-template <class P, bool BYP = false, bool LONG = false, bool STAMP = false, bool SRC32 = false>
-__global__ void __launch_bounds__(P::NT, P::min_waves(BYP, LONG))
-    k_wsplit_accum(const double* __restrict__ pm, long pitch, int T, long n_units,
-                   const cd* __restrict__ tw2, double* __restrict__ accg, int D, int R_arg,
-                   unsigned long long* __restrict__ stamps) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+//
+// PASS: the workgroup's pass as a compile-time constant (0 / 1), or -1 where it is read from the
+// block index.  The lag-sum kernels of R0 = 18, 20 on float64 slabs without an outer radix (wf_pass_split) take
+// body<0> or body<1> behind one workgroup-uniform branch: same launch, same grid, same lockstep of a
+// tuple's two workgroups, but each code path carries one first stage only --
+//   pass 0: no `h`, no multiplication by one, one seed request (g; g2 = g^2);
+//   pass 1: two seed requests (h, g2; g = h^2 -- R = 1: W_M^u = W_L^{2u}) and the twist inside the
+//           butterfly (DftTwisted) instead of R0 - 1 literal multiplications in front of it.
+// 21 / 22 instead of 23 memory requests per thread and unit.  (Pass 1 squaring g for g2 as well is
+// one request fewer and doubles the error of the lag sums -- the error of g2 enters R0 / 2 - 1 times
+// along either chain and h^4 carries four times that of a table entry: WF_SEED_DERIVE=3.  The
+// seed kept resident across the launch instead -- 4 registers -- spills 248-260 bytes.)
+#ifndef WF_PASS_SPLIT
+#define WF_PASS_SPLIT 1   // 0: every plan reads the pass at run time
+#endif
+#ifndef WF_SEED_DERIVE
+#define WF_SEED_DERIVE 2  // split bodies: 0: g, g2 (and h) loaded like the run-time body; 1: pass 1 squares h for g;
+                          // 2: and pass 0 squares g for g2; 3: and pass 1 too (one request per unit in both)
+#endif
+#ifndef WF_TWIST_FOLD
+#define WF_TWIST_FOLD 1   // 0: the split pass-1 body keeps the literal twist in front of Dft<R0>
+#endif
+// (float32 slabs stay on the run-time pass: their kernels spill already -- 16 / 36 bytes at R0 = 18 / 20 for the
+// row requests along S2 -- and every split variant spills more, 28-52 bytes: tools/wfft/isa_table.py)
+template <class P, bool BYP, bool LONG, bool SRC32>
+constexpr bool wf_pass_split = WF_PASS_SPLIT && !BYP && !LONG && !SRC32 && (P::R0 == 18 || P::R0 == 20);
+
+__device__ __forceinline__ cd wf_csqr(cd a) { return {a.x * a.x - a.y * a.y, 2.0 * (a.x * a.y)}; }
+
+template <class P, bool BYP, bool LONG, bool STAMP, bool SRC32, int PASS>
+__device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const double* __restrict__ pm, long pitch, int T,
+                                              long n_units, const cd* __restrict__ tw2, double* __restrict__ accg, int D,
+                                              int R_arg, unsigned long long* __restrict__ stamps) {
     cd* lds = reinterpret_cast<cd*>(smem_raw);
     constexpr int R0 = P::R0, N1 = P::N1, NW = P::NW, NS1 = P::NS1, M = P::M;
     static_assert(!(SRC32 && LONG), "float32 slabs: plans without an outer radix only");
+    static_assert(PASS < 0 || (!BYP && !LONG), "a compile-time pass: lag sums without an outer radix");
     const int R = LONG ? R_arg : 1, npass = 2 * R, L = npass * M;
     const int tid = threadIdx.x, wave = tid >> 6;
     int lane = tid & 63;
     const int bi = blockIdx.x >> 3;
-    const int pass = bi % npass;
+    const int pass = PASS >= 0 ? PASS : bi % npass;
+    constexpr bool kTwistFold = PASS == 1 && WF_TWIST_FOLD && DftTwisted<R0>::kHave;
     const long tuple = (blockIdx.x & 7) + 8 * (bi / npass), n_tuples = gridDim.x / npass;
     const int upa = BYP ? (D == 3 ? 2 : 1) : 1;  // units per atom (by-particle mode)
     // with an odd number of columns per atom, atoms 2i and 2i + 1 share a column pair (the last
@@ -969,9 +1057,15 @@ __global__ void __launch_bounds__(P::NT, P::min_waves(BYP, LONG))
         cd(&x)[R0] = wf_pick<SRC32>(xwide, xx[k1]);
         cd g, g2, h;
         auto load_seeds = [&]() {
-            g = wf_load(twr, (unsigned)(u * R) * 32u, 0u);
-            g2 = wf_load(twr, (unsigned)(u * R) * 64u, 0u);
-            h = wf_load(twr, (unsigned)(u * pass) * 16u, 0u);
+            if constexpr (PASS == 1 && WF_SEED_DERIVE >= 1) {  // g = W_L^{2u} by squaring: it only starts the odd chain
+                h = wf_load(twr, (unsigned)u * 16u, 0u);
+                g = wf_csqr(h);
+            } else {
+                g = wf_load(twr, (unsigned)(u * R) * 32u, 0u);
+                if (PASS != 0) h = wf_load(twr, (unsigned)(u * pass) * 16u, 0u);
+            }
+            if constexpr ((PASS == 0 && WF_SEED_DERIVE >= 2) || (PASS == 1 && WF_SEED_DERIVE >= 3)) g2 = wf_csqr(g);
+            else g2 = wf_load(twr, (unsigned)(u * R) * 64u, 0u);
         };
         if constexpr (!LONG) load_seeds();
         if constexpr (LONG) {
@@ -1024,18 +1118,27 @@ __global__ void __launch_bounds__(P::NT, P::min_waves(BYP, LONG))
             load_seeds();  // after the row loads: their registers are free again
         } else if (pass) {
             // pass B twist, lane-uniform part W_{2 R0}^j: literals (wfft_twist.inc) instead of 19
-            // scalar loads per butterfly
+            // scalar loads per butterfly (the split pass-1 body: inside the butterfly, DftTwisted)
+            if constexpr (!kTwistFold) {
 #pragma unroll
-            for (int j = 1; j < R0; ++j) x[j] = cmul(x[j], cd{WfTwist<R0>::re(j), WfTwist<R0>::im(j)});
+                for (int j = 1; j < R0; ++j) x[j] = cmul(x[j], cd{WfTwist<R0>::re(j), WfTwist<R0>::im(j)});
+            }
         }
-        Dft<R0>::run(x);
+        if constexpr (kTwistFold) DftTwisted<R0>::run(x);
+        else Dft<R0>::run(x);
         {
             // output twiddles W_L^{u (2R q + c)} = h g^q: two chains (even / odd q) by g^2, each
             // output stored as soon as it is scaled (the 20 stores of a wave take ~260 LDS-path
             // cycles: issued in one burst at the end they are fully exposed)
-            cd te = pass ? h : cd{1.0, 0.0};
-            cd to = pass ? cmul(h, g) : g;
-            if (pass) x[0] = cmul(x[0], te);
+            cd te, to;
+            if constexpr (PASS == 0) {  // the even chain starts at one: q = 0 goes out as it is, q = 2 takes g2 itself
+                te = cd{1.0, 0.0};
+                to = g;
+            } else {
+                te = pass ? h : cd{1.0, 0.0};
+                to = pass ? cmul(h, g) : g;
+                if (pass) x[0] = cmul(x[0], te);
+            }
             if (!(WF_REAL_S1_SKIP && BYP) || (qsel & 1u)) lds[u] = x[0];
             if constexpr (R0 > 1) {
                 x[1] = cmul(x[1], to);
@@ -1047,7 +1150,7 @@ __global__ void __launch_bounds__(P::NT, P::min_waves(BYP, LONG))
                     to = cmul(to, g2);
                     x[q] = cmul(x[q], to);
                 } else {
-                    te = cmul(te, g2);
+                    te = (PASS == 0 && q == 2) ? g2 : cmul(te, g2);
                     x[q] = cmul(x[q], te);
                 }
                 // (only the LDS store is skipped: branches around the products as well cost registers)
@@ -1192,6 +1295,27 @@ __global__ void __launch_bounds__(P::NT, P::min_waves(BYP, LONG))
         }
     }
 #undef WF_STAMP
+}
+
+template <class P, bool BYP = false, bool LONG = false, bool STAMP = false, bool SRC32 = false>
+__global__ void __launch_bounds__(P::NT, P::min_waves(BYP, LONG))
+    k_wsplit_accum(const double* __restrict__ pm, long pitch, int T, long n_units,
+                   const cd* __restrict__ tw2, double* __restrict__ accg, int D, int R_arg,
+                   unsigned long long* __restrict__ stamps) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    if constexpr (wf_pass_split<P, BYP, LONG, SRC32>) {
+#ifdef WF_FIX_PASS  // instruction counts per pass (tools/wfft/isa_table.py): this body alone; not a kernel to run
+        wf_accum_body<P, BYP, LONG, STAMP, SRC32, WF_FIX_PASS>(smem_raw, pm, pitch, T, n_units, tw2, accg, D, R_arg, stamps);
+        return;
+#endif
+        // workgroup-uniform: block b runs pass (b >> 3) & 1 (two passes without an outer radix)
+        if ((blockIdx.x >> 3) & 1)
+            wf_accum_body<P, BYP, LONG, STAMP, SRC32, 1>(smem_raw, pm, pitch, T, n_units, tw2, accg, D, R_arg, stamps);
+        else
+            wf_accum_body<P, BYP, LONG, STAMP, SRC32, 0>(smem_raw, pm, pitch, T, n_units, tw2, accg, D, R_arg, stamps);
+    } else {
+        wf_accum_body<P, BYP, LONG, STAMP, SRC32, -1>(smem_raw, pm, pitch, T, n_units, tw2, accg, D, R_arg, stamps);
+    }
 }
 
 // ================================================================================================
