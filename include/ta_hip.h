@@ -291,6 +291,42 @@ int ta_current_cross(ta_ctx *ctx, int fft, const double *h_currents, int n_speci
 int ta_species_self(ta_ctx *ctx, int quantity, int fft, int n_species, const int32_t *h_species, const double *h_weights,
                     double *h_self, int64_t *h_counts);
 
+/* ta_scatter : the intermediate scattering functions of the positions in slab 0 (IntermediateScattering) for n_k
+ *              wavevectors h_kvecs (n_k, dim), rad per length unit, one component per staged column.  With the phase
+ *              phi_j[t, n] = sum_d k_j[d] x[t, n, d]:
+ *                h_self[j * n_frames + tau]   = 1/(T - tau) sum_{t < T - tau} sum_n cos(phi_j[t + tau, n] - phi_j[t, n])
+ *                h_density[(j * n_frames + t) * 2 + {0, 1}] = sum_n {cos, sin} phi_j[t, n]
+ *                h_coll[j * n_frames + tau]   = 1/(T - tau) sum_{t < T - tau} (rc[t] rc[t + tau] + rs[t] rs[t + tau]),
+ *              rc, rs the two density components of wavevector j.  Lag 0 is kept (self: ~ n_atoms); NOTHING is divided
+ *              by an atom count.  Each output may be NULL (not computed), not all three.  self and density add up over
+ *              atoms -- shards, group members, ranks; coll does not: it is formed once from the summed density
+ *              (ta_scatter_collective; needs no staged slab and touches none), as ta_current_cross from summed currents.
+ *              The pass k_phase reads the slab ONCE per chunk of Kc wavevectors, in the element type it has (a float32
+ *              device slab is read as float32 and widened in registers), and writes the float64 scratch slab Z: for
+ *              wavevector jl of the chunk and atom n, pair jl n_atoms + n holds the rows (cos phi, sin phi) along time, in
+ *              the input's pitch; rows n_frames ... pitch - 1 are zeros.  Every block of n_atoms pairs is a pair-major
+ *              slab of n_atoms "atoms" with dim 2: self is ONE lag-sum evaluation of ta_vacf_fft (fft = 1) /
+ *              ta_vacf_direct (fft = 0) per wavevector on its block, the density the fixed-order sum over its atoms (no
+ *              atomics: the same bits from run to run), coll one by-particle autocorrelation of the n_k densities.
+ *              Chunking: Kc = n_k when n_k n_atoms pitch 16 bytes fit 32 GiB, else the largest count that does (at least
+ *              1); option "scatter_chunk" n >= 1 forces Kc = min(n, n_k).  The results do not depend on Kc bit for bit.
+ *              ta_trim releases Z.
+ *              Phases: the host passes q = k / (2 pi) (turns); u = sum_d q[d] x[d] in float64 (a product, then fma),
+ *              r = u - rint(u), (cos, sin)(2 pi r).  With U = max |k . x| / (2 pi) over the call every phase carries at most
+ *              2 pi (dim + 1) 2^-53 U rad of rounding plus the math functions' few ulp: each density component is within
+ *              n_atoms (2 pi (dim + 2) 2^-53 U + 8 2^-53) of the exact sum; the correlations are the library's usual
+ *              1e-10 of the series' scale for U up to ~1e3.  A wavevector commensurate with a constant box gives phases that
+ *              are invariant under periodic wrapping: wrapped positions need no ta_unwrap.
+ *              All outputs NULL, NULL h_kvecs, a non-finite component, fft other than 0 / 1, n_k outside
+ *              1 ... TA_SCATTER_MAX_K (checked before anything is written): TA_E_INVALID; nothing staged: TA_E_STATE;
+ *              n_atoms * max(dim, 2) must be below 2^31.  CPU backend: the same phase arithmetic, per wavevector a host
+ *              slab (n_frames, n_atoms, 2) and its VACF routines, the density a plain sum in atom order.  Timings: the
+ *              pass is the main kernel unless an evaluation after it records its own (ta_kernel_timeline names it
+ *              k_phase).                                                                                              */
+#define TA_SCATTER_MAX_K 4096
+int ta_scatter(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, double *h_self, double *h_density, double *h_coll);
+int ta_scatter_collective(ta_ctx *ctx, int fft, const double *h_density, int n_k, int64_t n_frames, double *h_coll);
+
 /* ---- periodic unwrapping of a staged position slab ---------------------------------------------------------------
  * ta_unwrap: undo periodic wrapping of staging slab `slab` in place (MDAnalysis' NoJump), over the staged frames
  * in order.  h_dimensions: (n_frames, 6) float64 rows [a, b, c, alpha, beta, gamma] (A, degrees; ts.dimensions).
@@ -384,6 +420,12 @@ int ta_species_self_dev(ta_ctx *ctx, const double *d_x, int64_t n_frames, int64_
                         int quantity, int fft, int n_species, const int32_t *h_species, const double *d_weights,
                         double *d_self, void *stream);
 
+/* d_pos: frame-major float64 positions; h_kvecs: HOST wavevectors (n_k, dim) (they size the launches; checked before
+ * anything is written); d_self (n_k, n_frames), d_density (n_k, n_frames, 2), d_coll (n_k, n_frames): device arrays, each
+ * may be NULL, not all three.  Shards' self parts and densities add up. */
+int ta_scatter_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row, int fft,
+                   int n_k, const double *h_kvecs, double *d_self, double *d_density, double *d_coll, void *stream);
+
 /* ---- compute on the staged (pair-major) slabs, device outputs, asynchronous on `stream` ----
  * Same arithmetic and outputs as the *_dev calls, on the slabs of ta_stage_alloc*: no
  * transposition, no second copy.  d_masses: (n_atoms,) float64 device array.              */
@@ -405,6 +447,10 @@ int ta_current_staged(ta_ctx *ctx, int fft, int n_species, const int32_t *d_spec
 /* h_species: HOST labels, as for ta_species_self_dev; slab 0 is read in the element type it has */
 int ta_species_self_staged(ta_ctx *ctx, int quantity, int fft, int n_species, const int32_t *h_species,
                            const double *d_weights, double *d_self, void *stream);
+
+/* h_kvecs: HOST wavevectors, as for ta_scatter_dev; slab 0 (the positions) is read in the element type it has */
+int ta_scatter_staged(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, double *d_self, double *d_density,
+                      double *d_coll, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns
@@ -475,6 +521,11 @@ int ta_group_current(ta_group *g, int fft, int n_species, const int32_t *h_speci
  * first); the members' (n_species, n_frames) arrays and counts are SUMMED on the host in member order.               */
 int ta_group_species_self(ta_group *g, int quantity, int fft, int n_species, const int32_t *h_species,
                           const double *h_weights, double *h_self, int64_t *h_counts);
+/* ta_group_scatter: ta_scatter on every member with the same wavevectors (checked first): the members' self parts and
+ * densities are SUMMED on the host in member order, then ONE collective part of the summed density runs on the first
+ * member that holds atoms.                                                                                          */
+int ta_group_scatter(ta_group *g, int fft, int n_k, const double *h_kvecs, double *h_self, double *h_density,
+                     double *h_coll);
 /* ta_group_unwrap: ta_unwrap on every member's block of slab `slab` (declared with ta_unwrap above) */
 int ta_group_unwrap(ta_group *g, int slab, const double *h_dimensions, const int *axes); /* every member's block */
 
@@ -495,6 +546,8 @@ int ta_timing_history(ta_ctx *ctx, int max_n, float *total_ms, float *main_kerne
  * names[i] (static strings owned by the library), ms[i], *n_out entries (<= max_n).  The sum is
  * the call's total_ms.  Blocks until the call has completed.                              */
 int ta_kernel_timeline(ta_ctx *ctx, int max_n, const char **names, float *ms, int *n_out);
+/* the number of launches recorded under `name` in the last compute call's timeline (0: none, or the option is off) */
+int ta_kernel_launches(ta_ctx *ctx, const char *name, int *n_out);
 /* The clock the headline kernel actually runs at (MI355X lowers it under load; board power and
  * the driver's sclk are not the test).  Launches a DIAGNOSTIC build of the lag-sum forward kernel
  * (in-kernel s_memtime / s_memrealtime stamps; the product kernels execute no stamp) n_launches
@@ -576,6 +629,8 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      ahead (default 2);
  *   "timeline" 0|1   : record an event before every kernel launch of a compute call
  *                      (ta_kernel_timeline);
+ *   "scatter_chunk" n : wavevectors per pass of ta_scatter* (0, the default: as many as fit 32 GiB of scratch; n >= 1:
+ *                      min(n, n_k)); the results do not depend on it;
  *   "async_commit" 1|0 : ta_stage_commit hands its frame range to a worker thread of the context, which
  *                      makes the HIP calls (the caller's frame loop never waits on the runtime, e.g. while
  *                      another thread page-locks a result array); every call that touches the slabs joins

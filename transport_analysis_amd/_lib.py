@@ -38,6 +38,7 @@ _COND = _int(_vp, _ci, _vp, _vp, _vp, _vp)
 _UNWRAP = _int(_vp, _ci, _vp, _vp)
 _ONSAGER = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, fft, n_species, h_species, h_weights, h_moments, h_cross)
 _SELF = _int(_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, quantity, fft, n_species, h_species, h_weights, h_self, h_counts)
+_SCATTER = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, fft, n_k, h_kvecs, h_self, h_density, h_coll)
 
 #: every symbol include/ta_hip.h declares -> (result type, argument types): the one table EXPORTS and lib() are made of
 _API = {
@@ -62,6 +63,9 @@ _API = {
     "ta_current_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_species_self": _SELF, "ta_species_self_staged": _int(_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp),
     "ta_species_self_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _ci, _vp, _vp, _vp, _vp),
+    "ta_scatter": _SCATTER, "ta_scatter_collective": _int(_vp, _ci, _vp, _ci, _i64, _vp),
+    "ta_scatter_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
+    "ta_scatter_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_compound": _int(_vp, _i64, _vp, _vp, _vp, _vp, _P(_vp)),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
     "ta_helfand_msd_dev": _int(_vp, _vp, _vp, _vp, _i64, _i64, _ci, _i64, _dbl, _vp, _vp, _i64, _vp),
@@ -71,7 +75,8 @@ _API = {
     "ta_helfand_msd_staged": _int(_vp, _vp, _dbl, _vp, _vp, _i64, _vp), "ta_msd_staged": _int(_vp, _ci, _vp, _vp, _i64, _vp),
     "ta_conductivity_staged": _int(_vp, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_last_timing": _int(_vp, _pf, _pf), "ta_timing_history": _int(_vp, _ci, _pf, _pf, _P(_ci)),
-    "ta_kernel_timeline": _int(_vp, _ci, _P(_str), _pf, _P(_ci)), "ta_clock_probe": _int(_vp, _ci, _P(_dbl), _P(_dbl), _P(_dbl)),
+    "ta_kernel_timeline": _int(_vp, _ci, _P(_str), _pf, _P(_ci)), "ta_kernel_launches": _int(_vp, _str, _P(_ci)),
+    "ta_clock_probe": _int(_vp, _ci, _P(_dbl), _P(_dbl), _P(_dbl)),
     "ta_group_create": _int(_P(_ci), _ci, _P(_vp)), "ta_group_destroy": _int(_vp), "ta_group_last_error": _text(_vp),
     "ta_group_size": _int(_vp), "ta_group_member": _int(_vp, _ci, _P(_vp), _P(_ci)),
     "ta_group_shard": _int(_vp, _i64, _ci, _P(_i64), _P(_i64)),
@@ -83,6 +88,7 @@ _API = {
     "ta_group_vacf_fft": _HOST, "ta_group_vacf_direct": _HOST, "ta_group_helfand_msd": _int(_vp, _vp, _dbl, _vp, _vp),
     "ta_group_msd": _int(_vp, _ci, _vp, _vp), "ta_group_conductivity": _COND, "ta_group_unwrap": _UNWRAP,
     "ta_group_onsager": _ONSAGER, "ta_group_current": _ONSAGER, "ta_group_species_self": _SELF,
+    "ta_group_scatter": _SCATTER,
 }
 EXPORTS = tuple(_API)
 
@@ -458,6 +464,27 @@ class _Staged:
         self._call("species_self", int(quantity), int(fft), S, _ptr(lab), _ptr(w), _ptr(out), _ptr(counts))
         return out, counts
 
+    def _kvectors(self, kvectors, dim):
+        """(wavevectors as a C-contiguous float64 (n_k, dim) array, n_k)"""
+        k = np.ascontiguousarray(kvectors, dtype=np.float64)
+        if k.ndim != 2 or k.shape[1] != dim:
+            raise ValueError(f"kvectors: shape {k.shape}, expected (n_k, {dim}) (one component per staged column)")
+        return k, int(k.shape[0])
+
+    def scatter(self, fft, kvectors, self_part=True, density=True, collective=True):
+        """Intermediate scattering functions of slab 0 (the positions), ta_scatter: `kvectors` (n_k, dim) in rad per length
+        unit: (self (n_k, n_frames) = sum_n <cos(k . (x_n(t + tau) - x_n(t)))>, density (n_k, n_frames, 2) = sum_n (cos, sin)
+        (k . x_n(t)), coll (n_k, n_frames) = the autocorrelation of the density), None for one not asked for; nothing is
+        divided by the number of atoms.  A group: the members' self parts and densities are summed, then ONE collective
+        part runs."""
+        T, _, D = self._staged_shape()
+        k, K = self._kvectors(kvectors, D)
+        fs = np.empty((K, T), dtype=np.float64) if self_part else None
+        rho = np.empty((K, T, 2), dtype=np.float64) if density else None
+        coll = np.empty((K, T), dtype=np.float64) if collective else None
+        self._call("scatter", int(fft), K, _ptr(k), _ptr(fs), _ptr(rho), _ptr(coll))
+        return fs, rho, coll
+
     def unwrap(self, slab, dimensions, axes):
         """Undo periodic wrapping of staged slab `slab` in place (MDAnalysis' NoJump, ta_unwrap; a group: on every
         member's block of the slab): `dimensions` the (n_frames, 6) boxes [a, b, c, alpha, beta, gamma] of the staged
@@ -586,6 +613,17 @@ class Context(_Staged):
         (ta_current_cross): needs no staged slab and leaves the context's slabs as they are."""
         return self._cross("current_cross", "currents", currents, fft)
 
+    def scatter_collective(self, density, fft):
+        """coll (n_k, n_frames) of a given (n_k, n_frames, 2) density, e.g. the sum of several shards' densities
+        (ta_scatter_collective): needs no staged slab and leaves the context's slabs as they are."""
+        a = np.ascontiguousarray(density, dtype=np.float64)
+        if a.ndim != 3 or a.shape[2] != 2:
+            raise ValueError(f"density: shape {a.shape}, expected (n_k, n_frames, 2)")
+        K, T, _ = a.shape
+        c = np.empty((K, T), dtype=np.float64)
+        self._call("scatter_collective", int(fft), _ptr(a), K, T, _ptr(c))
+        return c
+
     # -- device-pointer compute (asynchronous) --------------------------
     def vacf_fft_dev(self, d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._call("vacf_fft_dev", d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp or None, ld_bp, stream or None)
@@ -655,6 +693,17 @@ class Context(_Staged):
         self._call("species_self_staged", int(quantity), int(fft), int(n_species), _ptr(lab), d_weights or None, d_self,
                    stream or None)
 
+    def scatter_dev(self, d_pos, n_frames, n_atoms, dim, ld_row, fft, kvectors, d_self=0, d_density=0, d_coll=0, stream=0):
+        """`kvectors`: HOST wavevectors (n_k, dim) (checked by the library before anything is written)"""
+        k, K = self._kvectors(kvectors, dim)
+        self._call("scatter_dev", d_pos, n_frames, n_atoms, dim, ld_row, int(fft), K, _ptr(k), d_self or None,
+                   d_density or None, d_coll or None, stream or None)
+
+    def scatter_staged(self, fft, kvectors, d_self=0, d_density=0, d_coll=0, stream=0):
+        """`kvectors`: HOST wavevectors (n_k, dim) (checked by the library before anything is written)"""
+        k, K = self._kvectors(kvectors, self._staged_shape()[2])
+        self._call("scatter_staged", int(fft), K, _ptr(k), d_self or None, d_density or None, d_coll or None, stream or None)
+
     # -- timing ----------------------------------------------------------
     def timing_history(self, max_n=64):
         """[(total_ms, main_kernel_ms)] of the last compute calls, oldest first."""
@@ -671,6 +720,12 @@ class Context(_Staged):
         ms = (ctypes.c_float * max_n)()
         self._call("kernel_timeline", max_n, names, ms, ctypes.byref(n))
         return [(names[i].decode(), ms[i]) for i in range(n.value)]
+
+    def kernel_launches(self, name):
+        """launches recorded under `name` in the last compute call's timeline (needs set_option("timeline", 1))"""
+        n = ctypes.c_int()
+        self._call("kernel_launches", name.encode(), ctypes.byref(n))
+        return n.value
 
     def clock_probe(self, n_launches):
         """{"mhz", "cycles_per_unit_pass", "ms_per_launch"} of the stamped lag-sum forward kernel

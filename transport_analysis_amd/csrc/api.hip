@@ -101,6 +101,7 @@ private:
     X(direct_subwave, 1, nullptr)  /* k_direct's column groups may be 16 or 32 lanes (under ~640 frames) */                \
     X(stage_device_f32, 0, nullptr) /* device slabs hold float32 when nothing wider is coming in */                        \
     X(timeline, 0, nullptr)        /* record the kernel timeline of every compute call (ta_kernel_timeline) */             \
+    X(scatter_chunk, 0, opt_check_scatter_chunk) /* wavevectors per pass of ta_scatter* (0: as many as fit kScatterBudget) */ \
     X(async_commit, 1, opt_flush_commits) /* ta_stage_commit goes through the commit queue; flushed before it changes */   \
     X(lock_ahead, 1, nullptr)      /* the commit worker page-locks the chunks behind the one it committed */               \
     X(cpu_threads, 0, opt_set_cpu_threads) /* CPU backend: OpenMP team size (0: the runtime's default) */                  \
@@ -144,6 +145,14 @@ struct ta_ctx {
     DevBuf self_w{workspaces, kTrimmed}, self_order{workspaces, kKept}, self_out{workspaces, kKept};
     std::vector<int32_t> self_order_h;
     hipEvent_t ev_order = nullptr;
+    // intermediate scattering (scatter_pm): the phase slab Z of one chunk of wavevectors (trimmed), the zero labels of the
+    // density sum, the wavevectors in turns, the pair-major copy of the densities with their by-particle lag sums (and the
+    // density itself when the caller does not ask for it), the outputs of host-facing calls.  scatter_q_h is what the
+    // upload of the wavevectors reads: it stays until ev_kvec says the copy is done
+    DevBuf scatter_z{workspaces, kTrimmed}, scatter_lab{workspaces, kKept}, scatter_q{workspaces, kKept};
+    DevBuf scatter_work{workspaces, kTrimmed}, scatter_out{workspaces, kKept};
+    std::vector<double> scatter_q_h;
+    hipEvent_t ev_kvec = nullptr;
     // ta_compound: the plan (offsets, members, member weights, their sums per compound) and the (n_frames, dim) weighted
     // mean F of the barycentric term; the per-atom frame weights and F's partial sums use the Onsager workspaces
     DevBuf comp_plan{workspaces, kTrimmed}, comp_f{workspaces, kTrimmed};
@@ -1085,6 +1094,105 @@ int species_self_pm(ta_ctx* ctx, int quantity, bool fft, const Slab& slab, const
     return call_end(ctx, st);
 }
 
+// ---- intermediate scattering functions (scatter.hip) -----------------------------------------------------------------
+// The scratch budget of the phase slab: a chunk holds as many wavevectors as fit (at least one).  A choice, not a
+// measurement: two wavevectors of the headline shape (10000 x 100000: 16 GB each) next to its 24 GB slab and the FFT
+// workspaces on a 288 GB device.
+constexpr size_t kScatterBudget = (size_t)32 << 30;
+
+int scatter_args(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, int D, const void* o_self, const void* o_density,
+                 const void* o_coll) {
+    return check_kvecs(fail, ctx, fft, n_k, h_kvecs, D, o_self || o_density || o_coll);
+}
+
+// bytes of scatter_work for K wavevectors of T frames: the pair-major densities, their (T, K) by-particle lag sums and the
+// lag sum, then (own_density) the densities themselves
+size_t scatter_work_bytes(int64_t T, int K, bool own_density) {
+    return pm_bytes(T, 2 * (int64_t)K) + sizeof(double) * ((size_t)T * K + (size_t)T + (own_density ? (size_t)K * T * 2 : 0));
+}
+double* scatter_own_density(ta_ctx* ctx, int64_t T, int K) {
+    return (double*)((char*)ctx->scatter_work.p + pm_bytes(T, 2 * (int64_t)K)) + (size_t)T * K + (size_t)T;
+}
+
+// The host half of one call, before it is opened: the wavevectors in turns (q = k / 2 pi) queued for upload on `st`, the
+// buffers that do not depend on the chunking.  Nothing on the device has been written when this fails.
+int scatter_plan(ta_ctx* ctx, int K, const double* h_kvecs, int64_t A, int D, hipStream_t st) {
+    if (A * D >= (int64_t)1 << 31 || 2 * A >= (int64_t)1 << 31)
+        return fail(ctx, TA_E_INVALID, "scatter: n_atoms * max(dim, 2) must be below 2^31");
+    TA_CHECK(ensure(ctx, ctx->scatter_q, sizeof(double) * (size_t)K * D));
+    TA_CHECK(ensure(ctx, ctx->scatter_lab, sizeof(int32_t) * (size_t)A));
+    if (!ctx->ev_kvec) TA_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_kvec, hipEventDisableTiming));
+    else TA_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_kvec));  // the last call's upload has left scatter_q_h
+    ctx->scatter_q_h.resize((size_t)K * D);
+    for (size_t i = 0; i < (size_t)K * D; ++i) ctx->scatter_q_h[i] = h_kvecs[i] / 6.283185307179586476925;
+    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->scatter_q.p, ctx->scatter_q_h.data(), sizeof(double) * (size_t)K * D, hipMemcpyHostToDevice, st));
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev_kvec, st));
+    return TA_OK;
+}
+
+// coll (K, T) of the densities (K, T, 2) at d_density: their pair-major copy is a slab of K "atoms" with D = 2
+// (k_relayout, one wavevector at a time: a density is a frame-major (T, 2) array), ONE by-particle autocorrelation of it
+// by the VACF's dispatch, then the (T, K) -> (K, T) transposition.  scatter_work is ensured by the caller.
+int scatter_collective(ta_ctx* ctx, bool fft, const double* d_density, int K, int64_t T, double* d_coll, hipStream_t st) {
+    const int64_t pitch = pm_pitch(T);
+    double* pm = (double*)ctx->scatter_work.p;
+    double* bp = (double*)((char*)pm + pm_bytes(T, 2 * (int64_t)K));
+    double* lagsum = bp + (size_t)T * K;
+    if (pitch > T)  // rows T ... pitch - 1 as zeros, like every block of Z: the workspace is reused
+        TA_HIP_TRY(ctx, hipMemsetAsync(pm, 0, pm_bytes(T, 2 * (int64_t)K), st));
+    for (int j = 0; j < K; ++j)
+        TA_LAUNCH(ctx, "k_relayout", st,
+                  launch_relayout(d_density + (size_t)j * T * 2, false, 2, 2, (long)T, pm + (size_t)j * pitch * 2, false, (long)pitch, 0, st));
+    TA_CHECK(acf_impl(ctx, fft, pm, pitch, T, K, 2, lagsum, bp, K, st));
+    TA_LAUNCH(ctx, "k_scatter_transpose", st, launch_scatter_transpose(bp, (long)T, K, d_coll, st));
+    return TA_OK;
+}
+
+// One scattering call on a pair-major position slab of either element type, read as it is (the caller has opened the
+// call's bracket, it is closed here; scatter_plan has queued the wavevectors).  Per chunk of Kc wavevectors: the phase
+// pass writes Z; then per wavevector its block of A pairs -- a pair-major slab of A atoms with D = 2 of its own -- gets
+// ONE VACF lag-sum evaluation (d_self + j T) and ONE species-sum pass without shift, one species, no weights, with the
+// fixed-order sum of its partials (the density, (T, 2) at j).  After the last chunk the collective part of the K densities.
+// Nothing depends on Kc but which launches share a pass: the same bits for every chunk size.  ev[1] / ev[2] bracket the
+// (last) pass, unless an evaluation after it records its own kernel.
+int scatter_pm(ta_ctx* ctx, bool fft, const Slab& slab, int K, double* d_self, double* d_density, double* d_coll) {
+    const int64_t pitch = slab.pitch, T = slab.T, A = slab.A;
+    const int D = slab.D;
+    hipStream_t st = slab.st;
+    const size_t per = (size_t)A * (size_t)pitch * 16;  // Z of one wavevector
+    const int64_t Kc = ctx->opt_scatter_chunk > 0 ? std::min<int64_t>(ctx->opt_scatter_chunk, K)
+                                                   : std::max<int64_t>(1, std::min<int64_t>(K, (int64_t)(kScatterBudget / per)));
+    TA_CHECK(ensure(ctx, ctx->scatter_z, (size_t)Kc * per));
+    double* Z = (double*)ctx->scatter_z.p;
+    const bool sums = d_density || d_coll;
+    if (d_coll) TA_CHECK(ensure(ctx, ctx->scatter_work, scatter_work_bytes(T, K, !d_density)));
+    double* rho = d_density ? d_density : d_coll ? scatter_own_density(ctx, T, K) : nullptr;
+    const int n_parts = species_sum_parts(ctx->n_cu, 1, (long)T, (long)(2 * A));
+    if (sums) {
+        TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)n_parts * T * 2));
+        TA_HIP_TRY(ctx, hipMemsetAsync(ctx->scatter_lab.p, 0, sizeof(int32_t) * (size_t)A, st));
+    }
+    const double* d_q = (const double*)ctx->scatter_q.p;
+    for (int64_t j0 = 0; j0 < K; j0 += Kc) {
+        const int kc = (int)std::min<int64_t>(Kc, K - j0);
+        TA_LAUNCH_MAIN(ctx, "k_phase", st,
+                       launch_phase(ctx->n_cu, slab.pm, slab.f32, (long)pitch, (long)T, (long)A, D, d_q + j0 * D, kc, Z, st));
+        for (int jl = 0; jl < kc; ++jl) {
+            const double* blk = Z + (size_t)jl * A * pitch * 2;
+            const int64_t j = j0 + jl;
+            if (d_self) TA_CHECK(acf_impl(ctx, fft, blk, pitch, T, A, 2, d_self + (size_t)j * T, nullptr, 0, st));
+            if (!sums) continue;
+            TA_LAUNCH(ctx, "k_species_current", st,
+                      launch_species_sum(blk, false, false, (long)pitch, (long)T, (long)(2 * A), 2, 1, (const int*)ctx->scatter_lab.p,
+                                         nullptr, (double*)ctx->ons_part.p, n_parts, st));
+            TA_LAUNCH(ctx, "k_sum_partials", st,
+                      launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)(T * 2), rho + (size_t)j * T * 2, st));
+        }
+    }
+    if (d_coll) TA_CHECK(scatter_collective(ctx, fft, rho, K, T, d_coll, st));
+    return call_end(ctx, st);
+}
+
 // ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
 // This is the seam: a CPU context's staging and host-facing calls end up in the cpu_* functions below, reached by one
 // early branch of their entry point (after the checks both kinds of context share); nothing below makes a HIP call.
@@ -1161,6 +1269,9 @@ int opt_set_cpu_threads(ta_ctx* ctx, int64_t value) {
     return TA_OK;
 }
 int opt_flush_commits(ta_ctx* ctx, int64_t) { return ctx->commits.flush(); }
+int opt_check_scatter_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "scatter_chunk: 0 (automatic) or the wavevectors per pass");
+}
 
 struct Option {
     const char* key;
@@ -1284,10 +1395,11 @@ int ta_ctx_destroy(ta_ctx* ctx) {
         for (auto& ev : q)
             if (ev) hipEventDestroy(ev);
     if (ctx->ev_stage) hipEventDestroy(ctx->ev_stage);
-    if (ctx->ev_order) {
-        hipEventSynchronize(ctx->ev_order);  // (the upload may be on a caller's stream)
-        hipEventDestroy(ctx->ev_order);
-    }
+    for (hipEvent_t e : {ctx->ev_order, ctx->ev_kvec})
+        if (e) {
+            hipEventSynchronize(e);  // (the upload may be on a caller's stream)
+            hipEventDestroy(e);
+        }
     for (hipEvent_t e : ctx->mark_pool) hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) {
         if (ctx->ev_piece[i]) hipEventDestroy(ctx->ev_piece[i]);
@@ -1832,6 +1944,30 @@ int ta_species_self_staged(ta_ctx* ctx, int quantity, int fft, int n_species, co
     });
 }
 
+// Intermediate scattering: slab 0 / d_pos holds the positions; the staged slab is read in its own element type (never
+// widened); the wavevectors are a HOST array: they size the launches, and scatter_plan runs before the call is opened
+static int scatter_entry(ta_ctx* ctx, const DevSrc* dev, int fft, int n_k, const double* h_kvecs, double* d_self,
+                         double* d_density, double* d_coll, void* stream) {
+    return slab_entry(
+        ctx, dev, stream,
+        [&] { return scatter_args(ctx, fft, n_k, h_kvecs, dev ? dev->D : ctx->st_nslabs ? ctx->st_D : 0, d_self, d_density, d_coll); },
+        [&](const Slab& s) { return scatter_plan(ctx, n_k, h_kvecs, s.A, s.D, s.st); },
+        [&](const Slab& s) { return scatter_pm(ctx, fft != 0, s, n_k, d_self, d_density, d_coll); });
+}
+int ta_scatter_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int fft, int n_k,
+                   const double* h_kvecs, double* d_self, double* d_density, double* d_coll, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    const DevSrc src{d_pos, T, A, D, ld_row};
+    return scatter_entry(ctx, &src, fft, n_k, h_kvecs, d_self, d_density, d_coll, stream);
+    });
+}
+int ta_scatter_staged(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, double* d_self, double* d_density, double* d_coll,
+                      void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    return scatter_entry(ctx, nullptr, fft, n_k, h_kvecs, d_self, d_density, d_coll, stream);
+    });
+}
+
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guarded(fail, ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
@@ -1941,6 +2077,17 @@ int ta_kernel_timeline(ta_ctx* ctx, int max_n, const char** names, float* ms, in
         if (names) names[i] = agg[i].first;
         if (ms) ms[i] = agg[i].second;
     }
+    *n_out = n;
+    return TA_OK;
+    });
+}
+
+int ta_kernel_launches(ta_ctx* ctx, const char* name, int* n_out) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    if (!ctx || !name || !n_out) return fail(ctx, TA_E_INVALID, "null argument");
+    TA_NO_CPU(ctx);
+    int n = 0;
+    for (size_t i = 0; i + 1 < ctx->marks.size(); ++i) n += !strcmp(ctx->marks[i].name, name);
     *n_out = n;
     return TA_OK;
     });
@@ -2120,6 +2267,45 @@ int self_launch(ta_ctx* ctx, int quantity, int fft, int S, const int32_t* h_spec
     return TA_OK;
 }
 
+// Scattering share of a host-facing call, queued on ctx->stream and not waited for: the wavevectors (checked by the
+// caller) uploaded, self (K, T), then the density (K, T, 2), then coll (K, T) left on the device in *d_out (the ones asked for)
+int scatter_launch(ta_ctx* ctx, int fft, int K, const double* h_kvecs, bool self, bool density, bool coll, double** d_out) {
+    double* out = nullptr;
+    TA_CHECK(slab_entry(
+        ctx, nullptr, ctx->stream, no_args,
+        [&](const Slab& s) -> int {
+            TA_CHECK(scatter_plan(ctx, K, h_kvecs, s.A, s.D, ctx->stream));
+            TA_CHECK(ensure(ctx, ctx->scatter_out, sizeof(double) * (size_t)K * s.T * 4));
+            out = (double*)ctx->scatter_out.p;
+            return TA_OK;
+        },
+        [&](const Slab& s) {
+            const size_t KT = (size_t)K * s.T;
+            return scatter_pm(ctx, fft != 0, s, K, self ? out : nullptr, density ? out + KT : nullptr, coll ? out + 3 * KT : nullptr);
+        }));
+    *d_out = out;
+    return TA_OK;
+}
+
+// The collective part of a host (K, T, 2) density on this context's device, blocking, as a compute call of its own
+// (ta_scatter_collective; the group's ONE evaluation after its members' sums).  Needs no staged slab.
+int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int K, int64_t T, double* h_coll) {
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TA_CHECK(ctx->commits.flush());
+    const size_t KT = (size_t)K * T;
+    TA_CHECK(ensure(ctx, ctx->scatter_out, sizeof(double) * KT * 4));
+    TA_CHECK(ensure(ctx, ctx->scatter_work, scatter_work_bytes(T, K, false)));
+    double* out = (double*)ctx->scatter_out.p;
+    hipStream_t st = ctx->stream;
+    TA_HIP_TRY(ctx, hipMemcpyAsync(out + KT, h_density, sizeof(double) * KT * 2, hipMemcpyHostToDevice, st));
+    TA_CHECK(call_begin(ctx, st));
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));  // no dominant kernel of its own, unless the correlator records one
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
+    TA_CHECK(scatter_collective(ctx, fft != 0, out + KT, K, T, out + 3 * KT, st));
+    TA_CHECK(call_end(ctx, st));
+    return host_finish(ctx, {{h_coll, out + 3 * KT, KT}});
+}
+
 // One context's unwrap of staged slab `slab` (ta_unwrap, ta_group_unwrap), queued on ctx->stream behind the queued commits
 // and bracketed by the timing events: the box table's copy (box.tab must stay valid until host_wait), then the kernel
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes) {
@@ -2286,6 +2472,39 @@ int ta_species_self(ta_ctx* ctx, int quantity, int fft, int n_species, const int
     double* d_out = nullptr;
     TA_CHECK(ta::self_launch(ctx, quantity, fft, n_species, h_species, h_weights, h_counts, &d_out));
     return host_finish(ctx, {{h_self, d_out, (size_t)n_species * (size_t)ctx->st_T}});
+    });
+}
+
+int ta_scatter(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, double* h_self, double* h_density, double* h_coll) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(scatter_args(ctx, fft, n_k, h_kvecs, ctx->st_nslabs ? ctx->st_D : 0, h_self, h_density, h_coll));
+    TA_CHECK(check_staged(ctx));
+    if (ctx->is_cpu) {
+        if (int rc = ta::cpu::scatter(cpu_state(ctx), fft != 0, n_k, h_kvecs, h_self, h_density, h_coll))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    double* d_out = nullptr;
+    TA_CHECK(ta::scatter_launch(ctx, fft, n_k, h_kvecs, h_self != nullptr, h_density != nullptr, h_coll != nullptr, &d_out));
+    const size_t KT = (size_t)n_k * (size_t)ctx->st_T;
+    return host_finish(ctx, {{h_self, d_out, KT}, {h_density, d_out + KT, 2 * KT}, {h_coll, d_out + 3 * KT, KT}});
+    });
+}
+
+int ta_scatter_collective(ta_ctx* ctx, int fft, const double* h_density, int n_k, int64_t n_frames, double* h_coll) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(check_fft(ctx, fft));
+    if (!h_density || !h_coll) return fail(ctx, TA_E_INVALID, "density or collective output is NULL");
+    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(ctx, TA_E_INVALID, "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
+    if (n_frames < 1 || n_frames > (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30");
+    if (ctx->is_cpu) {
+        if (int rc = ta::cpu::scatter_collective(ctx->cpu_threads, fft != 0, h_density, n_k, n_frames, h_coll))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    return ta::scatter_collective_host(ctx, fft, h_density, n_k, n_frames, h_coll);
     });
 }
 

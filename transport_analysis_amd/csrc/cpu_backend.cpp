@@ -541,6 +541,64 @@ int species_self(const State& s, bool msd_quantity, bool fft, int S, const int32
     return TA_OK;
 }
 
+int scatter_collective(int threads, bool fft, const double* density, int K, int64_t T, double* coll) {
+    std::vector<double> pm, bp, ts;
+    try {
+        pm.assign((size_t)T * K * 2, 0.0);
+        bp.assign((size_t)T * K, 0.0);
+        ts.assign((size_t)T, 0.0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    for (int64_t t = 0; t < T; ++t)
+        for (int j = 0; j < K; ++j)
+            for (int h = 0; h < 2; ++h) pm[((size_t)t * K + j) * 2 + h] = density[((size_t)j * T + t) * 2 + h];
+    const State v = f64_slab(threads, T, K, 2, pm.data());
+    if (int rc = fft ? vacf_fft(v, ts.data(), bp.data()) : vacf_direct(v, ts.data(), bp.data())) return rc;
+    for (int j = 0; j < K; ++j)
+        for (int64_t t = 0; t < T; ++t) coll[(size_t)j * T + t] = bp[(size_t)t * K + j];
+    return TA_OK;
+}
+
+int scatter(const State& s, bool fft, int K, const double* kvecs, double* self, double* density, double* coll) {
+    const int64_t T = s.T, A = s.A;
+    const int D = s.D;
+    const void* slab = s.slabs[0];
+    const bool f32 = s.dtype == TA_F32;
+    std::vector<double> z, rho;
+    try {
+        z.assign((size_t)T * A * 2, 0.0);
+        if (!density && coll) rho.assign((size_t)K * T * 2, 0.0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    double* dens = density ? density : rho.data();
+    for (int j = 0; j < K; ++j) {
+        double q[3] = {0.0, 0.0, 0.0};
+        for (int d = 0; d < D; ++d) q[d] = kvecs[(size_t)j * D + d] / 6.283185307179586476925;
+#pragma omp parallel for num_threads(s.threads) schedule(static)
+        for (int64_t t = 0; t < T; ++t) {
+            double sc = 0.0, ss = 0.0;
+            for (int64_t n = 0; n < A; ++n) {
+                const size_t i = ((size_t)t * A + n) * D;
+                double u = q[0] * (f32 ? elem<float>(slab, i) : elem<double>(slab, i));
+                for (int d = 1; d < D; ++d) u = std::fma(q[d], f32 ? elem<float>(slab, i + d) : elem<double>(slab, i + d), u);
+                const double a = 6.283185307179586476925 * (u - std::nearbyint(u));
+                const double c = std::cos(a), sn = std::sin(a);
+                z[((size_t)t * A + n) * 2] = c, z[((size_t)t * A + n) * 2 + 1] = sn;
+                sc += c, ss += sn;
+            }
+            if (density || coll) dens[((size_t)j * T + t) * 2] = sc, dens[((size_t)j * T + t) * 2 + 1] = ss;
+        }
+        if (self) {
+            const State v = f64_slab(s.threads, T, A, 2, z.data());
+            double* out = self + (size_t)j * T;
+            if (int rc = fft ? vacf_fft(v, out, nullptr) : vacf_direct(v, out, nullptr)) return rc;
+        }
+    }
+    return coll ? scatter_collective(s.threads, fft, dens, K, T, coll) : TA_OK;
+}
+
 template <class E>
 int compound_t(const State& s, int64_t C, const int64_t* off, const int32_t* members, const double* w, const double* u,
                double* out) {

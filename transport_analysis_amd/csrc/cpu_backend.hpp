@@ -43,6 +43,13 @@ int current_cross(int threads, bool fft, const double* currents, int n_species, 
 // msd() / vacf_fft() / vacf_direct() on it; counts (n_species) or NULL; a species without atoms: zeros
 int species_self(const State& s, bool msd_quantity, bool fft, int n_species, const int32_t* species, const double* w,
                  double* self, int64_t* counts);
+// ta_scatter: the intermediate scattering functions of slab 0 (the positions) for K wavevectors kvecs (K, dim) in rad per length
+// unit, with scatter.hip's phase arithmetic (q = k / (2 pi); u = q . x by a product, then fma; r = u - rint(u); (cos, sin)(2 pi r)):
+// per wavevector a float64 (n_frames, n_atoms, 2) slab, self (K, n_frames) = its vacf_fft / vacf_direct lag sums, density
+// (K, n_frames, 2) = its plain sum in atom order, coll (K, n_frames) = scatter_collective of the density; each may be NULL
+int scatter(const State& s, bool fft, int K, const double* kvecs, double* self, double* density, double* coll);
+// coll (K, n_frames): the autocorrelations of the K densities (K, n_frames, 2), ONE by-particle vacf call on them as K atoms of dim 2
+int scatter_collective(int threads, bool fft, const double* density, int K, int64_t n_frames, double* coll);
 // ta_compound: out (n_frames, n_compounds, dim) float64 = sum_{i in [offsets[c], offsets[c + 1])} w_i x[t, members[i], d] -
 // g_c F[t, d] of slab 0 (g_c = sum_i w_i, F = sum_a u_a x[t, a, d]; frame_weights NULL: no such term; weights NULL: all 1),
 // the sum in member order (the first product, then fma), parallel over compounds; arguments checked by the caller

@@ -678,6 +678,28 @@ int ta_group_species_self(ta_group* g, int quantity, int fft, int n_species, con
     });
 }
 
+// Intermediate scattering: every member's self parts and densities of its atoms for the same wavevectors, added on the
+// host in member order, then ONE collective part of the summed density on the first member that holds atoms -- the rule of
+// ta_group_conductivity (a density the caller does not ask for is summed into a vector of the call's own)
+int ta_group_scatter(ta_group* g, int fft, int n_k, const double* h_kvecs, double* h_self, double* h_density, double* h_coll) {
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
+    TAG_CHECK(check_kvecs(gfail, g, fft, n_k, h_kvecs, g->T ? g->D : 0, h_self || h_density || h_coll));
+    TAG_CHECK(check_staged(g));
+    const size_t KT = (size_t)n_k * g->T;
+    std::vector<double> own;
+    if (h_coll && !h_density) own.resize(2 * KT);
+    double* dens = h_density ? h_density : h_coll ? own.data() : nullptr;
+    std::vector<int> who;
+    TAG_CHECK(sum_members(g, who, "scattering sums", {{0, KT, h_self}, {KT, 2 * KT, dens}}, [&](int i, double** d) {
+        return scatter_launch(g->ctx[i], fft, n_k, h_kvecs, h_self != nullptr, dens != nullptr, false, d);
+    }));
+    if (h_coll)
+        if (const int rc = scatter_collective_host(g->ctx[who[0]], fft, dens, n_k, g->T, h_coll)) return mfail(g, who[0], rc);
+    return TA_OK;
+    });
+}
+
 // Unwrap: every member's block of slab `slab` with the same box table, queued on all devices, then waited for
 int ta_group_unwrap(ta_group* g, int slab, const double* h_dimensions, const int* axes) {
     return group_call(g, [&]() -> int {

@@ -105,6 +105,24 @@ static int check_labels(Fail fail, Owner* owner, const int32_t* h_species, int64
 // h_counts (n_species) or NULL: its atoms per species
 int self_launch(ta_ctx* ctx, int quantity, int fft, int S, const int32_t* h_species, const double* h_w, int64_t* h_counts,
                 double** d_out);
+// the wavevector checks of ta_scatter* on a context (fail, ctx) or a group (gfail, g): the same messages for both.  D: the
+// components per wavevector (0: not known, nothing staged -- the caller reports that next)
+template <class Fail, class Owner>
+static int check_kvecs(Fail fail, Owner* owner, int fft, int n_k, const double* h_kvecs, int D, bool any_output) {
+    if (fft != 0 && fft != 1) return fail(owner, TA_E_INVALID, "fft must be 0 or 1");
+    if (!any_output) return fail(owner, TA_E_INVALID, "scatter: the self, density and collective outputs are all NULL");
+    if (!h_kvecs) return fail(owner, TA_E_INVALID, "wavevectors are NULL");
+    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(owner, TA_E_INVALID, "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
+    for (int64_t i = 0; i < (int64_t)n_k * D; ++i)
+        if (!(h_kvecs[i] - h_kvecs[i] == 0.0))
+            return fail(owner, TA_E_INVALID, "wavevector " + std::to_string(i / D) + " has a non-finite component");
+    return TA_OK;
+}
+// api.hip, for group.hip: one context's ta_scatter share (its staged slab 0, the call's wavevectors, checked by the caller),
+// queued: *d_out = self (n_k, n_frames), then the density (n_k, n_frames, 2), then coll (n_k, n_frames) -- the ones asked
+// for are valid after host_wait; and the collective part of a host density on the context's device, blocking
+int scatter_launch(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, bool self, bool density, bool coll, double** d_out);
+int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int n_k, int64_t T, double* h_coll);
 // api.hip, for group.hip: one context's ta_unwrap queued on its stream (box.tab must stay valid until host_wait)
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes);
 hipStream_t ctx_stream(ta_ctx* ctx);
@@ -243,6 +261,13 @@ hipError_t launch_species_sort(int n_cu, const void* x, bool f32, long pitch, lo
 hipError_t launch_compound(int n_cu, const void* x, bool f32, long pitch, long T, long n_cols, int D, long n_compounds,
                            const int* off, const int* member, const double* w, const double* g, const double* F, double* out,
                            hipStream_t st);
+
+// scatter.hip: the phase slab Z of Kc wavevectors q (Kc, D) (device array, turns per length unit) of a pair-major slab of
+// float64 or (f32) float32 elements, read as it is: pair jl n_atoms + n of Z = rows (cos, sin)(2 pi q_jl . x[t, n]), `pitch`
+// rows per pair, rows T ... pitch - 1 zeros; and the (T, K) -> (K, T) transposition of the collective part
+hipError_t launch_phase(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const double* q, int Kc,
+                        double* Z, hipStream_t st);
+hipError_t launch_scatter_transpose(const double* bp, long T, long K, double* out, hipStream_t st);
 
 // unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
 // box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)
