@@ -872,9 +872,11 @@ __device__ __forceinline__ auto& wf_pick(A& a, B& b) {
 //   pass 1: two seed requests (h, g2; g = h^2 -- R = 1: W_M^u = W_L^{2u}) and the twist inside the
 //           butterfly (DftTwisted) instead of R0 - 1 literal multiplications in front of it.
 // 21 / 22 instead of 23 memory requests per thread and unit.  (Pass 1 squaring g for g2 as well is
-// one request fewer and doubles the error of the lag sums -- the error of g2 enters R0 / 2 - 1 times
-// along either chain and h^4 carries four times that of a table entry: WF_SEED_DERIVE=3.  The
-// seed kept resident across the launch instead -- 4 registers -- spills 248-260 bytes.)
+// one request fewer: WF_SEED_DERIVE=3.  With both chains run to R0 - 1 it doubled the error of the
+// lag sums -- the error of g2 entered R0 / 2 - 1 times along either chain and h^4 carries four times
+// that of a table entry; with the chains stopped at R0 / 2 (WF_TWIDDLE_MIRROR) its error is below
+// the shipped one, and its gain, 0.3-0.7 %, under three spreads of the measurement: DESIGN.md section 9.
+// The seed kept resident across the launch instead -- 4 registers -- spills 248-260 bytes.)
 #ifndef WF_PASS_SPLIT
 #define WF_PASS_SPLIT 1   // 0: every plan reads the pass at run time
 #endif
@@ -884,6 +886,15 @@ __device__ __forceinline__ auto& wf_pick(A& a, B& b) {
 #endif
 #ifndef WF_TWIST_FOLD
 #define WF_TWIST_FOLD 1   // 0: the split pass-1 body keeps the literal twist in front of Dft<R0>
+#endif
+// The split bodies generate only half of the output twiddles t_q = W_L^{u (2q + c)}.  With G = W_L^{2 R0 u} = W_512^u
+//   pass 0: t_{R0-q} = G conj(t_q),   pass 1: t_{R0-q} = G conj(t_{q-1}),
+// and a sub-series scaled by conj(t) alone -- without G -- has its 512-point transform moved by one bin (shift theorem):
+// S2 only adds |.|^2 into per-bin accumulators, so the accumulator of position r of such a MIRRORED sub-series (pass 0:
+// q > R0/2, pass 1: q >= R0/2) holds the true bin of position r - 1 (mod 512), and store_acc, once per launch, writes it
+// there.  The chains by g2 stop at R0/2: 8 generating products instead of 17 at R0 = 20 (7 instead of 15 at R0 = 18).
+#ifndef WF_TWIDDLE_MIRROR
+#define WF_TWIDDLE_MIRROR 1  // 0: both chains run to R0 - 1 and every accumulator is stored where it stands
 #endif
 // (float32 slabs stay on the run-time pass: their kernels spill already -- 16 / 36 bytes at R0 = 18 / 20 for the
 // row requests along S2 -- and every split variant spills more, 28-52 bytes: tools/wfft/isa_table.py)
@@ -906,6 +917,7 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
     const int bi = blockIdx.x >> 3;
     const int pass = PASS >= 0 ? PASS : bi % npass;
     constexpr bool kTwistFold = PASS == 1 && WF_TWIST_FOLD && DftTwisted<R0>::kHave;
+    constexpr bool kMirror = PASS >= 0 && WF_TWIDDLE_MIRROR && R0 % 2 == 0;
     const long tuple = (blockIdx.x & 7) + 8 * (bi / npass), n_tuples = gridDim.x / npass;
     const int upa = BYP ? (D == 3 ? 2 : 1) : 1;  // units per atom (by-particle mode)
     // with an odd number of columns per atom, atoms 2i and 2i + 1 share a column pair (the last
@@ -1126,7 +1138,42 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
         }
         if constexpr (kTwistFold) DftTwisted<R0>::run(x);
         else Dft<R0>::run(x);
-        {
+        if constexpr (kMirror) {
+            // output twiddles t_q = W_L^{u (2q + c)} up to R0/2 only (two chains by g^2 as below); the far half of
+            // the outputs takes the conjugates (WF_TWIDDLE_MIRROR above); each output stored as soon as it is scaled
+            constexpr int H = R0 / 2;
+            cd te, to;
+            if constexpr (PASS == 0) {  // t_1 = g, t_2 = g2; x[q] t_q (q <= H), x[R0 - q] conj(t_q) (q < H)
+                te = g2;
+                to = g;
+                lds[u] = x[0];
+#pragma unroll
+                for (int q = 1; q <= H; ++q) {
+                    if (q >= 3 && (q & 1)) to = cmul(to, g2);
+                    else if (q >= 3) te = cmul(te, g2);
+                    const cd t = (q & 1) ? to : te;
+                    x[q] = cmul(x[q], t);
+                    lds[q * N1 + u] = x[q];
+                    if (q < H) {
+                        x[R0 - q] = cmulc(x[R0 - q], t);
+                        lds[(R0 - q) * N1 + u] = x[R0 - q];
+                    }
+                }
+            } else {  // t_0 = h, t_1 = h g; x[q] t_q and x[R0 - 1 - q] conj(t_q) (q < H)
+                te = h;
+                to = cmul(h, g);
+#pragma unroll
+                for (int q = 0; q < H; ++q) {
+                    if (q >= 2 && (q & 1)) to = cmul(to, g2);
+                    else if (q >= 2) te = cmul(te, g2);
+                    const cd t = (q & 1) ? to : te;
+                    x[q] = cmul(x[q], t);
+                    lds[q * N1 + u] = x[q];
+                    x[R0 - 1 - q] = cmulc(x[R0 - 1 - q], t);
+                    lds[(R0 - 1 - q) * N1 + u] = x[R0 - 1 - q];
+                }
+            }
+        } else {
             // output twiddles W_L^{u (2R q + c)} = h g^q: two chains (even / odd q) by g^2, each
             // output stored as soon as it is scaled (the 20 stores of a wave take ~260 LDS-path
             // cycles: issued in one burst at the end they are fully exposed)
@@ -1259,7 +1306,8 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
                 zero_pending = true;
             }
         } else {
-            if (nitem >= n_units) store_acc(tuple);
+            if constexpr (!kMirror)  // (the mirrored bodies store behind the loop)
+                if (nitem >= n_units) store_acc(tuple);
         }
         __builtin_amdgcn_sched_barrier(0);
         issue_loads_tail(nrs, nkind);
@@ -1267,6 +1315,40 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
         if constexpr (STAMP) st_tail += __builtin_amdgcn_s_memtime() - st_s2end;  // the row requests behind S2
         WF_STAMP(1)
         __syncthreads();
+    }
+    if constexpr (kMirror) {
+        // accg[tuple][pass][q][cc / 2][lane][cc & 1], once per launch.  A mirrored sub-series holds the true bin of
+        // position p - 1 at position p = (lane >> 3) + 8 (lane & 7) + 64 cc (mod 512): each of its accumulators goes to
+        // the address of that position -- lane - 8; lanes 1 ... 7: lane + 55; lane 0: lane 63 of cc - 1 -- 8 bytes at a
+        // time.  The three offsets below carry what differs from lane to lane, the rest is the instruction's constant.
+        if (tuple * grp < n_units) {
+            const int wv = __builtin_amdgcn_readfirstlane(wave);
+            const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
+                accg + (tuple * npass + pass) * (long)M, 0, M * 8, 0x00020000);
+            // (the lane counted again here: one register fewer across the loop, which R0 = 20 does not have)
+            int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            asm volatile("" : "+v"(ln));
+            const unsigned lm = (unsigned)(ln >= 8 ? ln - 8 : ln ? ln + 55 : 63) * 16u;
+#pragma unroll
+            for (int s = 0; s < NS1; ++s) {
+                const int q = P::sub_base(wv) + s;
+                if (s < P::NLO || wv < P::REM) {
+                    const bool mir = PASS == 0 ? q > R0 / 2 : q >= R0 / 2;
+                    const bool carry = mir && ln == 0;
+                    const unsigned ld = mir ? lm : (unsigned)ln * 16u;
+                    const unsigned v0 = ld + (carry ? 3080u : 0u);    // cc = 0:        -> cc = 7 of the same q
+                    const unsigned ve = ld + (carry ? 8u : 1024u);    // cc = 2, 4, 6:  -> cc - 1, the odd half
+                    const unsigned vo = ld + (carry ? 0u : 8u);       // cc odd:        -> cc - 1, the even half
+#pragma unroll
+                    for (int cc = 0; cc < 8; ++cc) {
+                        const unsigned at = (unsigned)((cc >> 1) * 64 * 16 + (cc & 1) * 8);
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(wf_u32x2, acc[s][cc]), sr,
+                                                              cc == 0 ? v0 : (cc & 1) ? vo + (at - 8u) : ve + (at - 1024u),
+                                                              (unsigned)(q * 4 * 64) * 16u, 0);
+                    }
+                }
+            }
+        }
     }
     if constexpr (!BYP) {
         // a tuple without units still owes its (zero) row of the partial spectra
