@@ -327,6 +327,37 @@ int ta_species_self(ta_ctx *ctx, int quantity, int fft, int n_species, const int
 int ta_scatter(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, double *h_self, double *h_density, double *h_coll);
 int ta_scatter_collective(ta_ctx *ctx, int fft, const double *h_density, int n_k, int64_t n_frames, double *h_coll);
 
+/* ta_vanhove : the self part of the van Hove function of the positions in slab 0 (VanHoveSelf): for n_lags frame lags
+ *              h_lags (strictly increasing, 0 <= lag < n_frames) the histogram of the displacements after a lag in n_bins
+ *              bins of width dr (r_max = n_bins dr) and their second and fourth moments.  With T frames, D staged columns:
+ *                d_j   = x[t + tau, n, j] - x[t, n, j]                 float64 (a float32 slab: widened first, then subtracted)
+ *                r2    = d_0 d_0, then fma(d_1, d_1, r2), then fma(d_2, d_2, r2)           (as many terms as D, in this order)
+ *                e[b]  = fl(fl(b dr) fl(b dr)), b = 0 ... n_bins      float64, formed once on the host
+ *                bin   = the b with e[b] <= r2 < e[b + 1];  r2 >= e[n_bins]: bin n_bins, the overflow bin
+ *                h_counts[l * (n_bins + 1) + b] = #{(t, n): t < T - tau_l, bin = b}                         int64
+ *                h_moments[l * 2 + {0, 1}]      = (sum r2, sum r2 r2) over the same pairs; r2 r2 added by fma(r2, r2, s4)
+ *              NOTHING is divided by an atom count or by T - tau.  The bin is defined on r2 against SQUARED edges, not on
+ *              sqrt(r2): the histogram is an exact integer quantity whenever r2 is exact, and because the CPU backend
+ *              follows the same operation order for r2, its counts equal the GPU's for any input.  Either output may be
+ *              NULL (not returned), not both; asking for one gives the same bits as asking for both.  counts and moments
+ *              add up over atoms -- shards, group members, ranks.
+ *              The pass k_vanhove reads the slab in the element type it has (a float32 device slab is read as float32 and
+ *              widened in registers), once per chunk of Lc lags: a workgroup keeps its origin frames in registers,
+ *              counts in a uint32 histogram in LDS (flushed into the uint64 one by integer atomic adds before it can
+ *              overflow) and adds the moments without floating-point atomics: a fixed reduction within a wave, a slot per
+ *              wave, one partial per (workgroup, lag), the partials added in a fixed order.  The same bits from run to
+ *              run.  Chunking: Lc = the largest count for which 8 (n_bins + 1) + Lc (64 + 4 (n_bins + 1)) bytes of LDS stay
+ *              within 64 KiB (at least 1), at most n_lags; option "vanhove_chunk" n >= 1 forces min(n, n_lags, that
+ *              count).  The results do not depend on Lc bit for bit.  ta_trim releases the scratch histogram and partials.
+ *              NULL h_lags, n_lags outside 1 ... TA_VANHOVE_MAX_LAGS, a lag < 0 or >= n_frames, lags not strictly
+ *              increasing, n_bins outside 1 ... TA_VANHOVE_MAX_BINS, dr not finite or <= 0, both outputs NULL (all checked
+ *              before anything is written): TA_E_INVALID; nothing staged: TA_E_STATE; n_atoms * dim must be below 2^31.
+ *              CPU backend: the same r2 arithmetic and table, OpenMP over atoms with int64 histograms per thread added at
+ *              the end, the moments per atom and then in atom order.  Timings: k_vanhove is the main kernel.              */
+#define TA_VANHOVE_MAX_LAGS 1024
+#define TA_VANHOVE_MAX_BINS 4096
+int ta_vanhove(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *h_counts, double *h_moments);
+
 /* ---- periodic unwrapping of a staged position slab ---------------------------------------------------------------
  * ta_unwrap: undo periodic wrapping of staging slab `slab` in place (MDAnalysis' NoJump), over the staged frames
  * in order.  h_dimensions: (n_frames, 6) float64 rows [a, b, c, alpha, beta, gamma] (A, degrees; ts.dimensions).
@@ -426,6 +457,12 @@ int ta_species_self_dev(ta_ctx *ctx, const double *d_x, int64_t n_frames, int64_
 int ta_scatter_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row, int fft,
                    int n_k, const double *h_kvecs, double *d_self, double *d_density, double *d_coll, void *stream);
 
+/* d_pos: frame-major float64 positions; h_lags: HOST lags (they size the launches; checked before anything is written);
+ * d_counts (n_lags, n_bins + 1) int64, d_moments (n_lags, 2) float64: device arrays, either may be NULL, not both.
+ * Shards' counts and moments add up. */
+int ta_vanhove_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row, int n_lags,
+                   const int64_t *h_lags, int n_bins, double dr, int64_t *d_counts, double *d_moments, void *stream);
+
 /* ---- compute on the staged (pair-major) slabs, device outputs, asynchronous on `stream` ----
  * Same arithmetic and outputs as the *_dev calls, on the slabs of ta_stage_alloc*: no
  * transposition, no second copy.  d_masses: (n_atoms,) float64 device array.              */
@@ -451,6 +488,10 @@ int ta_species_self_staged(ta_ctx *ctx, int quantity, int fft, int n_species, co
 /* h_kvecs: HOST wavevectors, as for ta_scatter_dev; slab 0 (the positions) is read in the element type it has */
 int ta_scatter_staged(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, double *d_self, double *d_density,
                       double *d_coll, void *stream);
+
+/* h_lags: HOST lags, as for ta_vanhove_dev; slab 0 (the positions) is read in the element type it has */
+int ta_vanhove_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *d_counts,
+                      double *d_moments, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns
@@ -526,6 +567,10 @@ int ta_group_species_self(ta_group *g, int quantity, int fft, int n_species, con
  * member that holds atoms.                                                                                          */
 int ta_group_scatter(ta_group *g, int fft, int n_k, const double *h_kvecs, double *h_self, double *h_density,
                      double *h_coll);
+/* ta_group_vanhove: ta_vanhove on every member with the same lags and bins (checked first): the members' counts are SUMMED
+ * on the host as int64, their moments in member order.                                                               */
+int ta_group_vanhove(ta_group *g, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *h_counts,
+                     double *h_moments);
 /* ta_group_unwrap: ta_unwrap on every member's block of slab `slab` (declared with ta_unwrap above) */
 int ta_group_unwrap(ta_group *g, int slab, const double *h_dimensions, const int *axes); /* every member's block */
 
@@ -631,6 +676,8 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      (ta_kernel_timeline);
  *   "scatter_chunk" n : wavevectors per pass of ta_scatter* (0, the default: as many as fit 32 GiB of scratch; n >= 1:
  *                      min(n, n_k)); the results do not depend on it;
+ *   "vanhove_chunk" n : lags per pass of ta_vanhove* (0, the default: as many as fit 64 KiB of LDS; n >= 1: min(n, n_lags,
+ *                      that count)); the results do not depend on it;
  *   "async_commit" 1|0 : ta_stage_commit hands its frame range to a worker thread of the context, which
  *                      makes the HIP calls (the caller's frame loop never waits on the runtime, e.g. while
  *                      another thread page-locks a result array); every call that touches the slabs joins

@@ -1,7 +1,8 @@
 """transport_analysis_amd — MI355X-native time-correlation kernels behind the
 transport-analysis API (VelocityAutocorr, ViscosityHelfand), MDAnalysis' EinsteinMSD, ConductivityHelfand and its species-resolved form, OnsagerHelfand, and their Green-Kubo
 (velocity) twins, ConductivityGreenKubo and OnsagerGreenKubo, and the intermediate scattering functions F_s(k, t) and F(k, t),
-IntermediateScattering."""
+IntermediateScattering, and their real-space partner, the self van Hove function G_s(r, t) with the non-Gaussian parameter,
+VanHoveSelf."""
 __version__ = "0.1.0"
 
 from .velocityautocorr import VelocityAutocorr  # noqa: F401
@@ -11,3 +12,4 @@ from .conductivity import ConductivityHelfand  # noqa: F401
 from .onsager import OnsagerHelfand  # noqa: F401
 from .greenkubo import ConductivityGreenKubo, OnsagerGreenKubo  # noqa: F401
 from .scattering import IntermediateScattering, kvectors_from_box  # noqa: F401
+from .vanhove import VanHoveSelf, log_lags  # noqa: F401

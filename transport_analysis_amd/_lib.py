@@ -39,6 +39,7 @@ _UNWRAP = _int(_vp, _ci, _vp, _vp)
 _ONSAGER = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, fft, n_species, h_species, h_weights, h_moments, h_cross)
 _SELF = _int(_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, quantity, fft, n_species, h_species, h_weights, h_self, h_counts)
 _SCATTER = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, fft, n_k, h_kvecs, h_self, h_density, h_coll)
+_VANHOVE = _int(_vp, _ci, _vp, _ci, _dbl, _vp, _vp)  # (handle, n_lags, h_lags, n_bins, dr, h_counts, h_moments)
 
 #: every symbol include/ta_hip.h declares -> (result type, argument types): the one table EXPORTS and lib() are made of
 _API = {
@@ -66,6 +67,8 @@ _API = {
     "ta_scatter": _SCATTER, "ta_scatter_collective": _int(_vp, _ci, _vp, _ci, _i64, _vp),
     "ta_scatter_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_scatter_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
+    "ta_vanhove": _VANHOVE, "ta_vanhove_staged": _int(_vp, _ci, _vp, _ci, _dbl, _vp, _vp, _vp),
+    "ta_vanhove_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _ci, _dbl, _vp, _vp, _vp),
     "ta_compound": _int(_vp, _i64, _vp, _vp, _vp, _vp, _P(_vp)),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
     "ta_helfand_msd_dev": _int(_vp, _vp, _vp, _vp, _i64, _i64, _ci, _i64, _dbl, _vp, _vp, _i64, _vp),
@@ -88,7 +91,7 @@ _API = {
     "ta_group_vacf_fft": _HOST, "ta_group_vacf_direct": _HOST, "ta_group_helfand_msd": _int(_vp, _vp, _dbl, _vp, _vp),
     "ta_group_msd": _int(_vp, _ci, _vp, _vp), "ta_group_conductivity": _COND, "ta_group_unwrap": _UNWRAP,
     "ta_group_onsager": _ONSAGER, "ta_group_current": _ONSAGER, "ta_group_species_self": _SELF,
-    "ta_group_scatter": _SCATTER,
+    "ta_group_scatter": _SCATTER, "ta_group_vanhove": _VANHOVE,
 }
 EXPORTS = tuple(_API)
 
@@ -485,6 +488,25 @@ class _Staged:
         self._call("scatter", int(fft), K, _ptr(k), _ptr(fs), _ptr(rho), _ptr(coll))
         return fs, rho, coll
 
+    @staticmethod
+    def _lags(lags):
+        lg = np.ascontiguousarray(lags, dtype=np.int64)
+        if lg.ndim != 1:
+            raise ValueError(f"lags: shape {lg.shape}, expected (n_lags,) integer frame lags")
+        return lg, int(lg.shape[0])
+
+    def vanhove(self, lags, n_bins, dr, counts=True, moments=True):
+        """Self van Hove function of slab 0 (the positions), ta_vanhove: for the integer frame `lags` (strictly increasing,
+        below n_frames) the histogram of |x(t + lag) - x(t)| in `n_bins` bins of width `dr` plus the overflow bin, and
+        (sum r2, sum r2 r2): (counts (n_lags, n_bins + 1) int64, moments (n_lags, 2)), None for one not asked for; nothing
+        is divided by the number of pairs.  A group: the members' counts and moments are summed."""
+        lg, L = self._lags(lags)
+        n_bins = int(n_bins)
+        cnt = np.empty((L, max(n_bins, 0) + 1), dtype=np.int64) if counts else None
+        mom = np.empty((L, 2), dtype=np.float64) if moments else None
+        self._call("vanhove", L, _ptr(lg), n_bins, float(dr), _ptr(cnt), _ptr(mom))
+        return cnt, mom
+
     def unwrap(self, slab, dimensions, axes):
         """Undo periodic wrapping of staged slab `slab` in place (MDAnalysis' NoJump, ta_unwrap; a group: on every
         member's block of the slab): `dimensions` the (n_frames, 6) boxes [a, b, c, alpha, beta, gamma] of the staged
@@ -703,6 +725,17 @@ class Context(_Staged):
         """`kvectors`: HOST wavevectors (n_k, dim) (checked by the library before anything is written)"""
         k, K = self._kvectors(kvectors, self._staged_shape()[2])
         self._call("scatter_staged", int(fft), K, _ptr(k), d_self or None, d_density or None, d_coll or None, stream or None)
+
+    def vanhove_dev(self, d_pos, n_frames, n_atoms, dim, ld_row, lags, n_bins, dr, d_counts=0, d_moments=0, stream=0):
+        """`lags`: HOST frame lags (checked by the library before anything is written); d_counts (n_lags, n_bins + 1) int64"""
+        lg, L = self._lags(lags)
+        self._call("vanhove_dev", d_pos, n_frames, n_atoms, dim, ld_row, L, _ptr(lg), int(n_bins), float(dr), d_counts or None,
+                   d_moments or None, stream or None)
+
+    def vanhove_staged(self, lags, n_bins, dr, d_counts=0, d_moments=0, stream=0):
+        """`lags`: HOST frame lags (checked by the library before anything is written); d_counts (n_lags, n_bins + 1) int64"""
+        lg, L = self._lags(lags)
+        self._call("vanhove_staged", L, _ptr(lg), int(n_bins), float(dr), d_counts or None, d_moments or None, stream or None)
 
     # -- timing ----------------------------------------------------------
     def timing_history(self, max_n=64):

@@ -23,6 +23,7 @@
 #include "direct_kernels.hpp"
 #include "ta_internal.hpp"
 #include "unwrap_box.hpp"
+#include "vanhove_math.hpp"
 
 using namespace ta;
 
@@ -102,6 +103,7 @@ private:
     X(stage_device_f32, 0, nullptr) /* device slabs hold float32 when nothing wider is coming in */                        \
     X(timeline, 0, nullptr)        /* record the kernel timeline of every compute call (ta_kernel_timeline) */             \
     X(scatter_chunk, 0, opt_check_scatter_chunk) /* wavevectors per pass of ta_scatter* (0: as many as fit kScatterBudget) */ \
+    X(vanhove_chunk, 0, opt_check_vanhove_chunk) /* lags per pass of ta_vanhove* (0: as many as fit a workgroup's LDS) */ \
     X(async_commit, 1, opt_flush_commits) /* ta_stage_commit goes through the commit queue; flushed before it changes */   \
     X(lock_ahead, 1, nullptr)      /* the commit worker page-locks the chunks behind the one it committed */               \
     X(cpu_threads, 0, opt_set_cpu_threads) /* CPU backend: OpenMP team size (0: the runtime's default) */                  \
@@ -153,6 +155,12 @@ struct ta_ctx {
     DevBuf scatter_work{workspaces, kTrimmed}, scatter_out{workspaces, kKept};
     std::vector<double> scatter_q_h;
     hipEvent_t ev_kvec = nullptr;
+    // self van Hove function (vanhove_pm): the lags (int64) with the squared edges behind them, the uint64 histogram and
+    // the workgroups' moment partials (the scratch: trimmed), the outputs of host-facing calls.  vh_tab_h is what the
+    // upload of the table reads: it stays until ev_vh says the copy is done
+    DevBuf vh_tab{workspaces, kKept}, vh_hist{workspaces, kTrimmed}, vh_part{workspaces, kTrimmed}, vh_out{workspaces, kKept};
+    std::vector<double> vh_tab_h;
+    hipEvent_t ev_vh = nullptr;
     // ta_compound: the plan (offsets, members, member weights, their sums per compound) and the (n_frames, dim) weighted
     // mean F of the barycentric term; the per-atom frame weights and F's partial sums use the Onsager workspaces
     DevBuf comp_plan{workspaces, kTrimmed}, comp_f{workspaces, kTrimmed};
@@ -1193,6 +1201,56 @@ int scatter_pm(ta_ctx* ctx, bool fft, const Slab& slab, int K, double* d_self, d
     return call_end(ctx, st);
 }
 
+// ---- self van Hove function (vanhove.hip) ---------------------------------------------------------------------------
+// T: the frames the lags are checked against (0: nothing staged -- the caller reports that next)
+int vanhove_args(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, int64_t T, const void* o_counts, const void* o_moments) {
+    return check_vanhove(fail, ctx, L, h_lags, B, dr, T, o_counts || o_moments);
+}
+
+// The host half of one call, before it is opened: the lags and the squared edges e[0 ... B] (formed once, here) queued for
+// upload on `st` as one table.  Nothing on the device has been written when this fails.
+int vanhove_plan(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, int64_t A, int D, hipStream_t st) {
+    if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "vanhove: n_atoms * dim must be below 2^31");
+    const size_t n = (size_t)L + (size_t)B + 1;
+    TA_CHECK(ensure(ctx, ctx->vh_tab, sizeof(double) * n));
+    if (!ctx->ev_vh) TA_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_vh, hipEventDisableTiming));
+    else TA_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_vh));  // the last call's upload has left vh_tab_h
+    ctx->vh_tab_h.resize(n);
+    static_assert(sizeof(int64_t) == sizeof(double), "the lags travel in the table's first n_lags slots");
+    memcpy(ctx->vh_tab_h.data(), h_lags, sizeof(int64_t) * (size_t)L);
+    vh_edges(B, dr, ctx->vh_tab_h.data() + L);
+    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->vh_tab.p, ctx->vh_tab_h.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev_vh, st));
+    return TA_OK;
+}
+
+// One van Hove call on a pair-major position slab of either element type, read as it is (the caller has opened the call's
+// bracket, it is closed here; vanhove_plan has queued the table).  The uint64 histogram is zeroed, then one k_vanhove
+// launch per chunk of Lc lags adds its bins and writes its columns of the workgroups' moment partials; after the last chunk
+// the partials are added in a fixed order (k_sum_partials) and the histogram is copied out.  Nothing depends on Lc but which lags share a
+// launch: the same bits for every chunk size.  ev[1] / ev[2] bracket the (last) pass.
+int vanhove_pm(ta_ctx* ctx, const Slab& slab, int L, int B, double dr, int64_t* d_counts, double* d_moments) {
+    hipStream_t st = slab.st;
+    const int fit = vanhove_max_chunk(B);
+    const int Lc = (int)std::min<int64_t>({ctx->opt_vanhove_chunk > 0 ? ctx->opt_vanhove_chunk : (int64_t)L, (int64_t)L, (int64_t)fit});
+    const int n_parts = vanhove_parts(ctx->n_cu, (long)slab.pitch, (long)slab.A);
+    const size_t hist_bytes = sizeof(int64_t) * (size_t)L * (size_t)(B + 1);
+    TA_CHECK(ensure(ctx, ctx->vh_hist, hist_bytes));
+    TA_CHECK(ensure(ctx, ctx->vh_part, sizeof(double) * (size_t)n_parts * 2 * (size_t)L));
+    const int64_t* d_lags = (const int64_t*)ctx->vh_tab.p;
+    const double* d_e = (const double*)ctx->vh_tab.p + L;
+    TA_HIP_TRY(ctx, hipMemsetAsync(ctx->vh_hist.p, 0, hist_bytes, st));
+    for (int l0 = 0; l0 < L; l0 += Lc)
+        TA_LAUNCH_MAIN(ctx, "k_vanhove", st,
+                       launch_vanhove(ctx->n_cu, slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, slab.D, d_lags, l0,
+                                      std::min(Lc, L - l0), L, d_e, B, vh_inv_dr(dr), (unsigned long long*)ctx->vh_hist.p,
+                                      (double*)ctx->vh_part.p, st));
+    if (d_moments)
+        TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->vh_part.p, n_parts, 2L * L, d_moments, st));
+    if (d_counts) TA_HIP_TRY(ctx, hipMemcpyAsync(d_counts, ctx->vh_hist.p, hist_bytes, hipMemcpyDeviceToDevice, st));
+    return call_end(ctx, st);
+}
+
 // ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
 // This is the seam: a CPU context's staging and host-facing calls end up in the cpu_* functions below, reached by one
 // early branch of their entry point (after the checks both kinds of context share); nothing below makes a HIP call.
@@ -1271,6 +1329,9 @@ int opt_set_cpu_threads(ta_ctx* ctx, int64_t value) {
 int opt_flush_commits(ta_ctx* ctx, int64_t) { return ctx->commits.flush(); }
 int opt_check_scatter_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "scatter_chunk: 0 (automatic) or the wavevectors per pass");
+}
+int opt_check_vanhove_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "vanhove_chunk: 0 (automatic) or the lags per pass");
 }
 
 struct Option {
@@ -1395,7 +1456,7 @@ int ta_ctx_destroy(ta_ctx* ctx) {
         for (auto& ev : q)
             if (ev) hipEventDestroy(ev);
     if (ctx->ev_stage) hipEventDestroy(ctx->ev_stage);
-    for (hipEvent_t e : {ctx->ev_order, ctx->ev_kvec})
+    for (hipEvent_t e : {ctx->ev_order, ctx->ev_kvec, ctx->ev_vh})
         if (e) {
             hipEventSynchronize(e);  // (the upload may be on a caller's stream)
             hipEventDestroy(e);
@@ -1968,6 +2029,30 @@ int ta_scatter_staged(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, doub
     });
 }
 
+// Self van Hove function: slab 0 / d_pos holds the positions; the staged slab is read in its own element type (never
+// widened); the lags are a HOST array: they size the launches, and vanhove_plan runs before the call is opened
+static int vanhove_entry(ta_ctx* ctx, const DevSrc* dev, int n_lags, const int64_t* h_lags, int n_bins, double dr,
+                         int64_t* d_counts, double* d_moments, void* stream) {
+    return slab_entry(
+        ctx, dev, stream,
+        [&] { return vanhove_args(ctx, n_lags, h_lags, n_bins, dr, dev ? dev->T : ctx->st_nslabs ? ctx->st_T : 0, d_counts, d_moments); },
+        [&](const Slab& s) { return vanhove_plan(ctx, n_lags, h_lags, n_bins, dr, s.A, s.D, s.st); },
+        [&](const Slab& s) { return vanhove_pm(ctx, s, n_lags, n_bins, dr, d_counts, d_moments); });
+}
+int ta_vanhove_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int n_lags, const int64_t* h_lags,
+                   int n_bins, double dr, int64_t* d_counts, double* d_moments, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    const DevSrc src{d_pos, T, A, D, ld_row};
+    return vanhove_entry(ctx, &src, n_lags, h_lags, n_bins, dr, d_counts, d_moments, stream);
+    });
+}
+int ta_vanhove_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, double dr, int64_t* d_counts, double* d_moments,
+                      void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    return vanhove_entry(ctx, nullptr, n_lags, h_lags, n_bins, dr, d_counts, d_moments, stream);
+    });
+}
+
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guarded(fail, ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
@@ -2287,6 +2372,27 @@ int scatter_launch(ta_ctx* ctx, int fft, int K, const double* h_kvecs, bool self
     return TA_OK;
 }
 
+// Van Hove share of a host-facing call, queued on ctx->stream and not waited for: the lags and bins (checked by the caller)
+// uploaded, counts (L, B + 1) int64, then moments (L, 2) left on the device in *d_out (the ones asked for)
+int vanhove_launch(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, bool counts, bool moments, void** d_out) {
+    char* out = nullptr;
+    const size_t n_counts = (size_t)L * (size_t)(B + 1);
+    TA_CHECK(slab_entry(
+        ctx, nullptr, ctx->stream, no_args,
+        [&](const Slab& s) -> int {
+            TA_CHECK(vanhove_plan(ctx, L, h_lags, B, dr, s.A, s.D, ctx->stream));
+            TA_CHECK(ensure(ctx, ctx->vh_out, sizeof(int64_t) * n_counts + sizeof(double) * 2 * (size_t)L));
+            out = (char*)ctx->vh_out.p;
+            return TA_OK;
+        },
+        [&](const Slab& s) {
+            return vanhove_pm(ctx, s, L, B, dr, counts ? (int64_t*)out : nullptr,
+                              moments ? (double*)(out + sizeof(int64_t) * n_counts) : nullptr);
+        }));
+    *d_out = out;
+    return TA_OK;
+}
+
 // The collective part of a host (K, T, 2) density on this context's device, blocking, as a compute call of its own
 // (ta_scatter_collective; the group's ONE evaluation after its members' sums).  Needs no staged slab.
 int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int K, int64_t T, double* h_coll) {
@@ -2505,6 +2611,25 @@ int ta_scatter_collective(ta_ctx* ctx, int fft, const double* h_density, int n_k
         return TA_OK;
     }
     return ta::scatter_collective_host(ctx, fft, h_density, n_k, n_frames, h_coll);
+    });
+}
+
+int ta_vanhove(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, double dr, int64_t* h_counts, double* h_moments) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(vanhove_args(ctx, n_lags, h_lags, n_bins, dr, ctx->st_nslabs ? ctx->st_T : 0, h_counts, h_moments));
+    TA_CHECK(check_staged(ctx));
+    if (ctx->is_cpu) {
+        if (ctx->st_A * ctx->st_D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "vanhove: n_atoms * dim must be below 2^31");
+        if (int rc = ta::cpu::vanhove(cpu_state(ctx), n_lags, h_lags, n_bins, dr, h_counts, h_moments))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    void* d_out = nullptr;
+    TA_CHECK(ta::vanhove_launch(ctx, n_lags, h_lags, n_bins, dr, h_counts != nullptr, h_moments != nullptr, &d_out));
+    const size_t n_counts = (size_t)n_lags * (size_t)(n_bins + 1);  // (int64 counts travel as 8-byte elements)
+    return host_finish(ctx, {{(double*)h_counts, (const double*)d_out, n_counts},
+                             {h_moments, (const double*)d_out + n_counts, 2 * (size_t)n_lags}});
     });
 }
 

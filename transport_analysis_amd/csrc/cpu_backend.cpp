@@ -40,6 +40,7 @@
 #include "../../include/ta_hip.h"
 #include "cpu_backend.hpp"
 #include "unwrap_box.hpp"
+#include "vanhove_math.hpp"
 
 namespace ta {
 namespace cpu {
@@ -597,6 +598,74 @@ int scatter(const State& s, bool fft, int K, const double* kvecs, double* self, 
         }
     }
     return coll ? scatter_collective(s.threads, fft, dens, K, T, coll) : TA_OK;
+}
+
+// Atoms in blocks of kVhBlock: OpenMP threads take atoms of a block, each with an int64 histogram of its own and every
+// atom's moments in a slot of its own; after a block the moments are added in atom order, after the last one the threads'
+// histograms: neither depends on the number of threads
+constexpr int64_t kVhBlock = 1024;
+
+template <class E, int D>
+int vanhove_t(const State& s, int L, const int64_t* lags, int B, double dr, int64_t* counts, double* moments) {
+    const int64_t T = s.T, A = s.A;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    const int nth = s.threads > 0 ? s.threads : 1;
+    const size_t nb = (size_t)B + 1, nh = (size_t)L * nb;
+    std::vector<double> e, mom;
+    std::vector<int64_t> hist;
+    try {
+        e.assign(nb, 0.0);
+        if (counts) hist.assign((size_t)nth * nh, 0);
+        if (moments) mom.assign((size_t)kVhBlock * L * 2, 0.0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    vh_edges(B, dr, e.data());
+    const float inv = vh_inv_dr(dr);
+    if (moments) std::fill(moments, moments + 2 * (size_t)L, 0.0);
+    for (int64_t n0 = 0; n0 < A; n0 += kVhBlock) {
+        const int64_t n1 = std::min(A, n0 + kVhBlock);
+#pragma omp parallel for num_threads(nth) schedule(static)
+        for (int64_t n = n0; n < n1; ++n) {
+            int64_t* h = counts ? hist.data() + (size_t)omp_get_thread_num() * nh : nullptr;
+            for (int l = 0; l < L; ++l) {
+                const int64_t tau = lags[l];
+                double s2 = 0.0, s4 = 0.0;
+                for (int64_t t = 0; t + tau < T; ++t) {
+                    double a[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
+                    for (int d = 0; d < D; ++d) {
+                        a[d] = (double)x[((size_t)t * A + n) * D + d];
+                        b[d] = (double)x[((size_t)(t + tau) * A + n) * D + d];
+                    }
+                    const double r2 = vh_r2<D>(a, b);
+                    s2 += r2;
+                    s4 = std::fma(r2, r2, s4);
+                    if (h) ++h[l * nb + vh_bin(r2, e.data(), B, inv)];
+                }
+                if (moments) mom[((size_t)(n - n0) * L + l) * 2] = s2, mom[((size_t)(n - n0) * L + l) * 2 + 1] = s4;
+            }
+        }
+        if (moments)
+            for (int64_t n = n0; n < n1; ++n)
+                for (size_t i = 0; i < 2 * (size_t)L; ++i) moments[i] += mom[(size_t)(n - n0) * L * 2 + i];
+    }
+    if (counts) {
+        std::fill(counts, counts + nh, (int64_t)0);
+        for (int th = 0; th < nth; ++th)
+            for (size_t i = 0; i < nh; ++i) counts[i] += hist[(size_t)th * nh + i];
+    }
+    return TA_OK;
+}
+
+template <class E>
+int vanhove_e(const State& s, int L, const int64_t* lags, int B, double dr, int64_t* counts, double* moments) {
+    if (s.D == 1) return vanhove_t<E, 1>(s, L, lags, B, dr, counts, moments);
+    if (s.D == 2) return vanhove_t<E, 2>(s, L, lags, B, dr, counts, moments);
+    return vanhove_t<E, 3>(s, L, lags, B, dr, counts, moments);
+}
+
+int vanhove(const State& s, int L, const int64_t* lags, int B, double dr, int64_t* counts, double* moments) {
+    return s.dtype == TA_F32 ? vanhove_e<float>(s, L, lags, B, dr, counts, moments) : vanhove_e<double>(s, L, lags, B, dr, counts, moments);
 }
 
 template <class E>

@@ -50,6 +50,11 @@ int species_self(const State& s, bool msd_quantity, bool fft, int n_species, con
 int scatter(const State& s, bool fft, int K, const double* kvecs, double* self, double* density, double* coll);
 // coll (K, n_frames): the autocorrelations of the K densities (K, n_frames, 2), ONE by-particle vacf call on them as K atoms of dim 2
 int scatter_collective(int threads, bool fft, const double* density, int K, int64_t n_frames, double* coll);
+// ta_vanhove: the self van Hove histogram of slab 0 (the positions) for L strictly increasing lags, B bins of width dr, with
+// vanhove_math.hpp's arithmetic (r2 by a product, then fma; the squared-edge table; the bin of the definition), as
+// vanhove.hip: counts (L, B + 1) int64 (OpenMP over atoms, a histogram per thread, added at the end), moments (L, 2) = (sum r2,
+// sum r2 r2) per atom, then in atom order; either may be NULL; arguments checked by the caller
+int vanhove(const State& s, int L, const int64_t* lags, int B, double dr, int64_t* counts, double* moments);
 // ta_compound: out (n_frames, n_compounds, dim) float64 = sum_{i in [offsets[c], offsets[c + 1])} w_i x[t, members[i], d] -
 // g_c F[t, d] of slab 0 (g_c = sum_i w_i, F = sum_a u_a x[t, a, d]; frame_weights NULL: no such term; weights NULL: all 1),
 // the sum in member order (the first product, then fma), parallel over compounds; arguments checked by the caller

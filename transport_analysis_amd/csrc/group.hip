@@ -700,6 +700,41 @@ int ta_group_scatter(ta_group* g, int fft, int n_k, const double* h_kvecs, doubl
     });
 }
 
+// Self van Hove function: every member's counts and moments of its atoms for the same lags and bins, copied into host
+// vectors of the members' own; then the counts are added as int64 and the moments in member order (both add up over
+// atoms: nothing follows the sums)
+int ta_group_vanhove(ta_group* g, int n_lags, const int64_t* h_lags, int n_bins, double dr, int64_t* h_counts, double* h_moments) {
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
+    TAG_CHECK(check_vanhove(gfail, g, n_lags, h_lags, n_bins, dr, g->T, h_counts || h_moments));
+    TAG_CHECK(check_staged(g));
+    const size_t nc = (size_t)n_lags * (size_t)(n_bins + 1), nm = 2 * (size_t)n_lags;
+    std::vector<std::vector<int64_t>> cnt(g->ctx.size());
+    std::vector<std::vector<double>> mom(g->ctx.size());
+    std::vector<int> who;
+    hipError_t he = hipSuccess;
+    int rc = for_members(g, &who, [&](int i) {
+        void* d = nullptr;
+        if (const int r = vanhove_launch(g->ctx[i], n_lags, h_lags, n_bins, dr, h_counts != nullptr, h_moments != nullptr, &d)) return r;
+        cnt[i].resize(h_counts ? nc : 0), mom[i].resize(h_moments ? nm : 0);  // (once: copies into them are in flight from here on)
+        if (h_counts) he = hipMemcpyAsync(cnt[i].data(), d, sizeof(int64_t) * nc, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
+        if (h_moments && he == hipSuccess)
+            he = hipMemcpyAsync(mom[i].data(), (const int64_t*)d + nc, sizeof(double) * nm, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
+        return he == hipSuccess ? TA_OK : TA_E_HIP;
+    });
+    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string("van Hove sums copy: ") + hipGetErrorString(he));
+    if (rc) return drained(g, who, rc);
+    TAG_CHECK(wait_members(g, who));
+    if (h_counts) std::fill(h_counts, h_counts + nc, (int64_t)0);
+    if (h_moments) std::fill(h_moments, h_moments + nm, 0.0);
+    for (int i : who) {
+        for (size_t k = 0; h_counts && k < nc; ++k) h_counts[k] += cnt[i][k];
+        for (size_t k = 0; h_moments && k < nm; ++k) h_moments[k] += mom[i][k];
+    }
+    return TA_OK;
+    });
+}
+
 // Unwrap: every member's block of slab `slab` with the same box table, queued on all devices, then waited for
 int ta_group_unwrap(ta_group* g, int slab, const double* h_dimensions, const int* axes) {
     return group_call(g, [&]() -> int {

@@ -123,6 +123,29 @@ static int check_kvecs(Fail fail, Owner* owner, int fft, int n_k, const double* 
 // for are valid after host_wait; and the collective part of a host density on the context's device, blocking
 int scatter_launch(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, bool self, bool density, bool coll, double** d_out);
 int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int n_k, int64_t T, double* h_coll);
+// the argument checks of ta_vanhove* on a context (fail, ctx) or a group (gfail, g): the same messages for both.  T: the
+// frames the lags are checked against (0: not known, nothing staged -- the caller reports that next)
+template <class Fail, class Owner>
+static int check_vanhove(Fail fail, Owner* owner, int n_lags, const int64_t* h_lags, int n_bins, double dr, int64_t T,
+                         bool any_output) {
+    if (!h_lags) return fail(owner, TA_E_INVALID, "vanhove: lags are NULL");
+    if (n_lags < 1 || n_lags > TA_VANHOVE_MAX_LAGS)
+        return fail(owner, TA_E_INVALID, "vanhove: n_lags must be 1 ... " + std::to_string(TA_VANHOVE_MAX_LAGS));
+    if (n_bins < 1 || n_bins > TA_VANHOVE_MAX_BINS)
+        return fail(owner, TA_E_INVALID, "vanhove: n_bins must be 1 ... " + std::to_string(TA_VANHOVE_MAX_BINS));
+    if (!(dr - dr == 0.0) || !(dr > 0.0)) return fail(owner, TA_E_INVALID, "vanhove: dr must be finite and > 0");
+    if (!any_output) return fail(owner, TA_E_INVALID, "vanhove: the counts and moments outputs are both NULL");
+    for (int l = 0; l < n_lags; ++l) {
+        if (h_lags[l] < 0 || (T > 0 && h_lags[l] >= T))
+            return fail(owner, TA_E_INVALID, "vanhove: lag " + std::to_string(h_lags[l]) + " is outside 0 ... n_frames - 1");
+        if (l && h_lags[l] <= h_lags[l - 1]) return fail(owner, TA_E_INVALID, "vanhove: the lags must be strictly increasing");
+    }
+    return TA_OK;
+}
+// api.hip, for group.hip: one context's ta_vanhove share (its staged slab 0, the call's lags and bins, checked by the
+// caller), queued: *d_out = counts (n_lags, n_bins + 1) int64, then moments (n_lags, 2) float64 -- the ones asked for are
+// valid after host_wait
+int vanhove_launch(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, double dr, bool counts, bool moments, void** d_out);
 // api.hip, for group.hip: one context's ta_unwrap queued on its stream (box.tab must stay valid until host_wait)
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes);
 hipStream_t ctx_stream(ta_ctx* ctx);
@@ -268,6 +291,17 @@ hipError_t launch_compound(int n_cu, const void* x, bool f32, long pitch, long T
 hipError_t launch_phase(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const double* q, int Kc,
                         double* Z, hipStream_t st);
 hipError_t launch_scatter_transpose(const double* bp, long T, long K, double* out, hipStream_t st);
+
+// vanhove.hip: the self van Hove histogram of a pair-major slab of float64 or (f32) float32 elements, read as it is, for the
+// lags [l0, l0 + Lc) of L (device array `lags`): counts (L, B + 1) uint64 (zeroed by the caller before the first chunk)
+// gets the chunk's bins added, partial [vanhove_parts][L][2] the chunk's (sum r2, sum r2 r2) per workgroup (k_sum_partials
+// adds them in order once every chunk has run).  e: the B + 1 squared edges (device), inv_dr: the float32 bin guess's
+// factor (vanhove_math.hpp).  vanhove_max_chunk: the lags per launch that fit a workgroup's LDS (at least 1).
+int vanhove_max_chunk(int B);
+int vanhove_parts(int n_cu, long pitch, long n_atoms);
+hipError_t launch_vanhove(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const int64_t* lags, int l0,
+                          int Lc, int L, const double* e, int B, float inv_dr, unsigned long long* counts, double* partial,
+                          hipStream_t st);
 
 // unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
 // box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)

@@ -1,0 +1,200 @@
+// vanhove.hip — the self part of the van Hove function: for L lags tau_l the histogram of the squared displacements
+// |x[t + tau, n] - x[t, n]|^2 over all pairs (t, n) with t + tau < T, against squared bin edges, and their first two moments
+//
+//   counts[l, b]  = #{(t, n): e[b] <= r2 < e[b + 1]}  (b = B: r2 >= e[B], the overflow bin)      uint64 (L, B + 1)
+//   moments[l, :] = (sum r2, sum r2 r2)                                                          float64 (L, 2)
+//
+// with the arithmetic of vanhove_math.hpp (the CPU backend follows it: equal counts for any input).  The slab is read as it
+// is, a float32 one as float32.  A histogram is no correlation: there is no FFT form and nothing else in the library
+// computes it; k_vanhove is one pass over the slab per chunk of Lc lags.
+//
+// Determinism.  The counts are integers: LDS and global integer adds give the same bits in any order.  The moments use
+// no floating-point atomics: a thread adds its frames in order, a wave reduces by a fixed butterfly, each wave adds into
+// its own LDS slot in atom-loop order, the workgroup adds its waves' slots in wave order into ONE partial per (workgroup,
+// lag), and k_sum_partials adds the partials in its fixed order.  None of this depends on Lc: the same bits for every chunk size.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <type_traits>
+
+#include "pm_read.hpp"
+#include "ta_internal.hpp"
+#include "vanhove_math.hpp"
+
+namespace ta {
+namespace {
+
+constexpr int kVhWaves = kPmThreads / 64;
+// A workgroup adds at most kPmThreads kPmFrames = 1024 to a bin per (atom, lag): its uint32 bins are flushed into the
+// uint64 histogram at the latest every 2^21 atoms of its loop (2^31 per bin)
+constexpr int kVhFlushAtoms = 1 << 21;
+constexpr size_t kVhLdsBudget = 64 << 10;  // a choice (two workgroups on a CU's 160 KB), not a measurement
+
+// LDS of a workgroup: e[B + 1] doubles, the waves' moment slots [wave][Lc][2] doubles, the histogram [Lc][B + 1] uint32
+constexpr size_t vh_lds_bytes(int B, int Lc) {
+    return sizeof(double) * (size_t)(B + 1) + (size_t)Lc * (sizeof(double) * 2 * kVhWaves + sizeof(unsigned) * (size_t)(B + 1));
+}
+
+// row r (one frame, 8 bytes per pair) of a float32 atom's pairs: what a lagged row at an odd lag needs
+template <int D>
+__device__ __forceinline__ void vh_row32(const PmAtom<float, D>& a, long r, double (&out)[3]) {
+    const float2* p = reinterpret_cast<const float2*>(a.src);
+    const float2 qa = p[r], qb = D == 3 ? p[2 * a.next + r] : qa;
+    pm_pick<D>(qa.x, qa.y, qb.x, qb.y, a.odd, out);
+}
+
+// LDS bins (uint32) of the chunk's lags into the uint64 histogram, and cleared (callers: between two barriers)
+__device__ __forceinline__ void vh_flush(unsigned* hist, int n, unsigned long long* __restrict__ counts) {
+    for (int i = threadIdx.x; i < n; i += kPmThreads) {
+        const unsigned v = hist[i];
+        if (v) {
+            atomicAdd(&counts[i], (unsigned long long)v);
+            hist[i] = 0;
+        }
+    }
+}
+
+// A work unit (pm_read.hpp) is one atom.  Workgroup (bx, g): origin frames [1024 bx, 1024 bx + 1024), atoms g, g + G, ...
+// (G = gridDim.y).  The atom's columns at the thread's kPmFrames origin frames stay in registers across the chunk's lags;
+// per lag the row t + tau of the same pairs is read: a float64 row is one 16-byte load at any t; two float32 rows share
+// a 16-byte load when tau is even (origin frames 2 m, 2 m + 1 -> rows 2 m + tau, 2 m + tau + 1), an odd tau takes 8-byte
+// loads.  A pair with t + tau >= T reads row 0 and contributes nothing: nothing is read at or past row T, but the second
+// half of a float32 load at row T - 1 of an odd T, which lies inside the pitch.
+// lags, counts, partial: the chunk's (lags + l0, counts + l0 (B + 1), partial + 2 l0; a workgroup's partials are 2 L apart).
+template <class E, int D>
+__global__ void __launch_bounds__(kPmThreads)
+    k_vanhove(const E* __restrict__ x, long pitch, long T, int n_atoms, const long* __restrict__ lags, int Lc,
+              const double* __restrict__ e_g, int B, float inv_dr, unsigned long long* __restrict__ counts,
+              double* __restrict__ partial, int L, int flush_atoms) {
+    constexpr bool kF32 = std::is_same_v<E, float>;
+    constexpr int F = kPmFrames;
+    extern __shared__ __attribute__((aligned(16))) unsigned char vh_lds[];
+    const int nb = B + 1;
+    double* e = reinterpret_cast<double*>(vh_lds);
+    double* mom = e + nb;
+    unsigned* hist = reinterpret_cast<unsigned*>(mom + 2 * kVhWaves * Lc);
+    for (int i = threadIdx.x; i < nb; i += kPmThreads) e[i] = e_g[i];
+    for (int i = threadIdx.x; i < 2 * kVhWaves * Lc; i += kPmThreads) mom[i] = 0.0;
+    for (int i = threadIdx.x; i < Lc * nb; i += kPmThreads) hist[i] = 0;
+    __syncthreads();
+
+    const long tb = (long)blockIdx.x * (kPmThreads * F);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int since = 0;
+    for (int n = blockIdx.y; n < n_atoms; n += gridDim.y) {
+        const PmAtom<E, D> a(x, pitch, (unsigned)n);  // (atom D < 2^31: launch_vanhove)
+        double col[F][3];
+        pm_load(a, T, tb, col);
+        for (int l = 0; l < Lc; ++l) {
+            const long tau = lags[l];
+            unsigned* h = hist + l * nb;
+            double s2 = 0.0, s4 = 0.0;
+            auto tally = [&](bool live, const double(&x0)[3], const double(&x1)[3]) {
+                const double r2 = vh_r2<D>(x0, x1);
+                if (live) {
+                    s2 += r2;
+                    s4 = fma(r2, r2, s4);
+                    atomicAdd(&h[vh_bin(r2, e, B, inv_dr)], 1u);
+                }
+            };
+            if constexpr (!kF32) {
+#pragma unroll
+                for (int f = 0; f < F; ++f) {
+                    const long t2 = pm_frame<false>(tb, f) + tau;
+                    double lo[3], hi[3];
+                    a.load(t2 < T ? t2 : 0, lo, hi);
+                    tally(t2 < T, col[f], lo);
+                }
+            } else if ((tau & 1) == 0) {
+#pragma unroll
+                for (int f = 0; f < F; f += 2) {
+                    const long t2 = pm_frame<true>(tb, f) + tau;  // (even)
+                    double lo[3], hi[3];
+                    a.load(t2 < T ? t2 / 2 : 0, lo, hi);
+                    tally(t2 < T, col[f], lo);
+                    tally(t2 + 1 < T, col[f + 1], hi);
+                }
+            } else {
+#pragma unroll
+                for (int f = 0; f < F; ++f) {
+                    const long t2 = pm_frame<true>(tb, f) + tau;
+                    double lo[3];
+                    vh_row32<D>(a, t2 < T ? t2 : 0, lo);
+                    tally(t2 < T, col[f], lo);
+                }
+            }
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {  // the same pattern whatever the values: every lane ends with the wave's sum
+                s2 += __shfl_xor(s2, m);
+                s4 += __shfl_xor(s4, m);
+            }
+            if (lane == 0) {
+                double* slot = mom + 2 * (wave * Lc + l);
+                slot[0] += s2;
+                slot[1] += s4;
+            }
+        }
+        if (++since == flush_atoms) {
+            __syncthreads();
+            vh_flush(hist, Lc * nb, counts);
+            __syncthreads();
+            since = 0;
+        }
+    }
+    __syncthreads();
+    vh_flush(hist, Lc * nb, counts);
+    double* out = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (size_t)(2 * L);
+    for (int i = threadIdx.x; i < 2 * Lc; i += kPmThreads) {
+        double s = mom[i];
+#pragma unroll
+        for (int w = 1; w < kVhWaves; ++w) s += mom[2 * w * Lc + i];
+        out[i] = s;
+    }
+}
+
+template <class E, int D>
+hipError_t vh_launch(dim3 grid, size_t lds, hipStream_t st, const void* x, long pitch, long T, int A, const long* lags, int Lc,
+                          const double* e, int B, float inv_dr, unsigned long long* counts, double* partial, int L) {
+    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_vanhove<E, D>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL((k_vanhove<E, D>), grid, dim3(kPmThreads), lds, st, (const E*)x, pitch, T, A, lags, Lc, e, B, inv_dr,
+                       counts, partial, L, kVhFlushAtoms);
+    return hipGetLastError();
+}
+template <class E, class... Args>
+hipError_t vh_launch_dim(int D, Args... args) {
+    if (D == 1) return vh_launch<E, 1>(args...);
+    if (D == 2) return vh_launch<E, 2>(args...);
+    return vh_launch<E, 3>(args...);
+}
+
+}  // namespace
+
+int vanhove_max_chunk(int B) {
+    return (int)std::max<size_t>(1, (kVhLdsBudget - sizeof(double) * (size_t)(B + 1)) /
+                                        (sizeof(double) * 2 * kVhWaves + sizeof(unsigned) * (size_t)(B + 1)));
+}
+
+int vanhove_parts(int n_cu, long pitch, long n_atoms) {
+    const dim3 grid = pm_unit_grid(n_cu, pitch, n_atoms);
+    return (int)(grid.x * grid.y);
+}
+
+hipError_t launch_vanhove(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const int64_t* lags, int l0,
+                          int Lc, int L, const double* e, int B, float inv_dr, unsigned long long* counts, double* partial,
+                          hipStream_t st) {
+    if (D < 1 || D > 3 || n_atoms < 1 || n_atoms * D >= (1L << 31) || (pitch & 7) || T < 1 || T > pitch || B < 1 || Lc < 1 ||
+        l0 < 0 || l0 + Lc > L || Lc > vanhove_max_chunk(B))
+        return hipErrorInvalidValue;
+    const dim3 grid = pm_unit_grid(n_cu, pitch, n_atoms);
+    const size_t lds = vh_lds_bytes(B, Lc);
+    static_assert(sizeof(long) == sizeof(int64_t), "lags are read as long");
+    const long* lg = reinterpret_cast<const long*>(lags) + l0;
+    unsigned long long* cnt = counts + (size_t)l0 * (size_t)(B + 1);
+    double* part = partial + 2 * (size_t)l0;
+    if (f32) return vh_launch_dim<float>(D, grid, lds, st, x, pitch, T, (int)n_atoms, lg, Lc, e, B, inv_dr, cnt, part, L);
+    return vh_launch_dim<double>(D, grid, lds, st, x, pitch, T, (int)n_atoms, lg, Lc, e, B, inv_dr, cnt, part, L);
+}
+
+}  // namespace ta
