@@ -358,6 +358,52 @@ int ta_scatter_collective(ta_ctx *ctx, int fft, const double *h_density, int n_k
 #define TA_VANHOVE_MAX_BINS 4096
 int ta_vanhove(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *h_counts, double *h_moments);
 
+/* ta_vanhove_distinct : the distinct part of the van Hove function of the positions in slab 0 (VanHoveDistinct): the
+ *              histogram of the distances between item a_p at an origin frame and item b_q a lag later, over ORDERED pairs
+ *              of different items.  With T frames, D staged columns:
+ *                a[0 ... Na), b[0 ... Nb): index lists into the staged items, each strictly increasing and in range (HOST
+ *                         arrays).  h_idx_a NULL: all items (n_a is ignored); h_idx_b NULL: b = a (n_b is ignored).
+ *                lags   : ta_vanhove's rules (strictly increasing, 0 <= tau < T, at most TA_VANHOVE_MAX_LAGS)
+ *                origins: t = origin_stride o, o = 0, 1, ...; lag l uses those with t + tau_l < T:
+ *                         n_orig[l] = ceil((T - tau_l) / origin_stride)
+ *                d_j    = x[t + tau, b_q, j] - x[t, a_p, j]          float64 (a float32 slab: widened first, then subtracted)
+ *                         periodic axis:  sc = d_j M_j;  k = rint(sc);  d_j = fma(-k, H_j, d_j)
+ *                         (H_j, M_j: the diagonal entries of the box table of ta_unwrap for that column's axis: the box
+ *                         length and its reciprocal; the box of the ORIGIN frame)
+ *                r2     = d_0 d_0, then fma(d_1, d_1, r2), then fma(d_2, d_2, r2)                     (ta_vanhove's order)
+ *                bin    = ta_vanhove's, against its squared edges e[b] = fl(fl(b dr) fl(b dr)); r2 >= e[n_bins]: bin n_bins
+ *                h_counts[l * (n_bins + 1) + bin] += 1 for every ordered pair (p, q) with a_p != b_q and every origin of lag l
+ *              int64.  Exact for every call:  sum_bin h_counts[l, :] = n_orig[l] (Na Nb - |a n b|).  NOTHING is divided by a
+ *              pair count, a volume or a shell measure (VanHoveDistinct does that); g(r) is the lag-0 row, normalised.
+ *              Box: h_dimensions (n_frames, 6) and axes (dim entries) as for ta_unwrap; h_dimensions NULL: no periodicity
+ *              (axes is ignored).  A non-orthogonal box in any frame: TA_E_INVALID (the one-step image is not the minimum
+ *              image there).  Per-frame boxes are accepted only when every lag is 0 (the image uses the origin frame's box);
+ *              with a lag > 0 the box must be constant.  fl(n_bins dr) must be <= half of every analysed box length in every
+ *              origin frame.  For an orthorhombic box the one-step image is the minimum image whichever periodic images
+ *              the positions are (an unwrapped trajectory included): nothing needs unwrapping or wrapping first.
+ *              Two passes.  k_vhd_gather (O(N) per chunk of lags) reads the slab in the element type it has -- a float32
+ *              device slab as float32, never a row at or past T -- and writes frame-major float64 scratch with the item
+ *              index contiguous; k_vhd_pairs (the hot pass, O(Na Nb) per origin and lag) takes one (lag, origin, 256 a-items,
+ *              1024 b-items) per workgroup, a lane owning 4 b-items in registers, counts into a uint32 LDS histogram (the
+ *              overflow bin in a register) and adds the non-zero bins to the uint64 histogram by integer atomics.  Only
+ *              integer adds: the same bits from run to run.  Lags go in chunks whose scratch fits 4 GiB (at least 1 lag);
+ *              option "vanhove_distinct_chunk" n >= 1 forces min(n, n_lags).  The results do not depend on the chunk bit
+ *              for bit.  ta_trim releases the scratch and the histogram.
+ *              The CPU backend follows the same arithmetic (vanhove_distinct_math.hpp): its counts EQUAL the GPU's for any
+ *              input, and do not depend on the number of threads.
+ *              NULL h_lags, n_lags / n_bins / dr outside ta_vanhove's limits, a bad lag, origin_stride < 1, NULL h_counts,
+ *              a list entry out of range or not increasing, n_a or n_b < 1 with a list, h_dimensions without axes, a box
+ *              this call cannot use (all checked before anything is written): TA_E_INVALID; nothing staged: TA_E_STATE;
+ *              n_atoms * dim must be below 2^31, and ceil(Na / 256) ceil(Nb / 1024) below 2^24 (about 2 million items on
+ *              both sides; TA_E_INVALID, on both backends).  Of the box only the analysed axes' lengths are looked at: a
+ *              zero or changing length on another axis is neither an error nor a per-frame box.  There is no ta_group_*
+ *              form: pair sums would cross the members' atom shards.  Timings: k_vhd_pairs is the main kernel;
+ *              ta_last_timing's main-kernel time is that of its LAST launch (one launch per chunk of lags and per 65535
+ *              origins), ta_kernel_timeline lists every launch.                                                         */
+int ta_vanhove_distinct(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int64_t origin_stride, int64_t n_a,
+                        const int64_t *h_idx_a, int64_t n_b, const int64_t *h_idx_b, const double *h_dimensions,
+                        const int *axes, int n_bins, double dr, int64_t *h_counts);
+
 /* ---- periodic unwrapping of a staged position slab ---------------------------------------------------------------
  * ta_unwrap: undo periodic wrapping of staging slab `slab` in place (MDAnalysis' NoJump), over the staged frames
  * in order.  h_dimensions: (n_frames, 6) float64 rows [a, b, c, alpha, beta, gamma] (A, degrees; ts.dimensions).
@@ -492,6 +538,12 @@ int ta_scatter_staged(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, doub
 /* h_lags: HOST lags, as for ta_vanhove_dev; slab 0 (the positions) is read in the element type it has */
 int ta_vanhove_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *d_counts,
                       double *d_moments, void *stream);
+
+/* every list and the box: HOST arrays, as for ta_vanhove_distinct (they size the launches; checked before anything is
+ * written); d_counts (n_lags, n_bins + 1) int64: a device array; slab 0 is read in the element type it has */
+int ta_vanhove_distinct_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int64_t origin_stride, int64_t n_a,
+                               const int64_t *h_idx_a, int64_t n_b, const int64_t *h_idx_b, const double *h_dimensions,
+                               const int *axes, int n_bins, double dr, int64_t *d_counts, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns
@@ -678,6 +730,8 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      min(n, n_k)); the results do not depend on it;
  *   "vanhove_chunk" n : lags per pass of ta_vanhove* (0, the default: as many as fit 64 KiB of LDS; n >= 1: min(n, n_lags,
  *                      that count)); the results do not depend on it;
+ *   "vanhove_distinct_chunk" n : lags per pass of ta_vanhove_distinct* (0, the default: as many as fit 4 GiB of gathered
+ *                      scratch, at least 1; n >= 1: min(n, n_lags)); the results do not depend on it;
  *   "async_commit" 1|0 : ta_stage_commit hands its frame range to a worker thread of the context, which
  *                      makes the HIP calls (the caller's frame loop never waits on the runtime, e.g. while
  *                      another thread page-locks a result array); every call that touches the slabs joins

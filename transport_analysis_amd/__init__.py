@@ -1,8 +1,8 @@
 """transport_analysis_amd — MI355X-native time-correlation kernels behind the
 transport-analysis API (VelocityAutocorr, ViscosityHelfand), MDAnalysis' EinsteinMSD, ConductivityHelfand and its species-resolved form, OnsagerHelfand, and their Green-Kubo
 (velocity) twins, ConductivityGreenKubo and OnsagerGreenKubo, and the intermediate scattering functions F_s(k, t) and F(k, t),
-IntermediateScattering, and their real-space partner, the self van Hove function G_s(r, t) with the non-Gaussian parameter,
-VanHoveSelf."""
+IntermediateScattering, and their real-space partners, the self van Hove function G_s(r, t) with the non-Gaussian parameter,
+VanHoveSelf, and the distinct van Hove function G_d(r, t) with the radial distribution function g(r), VanHoveDistinct."""
 __version__ = "0.1.0"
 
 from .velocityautocorr import VelocityAutocorr  # noqa: F401
@@ -13,3 +13,4 @@ from .onsager import OnsagerHelfand  # noqa: F401
 from .greenkubo import ConductivityGreenKubo, OnsagerGreenKubo  # noqa: F401
 from .scattering import IntermediateScattering, kvectors_from_box  # noqa: F401
 from .vanhove import VanHoveSelf, log_lags  # noqa: F401
+from .vanhove_distinct import VanHoveDistinct  # noqa: F401

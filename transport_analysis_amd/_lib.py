@@ -69,6 +69,9 @@ _API = {
     "ta_scatter_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_vanhove": _VANHOVE, "ta_vanhove_staged": _int(_vp, _ci, _vp, _ci, _dbl, _vp, _vp, _vp),
     "ta_vanhove_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _ci, _dbl, _vp, _vp, _vp),
+    # (handle, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr, counts[, stream])
+    "ta_vanhove_distinct": _int(_vp, _ci, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _dbl, _vp),
+    "ta_vanhove_distinct_staged": _int(_vp, _ci, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _dbl, _vp, _vp),
     "ta_compound": _int(_vp, _i64, _vp, _vp, _vp, _vp, _P(_vp)),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
     "ta_helfand_msd_dev": _int(_vp, _vp, _vp, _vp, _i64, _i64, _ci, _i64, _dbl, _vp, _vp, _i64, _vp),
@@ -736,6 +739,49 @@ class Context(_Staged):
         """`lags`: HOST frame lags (checked by the library before anything is written); d_counts (n_lags, n_bins + 1) int64"""
         lg, L = self._lags(lags)
         self._call("vanhove_staged", L, _ptr(lg), int(n_bins), float(dr), d_counts or None, d_moments or None, stream or None)
+
+    def _vhd_args(self, lags, origin_stride, idx_a, idx_b, dimensions, axes, n_bins, dr):
+        """the argument tuple ta_vanhove_distinct* share, and the arrays it points into (to be kept until the call is over)"""
+        lg, L = self._lags(lags)
+
+        def index_list(idx, name):
+            if idx is None:
+                return None, 0
+            a = np.ascontiguousarray(idx, dtype=np.int64)
+            if a.ndim != 1:
+                raise ValueError(f"{name}: shape {a.shape}, expected a 1-d list of item indices")
+            return a, int(a.shape[0])
+
+        (a, na), (b, nb) = index_list(idx_a, "idx_a"), index_list(idx_b, "idx_b")
+        dims = ax = None
+        if dimensions is not None:
+            dims = np.ascontiguousarray(dimensions, dtype=np.float64)
+            if self.shape is not None and dims.shape != (self.shape[0], 6):
+                raise ValueError(f"dimensions: shape {dims.shape}, expected ({self.shape[0]}, 6) (one box per staged frame)")
+            ax = np.ascontiguousarray(np.arange(self._staged_shape()[2]) if axes is None else axes, dtype=np.int32).ravel()
+        keep = (lg, a, b, dims, ax)
+        return (L, _ptr(lg), int(origin_stride), na, _ptr(a), nb, _ptr(b), _ptr(dims), _ptr(ax), int(n_bins), float(dr)), keep
+
+    def vanhove_distinct(self, lags, n_bins, dr, *, origin_stride=1, idx_a=None, idx_b=None, dimensions=None, axes=None):
+        """Distinct van Hove histogram of slab 0 (the positions), ta_vanhove_distinct: for the integer frame `lags` the
+        counts (n_lags, n_bins + 1) int64 of the distances between item a_p at an origin frame (every `origin_stride`-th)
+        and item b_q a lag later, over ordered pairs of different items, in `n_bins` bins of width `dr` plus the overflow
+        bin.  `idx_a`, `idx_b`: strictly increasing item indices (None: all items / the same as a).  `dimensions`: the
+        (n_frames, 6) boxes of the staged frames for the minimum image (None: no periodicity), `axes` the box axis of each
+        staged column (None: 0, 1, ...).  Nothing is normalised.  One context only: a device group has no such call."""
+        args, keep = self._vhd_args(lags, origin_stride, idx_a, idx_b, dimensions, axes, n_bins, dr)
+        cnt = np.empty((args[0], max(int(n_bins), 0) + 1), dtype=np.int64)
+        self._call("vanhove_distinct", *args, _ptr(cnt))
+        del keep
+        return cnt
+
+    def vanhove_distinct_staged(self, lags, n_bins, dr, d_counts, *, origin_stride=1, idx_a=None, idx_b=None, dimensions=None,
+                                axes=None, stream=0):
+        """the lists and boxes are HOST arrays (checked by the library before anything is written); d_counts (n_lags,
+        n_bins + 1) int64 on the device"""
+        args, keep = self._vhd_args(lags, origin_stride, idx_a, idx_b, dimensions, axes, n_bins, dr)
+        self._call("vanhove_distinct_staged", *args, d_counts or None, stream or None)
+        del keep
 
     # -- timing ----------------------------------------------------------
     def timing_history(self, max_n=64):

@@ -23,6 +23,7 @@
 #include "direct_kernels.hpp"
 #include "ta_internal.hpp"
 #include "unwrap_box.hpp"
+#include "vanhove_distinct_math.hpp"
 #include "vanhove_math.hpp"
 
 using namespace ta;
@@ -104,6 +105,7 @@ private:
     X(timeline, 0, nullptr)        /* record the kernel timeline of every compute call (ta_kernel_timeline) */             \
     X(scatter_chunk, 0, opt_check_scatter_chunk) /* wavevectors per pass of ta_scatter* (0: as many as fit kScatterBudget) */ \
     X(vanhove_chunk, 0, opt_check_vanhove_chunk) /* lags per pass of ta_vanhove* (0: as many as fit a workgroup's LDS) */ \
+    X(vanhove_distinct_chunk, 0, opt_check_vanhove_distinct_chunk) /* lags per pass of ta_vanhove_distinct* (0: as many as fit kVhdBudget) */ \
     X(async_commit, 1, opt_flush_commits) /* ta_stage_commit goes through the commit queue; flushed before it changes */   \
     X(lock_ahead, 1, nullptr)      /* the commit worker page-locks the chunks behind the one it committed */               \
     X(cpu_threads, 0, opt_set_cpu_threads) /* CPU backend: OpenMP team size (0: the runtime's default) */                  \
@@ -161,6 +163,12 @@ struct ta_ctx {
     DevBuf vh_tab{workspaces, kKept}, vh_hist{workspaces, kTrimmed}, vh_part{workspaces, kTrimmed}, vh_out{workspaces, kKept};
     std::vector<double> vh_tab_h;
     hipEvent_t ev_vh = nullptr;
+    // distinct van Hove function (vhd_pm): the table (lags, squared edges, box entries, padded index lists), the gathered
+    // frame-major scratch GA | GB and the uint64 histogram (trimmed), the output of host-facing calls.  vhd_tab_h is what
+    // the upload of the table reads: it stays until ev_vhd says the copy is done
+    DevBuf vhd_tab{workspaces, kKept}, vhd_scr{workspaces, kTrimmed}, vhd_hist{workspaces, kTrimmed}, vhd_out{workspaces, kKept};
+    std::vector<double> vhd_tab_h;
+    hipEvent_t ev_vhd = nullptr;
     // ta_compound: the plan (offsets, members, member weights, their sums per compound) and the (n_frames, dim) weighted
     // mean F of the barycentric term; the per-atom frame weights and F's partial sums use the Onsager workspaces
     DevBuf comp_plan{workspaces, kTrimmed}, comp_f{workspaces, kTrimmed};
@@ -1251,6 +1259,204 @@ int vanhove_pm(ta_ctx* ctx, const Slab& slab, int L, int B, double dr, int64_t* 
     return call_end(ctx, st);
 }
 
+// ---- distinct van Hove function (vanhove_distinct.hip) --------------------------------------------------------------
+constexpr size_t kVhdBudget = (size_t)4 << 30;  // the gathered scratch of one pass (a choice, not a measurement)
+
+// What ta_vanhove_distinct* can check without the staged shape.  T: the frames the lags are checked against (0: nothing
+// staged -- the caller reports that next)
+int vhd_args(ta_ctx* ctx, int L, const int64_t* h_lags, int64_t stride, int64_t n_a, const int64_t* h_idx_a, int64_t n_b,
+             const int64_t* h_idx_b, const double* h_dims, const int* axes, int B, double dr, int64_t T, const void* out) {
+    if (!h_lags) return fail(ctx, TA_E_INVALID, "vanhove_distinct: lags are NULL");
+    if (L < 1 || L > TA_VANHOVE_MAX_LAGS)
+        return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_lags must be 1 ... " + std::to_string(TA_VANHOVE_MAX_LAGS));
+    if (B < 1 || B > TA_VANHOVE_MAX_BINS)
+        return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_bins must be 1 ... " + std::to_string(TA_VANHOVE_MAX_BINS));
+    if (!(dr - dr == 0.0) || !(dr > 0.0)) return fail(ctx, TA_E_INVALID, "vanhove_distinct: dr must be finite and > 0");
+    if (stride < 1) return fail(ctx, TA_E_INVALID, "vanhove_distinct: origin_stride must be >= 1");
+    if (!out) return fail(ctx, TA_E_INVALID, "vanhove_distinct: the counts output is NULL");
+    if (h_idx_a && n_a < 1) return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_a must be >= 1");
+    if (h_idx_b && n_b < 1) return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_b must be >= 1");
+    if (h_dims && !axes) return fail(ctx, TA_E_INVALID, "vanhove_distinct: dimensions without axes");
+    for (int l = 0; l < L; ++l) {
+        if (h_lags[l] < 0 || (T > 0 && h_lags[l] >= T))
+            return fail(ctx, TA_E_INVALID, "vanhove_distinct: lag " + std::to_string(h_lags[l]) + " is outside 0 ... n_frames - 1");
+        if (l && h_lags[l] <= h_lags[l - 1]) return fail(ctx, TA_E_INVALID, "vanhove_distinct: the lags must be strictly increasing");
+    }
+    return TA_OK;
+}
+
+// The host side of one call (both kinds of context): the index lists padded to the pair kernel's tiles (-1: padding), the
+// box entries H[3], M[3] of the staged columns per box, the origins of lag 0
+struct VhdPlan {
+    int L = 0, B = 0, D = 0;
+    int64_t T = 0, stride = 1, n_a = 0, n_b = 0, n_orig = 0, pitch_a = 0, pitch_b = 0, n_box = 0;  // n_box 0: no box
+    bool per_frame = false;
+    std::vector<int32_t> ida, idb;
+    std::vector<double> hm;
+};
+
+static int vhd_index_list(ta_ctx* ctx, const char* name, int64_t n, const int64_t* idx, int64_t A, int64_t tile, std::vector<int32_t>* out,
+                          int64_t* pitch) {
+    for (int64_t i = 0; idx && i < n; ++i) {
+        if (idx[i] < 0 || idx[i] >= A)
+            return fail(ctx, TA_E_INVALID, std::string("vanhove_distinct: index list ") + name + ": entry " + std::to_string(idx[i]) +
+                                               " is outside 0 ... n_atoms - 1");
+        if (i && idx[i] <= idx[i - 1])
+            return fail(ctx, TA_E_INVALID, std::string("vanhove_distinct: index list ") + name + " must be strictly increasing");
+    }
+    *pitch = (n + tile - 1) / tile * tile;
+    out->assign((size_t)*pitch, -1);
+    for (int64_t i = 0; i < n; ++i) (*out)[(size_t)i] = (int32_t)(idx ? idx[i] : i);
+    return TA_OK;
+}
+
+// Everything that needs the staged shape (T, A, D), checked before anything is written
+int vhd_plan(ta_ctx* ctx, int L, const int64_t* h_lags, int64_t stride, int64_t n_a, const int64_t* h_idx_a, int64_t n_b,
+             const int64_t* h_idx_b, const double* h_dims, const int* axes, int B, double dr, int64_t T, int64_t A, int D, VhdPlan* p) {
+    if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_atoms * dim must be below 2^31");
+    p->L = L, p->B = B, p->D = D, p->T = T, p->stride = stride;
+    p->n_a = h_idx_a ? n_a : A;
+    TA_CHECK(vhd_index_list(ctx, "a", p->n_a, h_idx_a, A, VHD_TILE_A, &p->ida, &p->pitch_a));
+    if (!h_idx_b) {  // b = a
+        h_idx_b = h_idx_a;
+        n_b = p->n_a;
+    }
+    p->n_b = n_b;
+    TA_CHECK(vhd_index_list(ctx, "b", p->n_b, h_idx_b, A, VHD_TILE_B, &p->idb, &p->pitch_b));
+    // (a launch's grid is a-tiles x b-tiles in x: 256 threads each, below 2^32 threads)
+    if ((p->pitch_a / VHD_TILE_A) * (p->pitch_b / VHD_TILE_B) >= VHD_MAX_TILES)
+        return fail(ctx, TA_E_INVALID, "vanhove_distinct: ceil(n_a / " + std::to_string(VHD_TILE_A) + ") * ceil(n_b / " +
+                                           std::to_string(VHD_TILE_B) + ") must be below 2^24 (about 2 million items on both sides)");
+    p->n_orig = vhd_origins(T, 0, stride);
+    p->n_box = 0, p->per_frame = false;
+    if (!h_dims) return TA_OK;
+    // only the analysed axes' lengths count: the others are set to 1 before the table is made, so a zero length there
+    // (a slab geometry) is no error and a length that changes there makes no per-frame box
+    for (int d = 0; d < D; ++d)
+        if (axes[d] < 0 || axes[d] > 2) return fail(ctx, TA_E_INVALID, "vanhove_distinct: axes: every entry must be 0, 1 or 2");
+    std::vector<double> dims(h_dims, h_dims + 6 * (size_t)T);
+    for (int k = 0; k < 3; ++k)
+        if (std::find(axes, axes + D, k) == axes + D)
+            for (int64_t t = 0; t < T; ++t) dims[6 * (size_t)t + k] = 1.0;
+    BoxTable box;
+    const std::string why = box_table(dims.data(), T, D, axes, 1, &box);
+    if (!why.empty()) return fail(ctx, TA_E_INVALID, "vanhove_distinct: " + why);
+    if (box.triclinic)
+        return fail(ctx, TA_E_INVALID, "vanhove_distinct: a non-orthogonal box is not supported (the one-step image is not the "
+                                       "minimum image there)");
+    if (box.per_frame && h_lags[L - 1] > 0)
+        return fail(ctx, TA_E_INVALID, "vanhove_distinct: per-frame boxes are accepted only when every lag is 0");
+    p->per_frame = box.per_frame;
+    p->n_box = box.per_frame ? T : 1;
+    p->hm.assign((size_t)p->n_box * 6, 1.0);
+    const double r_max = (double)B * dr;
+    for (int64_t t = 0; t < p->n_box; ++t)
+        for (int d = 0; d < D; ++d) {
+            const double h = box.tab[(size_t)diag_row(axes[d]) * box.tpitch + t];
+            p->hm[(size_t)t * 6 + d] = h;
+            p->hm[(size_t)t * 6 + 3 + d] = box.tab[(size_t)(6 + diag_row(axes[d])) * box.tpitch + t];
+            if (t % stride == 0 && !(r_max <= 0.5 * h))
+                return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_bins * dr = " + std::to_string(r_max) + " exceeds half the box length " +
+                                                   std::to_string(h) + " of frame " + std::to_string(t));
+        }
+    return TA_OK;
+}
+
+// The table of a call queued for upload on `st`, before the call is opened: lags (int64) | e[0 ... B] | hm | ida | idb
+struct VhdTab {
+    const int64_t* lags;
+    const double *e, *hm;
+    const int *ida, *idb;
+};
+int vhd_upload(ta_ctx* ctx, const VhdPlan& p, const int64_t* h_lags, double dr, hipStream_t st) {
+    const size_t n = (size_t)p.L + (size_t)p.B + 1 + p.hm.size() + (size_t)(p.pitch_a + p.pitch_b) / 2;  // (both pitches are even)
+    TA_CHECK(ensure(ctx, ctx->vhd_tab, sizeof(double) * n));
+    if (!ctx->ev_vhd) TA_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_vhd, hipEventDisableTiming));
+    else TA_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_vhd));  // the last call's upload has left vhd_tab_h
+    ctx->vhd_tab_h.resize(n);
+    double* h = ctx->vhd_tab_h.data();
+    static_assert(sizeof(int64_t) == sizeof(double) && 2 * sizeof(int32_t) == sizeof(double), "the table's slots");
+    memcpy(h, h_lags, sizeof(int64_t) * (size_t)p.L);
+    vh_edges(p.B, dr, h + p.L);
+    double* q = h + p.L + p.B + 1;
+    if (!p.hm.empty()) memcpy(q, p.hm.data(), sizeof(double) * p.hm.size());
+    q += p.hm.size();
+    memcpy(q, p.ida.data(), sizeof(int32_t) * p.ida.size());
+    memcpy(q + p.pitch_a / 2, p.idb.data(), sizeof(int32_t) * p.idb.size());
+    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->vhd_tab.p, h, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev_vhd, st));
+    return TA_OK;
+}
+VhdTab vhd_tab(ta_ctx* ctx, const VhdPlan& p) {
+    const double* d = (const double*)ctx->vhd_tab.p;
+    const double* q = d + p.L + p.B + 1;
+    const int* ids = (const int*)(q + p.hm.size());
+    return {(const int64_t*)d, d + p.L, p.hm.empty() ? nullptr : q, ids, ids + p.pitch_a};
+}
+
+// One call on a pair-major position slab of either element type (the caller has opened the call's bracket, it is closed
+// here; vhd_upload has queued the table).  The uint64 histogram is zeroed; then per chunk of Lc lags one k_vhd_gather
+// launch (GA with the first chunk) and one k_vhd_pairs launch per 65535 origins.  Nothing depends on Lc but which lags
+// share a launch, and every add is an integer add: the same bits for every chunk size.  ev[1] / ev[2] bracket the LAST
+// k_vhd_pairs launch only (as vanhove_pm's): with several chunks or more than 65535 origins ta_last_timing's main-kernel
+// time is that launch's; the kernel timeline has them all.
+int vhd_pm(ta_ctx* ctx, const Slab& slab, const VhdPlan& p, double dr, int64_t* d_counts) {
+    hipStream_t st = slab.st;
+    const int L = p.L, B = p.B, D = p.D;
+    const double per_a = 8.0 * (double)p.n_orig * D * (double)p.pitch_a, per_lag = 8.0 * (double)p.n_orig * D * (double)p.pitch_b;
+    if (per_a + per_lag > 4e18) return fail(ctx, TA_E_INVALID, "vanhove_distinct: the gathered scratch of one lag does not fit");
+    const size_t bytes_a = (size_t)p.n_orig * D * (size_t)p.pitch_a * 8, bytes_lag = (size_t)p.n_orig * D * (size_t)p.pitch_b * 8;
+    const int64_t fit = kVhdBudget > bytes_a + bytes_lag ? (int64_t)((kVhdBudget - bytes_a) / bytes_lag) : 1;
+    const int Lc = (int)std::min<int64_t>(L, ctx->opt_vanhove_distinct_chunk > 0 ? ctx->opt_vanhove_distinct_chunk : fit);
+    const size_t hist_bytes = sizeof(int64_t) * (size_t)L * (size_t)(B + 1);
+    TA_CHECK(ensure(ctx, ctx->vhd_scr, bytes_a + (size_t)Lc * bytes_lag));
+    TA_CHECK(ensure(ctx, ctx->vhd_hist, hist_bytes));
+    const VhdTab tab = vhd_tab(ctx, p);
+    double* ga = (double*)ctx->vhd_scr.p;
+    double* gb = ga + bytes_a / 8;
+    TA_HIP_TRY(ctx, hipMemsetAsync(ctx->vhd_hist.p, 0, hist_bytes, st));
+    for (int l0 = 0; l0 < L; l0 += Lc) {
+        const int lc = std::min(Lc, L - l0);
+        TA_LAUNCH(ctx, "k_vhd_gather", st,
+                  launch_vhd_gather(slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, D, (long)p.stride, (long)p.n_orig,
+                                    tab.lags + l0, lc, l0 == 0, tab.ida, tab.idb, (long)p.pitch_a, (long)p.pitch_b, ga, gb, st));
+        for (int64_t o0 = 0; o0 < p.n_orig; o0 += 65535)
+            TA_LAUNCH_MAIN(ctx, "k_vhd_pairs", st,
+                           launch_vhd_pairs(ga, gb, tab.ida, tab.idb, (long)p.pitch_a, (long)p.pitch_b, (long)p.n_a, (long)p.n_b, D,
+                                            (long)slab.T, (long)p.stride, (long)p.n_orig, (long)o0,
+                                            (int)std::min<int64_t>(65535, p.n_orig - o0), tab.lags + l0, lc, tab.hm, p.per_frame, tab.e, B,
+                                            vh_inv_dr(dr), (unsigned long long*)ctx->vhd_hist.p + (size_t)l0 * (size_t)(B + 1), st));
+    }
+    TA_HIP_TRY(ctx, hipMemcpyAsync(d_counts, ctx->vhd_hist.p, hist_bytes, hipMemcpyDeviceToDevice, st));
+    return call_end(ctx, st);
+}
+
+// ta_vanhove_distinct_staged and the device half of ta_vanhove_distinct: d_counts NULL = the context's own output buffer
+// (*d_out tells where the counts are)
+int vhd_entry(ta_ctx* ctx, int L, const int64_t* h_lags, int64_t stride, int64_t n_a, const int64_t* h_idx_a, int64_t n_b,
+              const int64_t* h_idx_b, const double* h_dims, const int* axes, int B, double dr, int64_t* d_counts, bool own_output,
+              void* stream, int64_t** d_out) {
+    VhdPlan plan;
+    int64_t* out = d_counts;
+    return slab_entry(
+        ctx, nullptr, stream,
+        [&] {
+            return vhd_args(ctx, L, h_lags, stride, n_a, h_idx_a, n_b, h_idx_b, h_dims, axes, B, dr, ctx->st_nslabs ? ctx->st_T : 0,
+                            own_output ? (const void*)ctx : (const void*)d_counts);
+        },
+        [&](const Slab& s) -> int {
+            TA_CHECK(vhd_plan(ctx, L, h_lags, stride, n_a, h_idx_a, n_b, h_idx_b, h_dims, axes, B, dr, s.T, s.A, s.D, &plan));
+            TA_CHECK(vhd_upload(ctx, plan, h_lags, dr, s.st));
+            if (own_output) {
+                TA_CHECK(ensure(ctx, ctx->vhd_out, sizeof(int64_t) * (size_t)L * (size_t)(B + 1)));
+                out = (int64_t*)ctx->vhd_out.p;
+            }
+            if (d_out) *d_out = out;
+            return TA_OK;
+        },
+        [&](const Slab& s) { return vhd_pm(ctx, s, plan, dr, out); });
+}
+
 // ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
 // This is the seam: a CPU context's staging and host-facing calls end up in the cpu_* functions below, reached by one
 // early branch of their entry point (after the checks both kinds of context share); nothing below makes a HIP call.
@@ -1329,6 +1535,9 @@ int opt_set_cpu_threads(ta_ctx* ctx, int64_t value) {
 int opt_flush_commits(ta_ctx* ctx, int64_t) { return ctx->commits.flush(); }
 int opt_check_scatter_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "scatter_chunk: 0 (automatic) or the wavevectors per pass");
+}
+int opt_check_vanhove_distinct_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "vanhove_distinct_chunk: 0 (automatic) or the lags per pass");
 }
 int opt_check_vanhove_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "vanhove_chunk: 0 (automatic) or the lags per pass");
@@ -1456,7 +1665,7 @@ int ta_ctx_destroy(ta_ctx* ctx) {
         for (auto& ev : q)
             if (ev) hipEventDestroy(ev);
     if (ctx->ev_stage) hipEventDestroy(ctx->ev_stage);
-    for (hipEvent_t e : {ctx->ev_order, ctx->ev_kvec, ctx->ev_vh})
+    for (hipEvent_t e : {ctx->ev_order, ctx->ev_kvec, ctx->ev_vh, ctx->ev_vhd})
         if (e) {
             hipEventSynchronize(e);  // (the upload may be on a caller's stream)
             hipEventDestroy(e);
@@ -2053,6 +2262,16 @@ int ta_vanhove_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins
     });
 }
 
+// Distinct van Hove function on the staged slab 0, read in its own element type; every list is a HOST array
+int ta_vanhove_distinct_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int64_t origin_stride, int64_t n_a,
+                               const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes,
+                               int n_bins, double dr, int64_t* d_counts, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    return vhd_entry(ctx, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr, d_counts, false,
+                     stream, nullptr);
+    });
+}
+
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guarded(fail, ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
@@ -2630,6 +2849,30 @@ int ta_vanhove(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, doubl
     const size_t n_counts = (size_t)n_lags * (size_t)(n_bins + 1);  // (int64 counts travel as 8-byte elements)
     return host_finish(ctx, {{(double*)h_counts, (const double*)d_out, n_counts},
                              {h_moments, (const double*)d_out + n_counts, 2 * (size_t)n_lags}});
+    });
+}
+
+int ta_vanhove_distinct(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int64_t origin_stride, int64_t n_a, const int64_t* h_idx_a,
+                        int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes, int n_bins, double dr,
+                        int64_t* h_counts) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    if (ctx->is_cpu) {
+        TA_CHECK(vhd_args(ctx, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr,
+                          ctx->st_nslabs ? ctx->st_T : 0, h_counts));
+        TA_CHECK(check_staged(ctx));
+        VhdPlan p;
+        TA_CHECK(vhd_plan(ctx, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr, ctx->st_T,
+                          ctx->st_A, ctx->st_D, &p));
+        if (int rc = ta::cpu::vanhove_distinct(cpu_state(ctx), n_lags, h_lags, origin_stride, p.n_a, p.ida.data(), p.n_b, p.idb.data(),
+                                               p.hm.empty() ? nullptr : p.hm.data(), p.per_frame, n_bins, dr, h_counts))
+            return fail(ctx, rc, "CPU backend: out of host memory");
+        return TA_OK;
+    }
+    int64_t* d_out = nullptr;
+    TA_CHECK(vhd_entry(ctx, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr,
+                       nullptr, h_counts != nullptr, ctx->stream, &d_out));
+    return host_finish(ctx, {{(double*)h_counts, (const double*)d_out, (size_t)n_lags * (size_t)(n_bins + 1)}});  // (8-byte elements)
     });
 }
 

@@ -40,6 +40,7 @@
 #include "../../include/ta_hip.h"
 #include "cpu_backend.hpp"
 #include "unwrap_box.hpp"
+#include "vanhove_distinct_math.hpp"
 #include "vanhove_math.hpp"
 
 namespace ta {
@@ -666,6 +667,74 @@ int vanhove_e(const State& s, int L, const int64_t* lags, int B, double dr, int6
 
 int vanhove(const State& s, int L, const int64_t* lags, int B, double dr, int64_t* counts, double* moments) {
     return s.dtype == TA_F32 ? vanhove_e<float>(s, L, lags, B, dr, counts, moments) : vanhove_e<double>(s, L, lags, B, dr, counts, moments);
+}
+
+// The distinct van Hove histogram: OpenMP threads take (origin, tile of kVhdCpuTile a-items) units, each thread with an int64
+// histogram of its own; the threads' histograms are added at the end.  Integer adds only: nothing depends on the number of
+// threads or on which thread took which unit.
+constexpr int64_t kVhdCpuTile = 64;
+
+template <class E, int D, bool PERIODIC>
+int vanhove_distinct_t(const State& s, int L, const int64_t* lags, int64_t stride, int64_t n_a, const int32_t* ida, int64_t n_b,
+                       const int32_t* idb, const double* hm, bool per_frame, int B, double dr, int64_t* counts) {
+    const int64_t T = s.T, A = s.A;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    const int nth = s.threads > 0 ? s.threads : 1;
+    const size_t nb = (size_t)B + 1, nh = (size_t)L * nb;
+    std::vector<double> e;
+    std::vector<int64_t> hist;
+    try {
+        e.assign(nb, 0.0);
+        hist.assign((size_t)nth * nh, 0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    vh_edges(B, dr, e.data());
+    const float inv = vh_inv_dr(dr);
+    const int64_t n_orig = vhd_origins(T, 0, stride), n_tiles = (n_a + kVhdCpuTile - 1) / kVhdCpuTile;
+#pragma omp parallel for num_threads(nth) schedule(dynamic)
+    for (int64_t w = 0; w < n_orig * n_tiles; ++w) {
+        const int64_t t = (w / n_tiles) * stride, p0 = (w % n_tiles) * kVhdCpuTile, p1 = std::min(n_a, p0 + kVhdCpuTile);
+        int64_t* h = hist.data() + (size_t)omp_get_thread_num() * nh;
+        double H[3] = {1.0, 1.0, 1.0}, M[3] = {1.0, 1.0, 1.0};
+        if (PERIODIC) {
+            const double* box = hm + (per_frame ? t * 6 : 0);
+            for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
+        }
+        for (int l = 0; l < L && t + lags[l] < T; ++l) {  // (the lags increase)
+            const int64_t t2 = t + lags[l];
+            for (int64_t p = p0; p < p1; ++p) {
+                double a[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
+                for (int d = 0; d < D; ++d) a[d] = (double)x[((size_t)t * A + ida[p]) * D + d];
+                for (int64_t q = 0; q < n_b; ++q) {
+                    if (idb[q] == ida[p]) continue;
+                    for (int d = 0; d < D; ++d) b[d] = (double)x[((size_t)t2 * A + idb[q]) * D + d];
+                    ++h[l * nb + vh_bin(vhd_r2<D, PERIODIC>(a, b, H, M), e.data(), B, inv)];
+                }
+            }
+        }
+    }
+    std::fill(counts, counts + nh, (int64_t)0);
+    for (int th = 0; th < nth; ++th)
+        for (size_t i = 0; i < nh; ++i) counts[i] += hist[(size_t)th * nh + i];
+    return TA_OK;
+}
+
+template <class E, bool PERIODIC, class... Args>
+int vanhove_distinct_d(const State& s, Args... args) {
+    if (s.D == 1) return vanhove_distinct_t<E, 1, PERIODIC>(s, args...);
+    if (s.D == 2) return vanhove_distinct_t<E, 2, PERIODIC>(s, args...);
+    return vanhove_distinct_t<E, 3, PERIODIC>(s, args...);
+}
+
+int vanhove_distinct(const State& s, int L, const int64_t* lags, int64_t stride, int64_t n_a, const int32_t* ida, int64_t n_b,
+                     const int32_t* idb, const double* hm, bool per_frame, int B, double dr, int64_t* counts) {
+    const bool f32 = s.dtype == TA_F32;
+    if (hm)
+        return f32 ? vanhove_distinct_d<float, true>(s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts)
+                   : vanhove_distinct_d<double, true>(s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts);
+    return f32 ? vanhove_distinct_d<float, false>(s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts)
+               : vanhove_distinct_d<double, false>(s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts);
 }
 
 template <class E>

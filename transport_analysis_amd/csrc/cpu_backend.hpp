@@ -55,6 +55,13 @@ int scatter_collective(int threads, bool fft, const double* density, int K, int6
 // vanhove.hip: counts (L, B + 1) int64 (OpenMP over atoms, a histogram per thread, added at the end), moments (L, 2) = (sum r2,
 // sum r2 r2) per atom, then in atom order; either may be NULL; arguments checked by the caller
 int vanhove(const State& s, int L, const int64_t* lags, int B, double dr, int64_t* counts, double* moments);
+// ta_vanhove_distinct: the distinct van Hove histogram of slab 0 with vanhove_distinct_math.hpp's arithmetic, as
+// vanhove_distinct.hip: counts (L, B + 1) int64 over the ordered pairs (ida[p], idb[q]), ida[p] != idb[q], of the origins
+// t = stride o and the lags with t + lag < n_frames (OpenMP over (origin, a-tile), a histogram per thread, added at the end).
+// hm: NULL (no box) or H[3], M[3] of the staged columns per box (one, or per_frame: one per frame); arguments checked by
+// the caller
+int vanhove_distinct(const State& s, int L, const int64_t* lags, int64_t stride, int64_t n_a, const int32_t* ida, int64_t n_b,
+                     const int32_t* idb, const double* hm, bool per_frame, int B, double dr, int64_t* counts);
 // ta_compound: out (n_frames, n_compounds, dim) float64 = sum_{i in [offsets[c], offsets[c + 1])} w_i x[t, members[i], d] -
 // g_c F[t, d] of slab 0 (g_c = sum_i w_i, F = sum_a u_a x[t, a, d]; frame_weights NULL: no such term; weights NULL: all 1),
 // the sum in member order (the first product, then fma), parallel over compounds; arguments checked by the caller

@@ -303,6 +303,25 @@ hipError_t launch_vanhove(int n_cu, const void* x, bool f32, long pitch, long T,
                           int Lc, int L, const double* e, int B, float inv_dr, unsigned long long* counts, double* partial,
                           hipStream_t st);
 
+// vanhove_distinct.hip: the distinct van Hove histogram in two passes.  The item pitches of the scratch and of the padded
+// index lists (ids; -1: padding) are multiples of the pair kernel's tiles.  n_orig = ceil(T / stride): the origins of lag 0,
+// which size the scratch of every lag.
+//   launch_vhd_gather: the frame-major float64 scratch of a chunk of Lc lags (device array `lags`: the chunk's) from a
+//   pair-major slab of float64 or (f32) float32 elements, read as it is: ga [n_orig][D][pitch_a] (with_a: written by this
+//   launch), gb [Lc][n_orig][D][pitch_b]; rows at or past T are neither read nor written.
+//   launch_vhd_pairs: origins [o0, o0 + n_o) (n_o <= 65535) of the chunk's lags: counts (Lc, B + 1) uint64 (zeroed by the
+//   caller before the first launch) gets the bins added.  hm: NULL (no box) or per box H[3], M[3] of the staged columns
+//   (one box, or one per frame: box_per_frame); e: the B + 1 squared edges (device), inv_dr: vanhove_math.hpp's factor.
+constexpr int VHD_TILE_A = 256, VHD_TILE_B = 1024;
+constexpr long VHD_MAX_TILES = 1L << 24;  // a-tiles x b-tiles of one launch: x 256 threads stays below 2^32
+hipError_t launch_vhd_gather(const void* x, bool f32, long pitch, long T, long n_atoms, int D, long stride, long n_orig,
+                             const int64_t* lags, int Lc, bool with_a, const int* ida, const int* idb, long pitch_a, long pitch_b,
+                             double* ga, double* gb, hipStream_t st);
+hipError_t launch_vhd_pairs(const double* ga, const double* gb, const int* ida, const int* idb, long pitch_a, long pitch_b, long n_a,
+                            long n_b, int D, long T, long stride, long n_orig, long o0, int n_o, const int64_t* lags, int Lc,
+                            const double* hm, bool box_per_frame, const double* e, int B, float inv_dr, unsigned long long* counts,
+                            hipStream_t st);
+
 // unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
 // box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)
 hipError_t launch_unwrap(double* slab, long pitch, long T, long n_atoms, int D, const int* axes, bool triclinic,

@@ -1,0 +1,220 @@
+// vanhove_distinct.hip — the distinct part of the van Hove function: for L lags tau_l the histogram of the distances between
+// item a_p at an origin frame t and item b_q at frame t + tau, a_p != b_q, under the one-step minimum image of an
+// orthorhombic box, against squared bin edges
+//
+//   counts[l, b] = #{(o, p, q): t = stride o, t + tau_l < T, a_p != b_q, e[b] <= r2 < e[b + 1]}   (b = B: r2 >= e[B])   uint64 (L, B + 1)
+//
+// with the arithmetic of vanhove_distinct_math.hpp (the CPU backend follows it: equal counts for any input).  The cost is
+// O(Na Nb) per origin and lag, and the pair-major slab is contiguous along TIME: a lane per frame would put a wave's 64
+// lanes on one LDS bin (a pair's distance hardly moves between neighbouring frames).  So there are two passes:
+//
+//   k_vhd_gather<E, D>   O(N) per chunk of lags: reads the slab through PmAtom in its own element type (a float32 slab as
+//                        float32, one 8-byte row per load: nothing at or past row T is read) and writes frame-major
+//                        float64 scratch with the ITEM index contiguous, GA[o][d][p] = x[stride o, a_p, d] and
+//                        GB[l][o][d][q] = x[stride o + tau_l, b_q, d], the item pitch padded to the pair kernel's tiles
+//                        (padding written as zeros; its ids are -1).  The element type, the index lists, the stride and
+//                        the lag's parity are settled here.
+//   k_vhd_pairs<D, PERIODIC>   the hot pass: a workgroup takes one (lag, origin, tile of a, tile of b).  A lane owns kVhdR
+//                        b-items, coordinates and ids in registers; the a-items are uniform over the workgroup and are
+//                        read from GA by scalar loads.  Per pair: the id compare, the difference, the image, r2; r2 <
+//                        e[B]: vh_bin and one LDS integer add; otherwise a register counter.  At the end the non-zero
+//                        bins and the waves' overflow sums go into the uint64 histogram by integer atomics.
+//
+// Only integer adds: the same bits in any order, from run to run and for every chunk size.  No floating-point atomics.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <type_traits>
+
+#include "pm_read.hpp"
+#include "ta_internal.hpp"
+#include "vanhove_distinct_math.hpp"
+
+namespace ta {
+namespace {
+
+// Tiles.  A lane keeps kVhdR b-items (kVhdR (2 D + 1) VGPRs for D = 3: 28 of them; the bound is registers: twice as many
+// would cost occupancy without saving anything, the a-item's scalar loads are already shared by 4 pairs per lane), so a
+// workgroup's b-tile is 256 kVhdR = 1024 items; its a-tile is 256 items, bounded by nothing but the wish for enough
+// workgroups per origin at a few thousand items.  A workgroup counts at most kVhdTA kVhdTB = 2^18 pairs, and a bin of its
+// uint32 LDS histogram and a lane's overflow counter hold at most that: below 2^31 by construction.
+constexpr int kVhdR = 4;
+constexpr int kVhdTB = kPmThreads * kVhdR;
+constexpr int kVhdTA = 256;
+static_assert((long)kVhdTA * kVhdTB < (1L << 31), "a workgroup's pair count must stay below 2^31");
+static_assert(kVhdTA == VHD_TILE_A && kVhdTB == VHD_TILE_B, "ta_internal.hpp pads the item pitches to these tiles");
+
+// row t (one frame) of an atom's columns, in the slab's element type: a float64 row is PmAtom's 16-byte load, a float32
+// row one 8-byte load per source pair (PmAtom's 16-byte float32 load would take row t + 1 along)
+template <class E, int D>
+__device__ __forceinline__ void vhd_row(const PmAtom<E, D>& a, long t, double (&out)[3]) {
+    if constexpr (PmAtom<E, D>::kF32) {
+        const float2* p = reinterpret_cast<const float2*>(a.src);
+        const float2 qa = p[t], qb = D == 3 ? p[2 * a.next + t] : qa;
+        pm_pick<D>(qa.x, qa.y, qb.x, qb.y, a.odd, out);
+    } else {
+        double unused[3];
+        a.load(t, out, unused);
+    }
+}
+
+// grid (item blocks of the pitch, origins (looped), slots): slot z < with_a is GA, the others the chunk's lags.  ids: the
+// padded index list of the slot's side (-1: padding, written as zeros).  A lagged row t + tau >= T is neither read nor
+// written: k_vhd_pairs never starts a workgroup for it.
+template <class E, int D>
+__global__ void __launch_bounds__(kPmThreads)
+    k_vhd_gather(const E* __restrict__ x, long pitch, long T, long stride, long n_orig, const long* __restrict__ lags, int with_a,
+                 const int* __restrict__ ida, const int* __restrict__ idb, long pitch_a, long pitch_b, double* __restrict__ ga,
+                 double* __restrict__ gb) {
+    const int z = blockIdx.z;
+    const bool side_a = z < with_a;
+    const long ip = side_a ? pitch_a : pitch_b;
+    const long p = (long)blockIdx.x * kPmThreads + threadIdx.x;
+    if (p >= ip) return;
+    const int id = side_a ? ida[p] : idb[p];
+    const long tau = side_a ? 0 : lags[z - with_a];
+    double* out = side_a ? ga : gb + (size_t)(z - with_a) * (size_t)n_orig * D * (size_t)pitch_b;
+    for (long o = blockIdx.y; o < n_orig; o += gridDim.y) {
+        const long t = o * stride + tau;
+        if (t >= T) break;
+        double v[3] = {0.0, 0.0, 0.0};
+        if (id >= 0) {
+            const PmAtom<E, D> a(x, pitch, (unsigned)id);  // (atom D < 2^31: launch_vhd_gather)
+            vhd_row<E, D>(a, t, v);
+        }
+#pragma unroll
+        for (int d = 0; d < D; ++d) out[((size_t)o * D + d) * (size_t)ip + p] = v[d];
+    }
+}
+
+// grid (a-tiles x b-tiles, origins o0 + y, the chunk's lags).  lags, counts: the chunk's.  hm: per box (one, or one per
+// frame: box_per_frame) H[3] then M[3] of the staged columns.  LDS: e[B + 1] doubles, then the uint32 histogram [B + 1].
+template <int D, bool PERIODIC>
+__global__ void __launch_bounds__(kPmThreads)
+    k_vhd_pairs(const double* __restrict__ ga, const double* __restrict__ gb, const int* __restrict__ ida,
+                const int* __restrict__ idb, long pitch_a, long pitch_b, int n_a, int n_tb, long T, long stride, long n_orig,
+                long o0, const long* __restrict__ lags, const double* __restrict__ hm, int box_per_frame,
+                const double* __restrict__ e_g, int B, float inv_dr, unsigned long long* __restrict__ counts) {
+    const long o = o0 + blockIdx.y;
+    const long t = o * stride;
+    if (o >= n_orig || t + lags[blockIdx.z] >= T) return;  // (the whole workgroup: before any barrier)
+    extern __shared__ __attribute__((aligned(16))) unsigned char vhd_lds[];
+    const int nb = B + 1;
+    double* e = reinterpret_cast<double*>(vhd_lds);
+    unsigned* hist = reinterpret_cast<unsigned*>(e + nb);
+    for (int i = threadIdx.x; i < nb; i += kPmThreads) e[i] = e_g[i], hist[i] = 0;
+    __syncthreads();
+
+    const int tile_a = blockIdx.x / n_tb, tile_b = blockIdx.x % n_tb;
+    double H[3] = {1.0, 1.0, 1.0}, M[3] = {1.0, 1.0, 1.0};
+    if constexpr (PERIODIC) {
+        const double* box = hm + (box_per_frame ? t * 6 : 0);
+#pragma unroll
+        for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
+    }
+    // the lane's b-items at t + tau (coalesced: the item index is contiguous)
+    const double* gbo = gb + ((size_t)blockIdx.z * (size_t)n_orig + (size_t)o) * D * (size_t)pitch_b;
+    double xb[kVhdR][3];
+    int idq[kVhdR];
+#pragma unroll
+    for (int r = 0; r < kVhdR; ++r) {
+        const long q = (long)tile_b * kVhdTB + r * kPmThreads + threadIdx.x;  // (< pitch_b: a multiple of kVhdTB)
+        idq[r] = idb[q];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) xb[r][d] = d < D ? gbo[(size_t)d * pitch_b + q] : 0.0;
+    }
+    const double e_top = e_g[B];
+    const double* gao = ga + (size_t)o * D * (size_t)pitch_a;
+    const int p0 = tile_a * kVhdTA, p1 = min(p0 + kVhdTA, n_a);
+    unsigned over = 0;
+    for (int p = p0; p < p1; ++p) {  // (uniform: the a-item comes by scalar loads)
+        double xa[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int d = 0; d < D; ++d) xa[d] = gao[(size_t)d * pitch_a + p];
+        const int id = ida[p];
+#pragma unroll
+        for (int r = 0; r < kVhdR; ++r) {
+            const double r2 = vhd_r2<D, PERIODIC>(xa, xb[r], H, M);
+            if (idq[r] >= 0 && idq[r] != id) {
+                if (r2 < e_top) atomicAdd(&hist[vh_bin(r2, e, B, inv_dr)], 1u);
+                else ++over;
+            }
+        }
+    }
+    __syncthreads();
+    unsigned long long* row = counts + (size_t)blockIdx.z * nb;
+    for (int i = threadIdx.x; i < B; i += kPmThreads) {
+        const unsigned v = hist[i];
+        if (v) atomicAdd(&row[i], (unsigned long long)v);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) over += __shfl_xor(over, m);  // (a wave's sum: at most 2^18)
+    if ((threadIdx.x & 63) == 0 && over) atomicAdd(&row[B], (unsigned long long)over);
+}
+
+template <class E, int D>
+hipError_t vhd_gather_launch(dim3 grid, hipStream_t st, const void* x, long pitch, long T, long stride, long n_orig, const long* lags,
+                             int with_a, const int* ida, const int* idb, long pitch_a, long pitch_b, double* ga, double* gb) {
+    hipLaunchKernelGGL((k_vhd_gather<E, D>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, stride, n_orig, lags, with_a, ida,
+                       idb, pitch_a, pitch_b, ga, gb);
+    return hipGetLastError();
+}
+template <class E, class... Args>
+hipError_t vhd_gather_dim(int D, Args... args) {
+    if (D == 1) return vhd_gather_launch<E, 1>(args...);
+    if (D == 2) return vhd_gather_launch<E, 2>(args...);
+    return vhd_gather_launch<E, 3>(args...);
+}
+
+template <int D, bool PERIODIC, class... Args>
+hipError_t vhd_pairs_launch(dim3 grid, size_t lds, hipStream_t st, Args... args) {
+    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_vhd_pairs<D, PERIODIC>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL((k_vhd_pairs<D, PERIODIC>), grid, dim3(kPmThreads), lds, st, args...);
+    return hipGetLastError();
+}
+template <bool PERIODIC, class... Args>
+hipError_t vhd_pairs_dim(int D, Args... args) {
+    if (D == 1) return vhd_pairs_launch<1, PERIODIC>(args...);
+    if (D == 2) return vhd_pairs_launch<2, PERIODIC>(args...);
+    return vhd_pairs_launch<3, PERIODIC>(args...);
+}
+
+}  // namespace
+
+hipError_t launch_vhd_gather(const void* x, bool f32, long pitch, long T, long n_atoms, int D, long stride, long n_orig,
+                             const int64_t* lags, int Lc, bool with_a, const int* ida, const int* idb, long pitch_a, long pitch_b,
+                             double* ga, double* gb, hipStream_t st) {
+    if (D < 1 || D > 3 || n_atoms < 1 || n_atoms * D >= (1L << 31) || (pitch & 7) || T < 1 || T > pitch || stride < 1 || n_orig < 1 ||
+        (n_orig - 1) * stride >= T || Lc < 1 || Lc > TA_VANHOVE_MAX_LAGS || pitch_a < 1 || pitch_b < 1 || pitch_a % VHD_TILE_A ||
+        pitch_b % VHD_TILE_B)
+        return hipErrorInvalidValue;
+    static_assert(sizeof(long) == sizeof(int64_t), "lags are read as long");
+    const long ip = std::max(pitch_a, pitch_b);
+    const dim3 grid((unsigned)((ip + kPmThreads - 1) / kPmThreads), (unsigned)std::min(n_orig, 65535L), (unsigned)(Lc + (with_a ? 1 : 0)));
+    const long* lg = reinterpret_cast<const long*>(lags);
+    if (f32) return vhd_gather_dim<float>(D, grid, st, x, pitch, T, stride, n_orig, lg, with_a ? 1 : 0, ida, idb, pitch_a, pitch_b, ga, gb);
+    return vhd_gather_dim<double>(D, grid, st, x, pitch, T, stride, n_orig, lg, with_a ? 1 : 0, ida, idb, pitch_a, pitch_b, ga, gb);
+}
+
+hipError_t launch_vhd_pairs(const double* ga, const double* gb, const int* ida, const int* idb, long pitch_a, long pitch_b, long n_a,
+                            long n_b, int D, long T, long stride, long n_orig, long o0, int n_o, const int64_t* lags, int Lc,
+                            const double* hm, bool box_per_frame, const double* e, int B, float inv_dr, unsigned long long* counts,
+                            hipStream_t st) {
+    const long n_ta = (n_a + kVhdTA - 1) / kVhdTA, n_tb = (n_b + kVhdTB - 1) / kVhdTB;
+    if (D < 1 || D > 3 || n_a < 1 || n_b < 1 || n_a > pitch_a || n_b > pitch_b || pitch_a % kVhdTA || pitch_b % kVhdTB ||
+        n_ta * n_tb >= VHD_MAX_TILES || T < 1 || stride < 1 || n_orig < 1 || (n_orig - 1) * stride >= T || o0 < 0 || n_o < 1 ||
+        n_o > 65535 || o0 + n_o > n_orig || Lc < 1 || Lc > TA_VANHOVE_MAX_LAGS || B < 1 || B > TA_VANHOVE_MAX_BINS)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(n_ta * n_tb), (unsigned)n_o, (unsigned)Lc);
+    const size_t lds = (sizeof(double) + sizeof(unsigned)) * (size_t)(B + 1);
+    const long* lg = reinterpret_cast<const long*>(lags);
+    if (hm)
+        return vhd_pairs_dim<true>(D, grid, lds, st, ga, gb, ida, idb, pitch_a, pitch_b, (int)n_a, (int)n_tb, T, stride, n_orig, o0, lg,
+                                   hm, box_per_frame ? 1 : 0, e, B, inv_dr, counts);
+    return vhd_pairs_dim<false>(D, grid, lds, st, ga, gb, ida, idb, pitch_a, pitch_b, (int)n_a, (int)n_tb, T, stride, n_orig, o0, lg,
+                                hm, 0, e, B, inv_dr, counts);
+}
+
+}  // namespace ta
