@@ -47,6 +47,20 @@ struct DevBuf {
 };
 constexpr bool kTrimmed = true, kKept = false;
 
+// A table a call forms on the host and queues for upload before it is opened: the device copy (a kept workspace like any
+// other), the host storage the asynchronous copy reads, and the event that says the last upload has left it.  begin():
+// the device buffer ensured, that upload waited for, *h = `bytes` of host storage (8-byte aligned) to fill; send(): the
+// copy and the event queued on `st`.  Members of ta_ctx, entered in its list (ta_ctx_destroy walks it for the events).
+struct HostTable {
+    DevBuf dev;
+    std::vector<double> host;
+    size_t n_bytes = 0;
+    hipEvent_t ev = nullptr;
+    HostTable(std::vector<DevBuf*>& workspaces, std::vector<HostTable*>& tables) : dev(workspaces, kKept) { tables.push_back(this); }
+    int begin(ta_ctx* ctx, size_t bytes, void** h);
+    int send(ta_ctx* ctx, hipStream_t st);
+};
+
 // ta_stage_commit hands its frame range to a worker thread that makes the HIP calls (copies in pieces, the transposition
 // launches): the caller's frame loop never waits on the runtime — which it did, for as long as another thread's
 // hipHostMalloc of the by-particle result held the runtime's lock (0.17 s of a 0.6 s loop at 10000 x 50000 x 3).
@@ -126,6 +140,7 @@ struct ta_ctx {
     std::map<int, cd*> wf_tables;  // wfft.hip twiddle tables, keyed by 64 * R0 + R
     // ---- device workspaces: this is the one list of them (kTrimmed: ta_trim releases it, kKept: it does not)
     std::vector<DevBuf*> workspaces;
+    std::vector<HostTable*> tables;  // the host tables among them
     DevBuf partial{workspaces, kTrimmed}, spec{workspaces, kTrimmed}, ts_partial{workspaces, kTrimmed};
     DevBuf out_lagsum{workspaces, kKept}, out_bp{workspaces, kTrimmed}, masses{workspaces, kKept};
     DevBuf stage_buf{workspaces, kTrimmed}, helf_p{workspaces, kTrimmed}, helf_small{workspaces, kTrimmed};
@@ -144,31 +159,23 @@ struct ta_ctx {
     DevBuf ons_out{workspaces, kKept}, ons_pm{workspaces, kTrimmed}, ons_bp{workspaces, kTrimmed};
     DevBuf unwrap_box{workspaces, kTrimmed};    // ta_unwrap: the box table (unwrap_box.hpp) of the last call
     // species self terms (species_self_pm): the weighted slab with each species' atoms contiguous (the input's element
-    // count x 8 bytes + at most one column per species), the atoms in sorted order and the output of host-facing calls.
-    // self_order_h is what the upload of the order reads: it stays until ev_order says the copy is done
-    DevBuf self_w{workspaces, kTrimmed}, self_order{workspaces, kKept}, self_out{workspaces, kKept};
-    std::vector<int32_t> self_order_h;
-    hipEvent_t ev_order = nullptr;
+    // count x 8 bytes + at most one column per species), the atoms in sorted order (int32) and the output of host-facing calls
+    DevBuf self_w{workspaces, kTrimmed}, self_out{workspaces, kKept};
+    HostTable self_order{workspaces, tables};
     // intermediate scattering (scatter_pm): the phase slab Z of one chunk of wavevectors (trimmed), the zero labels of the
     // density sum, the wavevectors in turns, the pair-major copy of the densities with their by-particle lag sums (and the
-    // density itself when the caller does not ask for it), the outputs of host-facing calls.  scatter_q_h is what the
-    // upload of the wavevectors reads: it stays until ev_kvec says the copy is done
-    DevBuf scatter_z{workspaces, kTrimmed}, scatter_lab{workspaces, kKept}, scatter_q{workspaces, kKept};
+    // density itself when the caller does not ask for it), the outputs of host-facing calls
+    DevBuf scatter_z{workspaces, kTrimmed}, scatter_lab{workspaces, kKept};
     DevBuf scatter_work{workspaces, kTrimmed}, scatter_out{workspaces, kKept};
-    std::vector<double> scatter_q_h;
-    hipEvent_t ev_kvec = nullptr;
+    HostTable scatter_q{workspaces, tables};
     // self van Hove function (vanhove_pm): the lags (int64) with the squared edges behind them, the uint64 histogram and
-    // the workgroups' moment partials (the scratch: trimmed), the outputs of host-facing calls.  vh_tab_h is what the
-    // upload of the table reads: it stays until ev_vh says the copy is done
-    DevBuf vh_tab{workspaces, kKept}, vh_hist{workspaces, kTrimmed}, vh_part{workspaces, kTrimmed}, vh_out{workspaces, kKept};
-    std::vector<double> vh_tab_h;
-    hipEvent_t ev_vh = nullptr;
+    // the workgroups' moment partials (the scratch: trimmed), the outputs of host-facing calls
+    HostTable vh_tab{workspaces, tables};
+    DevBuf vh_hist{workspaces, kTrimmed}, vh_part{workspaces, kTrimmed}, vh_out{workspaces, kKept};
     // distinct van Hove function (vhd_pm): the table (lags, squared edges, box entries, padded index lists), the gathered
-    // frame-major scratch GA | GB and the uint64 histogram (trimmed), the output of host-facing calls.  vhd_tab_h is what
-    // the upload of the table reads: it stays until ev_vhd says the copy is done
-    DevBuf vhd_tab{workspaces, kKept}, vhd_scr{workspaces, kTrimmed}, vhd_hist{workspaces, kTrimmed}, vhd_out{workspaces, kKept};
-    std::vector<double> vhd_tab_h;
-    hipEvent_t ev_vhd = nullptr;
+    // frame-major scratch GA | GB and the uint64 histogram (trimmed), the output of host-facing calls
+    HostTable vhd_tab{workspaces, tables};
+    DevBuf vhd_scr{workspaces, kTrimmed}, vhd_hist{workspaces, kTrimmed}, vhd_out{workspaces, kKept};
     // ta_compound: the plan (offsets, members, member weights, their sums per compound) and the (n_frames, dim) weighted
     // mean F of the barycentric term; the per-atom frame weights and F's partial sums use the Onsager workspaces
     DevBuf comp_plan{workspaces, kTrimmed}, comp_f{workspaces, kTrimmed};
@@ -289,6 +296,21 @@ int ensure(ta_ctx* ctx, DevBuf& b, size_t bytes) {
     if (bytes == 0) bytes = 16;
     TA_HIP_TRY(ctx, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
+    return TA_OK;
+}
+
+int HostTable::begin(ta_ctx* ctx, size_t bytes, void** h) {
+    TA_CHECK(ensure(ctx, dev, bytes));
+    if (!ev) TA_HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    else TA_HIP_TRY(ctx, hipEventSynchronize(ev));  // the last call's upload has left `host`
+    host.resize((bytes + 7) / 8);
+    n_bytes = bytes;
+    *h = host.data();
+    return TA_OK;
+}
+int HostTable::send(ta_ctx* ctx, hipStream_t st) {
+    TA_HIP_TRY(ctx, hipMemcpyAsync(dev.p, host.data(), n_bytes, hipMemcpyHostToDevice, st));
+    TA_HIP_TRY(ctx, hipEventRecord(ev, st));
     return TA_OK;
 }
 
@@ -1072,14 +1094,10 @@ int self_args(ta_ctx* ctx, int quantity, int fft, int S, const void* species, co
 int self_plan(ta_ctx* ctx, int S, const int32_t* h_species, int64_t A, int D, hipStream_t st, SortPlan* plan) {
     if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "species self terms: n_atoms * dim must be below 2^31");
     TA_CHECK(check_labels(fail, ctx, h_species, A, S));
-    TA_CHECK(ensure(ctx, ctx->self_order, sizeof(int32_t) * (size_t)A));
-    if (!ctx->ev_order) TA_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_order, hipEventDisableTiming));
-    else TA_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_order));  // the last call's upload has left self_order_h
-    ctx->self_order_h.resize((size_t)A);
-    species_sort_plan(h_species, A, D, S, plan, ctx->self_order_h.data());
-    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->self_order.p, ctx->self_order_h.data(), sizeof(int32_t) * (size_t)A, hipMemcpyHostToDevice, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev_order, st));
-    return TA_OK;
+    void* order = nullptr;
+    TA_CHECK(ctx->self_order.begin(ctx, sizeof(int32_t) * (size_t)A, &order));
+    species_sort_plan(h_species, A, D, S, plan, (int32_t*)order);
+    return ctx->self_order.send(ctx, st);
 }
 
 // One self-term call on a pair-major slab of either element type, read as it is (the caller has opened the call's
@@ -1096,7 +1114,7 @@ int species_self_pm(ta_ctx* ctx, int quantity, bool fft, const Slab& slab, const
     double* W = (double*)ctx->self_w.p;
     TA_LAUNCH_MAIN(ctx, "k_species_sort", st,
                    launch_species_sort(ctx->n_cu, slab.pm, slab.f32, (long)pitch, (long)T, (long)(slab.A * D), D, plan,
-                                       (const int*)ctx->self_order.p, d_w, quantity == TA_SELF_MSD, W, st));
+                                       (const int*)ctx->self_order.dev.p, d_w, quantity == TA_SELF_MSD, W, st));
     for (int s = 0; s < plan.n_species; ++s) {
         double* out = d_self + (size_t)s * T;
         const int64_t n = plan.count[s];
@@ -1135,15 +1153,11 @@ double* scatter_own_density(ta_ctx* ctx, int64_t T, int K) {
 int scatter_plan(ta_ctx* ctx, int K, const double* h_kvecs, int64_t A, int D, hipStream_t st) {
     if (A * D >= (int64_t)1 << 31 || 2 * A >= (int64_t)1 << 31)
         return fail(ctx, TA_E_INVALID, "scatter: n_atoms * max(dim, 2) must be below 2^31");
-    TA_CHECK(ensure(ctx, ctx->scatter_q, sizeof(double) * (size_t)K * D));
+    void* q = nullptr;
+    TA_CHECK(ctx->scatter_q.begin(ctx, sizeof(double) * (size_t)K * D, &q));
     TA_CHECK(ensure(ctx, ctx->scatter_lab, sizeof(int32_t) * (size_t)A));
-    if (!ctx->ev_kvec) TA_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_kvec, hipEventDisableTiming));
-    else TA_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_kvec));  // the last call's upload has left scatter_q_h
-    ctx->scatter_q_h.resize((size_t)K * D);
-    for (size_t i = 0; i < (size_t)K * D; ++i) ctx->scatter_q_h[i] = h_kvecs[i] / 6.283185307179586476925;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->scatter_q.p, ctx->scatter_q_h.data(), sizeof(double) * (size_t)K * D, hipMemcpyHostToDevice, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev_kvec, st));
-    return TA_OK;
+    for (size_t i = 0; i < (size_t)K * D; ++i) ((double*)q)[i] = h_kvecs[i] / 6.283185307179586476925;
+    return ctx->scatter_q.send(ctx, st);
 }
 
 // coll (K, T) of the densities (K, T, 2) at d_density: their pair-major copy is a slab of K "atoms" with D = 2
@@ -1188,7 +1202,7 @@ int scatter_pm(ta_ctx* ctx, bool fft, const Slab& slab, int K, double* d_self, d
         TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)n_parts * T * 2));
         TA_HIP_TRY(ctx, hipMemsetAsync(ctx->scatter_lab.p, 0, sizeof(int32_t) * (size_t)A, st));
     }
-    const double* d_q = (const double*)ctx->scatter_q.p;
+    const double* d_q = (const double*)ctx->scatter_q.dev.p;
     for (int64_t j0 = 0; j0 < K; j0 += Kc) {
         const int kc = (int)std::min<int64_t>(Kc, K - j0);
         TA_LAUNCH_MAIN(ctx, "k_phase", st,
@@ -1210,26 +1224,16 @@ int scatter_pm(ta_ctx* ctx, bool fft, const Slab& slab, int K, double* d_self, d
 }
 
 // ---- self van Hove function (vanhove.hip) ---------------------------------------------------------------------------
-// T: the frames the lags are checked against (0: nothing staged -- the caller reports that next)
-int vanhove_args(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, int64_t T, const void* o_counts, const void* o_moments) {
-    return check_vanhove(fail, ctx, L, h_lags, B, dr, T, o_counts || o_moments);
-}
-
 // The host half of one call, before it is opened: the lags and the squared edges e[0 ... B] (formed once, here) queued for
 // upload on `st` as one table.  Nothing on the device has been written when this fails.
 int vanhove_plan(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, int64_t A, int D, hipStream_t st) {
     if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "vanhove: n_atoms * dim must be below 2^31");
-    const size_t n = (size_t)L + (size_t)B + 1;
-    TA_CHECK(ensure(ctx, ctx->vh_tab, sizeof(double) * n));
-    if (!ctx->ev_vh) TA_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_vh, hipEventDisableTiming));
-    else TA_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_vh));  // the last call's upload has left vh_tab_h
-    ctx->vh_tab_h.resize(n);
+    void* h = nullptr;
+    TA_CHECK(ctx->vh_tab.begin(ctx, sizeof(double) * ((size_t)L + (size_t)B + 1), &h));
     static_assert(sizeof(int64_t) == sizeof(double), "the lags travel in the table's first n_lags slots");
-    memcpy(ctx->vh_tab_h.data(), h_lags, sizeof(int64_t) * (size_t)L);
-    vh_edges(B, dr, ctx->vh_tab_h.data() + L);
-    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->vh_tab.p, ctx->vh_tab_h.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev_vh, st));
-    return TA_OK;
+    memcpy(h, h_lags, sizeof(int64_t) * (size_t)L);
+    vh_edges(B, dr, (double*)h + L);
+    return ctx->vh_tab.send(ctx, st);
 }
 
 // One van Hove call on a pair-major position slab of either element type, read as it is (the caller has opened the call's
@@ -1245,8 +1249,8 @@ int vanhove_pm(ta_ctx* ctx, const Slab& slab, int L, int B, double dr, int64_t* 
     const size_t hist_bytes = sizeof(int64_t) * (size_t)L * (size_t)(B + 1);
     TA_CHECK(ensure(ctx, ctx->vh_hist, hist_bytes));
     TA_CHECK(ensure(ctx, ctx->vh_part, sizeof(double) * (size_t)n_parts * 2 * (size_t)L));
-    const int64_t* d_lags = (const int64_t*)ctx->vh_tab.p;
-    const double* d_e = (const double*)ctx->vh_tab.p + L;
+    const int64_t* d_lags = (const int64_t*)ctx->vh_tab.dev.p;
+    const double* d_e = (const double*)ctx->vh_tab.dev.p + L;
     TA_HIP_TRY(ctx, hipMemsetAsync(ctx->vh_hist.p, 0, hist_bytes, st));
     for (int l0 = 0; l0 < L; l0 += Lc)
         TA_LAUNCH_MAIN(ctx, "k_vanhove", st,
@@ -1262,27 +1266,26 @@ int vanhove_pm(ta_ctx* ctx, const Slab& slab, int L, int B, double dr, int64_t* 
 // ---- distinct van Hove function (vanhove_distinct.hip) --------------------------------------------------------------
 constexpr size_t kVhdBudget = (size_t)4 << 30;  // the gathered scratch of one pass (a choice, not a measurement)
 
-// What ta_vanhove_distinct* can check without the staged shape.  T: the frames the lags are checked against (0: nothing
-// staged -- the caller reports that next)
-int vhd_args(ta_ctx* ctx, int L, const int64_t* h_lags, int64_t stride, int64_t n_a, const int64_t* h_idx_a, int64_t n_b,
-             const int64_t* h_idx_b, const double* h_dims, const int* axes, int B, double dr, int64_t T, const void* out) {
-    if (!h_lags) return fail(ctx, TA_E_INVALID, "vanhove_distinct: lags are NULL");
-    if (L < 1 || L > TA_VANHOVE_MAX_LAGS)
-        return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_lags must be 1 ... " + std::to_string(TA_VANHOVE_MAX_LAGS));
-    if (B < 1 || B > TA_VANHOVE_MAX_BINS)
-        return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_bins must be 1 ... " + std::to_string(TA_VANHOVE_MAX_BINS));
-    if (!(dr - dr == 0.0) || !(dr > 0.0)) return fail(ctx, TA_E_INVALID, "vanhove_distinct: dr must be finite and > 0");
-    if (stride < 1) return fail(ctx, TA_E_INVALID, "vanhove_distinct: origin_stride must be >= 1");
+// The caller's arguments of ta_vanhove_distinct*, as they came
+struct VhdArgs {
+    int L, B;
+    double dr;
+    int64_t stride, n_a, n_b;
+    const int64_t *h_lags, *h_idx_a, *h_idx_b;
+    const double* h_dims;
+    const int* axes;
+};
+
+// What ta_vanhove_distinct* can check without the staged shape: the van Hove checks of ta_internal.hpp with the family's
+// own between them.  T: the frames the lags are checked against (0: nothing staged -- the caller reports that next)
+int vhd_args(ta_ctx* ctx, const VhdArgs& a, int64_t T, const void* out) {
+    TA_CHECK(check_vanhove_grid(fail, ctx, "vanhove_distinct: ", a.L, a.h_lags, a.B, a.dr));
+    if (a.stride < 1) return fail(ctx, TA_E_INVALID, "vanhove_distinct: origin_stride must be >= 1");
     if (!out) return fail(ctx, TA_E_INVALID, "vanhove_distinct: the counts output is NULL");
-    if (h_idx_a && n_a < 1) return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_a must be >= 1");
-    if (h_idx_b && n_b < 1) return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_b must be >= 1");
-    if (h_dims && !axes) return fail(ctx, TA_E_INVALID, "vanhove_distinct: dimensions without axes");
-    for (int l = 0; l < L; ++l) {
-        if (h_lags[l] < 0 || (T > 0 && h_lags[l] >= T))
-            return fail(ctx, TA_E_INVALID, "vanhove_distinct: lag " + std::to_string(h_lags[l]) + " is outside 0 ... n_frames - 1");
-        if (l && h_lags[l] <= h_lags[l - 1]) return fail(ctx, TA_E_INVALID, "vanhove_distinct: the lags must be strictly increasing");
-    }
-    return TA_OK;
+    if (a.h_idx_a && a.n_a < 1) return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_a must be >= 1");
+    if (a.h_idx_b && a.n_b < 1) return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_b must be >= 1");
+    if (a.h_dims && !a.axes) return fail(ctx, TA_E_INVALID, "vanhove_distinct: dimensions without axes");
+    return check_vanhove_lags(fail, ctx, "vanhove_distinct: ", a.L, a.h_lags, T);
 }
 
 // The host side of one call (both kinds of context): the index lists padded to the pair kernel's tiles (-1: padding), the
@@ -1311,8 +1314,8 @@ static int vhd_index_list(ta_ctx* ctx, const char* name, int64_t n, const int64_
 }
 
 // Everything that needs the staged shape (T, A, D), checked before anything is written
-int vhd_plan(ta_ctx* ctx, int L, const int64_t* h_lags, int64_t stride, int64_t n_a, const int64_t* h_idx_a, int64_t n_b,
-             const int64_t* h_idx_b, const double* h_dims, const int* axes, int B, double dr, int64_t T, int64_t A, int D, VhdPlan* p) {
+int vhd_plan(ta_ctx* ctx, const VhdArgs& args, int64_t T, int64_t A, int D, VhdPlan* p) {
+    auto [L, B, dr, stride, n_a, n_b, h_lags, h_idx_a, h_idx_b, h_dims, axes] = args;
     if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_atoms * dim must be below 2^31");
     p->L = L, p->B = B, p->D = D, p->T = T, p->stride = stride;
     p->n_a = h_idx_a ? n_a : A;
@@ -1370,11 +1373,8 @@ struct VhdTab {
 };
 int vhd_upload(ta_ctx* ctx, const VhdPlan& p, const int64_t* h_lags, double dr, hipStream_t st) {
     const size_t n = (size_t)p.L + (size_t)p.B + 1 + p.hm.size() + (size_t)(p.pitch_a + p.pitch_b) / 2;  // (both pitches are even)
-    TA_CHECK(ensure(ctx, ctx->vhd_tab, sizeof(double) * n));
-    if (!ctx->ev_vhd) TA_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_vhd, hipEventDisableTiming));
-    else TA_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_vhd));  // the last call's upload has left vhd_tab_h
-    ctx->vhd_tab_h.resize(n);
-    double* h = ctx->vhd_tab_h.data();
+    double* h = nullptr;
+    TA_CHECK(ctx->vhd_tab.begin(ctx, sizeof(double) * n, (void**)&h));
     static_assert(sizeof(int64_t) == sizeof(double) && 2 * sizeof(int32_t) == sizeof(double), "the table's slots");
     memcpy(h, h_lags, sizeof(int64_t) * (size_t)p.L);
     vh_edges(p.B, dr, h + p.L);
@@ -1383,12 +1383,10 @@ int vhd_upload(ta_ctx* ctx, const VhdPlan& p, const int64_t* h_lags, double dr, 
     q += p.hm.size();
     memcpy(q, p.ida.data(), sizeof(int32_t) * p.ida.size());
     memcpy(q + p.pitch_a / 2, p.idb.data(), sizeof(int32_t) * p.idb.size());
-    TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->vhd_tab.p, h, sizeof(double) * n, hipMemcpyHostToDevice, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev_vhd, st));
-    return TA_OK;
+    return ctx->vhd_tab.send(ctx, st);
 }
 VhdTab vhd_tab(ta_ctx* ctx, const VhdPlan& p) {
-    const double* d = (const double*)ctx->vhd_tab.p;
+    const double* d = (const double*)ctx->vhd_tab.dev.p;
     const double* q = d + p.L + p.B + 1;
     const int* ids = (const int*)(q + p.hm.size());
     return {(const int64_t*)d, d + p.L, p.hm.empty() ? nullptr : q, ids, ids + p.pitch_a};
@@ -1431,30 +1429,21 @@ int vhd_pm(ta_ctx* ctx, const Slab& slab, const VhdPlan& p, double dr, int64_t* 
     return call_end(ctx, st);
 }
 
-// ta_vanhove_distinct_staged and the device half of ta_vanhove_distinct: d_counts NULL = the context's own output buffer
-// (*d_out tells where the counts are)
-int vhd_entry(ta_ctx* ctx, int L, const int64_t* h_lags, int64_t stride, int64_t n_a, const int64_t* h_idx_a, int64_t n_b,
-              const int64_t* h_idx_b, const double* h_dims, const int* axes, int B, double dr, int64_t* d_counts, bool own_output,
-              void* stream, int64_t** d_out) {
-    VhdPlan plan;
-    int64_t* out = d_counts;
+// What ta_vanhove_distinct_staged and ta_vanhove_distinct share once the plan is made: the table queued, the call opened,
+// vhd_pm.  d_counts NULL = the context's own output buffer; *d_out (d_out NULL: not asked) tells where the counts are
+int vhd_launch(ta_ctx* ctx, const VhdPlan& plan, const int64_t* h_lags, double dr, int64_t* d_counts, void* stream, int64_t** d_out) {
     return slab_entry(
-        ctx, nullptr, stream,
-        [&] {
-            return vhd_args(ctx, L, h_lags, stride, n_a, h_idx_a, n_b, h_idx_b, h_dims, axes, B, dr, ctx->st_nslabs ? ctx->st_T : 0,
-                            own_output ? (const void*)ctx : (const void*)d_counts);
-        },
+        ctx, nullptr, stream, no_args,
         [&](const Slab& s) -> int {
-            TA_CHECK(vhd_plan(ctx, L, h_lags, stride, n_a, h_idx_a, n_b, h_idx_b, h_dims, axes, B, dr, s.T, s.A, s.D, &plan));
             TA_CHECK(vhd_upload(ctx, plan, h_lags, dr, s.st));
-            if (own_output) {
-                TA_CHECK(ensure(ctx, ctx->vhd_out, sizeof(int64_t) * (size_t)L * (size_t)(B + 1)));
-                out = (int64_t*)ctx->vhd_out.p;
+            if (!d_counts) {
+                TA_CHECK(ensure(ctx, ctx->vhd_out, sizeof(int64_t) * (size_t)plan.L * (size_t)(plan.B + 1)));
+                d_counts = (int64_t*)ctx->vhd_out.p;
             }
-            if (d_out) *d_out = out;
+            if (d_out) *d_out = d_counts;
             return TA_OK;
         },
-        [&](const Slab& s) { return vhd_pm(ctx, s, plan, dr, out); });
+        [&](const Slab& s) { return vhd_pm(ctx, s, plan, dr, d_counts); });
 }
 
 // ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
@@ -1494,6 +1483,9 @@ int cpu_stage_alloc(ta_ctx* ctx, int64_t n_frames, int64_t n_atoms, int dim, int
     return TA_OK;
 }
 
+// the tail of every CPU branch: the backend's return code (0, or TA_E_NOMEM) as the entry's
+int cpu_rc(ta_ctx* ctx, int rc) { return rc ? fail(ctx, rc, "CPU backend: out of host memory") : TA_OK; }
+
 // the mean over atoms of a lag-indexed sum (velocityautocorr.py:214,237; viscosity.py:233)
 void atom_mean(const ta_ctx* ctx, double* h_ts) {
     const double n_at = (double)ctx->st_A;
@@ -1508,16 +1500,14 @@ int cpu_compute(ta_ctx* ctx, int which, const double* h_masses, double scale, do
                    : which == W_DIRECT ? ta::cpu::vacf_direct(s, h_ts, h_bp)
                    : is_msd(which)     ? ta::cpu::msd(s, which == W_MSD_FFT, h_ts, h_bp)
                                        : ta::cpu::helfand(s, h_masses, scale, h_ts, h_bp);
-    if (rc) return fail(ctx, rc, "CPU backend: out of host memory");
+    TA_CHECK(cpu_rc(ctx, rc));
     atom_mean(ctx, h_ts);
     return TA_OK;
 }
 
 int cpu_conductivity(ta_ctx* ctx, bool fft, const double* h_charges, double* h_moment, double* h_collective,
                      double* h_self_lagsum) {
-    if (int rc = ta::cpu::conductivity(cpu_state(ctx), fft, h_charges, h_moment, h_collective, h_self_lagsum))
-        return fail(ctx, rc, "CPU backend: out of host memory");
-    return TA_OK;
+    return cpu_rc(ctx, ta::cpu::conductivity(cpu_state(ctx), fft, h_charges, h_moment, h_collective, h_self_lagsum));
 }
 
 // ---- options: the table behind ta_set_option ------------------------------------------------------------------------
@@ -1665,10 +1655,10 @@ int ta_ctx_destroy(ta_ctx* ctx) {
         for (auto& ev : q)
             if (ev) hipEventDestroy(ev);
     if (ctx->ev_stage) hipEventDestroy(ctx->ev_stage);
-    for (hipEvent_t e : {ctx->ev_order, ctx->ev_kvec, ctx->ev_vh, ctx->ev_vhd})
-        if (e) {
-            hipEventSynchronize(e);  // (the upload may be on a caller's stream)
-            hipEventDestroy(e);
+    for (HostTable* t : ctx->tables)
+        if (t->ev) {
+            hipEventSynchronize(t->ev);  // (the upload may be on a caller's stream)
+            hipEventDestroy(t->ev);
         }
     for (hipEvent_t e : ctx->mark_pool) hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) {
@@ -2244,7 +2234,7 @@ static int vanhove_entry(ta_ctx* ctx, const DevSrc* dev, int n_lags, const int64
                          int64_t* d_counts, double* d_moments, void* stream) {
     return slab_entry(
         ctx, dev, stream,
-        [&] { return vanhove_args(ctx, n_lags, h_lags, n_bins, dr, dev ? dev->T : ctx->st_nslabs ? ctx->st_T : 0, d_counts, d_moments); },
+        [&] { return check_vanhove(fail, ctx, n_lags, h_lags, n_bins, dr, dev ? dev->T : ctx->st_nslabs ? ctx->st_T : 0, d_counts || d_moments); },
         [&](const Slab& s) { return vanhove_plan(ctx, n_lags, h_lags, n_bins, dr, s.A, s.D, s.st); },
         [&](const Slab& s) { return vanhove_pm(ctx, s, n_lags, n_bins, dr, d_counts, d_moments); });
 }
@@ -2267,8 +2257,14 @@ int ta_vanhove_distinct_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, i
                                const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes,
                                int n_bins, double dr, int64_t* d_counts, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
-    return vhd_entry(ctx, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr, d_counts, false,
-                     stream, nullptr);
+    const VhdArgs a{n_lags, n_bins, dr, origin_stride, n_a, n_b, h_lags, h_idx_a, h_idx_b, h_dimensions, axes};
+    VhdPlan plan;
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(vhd_args(ctx, a, ctx->st_nslabs ? ctx->st_T : 0, d_counts));
+    TA_CHECK(check_staged(ctx));
+    TA_CHECK(vhd_plan(ctx, a, ctx->st_T, ctx->st_A, ctx->st_D, &plan));
+    return vhd_launch(ctx, plan, h_lags, dr, d_counts, stream, nullptr);
     });
 }
 
@@ -2528,22 +2524,38 @@ int coll_launch(ta_ctx* ctx, int kind, int fft, int S, const int32_t* h_species,
     return TA_OK;
 }
 
-// The cross term of host (S, T, D) sums on this context's device, blocking, as a compute call of its own (ta_onsager_cross,
-// ta_current_cross; the group's ONE evaluation after its members' sums).  Needs no staged slab.
-int coll_cross_host(ta_ctx* ctx, int kind, int fft, const double* h_sums, int S, int64_t T, int D, double* h_cross) {
+// A correlation of host sums on this context's device, blocking, as a compute call of its own (the *_cross and
+// *_collective entries; a group's ONE evaluation after its members' sums).  Needs no staged slab.  upload(st): the
+// workspaces ensured, the sums queued for upload; body(st): the correlation, inside the call's bracket (no dominant
+// kernel of its own, unless the correlator records one); back(): the one copy to the host.
+template <class Upload, class Body, class Back>
+int host_sums_call(ta_ctx* ctx, Upload&& upload, Body&& body, Back&& back) {
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     TA_CHECK(ctx->commits.flush());
-    TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)T * S * (D + S)));
-    double* out = (double*)ctx->ons_out.p;
-    double* cross = out + (size_t)S * T * D;
     hipStream_t st = ctx->stream;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_sums, sizeof(double) * (size_t)S * T * D, hipMemcpyHostToDevice, st));
+    TA_CHECK(upload(st));
     TA_CHECK(call_begin(ctx, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));  // no dominant kernel of its own, unless the correlator records one
+    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
     TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-    TA_CHECK(coll_cross(ctx, kCollective[kind], fft != 0, out, S, T, D, cross, st));
+    TA_CHECK(body(st));
     TA_CHECK(call_end(ctx, st));
-    return host_finish(ctx, {{h_cross, cross, (size_t)T * S * S}});
+    return host_finish(ctx, {back()});
+}
+
+// The cross term (T, S, S) of host (S, T, D) sums (ta_onsager_cross, ta_current_cross)
+int coll_cross_host(ta_ctx* ctx, int kind, int fft, const double* h_sums, int S, int64_t T, int D, double* h_cross) {
+    const size_t n_sums = (size_t)S * T * D;
+    double* out = nullptr;
+    return host_sums_call(
+        ctx,
+        [&](hipStream_t st) -> int {
+            TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)T * S * (D + S)));
+            out = (double*)ctx->ons_out.p;
+            TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_sums, sizeof(double) * n_sums, hipMemcpyHostToDevice, st));
+            return TA_OK;
+        },
+        [&](hipStream_t st) { return coll_cross(ctx, kCollective[kind], fft != 0, out, S, T, D, out + n_sums, st); },
+        [&] { return HostCopy{h_cross, out + n_sums, (size_t)T * S * S}; });
 }
 
 // Self-term share of a host-facing call, queued on ctx->stream and not waited for: the labels (this context's atoms)
@@ -2612,23 +2624,21 @@ int vanhove_launch(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, 
     return TA_OK;
 }
 
-// The collective part of a host (K, T, 2) density on this context's device, blocking, as a compute call of its own
-// (ta_scatter_collective; the group's ONE evaluation after its members' sums).  Needs no staged slab.
+// The collective part (K, T) of a host (K, T, 2) density (ta_scatter_collective)
 int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int K, int64_t T, double* h_coll) {
-    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    TA_CHECK(ctx->commits.flush());
     const size_t KT = (size_t)K * T;
-    TA_CHECK(ensure(ctx, ctx->scatter_out, sizeof(double) * KT * 4));
-    TA_CHECK(ensure(ctx, ctx->scatter_work, scatter_work_bytes(T, K, false)));
-    double* out = (double*)ctx->scatter_out.p;
-    hipStream_t st = ctx->stream;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(out + KT, h_density, sizeof(double) * KT * 2, hipMemcpyHostToDevice, st));
-    TA_CHECK(call_begin(ctx, st));
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));  // no dominant kernel of its own, unless the correlator records one
-    TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-    TA_CHECK(scatter_collective(ctx, fft != 0, out + KT, K, T, out + 3 * KT, st));
-    TA_CHECK(call_end(ctx, st));
-    return host_finish(ctx, {{h_coll, out + 3 * KT, KT}});
+    double* out = nullptr;
+    return host_sums_call(
+        ctx,
+        [&](hipStream_t st) -> int {
+            TA_CHECK(ensure(ctx, ctx->scatter_out, sizeof(double) * KT * 4));
+            TA_CHECK(ensure(ctx, ctx->scatter_work, scatter_work_bytes(T, K, false)));
+            out = (double*)ctx->scatter_out.p;
+            TA_HIP_TRY(ctx, hipMemcpyAsync(out + KT, h_density, sizeof(double) * KT * 2, hipMemcpyHostToDevice, st));
+            return TA_OK;
+        },
+        [&](hipStream_t st) { return scatter_collective(ctx, fft != 0, out + KT, K, T, out + 3 * KT, st); },
+        [&] { return HostCopy{h_coll, out + 3 * KT, KT}; });
 }
 
 // One context's unwrap of staged slab `slab` (ta_unwrap, ta_group_unwrap), queued on ctx->stream behind the queued commits
@@ -2737,11 +2747,7 @@ static int coll_host(ta_ctx* ctx, int kind, int fft, int n_species, const int32_
     TA_CHECK(coll_args(ctx, q, fft, n_species, h_species, h_sums));
     TA_CHECK(check_staged(ctx));
     TA_CHECK(check_labels(fail, ctx, h_species, ctx->st_A, n_species));
-    if (ctx->is_cpu) {
-        if (int rc = q.cpu(cpu_state(ctx), fft != 0, n_species, h_species, h_weights, h_sums, h_cross))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
-    }
+    if (ctx->is_cpu) return cpu_rc(ctx, q.cpu(cpu_state(ctx), fft != 0, n_species, h_species, h_weights, h_sums, h_cross));
     double* d_out = nullptr;
     TA_CHECK(ta::coll_launch(ctx, kind, fft, n_species, h_species, h_weights, h_cross != nullptr, &d_out));
     const size_t T = (size_t)ctx->st_T, D = (size_t)ctx->st_D, S = (size_t)n_species;
@@ -2758,11 +2764,7 @@ static int coll_cross_call(ta_ctx* ctx, int kind, int fft, const double* h_sums,
     if (!h_sums || !h_cross) return fail(ctx, TA_E_INVALID, std::string(q.noun) + " or cross output is NULL");
     if (n_frames < 1 || dim < 1 || dim > 3 || n_frames > (int64_t)1 << 30)
         return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30, 1 <= dim <= 3");
-    if (ctx->is_cpu) {
-        if (int rc = q.cpu_cross(ctx->cpu_threads, fft != 0, h_sums, n_species, n_frames, dim, h_cross))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
-    }
+    if (ctx->is_cpu) return cpu_rc(ctx, q.cpu_cross(ctx->cpu_threads, fft != 0, h_sums, n_species, n_frames, dim, h_cross));
     return ta::coll_cross_host(ctx, kind, fft, h_sums, n_species, n_frames, dim, h_cross);
     });
 }
@@ -2789,10 +2791,8 @@ int ta_species_self(ta_ctx* ctx, int quantity, int fft, int n_species, const int
     TA_CHECK(check_staged(ctx));
     if (ctx->is_cpu) {
         TA_CHECK(check_labels(fail, ctx, h_species, ctx->st_A, n_species));
-        if (int rc = ta::cpu::species_self(cpu_state(ctx), quantity == TA_SELF_MSD, fft != 0, n_species, h_species, h_weights,
-                                           h_self, h_counts))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
+        return cpu_rc(ctx, ta::cpu::species_self(cpu_state(ctx), quantity == TA_SELF_MSD, fft != 0, n_species, h_species, h_weights,
+                                                 h_self, h_counts));
     }
     double* d_out = nullptr;
     TA_CHECK(ta::self_launch(ctx, quantity, fft, n_species, h_species, h_weights, h_counts, &d_out));
@@ -2805,11 +2805,7 @@ int ta_scatter(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, double* h_s
     TA_CHECK(need_ctx(ctx));
     TA_CHECK(scatter_args(ctx, fft, n_k, h_kvecs, ctx->st_nslabs ? ctx->st_D : 0, h_self, h_density, h_coll));
     TA_CHECK(check_staged(ctx));
-    if (ctx->is_cpu) {
-        if (int rc = ta::cpu::scatter(cpu_state(ctx), fft != 0, n_k, h_kvecs, h_self, h_density, h_coll))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
-    }
+    if (ctx->is_cpu) return cpu_rc(ctx, ta::cpu::scatter(cpu_state(ctx), fft != 0, n_k, h_kvecs, h_self, h_density, h_coll));
     double* d_out = nullptr;
     TA_CHECK(ta::scatter_launch(ctx, fft, n_k, h_kvecs, h_self != nullptr, h_density != nullptr, h_coll != nullptr, &d_out));
     const size_t KT = (size_t)n_k * (size_t)ctx->st_T;
@@ -2824,11 +2820,7 @@ int ta_scatter_collective(ta_ctx* ctx, int fft, const double* h_density, int n_k
     if (!h_density || !h_coll) return fail(ctx, TA_E_INVALID, "density or collective output is NULL");
     if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(ctx, TA_E_INVALID, "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
     if (n_frames < 1 || n_frames > (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30");
-    if (ctx->is_cpu) {
-        if (int rc = ta::cpu::scatter_collective(ctx->cpu_threads, fft != 0, h_density, n_k, n_frames, h_coll))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
-    }
+    if (ctx->is_cpu) return cpu_rc(ctx, ta::cpu::scatter_collective(ctx->cpu_threads, fft != 0, h_density, n_k, n_frames, h_coll));
     return ta::scatter_collective_host(ctx, fft, h_density, n_k, n_frames, h_coll);
     });
 }
@@ -2836,13 +2828,11 @@ int ta_scatter_collective(ta_ctx* ctx, int fft, const double* h_density, int n_k
 int ta_vanhove(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, double dr, int64_t* h_counts, double* h_moments) {
     return host_call(ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
-    TA_CHECK(vanhove_args(ctx, n_lags, h_lags, n_bins, dr, ctx->st_nslabs ? ctx->st_T : 0, h_counts, h_moments));
+    TA_CHECK(check_vanhove(fail, ctx, n_lags, h_lags, n_bins, dr, ctx->st_nslabs ? ctx->st_T : 0, h_counts || h_moments));
     TA_CHECK(check_staged(ctx));
     if (ctx->is_cpu) {
         if (ctx->st_A * ctx->st_D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "vanhove: n_atoms * dim must be below 2^31");
-        if (int rc = ta::cpu::vanhove(cpu_state(ctx), n_lags, h_lags, n_bins, dr, h_counts, h_moments))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
+        return cpu_rc(ctx, ta::cpu::vanhove(cpu_state(ctx), n_lags, h_lags, n_bins, dr, h_counts, h_moments));
     }
     void* d_out = nullptr;
     TA_CHECK(ta::vanhove_launch(ctx, n_lags, h_lags, n_bins, dr, h_counts != nullptr, h_moments != nullptr, &d_out));
@@ -2856,22 +2846,17 @@ int ta_vanhove_distinct(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int64_t 
                         int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes, int n_bins, double dr,
                         int64_t* h_counts) {
     return host_call(ctx, [&]() -> int {
+    const VhdArgs a{n_lags, n_bins, dr, origin_stride, n_a, n_b, h_lags, h_idx_a, h_idx_b, h_dimensions, axes};
+    VhdPlan p;
     TA_CHECK(need_ctx(ctx));
-    if (ctx->is_cpu) {
-        TA_CHECK(vhd_args(ctx, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr,
-                          ctx->st_nslabs ? ctx->st_T : 0, h_counts));
-        TA_CHECK(check_staged(ctx));
-        VhdPlan p;
-        TA_CHECK(vhd_plan(ctx, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr, ctx->st_T,
-                          ctx->st_A, ctx->st_D, &p));
-        if (int rc = ta::cpu::vanhove_distinct(cpu_state(ctx), n_lags, h_lags, origin_stride, p.n_a, p.ida.data(), p.n_b, p.idb.data(),
-                                               p.hm.empty() ? nullptr : p.hm.data(), p.per_frame, n_bins, dr, h_counts))
-            return fail(ctx, rc, "CPU backend: out of host memory");
-        return TA_OK;
-    }
+    TA_CHECK(vhd_args(ctx, a, ctx->st_nslabs ? ctx->st_T : 0, h_counts));
+    TA_CHECK(check_staged(ctx));
+    TA_CHECK(vhd_plan(ctx, a, ctx->st_T, ctx->st_A, ctx->st_D, &p));
+    if (ctx->is_cpu)
+        return cpu_rc(ctx, ta::cpu::vanhove_distinct(cpu_state(ctx), n_lags, h_lags, origin_stride, p.n_a, p.ida.data(), p.n_b, p.idb.data(),
+                                                     p.hm.empty() ? nullptr : p.hm.data(), p.per_frame, n_bins, dr, h_counts));
     int64_t* d_out = nullptr;
-    TA_CHECK(vhd_entry(ctx, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr,
-                       nullptr, h_counts != nullptr, ctx->stream, &d_out));
+    TA_CHECK(vhd_launch(ctx, p, h_lags, dr, nullptr, ctx->stream, &d_out));
     return host_finish(ctx, {{(double*)h_counts, (const double*)d_out, (size_t)n_lags * (size_t)(n_bins + 1)}});  // (8-byte elements)
     });
 }
@@ -2913,7 +2898,7 @@ int ta_compound(ta_ctx* ctx, int64_t n_compounds, const int64_t* h_offsets, cons
         if (host_block_map(out_elems * sizeof(double), &blk) != 0) return fail(ctx, TA_E_NOMEM, "compound: no host memory for the new slab");
         if (int rc = ta::cpu::compound(cpu_state(ctx), C, h_offsets, h_members, h_weights, h_frame_weights, (double*)blk.base)) {
             host_block_unmap(blk);
-            return fail(ctx, rc, "CPU backend: out of host memory");
+            return cpu_rc(ctx, rc);
         }
         release_host_slabs(ctx);
         ctx->h_slabs[0] = blk.base, ctx->h_blocks[0] = blk;

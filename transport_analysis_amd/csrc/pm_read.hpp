@@ -1,5 +1,6 @@
 // pm_read.hpp — reading a pair-major slab in its own element type, and writing whole pairs of a float64 one: the pieces
-// shared by k_species_sum (species_sum.hip), k_species_sort (species_self.hip) and k_compound (compound.hip).
+// shared by k_species_sum (species_sum.hip), k_species_sort (species_self.hip), k_compound (compound.hip), k_vanhove
+// (vanhove.hip) and k_vhd_gather (vanhove_distinct.hip).
 //
 // A pair is `pitch` rows of two columns along time (pitch a multiple of 8, T <= pitch frames are live).  Every load is 16
 // bytes: row t of a float64 pair, rows 2 q, 2 q + 1 of a float32 one (8-byte rows), widened in registers.  The rules:
@@ -56,6 +57,14 @@ struct PmAtom {
         const Row qa = src[i], qb = D == 3 ? src[next + i] : qa;
         pm_pick<D>(qa.x, qa.y, qb.x, qb.y, odd, lo);
         if constexpr (kF32) pm_pick<D>(qa.z, qa.w, qb.z, qb.w, odd, hi);
+    }
+    // row r (one frame) of a float32 atom alone: one 8-byte load per source pair, for the readers that must not take row
+    // r + 1 along (k_vanhove's lagged row at an odd lag, k_vhd_gather)
+    __device__ __forceinline__ void row32(long r, double (&out)[3]) const {
+        static_assert(kF32, "a float64 row is load()'s 16 bytes");
+        const float2* p = reinterpret_cast<const float2*>(src);
+        const float2 qa = p[r], qb = D == 3 ? p[2 * next + r] : qa;
+        pm_pick<D>(qa.x, qa.y, qb.x, qb.y, odd, out);
     }
 };
 

@@ -123,24 +123,36 @@ static int check_kvecs(Fail fail, Owner* owner, int fft, int n_k, const double* 
 // for are valid after host_wait; and the collective part of a host density on the context's device, blocking
 int scatter_launch(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, bool self, bool density, bool coll, double** d_out);
 int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int n_k, int64_t T, double* h_coll);
-// the argument checks of ta_vanhove* on a context (fail, ctx) or a group (gfail, g): the same messages for both.  T: the
-// frames the lags are checked against (0: not known, nothing staged -- the caller reports that next)
+// the argument checks the van Hove families share, on a context (fail, ctx) or a group (gfail, g), under the family's
+// message prefix `p`: the lags' array, the counts and the bin width ...
+template <class Fail, class Owner>
+static int check_vanhove_grid(Fail fail, Owner* owner, const std::string& p, int n_lags, const int64_t* h_lags, int n_bins, double dr) {
+    if (!h_lags) return fail(owner, TA_E_INVALID, p + "lags are NULL");
+    if (n_lags < 1 || n_lags > TA_VANHOVE_MAX_LAGS)
+        return fail(owner, TA_E_INVALID, p + "n_lags must be 1 ... " + std::to_string(TA_VANHOVE_MAX_LAGS));
+    if (n_bins < 1 || n_bins > TA_VANHOVE_MAX_BINS)
+        return fail(owner, TA_E_INVALID, p + "n_bins must be 1 ... " + std::to_string(TA_VANHOVE_MAX_BINS));
+    if (!(dr - dr == 0.0) || !(dr > 0.0)) return fail(owner, TA_E_INVALID, p + "dr must be finite and > 0");
+    return TA_OK;
+}
+// ... and, after the family's own checks, the lags against T frames (0: not known, nothing staged -- the caller reports
+// that next)
+template <class Fail, class Owner>
+static int check_vanhove_lags(Fail fail, Owner* owner, const std::string& p, int n_lags, const int64_t* h_lags, int64_t T) {
+    for (int l = 0; l < n_lags; ++l) {
+        if (h_lags[l] < 0 || (T > 0 && h_lags[l] >= T))
+            return fail(owner, TA_E_INVALID, p + "lag " + std::to_string(h_lags[l]) + " is outside 0 ... n_frames - 1");
+        if (l && h_lags[l] <= h_lags[l - 1]) return fail(owner, TA_E_INVALID, p + "the lags must be strictly increasing");
+    }
+    return TA_OK;
+}
+// the argument checks of ta_vanhove* (context or group: the same messages for both)
 template <class Fail, class Owner>
 static int check_vanhove(Fail fail, Owner* owner, int n_lags, const int64_t* h_lags, int n_bins, double dr, int64_t T,
                          bool any_output) {
-    if (!h_lags) return fail(owner, TA_E_INVALID, "vanhove: lags are NULL");
-    if (n_lags < 1 || n_lags > TA_VANHOVE_MAX_LAGS)
-        return fail(owner, TA_E_INVALID, "vanhove: n_lags must be 1 ... " + std::to_string(TA_VANHOVE_MAX_LAGS));
-    if (n_bins < 1 || n_bins > TA_VANHOVE_MAX_BINS)
-        return fail(owner, TA_E_INVALID, "vanhove: n_bins must be 1 ... " + std::to_string(TA_VANHOVE_MAX_BINS));
-    if (!(dr - dr == 0.0) || !(dr > 0.0)) return fail(owner, TA_E_INVALID, "vanhove: dr must be finite and > 0");
+    if (const int rc = check_vanhove_grid(fail, owner, "vanhove: ", n_lags, h_lags, n_bins, dr)) return rc;
     if (!any_output) return fail(owner, TA_E_INVALID, "vanhove: the counts and moments outputs are both NULL");
-    for (int l = 0; l < n_lags; ++l) {
-        if (h_lags[l] < 0 || (T > 0 && h_lags[l] >= T))
-            return fail(owner, TA_E_INVALID, "vanhove: lag " + std::to_string(h_lags[l]) + " is outside 0 ... n_frames - 1");
-        if (l && h_lags[l] <= h_lags[l - 1]) return fail(owner, TA_E_INVALID, "vanhove: the lags must be strictly increasing");
-    }
-    return TA_OK;
+    return check_vanhove_lags(fail, owner, "vanhove: ", n_lags, h_lags, T);
 }
 // api.hip, for group.hip: one context's ta_vanhove share (its staged slab 0, the call's lags and bins, checked by the
 // caller), queued: *d_out = counts (n_lags, n_bins + 1) int64, then moments (n_lags, 2) float64 -- the ones asked for are

@@ -35,14 +35,6 @@ constexpr size_t vh_lds_bytes(int B, int Lc) {
     return sizeof(double) * (size_t)(B + 1) + (size_t)Lc * (sizeof(double) * 2 * kVhWaves + sizeof(unsigned) * (size_t)(B + 1));
 }
 
-// row r (one frame, 8 bytes per pair) of a float32 atom's pairs: what a lagged row at an odd lag needs
-template <int D>
-__device__ __forceinline__ void vh_row32(const PmAtom<float, D>& a, long r, double (&out)[3]) {
-    const float2* p = reinterpret_cast<const float2*>(a.src);
-    const float2 qa = p[r], qb = D == 3 ? p[2 * a.next + r] : qa;
-    pm_pick<D>(qa.x, qa.y, qb.x, qb.y, a.odd, out);
-}
-
 // LDS bins (uint32) of the chunk's lags into the uint64 histogram, and cleared (callers: between two barriers)
 __device__ __forceinline__ void vh_flush(unsigned* hist, int n, unsigned long long* __restrict__ counts) {
     for (int i = threadIdx.x; i < n; i += kPmThreads) {
@@ -119,7 +111,7 @@ __global__ void __launch_bounds__(kPmThreads)
                 for (int f = 0; f < F; ++f) {
                     const long t2 = pm_frame<true>(tb, f) + tau;
                     double lo[3];
-                    vh_row32<D>(a, t2 < T ? t2 : 0, lo);
+                    a.row32(t2 < T ? t2 : 0, lo);
                     tally(t2 < T, col[f], lo);
                 }
             }

@@ -45,13 +45,11 @@ static_assert((long)kVhdTA * kVhdTB < (1L << 31), "a workgroup's pair count must
 static_assert(kVhdTA == VHD_TILE_A && kVhdTB == VHD_TILE_B, "ta_internal.hpp pads the item pitches to these tiles");
 
 // row t (one frame) of an atom's columns, in the slab's element type: a float64 row is PmAtom's 16-byte load, a float32
-// row one 8-byte load per source pair (PmAtom's 16-byte float32 load would take row t + 1 along)
+// row PmAtom's 8-byte one (its 16-byte float32 load would take row t + 1 along)
 template <class E, int D>
 __device__ __forceinline__ void vhd_row(const PmAtom<E, D>& a, long t, double (&out)[3]) {
     if constexpr (PmAtom<E, D>::kF32) {
-        const float2* p = reinterpret_cast<const float2*>(a.src);
-        const float2 qa = p[t], qb = D == 3 ? p[2 * a.next + t] : qa;
-        pm_pick<D>(qa.x, qa.y, qb.x, qb.y, a.odd, out);
+        a.row32(t, out);
     } else {
         double unused[3];
         a.load(t, out, unused);

@@ -50,7 +50,55 @@ def _check_lags(lags, n_frames=None):
     return lg
 
 
-class VanHoveSelf(CollectiveAnalysis):
+class _VanHove(CollectiveAnalysis):
+    """What ``VanHoveSelf`` and ``VanHoveDistinct`` share: the bins, the lags and the grid half of the results."""
+
+    _no_data_message = "Van Hove function computation requires positions in the trajectory"
+    _updating_message = "UpdatingAtomGroups are not valid for van Hove function computation"
+
+    def __init__(self, atomgroup, lags, r_max, n_bins, dim_type, unwrap, kwargs):
+        super().__init__(atomgroup, None, dim_type, None, False, unwrap, kwargs)
+        self.r_max, self.n_bins = float(r_max), int(n_bins)
+        if not np.isfinite(self.r_max) or not self.r_max > 0:
+            raise ValueError(f"r_max must be finite and > 0, got {r_max}")
+        if not 1 <= self.n_bins <= MAX_BINS:
+            raise ValueError(f"n_bins must be 1 ... {MAX_BINS}, got {n_bins}")
+        self.dr = self.r_max / self.n_bins
+        self.lags = None if lags is None else _check_lags(lags)
+
+    def _set_options(self, dtype):
+        # float32 staging stays float32 on the device: the kernels read it as it is (the unwrap pass works on float64 slabs)
+        self._ctx.set_option("stage_device_f32", int(dtype == np.float32 and not self._unwrap))
+
+    @staticmethod
+    def _has_data(ts):
+        return ts.has_positions
+
+    def _prepare(self):
+        # (before the slabs are allocated: the number of analysed frames is known here, the trajectory is not read yet)
+        self._lags = self._default_lags() if self.lags is None else _check_lags(self.lags, self.n_frames)
+        super()._prepare()
+        for key in self._result_keys:
+            setattr(self.results, key, None)
+
+    def _correlate(self, fft, sums):
+        return None  # the sums are the result: there is no correlation step
+
+    def _store_grid(self, counts):
+        """lags, times, bin_edges, r, counts and overflow of the (L, B + 1) int64 ``counts``; returns the (B,) measures
+        of the shells between the edges (4 pi / 3 (r+^3 - r-^3), pi (r+^2 - r-^2), 2 dr for d = 3, 2, 1)"""
+        r = self.results
+        B, dr = self.n_bins, self.dr
+        r.lags = self._lags
+        r.times = self._lags * (float(self.times[1] - self.times[0]) if self.n_frames > 1 else 0.0)
+        r.bin_edges = np.arange(B + 1) * dr
+        r.r = 0.5 * (r.bin_edges[1:] + r.bin_edges[:-1])
+        r.counts, r.overflow = np.ascontiguousarray(counts[:, :B]), counts[:, B].copy()
+        lo, hi = r.bin_edges[:-1], r.bin_edges[1:]
+        return {3: 4.0 * np.pi / 3.0 * (hi ** 3 - lo ** 3), 2: np.pi * (hi ** 2 - lo ** 2), 1: np.full(B, 2.0 * dr)}[self.dim_fac]
+
+
+class VanHoveSelf(_VanHove):
     r"""Self van Hove function and non-Gaussian parameter of a group of atoms (or of molecules' centres).
 
     .. math:: G_s(r, \tau) = \frac{1}{N (T - \tau)} \sum_{t < T - \tau} \sum_n
@@ -85,37 +133,18 @@ class VanHoveSelf(CollectiveAnalysis):
 
     _accepts_compound = True
     _record_volumes = False
-    _no_data_message = "Van Hove function computation requires positions in the trajectory"
-    _updating_message = "UpdatingAtomGroups are not valid for van Hove function computation"
     _by_particle_message = ("VanHoveSelf has no per-particle result: the histograms are sums over all atoms "
                             "(by_particle=True is not supported)")
+    _result_keys = ("lags", "times", "bin_edges", "r", "counts", "overflow", "prob", "gs", "msd", "r4", "alpha2")
 
     def __init__(self, atomgroup, lags=None, *, r_max, n_bins=200, dim_type="xyz", unwrap=False, **kwargs):
-        super().__init__(atomgroup, None, dim_type, None, False, unwrap, kwargs)
-        self.r_max, self.n_bins = float(r_max), int(n_bins)
-        if not np.isfinite(self.r_max) or not self.r_max > 0:
-            raise ValueError(f"r_max must be finite and > 0, got {r_max}")
-        if not 1 <= self.n_bins <= MAX_BINS:
-            raise ValueError(f"n_bins must be 1 ... {MAX_BINS}, got {n_bins}")
-        self.dr = self.r_max / self.n_bins
-        self.lags = None if lags is None else _check_lags(lags)
+        super().__init__(atomgroup, lags, r_max, n_bins, dim_type, unwrap, kwargs)
 
-    def _set_options(self, dtype):
-        # float32 staging stays float32 on the device: k_vanhove reads it as it is (the unwrap pass works on float64 slabs)
-        self._ctx.set_option("stage_device_f32", int(dtype == np.float32 and not self._unwrap))
-
-    @staticmethod
-    def _has_data(ts):
-        return ts.has_positions
-
-    def _prepare(self):
-        # (before the slabs are allocated: the number of analysed frames is known here, the trajectory is not read yet)
-        self._lags = log_lags(self.n_frames) if self.lags is None else _check_lags(self.lags, self.n_frames)
-        if self._lags.size == 0:
+    def _default_lags(self):
+        lags = log_lags(self.n_frames)
+        if lags.size == 0:
             raise ValueError(f"lags=None needs at least two analysed frames, got {self.n_frames}")
-        super()._prepare()
-        for key in ("lags", "times", "bin_edges", "r", "counts", "overflow", "prob", "gs", "msd", "r4", "alpha2"):
-            setattr(self.results, key, None)
+        return lags
 
     def _moments(self, fft, lo, hi, correlate):
         return self._ctx.vanhove(self._lags, self.n_bins, self.dr), None
@@ -124,25 +153,14 @@ class VanHoveSelf(CollectiveAnalysis):
         L = self._lags.size
         return np.zeros((L, self.n_bins + 1)), np.zeros((L, 2))
 
-    def _correlate(self, fft, sums):
-        return None  # the sums are the result: there is no correlation step
-
     def _store(self, sums, _):
         # (under distributed=True the counts have travelled as float64 through the all-reduce: integers below 2^53 are
         # exact there, and a count is at most N T, far below that)
-        counts = np.rint(sums[0]).astype(np.int64)
+        shell = self._store_grid(np.rint(sums[0]).astype(np.int64))
         moments = np.asarray(sums[1], dtype=np.float64)
-        r = self.results
-        d, B, dr = self.dim_fac, self.n_bins, self.dr
+        r, d = self.results, self.dim_fac
         n_pairs = (float(self.n_particles) * (self.n_frames - self._lags)).astype(np.float64)
-        r.lags = self._lags
-        r.times = self._lags * (float(self.times[1] - self.times[0]) if self.n_frames > 1 else 0.0)
-        r.bin_edges = np.arange(B + 1) * dr
-        r.r = 0.5 * (r.bin_edges[1:] + r.bin_edges[:-1])
-        r.counts, r.overflow = np.ascontiguousarray(counts[:, :B]), counts[:, B].copy()
-        lo, hi = r.bin_edges[:-1], r.bin_edges[1:]
-        shell = {3: 4.0 * np.pi / 3.0 * (hi ** 3 - lo ** 3), 2: np.pi * (hi ** 2 - lo ** 2), 1: np.full(B, 2.0 * dr)}[d]
-        r.prob = r.counts / (n_pairs[:, None] * dr)
+        r.prob = r.counts / (n_pairs[:, None] * self.dr)
         r.gs = r.counts / (n_pairs[:, None] * shell[None, :])
         r.msd, r.r4 = moments[:, 0] / n_pairs, moments[:, 1] / n_pairs
         with np.errstate(divide="ignore", invalid="ignore"):

@@ -14,8 +14,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._base import CollectiveAnalysis, UpdatingAtomGroup
-from .vanhove import MAX_BINS, _check_lags, log_lags
+from ._base import UpdatingAtomGroup
+from .vanhove import _VanHove, log_lags
 
 
 def _sorted_ix(group, name):
@@ -31,7 +31,7 @@ def _sorted_ix(group, name):
     return out
 
 
-class VanHoveDistinct(CollectiveAnalysis):
+class VanHoveDistinct(_VanHove):
     r"""Distinct van Hove function between two groups of atoms, with g(r) and the coordination number.
 
     .. math:: G_d(r, \tau) = \frac{1}{N_a\, n_\mathrm{orig}} \sum_{t_0} \sum_{p \in a} \sum_{q \in b,\, q \ne p}
@@ -68,10 +68,9 @@ class VanHoveDistinct(CollectiveAnalysis):
 
     _accepts_compound = False
     _record_volumes = True
-    _no_data_message = "Van Hove function computation requires positions in the trajectory"
-    _updating_message = "UpdatingAtomGroups are not valid for van Hove function computation"
     _by_particle_message = ("VanHoveDistinct has no per-particle result: the histograms are sums over all pairs "
                             "(by_particle=True is not supported)")
+    _result_keys = ("lags", "times", "bin_edges", "r", "counts", "overflow", "n_origins", "gd", "g", "rdf", "coordination")
 
     def __init__(self, atomgroup, atomgroup_b=None, lags=(0,), *, r_max, n_bins=200, origin_stride=1, periodic=True,
                  dim_type="xyz", **kwargs):
@@ -102,40 +101,22 @@ class VanHoveDistinct(CollectiveAnalysis):
         # (the group itself where it already is the sorted union: its frames are then read without a gather)
         own = np.asarray(atomgroup.ix if hasattr(atomgroup, "ix") else atomgroup.indices)
         staged = atomgroup if np.array_equal(union, own) else atomgroup.universe.atoms[union]
-        super().__init__(staged, None, dim_type, None, False, False, kwargs)
+        super().__init__(staged, lags, r_max, n_bins, dim_type, False, kwargs)
         self.group_a, self.group_b = atomgroup, atomgroup if same else atomgroup_b
         self._idx_a, self._idx_b = np.searchsorted(union, ix_a), np.searchsorted(union, ix_b)
         self.n_a, self.n_b = int(ix_a.size), int(ix_b.size)
         self.n_common = int(np.intersect1d(ix_a, ix_b).size)
-        self.r_max, self.n_bins = float(r_max), int(n_bins)
-        if not np.isfinite(self.r_max) or not self.r_max > 0:
-            raise ValueError(f"r_max must be finite and > 0, got {r_max}")
-        if not 1 <= self.n_bins <= MAX_BINS:
-            raise ValueError(f"n_bins must be 1 ... {MAX_BINS}, got {n_bins}")
-        self.dr = self.r_max / self.n_bins
         self.origin_stride = int(origin_stride)
         if self.origin_stride < 1:
             raise ValueError(f"origin_stride must be >= 1, got {origin_stride}")
         self.periodic = bool(periodic)
-        self.lags = None if lags is None else _check_lags(lags)
 
-    def _set_options(self, dtype):
-        # float32 staging stays float32 on the device: k_vhd_gather reads it as it is
-        self._ctx.set_option("stage_device_f32", int(dtype == np.float32))
-
-    @staticmethod
-    def _has_data(ts):
-        return ts.has_positions
+    def _default_lags(self):
+        return np.concatenate([np.zeros(1, dtype=np.int64), log_lags(self.n_frames)])
 
     def _prepare(self):
-        if self.lags is None:
-            self._lags = np.concatenate([np.zeros(1, dtype=np.int64), log_lags(self.n_frames)])
-        else:
-            self._lags = _check_lags(self.lags, self.n_frames)
         super()._prepare()
         self._pair_boxes = np.zeros((self.n_frames, 6)) if self.periodic else None
-        for key in ("lags", "times", "bin_edges", "r", "counts", "overflow", "n_origins", "gd", "g", "rdf", "coordination"):
-            setattr(self.results, key, None)
 
     def _single_frame(self):
         if self._pair_boxes is not None:
@@ -163,21 +144,10 @@ class VanHoveDistinct(CollectiveAnalysis):
     def _no_moments(self):
         return (np.zeros((self._lags.size, self.n_bins + 1)),)
 
-    def _correlate(self, fft, sums):
-        return None  # the counts are the result: there is no correlation step
-
     def _store(self, sums, _):
-        counts = np.asarray(sums[0], dtype=np.int64)
-        r = self.results
-        d, B, dr = self.dim_fac, self.n_bins, self.dr
-        r.lags = self._lags
-        r.times = self._lags * (float(self.times[1] - self.times[0]) if self.n_frames > 1 else 0.0)
-        r.bin_edges = np.arange(B + 1) * dr
-        r.r = 0.5 * (r.bin_edges[1:] + r.bin_edges[:-1])
-        r.counts, r.overflow = np.ascontiguousarray(counts[:, :B]), counts[:, B].copy()
+        shell = self._store_grid(np.asarray(sums[0], dtype=np.int64))
+        r, d = self.results, self.dim_fac
         r.n_origins = -(-(self.n_frames - self._lags) // self.origin_stride)
-        lo, hi = r.bin_edges[:-1], r.bin_edges[1:]
-        shell = {3: 4.0 * np.pi / 3.0 * (hi ** 3 - lo ** 3), 2: np.pi * (hi ** 2 - lo ** 2), 1: np.full(B, 2.0 * dr)}[d]
         norm = r.n_origins.astype(np.float64)[:, None] * float(self.n_a)
         r.gd = r.counts / (norm * shell[None, :])
         if not self.periodic:
