@@ -327,6 +327,48 @@ int ta_species_self(ta_ctx *ctx, int quantity, int fft, int n_species, const int
 int ta_scatter(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, double *h_self, double *h_density, double *h_coll);
 int ta_scatter_collective(ta_ctx *ctx, int fft, const double *h_density, int n_k, int64_t n_frames, double *h_coll);
 
+/* ta_kcurrent : the longitudinal and transverse current correlation functions (CurrentCorrelation) of n_k wavevectors
+ *              h_kvecs (n_k, dim), rad per length unit, one component per staged column.  Slab 0 holds the velocities v,
+ *              slab 1 the positions x (ta_helfand_msd's convention); h_weights: one weight per atom (mass, charge), or
+ *              NULL (all 1).  With T frames, D staged columns:
+ *                phi_j[t, n]        = sum_d k_j[d] x[t, n, d]
+ *                current[j, t, d]   = ( sum_n w_n v[t, n, d] cos phi_j[t, n],  sum_n w_n v[t, n, d] sin phi_j[t, n] )   (n_k, T, D, 2)
+ *                k^_j = k_j / |k_j|;  jL[j, t] = sum_d k^_j[d] current[j, t, d]  (complex);
+ *                jT[j, t, d] = current[j, t, d] - k^_j[d] jL[j, t]
+ *                long[j, tau]  = 1/(T - tau) sum_{t < T - tau} Re( conj(jL[j, t]) jL[j, t + tau] )                        (n_k, T)
+ *                trans[j, tau] = 1/(D - 1) 1/(T - tau) sum_{t < T - tau} sum_d Re( conj(jT[j, t, d]) jT[j, t + tau, d] )  (n_k, T)
+ *              (D = 1: trans is zeros).  NOTHING is divided by an atom count.  Each output may be NULL (not computed), not
+ *              all three.  current adds up over atoms -- shards, group members, ranks; long and trans do not: they are
+ *              formed once from the summed current (ta_kcurrent_correlate; needs no staged slab and touches none).
+ *              The pass k_kcurrent reads each atom ONCE per launch from both slabs, in the element type they have (a
+ *              float32 row pair in one 16-byte load, widened in registers), keeps the D complex sums of KC wavevectors
+ *              and F frames per thread in registers over the atoms of its group and writes one partial sum per group;
+ *              k_sum_partials adds the groups in a fixed order (no atomics: the same bits from run to run).  The groups
+ *              depend on the slab and the device only.  Chunking: one launch per KC wavevectors (ta_kcurrent_tile);
+ *              option "kcurrent_chunk" n >= 1 forces min(n, KC).  The results do not depend on it bit for bit.  The partial
+ *              buffer (groups x KC x T x D x 16 bytes, at most 1 GiB) does not depend on n_k; ta_trim releases it.
+ *              Phases as ta_scatter's: q = k / (2 pi), u = sum_d q[d] x[d] (a product, then fma), r = u - rint(u),
+ *              (cos, sin)(2 pi r); w_n v is one product, each sum one fma with the cosine and one with the sine.  With
+ *              U = max |k . x| / (2 pi) and S_d = max_t sum_n |w_n v[t, n, d]| each component of current is within
+ *              S_d (2 pi (D + 2) 2^-53 U + (10 + n_atoms) 2^-53) of the exact sum.  The correlations: the projections
+ *              jL, jT_d (kcurrent_math.hpp) are K (1 + D) pseudo-atoms (D = 1: K) with dim 2 in ONE by-particle evaluation
+ *              of ta_vacf_fft (fft = 1) / ta_vacf_direct (fft = 0), to the library's usual 1e-10 of the trace's scale.
+ *              All outputs NULL, NULL h_kvecs, a non-finite component, a wavevector with |k| = 0 ("use ta_current for
+ *              k = 0"; also one whose |k|^2 under- or overflows float64, which cannot be normalised), fft other than 0 / 1, n_k outside 1 ... TA_SCATTER_MAX_K (checked before anything is written):
+ *              TA_E_INVALID; fewer than two staged slabs: TA_E_STATE; n_atoms * dim must be below 2^31.  CPU backend: the
+ *              same phase arithmetic, a plain sum in atom order, the same projections, its VACF routines.  Timings: the
+ *              main kernel of ta_last_timing / ta_timing_history is the LAST launch of k_kcurrent alone -- with n_k > KC
+ *              one chunk's launch, not the whole pass -- unless an evaluation after it records its own; the time of all
+ *              launches is in ta_kernel_timeline, which names the kernels k_kcurrent, k_sum_partials,
+ *              k_kcurrent_project, k_kcurrent_finish.
+ * ta_kcurrent_tile : KC, and the frames per thread F on a float64 / a float32 slab, of the one tile the library ships
+ *              (a workgroup of k_kcurrent covers 256 F frames); each pointer may be NULL.                             */
+int ta_kcurrent(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, const double *h_weights, double *h_current,
+                double *h_long, double *h_trans);
+int ta_kcurrent_correlate(ta_ctx *ctx, int fft, const double *h_current, int n_k, const double *h_kvecs, int64_t n_frames,
+                          int dim, double *h_long, double *h_trans);
+int ta_kcurrent_tile(int *kc, int *frames_f64, int *frames_f32);
+
 /* ta_vanhove : the self part of the van Hove function of the positions in slab 0 (VanHoveSelf): for n_lags frame lags
  *              h_lags (strictly increasing, 0 <= lag < n_frames) the histogram of the displacements after a lag in n_bins
  *              bins of width dr (r_max = n_bins dr) and their second and fourth moments.  With T frames, D staged columns:
@@ -535,6 +577,11 @@ int ta_species_self_staged(ta_ctx *ctx, int quantity, int fft, int n_species, co
 int ta_scatter_staged(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, double *d_self, double *d_density,
                       double *d_coll, void *stream);
 
+/* h_kvecs: HOST wavevectors, d_weights: device weights (n_atoms) or NULL, as ta_conductivity_staged's charges; slab 0 (the
+ * velocities) and slab 1 (the positions) are read in the element type they have; each output may be NULL, not all three */
+int ta_kcurrent_staged(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, const double *d_weights, double *d_current,
+                       double *d_long, double *d_trans, void *stream);
+
 /* h_lags: HOST lags, as for ta_vanhove_dev; slab 0 (the positions) is read in the element type it has */
 int ta_vanhove_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *d_counts,
                       double *d_moments, void *stream);
@@ -619,6 +666,11 @@ int ta_group_species_self(ta_group *g, int quantity, int fft, int n_species, con
  * member that holds atoms.                                                                                          */
 int ta_group_scatter(ta_group *g, int fft, int n_k, const double *h_kvecs, double *h_self, double *h_density,
                      double *h_coll);
+/* ta_group_kcurrent: ta_kcurrent on every member with the same wavevectors (checked first) and its slice of h_weights (all
+ * n_atoms, or NULL): the members' currents are SUMMED on the host in member order, then ONE pair of correlations of the
+ * summed current runs on the first member that holds atoms.                                                          */
+int ta_group_kcurrent(ta_group *g, int fft, int n_k, const double *h_kvecs, const double *h_weights, double *h_current,
+                      double *h_long, double *h_trans);
 /* ta_group_vanhove: ta_vanhove on every member with the same lags and bins (checked first): the members' counts are SUMMED
  * on the host as int64, their moments in member order.                                                               */
 int ta_group_vanhove(ta_group *g, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *h_counts,
@@ -728,6 +780,8 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      (ta_kernel_timeline);
  *   "scatter_chunk" n : wavevectors per pass of ta_scatter* (0, the default: as many as fit 32 GiB of scratch; n >= 1:
  *                      min(n, n_k)); the results do not depend on it;
+ *   "kcurrent_chunk" n : wavevectors per launch of ta_kcurrent*'s pass (0, the default: KC, the tile's count; n >= 1:
+ *                      min(n, KC)); the results do not depend on it;
  *   "vanhove_chunk" n : lags per pass of ta_vanhove* (0, the default: as many as fit 64 KiB of LDS; n >= 1: min(n, n_lags,
  *                      that count)); the results do not depend on it;
  *   "vanhove_distinct_chunk" n : lags per pass of ta_vanhove_distinct* (0, the default: as many as fit 4 GiB of gathered

@@ -1,0 +1,325 @@
+"""The current correlation functions (ta_kcurrent*, CurrentCorrelation) on the CPU backend (Context("cpu"), device="cpu"):
+the long-double reference of kcurrent_ref, the sum rule, closed forms, the argument checks and the class."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import kcurrent_ref as ref
+from transport_analysis_amd import CurrentCorrelation, _lib
+from transport_analysis_amd._mini_mda import ArrayUniverse
+
+TWO_PI = 2.0 * np.pi
+
+
+def cpu_context(x, v, dtype=np.float64):
+    T, A, D = x.shape
+    c = _lib.Context("cpu")
+    vel, pos = c.stage_alloc(T, A, D, n_slabs=2, dtype=dtype)
+    vel[:], pos[:] = v, x
+    c.stage_commit(0, T)
+    return c
+
+
+@pytest.mark.parametrize("fft", [1, 0])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["stage64", "stage32"])
+@pytest.mark.parametrize("D", [1, 2, 3])
+def test_walks_against_reference(D, dtype, fft):
+    for T in (1, 2, 3, 7, 65, 200):
+        for A in (1, 2, 33):
+            for weighted in (True, False):
+                case = ref.case(T, A, D, 3, weighted=weighted)
+                c = cpu_context(case[0], case[1], dtype)
+                try:
+                    cur, lon, tr = c.kcurrent(fft, case[3], case[2])
+                    ref.assert_kcurrent(cur, lon, tr, case, what=f"T={T} A={A} w={weighted}")
+                    only = c.kcurrent(fft, case[3], case[2], longitudinal=False, transverse=False)
+                    assert only[1] is None and only[2] is None and np.array_equal(only[0], cur)
+                    only = c.kcurrent(fft, case[3], case[2], current=False, longitudinal=False)
+                    assert only[0] is None and only[1] is None and np.array_equal(only[2], tr)
+                finally:
+                    c.close()
+
+
+@pytest.mark.parametrize("D", [1, 2, 3])
+def test_sum_rule(D):
+    """long[., 0] + (D - 1) trans[., 0] = 1/T sum_t |current|^2: the projections split the current, they lose nothing"""
+    case = ref.case(65, 33, D, 3)
+    c = cpu_context(case[0], case[1])
+    try:
+        for fft in (0, 1):
+            cur, lon, tr = c.kcurrent(fft, case[3], case[2])
+            want = (cur.astype(ref.LD) ** 2).sum(axis=(2, 3)).mean(axis=1)
+            got = lon[:, 0] + (D - 1) * tr[:, 0]
+            err = float(np.max(np.abs(got - want) / want))
+            print(f"    D={D} fft={fft} sum rule: {err:.3e}")
+            assert err <= 1e-10
+    finally:
+        c.close()
+
+
+def lattice(n, a):
+    g = np.arange(n) * a
+    return np.stack(np.meshgrid(g, g, g, indexing="ij"), axis=-1).reshape(-1, 3) + 0.25
+
+
+def series(T):
+    """u(t): a sum of two cosines and an offset, on the 1/1024 grid"""
+    t = np.arange(T)
+    return np.rint((0.7 * np.cos(0.3 * t) + 0.2 * np.cos(1.1 * t + 0.4) + 0.1) * 1024) / 1024.0
+
+
+def acf(u):
+    T = u.size
+    return np.array([np.dot(u[:T - k], u[k:]) / (T - k) for k in range(T)])
+
+
+@pytest.mark.parametrize("polarisation", ["transverse", "longitudinal"])
+def test_wave_on_a_static_lattice(polarisation):
+    """A static simple-cubic lattice (4^3 sites, spacing 2) and k = 2 pi / 8 z^, commensurate with it.  The velocity field
+    v_n = u(t) cos(k . x_n) e^ has sum_n cos^2 = N / 2 and sum_n cos sin = 0 over the lattice: the current is (N / 2) u(t) e^,
+    real.  e^ = y^ (transverse): long = 0, trans = (N / 2)^2 acf(u) / (D - 1); e^ = z^ (longitudinal): the converse."""
+    n, a, T, D = 4, 2.0, 40, 3
+    sites = lattice(n, a)
+    N = n ** 3
+    k = np.array([[0.0, 0.0, TWO_PI / (n * a)]])
+    u = series(T)
+    axis = 1 if polarisation == "transverse" else 2
+    x = np.broadcast_to(sites, (T, N, 3)).copy()
+    v = np.zeros((T, N, 3))
+    v[:, :, axis] = u[:, None] * np.cos(sites @ k[0])[None, :]
+    want = (N / 2.0) ** 2 * acf(u)
+    scale = float(np.max(np.abs(want)))
+    c = cpu_context(x, v)
+    try:
+        for fft in (0, 1):
+            cur, lon, tr = c.kcurrent(fft, k)
+            bar = ref.current_bar(x, v, None, k)
+            assert np.max(np.abs(cur[0, :, axis, 0] - (N / 2.0) * u)) <= bar[axis]
+            assert np.max(np.abs(cur[0, :, axis, 1])) <= bar[axis]
+            on, off = (tr * (D - 1), lon) if polarisation == "transverse" else (lon, tr * (D - 1))
+            err_on, err_off = float(np.max(np.abs(on[0] - want))), float(np.max(np.abs(off)))
+            print(f"    {polarisation} fft={fft}: {err_on / scale:.3e}, {err_off / scale:.3e} of {scale:.3e}")
+            assert err_on <= 1e-10 * scale and err_off <= 1e-10 * scale
+    finally:
+        c.close()
+
+
+def test_correlate_of_a_given_current():
+    case = ref.case(65, 33, 3, 3)
+    c = cpu_context(case[0], case[1])
+    other = _lib.Context("cpu")  # nothing staged: none is needed
+    try:
+        for fft in (0, 1):
+            cur, lon, tr = c.kcurrent(fft, case[3], case[2])
+            for ctx in (other, c):
+                lon2, tr2 = ctx.kcurrent_correlate(cur, case[3], fft)
+                assert np.array_equal(lon2, lon) and np.array_equal(tr2, tr)
+        assert c.shape == (65, 33, 3)
+    finally:
+        c.close()
+        other.close()
+
+
+def test_two_shards_add_up():
+    case = ref.case(65, 33, 3, 3)
+    x, v, w, k = case[:4]
+    total = 0.0
+    for lo, hi in ((0, 16), (16, 33)):
+        c = cpu_context(x[:, lo:hi], v[:, lo:hi])
+        try:
+            total = total + c.kcurrent(1, k, w[lo:hi], longitudinal=False, transverse=False)[0]
+        finally:
+            c.close()
+    c = _lib.Context("cpu")
+    try:
+        ref.assert_kcurrent(total, *c.kcurrent_correlate(total, k, 1), case, what="two shards")
+    finally:
+        c.close()
+
+
+def test_error_returns_leave_the_outputs_untouched():
+    L = _lib.lib()
+    case = ref.case(7, 13, 3, 3)
+    k = np.ascontiguousarray(case[3])
+    c = cpu_context(case[0], case[1])
+    one = _lib.Context("cpu")
+    (view,) = one.stage_alloc(7, 13, 3)
+    view[:] = case[0]
+    one.stage_commit(0, 7)
+    empty = _lib.Context("cpu")
+    cur, lon, tr = np.full((3, 7, 3, 2), -7.0), np.full((3, 7), -7.0), np.full((3, 7), -7.0)
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+
+    def fails(ctx, code, match, fft=1, n_k=3, kv=k, outs=(cur, lon, tr)):
+        rc = L.ta_kcurrent(ctx._h, fft, n_k, None if kv is None else p(kv), None, *(None if o is None else p(o) for o in outs))
+        assert rc == code, (rc, L.ta_last_error(ctx._h).decode())
+        assert match in L.ta_last_error(ctx._h).decode(), L.ta_last_error(ctx._h).decode()
+        assert np.all(cur == -7.0) and np.all(lon == -7.0) and np.all(tr == -7.0)
+
+    try:
+        fails(c, -1, "n_k must be 1 ... 4096", n_k=0)
+        fails(c, -1, "n_k must be 1 ... 4096", n_k=4097)
+        bad = k.copy()
+        bad[1] = 0.0
+        fails(c, -1, "wavevector 1 is zero", kv=bad)
+        fails(c, -1, "use ta_current for k = 0", kv=bad)
+        for value in (1e-200, 1e200):  # |k|^2 under- or overflows: no unit vector
+            bad = k.copy()
+            bad[0] = value
+            fails(c, -1, "wavevector 0 is zero, or too small or too large to normalise", kv=bad)
+        for value in (np.inf, np.nan):
+            bad = k.copy()
+            bad[2, 1] = value
+            fails(c, -1, "wavevector 2 has a non-finite component", kv=bad)
+        fails(one, -4, "slabs have not been staged")
+        fails(empty, -4, "slabs have not been staged")
+        fails(c, -1, "outputs are all NULL", outs=(None, None, None))
+        fails(c, -1, "fft must be 0 or 1", fft=2)
+        fails(c, -1, "wavevectors are NULL", kv=None)
+        # ta_kcurrent_correlate
+        good = np.zeros((3, 7, 3, 2))
+
+        def corr_fails(code, match, fft=1, current=good, n_k=3, kv=k, T=7, D=3):
+            rc = L.ta_kcurrent_correlate(c._h, fft, None if current is None else p(current), n_k, p(kv), T, D, p(lon), p(tr))
+            assert rc == code and match in L.ta_last_error(c._h).decode(), (rc, L.ta_last_error(c._h).decode())
+            assert np.all(lon == -7.0) and np.all(tr == -7.0)
+
+        corr_fails(-1, "current is NULL", current=None)
+        corr_fails(-1, "fft must be 0 or 1", fft=3)
+        corr_fails(-1, "n_k must be", n_k=0)
+        corr_fails(-1, "1 <= dim <= 3", D=4)
+        corr_fails(-1, "1 <= n_frames", T=0)
+        with pytest.raises(ValueError, match="expected \\(n_k, 3\\)"):
+            c.kcurrent(1, np.ones((2, 2)))
+        with pytest.raises(ValueError, match="weights: 5 values for 13 atoms"):
+            c.kcurrent(1, k, np.ones(5))
+        with pytest.raises(_lib.TAError, match="kcurrent_chunk"):
+            c.set_option("kcurrent_chunk", -1)
+        c.set_option("kcurrent_chunk", 2)
+        t = _lib.kcurrent_tile()
+        assert t["KC"] >= 1 and t["F64"] in (1, 2) and t["F32"] == 2
+    finally:
+        for ctx in (c, one, empty):
+            ctx.close()
+
+
+def universe(T=50, A=12, box=None, seed=11):
+    rng = np.random.default_rng(seed)
+    x = np.cumsum(rng.normal(scale=0.2, size=(T, A, 3)), axis=0) + 20
+    v = rng.normal(scale=0.5, size=(T, A, 3))
+    m = rng.uniform(1.0, 16.0, size=A)
+    q = np.where(np.arange(A) % 2 == 0, 1.0, -1.0)
+    kw = {} if box is None else {"dimensions": box}
+    return ArrayUniverse(positions=x, velocities=v, masses=m, charges=q, **kw), x, v, m, q
+
+
+def test_class_normalisation_and_weights():
+    T, A = 50, 12
+    u, x, v, m, q = universe(T, A)
+    k = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.6, 0.8, 0.0]])
+    x32, v32 = x.astype(np.float32).astype(np.float64), v.astype(np.float32).astype(np.float64)
+    lags = ref.lag_sample(T)
+    for weights, w in (("mass", m), ("charge", q), (None, None), (np.arange(A) + 1.0, np.arange(A) + 1.0)):
+        r = CurrentCorrelation(u.atoms, k, weights=weights, device="cpu", fft=False).run()
+        res = r.results
+        assert res.kvectors.shape == (3, 3) and np.allclose(res.k, 1.0) and res.shell is None and res.cl_shell is None
+        assert res.current.shape == (3, T, 3, 2) and res.cl.shape == (T, 3) and res.ct.shape == (T, 3)
+        assert np.array_equal(res.times, np.arange(T) * 1.0)
+        want = ref.current_of(x32, v32, w, k)
+        assert np.all(np.max(np.abs(res.current - want), axis=(0, 1, 3)) <= ref.current_bar(x32, v32, w, k))
+        lon, tr = ref.correlations_at(res.current, k, lags)
+        scale = float(np.max(np.abs(lon + 2 * tr)))
+        assert np.max(np.abs(res.cl[lags].T * A - lon)) <= 1e-10 * scale  # cl = long / N
+        assert np.max(np.abs(res.ct[lags].T * A - tr)) <= 1e-10 * scale
+    fast = CurrentCorrelation(u.atoms, k, device="cpu", fft=True).run().results
+    slow = CurrentCorrelation(u.atoms, k, device="cpu", fft=False).run().results
+    assert np.max(np.abs(fast.cl - slow.cl)) <= 1e-10 * np.max(np.abs(slow.cl + 2 * slow.ct))
+    planar = CurrentCorrelation(u.atoms, k[:, :2], dim_type="xy", weights=None, device="cpu").run().results
+    assert planar.current.shape == (3, T, 2, 2)
+    line = CurrentCorrelation(u.atoms, [[1.5]], dim_type="z", weights=None, device="cpu").run().results
+    assert not np.any(line.ct) and np.any(line.cl)
+
+
+def test_class_shell_means_and_volume():
+    u, *_ = universe(box=[15, 15, 15, 90, 90, 90])
+    sh = CurrentCorrelation(u.atoms, q=[0.5, 0.9], dq=0.2, max_vectors=4, device="cpu").run().results
+    assert sh.volume == 15.0 ** 3 and set(sh.shell) == {0, 1}
+    for s in (0, 1):
+        pick = sh.shell == s
+        assert np.allclose(sh.cl_shell[:, s], sh.cl[:, pick].mean(axis=1), rtol=0, atol=1e-12 * np.max(np.abs(sh.cl)))
+        assert np.allclose(sh.ct_shell[:, s], sh.ct[:, pick].mean(axis=1), rtol=0, atol=1e-12 * np.max(np.abs(sh.ct)))
+        assert np.isclose(sh.k_shell[s], sh.k[pick].mean())
+
+
+def test_class_wrapped_positions_need_no_unwrap():
+    """wavevectors of the box: the current of the wrapped positions is that of the unwrapped walk; unwrap=True gives it too"""
+    rng = np.random.default_rng(5)
+    box = np.array([16.0, 12.0, 20.0])
+    walk = (np.cumsum(rng.integers(-40, 41, size=(120, 9, 3)), axis=0) + 512) / 64.0
+    wrapped = walk - np.floor(walk / box) * box
+    v = np.rint(rng.normal(scale=512, size=walk.shape)) / 1024.0
+    dims = [*box, 90, 90, 90]
+    runs = [CurrentCorrelation(ArrayUniverse(positions=p, velocities=v, dimensions=dims).atoms, q=[0.9, 1.6], dq=0.4, max_vectors=5,
+                               weights=None, device="cpu", **kw).run()
+            for p, kw in ((walk, {}), (wrapped, {}), (wrapped, {"unwrap": True}))]
+    k = runs[0].results.kvectors
+    assert k.shape[0] >= 6
+    bar = ref.current_bar(walk, v, None, k) + ref.current_bar(wrapped, v, None, k)
+    scale = np.max(np.abs(runs[0].results.cl + 2 * runs[0].results.ct))
+    for other in runs[1:]:
+        assert np.array_equal(k, other.results.kvectors)
+        assert np.all(np.max(np.abs(runs[0].results.current - other.results.current), axis=(0, 1, 3)) <= bar)
+        assert np.max(np.abs(runs[0].results.cl - other.results.cl)) <= 1e-10 * scale
+        assert np.max(np.abs(runs[0].results.ct - other.results.ct)) <= 1e-10 * scale
+
+
+def test_class_spectrum_of_a_pure_cosine():
+    u, *_ = universe(T=64, A=4)
+    r = CurrentCorrelation(u.atoms, np.eye(3), weights=None, device="cpu")
+    with pytest.raises(RuntimeError, match="must be run"):
+        r.spectrum()
+    r.run()
+    T, m0 = 64, 9
+    t = r.lag_times()
+    omega0 = np.pi * m0 / (T * 1.0)
+    r.results.cl = np.stack([np.cos(omega0 * t), np.ones(T), np.zeros(T)], axis=1)
+    r.results.ct = np.stack([np.zeros(T), np.cos(2 * omega0 * t), np.ones(T)], axis=1)
+    for window in ("hann", None):
+        omega, cl_w, ct_w = r.spectrum(window=window)
+        assert omega.shape == (T,) and cl_w.shape == (T, 3) and ct_w.shape == (T, 3)
+        assert np.isclose(omega[m0], omega0) and omega[0] == 0.0
+        assert int(np.argmax(cl_w[:, 0])) == m0 and int(np.argmax(ct_w[:, 1])) == 2 * m0
+        assert int(np.argmax(cl_w[:, 1])) == 0 and not np.any(cl_w[:, 2])
+    with pytest.raises(ValueError, match="window"):
+        r.spectrum(window="boxcar")
+
+
+def test_class_refusals():
+    u, *_ = universe()
+    k = np.eye(3)
+    with pytest.raises(ValueError, match="exactly one of kvectors"):
+        CurrentCorrelation(u.atoms)
+    with pytest.raises(ValueError, match="exactly one of kvectors"):
+        CurrentCorrelation(u.atoms, k, q=1.0, dq=0.1)
+    with pytest.raises(ValueError, match="dq"):
+        CurrentCorrelation(u.atoms, q=1.0)
+    with pytest.raises(TypeError, match="by_particle"):
+        CurrentCorrelation(u.atoms, k, by_particle=True)
+    for key, value in (("compound", "residues"), ("reference_frame", "barycentric"), ("compound_weights", "geometry")):
+        with pytest.raises(TypeError, match=key):
+            CurrentCorrelation(u.atoms, k, **{key: value})
+    with pytest.raises(ValueError, match="expected \\(K, 2\\)"):
+        CurrentCorrelation(u.atoms, k, dim_type="xy")
+    for bad in (np.zeros((1, 3)), np.full((1, 3), 1e-200), np.full((1, 3), 1e200)):
+        with pytest.raises(ValueError, match="none may be zero"):
+            CurrentCorrelation(u.atoms, bad)
+    with pytest.raises(ValueError, match="weights"):
+        CurrentCorrelation(u.atoms, k, weights="momentum")
+    with pytest.raises(ValueError, match="weights: 3 values for 12 atoms"):
+        CurrentCorrelation(u.atoms, k, weights=np.ones(3))
+    with pytest.raises(ValueError, match="needs the periodic box"):
+        CurrentCorrelation(u.atoms, q=1.0, dq=0.2, device="cpu").run()
+    no_vel = ArrayUniverse(positions=np.zeros((5, 2, 3)))
+    with pytest.raises(Exception, match="velocities"):
+        CurrentCorrelation(no_vel.atoms, k, weights=None, device="cpu").run()

@@ -39,6 +39,7 @@ _UNWRAP = _int(_vp, _ci, _vp, _vp)
 _ONSAGER = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, fft, n_species, h_species, h_weights, h_moments, h_cross)
 _SELF = _int(_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, quantity, fft, n_species, h_species, h_weights, h_self, h_counts)
 _SCATTER = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, fft, n_k, h_kvecs, h_self, h_density, h_coll)
+_KCURRENT = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp)  # (handle, fft, n_k, h_kvecs, h_weights, h_current, h_long, h_trans)
 _VANHOVE = _int(_vp, _ci, _vp, _ci, _dbl, _vp, _vp)  # (handle, n_lags, h_lags, n_bins, dr, h_counts, h_moments)
 
 #: every symbol include/ta_hip.h declares -> (result type, argument types): the one table EXPORTS and lib() are made of
@@ -67,6 +68,9 @@ _API = {
     "ta_scatter": _SCATTER, "ta_scatter_collective": _int(_vp, _ci, _vp, _ci, _i64, _vp),
     "ta_scatter_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_scatter_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
+    "ta_kcurrent": _KCURRENT, "ta_kcurrent_correlate": _int(_vp, _ci, _vp, _ci, _vp, _i64, _ci, _vp, _vp),
+    "ta_kcurrent_tile": _int(_P(_ci), _P(_ci), _P(_ci)),
+    "ta_kcurrent_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp),
     "ta_vanhove": _VANHOVE, "ta_vanhove_staged": _int(_vp, _ci, _vp, _ci, _dbl, _vp, _vp, _vp),
     "ta_vanhove_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _ci, _dbl, _vp, _vp, _vp),
     # (handle, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr, counts[, stream])
@@ -94,7 +98,7 @@ _API = {
     "ta_group_vacf_fft": _HOST, "ta_group_vacf_direct": _HOST, "ta_group_helfand_msd": _int(_vp, _vp, _dbl, _vp, _vp),
     "ta_group_msd": _int(_vp, _ci, _vp, _vp), "ta_group_conductivity": _COND, "ta_group_unwrap": _UNWRAP,
     "ta_group_onsager": _ONSAGER, "ta_group_current": _ONSAGER, "ta_group_species_self": _SELF,
-    "ta_group_scatter": _SCATTER, "ta_group_vanhove": _VANHOVE,
+    "ta_group_scatter": _SCATTER, "ta_group_kcurrent": _KCURRENT, "ta_group_vanhove": _VANHOVE,
 }
 EXPORTS = tuple(_API)
 
@@ -172,6 +176,14 @@ def fft_plan_info(n_frames):
     if rc != 0:
         return None
     return {"M": m.value, "n_threads": nt.value, "n_stages": ns.value}
+
+
+def kcurrent_tile():
+    """{"KC", "F64", "F32"}: the wavevectors per launch of k_kcurrent and the frames per thread on a float64 / float32
+    slab (a workgroup covers 256 F frames), ta_kcurrent_tile"""
+    kc, f64, f32 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    lib().ta_kcurrent_tile(ctypes.byref(kc), ctypes.byref(f64), ctypes.byref(f32))
+    return {"KC": kc.value, "F64": f64.value, "F32": f32.value}
 
 
 def _ptr(a):
@@ -491,6 +503,20 @@ class _Staged:
         self._call("scatter", int(fft), K, _ptr(k), _ptr(fs), _ptr(rho), _ptr(coll))
         return fs, rho, coll
 
+    def kcurrent(self, fft, kvectors, weights=None, current=True, longitudinal=True, transverse=True):
+        """Current correlation functions of slab 0 (the velocities) and slab 1 (the positions), ta_kcurrent: `kvectors`
+        (n_k, dim) in rad per length unit, `weights` one per staged atom or None (all 1): (current (n_k, n_frames, dim, 2) =
+        sum_n w_n v_n (cos, sin)(k . x_n), long (n_k, n_frames), trans (n_k, n_frames)), None for one not asked for; nothing
+        is divided by the number of atoms.  A group: the members' currents are summed, then ONE correlation runs."""
+        T, _, D = self._staged_shape()
+        k, K = self._kvectors(kvectors, D)
+        w = self._per_atom(weights, np.float64, "weights", "values")
+        cur = np.empty((K, T, D, 2), dtype=np.float64) if current else None
+        lon = np.empty((K, T), dtype=np.float64) if longitudinal else None
+        tr = np.empty((K, T), dtype=np.float64) if transverse else None
+        self._call("kcurrent", int(fft), K, _ptr(k), _ptr(w), _ptr(cur), _ptr(lon), _ptr(tr))
+        return cur, lon, tr
+
     @staticmethod
     def _lags(lags):
         lg = np.ascontiguousarray(lags, dtype=np.int64)
@@ -649,6 +675,20 @@ class Context(_Staged):
         self._call("scatter_collective", int(fft), _ptr(a), K, T, _ptr(c))
         return c
 
+    def kcurrent_correlate(self, current, kvectors, fft):
+        """(long, trans) (n_k, n_frames) of a given (n_k, n_frames, dim, 2) current, e.g. the sum of several shards' currents
+        (ta_kcurrent_correlate): needs no staged slab and leaves the context's slabs as they are."""
+        a = np.ascontiguousarray(current, dtype=np.float64)
+        if a.ndim != 4 or a.shape[3] != 2:
+            raise ValueError(f"current: shape {a.shape}, expected (n_k, n_frames, dim, 2)")
+        K, T, D, _ = a.shape
+        k, n_k = self._kvectors(kvectors, D)
+        if n_k != K:
+            raise ValueError(f"kvectors: {n_k} wavevectors for a current of {K}")
+        lon, tr = np.empty((K, T), dtype=np.float64), np.empty((K, T), dtype=np.float64)
+        self._call("kcurrent_correlate", int(fft), _ptr(a), K, _ptr(k), T, D, _ptr(lon), _ptr(tr))
+        return lon, tr
+
     # -- device-pointer compute (asynchronous) --------------------------
     def vacf_fft_dev(self, d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._call("vacf_fft_dev", d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp or None, ld_bp, stream or None)
@@ -728,6 +768,12 @@ class Context(_Staged):
         """`kvectors`: HOST wavevectors (n_k, dim) (checked by the library before anything is written)"""
         k, K = self._kvectors(kvectors, self._staged_shape()[2])
         self._call("scatter_staged", int(fft), K, _ptr(k), d_self or None, d_density or None, d_coll or None, stream or None)
+
+    def kcurrent_staged(self, fft, kvectors, d_current=0, d_long=0, d_trans=0, d_weights=0, stream=0):
+        """`kvectors`: HOST wavevectors (n_k, dim) (checked by the library before anything is written); d_weights: device"""
+        k, K = self._kvectors(kvectors, self._staged_shape()[2])
+        self._call("kcurrent_staged", int(fft), K, _ptr(k), d_weights or None, d_current or None, d_long or None,
+                   d_trans or None, stream or None)
 
     def vanhove_dev(self, d_pos, n_frames, n_atoms, dim, ld_row, lags, n_bins, dr, d_counts=0, d_moments=0, stream=0):
         """`lags`: HOST frame lags (checked by the library before anything is written); d_counts (n_lags, n_bins + 1) int64"""

@@ -21,6 +21,7 @@
 #include "../../include/ta_hip.h"
 #include "cpu_backend.hpp"
 #include "direct_kernels.hpp"
+#include "kcurrent_math.hpp"
 #include "ta_internal.hpp"
 #include "unwrap_box.hpp"
 #include "vanhove_distinct_math.hpp"
@@ -118,6 +119,7 @@ private:
     X(stage_device_f32, 0, nullptr) /* device slabs hold float32 when nothing wider is coming in */                        \
     X(timeline, 0, nullptr)        /* record the kernel timeline of every compute call (ta_kernel_timeline) */             \
     X(scatter_chunk, 0, opt_check_scatter_chunk) /* wavevectors per pass of ta_scatter* (0: as many as fit kScatterBudget) */ \
+    X(kcurrent_chunk, 0, opt_check_kcurrent_chunk) /* wavevectors per launch of k_kcurrent (0: the tile's own count) */     \
     X(vanhove_chunk, 0, opt_check_vanhove_chunk) /* lags per pass of ta_vanhove* (0: as many as fit a workgroup's LDS) */ \
     X(vanhove_distinct_chunk, 0, opt_check_vanhove_distinct_chunk) /* lags per pass of ta_vanhove_distinct* (0: as many as fit kVhdBudget) */ \
     X(async_commit, 1, opt_flush_commits) /* ta_stage_commit goes through the commit queue; flushed before it changes */   \
@@ -168,6 +170,12 @@ struct ta_ctx {
     DevBuf scatter_z{workspaces, kTrimmed}, scatter_lab{workspaces, kKept};
     DevBuf scatter_work{workspaces, kTrimmed}, scatter_out{workspaces, kKept};
     HostTable scatter_q{workspaces, tables};
+    // current correlation functions (kcurrent_pm): the partial sums of one chunk of wavevectors (trimmed; its size does not
+    // depend on their number), the pair-major slab of the pseudo-atoms jL, jT with their by-particle lag sums (and the current
+    // itself when the caller does not ask for it), the wavevectors in turns with the unit vectors (and a host call's weights)
+    // behind them, the outputs of host-facing calls
+    DevBuf kcur_part{workspaces, kTrimmed}, kcur_work{workspaces, kTrimmed}, kcur_out{workspaces, kKept};
+    HostTable kcur_tab{workspaces, tables};
     // self van Hove function (vanhove_pm): the lags (int64) with the squared edges behind them, the uint64 histogram and
     // the workgroups' moment partials (the scratch: trimmed), the outputs of host-facing calls
     HostTable vh_tab{workspaces, tables};
@@ -903,6 +911,7 @@ struct Slab {
     int64_t pitch, T, A;
     int D;
     hipStream_t st;
+    const void* pm1 = nullptr;  // staged slab 1 where there is one (the positions behind slab 0's velocities)
 };
 // the frame-major device input of a *_dev entry
 struct DevSrc {
@@ -935,6 +944,7 @@ int slab_entry(ta_ctx* ctx, const DevSrc* dev, void* stream, Args&& args, Pre&& 
     hipStream_t st = (hipStream_t)stream;  // NULL = the legacy default stream, as for any HIP call
     Slab s = dev ? Slab{nullptr, false, pm_pitch(dev->T), dev->T, dev->A, dev->D, st}
                  : Slab{ctx->d_slabs[0], ctx->st_dev_f32, ctx->st_pitch, ctx->st_T, ctx->st_A, ctx->st_D, st};
+    if (!dev && ctx->st_nslabs > 1) s.pm1 = ctx->d_slabs[1];
     TA_CHECK(pre(s));
     if (!dev) TA_CHECK(order_after_staging(ctx, st));
     TA_CHECK(call_begin(ctx, st));
@@ -1220,6 +1230,94 @@ int scatter_pm(ta_ctx* ctx, bool fft, const Slab& slab, int K, double* d_self, d
         }
     }
     if (d_coll) TA_CHECK(scatter_collective(ctx, fft, rho, K, T, d_coll, st));
+    return call_end(ctx, st);
+}
+
+// ---- current correlation functions (kcurrent.hip) -------------------------------------------------------------------
+// The budget of k_kcurrent's partial-sum buffer: G KC pitch D 16 bytes bound its atom groups G.  A choice, not a
+// measurement: the headline shape (10000 x 100000 x 3) asks for ~100 groups = 0.2 GB next to its 48 GB of slabs; the cap
+// bites only for trajectories of a million frames, where one group per frame block still has every atom to itself.
+constexpr size_t kKcurBudget = (size_t)1 << 30;
+
+// the family's argument checks (GPU and CPU contexts, one set of messages): both slabs staged and their columns ...
+int kcurrent_slabs(ta_ctx* ctx) {
+    TA_CHECK(check_staged(ctx, 2));
+    if (ctx->st_A * ctx->st_D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "kcurrent: n_atoms * dim must be below 2^31");
+    return TA_OK;
+}
+// ... behind the wavevectors and outputs
+int kcurrent_args(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, const void* o_current, const void* o_long,
+                  const void* o_trans) {
+    TA_CHECK(check_kcurrent(fail, ctx, fft, n_k, h_kvecs, ctx->st_nslabs ? ctx->st_D : 0, o_current || o_long || o_trans));
+    return kcurrent_slabs(ctx);
+}
+
+// bytes of kcur_work for K wavevectors of T frames: the pair-major pseudo-atoms, their (T, K S) by-particle lag sums and the
+// lag sum, then (own_current) the current itself
+size_t kcurrent_work_bytes(int64_t T, int K, int D, bool own_current) {
+    const size_t P = (size_t)K * kcur_series(D);
+    return pm_bytes(T, 2 * (int64_t)P) + sizeof(double) * ((size_t)T * P + (size_t)T + (own_current ? (size_t)K * T * D * 2 : 0));
+}
+
+// The host half of one call, before it is opened: ONE table -- the wavevectors in turns (q = k / 2 pi), the unit vectors
+// behind them, then a host-facing call's weights (n_w of them) -- queued for upload on `st`.  Nothing on the device has
+// been written when this fails.
+int kcurrent_plan(ta_ctx* ctx, int K, const double* h_kvecs, int D, const double* h_w, int64_t n_w, hipStream_t st) {
+    const size_t n = (size_t)K * D;
+    void* h = nullptr;
+    TA_CHECK(ctx->kcur_tab.begin(ctx, sizeof(double) * (2 * n + (h_w ? (size_t)n_w : 0)), &h));
+    double* q = (double*)h;
+    for (size_t i = 0; i < n; ++i) q[i] = h_kvecs[i] / 6.283185307179586476925;
+    for (int j = 0; j < K; ++j) kcur_khat(D, h_kvecs + (size_t)j * D, q + n + (size_t)j * D);
+    if (h_w) memcpy(q + 2 * n, h_w, sizeof(double) * (size_t)n_w);
+    return ctx->kcur_tab.send(ctx, st);
+}
+
+// long (K, T) and trans (K, T) of the current (K, T, D, 2) at d_current (either output may be NULL): the projections jL, jT_d
+// as a pair-major slab of K S pseudo-atoms with D = 2 (S = 1 + D; D = 1: 1), ONE by-particle autocorrelation of it by the
+// VACF's dispatch, then the pass that transposes, adds the D transverse series and divides by D - 1.  kcur_work is ensured by
+// the caller, the unit vectors are in kcur_tab (kcurrent_plan).
+int kcurrent_correlation(ta_ctx* ctx, bool fft, const double* d_current, int K, int64_t T, int D, double* d_long, double* d_trans,
+                         hipStream_t st) {
+    const int64_t pitch = pm_pitch(T), P = (int64_t)K * kcur_series(D);
+    double* pm = (double*)ctx->kcur_work.p;
+    double* bp = (double*)((char*)pm + pm_bytes(T, 2 * P));
+    double* lagsum = bp + (size_t)T * P;
+    const double* khat = (const double*)ctx->kcur_tab.dev.p + (size_t)K * D;
+    TA_LAUNCH(ctx, "k_kcurrent_project", st, launch_kcurrent_project(d_current, khat, K, (long)T, D, (long)pitch, pm, st));
+    TA_CHECK(acf_impl(ctx, fft, pm, pitch, T, P, 2, lagsum, bp, P, st));
+    TA_LAUNCH(ctx, "k_kcurrent_finish", st, launch_kcurrent_finish(bp, K, (long)T, D, d_long, d_trans, st));
+    return TA_OK;
+}
+
+// One call on the two pair-major slabs of either element type (slab 0 = velocities, slab 1 = positions), read as they are
+// (the caller has opened the call's bracket, it is closed here; kcurrent_plan has queued the table).  Per chunk of at most
+// KC wavevectors (the kernel's tile; "kcurrent_chunk" n: min(n, KC)) ONE fused pass and the fixed-order sum of its partials
+// into the current; after the last chunk the correlations.  The atom groups depend on the slab and the device only: the
+// same bits for every chunk size.  ev[1] / ev[2] bracket the (last) pass, unless an evaluation after it records its own.
+int kcurrent_pm(ta_ctx* ctx, bool fft, const Slab& s, int K, const double* d_w, double* d_current, double* d_long, double* d_trans) {
+    const int64_t pitch = s.pitch, T = s.T, A = s.A;
+    const int D = s.D;
+    hipStream_t st = s.st;
+    int KC = 1, f64 = 1, f32 = 2;
+    kcurrent_tile(&KC, &f64, &f32);
+    const int Kc = ctx->opt_kcurrent_chunk > 0 ? (int)std::min<int64_t>(ctx->opt_kcurrent_chunk, KC) : KC;
+    const bool corr = d_long || d_trans;
+    const int G = kcurrent_parts(ctx->n_cu, s.f32, (long)pitch, (long)A, D, kKcurBudget);
+    TA_CHECK(ensure(ctx, ctx->kcur_part, (size_t)G * KC * (size_t)T * D * 16));
+    if (corr) TA_CHECK(ensure(ctx, ctx->kcur_work, kcurrent_work_bytes(T, K, D, !d_current)));
+    double* part = (double*)ctx->kcur_part.p;
+    double* cur = d_current ? d_current
+                            : (double*)((char*)ctx->kcur_work.p + kcurrent_work_bytes(T, K, D, false));  // (then corr: kcurrent_args)
+    const double* d_q = (const double*)ctx->kcur_tab.dev.p;
+    const size_t per = (size_t)T * D * 2;  // doubles of one wavevector's current
+    for (int j0 = 0; j0 < K; j0 += Kc) {
+        const int kc = std::min(Kc, K - j0);
+        TA_LAUNCH_MAIN(ctx, "k_kcurrent", st,
+                       launch_kcurrent(s.pm, s.pm1, s.f32, (long)pitch, (long)T, (long)A, D, d_q + (size_t)j0 * D, kc, d_w, part, G, st));
+        TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials(part, G, (long)(kc * per), cur + j0 * per, st));
+    }
+    if (corr) TA_CHECK(kcurrent_correlation(ctx, fft, cur, K, T, D, d_long, d_trans, st));
     return call_end(ctx, st);
 }
 
@@ -1523,6 +1621,9 @@ int opt_set_cpu_threads(ta_ctx* ctx, int64_t value) {
     return TA_OK;
 }
 int opt_flush_commits(ta_ctx* ctx, int64_t) { return ctx->commits.flush(); }
+int opt_check_kcurrent_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "kcurrent_chunk: 0 (the tile's count) or the wavevectors per launch");
+}
 int opt_check_scatter_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "scatter_chunk: 0 (automatic) or the wavevectors per pass");
 }
@@ -2228,6 +2329,18 @@ int ta_scatter_staged(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, doub
     });
 }
 
+// Current correlation functions: slab 0 holds the velocities, slab 1 the positions, both read in the element type they have
+// (never widened); the wavevectors are a HOST array, the weights a device one (or NULL); there is no frame-major entry
+int ta_kcurrent_staged(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, const double* d_weights, double* d_current,
+                       double* d_long, double* d_trans, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    return slab_entry(
+        ctx, nullptr, stream, [&] { return kcurrent_args(ctx, fft, n_k, h_kvecs, d_current, d_long, d_trans); },
+        [&](const Slab& s) { return kcurrent_plan(ctx, n_k, h_kvecs, s.D, nullptr, 0, s.st); },
+        [&](const Slab& s) { return kcurrent_pm(ctx, fft != 0, s, n_k, d_weights, d_current, d_long, d_trans); });
+    });
+}
+
 // Self van Hove function: slab 0 / d_pos holds the positions; the staged slab is read in its own element type (never
 // widened); the lags are a HOST array: they size the launches, and vanhove_plan runs before the call is opened
 static int vanhove_entry(ta_ctx* ctx, const DevSrc* dev, int n_lags, const int64_t* h_lags, int n_bins, double dr,
@@ -2527,9 +2640,9 @@ int coll_launch(ta_ctx* ctx, int kind, int fft, int S, const int32_t* h_species,
 // A correlation of host sums on this context's device, blocking, as a compute call of its own (the *_cross and
 // *_collective entries; a group's ONE evaluation after its members' sums).  Needs no staged slab.  upload(st): the
 // workspaces ensured, the sums queued for upload; body(st): the correlation, inside the call's bracket (no dominant
-// kernel of its own, unless the correlator records one); back(): the one copy to the host.
-template <class Upload, class Body, class Back>
-int host_sums_call(ta_ctx* ctx, Upload&& upload, Body&& body, Back&& back) {
+// kernel of its own, unless the correlator records one); back(), back2(): the one or two copies to the host.
+template <class Upload, class Body>
+int host_sums_run(ta_ctx* ctx, Upload&& upload, Body&& body) {
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     TA_CHECK(ctx->commits.flush());
     hipStream_t st = ctx->stream;
@@ -2538,8 +2651,17 @@ int host_sums_call(ta_ctx* ctx, Upload&& upload, Body&& body, Back&& back) {
     TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
     TA_HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
     TA_CHECK(body(st));
-    TA_CHECK(call_end(ctx, st));
+    return call_end(ctx, st);
+}
+template <class Upload, class Body, class Back>
+int host_sums_call(ta_ctx* ctx, Upload&& upload, Body&& body, Back&& back) {
+    TA_CHECK(host_sums_run(ctx, upload, body));
     return host_finish(ctx, {back()});
+}
+template <class Upload, class Body, class Back, class Back2>
+int host_sums_call(ta_ctx* ctx, Upload&& upload, Body&& body, Back&& back, Back2&& back2) {
+    TA_CHECK(host_sums_run(ctx, upload, body));
+    return host_finish(ctx, {back(), back2()});
 }
 
 // The cross term (T, S, S) of host (S, T, D) sums (ta_onsager_cross, ta_current_cross)
@@ -2639,6 +2761,47 @@ int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int K
         },
         [&](hipStream_t st) { return scatter_collective(ctx, fft != 0, out + KT, K, T, out + 3 * KT, st); },
         [&] { return HostCopy{h_coll, out + 3 * KT, KT}; });
+}
+
+// Current-correlation share of a host-facing call, queued on ctx->stream and not waited for: the table (wavevectors, checked
+// by the caller, and this context's atoms' weights) uploaded, the current (K, T, D, 2), then (correlate) long (K, T) and trans
+// (K, T) left on the device in *d_out
+int kcurrent_launch(ta_ctx* ctx, int fft, int K, const double* h_kvecs, const double* h_w, bool correlate, double** d_out) {
+    double* out = nullptr;
+    TA_CHECK(slab_entry(
+        ctx, nullptr, ctx->stream, [&] { return kcurrent_slabs(ctx); },
+        [&](const Slab& s) -> int {
+            TA_CHECK(kcurrent_plan(ctx, K, h_kvecs, s.D, h_w, s.A, ctx->stream));
+            TA_CHECK(ensure(ctx, ctx->kcur_out, sizeof(double) * (size_t)K * s.T * (2 * s.D + 2)));
+            out = (double*)ctx->kcur_out.p;
+            return TA_OK;
+        },
+        [&](const Slab& s) {
+            const size_t KT = (size_t)K * s.T, n_cur = KT * s.D * 2;
+            const double* d_w = h_w ? (const double*)ctx->kcur_tab.dev.p + 2 * (size_t)K * s.D : nullptr;
+            return kcurrent_pm(ctx, fft != 0, s, K, d_w, out, correlate ? out + n_cur : nullptr, correlate ? out + n_cur + KT : nullptr);
+        }));
+    *d_out = out;
+    return TA_OK;
+}
+
+// long and trans (K, T) of a host (K, T, D, 2) current (ta_kcurrent_correlate)
+int kcurrent_correlate_host(ta_ctx* ctx, int fft, const double* h_current, int K, const double* h_kvecs, int64_t T, int D,
+                            double* h_long, double* h_trans) {
+    const size_t KT = (size_t)K * T, n_cur = KT * D * 2;
+    double* out = nullptr;
+    return host_sums_call(
+        ctx,
+        [&](hipStream_t st) -> int {
+            TA_CHECK(ensure(ctx, ctx->kcur_out, sizeof(double) * KT * (2 * D + 2)));
+            TA_CHECK(ensure(ctx, ctx->kcur_work, kcurrent_work_bytes(T, K, D, false)));
+            TA_CHECK(kcurrent_plan(ctx, K, h_kvecs, D, nullptr, 0, st));
+            out = (double*)ctx->kcur_out.p;
+            TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_current, sizeof(double) * n_cur, hipMemcpyHostToDevice, st));
+            return TA_OK;
+        },
+        [&](hipStream_t st) { return kcurrent_correlation(ctx, fft != 0, out, K, T, D, out + n_cur, out + n_cur + KT, st); },
+        [&] { return HostCopy{h_long, out + n_cur, KT}; }, [&] { return HostCopy{h_trans, out + n_cur + KT, KT}; });
 }
 
 // One context's unwrap of staged slab `slab` (ta_unwrap, ta_group_unwrap), queued on ctx->stream behind the queued commits
@@ -2823,6 +2986,43 @@ int ta_scatter_collective(ta_ctx* ctx, int fft, const double* h_density, int n_k
     if (ctx->is_cpu) return cpu_rc(ctx, ta::cpu::scatter_collective(ctx->cpu_threads, fft != 0, h_density, n_k, n_frames, h_coll));
     return ta::scatter_collective_host(ctx, fft, h_density, n_k, n_frames, h_coll);
     });
+}
+
+int ta_kcurrent(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, const double* h_weights, double* h_current, double* h_long,
+                double* h_trans) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(kcurrent_args(ctx, fft, n_k, h_kvecs, h_current, h_long, h_trans));
+    if (ctx->is_cpu)
+        return cpu_rc(ctx, ta::cpu::kcurrent(cpu_state(ctx), fft != 0, n_k, h_kvecs, h_weights, h_current, h_long, h_trans));
+    double* d_out = nullptr;
+    TA_CHECK(ta::kcurrent_launch(ctx, fft, n_k, h_kvecs, h_weights, h_long || h_trans, &d_out));
+    const size_t KT = (size_t)n_k * (size_t)ctx->st_T, n_cur = KT * (size_t)ctx->st_D * 2;
+    return host_finish(ctx, {{h_current, d_out, n_cur}, {h_long, d_out + n_cur, KT}, {h_trans, d_out + n_cur + KT, KT}});
+    });
+}
+
+int ta_kcurrent_correlate(ta_ctx* ctx, int fft, const double* h_current, int n_k, const double* h_kvecs, int64_t n_frames, int dim,
+                          double* h_long, double* h_trans) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    if (n_frames < 1 || dim < 1 || dim > 3 || n_frames > (int64_t)1 << 30)
+        return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30, 1 <= dim <= 3");
+    if (!h_current) return fail(ctx, TA_E_INVALID, "current is NULL");
+    TA_CHECK(check_kcurrent(fail, ctx, fft, n_k, h_kvecs, dim, h_long || h_trans));
+    if (ctx->is_cpu)
+        return cpu_rc(ctx, ta::cpu::kcurrent_correlate(ctx->cpu_threads, fft != 0, h_current, n_k, h_kvecs, n_frames, dim, h_long, h_trans));
+    return ta::kcurrent_correlate_host(ctx, fft, h_current, n_k, h_kvecs, n_frames, dim, h_long, h_trans);
+    });
+}
+
+int ta_kcurrent_tile(int* kc, int* frames_f64, int* frames_f32) {
+    int a = 0, b = 0, c = 0;
+    ta::kcurrent_tile(&a, &b, &c);
+    if (kc) *kc = a;
+    if (frames_f64) *frames_f64 = b;
+    if (frames_f32) *frames_f32 = c;
+    return TA_OK;
 }
 
 int ta_vanhove(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, double dr, int64_t* h_counts, double* h_moments) {

@@ -39,6 +39,7 @@
 
 #include "../../include/ta_hip.h"
 #include "cpu_backend.hpp"
+#include "kcurrent_math.hpp"
 #include "unwrap_box.hpp"
 #include "vanhove_distinct_math.hpp"
 #include "vanhove_math.hpp"
@@ -599,6 +600,80 @@ int scatter(const State& s, bool fft, int K, const double* kvecs, double* self, 
         }
     }
     return coll ? scatter_collective(s.threads, fft, dens, K, T, coll) : TA_OK;
+}
+
+int kcurrent_correlate(int threads, bool fft, const double* current, int K, const double* kvecs, int64_t T, int D, double* lon,
+                       double* trans) {
+    const int S = kcur_series(D);
+    const int64_t P = (int64_t)K * S;
+    std::vector<double> pm, bp, ts;
+    try {
+        pm.assign((size_t)T * P * 2, 0.0);
+        bp.assign((size_t)T * P, 0.0);
+        ts.assign((size_t)T, 0.0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    for (int j = 0; j < K; ++j) {
+        double kh[3] = {0.0, 0.0, 0.0}, out[8];
+        kcur_khat(D, kvecs + (size_t)j * D, kh);
+        for (int64_t t = 0; t < T; ++t) {
+            kcur_project(D, kh, current + ((size_t)j * T + t) * D * 2, out);
+            for (int c = 0; c < 2 * S; ++c) pm[((size_t)t * P + (size_t)j * S) * 2 + c] = out[c];
+        }
+    }
+    const State v = f64_slab(threads, T, P, 2, pm.data());
+    if (int rc = fft ? vacf_fft(v, ts.data(), bp.data()) : vacf_direct(v, ts.data(), bp.data())) return rc;
+    for (int j = 0; j < K; ++j)
+        for (int64_t t = 0; t < T; ++t) {
+            double l, tr;
+            kcur_finish(D, bp.data() + (size_t)t * P + (size_t)j * S, &l, &tr);
+            if (lon) lon[(size_t)j * T + t] = l;
+            if (trans) trans[(size_t)j * T + t] = tr;
+        }
+    return TA_OK;
+}
+
+int kcurrent(const State& s, bool fft, int K, const double* kvecs, const double* w, double* current, double* lon, double* trans) {
+    const int64_t T = s.T, A = s.A;
+    const int D = s.D;
+    const void *vel = s.slabs[0], *pos = s.slabs[1];
+    const bool f32 = s.dtype == TA_F32;
+    std::vector<double> own;
+    if (!current) {
+        try {
+            own.assign((size_t)K * T * D * 2, 0.0);
+        } catch (const std::bad_alloc&) {
+            return TA_E_NOMEM;
+        }
+    }
+    double* cur = current ? current : own.data();
+    for (int j = 0; j < K; ++j) {
+        double q[3] = {0.0, 0.0, 0.0};
+        for (int d = 0; d < D; ++d) q[d] = kvecs[(size_t)j * D + d] / 6.283185307179586476925;
+#pragma omp parallel for num_threads(s.threads) schedule(static)
+        for (int64_t t = 0; t < T; ++t) {
+            double re[3] = {0.0, 0.0, 0.0}, im[3] = {0.0, 0.0, 0.0};
+            for (int64_t n = 0; n < A; ++n) {
+                const size_t i = ((size_t)t * A + n) * D;
+                double u = q[0] * (f32 ? elem<float>(pos, i) : elem<double>(pos, i));
+                for (int d = 1; d < D; ++d) u = std::fma(q[d], f32 ? elem<float>(pos, i + d) : elem<double>(pos, i + d), u);
+                const double a = 6.283185307179586476925 * (u - std::nearbyint(u));
+                const double c = std::cos(a), sn = std::sin(a);
+                const double wn = w ? w[n] : 1.0;
+                for (int d = 0; d < D; ++d) {
+                    const double wv = wn * (f32 ? elem<float>(vel, i + d) : elem<double>(vel, i + d));
+                    re[d] = std::fma(wv, c, re[d]);
+                    im[d] = std::fma(wv, sn, im[d]);
+                }
+            }
+            for (int d = 0; d < D; ++d) {
+                cur[(((size_t)j * T + t) * D + d) * 2] = re[d];
+                cur[(((size_t)j * T + t) * D + d) * 2 + 1] = im[d];
+            }
+        }
+    }
+    return lon || trans ? kcurrent_correlate(s.threads, fft, cur, K, kvecs, T, D, lon, trans) : TA_OK;
 }
 
 // Atoms in blocks of kVhBlock: OpenMP threads take atoms of a block, each with an int64 histogram of its own and every

@@ -50,6 +50,15 @@ int species_self(const State& s, bool msd_quantity, bool fft, int n_species, con
 int scatter(const State& s, bool fft, int K, const double* kvecs, double* self, double* density, double* coll);
 // coll (K, n_frames): the autocorrelations of the K densities (K, n_frames, 2), ONE by-particle vacf call on them as K atoms of dim 2
 int scatter_collective(int threads, bool fft, const double* density, int K, int64_t n_frames, double* coll);
+// ta_kcurrent: the k-space current of slab 0 (the velocities) and slab 1 (the positions) for K wavevectors kvecs (K, dim), with
+// kcurrent.hip's arithmetic (the phase as scatter(); w_n v by a product, then one fma with the cosine and one with the sine):
+// current (K, n_frames, dim, 2) = the plain sum in atom order (w NULL: all 1), lon / trans (K, n_frames) = kcurrent_correlate
+// of it; each output may be NULL; arguments checked by the caller
+int kcurrent(const State& s, bool fft, int K, const double* kvecs, const double* w, double* current, double* lon, double* trans);
+// lon, trans (K, n_frames) of a current (K, n_frames, dim, 2): kcurrent_math.hpp's projections jL, jT_d as K (1 + dim) atoms
+// of dim 2 (dim = 1: K), ONE by-particle vacf call on them, the transverse series added and divided by dim - 1 (dim = 1: zeros)
+int kcurrent_correlate(int threads, bool fft, const double* current, int K, const double* kvecs, int64_t n_frames, int dim,
+                       double* lon, double* trans);
 // ta_vanhove: the self van Hove histogram of slab 0 (the positions) for L strictly increasing lags, B bins of width dr, with
 // vanhove_math.hpp's arithmetic (r2 by a product, then fma; the squared-edge table; the bin of the definition), as
 // vanhove.hip: counts (L, B + 1) int64 (OpenMP over atoms, a histogram per thread, added at the end), moments (L, 2) = (sum r2,

@@ -700,6 +700,30 @@ int ta_group_scatter(ta_group* g, int fft, int n_k, const double* h_kvecs, doubl
     });
 }
 
+// Current correlation functions: every member's current of its atoms (its slice of the weights) for the same wavevectors,
+// added on the host in member order, then ONE pair of correlations of the summed current on the first member that holds
+// atoms -- the rule of ta_group_conductivity (a current the caller does not ask for is summed into a vector of the call's own)
+int ta_group_kcurrent(ta_group* g, int fft, int n_k, const double* h_kvecs, const double* h_weights, double* h_current,
+                      double* h_long, double* h_trans) {
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
+    TAG_CHECK(check_kcurrent(gfail, g, fft, n_k, h_kvecs, g->T ? g->D : 0, h_current || h_long || h_trans));
+    TAG_CHECK(check_staged(g));
+    const size_t n_cur = (size_t)n_k * g->T * g->D * 2;
+    std::vector<double> own;
+    if (!h_current) own.resize(n_cur);
+    double* cur = h_current ? h_current : own.data();
+    std::vector<int> who;
+    TAG_CHECK(sum_members(g, who, "currents", {{0, n_cur, cur}}, [&](int i, double** d) {
+        return kcurrent_launch(g->ctx[i], fft, n_k, h_kvecs, h_weights ? h_weights + g->lo[i] : nullptr, false, d);
+    }));
+    if (h_long || h_trans)
+        if (const int rc = kcurrent_correlate_host(g->ctx[who[0]], fft, cur, n_k, h_kvecs, g->T, g->D, h_long, h_trans))
+            return mfail(g, who[0], rc);
+    return TA_OK;
+    });
+}
+
 // Self van Hove function: every member's counts and moments of its atoms for the same lags and bins, copied into host
 // vectors of the members' own; then the counts are added as int64 and the moments in member order (both add up over
 // atoms: nothing follows the sums)

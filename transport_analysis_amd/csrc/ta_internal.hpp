@@ -11,6 +11,7 @@
 
 #include "../../include/ta_hip.h"
 #include "fft_engine.hpp"
+#include "kcurrent_math.hpp"
 
 struct ta_ctx;
 
@@ -123,6 +124,33 @@ static int check_kvecs(Fail fail, Owner* owner, int fft, int n_k, const double* 
 // for are valid after host_wait; and the collective part of a host density on the context's device, blocking
 int scatter_launch(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, bool self, bool density, bool coll, double** d_out);
 int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int n_k, int64_t T, double* h_coll);
+// the argument checks of ta_kcurrent* on a context (fail, ctx) or a group (gfail, g): the same messages for both.  D: the
+// components per wavevector (0: not known, nothing staged -- the caller reports that next)
+template <class Fail, class Owner>
+static int check_kcurrent(Fail fail, Owner* owner, int fft, int n_k, const double* h_kvecs, int D, bool any_output) {
+    if (fft != 0 && fft != 1) return fail(owner, TA_E_INVALID, "fft must be 0 or 1");
+    if (!any_output) return fail(owner, TA_E_INVALID, "kcurrent: the current, longitudinal and transverse outputs are all NULL");
+    if (!h_kvecs) return fail(owner, TA_E_INVALID, "wavevectors are NULL");
+    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(owner, TA_E_INVALID, "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
+    for (int j = 0; j < n_k && D > 0; ++j) {
+        for (int d = 0; d < D; ++d) {
+            const double c = h_kvecs[(int64_t)j * D + d];
+            if (!(c - c == 0.0)) return fail(owner, TA_E_INVALID, "wavevector " + std::to_string(j) + " has a non-finite component");
+        }
+        const double n2 = kcur_norm2(D, h_kvecs + (int64_t)j * D);  // (the unit vector divides by its root)
+        if (!(n2 > 0.0) || !(n2 - n2 == 0.0))
+            return fail(owner, TA_E_INVALID, "wavevector " + std::to_string(j) + " is zero, or too small or too large to normalise "
+                                             "(|k|^2 under- or overflows): use ta_current for k = 0");
+    }
+    return TA_OK;
+}
+// api.hip, for group.hip: one context's ta_kcurrent share (its staged slabs 0 and 1, the call's wavevectors, checked by the
+// caller, its atoms' weights h_w or NULL), queued: *d_out = the current (n_k, n_frames, dim, 2), then (correlate) long
+// (n_k, n_frames) and trans (n_k, n_frames), valid after host_wait; and the two correlations of a host current on the
+// context's device, blocking
+int kcurrent_launch(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, const double* h_w, bool correlate, double** d_out);
+int kcurrent_correlate_host(ta_ctx* ctx, int fft, const double* h_current, int n_k, const double* h_kvecs, int64_t T, int D,
+                            double* h_long, double* h_trans);
 // the argument checks the van Hove families share, on a context (fail, ctx) or a group (gfail, g), under the family's
 // message prefix `p`: the lags' array, the counts and the bin width ...
 template <class Fail, class Owner>
@@ -303,6 +331,22 @@ hipError_t launch_compound(int n_cu, const void* x, bool f32, long pitch, long T
 hipError_t launch_phase(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const double* q, int Kc,
                         double* Z, hipStream_t st);
 hipError_t launch_scatter_transpose(const double* bp, long T, long K, double* out, hipStream_t st);
+
+// kcurrent.hip: the k-space current of kc <= KC wavevectors q (kc, D) (device array, turns per length unit) from the pair-major
+// slabs v (velocities) and x (positions) of float64 or (f32) float32 elements, both read as they are, in one pass: partial
+// [n_parts][kc][T][D] (re, im) sums over the atoms g, g + n_parts, ... of w_n v (cos, sin)(2 pi q . x) (written in full;
+// n_parts from kcurrent_parts, which depends on the slab and the device only; k_sum_partials adds them in order); w:
+// (n_atoms,) device weights or NULL (all 1).  kcurrent_tile: KC and the frames per thread on a float64 / float32 slab.
+// project: the pair-major slab (pitch rows per pair, dim 2) of the K kcur_series(D) pseudo-atoms jL, jT_d of a current
+// (K, T, D, 2) with the unit vectors khat (K, D); finish: lon (K, T), trans (K, T) (either may be NULL) from their
+// (T, K kcur_series(D)) by-particle autocorrelations (kcurrent_math.hpp)
+void kcurrent_tile(int* kc, int* frames_f64, int* frames_f32);
+int kcurrent_parts(int n_cu, bool f32, long pitch, long n_atoms, int D, size_t budget);
+hipError_t launch_kcurrent(const void* v, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const double* q,
+                           int kc, const double* w, double* partial, int n_parts, hipStream_t st);
+hipError_t launch_kcurrent_project(const double* current, const double* khat, int K, long T, int D, long pitch, double* pm,
+                                   hipStream_t st);
+hipError_t launch_kcurrent_finish(const double* bp, int K, long T, int D, double* lon, double* trans, hipStream_t st);
 
 // vanhove.hip: the self van Hove histogram of a pair-major slab of float64 or (f32) float32 elements, read as it is, for the
 // lags [l0, l0 + Lc) of L (device array `lags`): counts (L, B + 1) uint64 (zeroed by the caller before the first chunk)

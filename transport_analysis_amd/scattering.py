@@ -86,7 +86,53 @@ def kvectors_from_box(dimensions, q, dq, max_vectors=32, dim_type="xyz"):
     return np.ascontiguousarray(np.concatenate(vecs)), np.concatenate(shells)
 
 
-class IntermediateScattering(CollectiveAnalysis):
+def explicit_kvectors(kvectors, dim_fac, dim_type):
+    """Explicit wavevectors as a C-contiguous float64 (K, dim_fac) array, or the ValueError that says what is wrong."""
+    k = np.ascontiguousarray(kvectors, dtype=np.float64)
+    if k.ndim != 2 or k.shape[0] < 1 or k.shape[1] != dim_fac:
+        raise ValueError(f"kvectors: shape {k.shape}, expected (K, {dim_fac}) for dim_type={dim_type!r}")
+    if not np.all(np.isfinite(k)):
+        raise ValueError("kvectors must be finite")
+    return k
+
+
+def shell_mean(shell, by_kvector):
+    """(n_frames, n_shells): the mean of a (n_frames, K) array over the vectors of every shell"""
+    n_shells = int(shell.max()) + 1
+    counts = np.bincount(shell, minlength=n_shells)
+    out = np.zeros((by_kvector.shape[0], n_shells))
+    np.add.at(out.T, shell, by_kvector.T)
+    return out / counts
+
+
+class BoxWavevectors:
+    """What the k-space classes share: ``kvectors`` used as they are or, with ``q`` / ``dq`` / ``max_vectors``,
+    ``kvectors_from_box`` of the first analysed frame's box, and the shell means.  The class sets ``q``, ``dq``,
+    ``max_vectors``, ``kvectors`` and ``shell`` (``_init_kvectors``) and calls ``_box_kvectors()`` at the top of
+    ``_single_frame``."""
+
+    def _init_kvectors(self, kvectors, q, dq, max_vectors):
+        if (kvectors is None) == (q is None):
+            raise ValueError("exactly one of kvectors (explicit wavevectors) and q (magnitudes, with dq) must be given")
+        if kvectors is None and dq is None:
+            raise ValueError("q needs the shell width dq")
+        self.q, self.dq, self.max_vectors = q, dq, int(max_vectors)
+        self.kvectors = self.shell = None
+        if kvectors is not None:
+            self.kvectors = explicit_kvectors(kvectors, self.dim_fac, self.dim_type)
+
+    def _box_kvectors(self):
+        if self.q is not None and self._frame_index == 0:
+            dims = self._ts.dimensions
+            if dims is None:
+                raise ValueError("q= needs the periodic box of the first analysed frame, and it has none: give kvectors")
+            self.kvectors, self.shell = kvectors_from_box(dims, self.q, self.dq, self.max_vectors, self.dim_type)
+
+    def _shell_mean(self, by_kvector):
+        return shell_mean(self.shell, by_kvector)
+
+
+class IntermediateScattering(BoxWavevectors, CollectiveAnalysis):
     r"""Self and collective intermediate scattering functions of a group of atoms (or of molecules' centres).
 
     .. math:: F_s(\mathbf{k}, \tau) = \frac{1}{N} \frac{1}{T - \tau} \sum_{t < T - \tau} \sum_n
@@ -131,22 +177,11 @@ class IntermediateScattering(CollectiveAnalysis):
 
     def __init__(self, atomgroup, kvectors=None, *, q=None, dq=None, max_vectors=32, dim_type="xyz", fft=True,
                  coherent=True, unwrap=False, **kwargs):
-        if (kvectors is None) == (q is None):
-            raise ValueError("exactly one of kvectors (explicit wavevectors) and q (magnitudes, with dq) must be given")
         super().__init__(atomgroup, None, dim_type, None, fft, unwrap, kwargs)
         self.coherent = bool(coherent)
-        self.q, self.dq, self.max_vectors = q, dq, int(max_vectors)
-        self.kvectors = self.shell = None
-        if kvectors is not None:
-            k = np.ascontiguousarray(kvectors, dtype=np.float64)
-            if k.ndim != 2 or k.shape[0] < 1 or k.shape[1] != self.dim_fac:
-                raise ValueError(f"kvectors: shape {k.shape}, expected (K, {self.dim_fac}) for dim_type={self.dim_type!r}")
-            if not np.all(np.isfinite(k)):
-                raise ValueError("kvectors must be finite")
-            self.kvectors, self.shell = k, np.arange(k.shape[0])
-        else:
-            if dq is None:
-                raise ValueError("q needs the shell width dq")
+        self._init_kvectors(kvectors, q, dq, max_vectors)
+        if self.kvectors is not None:
+            self.shell = np.arange(self.kvectors.shape[0])
 
     def _set_options(self, dtype):
         # float32 staging stays float32 on the device: k_phase reads it as it is (the unwrap pass works on float64 slabs)
@@ -162,11 +197,7 @@ class IntermediateScattering(CollectiveAnalysis):
             setattr(self.results, key, None)
 
     def _single_frame(self):
-        if self.q is not None and self._frame_index == 0:
-            dims = self._ts.dimensions
-            if dims is None:
-                raise ValueError("q= needs the periodic box of the first analysed frame, and it has none: give kvectors")
-            self.kvectors, self.shell = kvectors_from_box(dims, self.q, self.dq, self.max_vectors, self.dim_type)
+        self._box_kvectors()
         super()._single_frame()
 
     def _moments(self, fft, lo, hi, correlate):
@@ -179,13 +210,6 @@ class IntermediateScattering(CollectiveAnalysis):
 
     def _correlate(self, fft, sums):
         return self._ctx.scatter_collective(sums[1], fft) if self.coherent else None
-
-    def _shell_mean(self, by_kvector):
-        n_shells = int(self.shell.max()) + 1
-        counts = np.bincount(self.shell, minlength=n_shells)
-        out = np.zeros((by_kvector.shape[0], n_shells))
-        np.add.at(out.T, self.shell, by_kvector.T)
-        return out / counts
 
     def _store(self, sums, coll):
         N = float(self.n_particles)
