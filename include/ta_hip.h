@@ -400,6 +400,35 @@ int ta_kcurrent_tile(int *kc, int *frames_f64, int *frames_f32);
 #define TA_VANHOVE_MAX_BINS 4096
 int ta_vanhove(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *h_counts, double *h_moments);
 
+/* ta_overlap : the self-overlap of the positions in slab 0 per time origin (DynamicSusceptibility): the sum whose variance
+ *              over origins is the four-point susceptibility chi_4.  With T frames, N atoms, D staged columns, n_lags lags
+ *              under ta_vanhove's rules (strictly increasing, 0 <= tau < T, at most TA_VANHOVE_MAX_LAGS) and n_cutoffs
+ *              cutoffs a_c (finite, > 0, strictly increasing, 1 <= n_cutoffs <= TA_OVERLAP_MAX_CUTOFFS):
+ *                r2      = ta_vanhove's, of x[t0] and x[t0 + tau]: the same order, the same fma's; a float32 slab widened first
+ *                a2[c]   = fl(a_c a_c)                                             float64, formed once on the host
+ *                h_q[(c * n_lags + l) * T + t0] = #{n: r2 < a2[c]}  for t0 < T - tau_l,  0 for t0 >= T - tau_l       int64
+ *              The comparison is strict, as the upper side of ta_vanhove's bins: with a_c = b dr the sum over t0 of
+ *              Q[c, l, :] equals the sum of ta_vanhove's counts[l, b'] over b' < b, exactly.  A NaN r2 is not counted.
+ *              NOTHING is divided; Q adds up over atoms -- shards, group members, ranks -- and a variance over origins is to
+ *              be taken AFTER that sum (Q^2 does not add up), which is why the counts leave this interface per origin.
+ *              A call with n_cutoffs * n_lags * T > 2^27 is refused: the output would pass 1 GiB.  That limit is a choice.
+ *              The pass k_overlap reads the slab in the element type it has, with k_vanhove's reads, once per launch of Lc
+ *              lags: a thread keeps a uint32 counter per (lag, cutoff, origin frame of its own) in registers across its
+ *              atoms and adds the non-zero ones to the zeroed Q by 64-bit integer atomic adds at the end -- integers, so the
+ *              same bits in any order, from run to run and for every Lc.  Lc = floor(S / n_cutoffs) with S the slots of
+ *              the kernel's tile (ta_overlap_tile), at most n_lags; option "overlap_chunk" n >= 1 forces min(n, n_lags,
+ *              that count).  ta_trim releases the output buffer of the host-facing calls.
+ *              NULL h_lags, n_lags outside 1 ... TA_VANHOVE_MAX_LAGS, NULL h_cutoffs, n_cutoffs outside 1 ...
+ *              TA_OVERLAP_MAX_CUTOFFS, a cutoff not finite or <= 0, cutoffs not strictly increasing, a NULL output, a lag
+ *              < 0 or >= n_frames, lags not strictly increasing, the 2^27 bound (all checked before anything is written):
+ *              TA_E_INVALID; nothing staged: TA_E_STATE; n_atoms * dim must be below 2^31.
+ *              CPU backend: the same r2 and a2; OpenMP over the (lag, origin) pairs, each of which one thread counts over
+ *              all atoms: the bits do not depend on the number of threads.  Timings: k_overlap is the main kernel.        */
+#define TA_OVERLAP_MAX_CUTOFFS 4
+int ta_overlap(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_cutoffs, const double *h_cutoffs, int64_t *h_q);
+/* the (lag, cutoff) slots S of one k_overlap launch, a compile-time tile of the library */
+int ta_overlap_tile(int *slots);
+
 /* ta_vanhove_distinct : the distinct part of the van Hove function of the positions in slab 0 (VanHoveDistinct): the
  *              histogram of the distances between item a_p at an origin frame and item b_q a lag later, over ORDERED pairs
  *              of different items.  With T frames, D staged columns:
@@ -551,6 +580,12 @@ int ta_scatter_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n
 int ta_vanhove_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row, int n_lags,
                    const int64_t *h_lags, int n_bins, double dr, int64_t *d_counts, double *d_moments, void *stream);
 
+/* d_pos: frame-major float64 positions; h_lags, h_cutoffs: HOST arrays, as for ta_overlap (they size the launches; checked
+ * before anything is written); d_q (n_cutoffs, n_lags, n_frames) int64: a device array, every element of it written (zeros
+ * at t0 >= n_frames - lag).  Shards' Q add up. */
+int ta_overlap_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row, int n_lags,
+                   const int64_t *h_lags, int n_cutoffs, const double *h_cutoffs, int64_t *d_q, void *stream);
+
 /* ---- compute on the staged (pair-major) slabs, device outputs, asynchronous on `stream` ----
  * Same arithmetic and outputs as the *_dev calls, on the slabs of ta_stage_alloc*: no
  * transposition, no second copy.  d_masses: (n_atoms,) float64 device array.              */
@@ -585,6 +620,10 @@ int ta_kcurrent_staged(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, con
 /* h_lags: HOST lags, as for ta_vanhove_dev; slab 0 (the positions) is read in the element type it has */
 int ta_vanhove_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *d_counts,
                       double *d_moments, void *stream);
+
+/* h_lags, h_cutoffs: HOST arrays, as for ta_overlap_dev; slab 0 (the positions) is read in the element type it has */
+int ta_overlap_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_cutoffs, const double *h_cutoffs, int64_t *d_q,
+                      void *stream);
 
 /* every list and the box: HOST arrays, as for ta_vanhove_distinct (they size the launches; checked before anything is
  * written); d_counts (n_lags, n_bins + 1) int64: a device array; slab 0 is read in the element type it has */
@@ -675,6 +714,9 @@ int ta_group_kcurrent(ta_group *g, int fft, int n_k, const double *h_kvecs, cons
  * on the host as int64, their moments in member order.                                                               */
 int ta_group_vanhove(ta_group *g, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *h_counts,
                      double *h_moments);
+/* ta_group_overlap: ta_overlap on every member with the same lags and cutoffs (checked first): the members' Q are SUMMED on
+ * the host as int64 -- the per-origin counts add up over atoms, their squares do not.                                */
+int ta_group_overlap(ta_group *g, int n_lags, const int64_t *h_lags, int n_cutoffs, const double *h_cutoffs, int64_t *h_q);
 /* ta_group_unwrap: ta_unwrap on every member's block of slab `slab` (declared with ta_unwrap above) */
 int ta_group_unwrap(ta_group *g, int slab, const double *h_dimensions, const int *axes); /* every member's block */
 
@@ -784,6 +826,8 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      min(n, KC)); the results do not depend on it;
  *   "vanhove_chunk" n : lags per pass of ta_vanhove* (0, the default: as many as fit 64 KiB of LDS; n >= 1: min(n, n_lags,
  *                      that count)); the results do not depend on it;
+ *   "overlap_chunk" n : lags per launch of ta_overlap* (0, the default: floor(S / n_cutoffs), S of ta_overlap_tile; n >= 1:
+ *                      min(n, n_lags, that count)); the results do not depend on it;
  *   "vanhove_distinct_chunk" n : lags per pass of ta_vanhove_distinct* (0, the default: as many as fit 4 GiB of gathered
  *                      scratch, at least 1; n >= 1: min(n, n_lags)); the results do not depend on it;
  *   "async_commit" 1|0 : ta_stage_commit hands its frame range to a worker thread of the context, which

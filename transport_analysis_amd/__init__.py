@@ -3,7 +3,8 @@ transport-analysis API (VelocityAutocorr, ViscosityHelfand), MDAnalysis' Einstei
 (velocity) twins, ConductivityGreenKubo and OnsagerGreenKubo, and the intermediate scattering functions F_s(k, t) and F(k, t),
 IntermediateScattering, and their real-space partners, the self van Hove function G_s(r, t) with the non-Gaussian parameter,
 VanHoveSelf, and the distinct van Hove function G_d(r, t) with the radial distribution function g(r), VanHoveDistinct, and
-the longitudinal and transverse current correlation functions C_L(k, t) and C_T(k, t), CurrentCorrelation."""
+the longitudinal and transverse current correlation functions C_L(k, t) and C_T(k, t), CurrentCorrelation, and the
+self-overlap Q(t) with the four-point susceptibility chi_4(t), DynamicSusceptibility."""
 __version__ = "0.1.0"
 
 from .velocityautocorr import VelocityAutocorr  # noqa: F401
@@ -16,3 +17,4 @@ from .scattering import IntermediateScattering, kvectors_from_box  # noqa: F401
 from .current_correlation import CurrentCorrelation  # noqa: F401
 from .vanhove import VanHoveSelf, log_lags  # noqa: F401
 from .vanhove_distinct import VanHoveDistinct  # noqa: F401
+from .susceptibility import DynamicSusceptibility  # noqa: F401

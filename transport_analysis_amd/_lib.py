@@ -41,6 +41,7 @@ _SELF = _int(_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, quantity, fft, 
 _SCATTER = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, fft, n_k, h_kvecs, h_self, h_density, h_coll)
 _KCURRENT = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp)  # (handle, fft, n_k, h_kvecs, h_weights, h_current, h_long, h_trans)
 _VANHOVE = _int(_vp, _ci, _vp, _ci, _dbl, _vp, _vp)  # (handle, n_lags, h_lags, n_bins, dr, h_counts, h_moments)
+_OVERLAP = _int(_vp, _ci, _vp, _ci, _vp, _vp)  # (handle, n_lags, h_lags, n_cutoffs, h_cutoffs, h_q)
 
 #: every symbol include/ta_hip.h declares -> (result type, argument types): the one table EXPORTS and lib() are made of
 _API = {
@@ -73,6 +74,8 @@ _API = {
     "ta_kcurrent_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp),
     "ta_vanhove": _VANHOVE, "ta_vanhove_staged": _int(_vp, _ci, _vp, _ci, _dbl, _vp, _vp, _vp),
     "ta_vanhove_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _ci, _dbl, _vp, _vp, _vp),
+    "ta_overlap": _OVERLAP, "ta_overlap_tile": _int(_P(_ci)), "ta_overlap_staged": _int(_vp, _ci, _vp, _ci, _vp, _vp, _vp),
+    "ta_overlap_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _ci, _vp, _vp, _vp),
     # (handle, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr, counts[, stream])
     "ta_vanhove_distinct": _int(_vp, _ci, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _dbl, _vp),
     "ta_vanhove_distinct_staged": _int(_vp, _ci, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _dbl, _vp, _vp),
@@ -99,6 +102,7 @@ _API = {
     "ta_group_msd": _int(_vp, _ci, _vp, _vp), "ta_group_conductivity": _COND, "ta_group_unwrap": _UNWRAP,
     "ta_group_onsager": _ONSAGER, "ta_group_current": _ONSAGER, "ta_group_species_self": _SELF,
     "ta_group_scatter": _SCATTER, "ta_group_kcurrent": _KCURRENT, "ta_group_vanhove": _VANHOVE,
+    "ta_group_overlap": _OVERLAP,
 }
 EXPORTS = tuple(_API)
 
@@ -184,6 +188,13 @@ def kcurrent_tile():
     kc, f64, f32 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     lib().ta_kcurrent_tile(ctypes.byref(kc), ctypes.byref(f64), ctypes.byref(f32))
     return {"KC": kc.value, "F64": f64.value, "F32": f32.value}
+
+
+def overlap_tile():
+    """the (lag, cutoff) slots of one k_overlap launch: floor(slots / n_cutoffs) lags share a launch, ta_overlap_tile"""
+    slots = ctypes.c_int()
+    lib().ta_overlap_tile(ctypes.byref(slots))
+    return slots.value
 
 
 def _ptr(a):
@@ -536,6 +547,25 @@ class _Staged:
         self._call("vanhove", L, _ptr(lg), n_bins, float(dr), _ptr(cnt), _ptr(mom))
         return cnt, mom
 
+    @staticmethod
+    def _cutoffs(cutoffs):
+        a = np.ascontiguousarray(np.atleast_1d(np.asarray(cutoffs, dtype=np.float64)))
+        if a.ndim != 1:
+            raise ValueError(f"cutoffs: shape {a.shape}, expected a scalar or (n_cutoffs,)")
+        return a, int(a.shape[0])
+
+    def overlap(self, lags, cutoffs):
+        """Self-overlap per time origin of slab 0 (the positions), ta_overlap: for the integer frame `lags` (strictly
+        increasing, below n_frames) and the `cutoffs` a_c (> 0, strictly increasing, at most 4) the int64 array Q (n_cutoffs,
+        n_lags, n_frames) of the atoms with |x(t0 + lag) - x(t0)| < a_c, zeros at t0 >= n_frames - lag; nothing is divided.
+        A group: the members' Q are summed (a variance over origins comes after that sum)."""
+        lg, L = self._lags(lags)
+        a, C = self._cutoffs(cutoffs)
+        T = self.shape[0] if self.shape is not None else 0
+        q = np.empty((C, L, T), dtype=np.int64)
+        self._call("overlap", L, _ptr(lg), C, _ptr(a), _ptr(q))
+        return q
+
     def unwrap(self, slab, dimensions, axes):
         """Undo periodic wrapping of staged slab `slab` in place (MDAnalysis' NoJump, ta_unwrap; a group: on every
         member's block of the slab): `dimensions` the (n_frames, 6) boxes [a, b, c, alpha, beta, gamma] of the staged
@@ -785,6 +815,20 @@ class Context(_Staged):
         """`lags`: HOST frame lags (checked by the library before anything is written); d_counts (n_lags, n_bins + 1) int64"""
         lg, L = self._lags(lags)
         self._call("vanhove_staged", L, _ptr(lg), int(n_bins), float(dr), d_counts or None, d_moments or None, stream or None)
+
+    def overlap_dev(self, d_pos, n_frames, n_atoms, dim, ld_row, lags, cutoffs, d_q, stream=0):
+        """`lags`, `cutoffs`: HOST arrays (checked by the library before anything is written); d_q (n_cutoffs, n_lags,
+        n_frames) int64 on the device"""
+        lg, L = self._lags(lags)
+        a, C = self._cutoffs(cutoffs)
+        self._call("overlap_dev", d_pos, n_frames, n_atoms, dim, ld_row, L, _ptr(lg), C, _ptr(a), d_q or None, stream or None)
+
+    def overlap_staged(self, lags, cutoffs, d_q, stream=0):
+        """`lags`, `cutoffs`: HOST arrays (checked by the library before anything is written); d_q (n_cutoffs, n_lags,
+        n_frames) int64 on the device"""
+        lg, L = self._lags(lags)
+        a, C = self._cutoffs(cutoffs)
+        self._call("overlap_staged", L, _ptr(lg), C, _ptr(a), d_q or None, stream or None)
 
     def _vhd_args(self, lags, origin_stride, idx_a, idx_b, dimensions, axes, n_bins, dr):
         """the argument tuple ta_vanhove_distinct* share, and the arrays it points into (to be kept until the call is over)"""

@@ -121,6 +121,7 @@ private:
     X(scatter_chunk, 0, opt_check_scatter_chunk) /* wavevectors per pass of ta_scatter* (0: as many as fit kScatterBudget) */ \
     X(kcurrent_chunk, 0, opt_check_kcurrent_chunk) /* wavevectors per launch of k_kcurrent (0: the tile's own count) */     \
     X(vanhove_chunk, 0, opt_check_vanhove_chunk) /* lags per pass of ta_vanhove* (0: as many as fit a workgroup's LDS) */ \
+    X(overlap_chunk, 0, opt_check_overlap_chunk) /* lags per launch of ta_overlap* (0: as many as the kernel's tile holds) */ \
     X(vanhove_distinct_chunk, 0, opt_check_vanhove_distinct_chunk) /* lags per pass of ta_vanhove_distinct* (0: as many as fit kVhdBudget) */ \
     X(async_commit, 1, opt_flush_commits) /* ta_stage_commit goes through the commit queue; flushed before it changes */   \
     X(lock_ahead, 1, nullptr)      /* the commit worker page-locks the chunks behind the one it committed */               \
@@ -180,6 +181,10 @@ struct ta_ctx {
     // the workgroups' moment partials (the scratch: trimmed), the outputs of host-facing calls
     HostTable vh_tab{workspaces, tables};
     DevBuf vh_hist{workspaces, kTrimmed}, vh_part{workspaces, kTrimmed}, vh_out{workspaces, kKept};
+    // self-overlap per origin (overlap_pm): the lags (int64) with the squared cutoffs behind them; Q goes straight into the
+    // caller's array, so the only buffer is the output of host-facing calls (up to 1 GiB: trimmed)
+    HostTable ov_tab{workspaces, tables};
+    DevBuf ov_out{workspaces, kTrimmed};
     // distinct van Hove function (vhd_pm): the table (lags, squared edges, box entries, padded index lists), the gathered
     // frame-major scratch GA | GB and the uint64 histogram (trimmed), the output of host-facing calls
     HostTable vhd_tab{workspaces, tables};
@@ -1361,6 +1366,37 @@ int vanhove_pm(ta_ctx* ctx, const Slab& slab, int L, int B, double dr, int64_t* 
     return call_end(ctx, st);
 }
 
+// ---- self-overlap per origin (overlap.hip) --------------------------------------------------------------------------
+// The host half of one call, before it is opened: the lags and the squared cutoffs a2[c] = fl(a_c a_c) (formed once, here)
+// queued for upload on `st` as one table.  Nothing on the device has been written when this fails.
+int overlap_plan(ta_ctx* ctx, int L, const int64_t* h_lags, int C, const double* h_cutoffs, int64_t A, int D, hipStream_t st) {
+    if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "overlap: n_atoms * dim must be below 2^31");
+    void* h = nullptr;
+    TA_CHECK(ctx->ov_tab.begin(ctx, sizeof(double) * ((size_t)L + (size_t)C), &h));
+    static_assert(sizeof(int64_t) == sizeof(double), "the lags travel in the table's first n_lags slots");
+    memcpy(h, h_lags, sizeof(int64_t) * (size_t)L);
+    vh_cutoffs2(C, h_cutoffs, (double*)h + L);
+    return ctx->ov_tab.send(ctx, st);
+}
+
+// One overlap call on a pair-major position slab of either element type, read as it is (the caller has opened the call's
+// bracket, it is closed here; overlap_plan has queued the table).  d_q (C, L, T) is zeroed, then one k_overlap launch per
+// chunk of Lc lags adds its counts: Lc C <= the kernel's slots.  Nothing depends on Lc but which lags share a launch: the
+// same bits for every chunk size.  ev[1] / ev[2] bracket the (last) launch.
+int overlap_pm(ta_ctx* ctx, const Slab& slab, int L, int C, int64_t* d_q) {
+    hipStream_t st = slab.st;
+    const int fit = std::max(1, overlap_slots() / C);
+    const int Lc = (int)std::min<int64_t>({ctx->opt_overlap_chunk > 0 ? ctx->opt_overlap_chunk : (int64_t)L, (int64_t)L, (int64_t)fit});
+    const int64_t* d_lags = (const int64_t*)ctx->ov_tab.dev.p;
+    const double* d_a2 = (const double*)ctx->ov_tab.dev.p + L;
+    TA_HIP_TRY(ctx, hipMemsetAsync(d_q, 0, sizeof(int64_t) * (size_t)C * (size_t)L * (size_t)slab.T, st));
+    for (int l0 = 0; l0 < L; l0 += Lc)
+        TA_LAUNCH_MAIN(ctx, "k_overlap", st,
+                       launch_overlap(ctx->n_cu, slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, slab.D, d_lags, l0,
+                                      std::min(Lc, L - l0), L, d_a2, C, (unsigned long long*)d_q, st));
+    return call_end(ctx, st);
+}
+
 // ---- distinct van Hove function (vanhove_distinct.hip) --------------------------------------------------------------
 constexpr size_t kVhdBudget = (size_t)4 << 30;  // the gathered scratch of one pass (a choice, not a measurement)
 
@@ -1629,6 +1665,9 @@ int opt_check_scatter_chunk(ta_ctx* ctx, int64_t value) {
 }
 int opt_check_vanhove_distinct_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "vanhove_distinct_chunk: 0 (automatic) or the lags per pass");
+}
+int opt_check_overlap_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "overlap_chunk: 0 (automatic) or the lags per launch");
 }
 int opt_check_vanhove_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "vanhove_chunk: 0 (automatic) or the lags per pass");
@@ -2365,6 +2404,30 @@ int ta_vanhove_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins
     });
 }
 
+// Self-overlap per origin: slab 0 / d_pos holds the positions; the staged slab is read in its own element type (never
+// widened); the lags and cutoffs are HOST arrays: they size the launches, and overlap_plan runs before the call is opened
+static int overlap_entry(ta_ctx* ctx, const DevSrc* dev, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs,
+                         int64_t* d_q, void* stream) {
+    return slab_entry(
+        ctx, dev, stream,
+        [&] { return check_overlap(fail, ctx, n_lags, h_lags, n_cutoffs, h_cutoffs, dev ? dev->T : ctx->st_nslabs ? ctx->st_T : 0, d_q != nullptr); },
+        [&](const Slab& s) { return overlap_plan(ctx, n_lags, h_lags, n_cutoffs, h_cutoffs, s.A, s.D, s.st); },
+        [&](const Slab& s) { return overlap_pm(ctx, s, n_lags, n_cutoffs, d_q); });
+}
+int ta_overlap_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int n_lags, const int64_t* h_lags,
+                   int n_cutoffs, const double* h_cutoffs, int64_t* d_q, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    const DevSrc src{d_pos, T, A, D, ld_row};
+    return overlap_entry(ctx, &src, n_lags, h_lags, n_cutoffs, h_cutoffs, d_q, stream);
+    });
+}
+int ta_overlap_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs, int64_t* d_q,
+                      void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    return overlap_entry(ctx, nullptr, n_lags, h_lags, n_cutoffs, h_cutoffs, d_q, stream);
+    });
+}
+
 // Distinct van Hove function on the staged slab 0, read in its own element type; every list is a HOST array
 int ta_vanhove_distinct_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int64_t origin_stride, int64_t n_a,
                                const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes,
@@ -2746,6 +2809,23 @@ int vanhove_launch(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, 
     return TA_OK;
 }
 
+// Overlap share of a host-facing call, queued on ctx->stream and not waited for: the lags and cutoffs (checked by the caller)
+// uploaded, Q (C, L, T) int64 left on the device in *d_out
+int overlap_launch(ta_ctx* ctx, int L, const int64_t* h_lags, int C, const double* h_cutoffs, int64_t** d_out) {
+    int64_t* out = nullptr;
+    TA_CHECK(slab_entry(
+        ctx, nullptr, ctx->stream, no_args,
+        [&](const Slab& s) -> int {
+            TA_CHECK(overlap_plan(ctx, L, h_lags, C, h_cutoffs, s.A, s.D, ctx->stream));
+            TA_CHECK(ensure(ctx, ctx->ov_out, sizeof(int64_t) * (size_t)C * (size_t)L * (size_t)s.T));
+            out = (int64_t*)ctx->ov_out.p;
+            return TA_OK;
+        },
+        [&](const Slab& s) { return overlap_pm(ctx, s, L, C, out); }));
+    *d_out = out;
+    return TA_OK;
+}
+
 // The collective part (K, T) of a host (K, T, 2) density (ta_scatter_collective)
 int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int K, int64_t T, double* h_coll) {
     const size_t KT = (size_t)K * T;
@@ -3040,6 +3120,27 @@ int ta_vanhove(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, doubl
     return host_finish(ctx, {{(double*)h_counts, (const double*)d_out, n_counts},
                              {h_moments, (const double*)d_out + n_counts, 2 * (size_t)n_lags}});
     });
+}
+
+int ta_overlap(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs, int64_t* h_q) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(check_overlap(fail, ctx, n_lags, h_lags, n_cutoffs, h_cutoffs, ctx->st_nslabs ? ctx->st_T : 0, h_q != nullptr));
+    TA_CHECK(check_staged(ctx));
+    if (ctx->is_cpu) {
+        if (ctx->st_A * ctx->st_D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "overlap: n_atoms * dim must be below 2^31");
+        return cpu_rc(ctx, ta::cpu::overlap(cpu_state(ctx), n_lags, h_lags, n_cutoffs, h_cutoffs, h_q));
+    }
+    int64_t* d_out = nullptr;
+    TA_CHECK(ta::overlap_launch(ctx, n_lags, h_lags, n_cutoffs, h_cutoffs, &d_out));
+    const size_t n_q = (size_t)n_cutoffs * (size_t)n_lags * (size_t)ctx->st_T;  // (int64 counts travel as 8-byte elements)
+    return host_finish(ctx, {{(double*)h_q, (const double*)d_out, n_q}});
+    });
+}
+
+int ta_overlap_tile(int* slots) {
+    if (slots) *slots = ta::overlap_slots();
+    return TA_OK;
 }
 
 int ta_vanhove_distinct(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int64_t origin_stride, int64_t n_a, const int64_t* h_idx_a,

@@ -744,6 +744,50 @@ int vanhove(const State& s, int L, const int64_t* lags, int B, double dr, int64_
     return s.dtype == TA_F32 ? vanhove_e<float>(s, L, lags, B, dr, counts, moments) : vanhove_e<double>(s, L, lags, B, dr, counts, moments);
 }
 
+// The self-overlap per origin.  The host slab is frame-major: the atoms of frames t0 and t0 + tau are two contiguous runs,
+// so a thread that owns (l, t0) streams both and writes its C counts -- no two threads share an element of q.
+template <class E, int D>
+int overlap_t(const State& s, int L, const int64_t* lags, int C, const double* cutoffs, int64_t* q) {
+    const int64_t T = s.T, A = s.A;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    const int nth = s.threads > 0 ? s.threads : 1;
+    double a2[TA_OVERLAP_MAX_CUTOFFS];
+    vh_cutoffs2(C, cutoffs, a2);
+    std::fill(q, q + (size_t)C * L * T, (int64_t)0);
+#pragma omp parallel for num_threads(nth) schedule(static) collapse(2)
+    for (int l = 0; l < L; ++l) {
+        for (int64_t t = 0; t < T; ++t) {
+            const int64_t tau = lags[l];
+            if (t + tau >= T) continue;
+            int64_t cnt[TA_OVERLAP_MAX_CUTOFFS] = {0, 0, 0, 0};
+            const E* x0 = x + (size_t)t * A * D;
+            const E* x1 = x + (size_t)(t + tau) * A * D;
+            for (int64_t n = 0; n < A; ++n) {
+                double a[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
+                for (int d = 0; d < D; ++d) {
+                    a[d] = (double)x0[n * D + d];
+                    b[d] = (double)x1[n * D + d];
+                }
+                const double r2 = vh_r2<D>(a, b);
+                for (int c = 0; c < C; ++c) cnt[c] += r2 < a2[c] ? 1 : 0;
+            }
+            for (int c = 0; c < C; ++c) q[((size_t)c * L + l) * T + t] = cnt[c];
+        }
+    }
+    return TA_OK;
+}
+
+template <class E>
+int overlap_e(const State& s, int L, const int64_t* lags, int C, const double* cutoffs, int64_t* q) {
+    if (s.D == 1) return overlap_t<E, 1>(s, L, lags, C, cutoffs, q);
+    if (s.D == 2) return overlap_t<E, 2>(s, L, lags, C, cutoffs, q);
+    return overlap_t<E, 3>(s, L, lags, C, cutoffs, q);
+}
+
+int overlap(const State& s, int L, const int64_t* lags, int C, const double* cutoffs, int64_t* q) {
+    return s.dtype == TA_F32 ? overlap_e<float>(s, L, lags, C, cutoffs, q) : overlap_e<double>(s, L, lags, C, cutoffs, q);
+}
+
 // The distinct van Hove histogram: OpenMP threads take (origin, tile of kVhdCpuTile a-items) units, each thread with an int64
 // histogram of its own; the threads' histograms are added at the end.  Integer adds only: nothing depends on the number of
 // threads or on which thread took which unit.

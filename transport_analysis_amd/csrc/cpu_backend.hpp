@@ -64,6 +64,10 @@ int kcurrent_correlate(int threads, bool fft, const double* current, int K, cons
 // vanhove.hip: counts (L, B + 1) int64 (OpenMP over atoms, a histogram per thread, added at the end), moments (L, 2) = (sum r2,
 // sum r2 r2) per atom, then in atom order; either may be NULL; arguments checked by the caller
 int vanhove(const State& s, int L, const int64_t* lags, int B, double dr, int64_t* counts, double* moments);
+// ta_overlap: the self-overlap per origin of slab 0 for L lags and C cutoffs, with vanhove_math.hpp's r2 and a2 = fl(a a), as
+// overlap.hip: q (C, L, T) int64, zeros at t0 >= T - lag.  OpenMP over the (lag, origin) pairs, each counted over all atoms by
+// one thread: no per-thread copies of q, and nothing depends on the number of threads.
+int overlap(const State& s, int L, const int64_t* lags, int C, const double* cutoffs, int64_t* q);
 // ta_vanhove_distinct: the distinct van Hove histogram of slab 0 with vanhove_distinct_math.hpp's arithmetic, as
 // vanhove_distinct.hip: counts (L, B + 1) int64 over the ordered pairs (ida[p], idb[q]), ida[p] != idb[q], of the origins
 // t = stride o and the lags with t + lag < n_frames (OpenMP over (origin, a-tile), a histogram per thread, added at the end).

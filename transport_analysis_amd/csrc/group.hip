@@ -759,6 +759,34 @@ int ta_group_vanhove(ta_group* g, int n_lags, const int64_t* h_lags, int n_bins,
     });
 }
 
+// Self-overlap per origin: every member's Q of its atoms for the same lags and cutoffs, copied into host vectors of the
+// members' own, then added as int64 (Q adds up over atoms; a variance over origins is the caller's, after this sum)
+int ta_group_overlap(ta_group* g, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs, int64_t* h_q) {
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
+    TAG_CHECK(check_overlap(gfail, g, n_lags, h_lags, n_cutoffs, h_cutoffs, g->T, h_q != nullptr));
+    TAG_CHECK(check_staged(g));
+    const size_t nq = (size_t)n_cutoffs * (size_t)n_lags * (size_t)g->T;
+    std::vector<std::vector<int64_t>> part(g->ctx.size());
+    std::vector<int> who;
+    hipError_t he = hipSuccess;
+    int rc = for_members(g, &who, [&](int i) {
+        int64_t* d = nullptr;
+        if (const int r = overlap_launch(g->ctx[i], n_lags, h_lags, n_cutoffs, h_cutoffs, &d)) return r;
+        part[i].resize(nq);  // (once: the copy into it is in flight from here on)
+        he = hipMemcpyAsync(part[i].data(), d, sizeof(int64_t) * nq, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
+        return he == hipSuccess ? TA_OK : TA_E_HIP;
+    });
+    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string("overlap counts copy: ") + hipGetErrorString(he));
+    if (rc) return drained(g, who, rc);
+    TAG_CHECK(wait_members(g, who));
+    std::fill(h_q, h_q + nq, (int64_t)0);
+    for (int i : who)
+        for (size_t k = 0; k < nq; ++k) h_q[k] += part[i][k];
+    return TA_OK;
+    });
+}
+
 // Unwrap: every member's block of slab `slab` with the same box table, queued on all devices, then waited for
 int ta_group_unwrap(ta_group* g, int slab, const double* h_dimensions, const int* axes) {
     return group_call(g, [&]() -> int {

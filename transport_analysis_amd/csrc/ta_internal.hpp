@@ -186,6 +186,33 @@ static int check_vanhove(Fail fail, Owner* owner, int n_lags, const int64_t* h_l
 // caller), queued: *d_out = counts (n_lags, n_bins + 1) int64, then moments (n_lags, 2) float64 -- the ones asked for are
 // valid after host_wait
 int vanhove_launch(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, double dr, bool counts, bool moments, void** d_out);
+// the argument checks of ta_overlap* (context or group: the same messages for both), all of them before anything is written.
+// T: the frames (0: not known, nothing staged -- the caller reports that next)
+template <class Fail, class Owner>
+static int check_overlap(Fail fail, Owner* owner, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs,
+                         int64_t T, bool any_output) {
+    const std::string p = "overlap: ";
+    if (!h_lags) return fail(owner, TA_E_INVALID, p + "lags are NULL");
+    if (n_lags < 1 || n_lags > TA_VANHOVE_MAX_LAGS)
+        return fail(owner, TA_E_INVALID, p + "n_lags must be 1 ... " + std::to_string(TA_VANHOVE_MAX_LAGS));
+    if (!h_cutoffs) return fail(owner, TA_E_INVALID, p + "cutoffs are NULL");
+    if (n_cutoffs < 1 || n_cutoffs > TA_OVERLAP_MAX_CUTOFFS)
+        return fail(owner, TA_E_INVALID, p + "n_cutoffs must be 1 ... " + std::to_string(TA_OVERLAP_MAX_CUTOFFS));
+    for (int c = 0; c < n_cutoffs; ++c) {
+        const double a = h_cutoffs[c];
+        if (!(a - a == 0.0) || !(a > 0.0)) return fail(owner, TA_E_INVALID, p + "cutoff " + std::to_string(c) + " must be finite and > 0");
+        if (c && !(a > h_cutoffs[c - 1])) return fail(owner, TA_E_INVALID, p + "the cutoffs must be strictly increasing");
+    }
+    if (!any_output) return fail(owner, TA_E_INVALID, p + "the output is NULL");
+    if (const int rc = check_vanhove_lags(fail, owner, p, n_lags, h_lags, T)) return rc;
+    if ((int64_t)n_cutoffs * n_lags * T > (int64_t)1 << 27)
+        return fail(owner, TA_E_INVALID, p + "n_cutoffs * n_lags * n_frames = " + std::to_string((int64_t)n_cutoffs * n_lags * T) +
+                                             " exceeds 2^27 (1 GiB of output): fewer lags or cutoffs per call");
+    return TA_OK;
+}
+// api.hip, for group.hip: one context's ta_overlap share (its staged slab 0, the call's lags and cutoffs, checked by the
+// caller), queued: *d_out = Q (n_cutoffs, n_lags, n_frames) int64, valid after host_wait
+int overlap_launch(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs, int64_t** d_out);
 // api.hip, for group.hip: one context's ta_unwrap queued on its stream (box.tab must stay valid until host_wait)
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes);
 hipStream_t ctx_stream(ta_ctx* ctx);
@@ -358,6 +385,13 @@ int vanhove_parts(int n_cu, long pitch, long n_atoms);
 hipError_t launch_vanhove(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const int64_t* lags, int l0,
                           int Lc, int L, const double* e, int B, float inv_dr, unsigned long long* counts, double* partial,
                           hipStream_t st);
+
+// overlap.hip: the self-overlap per origin of a pair-major slab of float64 or (f32) float32 elements, read as it is, for the
+// lags [l0, l0 + Lc) of L (device array `lags`) and C cutoffs with squared values a2 (device): q (C, L, T) uint64 (zeroed by
+// the caller before the first launch) gets the launch's counts added.  Lc C <= overlap_slots(), the kernel's tile.
+int overlap_slots();
+hipError_t launch_overlap(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const int64_t* lags, int l0,
+                          int Lc, int L, const double* a2, int C, unsigned long long* q, hipStream_t st);
 
 // vanhove_distinct.hip: the distinct van Hove histogram in two passes.  The item pitches of the scratch and of the padded
 // index lists (ids; -1: padding) are multiples of the pair kernel's tiles.  n_orig = ceil(T / stride): the origins of lag 0,

@@ -22,6 +22,10 @@ inline void vh_edges(int B, double dr, double* e) {
         e[b] = r * r;
     }
 }
+// the squared cutoffs of ta_overlap (C of them), formed once per call on the host: a2[c] = fl(a_c a_c)
+inline void vh_cutoffs2(int C, const double* a, double* a2) {
+    for (int c = 0; c < C; ++c) a2[c] = a[c] * a[c];
+}
 // the float32 factor of the bin guess
 inline float vh_inv_dr(double dr) { return (float)(1.0 / dr); }
 
