@@ -184,6 +184,42 @@ def phi_num(M):
     return sqdiff_cols(M).sum(axis=1)
 
 
+def species_moment_exact(y, q, labels, S, shift=True):
+    """Q[s, t, d] = sum_{n: labels[n] = s} q_n (y[t, n, d] - y[0, n, d]) (int64, (S, T, D)): the species moments of
+    positions; shift=False: the species currents sum q_n y[t, n, d] of velocities.  A label no atom carries: zeros."""
+    y = np.asarray(y, dtype=np.float64)
+    a = _as_int(y - y[0] if shift else y)
+    qi, labels = _as_int(q), np.asarray(labels)
+    Q = np.zeros((S,) + a.shape[:1] + a.shape[2:], dtype=np.int64)
+    for s in range(S):
+        sel = np.flatnonzero(labels == s)
+        Q[s] = np.einsum("n,tnd->td", qi[sel], a[:, sel, :])
+    return Q
+
+
+def pseudo_particles(Q):
+    """(T, S^2, D) int64: the series whose lag sums give the cross term by polarisation, pseudo-particle i S + j =
+    Q_i (i == j), Q_i + Q_j (i < j), Q_i - Q_j (i > j), of integer-valued sums Q (S, T, D)."""
+    Q = _as_int(Q)
+    S, T, D = Q.shape
+    P = np.empty((T, S * S, D), dtype=np.int64)
+    for i in range(S):
+        for j in range(S):
+            P[:, i * S + j] = Q[i] if i == j else Q[i] + Q[j] if i < j else Q[i] - Q[j]
+    return P
+
+
+def pseudo_num(Q, acf=False, fft_from=1 << 30):
+    """(T, S^2) numerators R[k, i S + j] of the pseudo-particles of Q (S, T, D): sum_d S_d(k) (the mean squared
+    differences of moments), or with acf sum_d C_d(k) (the autocorrelations of currents).  Over T - k:
+    C_ii = R[i S + i], C_ij = 1/4 (R[i S + j] - R[j S + i]) for i < j.  The sums of many atoms are large and their
+    columns few, so the correlations are np.correlate's int64 sums at every length (`fft_from`: correlate_cols)."""
+    P = pseudo_particles(Q)
+    T, n, D = P.shape
+    cols = P.reshape(T, n * D)
+    return per_particle(correlate_cols(cols, fft_from=fft_from) if acf else sqdiff_cols(cols, fft_from=fft_from), n, D)
+
+
 def self_num(x, q):
     """(T,) numerators of the Nernst-Einstein self term: sum_n q_n^2 sum_d S_nd(k)."""
     qi = _as_int(q)

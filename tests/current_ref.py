@@ -49,6 +49,17 @@ def cross_ref(J):
     return C
 
 
+def cross_at_lags(J, lags):
+    """cross_ref(J)[lags], (len(lags), S, S) long double, without the other lags' work."""
+    J = np.asarray(J, dtype=LD)
+    S, T, D = J.shape
+    C = np.zeros((len(lags), S, S), dtype=LD)
+    for n, k in enumerate(lags):
+        a = np.einsum("itd,jtd->ij", J[:, :T - k, :], J[:, k:, :]) / LD(T - k)
+        C[n] = LD(0.5) * (a + a.T)
+    return C
+
+
 def pair_scale(C):
     """(S, S): max(C_ii(0), C_jj(0)), what the error of C_ij is relative to."""
     diag = np.abs(np.einsum("ii->i", np.asarray(C[0], dtype=np.float64)))

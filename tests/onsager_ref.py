@@ -51,6 +51,18 @@ def cross_ref(M):
     return C
 
 
+def cross_at_lags(M, lags):
+    """cross_ref(M)[lags], (len(lags), S, S) long double, without the other lags' work."""
+    M = np.asarray(M, dtype=LD)
+    S, T, D = M.shape
+    C = np.zeros((len(lags), S, S), dtype=LD)
+    for n, k in enumerate(lags):
+        if k:
+            d = M[:, k:, :] - M[:, :T - k, :]
+            C[n] = np.einsum("itd,jtd->ij", d, d) / LD(T - k)
+    return C
+
+
 def pair_scale(C):
     """(S, S): max_k max(C_ii, C_jj), what the error of C_ij is relative to."""
     C = np.asarray(C, dtype=np.float64)

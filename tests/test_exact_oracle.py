@@ -95,6 +95,50 @@ def test_exact_expectations_match_the_numpy_oracle(T, A):
     assert ex.ulps(orc.self_term_at_lags(x, q, np.arange(T)), ex.divide(ex.self_num(x, q), ex.lag_den(T))).max() <= 2
 
 
+@pytest.mark.parametrize("shift", [True, False], ids=["moments", "currents"])
+def test_species_sums_and_pseudo_particle_numerators_match_fractions(shift):
+    """Three species (one of a single atom), seven frames: species_moment_exact against sums of Fractions atom by atom,
+    pseudo_particles in slab order, pseudo_num against the lag sums of each pseudo-particle in rational arithmetic, and
+    the polarisation identity 1/4 (R+ - R-) = the cross term of Q_i and Q_j."""
+    from fractions import Fraction
+
+    T, A, D, S = 7, 6, 2, 3
+    y = ex.int_walk(T, A, D, 4, seed=11, offset=2 ** 30) if shift else ex.int_velocities(T, A, D, 50, seed=11)
+    q = ex.int_charges(A, 3, seed=12)
+    lab = np.array([0, 2, 0, 1, 2, 0])
+    Q = ex.species_moment_exact(y, q, lab, S, shift=shift)
+    assert Q.shape == (S, T, D) and Q.dtype == np.int64
+    for s in range(S):
+        for t in range(T):
+            for d in range(D):
+                want = sum(Fraction(q[n]) * (Fraction(y[t, n, d]) - (Fraction(y[0, n, d]) if shift else 0))
+                           for n in range(A) if lab[n] == s)
+                assert Q[s, t, d] == want
+    assert not ex.species_moment_exact(y, q, lab, 4, shift=shift)[3].any()  # a label nobody carries
+    P = ex.pseudo_particles(Q)
+    assert P.shape == (T, S * S, D)
+    for i in range(S):
+        for j in range(S):
+            assert np.array_equal(P[:, i * S + j], Q[i] if i == j else Q[i] + Q[j] if i < j else Q[i] - Q[j])
+    R = ex.pseudo_num(Q, acf=not shift)
+    assert np.array_equal(R, ex.pseudo_num(Q, acf=not shift, fft_from=4))  # (7 frames: int64 products either way)
+    for p in range(S * S):
+        for k in range(T):
+            f = (ex.frac_sqdiff if shift else ex.frac_corr)
+            assert R[k, p] == sum(f(P[:, p, d].astype(np.float64), k) for d in range(D))
+    for i in range(S):
+        for j in range(i + 1, S):
+            for k in range(T):
+                if shift:
+                    cross = sum(int((Q[i, t + k, d] - Q[i, t, d]) * (Q[j, t + k, d] - Q[j, t, d]))
+                                for t in range(T - k) for d in range(D))
+                    assert R[k, i * S + j] + R[k, j * S + i] == 2 * (R[k, i * S + i] + R[k, j * S + j])
+                else:
+                    cross = Fraction(sum(int(Q[i, t, d] * Q[j, t + k, d] + Q[j, t, d] * Q[i, t + k, d])
+                                         for t in range(T - k) for d in range(D)), 2)
+                assert Fraction(int(R[k, i * S + j] - R[k, j * S + i]), 4) == cross
+
+
 needs_longdouble = pytest.mark.skipif(not ex.longdouble_ok(), reason="np.longdouble has no 64-bit significand here")
 
 
