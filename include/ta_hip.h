@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -156,7 +156,9 @@ int ta_stage_synth(ta_ctx *ctx, int slab, uint64_t seed, int64_t col_offset, int
  * for ta_species_self* the weighted slab with each species' atoms contiguous (the input's element count * 8 bytes, plus at
  * most one column per species) beside what the lag-sum evaluation of one species needs; for ta_compound its plan (12 bytes per
  * member entry, 12 per compound) and, with frame weights, the (n_frames, dim) weighted mean and its partial sums (the
- * ta_onsager workspace);
+ * ta_onsager workspace); for ta_orient* the block of the orientation columns (3 * n_vectors * pitch * 16 bytes, shared by
+ * the two ranks), the pair-major copy of the total (and the (n_frames, 3) total itself when it is not asked for) and the
+ * sum's partial sums (the ta_onsager workspace);
  * the labels, weights and outputs of host-facing calls are kept.                                                                                                            */
 int ta_trim(ta_ctx *ctx);
 
@@ -475,6 +477,73 @@ int ta_vanhove_distinct(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int64_t 
                         const int64_t *h_idx_a, int64_t n_b, const int64_t *h_idx_b, const double *h_dimensions,
                         const int *axes, int n_bins, double dr, int64_t *h_counts);
 
+/* ta_orient  : the rotational correlation functions of molecule-fixed unit vectors of the positions in slab 0
+ *              (OrientationalCorrelation), three staged columns per atom.  A vector n is row n of h_index, atoms of slab 0,
+ *              pairwise distinct and in [0, n_atoms):
+ *                TA_ORIENT_BOND     (a, b)    : v = d(a -> b)
+ *                TA_ORIENT_BISECTOR (a, b, c) : v = d(a -> b) + d(a -> c)              (a water's dipole direction, a = O)
+ *                TA_ORIENT_NORMAL   (a, b, c) : v = d(a -> b) x d(a -> c)
+ *              h_index is (n_vectors, 2) for a bond, else (n_vectors, 3), int32, row-major.  With u_n(t) = v / |v|:
+ *                h_c1[tau]          = 1/(T - tau) sum_{t < T - tau} sum_n u_n(t) . u_n(t + tau)
+ *                h_c2[tau]          = 1/(T - tau) sum_{t < T - tau} sum_n Q_n(t) : Q_n(t + tau),   Q = u (x) u - 1/3
+ *                                   = 1/(T - tau) sum sum ((u . u')^2 - 1/3) = 2/3 sum sum P2(u . u')
+ *                h_total[t * 3 + d] = M(t)_d = sum_n w_n u_n(t)_d             (h_weights: n_vectors values, NULL: all 1)
+ *                h_coll[tau]        = 1/(T - tau) sum_{t < T - tau} M(t) . M(t + tau)
+ *              Lag 0 is kept (c1: the number of non-degenerate vectors, c2: 2/3 of it).  NOTHING is divided by n_vectors or
+ *              multiplied by 3/2 (OrientationalCorrelation does that).  The weights enter total and coll only.  Each output
+ *              may be NULL (not computed), not all four.  c1, c2 and total add up over disjoint vector lists; coll does
+ *              not: it is the autocorrelation of the summed total.
+ *              Arithmetic (csrc/orient_math.hpp; the CPU backend runs the same sequence).  d(a -> b)_j = x[t, b, j] -
+ *              x[t, a, j] in float64 (a float32 slab: widened first).  h_dimensions (n_frames, 6) as for ta_unwrap, or NULL
+ *              (nothing is reduced): with H(t) the box vectors as rows (lower-triangular) and M = H^-1 of ta_unwrap's
+ *              table, the difference is reduced by ONE sequential image step per axis, z, then y, then x:
+ *                k = rint(d_2 M22);  d_2 = fma(-k, H22, d_2);  d_1 = fma(-k, H21, d_1);  d_0 = fma(-k, H20, d_0)
+ *                k = rint(d_1 M11);  d_1 = fma(-k, H11, d_1);  d_0 = fma(-k, H10, d_0)
+ *                k = rint(d_0 M00);  d_0 = fma(-k, H00, d_0)
+ *              An orthorhombic box is the same code with zero off-diagonals (fma(-k, 0, d) = d exactly): an orthorhombic
+ *              box given with angles that make it a triclinic table of the same H gives the same bits.  This is the
+ *              MINIMUM image while the true vector is shorter than half the smallest box width (the distance between
+ *              opposite faces) -- a bond, a molecule's arm -- whichever periodic images the atoms are; it is not a general
+ *              triclinic minimum image.  The box of frame t reduces frame t: per-frame boxes (NPT) are followed.
+ *              normal: v_0 = fma(b_1, c_2, -fl(b_2 c_1)) and cyclic.  n2 = fma(v_2, v_2, fma(v_1, v_1, fl(v_0 v_0))),
+ *              u = v / sqrt(n2), u = 0 where n2 == 0 (or is not finite): a degenerate vector contributes zeros to every
+ *              output, never a NaN.  Q's six columns: fma(u_j, u_j, -fl(1/3)) and fl(sqrt 2) fl(u_j u_k), zeros where u = 0.
+ *              Error bounds per component of u, with e = 2^-53, from that operation sequence.  A difference is one
+ *              rounding, e |d|.  Each of the (up to three) image steps a component goes through is one fma, i.e. one
+ *              rounding of an intermediate no larger than the raw difference: with a box at most 3 e R |v| more, R = the
+ *              largest raw |x_b - x_a| component over the smallest |v| of the call (R = 0 without a box; for wrapped
+ *              molecules R is about the box length over the bond length).  Combining: nothing (bond), one rounding
+ *              (bisector), two (normal: the product and the fma), relative to max(|d_ab|, |d_ac|)^2 there, so a nearly
+ *              degenerate vector loses in proportion to max(|d_ab|, |d_ac|) / |v| (bisector) or |d_ab| |d_ac| / |v|
+ *              (normal); for vectors that are not (that ratio <= 2) v is within 4 e |v| per component.  n2: three
+ *              roundings of positive terms, sqrt and the division one each.  Together every component of u is within
+ *              B_u e of the exact unit vector's, B_u = 12 + 3 R.  total: component d of M(t) is within
+ *              (B_u + 1 + n_vectors) e sum_n |w_n| of the exact sum -- B_u e |w_n| per term from u, one rounding of the
+ *              product w_n u_n, and at most n_vectors - 1 roundings of partial sums, each bounded by sum |w| (the pass
+ *              adds its partials in a fixed order; the bound holds for any order), as the density's bound of ta_scatter
+ *              grows with n_atoms.  c1, c2, coll: the library's usual 1e-10 of the series' maximum.
+ *              The pass k_orient reads the slab in the element type it has (a float32 device slab as float32, widened in
+ *              registers; never widened first), once per rank asked for, and writes a float64 pair-major block: rank 1
+ *              (c1, total or coll asked for) n_vectors "atoms" of dim 3 holding u, rank 2 (c2) 2 n_vectors pseudo-atoms of
+ *              dim 3 holding Q's columns, rows n_frames ... pitch - 1 zeros.  c1 and c2 are ONE lag-sum evaluation of
+ *              ta_vacf_fft (fft = 1) / ta_vacf_direct (fft = 0) each on their block, total the fixed-order weighted sum
+ *              over the rank-1 block's atoms (no atomics: the same bits from run to run), coll one evaluation of the total
+ *              as one atom of dim 3.  The block is 3 n_vectors pitch 16 bytes, shared by the two ranks; the call does not
+ *              chunk (a lag sum split over vectors would change its bits): TA_E_NOMEM when it does not fit.  ta_trim
+ *              releases it.  The staged slab is not changed.
+ *              A mode other than the three, fft other than 0 / 1, all outputs NULL, nothing staged or dim != 3,
+ *              n_vectors < 1, NULL h_index, n_atoms * 3 or n_vectors * 6 at or above 2^31, an index out of range, an atom
+ *              twice in a row, a non-finite weight, a box ta_unwrap's table rejects (all checked before anything is
+ *              written): TA_E_INVALID.  CPU backend: the same arithmetic, OpenMP over frames, frame-major u and Q arrays
+ *              and its VACF routines, total in vector order.  There is no ta_group_* form: a vector's atoms would have to
+ *              share a shard.  Timings: the pass is the main kernel unless an evaluation after it records its own
+ *              (ta_kernel_timeline names it k_orient, once per rank).                                                   */
+#define TA_ORIENT_BOND 0
+#define TA_ORIENT_BISECTOR 1
+#define TA_ORIENT_NORMAL 2
+int ta_orient(ta_ctx *ctx, int fft, int mode, int64_t n_vectors, const int32_t *h_index, const double *h_dimensions,
+              const double *h_weights, double *h_c1, double *h_c2, double *h_total, double *h_coll);
+
 /* ---- periodic unwrapping of a staged position slab ---------------------------------------------------------------
  * ta_unwrap: undo periodic wrapping of staging slab `slab` in place (MDAnalysis' NoJump), over the staged frames
  * in order.  h_dimensions: (n_frames, 6) float64 rows [a, b, c, alpha, beta, gamma] (A, degrees; ts.dimensions).
@@ -574,6 +643,13 @@ int ta_species_self_dev(ta_ctx *ctx, const double *d_x, int64_t n_frames, int64_
 int ta_scatter_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row, int fft,
                    int n_k, const double *h_kvecs, double *d_self, double *d_density, double *d_coll, void *stream);
 
+/* d_pos: frame-major float64 positions, dim must be 3; h_index, h_dimensions, h_weights: HOST arrays, as for ta_orient (they
+ * size the launches; checked before anything is written); d_c1 (n_frames), d_c2 (n_frames), d_total (n_frames, 3), d_coll
+ * (n_frames): device arrays, each may be NULL, not all four.  c1, c2 and total of disjoint vector lists add up. */
+int ta_orient_dev(ta_ctx *ctx, const double *d_pos, int64_t n_frames, int64_t n_atoms, int dim, int64_t ld_row, int fft,
+                  int mode, int64_t n_vectors, const int32_t *h_index, const double *h_dimensions, const double *h_weights,
+                  double *d_c1, double *d_c2, double *d_total, double *d_coll, void *stream);
+
 /* d_pos: frame-major float64 positions; h_lags: HOST lags (they size the launches; checked before anything is written);
  * d_counts (n_lags, n_bins + 1) int64, d_moments (n_lags, 2) float64: device arrays, either may be NULL, not both.
  * Shards' counts and moments add up. */
@@ -611,6 +687,10 @@ int ta_species_self_staged(ta_ctx *ctx, int quantity, int fft, int n_species, co
 /* h_kvecs: HOST wavevectors, as for ta_scatter_dev; slab 0 (the positions) is read in the element type it has */
 int ta_scatter_staged(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, double *d_self, double *d_density,
                       double *d_coll, void *stream);
+
+/* h_index, h_dimensions, h_weights: HOST arrays, as for ta_orient_dev; slab 0 (the positions) is read in the element type it has */
+int ta_orient_staged(ta_ctx *ctx, int fft, int mode, int64_t n_vectors, const int32_t *h_index, const double *h_dimensions,
+                     const double *h_weights, double *d_c1, double *d_c2, double *d_total, double *d_coll, void *stream);
 
 /* h_kvecs: HOST wavevectors, d_weights: device weights (n_atoms) or NULL, as ta_conductivity_staged's charges; slab 0 (the
  * velocities) and slab 1 (the positions) are read in the element type they have; each output may be NULL, not all three */

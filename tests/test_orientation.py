@@ -1,0 +1,369 @@
+"""ta_orient on the CPU backend and OrientationalCorrelation (device="cpu"): closed forms, the long-double reference of
+orient_ref, wrapped molecules under orthorhombic and triclinic boxes, the argument checks and the class.  Runs without a GPU."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import orient_ref as ref
+from transport_analysis_amd import IntermediateScattering, OrientationalCorrelation, _lib, group_indices
+from transport_analysis_amd._mini_mda import ArrayUniverse
+
+LD = np.longdouble
+DTYPES = [pytest.param(np.float64, id="f64"), pytest.param(np.float32, id="f32")]
+
+
+def staged(x, dtype=np.float64):
+    T, A, D = x.shape
+    c = _lib.Context("cpu")
+    (view,) = c.stage_alloc(T, A, D, dtype=dtype)
+    view[:] = x
+    c.stage_commit(0, T)
+    return c
+
+
+def orient(x, index, mode, dtype=np.float64, fft=1, **kw):
+    c = staged(np.asarray(x, dtype=np.float64), dtype)
+    try:
+        return c.orient(fft, np.asarray(index, dtype=np.int32), mode, **kw)
+    finally:
+        c.close()
+
+
+def rotating(T, N, omega, seed=0):
+    """N bonds in the xy plane, each at its own phase and length, all turning at angular velocity omega; atom 2 n at a
+    random place, atom 2 n + 1 at the bond's end"""
+    rng = np.random.default_rng(seed)
+    phase, length = rng.uniform(0, 2 * np.pi, N), rng.uniform(0.6, 1.4, N)
+    ang = omega * np.arange(T)[:, None] + phase[None, :]
+    a = np.broadcast_to(rng.uniform(0, 10, size=(1, N, 3)), (T, N, 3))
+    b = a + length[None, :, None] * np.stack([np.cos(ang), np.sin(ang), np.zeros_like(ang)], axis=2)
+    return np.stack([a, b], axis=2).reshape(T, 2 * N, 3), np.arange(2 * N, dtype=np.int32).reshape(N, 2)
+
+
+@pytest.mark.parametrize("fft", [1, 0])
+def test_rigid_rotation_closed_form(fft):
+    T, N, omega = 120, 7, 0.05
+    x, idx = rotating(T, N, omega)
+    c1, c2, total, coll = orient(x, idx, "bond", fft=fft)
+    tau = np.arange(T)
+    want1, want2 = N * np.cos(omega * tau), N * (3 * np.cos(omega * tau) ** 2 - 1) / 2
+    print(np.abs(c1 - want1).max(), np.abs(1.5 * c2 - want2).max())
+    assert np.abs(c1 - want1).max() <= 1e-10 * N
+    assert np.abs(1.5 * c2 - want2).max() <= 1e-10 * N
+    # whatever the time origin: the second half of the trajectory alone gives the same function
+    h1, h2, _, _ = orient(x[T // 2:], idx, "bond", fft=fft)
+    assert np.abs(h1 - want1[:T - T // 2]).max() <= 1e-10 * N and np.abs(1.5 * h2 - want2[:T - T // 2]).max() <= 1e-10 * N
+
+
+def test_static_parallel_and_antiparallel():
+    T, N = 40, 6
+    rng = np.random.default_rng(1)
+    a = rng.uniform(0, 9, size=(N, 3))
+    d = rng.normal(size=(N, 3))
+    x = np.broadcast_to(np.stack([a, a + d], axis=1).reshape(1, 2 * N, 3), (T, 2 * N, 3)).copy()
+    idx = np.arange(2 * N).reshape(N, 2)
+    w = rng.uniform(0.5, 2.0, N)
+    c1, c2, total, coll = orient(x, idx, "bond", weights=w)
+    u = d / np.linalg.norm(d, axis=1)[:, None]
+    M = (w[:, None] * u).sum(axis=0)
+    assert np.abs(c1 / N - 1).max() <= 1e-12 and np.abs(1.5 * c2 / N - 1).max() <= 1e-12
+    assert np.abs(total - M).max() <= 1e-13 and np.all(total == total[0])
+    assert np.abs(coll - M @ M).max() <= 1e-12 * (M @ M)
+    # antiparallel pairs: total 0 and Kirkwood factor 0; parallel vectors: Kirkwood factor N
+    pair = np.array([[0, 1], [1, 0], [2, 3], [3, 2]])
+    assert np.array_equal(orient(x, pair, "bond")[2], np.zeros((T, 3)))
+    for vec, want in ((pair, 0.0), (np.array([[0, 1]]), 1.0)):
+        r = OrientationalCorrelation(ArrayUniverse(positions=x).atoms, vec, minimum_image=False, device="cpu").run().results
+        assert abs(r.kirkwood - want) <= 1e-12
+    par = x.copy()
+    par[:, 1::2] = par[:, 0::2] + np.array([0.3, -0.4, 1.2])  # every bond the same direction
+    r = OrientationalCorrelation(ArrayUniverse(positions=par).atoms, idx, minimum_image=False, device="cpu").run().results
+    assert abs(r.kirkwood - N) <= 1e-12 * N and abs(r.total_acf[0] - N * N) <= 1e-9
+
+
+def water_like(T, omega, axis):
+    """a rigid water-like triple (O at the origin of its own frame, arms of 0.96 at 104.5 degrees in the xy plane) turned by
+    omega t about `axis`, translated"""
+    half = np.deg2rad(104.5 / 2)
+    body = np.array([[0, 0, 0], [0.96 * np.cos(half), 0.96 * np.sin(half), 0], [0.96 * np.cos(half), -0.96 * np.sin(half), 0]])
+    k = np.asarray(axis, dtype=np.float64) / np.linalg.norm(axis)
+    out = np.zeros((T, 3, 3))
+    for t in range(T):
+        a = omega * t
+        R = lambda v: v * np.cos(a) + np.cross(k, v) * np.sin(a) + k * (k @ v) * (1 - np.cos(a))
+        out[t] = np.stack([R(v) for v in body]) + np.array([3.0, 4.0, 5.0])
+    return out
+
+
+@pytest.mark.parametrize("mode", ref.MODES)
+def test_rigid_triple_all_modes(mode):
+    T, omega = 90, 0.07
+    idx = np.array([[0, 1]] if mode == "bond" else [[0, 1, 2]], dtype=np.int32)
+    tau = np.arange(T)
+    for axis in ((0, 0, 1), (1, 2, -0.5)):
+        x = water_like(T, omega, axis)
+        got = orient(x, idx, mode)
+        ref.assert_orient(got, ref.reference(x, idx, mode), what=f"{mode} about {axis}")
+    # about z -- the normal of the molecule's plane: the normal does not move, the in-plane vectors turn by omega tau
+    c1, c2, _, _ = orient(water_like(T, omega, (0, 0, 1)), idx, mode)
+    want = np.ones(T) if mode == "normal" else np.cos(omega * tau)
+    assert np.abs(c1 - want).max() <= 1e-10
+    assert np.abs(1.5 * c2 - (3 * want ** 2 - 1) / 2).max() <= 1e-10
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("T", [1, 2, 3, 7, 65, 200])
+def test_walks_against_reference(T, dtype):
+    for mode in ref.MODES:
+        for weighted in (False, True):
+            x, idx, w, r = ref.case(T, 9, mode, weighted=weighted, n_mol=6)  # nine vectors on six molecules: shared atoms
+            c = staged(x, dtype)
+            try:
+                for fft in (1, 0):
+                    ref.assert_orient(c.orient(fft, idx, mode, weights=w), r, what=f"T={T} {mode} w={weighted} fft={fft}")
+            finally:
+                c.close()
+
+
+ORTHO, TRIC = ref.ORTHO, ref.TRIC
+
+
+@pytest.mark.parametrize("mode", ref.MODES)
+@pytest.mark.parametrize("dims,moving", [(ORTHO, False), (ORTHO, True), (TRIC, False), (TRIC, True)],
+                         ids=["ortho-constant", "ortho-per-frame", "tric-constant", "tric-per-frame"])
+def test_wrapped_molecules(dims, moving, mode):
+    T, N = 60, 11
+    x, idx, _, want = ref.case(T, N, mode, seed=4)
+    box = ref.box_frames(dims, T, moving)
+    wrapped = ref.near_corner_wrapped(x, idx, box)
+    got = orient(wrapped, idx, mode, dimensions=box)
+    ref.assert_orient(got, ref.reference(wrapped, idx, mode, box), what="wrapped, own reference")
+    # ... and equal to the unwrapped trajectory within the bars (the total against the bar of the wrapped call, whose data
+    # carry one more rounding per image shift: 1e-10 sum |w| covers both)
+    lags, c1, c2, total = want[:4]
+    for g, w_, f in ((got[0], c1, 1.0), (got[1], c2, 1.5)):
+        assert float(np.max(np.abs(f * g[lags].astype(LD) - w_))) <= 1e-10 * float(np.max(np.abs(w_)))
+    assert float(np.max(np.abs(got[2].astype(LD) - total))) <= 1e-10 * N
+    # without the box the cut vectors point elsewhere: grossly different
+    bare = orient(wrapped, idx, mode)
+    assert np.abs(bare[2] - got[2]).max() > 0.1
+    if not moving and dims is ORTHO:
+        # float32 staging holds the same values (dyadic box): the same reference
+        ref.assert_orient(orient(wrapped, idx, mode, dtype=np.float32, dimensions=box), ref.reference(wrapped, idx, mode, box))
+
+
+def test_orthorhombic_box_in_a_triclinic_table_same_bits():
+    """One image path for both box shapes: the frames with the orthorhombic box give the same bits whether the table is
+    orthorhombic and constant or per-frame with a triclinic frame in it"""
+    T, N = 30, 8
+    x, idx, _, _ = ref.case(T, N, "bisector", seed=5)
+    wrapped = ref.wrap(x + 24.0, ORTHO)
+    const = orient(wrapped, idx, "bisector", dimensions=np.tile(ORTHO, (T, 1)), c1=False, c2=False, collective=False)[2]
+    mixed = ref.box_frames(ORTHO, T, False)
+    mixed[-1] = [30.0, 31.0, 32.0, 80.0, 85.0, 75.0]
+    tab = orient(wrapped, idx, "bisector", dimensions=mixed, c1=False, c2=False, collective=False)[2]
+    assert np.array_equal(const[:-1], tab[:-1])
+    assert np.abs(const).max() > 0
+
+
+def test_zero_length_vector_gives_zeros():
+    T = 12
+    x, idx, _, _ = ref.case(T, 3, "bond", seed=6)
+    x = np.array(x)
+    x[:, idx[1, 1]] = x[:, idx[1, 0]]  # vector 1 has no length in any frame
+    x[5, idx[2, 1]] = x[5, idx[2, 0]]  # vector 2 has none in frame 5
+    got = orient(x, idx, "bond")
+    assert all(np.all(np.isfinite(a)) for a in got)
+    ref.assert_orient(got, ref.reference(x, idx, "bond"), what="degenerate")
+    assert abs(got[0][0] - (2 - 1 / T)) <= 1e-12  # lag 0 counts the non-degenerate vectors
+    tri = np.array([[0, 1, 2]], dtype=np.int32)
+    flat = np.zeros((4, 3, 3))
+    flat[:, 1, 0], flat[:, 2, 0] = 1.0, 2.0  # collinear: the normal has no direction
+    c1, c2, total, coll = orient(flat, tri, "normal")
+    assert not c1.any() and not c2.any() and not total.any() and not coll.any()
+
+
+def raw_call(c, fft, mode, n, index, dims, w, outs):
+    L = _lib.lib()
+    ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    return L.ta_orient(c._h, fft, mode, n, ptr(index), ptr(dims), ptr(w), *[ptr(o) for o in outs])
+
+
+def test_argument_checks_leave_the_outputs_untouched():
+    T, N = 8, 4
+    x, idx, _, _ = ref.case(T, N, "bisector", seed=7)
+    A = x.shape[1]
+    c = staged(x)
+    two = staged(x[:, :, :2])
+    empty = _lib.Context("cpu")
+    dims = np.tile(np.asarray(ORTHO), (T, 1))
+    w = np.ones(N)
+
+    def outs():
+        return [np.full(T, 7.5), np.full(T, 7.5), np.full((T, 3), 7.5), np.full(T, 7.5)]
+
+    def bad(ctx, message, fft=1, mode=1, n=N, index=idx, d=dims, wt=w, o=None):
+        o = outs() if o is None else o
+        rc = raw_call(ctx, fft, mode, n, index, d, wt, o)
+        err = _lib.lib().ta_last_error(ctx._h).decode()
+        assert rc == -1 and message in err, (rc, err)  # TA_E_INVALID
+        assert all(a is None or np.all(a == 7.5) for a in o)
+
+    try:
+        bad(c, "mode must be", mode=3)
+        bad(c, "mode must be", mode=-1)
+        bad(c, "fft must be 0 or 1", fft=2)
+        bad(c, "all NULL", o=[None] * 4)
+        bad(empty, "no position slab is staged")
+        bad(two, "three columns per atom")
+        bad(c, "n_vectors must be >= 1", n=0)
+        bad(c, "index table is NULL", index=None)
+        for value in (-1, A):
+            i = np.array(idx)
+            i[2, 1] = value
+            bad(c, f"index {value} of vector 2 is outside", index=i)
+        for a, b in ((0, 1), (0, 2), (1, 2)):
+            i = np.array(idx)
+            i[3, b] = i[3, a]
+            bad(c, "vector 3 names an atom twice", index=i)
+        i = np.array(idx[:, :2])
+        i[1, 1] = i[1, 0]
+        bad(c, "vector 1 names an atom twice", mode=0, index=np.ascontiguousarray(i))
+        for value in (np.nan, np.inf):
+            wt = w.copy()
+            wt[2] = value
+            bad(c, "weight 2 is not finite", wt=wt)
+        d = dims.copy()
+        d[3, 1] = 0.0
+        bad(c, "box length <= 0 or not finite in frame 3", d=d)
+        d = dims.copy()
+        d[5, 4] = 180.0
+        bad(c, "box angle outside (0, 180) degrees in frame 5", d=d)
+        # the same table through the binding: a call that passes leaves results, and the device-facing twins are refused
+        assert raw_call(c, 1, 1, N, idx, dims, w, outs()) == 0
+        with pytest.raises(_lib.TAError, match="not available on the CPU backend") as e:
+            c.orient_staged(1, idx, "bisector", d_c1=8)
+        assert e.value.code == -5
+        with pytest.raises(_lib.TAError, match="not available on the CPU backend"):
+            c.orient_dev(8, T, A, 3, 3 * A, 1, idx, "bisector", d_c1=8)
+    finally:
+        for ctx in (c, two, empty):
+            ctx.close()
+
+
+def test_each_output_alone_equals_all_together():
+    x, idx, w, _ = ref.case(65, 9, "normal", weighted=True, n_mol=6)
+    c = staged(x, np.float32)
+    try:
+        for fft in (1, 0):
+            full = c.orient(fft, idx, "normal", weights=w)
+            for i, key in enumerate(("c1", "c2", "total", "collective")):
+                only = {k: k == key for k in ("c1", "c2", "total", "collective")}
+                got = c.orient(fft, idx, "normal", weights=w, **only)
+                assert np.array_equal(got[i], full[i]) and all(a is None for j, a in enumerate(got) if j != i)
+    finally:
+        c.close()
+
+
+# ---- the class -----------------------------------------------------------------------------------------------------
+def test_class_results_and_normalisation():
+    T, N = 50, 7
+    x, idx, w, r = ref.case(T, N, "bisector", seed=8, weighted=True)
+    box = np.tile(np.asarray(ORTHO), (T, 1))
+    wrapped = ref.wrap(x + 36.0, ORTHO)
+    u = ArrayUniverse(positions=wrapped.astype(np.float32), dimensions=ORTHO, dt=2.0)
+    a = OrientationalCorrelation(u.atoms, idx, mode="bisector", weights=w, device="cpu").run()
+    lags, c1, c2, total = r[:4]
+    res = a.results
+    assert res.c1.shape == res.c2.shape == res.total_acf.shape == (T,) and res.total.shape == (T, 3)
+    assert abs(res.c1[0] - 1) <= 1e-12 and abs(res.c2[0] - 1) <= 1e-12
+    assert np.abs(res.c1[lags] - (c1 / N).astype(np.float64)).max() <= 1e-10
+    assert np.abs(res.c2[lags] - (c2 / N).astype(np.float64)).max() <= 1e-10
+    assert np.abs(res.total - total.astype(np.float64)).max() <= 1e-10 * np.abs(w).sum()
+    assert np.abs(res.total_acf[lags] - ref.coll_at(res.total, lags).astype(np.float64)).max() <= 1e-10 * res.total_acf[0]
+    assert abs(res.kirkwood - np.mean((res.total ** 2).sum(axis=1)) / (w ** 2).sum()) <= 1e-12
+    assert np.array_equal(a.lag_times(), 2.0 * np.arange(T))
+    assert a._ctx.shape == (T, x.shape[1], 3)
+    # the raw call with the recorded boxes gives the class's sums
+    raw = orient(wrapped, idx, "bisector", dtype=np.float32, dimensions=box, weights=w)
+    assert np.array_equal(raw[0] / N, res.c1) and np.array_equal(1.5 * raw[1] / N, res.c2)
+    # minimum_image=False on the wrapped data differs; on the unwrapped data it agrees with the boxed run
+    off = OrientationalCorrelation(ArrayUniverse(positions=x.astype(np.float32)).atoms, idx, mode="bisector", weights=w,
+                                   minimum_image=False, collective=False, device="cpu").run().results
+    assert off.total_acf is None and np.abs(off.c1 - res.c1).max() <= 1e-10
+    with pytest.raises(ValueError, match="minimum_image=True needs the periodic box"):
+        OrientationalCorrelation(ArrayUniverse(positions=x.astype(np.float32)).atoms, idx, mode="bisector", device="cpu").run()
+
+
+def test_relaxation_times_on_an_exponential():
+    """u turning at a constant rate in the plane decays as cos; use a class instance whose results are set to exponentials"""
+    x, idx = rotating(40, 3, 0.01)
+    a = OrientationalCorrelation(ArrayUniverse(positions=x.astype(np.float32), dt=0.5).atoms, idx, minimum_image=False, device="cpu")
+    with pytest.raises(RuntimeError, match="must be run"):
+        a.relaxation_times()
+    a.run()
+    t = a.lag_times()
+    a.results.c1, a.results.c2 = np.exp(-t / 4.0), np.exp(-t / (4.0 / 3.0))
+    t1, t2 = a.relaxation_times()
+    # the chord of exp(-t / tau) over a step dt lies above it by at most dt^2 y_left / (8 tau^2), and the slope at the
+    # crossing is y / tau with y_left / y <= exp(dt / tau): the interpolated time is late by at most this
+    bound = lambda tau: 0.5 ** 2 / (8 * tau) * np.exp(0.5 / tau)
+    assert 0 <= t1 - 4.0 <= bound(4.0) and 0 <= t2 - 4.0 / 3.0 <= bound(4.0 / 3.0)
+    assert np.isnan(a.relaxation_times(level=1e-9)[0])
+    tl = a.relaxation_times(level=0.5)
+    assert 0 <= tl[0] - 4.0 * np.log(2) <= bound(4.0) and 0 <= tl[1] - 4.0 / 3.0 * np.log(2) <= bound(4.0 / 3.0)
+
+
+def test_intermediate_scattering_relaxation_times_unchanged():
+    """the interpolation moved into a shared function: the same values as the loop it replaced, on a fixed input"""
+    x = ref.molecules(30, 4, 11)
+    a = IntermediateScattering(ArrayUniverse(positions=x.astype(np.float32), dt=0.25).atoms, [[1.0, 0, 0], [0, 2.0, 0], [0, 0, 0.1]],
+                               coherent=False, device="cpu").run()
+    fs = np.stack([np.exp(-a.lag_times() / 1.7), 1.0 - 0.09 * a.lag_times(), np.full(30, 1.0), 0.2 * np.ones(30)], axis=1)
+    fs[0, 3] = 1.0
+    a.results.fs = fs
+    t = a.lag_times()
+    want = np.full(4, np.nan)
+    for s in range(4):  # the former body of IntermediateScattering.relaxation_times
+        y = fs[:, s] / fs[0, s]
+        below = np.flatnonzero(y < 1 / np.e)
+        if below.size == 0:
+            continue
+        i = int(below[0])
+        want[s] = t[0] if i == 0 else t[i - 1] + (1 / np.e - y[i - 1]) * (t[i] - t[i - 1]) / (y[i] - y[i - 1])
+    got = a.relaxation_times()
+    assert got.shape == (4,) and got.dtype == np.float64
+    assert np.array_equal(got, want, equal_nan=True) and np.isnan(got[2]) and 0 < got[3] < t[1]
+
+
+def test_group_indices():
+    u = ArrayUniverse(positions=np.zeros((2, 10, 3), dtype=np.float32))
+    ag = u.atoms[[7, 2, 5, 3]]
+    assert np.array_equal(group_indices(ag, [[2, 7], [3, 5]]), [[1, 0], [3, 2]])
+    assert group_indices(ag, np.zeros((0, 3), dtype=np.int64)).shape == (0, 3)
+    with pytest.raises(ValueError, match=r"atoms \[4, 9\] are not in the atom group"):
+        group_indices(ag, [[2, 9], [4, 5]])
+    with pytest.raises(ValueError, match="integers"):
+        group_indices(ag, [[2.0, 7.0]])
+
+
+def test_class_refusals_and_argument_errors():
+    x, idx = rotating(5, 3, 0.1)
+    ag = ArrayUniverse(positions=x.astype(np.float32)).atoms
+    with pytest.raises(TypeError, match="no per-particle result"):
+        OrientationalCorrelation(ag, idx, by_particle=True, device="cpu")
+    with pytest.raises(ValueError, match="all atoms of a molecule would have to share a shard"):
+        OrientationalCorrelation(ag, idx, devices=[0, 0])
+    with pytest.raises(ValueError, match="all atoms of a molecule would have to share a shard"):
+        OrientationalCorrelation(ag, idx, distributed=True)
+    with pytest.raises(ValueError, match="mode"):
+        OrientationalCorrelation(ag, idx, mode="dipole", device="cpu")
+    with pytest.raises(ValueError, match=r"expected an integer \(N, 3\)"):
+        OrientationalCorrelation(ag, idx, mode="normal", device="cpu")
+    with pytest.raises(ValueError, match="positions within the group"):
+        OrientationalCorrelation(ag, idx + 1, device="cpu")
+    with pytest.raises(ValueError, match="row 1 names an atom twice"):
+        OrientationalCorrelation(ag, [[0, 1], [2, 2]], device="cpu")
+    with pytest.raises(ValueError, match="weights"):
+        OrientationalCorrelation(ag, idx, weights=[1.0, 2.0], device="cpu")

@@ -134,6 +134,16 @@ def parse_dim_type(dim_str, what="dim_type"):
     return list(cols), len(cols)
 
 
+def first_crossing(t, y, level):
+    """The time at which the series y(t) first falls below ``level``, linearly interpolated between the two samples around
+    the crossing (t[0] when y[0] is already below); NaN for a series that never does."""
+    below = np.flatnonzero(y < level)
+    if below.size == 0:
+        return np.nan
+    i = int(below[0])
+    return t[0] if i == 0 else t[i - 1] + (level - y[i - 1]) * (t[i] - t[i - 1]) / (y[i] - y[i - 1])
+
+
 def stage_columns(dst, src, lo, hi, dim):
     """dst[: hi - lo] = src[lo:hi][:, dim] (the reference's per-frame slab fill,
     velocityautocorr.py:192-194, viscosity.py:189-199) without the temporary the fancy index

@@ -16,6 +16,8 @@ _SO = os.path.join(_HERE, "libta_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 
 TA_F32, TA_F64 = 0, 1
+#: ta_orient's modes (TA_ORIENT_*)
+ORIENT_MODES = {"bond": 0, "bisector": 1, "normal": 2}
 
 _vp, _i64, _ci, _dbl, _str = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_char_p
 _P = ctypes.POINTER
@@ -69,6 +71,10 @@ _API = {
     "ta_scatter": _SCATTER, "ta_scatter_collective": _int(_vp, _ci, _vp, _ci, _i64, _vp),
     "ta_scatter_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_scatter_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp),
+    # (handle, fft, mode, n_vectors, h_index, h_dimensions, h_weights, c1, c2, total, coll[, stream])
+    "ta_orient": _int(_vp, _ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp),
+    "ta_orient_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp),
+    "ta_orient_staged": _int(_vp, _ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp),
     "ta_kcurrent": _KCURRENT, "ta_kcurrent_correlate": _int(_vp, _ci, _vp, _ci, _vp, _i64, _ci, _vp, _vp),
     "ta_kcurrent_tile": _int(_P(_ci), _P(_ci), _P(_ci)),
     "ta_kcurrent_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp),
@@ -871,6 +877,62 @@ class Context(_Staged):
         n_bins + 1) int64 on the device"""
         args, keep = self._vhd_args(lags, origin_stride, idx_a, idx_b, dimensions, axes, n_bins, dr)
         self._call("vanhove_distinct_staged", *args, d_counts or None, stream or None)
+        del keep
+
+    def _orient_args(self, fft, index, mode, dimensions, weights):
+        """the argument tuple ta_orient* share, and the arrays it points into (to be kept until the call is over)"""
+        code = ORIENT_MODES.get(mode, mode)
+        if not isinstance(code, (int, np.integer)):
+            raise ValueError(f"mode: {mode!r}, expected one of {sorted(ORIENT_MODES)}")
+        width = 2 if code == 0 else 3
+        idx = np.ascontiguousarray(index)
+        if idx.ndim != 2 or idx.shape[1] != width or not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError(f"index: shape {idx.shape} and dtype {idx.dtype}, expected an integer (n_vectors, {width}) array "
+                             f"for mode {mode!r}")
+        if idx.size and (idx.min() < -2**31 or idx.max() >= 2**31):
+            raise ValueError("index: entries must fit int32")
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        dims = w = None
+        if dimensions is not None:
+            dims = np.ascontiguousarray(dimensions, dtype=np.float64)
+            if self.shape is not None and dims.shape != (self.shape[0], 6):
+                raise ValueError(f"dimensions: shape {dims.shape}, expected ({self.shape[0]}, 6) (one box per staged frame)")
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+            if w.size != idx.shape[0]:
+                raise ValueError(f"weights: {w.size} values for {idx.shape[0]} vectors")
+        return (int(fft), int(code), int(idx.shape[0]), _ptr(idx), _ptr(dims), _ptr(w)), (idx, dims, w)
+
+    def orient(self, fft, index, mode, dimensions=None, weights=None, c1=True, c2=True, total=True, collective=True):
+        """Rotational correlation functions of slab 0 (the positions, three columns per atom), ta_orient: `index` (n_vectors,
+        2) atoms (a, b) for mode "bond", (n_vectors, 3) atoms (a, b, c) for "bisector" and "normal"; `dimensions` the
+        (n_frames, 6) boxes of the staged frames for the image step (None: nothing is reduced); `weights` one per vector or
+        None (all 1; they enter total and coll only): (c1 (n_frames,) = sum_n <u_n . u_n'>, c2 (n_frames,) = sum_n
+        <Q_n : Q_n'> = 2/3 sum_n <P2>, total (n_frames, 3) = sum_n w_n u_n, coll (n_frames,) = the autocorrelation of the
+        total), None for one not asked for; nothing is divided by the number of vectors.  One context only: a device group
+        has no such call."""
+        T = self._staged_shape()[0]
+        args, keep = self._orient_args(fft, index, mode, dimensions, weights)
+        o1 = np.empty(T, dtype=np.float64) if c1 else None
+        o2 = np.empty(T, dtype=np.float64) if c2 else None
+        tot = np.empty((T, 3), dtype=np.float64) if total else None
+        coll = np.empty(T, dtype=np.float64) if collective else None
+        self._call("orient", *args, _ptr(o1), _ptr(o2), _ptr(tot), _ptr(coll))
+        del keep
+        return o1, o2, tot, coll
+
+    def orient_dev(self, d_pos, n_frames, n_atoms, dim, ld_row, fft, index, mode, dimensions=None, weights=None, d_c1=0, d_c2=0,
+                   d_total=0, d_coll=0, stream=0):
+        """`index`, `dimensions`, `weights`: HOST arrays (checked by the library before anything is written)"""
+        args, keep = self._orient_args(fft, index, mode, dimensions, weights)
+        self._call("orient_dev", d_pos, n_frames, n_atoms, dim, ld_row, *args, d_c1 or None, d_c2 or None, d_total or None,
+                   d_coll or None, stream or None)
+        del keep
+
+    def orient_staged(self, fft, index, mode, dimensions=None, weights=None, d_c1=0, d_c2=0, d_total=0, d_coll=0, stream=0):
+        """`index`, `dimensions`, `weights`: HOST arrays (checked by the library before anything is written)"""
+        args, keep = self._orient_args(fft, index, mode, dimensions, weights)
+        self._call("orient_staged", *args, d_c1 or None, d_c2 or None, d_total or None, d_coll or None, stream or None)
         del keep
 
     # -- timing ----------------------------------------------------------

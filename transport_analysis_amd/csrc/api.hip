@@ -22,6 +22,7 @@
 #include "cpu_backend.hpp"
 #include "direct_kernels.hpp"
 #include "kcurrent_math.hpp"
+#include "orient_math.hpp"
 #include "ta_internal.hpp"
 #include "unwrap_box.hpp"
 #include "vanhove_distinct_math.hpp"
@@ -171,6 +172,11 @@ struct ta_ctx {
     DevBuf scatter_z{workspaces, kTrimmed}, scatter_lab{workspaces, kKept};
     DevBuf scatter_work{workspaces, kTrimmed}, scatter_out{workspaces, kKept};
     HostTable scatter_q{workspaces, tables};
+    // orientational correlation functions (orient_pm): the block Z of the orientation columns (3 n_vectors pitch 16 bytes,
+    // shared by the two ranks; trimmed), the pair-major copy of the total (and the total itself when the caller does not
+    // ask for it), the table (box rows, weights, index rows, zero labels), the outputs of host-facing calls
+    DevBuf orient_z{workspaces, kTrimmed}, orient_work{workspaces, kTrimmed}, orient_out{workspaces, kKept};
+    HostTable orient_tab{workspaces, tables};
     // current correlation functions (kcurrent_pm): the partial sums of one chunk of wavevectors (trimmed; its size does not
     // depend on their number), the pair-major slab of the pseudo-atoms jL, jT with their by-particle lag sums (and the current
     // itself when the caller does not ask for it), the wavevectors in turns with the unit vectors (and a host call's weights)
@@ -1236,6 +1242,169 @@ int scatter_pm(ta_ctx* ctx, bool fft, const Slab& slab, int K, double* d_self, d
     }
     if (d_coll) TA_CHECK(scatter_collective(ctx, fft, rho, K, T, d_coll, st));
     return call_end(ctx, st);
+}
+
+// ---- orientational correlation functions (orient.hip) ---------------------------------------------------------------
+// The caller's arguments of ta_orient*, as they came (outputs: which of c1, c2, total, coll are asked for)
+struct OrientArgs {
+    int fft, mode;
+    int64_t N;
+    const int32_t* h_index;
+    const double *h_dims, *h_w;
+    bool c1, c2, total, coll;
+};
+
+// Every check of ta_orient* (both kinds of context), all of them before anything is written; T, A, D: the shape of slab 0
+// (D 0: nothing staged).  With h_dims the box table (unwrap_box.hpp; per-frame rows padded to the pitch) is left in *box.
+int orient_check(ta_ctx* ctx, const OrientArgs& a, int64_t T, int64_t A, int D, BoxTable* box) {
+    const std::string p = "orient: ";
+    if (a.mode < ORIENT_BOND || a.mode > ORIENT_NORMAL)
+        return fail(ctx, TA_E_INVALID, p + "mode must be TA_ORIENT_BOND (0), TA_ORIENT_BISECTOR (1) or TA_ORIENT_NORMAL (2)");
+    TA_CHECK(check_fft(ctx, a.fft));
+    if (!(a.c1 || a.c2 || a.total || a.coll)) return fail(ctx, TA_E_INVALID, p + "the c1, c2, total and collective outputs are all NULL");
+    if (D == 0) return fail(ctx, TA_E_INVALID, p + "no position slab is staged");
+    if (D != 3) return fail(ctx, TA_E_INVALID, p + "the position slab must hold three columns per atom (dim = " + std::to_string(D) + ")");
+    if (a.N < 1) return fail(ctx, TA_E_INVALID, p + "n_vectors must be >= 1");
+    if (!a.h_index) return fail(ctx, TA_E_INVALID, p + "the index table is NULL");
+    if (A * 3 >= (int64_t)1 << 31 || a.N * 6 >= (int64_t)1 << 31)
+        return fail(ctx, TA_E_INVALID, p + "n_atoms * 3 and n_vectors * 6 must be below 2^31");
+    const int K = orient_row_len(a.mode);
+    for (int64_t n = 0; n < a.N; ++n) {
+        const int32_t* r = a.h_index + n * K;
+        for (int j = 0; j < K; ++j)
+            if (r[j] < 0 || r[j] >= A)
+                return fail(ctx, TA_E_INVALID, p + "index " + std::to_string(r[j]) + " of vector " + std::to_string(n) +
+                                                   " is outside 0 ... n_atoms - 1");
+        if (r[0] == r[1] || (K == 3 && (r[0] == r[2] || r[1] == r[2])))
+            return fail(ctx, TA_E_INVALID, p + "vector " + std::to_string(n) + " names an atom twice");
+    }
+    for (int64_t n = 0; a.h_w && n < a.N; ++n)
+        if (!(a.h_w[n] - a.h_w[n] == 0.0)) return fail(ctx, TA_E_INVALID, p + "weight " + std::to_string(n) + " is not finite");
+    if (a.h_dims) {
+        const int axes[3] = {0, 1, 2};
+        const std::string why = box_table(a.h_dims, T, 3, axes, 8, box);
+        if (!why.empty()) return fail(ctx, TA_E_INVALID, p + why);
+    }
+    return TA_OK;
+}
+
+// The nine rows of orient_math.hpp's box (H's six entries, M's diagonal) of unwrap_box.hpp's table, tpitch doubles each
+void orient_box_rows(const BoxTable& box, double* out) {
+    static const int rows[kOrientBoxRows] = {0, 1, 2, 3, 4, 5, 6 + diag_row(0), 6 + diag_row(1), 6 + diag_row(2)};
+    for (int r = 0; r < kOrientBoxRows; ++r)
+        memcpy(out + (size_t)r * box.tpitch, box.tab.data() + (size_t)rows[r] * box.tpitch, sizeof(double) * (size_t)box.tpitch);
+}
+
+// The table of a call on the device: box rows | weights | index rows (int32) | N zero labels (int32: the one species of the sum)
+struct OrientTab {
+    const double *box, *w;
+    long tpitch;
+    const int *index, *lab;
+};
+struct OrientPlan {
+    int mode = 0;
+    int64_t N = 0, tpitch = 0;  // tpitch 0: no box
+    bool weights = false;
+    size_t n_box() const { return (size_t)kOrientBoxRows * (size_t)tpitch; }
+    size_t n_index() const { return ((size_t)N * orient_row_len(mode) + 1) / 2; }  // in doubles
+};
+// The host half of one call, before it is opened: the table queued for upload on `st`.  Nothing on the device has been
+// written when this fails.
+int orient_plan(ta_ctx* ctx, const OrientArgs& a, const BoxTable& box, hipStream_t st, OrientPlan* p) {
+    p->mode = a.mode, p->N = a.N, p->tpitch = a.h_dims ? box.tpitch : 0, p->weights = a.h_w != nullptr;
+    const size_t n = p->n_box() + (p->weights ? (size_t)a.N : 0) + p->n_index() + ((size_t)a.N + 1) / 2;
+    double* h = nullptr;
+    TA_CHECK(ctx->orient_tab.begin(ctx, sizeof(double) * n, (void**)&h));
+    memset(h, 0, sizeof(double) * n);
+    if (a.h_dims) orient_box_rows(box, h);
+    h += p->n_box();
+    if (a.h_w) memcpy(h, a.h_w, sizeof(double) * (size_t)a.N), h += a.N;
+    memcpy(h, a.h_index, sizeof(int32_t) * (size_t)a.N * orient_row_len(a.mode));
+    return ctx->orient_tab.send(ctx, st);
+}
+OrientTab orient_tab(ta_ctx* ctx, const OrientPlan& p) {
+    const double* d = (const double*)ctx->orient_tab.dev.p;
+    const double* w = d + p.n_box();
+    const double* idx = w + (p.weights ? (size_t)p.N : 0);
+    return {p.tpitch ? d : nullptr, p.weights ? w : nullptr, (long)p.tpitch, (const int*)idx, (const int*)(idx + p.n_index())};
+}
+
+// One orientation call on a pair-major position slab of either element type, read as it is (the caller has opened the
+// call's bracket, it is closed here; orient_plan has queued the table).  Rank 1, when c1, total or coll is asked for: the
+// pass writes the block of N atoms u into Z, ONE VACF lag-sum evaluation of it is c1, ONE species-sum pass (one species,
+// the weights) with the fixed-order sum of its partials the total (T, 3).  Rank 2, when c2 is asked for: the pass writes
+// the 2 N pseudo-atoms of Q into the SAME scratch, ONE evaluation is c2.  coll: the pair-major copy of the total as one
+// atom with D = 3, ONE evaluation.  The call does not chunk (a lag sum split over vectors would change its bits): Z is
+// 3 N pitch 16 bytes or TA_E_NOMEM.  ev[1] / ev[2] bracket the (last) pass, unless an evaluation after it records its own.
+int orient_pm(ta_ctx* ctx, bool fft, const Slab& slab, const OrientPlan& p, double* d_c1, double* d_c2, double* d_total,
+              double* d_coll) {
+    const int64_t pitch = slab.pitch, T = slab.T, N = p.N;
+    hipStream_t st = slab.st;
+    TA_CHECK(ensure(ctx, ctx->orient_z, (size_t)3 * (size_t)N * (size_t)pitch * 16));
+    double* Z = (double*)ctx->orient_z.p;
+    const OrientTab tab = orient_tab(ctx, p);
+    double* tot = d_total;
+    if (d_coll) {
+        TA_CHECK(ensure(ctx, ctx->orient_work, pm_bytes(T, 3) + (d_total ? 0 : sizeof(double) * (size_t)T * 3)));
+        if (!tot) tot = (double*)((char*)ctx->orient_work.p + pm_bytes(T, 3));
+    }
+    const int n_parts = species_sum_parts(ctx->n_cu, 1, (long)T, (long)(3 * N));
+    if (tot) TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)n_parts * T * 3));
+    auto pass = [&](int rank) -> int {
+        TA_LAUNCH_MAIN(ctx, "k_orient", st,
+                       launch_orient(ctx->n_cu, slab.pm, slab.f32, (long)pitch, (long)T, (long)slab.A, slab.D, p.mode, rank, (long)N,
+                                     tab.index, tab.box, tab.tpitch, Z, st));
+        return TA_OK;
+    };
+    if (d_c1 || tot) {
+        TA_CHECK(pass(1));
+        if (d_c1) TA_CHECK(acf_impl(ctx, fft, Z, pitch, T, N, 3, d_c1, nullptr, 0, st));
+        if (tot) {
+            TA_LAUNCH(ctx, "k_species_current", st,
+                      launch_species_sum(Z, false, false, (long)pitch, (long)T, (long)(3 * N), 3, 1, tab.lab, tab.w,
+                                         (double*)ctx->ons_part.p, n_parts, st));
+            TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)(T * 3), tot, st));
+        }
+    }
+    if (d_c2) {
+        TA_CHECK(pass(2));
+        TA_CHECK(acf_impl(ctx, fft, Z, pitch, T, 2 * N, 3, d_c2, nullptr, 0, st));
+    }
+    if (d_coll) {  // (the phantom column and the rows T ... pitch - 1 as zeros: the workspace is reused)
+        TA_HIP_TRY(ctx, hipMemsetAsync(ctx->orient_work.p, 0, pm_bytes(T, 3), st));
+        TA_LAUNCH(ctx, "k_relayout", st, launch_relayout(tot, false, 3, 3, (long)T, ctx->orient_work.p, false, (long)pitch, 0, st));
+        TA_CHECK(acf_impl(ctx, fft, (const double*)ctx->orient_work.p, pitch, T, 1, 3, d_coll, nullptr, 0, st));
+    }
+    return call_end(ctx, st);
+}
+
+// ta_orient_dev / ta_orient_staged (dev NULL) and the device half of ta_orient (out != NULL: the context's own output
+// buffer c1 (T) | c2 (T) | total (T, 3) | coll (T) takes the place of the d_* pointers, which then only say what is asked for)
+int orient_entry(ta_ctx* ctx, const DevSrc* dev, int fft, int mode, int64_t N, const int32_t* h_index, const double* h_dims,
+                 const double* h_w, double* d_c1, double* d_c2, double* d_total, double* d_coll, void* stream, double** out) {
+    const OrientArgs a{fft, mode, N, h_index, h_dims, h_w, d_c1 != nullptr, d_c2 != nullptr, d_total != nullptr, d_coll != nullptr};
+    BoxTable box;
+    OrientPlan plan;
+    return slab_entry(
+        ctx, dev, stream,
+        [&] {
+            return dev ? orient_check(ctx, a, dev->T, dev->A, dev->D, &box)
+                       : orient_check(ctx, a, ctx->st_T, ctx->st_A, ctx->st_nslabs ? ctx->st_D : 0, &box);
+        },
+        [&](const Slab& s) -> int {
+            TA_CHECK(orient_plan(ctx, a, box, s.st, &plan));
+            if (out) {
+                TA_CHECK(ensure(ctx, ctx->orient_out, sizeof(double) * (size_t)s.T * 6));
+                *out = (double*)ctx->orient_out.p;
+            }
+            return TA_OK;
+        },
+        [&](const Slab& s) {
+            if (!out) return orient_pm(ctx, fft != 0, s, plan, d_c1, d_c2, d_total, d_coll);
+            double* o = *out;
+            return orient_pm(ctx, fft != 0, s, plan, a.c1 ? o : nullptr, a.c2 ? o + s.T : nullptr, a.total ? o + 2 * s.T : nullptr,
+                             a.coll ? o + 5 * s.T : nullptr);
+        });
 }
 
 // ---- current correlation functions (kcurrent.hip) -------------------------------------------------------------------
@@ -2368,6 +2537,24 @@ int ta_scatter_staged(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, doub
     });
 }
 
+// Orientational correlation functions: slab 0 / d_pos holds the positions (three columns per atom); the staged slab is read
+// in its own element type (never widened); the index rows, the boxes and the weights are HOST arrays, checked and queued
+// for upload before the call is opened
+int ta_orient_dev(ta_ctx* ctx, const double* d_pos, int64_t T, int64_t A, int D, int64_t ld_row, int fft, int mode, int64_t n_vectors,
+                  const int32_t* h_index, const double* h_dimensions, const double* h_weights, double* d_c1, double* d_c2,
+                  double* d_total, double* d_coll, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    const DevSrc src{d_pos, T, A, D, ld_row};
+    return orient_entry(ctx, &src, fft, mode, n_vectors, h_index, h_dimensions, h_weights, d_c1, d_c2, d_total, d_coll, stream, nullptr);
+    });
+}
+int ta_orient_staged(ta_ctx* ctx, int fft, int mode, int64_t n_vectors, const int32_t* h_index, const double* h_dimensions,
+                     const double* h_weights, double* d_c1, double* d_c2, double* d_total, double* d_coll, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    return orient_entry(ctx, nullptr, fft, mode, n_vectors, h_index, h_dimensions, h_weights, d_c1, d_c2, d_total, d_coll, stream, nullptr);
+    });
+}
+
 // Current correlation functions: slab 0 holds the velocities, slab 1 the positions, both read in the element type they have
 // (never widened); the wavevectors are a HOST array, the weights a device one (or NULL); there is no frame-major entry
 int ta_kcurrent_staged(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, const double* d_weights, double* d_current,
@@ -3053,6 +3240,31 @@ int ta_scatter(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, double* h_s
     TA_CHECK(ta::scatter_launch(ctx, fft, n_k, h_kvecs, h_self != nullptr, h_density != nullptr, h_coll != nullptr, &d_out));
     const size_t KT = (size_t)n_k * (size_t)ctx->st_T;
     return host_finish(ctx, {{h_self, d_out, KT}, {h_density, d_out + KT, 2 * KT}, {h_coll, d_out + 3 * KT, KT}});
+    });
+}
+
+int ta_orient(ta_ctx* ctx, int fft, int mode, int64_t n_vectors, const int32_t* h_index, const double* h_dimensions,
+              const double* h_weights, double* h_c1, double* h_c2, double* h_total, double* h_coll) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    if (ctx->is_cpu) {
+        const OrientArgs a{fft, mode, n_vectors, h_index, h_dimensions, h_weights, h_c1 != nullptr, h_c2 != nullptr, h_total != nullptr,
+                           h_coll != nullptr};
+        BoxTable box;
+        TA_CHECK(orient_check(ctx, a, ctx->st_T, ctx->st_A, ctx->st_nslabs ? ctx->st_D : 0, &box));
+        std::vector<double> rows;
+        if (h_dimensions) {
+            rows.resize((size_t)kOrientBoxRows * (size_t)box.tpitch);
+            orient_box_rows(box, rows.data());
+        }
+        return cpu_rc(ctx, ta::cpu::orient(cpu_state(ctx), fft != 0, mode, n_vectors, h_index, h_dimensions ? rows.data() : nullptr,
+                                           box.tpitch, h_weights, h_c1, h_c2, h_total, h_coll));
+    }
+    double* d_out = nullptr;
+    TA_CHECK(orient_entry(ctx, nullptr, fft, mode, n_vectors, h_index, h_dimensions, h_weights, h_c1, h_c2, h_total, h_coll, ctx->stream,
+                          &d_out));
+    const size_t T = (size_t)ctx->st_T;
+    return host_finish(ctx, {{h_c1, d_out, T}, {h_c2, d_out + T, T}, {h_total, d_out + 2 * T, 3 * T}, {h_coll, d_out + 5 * T, T}});
     });
 }
 

@@ -40,6 +40,7 @@
 #include "../../include/ta_hip.h"
 #include "cpu_backend.hpp"
 #include "kcurrent_math.hpp"
+#include "orient_math.hpp"
 #include "unwrap_box.hpp"
 #include "vanhove_distinct_math.hpp"
 #include "vanhove_math.hpp"
@@ -600,6 +601,88 @@ int scatter(const State& s, bool fft, int K, const double* kvecs, double* self, 
         }
     }
     return coll ? scatter_collective(s.threads, fft, dens, K, T, coll) : TA_OK;
+}
+
+template <class E, int MODE, bool PERIODIC>
+static void orient_frames(const State& s, int64_t N, const int32_t* index, const double* box, int64_t tpitch, const double* w,
+                          double* u_out, double* q_out, double* total) {
+    const int64_t T = s.T, A = s.A;
+    const void* slab = s.slabs[0];
+    constexpr int K = MODE == ORIENT_BOND ? 2 : 3;
+#pragma omp parallel for num_threads(s.threads) schedule(static)
+    for (int64_t t = 0; t < T; ++t) {
+        OrientBox bx{};
+        if (PERIODIC) {
+            const double* b = box + (tpitch == 1 ? 0 : t);
+            bx = OrientBox{b[0], b[tpitch], b[2 * tpitch], b[3 * tpitch], b[4 * tpitch], b[5 * tpitch], b[6 * tpitch], b[7 * tpitch],
+                           b[8 * tpitch]};
+        }
+        double m[3] = {0.0, 0.0, 0.0};
+        for (int64_t n = 0; n < N; ++n) {
+            double x[3][3] = {};
+            for (int j = 0; j < K; ++j)
+                for (int d = 0; d < 3; ++d) x[j][d] = elem<E>(slab, ((size_t)t * A + (size_t)index[n * K + j]) * 3 + d);
+            double db[3], dc[3] = {0.0, 0.0, 0.0}, v[3], u[3];
+            orient_diff<PERIODIC>(x[0], x[1], bx, db);
+            if (MODE != ORIENT_BOND) orient_diff<PERIODIC>(x[0], x[2], bx, dc);
+            orient_combine<MODE>(db, dc, v);
+            orient_unit(v, u);
+            if (u_out)
+                for (int d = 0; d < 3; ++d) u_out[((size_t)t * N + n) * 3 + d] = u[d];
+            if (q_out) orient_q(u, *reinterpret_cast<double(*)[6]>(q_out + ((size_t)t * N + n) * 6));
+            if (total) {
+                const double wn = w ? w[n] : 1.0;
+                for (int d = 0; d < 3; ++d) m[d] += wn * u[d];
+            }
+        }
+        if (total)
+            for (int d = 0; d < 3; ++d) total[(size_t)t * 3 + d] = m[d];
+    }
+}
+
+template <class E, int MODE>
+static void orient_frames_box(const State& s, int64_t N, const int32_t* index, const double* box, int64_t tpitch, const double* w,
+                              double* u_out, double* q_out, double* total) {
+    if (box) orient_frames<E, MODE, true>(s, N, index, box, tpitch, w, u_out, q_out, total);
+    else orient_frames<E, MODE, false>(s, N, index, box, tpitch, w, u_out, q_out, total);
+}
+template <class E>
+static void orient_frames_mode(int mode, const State& s, int64_t N, const int32_t* index, const double* box, int64_t tpitch,
+                               const double* w, double* u_out, double* q_out, double* total) {
+    if (mode == ORIENT_BOND) orient_frames_box<E, ORIENT_BOND>(s, N, index, box, tpitch, w, u_out, q_out, total);
+    else if (mode == ORIENT_BISECTOR) orient_frames_box<E, ORIENT_BISECTOR>(s, N, index, box, tpitch, w, u_out, q_out, total);
+    else orient_frames_box<E, ORIENT_NORMAL>(s, N, index, box, tpitch, w, u_out, q_out, total);
+}
+
+int orient(const State& s, bool fft, int mode, int64_t N, const int32_t* index, const double* box, int64_t tpitch, const double* w,
+           double* c1, double* c2, double* total, double* coll) {
+    const int64_t T = s.T;
+    std::vector<double> u, q, own;
+    try {
+        if (c1) u.assign((size_t)T * N * 3, 0.0);
+        if (c2) q.assign((size_t)T * N * 6, 0.0);
+        if (!total && coll) own.assign((size_t)T * 3, 0.0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    double* tot = total ? total : coll ? own.data() : nullptr;
+    double* up = c1 ? u.data() : nullptr;
+    double* qp = c2 ? q.data() : nullptr;
+    if (s.dtype == TA_F32) orient_frames_mode<float>(mode, s, N, index, box, tpitch, w, up, qp, tot);
+    else orient_frames_mode<double>(mode, s, N, index, box, tpitch, w, up, qp, tot);
+    auto acf = [&](int64_t A, double* data, double* out) {
+        const State v = f64_slab(s.threads, T, A, 3, data);
+        return fft ? vacf_fft(v, out, nullptr) : vacf_direct(v, out, nullptr);
+    };
+    if (c1)
+        if (int rc = acf(N, up, c1)) return rc;
+    if (c2)  // the (T, N, 6) array is a slab of 2 N pseudo-atoms with dim 3
+        if (int rc = acf(2 * N, qp, c2)) return rc;
+    if (coll) {
+        std::vector<double> m(tot, tot + (size_t)T * 3);  // (the evaluation may not write to the caller's total)
+        if (int rc = acf(1, m.data(), coll)) return rc;
+    }
+    return TA_OK;
 }
 
 int kcurrent_correlate(int threads, bool fft, const double* current, int K, const double* kvecs, int64_t T, int D, double* lon,

@@ -50,6 +50,13 @@ int species_self(const State& s, bool msd_quantity, bool fft, int n_species, con
 int scatter(const State& s, bool fft, int K, const double* kvecs, double* self, double* density, double* coll);
 // coll (K, n_frames): the autocorrelations of the K densities (K, n_frames, 2), ONE by-particle vacf call on them as K atoms of dim 2
 int scatter_collective(int threads, bool fft, const double* density, int K, int64_t n_frames, double* coll);
+// ta_orient: the orientation columns of N vectors (index rows of 2 or 3 atoms of slab 0 by `mode`, dim 3) with orient_math.hpp's
+// arithmetic, as orient.hip: OpenMP over frames, the frame-major (n_frames, N, 3) array of u and the (n_frames, 2 N, 3) array of
+// Q's columns; c1, c2 (n_frames) = their vacf_fft / vacf_direct lag sums, total (n_frames, 3) = sum_n w_n u_n in vector order (w
+// NULL: all 1), coll (n_frames) = the same evaluation of the total as one atom; each may be NULL.  box: NULL or the nine rows
+// (H00 H10 H11 H20 H21 H22 M00 M11 M22) of tpitch doubles (tpitch 1: one constant box); arguments checked by the caller
+int orient(const State& s, bool fft, int mode, int64_t N, const int32_t* index, const double* box, int64_t tpitch, const double* w,
+           double* c1, double* c2, double* total, double* coll);
 // ta_kcurrent: the k-space current of slab 0 (the velocities) and slab 1 (the positions) for K wavevectors kvecs (K, dim), with
 // kcurrent.hip's arithmetic (the phase as scatter(); w_n v by a product, then one fma with the cosine and one with the sine):
 // current (K, n_frames, dim, 2) = the plain sum in atom order (w NULL: all 1), lon / trans (K, n_frames) = kcurrent_correlate

@@ -359,6 +359,14 @@ hipError_t launch_phase(int n_cu, const void* x, bool f32, long pitch, long T, l
                         double* Z, hipStream_t st);
 hipError_t launch_scatter_transpose(const double* bp, long T, long K, double* out, hipStream_t st);
 
+// orient.hip: one float64 pair-major block of the orientation columns of n_vectors vectors (orient_math.hpp: mode, the index
+// rows of orient_row_len(mode) atoms, device int32) of a pair-major slab of float64 or (f32) float32 elements with D = 3, read
+// as it is: rank 1 = n_vectors atoms of dim 3 holding u, rank 2 = 2 n_vectors pseudo-atoms of dim 3 holding Q's six columns;
+// `pitch` rows per pair, rows T ... pitch - 1 zeros; Z has 3 n_vectors pairs.  box: NULL (no image step) or the device table
+// of kOrientBoxRows rows of tpitch doubles (tpitch 1: one constant box; else one box per frame, tpitch >= T)
+hipError_t launch_orient(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, int mode, int rank,
+                         long n_vectors, const int* index, const double* box, long tpitch, double* Z, hipStream_t st);
+
 // kcurrent.hip: the k-space current of kc <= KC wavevectors q (kc, D) (device array, turns per length unit) from the pair-major
 // slabs v (velocities) and x (positions) of float64 or (f32) float32 elements, both read as they are, in one pass: partial
 // [n_parts][kc][T][D] (re, im) sums over the atoms g, g + n_parts, ... of w_n v (cos, sin)(2 pi q . x) (written in full;

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._base import CollectiveAnalysis, parse_dim_type
+from ._base import CollectiveAnalysis, first_crossing, parse_dim_type
 
 
 def triclinic_vectors(dimensions):
@@ -232,12 +232,4 @@ class IntermediateScattering(BoxWavevectors, CollectiveAnalysis):
             raise RuntimeError("Analysis must be run prior to reading relaxation times")
         t = self.lag_times()
         fs = self.results.fs
-        out = np.full(fs.shape[1], np.nan)
-        for s in range(fs.shape[1]):
-            y = fs[:, s] / fs[0, s]
-            below = np.flatnonzero(y < level)
-            if below.size == 0:
-                continue
-            i = int(below[0])
-            out[s] = t[0] if i == 0 else t[i - 1] + (level - y[i - 1]) * (t[i] - t[i - 1]) / (y[i] - y[i - 1])
-        return out
+        return np.array([first_crossing(t, fs[:, s] / fs[0, s], level) for s in range(fs.shape[1])])
