@@ -23,6 +23,7 @@
 #include "direct_kernels.hpp"
 #include "kcurrent_math.hpp"
 #include "orient_math.hpp"
+#include "phase_math.hpp"
 #include "ta_internal.hpp"
 #include "unwrap_box.hpp"
 #include "vanhove_distinct_math.hpp"
@@ -277,6 +278,10 @@ int no_cpu(ta_ctx* ctx) {
 #define TA_NO_CPU(ctx) TA_CHECK(no_cpu(ctx))
 int check_staged(ta_ctx* ctx, int n_slabs = 1) {
     return ctx->st_nslabs >= n_slabs ? TA_OK : fail(ctx, TA_E_STATE, "slabs have not been staged");
+}
+// the kernels index a slab's columns in 32 bits: "<prefix>n_atoms * <what> must be below 2^31" (D: what `what` names)
+int check_cols(ta_ctx* ctx, const std::string& prefix, int64_t A, int D, const char* what = "dim") {
+    return A * D < (int64_t)1 << 31 ? TA_OK : fail(ctx, TA_E_INVALID, prefix + "n_atoms * " + what + " must be below 2^31");
 }
 int check_slab(ta_ctx* ctx, int slab) {
     return slab >= 0 && slab < ctx->st_nslabs ? TA_OK : fail(ctx, TA_E_INVALID, "no such slab");
@@ -1075,8 +1080,7 @@ int coll_cross(ta_ctx* ctx, const Collective& q, bool fft, const double* d_sums,
 int coll_pm(ta_ctx* ctx, const Collective& q, bool fft, const Slab& s, int S, const int32_t* d_species, const double* d_w,
             double* d_sums, double* d_cross) {
     const int64_t T = s.T, n_cols = s.A * s.D;
-    if (n_cols >= (int64_t)1 << 31)
-        return fail(ctx, TA_E_INVALID, std::string("Onsager ") + q.noun + ": n_atoms * dim must be below 2^31");
+    TA_CHECK(check_cols(ctx, std::string("Onsager ") + q.noun + ": ", s.A, s.D));
     const void* pm = s.pm;
     const bool widen = s.f32 && q.shift;
     if (widen) TA_CHECK(widen_input(ctx, 0, s.pitch, n_cols, s.st, &pm));
@@ -1089,6 +1093,19 @@ int coll_pm(ta_ctx* ctx, const Collective& q, bool fft, const Slab& s, int S, co
     TA_LAUNCH(ctx, "k_sum_partials", s.st, launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)n_out, d_sums, s.st));
     if (d_cross) TA_CHECK(coll_cross(ctx, q, fft, d_sums, S, T, s.D, d_cross, s.st));
     return call_end(ctx, s.st);
+}
+
+// The weighted total of a pair-major block of n atoms with D columns each, sum_n w_n x[t, n, :] -> d_total (T, D): ONE
+// species-sum pass without shift (one species: the n zero labels d_lab; d_w NULL: weights 1) and the fixed-order sum of
+// its partials.  n_parts = species_sum_parts(n_cu, 1, T, n D), and ons_part holds n_parts T D doubles: the caller's ensure,
+// which comes before its launches.
+int weighted_total(ta_ctx* ctx, const void* pm, bool f32, int64_t pitch, int64_t T, int64_t n, int D, const int* d_lab,
+                   const double* d_w, int n_parts, double* d_total, hipStream_t st) {
+    TA_LAUNCH(ctx, "k_species_current", st,
+              launch_species_sum(pm, f32, false, (long)pitch, (long)T, (long)(n * D), D, 1, d_lab, d_w, (double*)ctx->ons_part.p,
+                                 n_parts, st));
+    TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)(T * D), d_total, st));
+    return TA_OK;
 }
 
 int coll_args(ta_ctx* ctx, const Collective& q, int fft, int S, const void* species, const void* sums) {
@@ -1113,7 +1130,7 @@ int self_args(ta_ctx* ctx, int quantity, int fft, int S, const void* species, co
 // The host half of one call: the labels checked, the blocks laid out, the sorted order (one int32 per atom) queued for
 // upload on `st`.  Nothing on the device has been written when this fails.
 int self_plan(ta_ctx* ctx, int S, const int32_t* h_species, int64_t A, int D, hipStream_t st, SortPlan* plan) {
-    if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "species self terms: n_atoms * dim must be below 2^31");
+    TA_CHECK(check_cols(ctx, "species self terms: ", A, D));
     TA_CHECK(check_labels(fail, ctx, h_species, A, S));
     void* order = nullptr;
     TA_CHECK(ctx->self_order.begin(ctx, sizeof(int32_t) * (size_t)A, &order));
@@ -1172,12 +1189,11 @@ double* scatter_own_density(ta_ctx* ctx, int64_t T, int K) {
 // The host half of one call, before it is opened: the wavevectors in turns (q = k / 2 pi) queued for upload on `st`, the
 // buffers that do not depend on the chunking.  Nothing on the device has been written when this fails.
 int scatter_plan(ta_ctx* ctx, int K, const double* h_kvecs, int64_t A, int D, hipStream_t st) {
-    if (A * D >= (int64_t)1 << 31 || 2 * A >= (int64_t)1 << 31)
-        return fail(ctx, TA_E_INVALID, "scatter: n_atoms * max(dim, 2) must be below 2^31");
+    TA_CHECK(check_cols(ctx, "scatter: ", A, std::max(D, 2), "max(dim, 2)"));
     void* q = nullptr;
     TA_CHECK(ctx->scatter_q.begin(ctx, sizeof(double) * (size_t)K * D, &q));
     TA_CHECK(ensure(ctx, ctx->scatter_lab, sizeof(int32_t) * (size_t)A));
-    for (size_t i = 0; i < (size_t)K * D; ++i) ((double*)q)[i] = h_kvecs[i] / 6.283185307179586476925;
+    for (size_t i = 0; i < (size_t)K * D; ++i) ((double*)q)[i] = phase_turns(h_kvecs[i]);
     return ctx->scatter_q.send(ctx, st);
 }
 
@@ -1233,11 +1249,8 @@ int scatter_pm(ta_ctx* ctx, bool fft, const Slab& slab, int K, double* d_self, d
             const int64_t j = j0 + jl;
             if (d_self) TA_CHECK(acf_impl(ctx, fft, blk, pitch, T, A, 2, d_self + (size_t)j * T, nullptr, 0, st));
             if (!sums) continue;
-            TA_LAUNCH(ctx, "k_species_current", st,
-                      launch_species_sum(blk, false, false, (long)pitch, (long)T, (long)(2 * A), 2, 1, (const int*)ctx->scatter_lab.p,
-                                         nullptr, (double*)ctx->ons_part.p, n_parts, st));
-            TA_LAUNCH(ctx, "k_sum_partials", st,
-                      launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)(T * 2), rho + (size_t)j * T * 2, st));
+            TA_CHECK(weighted_total(ctx, blk, false, pitch, T, A, 2, (const int*)ctx->scatter_lab.p, nullptr, n_parts,
+                                    rho + (size_t)j * T * 2, st));
         }
     }
     if (d_coll) TA_CHECK(scatter_collective(ctx, fft, rho, K, T, d_coll, st));
@@ -1359,12 +1372,7 @@ int orient_pm(ta_ctx* ctx, bool fft, const Slab& slab, const OrientPlan& p, doub
     if (d_c1 || tot) {
         TA_CHECK(pass(1));
         if (d_c1) TA_CHECK(acf_impl(ctx, fft, Z, pitch, T, N, 3, d_c1, nullptr, 0, st));
-        if (tot) {
-            TA_LAUNCH(ctx, "k_species_current", st,
-                      launch_species_sum(Z, false, false, (long)pitch, (long)T, (long)(3 * N), 3, 1, tab.lab, tab.w,
-                                         (double*)ctx->ons_part.p, n_parts, st));
-            TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)(T * 3), tot, st));
-        }
+        if (tot) TA_CHECK(weighted_total(ctx, Z, false, pitch, T, N, 3, tab.lab, tab.w, n_parts, tot, st));
     }
     if (d_c2) {
         TA_CHECK(pass(2));
@@ -1416,8 +1424,7 @@ constexpr size_t kKcurBudget = (size_t)1 << 30;
 // the family's argument checks (GPU and CPU contexts, one set of messages): both slabs staged and their columns ...
 int kcurrent_slabs(ta_ctx* ctx) {
     TA_CHECK(check_staged(ctx, 2));
-    if (ctx->st_A * ctx->st_D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "kcurrent: n_atoms * dim must be below 2^31");
-    return TA_OK;
+    return check_cols(ctx, "kcurrent: ", ctx->st_A, ctx->st_D);
 }
 // ... behind the wavevectors and outputs
 int kcurrent_args(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, const void* o_current, const void* o_long,
@@ -1441,7 +1448,7 @@ int kcurrent_plan(ta_ctx* ctx, int K, const double* h_kvecs, int D, const double
     void* h = nullptr;
     TA_CHECK(ctx->kcur_tab.begin(ctx, sizeof(double) * (2 * n + (h_w ? (size_t)n_w : 0)), &h));
     double* q = (double*)h;
-    for (size_t i = 0; i < n; ++i) q[i] = h_kvecs[i] / 6.283185307179586476925;
+    for (size_t i = 0; i < n; ++i) q[i] = phase_turns(h_kvecs[i]);
     for (int j = 0; j < K; ++j) kcur_khat(D, h_kvecs + (size_t)j * D, q + n + (size_t)j * D);
     if (h_w) memcpy(q + 2 * n, h_w, sizeof(double) * (size_t)n_w);
     return ctx->kcur_tab.send(ctx, st);
@@ -1495,17 +1502,27 @@ int kcurrent_pm(ta_ctx* ctx, bool fft, const Slab& s, int K, const double* d_w, 
     return call_end(ctx, st);
 }
 
-// ---- self van Hove function (vanhove.hip) ---------------------------------------------------------------------------
-// The host half of one call, before it is opened: the lags and the squared edges e[0 ... B] (formed once, here) queued for
-// upload on `st` as one table.  Nothing on the device has been written when this fails.
-int vanhove_plan(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, int64_t A, int D, hipStream_t st) {
-    if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "vanhove: n_atoms * dim must be below 2^31");
+// ---- self van Hove function (vanhove.hip) and self-overlap (overlap.hip): what their host halves share --------------
+// The host half of one call, before it is opened: the lags, then the n_tail doubles that fill(tail) forms once, here, queued
+// for upload on `st` as one table.  Nothing on the device has been written when this fails.
+template <class Fill>
+int lag_table_plan(ta_ctx* ctx, HostTable& tab, const char* prefix, int L, const int64_t* h_lags, size_t n_tail, Fill&& fill,
+                   int64_t A, int D, hipStream_t st) {
+    TA_CHECK(check_cols(ctx, prefix, A, D));
     void* h = nullptr;
-    TA_CHECK(ctx->vh_tab.begin(ctx, sizeof(double) * ((size_t)L + (size_t)B + 1), &h));
+    TA_CHECK(tab.begin(ctx, sizeof(double) * ((size_t)L + n_tail), &h));
     static_assert(sizeof(int64_t) == sizeof(double), "the lags travel in the table's first n_lags slots");
     memcpy(h, h_lags, sizeof(int64_t) * (size_t)L);
-    vh_edges(B, dr, (double*)h + L);
-    return ctx->vh_tab.send(ctx, st);
+    fill((double*)h + L);
+    return tab.send(ctx, st);
+}
+// the lags of one launch: the family's chunk option (0: all L), at most L and what the kernel fits
+int lag_chunk(int64_t opt, int L, int fit) { return (int)std::min<int64_t>({opt > 0 ? opt : (int64_t)L, (int64_t)L, (int64_t)fit}); }
+
+// ---- self van Hove function (vanhove.hip) ---------------------------------------------------------------------------
+// the table's tail: the squared edges e[0 ... B]
+int vanhove_plan(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, int64_t A, int D, hipStream_t st) {
+    return lag_table_plan(ctx, ctx->vh_tab, "vanhove: ", L, h_lags, (size_t)B + 1, [&](double* e) { vh_edges(B, dr, e); }, A, D, st);
 }
 
 // One van Hove call on a pair-major position slab of either element type, read as it is (the caller has opened the call's
@@ -1515,8 +1532,7 @@ int vanhove_plan(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, in
 // launch: the same bits for every chunk size.  ev[1] / ev[2] bracket the (last) pass.
 int vanhove_pm(ta_ctx* ctx, const Slab& slab, int L, int B, double dr, int64_t* d_counts, double* d_moments) {
     hipStream_t st = slab.st;
-    const int fit = vanhove_max_chunk(B);
-    const int Lc = (int)std::min<int64_t>({ctx->opt_vanhove_chunk > 0 ? ctx->opt_vanhove_chunk : (int64_t)L, (int64_t)L, (int64_t)fit});
+    const int Lc = lag_chunk(ctx->opt_vanhove_chunk, L, vanhove_max_chunk(B));
     const int n_parts = vanhove_parts(ctx->n_cu, (long)slab.pitch, (long)slab.A);
     const size_t hist_bytes = sizeof(int64_t) * (size_t)L * (size_t)(B + 1);
     TA_CHECK(ensure(ctx, ctx->vh_hist, hist_bytes));
@@ -1536,16 +1552,9 @@ int vanhove_pm(ta_ctx* ctx, const Slab& slab, int L, int B, double dr, int64_t* 
 }
 
 // ---- self-overlap per origin (overlap.hip) --------------------------------------------------------------------------
-// The host half of one call, before it is opened: the lags and the squared cutoffs a2[c] = fl(a_c a_c) (formed once, here)
-// queued for upload on `st` as one table.  Nothing on the device has been written when this fails.
+// the table's tail: the squared cutoffs a2[c] = fl(a_c a_c)
 int overlap_plan(ta_ctx* ctx, int L, const int64_t* h_lags, int C, const double* h_cutoffs, int64_t A, int D, hipStream_t st) {
-    if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "overlap: n_atoms * dim must be below 2^31");
-    void* h = nullptr;
-    TA_CHECK(ctx->ov_tab.begin(ctx, sizeof(double) * ((size_t)L + (size_t)C), &h));
-    static_assert(sizeof(int64_t) == sizeof(double), "the lags travel in the table's first n_lags slots");
-    memcpy(h, h_lags, sizeof(int64_t) * (size_t)L);
-    vh_cutoffs2(C, h_cutoffs, (double*)h + L);
-    return ctx->ov_tab.send(ctx, st);
+    return lag_table_plan(ctx, ctx->ov_tab, "overlap: ", L, h_lags, (size_t)C, [&](double* a2) { vh_cutoffs2(C, h_cutoffs, a2); }, A, D, st);
 }
 
 // One overlap call on a pair-major position slab of either element type, read as it is (the caller has opened the call's
@@ -1554,8 +1563,7 @@ int overlap_plan(ta_ctx* ctx, int L, const int64_t* h_lags, int C, const double*
 // same bits for every chunk size.  ev[1] / ev[2] bracket the (last) launch.
 int overlap_pm(ta_ctx* ctx, const Slab& slab, int L, int C, int64_t* d_q) {
     hipStream_t st = slab.st;
-    const int fit = std::max(1, overlap_slots() / C);
-    const int Lc = (int)std::min<int64_t>({ctx->opt_overlap_chunk > 0 ? ctx->opt_overlap_chunk : (int64_t)L, (int64_t)L, (int64_t)fit});
+    const int Lc = lag_chunk(ctx->opt_overlap_chunk, L, std::max(1, overlap_slots() / C));
     const int64_t* d_lags = (const int64_t*)ctx->ov_tab.dev.p;
     const double* d_a2 = (const double*)ctx->ov_tab.dev.p + L;
     TA_HIP_TRY(ctx, hipMemsetAsync(d_q, 0, sizeof(int64_t) * (size_t)C * (size_t)L * (size_t)slab.T, st));
@@ -1619,7 +1627,7 @@ static int vhd_index_list(ta_ctx* ctx, const char* name, int64_t n, const int64_
 // Everything that needs the staged shape (T, A, D), checked before anything is written
 int vhd_plan(ta_ctx* ctx, const VhdArgs& args, int64_t T, int64_t A, int D, VhdPlan* p) {
     auto [L, B, dr, stride, n_a, n_b, h_lags, h_idx_a, h_idx_b, h_dims, axes] = args;
-    if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_atoms * dim must be below 2^31");
+    TA_CHECK(check_cols(ctx, "vanhove_distinct: ", A, D));
     p->L = L, p->B = B, p->D = D, p->T = T, p->stride = stride;
     p->n_a = h_idx_a ? n_a : A;
     TA_CHECK(vhd_index_list(ctx, "a", p->n_a, h_idx_a, A, VHD_TILE_A, &p->ida, &p->pitch_a));
@@ -3323,7 +3331,7 @@ int ta_vanhove(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, doubl
     TA_CHECK(check_vanhove(fail, ctx, n_lags, h_lags, n_bins, dr, ctx->st_nslabs ? ctx->st_T : 0, h_counts || h_moments));
     TA_CHECK(check_staged(ctx));
     if (ctx->is_cpu) {
-        if (ctx->st_A * ctx->st_D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "vanhove: n_atoms * dim must be below 2^31");
+        TA_CHECK(check_cols(ctx, "vanhove: ", ctx->st_A, ctx->st_D));
         return cpu_rc(ctx, ta::cpu::vanhove(cpu_state(ctx), n_lags, h_lags, n_bins, dr, h_counts, h_moments));
     }
     void* d_out = nullptr;
@@ -3340,7 +3348,7 @@ int ta_overlap(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_cutoffs, co
     TA_CHECK(check_overlap(fail, ctx, n_lags, h_lags, n_cutoffs, h_cutoffs, ctx->st_nslabs ? ctx->st_T : 0, h_q != nullptr));
     TA_CHECK(check_staged(ctx));
     if (ctx->is_cpu) {
-        if (ctx->st_A * ctx->st_D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "overlap: n_atoms * dim must be below 2^31");
+        TA_CHECK(check_cols(ctx, "overlap: ", ctx->st_A, ctx->st_D));
         return cpu_rc(ctx, ta::cpu::overlap(cpu_state(ctx), n_lags, h_lags, n_cutoffs, h_cutoffs, h_q));
     }
     int64_t* d_out = nullptr;
@@ -3395,7 +3403,7 @@ int ta_compound(ta_ctx* ctx, int64_t n_compounds, const int64_t* h_offsets, cons
     if (ctx->st_nslabs != 1) return fail(ctx, TA_E_UNSUPPORTED, "compound: one staged slab only (this context holds " + std::to_string(ctx->st_nslabs) + ")");
     const int64_t T = ctx->st_T, A = ctx->st_A, C = n_compounds;
     const int D = ctx->st_D;
-    if (A * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "compound: n_atoms * dim must be below 2^31");
+    TA_CHECK(check_cols(ctx, "compound: ", A, D));
     if (C * D >= (int64_t)1 << 31) return fail(ctx, TA_E_INVALID, "compound: n_compounds * dim must be below 2^31");
     if (h_offsets[0] != 0) return fail(ctx, TA_E_INVALID, "compound: offsets must start at 0");
     for (int64_t c = 0; c < C; ++c)
@@ -3464,15 +3472,10 @@ int ta_compound(ta_ctx* ctx, int64_t n_compounds, const int64_t* h_offsets, cons
             d_F = (const double*)ctx->comp_f.p;
         }
         TA_CHECK(call_begin(ctx, st));
-        if (d_F) {
-            const int n_parts = species_sum_parts(ctx->n_cu, 1, (long)T, (long)n_cols);
-            TA_LAUNCH(ctx, "k_species_current", st,
-                      launch_species_sum(ctx->d_slabs[0], ctx->st_dev_f32, false, (long)pitch, (long)T, (long)n_cols, D, 1,
-                                         (const int*)ctx->ons_lab.p, (const double*)ctx->ons_w.p, (double*)ctx->ons_part.p,
-                                         n_parts, st));
-            TA_LAUNCH(ctx, "k_sum_partials", st,
-                      launch_sum_partials((const double*)ctx->ons_part.p, n_parts, (long)(T * D), (double*)ctx->comp_f.p, st));
-        }
+        if (d_F)
+            TA_CHECK(weighted_total(ctx, ctx->d_slabs[0], ctx->st_dev_f32, pitch, T, A, D, (const int*)ctx->ons_lab.p,
+                                    (const double*)ctx->ons_w.p, species_sum_parts(ctx->n_cu, 1, (long)T, (long)n_cols),
+                                    (double*)ctx->comp_f.p, st));
         TA_LAUNCH_MAIN(ctx, "k_compound", st,
                        launch_compound(ctx->n_cu, ctx->d_slabs[0], ctx->st_dev_f32, (long)pitch, (long)T, (long)n_cols, D, (long)C,
                                        d_off, d_off + n_off, h_weights ? d_w : nullptr, d_w + (h_weights ? (size_t)M : 0), d_F,

@@ -100,19 +100,6 @@ __global__ void __launch_bounds__(kPmThreads)
     }
 }
 
-template <class E, int D>
-void cmp_launch(dim3 grid, hipStream_t st, const void* x, long pitch, long T, int C, const int* off, const int* member,
-                const double* w, const double* g, const double* F, double* out) {
-    hipLaunchKernelGGL((k_compound<E, D>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, C, off, member, w, g, F, out);
-}
-template <class E>
-void cmp_launch_dim(int D, dim3 grid, hipStream_t st, const void* x, long pitch, long T, int C, const int* off,
-                    const int* member, const double* w, const double* g, const double* F, double* out) {
-    if (D == 1) cmp_launch<E, 1>(grid, st, x, pitch, T, C, off, member, w, g, F, out);
-    else if (D == 2) cmp_launch<E, 2>(grid, st, x, pitch, T, C, off, member, w, g, F, out);
-    else cmp_launch<E, 3>(grid, st, x, pitch, T, C, off, member, w, g, F, out);
-}
-
 }  // namespace
 
 hipError_t launch_compound(int n_cu, const void* x, bool f32, long pitch, long T, long n_cols, int D, long n_compounds,
@@ -122,8 +109,11 @@ hipError_t launch_compound(int n_cu, const void* x, bool f32, long pitch, long T
         n_compounds * D >= (1L << 31) || (F && !g))
         return hipErrorInvalidValue;
     const dim3 grid = pm_unit_grid(n_cu, pitch, (n_compounds + 1) / 2);
-    if (f32) cmp_launch_dim<float>(D, grid, st, x, pitch, T, (int)n_compounds, off, member, w, g, F, out);
-    else cmp_launch_dim<double>(D, grid, st, x, pitch, T, (int)n_compounds, off, member, w, g, F, out);
+    pm_dispatch(f32, D, [&](auto e, auto d) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((k_compound<E, d()>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, (int)n_compounds, off, member,
+                           w, g, F, out);
+    });
     return hipGetLastError();
 }
 

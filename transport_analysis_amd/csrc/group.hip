@@ -315,16 +315,23 @@ int drained(ta_group* g, const std::vector<int>& who, int rc) {
 }
 
 // The sum over members of what each leaves on its device.  launch(i, &d) queues member i's share and returns its device
-// result; of that result every part (n doubles at offset off; h NULL: skipped) is copied into a host vector of the member's
-// own.  A copy's HIP error is the group's own failure ("<what> copy: ..."); any failure drains the members first.  Then
-// every member is waited for, each part's h zeroed and the members' values added in member order (who: the members called).
+// result, an array of 8-byte elements; of that result every part (n elements at offset off, float64 or int64; h NULL:
+// skipped) is copied into a host vector of the member's own.  A copy's HIP error is the group's own failure ("<what> copy:
+// ..."); any failure drains the members first.  Then every member is waited for, each part's h zeroed and the members'
+// values added in member order, int64 parts as int64 (who: the members called).
 struct MemberPart {
+    enum Kind { F64, I64 };
     size_t off, n;
-    double* h;
+    void* h;
+    Kind kind = F64;
+};
+union MemberWord {  // (the copies fill it bytewise)
+    double f;
+    int64_t i;
 };
 template <class Launch>
 int sum_members(ta_group* g, std::vector<int>& who, const char* what, std::initializer_list<MemberPart> parts, Launch&& launch) {
-    std::vector<std::vector<double>> got(g->ctx.size());
+    std::vector<std::vector<MemberWord>> got(g->ctx.size());
     size_t total = 0;
     for (const MemberPart& p : parts) total += p.h ? p.n : 0;
     hipError_t he = hipSuccess;
@@ -332,7 +339,7 @@ int sum_members(ta_group* g, std::vector<int>& who, const char* what, std::initi
         double* d = nullptr;
         if (const int r = launch(i, &d)) return r;
         got[i].resize(total);  // (once: copies into it are in flight from here on)
-        double* dst = got[i].data();
+        MemberWord* dst = got[i].data();
         for (const MemberPart& p : parts) {
             if (!p.h || he != hipSuccess) continue;
             he = hipMemcpyAsync(dst, d + p.off, sizeof(double) * p.n, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
@@ -344,12 +351,15 @@ int sum_members(ta_group* g, std::vector<int>& who, const char* what, std::initi
     if (rc) return drained(g, who, rc);
     if ((rc = wait_members(g, who))) return rc;
     for (const MemberPart& p : parts)
-        if (p.h) std::fill(p.h, p.h + p.n, 0.0);
+        if (p.h) memset(p.h, 0, sizeof(double) * p.n);  // (+0.0 and 0)
     for (int i : who) {
-        const double* src = got[i].data();
+        const MemberWord* src = got[i].data();
         for (const MemberPart& p : parts) {
             if (!p.h) continue;
-            for (size_t k = 0; k < p.n; ++k) p.h[k] += src[k];
+            if (p.kind == MemberPart::I64)
+                for (size_t k = 0; k < p.n; ++k) ((int64_t*)p.h)[k] += src[k].i;
+            else
+                for (size_t k = 0; k < p.n; ++k) ((double*)p.h)[k] += src[k].f;
             src += p.n;
         }
     }
@@ -724,65 +734,40 @@ int ta_group_kcurrent(ta_group* g, int fft, int n_k, const double* h_kvecs, cons
     });
 }
 
-// Self van Hove function: every member's counts and moments of its atoms for the same lags and bins, copied into host
-// vectors of the members' own; then the counts are added as int64 and the moments in member order (both add up over
-// atoms: nothing follows the sums)
+// Self van Hove function: every member's counts and moments of its atoms for the same lags and bins, the counts added as
+// int64 and the moments in member order (both add up over atoms: nothing follows the sums)
 int ta_group_vanhove(ta_group* g, int n_lags, const int64_t* h_lags, int n_bins, double dr, int64_t* h_counts, double* h_moments) {
     return group_call(g, [&]() -> int {
     TAG_CHECK(check_group(g));
     TAG_CHECK(check_vanhove(gfail, g, n_lags, h_lags, n_bins, dr, g->T, h_counts || h_moments));
     TAG_CHECK(check_staged(g));
     const size_t nc = (size_t)n_lags * (size_t)(n_bins + 1), nm = 2 * (size_t)n_lags;
-    std::vector<std::vector<int64_t>> cnt(g->ctx.size());
-    std::vector<std::vector<double>> mom(g->ctx.size());
     std::vector<int> who;
-    hipError_t he = hipSuccess;
-    int rc = for_members(g, &who, [&](int i) {
-        void* d = nullptr;
-        if (const int r = vanhove_launch(g->ctx[i], n_lags, h_lags, n_bins, dr, h_counts != nullptr, h_moments != nullptr, &d)) return r;
-        cnt[i].resize(h_counts ? nc : 0), mom[i].resize(h_moments ? nm : 0);  // (once: copies into them are in flight from here on)
-        if (h_counts) he = hipMemcpyAsync(cnt[i].data(), d, sizeof(int64_t) * nc, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
-        if (h_moments && he == hipSuccess)
-            he = hipMemcpyAsync(mom[i].data(), (const int64_t*)d + nc, sizeof(double) * nm, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
-        return he == hipSuccess ? TA_OK : TA_E_HIP;
-    });
-    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string("van Hove sums copy: ") + hipGetErrorString(he));
-    if (rc) return drained(g, who, rc);
-    TAG_CHECK(wait_members(g, who));
-    if (h_counts) std::fill(h_counts, h_counts + nc, (int64_t)0);
-    if (h_moments) std::fill(h_moments, h_moments + nm, 0.0);
-    for (int i : who) {
-        for (size_t k = 0; h_counts && k < nc; ++k) h_counts[k] += cnt[i][k];
-        for (size_t k = 0; h_moments && k < nm; ++k) h_moments[k] += mom[i][k];
-    }
+    TAG_CHECK(sum_members(g, who, "van Hove sums", {{0, nc, h_counts, MemberPart::I64}, {nc, nm, h_moments}}, [&](int i, double** d) {
+        void* out = nullptr;
+        const int rc = vanhove_launch(g->ctx[i], n_lags, h_lags, n_bins, dr, h_counts != nullptr, h_moments != nullptr, &out);
+        *d = (double*)out;
+        return rc;
+    }));
     return TA_OK;
     });
 }
 
-// Self-overlap per origin: every member's Q of its atoms for the same lags and cutoffs, copied into host vectors of the
-// members' own, then added as int64 (Q adds up over atoms; a variance over origins is the caller's, after this sum)
+// Self-overlap per origin: every member's Q of its atoms for the same lags and cutoffs, added as int64 (Q adds up over
+// atoms; a variance over origins is the caller's, after this sum)
 int ta_group_overlap(ta_group* g, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs, int64_t* h_q) {
     return group_call(g, [&]() -> int {
     TAG_CHECK(check_group(g));
     TAG_CHECK(check_overlap(gfail, g, n_lags, h_lags, n_cutoffs, h_cutoffs, g->T, h_q != nullptr));
     TAG_CHECK(check_staged(g));
     const size_t nq = (size_t)n_cutoffs * (size_t)n_lags * (size_t)g->T;
-    std::vector<std::vector<int64_t>> part(g->ctx.size());
     std::vector<int> who;
-    hipError_t he = hipSuccess;
-    int rc = for_members(g, &who, [&](int i) {
-        int64_t* d = nullptr;
-        if (const int r = overlap_launch(g->ctx[i], n_lags, h_lags, n_cutoffs, h_cutoffs, &d)) return r;
-        part[i].resize(nq);  // (once: the copy into it is in flight from here on)
-        he = hipMemcpyAsync(part[i].data(), d, sizeof(int64_t) * nq, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
-        return he == hipSuccess ? TA_OK : TA_E_HIP;
-    });
-    if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string("overlap counts copy: ") + hipGetErrorString(he));
-    if (rc) return drained(g, who, rc);
-    TAG_CHECK(wait_members(g, who));
-    std::fill(h_q, h_q + nq, (int64_t)0);
-    for (int i : who)
-        for (size_t k = 0; k < nq; ++k) h_q[k] += part[i][k];
+    TAG_CHECK(sum_members(g, who, "overlap counts", {{0, nq, h_q, MemberPart::I64}}, [&](int i, double** d) {
+        int64_t* out = nullptr;
+        const int rc = overlap_launch(g->ctx[i], n_lags, h_lags, n_cutoffs, h_cutoffs, &out);
+        *d = (double*)out;
+        return rc;
+    }));
     return TA_OK;
     });
 }

@@ -4,10 +4,9 @@
 //
 // in ONE pass over both staged slabs (slab 0 = velocities, slab 1 = positions) per chunk of wavevectors: k_kcurrent reduces
 // over atoms in registers and writes partial sums per group of atoms, which k_sum_partials adds in a fixed order (no
-// atomics: the same bits from run to run).  Nothing of the size of a slab is written.  The phase arithmetic is k_phase's
-// (scatter.hip) to the letter: q = k / (2 pi) from the host, u = q . x by a product and then one fma per further term,
-// r = u - rint(u), (cos, sin)(2 pi r) by sincospi(2 r); every accumulator is then updated by one fma of (w_n v) with the
-// cosine and one with the sine.  k_kcurrent_project and k_kcurrent_finish are the two ends of the correlation
+// atomics: the same bits from run to run).  Nothing of the size of a slab is written.  The phase is phase_math.hpp's, the
+// one k_phase (scatter.hip) forms; every accumulator is then updated by one fma of (w_n v) with the cosine and one with the
+// sine.  k_kcurrent_project and k_kcurrent_finish are the two ends of the correlation
 // (kcurrent_math.hpp; api.hip: kcurrent_correlation).
 #include <hip/hip_runtime.h>
 
@@ -15,6 +14,7 @@
 #include <type_traits>
 
 #include "kcurrent_math.hpp"
+#include "phase_math.hpp"
 #include "pm_read.hpp"
 #include "ta_internal.hpp"
 
@@ -78,16 +78,11 @@ __global__ void __launch_bounds__(kPmThreads)
             const double q0 = q[j * D], q1 = D > 1 ? q[j * D + 1] : 0.0, q2 = D > 2 ? q[j * D + 2] : 0.0;
 #pragma unroll
             for (int f = 0; f < F; ++f) {
-                double u = q0 * pos[f][0];
-                if constexpr (D > 1) u = fma(q1, pos[f][1], u);
-                if constexpr (D > 2) u = fma(q2, pos[f][2], u);
-                const double r = u - rint(u);
-                double s, c;
-                sincospi(2.0 * r, &s, &c);
+                const double2 cs = phase_cs<D>(q0, q1, q2, pos[f]);
 #pragma unroll
                 for (int d = 0; d < D; ++d) {
-                    are[jl][f][d] = fma(vel[f][d], c, are[jl][f][d]);
-                    aim[jl][f][d] = fma(vel[f][d], s, aim[jl][f][d]);
+                    are[jl][f][d] = fma(vel[f][d], cs.x, are[jl][f][d]);
+                    aim[jl][f][d] = fma(vel[f][d], cs.y, aim[jl][f][d]);
                 }
             }
         }
@@ -144,20 +139,6 @@ __global__ void k_kcurrent_finish(const double* __restrict__ bp, int K, long T, 
     if (trans) trans[i] = tr;
 }
 
-template <class E, int D>
-void kcurrent_launch(dim3 grid, hipStream_t st, const void* v, const void* x, long pitch, long T, int A, const double* q, int kc,
-                     const double* w, double* partial) {
-    hipLaunchKernelGGL((k_kcurrent<E, D, kKC>), grid, dim3(kPmThreads), 0, st, (const E*)v, (const E*)x, pitch, T, A, q, kc, w,
-                       partial);
-}
-template <class E>
-void kcurrent_launch_dim(int D, dim3 grid, hipStream_t st, const void* v, const void* x, long pitch, long T, int A,
-                         const double* q, int kc, const double* w, double* partial) {
-    if (D == 1) kcurrent_launch<E, 1>(grid, st, v, x, pitch, T, A, q, kc, w, partial);
-    else if (D == 2) kcurrent_launch<E, 2>(grid, st, v, x, pitch, T, A, q, kc, w, partial);
-    else kcurrent_launch<E, 3>(grid, st, v, x, pitch, T, A, q, kc, w, partial);
-}
-
 long kcurrent_blocks(bool f32, long pitch) {
     const long fpb = (long)kPmThreads * (f32 ? kFramesOf<float> : kFramesOf<double>);
     return (pitch + fpb - 1) / fpb;
@@ -180,12 +161,13 @@ int kcurrent_parts(int n_cu, bool f32, long pitch, long n_atoms, int D, size_t b
 
 hipError_t launch_kcurrent(const void* v, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const double* q,
                            int kc, const double* w, double* partial, int n_parts, hipStream_t st) {
-    if (D < 1 || D > 3 || n_atoms < 1 || n_atoms * D >= (1L << 31) || (pitch & 7) || T < 1 || T > pitch || kc < 1 || kc > kKC ||
-        n_parts < 1 || n_parts > 65535)
-        return hipErrorInvalidValue;
+    if (!pm_slab_ok(pitch, T, n_atoms, D) || kc < 1 || kc > kKC || n_parts < 1 || n_parts > 65535) return hipErrorInvalidValue;
     const dim3 grid((unsigned)kcurrent_blocks(f32, pitch), (unsigned)n_parts);
-    if (f32) kcurrent_launch_dim<float>(D, grid, st, v, x, pitch, T, (int)n_atoms, q, kc, w, partial);
-    else kcurrent_launch_dim<double>(D, grid, st, v, x, pitch, T, (int)n_atoms, q, kc, w, partial);
+    pm_dispatch(f32, D, [&](auto e, auto d) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((k_kcurrent<E, d(), kKC>), grid, dim3(kPmThreads), 0, st, (const E*)v, (const E*)x, pitch, T, (int)n_atoms,
+                           q, kc, w, partial);
+    });
     return hipGetLastError();
 }
 

@@ -109,41 +109,25 @@ __global__ void __launch_bounds__(kPmThreads)
     }
 }
 
-template <class E, int MODE, int RANK>
-void orient_launch_box(dim3 grid, hipStream_t st, const void* x, long pitch, long T, int N, const int* index, const double* box,
-                       long tpitch, double* Z) {
-    if (!box)
-        hipLaunchKernelGGL((k_orient<E, MODE, RANK, BOX_NONE>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, N, index, box, tpitch, Z);
-    else if (tpitch == 1)
-        hipLaunchKernelGGL((k_orient<E, MODE, RANK, BOX_CONST>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, N, index, box, tpitch, Z);
-    else
-        hipLaunchKernelGGL((k_orient<E, MODE, RANK, BOX_FRAME>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, N, index, box, tpitch, Z);
-}
-template <class E, int MODE>
-void orient_launch_rank(int rank, dim3 grid, hipStream_t st, const void* x, long pitch, long T, int N, const int* index,
-                        const double* box, long tpitch, double* Z) {
-    if (rank == 1) orient_launch_box<E, MODE, 1>(grid, st, x, pitch, T, N, index, box, tpitch, Z);
-    else orient_launch_box<E, MODE, 2>(grid, st, x, pitch, T, N, index, box, tpitch, Z);
-}
-template <class E>
-void orient_launch_mode(int mode, int rank, dim3 grid, hipStream_t st, const void* x, long pitch, long T, int N, const int* index,
-                        const double* box, long tpitch, double* Z) {
-    if (mode == ORIENT_BOND) orient_launch_rank<E, ORIENT_BOND>(rank, grid, st, x, pitch, T, N, index, box, tpitch, Z);
-    else if (mode == ORIENT_BISECTOR) orient_launch_rank<E, ORIENT_BISECTOR>(rank, grid, st, x, pitch, T, N, index, box, tpitch, Z);
-    else orient_launch_rank<E, ORIENT_NORMAL>(rank, grid, st, x, pitch, T, N, index, box, tpitch, Z);
-}
-
 }  // namespace
 
 hipError_t launch_orient(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, int mode, int rank,
                          long n_vectors, const int* index, const double* box, long tpitch, double* Z, hipStream_t st) {
-    if (D != 3 || n_vectors < 1 || n_atoms < 1 || n_atoms * 3 >= (1L << 31) || 2 * n_vectors * 3 >= (1L << 31) || (pitch & 7) ||
-        T < 1 || T > pitch || mode < ORIENT_BOND || mode > ORIENT_NORMAL || (rank != 1 && rank != 2) || !index ||
-        (box && tpitch != 1 && tpitch < T))
+    if (D != 3 || !pm_slab_ok(pitch, T, n_atoms, D) || n_vectors < 1 || 2 * n_vectors * 3 >= (1L << 31) || mode < ORIENT_BOND ||
+        mode > ORIENT_NORMAL || (rank != 1 && rank != 2) || !index || (box && tpitch != 1 && tpitch < T))
         return hipErrorInvalidValue;
     const dim3 grid = pm_unit_grid(n_cu, pitch, rank == 1 ? (n_vectors + 1) / 2 : n_vectors);
-    if (f32) orient_launch_mode<float>(mode, rank, grid, st, x, pitch, T, (int)n_vectors, index, box, tpitch, Z);
-    else orient_launch_mode<double>(mode, rank, grid, st, x, pitch, T, (int)n_vectors, index, box, tpitch, Z);
+    // <MODE, RANK, BOX> as one variant number for the switch
+    static_assert(ORIENT_BOND == 0 && ORIENT_NORMAL == 2 && BOX_NONE == 0 && BOX_FRAME == 2, "the variant's digits");
+    const int variant = (mode * 2 + (rank - 1)) * 3 + (!box ? BOX_NONE : tpitch == 1 ? BOX_CONST : BOX_FRAME);
+    pm_element(f32, [&](auto e) {
+        pm_switch<0, 17>(variant, [&](auto v) {
+            using E = decltype(e);
+            constexpr int c = decltype(v)::value;
+            hipLaunchKernelGGL((k_orient<E, c / 6, c / 3 % 2 + 1, c % 3>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T,
+                               (int)n_vectors, index, box, tpitch, Z);
+        });
+    });
     return hipGetLastError();
 }
 

@@ -35,8 +35,7 @@ __device__ __forceinline__ double ov_r2(bool live, const double (&x0)[3], const 
 
 // Workgroup (bx, g) as k_vanhove's: origin frames [1024 bx, 1024 bx + 1024), atoms g, g + G, ... (G = gridDim.y); the atom's
 // columns at the thread's kPmFrames origin frames stay in registers across the launch's lags, and the lagged rows are read
-// as k_vanhove reads them (one 16-byte load per float64 row; float32: a 16-byte load for two rows at an even lag, 8-byte
-// loads at an odd one; a pair with t + tau >= T reads row 0 and counts nothing).
+// as k_vanhove reads them, by pm_lagged (pm_read.hpp; a pair with t + tau >= T reads row 0 and counts nothing).
 // Slot s = l C + c of the launch's lags l < Lc and the cutoffs c < C (Lc C <= kOvSlots).  Every index of cnt and thr is a
 // constant after unrolling: the lag loop is not unrolled, and which slots a lag owns is a UNIFORM test per slot.
 // lags: the launch's (lags + l0); q: Q + l0 T, its cutoffs q_ld = L T apart.
@@ -63,32 +62,7 @@ __global__ void __launch_bounds__(kPmThreads)
         for (int l = 0; l < Lc; ++l) {
             const long tau = lags[l];
             double r2[F];
-            if constexpr (!kF32) {
-#pragma unroll
-                for (int f = 0; f < F; ++f) {
-                    const long t2 = pm_frame<false>(tb, f) + tau;
-                    double lo[3], hi[3];
-                    a.load(t2 < T ? t2 : 0, lo, hi);
-                    r2[f] = ov_r2<D>(t2 < T, col[f], lo);
-                }
-            } else if ((tau & 1) == 0) {
-#pragma unroll
-                for (int f = 0; f < F; f += 2) {
-                    const long t2 = pm_frame<true>(tb, f) + tau;  // (even)
-                    double lo[3], hi[3];
-                    a.load(t2 < T ? t2 / 2 : 0, lo, hi);
-                    r2[f] = ov_r2<D>(t2 < T, col[f], lo);
-                    r2[f + 1] = ov_r2<D>(t2 + 1 < T, col[f + 1], hi);
-                }
-            } else {
-#pragma unroll
-                for (int f = 0; f < F; ++f) {
-                    const long t2 = pm_frame<true>(tb, f) + tau;
-                    double lo[3];
-                    a.row32(t2 < T ? t2 : 0, lo);
-                    r2[f] = ov_r2<D>(t2 < T, col[f], lo);
-                }
-            }
+            pm_lagged(a, T, tb, tau, [&](int f, bool live, const double(&x1)[3]) { r2[f] = ov_r2<D>(live, col[f], x1); });
             const int s0 = l * C;  // the lag's slots [s0, s0 + C): its cutoffs, smallest first
 #pragma unroll
             for (int s = 0; s < S; ++s) {
@@ -112,35 +86,25 @@ __global__ void __launch_bounds__(kPmThreads)
     }
 }
 
-template <class E, int D>
-hipError_t ov_launch(dim3 grid, hipStream_t st, const void* x, long pitch, long T, int A, const long* lags, int Lc, const double* a2,
-                     int C, unsigned long long* q, long q_ld) {
-    hipLaunchKernelGGL((k_overlap<E, D>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, A, lags, Lc, a2, C, q, q_ld);
-    return hipGetLastError();
-}
-template <class E, class... Args>
-hipError_t ov_launch_dim(int D, Args... args) {
-    if (D == 1) return ov_launch<E, 1>(args...);
-    if (D == 2) return ov_launch<E, 2>(args...);
-    return ov_launch<E, 3>(args...);
-}
-
 }  // namespace
 
 int overlap_slots() { return kOvSlots; }
 
 hipError_t launch_overlap(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const int64_t* lags, int l0,
                           int Lc, int L, const double* a2, int C, unsigned long long* q, hipStream_t st) {
-    if (D < 1 || D > 3 || n_atoms < 1 || n_atoms * D >= (1L << 31) || (pitch & 7) || T < 1 || T > pitch || C < 1 ||
-        C > TA_OVERLAP_MAX_CUTOFFS || Lc < 1 || Lc * C > kOvSlots || l0 < 0 || l0 + Lc > L)
+    if (!pm_slab_ok(pitch, T, n_atoms, D) || C < 1 || C > TA_OVERLAP_MAX_CUTOFFS || Lc < 1 || Lc * C > kOvSlots || l0 < 0 ||
+        l0 + Lc > L)
         return hipErrorInvalidValue;
     const dim3 grid = pm_unit_grid(n_cu, pitch, n_atoms);
-    static_assert(sizeof(long) == sizeof(int64_t), "lags are read as long");
-    const long* lg = reinterpret_cast<const long*>(lags) + l0;
+    const long* lg = pm_lags(lags) + l0;
     unsigned long long* q0 = q + (size_t)l0 * (size_t)T;
     const long q_ld = (long)L * T;
-    if (f32) return ov_launch_dim<float>(D, grid, st, x, pitch, T, (int)n_atoms, lg, Lc, a2, C, q0, q_ld);
-    return ov_launch_dim<double>(D, grid, st, x, pitch, T, (int)n_atoms, lg, Lc, a2, C, q0, q_ld);
+    pm_dispatch(f32, D, [&](auto e, auto d) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((k_overlap<E, d()>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, (int)n_atoms, lg, Lc, a2, C, q0,
+                           q_ld);
+    });
+    return hipGetLastError();
 }
 
 }  // namespace ta

@@ -1,6 +1,14 @@
-// pm_read.hpp — reading a pair-major slab in its own element type, and writing whole pairs of a float64 one: the pieces
-// shared by k_species_sum (species_sum.hip), k_species_sort (species_self.hip), k_compound (compound.hip), k_vanhove
-// (vanhove.hip) and k_vhd_gather (vanhove_distinct.hip).
+// pm_read.hpp — reading a pair-major slab in its own element type, and writing whole pairs of a float64 one.  Who shares what:
+//   pm_frame                      every kernel that walks frames: k_species_sum (species_sum.hip) and all of the following
+//   PmAtom, pm_load               k_species_sort (species_self.hip), k_compound (compound.hip), k_phase (scatter.hip), k_kcurrent
+//                                 (kcurrent.hip, PmAtom::load), k_orient (orient.hip), k_vanhove (vanhove.hip), k_overlap (overlap.hip)
+//   pm_lagged                     k_vanhove, k_overlap: row t + tau of the same atom
+//   PmAtom::row                   pm_lagged's odd float32 lag and float64 rows, k_vhd_gather (vanhove_distinct.hip)
+//   pm_store_row                  k_species_sort, k_compound, k_orient
+//   pm_unit_grid                  the launchers of the kernels that walk units
+//   pm_slab_ok, pm_lags,          the launchers: the shared precondition, the lags as the kernels read them, and the runtime
+//   pm_switch, pm_element,        (element type, dim) as template arguments of the one launch line
+//   pm_dispatch
 //
 // A pair is `pitch` rows of two columns along time (pitch a multiple of 8, T <= pitch frames are live).  Every load is 16
 // bytes: row t of a float64 pair, rows 2 q, 2 q + 1 of a float32 one (8-byte rows), widened in registers.  The rules:
@@ -12,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdint>
 #include <type_traits>
 
 namespace ta {
@@ -58,13 +67,17 @@ struct PmAtom {
         pm_pick<D>(qa.x, qa.y, qb.x, qb.y, odd, lo);
         if constexpr (kF32) pm_pick<D>(qa.z, qa.w, qb.z, qb.w, odd, hi);
     }
-    // row r (one frame) of a float32 atom alone: one 8-byte load per source pair, for the readers that must not take row
-    // r + 1 along (k_vanhove's lagged row at an odd lag, k_vhd_gather)
-    __device__ __forceinline__ void row32(long r, double (&out)[3]) const {
-        static_assert(kF32, "a float64 row is load()'s 16 bytes");
-        const float2* p = reinterpret_cast<const float2*>(src);
-        const float2 qa = p[r], qb = D == 3 ? p[2 * next + r] : qa;
-        pm_pick<D>(qa.x, qa.y, qb.x, qb.y, odd, out);
+    // row r (one frame) alone, in the slab's own type: float64 is load()'s 16 bytes, float32 one 8-byte load per source pair,
+    // for the readers that must not take row r + 1 along (pm_lagged at an odd lag, k_vhd_gather)
+    __device__ __forceinline__ void row(long r, double (&out)[3]) const {
+        if constexpr (kF32) {
+            const float2* p = reinterpret_cast<const float2*>(src);
+            const float2 qa = p[r], qb = D == 3 ? p[2 * next + r] : qa;
+            pm_pick<D>(qa.x, qa.y, qb.x, qb.y, odd, out);
+        } else {
+            double unused[3];
+            load(r, out, unused);
+        }
     }
 };
 
@@ -83,6 +96,34 @@ template <class E, int D>
 __device__ __forceinline__ void pm_load0(const PmAtom<E, D>& a, double (&col0)[3]) {
     double unused[3];
     a.load(0, col0, unused);
+}
+
+// Row t + tau of the same atom for the thread's kPmFrames origin frames t = pm_frame(tb, f): fn(f, live, row) per frame, in
+// frame order.  A float64 row is one 16-byte load at any t; two float32 rows share a 16-byte load when tau is even (origin
+// frames 2 m, 2 m + 1 -> rows 2 m + tau, 2 m + tau + 1), an odd tau takes 8-byte loads.  A row at or past T reads row 0 and is
+// not live: nothing is read at or past row T, but the second half of a float32 load at row T - 1 of an odd T, which lies
+// inside the pitch.
+template <class E, int D, class Fn>
+__device__ __forceinline__ void pm_lagged(const PmAtom<E, D>& a, long T, long tb, long tau, Fn&& fn) {
+    constexpr bool kF32 = PmAtom<E, D>::kF32;
+    if (kF32 && (tau & 1) == 0) {
+#pragma unroll
+        for (int f = 0; f < kPmFrames; f += 2) {
+            const long t2 = pm_frame<kF32>(tb, f) + tau;  // (even)
+            double lo[3], hi[3];
+            a.load(t2 < T ? t2 / 2 : 0, lo, hi);
+            fn(f, t2 < T, lo);
+            fn(f + 1, t2 + 1 < T, hi);
+        }
+    } else {
+#pragma unroll
+        for (int f = 0; f < kPmFrames; ++f) {
+            const long t2 = pm_frame<kF32>(tb, f) + tau;
+            double lo[3];
+            a.row(t2 < T ? t2 : 0, lo);
+            fn(f, t2 < T, lo);
+        }
+    }
 }
 
 // A work unit is two consecutive items (atoms, compounds) of D columns: 2 D columns = D WHOLE destination pairs from
@@ -104,6 +145,37 @@ inline dim3 pm_unit_grid(int n_cu, long pitch, long n_units) {
     const long n_tb = (pitch + kPmThreads * kPmFrames - 1) / (kPmThreads * kPmFrames);
     const long want = (16L * n_cu + n_tb - 1) / n_tb;
     return dim3((unsigned)n_tb, (unsigned)std::max(1L, std::min({want, n_units, 65535L})));
+}
+
+
+// ---- the host side of the launchers --------------------------------------------------------------------------------------
+// What every launcher of a kernel that reads a staged slab through PmAtom asks of it
+inline bool pm_slab_ok(long pitch, long T, long n_atoms, int D) {
+    return D >= 1 && D <= 3 && n_atoms >= 1 && n_atoms * D < (1L << 31) && !(pitch & 7) && T >= 1 && T <= pitch;
+}
+
+// the lags of a host-facing call (int64) as the kernels read them
+inline const long* pm_lags(const int64_t* lags) {
+    static_assert(sizeof(long) == sizeof(int64_t), "lags are read as long");
+    return reinterpret_cast<const long*>(lags);
+}
+
+// fn(std::integral_constant<int, v>) for a runtime v in [Lo, Hi] (checked by the caller: anything else takes Hi)
+template <int Lo, int Hi, class Fn>
+auto pm_switch(int v, Fn&& fn) {
+    if constexpr (Lo == Hi) return fn(std::integral_constant<int, Lo>{});
+    else return v == Lo ? fn(std::integral_constant<int, Lo>{}) : pm_switch<Lo + 1, Hi>(v, fn);
+}
+// fn(E()) for a slab's runtime element type, float32 or float64 ...
+template <class Fn>
+auto pm_element(bool f32, Fn&& fn) {
+    return f32 ? fn(float()) : fn(double());
+}
+// ... and fn(E(), std::integral_constant<int, D>) with its dim 1 ... 3 as well: the kernel's <E, D> in the one launch line of a
+// generic lambda
+template <class Fn>
+auto pm_dispatch(bool f32, int D, Fn&& fn) {
+    return pm_element(f32, [&](auto e) { return pm_switch<1, 3>(D, [&](auto d) { return fn(e, d); }); });
 }
 
 }  // namespace ta

@@ -9,14 +9,12 @@
 // reused between calls), rows >= pitch are not written.  No atomics, every destination element has one writer: the same
 // bits from run to run, and the same bits for every chunk size.
 //
-// The phase arithmetic (the CPU backend follows it): the host passes q = k / (2 pi), turns per length unit, as float64;
-//   u = fma(q[2], x[2], fma(q[1], x[1], q[0] x[0]))   (as many terms as D),   r = u - rint(u)   (|r| <= 1/2, exact),
-//   (cos, sin)(2 pi r) by sincospi(2 r).
-// The reduced argument keeps sincospi on its fast path: no large-argument reduction, no table in private memory.
+// The phase arithmetic is phase_math.hpp's (q = k / (2 pi) from the host).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
+#include "phase_math.hpp"
 #include "pm_read.hpp"
 #include "ta_internal.hpp"
 
@@ -46,13 +44,8 @@ __global__ void __launch_bounds__(kPmThreads)
             for (int f = 0; f < F; ++f) {
                 const long t = pm_frame<kF32>(tb, f);
                 if (t >= pitch) continue;
-                double u = q0 * col[f][0];
-                if constexpr (D > 1) u = fma(q1, col[f][1], u);
-                if constexpr (D > 2) u = fma(q2, col[f][2], u);
-                const double r = u - rint(u);
-                double s, c;
-                sincospi(2.0 * r, &s, &c);
-                dst[t] = t < T ? double2{c, s} : double2{0.0, 0.0};
+                const double2 cs = phase_cs<D>(q0, q1, q2, col[f]);
+                dst[t] = t < T ? cs : double2{0.0, 0.0};
             }
         }
     }
@@ -66,27 +59,16 @@ __global__ void k_scatter_transpose(const double* __restrict__ bp, long T, long 
     out[i] = bp[t * K + j];
 }
 
-template <class E, int D>
-void phase_launch(dim3 grid, hipStream_t st, const void* x, long pitch, long T, int A, const double* q, int Kc, double* Z) {
-    hipLaunchKernelGGL((k_phase<E, D>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, A, q, Kc, Z);
-}
-template <class E>
-void phase_launch_dim(int D, dim3 grid, hipStream_t st, const void* x, long pitch, long T, int A, const double* q, int Kc,
-                      double* Z) {
-    if (D == 1) phase_launch<E, 1>(grid, st, x, pitch, T, A, q, Kc, Z);
-    else if (D == 2) phase_launch<E, 2>(grid, st, x, pitch, T, A, q, Kc, Z);
-    else phase_launch<E, 3>(grid, st, x, pitch, T, A, q, Kc, Z);
-}
-
 }  // namespace
 
 hipError_t launch_phase(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const double* q, int Kc,
                         double* Z, hipStream_t st) {
-    if (D < 1 || D > 3 || n_atoms < 1 || n_atoms * D >= (1L << 31) || (pitch & 7) || T < 1 || T > pitch || Kc < 1)
-        return hipErrorInvalidValue;
+    if (!pm_slab_ok(pitch, T, n_atoms, D) || Kc < 1) return hipErrorInvalidValue;
     const dim3 grid = pm_unit_grid(n_cu, pitch, n_atoms);
-    if (f32) phase_launch_dim<float>(D, grid, st, x, pitch, T, (int)n_atoms, q, Kc, Z);
-    else phase_launch_dim<double>(D, grid, st, x, pitch, T, (int)n_atoms, q, Kc, Z);
+    pm_dispatch(f32, D, [&](auto e, auto d) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((k_phase<E, d()>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, (int)n_atoms, q, Kc, Z);
+    });
     return hipGetLastError();
 }
 

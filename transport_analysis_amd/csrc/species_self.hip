@@ -68,19 +68,6 @@ __global__ void __launch_bounds__(kPmThreads)
     }
 }
 
-template <class E, int D>
-void sort_launch(dim3 grid, hipStream_t st, const void* x, long pitch, long T, const SortPlan& plan, const int* order,
-                 const double* w, int shift, double* W) {
-    hipLaunchKernelGGL((k_species_sort<E, D>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, plan, order, w, shift, W);
-}
-template <class E>
-void sort_launch_dim(int D, dim3 grid, hipStream_t st, const void* x, long pitch, long T, const SortPlan& plan, const int* order,
-                     const double* w, int shift, double* W) {
-    if (D == 1) sort_launch<E, 1>(grid, st, x, pitch, T, plan, order, w, shift, W);
-    else if (D == 2) sort_launch<E, 2>(grid, st, x, pitch, T, plan, order, w, shift, W);
-    else sort_launch<E, 3>(grid, st, x, pitch, T, plan, order, w, shift, W);
-}
-
 }  // namespace
 
 // The blocks and the sorted order of host labels in [0, S) (checked by the caller): order[pos0[s] + r] = the atom of rank
@@ -108,8 +95,10 @@ hipError_t launch_species_sort(int n_cu, const void* x, bool f32, long pitch, lo
     if (D < 1 || D > 3 || n_cols < 1 || n_cols >= (1L << 31) || (pitch & 7) || T < 1 || T > pitch || plan.n_units < 1)
         return hipErrorInvalidValue;
     const dim3 grid = pm_unit_grid(n_cu, pitch, plan.n_units);
-    if (f32) sort_launch_dim<float>(D, grid, st, x, pitch, T, plan, order, w, shift, W);
-    else sort_launch_dim<double>(D, grid, st, x, pitch, T, plan, order, w, shift, W);
+    pm_dispatch(f32, D, [&](auto e, auto d) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((k_species_sort<E, d()>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, plan, order, w, (int)shift, W);
+    });
     return hipGetLastError();
 }
 

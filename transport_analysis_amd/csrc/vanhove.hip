@@ -15,7 +15,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <type_traits>
 
 #include "pm_read.hpp"
 #include "ta_internal.hpp"
@@ -48,17 +47,14 @@ __device__ __forceinline__ void vh_flush(unsigned* hist, int n, unsigned long lo
 
 // A work unit (pm_read.hpp) is one atom.  Workgroup (bx, g): origin frames [1024 bx, 1024 bx + 1024), atoms g, g + G, ...
 // (G = gridDim.y).  The atom's columns at the thread's kPmFrames origin frames stay in registers across the chunk's lags;
-// per lag the row t + tau of the same pairs is read: a float64 row is one 16-byte load at any t; two float32 rows share
-// a 16-byte load when tau is even (origin frames 2 m, 2 m + 1 -> rows 2 m + tau, 2 m + tau + 1), an odd tau takes 8-byte
-// loads.  A pair with t + tau >= T reads row 0 and contributes nothing: nothing is read at or past row T, but the second
-// half of a float32 load at row T - 1 of an odd T, which lies inside the pitch.
+// per lag the row t + tau of the same pairs is read by pm_lagged (pm_read.hpp): a pair with t + tau >= T reads row 0 and
+// contributes nothing.
 // lags, counts, partial: the chunk's (lags + l0, counts + l0 (B + 1), partial + 2 l0; a workgroup's partials are 2 L apart).
 template <class E, int D>
 __global__ void __launch_bounds__(kPmThreads)
     k_vanhove(const E* __restrict__ x, long pitch, long T, int n_atoms, const long* __restrict__ lags, int Lc,
               const double* __restrict__ e_g, int B, float inv_dr, unsigned long long* __restrict__ counts,
               double* __restrict__ partial, int L, int flush_atoms) {
-    constexpr bool kF32 = std::is_same_v<E, float>;
     constexpr int F = kPmFrames;
     extern __shared__ __attribute__((aligned(16))) unsigned char vh_lds[];
     const int nb = B + 1;
@@ -81,40 +77,14 @@ __global__ void __launch_bounds__(kPmThreads)
             const long tau = lags[l];
             unsigned* h = hist + l * nb;
             double s2 = 0.0, s4 = 0.0;
-            auto tally = [&](bool live, const double(&x0)[3], const double(&x1)[3]) {
-                const double r2 = vh_r2<D>(x0, x1);
+            pm_lagged(a, T, tb, tau, [&](int f, bool live, const double(&x1)[3]) {
+                const double r2 = vh_r2<D>(col[f], x1);
                 if (live) {
                     s2 += r2;
                     s4 = fma(r2, r2, s4);
                     atomicAdd(&h[vh_bin(r2, e, B, inv_dr)], 1u);
                 }
-            };
-            if constexpr (!kF32) {
-#pragma unroll
-                for (int f = 0; f < F; ++f) {
-                    const long t2 = pm_frame<false>(tb, f) + tau;
-                    double lo[3], hi[3];
-                    a.load(t2 < T ? t2 : 0, lo, hi);
-                    tally(t2 < T, col[f], lo);
-                }
-            } else if ((tau & 1) == 0) {
-#pragma unroll
-                for (int f = 0; f < F; f += 2) {
-                    const long t2 = pm_frame<true>(tb, f) + tau;  // (even)
-                    double lo[3], hi[3];
-                    a.load(t2 < T ? t2 / 2 : 0, lo, hi);
-                    tally(t2 < T, col[f], lo);
-                    tally(t2 + 1 < T, col[f + 1], hi);
-                }
-            } else {
-#pragma unroll
-                for (int f = 0; f < F; ++f) {
-                    const long t2 = pm_frame<true>(tb, f) + tau;
-                    double lo[3];
-                    a.row32(t2 < T ? t2 : 0, lo);
-                    tally(t2 < T, col[f], lo);
-                }
-            }
+            });
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1) {  // the same pattern whatever the values: every lane ends with the wave's sum
                 s2 += __shfl_xor(s2, m);
@@ -144,23 +114,6 @@ __global__ void __launch_bounds__(kPmThreads)
     }
 }
 
-template <class E, int D>
-hipError_t vh_launch(dim3 grid, size_t lds, hipStream_t st, const void* x, long pitch, long T, int A, const long* lags, int Lc,
-                          const double* e, int B, float inv_dr, unsigned long long* counts, double* partial, int L) {
-    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_vanhove<E, D>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL((k_vanhove<E, D>), grid, dim3(kPmThreads), lds, st, (const E*)x, pitch, T, A, lags, Lc, e, B, inv_dr,
-                       counts, partial, L, kVhFlushAtoms);
-    return hipGetLastError();
-}
-template <class E, class... Args>
-hipError_t vh_launch_dim(int D, Args... args) {
-    if (D == 1) return vh_launch<E, 1>(args...);
-    if (D == 2) return vh_launch<E, 2>(args...);
-    return vh_launch<E, 3>(args...);
-}
-
 }  // namespace
 
 int vanhove_max_chunk(int B) {
@@ -176,17 +129,22 @@ int vanhove_parts(int n_cu, long pitch, long n_atoms) {
 hipError_t launch_vanhove(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const int64_t* lags, int l0,
                           int Lc, int L, const double* e, int B, float inv_dr, unsigned long long* counts, double* partial,
                           hipStream_t st) {
-    if (D < 1 || D > 3 || n_atoms < 1 || n_atoms * D >= (1L << 31) || (pitch & 7) || T < 1 || T > pitch || B < 1 || Lc < 1 ||
-        l0 < 0 || l0 + Lc > L || Lc > vanhove_max_chunk(B))
+    if (!pm_slab_ok(pitch, T, n_atoms, D) || B < 1 || Lc < 1 || l0 < 0 || l0 + Lc > L || Lc > vanhove_max_chunk(B))
         return hipErrorInvalidValue;
     const dim3 grid = pm_unit_grid(n_cu, pitch, n_atoms);
     const size_t lds = vh_lds_bytes(B, Lc);
-    static_assert(sizeof(long) == sizeof(int64_t), "lags are read as long");
-    const long* lg = reinterpret_cast<const long*>(lags) + l0;
+    const long* lg = pm_lags(lags) + l0;
     unsigned long long* cnt = counts + (size_t)l0 * (size_t)(B + 1);
     double* part = partial + 2 * (size_t)l0;
-    if (f32) return vh_launch_dim<float>(D, grid, lds, st, x, pitch, T, (int)n_atoms, lg, Lc, e, B, inv_dr, cnt, part, L);
-    return vh_launch_dim<double>(D, grid, lds, st, x, pitch, T, (int)n_atoms, lg, Lc, e, B, inv_dr, cnt, part, L);
+    return pm_dispatch(f32, D, [&](auto el, auto d) {
+        using E = decltype(el);
+        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_vanhove<E, d()>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (err != hipSuccess) return err;
+        hipLaunchKernelGGL((k_vanhove<E, d()>), grid, dim3(kPmThreads), lds, st, (const E*)x, pitch, T, (int)n_atoms, lg, Lc, e, B,
+                           inv_dr, cnt, part, L, kVhFlushAtoms);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace ta

@@ -44,18 +44,6 @@ constexpr int kVhdTA = 256;
 static_assert((long)kVhdTA * kVhdTB < (1L << 31), "a workgroup's pair count must stay below 2^31");
 static_assert(kVhdTA == VHD_TILE_A && kVhdTB == VHD_TILE_B, "ta_internal.hpp pads the item pitches to these tiles");
 
-// row t (one frame) of an atom's columns, in the slab's element type: a float64 row is PmAtom's 16-byte load, a float32
-// row PmAtom's 8-byte one (its 16-byte float32 load would take row t + 1 along)
-template <class E, int D>
-__device__ __forceinline__ void vhd_row(const PmAtom<E, D>& a, long t, double (&out)[3]) {
-    if constexpr (PmAtom<E, D>::kF32) {
-        a.row32(t, out);
-    } else {
-        double unused[3];
-        a.load(t, out, unused);
-    }
-}
-
 // grid (item blocks of the pitch, origins (looped), slots): slot z < with_a is GA, the others the chunk's lags.  ids: the
 // padded index list of the slot's side (-1: padding, written as zeros).  A lagged row t + tau >= T is neither read nor
 // written: k_vhd_pairs never starts a workgroup for it.
@@ -77,8 +65,7 @@ __global__ void __launch_bounds__(kPmThreads)
         if (t >= T) break;
         double v[3] = {0.0, 0.0, 0.0};
         if (id >= 0) {
-            const PmAtom<E, D> a(x, pitch, (unsigned)id);  // (atom D < 2^31: launch_vhd_gather)
-            vhd_row<E, D>(a, t, v);
+            PmAtom<E, D>(x, pitch, (unsigned)id).row(t, v);  // (atom D < 2^31: launch_vhd_gather; row t alone: t + 1 may be row T)
         }
 #pragma unroll
         for (int d = 0; d < D; ++d) out[((size_t)o * D + d) * (size_t)ip + p] = v[d];
@@ -150,50 +137,22 @@ __global__ void __launch_bounds__(kPmThreads)
     if ((threadIdx.x & 63) == 0 && over) atomicAdd(&row[B], (unsigned long long)over);
 }
 
-template <class E, int D>
-hipError_t vhd_gather_launch(dim3 grid, hipStream_t st, const void* x, long pitch, long T, long stride, long n_orig, const long* lags,
-                             int with_a, const int* ida, const int* idb, long pitch_a, long pitch_b, double* ga, double* gb) {
-    hipLaunchKernelGGL((k_vhd_gather<E, D>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, stride, n_orig, lags, with_a, ida,
-                       idb, pitch_a, pitch_b, ga, gb);
-    return hipGetLastError();
-}
-template <class E, class... Args>
-hipError_t vhd_gather_dim(int D, Args... args) {
-    if (D == 1) return vhd_gather_launch<E, 1>(args...);
-    if (D == 2) return vhd_gather_launch<E, 2>(args...);
-    return vhd_gather_launch<E, 3>(args...);
-}
-
-template <int D, bool PERIODIC, class... Args>
-hipError_t vhd_pairs_launch(dim3 grid, size_t lds, hipStream_t st, Args... args) {
-    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_vhd_pairs<D, PERIODIC>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL((k_vhd_pairs<D, PERIODIC>), grid, dim3(kPmThreads), lds, st, args...);
-    return hipGetLastError();
-}
-template <bool PERIODIC, class... Args>
-hipError_t vhd_pairs_dim(int D, Args... args) {
-    if (D == 1) return vhd_pairs_launch<1, PERIODIC>(args...);
-    if (D == 2) return vhd_pairs_launch<2, PERIODIC>(args...);
-    return vhd_pairs_launch<3, PERIODIC>(args...);
-}
-
 }  // namespace
 
 hipError_t launch_vhd_gather(const void* x, bool f32, long pitch, long T, long n_atoms, int D, long stride, long n_orig,
                              const int64_t* lags, int Lc, bool with_a, const int* ida, const int* idb, long pitch_a, long pitch_b,
                              double* ga, double* gb, hipStream_t st) {
-    if (D < 1 || D > 3 || n_atoms < 1 || n_atoms * D >= (1L << 31) || (pitch & 7) || T < 1 || T > pitch || stride < 1 || n_orig < 1 ||
-        (n_orig - 1) * stride >= T || Lc < 1 || Lc > TA_VANHOVE_MAX_LAGS || pitch_a < 1 || pitch_b < 1 || pitch_a % VHD_TILE_A ||
-        pitch_b % VHD_TILE_B)
+    if (!pm_slab_ok(pitch, T, n_atoms, D) || stride < 1 || n_orig < 1 || (n_orig - 1) * stride >= T || Lc < 1 ||
+        Lc > TA_VANHOVE_MAX_LAGS || pitch_a < 1 || pitch_b < 1 || pitch_a % VHD_TILE_A || pitch_b % VHD_TILE_B)
         return hipErrorInvalidValue;
-    static_assert(sizeof(long) == sizeof(int64_t), "lags are read as long");
     const long ip = std::max(pitch_a, pitch_b);
     const dim3 grid((unsigned)((ip + kPmThreads - 1) / kPmThreads), (unsigned)std::min(n_orig, 65535L), (unsigned)(Lc + (with_a ? 1 : 0)));
-    const long* lg = reinterpret_cast<const long*>(lags);
-    if (f32) return vhd_gather_dim<float>(D, grid, st, x, pitch, T, stride, n_orig, lg, with_a ? 1 : 0, ida, idb, pitch_a, pitch_b, ga, gb);
-    return vhd_gather_dim<double>(D, grid, st, x, pitch, T, stride, n_orig, lg, with_a ? 1 : 0, ida, idb, pitch_a, pitch_b, ga, gb);
+    pm_dispatch(f32, D, [&](auto e, auto d) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((k_vhd_gather<E, d()>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, stride, n_orig, pm_lags(lags),
+                           with_a ? 1 : 0, ida, idb, pitch_a, pitch_b, ga, gb);
+    });
+    return hipGetLastError();
 }
 
 hipError_t launch_vhd_pairs(const double* ga, const double* gb, const int* ida, const int* idb, long pitch_a, long pitch_b, long n_a,
@@ -207,12 +166,17 @@ hipError_t launch_vhd_pairs(const double* ga, const double* gb, const int* ida, 
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)(n_ta * n_tb), (unsigned)n_o, (unsigned)Lc);
     const size_t lds = (sizeof(double) + sizeof(unsigned)) * (size_t)(B + 1);
-    const long* lg = reinterpret_cast<const long*>(lags);
-    if (hm)
-        return vhd_pairs_dim<true>(D, grid, lds, st, ga, gb, ida, idb, pitch_a, pitch_b, (int)n_a, (int)n_tb, T, stride, n_orig, o0, lg,
-                                   hm, box_per_frame ? 1 : 0, e, B, inv_dr, counts);
-    return vhd_pairs_dim<false>(D, grid, lds, st, ga, gb, ida, idb, pitch_a, pitch_b, (int)n_a, (int)n_tb, T, stride, n_orig, o0, lg,
-                                hm, 0, e, B, inv_dr, counts);
+    auto launch = [&](auto periodic) {  // (without a box box_per_frame is 0)
+        return pm_switch<1, 3>(D, [&](auto d) {
+            auto* kernel = k_vhd_pairs<decltype(d)::value, decltype(periodic)::value>;
+            const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (err != hipSuccess) return err;
+            hipLaunchKernelGGL(kernel, grid, dim3(kPmThreads), lds, st, ga, gb, ida, idb, pitch_a, pitch_b, (int)n_a, (int)n_tb, T, stride,
+                               n_orig, o0, pm_lags(lags), hm, hm && box_per_frame ? 1 : 0, e, B, inv_dr, counts);
+            return hipGetLastError();
+        });
+    };
+    return hm ? launch(std::true_type{}) : launch(std::false_type{});
 }
 
 }  // namespace ta
