@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_pair_find / ta_pair_find_read / ta_pair_lifetime / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -477,6 +477,81 @@ int ta_vanhove_distinct(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int64_t 
                         const int64_t *h_idx_a, int64_t n_b, const int64_t *h_idx_b, const double *h_dimensions,
                         const int *axes, int n_bins, double dr, int64_t *h_counts);
 
+/* ta_pair_find, ta_pair_find_read, ta_pair_lifetime : how long a pair of items stays together (PairLifetime): Rapaport's
+ *              and Luzar-Chandler's pair population correlation functions of the positions in slab 0.  With T frames, D
+ *              staged columns and the bond indicator of items p, q in frame t
+ *                d_j    = x[t, q, j] - x[t, p, j]                      float64 (a float32 slab: widened first, then subtracted)
+ *                         periodic axis:  sc = d_j M_j;  k = rint(sc);  d_j = fma(-k, H_j, d_j)        (ta_vanhove_distinct's
+ *                         one-step image, H_j, M_j of frame t: both items are taken at the SAME frame)
+ *                r2     = d_0 d_0, then fma(d_1, d_1, r2), then fma(d_2, d_2, r2)
+ *                h_pq(t) = r2 < rc2,   rc2 = fl(r_cut r_cut) formed once in float64 on the host        (csrc/pair_math.hpp)
+ *              the three calls give
+ *                ta_pair_find     : the candidate pairs: every (a_p, b_q), a_p != b_q, with h = 1 in at least one SEARCHED
+ *                         frame t = search_stride o, o = 0, 1, ... .  a, b: index lists as for ta_vanhove_distinct (strictly
+ *                         increasing, in range, HOST arrays; h_idx_a NULL: all items; h_idx_b NULL: b = a).  With b = a (NULL,
+ *                         or the same list twice) the pairs are unordered and only a_p < b_q is listed.  Two different lists
+ *                         must be DISJOINT.  The list is kept in a workspace of the context, sorted by (a, b), as int32 staged
+ *                         item ids; *n_pairs gets its length.  ta_trim, and a new staging, release it.
+ *                ta_pair_find_read : copies the list into h_pairs (capacity, 2) int32, capacity >= the found count; with
+ *                         nothing found (no search, or a search that found no pair) there is nothing to read: TA_E_STATE.
+ *                ta_pair_lifetime : of the n_pairs pairs h_pairs (n_pairs, 2) int32 (HOST; two distinct in-range items per row;
+ *                         rows named twice are counted twice: the caller's business), or with h_pairs NULL of the context's
+ *                         found list (n_pairs is ignored).  An explicit list need not come from the search: donor-acceptor
+ *                         lists of hydrogen bonds, 1-4 pairs.
+ *                           h_ci[tau] = sum_pairs sum_{t < T - tau} h(t) h(t + tau)                     (T)      float64
+ *                           h_runs[l] = the number of maximal runs of exactly l consecutive bonded frames,
+ *                                       l = 1 ... T, h_runs[0] = 0; the run open at frame T - 1 ends there   (T + 1)  int64
+ *                           h_nb[t]   = sum_pairs h(t)                                                  (T)      float64
+ *                         NOTHING is divided: ci is NOT divided by T - tau (the other lag sums of this header are).  Each
+ *                         output may be NULL (not computed), not all three.  With every frame an origin, the continuous
+ *                         function's sum over origins is sum_l max(0, l - tau) h_runs[l], and sum_l l h_runs[l] = sum_t h_nb[t].
+ *              Exactness.  h_runs and h_nb are integers for any input.  h_ci with fft = 0 is a sum of products of 0 / 1
+ *              values: every path of ta_vacf_direct gives the partial sums exactly and divides them by T - tau; the call
+ *              multiplies each block's row by T - tau again and rounds to the nearest integer, which is the exact sum while
+ *              (the kernel's partial sums + 2) P_b T stays below 2^52 (the automatic block keeps P_b T at or below 2^32, which
+ *              leaves room for 2^20 partial sums; the kernels use fewer than 2^18): exact integers, the same for every block
+ *              size.  With fft = 1 the lag sums come from ta_vacf_fft's transforms, within the library's usual
+ *              1e-10 of h_ci[0], and are not rounded.
+ *              Box: h_dimensions (n_frames, 6) and axes (dim entries) as for ta_unwrap; NULL: no periodicity (axes is
+ *              ignored).  Per-frame orthorhombic boxes are always accepted (frame t's box reduces frame t).  A
+ *              non-orthogonal box in any frame: TA_E_INVALID.  r_cut must be finite, > 0 and, with a box, at most half of
+ *              every analysed box length in every frame.  Of the box only the analysed axes' lengths are looked at.
+ *              Passes.  ta_pair_find: k_vhd_gather at lag 0 writes the searched frames as frame-major float64 scratch (the
+ *              slab read in the element type it has), k_pair_find takes one (256 a-items, 1024 b-items, searched frame) per
+ *              workgroup on k_vhd_pairs' tiles; a wave's ballot of "bonded and a different item" over its 64 consecutive
+ *              b-items is a word of the device bitmap [pitch_a][pitch_b / 64] and is ORed in by one lane when non-zero.
+ *              The searched frames go in chunks whose scratch fits 4 GiB (option "pair_find_chunk" n >= 1 forces
+ *              min(n, frames)); OR is idempotent: the same list for every chunk, from run to run.  k_pair_count takes
+ *              popcounts per block of words, the block counts are scanned on the host (one small copy, the call's only
+ *              synchronisation), k_pair_list expands the bits in (a, b) order.  ta_pair_lifetime: per block of pairs
+ *              k_pair_series writes the indicator as a float64 pair-major block of P_b pseudo-atoms of dim 1 (1.0 / 0.0, rows
+ *              n_frames ... pitch - 1 and an odd count's phantom column zeros; the slab read as it is, a float32 slab never
+ *              widened first), k_pair_runs adds the block's run lengths by 64-bit integer atomics (runs of up to 8 frames
+ *              are counted in registers first), ONE lag-sum evaluation of the block is its part of ci, ONE species-sum pass
+ *              with unit weights its part of nb; the parts are added in block order.  Blocks hold as many pairs as fit
+ *              32 GiB of indicator block (option "pair_chunk" n >= 1 forces min(n, n_pairs)).  Only integer atomics: the
+ *              same bits from run to run.  ta_trim releases the scratch, the bitmap, the found list and the block.  The
+ *              staged slab is not changed.
+ *              The CPU backend follows the same arithmetic: its found lists and runs EQUAL the GPU's for any input, and so
+ *              do ci and nb with fft = 0; nothing depends on the number of threads.
+ *              Errors, all checked before anything is written.  TA_E_INVALID: NULL n_pairs, search_stride < 1, n_a or n_b < 1
+ *              with a list, a list entry out of range or not increasing, two lists that overlap but differ, r_cut not finite
+ *              or <= 0 or above half a box length, h_dimensions without axes, a box this call cannot use, fft other than
+ *              0 / 1, all three outputs NULL, n_pairs < 1 or >= 2^30 with a list, a row out of range or naming an item twice,
+ *              a capacity below the found count; ceil(Na / 256) ceil(Nb / 1024) at or above 2^24, a bitmap of more than 2^35
+ *              bits (4 GiB: the padded item counts' product), n_atoms * dim at or above 2^31.  TA_E_STATE: nothing staged;
+ *              ta_pair_find_read, or ta_pair_lifetime with h_pairs NULL, without a found list (never searched, trimmed,
+ *              restaged) or with an EMPTY one.  There is no ta_group_* form: pairs cross the
+ *              members' atom shards.  Timings: k_pair_find is the main kernel of ta_pair_find (its LAST launch, one per
+ *              chunk of frames); k_pair_series (its last launch, one per block) is the main kernel of ta_pair_lifetime
+ *              unless a lag-sum evaluation after it records its own; ta_kernel_timeline lists every launch.          */
+int ta_pair_find(ta_ctx *ctx, int64_t n_a, const int64_t *h_idx_a, int64_t n_b, const int64_t *h_idx_b,
+                 const double *h_dimensions, const int *axes, double r_cut, int64_t search_stride, int64_t *n_pairs);
+int ta_pair_find_read(ta_ctx *ctx, int64_t capacity, int32_t *h_pairs);
+int ta_pair_lifetime(ta_ctx *ctx, int fft, int64_t n_pairs, const int32_t *h_pairs /* (n_pairs, 2); NULL: the found list */,
+                     const double *h_dimensions, const int *axes, double r_cut, double *h_ci /* (T) */,
+                     int64_t *h_runs /* (T + 1), [0] = 0 */, double *h_nb /* (T) */);
+
 /* ta_orient  : the rotational correlation functions of molecule-fixed unit vectors of the positions in slab 0
  *              (OrientationalCorrelation), three staged columns per atom.  A vector n is row n of h_index, atoms of slab 0,
  *              pairwise distinct and in [0, n_atoms):
@@ -710,6 +785,11 @@ int ta_overlap_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_cuto
 int ta_vanhove_distinct_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int64_t origin_stride, int64_t n_a,
                                const int64_t *h_idx_a, int64_t n_b, const int64_t *h_idx_b, const double *h_dimensions,
                                const int *axes, int n_bins, double dr, int64_t *d_counts, void *stream);
+/* the pair list (or NULL: the context's found list) and the box: HOST arrays, as for ta_pair_lifetime (checked before anything
+ * is written); slab 0 is read in the element type it has; d_ci (T), d_runs (T + 1) int64, d_nb (T) on the device, each may be
+ * NULL, not all three */
+int ta_pair_lifetime_staged(ta_ctx *ctx, int fft, int64_t n_pairs, const int32_t *h_pairs, const double *h_dimensions,
+                            const int *axes, double r_cut, double *d_ci, int64_t *d_runs, double *d_nb, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns
@@ -910,6 +990,11 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      min(n, n_lags, that count)); the results do not depend on it;
  *   "vanhove_distinct_chunk" n : lags per pass of ta_vanhove_distinct* (0, the default: as many as fit 4 GiB of gathered
  *                      scratch, at least 1; n >= 1: min(n, n_lags)); the results do not depend on it;
+ *   "pair_chunk" n : candidate pairs per block of ta_pair_lifetime* (0, the default: as many as fit 32 GiB of indicator
+ *                      block, at least 2; n >= 1: min(n, n_pairs)); the results do not depend on it (ci with fft = 0 bit for
+ *                      bit; with fft = 1 within the FFT path's bound);
+ *   "pair_find_chunk" n : searched frames per pass of ta_pair_find (0, the default: as many as fit 4 GiB of gathered scratch,
+ *                      at least 1, at most 65535; n >= 1: min(n, frames)); the found list does not depend on it;
  *   "async_commit" 1|0 : ta_stage_commit hands its frame range to a worker thread of the context, which
  *                      makes the HIP calls (the caller's frame loop never waits on the runtime, e.g. while
  *                      another thread page-locks a result array); every call that touches the slabs joins

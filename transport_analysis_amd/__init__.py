@@ -5,7 +5,8 @@ IntermediateScattering, and their real-space partners, the self van Hove functio
 VanHoveSelf, and the distinct van Hove function G_d(r, t) with the radial distribution function g(r), VanHoveDistinct, and
 the longitudinal and transverse current correlation functions C_L(k, t) and C_T(k, t), CurrentCorrelation, and the
 self-overlap Q(t) with the four-point susceptibility chi_4(t), DynamicSusceptibility, and the rotational correlation functions
-C_1(t), C_2(t) of molecule-fixed unit vectors with their dipole sum, OrientationalCorrelation."""
+C_1(t), C_2(t) of molecule-fixed unit vectors with their dipole sum, OrientationalCorrelation, and the intermittent and
+continuous pair population correlation functions with the lifetimes of ion pairs and hydrogen bonds, PairLifetime."""
 __version__ = "0.1.0"
 
 from .velocityautocorr import VelocityAutocorr  # noqa: F401
@@ -20,3 +21,4 @@ from .vanhove import VanHoveSelf, log_lags  # noqa: F401
 from .vanhove_distinct import VanHoveDistinct  # noqa: F401
 from .susceptibility import DynamicSusceptibility  # noqa: F401
 from .orientation import OrientationalCorrelation, group_indices  # noqa: F401
+from .pair_lifetime import PairLifetime  # noqa: F401

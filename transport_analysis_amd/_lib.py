@@ -84,6 +84,10 @@ _API = {
     "ta_overlap_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _ci, _vp, _vp, _vp),
     # (handle, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr, counts[, stream])
     "ta_vanhove_distinct": _int(_vp, _ci, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _dbl, _vp),
+    "ta_pair_find": _int(_vp, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _i64, _vp),
+    "ta_pair_find_read": _int(_vp, _i64, _vp),
+    "ta_pair_lifetime": _int(_vp, _ci, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp),
+    "ta_pair_lifetime_staged": _int(_vp, _ci, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp),
     "ta_vanhove_distinct_staged": _int(_vp, _ci, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _dbl, _vp, _vp),
     "ta_compound": _int(_vp, _i64, _vp, _vp, _vp, _vp, _P(_vp)),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
@@ -877,6 +881,75 @@ class Context(_Staged):
         n_bins + 1) int64 on the device"""
         args, keep = self._vhd_args(lags, origin_stride, idx_a, idx_b, dimensions, axes, n_bins, dr)
         self._call("vanhove_distinct_staged", *args, d_counts or None, stream or None)
+        del keep
+
+    def _pair_box(self, dimensions, axes):
+        """(dimensions, axes) of a pair call as contiguous arrays, or (None, None)"""
+        if dimensions is None:
+            return None, None
+        dims = np.ascontiguousarray(dimensions, dtype=np.float64)
+        if self.shape is not None and dims.shape != (self.shape[0], 6):
+            raise ValueError(f"dimensions: shape {dims.shape}, expected ({self.shape[0]}, 6) (one box per staged frame)")
+        ax = np.ascontiguousarray(np.arange(self._staged_shape()[2]) if axes is None else axes, dtype=np.int32).ravel()
+        return dims, ax
+
+    def pair_find(self, r_cut, *, search_stride=1, idx_a=None, idx_b=None, dimensions=None, axes=None):
+        """Candidate pairs of slab 0 (the positions), ta_pair_find + ta_pair_find_read: the (n, 2) int32 staged item ids
+        (a, b), sorted, of every pair of different items from `idx_a` x `idx_b` (strictly increasing item indices; None: all
+        items / the same as a, then only a < b) closer than `r_cut` in at least one of the frames 0, search_stride, ...
+        `dimensions`, `axes`: as for vanhove_distinct.  The list stays in the context (pair_lifetime(pairs=None) uses it)
+        until trim() or a new staging.  One context only: a device group has no such call."""
+
+        def index_list(idx, name):
+            if idx is None:
+                return None, 0
+            a = np.ascontiguousarray(idx, dtype=np.int64)
+            if a.ndim != 1:
+                raise ValueError(f"{name}: shape {a.shape}, expected a 1-d list of item indices")
+            return a, int(a.shape[0])
+
+        (a, na), (b, nb) = index_list(idx_a, "idx_a"), index_list(idx_b, "idx_b")
+        dims, ax = self._pair_box(dimensions, axes)
+        n = ctypes.c_int64(0)
+        self._call("pair_find", na, _ptr(a), nb, _ptr(b), _ptr(dims), _ptr(ax), float(r_cut), int(search_stride), ctypes.byref(n))
+        pairs = np.empty((int(n.value), 2), dtype=np.int32)
+        if n.value:  # (an empty list is not read: ta_pair_find_read refuses it)
+            self._call("pair_find_read", int(n.value), _ptr(pairs))
+        return pairs
+
+    def _pair_args(self, fft, pairs, r_cut, dimensions, axes):
+        """the argument tuple ta_pair_lifetime* share, and the arrays it points into (to be kept until the call is over)"""
+        pr, n = None, 0
+        if pairs is not None:
+            pr = np.ascontiguousarray(pairs)
+            if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
+                raise ValueError(f"pairs: shape {pr.shape} and dtype {pr.dtype}, expected an integer (n_pairs, 2) array")
+            if pr.size and (pr.min() < -2**31 or pr.max() >= 2**31):
+                raise ValueError("pairs: entries must fit int32")
+            pr, n = np.ascontiguousarray(pr, dtype=np.int32), int(pr.shape[0])
+        dims, ax = self._pair_box(dimensions, axes)
+        return (int(fft), n, _ptr(pr), _ptr(dims), _ptr(ax), float(r_cut)), (pr, dims, ax)
+
+    def pair_lifetime(self, fft, r_cut, pairs=None, *, dimensions=None, axes=None, ci=True, runs=True, nb=True):
+        """Pair population sums of slab 0 (the positions), ta_pair_lifetime, of the (n_pairs, 2) staged item ids `pairs`
+        (None: the list pair_find left in the context): (ci (n_frames,) = sum_pairs sum_t h(t) h(t + tau), NOT divided by
+        n_frames - tau; runs (n_frames + 1,) int64 = the histogram of the lengths of the runs of bonded frames; nb
+        (n_frames,) = the bonded pairs per frame), None for one not asked for.  One context only: a device group has no
+        such call."""
+        T = self._staged_shape()[0]
+        args, keep = self._pair_args(fft, pairs, r_cut, dimensions, axes)
+        o_ci = np.empty(T, dtype=np.float64) if ci else None
+        o_runs = np.empty(T + 1, dtype=np.int64) if runs else None
+        o_nb = np.empty(T, dtype=np.float64) if nb else None
+        self._call("pair_lifetime", *args, _ptr(o_ci), _ptr(o_runs), _ptr(o_nb))
+        del keep
+        return o_ci, o_runs, o_nb
+
+    def pair_lifetime_staged(self, fft, r_cut, pairs=None, *, dimensions=None, axes=None, d_ci=0, d_runs=0, d_nb=0, stream=0):
+        """`pairs`, `dimensions`: HOST arrays (checked by the library before anything is written); d_ci (n_frames,), d_runs
+        (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
+        args, keep = self._pair_args(fft, pairs, r_cut, dimensions, axes)
+        self._call("pair_lifetime_staged", *args, d_ci or None, d_runs or None, d_nb or None, stream or None)
         del keep
 
     def _orient_args(self, fft, index, mode, dimensions, weights):

@@ -23,6 +23,7 @@
 #include "direct_kernels.hpp"
 #include "kcurrent_math.hpp"
 #include "orient_math.hpp"
+#include "pair_math.hpp"
 #include "phase_math.hpp"
 #include "ta_internal.hpp"
 #include "unwrap_box.hpp"
@@ -125,6 +126,8 @@ private:
     X(vanhove_chunk, 0, opt_check_vanhove_chunk) /* lags per pass of ta_vanhove* (0: as many as fit a workgroup's LDS) */ \
     X(overlap_chunk, 0, opt_check_overlap_chunk) /* lags per launch of ta_overlap* (0: as many as the kernel's tile holds) */ \
     X(vanhove_distinct_chunk, 0, opt_check_vanhove_distinct_chunk) /* lags per pass of ta_vanhove_distinct* (0: as many as fit kVhdBudget) */ \
+    X(pair_chunk, 0, opt_check_pair_chunk) /* candidate pairs per block of ta_pair_lifetime* (0: as many as fit kPairBudget) */ \
+    X(pair_find_chunk, 0, opt_check_pair_find_chunk) /* searched frames per pass of ta_pair_find (0: as many as fit kVhdBudget) */ \
     X(async_commit, 1, opt_flush_commits) /* ta_stage_commit goes through the commit queue; flushed before it changes */   \
     X(lock_ahead, 1, nullptr)      /* the commit worker page-locks the chunks behind the one it committed */               \
     X(cpu_threads, 0, opt_set_cpu_threads) /* CPU backend: OpenMP team size (0: the runtime's default) */                  \
@@ -196,6 +199,17 @@ struct ta_ctx {
     // frame-major scratch GA | GB and the uint64 histogram (trimmed), the output of host-facing calls
     HostTable vhd_tab{workspaces, tables};
     DevBuf vhd_scr{workspaces, kTrimmed}, vhd_hist{workspaces, kTrimmed}, vhd_out{workspaces, kKept};
+    // pair lifetimes (pair_find_pm, pair_life_pm): the search's table (a zero lag, box entries, padded index lists), its
+    // bitmap with the block counts and offsets behind it (the gathered scratch is vhd_scr), the found list (n_pairs, 2)
+    // int32 with its length and the staged atom count it was found for (pair_n < 0: none); the lifetime call's table (box
+    // entries, pairs, zero labels), the indicator block Z of one block of pairs, the blocks' rows of lag sums and bonded
+    // counts with the uint64 run histogram behind them, the outputs of host-facing calls.  A CPU context keeps its found
+    // list in pair_host.
+    HostTable pair_ftab{workspaces, tables}, pair_tab{workspaces, tables};
+    DevBuf pair_bits{workspaces, kTrimmed}, pair_list{workspaces, kTrimmed}, pair_z{workspaces, kTrimmed};
+    DevBuf pair_rows{workspaces, kTrimmed}, pair_out{workspaces, kKept};
+    int64_t pair_n = -1, pair_A = 0;
+    std::vector<int32_t> pair_host;
     // ta_compound: the plan (offsets, members, member weights, their sums per compound) and the (n_frames, dim) weighted
     // mean F of the barycentric term; the per-atom frame weights and F's partial sums use the Onsager workspaces
     DevBuf comp_plan{workspaces, kTrimmed}, comp_f{workspaces, kTrimmed};
@@ -1610,13 +1624,13 @@ struct VhdPlan {
 };
 
 static int vhd_index_list(ta_ctx* ctx, const char* name, int64_t n, const int64_t* idx, int64_t A, int64_t tile, std::vector<int32_t>* out,
-                          int64_t* pitch) {
+                          int64_t* pitch, const std::string& who = "vanhove_distinct") {
     for (int64_t i = 0; idx && i < n; ++i) {
         if (idx[i] < 0 || idx[i] >= A)
-            return fail(ctx, TA_E_INVALID, std::string("vanhove_distinct: index list ") + name + ": entry " + std::to_string(idx[i]) +
+            return fail(ctx, TA_E_INVALID, who + ": index list " + name + ": entry " + std::to_string(idx[i]) +
                                                " is outside 0 ... n_atoms - 1");
         if (i && idx[i] <= idx[i - 1])
-            return fail(ctx, TA_E_INVALID, std::string("vanhove_distinct: index list ") + name + " must be strictly increasing");
+            return fail(ctx, TA_E_INVALID, who + ": index list " + name + " must be strictly increasing");
     }
     *pitch = (n + tile - 1) / tile * tile;
     out->assign((size_t)*pitch, -1);
@@ -1757,6 +1771,285 @@ int vhd_launch(ta_ctx* ctx, const VhdPlan& plan, const int64_t* h_lags, double d
         [&](const Slab& s) { return vhd_pm(ctx, s, plan, dr, d_counts); });
 }
 
+// ---- pair lifetimes: candidate search, indicator series, run lengths (pair_lifetime.hip) ----------------------------
+constexpr size_t kPairBudget = (size_t)32 << 30;  // the indicator block of one block of pairs (a choice, as kScatterBudget)
+
+// The box of a pair call (both kinds of context): per box H[3], M[3] of the staged columns, as VhdPlan's; r_cut checked
+// against it.  Only the analysed axes' lengths are looked at.  n_box 0: no box.
+struct PairBox {
+    bool per_frame = false;
+    int64_t n_box = 0;
+    std::vector<double> hm;
+};
+int pair_box(ta_ctx* ctx, const std::string& who, const double* h_dims, const int* axes, int64_t T, int D, double r_cut, PairBox* b) {
+    for (int d = 0; d < D; ++d)
+        if (axes[d] < 0 || axes[d] > 2) return fail(ctx, TA_E_INVALID, who + "axes: every entry must be 0, 1 or 2");
+    std::vector<double> dims(h_dims, h_dims + 6 * (size_t)T);
+    for (int k = 0; k < 3; ++k)
+        if (std::find(axes, axes + D, k) == axes + D)
+            for (int64_t t = 0; t < T; ++t) dims[6 * (size_t)t + k] = 1.0;
+    BoxTable box;
+    const std::string why = box_table(dims.data(), T, D, axes, 1, &box);
+    if (!why.empty()) return fail(ctx, TA_E_INVALID, who + why);
+    if (box.triclinic)
+        return fail(ctx, TA_E_INVALID, who + "a non-orthogonal box is not supported (the one-step image is not the minimum image there)");
+    b->per_frame = box.per_frame;
+    b->n_box = box.per_frame ? T : 1;
+    b->hm.assign((size_t)b->n_box * 6, 1.0);
+    for (int64_t t = 0; t < b->n_box; ++t)
+        for (int d = 0; d < D; ++d) {
+            const double h = box.tab[(size_t)diag_row(axes[d]) * box.tpitch + t];
+            b->hm[(size_t)t * 6 + d] = h;
+            b->hm[(size_t)t * 6 + 3 + d] = box.tab[(size_t)(6 + diag_row(axes[d])) * box.tpitch + t];
+            if (!(r_cut <= 0.5 * h))
+                return fail(ctx, TA_E_INVALID, who + "r_cut = " + std::to_string(r_cut) + " exceeds half the box length " + std::to_string(h) +
+                                                   " of frame " + std::to_string(t));
+        }
+    return TA_OK;
+}
+// what both pair calls check of r_cut and the box arguments before the staged shape is needed
+int pair_cut_args(ta_ctx* ctx, const std::string& who, double r_cut, const double* h_dims, const int* axes) {
+    if (!(r_cut > 0.0) || !(r_cut - r_cut == 0.0)) return fail(ctx, TA_E_INVALID, who + "r_cut must be finite and greater than 0");
+    if (h_dims && !axes) return fail(ctx, TA_E_INVALID, who + "dimensions without axes");
+    return TA_OK;
+}
+
+// The host side of one search (both kinds of context)
+struct PairFindPlan {
+    int D = 0;
+    int64_t T = 0, A = 0, stride = 1, n_a = 0, n_b = 0, n_srch = 0, pitch_a = 0, pitch_b = 0;
+    bool same = false;
+    double rc2 = 0.0;
+    std::vector<int32_t> ida, idb;
+    PairBox box;
+};
+int pair_find_plan(ta_ctx* ctx, int64_t n_a, const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dims,
+                   const int* axes, double r_cut, int64_t stride, const void* out, PairFindPlan* p) {
+    const std::string who = "pair_find: ";
+    if (!out) return fail(ctx, TA_E_INVALID, who + "the n_pairs output is NULL");
+    if (stride < 1) return fail(ctx, TA_E_INVALID, who + "search_stride must be >= 1");
+    if (h_idx_a && n_a < 1) return fail(ctx, TA_E_INVALID, who + "n_a must be >= 1");
+    if (h_idx_b && n_b < 1) return fail(ctx, TA_E_INVALID, who + "n_b must be >= 1");
+    TA_CHECK(pair_cut_args(ctx, who, r_cut, h_dims, axes));
+    TA_CHECK(check_staged(ctx));
+    const int64_t T = ctx->st_T, A = ctx->st_A;
+    const int D = ctx->st_D;
+    TA_CHECK(check_cols(ctx, who, A, D));
+    p->D = D, p->T = T, p->A = A, p->stride = stride, p->rc2 = r_cut * r_cut;
+    p->n_a = h_idx_a ? n_a : A;
+    TA_CHECK(vhd_index_list(ctx, "a", p->n_a, h_idx_a, A, VHD_TILE_A, &p->ida, &p->pitch_a, "pair_find"));
+    p->same = !h_idx_b;
+    if (!h_idx_b) h_idx_b = h_idx_a, n_b = p->n_a;
+    p->n_b = n_b;
+    TA_CHECK(vhd_index_list(ctx, "b", p->n_b, h_idx_b, A, VHD_TILE_B, &p->idb, &p->pitch_b, "pair_find"));
+    if (!p->same) {  // two lists: the same list twice, or disjoint ones (both increase strictly: one merge walk)
+        p->same = p->n_a == p->n_b && std::equal(p->ida.begin(), p->ida.begin() + p->n_a, p->idb.begin());
+        for (int64_t i = 0, j = 0; !p->same && i < p->n_a && j < p->n_b;) {
+            if (p->ida[i] == p->idb[j])
+                return fail(ctx, TA_E_INVALID, who + "the index lists overlap (item " + std::to_string(p->ida[i]) +
+                                                   " is in both) but differ: they must be one list or disjoint");
+            p->ida[i] < p->idb[j] ? ++i : ++j;
+        }
+    }
+    if ((p->pitch_a / VHD_TILE_A) * (p->pitch_b / VHD_TILE_B) >= VHD_MAX_TILES)
+        return fail(ctx, TA_E_INVALID, who + "ceil(n_a / " + std::to_string(VHD_TILE_A) + ") * ceil(n_b / " + std::to_string(VHD_TILE_B) +
+                                           ") must be below 2^24 (about 2 million items on both sides)");
+    if (p->pitch_a * p->pitch_b > (int64_t)1 << 35)
+        return fail(ctx, TA_E_INVALID, who + "the pair bitmap of " + std::to_string(p->pitch_a) + " x " + std::to_string(p->pitch_b) +
+                                           " padded items exceeds 2^35 bits (4 GiB)");
+    p->n_srch = vhd_origins(T, 0, stride);
+    if (h_dims) TA_CHECK(pair_box(ctx, who, h_dims, axes, T, D, r_cut, &p->box));
+    return TA_OK;
+}
+
+// One search on the staged position slab of either element type (the caller has opened the call's bracket, it is closed
+// here; the table zero lag | hm | ida | idb has been queued).  The bitmap is zeroed; per chunk of searched frames one
+// k_vhd_gather launch at lag 0 and one k_pair_find launch; k_pair_count, the block counts copied to the host (the call's
+// only synchronisation) and scanned there, k_pair_list.  Nothing depends on the chunk: OR is idempotent.
+int pair_find_pm(ta_ctx* ctx, const Slab& slab, const PairFindPlan& p) {
+    hipStream_t st = slab.st;
+    const int D = p.D;
+    const double* tab = (const double*)ctx->pair_ftab.dev.p;
+    const int64_t* lag0 = (const int64_t*)tab;
+    const double* hm = p.box.n_box ? tab + 1 : nullptr;
+    const int* ida = (const int*)(tab + 1 + p.box.hm.size());
+    const int* idb = ida + p.pitch_a;
+    const size_t per = sizeof(double) * (size_t)D * (size_t)(p.pitch_a + p.pitch_b);
+    const int64_t fit = std::max<int64_t>(1, (int64_t)(kVhdBudget / per));
+    const int64_t oc = std::min<int64_t>({p.n_srch, 65535, ctx->opt_pair_find_chunk > 0 ? ctx->opt_pair_find_chunk : fit});
+    const long n_words = (long)(p.pitch_a * p.pitch_b / 64), n_blk = pair_list_blocks(n_words);
+    const size_t bits_bytes = sizeof(uint64_t) * (size_t)n_words, cnt_bytes = (sizeof(unsigned) * (size_t)n_blk + 7) / 8 * 8;
+    TA_CHECK(ensure(ctx, ctx->vhd_scr, (size_t)oc * per));
+    TA_CHECK(ensure(ctx, ctx->pair_bits, bits_bytes + cnt_bytes + sizeof(long long) * (size_t)n_blk));
+    unsigned long long* bitmap = (unsigned long long*)ctx->pair_bits.p;
+    unsigned* counts = (unsigned*)((char*)ctx->pair_bits.p + bits_bytes);
+    long long* offs = (long long*)((char*)counts + cnt_bytes);
+    double* ga = (double*)ctx->vhd_scr.p;
+    ctx->pair_n = -1;
+    TA_HIP_TRY(ctx, hipMemsetAsync(bitmap, 0, bits_bytes, st));
+    for (int64_t o0 = 0; o0 < p.n_srch; o0 += oc) {
+        const int64_t n_o = std::min(oc, p.n_srch - o0);
+        double* gb = ga + (size_t)n_o * D * (size_t)p.pitch_a;
+        TA_LAUNCH(ctx, "k_vhd_gather", st,
+                  launch_vhd_gather(slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, D, (long)p.stride, (long)n_o, lag0, 1,
+                                    true, ida, idb, (long)p.pitch_a, (long)p.pitch_b, ga, gb, st, (long)o0));
+        TA_LAUNCH_MAIN(ctx, "k_pair_find", st,
+                       launch_pair_find(ga, gb, ida, idb, (long)p.pitch_a, (long)p.pitch_b, (long)p.n_a, (long)p.n_b, D, (long)slab.T,
+                                        (long)p.stride, (long)o0, (int)n_o, hm, p.box.per_frame, p.rc2, p.same, bitmap, st));
+    }
+    TA_LAUNCH(ctx, "k_pair_count", st, launch_pair_count(bitmap, n_words, counts, st));
+    std::vector<unsigned> h_counts((size_t)n_blk);
+    std::vector<long long> h_offs((size_t)n_blk);
+    TA_HIP_TRY(ctx, hipMemcpyAsync(h_counts.data(), counts, sizeof(unsigned) * (size_t)n_blk, hipMemcpyDeviceToHost, st));
+    TA_HIP_TRY(ctx, hipStreamSynchronize(st));
+    long long total = 0;
+    for (long b = 0; b < n_blk; ++b) h_offs[(size_t)b] = total, total += h_counts[(size_t)b];
+    if (total >= (long long)1 << 30)
+        return fail(ctx, TA_E_INVALID, "pair_find: " + std::to_string(total) + " pairs found: the list holds fewer than 2^30");
+    TA_CHECK(ensure(ctx, ctx->pair_list, sizeof(int32_t) * 2 * (size_t)total));
+    if (total) {
+        TA_HIP_TRY(ctx, hipMemcpyAsync(offs, h_offs.data(), sizeof(long long) * (size_t)n_blk, hipMemcpyHostToDevice, st));
+        TA_LAUNCH(ctx, "k_pair_list", st, launch_pair_list(bitmap, n_words, (long)(p.pitch_b / 64), offs, ida, idb, (int*)ctx->pair_list.p, st));
+        TA_HIP_TRY(ctx, hipStreamSynchronize(st));  // (h_offs leaves with this scope)
+    }
+    ctx->pair_n = total, ctx->pair_A = p.A;
+    return call_end(ctx, st);
+}
+
+int pair_find_launch(ta_ctx* ctx, const PairFindPlan& p) {
+    return slab_entry(
+        ctx, nullptr, ctx->stream, no_args,
+        [&](const Slab& s) -> int {
+            const size_t n = 1 + p.box.hm.size() + (size_t)(p.pitch_a + p.pitch_b) / 2;  // (both pitches are even)
+            double* h = nullptr;
+            TA_CHECK(ctx->pair_ftab.begin(ctx, sizeof(double) * n, (void**)&h));
+            memset(h, 0, sizeof(double));  // the zero lag (int64)
+            if (!p.box.hm.empty()) memcpy(h + 1, p.box.hm.data(), sizeof(double) * p.box.hm.size());
+            double* q = h + 1 + p.box.hm.size();
+            memcpy(q, p.ida.data(), sizeof(int32_t) * p.ida.size());
+            memcpy(q + p.pitch_a / 2, p.idb.data(), sizeof(int32_t) * p.idb.size());
+            return ctx->pair_ftab.send(ctx, s.st);
+        },
+        [&](const Slab& s) { return pair_find_pm(ctx, s, p); });
+}
+
+// The host side of one lifetime call (both kinds of context).  h_pairs NULL: the context's found list
+struct PairLifePlan {
+    int64_t P = 0;
+    const int32_t* h_pairs = nullptr;
+    double rc2 = 0.0;
+    PairBox box;
+};
+int pair_life_plan(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs, const double* h_dims, const int* axes, double r_cut,
+                   bool any_out, PairLifePlan* p) {
+    const std::string who = "pair_lifetime: ";
+    TA_CHECK(check_fft(ctx, fft));
+    if (!any_out) return fail(ctx, TA_E_INVALID, who + "the ci, runs and nb outputs are all NULL");
+    TA_CHECK(pair_cut_args(ctx, who, r_cut, h_dims, axes));
+    TA_CHECK(check_staged(ctx));
+    const int64_t T = ctx->st_T, A = ctx->st_A;
+    TA_CHECK(check_cols(ctx, who, A, ctx->st_D));
+    p->rc2 = r_cut * r_cut, p->h_pairs = h_pairs;
+    if (h_pairs) {
+        if (n_pairs < 1 || n_pairs >= (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, who + "n_pairs must be 1 ... 2^30 - 1");
+        for (int64_t n = 0; n < n_pairs; ++n) {
+            const int32_t a = h_pairs[2 * n], b = h_pairs[2 * n + 1];
+            if (a < 0 || a >= A || b < 0 || b >= A)
+                return fail(ctx, TA_E_INVALID, who + "pair " + std::to_string(n) + " (" + std::to_string(a) + ", " + std::to_string(b) +
+                                                   ") is outside 0 ... n_atoms - 1");
+            if (a == b) return fail(ctx, TA_E_INVALID, who + "pair " + std::to_string(n) + " names item " + std::to_string(a) + " twice");
+        }
+        p->P = n_pairs;
+    } else {
+        const bool have = ctx->pair_n >= 0 && ctx->pair_A == A && (ctx->is_cpu || ctx->pair_list.p);
+        if (!have)
+            return fail(ctx, TA_E_STATE, who + "no pair list has been found for the staged slab (ta_pair_find comes first; ta_trim "
+                                               "releases it)");
+        if (ctx->pair_n == 0) return fail(ctx, TA_E_STATE, who + "the found pair list is empty");
+        p->P = ctx->pair_n;
+    }
+    if (h_dims) TA_CHECK(pair_box(ctx, who, h_dims, axes, T, ctx->st_D, r_cut, &p->box));
+    return TA_OK;
+}
+
+// the candidate pairs per block: "pair_chunk", or as many as kPairBudget holds of the indicator block
+int64_t pair_block(const ta_ctx* ctx, int64_t P, int64_t pitch) {
+    const int64_t fit = std::max<int64_t>(2, 2 * (int64_t)(kPairBudget / ((size_t)pitch * 16)));
+    return std::min<int64_t>(P, ctx->opt_pair_chunk > 0 ? ctx->opt_pair_chunk : fit);
+}
+
+// One lifetime call on the staged position slab of either element type, read as it is (the caller has opened the call's
+// bracket, it is closed here; the table hm | pairs | zero labels has been queued).  Per block of pairs: k_pair_series
+// writes the indicator block Z (P_b pseudo-atoms of dim 1), k_pair_runs adds its runs to the histogram, ONE VACF lag-sum
+// evaluation of Z is the block's row of ci / (T - tau), ONE species-sum pass with unit weights its row of nb.  The rows are
+// added in block order by k_pair_reduce, which also takes the 1 / (T - tau) out again: with fft = 0 every product is exact,
+// a row's value times (T - tau) is within (partial sums + 2) 2^-53 of the integer it stands for (at most P_b T <= 2^32 with
+// the automatic block), and rint gives that integer: the same bits for every block size.  ev[1] / ev[2] bracket the
+// (last) k_pair_series launch, unless a lag-sum evaluation after it records its own main kernel.
+int pair_life_pm(ta_ctx* ctx, bool fft, const Slab& slab, const PairLifePlan& p, double* d_ci, int64_t* d_runs, double* d_nb) {
+    hipStream_t st = slab.st;
+    const int64_t T = slab.T, pitch = slab.pitch, P = p.P;
+    const int64_t Pc = pair_block(ctx, P, pitch), n_blocks = (P + Pc - 1) / Pc;
+    const double* tab = (const double*)ctx->pair_tab.dev.p;
+    const double* hm = p.box.n_box ? tab : nullptr;
+    const int* pairs = p.h_pairs ? (const int*)(tab + p.box.hm.size()) : (const int*)ctx->pair_list.p;
+    const int* lab = (const int*)(tab + p.box.hm.size() + (p.h_pairs ? (size_t)P : 0));
+    TA_CHECK(ensure(ctx, ctx->pair_z, (size_t)((Pc + 1) / 2) * (size_t)pitch * 16));
+    const size_t n_rows = (size_t)n_blocks * (size_t)T;
+    TA_CHECK(ensure(ctx, ctx->pair_rows, sizeof(double) * (2 * n_rows + (size_t)T + 1)));
+    double* ci_rows = (double*)ctx->pair_rows.p;
+    double* nb_rows = ci_rows + n_rows;
+    unsigned long long* runs = (unsigned long long*)(nb_rows + n_rows);
+    const int64_t P_last = P - (n_blocks - 1) * Pc;
+    const int parts_full = species_sum_parts(ctx->n_cu, 1, (long)T, (long)Pc), parts_last = species_sum_parts(ctx->n_cu, 1, (long)T, (long)P_last);
+    if (d_nb) TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)std::max(parts_full, parts_last) * (size_t)T));
+    double* Z = (double*)ctx->pair_z.p;
+    if (d_runs) TA_HIP_TRY(ctx, hipMemsetAsync(runs, 0, sizeof(uint64_t) * ((size_t)T + 1), st));
+    for (int64_t b = 0; b < n_blocks; ++b) {
+        const int64_t p0 = b * Pc, pb = std::min(Pc, P - p0);
+        TA_LAUNCH_MAIN(ctx, "k_pair_series", st,
+                       launch_pair_series(ctx->n_cu, slab.pm, slab.f32, (long)pitch, (long)T, (long)slab.A, slab.D, (long)pb, pairs + 2 * p0,
+                                          hm, p.box.per_frame, p.rc2, Z, st));
+        if (d_runs) TA_LAUNCH(ctx, "k_pair_runs", st, launch_pair_runs(ctx->n_cu, Z, (long)pitch, (long)T, (long)pb, runs, st));
+        if (d_ci) TA_CHECK(acf_impl(ctx, fft, Z, pitch, T, pb, 1, ci_rows + (size_t)b * T, nullptr, 0, st));
+        if (d_nb)
+            TA_CHECK(weighted_total(ctx, Z, false, pitch, T, pb, 1, lab, nullptr, pb == Pc ? parts_full : parts_last,
+                                    nb_rows + (size_t)b * T, st));
+    }
+    if (d_ci)
+        TA_LAUNCH(ctx, "k_pair_reduce", st, launch_pair_reduce(ci_rows, (int)n_blocks, (long)T, (long)T, fft ? PAIR_LAGS : PAIR_LAGS_INT, d_ci, st));
+    if (d_nb) TA_LAUNCH(ctx, "k_pair_reduce", st, launch_pair_reduce(nb_rows, (int)n_blocks, (long)T, (long)T, PAIR_SUM, d_nb, st));
+    if (d_runs) TA_HIP_TRY(ctx, hipMemcpyAsync(d_runs, runs, sizeof(int64_t) * ((size_t)T + 1), hipMemcpyDeviceToDevice, st));
+    return call_end(ctx, st);
+}
+
+// ta_pair_lifetime_staged and the device half of ta_pair_lifetime (out != NULL: the context's own output buffer ci (T) |
+// runs (T + 1) | nb (T) takes the place of the d_* pointers, which then only say what is asked for)
+int pair_life_launch(ta_ctx* ctx, int fft, const PairLifePlan& p, double* d_ci, int64_t* d_runs, double* d_nb, void* stream, double** out) {
+    return slab_entry(
+        ctx, nullptr, stream, no_args,
+        [&](const Slab& s) -> int {
+            const int64_t Pc = pair_block(ctx, p.P, s.pitch);
+            const size_t n = p.box.hm.size() + (p.h_pairs ? (size_t)p.P : 0) + ((size_t)Pc + 1) / 2;
+            double* h = nullptr;
+            TA_CHECK(ctx->pair_tab.begin(ctx, sizeof(double) * n, (void**)&h));
+            memset(h, 0, sizeof(double) * n);
+            if (!p.box.hm.empty()) memcpy(h, p.box.hm.data(), sizeof(double) * p.box.hm.size());
+            if (p.h_pairs) memcpy(h + p.box.hm.size(), p.h_pairs, sizeof(int32_t) * 2 * (size_t)p.P);
+            if (out) {
+                TA_CHECK(ensure(ctx, ctx->pair_out, sizeof(double) * (3 * (size_t)s.T + 1)));
+                *out = (double*)ctx->pair_out.p;
+            }
+            return ctx->pair_tab.send(ctx, s.st);
+        },
+        [&](const Slab& s) {
+            if (!out) return pair_life_pm(ctx, fft != 0, s, p, d_ci, d_runs, d_nb);
+            double* o = *out;
+            return pair_life_pm(ctx, fft != 0, s, p, d_ci ? o : nullptr, d_runs ? (int64_t*)(o + s.T) : nullptr,
+                                d_nb ? o + 2 * s.T + 1 : nullptr);
+        });
+}
+
 // ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
 // This is the seam: a CPU context's staging and host-facing calls end up in the cpu_* functions below, reached by one
 // early branch of their entry point (after the checks both kinds of context share); nothing below makes a HIP call.
@@ -1764,6 +2057,7 @@ void set_staged(ta_ctx* ctx, int64_t T, int64_t A, int D, int dtype, int n_slabs
     ctx->st_T = T, ctx->st_A = A, ctx->st_D = D, ctx->st_dtype = dtype, ctx->st_nslabs = n_slabs;
     ctx->st_dev_f32 = dev_f32;
     ctx->st_pitch = pm_pitch(T);
+    ctx->pair_n = -1;  // (a found pair list belongs to the staging it was found in)
 }
 
 // what cpu_backend.cpp works on: the staged shape and the host slabs, read where they are
@@ -1842,6 +2136,12 @@ int opt_check_scatter_chunk(ta_ctx* ctx, int64_t value) {
 }
 int opt_check_vanhove_distinct_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "vanhove_distinct_chunk: 0 (automatic) or the lags per pass");
+}
+int opt_check_pair_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "pair_chunk: 0 (automatic) or the candidate pairs per block");
+}
+int opt_check_pair_find_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "pair_find_chunk: 0 (automatic) or the searched frames per pass");
 }
 int opt_check_overlap_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "overlap_chunk: 0 (automatic) or the lags per launch");
@@ -2639,6 +2939,18 @@ int ta_vanhove_distinct_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, i
     });
 }
 
+// Pair lifetimes on the staged slab 0, read in its own element type; the pair list and the box are HOST arrays
+int ta_pair_lifetime_staged(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs, const double* h_dimensions, const int* axes,
+                            double r_cut, double* d_ci, int64_t* d_runs, double* d_nb, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    PairLifePlan plan;
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(pair_life_plan(ctx, fft, n_pairs, h_pairs, h_dimensions, axes, r_cut, d_ci || d_runs || d_nb, &plan));
+    return pair_life_launch(ctx, fft, plan, d_ci, d_runs, d_nb, stream, nullptr);
+    });
+}
+
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guarded(fail, ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
@@ -3379,6 +3691,62 @@ int ta_vanhove_distinct(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int64_t 
     int64_t* d_out = nullptr;
     TA_CHECK(vhd_launch(ctx, p, h_lags, dr, nullptr, ctx->stream, &d_out));
     return host_finish(ctx, {{(double*)h_counts, (const double*)d_out, (size_t)n_lags * (size_t)(n_bins + 1)}});  // (8-byte elements)
+    });
+}
+
+int ta_pair_find(ta_ctx* ctx, int64_t n_a, const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions,
+                 const int* axes, double r_cut, int64_t search_stride, int64_t* n_pairs) {
+    return host_call(ctx, [&]() -> int {
+    PairFindPlan p;
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(pair_find_plan(ctx, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, r_cut, search_stride, n_pairs, &p));
+    if (ctx->is_cpu) {
+        ctx->pair_n = -1;
+        TA_CHECK(cpu_rc(ctx, ta::cpu::pair_find(cpu_state(ctx), p.n_a, p.ida.data(), p.n_b, p.idb.data(), p.same, search_stride,
+                                                p.box.hm.empty() ? nullptr : p.box.hm.data(), p.box.per_frame, p.rc2, &ctx->pair_host)));
+        ctx->pair_n = (int64_t)(ctx->pair_host.size() / 2), ctx->pair_A = p.A;
+    } else {
+        TA_CHECK(pair_find_launch(ctx, p));
+    }
+    *n_pairs = ctx->pair_n;
+    return TA_OK;
+    });
+}
+
+int ta_pair_find_read(ta_ctx* ctx, int64_t capacity, int32_t* h_pairs) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    if (ctx->pair_n < 0 || (!ctx->is_cpu && !ctx->pair_list.p))
+        return fail(ctx, TA_E_STATE, "pair_find_read: no pair list has been found (ta_pair_find comes first; ta_trim and a new staging release it)");
+    if (capacity < ctx->pair_n)
+        return fail(ctx, TA_E_INVALID, "pair_find_read: capacity " + std::to_string(capacity) + " is smaller than the " +
+                                           std::to_string(ctx->pair_n) + " pairs found");
+    if (ctx->pair_n == 0) return fail(ctx, TA_E_STATE, "pair_find_read: the found pair list is empty");
+    if (!h_pairs) return fail(ctx, TA_E_INVALID, "pair_find_read: the pairs output is NULL");
+    const size_t bytes = sizeof(int32_t) * 2 * (size_t)ctx->pair_n;
+    if (ctx->is_cpu) {
+        memcpy(h_pairs, ctx->pair_host.data(), bytes);
+        return TA_OK;
+    }
+    TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TA_HIP_TRY(ctx, hipMemcpyAsync(h_pairs, ctx->pair_list.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return host_wait(ctx);
+    });
+}
+
+int ta_pair_lifetime(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs, const double* h_dimensions, const int* axes,
+                     double r_cut, double* h_ci, int64_t* h_runs, double* h_nb) {
+    return host_call(ctx, [&]() -> int {
+    PairLifePlan p;
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(pair_life_plan(ctx, fft, n_pairs, h_pairs, h_dimensions, axes, r_cut, h_ci || h_runs || h_nb, &p));
+    if (ctx->is_cpu)
+        return cpu_rc(ctx, ta::cpu::pair_lifetime(cpu_state(ctx), fft != 0, p.P, h_pairs ? h_pairs : ctx->pair_host.data(),
+                                                  p.box.hm.empty() ? nullptr : p.box.hm.data(), p.box.per_frame, p.rc2, h_ci, h_runs, h_nb));
+    double* d_out = nullptr;
+    TA_CHECK(pair_life_launch(ctx, fft, p, h_ci, h_runs, h_nb, ctx->stream, &d_out));
+    const size_t T = (size_t)ctx->st_T;  // (int64 counts travel as 8-byte elements)
+    return host_finish(ctx, {{h_ci, d_out, T}, {(double*)h_runs, d_out + T, T + 1}, {h_nb, d_out + 2 * T + 1, T}});
     });
 }
 

@@ -41,6 +41,7 @@
 #include "cpu_backend.hpp"
 #include "kcurrent_math.hpp"
 #include "orient_math.hpp"
+#include "pair_math.hpp"
 #include "unwrap_box.hpp"
 #include "vanhove_distinct_math.hpp"
 #include "vanhove_math.hpp"
@@ -938,6 +939,155 @@ int vanhove_distinct(const State& s, int L, const int64_t* lags, int64_t stride,
     return f32 ? vanhove_distinct_d<float, false>(s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts)
                : vanhove_distinct_d<double, false>(s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts);
 }
+
+// ---- pair lifetimes (pair_math.hpp) ---------------------------------------------------------------------------------
+template <class E, int D, bool PERIODIC>
+int pair_find_t(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, bool same, int64_t stride,
+                const double* hm, bool per_frame, double rc2, std::vector<int32_t>* pairs) {
+    const int64_t T = s.T, A = s.A, words_b = (n_b + 63) / 64;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    std::vector<uint64_t> bits;
+    try {
+        bits.assign((size_t)n_a * (size_t)words_b, 0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+#pragma omp parallel for num_threads(s.threads > 0 ? s.threads : 1) schedule(dynamic)
+    for (int64_t p = 0; p < n_a; ++p) {
+        uint64_t* row = bits.data() + (size_t)p * words_b;
+        for (int64_t t = 0; t < T; t += stride) {
+            double H[3] = {1.0, 1.0, 1.0}, M[3] = {1.0, 1.0, 1.0};
+            if (PERIODIC) {
+                const double* box = hm + (per_frame ? t * 6 : 0);
+                for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
+            }
+            double a[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
+            for (int d = 0; d < D; ++d) a[d] = (double)x[((size_t)t * A + ida[p]) * D + d];
+            for (int64_t q = same ? p + 1 : 0; q < n_b; ++q) {
+                if (idb[q] == ida[p]) continue;
+                for (int d = 0; d < D; ++d) b[d] = (double)x[((size_t)t * A + idb[q]) * D + d];
+                if (pair_bonded<D, PERIODIC>(a, b, H, M, rc2)) row[q >> 6] |= (uint64_t)1 << (q & 63);
+            }
+        }
+    }
+    try {
+        pairs->clear();
+        for (int64_t p = 0; p < n_a; ++p)
+            for (int64_t w = 0; w < words_b; ++w)
+                for (uint64_t m = bits[(size_t)p * words_b + w]; m; m &= m - 1) {
+                    pairs->push_back(ida[p]);
+                    pairs->push_back(idb[w * 64 + __builtin_ctzll(m)]);
+                }
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    return TA_OK;
+}
+
+template <class E, int D, bool PERIODIC>
+int pair_lifetime_t(const State& s, bool fft, int64_t P, const int32_t* pairs, const double* hm, bool per_frame, double rc2, double* ci,
+                    int64_t* runs, double* nb) {
+    const int64_t T = s.T, A = s.A, W = (T + 63) / 64;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    const int nth = s.threads > 0 ? s.threads : 1;
+    const size_t per = 3 * (size_t)T + 1;  // a thread's ci | nb | runs
+    std::vector<int64_t> acc;
+    std::vector<uint64_t> words;
+    std::vector<double> ind;
+    try {
+        acc.assign((size_t)nth * per, 0);
+        words.assign((size_t)nth * (size_t)(W + 1), 0);
+        if (ci && fft) ind.assign((size_t)T * (size_t)P, 0.0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+#pragma omp parallel for num_threads(nth) schedule(dynamic)
+    for (int64_t n = 0; n < P; ++n) {
+        const int th = omp_get_thread_num();
+        int64_t *a_ci = acc.data() + (size_t)th * per, *a_nb = a_ci + T, *a_runs = a_nb + T;
+        uint64_t* w = words.data() + (size_t)th * (size_t)(W + 1);
+        std::fill(w, w + W + 1, (uint64_t)0);  // (w[W] stays 0: the word behind the last)
+        const int32_t ia = pairs[2 * n], ib = pairs[2 * n + 1];
+        for (int64_t t = 0; t < T; ++t) {
+            double H[3] = {1.0, 1.0, 1.0}, M[3] = {1.0, 1.0, 1.0};
+            if (PERIODIC) {
+                const double* box = hm + (per_frame ? t * 6 : 0);
+                for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
+            }
+            double a[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
+            for (int d = 0; d < D; ++d) a[d] = (double)x[((size_t)t * A + ia) * D + d], b[d] = (double)x[((size_t)t * A + ib) * D + d];
+            if (pair_bonded<D, PERIODIC>(a, b, H, M, rc2)) {
+                w[t >> 6] |= (uint64_t)1 << (t & 63);
+                ++a_nb[t];
+                if (!ind.empty()) ind[(size_t)t * P + n] = 1.0;
+            }
+        }
+        if (runs) {
+            long long carry = 0;
+            for (int64_t j = 0; j < W; ++j) {
+                const uint64_t m = w[j];
+                if (carry && !(m & 1)) ++a_runs[carry];
+                for (uint64_t ends = m & ~(m >> 1) & ~((uint64_t)1 << 63); ends; ends &= ends - 1)
+                    ++a_runs[pair_runs_word(m, __builtin_ctzll(ends), carry)];
+                carry = pair_runs_carry(m, carry);
+            }
+            if (carry) ++a_runs[carry];
+        }
+        if (ci && !fft) {  // sum_t h(t) h(t + tau): the popcount of the series against itself moved down by tau
+            for (int64_t tau = 0; tau < T; ++tau) {
+                const int64_t jw = tau >> 6;
+                const int sh = (int)(tau & 63);
+                int64_t c = 0;
+                for (int64_t j = 0; j + jw < W; ++j) {
+                    const uint64_t moved = sh ? (w[j + jw] >> sh) | (w[j + jw + 1] << (64 - sh)) : w[j + jw];
+                    c += __builtin_popcountll(w[j] & moved);
+                }
+                a_ci[tau] += c;
+            }
+        }
+    }
+    auto total = [&](size_t off, size_t i) {
+        int64_t v = 0;
+        for (int th = 0; th < nth; ++th) v += acc[(size_t)th * per + off + i];
+        return v;
+    };
+    if (ci && !fft)
+        for (int64_t k = 0; k < T; ++k) ci[k] = (double)total(0, (size_t)k);
+    if (nb)
+        for (int64_t t = 0; t < T; ++t) nb[t] = (double)total((size_t)T, (size_t)t);
+    if (runs)
+        for (int64_t l = 0; l <= T; ++l) runs[l] = total(2 * (size_t)T, (size_t)l);
+    if (ci && fft) {  // the (T, P) indicator array is a slab of P atoms with dim 1
+        const State v = f64_slab(s.threads, T, P, 1, ind.data());
+        if (int rc = vacf_fft(v, ci, nullptr)) return rc;
+        for (int64_t k = 0; k < T; ++k) ci[k] *= (double)(T - k);
+    }
+    return TA_OK;
+}
+
+// fn(E(), D, PERIODIC) as template arguments for the staged element type, dim and box
+#define TA_PAIR_DISPATCH(fn, ...)                                                                                  \
+    do {                                                                                                           \
+        const bool f32 = s.dtype == TA_F32;                                                                        \
+        if (hm) {                                                                                                  \
+            if (s.D == 1) return f32 ? fn<float, 1, true>(__VA_ARGS__) : fn<double, 1, true>(__VA_ARGS__);         \
+            if (s.D == 2) return f32 ? fn<float, 2, true>(__VA_ARGS__) : fn<double, 2, true>(__VA_ARGS__);         \
+            return f32 ? fn<float, 3, true>(__VA_ARGS__) : fn<double, 3, true>(__VA_ARGS__);                       \
+        }                                                                                                          \
+        if (s.D == 1) return f32 ? fn<float, 1, false>(__VA_ARGS__) : fn<double, 1, false>(__VA_ARGS__);           \
+        if (s.D == 2) return f32 ? fn<float, 2, false>(__VA_ARGS__) : fn<double, 2, false>(__VA_ARGS__);           \
+        return f32 ? fn<float, 3, false>(__VA_ARGS__) : fn<double, 3, false>(__VA_ARGS__);                         \
+    } while (0)
+
+int pair_find(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, bool same, int64_t stride,
+              const double* hm, bool per_frame, double rc2, std::vector<int32_t>* pairs) {
+    TA_PAIR_DISPATCH(pair_find_t, s, n_a, ida, n_b, idb, same, stride, hm, per_frame, rc2, pairs);
+}
+int pair_lifetime(const State& s, bool fft, int64_t P, const int32_t* pairs, const double* hm, bool per_frame, double rc2, double* ci,
+                  int64_t* runs, double* nb) {
+    TA_PAIR_DISPATCH(pair_lifetime_t, s, fft, P, pairs, hm, per_frame, rc2, ci, runs, nb);
+}
+#undef TA_PAIR_DISPATCH
 
 template <class E>
 int compound_t(const State& s, int64_t C, const int64_t* off, const int32_t* members, const double* w, const double* u,

@@ -82,6 +82,18 @@ int overlap(const State& s, int L, const int64_t* lags, int C, const double* cut
 // the caller
 int vanhove_distinct(const State& s, int L, const int64_t* lags, int64_t stride, int64_t n_a, const int32_t* ida, int64_t n_b,
                      const int32_t* idb, const double* hm, bool per_frame, int B, double dr, int64_t* counts);
+// ta_pair_find: the pairs (ida[p], idb[q]) of different items of slab 0 that are closer than sqrt(rc2) in at least one of the
+// frames t = stride o, with pair_math.hpp's arithmetic, as pair_lifetime.hip: *pairs = the list (n, 2) sorted by (a, b); same:
+// b is a, only q > p is listed.  OpenMP over the a-items, each of which owns its row of the bitmap.  hm as vanhove_distinct's.
+int pair_find(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, bool same, int64_t stride,
+              const double* hm, bool per_frame, double rc2, std::vector<int32_t>* pairs);
+// ta_pair_lifetime: of the P atom pairs `pairs` (P, 2) of slab 0 with the indicator h of pair_math.hpp: ci (T) = sum over pairs and
+// t < T - tau of h(t) h(t + tau) (fft false: popcounts of the packed series, exact integers; fft true: the FFT lag sums of the
+// indicator array, times T - tau), runs (T + 1) = the histogram of the lengths of the maximal runs of bonded frames, nb (T) =
+// the bonded pairs per frame; each may be NULL.  OpenMP over pairs, integer sums per thread, added at the end: nothing
+// depends on the number of threads.
+int pair_lifetime(const State& s, bool fft, int64_t P, const int32_t* pairs, const double* hm, bool per_frame, double rc2, double* ci,
+                  int64_t* runs, double* nb);
 // ta_compound: out (n_frames, n_compounds, dim) float64 = sum_{i in [offsets[c], offsets[c + 1])} w_i x[t, members[i], d] -
 // g_c F[t, d] of slab 0 (g_c = sum_i w_i, F = sum_a u_a x[t, a, d]; frame_weights NULL: no such term; weights NULL: all 1),
 // the sum in member order (the first product, then fma), parallel over compounds; arguments checked by the caller

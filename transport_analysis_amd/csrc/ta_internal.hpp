@@ -406,7 +406,8 @@ hipError_t launch_overlap(int n_cu, const void* x, bool f32, long pitch, long T,
 // which size the scratch of every lag.
 //   launch_vhd_gather: the frame-major float64 scratch of a chunk of Lc lags (device array `lags`: the chunk's) from a
 //   pair-major slab of float64 or (f32) float32 elements, read as it is: ga [n_orig][D][pitch_a] (with_a: written by this
-//   launch), gb [Lc][n_orig][D][pitch_b]; rows at or past T are neither read nor written.
+//   launch), gb [Lc][n_orig][D][pitch_b]; rows at or past T are neither read nor written.  o_base: origin 0 of the scratch
+//   is origin o_base of the slab (the pair search gathers its frames in chunks; 0: the whole set of origins).
 //   launch_vhd_pairs: origins [o0, o0 + n_o) (n_o <= 65535) of the chunk's lags: counts (Lc, B + 1) uint64 (zeroed by the
 //   caller before the first launch) gets the bins added.  hm: NULL (no box) or per box H[3], M[3] of the staged columns
 //   (one box, or one per frame: box_per_frame); e: the B + 1 squared edges (device), inv_dr: vanhove_math.hpp's factor.
@@ -414,11 +415,37 @@ constexpr int VHD_TILE_A = 256, VHD_TILE_B = 1024;
 constexpr long VHD_MAX_TILES = 1L << 24;  // a-tiles x b-tiles of one launch: x 256 threads stays below 2^32
 hipError_t launch_vhd_gather(const void* x, bool f32, long pitch, long T, long n_atoms, int D, long stride, long n_orig,
                              const int64_t* lags, int Lc, bool with_a, const int* ida, const int* idb, long pitch_a, long pitch_b,
-                             double* ga, double* gb, hipStream_t st);
+                             double* ga, double* gb, hipStream_t st, long o_base = 0);
 hipError_t launch_vhd_pairs(const double* ga, const double* gb, const int* ida, const int* idb, long pitch_a, long pitch_b, long n_a,
                             long n_b, int D, long T, long stride, long n_orig, long o0, int n_o, const int64_t* lags, int Lc,
                             const double* hm, bool box_per_frame, const double* e, int B, float inv_dr, unsigned long long* counts,
                             hipStream_t st);
+
+// pair_lifetime.hip: the pair population correlation functions (pair_math.hpp).
+//   launch_pair_find: the searched frames [o_base, o_base + n_o) stride (n_o <= 65535) of the scratch ga [n_o][D][pitch_a],
+//   gb [n_o][D][pitch_b] that launch_vhd_gather wrote at lag 0 with the same o_base: bit (p, q) of bitmap [pitch_a][pitch_b /
+//   64] (zeroed by the caller before the first chunk) is set where items a_p != b_q are closer than sqrt(rc2) (same: b is a,
+//   only q > p).  hm as launch_vhd_pairs'.
+//   launch_pair_count / launch_pair_list: counts[block] = the set bits of the block's words (pair_list_blocks(n_words)
+//   blocks); with offs[block] their exclusive scan, pairs (n, 2) int32 = the item ids of the set bits in (a, b) order.
+//   launch_pair_series: the float64 indicator block Z (ceil(n_pairs / 2) destination pairs of `pitch` rows: n_pairs
+//   pseudo-atoms of dim 1, 1.0 / 0.0, rows T ... pitch - 1 and an odd n_pairs' phantom column zeros) of the atom pairs
+//   `pairs` (n_pairs, 2) (device int32) of a pair-major slab of float64 or (f32) float32 elements, read as it is.
+//   launch_pair_runs: runs[l] += the maximal runs of l consecutive bonded frames of such a block (T + 1 entries, uint64).
+//   launch_pair_reduce: out[i] = sum over n_rows rows of n values in row order: as they are (PAIR_SUM), times T - i
+//   (PAIR_LAGS: the lag sums carry 1 / (T - i)), or that rounded to the integer it stands for (PAIR_LAGS_INT).
+enum { PAIR_SUM = 0, PAIR_LAGS = 1, PAIR_LAGS_INT = 2 };
+long pair_list_blocks(long n_words);
+hipError_t launch_pair_find(const double* ga, const double* gb, const int* ida, const int* idb, long pitch_a, long pitch_b, long n_a,
+                            long n_b, int D, long T, long stride, long o_base, int n_o, const double* hm, bool box_per_frame,
+                            double rc2, bool same, unsigned long long* bitmap, hipStream_t st);
+hipError_t launch_pair_count(const unsigned long long* bitmap, long n_words, unsigned* counts, hipStream_t st);
+hipError_t launch_pair_list(const unsigned long long* bitmap, long n_words, long words_b, const long long* offs, const int* ida,
+                            const int* idb, int* pairs, hipStream_t st);
+hipError_t launch_pair_series(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, long n_pairs,
+                              const int* pairs, const double* hm, bool box_per_frame, double rc2, double* Z, hipStream_t st);
+hipError_t launch_pair_runs(int n_cu, const double* Z, long pitch, long T, long n_pairs, unsigned long long* runs, hipStream_t st);
+hipError_t launch_pair_reduce(const double* rows, int n_rows, long n, long T, int mode, double* out, hipStream_t st);
 
 // unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
 // box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)

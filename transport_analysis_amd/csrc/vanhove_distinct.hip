@@ -46,12 +46,13 @@ static_assert(kVhdTA == VHD_TILE_A && kVhdTB == VHD_TILE_B, "ta_internal.hpp pad
 
 // grid (item blocks of the pitch, origins (looped), slots): slot z < with_a is GA, the others the chunk's lags.  ids: the
 // padded index list of the slot's side (-1: padding, written as zeros).  A lagged row t + tau >= T is neither read nor
-// written: k_vhd_pairs never starts a workgroup for it.
+// written: k_vhd_pairs never starts a workgroup for it.  o_base: the scratch's origin 0 is origin o_base of the slab (0 for
+// the van Hove passes; the pair search of pair_lifetime.hip gathers its searched frames in chunks).
 template <class E, int D>
 __global__ void __launch_bounds__(kPmThreads)
     k_vhd_gather(const E* __restrict__ x, long pitch, long T, long stride, long n_orig, const long* __restrict__ lags, int with_a,
                  const int* __restrict__ ida, const int* __restrict__ idb, long pitch_a, long pitch_b, double* __restrict__ ga,
-                 double* __restrict__ gb) {
+                 double* __restrict__ gb, long o_base) {
     const int z = blockIdx.z;
     const bool side_a = z < with_a;
     const long ip = side_a ? pitch_a : pitch_b;
@@ -61,7 +62,7 @@ __global__ void __launch_bounds__(kPmThreads)
     const long tau = side_a ? 0 : lags[z - with_a];
     double* out = side_a ? ga : gb + (size_t)(z - with_a) * (size_t)n_orig * D * (size_t)pitch_b;
     for (long o = blockIdx.y; o < n_orig; o += gridDim.y) {
-        const long t = o * stride + tau;
+        const long t = (o_base + o) * stride + tau;
         if (t >= T) break;
         double v[3] = {0.0, 0.0, 0.0};
         if (id >= 0) {
@@ -141,8 +142,8 @@ __global__ void __launch_bounds__(kPmThreads)
 
 hipError_t launch_vhd_gather(const void* x, bool f32, long pitch, long T, long n_atoms, int D, long stride, long n_orig,
                              const int64_t* lags, int Lc, bool with_a, const int* ida, const int* idb, long pitch_a, long pitch_b,
-                             double* ga, double* gb, hipStream_t st) {
-    if (!pm_slab_ok(pitch, T, n_atoms, D) || stride < 1 || n_orig < 1 || (n_orig - 1) * stride >= T || Lc < 1 ||
+                             double* ga, double* gb, hipStream_t st, long o_base) {
+    if (!pm_slab_ok(pitch, T, n_atoms, D) || stride < 1 || n_orig < 1 || o_base < 0 || (o_base + n_orig - 1) * stride >= T || Lc < 1 ||
         Lc > TA_VANHOVE_MAX_LAGS || pitch_a < 1 || pitch_b < 1 || pitch_a % VHD_TILE_A || pitch_b % VHD_TILE_B)
         return hipErrorInvalidValue;
     const long ip = std::max(pitch_a, pitch_b);
@@ -150,7 +151,7 @@ hipError_t launch_vhd_gather(const void* x, bool f32, long pitch, long T, long n
     pm_dispatch(f32, D, [&](auto e, auto d) {
         using E = decltype(e);
         hipLaunchKernelGGL((k_vhd_gather<E, d()>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, stride, n_orig, pm_lags(lags),
-                           with_a ? 1 : 0, ida, idb, pitch_a, pitch_b, ga, gb);
+                           with_a ? 1 : 0, ida, idb, pitch_a, pitch_b, ga, gb, o_base);
     });
     return hipGetLastError();
 }
