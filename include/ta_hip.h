@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_pair_find / ta_pair_find_read / ta_pair_lifetime / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_pair_find / ta_pair_find_read / ta_pair_lifetime / ta_bond_lifetime / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -552,6 +552,46 @@ int ta_pair_lifetime(ta_ctx *ctx, int fft, int64_t n_pairs, const int32_t *h_pai
                      const double *h_dimensions, const int *axes, double r_cut, double *h_ci /* (T) */,
                      int64_t *h_runs /* (T + 1), [0] = 0 */, double *h_nb /* (T) */);
 
+/* ta_bond_lifetime : ta_pair_lifetime's three sums for bonds with an angle criterion, separate form and break criteria
+ *              (hysteresis) and a tolerated absence (HydrogenBondLifetime, PairLifetime(r_break=, intermittency=)).  A bond
+ *              is row n of h_atoms (n_bonds, n_at) int32 (HOST; distinct in-range items of slab 0): n_at = 2 a pair (p, q),
+ *              n_at = 3 a triplet (d, h, a) = donor, hydrogen, acceptor.  In frame t, with the box of frame t
+ *                r2   = ta_pair_lifetime's r2 between the FIRST and the LAST item of the row, in its order
+ *                u_j  = image(x[t, d, j] - x[t, h, j]),  v_j = image(x[t, a, j] - x[t, h, j])        (triplets; the one-step image)
+ *                dot  = u_0 v_0, then fma(u_1, v_1, dot), then fma(u_2, v_2, dot);  uu = u.u and vv = v.v the same way
+ *                ang_ok(c2) = dot <= 0 && dot dot >= (c2 uu) vv      every product alone in its statement; c2 = fl(cos_cut cos_cut)
+ *                             and cb2 = fl(cos_break cos_break) formed once on the host: the angle D-H-A is at least
+ *                             acos(cos_cut), for cos_cut in [-1, 0] (90 ... 180 degrees), without a square root or an acos
+ *                form = r2 < rc2 && ang_ok(c2),   brk = r2 < rb2 && ang_ok(cb2),   rc2 = fl(r_cut r_cut), rb2 = fl(r_break r_break)
+ *                s(t) = brk ? (form ? 2 : 1) : 0                                                        the level
+ *                h(t) = [s(t) = 2] || ([s(t) >= 1] && h(t - 1)),  h(-1) = 0                             hysteresis
+ *                g(t) = h(t) || (t1 < t < t2 exist with h(t1) = h(t2) = 1 and t2 - t1 - 1 <= gap)        gap tolerance
+ *              and h_ci, h_runs, h_nb are ta_pair_lifetime's outputs of the 0/1 series g; its exactness statements carry
+ *              over.  Choices: the angle test is INCLUSIVE (a triplet exactly on the angle is bonded), the distance test
+ *              STRICT as ta_pair_lifetime's.  With n_at = 2 there is no angle: cos_cut and cos_break are IGNORED (not even
+ *              checked).  r_break >= r_cut and cos_break >= cos_cut: form implies brk; with both equal h = form.  A bond
+ *              forms at level 2 and lasts while the level stays >= 1 (the stable-states picture).  An absence of at most
+ *              gap frames BETWEEN two bonded frames is filled and counts as bonded in every output (MDAnalysis'
+ *              intermittency, the tolerated absence t* of residence times); absences at the start and the end of the
+ *              series are never filled.  gap is 0 ... 63: the series are filtered as 64-frame words, and an absence of up to
+ *              63 frames is decided by a window of three words (the one before, the frame's own, the one behind).
+ *              Passes: ta_pair_lifetime's, on its blocks ("pair_chunk"), with k_bond_series in k_pair_series' place: it
+ *              writes the level 0.0 / 1.0 / 2.0, and k_pair_filter turns the block into g in place (a wave per destination
+ *              pair; the ballots of v == 2 and v >= 1 are the words; hysteresis is a fill of six shift / and / or steps with
+ *              one carry bit across words; no atomics, no loop whose trip count depends on the data).  With gap = 0 and the
+ *              break criterion equal to the form criterion there is nothing to filter: k_pair_filter is not launched and
+ *              k_bond_series writes 1.0 for level 2; with n_at = 2 the outputs then have ta_pair_lifetime's bits.  The CPU
+ *              backend follows the same arithmetic on the same packed words: its outputs (ci with fft = 0) EQUAL the GPU's.
+ *              Errors, all checked before anything is written.  TA_E_INVALID: fft other than 0 / 1; all three outputs NULL;
+ *              n_at other than 2 or 3; r_cut not finite or <= 0; r_break not finite or below r_cut; a cosine outside
+ *              [-1, 0] or not finite; cos_break < cos_cut; gap outside 0 ... 63; n_bonds < 1 or >= 2^30, h_atoms NULL; a row
+ *              naming an item out of range or twice; h_dimensions without axes, a non-orthogonal box, r_break above half an
+ *              analysed box length in any frame; n_atoms * dim at or above 2^31.  TA_E_STATE: nothing staged.  There is no
+ *              found-list form and no ta_group_* form.  k_bond_series (its last launch) is the main kernel.            */
+int ta_bond_lifetime(ta_ctx *ctx, int fft, int64_t n_bonds, int n_at, const int32_t *h_atoms /* (n_bonds, n_at) */,
+                     const double *h_dimensions, const int *axes, double r_cut, double r_break, double cos_cut,
+                     double cos_break, int gap, double *h_ci /* (T) */, int64_t *h_runs /* (T + 1) */, double *h_nb /* (T) */);
+
 /* ta_orient  : the rotational correlation functions of molecule-fixed unit vectors of the positions in slab 0
  *              (OrientationalCorrelation), three staged columns per atom.  A vector n is row n of h_index, atoms of slab 0,
  *              pairwise distinct and in [0, n_atoms):
@@ -790,6 +830,11 @@ int ta_vanhove_distinct_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, i
  * NULL, not all three */
 int ta_pair_lifetime_staged(ta_ctx *ctx, int fft, int64_t n_pairs, const int32_t *h_pairs, const double *h_dimensions,
                             const int *axes, double r_cut, double *d_ci, int64_t *d_runs, double *d_nb, void *stream);
+/* the bond list and the box: HOST arrays, as for ta_bond_lifetime (checked before anything is written); the outputs on the
+ * device, as ta_pair_lifetime_staged's */
+int ta_bond_lifetime_staged(ta_ctx *ctx, int fft, int64_t n_bonds, int n_at, const int32_t *h_atoms, const double *h_dimensions,
+                            const int *axes, double r_cut, double r_break, double cos_cut, double cos_break, int gap,
+                            double *d_ci, int64_t *d_runs, double *d_nb, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns

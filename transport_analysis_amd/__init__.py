@@ -6,7 +6,8 @@ VanHoveSelf, and the distinct van Hove function G_d(r, t) with the radial distri
 the longitudinal and transverse current correlation functions C_L(k, t) and C_T(k, t), CurrentCorrelation, and the
 self-overlap Q(t) with the four-point susceptibility chi_4(t), DynamicSusceptibility, and the rotational correlation functions
 C_1(t), C_2(t) of molecule-fixed unit vectors with their dipole sum, OrientationalCorrelation, and the intermittent and
-continuous pair population correlation functions with the lifetimes of ion pairs and hydrogen bonds, PairLifetime."""
+continuous pair population correlation functions with the lifetimes of ion pairs and solvation contacts, PairLifetime, and
+of hydrogen bonds with a donor-hydrogen-acceptor angle criterion, HydrogenBondLifetime."""
 __version__ = "0.1.0"
 
 from .velocityautocorr import VelocityAutocorr  # noqa: F401
@@ -22,3 +23,4 @@ from .vanhove_distinct import VanHoveDistinct  # noqa: F401
 from .susceptibility import DynamicSusceptibility  # noqa: F401
 from .orientation import OrientationalCorrelation, group_indices  # noqa: F401
 from .pair_lifetime import PairLifetime  # noqa: F401
+from .hbond_lifetime import HydrogenBondLifetime  # noqa: F401

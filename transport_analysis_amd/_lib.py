@@ -88,6 +88,9 @@ _API = {
     "ta_pair_find_read": _int(_vp, _i64, _vp),
     "ta_pair_lifetime": _int(_vp, _ci, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp),
     "ta_pair_lifetime_staged": _int(_vp, _ci, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp),
+    # (handle, fft, n_bonds, n_at, h_atoms, h_dimensions, axes, r_cut, r_break, cos_cut, cos_break, gap, ci, runs, nb[, stream])
+    "ta_bond_lifetime": _int(_vp, _ci, _i64, _ci, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _ci, _vp, _vp, _vp),
+    "ta_bond_lifetime_staged": _int(_vp, _ci, _i64, _ci, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp),
     "ta_vanhove_distinct_staged": _int(_vp, _ci, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _dbl, _vp, _vp),
     "ta_compound": _int(_vp, _i64, _vp, _vp, _vp, _vp, _P(_vp)),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
@@ -950,6 +953,43 @@ class Context(_Staged):
         (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
         args, keep = self._pair_args(fft, pairs, r_cut, dimensions, axes)
         self._call("pair_lifetime_staged", *args, d_ci or None, d_runs or None, d_nb or None, stream or None)
+        del keep
+
+    def _bond_args(self, fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes):
+        """the argument tuple ta_bond_lifetime* share, and the arrays it points into (to be kept until the call is over)"""
+        at = np.ascontiguousarray(atoms)
+        if at.ndim != 2 or at.shape[1] not in (2, 3) or not np.issubdtype(at.dtype, np.integer):
+            raise ValueError(f"atoms: shape {at.shape} and dtype {at.dtype}, expected an integer (n_bonds, 2) or (n_bonds, 3) array")
+        if at.size and (at.min() < -2**31 or at.max() >= 2**31):
+            raise ValueError("atoms: entries must fit int32")
+        at = np.ascontiguousarray(at, dtype=np.int32)
+        dims, ax = self._pair_box(dimensions, axes)
+        r_break = r_cut if r_break is None else r_break
+        cos_break = cos_cut if cos_break is None else cos_break
+        return (int(fft), int(at.shape[0]), int(at.shape[1]), _ptr(at), _ptr(dims), _ptr(ax), float(r_cut), float(r_break),
+                float(cos_cut), float(cos_break), int(gap)), (at, dims, ax)
+
+    def bond_lifetime(self, fft, atoms, r_cut, *, r_break=None, cos_cut=0.0, cos_break=None, gap=0, dimensions=None, axes=None,
+                      ci=True, runs=True, nb=True):
+        """pair_lifetime's sums (ci, runs, nb) of slab 0 for the bonds `atoms`, ta_bond_lifetime: rows (p, q) or (donor,
+        hydrogen, acceptor) of staged item ids; a bond forms below `r_cut` with (triplets) the cosine of the D-H-A angle at most
+        `cos_cut`, lasts while below `r_break` / `cos_break` (None: the form values), and absences of up to `gap` frames (0 ...
+        63) between bonded frames are filled.  One context only: a device group has no such call."""
+        T = self._staged_shape()[0]
+        args, keep = self._bond_args(fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes)
+        o_ci = np.empty(T, dtype=np.float64) if ci else None
+        o_runs = np.empty(T + 1, dtype=np.int64) if runs else None
+        o_nb = np.empty(T, dtype=np.float64) if nb else None
+        self._call("bond_lifetime", *args, _ptr(o_ci), _ptr(o_runs), _ptr(o_nb))
+        del keep
+        return o_ci, o_runs, o_nb
+
+    def bond_lifetime_staged(self, fft, atoms, r_cut, *, r_break=None, cos_cut=0.0, cos_break=None, gap=0, dimensions=None, axes=None,
+                             d_ci=0, d_runs=0, d_nb=0, stream=0):
+        """`atoms`, `dimensions`: HOST arrays (checked by the library before anything is written); d_ci (n_frames,), d_runs
+        (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
+        args, keep = self._bond_args(fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes)
+        self._call("bond_lifetime_staged", *args, d_ci or None, d_runs or None, d_nb or None, stream or None)
         del keep
 
     def _orient_args(self, fft, index, mode, dimensions, weights):

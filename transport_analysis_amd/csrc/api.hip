@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/ta_hip.h"
+#include "bond_math.hpp"
 #include "cpu_backend.hpp"
 #include "direct_kernels.hpp"
 #include "kcurrent_math.hpp"
@@ -1781,7 +1782,8 @@ struct PairBox {
     int64_t n_box = 0;
     std::vector<double> hm;
 };
-int pair_box(ta_ctx* ctx, const std::string& who, const double* h_dims, const int* axes, int64_t T, int D, double r_cut, PairBox* b) {
+int pair_box(ta_ctx* ctx, const std::string& who, const double* h_dims, const int* axes, int64_t T, int D, double r_cut, PairBox* b,
+             const char* cut_name = "r_cut") {
     for (int d = 0; d < D; ++d)
         if (axes[d] < 0 || axes[d] > 2) return fail(ctx, TA_E_INVALID, who + "axes: every entry must be 0, 1 or 2");
     std::vector<double> dims(h_dims, h_dims + 6 * (size_t)T);
@@ -1802,7 +1804,7 @@ int pair_box(ta_ctx* ctx, const std::string& who, const double* h_dims, const in
             b->hm[(size_t)t * 6 + d] = h;
             b->hm[(size_t)t * 6 + 3 + d] = box.tab[(size_t)(6 + diag_row(axes[d])) * box.tpitch + t];
             if (!(r_cut <= 0.5 * h))
-                return fail(ctx, TA_E_INVALID, who + "r_cut = " + std::to_string(r_cut) + " exceeds half the box length " + std::to_string(h) +
+                return fail(ctx, TA_E_INVALID, who + cut_name + " = " + std::to_string(r_cut) + " exceeds half the box length " + std::to_string(h) +
                                                    " of frame " + std::to_string(t));
         }
     return TA_OK;
@@ -1933,24 +1935,73 @@ int pair_find_launch(ta_ctx* ctx, const PairFindPlan& p) {
         [&](const Slab& s) { return pair_find_pm(ctx, s, p); });
 }
 
-// The host side of one lifetime call (both kinds of context).  h_pairs NULL: the context's found list
+// What ta_bond_lifetime* add to a lifetime call: items per row, the break criterion, the gap tolerance
+struct BondArgs {
+    int n_at;
+    double r_break, cos_cut, cos_break;
+    int gap;
+};
+// The host side of one lifetime call (both kinds of context).  h_pairs NULL: the context's found list.  A pair call is a
+// bond call of 2 items per row whose break criterion is its form criterion, without gap tolerance: bond == false, and
+// the pair kernels run as ever.
 struct PairLifePlan {
     int64_t P = 0;
     const int32_t* h_pairs = nullptr;
     double rc2 = 0.0;
     PairBox box;
+    bool bond = false;
+    int n_at = 2, gap = 0;
+    ta::BondCuts cuts{};
+    // the level block needs k_pair_filter: a gap to close, or a break criterion apart from the form criterion
+    bool filter() const { return gap > 0 || cuts.rb2 != cuts.rc2 || (n_at == 3 && cuts.cb2 != cuts.c2); }
+    size_t list_doubles() const { return h_pairs ? ((size_t)n_at * (size_t)P + 1) / 2 : 0; }  // the int32 rows in the table
 };
+int bond_rows(ta_ctx* ctx, const std::string& who, int64_t n_bonds, int n_at, const int32_t* h_atoms, int64_t A) {
+    if (n_bonds < 1 || n_bonds >= (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, who + "n_bonds must be 1 ... 2^30 - 1");
+    if (!h_atoms) return fail(ctx, TA_E_INVALID, who + "the atoms list is NULL");
+    for (int64_t n = 0; n < n_bonds; ++n) {
+        const int32_t* r = h_atoms + (size_t)n_at * (size_t)n;
+        for (int i = 0; i < n_at; ++i) {
+            if (r[i] < 0 || r[i] >= A)
+                return fail(ctx, TA_E_INVALID, who + "bond " + std::to_string(n) + " names item " + std::to_string(r[i]) +
+                                                   " outside 0 ... n_atoms - 1");
+            for (int j = 0; j < i; ++j)
+                if (r[j] == r[i]) return fail(ctx, TA_E_INVALID, who + "bond " + std::to_string(n) + " names item " + std::to_string(r[i]) + " twice");
+        }
+    }
+    return TA_OK;
+}
 int pair_life_plan(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs, const double* h_dims, const int* axes, double r_cut,
-                   bool any_out, PairLifePlan* p) {
-    const std::string who = "pair_lifetime: ";
+                   bool any_out, PairLifePlan* p, const BondArgs* bond = nullptr) {
+    const std::string who = bond ? "bond_lifetime: " : "pair_lifetime: ";
     TA_CHECK(check_fft(ctx, fft));
     if (!any_out) return fail(ctx, TA_E_INVALID, who + "the ci, runs and nb outputs are all NULL");
+    if (bond && bond->n_at != 2 && bond->n_at != 3) return fail(ctx, TA_E_INVALID, who + "n_at must be 2 (pairs) or 3 (donor, hydrogen, acceptor)");
     TA_CHECK(pair_cut_args(ctx, who, r_cut, h_dims, axes));
+    p->rc2 = r_cut * r_cut, p->h_pairs = h_pairs;
+    p->cuts = ta::BondCuts{p->rc2, p->rc2, 0.0, 0.0};
+    if (bond) {
+        p->bond = true, p->n_at = bond->n_at, p->gap = bond->gap;
+        if (!(bond->r_break - bond->r_break == 0.0) || bond->r_break < r_cut)
+            return fail(ctx, TA_E_INVALID, who + "r_break must be finite and at least r_cut");
+        p->cuts.rb2 = bond->r_break * bond->r_break;
+        if (bond->n_at == 3) {  // (pairs have no angle: their cosines are not looked at)
+            for (const double c : {bond->cos_cut, bond->cos_break})
+                if (!(c >= -1.0 && c <= 0.0)) return fail(ctx, TA_E_INVALID, who + "cos_cut and cos_break must lie in [-1, 0] (angles of 90 ... 180 degrees)");
+            if (bond->cos_break < bond->cos_cut)
+                return fail(ctx, TA_E_INVALID, who + "cos_break must be at least cos_cut (the break angle at most the form angle)");
+            p->cuts.c2 = bond->cos_cut * bond->cos_cut, p->cuts.cb2 = bond->cos_break * bond->cos_break;
+        }
+        if (bond->gap < 0 || bond->gap > 63)
+            return fail(ctx, TA_E_INVALID, who + "gap must be 0 ... 63 (absences are closed inside a window of three 64-frame words)");
+    }
     TA_CHECK(check_staged(ctx));
     const int64_t T = ctx->st_T, A = ctx->st_A;
     TA_CHECK(check_cols(ctx, who, A, ctx->st_D));
-    p->rc2 = r_cut * r_cut, p->h_pairs = h_pairs;
-    if (h_pairs) {
+    if (bond) {
+        TA_CHECK(bond_rows(ctx, who, n_pairs, bond->n_at, h_pairs, A));
+        p->P = n_pairs;
+    } else if (h_pairs) {
         if (n_pairs < 1 || n_pairs >= (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, who + "n_pairs must be 1 ... 2^30 - 1");
         for (int64_t n = 0; n < n_pairs; ++n) {
             const int32_t a = h_pairs[2 * n], b = h_pairs[2 * n + 1];
@@ -1968,7 +2019,7 @@ int pair_life_plan(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs
         if (ctx->pair_n == 0) return fail(ctx, TA_E_STATE, who + "the found pair list is empty");
         p->P = ctx->pair_n;
     }
-    if (h_dims) TA_CHECK(pair_box(ctx, who, h_dims, axes, T, ctx->st_D, r_cut, &p->box));
+    if (h_dims) TA_CHECK(pair_box(ctx, who, h_dims, axes, T, ctx->st_D, bond ? bond->r_break : r_cut, &p->box, bond ? "r_break" : "r_cut"));
     return TA_OK;
 }
 
@@ -1985,7 +2036,8 @@ int64_t pair_block(const ta_ctx* ctx, int64_t P, int64_t pitch) {
 // added in block order by k_pair_reduce, which also takes the 1 / (T - tau) out again: with fft = 0 every product is exact,
 // a row's value times (T - tau) is within (partial sums + 2) 2^-53 of the integer it stands for (at most P_b T <= 2^32 with
 // the automatic block), and rint gives that integer: the same bits for every block size.  ev[1] / ev[2] bracket the
-// (last) k_pair_series launch, unless a lag-sum evaluation after it records its own main kernel.
+// (last) k_pair_series launch, unless a lag-sum evaluation after it records its own main kernel.  A bond call (p.bond) has
+// k_bond_series in k_pair_series' place, rows of p.n_at items, and k_pair_filter behind it where p.filter() says so.
 int pair_life_pm(ta_ctx* ctx, bool fft, const Slab& slab, const PairLifePlan& p, double* d_ci, int64_t* d_runs, double* d_nb) {
     hipStream_t st = slab.st;
     const int64_t T = slab.T, pitch = slab.pitch, P = p.P;
@@ -1993,7 +2045,7 @@ int pair_life_pm(ta_ctx* ctx, bool fft, const Slab& slab, const PairLifePlan& p,
     const double* tab = (const double*)ctx->pair_tab.dev.p;
     const double* hm = p.box.n_box ? tab : nullptr;
     const int* pairs = p.h_pairs ? (const int*)(tab + p.box.hm.size()) : (const int*)ctx->pair_list.p;
-    const int* lab = (const int*)(tab + p.box.hm.size() + (p.h_pairs ? (size_t)P : 0));
+    const int* lab = (const int*)(tab + p.box.hm.size() + p.list_doubles());
     TA_CHECK(ensure(ctx, ctx->pair_z, (size_t)((Pc + 1) / 2) * (size_t)pitch * 16));
     const size_t n_rows = (size_t)n_blocks * (size_t)T;
     TA_CHECK(ensure(ctx, ctx->pair_rows, sizeof(double) * (2 * n_rows + (size_t)T + 1)));
@@ -2007,9 +2059,15 @@ int pair_life_pm(ta_ctx* ctx, bool fft, const Slab& slab, const PairLifePlan& p,
     if (d_runs) TA_HIP_TRY(ctx, hipMemsetAsync(runs, 0, sizeof(uint64_t) * ((size_t)T + 1), st));
     for (int64_t b = 0; b < n_blocks; ++b) {
         const int64_t p0 = b * Pc, pb = std::min(Pc, P - p0);
-        TA_LAUNCH_MAIN(ctx, "k_pair_series", st,
-                       launch_pair_series(ctx->n_cu, slab.pm, slab.f32, (long)pitch, (long)T, (long)slab.A, slab.D, (long)pb, pairs + 2 * p0,
-                                          hm, p.box.per_frame, p.rc2, Z, st));
+        if (p.bond)
+            TA_LAUNCH_MAIN(ctx, "k_bond_series", st,
+                           launch_bond_series(ctx->n_cu, slab.pm, slab.f32, (long)pitch, (long)T, (long)slab.A, slab.D, (long)pb, p.n_at,
+                                              pairs + p.n_at * p0, hm, p.box.per_frame, p.cuts, p.filter() ? 2.0 : 1.0, Z, st));
+        else
+            TA_LAUNCH_MAIN(ctx, "k_pair_series", st,
+                           launch_pair_series(ctx->n_cu, slab.pm, slab.f32, (long)pitch, (long)T, (long)slab.A, slab.D, (long)pb, pairs + 2 * p0,
+                                              hm, p.box.per_frame, p.rc2, Z, st));
+        if (p.filter()) TA_LAUNCH(ctx, "k_pair_filter", st, launch_pair_filter(ctx->n_cu, Z, (long)pitch, (long)T, (long)pb, p.gap, st));
         if (d_runs) TA_LAUNCH(ctx, "k_pair_runs", st, launch_pair_runs(ctx->n_cu, Z, (long)pitch, (long)T, (long)pb, runs, st));
         if (d_ci) TA_CHECK(acf_impl(ctx, fft, Z, pitch, T, pb, 1, ci_rows + (size_t)b * T, nullptr, 0, st));
         if (d_nb)
@@ -2030,12 +2088,12 @@ int pair_life_launch(ta_ctx* ctx, int fft, const PairLifePlan& p, double* d_ci, 
         ctx, nullptr, stream, no_args,
         [&](const Slab& s) -> int {
             const int64_t Pc = pair_block(ctx, p.P, s.pitch);
-            const size_t n = p.box.hm.size() + (p.h_pairs ? (size_t)p.P : 0) + ((size_t)Pc + 1) / 2;
+            const size_t n = p.box.hm.size() + p.list_doubles() + ((size_t)Pc + 1) / 2;
             double* h = nullptr;
             TA_CHECK(ctx->pair_tab.begin(ctx, sizeof(double) * n, (void**)&h));
             memset(h, 0, sizeof(double) * n);
             if (!p.box.hm.empty()) memcpy(h, p.box.hm.data(), sizeof(double) * p.box.hm.size());
-            if (p.h_pairs) memcpy(h + p.box.hm.size(), p.h_pairs, sizeof(int32_t) * 2 * (size_t)p.P);
+            if (p.h_pairs) memcpy(h + p.box.hm.size(), p.h_pairs, sizeof(int32_t) * (size_t)p.n_at * (size_t)p.P);
             if (out) {
                 TA_CHECK(ensure(ctx, ctx->pair_out, sizeof(double) * (3 * (size_t)s.T + 1)));
                 *out = (double*)ctx->pair_out.p;
@@ -2951,6 +3009,20 @@ int ta_pair_lifetime_staged(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t
     });
 }
 
+// Bond lifetimes on the staged slab 0: ta_pair_lifetime_staged's path with k_bond_series (and k_pair_filter where needed)
+int ta_bond_lifetime_staged(ta_ctx* ctx, int fft, int64_t n_bonds, int n_at, const int32_t* h_atoms, const double* h_dimensions,
+                            const int* axes, double r_cut, double r_break, double cos_cut, double cos_break, int gap, double* d_ci,
+                            int64_t* d_runs, double* d_nb, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    PairLifePlan plan;
+    const BondArgs bond{n_at, r_break, cos_cut, cos_break, gap};
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(pair_life_plan(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, d_ci || d_runs || d_nb, &plan, &bond));
+    return pair_life_launch(ctx, fft, plan, d_ci, d_runs, d_nb, stream, nullptr);
+    });
+}
+
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guarded(fail, ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
@@ -3746,6 +3818,23 @@ int ta_pair_lifetime(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pai
     double* d_out = nullptr;
     TA_CHECK(pair_life_launch(ctx, fft, p, h_ci, h_runs, h_nb, ctx->stream, &d_out));
     const size_t T = (size_t)ctx->st_T;  // (int64 counts travel as 8-byte elements)
+    return host_finish(ctx, {{h_ci, d_out, T}, {(double*)h_runs, d_out + T, T + 1}, {h_nb, d_out + 2 * T + 1, T}});
+    });
+}
+
+int ta_bond_lifetime(ta_ctx* ctx, int fft, int64_t n_bonds, int n_at, const int32_t* h_atoms, const double* h_dimensions, const int* axes,
+                     double r_cut, double r_break, double cos_cut, double cos_break, int gap, double* h_ci, int64_t* h_runs, double* h_nb) {
+    return host_call(ctx, [&]() -> int {
+    PairLifePlan p;
+    const BondArgs bond{n_at, r_break, cos_cut, cos_break, gap};
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(pair_life_plan(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, h_ci || h_runs || h_nb, &p, &bond));
+    if (ctx->is_cpu)
+        return cpu_rc(ctx, ta::cpu::bond_lifetime(cpu_state(ctx), fft != 0, p.P, p.n_at, h_atoms, p.box.hm.empty() ? nullptr : p.box.hm.data(),
+                                                  p.box.per_frame, p.cuts, p.gap, h_ci, h_runs, h_nb));
+    double* d_out = nullptr;
+    TA_CHECK(pair_life_launch(ctx, fft, p, h_ci, h_runs, h_nb, ctx->stream, &d_out));
+    const size_t T = (size_t)ctx->st_T;
     return host_finish(ctx, {{h_ci, d_out, T}, {(double*)h_runs, d_out + T, T + 1}, {h_nb, d_out + 2 * T + 1, T}});
     });
 }

@@ -41,6 +41,7 @@
 #include "cpu_backend.hpp"
 #include "kcurrent_math.hpp"
 #include "orient_math.hpp"
+#include "bond_math.hpp"
 #include "pair_math.hpp"
 #include "unwrap_box.hpp"
 #include "vanhove_distinct_math.hpp"
@@ -940,7 +941,7 @@ int vanhove_distinct(const State& s, int L, const int64_t* lags, int64_t stride,
                : vanhove_distinct_d<double, false>(s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts);
 }
 
-// ---- pair lifetimes (pair_math.hpp) ---------------------------------------------------------------------------------
+// ---- pair and bond lifetimes (pair_math.hpp, bond_math.hpp) ---------------------------------------------------------------------------------
 template <class E, int D, bool PERIODIC>
 int pair_find_t(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, bool same, int64_t stride,
                 const double* hm, bool per_frame, double rc2, std::vector<int32_t>* pairs) {
@@ -984,11 +985,10 @@ int pair_find_t(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, co
     return TA_OK;
 }
 
-template <class E, int D, bool PERIODIC>
-int pair_lifetime_t(const State& s, bool fft, int64_t P, const int32_t* pairs, const double* hm, bool per_frame, double rc2, double* ci,
-                    int64_t* runs, double* nb) {
-    const int64_t T = s.T, A = s.A, W = (T + 63) / 64;
-    const E* x = static_cast<const E*>(s.slabs[0]);
+// The three sums of P packed 0/1 series: fill(n, w) sets the bits of series n in its W = ceil(T / 64) zeroed words
+template <class Fill>
+int lifetime_sums(const State& s, bool fft, int64_t P, double* ci, int64_t* runs, double* nb, Fill fill) {
+    const int64_t T = s.T, W = (T + 63) / 64;
     const int nth = s.threads > 0 ? s.threads : 1;
     const size_t per = 3 * (size_t)T + 1;  // a thread's ci | nb | runs
     std::vector<int64_t> acc;
@@ -1007,21 +1007,13 @@ int pair_lifetime_t(const State& s, bool fft, int64_t P, const int32_t* pairs, c
         int64_t *a_ci = acc.data() + (size_t)th * per, *a_nb = a_ci + T, *a_runs = a_nb + T;
         uint64_t* w = words.data() + (size_t)th * (size_t)(W + 1);
         std::fill(w, w + W + 1, (uint64_t)0);  // (w[W] stays 0: the word behind the last)
-        const int32_t ia = pairs[2 * n], ib = pairs[2 * n + 1];
-        for (int64_t t = 0; t < T; ++t) {
-            double H[3] = {1.0, 1.0, 1.0}, M[3] = {1.0, 1.0, 1.0};
-            if (PERIODIC) {
-                const double* box = hm + (per_frame ? t * 6 : 0);
-                for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
-            }
-            double a[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
-            for (int d = 0; d < D; ++d) a[d] = (double)x[((size_t)t * A + ia) * D + d], b[d] = (double)x[((size_t)t * A + ib) * D + d];
-            if (pair_bonded<D, PERIODIC>(a, b, H, M, rc2)) {
-                w[t >> 6] |= (uint64_t)1 << (t & 63);
+        fill(n, w);
+        for (int64_t j = 0; j < W; ++j)
+            for (uint64_t m = w[j]; m; m &= m - 1) {
+                const int64_t t = j * 64 + __builtin_ctzll(m);
                 ++a_nb[t];
                 if (!ind.empty()) ind[(size_t)t * P + n] = 1.0;
             }
-        }
         if (runs) {
             long long carry = 0;
             for (int64_t j = 0; j < W; ++j) {
@@ -1065,6 +1057,82 @@ int pair_lifetime_t(const State& s, bool fft, int64_t P, const int32_t* pairs, c
     return TA_OK;
 }
 
+// the box of frame t and the NAT items of a row in it, widened
+template <class E, int D, bool PERIODIC, int NAT>
+void bond_frame(const E* x, int64_t A, int64_t t, const int32_t* row, const double* hm, bool per_frame, double (&H)[3], double (&M)[3],
+                double (&at)[NAT][3]) {
+    for (int d = 0; d < 3; ++d) H[d] = 1.0, M[d] = 1.0;
+    if (PERIODIC) {
+        const double* box = hm + (per_frame ? t * 6 : 0);
+        for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
+    }
+    for (int i = 0; i < NAT; ++i)
+        for (int d = 0; d < 3; ++d) at[i][d] = d < D ? (double)x[((size_t)t * A + row[i]) * D + d] : 0.0;
+}
+
+template <class E, int D, bool PERIODIC>
+int pair_lifetime_t(const State& s, bool fft, int64_t P, const int32_t* pairs, const double* hm, bool per_frame, double rc2, double* ci,
+                    int64_t* runs, double* nb) {
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    return lifetime_sums(s, fft, P, ci, runs, nb, [&](int64_t n, uint64_t* w) {
+        for (int64_t t = 0; t < s.T; ++t) {
+            double H[3], M[3], at[2][3];
+            bond_frame<E, D, PERIODIC, 2>(x, s.A, t, pairs + 2 * n, hm, per_frame, H, M, at);
+            if (pair_bonded<D, PERIODIC>(at[0], at[1], H, M, rc2)) w[t >> 6] |= (uint64_t)1 << (t & 63);
+        }
+    });
+}
+
+// the level words S (level 2) and W (level >= 1) of bond n, then hysteresis word by word and the closing of every clear bit
+// of a word against the words around it (bond_math.hpp): w gets g
+template <class E, int D, bool PERIODIC, int NAT>
+void bond_fill(const State& s, const int32_t* row, const double* hm, bool per_frame, const BondCuts& cuts, int gap, uint64_t* w,
+               uint64_t* S) {
+    const int64_t T = s.T, nw = (T + 63) / 64;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    std::fill(S, S + nw, (uint64_t)0);
+    for (int64_t t = 0; t < T; ++t) {  // (w holds the W bits first)
+        double H[3], M[3], at[NAT][3];
+        bond_frame<E, D, PERIODIC, NAT>(x, s.A, t, row, hm, per_frame, H, M, at);
+        const int level = bond_level<D, PERIODIC, NAT>(at, H, M, cuts);
+        if (level >= 1) w[t >> 6] |= (uint64_t)1 << (t & 63);
+        if (level == 2) S[(size_t)(t >> 6)] |= (uint64_t)1 << (t & 63);
+    }
+    bool carry = false;
+    for (int64_t j = 0; j < nw; ++j) {
+        w[j] = bond_hyst_word(S[(size_t)j], w[j], carry);
+        carry = w[j] >> 63;
+    }
+    if (!gap) return;
+    uint64_t prev = 0;  // (the word before, as it was before its own closing)
+    for (int64_t j = 0; j < nw; ++j) {
+        const uint64_t cur = w[j], next = w[j + 1];  // (w[nw] is 0)
+        uint64_t add = 0;
+        for (uint64_t m = ~cur; m; m &= m - 1) {
+            const int i = __builtin_ctzll(m);
+            if (bond_close_bit(prev, cur, next, i, gap)) add |= (uint64_t)1 << i;
+        }
+        w[j] = cur | add, prev = cur;  // (no bit at or behind frame T is filled: nothing is set above it)
+    }
+}
+
+template <class E, int D, bool PERIODIC>
+int bond_lifetime_t(const State& s, bool fft, int64_t P, int n_at, const int32_t* atoms, const double* hm, bool per_frame,
+                    const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb) {
+    const size_t nw = (size_t)((s.T + 63) / 64);
+    std::vector<uint64_t> S;  // a thread's level-2 words
+    try {
+        S.assign((size_t)(s.threads > 0 ? s.threads : 1) * nw, 0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    return lifetime_sums(s, fft, P, ci, runs, nb, [&](int64_t n, uint64_t* w) {
+        uint64_t* Sw = S.data() + (size_t)omp_get_thread_num() * nw;
+        if (n_at == 3) bond_fill<E, D, PERIODIC, 3>(s, atoms + 3 * n, hm, per_frame, cuts, gap, w, Sw);
+        else bond_fill<E, D, PERIODIC, 2>(s, atoms + 2 * n, hm, per_frame, cuts, gap, w, Sw);
+    });
+}
+
 // fn(E(), D, PERIODIC) as template arguments for the staged element type, dim and box
 #define TA_PAIR_DISPATCH(fn, ...)                                                                                  \
     do {                                                                                                           \
@@ -1086,6 +1154,10 @@ int pair_find(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, cons
 int pair_lifetime(const State& s, bool fft, int64_t P, const int32_t* pairs, const double* hm, bool per_frame, double rc2, double* ci,
                   int64_t* runs, double* nb) {
     TA_PAIR_DISPATCH(pair_lifetime_t, s, fft, P, pairs, hm, per_frame, rc2, ci, runs, nb);
+}
+int bond_lifetime(const State& s, bool fft, int64_t P, int n_at, const int32_t* atoms, const double* hm, bool per_frame,
+                  const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb) {
+    TA_PAIR_DISPATCH(bond_lifetime_t, s, fft, P, n_at, atoms, hm, per_frame, cuts, gap, ci, runs, nb);
 }
 #undef TA_PAIR_DISPATCH
 

@@ -5,6 +5,7 @@
 
 namespace ta {
 struct BoxTable;  // unwrap_box.hpp
+struct BondCuts;  // bond_math.hpp
 namespace cpu {
 
 struct State {
@@ -94,6 +95,10 @@ int pair_find(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, cons
 // depends on the number of threads.
 int pair_lifetime(const State& s, bool fft, int64_t P, const int32_t* pairs, const double* hm, bool per_frame, double rc2, double* ci,
                   int64_t* runs, double* nb);
+// ta_bond_lifetime: the same three sums of the series g of the P bonds `atoms` (P, n_at), n_at = 2 or 3, with bond_math.hpp's
+// level, hysteresis and closing of absences of up to `gap` frames on the packed words, as k_bond_series and k_pair_filter
+int bond_lifetime(const State& s, bool fft, int64_t P, int n_at, const int32_t* atoms, const double* hm, bool per_frame,
+                  const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb);
 // ta_compound: out (n_frames, n_compounds, dim) float64 = sum_{i in [offsets[c], offsets[c + 1])} w_i x[t, members[i], d] -
 // g_c F[t, d] of slab 0 (g_c = sum_i w_i, F = sum_a u_a x[t, a, d]; frame_weights NULL: no such term; weights NULL: all 1),
 // the sum in member order (the first product, then fma), parallel over compounds; arguments checked by the caller

@@ -22,12 +22,17 @@
 //                               counted in a register per lane and added once per wave (which walks several pairs); longer
 //                               ones take one 64-bit integer atomic each.  Integer adds only: the same bits in any order.
 //   k_pair_reduce               the blocks' rows added in block order (the lag sums rescaled to integers on the way).
+// and of the bond lifetimes (bond_math.hpp: pairs or donor-hydrogen-acceptor triplets, a form and a break criterion):
+//   k_bond_series<E, D, BOX, NAT>  k_pair_series with NAT atoms per row and the frame's LEVEL 0 / 1 / 2 as its value.
+//   k_pair_filter               the level block -> the 0/1 block in place, on k_pair_runs' walk: hysteresis (a fill of the
+//                               level-2 bits through the runs of level >= 1, one carry bit across words) and the closing of
+//                               absences of up to 63 frames (a window of three resolved words).  No atomics, no LDS.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <type_traits>
 
-#include "pair_math.hpp"
+#include "bond_math.hpp"
 #include "pm_read.hpp"
 #include "ta_internal.hpp"
 
@@ -139,6 +144,31 @@ __global__ void __launch_bounds__(kPmThreads)
 
 enum { BOX_NONE = 0, BOX_CONST = 1, BOX_FRAME = 2 };
 
+// the boxes of the thread's frames: H[3] then M[3] of the staged columns per box (BOX_CONST: one, in slot 0; BOX_FRAME: one per
+// frame, loaded ONCE per thread before the loop over units)
+template <bool F32, int D, int BOX>
+__device__ __forceinline__ void pair_boxes(const double* __restrict__ hm, long T, long tb, double (&H)[kPmFrames][3],
+                                           double (&M)[kPmFrames][3]) {
+    constexpr int F = kPmFrames;
+#pragma unroll
+    for (int f = 0; f < F; ++f)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) H[f][d] = 1.0, M[f][d] = 1.0;
+    if constexpr (BOX == BOX_CONST) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) H[0][d] = hm[d], M[0][d] = hm[3 + d];
+    }
+    if constexpr (BOX == BOX_FRAME) {
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            const long t = pm_frame<F32>(tb, f);
+            const double* box = hm + (t < T ? t : 0) * 6;  // (a frame >= T stores zeros: any box will do)
+#pragma unroll
+            for (int d = 0; d < D; ++d) H[f][d] = box[d], M[f][d] = box[3 + d];
+        }
+    }
+}
+
 // the indicator of pair `row` (its atoms at a workgroup-uniform address: scalar loads) in the thread's frames
 template <class E, int D, int BOX>
 __device__ __forceinline__ void pair_indicator(const E* __restrict__ x, long pitch, long T, long tb, const int* __restrict__ row,
@@ -167,23 +197,7 @@ __global__ void __launch_bounds__(kPmThreads)
     constexpr int F = kPmFrames;
     const long tb = (long)blockIdx.x * (kPmThreads * F);
     double H[F][3], M[F][3];
-#pragma unroll
-    for (int f = 0; f < F; ++f)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) H[f][d] = 1.0, M[f][d] = 1.0;
-    if constexpr (BOX == BOX_CONST) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) H[0][d] = hm[d], M[0][d] = hm[3 + d];
-    }
-    if constexpr (BOX == BOX_FRAME) {
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            const long t = pm_frame<kF32>(tb, f);
-            const double* box = hm + (t < T ? t : 0) * 6;  // (a frame >= T stores zeros: any box will do)
-#pragma unroll
-            for (int d = 0; d < D; ++d) H[f][d] = box[d], M[f][d] = box[3 + d];
-        }
-    }
+    pair_boxes<kF32, D, BOX>(hm, T, tb, H, M);
     double2* Zp = reinterpret_cast<double2*>(Z);
     const int n_units = (P + 1) / 2;
     for (int g = blockIdx.y; g < n_units; g += gridDim.y) {
@@ -196,6 +210,95 @@ __global__ void __launch_bounds__(kPmThreads)
             if (t >= pitch) continue;
             const double v[2] = {h0[f], h1[f]};
             pm_store_row<1>(Zp + (long)g * pitch, pitch, t, t < T, 1, v);
+        }
+    }
+}
+
+// the level of bond `row` (NAT atoms at a workgroup-uniform address) in the thread's frames: 0.0, 1.0, or `two` for level 2
+template <class E, int D, int BOX, int NAT>
+__device__ __forceinline__ void bond_levels(const E* __restrict__ x, long pitch, long T, long tb, const int* __restrict__ row,
+                                            const double (&H)[kPmFrames][3], const double (&M)[kPmFrames][3], const BondCuts& k,
+                                            double two, double (&s)[kPmFrames]) {
+    constexpr int F = kPmFrames;
+    double at[NAT][F][3] = {};
+#pragma unroll
+    for (int i = 0; i < NAT; ++i) pm_load(PmAtom<E, D>(x, pitch, (unsigned)row[i]), T, tb, at[i]);  // (atom D < 2^31: the launcher)
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        constexpr bool kPeriodic = BOX != BOX_NONE;
+        const int fb = BOX == BOX_FRAME ? f : 0;
+        double xs[NAT][3];
+#pragma unroll
+        for (int i = 0; i < NAT; ++i)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) xs[i][d] = at[i][f][d];
+        const int level = bond_level<D, kPeriodic, NAT>(xs, H[fb], M[fb], k);
+        s[f] = level == 2 ? two : level == 1 ? 1.0 : 0.0;
+    }
+}
+
+// k_pair_series for bonds of NAT items and two levels (bond_math.hpp): the same grid, units, reads and stores; atoms
+// (P, NAT) int32; Z gets the LEVEL 0.0 / 1.0 / two per frame, two = 2.0 in front of k_pair_filter and 1.0 where no filter
+// follows (the break criterion is then the form criterion, level 1 does not occur and the level-2 frames are the series).
+// The second bond's atoms are loaded after the first bond's levels are formed: three float64 atoms of D = 3 are 72 registers.
+template <class E, int D, int BOX, int NAT>
+__global__ void __launch_bounds__(kPmThreads)
+    k_bond_series(const E* __restrict__ x, long pitch, long T, int P, const int* __restrict__ atoms, const double* __restrict__ hm,
+                  BondCuts k, double two, double* __restrict__ Z) {
+    constexpr bool kF32 = std::is_same_v<E, float>;
+    constexpr int F = kPmFrames;
+    const long tb = (long)blockIdx.x * (kPmThreads * F);
+    double H[F][3], M[F][3];
+    pair_boxes<kF32, D, BOX>(hm, T, tb, H, M);
+    double2* Zp = reinterpret_cast<double2*>(Z);
+    const int n_units = (P + 1) / 2;
+    for (int g = blockIdx.y; g < n_units; g += gridDim.y) {
+        double s0[F], s1[F] = {};
+        bond_levels<E, D, BOX, NAT>(x, pitch, T, tb, atoms + 2L * NAT * g, H, M, k, two, s0);
+        if (2 * g + 1 < P) bond_levels<E, D, BOX, NAT>(x, pitch, T, tb, atoms + 2L * NAT * g + NAT, H, M, k, two, s1);  // (uniform)
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            const long t = pm_frame<kF32>(tb, f);
+            if (t >= pitch) continue;
+            const double v[2] = {s0[f], s1[f]};
+            pm_store_row<1>(Zp + (long)g * pitch, pitch, t, t < T, 1, v);
+        }
+    }
+}
+
+// one series' filter state: the hysteresis carry and the h words before and at the word that is closed next
+struct FilterState {
+    bool carry = false;
+    unsigned long long prev = 0, cur = 0;
+};
+// the word behind `cur` has been resolved to `next`: lane's frame of `cur` after closing, the window moved on
+__device__ __forceinline__ bool filter_step(FilterState& f, unsigned long long next, int lane, int gap) {
+    const bool on = ((f.cur >> lane) & 1ull) || (gap && bond_close_bit(f.prev, f.cur, next, lane, gap));
+    f.prev = f.cur, f.cur = next;
+    return on;
+}
+
+// Z: the LEVEL block k_bond_series wrote with two = 2.0 (n_units destination pairs of `pitch` rows) becomes the 0/1 block of
+// g(t) in place: hysteresis, then closing of absences of up to `gap` frames.  A wave per destination pair at a time, as
+// k_pair_runs: lane l reads frame 64 j + l, the ballots of v == 2 and v >= 1 are the words S and W, bond_hyst_word resolves
+// word j with the wave-uniform carry, and word j - 1 is closed against words j - 2 and j and written back, one frame per
+// lane.  Every trip count depends on T alone.  Rows >= T and the phantom column stay as they are: zeros.
+__global__ void __launch_bounds__(kPmThreads)
+    k_pair_filter(double* __restrict__ Z, long pitch, long T, long n_units, int gap) {
+    const int lane = threadIdx.x & 63;
+    const long n_waves = (long)gridDim.x * (kPmThreads / 64), n_words = (T + 63) / 64;
+    for (long g = (long)blockIdx.x * (kPmThreads / 64) + (threadIdx.x >> 6); g < n_units; g += n_waves) {  // (a whole wave)
+        double2* z = reinterpret_cast<double2*>(Z) + g * pitch;
+        FilterState f0, f1;
+        for (long j = 0; j <= n_words; ++j) {  // (trip n_words: word n_words is the zeros behind the series)
+            const long t = j * 64 + lane;
+            double2 v = {0.0, 0.0};
+            if (t < T) v = z[t];
+            const unsigned long long h0 = bond_hyst_word(__ballot(v.x == 2.0), __ballot(v.x >= 1.0), f0.carry);
+            const unsigned long long h1 = bond_hyst_word(__ballot(v.y == 2.0), __ballot(v.y >= 1.0), f1.carry);
+            f0.carry = h0 >> 63, f1.carry = h1 >> 63;
+            const bool on0 = filter_step(f0, h0, lane, gap), on1 = filter_step(f1, h1, lane, gap);
+            if (j > 0 && t - 64 < T) z[t - 64] = double2{on0 ? 1.0 : 0.0, on1 ? 1.0 : 0.0};
         }
     }
 }
@@ -319,9 +422,41 @@ hipError_t launch_pair_series(int n_cu, const void* x, bool f32, long pitch, lon
     return hipGetLastError();
 }
 
+hipError_t launch_bond_series(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, long n_bonds, int n_at,
+                              const int* atoms, const double* hm, bool box_per_frame, const BondCuts& k, double two, double* Z,
+                              hipStream_t st) {
+    if (!pm_slab_ok(pitch, T, n_atoms, D) || n_bonds < 1 || n_bonds >= (1L << 30) || (n_at != 2 && n_at != 3) || !atoms ||
+        !(k.rc2 > 0.0) || !(k.rb2 >= k.rc2) || !(k.cb2 <= k.c2) || (two != 1.0 && two != 2.0) || !Z)
+        return hipErrorInvalidValue;
+    const dim3 grid = pm_unit_grid(n_cu, pitch, (n_bonds + 1) / 2);
+    const int box = !hm ? BOX_NONE : box_per_frame ? BOX_FRAME : BOX_CONST;
+    pm_dispatch(f32, D, [&](auto e, auto d) {
+        pm_switch<BOX_NONE, BOX_FRAME>(box, [&](auto b) {
+            pm_switch<2, 3>(n_at, [&](auto nat) {
+                using E = decltype(e);
+                hipLaunchKernelGGL((k_bond_series<E, d(), decltype(b)::value, decltype(nat)::value>), grid, dim3(kPmThreads), 0, st,
+                                   (const E*)x, pitch, T, (int)n_bonds, atoms, hm, k, two, Z);
+            });
+        });
+    });
+    return hipGetLastError();
+}
+
+// the grid of the two kernels that walk a block a wave per destination pair: eight workgroups per CU, at most one wave per pair
+static long pair_walk_grid(int n_cu, long n_units) {
+    return std::min<long>(8L * std::max(n_cu, 1), (n_units + kPmThreads / 64 - 1) / (kPmThreads / 64));
+}
+
+hipError_t launch_pair_filter(int n_cu, double* Z, long pitch, long T, long n_pairs, int gap, hipStream_t st) {
+    const long n_units = (n_pairs + 1) / 2;
+    if (n_pairs < 1 || T < 1 || T > pitch || gap < 0 || gap > 63 || !Z) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pair_filter, dim3((unsigned)pair_walk_grid(n_cu, n_units)), dim3(kPmThreads), 0, st, Z, pitch, T, n_units, gap);
+    return hipGetLastError();
+}
+
 hipError_t launch_pair_runs(int n_cu, const double* Z, long pitch, long T, long n_pairs, unsigned long long* runs, hipStream_t st) {
     // eight workgroups per CU (22 VGPRs: eight waves per SIMD), at most one wave per destination pair
-    const long n_units = (n_pairs + 1) / 2, n_wg = std::min<long>(8L * std::max(n_cu, 1), (n_units + kPmThreads / 64 - 1) / (kPmThreads / 64));
+    const long n_units = (n_pairs + 1) / 2, n_wg = pair_walk_grid(n_cu, n_units);
     if (n_pairs < 1 || T < 1 || T > pitch || !Z || !runs) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_pair_runs, dim3((unsigned)n_wg), dim3(kPmThreads), 0, st, Z, pitch, T, n_units, runs);
     return hipGetLastError();

@@ -434,8 +434,17 @@ hipError_t launch_vhd_pairs(const double* ga, const double* gb, const int* ida, 
 //   launch_pair_runs: runs[l] += the maximal runs of l consecutive bonded frames of such a block (T + 1 entries, uint64).
 //   launch_pair_reduce: out[i] = sum over n_rows rows of n values in row order: as they are (PAIR_SUM), times T - i
 //   (PAIR_LAGS: the lag sums carry 1 / (T - i)), or that rounded to the integer it stands for (PAIR_LAGS_INT).
+//   launch_bond_series: launch_pair_series for the bonds `atoms` (n_bonds, n_at) of n_at = 2 or 3 items with the cutoffs k
+//   (bond_math.hpp): Z gets the level 0.0 / 1.0 / `two` per frame, two = 2.0 where launch_pair_filter follows, else 1.0.
+//   launch_pair_filter: such a level block becomes the 0/1 block of the hysteresis-resolved series with absences of up to
+//   gap (0 ... 63) frames closed, in place.
 enum { PAIR_SUM = 0, PAIR_LAGS = 1, PAIR_LAGS_INT = 2 };
+struct BondCuts;
 long pair_list_blocks(long n_words);
+hipError_t launch_bond_series(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, long n_bonds, int n_at,
+                              const int* atoms, const double* hm, bool box_per_frame, const BondCuts& k, double two, double* Z,
+                              hipStream_t st);
+hipError_t launch_pair_filter(int n_cu, double* Z, long pitch, long T, long n_pairs, int gap, hipStream_t st);
 hipError_t launch_pair_find(const double* ga, const double* gb, const int* ida, const int* idb, long pitch_a, long pitch_b, long n_a,
                             long n_b, int D, long T, long stride, long o_base, int n_o, const double* hm, bool box_per_frame,
                             double rc2, bool same, unsigned long long* bitmap, hipStream_t st);

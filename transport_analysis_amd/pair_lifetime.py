@@ -50,6 +50,12 @@ class PairLifetime(CollectiveAnalysis):
     fft : keyword-only, default True — the lag sums by the FFT path (within 1e-10 of their largest value); False: the direct
         paths, exact integers.
     dim_type : {'xyz', 'xy', 'yz', 'xz', 'x', 'y', 'z'} — the analysed dimensions.
+    r_break : keyword-only, default None — a second, larger cutoff (hysteresis, the stable-states picture): a bond forms below
+        ``r_cut`` and lasts while the distance stays below ``r_break``.  None: one cutoff.
+    intermittency : keyword-only, default 0 — absences of at most this many frames (0 ... 63) between two bonded frames count
+        as bonded (MDAnalysis' ``intermittency``, the tolerated absence of residence times), in every result.  With either
+        keyword set the series are filtered on the device (``ta_bond_lifetime``: ``k_bond_series``, ``k_pair_filter``); with
+        the defaults nothing changes.
     device, stage_dtype : keyword-only — as for the other classes.  float32 staging stays float32 on the device.
 
     Pairs cross any split of the atoms: ``devices=[...]`` with more than one member and ``distributed=True`` raise
@@ -73,37 +79,56 @@ class PairLifetime(CollectiveAnalysis):
     _updating_message = "UpdatingAtomGroups are not valid for pair lifetime computation"
     _by_particle_message = ("PairLifetime has no per-particle result: the correlations are sums over all pairs "
                             "(by_particle=True is not supported)")
+    _n_at = 2  # items per row of the list, results.<_result_keys[0]>
     _result_keys = ("pairs", "times", "n_bonded", "coordination", "run_lengths", "intermittent", "continuous",
                     "tau_intermittent", "tau_continuous", "mean_run")
 
-    def __init__(self, atomgroup, atomgroup_b=None, *, r_cut, pairs=None, search_stride=1, periodic=True, fft=True,
-                 dim_type="xyz", **kwargs):
+    @staticmethod
+    def _check_filters(r_cut, r_break, intermittency, name="r_break", cut_name="r_cut"):
+        """(r_break or None, intermittency) of the two filter keywords, checked"""
+        if r_break is not None:
+            r_break = float(r_break)
+            if not np.isfinite(r_break) or r_break < r_cut:
+                raise ValueError(f"{name} must be finite and at least {cut_name}, got {r_break}")
+        gap = int(intermittency)
+        if gap != intermittency or not 0 <= gap <= 63:
+            raise ValueError(f"intermittency must be an integer 0 ... 63 (frames of tolerated absence), got {intermittency}")
+        return r_break, gap
+
+    def _refuse(self, kwargs, *groups):
+        """the keywords and groups this class and HydrogenBondLifetime cannot take; `kwargs` is left as the base class takes it"""
+        name = type(self).__name__
         for key, why in (("compound", "pairs of atoms are followed, not of molecules' centres: run it on a group of one atom "
                                       "per molecule"),
                          ("compound_weights", "there are no compounds"),
                          ("reference_frame", "a pair distance does not depend on the frame of reference"),
                          ("unwrap", "the minimum image makes unwrapping unnecessary")):
             if kwargs.get(key) is not None and kwargs.get(key) is not False:
-                raise TypeError(f"PairLifetime does not take {key}=: {why}")
+                raise TypeError(f"{name} does not take {key}=: {why}")
             kwargs.pop(key, None)
         devices = kwargs.get("devices")
         if devices is not None and len(list(devices)) > 1:
-            raise ValueError("PairLifetime: devices=[...] with more than one member is not supported -- the atoms would be "
+            raise ValueError(f"{name}: devices=[...] with more than one member is not supported -- the atoms would be "
                              "split over the GPUs by index, and the pairs cross the shards")
         if kwargs.get("distributed", False):
-            raise ValueError("PairLifetime: distributed=True is not supported -- every rank holds a block of the atoms, and "
+            raise ValueError(f"{name}: distributed=True is not supported -- every rank holds a block of the atoms, and "
                              "the pairs cross the blocks")
         if devices is not None:  # one member: a plain context on that device
             kwargs.pop("devices")
             kwargs.setdefault("device", list(devices)[0])
-        if isinstance(atomgroup, UpdatingAtomGroup) or isinstance(atomgroup_b, UpdatingAtomGroup):
+        if any(isinstance(g, UpdatingAtomGroup) for g in groups):
             raise TypeError(self._updating_message)
+
+    def __init__(self, atomgroup, atomgroup_b=None, *, r_cut, pairs=None, search_stride=1, periodic=True, fft=True,
+                 dim_type="xyz", r_break=None, intermittency=0, **kwargs):
+        self._refuse(kwargs, atomgroup, atomgroup_b)
         self.r_cut = float(r_cut)
         if not np.isfinite(self.r_cut) or not self.r_cut > 0:
             raise ValueError(f"r_cut must be finite and > 0, got {r_cut}")
         self.search_stride = int(search_stride)
         if self.search_stride < 1:
             raise ValueError(f"search_stride must be >= 1, got {search_stride}")
+        self.r_break, self.intermittency = self._check_filters(self.r_cut, r_break, intermittency)
         same = atomgroup_b is None
         ix_a = _sorted_ix(atomgroup, "atomgroup")
         ix_b = ix_a if same else _sorted_ix(atomgroup_b, "atomgroup_b")
@@ -172,9 +197,10 @@ class PairLifetime(CollectiveAnalysis):
                                          idx_b=None if self._same else self._idx_b, **box)
             if staged.shape[0] == 0:
                 return self._no_moments() + (staged,), None
-            ci, runs, nb = self._ctx.pair_lifetime(fft, self.r_cut, None, **box)  # (the list the search left in the context)
-        else:
-            ci, runs, nb = self._ctx.pair_lifetime(fft, self.r_cut, staged, **box)
+        if self.r_break is not None or self.intermittency:  # the filtered series: ta_bond_lifetime on rows of two items
+            ci, runs, nb = self._ctx.bond_lifetime(fft, staged, self.r_cut, r_break=self.r_break, gap=self.intermittency, **box)
+        else:  # (a searched list is the one the search left in the context)
+            ci, runs, nb = self._ctx.pair_lifetime(fft, self.r_cut, None if self._pairs is None else staged, **box)
         return (ci, runs, nb, staged), None
 
     def _no_moments(self):
@@ -187,7 +213,7 @@ class PairLifetime(CollectiveAnalysis):
     def _store(self, sums, _):
         ci, runs, nb, staged = sums
         r, T = self.results, self.n_frames
-        r.pairs = self._union[np.asarray(staged, dtype=np.int64)].reshape(-1, 2)
+        setattr(r, self._result_keys[0], self._union[np.asarray(staged, dtype=np.int64)].reshape(-1, self._n_at))
         r.times = self.lag_times()
         r.n_bonded = np.rint(nb).astype(np.int64)
         r.coordination = float(np.mean(r.n_bonded / float(self.n_a)))
@@ -200,7 +226,7 @@ class PairLifetime(CollectiveAnalysis):
         tau = ell[:T]
         cc = s1[1:] - tau * s0[1:]
         if not r.n_bonded.any():
-            warnings.warn("PairLifetime: no pair is bonded in any frame; the correlation functions are nan", UserWarning,
+            warnings.warn(f"{type(self).__name__}: no pair is bonded in any frame; the correlation functions are nan", UserWarning,
                           stacklevel=4)
         with np.errstate(divide="ignore", invalid="ignore"):
             r.intermittent = np.asarray(ci, dtype=np.float64) / n0
