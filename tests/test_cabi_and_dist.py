@@ -49,7 +49,10 @@ def test_plan_info():
     for T, M in ((10241, 12288), (12289, 14336), (14337, 16384), (16385, 18432), (18433, 20480),
                  (20481, 21504), (24577, 27648), (27649, 30720), (30000, 30720), (30721, 32768),
                  (40961, 46080), (50000, 51200), (51201, 57344), (81921, 98304), (100000, 114688),
-                 (163840, 163840)):
+                 (163840, 163840),
+                 # the first frame count of each of the 23 outer-radix plans (tests/test_fft_plans.py: PLANS)
+                 (21505, 24576), (32769, 36864), (36865, 40960), (46081, 51200), (57345, 65536), (65537, 73728),
+                 (73729, 81920), (98305, 114688), (114689, 131072), (131073, 147456), (147457, 163840)):
         info = _lib.fft_plan_info(T)
         assert info["M"] == M
     assert _lib.fft_plan_info(163841) is None  # handled by the direct correlator

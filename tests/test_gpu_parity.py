@@ -639,10 +639,11 @@ def test_vacf_long_trajectory(ctx, fft):
                                    (20481, 3, 1), (33000, 2, 3), (50000, 1, 3), (70000, 1, 2),
                                    (90000, 1, 1), (140000, 1, 2), (163840, 1, 1)])
 def test_vacf_fft_long_trajectory(ctx, T, A, D):
-    """fft=True with n_frames beyond the largest on-chip transform: outer radix 2/4/8/16 while the
+    """fft=True with n_frames beyond the largest on-chip transform: outer radix 2/3/4/5/8/16 while the
     rows are read + on-chip transforms per pass (csrc/wfft.hpp), lag sums and the by-particle
-    array; covers every outer radix, an odd column count (unpaired last column), single-column
-    units in either half of a pair, rows past the end."""
+    array; 11 of the 23 outer-radix plans (R = 3 in front of R0 = 14 and 20 only, R = 5 in front of
+    R0 = 20 only: tests/test_fft_plans.py runs every plan), an odd column count (unpaired last
+    column), single-column units in either half of a pair, rows past the end."""
     from oracle import numpy_oracle as orc
 
     v = orc.synthetic_velocities(T, A, D, seed=T % 1000 + A)
