@@ -354,3 +354,132 @@ def s1_float(a):
     p = np.concatenate([np.zeros((1,) + a2.shape[1:]), np.cumsum(a2, axis=0)])
     k = np.arange(T)
     return p[T - k] + (p[T] - p[k])
+
+
+# ----------------------------------------------------------------------- k-space: quarter-turn phases (scattering, currents)
+# Integer positions and wavevectors k = 2 pi q with every component of q a multiple of 1/4: u = q . x is an exact multiple
+# of 1/4 in float64, r = u - rint(u) one of 0, +-1/4, +-1/2, and exp(2 pi i r) one of 1, i, -1, -i.  Every density,
+# current and lag-sum numerator behind such phases is an integer.
+TWO_PI = 6.283185307179586476925  # the literal of phase_math.hpp (it rounds to float64's 2 pi)
+QUARTER_COS = np.array([1, 0, -1, 0], dtype=np.int64)
+QUARTER_SIN = np.array([0, 1, 0, -1], dtype=np.int64)
+
+
+def quarter_wavevectors(q):
+    """k = q 2 pi (rad per length unit) of turns q whose components are multiples of 1/4; asserts that the library's
+    k / 2 pi gives q back in float64 (it does for the multiples of 1/4 in [-2.5, 2.5] and +-3, +-3.5, +-4; not for
+    +-2.75, +-3.25, +-3.75)."""
+    q = np.asarray(q, dtype=np.float64)
+    _as_int(4 * q)
+    k = q * TWO_PI
+    back = k / TWO_PI
+    if not np.array_equal(back, q):
+        bad = q[back != q]
+        raise AssertionError(f"k / 2 pi does not give q back for q = {sorted(set(bad.ravel().tolist()))}")
+    return k
+
+
+def quarter_phases(x, q):
+    """(K, T, A) int64 in 0 ... 3: the phase of exp(i k_j . x[t, n]) in quarter turns, for integer positions x (T, A, D)
+    and turns q (K, D) that are multiples of 1/4."""
+    return np.einsum("kd,tnd->ktn", _as_int(4 * np.asarray(q, dtype=np.float64)), _as_int(x)) % 4
+
+
+def quarter_cs(x, q):
+    """((K, T, A), (K, T, A)) int64: cos and sin of the quarter-turn phases, each one of 1, 0, -1."""
+    p = quarter_phases(x, q)
+    return QUARTER_COS[p], QUARTER_SIN[p]
+
+
+def pair_acf_num(a):
+    """(T, P) numerators sum_i a[i, p] . a[i + k, p] of an integer-valued (T, P, C) series: the autocorrelation of every
+    pseudo-atom p over its C columns (vacf_num under another name, for series that are no velocities)."""
+    return vacf_num(np.asarray(a, dtype=np.float64))
+
+
+def scatter_exact(x, q):
+    """The exact integers behind ta_scatter at quarter-turn phases: (density (K, T, 2) int64 = sum_n (cos, sin),
+    self numerators by atom (K, T, A) = sum_t cos(phi[t + k, n] - phi[t, n]), coll numerators (K, T) = the autocorrelation
+    of the density)."""
+    c, s = quarter_cs(x, q)
+    rho = np.stack([c.sum(axis=2), s.sum(axis=2)], axis=2)
+    self_num = np.stack([pair_acf_num(np.stack([cj, sj], axis=2)) for cj, sj in zip(c, s)])
+    return rho, self_num, pair_acf_num(rho.transpose(1, 0, 2)).T
+
+
+def current_exact(x, v, w, q):
+    """(K, T, D, 2) int64: current[j, t, d] = sum_n w_n v[t, n, d] (cos, sin)(k_j . x[t, n]) at quarter-turn phases, for
+    integer velocities and integer weights (None: ones)."""
+    c, s = quarter_cs(x, q)
+    wv = _as_int(v) * (1 if w is None else _as_int(w)[None, :, None])
+    return np.stack([np.einsum("ktn,tnd->ktd", c, wv), np.einsum("ktn,tnd->ktd", s, wv)], axis=3)
+
+
+def axis_current_num(cur, axis):
+    """(long numerators (T,), transverse numerators by component (T, D)) of one wavevector's integer current (T, D, 2) when
+    the wavevector has ONE non-zero component `axis`: k^ = +-e_axis exactly, jL = +-current[axis], jT[d] = current[d] for
+    d != axis and exactly 0 for d = axis.  trans = sum_d of the second / ((D - 1) (T - k))."""
+    num = pair_acf_num(cur)  # (T, D)
+    tr = num.copy()
+    tr[:, axis] = 0
+    return num[:, axis], tr
+
+
+# ------------------------------------------------------------------------------- axis-aligned molecules (orientation)
+def axis_molecules(T, N, mode, seed, hop=0.15, degenerate=0.04, box=None):
+    """Molecules (a, b, c) of integer positions whose orientation vector is exactly +-e_x, +-e_y or +-e_z times an integer
+    length, hopping between the six directions with probability `hop` per frame, and degenerate (no direction) in a
+    fraction `degenerate` of the (frame, molecule) pairs.  mode "bond": b - a = L e; "normal": b - a = L1 e_i, c - a =
+    L2 e_j, v = L1 L2 e_i x e_j; "bisector": b - a = p e + q e', c - a = p e - q e' (e' another axis), v = 2 p e.
+    box: None, or (T,) integer box lengths (cubic; every arm is shorter than a quarter of the smallest): the atoms are
+    wrapped into [0, box) one by one, so that the image step has work to do.
+    -> (x (T, 3 N, 3) float64 integers, index (N, 2 or 3) int32 in a permuted order, u (T, N, 3) int64 in {-1, 0, 1})."""
+    rng = np.random.default_rng(seed)
+    direction = np.empty((T, N), dtype=np.int64)  # 0 ... 5: +x, -x, +y, -y, +z, -z
+    direction[0] = rng.integers(0, 6, size=N)
+    hops = rng.random((T, N)) < hop
+    fresh = rng.integers(0, 6, size=(T, N))
+    for t in range(1, T):
+        direction[t] = np.where(hops[t], fresh[t], direction[t - 1])
+    axis, sign = direction // 2, 1 - 2 * (direction % 2)
+    live = rng.random((T, N)) >= degenerate
+    e = np.zeros((T, N, 3), dtype=np.int64)
+    np.put_along_axis(e, axis[:, :, None], sign[:, :, None], axis=2)
+    a = np.rint(np.cumsum(rng.integers(-1, 2, size=(T, N, 3)), axis=0) + rng.integers(0, 9, size=(1, N, 3))).astype(np.int64)
+    L1 = rng.integers(1, 4, size=(T, N, 1))
+    L2 = rng.integers(1, 4, size=(T, N, 1))
+    if mode == "bond":
+        db, dc = L1 * e * live[:, :, None], np.zeros_like(e)
+    elif mode == "bisector":
+        other = np.zeros_like(e)  # a unit vector along the next axis
+        np.put_along_axis(other, ((axis + 1) % 3)[:, :, None], 1, axis=2)
+        p = L1 * live[:, :, None]  # degenerate: p = 0, the arms opposite
+        db, dc = p * e + L2 * other, p * e - L2 * other
+    else:
+        assert mode == "normal"
+        e_i = np.zeros_like(e)
+        e_j = np.zeros_like(e)
+        np.put_along_axis(e_i, ((axis + 1) % 3)[:, :, None], 1, axis=2)
+        np.put_along_axis(e_j, ((axis + 2) % 3)[:, :, None], 1, axis=2)
+        db = L1 * e_i
+        dc = np.where(live[:, :, None], L2 * sign[:, :, None] * e_j, 2 * db)  # degenerate: parallel arms
+    x = np.stack([a, a + db, a + dc], axis=2).reshape(T, 3 * N, 3)
+    if box is not None:
+        x = x % np.asarray(box, dtype=np.int64).reshape(T, 1, 1)
+    order = rng.permutation(N)
+    rows = np.stack([3 * order, 3 * order + 1] + ([] if mode == "bond" else [3 * order + 2]), axis=1)
+    u = (e * live[:, :, None])[:, order]
+    return x.astype(np.float64), np.ascontiguousarray(rows, dtype=np.int32), u
+
+
+def orient_exact(u, w=None):
+    """The exact integers behind ta_orient for unit vectors u (T, N, 3) in {-1, 0, 1} (one non-zero component, or none):
+    (c1 numerators by vector (T, N) = sum_t u . u', n_same (T,), n_diff (T,): the pairs (t, t + k) of one vector, both
+    with a direction, along the same axis / along different axes -- c2[k] = (2/3 n_same - 1/3 n_diff) / (T - k) --,
+    total (T, 3) int64 = sum_n w_n u_n with integer weights, coll numerators (T,))."""
+    u = _as_int(u)
+    same = pair_acf_num(np.abs(u)).sum(axis=1)
+    live = np.abs(u).sum(axis=2, keepdims=True)
+    both = pair_acf_num(live).sum(axis=1)
+    total = np.einsum("n,tnd->td", np.ones(u.shape[1], dtype=np.int64) if w is None else _as_int(w), u)
+    return pair_acf_num(u), same, both - same, total, pair_acf_num(total[:, None, :])[:, 0]
