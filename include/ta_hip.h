@@ -518,7 +518,8 @@ int ta_vanhove_distinct(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int64_t 
  *              every analysed box length in every frame.  Of the box only the analysed axes' lengths are looked at.
  *              Passes.  ta_pair_find: k_vhd_gather at lag 0 writes the searched frames as frame-major float64 scratch (the
  *              slab read in the element type it has), k_pair_find takes one (256 a-items, 1024 b-items, searched frame) per
- *              workgroup on k_vhd_pairs' tiles; a wave's ballot of "bonded and a different item" over its 64 consecutive
+ *              workgroup on k_vhd_pairs' tile walk (one walk for both kernels, each with its own visitor); a wave's
+ *              ballot of "bonded and a different item" over its 64 consecutive
  *              b-items is a word of the device bitmap [pitch_a][pitch_b / 64] and is ORed in by one lane when non-zero.
  *              The searched frames go in chunks whose scratch fits 4 GiB (option "pair_find_chunk" n >= 1 forces
  *              min(n, frames)); OR is idempotent: the same list for every chunk, from run to run.  k_pair_count takes
@@ -575,7 +576,8 @@ int ta_pair_lifetime(ta_ctx *ctx, int fft, int64_t n_pairs, const int32_t *h_pai
  *              intermittency, the tolerated absence t* of residence times); absences at the start and the end of the
  *              series are never filled.  gap is 0 ... 63: the series are filtered as 64-frame words, and an absence of up to
  *              63 frames is decided by a window of three words (the one before, the frame's own, the one behind).
- *              Passes: ta_pair_lifetime's, on its blocks ("pair_chunk"), with k_bond_series in k_pair_series' place: it
+ *              Passes: ta_pair_lifetime's, on its blocks ("pair_chunk"), with k_bond_series in k_pair_series' place (one
+ *              kernel body under both, a row function each: the pair row keeps its single compare): it
  *              writes the level 0.0 / 1.0 / 2.0, and k_pair_filter turns the block into g in place (a wave per destination
  *              pair; the ballots of v == 2 and v >= 1 are the words; hysteresis is a fill of six shift / and / or steps with
  *              one carry bit across words; no atomics, no loop whose trip count depends on the data).  With gap = 0 and the

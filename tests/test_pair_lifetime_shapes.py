@@ -10,6 +10,8 @@ slab's bits (padding included) unchanged, and the host-facing entry bit-equal to
   series  explicit pairs, P = 1, 2, 3, 129 (odd counts reach the phantom column), T = 1, 2, 3, 7, 63, 64, 65, 1023, 1024, 1025,
   runs    2049, constructed bit patterns: always bonded (one run of T), never bonded, alternating, a single run covering
           exactly frames [63, 65], [1023, 1025] and [0, T - 1] (clipped to the frames there are); "pair_chunk" 1, 2, automatic.
+  walk    the two visitors of the shared tile walk (pair_tile.hpp) against each other on exact inputs: the pairs k_pair_find
+          finds below r_cut = n_bins dr are the pairs k_vhd_pairs bins below its last edge.
   A small call straight after a large one on one context without ta_trim; float64 positions off any grid in a non-dyadic box:
   everything equal to the CPU backend's; n_atoms dim >= 2^31 is refused before anything is allocated."""
 import functools
@@ -18,7 +20,7 @@ import numpy as np
 import pytest
 
 import pair_ref as ref
-from test_vanhove_distinct_shapes import SLABS, TA, TB, TILE_CASES, slab_bits, stage, staged_bits
+from test_vanhove_distinct_shapes import SLABS, TA, TB, TILE_CASES, run_staged, slab_bits, stage, staged_bits
 from transport_analysis_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -157,6 +159,52 @@ def test_find_chunks_give_the_same_list(dtype):
             assert c.kernel_launches("k_vhd_gather") == launches == c.kernel_launches("k_pair_find")
     finally:
         c.close()
+
+
+# ---- the shared tile walk: both visitors on the same exact inputs -----------------------------------------------------------
+WALK_BINS, WALK_DR, WALK_BOX = 12, 0.25, 16.0  # r_cut = 12 * 0.25 = 3: fl(r_cut^2) = 9 is the last squared edge (12 * 0.25)^2
+
+
+@functools.lru_cache(maxsize=None)
+def walk_case(D, lists, boxed):
+    """2 frames of integer positions in [0, 16]: exact in float32, every r2 an exact integer with or without the box of 16.
+    lists "same": one list of TB + 1 items; "disjoint": TA + 1 a-items and TB + 1 b-items, one past each tile edge.  Returns
+    x, a, b (None: all items), dimensions and the (n, 2) pairs of frame 0 below r_cut by a NumPy all-pairs compare."""
+    Na, Nb = (TB + 1, TB + 1) if lists == "same" else (TA + 1, TB + 1)
+    A = Nb if lists == "same" else Na + Nb
+    x = np.random.default_rng(100 * D + A).integers(0, 17, size=(2, A, D)).astype(np.float64)
+    a, b = (None, None) if lists == "same" else (np.arange(Na), np.arange(Na, A))
+    ia, ib = (np.arange(A), np.arange(A)) if lists == "same" else (a, b)
+    d = x[0, ib][None, :, :] - x[0, ia][:, None, :]
+    if boxed:
+        d -= np.rint(d / WALK_BOX) * WALK_BOX
+    near = (d * d).sum(axis=2) < (WALK_BINS * WALK_DR) ** 2
+    if lists == "same":
+        near = np.triu(near, k=1)
+    p, q = np.nonzero(near)  # (row-major: sorted by (a, b))
+    return x, a, b, ref.dimensions((WALK_BOX,) * 3, 2) if boxed else None, np.stack([ia[p], ib[q]], axis=1).astype(np.int32)
+
+
+@pytest.mark.parametrize("dtype", SLABS)
+@pytest.mark.parametrize("lists", ["same", "disjoint"])
+@pytest.mark.parametrize("D", [1, 2, 3])
+def test_walk_visitors_agree(D, lists, dtype):
+    """one searched frame (both strides = T) at lag 0: the pair count of ta_pair_find (twice it for one list: the histogram
+    counts ordered pairs) equals the sum of ta_vanhove_distinct's non-overflow bins, and the found list is NumPy's"""
+    for boxed in (False, True):
+        x, a, b, dims, want = walk_case(D, lists, boxed)
+        T = x.shape[0]
+        c = stage(_lib.Context(0), x, dtype)
+        try:
+            got = run_find(c, dtype, x, WALK_BINS * WALK_DR, want, repeat=1, search_stride=T, idx_a=a, idx_b=b, dimensions=dims)
+            cnt = run_staged(c, [0], WALK_BINS, WALK_DR, repeat=1, origin_stride=T, idx_a=a, idx_b=b, dimensions=dims)
+            assert "k_vhd_pairs" in timeline(c)
+            n_in = int(cnt[0, :WALK_BINS].sum())
+            print(f"    D={D} {lists} boxed={boxed}: {got.shape[0]} pairs found, {n_in} binned below the last edge")
+            assert got.shape[0] > 100 and n_in == (2 if lists == "same" else 1) * got.shape[0]
+            assert int(cnt[0].sum()) == (x.shape[1] * (x.shape[1] - 1) if lists == "same" else a.size * b.size)
+        finally:
+            c.close()
 
 
 # ---- series and runs ------------------------------------------------------------------------------------------------------

@@ -214,6 +214,16 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None else ctypes.c_void_p(None)
 
 
+def _index_list(idx, name):
+    """(int64 array, length) of a list of item indices of the pair calls, or (None, 0)"""
+    if idx is None:
+        return None, 0
+    a = np.ascontiguousarray(idx, dtype=np.int64)
+    if a.ndim != 1:
+        raise ValueError(f"{name}: shape {a.shape}, expected a 1-d list of item indices")
+    return a, int(a.shape[0])
+
+
 def frame_source(arr):
     """(pointer, dtype code, ld_row) of a frame's (n_atoms, n_coord) array if ta_stage_frame can read it in
     place -- float32 / float64, unit stride along the coordinates, a non-negative whole-element row stride --
@@ -846,22 +856,8 @@ class Context(_Staged):
     def _vhd_args(self, lags, origin_stride, idx_a, idx_b, dimensions, axes, n_bins, dr):
         """the argument tuple ta_vanhove_distinct* share, and the arrays it points into (to be kept until the call is over)"""
         lg, L = self._lags(lags)
-
-        def index_list(idx, name):
-            if idx is None:
-                return None, 0
-            a = np.ascontiguousarray(idx, dtype=np.int64)
-            if a.ndim != 1:
-                raise ValueError(f"{name}: shape {a.shape}, expected a 1-d list of item indices")
-            return a, int(a.shape[0])
-
-        (a, na), (b, nb) = index_list(idx_a, "idx_a"), index_list(idx_b, "idx_b")
-        dims = ax = None
-        if dimensions is not None:
-            dims = np.ascontiguousarray(dimensions, dtype=np.float64)
-            if self.shape is not None and dims.shape != (self.shape[0], 6):
-                raise ValueError(f"dimensions: shape {dims.shape}, expected ({self.shape[0]}, 6) (one box per staged frame)")
-            ax = np.ascontiguousarray(np.arange(self._staged_shape()[2]) if axes is None else axes, dtype=np.int32).ravel()
+        (a, na), (b, nb) = _index_list(idx_a, "idx_a"), _index_list(idx_b, "idx_b")
+        dims, ax = self._pair_box(dimensions, axes)
         keep = (lg, a, b, dims, ax)
         return (L, _ptr(lg), int(origin_stride), na, _ptr(a), nb, _ptr(b), _ptr(dims), _ptr(ax), int(n_bins), float(dr)), keep
 
@@ -902,16 +898,7 @@ class Context(_Staged):
         items / the same as a, then only a < b) closer than `r_cut` in at least one of the frames 0, search_stride, ...
         `dimensions`, `axes`: as for vanhove_distinct.  The list stays in the context (pair_lifetime(pairs=None) uses it)
         until trim() or a new staging.  One context only: a device group has no such call."""
-
-        def index_list(idx, name):
-            if idx is None:
-                return None, 0
-            a = np.ascontiguousarray(idx, dtype=np.int64)
-            if a.ndim != 1:
-                raise ValueError(f"{name}: shape {a.shape}, expected a 1-d list of item indices")
-            return a, int(a.shape[0])
-
-        (a, na), (b, nb) = index_list(idx_a, "idx_a"), index_list(idx_b, "idx_b")
+        (a, na), (b, nb) = _index_list(idx_a, "idx_a"), _index_list(idx_b, "idx_b")
         dims, ax = self._pair_box(dimensions, axes)
         n = ctypes.c_int64(0)
         self._call("pair_find", na, _ptr(a), nb, _ptr(b), _ptr(dims), _ptr(ax), float(r_cut), int(search_stride), ctypes.byref(n))
@@ -939,20 +926,27 @@ class Context(_Staged):
         n_frames - tau; runs (n_frames + 1,) int64 = the histogram of the lengths of the runs of bonded frames; nb
         (n_frames,) = the bonded pairs per frame), None for one not asked for.  One context only: a device group has no
         such call."""
-        T = self._staged_shape()[0]
-        args, keep = self._pair_args(fft, pairs, r_cut, dimensions, axes)
-        o_ci = np.empty(T, dtype=np.float64) if ci else None
-        o_runs = np.empty(T + 1, dtype=np.int64) if runs else None
-        o_nb = np.empty(T, dtype=np.float64) if nb else None
-        self._call("pair_lifetime", *args, _ptr(o_ci), _ptr(o_runs), _ptr(o_nb))
-        del keep
-        return o_ci, o_runs, o_nb
+        return self._life("pair_lifetime", self._pair_args, (fft, pairs, r_cut, dimensions, axes), ci, runs, nb)
 
     def pair_lifetime_staged(self, fft, r_cut, pairs=None, *, dimensions=None, axes=None, d_ci=0, d_runs=0, d_nb=0, stream=0):
         """`pairs`, `dimensions`: HOST arrays (checked by the library before anything is written); d_ci (n_frames,), d_runs
         (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
-        args, keep = self._pair_args(fft, pairs, r_cut, dimensions, axes)
-        self._call("pair_lifetime_staged", *args, d_ci or None, d_runs or None, d_nb or None, stream or None)
+        self._life_staged("pair_lifetime_staged", self._pair_args(fft, pairs, r_cut, dimensions, axes), d_ci, d_runs, d_nb, stream)
+
+    def _life(self, name, make_args, given, ci, runs, nb):
+        """what pair_lifetime and bond_lifetime share: the outputs asked for allocated, the call, (ci, runs, nb)"""
+        T = self._staged_shape()[0]
+        args, keep = make_args(*given)
+        o_ci = np.empty(T, dtype=np.float64) if ci else None
+        o_runs = np.empty(T + 1, dtype=np.int64) if runs else None
+        o_nb = np.empty(T, dtype=np.float64) if nb else None
+        self._call(name, *args, _ptr(o_ci), _ptr(o_runs), _ptr(o_nb))
+        del keep
+        return o_ci, o_runs, o_nb
+
+    def _life_staged(self, name, args_keep, d_ci, d_runs, d_nb, stream):
+        args, keep = args_keep
+        self._call(name, *args, d_ci or None, d_runs or None, d_nb or None, stream or None)
         del keep
 
     def _bond_args(self, fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes):
@@ -975,22 +969,14 @@ class Context(_Staged):
         hydrogen, acceptor) of staged item ids; a bond forms below `r_cut` with (triplets) the cosine of the D-H-A angle at most
         `cos_cut`, lasts while below `r_break` / `cos_break` (None: the form values), and absences of up to `gap` frames (0 ...
         63) between bonded frames are filled.  One context only: a device group has no such call."""
-        T = self._staged_shape()[0]
-        args, keep = self._bond_args(fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes)
-        o_ci = np.empty(T, dtype=np.float64) if ci else None
-        o_runs = np.empty(T + 1, dtype=np.int64) if runs else None
-        o_nb = np.empty(T, dtype=np.float64) if nb else None
-        self._call("bond_lifetime", *args, _ptr(o_ci), _ptr(o_runs), _ptr(o_nb))
-        del keep
-        return o_ci, o_runs, o_nb
+        return self._life("bond_lifetime", self._bond_args, (fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes), ci, runs, nb)
 
     def bond_lifetime_staged(self, fft, atoms, r_cut, *, r_break=None, cos_cut=0.0, cos_break=None, gap=0, dimensions=None, axes=None,
                              d_ci=0, d_runs=0, d_nb=0, stream=0):
         """`atoms`, `dimensions`: HOST arrays (checked by the library before anything is written); d_ci (n_frames,), d_runs
         (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
-        args, keep = self._bond_args(fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes)
-        self._call("bond_lifetime_staged", *args, d_ci or None, d_runs or None, d_nb or None, stream or None)
-        del keep
+        self._life_staged("bond_lifetime_staged", self._bond_args(fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes),
+                          d_ci, d_runs, d_nb, stream)
 
     def _orient_args(self, fft, index, mode, dimensions, weights):
         """the argument tuple ta_orient* share, and the arrays it points into (to be kept until the call is over)"""

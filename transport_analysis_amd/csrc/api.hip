@@ -1614,18 +1614,55 @@ int vhd_args(ta_ctx* ctx, const VhdArgs& a, int64_t T, const void* out) {
     return check_vanhove_lags(fail, ctx, "vanhove_distinct: ", a.L, a.h_lags, T);
 }
 
-// The host side of one call (both kinds of context): the index lists padded to the pair kernel's tiles (-1: padding), the
-// box entries H[3], M[3] of the staged columns per box, the origins of lag 0
-struct VhdPlan {
-    int L = 0, B = 0, D = 0;
-    int64_t T = 0, stride = 1, n_a = 0, n_b = 0, n_orig = 0, pitch_a = 0, pitch_b = 0, n_box = 0;  // n_box 0: no box
+// ---- what the pair family's calls share on the host (both kinds of context): the box, the item lists, the table's tail ----
+// The box of a call: per box H[3], M[3] of the staged columns (one box, or one per frame).  n_box 0: no box.
+struct PairBox {
     bool per_frame = false;
-    std::vector<int32_t> ida, idb;
+    int64_t n_box = 0;
     std::vector<double> hm;
+    const double* data() const { return hm.empty() ? nullptr : hm.data(); }
 };
+// Only the analysed axes' lengths count: the others are set to 1 before the table is made, so a zero length there (a slab
+// geometry) is no error and a length that changes there makes no per-frame box.  who: "<call>: "
+int image_box(ta_ctx* ctx, const std::string& who, const double* h_dims, const int* axes, int64_t T, int D, PairBox* b) {
+    for (int d = 0; d < D; ++d)
+        if (axes[d] < 0 || axes[d] > 2) return fail(ctx, TA_E_INVALID, who + "axes: every entry must be 0, 1 or 2");
+    std::vector<double> dims(h_dims, h_dims + 6 * (size_t)T);
+    for (int k = 0; k < 3; ++k)
+        if (std::find(axes, axes + D, k) == axes + D)
+            for (int64_t t = 0; t < T; ++t) dims[6 * (size_t)t + k] = 1.0;
+    BoxTable box;
+    const std::string why = box_table(dims.data(), T, D, axes, 1, &box);
+    if (!why.empty()) return fail(ctx, TA_E_INVALID, who + why);
+    if (box.triclinic)
+        return fail(ctx, TA_E_INVALID, who + "a non-orthogonal box is not supported (the one-step image is not the minimum image there)");
+    b->per_frame = box.per_frame;
+    b->n_box = box.per_frame ? T : 1;
+    b->hm.assign((size_t)b->n_box * 6, 1.0);
+    for (int64_t t = 0; t < b->n_box; ++t)
+        for (int d = 0; d < D; ++d) {
+            b->hm[(size_t)t * 6 + d] = box.tab[(size_t)diag_row(axes[d]) * box.tpitch + t];
+            b->hm[(size_t)t * 6 + 3 + d] = box.tab[(size_t)(6 + diag_row(axes[d])) * box.tpitch + t];
+        }
+    return TA_OK;
+}
+// `value` (reported as `name`) against half the box on the boxes of the frames 0, stride, 2 stride, ...
+int half_box(ta_ctx* ctx, const std::string& who, const char* name, double value, const PairBox& b, int D, int64_t stride) {
+    for (int64_t t = 0; t < b.n_box; t += stride)
+        for (int d = 0; d < D; ++d)
+            if (const double h = b.hm[(size_t)t * 6 + d]; !(value <= 0.5 * h))
+                return fail(ctx, TA_E_INVALID, who + name + " = " + std::to_string(value) + " exceeds half the box length " + std::to_string(h) +
+                                                   " of frame " + std::to_string(t));
+    return TA_OK;
+}
 
-static int vhd_index_list(ta_ctx* ctx, const char* name, int64_t n, const int64_t* idx, int64_t A, int64_t tile, std::vector<int32_t>* out,
-                          int64_t* pitch, const std::string& who = "vanhove_distinct") {
+// The two index lists padded to the pair kernels' tiles (-1: padding); no b list: b = a.  who: "<call>"
+struct ItemLists {
+    int64_t n_a = 0, n_b = 0, pitch_a = 0, pitch_b = 0;
+    std::vector<int32_t> ida, idb;
+};
+static int vhd_index_list(ta_ctx* ctx, const std::string& who, const char* name, int64_t n, const int64_t* idx, int64_t A, int64_t tile,
+                          std::vector<int32_t>* out, int64_t* pitch) {
     for (int64_t i = 0; idx && i < n; ++i) {
         if (idx[i] < 0 || idx[i] >= A)
             return fail(ctx, TA_E_INVALID, who + ": index list " + name + ": entry " + std::to_string(idx[i]) +
@@ -1638,84 +1675,68 @@ static int vhd_index_list(ta_ctx* ctx, const char* name, int64_t n, const int64_
     for (int64_t i = 0; i < n; ++i) (*out)[(size_t)i] = (int32_t)(idx ? idx[i] : i);
     return TA_OK;
 }
+int item_lists(ta_ctx* ctx, const std::string& who, int64_t n_a, const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, int64_t A,
+               ItemLists* p) {
+    p->n_a = h_idx_a ? n_a : A;
+    TA_CHECK(vhd_index_list(ctx, who, "a", p->n_a, h_idx_a, A, VHD_TILE_A, &p->ida, &p->pitch_a));
+    if (!h_idx_b) h_idx_b = h_idx_a, n_b = p->n_a;  // b = a
+    p->n_b = n_b;
+    TA_CHECK(vhd_index_list(ctx, who, "b", p->n_b, h_idx_b, A, VHD_TILE_B, &p->idb, &p->pitch_b));
+    // (a launch's grid is a-tiles x b-tiles in x: 256 threads each, below 2^32 threads)
+    if ((p->pitch_a / VHD_TILE_A) * (p->pitch_b / VHD_TILE_B) >= VHD_MAX_TILES)
+        return fail(ctx, TA_E_INVALID, who + ": ceil(n_a / " + std::to_string(VHD_TILE_A) + ") * ceil(n_b / " + std::to_string(VHD_TILE_B) +
+                                           ") must be below 2^24 (about 2 million items on both sides)");
+    return TA_OK;
+}
+
+// The tail hm | ida | idb of a call's table behind the caller's own head: its doubles (both pitches are even), the packer
+// and the device pointers
+struct PairTail {
+    const double* hm;
+    const int *ida, *idb;
+};
+size_t pair_tail_size(const PairBox& box, const ItemLists& l) { return box.hm.size() + (size_t)(l.pitch_a + l.pitch_b) / 2; }
+void pair_tail_pack(double* q, const PairBox& box, const ItemLists& l) {
+    static_assert(sizeof(int64_t) == sizeof(double) && 2 * sizeof(int32_t) == sizeof(double), "the table's slots");
+    if (!box.hm.empty()) memcpy(q, box.hm.data(), sizeof(double) * box.hm.size());
+    q += box.hm.size();
+    memcpy(q, l.ida.data(), sizeof(int32_t) * l.ida.size());
+    memcpy(q + l.pitch_a / 2, l.idb.data(), sizeof(int32_t) * l.idb.size());
+}
+PairTail pair_tail(const double* q, const PairBox& box, const ItemLists& l) {
+    const int* ids = (const int*)(q + box.hm.size());
+    return {box.hm.empty() ? nullptr : q, ids, ids + l.pitch_a};
+}
+
+// The host side of one van Hove call: the lists, the box, the origins of lag 0
+struct VhdPlan : ItemLists {
+    int L = 0, B = 0, D = 0;
+    int64_t T = 0, stride = 1, n_orig = 0;
+    PairBox box;
+};
 
 // Everything that needs the staged shape (T, A, D), checked before anything is written
 int vhd_plan(ta_ctx* ctx, const VhdArgs& args, int64_t T, int64_t A, int D, VhdPlan* p) {
     auto [L, B, dr, stride, n_a, n_b, h_lags, h_idx_a, h_idx_b, h_dims, axes] = args;
     TA_CHECK(check_cols(ctx, "vanhove_distinct: ", A, D));
     p->L = L, p->B = B, p->D = D, p->T = T, p->stride = stride;
-    p->n_a = h_idx_a ? n_a : A;
-    TA_CHECK(vhd_index_list(ctx, "a", p->n_a, h_idx_a, A, VHD_TILE_A, &p->ida, &p->pitch_a));
-    if (!h_idx_b) {  // b = a
-        h_idx_b = h_idx_a;
-        n_b = p->n_a;
-    }
-    p->n_b = n_b;
-    TA_CHECK(vhd_index_list(ctx, "b", p->n_b, h_idx_b, A, VHD_TILE_B, &p->idb, &p->pitch_b));
-    // (a launch's grid is a-tiles x b-tiles in x: 256 threads each, below 2^32 threads)
-    if ((p->pitch_a / VHD_TILE_A) * (p->pitch_b / VHD_TILE_B) >= VHD_MAX_TILES)
-        return fail(ctx, TA_E_INVALID, "vanhove_distinct: ceil(n_a / " + std::to_string(VHD_TILE_A) + ") * ceil(n_b / " +
-                                           std::to_string(VHD_TILE_B) + ") must be below 2^24 (about 2 million items on both sides)");
+    TA_CHECK(item_lists(ctx, "vanhove_distinct", n_a, h_idx_a, n_b, h_idx_b, A, p));
     p->n_orig = vhd_origins(T, 0, stride);
-    p->n_box = 0, p->per_frame = false;
     if (!h_dims) return TA_OK;
-    // only the analysed axes' lengths count: the others are set to 1 before the table is made, so a zero length there
-    // (a slab geometry) is no error and a length that changes there makes no per-frame box
-    for (int d = 0; d < D; ++d)
-        if (axes[d] < 0 || axes[d] > 2) return fail(ctx, TA_E_INVALID, "vanhove_distinct: axes: every entry must be 0, 1 or 2");
-    std::vector<double> dims(h_dims, h_dims + 6 * (size_t)T);
-    for (int k = 0; k < 3; ++k)
-        if (std::find(axes, axes + D, k) == axes + D)
-            for (int64_t t = 0; t < T; ++t) dims[6 * (size_t)t + k] = 1.0;
-    BoxTable box;
-    const std::string why = box_table(dims.data(), T, D, axes, 1, &box);
-    if (!why.empty()) return fail(ctx, TA_E_INVALID, "vanhove_distinct: " + why);
-    if (box.triclinic)
-        return fail(ctx, TA_E_INVALID, "vanhove_distinct: a non-orthogonal box is not supported (the one-step image is not the "
-                                       "minimum image there)");
-    if (box.per_frame && h_lags[L - 1] > 0)
+    TA_CHECK(image_box(ctx, "vanhove_distinct: ", h_dims, axes, T, D, &p->box));
+    if (p->box.per_frame && h_lags[L - 1] > 0)
         return fail(ctx, TA_E_INVALID, "vanhove_distinct: per-frame boxes are accepted only when every lag is 0");
-    p->per_frame = box.per_frame;
-    p->n_box = box.per_frame ? T : 1;
-    p->hm.assign((size_t)p->n_box * 6, 1.0);
-    const double r_max = (double)B * dr;
-    for (int64_t t = 0; t < p->n_box; ++t)
-        for (int d = 0; d < D; ++d) {
-            const double h = box.tab[(size_t)diag_row(axes[d]) * box.tpitch + t];
-            p->hm[(size_t)t * 6 + d] = h;
-            p->hm[(size_t)t * 6 + 3 + d] = box.tab[(size_t)(6 + diag_row(axes[d])) * box.tpitch + t];
-            if (t % stride == 0 && !(r_max <= 0.5 * h))
-                return fail(ctx, TA_E_INVALID, "vanhove_distinct: n_bins * dr = " + std::to_string(r_max) + " exceeds half the box length " +
-                                                   std::to_string(h) + " of frame " + std::to_string(t));
-        }
-    return TA_OK;
+    return half_box(ctx, "vanhove_distinct: ", "n_bins * dr", (double)B * dr, p->box, D, stride);  // (origin frames only)
 }
 
 // The table of a call queued for upload on `st`, before the call is opened: lags (int64) | e[0 ... B] | hm | ida | idb
-struct VhdTab {
-    const int64_t* lags;
-    const double *e, *hm;
-    const int *ida, *idb;
-};
 int vhd_upload(ta_ctx* ctx, const VhdPlan& p, const int64_t* h_lags, double dr, hipStream_t st) {
-    const size_t n = (size_t)p.L + (size_t)p.B + 1 + p.hm.size() + (size_t)(p.pitch_a + p.pitch_b) / 2;  // (both pitches are even)
     double* h = nullptr;
-    TA_CHECK(ctx->vhd_tab.begin(ctx, sizeof(double) * n, (void**)&h));
-    static_assert(sizeof(int64_t) == sizeof(double) && 2 * sizeof(int32_t) == sizeof(double), "the table's slots");
+    TA_CHECK(ctx->vhd_tab.begin(ctx, sizeof(double) * ((size_t)p.L + (size_t)p.B + 1 + pair_tail_size(p.box, p)), (void**)&h));
     memcpy(h, h_lags, sizeof(int64_t) * (size_t)p.L);
     vh_edges(p.B, dr, h + p.L);
-    double* q = h + p.L + p.B + 1;
-    if (!p.hm.empty()) memcpy(q, p.hm.data(), sizeof(double) * p.hm.size());
-    q += p.hm.size();
-    memcpy(q, p.ida.data(), sizeof(int32_t) * p.ida.size());
-    memcpy(q + p.pitch_a / 2, p.idb.data(), sizeof(int32_t) * p.idb.size());
+    pair_tail_pack(h + p.L + p.B + 1, p.box, p);
     return ctx->vhd_tab.send(ctx, st);
-}
-VhdTab vhd_tab(ta_ctx* ctx, const VhdPlan& p) {
-    const double* d = (const double*)ctx->vhd_tab.dev.p;
-    const double* q = d + p.L + p.B + 1;
-    const int* ids = (const int*)(q + p.hm.size());
-    return {(const int64_t*)d, d + p.L, p.hm.empty() ? nullptr : q, ids, ids + p.pitch_a};
 }
 
 // One call on a pair-major position slab of either element type (the caller has opened the call's bracket, it is closed
@@ -1735,7 +1756,9 @@ int vhd_pm(ta_ctx* ctx, const Slab& slab, const VhdPlan& p, double dr, int64_t* 
     const size_t hist_bytes = sizeof(int64_t) * (size_t)L * (size_t)(B + 1);
     TA_CHECK(ensure(ctx, ctx->vhd_scr, bytes_a + (size_t)Lc * bytes_lag));
     TA_CHECK(ensure(ctx, ctx->vhd_hist, hist_bytes));
-    const VhdTab tab = vhd_tab(ctx, p);
+    const int64_t* lags = (const int64_t*)ctx->vhd_tab.dev.p;
+    const double* e = (const double*)(lags + L);
+    const PairTail tab = pair_tail(e + B + 1, p.box, p);
     double* ga = (double*)ctx->vhd_scr.p;
     double* gb = ga + bytes_a / 8;
     TA_HIP_TRY(ctx, hipMemsetAsync(ctx->vhd_hist.p, 0, hist_bytes, st));
@@ -1743,12 +1766,12 @@ int vhd_pm(ta_ctx* ctx, const Slab& slab, const VhdPlan& p, double dr, int64_t* 
         const int lc = std::min(Lc, L - l0);
         TA_LAUNCH(ctx, "k_vhd_gather", st,
                   launch_vhd_gather(slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, D, (long)p.stride, (long)p.n_orig,
-                                    tab.lags + l0, lc, l0 == 0, tab.ida, tab.idb, (long)p.pitch_a, (long)p.pitch_b, ga, gb, st));
+                                    lags + l0, lc, l0 == 0, tab.ida, tab.idb, (long)p.pitch_a, (long)p.pitch_b, ga, gb, st));
         for (int64_t o0 = 0; o0 < p.n_orig; o0 += 65535)
             TA_LAUNCH_MAIN(ctx, "k_vhd_pairs", st,
                            launch_vhd_pairs(ga, gb, tab.ida, tab.idb, (long)p.pitch_a, (long)p.pitch_b, (long)p.n_a, (long)p.n_b, D,
                                             (long)slab.T, (long)p.stride, (long)p.n_orig, (long)o0,
-                                            (int)std::min<int64_t>(65535, p.n_orig - o0), tab.lags + l0, lc, tab.hm, p.per_frame, tab.e, B,
+                                            (int)std::min<int64_t>(65535, p.n_orig - o0), lags + l0, lc, tab.hm, p.box.per_frame, e, B,
                                             vh_inv_dr(dr), (unsigned long long*)ctx->vhd_hist.p + (size_t)l0 * (size_t)(B + 1), st));
     }
     TA_HIP_TRY(ctx, hipMemcpyAsync(d_counts, ctx->vhd_hist.p, hist_bytes, hipMemcpyDeviceToDevice, st));
@@ -1775,40 +1798,6 @@ int vhd_launch(ta_ctx* ctx, const VhdPlan& plan, const int64_t* h_lags, double d
 // ---- pair lifetimes: candidate search, indicator series, run lengths (pair_lifetime.hip) ----------------------------
 constexpr size_t kPairBudget = (size_t)32 << 30;  // the indicator block of one block of pairs (a choice, as kScatterBudget)
 
-// The box of a pair call (both kinds of context): per box H[3], M[3] of the staged columns, as VhdPlan's; r_cut checked
-// against it.  Only the analysed axes' lengths are looked at.  n_box 0: no box.
-struct PairBox {
-    bool per_frame = false;
-    int64_t n_box = 0;
-    std::vector<double> hm;
-};
-int pair_box(ta_ctx* ctx, const std::string& who, const double* h_dims, const int* axes, int64_t T, int D, double r_cut, PairBox* b,
-             const char* cut_name = "r_cut") {
-    for (int d = 0; d < D; ++d)
-        if (axes[d] < 0 || axes[d] > 2) return fail(ctx, TA_E_INVALID, who + "axes: every entry must be 0, 1 or 2");
-    std::vector<double> dims(h_dims, h_dims + 6 * (size_t)T);
-    for (int k = 0; k < 3; ++k)
-        if (std::find(axes, axes + D, k) == axes + D)
-            for (int64_t t = 0; t < T; ++t) dims[6 * (size_t)t + k] = 1.0;
-    BoxTable box;
-    const std::string why = box_table(dims.data(), T, D, axes, 1, &box);
-    if (!why.empty()) return fail(ctx, TA_E_INVALID, who + why);
-    if (box.triclinic)
-        return fail(ctx, TA_E_INVALID, who + "a non-orthogonal box is not supported (the one-step image is not the minimum image there)");
-    b->per_frame = box.per_frame;
-    b->n_box = box.per_frame ? T : 1;
-    b->hm.assign((size_t)b->n_box * 6, 1.0);
-    for (int64_t t = 0; t < b->n_box; ++t)
-        for (int d = 0; d < D; ++d) {
-            const double h = box.tab[(size_t)diag_row(axes[d]) * box.tpitch + t];
-            b->hm[(size_t)t * 6 + d] = h;
-            b->hm[(size_t)t * 6 + 3 + d] = box.tab[(size_t)(6 + diag_row(axes[d])) * box.tpitch + t];
-            if (!(r_cut <= 0.5 * h))
-                return fail(ctx, TA_E_INVALID, who + cut_name + " = " + std::to_string(r_cut) + " exceeds half the box length " + std::to_string(h) +
-                                                   " of frame " + std::to_string(t));
-        }
-    return TA_OK;
-}
 // what both pair calls check of r_cut and the box arguments before the staged shape is needed
 int pair_cut_args(ta_ctx* ctx, const std::string& who, double r_cut, const double* h_dims, const int* axes) {
     if (!(r_cut > 0.0) || !(r_cut - r_cut == 0.0)) return fail(ctx, TA_E_INVALID, who + "r_cut must be finite and greater than 0");
@@ -1817,12 +1806,11 @@ int pair_cut_args(ta_ctx* ctx, const std::string& who, double r_cut, const doubl
 }
 
 // The host side of one search (both kinds of context)
-struct PairFindPlan {
+struct PairFindPlan : ItemLists {
     int D = 0;
-    int64_t T = 0, A = 0, stride = 1, n_a = 0, n_b = 0, n_srch = 0, pitch_a = 0, pitch_b = 0;
+    int64_t T = 0, A = 0, stride = 1, n_srch = 0;
     bool same = false;
     double rc2 = 0.0;
-    std::vector<int32_t> ida, idb;
     PairBox box;
 };
 int pair_find_plan(ta_ctx* ctx, int64_t n_a, const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dims,
@@ -1838,12 +1826,8 @@ int pair_find_plan(ta_ctx* ctx, int64_t n_a, const int64_t* h_idx_a, int64_t n_b
     const int D = ctx->st_D;
     TA_CHECK(check_cols(ctx, who, A, D));
     p->D = D, p->T = T, p->A = A, p->stride = stride, p->rc2 = r_cut * r_cut;
-    p->n_a = h_idx_a ? n_a : A;
-    TA_CHECK(vhd_index_list(ctx, "a", p->n_a, h_idx_a, A, VHD_TILE_A, &p->ida, &p->pitch_a, "pair_find"));
+    TA_CHECK(item_lists(ctx, "pair_find", n_a, h_idx_a, n_b, h_idx_b, A, p));
     p->same = !h_idx_b;
-    if (!h_idx_b) h_idx_b = h_idx_a, n_b = p->n_a;
-    p->n_b = n_b;
-    TA_CHECK(vhd_index_list(ctx, "b", p->n_b, h_idx_b, A, VHD_TILE_B, &p->idb, &p->pitch_b, "pair_find"));
     if (!p->same) {  // two lists: the same list twice, or disjoint ones (both increase strictly: one merge walk)
         p->same = p->n_a == p->n_b && std::equal(p->ida.begin(), p->ida.begin() + p->n_a, p->idb.begin());
         for (int64_t i = 0, j = 0; !p->same && i < p->n_a && j < p->n_b;) {
@@ -1853,15 +1837,13 @@ int pair_find_plan(ta_ctx* ctx, int64_t n_a, const int64_t* h_idx_a, int64_t n_b
             p->ida[i] < p->idb[j] ? ++i : ++j;
         }
     }
-    if ((p->pitch_a / VHD_TILE_A) * (p->pitch_b / VHD_TILE_B) >= VHD_MAX_TILES)
-        return fail(ctx, TA_E_INVALID, who + "ceil(n_a / " + std::to_string(VHD_TILE_A) + ") * ceil(n_b / " + std::to_string(VHD_TILE_B) +
-                                           ") must be below 2^24 (about 2 million items on both sides)");
     if (p->pitch_a * p->pitch_b > (int64_t)1 << 35)
         return fail(ctx, TA_E_INVALID, who + "the pair bitmap of " + std::to_string(p->pitch_a) + " x " + std::to_string(p->pitch_b) +
                                            " padded items exceeds 2^35 bits (4 GiB)");
     p->n_srch = vhd_origins(T, 0, stride);
-    if (h_dims) TA_CHECK(pair_box(ctx, who, h_dims, axes, T, D, r_cut, &p->box));
-    return TA_OK;
+    if (!h_dims) return TA_OK;
+    TA_CHECK(image_box(ctx, who, h_dims, axes, T, D, &p->box));
+    return half_box(ctx, who, "r_cut", r_cut, p->box, D, 1);
 }
 
 // One search on the staged position slab of either element type (the caller has opened the call's bracket, it is closed
@@ -1871,11 +1853,8 @@ int pair_find_plan(ta_ctx* ctx, int64_t n_a, const int64_t* h_idx_a, int64_t n_b
 int pair_find_pm(ta_ctx* ctx, const Slab& slab, const PairFindPlan& p) {
     hipStream_t st = slab.st;
     const int D = p.D;
-    const double* tab = (const double*)ctx->pair_ftab.dev.p;
-    const int64_t* lag0 = (const int64_t*)tab;
-    const double* hm = p.box.n_box ? tab + 1 : nullptr;
-    const int* ida = (const int*)(tab + 1 + p.box.hm.size());
-    const int* idb = ida + p.pitch_a;
+    const int64_t* lag0 = (const int64_t*)ctx->pair_ftab.dev.p;
+    const auto [hm, ida, idb] = pair_tail((const double*)(lag0 + 1), p.box, p);
     const size_t per = sizeof(double) * (size_t)D * (size_t)(p.pitch_a + p.pitch_b);
     const int64_t fit = std::max<int64_t>(1, (int64_t)(kVhdBudget / per));
     const int64_t oc = std::min<int64_t>({p.n_srch, 65535, ctx->opt_pair_find_chunk > 0 ? ctx->opt_pair_find_chunk : fit});
@@ -1922,14 +1901,10 @@ int pair_find_launch(ta_ctx* ctx, const PairFindPlan& p) {
     return slab_entry(
         ctx, nullptr, ctx->stream, no_args,
         [&](const Slab& s) -> int {
-            const size_t n = 1 + p.box.hm.size() + (size_t)(p.pitch_a + p.pitch_b) / 2;  // (both pitches are even)
             double* h = nullptr;
-            TA_CHECK(ctx->pair_ftab.begin(ctx, sizeof(double) * n, (void**)&h));
+            TA_CHECK(ctx->pair_ftab.begin(ctx, sizeof(double) * (1 + pair_tail_size(p.box, p)), (void**)&h));
             memset(h, 0, sizeof(double));  // the zero lag (int64)
-            if (!p.box.hm.empty()) memcpy(h + 1, p.box.hm.data(), sizeof(double) * p.box.hm.size());
-            double* q = h + 1 + p.box.hm.size();
-            memcpy(q, p.ida.data(), sizeof(int32_t) * p.ida.size());
-            memcpy(q + p.pitch_a / 2, p.idb.data(), sizeof(int32_t) * p.idb.size());
+            pair_tail_pack(h + 1, p.box, p);
             return ctx->pair_ftab.send(ctx, s.st);
         },
         [&](const Slab& s) { return pair_find_pm(ctx, s, p); });
@@ -2019,8 +1994,9 @@ int pair_life_plan(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs
         if (ctx->pair_n == 0) return fail(ctx, TA_E_STATE, who + "the found pair list is empty");
         p->P = ctx->pair_n;
     }
-    if (h_dims) TA_CHECK(pair_box(ctx, who, h_dims, axes, T, ctx->st_D, bond ? bond->r_break : r_cut, &p->box, bond ? "r_break" : "r_cut"));
-    return TA_OK;
+    if (!h_dims) return TA_OK;
+    TA_CHECK(image_box(ctx, who, h_dims, axes, T, ctx->st_D, &p->box));
+    return half_box(ctx, who, bond ? "r_break" : "r_cut", bond ? bond->r_break : r_cut, p->box, ctx->st_D, 1);
 }
 
 // the candidate pairs per block: "pair_chunk", or as many as kPairBudget holds of the indicator block
@@ -2997,30 +2973,27 @@ int ta_vanhove_distinct_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, i
     });
 }
 
-// Pair lifetimes on the staged slab 0, read in its own element type; the pair list and the box are HOST arrays
-int ta_pair_lifetime_staged(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs, const double* h_dimensions, const int* axes,
-                            double r_cut, double* d_ci, int64_t* d_runs, double* d_nb, void* stream) {
+// Pair lifetimes on the staged slab 0, read in its own element type; the pair list and the box are HOST arrays.  Bond
+// lifetimes (bond != NULL) take the same path with k_bond_series (and k_pair_filter where needed)
+static int life_staged(ta_ctx* ctx, int fft, int64_t n_rows, const int32_t* h_rows, const double* h_dimensions, const int* axes, double r_cut,
+                       const BondArgs* bond, double* d_ci, int64_t* d_runs, double* d_nb, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
     PairLifePlan plan;
     TA_CHECK(need_ctx(ctx));
     TA_NO_CPU(ctx);
-    TA_CHECK(pair_life_plan(ctx, fft, n_pairs, h_pairs, h_dimensions, axes, r_cut, d_ci || d_runs || d_nb, &plan));
+    TA_CHECK(pair_life_plan(ctx, fft, n_rows, h_rows, h_dimensions, axes, r_cut, d_ci || d_runs || d_nb, &plan, bond));
     return pair_life_launch(ctx, fft, plan, d_ci, d_runs, d_nb, stream, nullptr);
     });
 }
-
-// Bond lifetimes on the staged slab 0: ta_pair_lifetime_staged's path with k_bond_series (and k_pair_filter where needed)
+int ta_pair_lifetime_staged(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs, const double* h_dimensions, const int* axes,
+                            double r_cut, double* d_ci, int64_t* d_runs, double* d_nb, void* stream) {
+    return life_staged(ctx, fft, n_pairs, h_pairs, h_dimensions, axes, r_cut, nullptr, d_ci, d_runs, d_nb, stream);
+}
 int ta_bond_lifetime_staged(ta_ctx* ctx, int fft, int64_t n_bonds, int n_at, const int32_t* h_atoms, const double* h_dimensions,
                             const int* axes, double r_cut, double r_break, double cos_cut, double cos_break, int gap, double* d_ci,
                             int64_t* d_runs, double* d_nb, void* stream) {
-    return ta::guarded(fail, ctx, [&]() -> int {
-    PairLifePlan plan;
     const BondArgs bond{n_at, r_break, cos_cut, cos_break, gap};
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(pair_life_plan(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, d_ci || d_runs || d_nb, &plan, &bond));
-    return pair_life_launch(ctx, fft, plan, d_ci, d_runs, d_nb, stream, nullptr);
-    });
+    return life_staged(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, &bond, d_ci, d_runs, d_nb, stream);
 }
 
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
@@ -3759,7 +3732,7 @@ int ta_vanhove_distinct(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int64_t 
     TA_CHECK(vhd_plan(ctx, a, ctx->st_T, ctx->st_A, ctx->st_D, &p));
     if (ctx->is_cpu)
         return cpu_rc(ctx, ta::cpu::vanhove_distinct(cpu_state(ctx), n_lags, h_lags, origin_stride, p.n_a, p.ida.data(), p.n_b, p.idb.data(),
-                                                     p.hm.empty() ? nullptr : p.hm.data(), p.per_frame, n_bins, dr, h_counts));
+                                                     p.box.data(), p.box.per_frame, n_bins, dr, h_counts));
     int64_t* d_out = nullptr;
     TA_CHECK(vhd_launch(ctx, p, h_lags, dr, nullptr, ctx->stream, &d_out));
     return host_finish(ctx, {{(double*)h_counts, (const double*)d_out, (size_t)n_lags * (size_t)(n_bins + 1)}});  // (8-byte elements)
@@ -3775,7 +3748,7 @@ int ta_pair_find(ta_ctx* ctx, int64_t n_a, const int64_t* h_idx_a, int64_t n_b, 
     if (ctx->is_cpu) {
         ctx->pair_n = -1;
         TA_CHECK(cpu_rc(ctx, ta::cpu::pair_find(cpu_state(ctx), p.n_a, p.ida.data(), p.n_b, p.idb.data(), p.same, search_stride,
-                                                p.box.hm.empty() ? nullptr : p.box.hm.data(), p.box.per_frame, p.rc2, &ctx->pair_host)));
+                                                p.box.data(), p.box.per_frame, p.rc2, &ctx->pair_host)));
         ctx->pair_n = (int64_t)(ctx->pair_host.size() / 2), ctx->pair_A = p.A;
     } else {
         TA_CHECK(pair_find_launch(ctx, p));
@@ -3806,37 +3779,33 @@ int ta_pair_find_read(ta_ctx* ctx, int64_t capacity, int32_t* h_pairs) {
     });
 }
 
-int ta_pair_lifetime(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs, const double* h_dimensions, const int* axes,
-                     double r_cut, double* h_ci, int64_t* h_runs, double* h_nb) {
+// ta_pair_lifetime and (bond != NULL) ta_bond_lifetime: the plan, the CPU backend or the device half, the outputs copied back
+static int life_host(ta_ctx* ctx, int fft, int64_t n_rows, const int32_t* h_rows, const double* h_dimensions, const int* axes, double r_cut,
+                     const BondArgs* bond, double* h_ci, int64_t* h_runs, double* h_nb) {
     return host_call(ctx, [&]() -> int {
     PairLifePlan p;
     TA_CHECK(need_ctx(ctx));
-    TA_CHECK(pair_life_plan(ctx, fft, n_pairs, h_pairs, h_dimensions, axes, r_cut, h_ci || h_runs || h_nb, &p));
+    TA_CHECK(pair_life_plan(ctx, fft, n_rows, h_rows, h_dimensions, axes, r_cut, h_ci || h_runs || h_nb, &p, bond));
+    if (ctx->is_cpu && bond)
+        return cpu_rc(ctx, ta::cpu::bond_lifetime(cpu_state(ctx), fft != 0, p.P, p.n_at, h_rows, p.box.data(), p.box.per_frame, p.cuts, p.gap,
+                                                  h_ci, h_runs, h_nb));
     if (ctx->is_cpu)
-        return cpu_rc(ctx, ta::cpu::pair_lifetime(cpu_state(ctx), fft != 0, p.P, h_pairs ? h_pairs : ctx->pair_host.data(),
-                                                  p.box.hm.empty() ? nullptr : p.box.hm.data(), p.box.per_frame, p.rc2, h_ci, h_runs, h_nb));
+        return cpu_rc(ctx, ta::cpu::pair_lifetime(cpu_state(ctx), fft != 0, p.P, h_rows ? h_rows : ctx->pair_host.data(), p.box.data(),
+                                                  p.box.per_frame, p.rc2, h_ci, h_runs, h_nb));
     double* d_out = nullptr;
     TA_CHECK(pair_life_launch(ctx, fft, p, h_ci, h_runs, h_nb, ctx->stream, &d_out));
     const size_t T = (size_t)ctx->st_T;  // (int64 counts travel as 8-byte elements)
     return host_finish(ctx, {{h_ci, d_out, T}, {(double*)h_runs, d_out + T, T + 1}, {h_nb, d_out + 2 * T + 1, T}});
     });
 }
-
+int ta_pair_lifetime(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs, const double* h_dimensions, const int* axes,
+                     double r_cut, double* h_ci, int64_t* h_runs, double* h_nb) {
+    return life_host(ctx, fft, n_pairs, h_pairs, h_dimensions, axes, r_cut, nullptr, h_ci, h_runs, h_nb);
+}
 int ta_bond_lifetime(ta_ctx* ctx, int fft, int64_t n_bonds, int n_at, const int32_t* h_atoms, const double* h_dimensions, const int* axes,
                      double r_cut, double r_break, double cos_cut, double cos_break, int gap, double* h_ci, int64_t* h_runs, double* h_nb) {
-    return host_call(ctx, [&]() -> int {
-    PairLifePlan p;
     const BondArgs bond{n_at, r_break, cos_cut, cos_break, gap};
-    TA_CHECK(need_ctx(ctx));
-    TA_CHECK(pair_life_plan(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, h_ci || h_runs || h_nb, &p, &bond));
-    if (ctx->is_cpu)
-        return cpu_rc(ctx, ta::cpu::bond_lifetime(cpu_state(ctx), fft != 0, p.P, p.n_at, h_atoms, p.box.hm.empty() ? nullptr : p.box.hm.data(),
-                                                  p.box.per_frame, p.cuts, p.gap, h_ci, h_runs, h_nb));
-    double* d_out = nullptr;
-    TA_CHECK(pair_life_launch(ctx, fft, p, h_ci, h_runs, h_nb, ctx->stream, &d_out));
-    const size_t T = (size_t)ctx->st_T;
-    return host_finish(ctx, {{h_ci, d_out, T}, {(double*)h_runs, d_out + T, T + 1}, {h_nb, d_out + 2 * T + 1, T}});
-    });
+    return life_host(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, &bond, h_ci, h_runs, h_nb);
 }
 
 // The host slabs of a context go away (ta_compound: they hold atoms, the staged slab no longer does)

@@ -873,6 +873,30 @@ int overlap(const State& s, int L, const int64_t* lags, int C, const double* cut
     return s.dtype == TA_F32 ? overlap_e<float>(s, L, lags, C, cutoffs, q) : overlap_e<double>(s, L, lags, C, cutoffs, q);
 }
 
+// fn(E(), D, PERIODIC) as template arguments for the staged element type, dim and box
+#define TA_PAIR_DISPATCH(fn, ...)                                                                                  \
+    do {                                                                                                           \
+        const bool f32 = s.dtype == TA_F32;                                                                        \
+        if (hm) {                                                                                                  \
+            if (s.D == 1) return f32 ? fn<float, 1, true>(__VA_ARGS__) : fn<double, 1, true>(__VA_ARGS__);         \
+            if (s.D == 2) return f32 ? fn<float, 2, true>(__VA_ARGS__) : fn<double, 2, true>(__VA_ARGS__);         \
+            return f32 ? fn<float, 3, true>(__VA_ARGS__) : fn<double, 3, true>(__VA_ARGS__);                       \
+        }                                                                                                          \
+        if (s.D == 1) return f32 ? fn<float, 1, false>(__VA_ARGS__) : fn<double, 1, false>(__VA_ARGS__);           \
+        if (s.D == 2) return f32 ? fn<float, 2, false>(__VA_ARGS__) : fn<double, 2, false>(__VA_ARGS__);           \
+        return f32 ? fn<float, 3, false>(__VA_ARGS__) : fn<double, 3, false>(__VA_ARGS__);                         \
+    } while (0)
+
+// the box of frame t: H[3], M[3] of the staged columns (ones without a box and on the axes past D)
+template <int D, bool PERIODIC>
+inline void frame_box(const double* hm, bool per_frame, int64_t t, double (&H)[3], double (&M)[3]) {
+    for (int d = 0; d < 3; ++d) H[d] = 1.0, M[d] = 1.0;
+    if (PERIODIC) {
+        const double* box = hm + (per_frame ? t * 6 : 0);
+        for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
+    }
+}
+
 // The distinct van Hove histogram: OpenMP threads take (origin, tile of kVhdCpuTile a-items) units, each thread with an int64
 // histogram of its own; the threads' histograms are added at the end.  Integer adds only: nothing depends on the number of
 // threads or on which thread took which unit.
@@ -900,11 +924,8 @@ int vanhove_distinct_t(const State& s, int L, const int64_t* lags, int64_t strid
     for (int64_t w = 0; w < n_orig * n_tiles; ++w) {
         const int64_t t = (w / n_tiles) * stride, p0 = (w % n_tiles) * kVhdCpuTile, p1 = std::min(n_a, p0 + kVhdCpuTile);
         int64_t* h = hist.data() + (size_t)omp_get_thread_num() * nh;
-        double H[3] = {1.0, 1.0, 1.0}, M[3] = {1.0, 1.0, 1.0};
-        if (PERIODIC) {
-            const double* box = hm + (per_frame ? t * 6 : 0);
-            for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
-        }
+        double H[3], M[3];
+        frame_box<D, PERIODIC>(hm, per_frame, t, H, M);
         for (int l = 0; l < L && t + lags[l] < T; ++l) {  // (the lags increase)
             const int64_t t2 = t + lags[l];
             for (int64_t p = p0; p < p1; ++p) {
@@ -924,21 +945,9 @@ int vanhove_distinct_t(const State& s, int L, const int64_t* lags, int64_t strid
     return TA_OK;
 }
 
-template <class E, bool PERIODIC, class... Args>
-int vanhove_distinct_d(const State& s, Args... args) {
-    if (s.D == 1) return vanhove_distinct_t<E, 1, PERIODIC>(s, args...);
-    if (s.D == 2) return vanhove_distinct_t<E, 2, PERIODIC>(s, args...);
-    return vanhove_distinct_t<E, 3, PERIODIC>(s, args...);
-}
-
 int vanhove_distinct(const State& s, int L, const int64_t* lags, int64_t stride, int64_t n_a, const int32_t* ida, int64_t n_b,
                      const int32_t* idb, const double* hm, bool per_frame, int B, double dr, int64_t* counts) {
-    const bool f32 = s.dtype == TA_F32;
-    if (hm)
-        return f32 ? vanhove_distinct_d<float, true>(s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts)
-                   : vanhove_distinct_d<double, true>(s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts);
-    return f32 ? vanhove_distinct_d<float, false>(s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts)
-               : vanhove_distinct_d<double, false>(s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts);
+    TA_PAIR_DISPATCH(vanhove_distinct_t, s, L, lags, stride, n_a, ida, n_b, idb, hm, per_frame, B, dr, counts);
 }
 
 // ---- pair and bond lifetimes (pair_math.hpp, bond_math.hpp) ---------------------------------------------------------------------------------
@@ -957,11 +966,8 @@ int pair_find_t(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, co
     for (int64_t p = 0; p < n_a; ++p) {
         uint64_t* row = bits.data() + (size_t)p * words_b;
         for (int64_t t = 0; t < T; t += stride) {
-            double H[3] = {1.0, 1.0, 1.0}, M[3] = {1.0, 1.0, 1.0};
-            if (PERIODIC) {
-                const double* box = hm + (per_frame ? t * 6 : 0);
-                for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
-            }
+            double H[3], M[3];
+            frame_box<D, PERIODIC>(hm, per_frame, t, H, M);
             double a[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
             for (int d = 0; d < D; ++d) a[d] = (double)x[((size_t)t * A + ida[p]) * D + d];
             for (int64_t q = same ? p + 1 : 0; q < n_b; ++q) {
@@ -1061,11 +1067,7 @@ int lifetime_sums(const State& s, bool fft, int64_t P, double* ci, int64_t* runs
 template <class E, int D, bool PERIODIC, int NAT>
 void bond_frame(const E* x, int64_t A, int64_t t, const int32_t* row, const double* hm, bool per_frame, double (&H)[3], double (&M)[3],
                 double (&at)[NAT][3]) {
-    for (int d = 0; d < 3; ++d) H[d] = 1.0, M[d] = 1.0;
-    if (PERIODIC) {
-        const double* box = hm + (per_frame ? t * 6 : 0);
-        for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
-    }
+    frame_box<D, PERIODIC>(hm, per_frame, t, H, M);
     for (int i = 0; i < NAT; ++i)
         for (int d = 0; d < 3; ++d) at[i][d] = d < D ? (double)x[((size_t)t * A + row[i]) * D + d] : 0.0;
 }
@@ -1132,20 +1134,6 @@ int bond_lifetime_t(const State& s, bool fft, int64_t P, int n_at, const int32_t
         else bond_fill<E, D, PERIODIC, 2>(s, atoms + 2 * n, hm, per_frame, cuts, gap, w, Sw);
     });
 }
-
-// fn(E(), D, PERIODIC) as template arguments for the staged element type, dim and box
-#define TA_PAIR_DISPATCH(fn, ...)                                                                                  \
-    do {                                                                                                           \
-        const bool f32 = s.dtype == TA_F32;                                                                        \
-        if (hm) {                                                                                                  \
-            if (s.D == 1) return f32 ? fn<float, 1, true>(__VA_ARGS__) : fn<double, 1, true>(__VA_ARGS__);         \
-            if (s.D == 2) return f32 ? fn<float, 2, true>(__VA_ARGS__) : fn<double, 2, true>(__VA_ARGS__);         \
-            return f32 ? fn<float, 3, true>(__VA_ARGS__) : fn<double, 3, true>(__VA_ARGS__);                       \
-        }                                                                                                          \
-        if (s.D == 1) return f32 ? fn<float, 1, false>(__VA_ARGS__) : fn<double, 1, false>(__VA_ARGS__);           \
-        if (s.D == 2) return f32 ? fn<float, 2, false>(__VA_ARGS__) : fn<double, 2, false>(__VA_ARGS__);           \
-        return f32 ? fn<float, 3, false>(__VA_ARGS__) : fn<double, 3, false>(__VA_ARGS__);                         \
-    } while (0)
 
 int pair_find(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, bool same, int64_t stride,
               const double* hm, bool per_frame, double rc2, std::vector<int32_t>* pairs) {

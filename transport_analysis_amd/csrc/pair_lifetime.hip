@@ -2,12 +2,13 @@
 // bonds): which pairs of items are ever bonded, their 0/1 indicator series as a pair-major block, and the histogram of the
 // lengths of their runs of bonded frames.  pair_math.hpp has the arithmetic, which the CPU backend follows.
 //
-//   k_pair_find<D, PERIODIC>    the candidate search on k_vhd_pairs' tiles and grid, over the frame-major scratch that
-//                               k_vhd_gather writes at lag 0: a workgroup per (256 a-items, 1024 b-items, searched frame), a
-//                               lane owning 4 b-items in registers, the a-item read by scalar loads.  No histogram: a wave's
-//                               64 lanes hold 64 consecutive b-items, so its ballot of "bonded and a different item" IS the
-//                               64-bit word of the bitmap [pitch_a][pitch_b / 64]; one lane ORs it in, and only when it is
-//                               non-zero.  OR is idempotent: the bitmap is the same from run to run and for every chunk.
+//   k_pair_find<D, PERIODIC>    the candidate search: k_vhd_pairs' walk (pair_tile_walk of pair_tile.hpp: a workgroup per (256
+//                               a-items, 1024 b-items, searched frame), a lane owning 4 b-items in registers, the a-item read
+//                               by scalar loads) over the frame-major scratch that k_vhd_gather writes at lag 0, with another
+//                               visitor.  No histogram: a wave's 64 lanes hold 64 consecutive b-items, so its ballot of "bonded
+//                               and a different item" IS the 64-bit word of the bitmap [pitch_a][pitch_b / 64]; one lane ORs it
+//                               in, and only when it is non-zero.  OR is idempotent: the same bitmap from run to run and for
+//                               every chunk.
 //   k_pair_count, k_pair_list   the bitmap -> the list of (item a, item b) as int32, sorted by (a, b): popcounts per block
 //                               of 1024 words, an exclusive scan of the block counts on the host, then every block expands
 //                               its bits behind its offset (a wave scan and the waves' totals order the threads).
@@ -15,7 +16,8 @@
 //                               the pitch and the units g, g + G, ...; a unit is two candidate pairs = one whole destination
 //                               pair of columns of a float64 block of P pseudo-atoms with D = 1, values 1.0 / 0.0, rows
 //                               T ... pitch - 1 and the phantom column of an odd P zeros.  The atoms are read through PmAtom
-//                               in the slab's own element type.  Every element has one writer.
+//                               in the slab's own element type.  Every element has one writer.  All of that is series_body,
+//                               which k_bond_series shares; the kernel's own part is its row, pair_indicator (one compare).
 //   k_pair_runs                 a wave per destination pair at a time (two series): lane l reads frame 64 j + l, the ballot
 //                               is the 64-frame word, a lane at a run's end finds the run's start with bit operations on the
 //                               word and the carry of the run open since the words before.  Runs of up to kRunsSmall frames are
@@ -23,7 +25,8 @@
 //                               ones take one 64-bit integer atomic each.  Integer adds only: the same bits in any order.
 //   k_pair_reduce               the blocks' rows added in block order (the lag sums rescaled to integers on the way).
 // and of the bond lifetimes (bond_math.hpp: pairs or donor-hydrogen-acceptor triplets, a form and a break criterion):
-//   k_bond_series<E, D, BOX, NAT>  k_pair_series with NAT atoms per row and the frame's LEVEL 0 / 1 / 2 as its value.
+//   k_bond_series<E, D, BOX, NAT>  series_body with bond_levels as its row: NAT atoms per row, the frame's LEVEL 0 / 1 / 2 as
+//                               its value.  (Pair calls do not go through it with NAT = 2: the pair row keeps its one compare.)
 //   k_pair_filter               the level block -> the 0/1 block in place, on k_pair_runs' walk: hysteresis (a fill of the
 //                               level-2 bits through the runs of level >= 1, one carry bit across words) and the closing of
 //                               absences of up to 63 frames (a window of three resolved words).  No atomics, no LDS.
@@ -33,14 +36,10 @@
 #include <type_traits>
 
 #include "bond_math.hpp"
-#include "pm_read.hpp"
-#include "ta_internal.hpp"
+#include "pair_tile.hpp"
 
 namespace ta {
 namespace {
-
-constexpr int kPfR = 4;  // b-items per lane, as k_vhd_pairs
-static_assert(kPmThreads * kPfR == VHD_TILE_B && VHD_TILE_B % 64 == 0, "a wave's 64 lanes hold one whole word of the b-tile");
 
 // grid (a-tiles x b-tiles, the chunk's searched frames).  ga [n_o][D][pitch_a], gb [n_o][D][pitch_b]: the chunk's gathered
 // frames; frame y of the chunk is frame (o_base + y) stride of the slab (its box with box_per_frame).  hm as k_vhd_pairs'.
@@ -51,40 +50,15 @@ __global__ void __launch_bounds__(kPmThreads)
                 const int* __restrict__ idb, long pitch_a, long pitch_b, int n_a, int n_tb, long stride, long o_base,
                 const double* __restrict__ hm, int box_per_frame, double rc2, int same, unsigned long long* __restrict__ bitmap) {
     const long o = blockIdx.y;
-    const int tile_a = blockIdx.x / n_tb, tile_b = blockIdx.x % n_tb;
-    double H[3] = {1.0, 1.0, 1.0}, M[3] = {1.0, 1.0, 1.0};
-    if constexpr (PERIODIC) {
-        const double* box = hm + (box_per_frame ? (o_base + o) * stride * 6 : 0);
-#pragma unroll
-        for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
-    }
-    const double* gbo = gb + (size_t)o * D * (size_t)pitch_b;
-    double xb[kPfR][3];
-    int idq[kPfR];
-#pragma unroll
-    for (int r = 0; r < kPfR; ++r) {
-        const long q = (long)tile_b * VHD_TILE_B + r * kPmThreads + threadIdx.x;  // (< pitch_b: a multiple of the tile)
-        idq[r] = idb[q];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) xb[r][d] = d < D ? gbo[(size_t)d * pitch_b + q] : 0.0;
-    }
-    const double* gao = ga + (size_t)o * D * (size_t)pitch_a;
-    const int p0 = tile_a * VHD_TILE_A, p1 = min(p0 + VHD_TILE_A, n_a);
     const int lane = threadIdx.x & 63;
     const long words_b = pitch_b / 64;
-    const long w0 = ((long)tile_b * VHD_TILE_B + (threadIdx.x - lane)) / 64;  // the wave's word of r = 0
-    for (int p = p0; p < p1; ++p) {  // (uniform: the a-item comes by scalar loads)
-        double xa[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-        for (int d = 0; d < D; ++d) xa[d] = gao[(size_t)d * pitch_a + p];
-        const int id = ida[p];
-#pragma unroll
-        for (int r = 0; r < kPfR; ++r) {
-            const bool keep = pair_bonded<D, PERIODIC>(xa, xb[r], H, M, rc2) && idq[r] >= 0 && (same ? idq[r] > id : idq[r] != id);
-            const unsigned long long word = __ballot(keep);
-            if (lane == 0 && word) atomicOr(&bitmap[(size_t)p * words_b + w0 + r * (kPmThreads / 64)], word);
-        }
-    }
+    const long w0 = ((long)(blockIdx.x % n_tb) * VHD_TILE_B + (threadIdx.x - lane)) / 64;  // the wave's word of r = 0
+    pair_tile_walk<D, PERIODIC>(ga + (size_t)o * D * (size_t)pitch_a, gb + (size_t)o * D * (size_t)pitch_b, ida, idb, pitch_a, pitch_b, n_a,
+                                n_tb, hm + (box_per_frame ? (o_base + o) * stride * 6 : 0),
+                                [&](int p, int r, int id, int idq, double r2) {  // ballot, one lane ORs a non-zero word
+                                    const unsigned long long word = __ballot(r2 < rc2 && idq >= 0 && (same ? idq > id : idq != id));
+                                    if (lane == 0 && word) atomicOr(&bitmap[(size_t)p * words_b + w0 + r * (kPmThreads / 64)], word);
+                                });
 }
 
 constexpr int kPlWords = 4;                          // words per thread of the two list kernels
@@ -186,13 +160,14 @@ __device__ __forceinline__ void pair_indicator(const E* __restrict__ x, long pit
     }
 }
 
-// grid pm_unit_grid(units = ceil(P / 2)).  pairs (P, 2) int32 atoms of the slab; hm: per box H[3] then M[3] of the staged
-// columns (BOX_CONST: one; BOX_FRAME: one per frame, loaded ONCE per thread before the loop over units).  Z: ceil(P / 2)
-// destination pairs of `pitch` rows.
-template <class E, int D, int BOX>
-__global__ void __launch_bounds__(kPmThreads)
-    k_pair_series(const E* __restrict__ x, long pitch, long T, int P, const int* __restrict__ pairs, const double* __restrict__ hm,
-                  double rc2, double* __restrict__ Z) {
+// The body of both series kernels.  grid pm_unit_grid(units = ceil(P / 2)).  rows (P, NAT) int32 atoms of the slab; hm: per box
+// H[3] then M[3] of the staged columns (BOX_CONST: one; BOX_FRAME: one per frame, loaded ONCE per thread before the loop over
+// units).  Z: ceil(P / 2) destination pairs of `pitch` rows.  row(atoms, tb, H, M, v): the values of one row in the thread's
+// frames; the second row's atoms are loaded after the first row's values are formed (three float64 atoms of D = 3 are 72
+// registers).
+template <class E, int D, int BOX, class Row>
+__device__ __forceinline__ void series_body(long pitch, long T, int P, const int* __restrict__ rows, int NAT, const double* __restrict__ hm,
+                                            double* __restrict__ Z, Row&& row) {
     constexpr bool kF32 = std::is_same_v<E, float>;
     constexpr int F = kPmFrames;
     const long tb = (long)blockIdx.x * (kPmThreads * F);
@@ -201,17 +176,27 @@ __global__ void __launch_bounds__(kPmThreads)
     double2* Zp = reinterpret_cast<double2*>(Z);
     const int n_units = (P + 1) / 2;
     for (int g = blockIdx.y; g < n_units; g += gridDim.y) {
-        double h0[F], h1[F] = {};
-        pair_indicator<E, D, BOX>(x, pitch, T, tb, pairs + 4L * g, H, M, rc2, h0);
-        if (2 * g + 1 < P) pair_indicator<E, D, BOX>(x, pitch, T, tb, pairs + 4L * g + 2, H, M, rc2, h1);  // (workgroup-uniform)
+        double v0[F], v1[F] = {};
+        row(rows + 2L * NAT * g, tb, H, M, v0);
+        if (2 * g + 1 < P) row(rows + 2L * NAT * g + NAT, tb, H, M, v1);  // (workgroup-uniform)
 #pragma unroll
         for (int f = 0; f < F; ++f) {
             const long t = pm_frame<kF32>(tb, f);
             if (t >= pitch) continue;
-            const double v[2] = {h0[f], h1[f]};
+            const double v[2] = {v0[f], v1[f]};
             pm_store_row<1>(Zp + (long)g * pitch, pitch, t, t < T, 1, v);
         }
     }
+}
+
+// series_body with pair_indicator as its row: the 0/1 indicator of the pairs (P, 2), one compare per frame
+template <class E, int D, int BOX>
+__global__ void __launch_bounds__(kPmThreads)
+    k_pair_series(const E* __restrict__ x, long pitch, long T, int P, const int* __restrict__ pairs, const double* __restrict__ hm,
+                  double rc2, double* __restrict__ Z) {
+    series_body<E, D, BOX>(pitch, T, P, pairs, 2, hm, Z, [&](const int* row, long tb, const auto& H, const auto& M, double (&h)[kPmFrames]) {
+        pair_indicator<E, D, BOX>(x, pitch, T, tb, row, H, M, rc2, h);
+    });
 }
 
 // the level of bond `row` (NAT atoms at a workgroup-uniform address) in the thread's frames: 0.0, 1.0, or `two` for level 2
@@ -237,33 +222,16 @@ __device__ __forceinline__ void bond_levels(const E* __restrict__ x, long pitch,
     }
 }
 
-// k_pair_series for bonds of NAT items and two levels (bond_math.hpp): the same grid, units, reads and stores; atoms
-// (P, NAT) int32; Z gets the LEVEL 0.0 / 1.0 / two per frame, two = 2.0 in front of k_pair_filter and 1.0 where no filter
-// follows (the break criterion is then the form criterion, level 1 does not occur and the level-2 frames are the series).
-// The second bond's atoms are loaded after the first bond's levels are formed: three float64 atoms of D = 3 are 72 registers.
+// series_body with bond_levels as its row, for bonds of NAT items and two levels (bond_math.hpp): atoms (P, NAT) int32; Z gets
+// the LEVEL 0.0 / 1.0 / two per frame, two = 2.0 in front of k_pair_filter and 1.0 where no filter follows (the break criterion
+// is then the form criterion, level 1 does not occur and the level-2 frames are the series).
 template <class E, int D, int BOX, int NAT>
 __global__ void __launch_bounds__(kPmThreads)
     k_bond_series(const E* __restrict__ x, long pitch, long T, int P, const int* __restrict__ atoms, const double* __restrict__ hm,
                   BondCuts k, double two, double* __restrict__ Z) {
-    constexpr bool kF32 = std::is_same_v<E, float>;
-    constexpr int F = kPmFrames;
-    const long tb = (long)blockIdx.x * (kPmThreads * F);
-    double H[F][3], M[F][3];
-    pair_boxes<kF32, D, BOX>(hm, T, tb, H, M);
-    double2* Zp = reinterpret_cast<double2*>(Z);
-    const int n_units = (P + 1) / 2;
-    for (int g = blockIdx.y; g < n_units; g += gridDim.y) {
-        double s0[F], s1[F] = {};
-        bond_levels<E, D, BOX, NAT>(x, pitch, T, tb, atoms + 2L * NAT * g, H, M, k, two, s0);
-        if (2 * g + 1 < P) bond_levels<E, D, BOX, NAT>(x, pitch, T, tb, atoms + 2L * NAT * g + NAT, H, M, k, two, s1);  // (uniform)
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            const long t = pm_frame<kF32>(tb, f);
-            if (t >= pitch) continue;
-            const double v[2] = {s0[f], s1[f]};
-            pm_store_row<1>(Zp + (long)g * pitch, pitch, t, t < T, 1, v);
-        }
-    }
+    series_body<E, D, BOX>(pitch, T, P, atoms, NAT, hm, Z, [&](const int* row, long tb, const auto& H, const auto& M, double (&s)[kPmFrames]) {
+        bond_levels<E, D, BOX, NAT>(x, pitch, T, tb, row, H, M, k, two, s);
+    });
 }
 
 // one series' filter state: the hysteresis carry and the h words before and at the word that is closed next
@@ -373,9 +341,7 @@ hipError_t launch_pair_find(const double* ga, const double* gb, const int* ida, 
                             long n_b, int D, long T, long stride, long o_base, int n_o, const double* hm, bool box_per_frame,
                             double rc2, bool same, unsigned long long* bitmap, hipStream_t st) {
     const long n_ta = (n_a + VHD_TILE_A - 1) / VHD_TILE_A, n_tb = (n_b + VHD_TILE_B - 1) / VHD_TILE_B;
-    if (D < 1 || D > 3 || n_a < 1 || n_b < 1 || n_a > pitch_a || n_b > pitch_b || pitch_a % VHD_TILE_A || pitch_b % VHD_TILE_B ||
-        n_ta * n_tb >= VHD_MAX_TILES || T < 1 || stride < 1 || o_base < 0 || n_o < 1 || n_o > 65535 ||
-        (o_base + n_o - 1) * stride >= T || !(rc2 > 0.0) || !bitmap)
+    if (!pair_tile_ok(pitch_a, pitch_b, n_a, n_b, D, T, stride, n_o) || o_base < 0 || (o_base + n_o - 1) * stride >= T || !(rc2 > 0.0) || !bitmap)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)(n_ta * n_tb), (unsigned)n_o);
     auto launch = [&](auto periodic) {
@@ -406,40 +372,36 @@ hipError_t launch_pair_list(const unsigned long long* bitmap, long n_words, long
     return hipGetLastError();
 }
 
+// what both series launchers check and switch on: launch(grid, E(), D, BOX) is the one launch line (ok: the caller's own checks)
+template <class Launch>
+static hipError_t launch_series(int n_cu, bool f32, long pitch, long T, long n_atoms, int D, long n_rows, const int* rows, const double* hm,
+                                bool box_per_frame, const double* Z, bool ok, Launch&& launch) {
+    if (!pm_slab_ok(pitch, T, n_atoms, D) || n_rows < 1 || n_rows >= (1L << 30) || !rows || !ok || !Z) return hipErrorInvalidValue;
+    const dim3 grid = pm_unit_grid(n_cu, pitch, (n_rows + 1) / 2);
+    const int box = !hm ? BOX_NONE : box_per_frame ? BOX_FRAME : BOX_CONST;
+    pm_dispatch(f32, D, [&](auto e, auto d) { pm_switch<BOX_NONE, BOX_FRAME>(box, [&](auto b) { launch(grid, e, d, b); }); });
+    return hipGetLastError();
+}
+
 hipError_t launch_pair_series(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, long n_pairs,
                               const int* pairs, const double* hm, bool box_per_frame, double rc2, double* Z, hipStream_t st) {
-    if (!pm_slab_ok(pitch, T, n_atoms, D) || n_pairs < 1 || n_pairs >= (1L << 30) || !pairs || !(rc2 > 0.0) || !Z)
-        return hipErrorInvalidValue;
-    const dim3 grid = pm_unit_grid(n_cu, pitch, (n_pairs + 1) / 2);
-    const int box = !hm ? BOX_NONE : box_per_frame ? BOX_FRAME : BOX_CONST;
-    pm_dispatch(f32, D, [&](auto e, auto d) {
-        pm_switch<BOX_NONE, BOX_FRAME>(box, [&](auto b) {
-            using E = decltype(e);
-            hipLaunchKernelGGL((k_pair_series<E, d(), decltype(b)::value>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T,
-                               (int)n_pairs, pairs, hm, rc2, Z);
-        });
+    return launch_series(n_cu, f32, pitch, T, n_atoms, D, n_pairs, pairs, hm, box_per_frame, Z, rc2 > 0.0, [&](dim3 grid, auto e, auto d, auto b) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((k_pair_series<E, d(), b()>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, (int)n_pairs, pairs, hm, rc2, Z);
     });
-    return hipGetLastError();
 }
 
 hipError_t launch_bond_series(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, long n_bonds, int n_at,
                               const int* atoms, const double* hm, bool box_per_frame, const BondCuts& k, double two, double* Z,
                               hipStream_t st) {
-    if (!pm_slab_ok(pitch, T, n_atoms, D) || n_bonds < 1 || n_bonds >= (1L << 30) || (n_at != 2 && n_at != 3) || !atoms ||
-        !(k.rc2 > 0.0) || !(k.rb2 >= k.rc2) || !(k.cb2 <= k.c2) || (two != 1.0 && two != 2.0) || !Z)
-        return hipErrorInvalidValue;
-    const dim3 grid = pm_unit_grid(n_cu, pitch, (n_bonds + 1) / 2);
-    const int box = !hm ? BOX_NONE : box_per_frame ? BOX_FRAME : BOX_CONST;
-    pm_dispatch(f32, D, [&](auto e, auto d) {
-        pm_switch<BOX_NONE, BOX_FRAME>(box, [&](auto b) {
-            pm_switch<2, 3>(n_at, [&](auto nat) {
-                using E = decltype(e);
-                hipLaunchKernelGGL((k_bond_series<E, d(), decltype(b)::value, decltype(nat)::value>), grid, dim3(kPmThreads), 0, st,
-                                   (const E*)x, pitch, T, (int)n_bonds, atoms, hm, k, two, Z);
-            });
+    const bool ok = (n_at == 2 || n_at == 3) && k.rc2 > 0.0 && k.rb2 >= k.rc2 && k.cb2 <= k.c2 && (two == 1.0 || two == 2.0);
+    return launch_series(n_cu, f32, pitch, T, n_atoms, D, n_bonds, atoms, hm, box_per_frame, Z, ok, [&](dim3 grid, auto e, auto d, auto b) {
+        pm_switch<2, 3>(n_at, [&](auto nat) {
+            using E = decltype(e);
+            hipLaunchKernelGGL((k_bond_series<E, d(), b(), nat()>), grid, dim3(kPmThreads), 0, st, (const E*)x, pitch, T, (int)n_bonds, atoms,
+                               hm, k, two, Z);
         });
     });
-    return hipGetLastError();
 }
 
 // the grid of the two kernels that walk a block a wave per destination pair: eight workgroups per CU, at most one wave per pair

@@ -14,11 +14,12 @@
 //                        GB[l][o][d][q] = x[stride o + tau_l, b_q, d], the item pitch padded to the pair kernel's tiles
 //                        (padding written as zeros; its ids are -1).  The element type, the index lists, the stride and
 //                        the lag's parity are settled here.
-//   k_vhd_pairs<D, PERIODIC>   the hot pass: a workgroup takes one (lag, origin, tile of a, tile of b).  A lane owns kVhdR
-//                        b-items, coordinates and ids in registers; the a-items are uniform over the workgroup and are
-//                        read from GA by scalar loads.  Per pair: the id compare, the difference, the image, r2; r2 <
-//                        e[B]: vh_bin and one LDS integer add; otherwise a register counter.  At the end the non-zero
-//                        bins and the waves' overflow sums go into the uint64 histogram by integer atomics.
+//   k_vhd_pairs<D, PERIODIC>   the hot pass: a workgroup takes one (lag, origin, tile of a, tile of b) and walks it with
+//                        pair_tile_walk (pair_tile.hpp, shared with k_pair_find of pair_lifetime.hip: the tiles, the lane's
+//                        b-items in registers, the a-items by scalar loads, the id rule's operands and r2).  The kernel
+//                        itself is the LDS setup, the visitor "r2 < e[B]: vh_bin and one LDS integer add; otherwise a register
+//                        counter", and the flush: the non-zero bins and the waves' overflow sums go into the uint64
+//                        histogram by integer atomics.
 //
 // Only integer adds: the same bits in any order, from run to run and for every chunk size.  No floating-point atomics.
 #include <hip/hip_runtime.h>
@@ -26,23 +27,10 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "pm_read.hpp"
-#include "ta_internal.hpp"
-#include "vanhove_distinct_math.hpp"
+#include "pair_tile.hpp"
 
 namespace ta {
 namespace {
-
-// Tiles.  A lane keeps kVhdR b-items (kVhdR (2 D + 1) VGPRs for D = 3: 28 of them; the bound is registers: twice as many
-// would cost occupancy without saving anything, the a-item's scalar loads are already shared by 4 pairs per lane), so a
-// workgroup's b-tile is 256 kVhdR = 1024 items; its a-tile is 256 items, bounded by nothing but the wish for enough
-// workgroups per origin at a few thousand items.  A workgroup counts at most kVhdTA kVhdTB = 2^18 pairs, and a bin of its
-// uint32 LDS histogram and a lane's overflow counter hold at most that: below 2^31 by construction.
-constexpr int kVhdR = 4;
-constexpr int kVhdTB = kPmThreads * kVhdR;
-constexpr int kVhdTA = 256;
-static_assert((long)kVhdTA * kVhdTB < (1L << 31), "a workgroup's pair count must stay below 2^31");
-static_assert(kVhdTA == VHD_TILE_A && kVhdTB == VHD_TILE_B, "ta_internal.hpp pads the item pitches to these tiles");
 
 // grid (item blocks of the pitch, origins (looped), slots): slot z < with_a is GA, the others the chunk's lags.  ids: the
 // padded index list of the slot's side (-1: padding, written as zeros).  A lagged row t + tau >= T is neither read nor
@@ -91,42 +79,16 @@ __global__ void __launch_bounds__(kPmThreads)
     for (int i = threadIdx.x; i < nb; i += kPmThreads) e[i] = e_g[i], hist[i] = 0;
     __syncthreads();
 
-    const int tile_a = blockIdx.x / n_tb, tile_b = blockIdx.x % n_tb;
-    double H[3] = {1.0, 1.0, 1.0}, M[3] = {1.0, 1.0, 1.0};
-    if constexpr (PERIODIC) {
-        const double* box = hm + (box_per_frame ? t * 6 : 0);
-#pragma unroll
-        for (int d = 0; d < D; ++d) H[d] = box[d], M[d] = box[3 + d];
-    }
-    // the lane's b-items at t + tau (coalesced: the item index is contiguous)
-    const double* gbo = gb + ((size_t)blockIdx.z * (size_t)n_orig + (size_t)o) * D * (size_t)pitch_b;
-    double xb[kVhdR][3];
-    int idq[kVhdR];
-#pragma unroll
-    for (int r = 0; r < kVhdR; ++r) {
-        const long q = (long)tile_b * kVhdTB + r * kPmThreads + threadIdx.x;  // (< pitch_b: a multiple of kVhdTB)
-        idq[r] = idb[q];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) xb[r][d] = d < D ? gbo[(size_t)d * pitch_b + q] : 0.0;
-    }
     const double e_top = e_g[B];
-    const double* gao = ga + (size_t)o * D * (size_t)pitch_a;
-    const int p0 = tile_a * kVhdTA, p1 = min(p0 + kVhdTA, n_a);
     unsigned over = 0;
-    for (int p = p0; p < p1; ++p) {  // (uniform: the a-item comes by scalar loads)
-        double xa[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-        for (int d = 0; d < D; ++d) xa[d] = gao[(size_t)d * pitch_a + p];
-        const int id = ida[p];
-#pragma unroll
-        for (int r = 0; r < kVhdR; ++r) {
-            const double r2 = vhd_r2<D, PERIODIC>(xa, xb[r], H, M);
-            if (idq[r] >= 0 && idq[r] != id) {
-                if (r2 < e_top) atomicAdd(&hist[vh_bin(r2, e, B, inv_dr)], 1u);
-                else ++over;
-            }
-        }
-    }
+    pair_tile_walk<D, PERIODIC>(ga + (size_t)o * D * (size_t)pitch_a, gb + ((size_t)blockIdx.z * (size_t)n_orig + (size_t)o) * D * (size_t)pitch_b,
+                                ida, idb, pitch_a, pitch_b, n_a, n_tb, hm + (box_per_frame ? t * 6 : 0),
+                                [&](int, int, int id, int idq, double r2) {  // bin or overflow
+                                    if (idq >= 0 && idq != id) {
+                                        if (r2 < e_top) atomicAdd(&hist[vh_bin(r2, e, B, inv_dr)], 1u);
+                                        else ++over;
+                                    }
+                                });
     __syncthreads();
     unsigned long long* row = counts + (size_t)blockIdx.z * nb;
     for (int i = threadIdx.x; i < B; i += kPmThreads) {
@@ -160,10 +122,9 @@ hipError_t launch_vhd_pairs(const double* ga, const double* gb, const int* ida, 
                             long n_b, int D, long T, long stride, long n_orig, long o0, int n_o, const int64_t* lags, int Lc,
                             const double* hm, bool box_per_frame, const double* e, int B, float inv_dr, unsigned long long* counts,
                             hipStream_t st) {
-    const long n_ta = (n_a + kVhdTA - 1) / kVhdTA, n_tb = (n_b + kVhdTB - 1) / kVhdTB;
-    if (D < 1 || D > 3 || n_a < 1 || n_b < 1 || n_a > pitch_a || n_b > pitch_b || pitch_a % kVhdTA || pitch_b % kVhdTB ||
-        n_ta * n_tb >= VHD_MAX_TILES || T < 1 || stride < 1 || n_orig < 1 || (n_orig - 1) * stride >= T || o0 < 0 || n_o < 1 ||
-        n_o > 65535 || o0 + n_o > n_orig || Lc < 1 || Lc > TA_VANHOVE_MAX_LAGS || B < 1 || B > TA_VANHOVE_MAX_BINS)
+    const long n_ta = (n_a + VHD_TILE_A - 1) / VHD_TILE_A, n_tb = (n_b + VHD_TILE_B - 1) / VHD_TILE_B;
+    if (!pair_tile_ok(pitch_a, pitch_b, n_a, n_b, D, T, stride, n_o) || n_orig < 1 || (n_orig - 1) * stride >= T || o0 < 0 ||
+        o0 + n_o > n_orig || Lc < 1 || Lc > TA_VANHOVE_MAX_LAGS || B < 1 || B > TA_VANHOVE_MAX_BINS)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)(n_ta * n_tb), (unsigned)n_o, (unsigned)Lc);
     const size_t lds = (sizeof(double) + sizeof(unsigned)) * (size_t)(B + 1);
