@@ -235,10 +235,10 @@ def water(n_mol=24, n_frames=40, seed=3, box=8.0):
     return u, x, ox, hy, dh
 
 
-def test_hydrogen_bond_lifetime_on_water():
+def hydrogen_bond_lifetime_on_water(**place):
     u, x, ox, hy, dh = water()
     n_frames = x.shape[0]
-    kw = dict(d_a_cutoff=3.2, d_h_a_angle_cutoff=150.0, d_a_break=3.6, angle_break=130.0, intermittency=1, fft=False, device="cpu")
+    kw = dict(d_a_cutoff=3.2, d_h_a_angle_cutoff=150.0, d_a_break=3.6, angle_break=130.0, intermittency=1, fft=False, **place)
     hb = HydrogenBondLifetime(u.atoms[ox], u.atoms[hy], u.atoms[ox], donor_hydrogen_pairs=dh, **kw).run()
     r = hb.results
     # both directions of every found pair, each with the donor's two hydrogens
@@ -267,6 +267,10 @@ def test_hydrogen_bond_lifetime_on_water():
     assert set(one.bonds[:, 0]) <= set(d_) and set(one.bonds[:, 2]) <= set(a_)
     s1 = ref.levels(x, one.bonds, box, 3.2, 3.6, hb.cos_cut * hb.cos_cut, hb.cos_break * hb.cos_break, margin=1e-9)
     assert np.array_equal(one.n_bonded, ref.filtered(s1, 1).sum(axis=0))
+
+
+def test_hydrogen_bond_lifetime_on_water():
+    hydrogen_bond_lifetime_on_water(device="cpu")
 
 
 def test_hydrogen_bond_lifetime_refusals():
@@ -300,14 +304,13 @@ def test_hydrogen_bond_lifetime_refusals():
         PairLifetime(u.atoms, r_cut=2.0, intermittency=-1)
 
 
-@pytest.mark.parametrize("kind", ["same", "explicit"])
-def test_pair_lifetime_with_filters(kind):
+def pair_lifetime_with_filters(kind, **place):
     """PairLifetime(r_break=, intermittency=) against the reference on pair_ref's walks (searched and explicit lists); with the
     defaults the results are those of the unfiltered call, bit for bit"""
     case = pair_ref.case(40, 60, 3, kind, True, 1)
     x, a, b, dims, axes, pairs, sums = case
     u = ArrayUniverse(positions=x, dimensions=dims)
-    common = dict(r_cut=0.75, fft=False, dim_type=DIM_TYPES[3], device="cpu", **({} if kind == "same" else dict(pairs=pairs)))
+    common = dict(r_cut=0.75, fft=False, dim_type=DIM_TYPES[3], **place, **({} if kind == "same" else dict(pairs=pairs)))
     r = PairLifetime(u.atoms, r_break=1.0, intermittency=2, **common).run().results
     s = ref.levels(x, r.pairs, dims[:, :3], 0.75, 1.0)
     g = ref.filtered(s, 2)
@@ -322,3 +325,8 @@ def test_pair_lifetime_with_filters(kind):
     assert np.array_equal(plain.n_bonded, want[2]) and np.array_equal(plain.run_lengths, want[1])
     for key in ("pairs", "n_bonded", "run_lengths", "intermittent", "continuous"):
         assert np.array_equal(getattr(plain, key), getattr(again, key), equal_nan=True)
+
+
+@pytest.mark.parametrize("kind", ["same", "explicit"])
+def test_pair_lifetime_with_filters(kind):
+    pair_lifetime_with_filters(kind, device="cpu")

@@ -214,14 +214,16 @@ def universe(T=50, A=12, box=None, seed=11):
     return ArrayUniverse(positions=x, velocities=v, masses=m, charges=q, **kw), x, v, m, q
 
 
-def test_class_normalisation_and_weights():
+def class_normalisation_and_weights(**place):
+    """the body of test_class_normalisation_and_weights under the placement keywords `place` (test_classes_gpu.py runs it
+    on the GPU)"""
     T, A = 50, 12
     u, x, v, m, q = universe(T, A)
     k = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.6, 0.8, 0.0]])
     x32, v32 = x.astype(np.float32).astype(np.float64), v.astype(np.float32).astype(np.float64)
     lags = ref.lag_sample(T)
     for weights, w in (("mass", m), ("charge", q), (None, None), (np.arange(A) + 1.0, np.arange(A) + 1.0)):
-        r = CurrentCorrelation(u.atoms, k, weights=weights, device="cpu", fft=False).run()
+        r = CurrentCorrelation(u.atoms, k, weights=weights, fft=False, **place).run()
         res = r.results
         assert res.kvectors.shape == (3, 3) and np.allclose(res.k, 1.0) and res.shell is None and res.cl_shell is None
         assert res.current.shape == (3, T, 3, 2) and res.cl.shape == (T, 3) and res.ct.shape == (T, 3)
@@ -232,18 +234,22 @@ def test_class_normalisation_and_weights():
         scale = float(np.max(np.abs(lon + 2 * tr)))
         assert np.max(np.abs(res.cl[lags].T * A - lon)) <= 1e-10 * scale  # cl = long / N
         assert np.max(np.abs(res.ct[lags].T * A - tr)) <= 1e-10 * scale
-    fast = CurrentCorrelation(u.atoms, k, device="cpu", fft=True).run().results
-    slow = CurrentCorrelation(u.atoms, k, device="cpu", fft=False).run().results
+    fast = CurrentCorrelation(u.atoms, k, fft=True, **place).run().results
+    slow = CurrentCorrelation(u.atoms, k, fft=False, **place).run().results
     assert np.max(np.abs(fast.cl - slow.cl)) <= 1e-10 * np.max(np.abs(slow.cl + 2 * slow.ct))
-    planar = CurrentCorrelation(u.atoms, k[:, :2], dim_type="xy", weights=None, device="cpu").run().results
+    planar = CurrentCorrelation(u.atoms, k[:, :2], dim_type="xy", weights=None, **place).run().results
     assert planar.current.shape == (3, T, 2, 2)
-    line = CurrentCorrelation(u.atoms, [[1.5]], dim_type="z", weights=None, device="cpu").run().results
+    line = CurrentCorrelation(u.atoms, [[1.5]], dim_type="z", weights=None, **place).run().results
     assert not np.any(line.ct) and np.any(line.cl)
 
 
-def test_class_shell_means_and_volume():
+def test_class_normalisation_and_weights():
+    class_normalisation_and_weights(device="cpu")
+
+
+def class_shell_means_and_volume(**place):
     u, *_ = universe(box=[15, 15, 15, 90, 90, 90])
-    sh = CurrentCorrelation(u.atoms, q=[0.5, 0.9], dq=0.2, max_vectors=4, device="cpu").run().results
+    sh = CurrentCorrelation(u.atoms, q=[0.5, 0.9], dq=0.2, max_vectors=4, **place).run().results
     assert sh.volume == 15.0 ** 3 and set(sh.shell) == {0, 1}
     for s in (0, 1):
         pick = sh.shell == s
@@ -252,7 +258,11 @@ def test_class_shell_means_and_volume():
         assert np.isclose(sh.k_shell[s], sh.k[pick].mean())
 
 
-def test_class_wrapped_positions_need_no_unwrap():
+def test_class_shell_means_and_volume():
+    class_shell_means_and_volume(device="cpu")
+
+
+def class_wrapped_positions_need_no_unwrap(**place):
     """wavevectors of the box: the current of the wrapped positions is that of the unwrapped walk; unwrap=True gives it too"""
     rng = np.random.default_rng(5)
     box = np.array([16.0, 12.0, 20.0])
@@ -261,7 +271,7 @@ def test_class_wrapped_positions_need_no_unwrap():
     v = np.rint(rng.normal(scale=512, size=walk.shape)) / 1024.0
     dims = [*box, 90, 90, 90]
     runs = [CurrentCorrelation(ArrayUniverse(positions=p, velocities=v, dimensions=dims).atoms, q=[0.9, 1.6], dq=0.4, max_vectors=5,
-                               weights=None, device="cpu", **kw).run()
+                               weights=None, **place, **kw).run()
             for p, kw in ((walk, {}), (wrapped, {}), (wrapped, {"unwrap": True}))]
     k = runs[0].results.kvectors
     assert k.shape[0] >= 6
@@ -272,6 +282,10 @@ def test_class_wrapped_positions_need_no_unwrap():
         assert np.all(np.max(np.abs(runs[0].results.current - other.results.current), axis=(0, 1, 3)) <= bar)
         assert np.max(np.abs(runs[0].results.cl - other.results.cl)) <= 1e-10 * scale
         assert np.max(np.abs(runs[0].results.ct - other.results.ct)) <= 1e-10 * scale
+
+
+def test_class_wrapped_positions_need_no_unwrap():
+    class_wrapped_positions_need_no_unwrap(device="cpu")
 
 
 def test_class_spectrum_of_a_pure_cosine():
@@ -323,3 +337,43 @@ def test_class_refusals():
     no_vel = ArrayUniverse(positions=np.zeros((5, 2, 3)))
     with pytest.raises(Exception, match="velocities"):
         CurrentCorrelation(no_vel.atoms, k, weights=None, device="cpu").run()
+
+
+# ---- the class on several devices and ranks: devices=[...], distributed=True ------------------------------------------------
+PLACED_T = 65
+INTEGER_KEYS = ()  # (nothing here is an integer)
+
+
+def placed_results(A, **place):
+    """CurrentCorrelation on kcurrent_ref.case(65, A, 3, 3) -- with its non-uniform weights, so a block that took the wrong
+    slice of them shows -- with fft True and False under the placement keywords `place`: {name: array} (placement.py)"""
+    from placement import record_ranges
+
+    x, v, w, k = ref.case(PLACED_T, A, 3, 3)[:4]
+    u = ArrayUniverse(positions=x, velocities=v)
+    out = {}
+    for fft in (1, 0):
+        r = CurrentCorrelation(u.atoms, k, weights=w, fft=bool(fft), **place).run().results
+        out[f"cur_{fft}"], out[f"cl_{fft}"], out[f"ct_{fft}"] = r.current, r.cl, r.ct
+        record_ranges(out, r)
+    return out
+
+
+def check_placed(out, A, what):
+    """placed_results against the reference over ALL atoms at test_walks_against_reference's bars (cl and ct are long / N
+    and trans / N)"""
+    case = ref.case(PLACED_T, A, 3, 3)
+    assert A == 1 or np.unique(case[2]).size > 1, "the weights must differ between the atoms"
+    for fft in (1, 0):
+        ref.assert_kcurrent(out[f"cur_{fft}"], out[f"cl_{fft}"].T * A, out[f"ct_{fft}"].T * A, case, what=f"{what} fft={fft}")
+
+
+@pytest.mark.parametrize("A", [33, 1])
+def test_class_distributed_two_gloo_ranks_cpu_backend(tmp_path, A):
+    """A = 33: the ranks hold 16 and 17 atoms, each with its own slice of the weights; A = 1: rank 0 holds no atom and
+    contributes zeros (_no_moments).  The currents are summed over the ranks BEFORE the projections are correlated."""
+    import sys
+
+    import placement
+
+    placement.check_ranks(sys.modules[__name__], A, 2, "cpu", tmp_path, dict(device="cpu"))

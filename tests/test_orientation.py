@@ -267,13 +267,15 @@ def test_each_output_alone_equals_all_together():
 
 
 # ---- the class -----------------------------------------------------------------------------------------------------
-def test_class_results_and_normalisation():
+def class_results_and_normalisation(**place):
+    """the class on the wrapped weighted bisectors under the placement keywords `place`; returns what the CPU test compares
+    with the raw call on the CPU backend"""
     T, N = 50, 7
     x, idx, w, r = ref.case(T, N, "bisector", seed=8, weighted=True)
     box = np.tile(np.asarray(ORTHO), (T, 1))
     wrapped = ref.wrap(x + 36.0, ORTHO)
     u = ArrayUniverse(positions=wrapped.astype(np.float32), dimensions=ORTHO, dt=2.0)
-    a = OrientationalCorrelation(u.atoms, idx, mode="bisector", weights=w, device="cpu").run()
+    a = OrientationalCorrelation(u.atoms, idx, mode="bisector", weights=w, **place).run()
     lags, c1, c2, total = r[:4]
     res = a.results
     assert res.c1.shape == res.c2.shape == res.total_acf.shape == (T,) and res.total.shape == (T, 3)
@@ -285,15 +287,69 @@ def test_class_results_and_normalisation():
     assert abs(res.kirkwood - np.mean((res.total ** 2).sum(axis=1)) / (w ** 2).sum()) <= 1e-12
     assert np.array_equal(a.lag_times(), 2.0 * np.arange(T))
     assert a._ctx.shape == (T, x.shape[1], 3)
+    # minimum_image=False on the wrapped data differs; on the unwrapped data it agrees with the boxed run
+    off = OrientationalCorrelation(ArrayUniverse(positions=x.astype(np.float32)).atoms, idx, mode="bisector", weights=w,
+                                   minimum_image=False, collective=False, **place).run().results
+    assert off.total_acf is None and np.abs(off.c1 - res.c1).max() <= 1e-10
+    with pytest.raises(ValueError, match="minimum_image=True needs the periodic box"):
+        OrientationalCorrelation(ArrayUniverse(positions=x.astype(np.float32)).atoms, idx, mode="bisector", **place).run()
+    return wrapped, idx, box, w, N, res
+
+
+def test_class_results_and_normalisation():
+    wrapped, idx, box, w, N, res = class_results_and_normalisation(device="cpu")
     # the raw call with the recorded boxes gives the class's sums
     raw = orient(wrapped, idx, "bisector", dtype=np.float32, dimensions=box, weights=w)
     assert np.array_equal(raw[0] / N, res.c1) and np.array_equal(1.5 * raw[1] / N, res.c2)
-    # minimum_image=False on the wrapped data differs; on the unwrapped data it agrees with the boxed run
-    off = OrientationalCorrelation(ArrayUniverse(positions=x.astype(np.float32)).atoms, idx, mode="bisector", weights=w,
-                                   minimum_image=False, collective=False, device="cpu").run().results
-    assert off.total_acf is None and np.abs(off.c1 - res.c1).max() <= 1e-10
-    with pytest.raises(ValueError, match="minimum_image=True needs the periodic box"):
-        OrientationalCorrelation(ArrayUniverse(positions=x.astype(np.float32)).atoms, idx, mode="bisector", device="cpu").run()
+
+
+def class_sums(r, N):
+    """the class's results as the library's four outputs (c1 = sum / N, c2 = 1.5 sum / N): what orient_ref.assert_orient takes"""
+    return r.c1 * N, r.c2 * N / 1.5, r.total, r.total_acf
+
+
+def class_on_walks(mode, weighted, **place):
+    """OrientationalCorrelation without the image on orient_ref.case(65, 9, mode, n_mol=6) -- nine vectors on six molecules,
+    exact in float32 -- with fft True and False, at test_walks_against_reference's bars"""
+    x, idx, w, r = ref.case(65, 9, mode, weighted=weighted, n_mol=6)
+    u = ArrayUniverse(positions=x)
+    for fft in (True, False):
+        got = OrientationalCorrelation(u.atoms, idx, mode=mode, weights=w, fft=fft, minimum_image=False, **place).run().results
+        ref.assert_orient(class_sums(got, 9), r, what=f"class {mode} w={weighted} fft={fft}")
+
+
+def class_on_wrapped_molecules(mode, dims, moving, **place):
+    """test_wrapped_molecules through the class (minimum_image=True on the recorded boxes): against the reference of the
+    positions the trajectory holds (float32), and in the constant dyadic box against the unwrapped molecules at that test's bar"""
+    T, N = 60, 11
+    x, idx, _, want = ref.case(T, N, mode, seed=4)
+    box = ref.box_frames(dims, T, moving)
+    held = ref.near_corner_wrapped(x, idx, box).astype(np.float32).astype(np.float64)
+    u = ArrayUniverse(positions=held, dimensions=box if moving else list(dims))
+    r = OrientationalCorrelation(u.atoms, idx, mode=mode, **place).run().results
+    got = class_sums(r, N)
+    ref.assert_orient(got, ref.reference(held, idx, mode, box), what=f"class wrapped {mode}, own reference")
+    if dims is ORTHO and not moving:  # (the dyadic box: the wrapped positions are exact in float32, as the unwrapped ones)
+        lags, c1, c2, total = want[:4]
+        for g, w_, f in ((got[0], c1, 1.0), (got[1], c2, 1.5)):
+            err = float(np.max(np.abs(f * g[lags].astype(LD) - w_))) / float(np.max(np.abs(w_)))
+            print(f"    class wrapped {mode}: {err:.3e} from the unwrapped molecules' function")
+            assert err <= 1e-10
+    bare = OrientationalCorrelation(ArrayUniverse(positions=held).atoms, idx, mode=mode, minimum_image=False, **place).run().results
+    assert np.abs(bare.total - r.total).max() > 0.1  # (without the box the cut vectors point elsewhere)
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["plain", "weighted"])
+@pytest.mark.parametrize("mode", ref.MODES)
+def test_class_on_walks(mode, weighted):
+    class_on_walks(mode, weighted, device="cpu")
+
+
+@pytest.mark.parametrize("mode", ref.MODES)
+@pytest.mark.parametrize("dims,moving", [(ORTHO, False), (ORTHO, True), (TRIC, False), (TRIC, True)],
+                         ids=["ortho-constant", "ortho-per-frame", "tric-constant", "tric-per-frame"])
+def test_class_on_wrapped_molecules(dims, moving, mode):
+    class_on_wrapped_molecules(mode, dims, moving, device="cpu")
 
 
 def test_relaxation_times_on_an_exponential():

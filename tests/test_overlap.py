@@ -191,14 +191,14 @@ def test_output_bound():
 
 
 # ---- the class ---------------------------------------------------------------------------------------------------------
-def test_class_against_reference():
+def class_against_reference(**place):
     for D, dim_type in ((3, "xyz"), (2, "xy"), (1, "x")):
         x3 = ref.walk(200, 13, 3, 1)
         x = x3[:, :, :D]
         lags = ref.lag_sample(200)
         Q, _ = ref.reference(x, lags, ref.CUTOFFS)
         q, chi4 = ref.moments(Q, lags, 13)
-        r = DynamicSusceptibility(ArrayUniverse(positions=x3).atoms, lags, cutoff=ref.CUTOFFS, dim_type=dim_type, device="cpu").run().results
+        r = DynamicSusceptibility(ArrayUniverse(positions=x3).atoms, lags, cutoff=ref.CUTOFFS, dim_type=dim_type, **place).run().results
         ref.assert_q(r.overlap_by_origin, Q, lags, what=f"class {dim_type}")
         assert np.array_equal(r.lags, lags) and np.array_equal(r.times, lags * 1.0) and np.array_equal(r.cutoffs, ref.CUTOFFS)
         assert np.array_equal(r.n_origins, 200 - lags)
@@ -212,9 +212,13 @@ def test_class_against_reference():
         assert float(chi4[:, ok].max()) > 0
 
 
-def test_class_scalar_cutoff_and_default_lags():
+def test_class_against_reference():
+    class_against_reference(device="cpu")
+
+
+def class_scalar_cutoff_and_default_lags(**place):
     x, _, _, _, _ = ref.case(200, 13, 3)
-    r = DynamicSusceptibility(ArrayUniverse(positions=x).atoms, cutoff=1.5, device="cpu").run().results
+    r = DynamicSusceptibility(ArrayUniverse(positions=x).atoms, cutoff=1.5, **place).run().results
     lags = log_lags(200)
     assert np.array_equal(r.lags, lags)
     assert r.overlap_by_origin.shape == (1, len(lags), 200) and r.q.shape == r.chi4.shape == (1, len(lags))
@@ -222,18 +226,26 @@ def test_class_scalar_cutoff_and_default_lags():
     ref.assert_q(r.overlap_by_origin, Q, lags, what="scalar cutoff")
 
 
-def test_class_float32_staging_is_the_same():
+def test_class_scalar_cutoff_and_default_lags():
+    class_scalar_cutoff_and_default_lags(device="cpu")
+
+
+def class_float32_staging_is_the_same(**place):
     x, lags, Q, _, _ = ref.case(65, 13, 3)
     u = ArrayUniverse(positions=x.astype(np.float32))
-    r = DynamicSusceptibility(u.atoms, lags, cutoff=ref.CUTOFFS, device="cpu").run().results
+    r = DynamicSusceptibility(u.atoms, lags, cutoff=ref.CUTOFFS, **place).run().results
     ref.assert_q(r.overlap_by_origin, Q, lags, what="float32 staging")
 
 
-def test_unwrap_gives_the_unwrapped_walk():
+def test_class_float32_staging_is_the_same():
+    class_float32_staging_is_the_same(device="cpu")
+
+
+def unwrap_gives_the_unwrapped_walk(**place):
     walk, wrapped, box = wrapped_walk()
     dims = [*box, 90, 90, 90]
     lags = ref.lag_sample(120)
-    kw = dict(cutoff=(0.5, 1.5, 4.0), device="cpu")
+    kw = dict(cutoff=(0.5, 1.5, 4.0), **place)
     a = DynamicSusceptibility(ArrayUniverse(positions=walk).atoms, lags, **kw).run().results
     b = DynamicSusceptibility(ArrayUniverse(positions=wrapped, dimensions=dims).atoms, lags, unwrap=True, **kw).run().results
     w = DynamicSusceptibility(ArrayUniverse(positions=wrapped, dimensions=dims).atoms, lags, **kw).run().results
@@ -243,14 +255,18 @@ def test_unwrap_gives_the_unwrapped_walk():
     assert np.array_equal(a.chi4, b.chi4, equal_nan=True)
 
 
-def test_compounds_with_dyadic_weights():
+def test_unwrap_gives_the_unwrapped_walk():
+    unwrap_gives_the_unwrapped_walk(device="cpu")
+
+
+def compounds_with_dyadic_weights(**place):
     """16 atoms of equal mass in molecules of 4: the weights 1/4 and 1/16 are dyadic, so the centres (and the centres in the
     barycentric frame) stay on a grid and Q is exact; N is the number of compounds"""
     x, lags, _, _, _ = ref.case(65, 16, 3)
     mol = np.arange(16) // 4
     u = ArrayUniverse(positions=x, masses=np.full(16, 2.0))
     centres = x.reshape(65, 4, 4, 3).mean(axis=2)
-    kw = dict(cutoff=ref.CUTOFFS, device="cpu")
+    kw = dict(cutoff=ref.CUTOFFS, **place)
     r = DynamicSusceptibility(u.atoms, lags, compound=mol, **kw).run().results
     Q, _ = ref.reference(centres, lags, ref.CUTOFFS)
     ref.assert_q(r.overlap_by_origin, Q, lags, what="compound")
@@ -259,6 +275,10 @@ def test_compounds_with_dyadic_weights():
     r = DynamicSusceptibility(u.atoms, lags, compound=mol, reference_frame="barycentric", **kw).run().results
     Q, _ = ref.reference(centres - x.mean(axis=1)[:, None, :], lags, ref.CUTOFFS)
     ref.assert_q(r.overlap_by_origin, Q, lags, what="barycentric")
+
+
+def test_compounds_with_dyadic_weights():
+    compounds_with_dyadic_weights(device="cpu")
 
 
 def test_cumulative_counts_of_vanhove_self():
@@ -296,3 +316,48 @@ def test_class_refusals():
         DynamicSusceptibility(u.atoms, lags, cutoff=1.0, unwrap=True, device="cpu").run()
     doc = DynamicSusceptibility.__doc__
     assert "ensemble-dependent" in doc and "origins are correlated" in doc
+
+
+# ---- the class on several devices and ranks: devices=[...], distributed=True ------------------------------------------------
+PLACED_T = 65
+INTEGER_KEYS = ("Q",)
+
+
+def placed_results(A, **place):
+    """DynamicSusceptibility on overlap_ref.case(65, A, 3) under the placement keywords `place`: {name: array} (placement.py)"""
+    from placement import record_ranges
+
+    x, lags, _, _, _ = ref.case(PLACED_T, A, 3)
+    r = DynamicSusceptibility(ArrayUniverse(positions=x).atoms, lags, cutoff=ref.CUTOFFS, **place).run().results
+    out = {"Q": r.overlap_by_origin, "q": r.q, "chi4": r.chi4}
+    record_ranges(out, r)
+    return out
+
+
+def check_placed(out, A, what):
+    """placed_results against the reference over ALL atoms: Q EQUAL, q and chi4 at test_class_against_reference's bar.  The
+    blocks' Q are added before the variance is taken: the blocks' own variances would not add up to chi4 (asserted for
+    devices=[0, 0] in test_overlap_shapes.py)"""
+    x, lags, Q, q, chi4 = ref.case(PLACED_T, A, 3)
+    ref.assert_q(out["Q"], Q, lags, what=what)
+    ok = (PLACED_T - lags) >= 2
+    err_q = float(np.max(np.abs(out["q"] - q) / np.where(q > 0, q, 1)))
+    err_c = float(np.max(np.abs(out["chi4"][:, ok] - chi4[:, ok]) / np.where(chi4[:, ok] > 0, chi4[:, ok], 1)))
+    print(f"    {what}: q {err_q:.2e}, chi4 {err_c:.2e} relative")
+    assert err_q <= 1e-12 and err_c <= 1e-12 and np.all(np.isnan(out["chi4"][:, ~ok]))
+
+
+@pytest.mark.parametrize("A", [13, 1])
+def test_class_distributed_two_gloo_ranks_cpu_backend(tmp_path, A):
+    """A = 13: the ranks hold 6 and 7 atoms; A = 1: rank 0 holds no atom and contributes zeros (_no_moments).  The int64 Q
+    travels through the all-reduce as float64 and comes back as the same integers, and the variance is taken of the sum."""
+    import sys
+
+    import placement
+
+    placement.check_ranks(sys.modules[__name__], A, 2, "cpu", tmp_path, dict(device="cpu"))
+    if A > 1:
+        x, lags, _, _, chi4 = ref.case(PLACED_T, A, 3)
+        ok = (PLACED_T - lags) >= 2
+        halves = [ref.moments(ref.reference(x[:, lo:hi], lags, ref.CUTOFFS)[0], lags, A)[1] for lo, hi in ((0, A // 2), (A // 2, A))]
+        assert float(np.max(np.abs((halves[0] + halves[1])[:, ok] - chi4[:, ok]))) > 1e-3  # (what summing variances would give)

@@ -36,10 +36,11 @@ def universe(case):
 
 
 def run_class(case, kind, stride, fft, **kw):
+    """PairLifetime on the case; kw: the class's other keywords, the placement among them (default device="cpu")"""
     x, a, b, dims, axes, pairs, sums = case
     u = universe(case)
     D = x.shape[2]
-    common = dict(r_cut=ref.R_CUT, periodic=dims is not None, fft=fft, dim_type=DIM_TYPES[D], device="cpu", **kw)
+    common = dict(r_cut=ref.R_CUT, periodic=dims is not None, fft=fft, dim_type=DIM_TYPES[D], **{"device": "cpu", **kw})
     if kind == "same":
         return PairLifetime(u.atoms, search_stride=stride, **common).run()
     if kind == "disjoint":
@@ -47,9 +48,7 @@ def run_class(case, kind, stride, fft, **kw):
     return PairLifetime(u.atoms, pairs=pairs, **common).run()
 
 
-@pytest.mark.parametrize("D", [1, 2, 3])
-@pytest.mark.parametrize("kind", ["same", "disjoint", "explicit"])
-def test_class_against_reference(kind, D):
+def class_against_reference(kind, D, **place):
     """T = 40, A = 60: no box, the constant box and per-frame boxes, search strides 1 and 3; exact with fft=False, the
     project's 1e-10 of the scale (ci[0]) with fft=True"""
     for boxed, stride in itertools.product((False, True, "frames"), (1, 3)):
@@ -58,13 +57,13 @@ def test_class_against_reference(kind, D):
         what = (kind, D, boxed, stride)
         if sums is None or not sums[2].any():  # (no pair ever bonded: D = 3 walks without a box spread over 50 length units)
             with pytest.warns(UserWarning, match="no pair is bonded"):
-                r = run_class(case, kind, stride, False).results
+                r = run_class(case, kind, stride, False, **place).results
             assert np.array_equal(r.pairs, pairs) and np.all(np.isnan(r.intermittent)) and np.all(np.isnan(r.continuous))
             assert not r.n_bonded.any() and not r.run_lengths.any() and np.isnan(r.mean_run)
             continue
         ci, runs, nb, cc = sums
         want_i, want_c = ref.correlations(ci, nb, cc)
-        r = run_class(case, kind, stride, False).results
+        r = run_class(case, kind, stride, False, **place).results
         assert np.array_equal(r.pairs, pairs), what
         assert r.n_bonded.dtype == np.int64 and np.array_equal(r.n_bonded, nb), what
         assert r.run_lengths.dtype == np.int64 and r.run_lengths.shape == (T + 1,) and np.array_equal(r.run_lengths, runs), what
@@ -83,13 +82,19 @@ def test_class_against_reference(kind, D):
         assert np.all(r.continuous[ok] <= r.intermittent[ok])
         assert (np.arange(T + 1) * r.run_lengths).sum() == r.n_bonded.sum()
         # fft=True: the same integers for runs and counts, the lag sums within 1e-10 of ci[0]
-        f = run_class(case, kind, stride, True).results
+        f = run_class(case, kind, stride, True, **place).results
         assert np.array_equal(f.pairs, pairs) and np.array_equal(f.n_bonded, nb) and np.array_equal(f.run_lengths, runs)
         n0 = np.cumsum(nb)[::-1].astype(np.float64)
         err = float(np.max(np.abs(f.intermittent[ok] * n0[ok] - ci[ok])))
         print(f"    {what}: fft max |ci - exact| = {err:.3e}, bound {1e-10 * ci[0]:.3e}")
         assert err <= 1e-10 * ci[0]
         assert np.array_equal(f.continuous, want_c, equal_nan=True)
+
+
+@pytest.mark.parametrize("D", [1, 2, 3])
+@pytest.mark.parametrize("kind", ["same", "disjoint", "explicit"])
+def test_class_against_reference(kind, D):
+    class_against_reference(kind, D, device="cpu")
 
 
 @pytest.mark.parametrize("D", [1, 2, 3])
@@ -228,23 +233,27 @@ def test_class_refusals():
     assert r.pairs.tolist() == [[8, 1], [4, 5]]
 
 
-def test_class_without_any_bond_gives_nan_with_a_warning():
+def class_without_any_bond_gives_nan_with_a_warning(**place):
     x = np.zeros((4, 3, 3))
     x[:, :, 0] = 100.0 * np.arange(3)[None, :]
     with pytest.warns(UserWarning, match="no pair is bonded in any frame"):
-        r = PairLifetime(ArrayUniverse(positions=x).atoms, r_cut=1.0, periodic=False, device="cpu").run().results
+        r = PairLifetime(ArrayUniverse(positions=x).atoms, r_cut=1.0, periodic=False, **place).run().results
     assert r.pairs.shape == (0, 2) and np.all(np.isnan(r.intermittent)) and np.all(np.isnan(r.continuous))
     assert np.isnan(r.tau_intermittent) and np.isnan(r.tau_continuous) and np.isnan(r.mean_run) and r.coordination == 0.0
     # an explicit list that is never bonded: the same
     with pytest.warns(UserWarning, match="no pair is bonded in any frame"):
-        r = PairLifetime(ArrayUniverse(positions=x).atoms, r_cut=1.0, pairs=[[0, 2]], periodic=False, device="cpu").run().results
+        r = PairLifetime(ArrayUniverse(positions=x).atoms, r_cut=1.0, pairs=[[0, 2]], periodic=False, **place).run().results
     assert r.pairs.tolist() == [[0, 2]] and np.all(np.isnan(r.continuous)) and not r.run_lengths.any()
     with warnings.catch_warnings():
         warnings.simplefilter("error")
         x[:, 1, 0] = 0.5
-        r = PairLifetime(ArrayUniverse(positions=x).atoms, r_cut=1.0, periodic=False, device="cpu").run().results
+        r = PairLifetime(ArrayUniverse(positions=x).atoms, r_cut=1.0, periodic=False, **place).run().results
     assert r.pairs.tolist() == [[0, 1]] and r.intermittent.tolist() == [1.0] * 4 and r.run_lengths.tolist() == [0, 0, 0, 0, 1]
     assert r.mean_run == 4.0 and r.tau_continuous == 3.0
+
+
+def test_class_without_any_bond_gives_nan_with_a_warning():
+    class_without_any_bond_gives_nan_with_a_warning(device="cpu")
 
 
 # ---- the C-ABI's argument checks ------------------------------------------------------------------------------------------

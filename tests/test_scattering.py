@@ -122,12 +122,14 @@ def wrapped_walk():
     return walk, walk - np.floor(walk / box) * box, box
 
 
-def test_wrapped_positions_need_no_unwrap():
+def wrapped_positions_need_no_unwrap(**place):
+    """the body of test_wrapped_positions_need_no_unwrap under the placement keywords `place` (test_classes_gpu.py runs it
+    on the GPU)"""
     walk, wrapped, box = wrapped_walk()
     dims = [*box, 90, 90, 90]
     N = walk.shape[1]
     runs = [IntermediateScattering(ArrayUniverse(positions=p, dimensions=dims).atoms, q=[0.9, 1.6], dq=0.4, max_vectors=5,
-                                   device="cpu").run() for p in (walk, wrapped)]
+                                   **place).run() for p in (walk, wrapped)]
     k = runs[0].results.kvectors
     assert np.array_equal(k, runs[1].results.kvectors) and k.shape[0] >= 6
     m = k * box / TWO_PI
@@ -137,11 +139,18 @@ def test_wrapped_positions_need_no_unwrap():
     assert np.max(np.abs(runs[0].results.density - runs[1].results.density)) <= ref.density_bar(walk, k) + ref.density_bar(wrapped, k)
     # one incommensurate vector: the wrapped series is another function altogether
     bad = np.vstack([k[:2], [[1.0, 0.3, 0.2]]])
-    a, b = (IntermediateScattering(ArrayUniverse(positions=p, dimensions=dims).atoms, bad, device="cpu", coherent=False).run()
+    a, b = (IntermediateScattering(ArrayUniverse(positions=p, dimensions=dims).atoms, bad, coherent=False, **place).run()
             for p in (walk, wrapped))
     diff = np.max(np.abs(a.results.fs_by_kvector - b.results.fs_by_kvector), axis=0)
     assert diff[0] <= 1e-10 and diff[1] <= 1e-10 and diff[2] > 1e-3, diff
     assert N == 9
+    # ... and unwrap=True on the wrapped positions gives the walk's series for that vector too
+    c = IntermediateScattering(ArrayUniverse(positions=wrapped, dimensions=dims).atoms, bad, coherent=False, unwrap=True, **place).run()
+    assert np.max(np.abs(a.results.fs_by_kvector - c.results.fs_by_kvector)) <= 1e-10
+
+
+def test_wrapped_positions_need_no_unwrap():
+    wrapped_positions_need_no_unwrap(device="cpu")
 
 
 def test_kvectors_from_box():
@@ -230,7 +239,8 @@ def test_argument_checks_with_messages():
         empty.close()
 
 
-def test_class_refusals_and_results():
+def class_refusals_and_results(**place):
+    """the body of test_class_refusals_and_results under the placement keywords `place`"""
     rng = np.random.default_rng(11)
     T, A = 50, 12
     x = np.cumsum(rng.normal(scale=0.2, size=(T, A, 3)), axis=0) + 20
@@ -247,8 +257,8 @@ def test_class_refusals_and_results():
     with pytest.raises(ValueError, match="expected \\(K, 2\\)"):
         IntermediateScattering(u.atoms, k, dim_type="xy")
     with pytest.raises(ValueError, match="needs the periodic box"):
-        IntermediateScattering(u.atoms, q=1.0, dq=0.2, device="cpu").run()
-    r = IntermediateScattering(u.atoms, k, device="cpu", fft=False).run()
+        IntermediateScattering(u.atoms, q=1.0, dq=0.2, **place).run()
+    r = IntermediateScattering(u.atoms, k, **place, fft=False).run()
     res = r.results
     x32 = x.astype(np.float32).astype(np.float64)
     lags = ref.lag_sample(T)
@@ -261,21 +271,25 @@ def test_class_refusals_and_results():
     assert np.array_equal(res.sk, res.f[0]) and np.array_equal(res.fs, res.fs_by_kvector)
     assert np.allclose(res.f_by_kvector[0], (res.density ** 2).sum(axis=2).mean(axis=1) / A, rtol=1e-12)
     assert np.array_equal(r.lag_times(), np.arange(T) * 1.0)
-    inc = IntermediateScattering(u.atoms, k, device="cpu", coherent=False).run()
+    inc = IntermediateScattering(u.atoms, k, **place, coherent=False).run()
     assert inc.results.density is None and inc.results.f is None
     assert np.max(np.abs(inc.results.fs - res.fs)) <= 1e-10
     # shells: the mean over a shell's vectors
     boxed = ArrayUniverse(positions=x, dimensions=[15, 15, 15, 90, 90, 90])
-    sh = IntermediateScattering(boxed.atoms, q=[0.5, 0.9], dq=0.2, max_vectors=4, device="cpu").run().results
+    sh = IntermediateScattering(boxed.atoms, q=[0.5, 0.9], dq=0.2, max_vectors=4, **place).run().results
     for s in (0, 1):
         assert np.allclose(sh.fs[:, s], sh.fs_by_kvector[:, sh.shell == s].mean(axis=1), rtol=0, atol=1e-15)
         assert np.isclose(sh.q_shell[s], np.linalg.norm(sh.kvectors[sh.shell == s], axis=1).mean())
     # molecules: N is the number of compounds
     mol = np.arange(A) // 3
-    com = IntermediateScattering(u.atoms, k, device="cpu", compound=mol, compound_weights="geometry", coherent=False).run()
+    com = IntermediateScattering(u.atoms, k, **place, compound=mol, compound_weights="geometry", coherent=False).run()
     centres = x32.reshape(T, A // 3, 3, 3).mean(axis=2)
     want = ref.reference(centres, k, lags)[0]
     assert np.max(np.abs(com.results.fs_by_kvector[lags].T * (A // 3) - want)) <= 1e-10 * (A // 3)
+
+
+def test_class_refusals_and_results():
+    class_refusals_and_results(device="cpu")
 
 
 def test_relaxation_times_of_an_exponential():
@@ -293,3 +307,55 @@ def test_relaxation_times_of_an_exponential():
     y0, y1 = np.exp(-3 / 4.0), np.exp(-4 / 4.0)
     half = r.relaxation_times(level=0.4)
     assert np.isclose(half[0], 3 + (0.4 - y0) / (y1 - y0)) and i == 4
+
+
+# ---- the class on several devices and ranks: devices=[...], distributed=True ------------------------------------------------
+PLACED_T = 65
+INTEGER_KEYS = ()  # (nothing here is an integer)
+
+
+def placed_results(A, **place):
+    """IntermediateScattering on scatter_ref.case(65, A, 3, 3) with fft True and False under the placement keywords `place`:
+    {name: array} (placement.py)"""
+    from placement import record_ranges
+
+    x, k = ref.case(PLACED_T, A, 3, 3)[:2]
+    u = ArrayUniverse(positions=x)
+    out = {}
+    for fft in (1, 0):
+        r = IntermediateScattering(u.atoms, k, fft=bool(fft), **place).run().results
+        out[f"fs_{fft}"], out[f"rho_{fft}"], out[f"f_{fft}"] = r.fs_by_kvector, r.density, r.f_by_kvector
+        record_ranges(out, r)
+    return out
+
+
+def check_placed(out, A, what):
+    """placed_results against the reference over ALL atoms at test_walks_against_reference's bars (fs and f are self / N
+    and coll / N)"""
+    case = ref.case(PLACED_T, A, 3, 3)
+    for fft in (1, 0):
+        ref.assert_scatter(out[f"fs_{fft}"].T * A, out[f"rho_{fft}"], out[f"f_{fft}"].T * A, case, what=f"{what} fft={fft}")
+
+
+def own_correlations_differ(A, blocks):
+    """what a block-wise correlation would give: the sum of the blocks' own collective functions differs from the function
+    of the summed density by far more than the bar of 1e-10 -- check_placed can tell the two orders apart"""
+    x, k, lags, _, rho, _ = ref.case(PLACED_T, A, 3, 3)
+    want = ref.coll_at(rho, lags)
+    own = sum(ref.reference(x[:, lo:hi], k, lags)[2] for lo, hi in blocks)
+    rel = float(np.max(np.abs(own - want)) / np.max(np.abs(want)))
+    print(f"    the blocks' own F(k, t) summed: {rel:.3e} of the scale from the reference")
+    assert rel > 1e-3
+
+
+@pytest.mark.parametrize("A", [13, 1])
+def test_class_distributed_two_gloo_ranks_cpu_backend(tmp_path, A):
+    """A = 13: the ranks hold 6 and 7 atoms; A = 1: rank 0 holds no atom and contributes zeros (_no_moments).  The self
+    parts and the densities are summed over the ranks BEFORE the collective correlation."""
+    import sys
+
+    import placement
+
+    placement.check_ranks(sys.modules[__name__], A, 2, "cpu", tmp_path, dict(device="cpu"))
+    if A > 1:
+        own_correlations_differ(A, [(0, A // 2), (A // 2, A)])

@@ -52,12 +52,16 @@ def test_ballistic_closed_form():
     assert np.isnan(r.alpha2[0]) and np.max(np.abs(r.alpha2[1:] - alpha2)) <= 1e-10 * max(1.0, abs(alpha2))
 
 
-def test_static_atoms():
+def static_atoms(**place):
     x = np.broadcast_to(np.random.default_rng(4).uniform(0, 20, (1, 7, 3)), (12, 7, 3)).copy()
     lags = ref.lag_sample(12)
-    r = VanHoveSelf(ArrayUniverse(positions=x).atoms, lags, r_max=2.0, n_bins=10, device="cpu").run().results
+    r = VanHoveSelf(ArrayUniverse(positions=x).atoms, lags, r_max=2.0, n_bins=10, **place).run().results
     assert np.array_equal(r.counts[:, 0], 7 * (12 - lags)) and not r.counts[:, 1:].any() and not r.overflow.any()
     assert not r.msd.any() and not r.r4.any() and np.all(np.isnan(r.alpha2))
+
+
+def test_static_atoms():
+    static_atoms(device="cpu")
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["stage64", "stage32"])
@@ -185,11 +189,11 @@ def test_argument_checks_with_messages():
         empty.close()
 
 
-def test_normalisation():
+def normalisation(**place):
     """sum prob dr + the overflow share = 1, and sum gs V_b likewise, for every d"""
     for dim_type, d in (("xyz", 3), ("xy", 2), ("z", 1)):
         x, lags, _ = ref.case(200, 13, 3)
-        v = VanHoveSelf(ArrayUniverse(positions=x).atoms, lags, r_max=5.0, n_bins=50, dim_type=dim_type, device="cpu").run()
+        v = VanHoveSelf(ArrayUniverse(positions=x).atoms, lags, r_max=5.0, n_bins=50, dim_type=dim_type, **place).run()
         r = v.results
         n_pairs = 13.0 * (200 - lags)
         share = r.overflow / n_pairs
@@ -207,16 +211,24 @@ def test_normalisation():
         assert g.shape == (len(lags), 50) and np.all(np.isnan(g[0])) and np.allclose(g[1:], want[1:], rtol=1e-13, atol=0)
 
 
-def test_log_lags():
+def test_normalisation():
+    normalisation(device="cpu")
+
+
+def default_lags_are_log_lags(**place):
     assert log_lags(200).tolist() == [1, 2, 3, 4, 6, 7, 10, 13, 18, 24, 32, 42, 56, 75, 100, 133, 178]
     assert log_lags(2).tolist() == [1] and log_lags(1).size == 0 and log_lags(10 ** 6, per_decade=1).tolist() == [1, 10, 100, 1000, 10000, 100000]
     many = log_lags(2 ** 62, per_decade=64)
     assert many.size == 1024 and np.all(np.diff(many) > 0)  # cut at TA_VANHOVE_MAX_LAGS
     x, _, _ = ref.case(200, 13, 3)
-    r = VanHoveSelf(ArrayUniverse(positions=x).atoms, r_max=8.0, device="cpu").run().results
+    r = VanHoveSelf(ArrayUniverse(positions=x).atoms, r_max=8.0, **place).run().results
     assert np.array_equal(r.lags, log_lags(200)) and r.counts.shape == (17, 200)
     want = ref.reference(x, log_lags(200), 200, 8.0 / 200)
     ref.assert_vanhove(np.column_stack([r.counts, r.overflow]), None, want, what="default lags")
+
+
+def test_log_lags():
+    default_lags_are_log_lags(device="cpu")
 
 
 def wrapped_walk():
@@ -227,11 +239,11 @@ def wrapped_walk():
     return walk, walk - np.floor(walk / box) * box, box
 
 
-def test_unwrap_gives_the_unwrapped_walk():
+def unwrap_gives_the_unwrapped_walk(**place):
     walk, wrapped, box = wrapped_walk()
     dims = [*box, 90, 90, 90]
     lags = ref.lag_sample(120)
-    kw = dict(r_max=8.0, n_bins=64, device="cpu")
+    kw = dict(r_max=8.0, n_bins=64, **place)
     a = VanHoveSelf(ArrayUniverse(positions=walk).atoms, lags, **kw).run().results
     b = VanHoveSelf(ArrayUniverse(positions=wrapped, dimensions=dims).atoms, lags, unwrap=True, **kw).run().results
     w = VanHoveSelf(ArrayUniverse(positions=wrapped, dimensions=dims).atoms, lags, **kw).run().results
@@ -242,14 +254,18 @@ def test_unwrap_gives_the_unwrapped_walk():
     assert np.max(np.abs(b.msd - a.msd)) <= 1e-10 * np.max(a.msd)
 
 
-def test_compounds_and_barycentric_frame():
+def test_unwrap_gives_the_unwrapped_walk():
+    unwrap_gives_the_unwrapped_walk(device="cpu")
+
+
+def compounds_and_barycentric_frame(**place):
     """16 atoms of equal mass in molecules of 4: the weights 1/4 and 1/16 are dyadic, so the centres (and the centres in the
     barycentric frame) stay on a grid and the counts are exact"""
     x, lags, _ = ref.case(65, 16, 3)
     mol = np.arange(16) // 4
     u = ArrayUniverse(positions=x, masses=np.full(16, 2.0))
     centres = x.reshape(65, 4, 4, 3).mean(axis=2)
-    kw = dict(r_max=8.0, n_bins=64, device="cpu")
+    kw = dict(r_max=8.0, n_bins=64, **place)
     r = VanHoveSelf(u.atoms, lags, compound=mol, **kw).run().results
     want = ref.reference(centres, lags, 64, 0.125)
     ref.assert_vanhove(np.column_stack([r.counts, r.overflow]), None, want, what="compound")
@@ -258,6 +274,10 @@ def test_compounds_and_barycentric_frame():
     r = VanHoveSelf(u.atoms, lags, compound=mol, reference_frame="barycentric", **kw).run().results
     want = ref.reference(centres - x.mean(axis=1)[:, None, :], lags, 64, 0.125)
     ref.assert_vanhove(np.column_stack([r.counts, r.overflow]), None, want, what="barycentric")
+
+
+def test_compounds_and_barycentric_frame():
+    compounds_and_barycentric_frame(device="cpu")
 
 
 def test_class_refusals():
@@ -284,3 +304,42 @@ def test_class_refusals():
         VanHoveSelf(u.atoms, lags, r_max=2.0, unwrap=True, device="cpu").run()
     # no box, no volume: accepted without unwrap
     assert VanHoveSelf(u.atoms, lags, r_max=2.0, n_bins=4, device="cpu").run().results.counts.shape == (len(lags), 4)
+
+
+# ---- the class on several devices and ranks: devices=[...], distributed=True ------------------------------------------------
+PLACED_T = 65
+INTEGER_KEYS = ("counts",)
+
+
+def placed_results(A, **place):
+    """VanHoveSelf on vanhove_ref.case(65, A, 3) under the placement keywords `place`: {name: array} (placement.py); the
+    counts with the overflow column, the moments as the sums the library returns (msd and r4 times the pairs of the lag)"""
+    from placement import record_ranges
+
+    x, lags, _ = ref.case(PLACED_T, A, 3)
+    out = {}
+    for i, (n_bins, dr) in enumerate(ref.BINS):
+        r = VanHoveSelf(ArrayUniverse(positions=x).atoms, lags, r_max=n_bins * dr, n_bins=n_bins, **place).run().results
+        n_pairs = float(A) * (PLACED_T - lags)
+        out["counts" if i == 0 else f"counts_{i}"] = np.column_stack([r.counts, r.overflow])
+        out[f"moments_{i}"] = np.stack([r.msd * n_pairs, r.r4 * n_pairs], axis=1)
+        record_ranges(out, r)
+    return out
+
+
+def check_placed(out, A, what):
+    """placed_results against the reference over ALL atoms: the counts EQUAL, the moments at test_walks_against_reference's bar"""
+    _, _, refs = ref.case(PLACED_T, A, 3)
+    for i, bins in enumerate(ref.BINS):
+        ref.assert_vanhove(out["counts" if i == 0 else f"counts_{i}"], out[f"moments_{i}"], refs[bins], what=f"{what} bins={bins}")
+
+
+@pytest.mark.parametrize("A", [13, 1])
+def test_class_distributed_two_gloo_ranks_cpu_backend(tmp_path, A):
+    """A = 13: the ranks hold 6 and 7 atoms; A = 1: rank 0 holds no atom and contributes zeros (_no_moments).  The int64
+    counts travel through the all-reduce as float64 and come back as the same integers."""
+    import sys
+
+    import placement
+
+    placement.check_ranks(sys.modules[__name__], A, 2, "cpu", tmp_path, dict(device="cpu"))

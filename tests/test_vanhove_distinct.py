@@ -264,14 +264,14 @@ def gas(T=8, N=400, box=8.0, seed=0):
     return np.random.default_rng(seed).uniform(0, box, size=(T, N, 3)), [box, box, box, 90.0, 90.0, 90.0]
 
 
-def test_class_normalisation():
+def class_normalisation(**place):
     """gd, g, rdf and coordination from the counts by the formulas of the class's docstring, to 1e-14, for every d and for two
     groups that overlap"""
     x, lags, _, _, dims, _, _ = ref.case(65, 33, 3, 2, "overlap", True)
     u = ArrayUniverse(positions=x, dimensions=dims[0])
     ga, gb = u.select_atoms("index 0:21"), u.select_atoms("index 11:32")
     for dim_type, d, cols in (("xyz", 3, [0, 1, 2]), ("xz", 2, [0, 2]), ("y", 1, [1])):
-        v = VanHoveDistinct(ga, gb, lags, r_max=1.0, n_bins=64, origin_stride=2, dim_type=dim_type, device="cpu").run()
+        v = VanHoveDistinct(ga, gb, lags, r_max=1.0, n_bins=64, origin_stride=2, dim_type=dim_type, **place).run()
         r = v.results
         want = ref.reference(x[:, 0:33][:, :, cols], lags, 2, np.arange(0, 22), np.arange(11, 33), np.array(ref.BOX)[cols], 64, 1.0 / 64)
         ref.assert_counts(np.column_stack([r.counts, r.overflow]), want, what=f"class {dim_type}")
@@ -287,12 +287,16 @@ def test_class_normalisation():
         assert r.counts.dtype == np.int64 and r.counts.shape == (len(lags), 64) and r.r.shape == (64,)
 
 
-def test_class_uniform_gas_has_g_of_one():
+def test_class_normalisation():
+    class_normalisation(device="cpu")
+
+
+def class_uniform_gas_has_g_of_one(**place):
     """400 independent uniform points in a box of 8 over 8 frames: the lag-0 g, averaged over the bins with the counts as
     weights, is 1 within 3 / sqrt(the pairs counted), the Poisson error of that many pairs (the reference alone meets it with
     this seed: 1.00063 against a bound of 0.00367)"""
     x, dims = gas()
-    r = VanHoveDistinct(ArrayUniverse(positions=x, dimensions=dims).atoms, r_max=4.0, n_bins=64, device="cpu").run().results
+    r = VanHoveDistinct(ArrayUniverse(positions=x, dimensions=dims).atoms, r_max=4.0, n_bins=64, **place).run().results
     x32 = x.astype(np.float32).astype(np.float64)
     d = x32[:, None, :, :] - x32[:, :, None, :]
     d -= np.rint(d / 8.0) * 8.0
@@ -308,18 +312,22 @@ def test_class_uniform_gas_has_g_of_one():
     assert abs(r.coordination[-1] - 399 * (4 * np.pi / 3 * 64) / 512) < 0.5
 
 
-def test_class_same_group_twice_and_no_box():
+def test_class_uniform_gas_has_g_of_one():
+    class_uniform_gas_has_g_of_one(device="cpu")
+
+
+def class_same_group_twice_and_no_box(**place):
     x, dims = gas(T=3, N=60)
     u = ArrayUniverse(positions=x, dimensions=dims)
-    kw = dict(lags=[0, 1], r_max=3.0, n_bins=30, device="cpu")
+    kw = dict(lags=[0, 1], r_max=3.0, n_bins=30, **place)
     one = VanHoveDistinct(u.atoms, **kw).run().results
     two = VanHoveDistinct(u.atoms, u.atoms, **kw).run().results
     assert np.array_equal(one.counts, two.counts) and np.array_equal(one.overflow, two.overflow)
     assert np.array_equal(one.g, two.g)
     # lags=None: 0 and the logarithmic lags; a lag list without 0 has no rdf
-    r = VanHoveDistinct(u.atoms, lags=None, r_max=3.0, n_bins=30, device="cpu").run().results
+    r = VanHoveDistinct(u.atoms, lags=None, r_max=3.0, n_bins=30, **place).run().results
     assert r.lags.tolist() == [0, 1, 2] and np.array_equal(r.counts[:2], one.counts)
-    r = VanHoveDistinct(u.atoms, lags=[1], r_max=3.0, n_bins=30, device="cpu").run().results
+    r = VanHoveDistinct(u.atoms, lags=[1], r_max=3.0, n_bins=30, **place).run().results
     assert r.rdf is None and r.coordination is None and r.g.shape == (1, 30)
     # no periodicity: no box needed, plain distances, and nothing that needs a density
     free = VanHoveDistinct(ArrayUniverse(positions=x).atoms, periodic=False, **kw).run().results
@@ -328,7 +336,11 @@ def test_class_same_group_twice_and_no_box():
     with pytest.raises(ValueError, match="needs the periodic box"):
         VanHoveDistinct(ArrayUniverse(positions=x).atoms, **kw).run()
     with pytest.raises(_lib.TAError, match="exceeds half the box length"):
-        VanHoveDistinct(u.atoms, r_max=4.5, device="cpu").run()
+        VanHoveDistinct(u.atoms, r_max=4.5, **place).run()
+
+
+def test_class_same_group_twice_and_no_box():
+    class_same_group_twice_and_no_box(device="cpu")
 
 
 def test_class_refusals():
@@ -367,3 +379,29 @@ def test_class_refusals():
         VanHoveDistinct(u.atoms, lags=[0, 3], r_max=2.0, device="cpu").run()
     # one device in devices=[...] is one context
     assert VanHoveDistinct(u.atoms, r_max=2.0, n_bins=4, device="cpu", unwrap=False, compound=None).run().results.counts.shape == (1, 4)
+
+
+# ---- the class against the reference: the relations of the two groups, the boxes, the origin strides -----------------------
+CLASS_CASES = [(kind, boxed, stride) for kind in ("same", "disjoint", "overlap") for boxed in (True, "frames", False) for stride in (1, 3)]
+DERIVED_KEYS = ("gd", "g", "rdf", "coordination")
+
+
+def class_on_case(kind, boxed, stride, **place):
+    """VanHoveDistinct on vanhove_distinct_ref.case(65, 33, 3, stride, kind, boxed) under the placement keywords `place`:
+    counts, overflow and n_origins EQUAL to the reference's; returns the results (test_classes_gpu.py compares the
+    normalised functions with the device="cpu" run's: both come from the same integers through the same NumPy lines)"""
+    x, lags, a, b, dims, axes, refs = ref.case(65, 33, 3, stride, kind, boxed)
+    u = ArrayUniverse(positions=x, dimensions=dims)
+    n_bins, dr = ref.BINS[0]
+    v = VanHoveDistinct(u.atoms if a is None else u.atoms[a], None if b is None else u.atoms[b], lags, r_max=n_bins * dr, n_bins=n_bins,
+                        origin_stride=stride, periodic=bool(boxed), **place).run()
+    r = v.results
+    ref.assert_counts(np.column_stack([r.counts, r.overflow]), refs[ref.BINS[0]], what=f"class {kind} box={boxed} stride={stride}")
+    assert np.array_equal(r.n_origins, ref.n_origins(65, lags, stride)) and np.array_equal(r.lags, lags)
+    assert (r.g is None) == (not boxed) and r.gd.shape == (len(lags), n_bins)
+    return r
+
+
+@pytest.mark.parametrize("kind,boxed,stride", CLASS_CASES)
+def test_class_against_reference(kind, boxed, stride):
+    class_on_case(kind, boxed, stride, device="cpu")
