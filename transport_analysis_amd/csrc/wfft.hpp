@@ -357,7 +357,9 @@ struct WPlan {
     // barrier).  Measured per plan, same box (tools/wfft, -DWF_SPREAD_ALL=0/1): pays where ONE
     // 8-wave workgroup owns the compute unit and two sub-series plus all row registers fit;
     // the plans with several workgroups per unit overlap across workgroups already and lose
-    // 3-6 %; R0 = 18, 20 have no registers for it (three sub-series in flight, 96 registers).
+    // 3-6 %; R0 = 18, 20 (three sub-series in flight, 96 registers) have no room for the rows over all of S2: their
+    // lag-sum kernels on float64 slabs request them along the LAST stage instead, into the registers each sub-series
+    // frees as it retires (wf_accum_body, WF_ROWS_ALONG_C); their by-particle kernels keep the burst.
 #ifndef WF_SPREAD_ALL
     static constexpr bool kSpreadRows = R0 >= 9 && R0 <= 16;
 #else
@@ -754,9 +756,11 @@ __device__ __forceinline__ void wf_sub512_w(const WfSub& w, const WfTw& tw, doub
 // XV: the second sub-series takes exchange 1 through the register file (WfSub::stage_a) while
 // the first one's is in the LDS pipe: one sixth of the wave's LDS exchange traffic becomes vector
 // work (WPlan::kRegExchange; both of them that way is slower: the vector pipe becomes the limit)
-template <int S0, bool XV = false, class Hook = WfNoHook>
+// `retired(s)`, s = integral_constant, is called behind stage c of the call's sub-series s: its 32
+// registers are free from there on, with the later ones' last-stage butterflies still to run
+template <int S0, bool XV = false, class Hook = WfNoHook, class Retired = WfNoHook>
 __device__ __forceinline__ void wf_sub512_x2(const WfSub& w, const WfTw& tw, double (&acc0)[8],
-                                             double (&acc1)[8], Hook&& hook = Hook{}) {
+                                             double (&acc1)[8], Hook&& hook = Hook{}, Retired&& retired = Retired{}) {
     constexpr unsigned A = S0 * kWfSubBytes, B = A + kWfSubBytes;
     cd v0[8], v1[8];
     w.read_a<A>(v0);
@@ -770,15 +774,18 @@ __device__ __forceinline__ void wf_sub512_x2(const WfSub& w, const WfTw& tw, dou
     w.stage_b<B>(v1, tw);
     hook(wf_part<2>{});
     w.stage_c(v0, tw, acc0);
+    retired(wf_part<0>{});
     w.stage_c(v1, tw, acc1);
+    retired(wf_part<1>{});
     hook(wf_part<3>{});
 }
 
 // Three sub-series interleaved (the waves that own one more than the others: they then finish
 // together with their SIMD partner's two instead of running a third alone).
-template <bool XV = false, class Hook = WfNoHook>
+template <bool XV = false, class Hook = WfNoHook, class Retired = WfNoHook>
 __device__ __forceinline__ void wf_sub512_x3(const WfSub& w, const WfTw& tw, double (&acc0)[8],
-                                             double (&acc1)[8], double (&acc2)[8], Hook&& hook = Hook{}) {
+                                             double (&acc1)[8], double (&acc2)[8], Hook&& hook = Hook{},
+                                             Retired&& retired = Retired{}) {
     constexpr unsigned A = 0, B = kWfSubBytes, C = 2 * kWfSubBytes;
     cd v0[8], v1[8], v2[8];
     w.read_a<A>(v0);
@@ -795,8 +802,11 @@ __device__ __forceinline__ void wf_sub512_x3(const WfSub& w, const WfTw& tw, dou
     w.stage_b<C>(v2, tw);
     hook(wf_part<2>{});
     w.stage_c(v0, tw, acc0);
+    retired(wf_part<0>{});
     w.stage_c(v1, tw, acc1);
+    retired(wf_part<1>{});
     w.stage_c(v2, tw, acc2);
+    retired(wf_part<2>{});
     hook(wf_part<3>{});
 }
 
@@ -807,8 +817,9 @@ __device__ __forceinline__ void wf_sub512_x3(const WfSub& w, const WfTw& tw, dou
 //
 // Per unit: S1 (rows -> radix-R0 butterfly -> output twiddles -> LDS), barrier, S2 (the wave's
 // sub-series, |.|^2 into its accumulators), barrier.  The rows of the NEXT unit are requested
-// during S2 -- spread over it where the plan has the registers (WPlan::kSpreadRows), else in one
-// burst behind it -- and land while the slowest wave finishes.  The tangent-form constants of the
+// during S2 -- spread over it where the plan has the registers (WPlan::kSpreadRows), along its
+// last stage in the lag-sum kernels of R0 = 18, 20 (WF_ROWS_ALONG_C), else in one burst behind
+// it -- and land while the slowest wave finishes.  The tangent-form constants of the
 // second and third radix-8 stage (32 registers per lane) stay resident for the whole launch.
 // Forward kernel: |transform|^2 of column units, accumulated per pass in registers.
 //
@@ -1011,7 +1022,27 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
                             // 10000 x 100000 x 3 (float64 slab 8.69 ms): 20 (none along S2) 8.78 ms, 8: 8.30, 4: 8.24, 0: 7.85 ms
                             // (28 bytes of scratch and still the fastest)
 #endif
-    constexpr int NSPREAD = WF_LOAD_PARTS != 4 ? 0 : (kSpread ? (SRC32 && R0 >= 18 ? NR - WF_SPREAD32_TAIL : NR) : 0);
+    // float64 rows, R0 = 18, 20, lag sums (the split bodies and the outer-radix kernels; the by-particle kernels would
+    // spill 96 - 112 bytes and keep the burst): the 80 row registers are dead during S2 and the 96 of
+    // the three sub-series in flight do not die together -- stage c of a sub-series frees its 32.  The requests are
+    // written behind each stage c, a scheduling barrier behind each group and none in front: three-at-a-time waves
+    // rows [0, 8), [8, 16), [16, NR); two-at-a-time waves
+    //   1: [0, 8), [8, NR);   2: all NR behind their S2 (they finish early anyway);   3: [0, 8), [8, 16), the rest behind.
+    // Nothing stays for issue_loads_tail.  0: the burst behind S2, the code before.  The compiler lifts each group over
+    // the stage c it stands behind (88 FP64 instructions; the registers are there: 256, no scratch), so every group,
+    // the last one too, has a block of butterflies behind it: tools/wfft/isa_table.py shows where they stand.
+    // Same-box harness, mean of 250 launches per 24 GB, medians of five rounds: R0 = 20 0: 8.576 ms, 1: 8.356, 2: 8.377,
+    // 2 with a second barrier in FRONT of each group (the requests strictly behind stage c): 8.469; R0 = 18 7.745 /
+    // 7.488 / 7.561 / 7.619 ms; 3 spills 12 bytes at R0 = 20 and was not run.  bench.py: 8.533 -> 8.336 ms.  With an
+    // outer radix (which spilled 28 / 8 bytes at R0 = 20 / 18 and now does not), 0 against 1: R0 = 20, R = 2 11.277 ->
+    // 10.917 ms per 73000 pairs, R = 3 13.846 -> 13.325 ms per 48000; R0 = 18, R = 2 10.921 -> 10.704 ms per 80000.
+    // (profiles/r10_headline_ab.txt)
+#ifndef WF_ROWS_ALONG_C
+#define WF_ROWS_ALONG_C 1
+#endif
+    constexpr bool kAlongC = WF_ROWS_ALONG_C && WF_LOAD_PARTS == 4 && !BYP && !SRC32 && NS1 == 3 && P::NLO == 2 && P::REM != 0;
+    constexpr int NSPREAD =
+        WF_LOAD_PARTS != 4 ? 0 : kAlongC ? NR : (kSpread ? (SRC32 && R0 >= 18 ? NR - WF_SPREAD32_TAIL : NR) : 0);
     auto issue_row = [&](auto ii, __amdgpu_buffer_rsrc_t rs, int kd) {
         constexpr int i = decltype(ii)::value, k1 = i / R0, j = i % R0;
         const int u = tid + NT * k1;
@@ -1049,6 +1080,13 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
     const WfSub wsub(wad, smem_raw);
     int k = 0;  // unit of the atom (by-particle mode)
     bool zero_pending = false;
+    // the wave's number as a scalar.  The bodies with the row requests behind stage c take it once, here: taken again
+    // behind the loop it keeps a vector register alive across it, which the split bodies do not have (8 bytes of scratch)
+    [[maybe_unused]] const int wv_once = kAlongC ? __builtin_amdgcn_readfirstlane(wave) : 0;
+    auto wave_id = [&]() {
+        if constexpr (kAlongC) return wv_once;
+        else return __builtin_amdgcn_readfirstlane(wave);
+    };
     for (long item = tuple * grp; item < n_units;) {
         // ---- S1: radix-R0 butterflies u = tid + NT k over rows u + 512 j of u_c (jo = 0 requested
         // during the previous S2); g = W_M^u, h = W_L^{c u}
@@ -1235,7 +1273,7 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
 #endif
         };
         if (BYP && kind != 2) {
-            const int wv = __builtin_amdgcn_readfirstlane(wave);
+            const int wv = wave_id();
             // a real column: the wave's share of P::kRealSel, one sub-series at a time
             // (the next unit's row requests that would ride along S2 go out first)
             static_for_range<0, 4>([&](auto part_c) { row_hook(part_c); });
@@ -1251,12 +1289,31 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
         } else
         if constexpr (NS1 == 3 && P::NLO == 2 && P::REM != 0) {
             // two full slots and a partial third: the waves that own three sub-series take them
-            // three at a time, the others two at a time (no row requests along S2 in these plans:
-            // NSPREAD = 0.  Measured instead, R0 = 20, same box: every wave two at a time with 8 of
+            // three at a time, the others two at a time (float64 rows: no requests over the whole of
+            // S2 in these plans.  Measured instead, R0 = 20, same box: every wave two at a time with 8 of
             // the 20 requests spread, the third alone afterwards -- correct, 2.12 against 2.11 ms.)
             if constexpr (SRC32) {  // room for the next unit's (float32) rows: requested along S2
                 if (wave < P::REM) wf_sub512_x3<P::kRegExchange>(wsub, stw, acc[0], acc[1], acc[2], row_hook);
                 else wf_sub512_x2<0, P::kRegExchange>(wsub, stw, acc[0], acc[1], row_hook);
+            } else if constexpr (kAlongC) {  // behind each stage c, into the registers it frees
+                auto rows = [&](auto lo, auto hi) {
+                    static_for_range<decltype(lo)::value, decltype(hi)::value>([&](auto ii) { issue_row(ii, nrs, nkind); });
+                    __builtin_amdgcn_sched_barrier(0);  // (they stay where they stand)
+                };
+                constexpr int kLight = WF_ROWS_ALONG_C;  // the two-at-a-time waves' share, see above
+                if (wave < P::REM) {
+                    wf_sub512_x3<P::kRegExchange>(wsub, stw, acc[0], acc[1], acc[2], WfNoHook{}, [&](auto sc) {
+                        constexpr int s = decltype(sc)::value;
+                        rows(wf_part<8 * s>{}, wf_part<(s == 2 ? NR : 8 * s + 8)>{});
+                    });
+                } else {
+                    wf_sub512_x2<0, P::kRegExchange>(wsub, stw, acc[0], acc[1], WfNoHook{}, [&](auto sc) {
+                        constexpr int s = decltype(sc)::value;
+                        if constexpr (kLight == 1) rows(wf_part<8 * s>{}, wf_part<(s == 1 ? NR : 8)>{});
+                        else if constexpr (kLight == 3) rows(wf_part<8 * s>{}, wf_part<8 * s + 8>{});
+                    });
+                    if constexpr (kLight != 1) rows(wf_part<(kLight == 3 ? 16 : 0)>{}, wf_part<NR>{});
+                }
             } else {
                 if (wave < P::REM) wf_sub512_x3<P::kRegExchange>(wsub, stw, acc[0], acc[1], acc[2]);
                 else wf_sub512_x2<0, P::kRegExchange>(wsub, stw, acc[0], acc[1]);
@@ -1279,7 +1336,7 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
             });
         }
         if constexpr (STAMP) st_s2end = __builtin_amdgcn_s_memtime();  // behind the wave's own sub-series
-        const int wv = __builtin_amdgcn_readfirstlane(wave);
+        const int wv = wave_id();
         auto store_acc = [&](long row) {  // accg[row][pass][q][cc / 2][lane][cc & 1]
             const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
                 accg + (row * npass + pass) * (long)M, 0, M * 8, 0x00020000);
@@ -1322,7 +1379,7 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
         // the address of that position -- lane - 8; lanes 1 ... 7: lane + 55; lane 0: lane 63 of cc - 1 -- 8 bytes at a
         // time.  The three offsets below carry what differs from lane to lane, the rest is the instruction's constant.
         if (tuple * grp < n_units) {
-            const int wv = __builtin_amdgcn_readfirstlane(wave);
+            const int wv = wave_id();
             const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
                 accg + (tuple * npass + pass) * (long)M, 0, M * 8, 0x00020000);
             // (the lane counted again here: one register fewer across the loop, which R0 = 20 does not have)
@@ -1353,9 +1410,14 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
     if constexpr (!BYP) {
         // a tuple without units still owes its (zero) row of the partial spectra
         if (tuple * grp >= n_units) {
-            const int wv = __builtin_amdgcn_readfirstlane(wave);
+            const int wv = wave_id();
             const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
                 accg + (tuple * npass + pass) * (long)M, 0, M * 8, 0x00020000);
+            int ln = lane;
+            if constexpr (kAlongC) {  // (counted again, as above)
+                ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                asm volatile("" : "+v"(ln));
+            }
 #pragma unroll
             for (int s = 0; s < NS1; ++s) {
                 const int q = P::sub_base(wv) + s;
@@ -1363,7 +1425,7 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
 #pragma unroll
                     for (int c2 = 0; c2 < 4; ++c2)
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wf_u32x4, cd{0.0, 0.0}), sr,
-                                                               (unsigned)lane * 16u, (unsigned)((q * 4 + c2) * 64) * 16u, 0);
+                                                               (unsigned)ln * 16u, (unsigned)((q * 4 + c2) * 64) * 16u, 0);
                 }
             }
         }
