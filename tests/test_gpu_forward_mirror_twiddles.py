@@ -1,4 +1,4 @@
-"""The split forward bodies (R0 = 18, 20, lag sums, float64 slab; wfft.hpp, WF_TWIDDLE_MIRROR) generate the first-stage
+"""The split forward bodies (R0 = 18, 20, lag sums, float64 slab; wfft.hpp, the mirrored output twiddles) generate the first-stage
 output twiddles up to R0/2 only and scale the far half of the sub-series by conjugates.  Such a mirrored sub-series has its
 512-point transform one bin over, and the accumulators are stored at the address of their true position once per launch.
 A bin stored one place off -- or right everywhere except where position (lane >> 3) + 8 (lane & 7) + 64 cc carries from one

@@ -1,4 +1,4 @@
-"""The split forward bodies (R0 = 18, 20, lag sums, float64 slab; wfft.hpp, WF_ROWS_ALONG_C) request the next unit's rows
+"""The split forward bodies (R0 = 18, 20, lag sums, float64 slab; wfft.hpp, kAlongC) request the next unit's rows
 behind the last-stage butterflies of S2, a group into the registers of each sub-series as it retires, instead of in one burst
 behind S2.  A row that lands in a register still in use, a group left out on one of the two paths (three sub-series at a time,
 two at a time), or a prefetch that runs on after the tuple's last unit shows in the lag sums: every lag of ta_vacf_fft_staged is

@@ -4,7 +4,7 @@
 # spectrum and the inverse transform on the compute unit), same box, 10000 frames x 100000 atoms x 3:
 #   library          tools/timeline_case.py fft 10000 100000 --bp [--f32]   (kernel timeline from the library's events)
 #   wfft_test_fu8    the fused kernel on 8 waves x 256 registers (two per SIMD)
-#   wfft_test_fu4    ... on 4 waves x 512 registers (-DWF_NW_R0=20 -DWF_NW_VAL=4)
+#   (wfft_test_fu4, the same on 4 waves x 512 registers, built with a switch the header no longer has: at commit 842be10)
 # per run: rocm-smi package power and sclk sampled while it loops, hipEvent time, in-kernel cycles per phase (wave 0).
 # Run on the GPU box: tools/wfft/fused_report.sh -> gpurun_out/r06_bp_fused_raw.txt
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -20,7 +20,7 @@ for f32 in "" "--f32"; do
   sample $!
   tail -2 /tmp/fr.log
 done
-for v in fu8 fu4; do
+for v in fu8; do
   for f32 in 0 1; do
     BIN=$R/tools/wfft/wfft_test_$v
     echo "## wfft_test_$v  float32 rows: $f32  (sha $(sha256sum $BIN | cut -c1-16))"

@@ -37,11 +37,6 @@
 
 namespace ta {
 
-#ifndef WF_NW_R0
-#define WF_NW_R0 0  // experiment: plan R0 = WF_NW_R0 runs with WF_NW_VAL waves per workgroup
-#define WF_NW_VAL 0
-#endif
-
 template <int LO, int HI, class F>
 __device__ __forceinline__ void static_for_range(F&& f) {
     [&]<int... I>(std::integer_sequence<int, I...>) {
@@ -347,50 +342,33 @@ struct WPlan {
     // R0 = 18 with 6: 19.9 vs 4.8; R0 = 8 with 4:
     // 8.3 vs 7.6 ms; R0 = 10 with 4 / 5: 10.8 / 14.3 vs 9.7; R0 = 12 with 4 / 6: 13.4 / 19.4 vs 11.8;
     // R0 = 20 with 4: 11.6 vs 9.2).
-    static constexpr int NW = R0 == WF_NW_R0 ? WF_NW_VAL : R0 <= 4 ? 2 : R0 <= 7 ? 4 : 8;
+    static constexpr int NW = R0 <= 4 ? 2 : R0 <= 7 ? 4 : 8;
     static constexpr int NT = 64 * NW;
     static constexpr int K1 = (N1 + NT - 1) / NT;
     // (measured: trading the resident stage twiddles for a fourth wave per SIMD in the small plans
     // costs 5-10 %: 1000 frames 9.96 vs 9.26 ms, 2000 frames 10.56 vs 9.62 ms per 24 GB)
     // Row requests of the next unit spread over S2 instead of one burst behind it (the burst: 20
     // requests of 1 KiB per wave, 16 cycles each in the texture addresser, queue up in front of the
-    // barrier).  Measured per plan, same box (tools/wfft, -DWF_SPREAD_ALL=0/1): pays where ONE
+    // barrier).  Measured per plan, same box (tools/wfft, every plan with and without): pays where ONE
     // 8-wave workgroup owns the compute unit and two sub-series plus all row registers fit;
     // the plans with several workgroups per unit overlap across workgroups already and lose
     // 3-6 %; R0 = 18, 20 (three sub-series in flight, 96 registers) have no room for the rows over all of S2: their
     // lag-sum kernels on float64 slabs request them along the LAST stage instead, into the registers each sub-series
-    // frees as it retires (wf_accum_body, WF_ROWS_ALONG_C); their by-particle kernels keep the burst.
-#ifndef WF_SPREAD_ALL
+    // frees as it retires (wf_accum_body, kAlongC); their by-particle kernels keep the burst.
     static constexpr bool kSpreadRows = R0 >= 9 && R0 <= 16;
-#else
-    static constexpr bool kSpreadRows = WF_SPREAD_ALL && (R0 < 18 || R0 == WF_NW_R0);  // (a 4-wave experiment plan has 512 registers)
-#endif
     // One of two (three) sub-series in flight takes its first exchange through the register file
     // (gfx950 permlane swaps + DPP) instead of the LDS: same-box A/B per 30000 pairs R0 = 16: 1.63
     // -> 1.575 ms, R0 = 18: 1.91 -> 1.84, R0 = 20: 2.07 -> 2.02 ms; both sub-series that way: R0 = 16 +-0,
-    // R0 = 20 +5 % (spills).  (-DWF_REG_EXCHANGE=0/1 overrides.)
-#ifndef WF_REG_EXCHANGE
+    // R0 = 20 +5 % (spills).
     static constexpr bool kRegExchange = R0 >= 16;
-#else
-    static constexpr bool kRegExchange = WF_REG_EXCHANGE;
-#endif
     // ... and where a wave runs its sub-series one at a time (one full slot per wave), every one of
     // them, on the plans where the same-box A/B says so (per ~24 GB: R0 = 2 -4 %, 7 -2 %, 9 -1.5 %,
     // 10 -2.4 %, 12 -1.5..-3 %, 14 -3.7 %; R0 = 3..6 +-1 %, R0 = 8 +5..13 %: two workgroups per unit
     // there, the vector pipe is the busier one)
-#ifndef WF_REG_EXCHANGE_SINGLE
     static constexpr bool kRegExchangeSingle = R0 == 2 || R0 == 7 || R0 == 9 || R0 == 10 || R0 == 12 || R0 == 14;
-#else
-    static constexpr bool kRegExchangeSingle = (WF_REG_EXCHANGE_SINGLE >> (R0 - 1)) & 1;  // bit mask over R0
-#endif
-#ifndef WF_MINW_R0
     // R0 = 2 lives on four waves per SIMD -- several workgroups per compute unit -- and sits just
     // under the 128 registers that takes: hold it there
-    static __host__ __device__ constexpr int min_waves(bool /*byp*/, bool lng) { return R0 == 2 ? 4 : 1; }
-#else  // experiment: plan R0 = WF_MINW_R0 is compiled for WF_MINW_VAL waves per SIMD
-    static __host__ __device__ constexpr int min_waves(bool, bool) { return R0 == WF_MINW_R0 ? WF_MINW_VAL : 1; }
-#endif
-    static constexpr bool kTwResident = true;
+    static __host__ __device__ constexpr int min_waves() { return R0 == 2 ? 4 : 1; }
     static constexpr int M = R0 * N1;
     // sub-series of a wave (forward kernel): consecutive ones, q = sub_base(wave) + s, s < sub_count(wave);
     // the first R0 % NW waves own one more than the others, NS1 at most
@@ -456,12 +434,7 @@ __device__ __forceinline__ cd wf_load(__amdgpu_buffer_rsrc_t r, unsigned lane_of
 // (post-twiddle form, kept for the 512-frame kernels at the end of this file)
 // One wave's 512-point DIF transform of the sub-series at `reg` (natural order in, the lane's
 // eight outputs c = 0..7 are bins s = (lane>>3) + 8 (lane&7) + 64 c), |.|^2 added to acc.
-// The two exchanges stay inside the sub-series' own 8 KiB; their layouts are conflict-free for
-// ds_write_b128 / ds_read_b128 (verified exhaustively against the lane groups of the LDS):
-//   exchange 1: (a, l)      at a*64 + (l ^ 8 (a&1))
-//   exchange 2: (a, b, n0)  at (8a + b)*8 + (n0 ^ a ^ b)
-// A wave's own DS operations execute in order, so a read issued after a write of the same wave
-// sees it: no barrier, only the compiler has to keep the order (wave_barrier).
+// The two exchanges and their layouts are those of WfSub below; the twiddles follow the butterflies.
 struct WfSubPost {
     int lane, hi, lo;
     __device__ __forceinline__ explicit WfSubPost(int lane_) : lane(lane_) {
@@ -818,7 +791,7 @@ __device__ __forceinline__ void wf_sub512_x3(const WfSub& w, const WfTw& tw, dou
 // Per unit: S1 (rows -> radix-R0 butterfly -> output twiddles -> LDS), barrier, S2 (the wave's
 // sub-series, |.|^2 into its accumulators), barrier.  The rows of the NEXT unit are requested
 // during S2 -- spread over it where the plan has the registers (WPlan::kSpreadRows), along its
-// last stage in the lag-sum kernels of R0 = 18, 20 (WF_ROWS_ALONG_C), else in one burst behind
+// last stage in the lag-sum kernels of R0 = 18, 20 (kAlongC), else in one burst behind
 // it -- and land while the slowest wave finishes.  The tangent-form constants of the
 // second and third radix-8 stage (32 registers per lane) stay resident for the whole launch.
 // Forward kernel: |transform|^2 of column units, accumulated per pass in registers.
@@ -883,20 +856,15 @@ __device__ __forceinline__ auto& wf_pick(A& a, B& b) {
 //   pass 1: two seed requests (h, g2; g = h^2 -- R = 1: W_M^u = W_L^{2u}) and the twist inside the
 //           butterfly (DftTwisted) instead of R0 - 1 literal multiplications in front of it.
 // 21 / 22 instead of 23 memory requests per thread and unit.  (Pass 1 squaring g for g2 as well is
-// one request fewer: WF_SEED_DERIVE=3.  With both chains run to R0 - 1 it doubled the error of the
+// one request fewer.  With both chains run to R0 - 1 it doubled the error of the
 // lag sums -- the error of g2 entered R0 / 2 - 1 times along either chain and h^4 carries four times
-// that of a table entry; with the chains stopped at R0 / 2 (WF_TWIDDLE_MIRROR) its error is below
+// that of a table entry; with the chains stopped at R0 / 2 (the mirror below) its error is below
 // the shipped one, and its gain, 0.3-0.7 %, under three spreads of the measurement: DESIGN.md section 9.
-// The seed kept resident across the launch instead -- 4 registers -- spills 248-260 bytes.)
+// The seed kept resident across the launch instead -- 4 registers -- spills 248-260 bytes.
+// The seeds loaded like the run-time body, and the literal twist in front of Dft<R0>: the code before,
+// parent of 9ea77a2.)
 #ifndef WF_PASS_SPLIT
 #define WF_PASS_SPLIT 1   // 0: every plan reads the pass at run time
-#endif
-#ifndef WF_SEED_DERIVE
-#define WF_SEED_DERIVE 2  // split bodies: 0: g, g2 (and h) loaded like the run-time body; 1: pass 1 squares h for g;
-                          // 2: and pass 0 squares g for g2; 3: and pass 1 too (one request per unit in both)
-#endif
-#ifndef WF_TWIST_FOLD
-#define WF_TWIST_FOLD 1   // 0: the split pass-1 body keeps the literal twist in front of Dft<R0>
 #endif
 // The split bodies generate only half of the output twiddles t_q = W_L^{u (2q + c)}.  With G = W_L^{2 R0 u} = W_512^u
 //   pass 0: t_{R0-q} = G conj(t_q),   pass 1: t_{R0-q} = G conj(t_{q-1}),
@@ -904,9 +872,7 @@ __device__ __forceinline__ auto& wf_pick(A& a, B& b) {
 // S2 only adds |.|^2 into per-bin accumulators, so the accumulator of position r of such a MIRRORED sub-series (pass 0:
 // q > R0/2, pass 1: q >= R0/2) holds the true bin of position r - 1 (mod 512), and store_acc, once per launch, writes it
 // there.  The chains by g2 stop at R0/2: 8 generating products instead of 17 at R0 = 20 (7 instead of 15 at R0 = 18).
-#ifndef WF_TWIDDLE_MIRROR
-#define WF_TWIDDLE_MIRROR 1  // 0: both chains run to R0 - 1 and every accumulator is stored where it stands
-#endif
+// (Both chains run to R0 - 1 and every accumulator stored where it stands: the code before, parent of 8aef63a.)
 // (float32 slabs stay on the run-time pass: their kernels spill already -- 16 / 36 bytes at R0 = 18 / 20 for the
 // row requests along S2 -- and every split variant spills more, 28-52 bytes: tools/wfft/isa_table.py)
 template <class P, bool BYP, bool LONG, bool SRC32>
@@ -914,6 +880,153 @@ constexpr bool wf_pass_split = WF_PASS_SPLIT && !BYP && !LONG && !SRC32 && (P::R
 
 __device__ __forceinline__ cd wf_csqr(cd a) { return {a.x * a.x - a.y * a.y, 2.0 * (a.x * a.y)}; }
 
+// ---- unit and row access --------------------------------------------------------------------------
+// The tuple's units in order: lag-sum mode pairs tuple + i n_tuples; by-particle mode the units
+// k < upa of its atoms.  A unit past the end gets an empty buffer: its loads return zeros and are
+// never used.
+template <bool BYP, bool SRC32>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wf_unit_rsrc(const double* __restrict__ pm, long pitch, int T,
+                                                               long n_units, int D, long item, int k, int* kind) {
+    long pair = item;
+    const bool live = item < n_units;
+    *kind = 2;
+    if constexpr (BYP) wf_unit_of(live ? item : 0, k, D, &pair, kind);
+    if constexpr (SRC32)
+        return __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(reinterpret_cast<const float*>(pm) + (live ? pair : 0) * pitch * 2), 0,
+            live ? T * 8 : 0, 0x00020000);
+    else
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(pm + (live ? pair : 0) * pitch * 2), 0,
+                                                 live ? T * 16 : 0, 0x00020000);
+}
+// row u + row_off of the unit (a single real column: that half of the row, imaginary part 0);
+// SRC32: the raw 8 bytes (one column: its 4 bytes in .x), widened by wf_widen when S1 starts
+template <bool SRC32>
+using WfRow = std::conditional_t<SRC32, wf_u32x2, cd>;
+template <bool BYP, bool SRC32>
+__device__ __forceinline__ WfRow<SRC32> wf_load_row(__amdgpu_buffer_rsrc_t rs, int kd, int u, unsigned row_off) {
+    if constexpr (SRC32) {
+        // the whole 8-byte row also for a single column (wf_widen picks its half): 4-byte requests
+        // fetch the same lines at half the rate
+        return __builtin_amdgcn_raw_buffer_load_b64(rs, (unsigned)u * 8u, row_off * 8u, 0);
+    } else {
+        if (!BYP || kd == 2) return wf_load(rs, (unsigned)u * 16u, row_off * 16u);
+        return cd{__builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
+                                                 rs, (unsigned)u * 16u + (unsigned)kd * 8u, row_off * 16u, 0)),
+                  0.0};
+    }
+}
+template <bool BYP>
+__device__ __forceinline__ cd wf_widen(wf_u32x2 r, int kd) {
+    if (!BYP || kd == 2)
+        return cd{(double)__builtin_bit_cast(float, (unsigned)r[0]), (double)__builtin_bit_cast(float, (unsigned)r[1])};
+    return cd{(double)__builtin_bit_cast(float, (unsigned)(kd ? r[1] : r[0])), 0.0};
+}
+
+// The rows jo = 0 of a unit in the registers of the thread that runs the first-stage butterflies
+// u = tid + NT k1, k1 < K1 (u < 512): row j of butterfly k1 has linear index i = k1 R0 + j.
+template <class P, bool BYP, bool SRC32>
+struct WfRows {
+    static constexpr int R0 = P::R0, N1 = P::N1, K1 = P::K1, NT = P::NT, NR = K1 * R0;
+    WfRow<SRC32> xx[K1][R0];
+    template <int I>
+    __device__ __forceinline__ void request_row(int tid, __amdgpu_buffer_rsrc_t rs, int kd) {
+        constexpr int k1 = I / R0, j = I % R0;
+        const int u = tid + NT * k1;  // rows past 512 j + 511 belong to the next j: never loaded
+        if (K1 * NT != N1 && u >= N1) return;
+        if (!BYP || kd == 2) xx[k1][j] = wf_load_row<BYP, SRC32>(rs, 2, u, (unsigned)(N1 * j));
+        else xx[k1][j] = wf_load_row<BYP, SRC32>(rs, kd, u, (unsigned)(N1 * j));
+    }
+    // rows [lo, hi), integral constants
+    template <class LO, class HI>
+    __device__ __forceinline__ void request(LO, HI, int tid, __amdgpu_buffer_rsrc_t rs, int kd) {
+        static_for_range<LO::value, HI::value>([&](auto ii) { request_row<decltype(ii)::value>(tid, rs, kd); });
+    }
+    // the first unit's rows, before the loop: the unit's kind decided once per k1, not per row (folded
+    // onto request() the by-particle kernels come out as different code)
+    __device__ __forceinline__ void request_first(int tid, __amdgpu_buffer_rsrc_t rs, int kd) {
+#pragma unroll
+        for (int k1 = 0; k1 < K1; ++k1) {
+            const int u = tid + NT * k1;
+            if (K1 * NT != N1 && u >= N1) continue;
+            if (!BYP || kd == 2) {
+#pragma unroll
+                for (int j = 0; j < R0; ++j) xx[k1][j] = wf_load_row<BYP, SRC32>(rs, 2, u, (unsigned)(N1 * j));
+            } else {
+#pragma unroll
+                for (int j = 0; j < R0; ++j) xx[k1][j] = wf_load_row<BYP, SRC32>(rs, kd, u, (unsigned)(N1 * j));
+            }
+        }
+    }
+};
+
+// ---- S1 -------------------------------------------------------------------------------------------
+// seeds of the output twiddles of butterfly u: g = W_M^u, g2 = g^2, h = W_L^{c u} (see PASS above)
+template <int PASS>
+__device__ __forceinline__ void wf_load_seeds(__amdgpu_buffer_rsrc_t twr, int u, int R, int pass, cd& g, cd& g2, cd& h) {
+    if constexpr (PASS == 1) {  // g = W_L^{2u} by squaring: it only starts the odd chain
+        h = wf_load(twr, (unsigned)u * 16u, 0u);
+        g = wf_csqr(h);
+    } else {
+        g = wf_load(twr, (unsigned)(u * R) * 32u, 0u);
+        if (PASS != 0) h = wf_load(twr, (unsigned)(u * pass) * 16u, 0u);
+    }
+    if constexpr (PASS == 0) g2 = wf_csqr(g);
+    else g2 = wf_load(twr, (unsigned)(u * R) * 64u, 0u);
+}
+
+// ---- S2: the wave's sub-series, |.|^2 into acc[s]; `hook` carries the next unit's row requests -------
+// A real column (by-particle mode): the wave's share of P::kRealSel, one sub-series at a time
+// (the next unit's row requests that would ride along S2 go out first)
+template <class P, class Hook>
+__device__ __forceinline__ void wf_s2_real(const WfSub& wsub, const WfTw& stw, double (&acc)[P::NS1][8], int wv, int pass,
+                                           Hook&& hook) {
+    static_for_range<0, 4>([&](auto part_c) { hook(part_c); });
+    const unsigned qs = P::kRealSel.qmask[pass ? 1 : 0] >> P::sub_base(wv);
+    const unsigned q1 = P::kRealSel.q1mask[pass ? 1 : 0] >> P::sub_base(wv);
+    // (measured: the waves with two selected sub-series running them interleaved instead -- 13.07
+    // against 13.04 ms at 10000 x 100000 x 3 -- changes nothing: the unit waits for its first stage)
+    static_for_range<0, P::NS1>([&](auto ss) {
+        constexpr int s = decltype(ss)::value;
+        if ((s < P::NLO || wv < P::REM) && (qs >> s & 1u))
+            wf_sub512_w<s, P::kRegExchangeSingle>(wsub, stw, acc[s], (q1 >> s & 1u) ? 1.0 : 2.0);
+    });
+}
+// every other plan: the slots two at a time where every wave has both, else one at a time
+// (the row requests ride on the wave's first call: every wave has slot 0)
+template <class P, class Hook>
+__device__ __forceinline__ void wf_s2_slots(const WfSub& wsub, const WfTw& stw, double (&acc)[P::NS1][8], int wave,
+                                            Hook&& hook) {
+    static_for_range<0, P::NS1>([&](auto ss) {
+        constexpr int s = decltype(ss)::value;
+        constexpr bool full = s < P::NLO;                       // every wave has this slot
+        constexpr bool nfull = s + 1 < P::NLO;                  // ... and the next one
+        constexpr bool head = full && nfull && (s % 2 == 0);
+        constexpr bool tail = full && s > 0 && (s % 2 == 1);
+        if constexpr (head) {
+            if constexpr (s == 0) wf_sub512_x2<s, P::kRegExchange>(wsub, stw, acc[s], acc[s + 1], hook);
+            else wf_sub512_x2<s, P::kRegExchange>(wsub, stw, acc[s], acc[s + 1]);
+        } else if constexpr (!tail) {
+            if constexpr (s == 0) wf_sub512<s, P::kRegExchangeSingle>(wsub, stw, acc[s], hook);
+            else if (full || wave < P::REM) wf_sub512<s, P::kRegExchangeSingle>(wsub, stw, acc[s]);
+        }
+    });
+}
+
+// ---- stores ---------------------------------------------------------------------------------------
+// one pass's row of spectra, accg[row][pass][q][cc / 2][lane][cc & 1]: M doubles
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wf_acc_rsrc(double* __restrict__ accg, long row, int npass, int pass,
+                                                              int M) {
+    return __builtin_amdgcn_make_buffer_rsrc(accg + (row * npass + pass) * (long)M, 0, M * 8, 0x00020000);
+}
+
+// ---- the forward kernel's body ----------------------------------------------------------------------
+// The unit loop: S1, barrier, S2 with the next unit's row requests, stores, barrier.  What stands inline
+// in it and not in a function of its own stands there because the function, forced inline, compiles to
+// different code (tools/wfft/isa_same.sh; this kernel's register allocation is on an edge): the outer-radix
+// fold and the two forms of the output twiddles in S1, the three-at-a-time case of S2, the three stores,
+// and the whole of S1 (presumably a forced-inline function is inlined before it is simplified and a
+// lambda after; not looked into further).
 template <class P, bool BYP, bool LONG, bool STAMP, bool SRC32, int PASS>
 __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const double* __restrict__ pm, long pitch, int T,
                                               long n_units, const cd* __restrict__ tw2, double* __restrict__ accg, int D,
@@ -927,8 +1040,8 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
     int lane = tid & 63;
     const int bi = blockIdx.x >> 3;
     const int pass = PASS >= 0 ? PASS : bi % npass;
-    constexpr bool kTwistFold = PASS == 1 && WF_TWIST_FOLD && DftTwisted<R0>::kHave;
-    constexpr bool kMirror = PASS >= 0 && WF_TWIDDLE_MIRROR && R0 % 2 == 0;
+    constexpr bool kTwistFold = PASS == 1 && DftTwisted<R0>::kHave;
+    static_assert(PASS < 0 || R0 % 2 == 0, "a compile-time pass mirrors its output twiddles: even R0 only");
     const long tuple = (blockIdx.x & 7) + 8 * (bi / npass), n_tuples = gridDim.x / npass;
     const int upa = BYP ? (D == 3 ? 2 : 1) : 1;  // units per atom (by-particle mode)
     // with an odd number of columns per atom, atoms 2i and 2i + 1 share a column pair (the last
@@ -957,78 +1070,25 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
     }
     const __amdgpu_buffer_rsrc_t twr =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<cd*>(tw2), 0, (L + kWfStageRows * 64) * 16, 0x00020000);
-    // the tuple's units in order: lag-sum mode pairs tuple + i n_tuples; by-particle mode the
-    // units k < upa of its atoms.  A unit past the end gets an empty buffer: its loads return
-    // zeros and are never used.
-    auto unit_rsrc = [&](long item, int k, int* kind) {
-        long pair = item;
-        const bool live = item < n_units;
-        *kind = 2;
-        if constexpr (BYP) wf_unit_of(live ? item : 0, k, D, &pair, kind);
-        if constexpr (SRC32)
-            return __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float*>(reinterpret_cast<const float*>(pm) + (live ? pair : 0) * pitch * 2), 0,
-                live ? T * 8 : 0, 0x00020000);
-        else
-            return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(pm + (live ? pair : 0) * pitch * 2), 0,
-                                                     live ? T * 16 : 0, 0x00020000);
-    };
-    // row u + 512 j + M jo of the unit (a single real column: that half of the row, imaginary part 0);
-    // SRC32: the raw 8 bytes (one column: its 4 bytes in .x), widened by wf_widen when S1 starts
-    using RowT = std::conditional_t<SRC32, wf_u32x2, cd>;
-    auto load_row = [&](__amdgpu_buffer_rsrc_t rs, int kd, int u, unsigned row_off) -> RowT {
-        if constexpr (SRC32) {
-            // the whole 8-byte row also for a single column (wf_widen picks its half): 4-byte requests
-            // fetch the same lines at half the rate
-            return __builtin_amdgcn_raw_buffer_load_b64(rs, (unsigned)u * 8u, row_off * 8u, 0);
-        } else {
-            if (!BYP || kd == 2) return wf_load(rs, (unsigned)u * 16u, row_off * 16u);
-            return cd{__builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
-                                                     rs, (unsigned)u * 16u + (unsigned)kd * 8u, row_off * 16u, 0)),
-                      0.0};
-        }
-    };
-    [[maybe_unused]] auto wf_widen = [&](wf_u32x2 r, int kd) {
-        if (!BYP || kd == 2)
-            return cd{(double)__builtin_bit_cast(float, (unsigned)r[0]), (double)__builtin_bit_cast(float, (unsigned)r[1])};
-        return cd{(double)__builtin_bit_cast(float, (unsigned)(kd ? r[1] : r[0])), 0.0};
-    };
     // thread tid runs the first-stage butterflies u = tid + NT k, k < K1 (u < 512)
     constexpr int K1 = P::K1, NT = P::NT;
-    RowT xx[K1][R0];
-    auto issue_loads = [&](__amdgpu_buffer_rsrc_t rs, int kd) {
-#pragma unroll
-        for (int k1 = 0; k1 < K1; ++k1) {
-            const int u = tid + NT * k1;  // rows past 512 j + 511 belong to the next j: never loaded
-            if (K1 * NT != N1 && u >= N1) continue;
-            if (!BYP || kd == 2) {
-#pragma unroll
-                for (int j = 0; j < R0; ++j) xx[k1][j] = load_row(rs, 2, u, (unsigned)(N1 * j));
-            } else {
-#pragma unroll
-                for (int j = 0; j < R0; ++j) xx[k1][j] = load_row(rs, kd, u, (unsigned)(N1 * j));
-            }
-        }
-    };
-#ifndef WF_LOAD_PARTS
-#define WF_LOAD_PARTS 4  // 1: all of the next unit's rows in one burst behind S2 (as before round 3)
-#endif
+    using Rows = WfRows<P, BYP, SRC32>;
+    Rows rows;
     // Rows with linear index i = k1 R0 + j.  Plans with kSpreadRows request them along S2, a quarter
-    // at each hook point of the wave's first call; the others in one burst behind S2.
+    // at each hook point of the wave's first call; the others in one burst behind S2 (all of them in one
+    // burst: the code before round 3, parent of bf86bfa).
     constexpr int NR = K1 * R0;
-    constexpr bool kSpread = P::kSpreadRows || (SRC32 && R0 >= 18);  // float32 rows: 2 registers each
-#ifndef WF_SPREAD32_TAIL
-#define WF_SPREAD32_TAIL 0  // float32 rows, R0 = 18, 20: this many of the rows stay behind S2.  Same-box A/B at
-                            // 10000 x 100000 x 3 (float64 slab 8.69 ms): 20 (none along S2) 8.78 ms, 8: 8.30, 4: 8.24, 0: 7.85 ms
-                            // (28 bytes of scratch and still the fastest)
-#endif
+    // float32 rows: 2 registers each.  (R0 = 18, 20 with some of them left behind S2, same-box A/B at
+    // 10000 x 100000 x 3 (float64 slab 8.69 ms): 20 (none along S2) 8.78 ms, 8: 8.30, 4: 8.24, 0: 7.85 ms
+    // (28 bytes of scratch and still the fastest): the switch of 4c6fc48.)
+    constexpr bool kSpread = P::kSpreadRows || (SRC32 && R0 >= 18);
     // float64 rows, R0 = 18, 20, lag sums (the split bodies and the outer-radix kernels; the by-particle kernels would
     // spill 96 - 112 bytes and keep the burst): the 80 row registers are dead during S2 and the 96 of
     // the three sub-series in flight do not die together -- stage c of a sub-series frees its 32.  The requests are
     // written behind each stage c, a scheduling barrier behind each group and none in front: three-at-a-time waves
     // rows [0, 8), [8, 16), [16, NR); two-at-a-time waves
     //   1: [0, 8), [8, NR);   2: all NR behind their S2 (they finish early anyway);   3: [0, 8), [8, 16), the rest behind.
-    // Nothing stays for issue_loads_tail.  0: the burst behind S2, the code before.  The compiler lifts each group over
+    // Form 1 is the code; 0 is the burst behind S2.  All four are the code of 842be10.  The compiler lifts each group over
     // the stage c it stands behind (88 FP64 instructions; the registers are there: 256, no scratch), so every group,
     // the last one too, has a block of butterflies behind it: tools/wfft/isa_table.py shows where they stand.
     // Same-box harness, mean of 250 launches per 24 GB, medians of five rounds: R0 = 20 0: 8.576 ms, 1: 8.356, 2: 8.377,
@@ -1037,32 +1097,13 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
     // outer radix (which spilled 28 / 8 bytes at R0 = 20 / 18 and now does not), 0 against 1: R0 = 20, R = 2 11.277 ->
     // 10.917 ms per 73000 pairs, R = 3 13.846 -> 13.325 ms per 48000; R0 = 18, R = 2 10.921 -> 10.704 ms per 80000.
     // (profiles/r10_headline_ab.txt)
-#ifndef WF_ROWS_ALONG_C
-#define WF_ROWS_ALONG_C 1
-#endif
-    constexpr bool kAlongC = WF_ROWS_ALONG_C && WF_LOAD_PARTS == 4 && !BYP && !SRC32 && NS1 == 3 && P::NLO == 2 && P::REM != 0;
-    constexpr int NSPREAD =
-        WF_LOAD_PARTS != 4 ? 0 : kAlongC ? NR : (kSpread ? (SRC32 && R0 >= 18 ? NR - WF_SPREAD32_TAIL : NR) : 0);
-    auto issue_row = [&](auto ii, __amdgpu_buffer_rsrc_t rs, int kd) {
-        constexpr int i = decltype(ii)::value, k1 = i / R0, j = i % R0;
-        const int u = tid + NT * k1;
-        if (K1 * NT != N1 && u >= N1) return;
-        if (!BYP || kd == 2) xx[k1][j] = load_row(rs, 2, u, (unsigned)(N1 * j));
-        else xx[k1][j] = load_row(rs, kd, u, (unsigned)(N1 * j));
-    };
-    auto issue_loads_part = [&](auto part_c, __amdgpu_buffer_rsrc_t rs, int kd) {
-        constexpr int PART = decltype(part_c)::value;
-        static_for_range<PART * NSPREAD / 4, (PART + 1) * NSPREAD / 4>([&](auto ii) { issue_row(ii, rs, kd); });
-    };
-    auto issue_loads_tail = [&](__amdgpu_buffer_rsrc_t rs, int kd) {
-        static_for_range<NSPREAD, NR>([&](auto ii) { issue_row(ii, rs, kd); });
-    };
+    constexpr bool kAlongC = !BYP && !SRC32 && NS1 == 3 && P::NLO == 2 && P::REM != 0;
+    constexpr bool kAlongS2 = kAlongC || kSpread;  // else: in one burst behind S2
     int kind = 2, nkind = 2;
-    __amdgpu_buffer_rsrc_t crs = unit_rsrc(tuple * grp, 0, &kind);
-    issue_loads(crs, kind);
-    // the wave-local stage twiddles stay in registers for the whole launch where one pass's
-    // accumulators leave room for them (14 fewer loads per wave and unit); the small plans trade
-    // them for a fourth wave per SIMD and load them again before every S2
+    __amdgpu_buffer_rsrc_t crs = wf_unit_rsrc<BYP, SRC32>(pm, pitch, T, n_units, D, tuple * grp, 0, &kind);
+    rows.request_first(tid, crs, kind);
+    // the wave-local stage twiddles stay in registers for the whole launch (14 fewer loads per wave and
+    // unit; the small plans trading them for a fourth wave per SIMD: 5-10 % slower, see WPlan)
     WfTw stw;
     auto load_stage_tw = [&]() {
 #pragma unroll
@@ -1073,7 +1114,7 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
     };
     // (the by-particle variant with an outer radix on the two largest plans loads them again after
     // every first stage instead: 32 registers it does not have while the outer rows are folded in)
-    constexpr bool kTwRes = P::kTwResident && !(BYP && LONG && R0 >= 18);
+    constexpr bool kTwRes = !(BYP && LONG && R0 >= 18);
     if constexpr (kTwRes) load_stage_tw();
     WfAddr wad;
     wad.init(lane, (unsigned)P::sub_base(wave) * kWfSubBytes);
@@ -1090,11 +1131,8 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
     for (long item = tuple * grp; item < n_units;) {
         // ---- S1: radix-R0 butterflies u = tid + NT k over rows u + 512 j of u_c (jo = 0 requested
         // during the previous S2); g = W_M^u, h = W_L^{c u}
-#ifndef WF_REAL_S1_SKIP
-#define WF_REAL_S1_SKIP 0  // 1: a real column's unwanted sub-series are not stored either (wave-uniform branches
-                           // around the output twiddles and LDS stores; costs registers: spills at R0 = 20)
-#endif
-        const unsigned qsel = (WF_REAL_S1_SKIP && BYP && kind != 2) ? P::kRealSel.qmask[pass ? 1 : 0] : ~0u;
+        // (a real column's unwanted sub-series are stored all the same: wave-uniform branches around their output
+        // twiddles and LDS stores cost registers, spills at R0 = 20 -- the code of 68e0c12)
 #pragma unroll
         for (int k1 = 0; k1 < K1; ++k1) {
         const int u = tid + NT * k1;
@@ -1102,22 +1140,11 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
         [[maybe_unused]] cd xwide[SRC32 ? R0 : 1];
         if constexpr (SRC32) {
 #pragma unroll
-            for (int j = 0; j < R0; ++j) xwide[j] = wf_widen(xx[k1][j], kind);
+            for (int j = 0; j < R0; ++j) xwide[j] = wf_widen<BYP>(rows.xx[k1][j], kind);
         }
-        cd(&x)[R0] = wf_pick<SRC32>(xwide, xx[k1]);
+        cd(&x)[R0] = wf_pick<SRC32>(xwide, rows.xx[k1]);
         cd g, g2, h;
-        auto load_seeds = [&]() {
-            if constexpr (PASS == 1 && WF_SEED_DERIVE >= 1) {  // g = W_L^{2u} by squaring: it only starts the odd chain
-                h = wf_load(twr, (unsigned)u * 16u, 0u);
-                g = wf_csqr(h);
-            } else {
-                g = wf_load(twr, (unsigned)(u * R) * 32u, 0u);
-                if (PASS != 0) h = wf_load(twr, (unsigned)(u * pass) * 16u, 0u);
-            }
-            if constexpr ((PASS == 0 && WF_SEED_DERIVE >= 2) || (PASS == 1 && WF_SEED_DERIVE >= 3)) g2 = wf_csqr(g);
-            else g2 = wf_load(twr, (unsigned)(u * R) * 64u, 0u);
-        };
-        if constexpr (!LONG) load_seeds();
+        if constexpr (!LONG) wf_load_seeds<PASS>(twr, u, R, pass, g, g2, h);
         if constexpr (LONG) {
             // u_c[u + 512 j] = sum_jo z[u + 512 j + M jo] U(j, jo), U = W_L^{c (512 j + M jo)} lane-uniform,
             // its index advanced by c 512 per j and c M per jo (mod L: one conditional subtraction)
@@ -1150,7 +1177,7 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
 #pragma unroll
                         for (int i = 0; i < NZ; ++i)
                             if (j0 + i < R0)
-                                z[i] = load_row(crs, decltype(single)::value ? kind : 2, u, (unsigned)(N1 * (j0 + i) + M * jo));
+                                z[i] = wf_load_row<BYP, SRC32>(crs, decltype(single)::value ? kind : 2, u, (unsigned)(N1 * (j0 + i) + M * jo));
 #pragma unroll
                         for (int i = 0; i < NZ; ++i)
                             if (j0 + i < R0) {
@@ -1165,7 +1192,7 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
             if (BYP && kind != 2) outer_rows(std::true_type{});
             else outer_rows(std::false_type{});
             __builtin_amdgcn_sched_barrier(0);
-            load_seeds();  // after the row loads: their registers are free again
+            wf_load_seeds<PASS>(twr, u, R, pass, g, g2, h);  // after the row loads: their registers are free again
         } else if (pass) {
             // pass B twist, lane-uniform part W_{2 R0}^j: literals (wfft_twist.inc) instead of 19
             // scalar loads per butterfly (the split pass-1 body: inside the butterfly, DftTwisted)
@@ -1176,9 +1203,9 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
         }
         if constexpr (kTwistFold) DftTwisted<R0>::run(x);
         else Dft<R0>::run(x);
-        if constexpr (kMirror) {
+        if constexpr (PASS >= 0) {
             // output twiddles t_q = W_L^{u (2q + c)} up to R0/2 only (two chains by g^2 as below); the far half of
-            // the outputs takes the conjugates (WF_TWIDDLE_MIRROR above); each output stored as soon as it is scaled
+            // the outputs takes the conjugates (the mirror, above wf_pass_split); each output stored as soon as it is scaled
             constexpr int H = R0 / 2;
             cd te, to;
             if constexpr (PASS == 0) {  // t_1 = g, t_2 = g2; x[q] t_q (q <= H), x[R0 - q] conj(t_q) (q < H)
@@ -1215,19 +1242,13 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
             // output twiddles W_L^{u (2R q + c)} = h g^q: two chains (even / odd q) by g^2, each
             // output stored as soon as it is scaled (the 20 stores of a wave take ~260 LDS-path
             // cycles: issued in one burst at the end they are fully exposed)
-            cd te, to;
-            if constexpr (PASS == 0) {  // the even chain starts at one: q = 0 goes out as it is, q = 2 takes g2 itself
-                te = cd{1.0, 0.0};
-                to = g;
-            } else {
-                te = pass ? h : cd{1.0, 0.0};
-                to = pass ? cmul(h, g) : g;
-                if (pass) x[0] = cmul(x[0], te);
-            }
-            if (!(WF_REAL_S1_SKIP && BYP) || (qsel & 1u)) lds[u] = x[0];
+            cd te = pass ? h : cd{1.0, 0.0};
+            cd to = pass ? cmul(h, g) : g;
+            if (pass) x[0] = cmul(x[0], te);
+            lds[u] = x[0];
             if constexpr (R0 > 1) {
                 x[1] = cmul(x[1], to);
-                if (!(WF_REAL_S1_SKIP && BYP) || (qsel & 2u)) lds[N1 + u] = x[1];
+                lds[N1 + u] = x[1];
             }
 #pragma unroll
             for (int q = 2; q < R0; ++q) {
@@ -1235,11 +1256,10 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
                     to = cmul(to, g2);
                     x[q] = cmul(x[q], to);
                 } else {
-                    te = (PASS == 0 && q == 2) ? g2 : cmul(te, g2);
+                    te = cmul(te, g2);
                     x[q] = cmul(x[q], te);
                 }
-                // (only the LDS store is skipped: branches around the products as well cost registers)
-                if (!(WF_REAL_S1_SKIP && BYP) || (qsel >> q & 1u)) lds[q * N1 + u] = x[q];
+                lds[q * N1 + u] = x[q];
             }
         }
         }
@@ -1265,27 +1285,14 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
             else nitem = (item & ~(long)(grp - 1)) + grp * n_tuples;
         }
         const int nk = last_of_item ? 0 : k + 1;
-        const __amdgpu_buffer_rsrc_t nrs = unit_rsrc(nitem, nk, &nkind);
+        const __amdgpu_buffer_rsrc_t nrs = wf_unit_rsrc<BYP, SRC32>(pm, pitch, T, n_units, D, nitem, nk, &nkind);
         // the next unit's rows: a quarter at each of four points of the wave's (first) S2 call
         auto row_hook = [&](auto part_c) {
-#if WF_LOAD_PARTS == 4
-            issue_loads_part(part_c, nrs, nkind);
-#endif
+            constexpr int PART = decltype(part_c)::value;
+            if constexpr (kAlongS2) rows.request(wf_part<PART * NR / 4>{}, wf_part<(PART + 1) * NR / 4>{}, tid, nrs, nkind);
         };
         if (BYP && kind != 2) {
-            const int wv = wave_id();
-            // a real column: the wave's share of P::kRealSel, one sub-series at a time
-            // (the next unit's row requests that would ride along S2 go out first)
-            static_for_range<0, 4>([&](auto part_c) { row_hook(part_c); });
-            const unsigned qs = P::kRealSel.qmask[pass ? 1 : 0] >> P::sub_base(wv);
-            const unsigned q1 = P::kRealSel.q1mask[pass ? 1 : 0] >> P::sub_base(wv);
-            // (measured: the waves with two selected sub-series running them interleaved instead -- 13.07
-            // against 13.04 ms at 10000 x 100000 x 3 -- changes nothing: the unit waits for its first stage)
-            static_for_range<0, NS1>([&](auto ss) {
-                constexpr int s = decltype(ss)::value;
-                if ((s < P::NLO || wv < P::REM) && (qs >> s & 1u))
-                    wf_sub512_w<s, P::kRegExchangeSingle>(wsub, stw, acc[s], (q1 >> s & 1u) ? 1.0 : 2.0);
-            });
+            wf_s2_real<P>(wsub, stw, acc, wave_id(), pass, row_hook);
         } else
         if constexpr (NS1 == 3 && P::NLO == 2 && P::REM != 0) {
             // two full slots and a partial third: the waves that own three sub-series take them
@@ -1296,50 +1303,32 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
                 if (wave < P::REM) wf_sub512_x3<P::kRegExchange>(wsub, stw, acc[0], acc[1], acc[2], row_hook);
                 else wf_sub512_x2<0, P::kRegExchange>(wsub, stw, acc[0], acc[1], row_hook);
             } else if constexpr (kAlongC) {  // behind each stage c, into the registers it frees
-                auto rows = [&](auto lo, auto hi) {
-                    static_for_range<decltype(lo)::value, decltype(hi)::value>([&](auto ii) { issue_row(ii, nrs, nkind); });
+                auto behind = [&](auto lo, auto hi) {
+                    rows.request(lo, hi, tid, nrs, nkind);
                     __builtin_amdgcn_sched_barrier(0);  // (they stay where they stand)
                 };
-                constexpr int kLight = WF_ROWS_ALONG_C;  // the two-at-a-time waves' share, see above
                 if (wave < P::REM) {
                     wf_sub512_x3<P::kRegExchange>(wsub, stw, acc[0], acc[1], acc[2], WfNoHook{}, [&](auto sc) {
                         constexpr int s = decltype(sc)::value;
-                        rows(wf_part<8 * s>{}, wf_part<(s == 2 ? NR : 8 * s + 8)>{});
+                        behind(wf_part<8 * s>{}, wf_part<(s == 2 ? NR : 8 * s + 8)>{});
                     });
                 } else {
                     wf_sub512_x2<0, P::kRegExchange>(wsub, stw, acc[0], acc[1], WfNoHook{}, [&](auto sc) {
                         constexpr int s = decltype(sc)::value;
-                        if constexpr (kLight == 1) rows(wf_part<8 * s>{}, wf_part<(s == 1 ? NR : 8)>{});
-                        else if constexpr (kLight == 3) rows(wf_part<8 * s>{}, wf_part<8 * s + 8>{});
+                        behind(wf_part<8 * s>{}, wf_part<(s == 1 ? NR : 8)>{});
                     });
-                    if constexpr (kLight != 1) rows(wf_part<(kLight == 3 ? 16 : 0)>{}, wf_part<NR>{});
                 }
             } else {
                 if (wave < P::REM) wf_sub512_x3<P::kRegExchange>(wsub, stw, acc[0], acc[1], acc[2]);
                 else wf_sub512_x2<0, P::kRegExchange>(wsub, stw, acc[0], acc[1]);
             }
         } else {
-            static_for_range<0, NS1>([&](auto ss) {
-                constexpr int s = decltype(ss)::value;
-                constexpr bool full = s < P::NLO;                       // every wave has this slot
-                constexpr bool nfull = s + 1 < P::NLO;                  // ... and the next one
-                constexpr bool head = full && nfull && (s % 2 == 0);
-                constexpr bool tail = full && s > 0 && (s % 2 == 1);
-                // (the row requests ride on the wave's first call: every wave has slot 0)
-                if constexpr (head) {
-                    if constexpr (s == 0) wf_sub512_x2<s, P::kRegExchange>(wsub, stw, acc[s], acc[s + 1], row_hook);
-                    else wf_sub512_x2<s, P::kRegExchange>(wsub, stw, acc[s], acc[s + 1]);
-                } else if constexpr (!tail) {
-                    if constexpr (s == 0) wf_sub512<s, P::kRegExchangeSingle>(wsub, stw, acc[s], row_hook);
-                    else if (full || wave < P::REM) wf_sub512<s, P::kRegExchangeSingle>(wsub, stw, acc[s]);
-                }
-            });
+            wf_s2_slots<P>(wsub, stw, acc, wave, row_hook);
         }
         if constexpr (STAMP) st_s2end = __builtin_amdgcn_s_memtime();  // behind the wave's own sub-series
         const int wv = wave_id();
         auto store_acc = [&](long row) {  // accg[row][pass][q][cc / 2][lane][cc & 1]
-            const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
-                accg + (row * npass + pass) * (long)M, 0, M * 8, 0x00020000);
+            const __amdgpu_buffer_rsrc_t sr = wf_acc_rsrc(accg, row, npass, pass, M);
 #pragma unroll
             for (int s = 0; s < NS1; ++s) {
                 const int q = P::sub_base(wv) + s;
@@ -1363,25 +1352,24 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
                 zero_pending = true;
             }
         } else {
-            if constexpr (!kMirror)  // (the mirrored bodies store behind the loop)
+            if constexpr (PASS < 0)  // (the mirrored bodies store behind the loop)
                 if (nitem >= n_units) store_acc(tuple);
         }
         __builtin_amdgcn_sched_barrier(0);
-        issue_loads_tail(nrs, nkind);
+        if constexpr (!kAlongS2) rows.request(wf_part<0>{}, wf_part<NR>{}, tid, nrs, nkind);
         kind = nkind, item = nitem, k = nk, crs = nrs;
         if constexpr (STAMP) st_tail += __builtin_amdgcn_s_memtime() - st_s2end;  // the row requests behind S2
         WF_STAMP(1)
         __syncthreads();
     }
-    if constexpr (kMirror) {
+    if constexpr (PASS >= 0) {
         // accg[tuple][pass][q][cc / 2][lane][cc & 1], once per launch.  A mirrored sub-series holds the true bin of
         // position p - 1 at position p = (lane >> 3) + 8 (lane & 7) + 64 cc (mod 512): each of its accumulators goes to
         // the address of that position -- lane - 8; lanes 1 ... 7: lane + 55; lane 0: lane 63 of cc - 1 -- 8 bytes at a
         // time.  The three offsets below carry what differs from lane to lane, the rest is the instruction's constant.
         if (tuple * grp < n_units) {
             const int wv = wave_id();
-            const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
-                accg + (tuple * npass + pass) * (long)M, 0, M * 8, 0x00020000);
+            const __amdgpu_buffer_rsrc_t sr = wf_acc_rsrc(accg, tuple, npass, pass, M);
             // (the lane counted again here: one register fewer across the loop, which R0 = 20 does not have)
             int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             asm volatile("" : "+v"(ln));
@@ -1411,8 +1399,7 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
         // a tuple without units still owes its (zero) row of the partial spectra
         if (tuple * grp >= n_units) {
             const int wv = wave_id();
-            const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
-                accg + (tuple * npass + pass) * (long)M, 0, M * 8, 0x00020000);
+            const __amdgpu_buffer_rsrc_t sr = wf_acc_rsrc(accg, tuple, npass, pass, M);
             int ln = lane;
             if constexpr (kAlongC) {  // (counted again, as above)
                 ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -1442,7 +1429,7 @@ __device__ __forceinline__ void wf_accum_body(unsigned char* smem_raw, const dou
 }
 
 template <class P, bool BYP = false, bool LONG = false, bool STAMP = false, bool SRC32 = false>
-__global__ void __launch_bounds__(P::NT, P::min_waves(BYP, LONG))
+__global__ void __launch_bounds__(P::NT, P::min_waves())
     k_wsplit_accum(const double* __restrict__ pm, long pitch, int T, long n_units,
                    const cd* __restrict__ tw2, double* __restrict__ accg, int D, int R_arg,
                    unsigned long long* __restrict__ stamps) {
@@ -1821,14 +1808,7 @@ __global__ void __launch_bounds__(W1::NT)
     const int n_units = D == 3 ? 2 : 1;
     // the power spectrum of one particle (its units' spectra added) into acc
     auto forward = [&](long atom, double (&accA)[8], double (&accB)[8]) __attribute__((always_inline)) {
-        // units as in k_wbp: the atom's aligned column pair (kind 2) and/or a single column
-        auto unit_of = [&](int k, long* pair, int* kind) {
-            const long c0 = atom * D;
-            if (D == 2) *pair = atom, *kind = 2;
-            else if (D == 1) *pair = c0 >> 1, *kind = (int)(c0 & 1);
-            else if ((c0 & 1) == 0) *pair = (c0 >> 1) + k, *kind = k == 0 ? 2 : 0;
-            else *pair = (c0 >> 1) + k, *kind = k == 0 ? 1 : 2;
-        };
+        // units as in k_wsplit_accum by particle (wf_unit_of): the atom's aligned column pair (kind 2) and/or a single column
         if (SINGLE && n_units == 2 && T <= 128) {
             // both units of the atom in ONE transform, 256 rows apart (their autocorrelations add: k_w1_accum's packing)
             cd v[8];
@@ -1836,7 +1816,7 @@ __global__ void __launch_bounds__(W1::NT)
             for (int k = 0; k < 2; ++k) {
                 long pair;
                 int kind;
-                unit_of(k, &pair, &kind);
+                wf_unit_of(atom, k, D, &pair, &kind);
                 const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<double*>(pm + pair * pitch * 2), 0, T * 16, 0x00020000);
 #pragma unroll
@@ -1852,7 +1832,7 @@ __global__ void __launch_bounds__(W1::NT)
         for (int k = 0; k < n_units; ++k) {
             long pair;
             int kind;
-            unit_of(k, &pair, &kind);
+            wf_unit_of(atom, k, D, &pair, &kind);
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<double*>(pm + pair * pitch * 2), 0, T * 16, 0x00020000);
             cd v[8];
