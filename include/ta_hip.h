@@ -371,6 +371,59 @@ int ta_kcurrent_correlate(ta_ctx *ctx, int fft, const double *h_current, int n_k
                           int dim, double *h_long, double *h_trans);
 int ta_kcurrent_tile(int *kc, int *frames_f64, int *frames_f32);
 
+/* ta_partial_density : the species-resolved density behind the partial intermediate scattering functions F_ab(k, t) and the
+ *              partial structure factors S_ab(k) (PartialScattering), for n_k wavevectors h_kvecs (n_k, dim), rad per length
+ *              unit, one component per staged column, of the positions in slab 0.  h_species: one label in
+ *              0 ... n_species - 1 per atom, in any order (S = n_species <= TA_ONSAGER_MAX_SPECIES); h_weights: one weight
+ *              per atom (scattering length, charge), or NULL (all 1).  With T frames:
+ *                phi_j[t, n]      = sum_d k_j[d] x[t, n, d]
+ *                rho[j, a, t]     = sum_{n: species[n] = a} w_n ( cos phi_j[t, n], sin phi_j[t, n] )               (n_k, S, T, 2)
+ *                cross[j, tau, a, b] = 1/2 1/(T - tau) sum_{t < T - tau} Re( conj(rho[j, a, t]) rho[j, b, t + tau]
+ *                                                                        + conj(rho[j, b, t]) rho[j, a, t + tau] )  (n_k, T, S, S)
+ *              Lag 0 is kept; NOTHING is divided by an atom count.  h_cross may be NULL (not computed).  The density adds up
+ *              over atoms -- shards, group members, ranks; the cross term does not: it is formed once from the summed
+ *              density (ta_partial_cross; needs no staged slab and touches none).  Summed over a and b with unit weights
+ *              the cross term is h_coll of ta_scatter.
+ *              The pass k_species_density is k_kcurrent without the velocity slab and with the sum split by the label: it
+ *              reads each atom ONCE per launch, in the element type the slab has (a float32 row pair in one 16-byte load,
+ *              widened in registers), keeps ST x KC complex sums for each of its F frames per thread in registers over
+ *              the atoms of its group (ST: the smallest of 1, 2, 4, 8 that holds S; the label picks the accumulator by a
+ *              workgroup-uniform branch) and writes one partial sum per group; k_sum_partials adds the groups in a fixed
+ *              order (no atomics: the same bits from run to run).  The groups depend on the slab and the device only.
+ *              Chunking: one launch per KC wavevectors (ta_partial_density_tile); option "partial_chunk" n >= 1 forces
+ *              min(n, KC).  The results do not depend on it bit for bit.  The partial buffer (groups x KC x S x T x 16
+ *              bytes, at most 1 GiB) does not depend on n_k; ta_trim releases it.
+ *              Phases as ta_scatter's: q = k / (2 pi), u = sum_d q[d] x[d] (a product, then fma), r = u - rint(u),
+ *              (cos, sin)(2 pi r); each sum is one fma of w_n with the cosine and one with the sine.  With
+ *              U = max |k . x| / (2 pi), n_a the atoms of species a and W_a = sum_{n in a} |w_n| each component of rho[., a, .]
+ *              is within W_a (2 pi (dim + 2) 2^-53 U + (10 + n_a) 2^-53) of the exact sum.  The cross term: a complex
+ *              density is a species sum with dim 2 (Re(conj(p) r) is the dot product), so it is ta_current_cross's
+ *              polarisation on the S^2 pseudo-particles rho_a, rho_a + rho_b, rho_a - rho_b of every wavevector, ONE
+ *              by-particle evaluation of ta_vacf_fft (fft = 1) / ta_vacf_direct (fft = 0) for all wavevectors of a chunk
+ *              (as many as keep its workspace under 1 GiB); symmetric in (a, b) bit for bit; a species without atoms (or
+ *              with an all-zero density) gives exact zeros in its density and in its row and column.  Accuracy: the
+ *              library's usual 1e-10 of max(cross[j, 0, a, a], cross[j, 0, b, b]), NOT of |cross[j, tau, a, b]| -- an off-diagonal
+ *              element is a difference of two autocorrelations of that size (ta_onsager gives the same warning).
+ *              Checked before anything is written, TA_E_INVALID: fft other than 0 / 1, n_species outside
+ *              1 ... TA_ONSAGER_MAX_SPECIES, NULL h_kvecs, n_k outside 1 ... TA_SCATTER_MAX_K, a non-finite component,
+ *              NULL h_species or h_density, a label outside 0 ... S - 1, n_atoms * dim not below 2^31; nothing staged:
+ *              TA_E_STATE.  CPU backend: the same phase arithmetic, a plain sum in atom order per species, ta_current_cross's
+ *              routine on dim 2 per wavevector.  Timings: the main kernel of ta_last_timing / ta_timing_history is the LAST
+ *              launch of k_species_density alone -- with n_k > KC one chunk's launch, not the whole pass -- unless an
+ *              evaluation after it records its own; the time of all launches is in ta_kernel_timeline, which names the
+ *              kernels k_species_density, k_sum_partials, k_onsager_combos, the lag kernels, k_partial_finish.
+ * ta_partial_cross : the cross term (n_k, n_frames, S, S) of a host density (n_k, S, n_frames, 2), e.g. the sum of several
+ *              shards' densities; TA_E_INVALID for fft other than 0 / 1, n_species or n_k out of range, a NULL array,
+ *              n_frames outside 1 ... 2^30.
+ * ta_partial_density_tile : for n_species (1 ... TA_ONSAGER_MAX_SPECIES, else TA_E_INVALID) the species slots ST and the
+ *              wavevectors per launch KC of the tile that serves it, and the frames per thread F on a float64 / a float32
+ *              slab (a workgroup of k_species_density covers 256 F frames); each pointer may be NULL.                  */
+int ta_partial_density(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, int n_species, const int32_t *h_species,
+                       const double *h_weights, double *h_density, double *h_cross);
+int ta_partial_cross(ta_ctx *ctx, int fft, const double *h_density, int n_k, int n_species, int64_t n_frames,
+                     double *h_cross);
+int ta_partial_density_tile(int n_species, int *st, int *kc, int *frames_f64, int *frames_f32);
+
 /* ta_vanhove : the self part of the van Hove function of the positions in slab 0 (VanHoveSelf): for n_lags frame lags
  *              h_lags (strictly increasing, 0 <= lag < n_frames) the histogram of the displacements after a lag in n_bins
  *              bins of width dr (r_max = n_bins dr) and their second and fourth moments.  With T frames, D staged columns:
@@ -814,6 +867,12 @@ int ta_orient_staged(ta_ctx *ctx, int fft, int mode, int64_t n_vectors, const in
 int ta_kcurrent_staged(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, const double *d_weights, double *d_current,
                        double *d_long, double *d_trans, void *stream);
 
+/* h_kvecs: HOST wavevectors; d_species (n_atoms) int32 device labels (one outside 0 ... n_species - 1 is skipped: only a host
+ * array can be checked), d_weights: device weights (n_atoms) or NULL; d_density (n_k, S, n_frames, 2), d_cross (n_k, n_frames,
+ * S, S) or NULL: device outputs; slab 0 (the positions) is read in the element type it has */
+int ta_partial_density_staged(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, int n_species, const int32_t *d_species,
+                              const double *d_weights, double *d_density, double *d_cross, void *stream);
+
 /* h_lags: HOST lags, as for ta_vanhove_dev; slab 0 (the positions) is read in the element type it has */
 int ta_vanhove_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *d_counts,
                       double *d_moments, void *stream);
@@ -917,6 +976,11 @@ int ta_group_scatter(ta_group *g, int fft, int n_k, const double *h_kvecs, doubl
  * summed current runs on the first member that holds atoms.                                                          */
 int ta_group_kcurrent(ta_group *g, int fft, int n_k, const double *h_kvecs, const double *h_weights, double *h_current,
                       double *h_long, double *h_trans);
+/* ta_group_partial_density: ta_partial_density on every member with the same wavevectors (checked first) and its slice of
+ * h_species and h_weights (all n_atoms; weights or NULL): the members' densities are SUMMED on the host in member order,
+ * then ONE cross term of the summed density runs on the first member that holds atoms.                               */
+int ta_group_partial_density(ta_group *g, int fft, int n_k, const double *h_kvecs, int n_species, const int32_t *h_species,
+                             const double *h_weights, double *h_density, double *h_cross);
 /* ta_group_vanhove: ta_vanhove on every member with the same lags and bins (checked first): the members' counts are SUMMED
  * on the host as int64, their moments in member order.                                                               */
 int ta_group_vanhove(ta_group *g, int n_lags, const int64_t *h_lags, int n_bins, double dr, int64_t *h_counts,
@@ -1031,6 +1095,8 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      min(n, n_k)); the results do not depend on it;
  *   "kcurrent_chunk" n : wavevectors per launch of ta_kcurrent*'s pass (0, the default: KC, the tile's count; n >= 1:
  *                      min(n, KC)); the results do not depend on it;
+ *   "partial_chunk" n : wavevectors per launch of ta_partial_density*'s pass (0, the default: KC, the count of the tile
+ *                      that serves the call's species; n >= 1: min(n, KC)); the results do not depend on it;
  *   "vanhove_chunk" n : lags per pass of ta_vanhove* (0, the default: as many as fit 64 KiB of LDS; n >= 1: min(n, n_lags,
  *                      that count)); the results do not depend on it;
  *   "overlap_chunk" n : lags per launch of ta_overlap* (0, the default: floor(S / n_cutoffs), S of ta_overlap_tile; n >= 1:

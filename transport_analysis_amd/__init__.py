@@ -1,7 +1,7 @@
 """transport_analysis_amd — MI355X-native time-correlation kernels behind the
 transport-analysis API (VelocityAutocorr, ViscosityHelfand), MDAnalysis' EinsteinMSD, ConductivityHelfand and its species-resolved form, OnsagerHelfand, and their Green-Kubo
 (velocity) twins, ConductivityGreenKubo and OnsagerGreenKubo, and the intermediate scattering functions F_s(k, t) and F(k, t),
-IntermediateScattering, and their real-space partners, the self van Hove function G_s(r, t) with the non-Gaussian parameter,
+IntermediateScattering, with their species-resolved partials F_ab(k, t) and S_ab(k), PartialScattering, and their real-space partners, the self van Hove function G_s(r, t) with the non-Gaussian parameter,
 VanHoveSelf, and the distinct van Hove function G_d(r, t) with the radial distribution function g(r), VanHoveDistinct, and
 the longitudinal and transverse current correlation functions C_L(k, t) and C_T(k, t), CurrentCorrelation, and the
 self-overlap Q(t) with the four-point susceptibility chi_4(t), DynamicSusceptibility, and the rotational correlation functions
@@ -17,6 +17,7 @@ from .conductivity import ConductivityHelfand  # noqa: F401
 from .onsager import OnsagerHelfand  # noqa: F401
 from .greenkubo import ConductivityGreenKubo, OnsagerGreenKubo  # noqa: F401
 from .scattering import IntermediateScattering, kvectors_from_box  # noqa: F401
+from .partial_scattering import PartialScattering  # noqa: F401
 from .current_correlation import CurrentCorrelation  # noqa: F401
 from .vanhove import VanHoveSelf, log_lags  # noqa: F401
 from .vanhove_distinct import VanHoveDistinct  # noqa: F401

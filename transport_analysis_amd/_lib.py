@@ -42,6 +42,8 @@ _ONSAGER = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, fft, n_species, h
 _SELF = _int(_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, quantity, fft, n_species, h_species, h_weights, h_self, h_counts)
 _SCATTER = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp)  # (handle, fft, n_k, h_kvecs, h_self, h_density, h_coll)
 _KCURRENT = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp)  # (handle, fft, n_k, h_kvecs, h_weights, h_current, h_long, h_trans)
+# (handle, fft, n_k, h_kvecs, n_species, h_species, h_weights, h_density, h_cross)
+_PARTIAL = _int(_vp, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp)
 _VANHOVE = _int(_vp, _ci, _vp, _ci, _dbl, _vp, _vp)  # (handle, n_lags, h_lags, n_bins, dr, h_counts, h_moments)
 _OVERLAP = _int(_vp, _ci, _vp, _ci, _vp, _vp)  # (handle, n_lags, h_lags, n_cutoffs, h_cutoffs, h_q)
 
@@ -78,6 +80,9 @@ _API = {
     "ta_kcurrent": _KCURRENT, "ta_kcurrent_correlate": _int(_vp, _ci, _vp, _ci, _vp, _i64, _ci, _vp, _vp),
     "ta_kcurrent_tile": _int(_P(_ci), _P(_ci), _P(_ci)),
     "ta_kcurrent_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp),
+    "ta_partial_density": _PARTIAL, "ta_partial_cross": _int(_vp, _ci, _vp, _ci, _ci, _i64, _vp),
+    "ta_partial_density_tile": _int(_ci, _P(_ci), _P(_ci), _P(_ci), _P(_ci)),
+    "ta_partial_density_staged": _int(_vp, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_vanhove": _VANHOVE, "ta_vanhove_staged": _int(_vp, _ci, _vp, _ci, _dbl, _vp, _vp, _vp),
     "ta_vanhove_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _ci, _dbl, _vp, _vp, _vp),
     "ta_overlap": _OVERLAP, "ta_overlap_tile": _int(_P(_ci)), "ta_overlap_staged": _int(_vp, _ci, _vp, _ci, _vp, _vp, _vp),
@@ -114,7 +119,8 @@ _API = {
     "ta_group_vacf_fft": _HOST, "ta_group_vacf_direct": _HOST, "ta_group_helfand_msd": _int(_vp, _vp, _dbl, _vp, _vp),
     "ta_group_msd": _int(_vp, _ci, _vp, _vp), "ta_group_conductivity": _COND, "ta_group_unwrap": _UNWRAP,
     "ta_group_onsager": _ONSAGER, "ta_group_current": _ONSAGER, "ta_group_species_self": _SELF,
-    "ta_group_scatter": _SCATTER, "ta_group_kcurrent": _KCURRENT, "ta_group_vanhove": _VANHOVE,
+    "ta_group_scatter": _SCATTER, "ta_group_kcurrent": _KCURRENT, "ta_group_partial_density": _PARTIAL,
+    "ta_group_vanhove": _VANHOVE,
     "ta_group_overlap": _OVERLAP,
 }
 EXPORTS = tuple(_API)
@@ -201,6 +207,17 @@ def kcurrent_tile():
     kc, f64, f32 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     lib().ta_kcurrent_tile(ctypes.byref(kc), ctypes.byref(f64), ctypes.byref(f32))
     return {"KC": kc.value, "F64": f64.value, "F32": f32.value}
+
+
+def partial_density_tile(n_species):
+    """{"ST", "KC", "F64", "F32"}: the species slots and the wavevectors per launch of the k_species_density tile that serves
+    `n_species`, and the frames per thread on a float64 / float32 slab (a workgroup covers 256 F frames),
+    ta_partial_density_tile"""
+    st, kc, f64, f32 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = lib().ta_partial_density_tile(int(n_species), ctypes.byref(st), ctypes.byref(kc), ctypes.byref(f64), ctypes.byref(f32))
+    if rc != 0:
+        raise TAError(rc, lib().ta_last_error(None).decode())
+    return {"ST": st.value, "KC": kc.value, "F64": f64.value, "F32": f32.value}
 
 
 def overlap_tile():
@@ -551,6 +568,20 @@ class _Staged:
         self._call("kcurrent", int(fft), K, _ptr(k), _ptr(w), _ptr(cur), _ptr(lon), _ptr(tr))
         return cur, lon, tr
 
+    def partial_density(self, fft, kvectors, species, n_species=None, weights=None, cross=True):
+        """Species-resolved density of slab 0 (the positions) and its cross term, ta_partial_density: `kvectors` (n_k, dim) in
+        rad per length unit, `species` one integer label in 0 ... n_species - 1 per staged atom (n_species: default the
+        largest label + 1), `weights` one per atom or None (all 1): (density (n_k, n_species, n_frames, 2) = sum_{n in a} w_n
+        (cos, sin)(k . x_n), cross (n_k, n_frames, n_species, n_species) with lag 0, or None); nothing is divided by the
+        number of atoms.  A group: the members' densities are summed, then ONE cross term runs."""
+        T, _, D = self._staged_shape()
+        k, K = self._kvectors(kvectors, D)
+        lab, S, w, n = self._species_args(species, n_species, weights)
+        rho = np.empty((K, n, T, 2), dtype=np.float64)
+        c = np.empty((K, T, n, n), dtype=np.float64) if cross else None
+        self._call("partial_density", int(fft), K, _ptr(k), S, _ptr(lab), _ptr(w), _ptr(rho), _ptr(c))
+        return rho, c
+
     @staticmethod
     def _lags(lags):
         lg = np.ascontiguousarray(lags, dtype=np.int64)
@@ -742,6 +773,17 @@ class Context(_Staged):
         self._call("kcurrent_correlate", int(fft), _ptr(a), K, _ptr(k), T, D, _ptr(lon), _ptr(tr))
         return lon, tr
 
+    def partial_cross(self, density, fft):
+        """cross (n_k, n_frames, S, S) of a given (n_k, S, n_frames, 2) density, e.g. the sum of several shards' densities
+        (ta_partial_cross): needs no staged slab and leaves the context's slabs as they are."""
+        a = np.ascontiguousarray(density, dtype=np.float64)
+        if a.ndim != 4 or a.shape[3] != 2:
+            raise ValueError(f"density: shape {a.shape}, expected (n_k, n_species, n_frames, 2)")
+        K, S, T, _ = a.shape
+        c = np.empty((K, T, S, S), dtype=np.float64)
+        self._call("partial_cross", int(fft), _ptr(a), K, S, T, _ptr(c))
+        return c
+
     # -- device-pointer compute (asynchronous) --------------------------
     def vacf_fft_dev(self, d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp=0, ld_bp=0, stream=0):
         self._call("vacf_fft_dev", d_vel, n_frames, n_atoms, dim, ld_row, d_lagsum, d_bp or None, ld_bp, stream or None)
@@ -827,6 +869,13 @@ class Context(_Staged):
         k, K = self._kvectors(kvectors, self._staged_shape()[2])
         self._call("kcurrent_staged", int(fft), K, _ptr(k), d_weights or None, d_current or None, d_long or None,
                    d_trans or None, stream or None)
+
+    def partial_density_staged(self, fft, kvectors, n_species, d_species, d_density, d_cross=0, d_weights=0, stream=0):
+        """`kvectors`: HOST wavevectors (n_k, dim) (checked by the library before anything is written); d_species (int32
+        labels), d_weights: device"""
+        k, K = self._kvectors(kvectors, self._staged_shape()[2])
+        self._call("partial_density_staged", int(fft), K, _ptr(k), int(n_species), d_species or None, d_weights or None,
+                   d_density or None, d_cross or None, stream or None)
 
     def vanhove_dev(self, d_pos, n_frames, n_atoms, dim, ld_row, lags, n_bins, dr, d_counts=0, d_moments=0, stream=0):
         """`lags`: HOST frame lags (checked by the library before anything is written); d_counts (n_lags, n_bins + 1) int64"""

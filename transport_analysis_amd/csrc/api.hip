@@ -124,6 +124,7 @@ private:
     X(timeline, 0, nullptr)        /* record the kernel timeline of every compute call (ta_kernel_timeline) */             \
     X(scatter_chunk, 0, opt_check_scatter_chunk) /* wavevectors per pass of ta_scatter* (0: as many as fit kScatterBudget) */ \
     X(kcurrent_chunk, 0, opt_check_kcurrent_chunk) /* wavevectors per launch of k_kcurrent (0: the tile's own count) */     \
+    X(partial_chunk, 0, opt_check_partial_chunk) /* wavevectors per launch of k_species_density (0: the tile's own count) */ \
     X(vanhove_chunk, 0, opt_check_vanhove_chunk) /* lags per pass of ta_vanhove* (0: as many as fit a workgroup's LDS) */ \
     X(overlap_chunk, 0, opt_check_overlap_chunk) /* lags per launch of ta_overlap* (0: as many as the kernel's tile holds) */ \
     X(vanhove_distinct_chunk, 0, opt_check_vanhove_distinct_chunk) /* lags per pass of ta_vanhove_distinct* (0: as many as fit kVhdBudget) */ \
@@ -188,6 +189,11 @@ struct ta_ctx {
     // behind them, the outputs of host-facing calls
     DevBuf kcur_part{workspaces, kTrimmed}, kcur_work{workspaces, kTrimmed}, kcur_out{workspaces, kKept};
     HostTable kcur_tab{workspaces, tables};
+    // partial scattering functions (partial_pm): the partial sums of one chunk of wavevectors (trimmed; its size does not
+    // depend on their number or on the species), the wavevectors in turns (and a host call's weights behind them), a host
+    // call's labels and outputs; the cross term's pseudo-particles and lag sums use the Onsager workspaces
+    DevBuf psd_part{workspaces, kTrimmed}, psd_lab{workspaces, kKept}, psd_out{workspaces, kKept};
+    HostTable psd_tab{workspaces, tables};
     // self van Hove function (vanhove_pm): the lags (int64) with the squared edges behind them, the uint64 histogram and
     // the workgroups' moment partials (the scratch: trimmed), the outputs of host-facing calls
     HostTable vh_tab{workspaces, tables};
@@ -1517,6 +1523,92 @@ int kcurrent_pm(ta_ctx* ctx, bool fft, const Slab& s, int K, const double* d_w, 
     return call_end(ctx, st);
 }
 
+// ---- partial scattering functions (species_density.hip) --------------------------------------------------------------
+// The budget of k_species_density's partial-sum buffer, G (ST KC <= 16) pitch 16 bytes, as kKcurBudget; and of the cross
+// term's workspaces (the pseudo-particles and their by-particle lag sums of one chunk of wavevectors): choices, not
+// measurements.  At 10000 frames and 8 species a wavevector's share of the latter is 15 MB: the cap bites above ~70.
+constexpr size_t kPartialBudget = (size_t)1 << 30;
+constexpr size_t kPartialCrossBudget = (size_t)1 << 30;
+
+// the family's argument checks (GPU and CPU contexts, one set of messages), in the order of ta_scatter and ta_onsager; D:
+// the components per wavevector (0: not known, nothing staged -- reported after these)
+int partial_args(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, int D, int S, const void* species, const void* o_density) {
+    return check_partial(fail, ctx, fft, n_k, h_kvecs, D, S, species, o_density);
+}
+// ... and, behind them, the staged slab and its columns
+int partial_slab(ta_ctx* ctx) {
+    TA_CHECK(check_staged(ctx));
+    return check_cols(ctx, "partial density: ", ctx->st_A, ctx->st_D);
+}
+
+// The host half of one call, before it is opened: ONE table -- the wavevectors in turns (q = k / 2 pi), then a host-facing
+// call's weights (n_w of them) -- queued for upload on `st`.  Nothing on the device has been written when this fails.
+int partial_plan(ta_ctx* ctx, int K, const double* h_kvecs, int D, const double* h_w, int64_t n_w, hipStream_t st) {
+    const size_t n = (size_t)K * D;
+    void* h = nullptr;
+    TA_CHECK(ctx->psd_tab.begin(ctx, sizeof(double) * (n + (h_w ? (size_t)n_w : 0)), &h));
+    double* q = (double*)h;
+    for (size_t i = 0; i < n; ++i) q[i] = phase_turns(h_kvecs[i]);
+    if (h_w) memcpy(q + n, h_w, sizeof(double) * (size_t)n_w);
+    return ctx->psd_tab.send(ctx, st);
+}
+
+// cross (K, T, S, S) of the densities (K, S, T, 2) at d_density: a complex density is a species sum with dim 2, so wavevector
+// j's block is the (S, T, 2) sums coll_cross takes, and its S^2 pseudo-particles rho_a, rho_a + rho_b, rho_a - rho_b are S^2
+// whole pairs.  Per chunk of Kx wavevectors -- as many as keep the Onsager workspaces under kPartialCrossBudget, which bounds
+// memory and nothing else: a particle's autocorrelation does not depend on its neighbours -- k_onsager_combos per wavevector,
+// ONE by-particle evaluation of the chunk's Kx S^2 particles by the VACF's dispatch, and the finish.
+int partial_cross(ta_ctx* ctx, bool fft, const double* d_density, int K, int S, int64_t T, double* d_cross, hipStream_t st) {
+    const int64_t P1 = (int64_t)S * S, pitch = pm_pitch(T);
+    const size_t per_k = pm_bytes(T, 2 * P1) + sizeof(double) * (size_t)(T * P1);
+    const int Kx = (int)std::max<size_t>(1, std::min<size_t>((size_t)K, kPartialCrossBudget / per_k));
+    TA_CHECK(ensure(ctx, ctx->ons_pm, pm_bytes(T, 2 * P1 * Kx)));
+    TA_CHECK(ensure(ctx, ctx->ons_bp, sizeof(double) * (size_t)(T * P1 * Kx + T) + sizeof(int) * TA_ONSAGER_MAX_SPECIES * (size_t)Kx));
+    double* pm = (double*)ctx->ons_pm.p;
+    double* bp = (double*)ctx->ons_bp.p;
+    double* lagsum = bp + T * P1 * Kx;
+    int* nz = (int*)(lagsum + T);
+    for (int j0 = 0; j0 < K; j0 += Kx) {
+        const int kx = std::min(Kx, K - j0);
+        TA_HIP_TRY(ctx, hipMemsetAsync(nz, 0, sizeof(int) * TA_ONSAGER_MAX_SPECIES * (size_t)kx, st));
+        for (int b = 0; b < kx; ++b)
+            TA_LAUNCH(ctx, "k_onsager_combos", st,
+                      launch_onsager_combos(d_density + (size_t)(j0 + b) * S * T * 2, S, (long)T, 2, (long)pitch,
+                                            pm + (size_t)b * P1 * pitch * 2, nz + b * TA_ONSAGER_MAX_SPECIES, st));
+        TA_CHECK(acf_impl(ctx, fft, pm, pitch, T, P1 * kx, 2, lagsum, bp, P1 * kx, st));
+        TA_LAUNCH(ctx, "k_partial_finish", st, launch_partial_finish(bp, kx, S, (long)T, nz, d_cross + (size_t)j0 * T * P1, st));
+    }
+    return TA_OK;
+}
+
+// One call on the pair-major position slab of either element type, read as it is (the caller has opened the call's bracket,
+// it is closed here; partial_plan has queued the table).  Per chunk of at most KC wavevectors (the tile of the call's species
+// count; "partial_chunk" n: min(n, KC)) ONE pass and the fixed-order sum of its partials into the density (K, S, T, 2); after
+// the last chunk the cross term.  The atom groups depend on the slab and the device only: the same bits for every chunk
+// size.  ev[1] / ev[2] bracket the (last) pass, unless an evaluation after it records its own.
+int partial_pm(ta_ctx* ctx, bool fft, const Slab& s, int K, int S, const int32_t* d_species, const double* d_w, double* d_density,
+               double* d_cross) {
+    const int64_t pitch = s.pitch, T = s.T, A = s.A;
+    hipStream_t st = s.st;
+    int ST = 1, KC = 1, f64 = 1, f32 = 2;
+    species_density_tile(S, &ST, &KC, &f64, &f32);
+    const int Kc = ctx->opt_partial_chunk > 0 ? (int)std::min<int64_t>(ctx->opt_partial_chunk, KC) : KC;
+    const int G = species_density_parts(ctx->n_cu, s.f32, (long)pitch, (long)A, kPartialBudget);
+    TA_CHECK(ensure(ctx, ctx->psd_part, (size_t)G * KC * S * (size_t)T * 16));
+    double* part = (double*)ctx->psd_part.p;
+    const double* d_q = (const double*)ctx->psd_tab.dev.p;
+    const size_t per = (size_t)S * T * 2;  // doubles of one wavevector's density
+    for (int j0 = 0; j0 < K; j0 += Kc) {
+        const int kc = std::min(Kc, K - j0);
+        TA_LAUNCH_MAIN(ctx, "k_species_density", st,
+                       launch_species_density(s.pm, s.f32, (long)pitch, (long)T, (long)A, s.D, d_q + (size_t)j0 * s.D, kc, S, d_species,
+                                              d_w, part, G, st));
+        TA_LAUNCH(ctx, "k_sum_partials", st, launch_sum_partials(part, G, (long)(kc * per), d_density + j0 * per, st));
+    }
+    if (d_cross) TA_CHECK(partial_cross(ctx, fft, d_density, K, S, T, d_cross, st));
+    return call_end(ctx, st);
+}
+
 // ---- self van Hove function (vanhove.hip) and self-overlap (overlap.hip): what their host halves share --------------
 // The host half of one call, before it is opened: the lags, then the n_tail doubles that fill(tail) forms once, here, queued
 // for upload on `st` as one table.  Nothing on the device has been written when this fails.
@@ -2164,6 +2256,9 @@ int opt_set_cpu_threads(ta_ctx* ctx, int64_t value) {
 int opt_flush_commits(ta_ctx* ctx, int64_t) { return ctx->commits.flush(); }
 int opt_check_kcurrent_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "kcurrent_chunk: 0 (the tile's count) or the wavevectors per launch");
+}
+int opt_check_partial_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "partial_chunk: 0 (the tile's count) or the wavevectors per launch");
 }
 int opt_check_scatter_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "scatter_chunk: 0 (automatic) or the wavevectors per pass");
@@ -2909,6 +3004,22 @@ int ta_kcurrent_staged(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, con
     });
 }
 
+// Partial scattering functions: slab 0 holds the positions, read in the element type it has (never widened); the wavevectors
+// are a HOST array, the labels and weights device ones (weights or NULL); there is no frame-major entry
+int ta_partial_density_staged(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, int n_species, const int32_t* d_species,
+                              const double* d_weights, double* d_density, double* d_cross, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    return slab_entry(
+        ctx, nullptr, stream,
+        [&]() -> int {
+            TA_CHECK(partial_args(ctx, fft, n_k, h_kvecs, ctx->st_nslabs ? ctx->st_D : 0, n_species, d_species, d_density));
+            return partial_slab(ctx);
+        },
+        [&](const Slab& s) { return partial_plan(ctx, n_k, h_kvecs, s.D, nullptr, 0, s.st); },
+        [&](const Slab& s) { return partial_pm(ctx, fft != 0, s, n_k, n_species, d_species, d_weights, d_density, d_cross); });
+    });
+}
+
 // Self van Hove function: slab 0 / d_pos holds the positions; the staged slab is read in its own element type (never
 // widened); the lags are a HOST array: they size the launches, and vanhove_plan runs before the call is opened
 static int vanhove_entry(ta_ctx* ctx, const DevSrc* dev, int n_lags, const int64_t* h_lags, int n_bins, double dr,
@@ -3436,6 +3547,47 @@ int kcurrent_correlate_host(ta_ctx* ctx, int fft, const double* h_current, int K
         [&] { return HostCopy{h_long, out + n_cur, KT}; }, [&] { return HostCopy{h_trans, out + n_cur + KT, KT}; });
 }
 
+// Partial-density share of a host-facing call, queued on ctx->stream and not waited for: the table (wavevectors, checked by
+// the caller, and this context's atoms' weights) and the labels (checked by the caller) uploaded, the density (K, S, T, 2),
+// then (cross) the cross term (K, T, S, S) left on the device in *d_out
+int partial_launch(ta_ctx* ctx, int fft, int K, const double* h_kvecs, int S, const int32_t* h_species, const double* h_w,
+                   bool cross, double** d_out) {
+    double* out = nullptr;
+    TA_CHECK(slab_entry(
+        ctx, nullptr, ctx->stream, [&] { return partial_slab(ctx); },
+        [&](const Slab& s) -> int {
+            TA_CHECK(partial_plan(ctx, K, h_kvecs, s.D, h_w, s.A, ctx->stream));
+            TA_CHECK(ensure(ctx, ctx->psd_lab, sizeof(int32_t) * (size_t)s.A));
+            TA_CHECK(ensure(ctx, ctx->psd_out, sizeof(double) * (size_t)K * s.T * S * (2 + S)));
+            out = (double*)ctx->psd_out.p;
+            TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->psd_lab.p, h_species, sizeof(int32_t) * s.A, hipMemcpyHostToDevice, ctx->stream));
+            return TA_OK;
+        },
+        [&](const Slab& s) {
+            const double* d_w = h_w ? (const double*)ctx->psd_tab.dev.p + (size_t)K * s.D : nullptr;
+            return partial_pm(ctx, fft != 0, s, K, S, (const int32_t*)ctx->psd_lab.p, d_w, out,
+                              cross ? out + (size_t)K * S * s.T * 2 : nullptr);
+        }));
+    *d_out = out;
+    return TA_OK;
+}
+
+// The cross term (K, T, S, S) of a host (K, S, T, 2) density (ta_partial_cross)
+int partial_cross_host(ta_ctx* ctx, int fft, const double* h_density, int K, int S, int64_t T, double* h_cross) {
+    const size_t n_den = (size_t)K * S * T * 2;
+    double* out = nullptr;
+    return host_sums_call(
+        ctx,
+        [&](hipStream_t st) -> int {
+            TA_CHECK(ensure(ctx, ctx->psd_out, sizeof(double) * (size_t)K * T * S * (2 + S)));
+            out = (double*)ctx->psd_out.p;
+            TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_density, sizeof(double) * n_den, hipMemcpyHostToDevice, st));
+            return TA_OK;
+        },
+        [&](hipStream_t st) { return partial_cross(ctx, fft != 0, out, K, S, T, out + n_den, st); },
+        [&] { return HostCopy{h_cross, out + n_den, (size_t)K * T * S * S}; });
+}
+
 // One context's unwrap of staged slab `slab` (ta_unwrap, ta_group_unwrap), queued on ctx->stream behind the queued commits
 // and bracketed by the timing events: the box table's copy (box.tab must stay valid until host_wait), then the kernel
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes) {
@@ -3679,6 +3831,49 @@ int ta_kcurrent_tile(int* kc, int* frames_f64, int* frames_f32) {
     if (kc) *kc = a;
     if (frames_f64) *frames_f64 = b;
     if (frames_f32) *frames_f32 = c;
+    return TA_OK;
+}
+
+int ta_partial_density(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, int n_species, const int32_t* h_species,
+                       const double* h_weights, double* h_density, double* h_cross) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(partial_args(ctx, fft, n_k, h_kvecs, ctx->st_nslabs ? ctx->st_D : 0, n_species, h_species, h_density));
+    TA_CHECK(partial_slab(ctx));
+    TA_CHECK(check_labels(fail, ctx, h_species, ctx->st_A, n_species));
+    if (ctx->is_cpu)
+        return cpu_rc(ctx, ta::cpu::partial_density(cpu_state(ctx), fft != 0, n_k, h_kvecs, n_species, h_species, h_weights, h_density,
+                                                    h_cross));
+    double* d_out = nullptr;
+    TA_CHECK(ta::partial_launch(ctx, fft, n_k, h_kvecs, n_species, h_species, h_weights, h_cross != nullptr, &d_out));
+    const size_t n_den = (size_t)n_k * (size_t)n_species * (size_t)ctx->st_T * 2;
+    return host_finish(ctx, {{h_density, d_out, n_den},
+                             {h_cross, d_out + n_den, (size_t)n_k * (size_t)ctx->st_T * (size_t)n_species * (size_t)n_species}});
+    });
+}
+
+int ta_partial_cross(ta_ctx* ctx, int fft, const double* h_density, int n_k, int n_species, int64_t n_frames, double* h_cross) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(check_fft(ctx, fft));
+    TA_CHECK(check_species_count(fail, ctx, n_species));
+    if (!h_density || !h_cross) return fail(ctx, TA_E_INVALID, "partial density or cross output is NULL");
+    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(ctx, TA_E_INVALID, "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
+    if (n_frames < 1 || n_frames > (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30");
+    if (ctx->is_cpu)
+        return cpu_rc(ctx, ta::cpu::partial_cross(ctx->cpu_threads, fft != 0, h_density, n_k, n_species, n_frames, h_cross));
+    return ta::partial_cross_host(ctx, fft, h_density, n_k, n_species, n_frames, h_cross);
+    });
+}
+
+int ta_partial_density_tile(int n_species, int* st, int* kc, int* frames_f64, int* frames_f32) {
+    int a = 0, b = 0, c = 0, d = 0;
+    if (!ta::species_density_tile(n_species, &a, &b, &c, &d))
+        return fail(nullptr, TA_E_INVALID, "n_species must be 1 ... " + std::to_string(TA_ONSAGER_MAX_SPECIES));
+    if (st) *st = a;
+    if (kc) *kc = b;
+    if (frames_f64) *frames_f64 = c;
+    if (frames_f32) *frames_f32 = d;
     return TA_OK;
 }
 

@@ -761,6 +761,44 @@ int kcurrent(const State& s, bool fft, int K, const double* kvecs, const double*
     return lon || trans ? kcurrent_correlate(s.threads, fft, cur, K, kvecs, T, D, lon, trans) : TA_OK;
 }
 
+int partial_cross(int threads, bool fft, const double* density, int K, int S, int64_t T, double* cross) {
+    // a complex density is a species sum with dim 2: wavevector j's (S, T, 2) block is what current_cross takes
+    for (int j = 0; j < K; ++j)
+        if (int rc = current_cross(threads, fft, density + (size_t)j * S * T * 2, S, T, 2, cross + (size_t)j * T * S * S)) return rc;
+    return TA_OK;
+}
+
+int partial_density(const State& s, bool fft, int K, const double* kvecs, int S, const int32_t* species, const double* w,
+                    double* density, double* cross) {
+    const int64_t T = s.T, A = s.A;
+    const int D = s.D;
+    const void* pos = s.slabs[0];
+    const bool f32 = s.dtype == TA_F32;
+    for (int j = 0; j < K; ++j) {
+        double q[3] = {0.0, 0.0, 0.0};
+        for (int d = 0; d < D; ++d) q[d] = kvecs[(size_t)j * D + d] / 6.283185307179586476925;
+#pragma omp parallel for num_threads(s.threads) schedule(static)
+        for (int64_t t = 0; t < T; ++t) {
+            double re[8] = {}, im[8] = {};
+            for (int64_t n = 0; n < A; ++n) {
+                const size_t i = ((size_t)t * A + n) * D;
+                double u = q[0] * (f32 ? elem<float>(pos, i) : elem<double>(pos, i));
+                for (int d = 1; d < D; ++d) u = std::fma(q[d], f32 ? elem<float>(pos, i + d) : elem<double>(pos, i + d), u);
+                const double a = 6.283185307179586476925 * (u - std::nearbyint(u));
+                const double wn = w ? w[n] : 1.0;
+                const int lab = species[n];
+                re[lab] = std::fma(wn, std::cos(a), re[lab]);
+                im[lab] = std::fma(wn, std::sin(a), im[lab]);
+            }
+            for (int a = 0; a < S; ++a) {
+                density[(((size_t)j * S + a) * T + t) * 2] = re[a];
+                density[(((size_t)j * S + a) * T + t) * 2 + 1] = im[a];
+            }
+        }
+    }
+    return cross ? partial_cross(s.threads, fft, density, K, S, T, cross) : TA_OK;
+}
+
 // Atoms in blocks of kVhBlock: OpenMP threads take atoms of a block, each with an int64 histogram of its own and every
 // atom's moments in a slot of its own; after a block the moments are added in atom order, after the last one the threads'
 // histograms: neither depends on the number of threads

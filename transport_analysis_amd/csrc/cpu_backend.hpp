@@ -63,6 +63,14 @@ int orient(const State& s, bool fft, int mode, int64_t N, const int32_t* index, 
 // current (K, n_frames, dim, 2) = the plain sum in atom order (w NULL: all 1), lon / trans (K, n_frames) = kcurrent_correlate
 // of it; each output may be NULL; arguments checked by the caller
 int kcurrent(const State& s, bool fft, int K, const double* kvecs, const double* w, double* current, double* lon, double* trans);
+// ta_partial_density: the species-resolved density of slab 0 (the positions) for K wavevectors, with species_density.hip's
+// arithmetic (the phase as scatter(); one fma of w_n with the cosine and one with the sine): density (K, n_species, n_frames, 2)
+// = the plain sum in atom order per species (labels in [0, n_species), checked by the caller; w NULL: all 1), cross (K,
+// n_frames, S, S) = partial_cross of it (or NULL)
+int partial_density(const State& s, bool fft, int K, const double* kvecs, int n_species, const int32_t* species, const double* w,
+                    double* density, double* cross);
+// cross (K, n_frames, S, S) of a density (K, S, n_frames, 2): current_cross on dim 2 per wavevector
+int partial_cross(int threads, bool fft, const double* density, int K, int n_species, int64_t n_frames, double* cross);
 // lon, trans (K, n_frames) of a current (K, n_frames, dim, 2): kcurrent_math.hpp's projections jL, jT_d as K (1 + dim) atoms
 // of dim 2 (dim = 1: K), ONE by-particle vacf call on them, the transverse series added and divided by dim - 1 (dim = 1: zeros)
 int kcurrent_correlate(int threads, bool fft, const double* current, int K, const double* kvecs, int64_t n_frames, int dim,

@@ -734,6 +734,28 @@ int ta_group_kcurrent(ta_group* g, int fft, int n_k, const double* h_kvecs, cons
     });
 }
 
+// Partial scattering functions: every member's species-resolved density of its atoms (its slice of the labels and weights, the
+// call's n_species) for the same wavevectors, added on the host in member order, then ONE cross term of the summed density on
+// the first member that holds atoms -- the rule of ta_group_conductivity
+int ta_group_partial_density(ta_group* g, int fft, int n_k, const double* h_kvecs, int n_species, const int32_t* h_species,
+                             const double* h_weights, double* h_density, double* h_cross) {
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
+    TAG_CHECK(check_partial(gfail, g, fft, n_k, h_kvecs, g->T ? g->D : 0, n_species, h_species, h_density));
+    TAG_CHECK(check_staged(g));
+    TAG_CHECK(check_labels(gfail, g, h_species, g->A, n_species));
+    const size_t n_den = (size_t)n_k * n_species * g->T * 2;
+    std::vector<int> who;
+    TAG_CHECK(sum_members(g, who, "partial densities", {{0, n_den, h_density}}, [&](int i, double** d) {
+        return partial_launch(g->ctx[i], fft, n_k, h_kvecs, n_species, h_species + g->lo[i],
+                              h_weights ? h_weights + g->lo[i] : nullptr, false, d);
+    }));
+    if (h_cross)
+        if (const int rc = partial_cross_host(g->ctx[who[0]], fft, h_density, n_k, n_species, g->T, h_cross)) return mfail(g, who[0], rc);
+    return TA_OK;
+    });
+}
+
 // Self van Hove function: every member's counts and moments of its atoms for the same lags and bins, the counts added as
 // int64 and the moments in member order (both add up over atoms: nothing follows the sums)
 int ta_group_vanhove(ta_group* g, int n_lags, const int64_t* h_lags, int n_bins, double dr, int64_t* h_counts, double* h_moments) {

@@ -151,6 +151,30 @@ static int check_kcurrent(Fail fail, Owner* owner, int fft, int n_k, const doubl
 int kcurrent_launch(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, const double* h_w, bool correlate, double** d_out);
 int kcurrent_correlate_host(ta_ctx* ctx, int fft, const double* h_current, int n_k, const double* h_kvecs, int64_t T, int D,
                             double* h_long, double* h_trans);
+// the argument checks of ta_partial_density* on a context (fail, ctx) or a group (gfail, g): the same messages for both, in
+// the order of ta_scatter and ta_onsager.  D: the components per wavevector (0: not known, nothing staged -- the caller
+// reports that next)
+template <class Fail, class Owner>
+static int check_partial(Fail fail, Owner* owner, int fft, int n_k, const double* h_kvecs, int D, int S, const void* species,
+                         const void* o_density) {
+    if (fft != 0 && fft != 1) return fail(owner, TA_E_INVALID, "fft must be 0 or 1");
+    if (const int rc = check_species_count(fail, owner, S)) return rc;
+    if (!h_kvecs) return fail(owner, TA_E_INVALID, "wavevectors are NULL");
+    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(owner, TA_E_INVALID, "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
+    for (int64_t i = 0; i < (int64_t)n_k * D; ++i)
+        if (!(h_kvecs[i] - h_kvecs[i] == 0.0))
+            return fail(owner, TA_E_INVALID, "wavevector " + std::to_string(i / D) + " has a non-finite component");
+    if (!species) return fail(owner, TA_E_INVALID, "species labels are NULL");
+    if (!o_density) return fail(owner, TA_E_INVALID, "partial density output is NULL");
+    return TA_OK;
+}
+// api.hip, for group.hip: one context's ta_partial_density share (its staged slab 0, the call's wavevectors, checked by the
+// caller, its atoms' labels h_species (checked by the caller) and weights h_w or NULL), queued: *d_out = the density (n_k,
+// n_species, n_frames, 2), then (cross) the cross term (n_k, n_frames, S, S), valid after host_wait; and the cross term of a
+// host density on the context's device, blocking
+int partial_launch(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, int S, const int32_t* h_species, const double* h_w,
+                   bool cross, double** d_out);
+int partial_cross_host(ta_ctx* ctx, int fft, const double* h_density, int n_k, int S, int64_t T, double* h_cross);
 // the argument checks the van Hove families share, on a context (fail, ctx) or a group (gfail, g), under the family's
 // message prefix `p`: the lags' array, the counts and the bin width ...
 template <class Fail, class Owner>
@@ -382,6 +406,21 @@ hipError_t launch_kcurrent(const void* v, const void* x, bool f32, long pitch, l
 hipError_t launch_kcurrent_project(const double* current, const double* khat, int K, long T, int D, long pitch, double* pm,
                                    hipStream_t st);
 hipError_t launch_kcurrent_finish(const double* bp, int K, long T, int D, double* lon, double* trans, hipStream_t st);
+
+// species_density.hip: the species-resolved density of kc <= KC wavevectors q (kc, D) (device array, turns per length unit) and
+// S species from the pair-major position slab x of float64 or (f32) float32 elements, read as it is, in one pass: partial
+// [n_parts][kc][S][T] (re, im) sums over the atoms g, g + n_parts, ... of w_n (cos, sin)(2 pi q . x), each into the row of
+// its label (written in full; n_parts from species_density_parts, which depends on the slab and the device only;
+// k_sum_partials adds them in order); species: (n_atoms,) int32 device labels, one outside [0, S) is skipped; w: (n_atoms,)
+// device weights or NULL (all 1).  species_density_tile: the species slots ST and the wavevectors per launch KC of the tile
+// that serves n_species, and the frames per thread on a float64 / float32 slab (false: n_species outside 1 ... 8).
+// finish: C (B, T, S, S) of a batch of B wavevectors from the (T, B S^2) by-particle autocorrelations of their pseudo-particles
+// (launch_onsager_combos per wavevector, dim 2) and the flags nz (B, TA_ONSAGER_MAX_SPECIES); lag 0 is kept
+bool species_density_tile(int n_species, int* st, int* kc, int* frames_f64, int* frames_f32);
+int species_density_parts(int n_cu, bool f32, long pitch, long n_atoms, size_t budget);
+hipError_t launch_species_density(const void* x, bool f32, long pitch, long T, long n_atoms, int D, const double* q, int kc, int S,
+                                  const int* species, const double* w, double* partial, int n_parts, hipStream_t st);
+hipError_t launch_partial_finish(const double* bp, int B, int S, long T, const int* nz, double* C, hipStream_t st);
 
 // vanhove.hip: the self van Hove histogram of a pair-major slab of float64 or (f32) float32 elements, read as it is, for the
 // lags [l0, l0 + Lc) of L (device array `lags`): counts (L, B + 1) uint64 (zeroed by the caller before the first chunk)
