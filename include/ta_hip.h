@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_pair_find / ta_pair_find_read / ta_pair_lifetime / ta_bond_lifetime / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_pair_find / ta_pair_find_read / ta_pair_lifetime / ta_bond_lifetime / ta_shell_residence / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -647,6 +647,46 @@ int ta_bond_lifetime(ta_ctx *ctx, int fft, int64_t n_bonds, int n_at, const int3
                      const double *h_dimensions, const int *axes, double r_cut, double r_break, double cos_cut,
                      double cos_break, int gap, double *h_ci /* (T) */, int64_t *h_runs /* (T + 1) */, double *h_nb /* (T) */);
 
+/* ta_shell_residence : residence times in the shell of a GROUP (ShellResidence): ta_pair_lifetime's three sums of one series
+ *              per OBSERVED item q of h_idx_b, whose indicator is the OR over all REFERENCE items p of h_idx_a (the residence
+ *              function of Impey, Madden and McDonald).  In frame t, with the box of frame t and ta_pair_lifetime's r2 of
+ *              d = x_q - x_p,
+ *                form = [some p in a with id(p) != id(q) has r2 < rc2],   brk = [some such p has r2 < rb2],
+ *                s(t) = brk ? (form ? 2 : 1) : 0,    rc2 = fl(r_cut r_cut), rb2 = fl(r_break r_break), both tests STRICT,
+ *              then ta_bond_lifetime's hysteresis h and gap tolerance g, and h_ci, h_runs, h_nb are ta_pair_lifetime's
+ *              outputs of the n_b series g: ci[tau] = sum_q sum_t g(t) g(t + tau) (undivided), runs[l] the maximal runs of
+ *              l frames inside, nb[t] the observed items inside; the exactness statements carry over.  An item that passes
+ *              from the shell of one reference item into that of another without a frame outside is ONE residence: no
+ *              combination of pair-resolved calls gives that.  With ONE reference item the outputs have the bits of
+ *              ta_bond_lifetime on the rows (a_0, q).
+ *              Index lists as ta_pair_find's: HOST, strictly increasing, in range; h_idx_a NULL: all items; h_idx_b NULL:
+ *              b = a; two lists are the same list or disjoint.  The same list means "in the shell of ANOTHER member".
+ *              Box, r_cut, r_break, gap as ta_bond_lifetime's (r_break against half of every frame's analysed box lengths).
+ *              Passes.  Per block of observed items and chunk of whole 64-frame words: k_vhd_gather at lag 0 writes the
+ *              chunk's frames as frame-major float64 scratch (the slab read in the element type it has, never widened
+ *              first); k_shell_series gives a workgroup 1024 observed items (4 per lane, in registers) and ONE 64-frame
+ *              word, walks ALL reference items per frame on k_pair_find's tile walk and ORs the two flags; a wave's ballots
+ *              after frame f are the 64-item words of that frame and lane f keeps them, so after the last frame lane f holds
+ *              every item's bits at frame 64 w + f and stores one 16-byte row per pair of items: the block Z of
+ *              ta_bond_lifetime (level 0.0 / 1.0 / 2.0, or 1.0 for level 2 where nothing is filtered), every row with one
+ *              writer, without atomics, LDS or shuffles.  Then ta_bond_lifetime's passes, unchanged: k_pair_filter where
+ *              needed, k_pair_runs, one lag-sum evaluation and one unit-weight species sum per block.  Blocks hold as many
+ *              observed items as "pair_chunk" allows series (a block behind the first starts at an even item: a forced odd
+ *              n counts as n - 1, at least 2); the frames go in chunks of words whose scratch fits 4 GiB, at most 65535
+ *              (option "shell_chunk" n >= 1 forces min(n, words)).  Neither chunking changes a bit of the outputs.  The CPU
+ *              backend follows the same arithmetic on packed words: its outputs (ci with fft = 0) EQUAL the GPU's.
+ *              Errors, all checked before anything is written.  TA_E_INVALID: fft other than 0 / 1; all three outputs NULL;
+ *              n_a or n_b < 1 with a list, a list entry out of range or not increasing, two lists that overlap but differ;
+ *              n_b at or above 2^30; r_cut not finite or <= 0; r_break not finite or below r_cut; gap outside 0 ... 63;
+ *              h_dimensions without axes, a non-orthogonal box, r_break above half an analysed box length in any frame;
+ *              ceil(Na / 256) ceil(Nb / 1024) at or above 2^24; n_atoms * dim at or above 2^31.  TA_E_STATE: nothing staged.
+ *              There is no ta_group_* form.  k_shell_series (its last launch) is the main kernel unless a lag-sum
+ *              evaluation after it records its own.                                                                      */
+int ta_shell_residence(ta_ctx *ctx, int fft, int64_t n_a, const int64_t *h_idx_a /* reference items; NULL: all */,
+                       int64_t n_b, const int64_t *h_idx_b /* observed items; NULL: b = a */, const double *h_dimensions,
+                       const int *axes, double r_cut, double r_break, int gap, double *h_ci /* (T) */,
+                       int64_t *h_runs /* (T + 1) */, double *h_nb /* (T) */);
+
 /* ta_orient  : the rotational correlation functions of molecule-fixed unit vectors of the positions in slab 0
  *              (OrientationalCorrelation), three staged columns per atom.  A vector n is row n of h_index, atoms of slab 0,
  *              pairwise distinct and in [0, n_atoms):
@@ -896,6 +936,11 @@ int ta_pair_lifetime_staged(ta_ctx *ctx, int fft, int64_t n_pairs, const int32_t
 int ta_bond_lifetime_staged(ta_ctx *ctx, int fft, int64_t n_bonds, int n_at, const int32_t *h_atoms, const double *h_dimensions,
                             const int *axes, double r_cut, double r_break, double cos_cut, double cos_break, int gap,
                             double *d_ci, int64_t *d_runs, double *d_nb, void *stream);
+/* the index lists and the box: HOST arrays, as for ta_shell_residence (checked before anything is written); the outputs on
+ * the device, as ta_pair_lifetime_staged's */
+int ta_shell_residence_staged(ta_ctx *ctx, int fft, int64_t n_a, const int64_t *h_idx_a, int64_t n_b, const int64_t *h_idx_b,
+                              const double *h_dimensions, const int *axes, double r_cut, double r_break, int gap, double *d_ci,
+                              int64_t *d_runs, double *d_nb, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns
@@ -1105,9 +1150,11 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      scratch, at least 1; n >= 1: min(n, n_lags)); the results do not depend on it;
  *   "pair_chunk" n : candidate pairs per block of ta_pair_lifetime* (0, the default: as many as fit 32 GiB of indicator
  *                      block, at least 2; n >= 1: min(n, n_pairs)); the results do not depend on it (ci with fft = 0 bit for
- *                      bit; with fft = 1 within the FFT path's bound);
+ *                      bit; with fft = 1 within the FFT path's bound); ta_shell_residence* takes it as observed items per block;
  *   "pair_find_chunk" n : searched frames per pass of ta_pair_find (0, the default: as many as fit 4 GiB of gathered scratch,
  *                      at least 1, at most 65535; n >= 1: min(n, frames)); the found list does not depend on it;
+ *   "shell_chunk" n : 64-frame words per pass of ta_shell_residence* (0, the default: as many as fit 4 GiB of gathered
+ *                      scratch, at least 1, at most 65535; n >= 1: min(n, words)); the results do not depend on it;
  *   "async_commit" 1|0 : ta_stage_commit hands its frame range to a worker thread of the context, which
  *                      makes the HIP calls (the caller's frame loop never waits on the runtime, e.g. while
  *                      another thread page-locks a result array); every call that touches the slabs joins

@@ -96,6 +96,8 @@ _API = {
     # (handle, fft, n_bonds, n_at, h_atoms, h_dimensions, axes, r_cut, r_break, cos_cut, cos_break, gap, ci, runs, nb[, stream])
     "ta_bond_lifetime": _int(_vp, _ci, _i64, _ci, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _ci, _vp, _vp, _vp),
     "ta_bond_lifetime_staged": _int(_vp, _ci, _i64, _ci, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp),
+    "ta_shell_residence": _int(_vp, _ci, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _vp, _vp),
+    "ta_shell_residence_staged": _int(_vp, _ci, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp),
     "ta_vanhove_distinct_staged": _int(_vp, _ci, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _dbl, _vp, _vp),
     "ta_compound": _int(_vp, _i64, _vp, _vp, _vp, _vp, _P(_vp)),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
@@ -1025,6 +1027,29 @@ class Context(_Staged):
         """`atoms`, `dimensions`: HOST arrays (checked by the library before anything is written); d_ci (n_frames,), d_runs
         (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
         self._life_staged("bond_lifetime_staged", self._bond_args(fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes),
+                          d_ci, d_runs, d_nb, stream)
+
+    def _shell_args(self, fft, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes):
+        """the argument tuple ta_shell_residence* share, and the arrays it points into (to be kept until the call is over)"""
+        (a, na), (b, nb) = _index_list(idx_a, "idx_a"), _index_list(idx_b, "idx_b")
+        dims, ax = self._pair_box(dimensions, axes)
+        r_break = r_cut if r_break is None else r_break
+        return (int(fft), na, _ptr(a), nb, _ptr(b), _ptr(dims), _ptr(ax), float(r_cut), float(r_break), int(gap)), (a, b, dims, ax)
+
+    def shell_residence(self, fft, r_cut, *, r_break=None, gap=0, idx_a=None, idx_b=None, dimensions=None, axes=None, ci=True,
+                        runs=True, nb=True):
+        """pair_lifetime's sums (ci, runs, nb) of slab 0 for one series per OBSERVED item of `idx_b` (None: the same as a),
+        ta_shell_residence: the item is inside while SOME reference item of `idx_a` (None: all items) other than itself is
+        closer than `r_cut`, stays inside while some is closer than `r_break` (None: r_cut), and absences of up to `gap` frames
+        (0 ... 63) between frames inside are filled.  The lists: strictly increasing item indices, the same list or disjoint
+        ones.  One context only: a device group has no such call."""
+        return self._life("shell_residence", self._shell_args, (fft, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes), ci, runs, nb)
+
+    def shell_residence_staged(self, fft, r_cut, *, r_break=None, gap=0, idx_a=None, idx_b=None, dimensions=None, axes=None,
+                               d_ci=0, d_runs=0, d_nb=0, stream=0):
+        """the lists and `dimensions`: HOST arrays (checked by the library before anything is written); d_ci (n_frames,), d_runs
+        (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
+        self._life_staged("shell_residence_staged", self._shell_args(fft, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes),
                           d_ci, d_runs, d_nb, stream)
 
     def _orient_args(self, fft, index, mode, dimensions, weights):

@@ -130,6 +130,7 @@ private:
     X(vanhove_distinct_chunk, 0, opt_check_vanhove_distinct_chunk) /* lags per pass of ta_vanhove_distinct* (0: as many as fit kVhdBudget) */ \
     X(pair_chunk, 0, opt_check_pair_chunk) /* candidate pairs per block of ta_pair_lifetime* (0: as many as fit kPairBudget) */ \
     X(pair_find_chunk, 0, opt_check_pair_find_chunk) /* searched frames per pass of ta_pair_find (0: as many as fit kVhdBudget) */ \
+    X(shell_chunk, 0, opt_check_shell_chunk) /* 64-frame words per pass of ta_shell_residence* (0: as many as fit kVhdBudget) */ \
     X(async_commit, 1, opt_flush_commits) /* ta_stage_commit goes through the commit queue; flushed before it changes */   \
     X(lock_ahead, 1, nullptr)      /* the commit worker page-locks the chunks behind the one it committed */               \
     X(cpu_threads, 0, opt_set_cpu_threads) /* CPU backend: OpenMP team size (0: the runtime's default) */                  \
@@ -216,6 +217,9 @@ struct ta_ctx {
     DevBuf pair_bits{workspaces, kTrimmed}, pair_list{workspaces, kTrimmed}, pair_z{workspaces, kTrimmed};
     DevBuf pair_rows{workspaces, kTrimmed}, pair_out{workspaces, kKept};
     int64_t pair_n = -1, pair_A = 0;
+    // shell residence times (shell_pm): the table (a zero lag, box entries, padded index lists, zero labels); the scratch is
+    // vhd_scr, the level block and everything behind it the pair lifetimes' (pair_z, pair_rows, pair_out)
+    HostTable shell_tab{workspaces, tables};
     std::vector<int32_t> pair_host;
     // ta_compound: the plan (offsets, members, member weights, their sums per compound) and the (n_frames, dim) weighted
     // mean F of the barycentric term; the per-atom frame weights and F's partial sums use the Onsager workspaces
@@ -1897,6 +1901,20 @@ int pair_cut_args(ta_ctx* ctx, const std::string& who, double r_cut, const doubl
     return TA_OK;
 }
 
+// two lists must be the same list twice or disjoint ones (both increase strictly: one merge walk); *same: b is a
+int lists_same_or_disjoint(ta_ctx* ctx, const std::string& who, const ItemLists& l, bool two_lists, bool* same) {
+    *same = !two_lists;
+    if (*same) return TA_OK;
+    *same = l.n_a == l.n_b && std::equal(l.ida.begin(), l.ida.begin() + l.n_a, l.idb.begin());
+    for (int64_t i = 0, j = 0; !*same && i < l.n_a && j < l.n_b;) {
+        if (l.ida[i] == l.idb[j])
+            return fail(ctx, TA_E_INVALID, who + "the index lists overlap (item " + std::to_string(l.ida[i]) +
+                                               " is in both) but differ: they must be one list or disjoint");
+        l.ida[i] < l.idb[j] ? ++i : ++j;
+    }
+    return TA_OK;
+}
+
 // The host side of one search (both kinds of context)
 struct PairFindPlan : ItemLists {
     int D = 0;
@@ -1919,16 +1937,7 @@ int pair_find_plan(ta_ctx* ctx, int64_t n_a, const int64_t* h_idx_a, int64_t n_b
     TA_CHECK(check_cols(ctx, who, A, D));
     p->D = D, p->T = T, p->A = A, p->stride = stride, p->rc2 = r_cut * r_cut;
     TA_CHECK(item_lists(ctx, "pair_find", n_a, h_idx_a, n_b, h_idx_b, A, p));
-    p->same = !h_idx_b;
-    if (!p->same) {  // two lists: the same list twice, or disjoint ones (both increase strictly: one merge walk)
-        p->same = p->n_a == p->n_b && std::equal(p->ida.begin(), p->ida.begin() + p->n_a, p->idb.begin());
-        for (int64_t i = 0, j = 0; !p->same && i < p->n_a && j < p->n_b;) {
-            if (p->ida[i] == p->idb[j])
-                return fail(ctx, TA_E_INVALID, who + "the index lists overlap (item " + std::to_string(p->ida[i]) +
-                                                   " is in both) but differ: they must be one list or disjoint");
-            p->ida[i] < p->idb[j] ? ++i : ++j;
-        }
-    }
+    TA_CHECK(lists_same_or_disjoint(ctx, who, *p, h_idx_b != nullptr, &p->same));
     if (p->pitch_a * p->pitch_b > (int64_t)1 << 35)
         return fail(ctx, TA_E_INVALID, who + "the pair bitmap of " + std::to_string(p->pitch_a) + " x " + std::to_string(p->pitch_b) +
                                            " padded items exceeds 2^35 bits (4 GiB)");
@@ -2106,47 +2115,81 @@ int64_t pair_block(const ta_ctx* ctx, int64_t P, int64_t pitch) {
 // the automatic block), and rint gives that integer: the same bits for every block size.  ev[1] / ev[2] bracket the
 // (last) k_pair_series launch, unless a lag-sum evaluation after it records its own main kernel.  A bond call (p.bond) has
 // k_bond_series in k_pair_series' place, rows of p.n_at items, and k_pair_filter behind it where p.filter() says so.
+// What follows a block's level or indicator block Z, for pair_life_pm and shell_pm alike: the workspaces of a call of P
+// series in blocks of Pc (begin), the block's passes over Z (block: the filter where asked for, the runs, the lag sums, the
+// bonded counts; lab: Pc zero labels on the device), the rows added in block order into the outputs and the call closed (end).
+struct LifeSums {
+    bool fft = false;
+    int64_t T = 0, pitch = 0, Pc = 0, n_blocks = 0;
+    int parts_full = 0, parts_last = 0;
+    double *Z = nullptr, *ci_rows = nullptr, *nb_rows = nullptr, *d_ci = nullptr, *d_nb = nullptr;
+    unsigned long long* runs = nullptr;
+    int64_t* d_runs = nullptr;
+    hipStream_t st = nullptr;
+};
+int life_sums_begin(ta_ctx* ctx, bool fft, const Slab& slab, int64_t P, int64_t Pc, double* d_ci, int64_t* d_runs, double* d_nb, LifeSums* s) {
+    const int64_t T = slab.T, n_blocks = (P + Pc - 1) / Pc;
+    *s = LifeSums{fft, T, slab.pitch, Pc, n_blocks};
+    s->d_ci = d_ci, s->d_runs = d_runs, s->d_nb = d_nb, s->st = slab.st;
+    TA_CHECK(ensure(ctx, ctx->pair_z, (size_t)((Pc + 1) / 2) * (size_t)slab.pitch * 16));
+    const size_t n_rows = (size_t)n_blocks * (size_t)T;
+    TA_CHECK(ensure(ctx, ctx->pair_rows, sizeof(double) * (2 * n_rows + (size_t)T + 1)));
+    s->ci_rows = (double*)ctx->pair_rows.p;
+    s->nb_rows = s->ci_rows + n_rows;
+    s->runs = (unsigned long long*)(s->nb_rows + n_rows);
+    const int64_t P_last = P - (n_blocks - 1) * Pc;
+    s->parts_full = species_sum_parts(ctx->n_cu, 1, (long)T, (long)Pc), s->parts_last = species_sum_parts(ctx->n_cu, 1, (long)T, (long)P_last);
+    if (d_nb) TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)std::max(s->parts_full, s->parts_last) * (size_t)T));
+    s->Z = (double*)ctx->pair_z.p;
+    if (d_runs) TA_HIP_TRY(ctx, hipMemsetAsync(s->runs, 0, sizeof(uint64_t) * ((size_t)T + 1), s->st));
+    return TA_OK;
+}
+int life_sums_block(ta_ctx* ctx, const LifeSums& s, int64_t b, int64_t pb, bool filter, int gap, const int* lab) {
+    hipStream_t st = s.st;
+    const int64_t T = s.T, pitch = s.pitch;
+    double* Z = s.Z;
+    if (filter) TA_LAUNCH(ctx, "k_pair_filter", st, launch_pair_filter(ctx->n_cu, Z, (long)pitch, (long)T, (long)pb, gap, st));
+    if (s.d_runs) TA_LAUNCH(ctx, "k_pair_runs", st, launch_pair_runs(ctx->n_cu, Z, (long)pitch, (long)T, (long)pb, s.runs, st));
+    if (s.d_ci) TA_CHECK(acf_impl(ctx, s.fft, Z, pitch, T, pb, 1, s.ci_rows + (size_t)b * T, nullptr, 0, st));
+    if (s.d_nb)
+        TA_CHECK(weighted_total(ctx, Z, false, pitch, T, pb, 1, lab, nullptr, pb == s.Pc ? s.parts_full : s.parts_last,
+                                s.nb_rows + (size_t)b * T, st));
+    return TA_OK;
+}
+int life_sums_end(ta_ctx* ctx, const LifeSums& s) {
+    hipStream_t st = s.st;
+    const int64_t T = s.T;
+    if (s.d_ci)
+        TA_LAUNCH(ctx, "k_pair_reduce", st,
+                  launch_pair_reduce(s.ci_rows, (int)s.n_blocks, (long)T, (long)T, s.fft ? PAIR_LAGS : PAIR_LAGS_INT, s.d_ci, st));
+    if (s.d_nb) TA_LAUNCH(ctx, "k_pair_reduce", st, launch_pair_reduce(s.nb_rows, (int)s.n_blocks, (long)T, (long)T, PAIR_SUM, s.d_nb, st));
+    if (s.d_runs) TA_HIP_TRY(ctx, hipMemcpyAsync(s.d_runs, s.runs, sizeof(int64_t) * ((size_t)T + 1), hipMemcpyDeviceToDevice, st));
+    return call_end(ctx, st);
+}
+
 int pair_life_pm(ta_ctx* ctx, bool fft, const Slab& slab, const PairLifePlan& p, double* d_ci, int64_t* d_runs, double* d_nb) {
     hipStream_t st = slab.st;
     const int64_t T = slab.T, pitch = slab.pitch, P = p.P;
-    const int64_t Pc = pair_block(ctx, P, pitch), n_blocks = (P + Pc - 1) / Pc;
+    const int64_t Pc = pair_block(ctx, P, pitch);
     const double* tab = (const double*)ctx->pair_tab.dev.p;
     const double* hm = p.box.n_box ? tab : nullptr;
     const int* pairs = p.h_pairs ? (const int*)(tab + p.box.hm.size()) : (const int*)ctx->pair_list.p;
     const int* lab = (const int*)(tab + p.box.hm.size() + p.list_doubles());
-    TA_CHECK(ensure(ctx, ctx->pair_z, (size_t)((Pc + 1) / 2) * (size_t)pitch * 16));
-    const size_t n_rows = (size_t)n_blocks * (size_t)T;
-    TA_CHECK(ensure(ctx, ctx->pair_rows, sizeof(double) * (2 * n_rows + (size_t)T + 1)));
-    double* ci_rows = (double*)ctx->pair_rows.p;
-    double* nb_rows = ci_rows + n_rows;
-    unsigned long long* runs = (unsigned long long*)(nb_rows + n_rows);
-    const int64_t P_last = P - (n_blocks - 1) * Pc;
-    const int parts_full = species_sum_parts(ctx->n_cu, 1, (long)T, (long)Pc), parts_last = species_sum_parts(ctx->n_cu, 1, (long)T, (long)P_last);
-    if (d_nb) TA_CHECK(ensure(ctx, ctx->ons_part, sizeof(double) * (size_t)std::max(parts_full, parts_last) * (size_t)T));
-    double* Z = (double*)ctx->pair_z.p;
-    if (d_runs) TA_HIP_TRY(ctx, hipMemsetAsync(runs, 0, sizeof(uint64_t) * ((size_t)T + 1), st));
-    for (int64_t b = 0; b < n_blocks; ++b) {
+    LifeSums s;
+    TA_CHECK(life_sums_begin(ctx, fft, slab, P, Pc, d_ci, d_runs, d_nb, &s));
+    for (int64_t b = 0; b < s.n_blocks; ++b) {
         const int64_t p0 = b * Pc, pb = std::min(Pc, P - p0);
         if (p.bond)
             TA_LAUNCH_MAIN(ctx, "k_bond_series", st,
                            launch_bond_series(ctx->n_cu, slab.pm, slab.f32, (long)pitch, (long)T, (long)slab.A, slab.D, (long)pb, p.n_at,
-                                              pairs + p.n_at * p0, hm, p.box.per_frame, p.cuts, p.filter() ? 2.0 : 1.0, Z, st));
+                                              pairs + p.n_at * p0, hm, p.box.per_frame, p.cuts, p.filter() ? 2.0 : 1.0, s.Z, st));
         else
             TA_LAUNCH_MAIN(ctx, "k_pair_series", st,
                            launch_pair_series(ctx->n_cu, slab.pm, slab.f32, (long)pitch, (long)T, (long)slab.A, slab.D, (long)pb, pairs + 2 * p0,
-                                              hm, p.box.per_frame, p.rc2, Z, st));
-        if (p.filter()) TA_LAUNCH(ctx, "k_pair_filter", st, launch_pair_filter(ctx->n_cu, Z, (long)pitch, (long)T, (long)pb, p.gap, st));
-        if (d_runs) TA_LAUNCH(ctx, "k_pair_runs", st, launch_pair_runs(ctx->n_cu, Z, (long)pitch, (long)T, (long)pb, runs, st));
-        if (d_ci) TA_CHECK(acf_impl(ctx, fft, Z, pitch, T, pb, 1, ci_rows + (size_t)b * T, nullptr, 0, st));
-        if (d_nb)
-            TA_CHECK(weighted_total(ctx, Z, false, pitch, T, pb, 1, lab, nullptr, pb == Pc ? parts_full : parts_last,
-                                    nb_rows + (size_t)b * T, st));
+                                              hm, p.box.per_frame, p.rc2, s.Z, st));
+        TA_CHECK(life_sums_block(ctx, s, b, pb, p.filter(), p.gap, lab));
     }
-    if (d_ci)
-        TA_LAUNCH(ctx, "k_pair_reduce", st, launch_pair_reduce(ci_rows, (int)n_blocks, (long)T, (long)T, fft ? PAIR_LAGS : PAIR_LAGS_INT, d_ci, st));
-    if (d_nb) TA_LAUNCH(ctx, "k_pair_reduce", st, launch_pair_reduce(nb_rows, (int)n_blocks, (long)T, (long)T, PAIR_SUM, d_nb, st));
-    if (d_runs) TA_HIP_TRY(ctx, hipMemcpyAsync(d_runs, runs, sizeof(int64_t) * ((size_t)T + 1), hipMemcpyDeviceToDevice, st));
-    return call_end(ctx, st);
+    return life_sums_end(ctx, s);
 }
 
 // ta_pair_lifetime_staged and the device half of ta_pair_lifetime (out != NULL: the context's own output buffer ci (T) |
@@ -2173,6 +2216,123 @@ int pair_life_launch(ta_ctx* ctx, int fft, const PairLifePlan& p, double* d_ci, 
             double* o = *out;
             return pair_life_pm(ctx, fft != 0, s, p, d_ci ? o : nullptr, d_runs ? (int64_t*)(o + s.T) : nullptr,
                                 d_nb ? o + 2 * s.T + 1 : nullptr);
+        });
+}
+
+// ---- shell residence times: the level of an observed item against a group of reference items (shell.hip) ------------
+// The caller's arguments of ta_shell_residence*, as they came
+struct ShellArgs {
+    int64_t n_a, n_b;
+    const int64_t *h_idx_a, *h_idx_b;
+    const double* h_dims;
+    const int* axes;
+    double r_cut, r_break;
+    int gap;
+};
+// The host side of one call (both kinds of context): a = the reference items, b = the observed ones, one series per b-item.
+// The b list carries one more tile of padding than item_lists gives it: a block of observed items is read from its first
+// item on, a whole number of tiles long.
+struct ShellPlan : ItemLists {
+    int D = 0, gap = 0;
+    int64_t T = 0, A = 0;
+    ta::BondCuts cuts{};
+    PairBox box;
+    bool filter() const { return gap > 0 || cuts.rb2 != cuts.rc2; }
+};
+int shell_plan(ta_ctx* ctx, int fft, const ShellArgs& a, bool any_out, ShellPlan* p) {
+    const std::string who = "shell_residence: ";
+    TA_CHECK(check_fft(ctx, fft));
+    if (!any_out) return fail(ctx, TA_E_INVALID, who + "the ci, runs and nb outputs are all NULL");
+    if (a.h_idx_a && a.n_a < 1) return fail(ctx, TA_E_INVALID, who + "n_a must be >= 1");
+    if (a.h_idx_b && a.n_b < 1) return fail(ctx, TA_E_INVALID, who + "n_b must be >= 1");
+    TA_CHECK(pair_cut_args(ctx, who, a.r_cut, a.h_dims, a.axes));
+    if (!(a.r_break - a.r_break == 0.0) || a.r_break < a.r_cut) return fail(ctx, TA_E_INVALID, who + "r_break must be finite and at least r_cut");
+    if (a.gap < 0 || a.gap > 63)
+        return fail(ctx, TA_E_INVALID, who + "gap must be 0 ... 63 (absences are closed inside a window of three 64-frame words)");
+    TA_CHECK(check_staged(ctx));
+    const int64_t T = ctx->st_T, A = ctx->st_A;
+    const int D = ctx->st_D;
+    TA_CHECK(check_cols(ctx, who, A, D));
+    p->D = D, p->T = T, p->A = A, p->gap = a.gap;
+    p->cuts = ta::BondCuts{a.r_cut * a.r_cut, a.r_break * a.r_break, 0.0, 0.0};
+    TA_CHECK(item_lists(ctx, "shell_residence", a.n_a, a.h_idx_a, a.n_b, a.h_idx_b, A, p));
+    bool same = false;
+    TA_CHECK(lists_same_or_disjoint(ctx, who, *p, a.h_idx_b != nullptr, &same));
+    if (p->n_b >= (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, who + "n_b must be below 2^30");
+    p->pitch_b += VHD_TILE_B;
+    p->idb.resize((size_t)p->pitch_b, -1);
+    if (!a.h_dims) return TA_OK;
+    TA_CHECK(image_box(ctx, who, a.h_dims, a.axes, T, D, &p->box));
+    return half_box(ctx, who, "r_break", a.r_break, p->box, D, 1);
+}
+
+// the observed items per block: pair_block's count of series; a block behind the first starts at an even item
+int64_t shell_block(const ta_ctx* ctx, int64_t n_b, int64_t pitch) {
+    const int64_t Qc = pair_block(ctx, n_b, pitch);
+    return Qc < n_b ? std::max<int64_t>(2, Qc & ~(int64_t)1) : Qc;
+}
+
+// One call on the staged position slab of either element type (the caller has opened the call's bracket, it is closed here;
+// the table zero lag | hm | ida | idb | zero labels has been queued).  Per block of observed items: per chunk of whole
+// 64-frame words one k_vhd_gather launch at lag 0, stride 1 (the reference items and the block's observed items, read in the
+// slab's own element type) and one k_shell_series launch, which writes the chunk's rows of the level block Z; then
+// life_sums_block, pair_life_pm's passes.  Neither chunking changes a bit: every row of Z has one writer whatever the chunk,
+// and the blocks' rows are added as pair_life_pm's.  ev[1] / ev[2] bracket the (last) k_shell_series launch, unless a
+// lag-sum evaluation after it records its own main kernel.
+int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, double* d_ci, int64_t* d_runs, double* d_nb) {
+    hipStream_t st = slab.st;
+    const int D = p.D;
+    const int64_t T = slab.T, pitch = slab.pitch, N = p.n_b, Qc = shell_block(ctx, N, pitch);
+    const int64_t* lag0 = (const int64_t*)ctx->shell_tab.dev.p;
+    const auto [hm, ida, idb] = pair_tail((const double*)(lag0 + 1), p.box, p);
+    const int* lab = idb + p.pitch_b;
+    const int64_t pitch_q = (Qc + VHD_TILE_B - 1) / VHD_TILE_B * VHD_TILE_B, words = (T + 63) / 64;
+    const size_t per = sizeof(double) * (size_t)D * (size_t)(p.pitch_a + pitch_q);  // a gathered frame
+    const int64_t fit = std::max<int64_t>(1, (int64_t)(kVhdBudget / (64 * per)));
+    const int64_t wc = std::min<int64_t>({words, 65535, ctx->opt_shell_chunk > 0 ? ctx->opt_shell_chunk : fit});
+    TA_CHECK(ensure(ctx, ctx->vhd_scr, (size_t)std::min(T, 64 * wc) * per));
+    double* ga = (double*)ctx->vhd_scr.p;
+    LifeSums s;
+    TA_CHECK(life_sums_begin(ctx, fft, slab, N, Qc, d_ci, d_runs, d_nb, &s));
+    for (int64_t b = 0; b < s.n_blocks; ++b) {
+        const int64_t q0 = b * Qc, nb = std::min(Qc, N - q0), pitch_b = (nb + VHD_TILE_B - 1) / VHD_TILE_B * VHD_TILE_B;
+        for (int64_t w0 = 0; w0 < words; w0 += wc) {
+            const int64_t f_base = 64 * w0, n_f = std::min(T, 64 * (w0 + wc)) - f_base;
+            double* gb = ga + (size_t)n_f * D * (size_t)p.pitch_a;
+            TA_LAUNCH(ctx, "k_vhd_gather", st,
+                      launch_vhd_gather(slab.pm, slab.f32, (long)pitch, (long)T, (long)slab.A, D, 1, (long)n_f, lag0, 1, true, ida, idb + q0,
+                                        (long)p.pitch_a, (long)pitch_b, ga, gb, st, (long)f_base));
+            TA_LAUNCH_MAIN(ctx, "k_shell_series", st,
+                           launch_shell_series(ga, gb, ida, idb + q0, (long)p.pitch_a, (long)pitch_b, (long)p.n_a, (long)nb, D, (long)T,
+                                               (long)pitch, (long)f_base, (long)n_f, hm, p.box.per_frame, p.cuts.rc2, p.cuts.rb2,
+                                               p.filter() ? 2.0 : 1.0, s.Z, st));
+        }
+        TA_CHECK(life_sums_block(ctx, s, b, nb, p.filter(), p.gap, lab));
+    }
+    return life_sums_end(ctx, s);
+}
+
+// ta_shell_residence_staged and the device half of ta_shell_residence (out as pair_life_launch's)
+int shell_launch(ta_ctx* ctx, int fft, const ShellPlan& p, double* d_ci, int64_t* d_runs, double* d_nb, void* stream, double** out) {
+    return slab_entry(
+        ctx, nullptr, stream, no_args,
+        [&](const Slab& s) -> int {
+            const int64_t Qc = shell_block(ctx, p.n_b, s.pitch);
+            const size_t n = 1 + pair_tail_size(p.box, p) + ((size_t)Qc + 1) / 2;
+            double* h = nullptr;
+            TA_CHECK(ctx->shell_tab.begin(ctx, sizeof(double) * n, (void**)&h));
+            memset(h, 0, sizeof(double) * n);  // (the zero lag in front, the zero labels behind)
+            pair_tail_pack(h + 1, p.box, p);
+            if (out) {
+                TA_CHECK(ensure(ctx, ctx->pair_out, sizeof(double) * (3 * (size_t)s.T + 1)));
+                *out = (double*)ctx->pair_out.p;
+            }
+            return ctx->shell_tab.send(ctx, s.st);
+        },
+        [&](const Slab& s) {
+            if (!out) return shell_pm(ctx, fft != 0, s, p, d_ci, d_runs, d_nb);
+            double* o = *out;
+            return shell_pm(ctx, fft != 0, s, p, d_ci ? o : nullptr, d_runs ? (int64_t*)(o + s.T) : nullptr, d_nb ? o + 2 * s.T + 1 : nullptr);
         });
 }
 
@@ -2271,6 +2431,9 @@ int opt_check_pair_chunk(ta_ctx* ctx, int64_t value) {
 }
 int opt_check_pair_find_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "pair_find_chunk: 0 (automatic) or the searched frames per pass");
+}
+int opt_check_shell_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "shell_chunk: 0 (automatic) or the 64-frame words per pass");
 }
 int opt_check_overlap_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "overlap_chunk: 0 (automatic) or the lags per launch");
@@ -3105,6 +3268,20 @@ int ta_bond_lifetime_staged(ta_ctx* ctx, int fft, int64_t n_bonds, int n_at, con
                             int64_t* d_runs, double* d_nb, void* stream) {
     const BondArgs bond{n_at, r_break, cos_cut, cos_break, gap};
     return life_staged(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, &bond, d_ci, d_runs, d_nb, stream);
+}
+
+// Shell residence times on the staged slab 0, read in its own element type; the index lists and the box are HOST arrays
+int ta_shell_residence_staged(ta_ctx* ctx, int fft, int64_t n_a, const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b,
+                              const double* h_dimensions, const int* axes, double r_cut, double r_break, int gap, double* d_ci,
+                              int64_t* d_runs, double* d_nb, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
+    ShellPlan plan;
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(shell_plan(ctx, fft, a, d_ci || d_runs || d_nb, &plan));
+    return shell_launch(ctx, fft, plan, d_ci, d_runs, d_nb, stream, nullptr);
+    });
 }
 
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
@@ -4001,6 +4178,24 @@ int ta_bond_lifetime(ta_ctx* ctx, int fft, int64_t n_bonds, int n_at, const int3
                      double r_cut, double r_break, double cos_cut, double cos_break, int gap, double* h_ci, int64_t* h_runs, double* h_nb) {
     const BondArgs bond{n_at, r_break, cos_cut, cos_break, gap};
     return life_host(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, &bond, h_ci, h_runs, h_nb);
+}
+
+int ta_shell_residence(ta_ctx* ctx, int fft, int64_t n_a, const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b,
+                       const double* h_dimensions, const int* axes, double r_cut, double r_break, int gap, double* h_ci, int64_t* h_runs,
+                       double* h_nb) {
+    return host_call(ctx, [&]() -> int {
+    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
+    ShellPlan p;
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(shell_plan(ctx, fft, a, h_ci || h_runs || h_nb, &p));
+    if (ctx->is_cpu)
+        return cpu_rc(ctx, ta::cpu::shell_residence(cpu_state(ctx), fft != 0, p.n_a, p.ida.data(), p.n_b, p.idb.data(), p.box.data(),
+                                                    p.box.per_frame, p.cuts, p.gap, h_ci, h_runs, h_nb));
+    double* d_out = nullptr;
+    TA_CHECK(shell_launch(ctx, fft, p, h_ci, h_runs, h_nb, ctx->stream, &d_out));
+    const size_t T = (size_t)ctx->st_T;  // (int64 counts travel as 8-byte elements)
+    return host_finish(ctx, {{h_ci, d_out, T}, {(double*)h_runs, d_out + T, T + 1}, {h_nb, d_out + 2 * T + 1, T}});
+    });
 }
 
 // The host slabs of a context go away (ta_compound: they hold atoms, the staged slab no longer does)

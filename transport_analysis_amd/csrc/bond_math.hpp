@@ -73,6 +73,10 @@ TA_VH_HD int bond_level(const double (&x)[NAT][3], const double (&H)[3], const d
     return brk ? (form ? 2 : 1) : 0;
 }
 
+// the level of an observed item in a frame against a GROUP of reference items (ta_shell_residence): form = some reference
+// item other than itself is closer than sqrt(rc2), brk = some is closer than sqrt(rb2) (rb2 >= rc2: form implies brk)
+TA_VH_HD int shell_level(bool form, bool brk) { return brk ? (form ? 2 : 1) : 0; }
+
 // one word of h from its S and W bits and the carry h(frame before the word): a fixed six steps, whatever the data
 TA_VH_HD unsigned long long bond_hyst_word(unsigned long long S, unsigned long long W, bool carry) {
     unsigned long long g = S | (carry ? W & 1ull : 0ull), p = W;

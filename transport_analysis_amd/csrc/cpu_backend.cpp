@@ -1123,6 +1123,8 @@ int pair_lifetime_t(const State& s, bool fft, int64_t P, const int32_t* pairs, c
     });
 }
 
+void level_words_filter(int64_t nw, int gap, uint64_t* w, const uint64_t* S);
+
 // the level words S (level 2) and W (level >= 1) of bond n, then hysteresis word by word and the closing of every clear bit
 // of a word against the words around it (bond_math.hpp): w gets g
 template <class E, int D, bool PERIODIC, int NAT>
@@ -1138,6 +1140,11 @@ void bond_fill(const State& s, const int32_t* row, const double* hm, bool per_fr
         if (level >= 1) w[t >> 6] |= (uint64_t)1 << (t & 63);
         if (level == 2) S[(size_t)(t >> 6)] |= (uint64_t)1 << (t & 63);
     }
+    level_words_filter(nw, gap, w, S);
+}
+
+// w: the W bits (level >= 1) of nw words with w[nw] = 0 behind them, S: the level-2 bits: w gets g (hysteresis, then closing)
+void level_words_filter(int64_t nw, int gap, uint64_t* w, const uint64_t* S) {
     bool carry = false;
     for (int64_t j = 0; j < nw; ++j) {
         w[j] = bond_hyst_word(S[(size_t)j], w[j], carry);
@@ -1173,6 +1180,41 @@ int bond_lifetime_t(const State& s, bool fft, int64_t P, int n_at, const int32_t
     });
 }
 
+// The series of observed item idb[n] against ALL reference items ida (one with its own id does not count): the level words
+// by shell_level, then bond_fill's filter; OpenMP over the observed items (lifetime_sums)
+template <class E, int D, bool PERIODIC>
+int shell_residence_t(const State& s, bool fft, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
+                      bool per_frame, const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb) {
+    const int64_t T = s.T, A = s.A, nw = (T + 63) / 64;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    std::vector<uint64_t> S;  // a thread's level-2 words
+    try {
+        S.assign((size_t)(s.threads > 0 ? s.threads : 1) * (size_t)nw, 0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    return lifetime_sums(s, fft, n_b, ci, runs, nb, [&](int64_t n, uint64_t* w) {
+        uint64_t* Sw = S.data() + (size_t)omp_get_thread_num() * (size_t)nw;
+        std::fill(Sw, Sw + nw, (uint64_t)0);
+        for (int64_t t = 0; t < T; ++t) {
+            double H[3], M[3], a[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
+            frame_box<D, PERIODIC>(hm, per_frame, t, H, M);
+            for (int d = 0; d < D; ++d) b[d] = (double)x[((size_t)t * A + idb[n]) * D + d];
+            bool form = false, brk = false;
+            for (int64_t p = 0; p < n_a; ++p) {
+                if (ida[p] == idb[n]) continue;
+                for (int d = 0; d < D; ++d) a[d] = (double)x[((size_t)t * A + ida[p]) * D + d];
+                const double r2 = vhd_r2<D, PERIODIC>(a, b, H, M);
+                form |= r2 < cuts.rc2, brk |= r2 < cuts.rb2;
+            }
+            const int level = shell_level(form, brk);
+            if (level >= 1) w[t >> 6] |= (uint64_t)1 << (t & 63);
+            if (level == 2) Sw[t >> 6] |= (uint64_t)1 << (t & 63);
+        }
+        level_words_filter(nw, gap, w, Sw);
+    });
+}
+
 int pair_find(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, bool same, int64_t stride,
               const double* hm, bool per_frame, double rc2, std::vector<int32_t>* pairs) {
     TA_PAIR_DISPATCH(pair_find_t, s, n_a, ida, n_b, idb, same, stride, hm, per_frame, rc2, pairs);
@@ -1184,6 +1226,10 @@ int pair_lifetime(const State& s, bool fft, int64_t P, const int32_t* pairs, con
 int bond_lifetime(const State& s, bool fft, int64_t P, int n_at, const int32_t* atoms, const double* hm, bool per_frame,
                   const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb) {
     TA_PAIR_DISPATCH(bond_lifetime_t, s, fft, P, n_at, atoms, hm, per_frame, cuts, gap, ci, runs, nb);
+}
+int shell_residence(const State& s, bool fft, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
+                    bool per_frame, const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb) {
+    TA_PAIR_DISPATCH(shell_residence_t, s, fft, n_a, ida, n_b, idb, hm, per_frame, cuts, gap, ci, runs, nb);
 }
 #undef TA_PAIR_DISPATCH
 

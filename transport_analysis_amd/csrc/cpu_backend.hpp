@@ -107,6 +107,11 @@ int pair_lifetime(const State& s, bool fft, int64_t P, const int32_t* pairs, con
 // level, hysteresis and closing of absences of up to `gap` frames on the packed words, as k_bond_series and k_pair_filter
 int bond_lifetime(const State& s, bool fft, int64_t P, int n_at, const int32_t* atoms, const double* hm, bool per_frame,
                   const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb);
+// ta_shell_residence: the same three sums of the n_b series of the observed items idb against ALL reference items ida (one
+// with the observed item's own id does not count): bond_math.hpp's shell_level of "some reference item closer than
+// sqrt(rc2)" / "... sqrt(rb2)", then bond_lifetime's filters, as k_shell_series and k_pair_filter.  OpenMP over observed items.
+int shell_residence(const State& s, bool fft, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
+                    bool per_frame, const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb);
 // ta_compound: out (n_frames, n_compounds, dim) float64 = sum_{i in [offsets[c], offsets[c + 1])} w_i x[t, members[i], d] -
 // g_c F[t, d] of slab 0 (g_c = sum_i w_i, F = sum_a u_a x[t, a, d]; frame_weights NULL: no such term; weights NULL: all 1),
 // the sum in member order (the first product, then fma), parallel over compounds; arguments checked by the caller

@@ -53,8 +53,9 @@ __global__ void __launch_bounds__(kPmThreads)
     const int lane = threadIdx.x & 63;
     const long words_b = pitch_b / 64;
     const long w0 = ((long)(blockIdx.x % n_tb) * VHD_TILE_B + (threadIdx.x - lane)) / 64;  // the wave's word of r = 0
-    pair_tile_walk<D, PERIODIC>(ga + (size_t)o * D * (size_t)pitch_a, gb + (size_t)o * D * (size_t)pitch_b, ida, idb, pitch_a, pitch_b, n_a,
-                                n_tb, hm + (box_per_frame ? (o_base + o) * stride * 6 : 0),
+    const PairTile tile = pair_tile_of(blockIdx.x, n_a, n_tb);
+    pair_tile_walk<D, PERIODIC>(ga + (size_t)o * D * (size_t)pitch_a, gb + (size_t)o * D * (size_t)pitch_b, ida, idb, pitch_a, pitch_b, tile.p0,
+                                tile.p1, tile.tile_b, hm + (box_per_frame ? (o_base + o) * stride * 6 : 0),
                                 [&](int p, int r, int id, int idq, double r2) {  // ballot, one lane ORs a non-zero word
                                     const unsigned long long word = __ballot(r2 < rc2 && idq >= 0 && (same ? idq > id : idq != id));
                                     if (lane == 0 && word) atomicOr(&bitmap[(size_t)p * words_b + w0 + r * (kPmThreads / 64)], word);

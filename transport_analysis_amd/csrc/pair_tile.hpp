@@ -1,5 +1,6 @@
-// pair_tile.hpp — the tile walk that k_vhd_pairs (vanhove_distinct.hip) and k_pair_find (pair_lifetime.hip) share, over the
-// frame-major float64 scratch of k_vhd_gather.  A workgroup takes (VHD_TILE_A a-items, VHD_TILE_B b-items) of one frame pair.
+// pair_tile.hpp — the tile walk that k_vhd_pairs (vanhove_distinct.hip), k_pair_find (pair_lifetime.hip) and k_shell_series
+// (shell.hip) share, over the frame-major float64 scratch of k_vhd_gather.  A workgroup of the first two takes (VHD_TILE_A
+// a-items, VHD_TILE_B b-items) of one frame pair; k_shell_series' takes all a-items against one b-tile, frame after frame.
 // A lane keeps kPairR b-items (kPairR (2 D + 1) VGPRs for D = 3: 28 of them; the bound is registers: twice as many would cost
 // occupancy without saving anything, the a-item's scalar loads are already shared by 4 pairs per lane), so the b-tile is
 // 256 kPairR = 1024 items; the a-tile is 256 items, bounded by nothing but the wish for enough workgroups per frame at a few
@@ -22,7 +23,17 @@ inline bool pair_tile_ok(long pitch_a, long pitch_b, long n_a, long n_b, int D, 
            pitch_b % VHD_TILE_B == 0 && n_ta * n_tb < VHD_MAX_TILES && T >= 1 && stride >= 1 && n_o >= 1 && n_o <= 65535;
 }
 
-// The walk of tile blockIdx.x = tile_a n_tb + tile_b.  gao [D][pitch_a], gbo [D][pitch_b]: the two frames' gathered items; ida,
+// tile x = tile_a n_tb + tile_b of a grid of a-tiles x b-tiles (k_vhd_pairs, k_pair_find): its a-items [p0, p1) and its b-tile
+struct PairTile {
+    int p0, p1, tile_b;
+};
+__device__ __forceinline__ PairTile pair_tile_of(unsigned x, int n_a, int n_tb) {
+    const int p0 = (int)(x / n_tb) * VHD_TILE_A;
+    return {p0, min(p0 + VHD_TILE_A, n_a), (int)(x % n_tb)};
+}
+
+// The walk of the a-items [p0, p1) against b-tile tile_b, all three workgroup-uniform (a tile of pair_tile_of, or every a-item
+// against one b-tile: k_shell_series).  gao [D][pitch_a], gbo [D][pitch_b]: the two frames' gathered items; ida,
 // idb: the padded lists (-1: padding); box: H[3] then M[3] of the a-frame (PERIODIC).  The lane's b-items q = tile_b VHD_TILE_B
 // + r kPmThreads + threadIdx.x, r < kPairR, sit in registers; the a-items p come by scalar loads (the loop is uniform: visit
 // may hold a ballot).  visit(p, r, id_a, id_b, r2) for every (p, r): r2 = vhd_r2<D, PERIODIC>; id_b < 0 is padding, which the
@@ -30,9 +41,8 @@ inline bool pair_tile_ok(long pitch_a, long pitch_b, long n_a, long n_b, int D, 
 // every compare of k_vhd_pairs' bin search went to a scalar pair: docs/HISTORY.md).
 template <int D, bool PERIODIC, class Visit>
 __device__ __forceinline__ void pair_tile_walk(const double* __restrict__ gao, const double* __restrict__ gbo, const int* __restrict__ ida,
-                                               const int* __restrict__ idb, long pitch_a, long pitch_b, int n_a, int n_tb,
+                                               const int* __restrict__ idb, long pitch_a, long pitch_b, int p0, int p1, int tile_b,
                                                const double* __restrict__ box, Visit&& visit) {
-    const int tile_a = blockIdx.x / n_tb, tile_b = blockIdx.x % n_tb;
     double H[3] = {1.0, 1.0, 1.0}, M[3] = {1.0, 1.0, 1.0};
     if constexpr (PERIODIC) {
 #pragma unroll
@@ -47,7 +57,6 @@ __device__ __forceinline__ void pair_tile_walk(const double* __restrict__ gao, c
 #pragma unroll
         for (int d = 0; d < 3; ++d) xb[r][d] = d < D ? gbo[(size_t)d * pitch_b + q] : 0.0;
     }
-    const int p0 = tile_a * VHD_TILE_A, p1 = min(p0 + VHD_TILE_A, n_a);
     for (int p = p0; p < p1; ++p) {  // (uniform: the a-item comes by scalar loads)
         double xa[3] = {0.0, 0.0, 0.0};
 #pragma unroll

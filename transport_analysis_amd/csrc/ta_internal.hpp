@@ -495,6 +495,16 @@ hipError_t launch_pair_series(int n_cu, const void* x, bool f32, long pitch, lon
 hipError_t launch_pair_runs(int n_cu, const double* Z, long pitch, long T, long n_pairs, unsigned long long* runs, hipStream_t st);
 hipError_t launch_pair_reduce(const double* rows, int n_rows, long n, long T, int mode, double* out, hipStream_t st);
 
+// shell.hip: the level block of the shell residence times.  The frames [f_base, f_base + n_f) of the slab (f_base a multiple of
+// 64, at most 65535 64-frame words) are the scratch ga [n_f][D][pitch_a], gb [n_f][D][pitch_b] that launch_vhd_gather wrote at
+// lag 0, stride 1, o_base = f_base; pitch_b = ceil(n_b / VHD_TILE_B) VHD_TILE_B.  Rows f_base ... of Z (ceil(n_b / 2) destination
+// pairs of `pitch` rows, one pseudo-atom of dim 1 per b-item) get the level 0.0 / 1.0 / `two` of b-item q against ALL a-items
+// (bond_math.hpp, shell_level; an a-item with q's id does not count), the launch that holds frame T - 1 also the zeros of the
+// rows T ... pitch - 1 and of an odd n_b's phantom column.  hm as launch_vhd_pairs'; two as launch_bond_series'.
+hipError_t launch_shell_series(const double* ga, const double* gb, const int* ida, const int* idb, long pitch_a, long pitch_b, long n_a,
+                               long n_b, int D, long T, long pitch, long f_base, long n_f, const double* hm, bool box_per_frame,
+                               double rc2, double rb2, double two, double* Z, hipStream_t st);
+
 // unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
 // box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)
 hipError_t launch_unwrap(double* slab, long pitch, long T, long n_atoms, int D, const int* axes, bool triclinic,

@@ -81,8 +81,9 @@ __global__ void __launch_bounds__(kPmThreads)
 
     const double e_top = e_g[B];
     unsigned over = 0;
+    const PairTile tile = pair_tile_of(blockIdx.x, n_a, n_tb);
     pair_tile_walk<D, PERIODIC>(ga + (size_t)o * D * (size_t)pitch_a, gb + ((size_t)blockIdx.z * (size_t)n_orig + (size_t)o) * D * (size_t)pitch_b,
-                                ida, idb, pitch_a, pitch_b, n_a, n_tb, hm + (box_per_frame ? t * 6 : 0),
+                                ida, idb, pitch_a, pitch_b, tile.p0, tile.p1, tile.tile_b, hm + (box_per_frame ? t * 6 : 0),
                                 [&](int, int, int id, int idq, double r2) {  // bin or overflow
                                     if (idq >= 0 && idq != id) {
                                         if (r2 < e_top) atomicAdd(&hist[vh_bin(r2, e, B, inv_dr)], 1u);
