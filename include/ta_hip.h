@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_pair_find / ta_pair_find_read / ta_pair_lifetime / ta_bond_lifetime / ta_shell_residence / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_pair_find / ta_pair_find_read / ta_pair_lifetime / ta_bond_lifetime / ta_shell_residence / ta_shell_msd / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -687,6 +687,42 @@ int ta_shell_residence(ta_ctx *ctx, int fft, int64_t n_a, const int64_t *h_idx_a
                        const int *axes, double r_cut, double r_break, int gap, double *h_ci /* (T) */,
                        int64_t *h_runs /* (T + 1) */, double *h_nb /* (T) */);
 
+/* ta_shell_msd : the mean squared displacement of the observed items WHILE they are in the shell of the group (ShellMSD; the
+ *              shell-resolved diffusion of Liu, Harder and Berne, MDAnalysis' waterdynamics zone MSD).  With g_q(t) the 0/1
+ *              series of ta_shell_residence (same arguments, same bits), for the lags tau = 0 ... max_lag and axes j < dim
+ *                w_q(t, tau) = prod_{s = t ... t + tau} g_q(s)         condition TA_SHELL_CONTINUOUS (0)
+ *                w_q(t, tau) = g_q(t) g_q(t + tau)                     condition TA_SHELL_ENDPOINTS  (1)
+ *                h_sums[tau][j] = sum_q sum_{t < T - tau} w_q(t, tau) (x_qj(t + tau) - x_qj(t))^2      float64 (max_lag + 1, dim)
+ *                h_count[tau]   = sum_q sum_{t < T - tau} w_q(t, tau)                                  exact int64 (max_lag + 1)
+ *              h_runs, h_nb: ta_shell_residence's.  The difference is formed in float64 after widening a float32 slab's
+ *              elements in registers; NO image is applied to it: the positions must be unwrapped (ta_unwrap subtracts whole
+ *              boxes of the frame itself, so the distance pass, which keeps its rint image, gives the same g on the unwrapped
+ *              slab for orthorhombic boxes).  Every term is fma(d, d, acc).  count[tau] under "continuous" equals
+ *              sum_{l > tau} runs[l] (l - tau), under "endpoints" ta_shell_residence's ci[tau] with fft = 0.
+ *              Passes.  ta_shell_residence's, per block of observed items, up to k_pair_filter, k_pair_runs and the nb sum;
+ *              then k_shell_bits packs the block's series by ballots (Z is read once more, everything behind reads 1 / 64 of
+ *              it); k_shell_msd gives a workgroup the 256 lags of one pass, one per thread, and the items x, x + G, ... of
+ *              the block: per chunk of origin frames ("shell_msd_chunk") the item's columns of the lagged frames go from the
+ *              slab, in its own element type and through the same reader as every pair-major kernel, to LDS; a chunk without
+ *              a frame inside is left after its words have been read; per origin inside (a scalar loop over the set bits of
+ *              a workgroup-uniform word) the origin comes from a lane by v_readlane, the lagged frame from LDS, and the gate
+ *              is one compare against the frames left in the run ("continuous"; origins whose run ends below the pass's
+ *              lags are skipped by the whole workgroup) or one bit of the thread's window of g ("endpoints", whose popcount
+ *              is the count).  Sums and counts stay in registers over all items of a workgroup; k_shell_fold adds the
+ *              workgroups' rows in row order, the blocks in block order.  No atomics, no float add whose order depends on
+ *              timing: repeat runs give the same bits.  The staged slab is only read.  The CPU backend follows the same
+ *              arithmetic (shell_msd_math.hpp): on inputs whose sums are exact in float64 the outputs are EQUAL, otherwise
+ *              within the library's 1e-10 scale-relative bound (the order of the adds differs).
+ *              Errors, all checked before anything is written.  ta_shell_residence's (without fft), and TA_E_INVALID:
+ *              condition other than 0 / 1; all four outputs NULL; max_lag < 0, above n_frames - 1 or above the cap 2047
+ *              (eight passes of 256 lags; the message names it).  There is no ta_group_* form.                          */
+#define TA_SHELL_CONTINUOUS 0
+#define TA_SHELL_ENDPOINTS 1
+int ta_shell_msd(ta_ctx *ctx, int condition, int64_t max_lag, int64_t n_a, const int64_t *h_idx_a /* reference; NULL: all */,
+                 int64_t n_b, const int64_t *h_idx_b /* observed; NULL: b = a */, const double *h_dimensions, const int *axes,
+                 double r_cut, double r_break, int gap, double *h_sums /* (max_lag + 1, dim) */,
+                 int64_t *h_count /* (max_lag + 1) */, int64_t *h_runs /* (T + 1) */, double *h_nb /* (T) */);
+
 /* ta_orient  : the rotational correlation functions of molecule-fixed unit vectors of the positions in slab 0
  *              (OrientationalCorrelation), three staged columns per atom.  A vector n is row n of h_index, atoms of slab 0,
  *              pairwise distinct and in [0, n_atoms):
@@ -941,6 +977,11 @@ int ta_bond_lifetime_staged(ta_ctx *ctx, int fft, int64_t n_bonds, int n_at, con
 int ta_shell_residence_staged(ta_ctx *ctx, int fft, int64_t n_a, const int64_t *h_idx_a, int64_t n_b, const int64_t *h_idx_b,
                               const double *h_dimensions, const int *axes, double r_cut, double r_break, int gap, double *d_ci,
                               int64_t *d_runs, double *d_nb, void *stream);
+/* the index lists and the box: HOST arrays, as for ta_shell_msd (checked before anything is written); the outputs on the
+ * device: d_sums (max_lag + 1, dim) float64, d_count (max_lag + 1) int64, d_runs (T + 1) int64, d_nb (T) float64 */
+int ta_shell_msd_staged(ta_ctx *ctx, int condition, int64_t max_lag, int64_t n_a, const int64_t *h_idx_a, int64_t n_b,
+                        const int64_t *h_idx_b, const double *h_dimensions, const int *axes, double r_cut, double r_break, int gap,
+                        double *d_sums, int64_t *d_count, int64_t *d_runs, double *d_nb, void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns
@@ -1155,6 +1196,9 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      at least 1, at most 65535; n >= 1: min(n, frames)); the found list does not depend on it;
  *   "shell_chunk" n : 64-frame words per pass of ta_shell_residence* (0, the default: as many as fit 4 GiB of gathered
  *                      scratch, at least 1, at most 65535; n >= 1: min(n, words)); the results do not depend on it;
+ *   "shell_msd_chunk" n : origin frames per staged chunk of k_shell_msd (0, the default: 512; n >= 1: n rounded up to a
+ *                      multiple of 64, at most 1024); counts do not depend on it, sums by the order of a thread's adds only
+ *                      (the origins stay in frame order: the same bits);
  *   "async_commit" 1|0 : ta_stage_commit hands its frame range to a worker thread of the context, which
  *                      makes the HIP calls (the caller's frame loop never waits on the runtime, e.g. while
  *                      another thread page-locks a result array); every call that touches the slabs joins

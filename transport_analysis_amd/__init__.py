@@ -8,7 +8,8 @@ self-overlap Q(t) with the four-point susceptibility chi_4(t), DynamicSusceptibi
 C_1(t), C_2(t) of molecule-fixed unit vectors with their dipole sum, OrientationalCorrelation, and the intermittent and
 continuous pair population correlation functions with the lifetimes of ion pairs and solvation contacts, PairLifetime, and
 of hydrogen bonds with a donor-hydrogen-acceptor angle criterion, HydrogenBondLifetime, and the residence times of atoms in
-the solvation shell of a whole group, ShellResidence."""
+the solvation shell of a whole group, ShellResidence, with the mean squared displacement of the atoms while they stay in that
+shell, ShellMSD."""
 __version__ = "0.1.0"
 
 from .velocityautocorr import VelocityAutocorr  # noqa: F401
@@ -27,3 +28,4 @@ from .orientation import OrientationalCorrelation, group_indices  # noqa: F401
 from .pair_lifetime import PairLifetime  # noqa: F401
 from .hbond_lifetime import HydrogenBondLifetime  # noqa: F401
 from .shell_residence import ShellResidence  # noqa: F401
+from .shell_msd import ShellMSD  # noqa: F401

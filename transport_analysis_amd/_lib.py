@@ -18,6 +18,8 @@ _CSRC = os.path.join(_HERE, "csrc")
 TA_F32, TA_F64 = 0, 1
 #: ta_orient's modes (TA_ORIENT_*)
 ORIENT_MODES = {"bond": 0, "bisector": 1, "normal": 2}
+#: ta_shell_msd's conditions (TA_SHELL_*)
+SHELL_CONDITIONS = {"continuous": 0, "endpoints": 1}
 
 _vp, _i64, _ci, _dbl, _str = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_char_p
 _P = ctypes.POINTER
@@ -98,6 +100,9 @@ _API = {
     "ta_bond_lifetime_staged": _int(_vp, _ci, _i64, _ci, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp),
     "ta_shell_residence": _int(_vp, _ci, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _vp, _vp),
     "ta_shell_residence_staged": _int(_vp, _ci, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp),
+    # (handle, condition, max_lag, n_a, idx_a, n_b, idx_b, h_dimensions, axes, r_cut, r_break, gap, sums, count, runs, nb[, stream])
+    "ta_shell_msd": _int(_vp, _ci, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp),
+    "ta_shell_msd_staged": _int(_vp, _ci, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp, _vp),
     "ta_vanhove_distinct_staged": _int(_vp, _ci, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _dbl, _vp, _vp),
     "ta_compound": _int(_vp, _i64, _vp, _vp, _vp, _vp, _P(_vp)),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
@@ -1051,6 +1056,40 @@ class Context(_Staged):
         (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
         self._life_staged("shell_residence_staged", self._shell_args(fft, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes),
                           d_ci, d_runs, d_nb, stream)
+
+    def _shell_msd_args(self, condition, max_lag, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes):
+        """the argument tuple ta_shell_msd* share, and the arrays it points into (to be kept until the call is over)"""
+        code = SHELL_CONDITIONS.get(condition, condition)
+        if isinstance(code, str):
+            raise ValueError(f"condition: {condition!r}, expected one of {sorted(SHELL_CONDITIONS)}")
+        args, keep = self._shell_args(code, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
+        return (args[0], int(max_lag)) + args[1:], keep
+
+    def shell_msd(self, condition, max_lag, r_cut, *, r_break=None, gap=0, idx_a=None, idx_b=None, dimensions=None, axes=None,
+                  sums=True, count=True, runs=True, nb=True):
+        """(sums (max_lag + 1, dim), count (max_lag + 1,) int64, runs, nb) of slab 0, ta_shell_msd: the squared displacements
+        of the observed items of `idx_b` over the lags 0 ... max_lag, summed over the origins at which the item is in the shell
+        of the reference items `idx_a` under `condition`: "continuous" (inside in every frame from the origin to the lag) or
+        "endpoints" (inside at both ends); the shell, `runs` and `nb` as shell_residence's.  The positions must be unwrapped.
+        One context only: a device group has no such call."""
+        T, _, D = self._staged_shape()
+        args, keep = self._shell_msd_args(condition, max_lag, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
+        L = max(int(max_lag), 0)
+        o_sums = np.empty((L + 1, D), dtype=np.float64) if sums else None
+        o_count = np.empty(L + 1, dtype=np.int64) if count else None
+        o_runs = np.empty(T + 1, dtype=np.int64) if runs else None
+        o_nb = np.empty(T, dtype=np.float64) if nb else None
+        self._call("shell_msd", *args, _ptr(o_sums), _ptr(o_count), _ptr(o_runs), _ptr(o_nb))
+        del keep
+        return o_sums, o_count, o_runs, o_nb
+
+    def shell_msd_staged(self, condition, max_lag, r_cut, *, r_break=None, gap=0, idx_a=None, idx_b=None, dimensions=None,
+                         axes=None, d_sums=0, d_count=0, d_runs=0, d_nb=0, stream=0):
+        """the lists and `dimensions`: HOST arrays (checked by the library before anything is written); d_sums (max_lag + 1,
+        dim), d_count (max_lag + 1,) int64, d_runs (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
+        args, keep = self._shell_msd_args(condition, max_lag, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
+        self._call("shell_msd_staged", *args, d_sums or None, d_count or None, d_runs or None, d_nb or None, stream or None)
+        del keep
 
     def _orient_args(self, fft, index, mode, dimensions, weights):
         """the argument tuple ta_orient* share, and the arrays it points into (to be kept until the call is over)"""

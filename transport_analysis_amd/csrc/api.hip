@@ -26,6 +26,7 @@
 #include "orient_math.hpp"
 #include "pair_math.hpp"
 #include "phase_math.hpp"
+#include "shell_msd_math.hpp"
 #include "ta_internal.hpp"
 #include "unwrap_box.hpp"
 #include "vanhove_distinct_math.hpp"
@@ -131,6 +132,7 @@ private:
     X(pair_chunk, 0, opt_check_pair_chunk) /* candidate pairs per block of ta_pair_lifetime* (0: as many as fit kPairBudget) */ \
     X(pair_find_chunk, 0, opt_check_pair_find_chunk) /* searched frames per pass of ta_pair_find (0: as many as fit kVhdBudget) */ \
     X(shell_chunk, 0, opt_check_shell_chunk) /* 64-frame words per pass of ta_shell_residence* (0: as many as fit kVhdBudget) */ \
+    X(shell_msd_chunk, 0, opt_check_shell_msd_chunk) /* origin frames per staged chunk of k_shell_msd (0: 512) */ \
     X(async_commit, 1, opt_flush_commits) /* ta_stage_commit goes through the commit queue; flushed before it changes */   \
     X(lock_ahead, 1, nullptr)      /* the commit worker page-locks the chunks behind the one it committed */               \
     X(cpu_threads, 0, opt_set_cpu_threads) /* CPU backend: OpenMP team size (0: the runtime's default) */                  \
@@ -220,6 +222,8 @@ struct ta_ctx {
     // shell residence times (shell_pm): the table (a zero lag, box entries, padded index lists, zero labels); the scratch is
     // vhd_scr, the level block and everything behind it the pair lifetimes' (pair_z, pair_rows, pair_out)
     HostTable shell_tab{workspaces, tables};
+    // ta_shell_msd*: the packed words of g of one block of observed items, and k_shell_msd's partial rows
+    DevBuf shell_words{workspaces, kTrimmed}, shell_part{workspaces, kTrimmed};
     std::vector<int32_t> pair_host;
     // ta_compound: the plan (offsets, members, member weights, their sums per compound) and the (n_frames, dim) weighted
     // mean F of the barycentric term; the per-atom frame weights and F's partial sums use the Onsager workspaces
@@ -2239,10 +2243,11 @@ struct ShellPlan : ItemLists {
     PairBox box;
     bool filter() const { return gap > 0 || cuts.rb2 != cuts.rc2; }
 };
-int shell_plan(ta_ctx* ctx, int fft, const ShellArgs& a, bool any_out, ShellPlan* p) {
-    const std::string who = "shell_residence: ";
+int shell_plan(ta_ctx* ctx, int fft, const ShellArgs& a, bool any_out, ShellPlan* p, const char* name = "shell_residence",
+               const char* outputs = "ci, runs and nb") {
+    const std::string who = std::string(name) + ": ";
     TA_CHECK(check_fft(ctx, fft));
-    if (!any_out) return fail(ctx, TA_E_INVALID, who + "the ci, runs and nb outputs are all NULL");
+    if (!any_out) return fail(ctx, TA_E_INVALID, who + "the " + outputs + " outputs are all NULL");
     if (a.h_idx_a && a.n_a < 1) return fail(ctx, TA_E_INVALID, who + "n_a must be >= 1");
     if (a.h_idx_b && a.n_b < 1) return fail(ctx, TA_E_INVALID, who + "n_b must be >= 1");
     TA_CHECK(pair_cut_args(ctx, who, a.r_cut, a.h_dims, a.axes));
@@ -2255,7 +2260,7 @@ int shell_plan(ta_ctx* ctx, int fft, const ShellArgs& a, bool any_out, ShellPlan
     TA_CHECK(check_cols(ctx, who, A, D));
     p->D = D, p->T = T, p->A = A, p->gap = a.gap;
     p->cuts = ta::BondCuts{a.r_cut * a.r_cut, a.r_break * a.r_break, 0.0, 0.0};
-    TA_CHECK(item_lists(ctx, "shell_residence", a.n_a, a.h_idx_a, a.n_b, a.h_idx_b, A, p));
+    TA_CHECK(item_lists(ctx, name, a.n_a, a.h_idx_a, a.n_b, a.h_idx_b, A, p));
     bool same = false;
     TA_CHECK(lists_same_or_disjoint(ctx, who, *p, a.h_idx_b != nullptr, &same));
     if (p->n_b >= (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, who + "n_b must be below 2^30");
@@ -2279,7 +2284,29 @@ int64_t shell_block(const ta_ctx* ctx, int64_t n_b, int64_t pitch) {
 // life_sums_block, pair_life_pm's passes.  Neither chunking changes a bit: every row of Z has one writer whatever the chunk,
 // and the blocks' rows are added as pair_life_pm's.  ev[1] / ev[2] bracket the (last) k_shell_series launch, unless a
 // lag-sum evaluation after it records its own main kernel.
-int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, double* d_ci, int64_t* d_runs, double* d_nb) {
+// msd (ta_shell_msd*, otherwise NULL): behind a block's filter k_shell_bits packs its series, k_shell_msd (shell_msd.hip) adds
+// up the gated squared displacements of the block's items over the lags 0 ... L and k_shell_fold adds the workgroups' partial
+// rows in row order onto sums and count: the blocks in block order.
+struct ShellMsd {
+    int condition;
+    int64_t L;
+    double* d_sums;
+    int64_t* d_count;
+};
+int shell_msd_block(ta_ctx* ctx, const ShellMsd& m, const Slab& slab, const LifeSums& s, int64_t b, int64_t nb, const int* ids) {
+    hipStream_t st = slab.st;
+    const int G = ta::shell_msd_groups(ctx->n_cu, (long)nb, (long)m.L);
+    unsigned long long* words = (unsigned long long*)ctx->shell_words.p;
+    TA_LAUNCH(ctx, "k_shell_bits", st, ta::launch_shell_bits(ctx->n_cu, s.Z, (long)s.pitch, (long)s.T, (long)nb, words, st));
+    TA_LAUNCH(ctx, "k_shell_msd", st,
+              ta::launch_shell_msd(slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, slab.D, ids, (long)nb, words, m.condition,
+                                   (long)m.L, ta::shell_msd_chunk((long)ctx->opt_shell_msd_chunk), G, ctx->shell_part.p, st));
+    TA_LAUNCH(ctx, "k_shell_fold", st,
+              ta::launch_shell_fold(ctx->shell_part.p, G, (long)m.L, slab.D, b == 0, m.d_sums, (long long*)m.d_count, st));
+    return TA_OK;
+}
+int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, double* d_ci, int64_t* d_runs, double* d_nb,
+             const ShellMsd* msd = nullptr) {
     hipStream_t st = slab.st;
     const int D = p.D;
     const int64_t T = slab.T, pitch = slab.pitch, N = p.n_b, Qc = shell_block(ctx, N, pitch);
@@ -2292,6 +2319,12 @@ int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, double
     const int64_t wc = std::min<int64_t>({words, 65535, ctx->opt_shell_chunk > 0 ? ctx->opt_shell_chunk : fit});
     TA_CHECK(ensure(ctx, ctx->vhd_scr, (size_t)std::min(T, 64 * wc) * per));
     double* ga = (double*)ctx->vhd_scr.p;
+    if (msd && (msd->d_sums || msd->d_count)) {
+        TA_CHECK(ensure(ctx, ctx->shell_words, sizeof(uint64_t) * (size_t)Qc * (size_t)words));
+        TA_CHECK(ensure(ctx, ctx->shell_part, ta::shell_msd_part_bytes(ta::shell_msd_groups(ctx->n_cu, (long)Qc, (long)msd->L), (long)msd->L, D)));
+    } else {
+        msd = nullptr;
+    }
     LifeSums s;
     TA_CHECK(life_sums_begin(ctx, fft, slab, N, Qc, d_ci, d_runs, d_nb, &s));
     for (int64_t b = 0; b < s.n_blocks; ++b) {
@@ -2308,12 +2341,15 @@ int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, double
                                                p.filter() ? 2.0 : 1.0, s.Z, st));
         }
         TA_CHECK(life_sums_block(ctx, s, b, nb, p.filter(), p.gap, lab));
+        if (msd) TA_CHECK(shell_msd_block(ctx, *msd, slab, s, b, nb, idb + q0));
     }
     return life_sums_end(ctx, s);
 }
 
-// ta_shell_residence_staged and the device half of ta_shell_residence (out as pair_life_launch's)
-int shell_launch(ta_ctx* ctx, int fft, const ShellPlan& p, double* d_ci, int64_t* d_runs, double* d_nb, void* stream, double** out) {
+// ta_shell_residence_staged and the device half of ta_shell_residence (out as pair_life_launch's).  msd (ta_shell_msd*): no ci;
+// the context's own output buffer is then sums ((L + 1) D) | count (L + 1) | runs (T + 1) | nb (T)
+int shell_launch(ta_ctx* ctx, int fft, const ShellPlan& p, double* d_ci, int64_t* d_runs, double* d_nb, void* stream, double** out,
+                 const ShellMsd* msd = nullptr) {
     return slab_entry(
         ctx, nullptr, stream, no_args,
         [&](const Slab& s) -> int {
@@ -2324,16 +2360,36 @@ int shell_launch(ta_ctx* ctx, int fft, const ShellPlan& p, double* d_ci, int64_t
             memset(h, 0, sizeof(double) * n);  // (the zero lag in front, the zero labels behind)
             pair_tail_pack(h + 1, p.box, p);
             if (out) {
-                TA_CHECK(ensure(ctx, ctx->pair_out, sizeof(double) * (3 * (size_t)s.T + 1)));
+                const size_t n_msd = msd ? (size_t)(msd->L + 1) * (size_t)(p.D + 1) : (size_t)s.T;
+                TA_CHECK(ensure(ctx, ctx->pair_out, sizeof(double) * (n_msd + 2 * (size_t)s.T + 1)));
                 *out = (double*)ctx->pair_out.p;
             }
             return ctx->shell_tab.send(ctx, s.st);
         },
         [&](const Slab& s) {
-            if (!out) return shell_pm(ctx, fft != 0, s, p, d_ci, d_runs, d_nb);
+            if (msd && out) {
+                double* o = *out;
+                const size_t n1 = (size_t)(msd->L + 1) * (size_t)p.D, n2 = (size_t)msd->L + 1;
+                const ShellMsd m{msd->condition, msd->L, msd->d_sums ? o : nullptr, msd->d_count ? (int64_t*)(o + n1) : nullptr};
+                return shell_pm(ctx, false, s, p, nullptr, d_runs ? (int64_t*)(o + n1 + n2) : nullptr, d_nb ? o + n1 + n2 + s.T + 1 : nullptr, &m);
+            }
+            if (!out) return shell_pm(ctx, fft != 0, s, p, d_ci, d_runs, d_nb, msd);
             double* o = *out;
             return shell_pm(ctx, fft != 0, s, p, d_ci ? o : nullptr, d_runs ? (int64_t*)(o + s.T) : nullptr, d_nb ? o + 2 * s.T + 1 : nullptr);
         });
+}
+
+// the argument checks of ta_shell_msd*: shell_plan's, and the condition and max_lag against the staged frames and the cap
+int shell_msd_plan(ta_ctx* ctx, int condition, int64_t max_lag, const ShellArgs& a, bool any_out, ShellPlan* p) {
+    const std::string who = "shell_msd: ";
+    if (condition != ta::SHELL_CONTINUOUS && condition != ta::SHELL_ENDPOINTS)
+        return fail(ctx, TA_E_INVALID, who + "condition must be 0 (continuous) or 1 (endpoints)");
+    TA_CHECK(shell_plan(ctx, 0, a, any_out, p, "shell_msd", "sums, count, runs and nb"));
+    if (max_lag < 0 || max_lag > p->T - 1)
+        return fail(ctx, TA_E_INVALID, who + "max_lag must be 0 ... n_frames - 1 = " + std::to_string(p->T - 1));
+    if (max_lag > ta::kShellMsdMaxLag)
+        return fail(ctx, TA_E_INVALID, who + "max_lag must be at most " + std::to_string(ta::kShellMsdMaxLag) + " (eight passes of 256 lags)");
+    return TA_OK;
 }
 
 // ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
@@ -2434,6 +2490,9 @@ int opt_check_pair_find_chunk(ta_ctx* ctx, int64_t value) {
 }
 int opt_check_shell_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "shell_chunk: 0 (automatic) or the 64-frame words per pass");
+}
+int opt_check_shell_msd_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "shell_msd_chunk: 0 (automatic) or the origin frames per staged chunk");
 }
 int opt_check_overlap_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "overlap_chunk: 0 (automatic) or the lags per launch");
@@ -3281,6 +3340,21 @@ int ta_shell_residence_staged(ta_ctx* ctx, int fft, int64_t n_a, const int64_t* 
     TA_NO_CPU(ctx);
     TA_CHECK(shell_plan(ctx, fft, a, d_ci || d_runs || d_nb, &plan));
     return shell_launch(ctx, fft, plan, d_ci, d_runs, d_nb, stream, nullptr);
+    });
+}
+
+// The shell-resolved MSD on the staged slab 0; the index lists and the box are HOST arrays, the outputs on the device
+int ta_shell_msd_staged(ta_ctx* ctx, int condition, int64_t max_lag, int64_t n_a, const int64_t* h_idx_a, int64_t n_b,
+                        const int64_t* h_idx_b, const double* h_dimensions, const int* axes, double r_cut, double r_break, int gap,
+                        double* d_sums, int64_t* d_count, int64_t* d_runs, double* d_nb, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
+    ShellPlan plan;
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(shell_msd_plan(ctx, condition, max_lag, a, d_sums || d_count || d_runs || d_nb, &plan));
+    const ShellMsd m{condition, max_lag, d_sums, d_count};
+    return shell_launch(ctx, 0, plan, nullptr, d_runs, d_nb, stream, nullptr, &m);
     });
 }
 
@@ -4195,6 +4269,26 @@ int ta_shell_residence(ta_ctx* ctx, int fft, int64_t n_a, const int64_t* h_idx_a
     TA_CHECK(shell_launch(ctx, fft, p, h_ci, h_runs, h_nb, ctx->stream, &d_out));
     const size_t T = (size_t)ctx->st_T;  // (int64 counts travel as 8-byte elements)
     return host_finish(ctx, {{h_ci, d_out, T}, {(double*)h_runs, d_out + T, T + 1}, {h_nb, d_out + 2 * T + 1, T}});
+    });
+}
+
+int ta_shell_msd(ta_ctx* ctx, int condition, int64_t max_lag, int64_t n_a, const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b,
+                 const double* h_dimensions, const int* axes, double r_cut, double r_break, int gap, double* h_sums, int64_t* h_count,
+                 int64_t* h_runs, double* h_nb) {
+    return host_call(ctx, [&]() -> int {
+    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
+    ShellPlan p;
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(shell_msd_plan(ctx, condition, max_lag, a, h_sums || h_count || h_runs || h_nb, &p));
+    if (ctx->is_cpu)
+        return cpu_rc(ctx, ta::cpu::shell_msd(cpu_state(ctx), condition, max_lag, p.n_a, p.ida.data(), p.n_b, p.idb.data(), p.box.data(),
+                                              p.box.per_frame, p.cuts, p.gap, h_sums, h_count, h_runs, h_nb));
+    double* d_out = nullptr;
+    const ShellMsd m{condition, max_lag, h_sums, h_count};  // (which outputs are asked for: shell_launch points them into d_out)
+    TA_CHECK(shell_launch(ctx, 0, p, nullptr, h_runs, h_nb, ctx->stream, &d_out, &m));
+    const size_t T = (size_t)ctx->st_T, n1 = (size_t)(max_lag + 1) * (size_t)p.D, n2 = (size_t)max_lag + 1;  // (int64 as 8-byte elements)
+    return host_finish(ctx, {{h_sums, d_out, n1}, {(double*)h_count, d_out + n1, n2}, {(double*)h_runs, d_out + n1 + n2, T + 1},
+                             {h_nb, d_out + n1 + n2 + T + 1, T}});
     });
 }
 

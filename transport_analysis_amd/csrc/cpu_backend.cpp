@@ -43,6 +43,7 @@
 #include "orient_math.hpp"
 #include "bond_math.hpp"
 #include "pair_math.hpp"
+#include "shell_msd_math.hpp"
 #include "unwrap_box.hpp"
 #include "vanhove_distinct_math.hpp"
 #include "vanhove_math.hpp"
@@ -1180,8 +1181,32 @@ int bond_lifetime_t(const State& s, bool fft, int64_t P, int n_at, const int32_t
     });
 }
 
-// The series of observed item idb[n] against ALL reference items ida (one with its own id does not count): the level words
-// by shell_level, then bond_fill's filter; OpenMP over the observed items (lifetime_sums)
+// The series of the observed item idq against ALL reference items ida (one with its own id does not count): the level words
+// by shell_level (Sw: nw words for the level-2 bits), then bond_fill's filter: w gets g
+template <class E, int D, bool PERIODIC>
+void shell_fill(const E* x, int64_t T, int64_t A, int64_t n_a, const int32_t* ida, int32_t idq, const double* hm, bool per_frame,
+                const BondCuts& cuts, int gap, uint64_t* Sw, uint64_t* w) {
+    const int64_t nw = (T + 63) / 64;
+    std::fill(Sw, Sw + nw, (uint64_t)0);
+    for (int64_t t = 0; t < T; ++t) {
+        double H[3], M[3], a[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
+        frame_box<D, PERIODIC>(hm, per_frame, t, H, M);
+        for (int d = 0; d < D; ++d) b[d] = (double)x[((size_t)t * A + idq) * D + d];
+        bool form = false, brk = false;
+        for (int64_t p = 0; p < n_a; ++p) {
+            if (ida[p] == idq) continue;
+            for (int d = 0; d < D; ++d) a[d] = (double)x[((size_t)t * A + ida[p]) * D + d];
+            const double r2 = vhd_r2<D, PERIODIC>(a, b, H, M);
+            form |= r2 < cuts.rc2, brk |= r2 < cuts.rb2;
+        }
+        const int level = shell_level(form, brk);
+        if (level >= 1) w[t >> 6] |= (uint64_t)1 << (t & 63);
+        if (level == 2) Sw[t >> 6] |= (uint64_t)1 << (t & 63);
+    }
+    level_words_filter(nw, gap, w, Sw);
+}
+
+// shell_fill per observed item; OpenMP over the observed items (lifetime_sums)
 template <class E, int D, bool PERIODIC>
 int shell_residence_t(const State& s, bool fft, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
                       bool per_frame, const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb) {
@@ -1194,25 +1219,65 @@ int shell_residence_t(const State& s, bool fft, int64_t n_a, const int32_t* ida,
         return TA_E_NOMEM;
     }
     return lifetime_sums(s, fft, n_b, ci, runs, nb, [&](int64_t n, uint64_t* w) {
-        uint64_t* Sw = S.data() + (size_t)omp_get_thread_num() * (size_t)nw;
-        std::fill(Sw, Sw + nw, (uint64_t)0);
-        for (int64_t t = 0; t < T; ++t) {
-            double H[3], M[3], a[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
-            frame_box<D, PERIODIC>(hm, per_frame, t, H, M);
-            for (int d = 0; d < D; ++d) b[d] = (double)x[((size_t)t * A + idb[n]) * D + d];
-            bool form = false, brk = false;
-            for (int64_t p = 0; p < n_a; ++p) {
-                if (ida[p] == idb[n]) continue;
-                for (int d = 0; d < D; ++d) a[d] = (double)x[((size_t)t * A + ida[p]) * D + d];
-                const double r2 = vhd_r2<D, PERIODIC>(a, b, H, M);
-                form |= r2 < cuts.rc2, brk |= r2 < cuts.rb2;
-            }
-            const int level = shell_level(form, brk);
-            if (level >= 1) w[t >> 6] |= (uint64_t)1 << (t & 63);
-            if (level == 2) Sw[t >> 6] |= (uint64_t)1 << (t & 63);
-        }
-        level_words_filter(nw, gap, w, Sw);
+        shell_fill<E, D, PERIODIC>(x, T, A, n_a, ida, idb[n], hm, per_frame, cuts, gap, S.data() + (size_t)omp_get_thread_num() * (size_t)nw, w);
     });
+}
+
+// ta_shell_msd: shell_residence_t's series g of every observed item (runs, nb by lifetime_sums), and behind each item's fill its
+// gated squared displacements over the lags 0 ... L (shell_msd_math.hpp: the same term, fma(d, d, acc), and the same gates as
+// k_shell_msd): a plain loop over the origins inside, left(s) from one walk down the frames.  A thread adds into sums and
+// counts of its own; the threads' sums are added in thread order (exact inputs: any order gives the same bits).
+template <class E, int D, bool PERIODIC>
+int shell_msd_t(const State& s, int condition, int64_t L, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
+                bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs, double* nb) {
+    const int64_t T = s.T, A = s.A, nw = (T + 63) / 64;
+    const int nth = s.threads > 0 ? s.threads : 1;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    const size_t n1 = (size_t)(L + 1) * D, n2 = (size_t)L + 1;
+    std::vector<uint64_t> S;
+    std::vector<double> acc;
+    std::vector<int64_t> cnt, left;
+    try {
+        S.assign((size_t)nth * (size_t)nw, 0);
+        acc.assign((size_t)nth * n1, 0.0);
+        cnt.assign((size_t)nth * n2, 0);
+        left.assign((size_t)nth * (size_t)(T + 1), 0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    const int rc = lifetime_sums(s, false, n_b, nullptr, runs, nb, [&](int64_t n, uint64_t* w) {
+        const int th = omp_get_thread_num();
+        shell_fill<E, D, PERIODIC>(x, T, A, n_a, ida, idb[n], hm, per_frame, cuts, gap, S.data() + (size_t)th * (size_t)nw, w);
+        if (!sums && !count) return;
+        double* a_s = acc.data() + (size_t)th * n1;
+        int64_t *a_n = cnt.data() + (size_t)th * n2, *lf = left.data() + (size_t)th * (size_t)(T + 1);
+        auto inside = [&](int64_t t) { return (w[t >> 6] >> (t & 63)) & 1; };
+        lf[T] = 0;
+        for (int64_t t = T - 1; t >= 0; --t) lf[t] = inside(t) ? lf[t + 1] + 1 : 0;
+        const E* xq = x + (size_t)idb[n] * D;
+        for (int64_t t = 0; t < T; ++t) {
+            if (!inside(t)) continue;
+            const int64_t k_end = condition == SHELL_CONTINUOUS ? std::min(lf[t], L + 1) : std::min(T - t, L + 1);
+            for (int64_t k = 0; k < k_end; ++k) {
+                if (condition == SHELL_ENDPOINTS && !inside(t + k)) continue;
+                ++a_n[k];
+                for (int d = 0; d < D; ++d)
+                    a_s[k * D + d] = shell_msd_add(a_s[k * D + d], (double)xq[(size_t)t * A * D + d], (double)xq[(size_t)(t + k) * A * D + d]);
+            }
+        }
+    });
+    if (rc) return rc;
+    for (size_t i = 0; sums && i < n1; ++i) {
+        double v = 0.0;
+        for (int th = 0; th < nth; ++th) v += acc[(size_t)th * n1 + i];
+        sums[i] = v;
+    }
+    for (size_t i = 0; count && i < n2; ++i) {
+        int64_t v = 0;
+        for (int th = 0; th < nth; ++th) v += cnt[(size_t)th * n2 + i];
+        count[i] = v;
+    }
+    return TA_OK;
 }
 
 int pair_find(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, bool same, int64_t stride,
@@ -1230,6 +1295,10 @@ int bond_lifetime(const State& s, bool fft, int64_t P, int n_at, const int32_t* 
 int shell_residence(const State& s, bool fft, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
                     bool per_frame, const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb) {
     TA_PAIR_DISPATCH(shell_residence_t, s, fft, n_a, ida, n_b, idb, hm, per_frame, cuts, gap, ci, runs, nb);
+}
+int shell_msd(const State& s, int condition, int64_t max_lag, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb,
+              const double* hm, bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs, double* nb) {
+    TA_PAIR_DISPATCH(shell_msd_t, s, condition, max_lag, n_a, ida, n_b, idb, hm, per_frame, cuts, gap, sums, count, runs, nb);
 }
 #undef TA_PAIR_DISPATCH
 

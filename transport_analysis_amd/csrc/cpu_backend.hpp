@@ -112,6 +112,11 @@ int bond_lifetime(const State& s, bool fft, int64_t P, int n_at, const int32_t* 
 // sqrt(rc2)" / "... sqrt(rb2)", then bond_lifetime's filters, as k_shell_series and k_pair_filter.  OpenMP over observed items.
 int shell_residence(const State& s, bool fft, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
                     bool per_frame, const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb);
+// ta_shell_msd: shell_residence's series g, its runs and nb, and sums (max_lag + 1, D), count (max_lag + 1): the squared
+// displacements of the observed items over the lags 0 ... max_lag, gated by g under `condition` (shell_msd_math.hpp, as
+// k_shell_msd: the same term and gates); any output may be NULL.  OpenMP over observed items.
+int shell_msd(const State& s, int condition, int64_t max_lag, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb,
+              const double* hm, bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs, double* nb);
 // ta_compound: out (n_frames, n_compounds, dim) float64 = sum_{i in [offsets[c], offsets[c + 1])} w_i x[t, members[i], d] -
 // g_c F[t, d] of slab 0 (g_c = sum_i w_i, F = sum_a u_a x[t, a, d]; frame_weights NULL: no such term; weights NULL: all 1),
 // the sum in member order (the first product, then fma), parallel over compounds; arguments checked by the caller

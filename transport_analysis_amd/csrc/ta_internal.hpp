@@ -505,6 +505,23 @@ hipError_t launch_shell_series(const double* ga, const double* gb, const int* id
                                long n_b, int D, long T, long pitch, long f_base, long n_f, const double* hm, bool box_per_frame,
                                double rc2, double rb2, double two, double* Z, hipStream_t st);
 
+// shell_msd.hip: the shell-resolved MSD of one block of observed items behind k_pair_filter (shell_msd_math.hpp: the conditions,
+// the cap kShellMsdMaxLag).  launch_shell_bits: the block Z (ceil(n_items / 2) destination pairs of `pitch` rows, 0/1) -> words,
+// n_items rows of ceil(T / 64) packed words.  launch_shell_msd: the items ids[0 ... n_items) (atoms of the slab x, read through
+// PmAtom in its own element type and left as it is) over the lags 0 ... max_lag < T under `condition`, origins in chunks of
+// `chunk` frames (shell_msd_chunk of the option: a multiple of 64, 64 ... 1024), G workgroups per pass of 256 lags
+// (shell_msd_groups of the device, the FULL block's count or fewer); part: shell_msd_part_bytes of the largest G.
+// launch_shell_fold: part's G rows added in row order into (first) or onto sums (max_lag + 1, D) and count (max_lag + 1),
+// either may be NULL.
+int shell_msd_chunk(long option);
+int shell_msd_groups(int n_cu, long n_items, long max_lag);
+size_t shell_msd_part_bytes(int G, long max_lag, int D);
+hipError_t launch_shell_bits(int n_cu, const double* Z, long pitch, long T, long n_items, unsigned long long* words, hipStream_t st);
+hipError_t launch_shell_msd(const void* x, bool f32, long pitch, long T, long n_atoms, int D, const int* ids, long n_items,
+                            const unsigned long long* words, int condition, long max_lag, int chunk, int G, void* part,
+                            hipStream_t st);
+hipError_t launch_shell_fold(const void* part, int G, long max_lag, int D, bool first, double* sums, long long* count, hipStream_t st);
+
 // unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
 // box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)
 hipError_t launch_unwrap(double* slab, long pitch, long T, long n_atoms, int D, const int* axes, bool triclinic,

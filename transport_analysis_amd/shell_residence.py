@@ -72,7 +72,7 @@ class ShellResidence(PairLifetime):
                  **kwargs):
         for key in ("pairs", "search_stride"):
             if key in kwargs:
-                raise TypeError(f"ShellResidence does not take {key}=: every observed atom is followed against the whole reference "
+                raise TypeError(f"{type(self).__name__} does not take {key}=: every observed atom is followed against the whole reference "
                                 "group, there is no list of pairs")
         self._refuse(kwargs, reference, observed)
         if observed is not None:
