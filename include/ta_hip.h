@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_pair_find / ta_pair_find_read / ta_pair_lifetime / ta_bond_lifetime / ta_shell_residence / ta_shell_msd / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_pair_find / ta_pair_find_read / ta_pair_lifetime / ta_bond_lifetime / ta_shell_residence / ta_shell_msd / ta_shell_orient / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -723,6 +723,51 @@ int ta_shell_msd(ta_ctx *ctx, int condition, int64_t max_lag, int64_t n_a, const
                  double r_cut, double r_break, int gap, double *h_sums /* (max_lag + 1, dim) */,
                  int64_t *h_count /* (max_lag + 1) */, int64_t *h_runs /* (T + 1) */, double *h_nb /* (T) */);
 
+/* ta_shell_orient : the reorientation of molecule-fixed unit vectors WHILE their molecule is in the shell of the group
+ *              (ShellOrientation; MDAnalysis' waterdynamics WaterOrientationalRelaxation).  A vector n is row n of h_index, an
+ *              int32 array (n_b, 2) for TA_ORIENT_BOND, (n_b, 3) for TA_ORIENT_BISECTOR / TA_ORIENT_NORMAL, atoms of slab 0 as
+ *              ta_orient's; u_n(t) is formed by ta_orient's operation sequence (csrc/orient_math.hpp: orient_diff,
+ *              orient_combine, orient_unit), a degenerate vector giving u = 0, never a NaN.  Column `anchor` of the row
+ *              (0 <= anchor < row length) is the vector's ANCHOR atom: the anchors are the observed items of the shell,
+ *              h_idx_b[n] must equal h_index[n][anchor]; with h_idx_b NULL the anchors must be the reference list itself ("in
+ *              the shell of another member": water around water).  The anchors are therefore pairwise distinct and strictly
+ *              increasing, as ta_shell_residence demands of its lists.  Two vectors on one anchor (OH1 and OH2 of a water)
+ *              are two calls: their sums and counts add.  With g_n(t) ta_shell_residence's series of the anchor (same
+ *              arguments, same bits: r_cut, r_break, gap, h_dimensions) and w_n(t, tau) ta_shell_msd's gate under
+ *              `condition`, for the lags tau = 0 ... max_lag, with c = u_n(t) . u_n(t + tau),
+ *                h_sums[tau][0] = sum_n sum_{t < T - tau} w_n(t, tau) c         float64 (max_lag + 1, 2)
+ *                h_sums[tau][1] = sum_n sum_{t < T - tau} w_n(t, tau) c c
+ *                h_count[tau]   = sum_n sum_{t < T - tau} w_n(t, tau)           exact int64 (max_lag + 1)
+ *              h_runs, h_nb: ta_shell_residence's.  Arithmetic (csrc/shell_orient_math.hpp, shared with the CPU backend):
+ *              c = fma(a_2, b_2, fma(a_1, b_1, fl(a_0 b_0))); per term s1 += c and s2 = fma(c, c, s2).  NOTHING is divided:
+ *              ShellOrientation forms C_1 = S1 / N and C_2 = (3 S2 / N - 1) / 2.  A degenerate vector adds zeros to the sums
+ *              and IS counted in N, because the gate is the shell alone; S1[0] is the number of non-degenerate terms at lag
+ *              0, which shows it.
+ *              The box.  h_dimensions serves both the distance pass (its rint image, orthorhombic boxes only) and the vectors'
+ *              image step (ta_orient's, with the same H and M; only the orthorhombic entries can be non-zero here); NULL:
+ *              neither.  It requires axes = {0, 1, 2}; three staged columns are required in any case.
+ *              Passes.  ta_shell_msd's with ONE kernel exchanged: k_shell_orient stands in k_shell_msd's place and is the
+ *              second instantiation of the same gated walk (csrc/shell_gate.hpp).  It forms u where the MSD reads a row:
+ *              the vector's atoms of a frame through the same slab reader (a float32 slab as float32, widened in registers),
+ *              the image step with that frame's box, u kept in LDS as float64, for the frames INSIDE only (under either
+ *              gate a term's lagged frame is itself inside; ta_shell_msd's kernel now skips the others too, without a
+ *              changed bit).  No block of u is written (ta_orient's route
+ *              would need 3 n_b pitch 16 bytes); a chunk of origins without a frame inside costs its words alone.
+ *              k_shell_fold adds the partial rows with two sums per lag.  Options "pair_chunk" and "shell_msd_chunk" as for
+ *              ta_shell_msd; a block's index rows are the rows of its observed items.  No atomics: repeat runs give the
+ *              same bits.  The CPU backend follows the same arithmetic: on inputs whose sums are exact the outputs are
+ *              EQUAL, otherwise within the library's 1e-10 scale-relative bound.
+ *              Errors, all checked before anything is written.  ta_shell_msd's (the cap 2047 on max_lag included), and
+ *              TA_E_INVALID: a mode other than the three; anchor outside 0 ... row length - 1; NULL h_index; dim != 3; a box
+ *              with axes other than {0, 1, 2}; n_atoms * 3 or n_b * 6 at or above 2^31; an index out of range; an atom twice
+ *              in a row; a row whose anchor is not the observed item of the same number.  There is no ta_group_* form.
+ *              ta_kernel_timeline names the kernel k_shell_orient.                                                      */
+int ta_shell_orient(ta_ctx *ctx, int condition, int64_t max_lag, int mode, int anchor, const int32_t *h_index /* (n_b, 2 | 3) */,
+                    int64_t n_a, const int64_t *h_idx_a /* reference; NULL: all */, int64_t n_b,
+                    const int64_t *h_idx_b /* the anchors; NULL: b = a */, const double *h_dimensions, const int *axes, double r_cut,
+                    double r_break, int gap, double *h_sums /* (max_lag + 1, 2) */, int64_t *h_count /* (max_lag + 1) */,
+                    int64_t *h_runs /* (T + 1) */, double *h_nb /* (T) */);
+
 /* ta_orient  : the rotational correlation functions of molecule-fixed unit vectors of the positions in slab 0
  *              (OrientationalCorrelation), three staged columns per atom.  A vector n is row n of h_index, atoms of slab 0,
  *              pairwise distinct and in [0, n_atoms):
@@ -982,6 +1027,13 @@ int ta_shell_residence_staged(ta_ctx *ctx, int fft, int64_t n_a, const int64_t *
 int ta_shell_msd_staged(ta_ctx *ctx, int condition, int64_t max_lag, int64_t n_a, const int64_t *h_idx_a, int64_t n_b,
                         const int64_t *h_idx_b, const double *h_dimensions, const int *axes, double r_cut, double r_break, int gap,
                         double *d_sums, int64_t *d_count, int64_t *d_runs, double *d_nb, void *stream);
+
+/* the index rows, the index lists and the box: HOST arrays, as for ta_shell_orient (checked before anything is written); the
+ * outputs on the device: d_sums (max_lag + 1, 2) float64, d_count (max_lag + 1) int64, d_runs (T + 1) int64, d_nb (T) float64 */
+int ta_shell_orient_staged(ta_ctx *ctx, int condition, int64_t max_lag, int mode, int anchor, const int32_t *h_index, int64_t n_a,
+                           const int64_t *h_idx_a, int64_t n_b, const int64_t *h_idx_b, const double *h_dimensions, const int *axes,
+                           double r_cut, double r_break, int gap, double *d_sums, int64_t *d_count, int64_t *d_runs, double *d_nb,
+                           void *stream);
 
 /* ---- several GPUs behind one call (one process, one frame loop) ---------------------------
  * the multi-GPU fan-out and the reduce happen INSIDE the call.  A group owns

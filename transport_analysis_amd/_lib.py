@@ -103,6 +103,9 @@ _API = {
     # (handle, condition, max_lag, n_a, idx_a, n_b, idx_b, h_dimensions, axes, r_cut, r_break, gap, sums, count, runs, nb[, stream])
     "ta_shell_msd": _int(_vp, _ci, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp),
     "ta_shell_msd_staged": _int(_vp, _ci, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp, _vp),
+    "ta_shell_orient": _int(_vp, _ci, _i64, _ci, _ci, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp),
+    "ta_shell_orient_staged": _int(_vp, _ci, _i64, _ci, _ci, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp,
+                                   _vp),
     "ta_vanhove_distinct_staged": _int(_vp, _ci, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _dbl, _vp, _vp),
     "ta_compound": _int(_vp, _i64, _vp, _vp, _vp, _vp, _P(_vp)),
     "ta_vacf_fft_dev": _DEV, "ta_vacf_direct_dev": _DEV,
@@ -1089,6 +1092,42 @@ class Context(_Staged):
         dim), d_count (max_lag + 1,) int64, d_runs (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
         args, keep = self._shell_msd_args(condition, max_lag, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
         self._call("shell_msd_staged", *args, d_sums or None, d_count or None, d_runs or None, d_nb or None, stream or None)
+        del keep
+
+    def _shell_orient_args(self, condition, max_lag, index, mode, anchor, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes):
+        """the argument tuple ta_shell_orient* share, and the arrays it points into (to be kept until the call is over)"""
+        (_, code, n_rows, p_idx, _, _), keep_o = self._orient_args(0, index, mode, None, None)
+        args, keep = self._shell_msd_args(condition, max_lag, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
+        n_a, n_b = args[2], args[4]  # (the library reads one index row per observed item)
+        n_obs = n_b if idx_b is not None else n_a if idx_a is not None else self._staged_shape()[1]
+        if n_rows != n_obs:
+            raise ValueError(f"index: {n_rows} rows for {n_obs} observed items")
+        return args[:2] + (code, int(anchor), p_idx) + args[2:], (keep, keep_o)
+
+    def shell_orient(self, condition, max_lag, index, mode, r_cut, *, anchor=0, r_break=None, gap=0, idx_a=None, idx_b=None,
+                     dimensions=None, axes=None, sums=True, count=True, runs=True, nb=True):
+        """(sums (max_lag + 1, 2), count (max_lag + 1,) int64, runs, nb) of slab 0, ta_shell_orient: (sum c, sum c c) of
+        c = u(t) . u(t + lag) over the unit vectors of `index` (rows as orient's for `mode`), each gated as shell_msd's terms
+        by the shell series of its anchor atom, column `anchor` of its row; `idx_b` must list the anchors row by row (None:
+        the anchors are the reference list `idx_a` itself).  `dimensions` serves the distance pass and the vectors' image
+        step.  One context only: a device group has no such call."""
+        T = self._staged_shape()[0]
+        args, keep = self._shell_orient_args(condition, max_lag, index, mode, anchor, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
+        L = max(int(max_lag), 0)
+        o_sums = np.empty((L + 1, 2), dtype=np.float64) if sums else None
+        o_count = np.empty(L + 1, dtype=np.int64) if count else None
+        o_runs = np.empty(T + 1, dtype=np.int64) if runs else None
+        o_nb = np.empty(T, dtype=np.float64) if nb else None
+        self._call("shell_orient", *args, _ptr(o_sums), _ptr(o_count), _ptr(o_runs), _ptr(o_nb))
+        del keep
+        return o_sums, o_count, o_runs, o_nb
+
+    def shell_orient_staged(self, condition, max_lag, index, mode, r_cut, *, anchor=0, r_break=None, gap=0, idx_a=None, idx_b=None,
+                            dimensions=None, axes=None, d_sums=0, d_count=0, d_runs=0, d_nb=0, stream=0):
+        """`index`, the lists and `dimensions`: HOST arrays (checked by the library before anything is written); d_sums
+        (max_lag + 1, 2), d_count (max_lag + 1,) int64, d_runs (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
+        args, keep = self._shell_orient_args(condition, max_lag, index, mode, anchor, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
+        self._call("shell_orient_staged", *args, d_sums or None, d_count or None, d_runs or None, d_nb or None, stream or None)
         del keep
 
     def _orient_args(self, fft, index, mode, dimensions, weights):

@@ -2287,22 +2287,38 @@ int64_t shell_block(const ta_ctx* ctx, int64_t n_b, int64_t pitch) {
 // msd (ta_shell_msd*, otherwise NULL): behind a block's filter k_shell_bits packs its series, k_shell_msd (shell_msd.hip) adds
 // up the gated squared displacements of the block's items over the lags 0 ... L and k_shell_fold adds the workgroups' partial
 // rows in row order onto sums and count: the blocks in block order.
+// orient (ta_shell_orient*, otherwise NULL): k_shell_orient (shell_orient.hip) stands in k_shell_msd's place, the walk over the
+// unit vectors of the block's index rows (one per observed item, its anchor; the table carries them behind the zero labels)
+// with the distance pass's boxes for the image step; two sums per lag in place of D.
+struct ShellOrient {
+    int mode, anchor;
+    const int32_t* h_index;
+};
 struct ShellMsd {
     int condition;
     int64_t L;
     double* d_sums;
     int64_t* d_count;
+    const ShellOrient* orient = nullptr;
+    int n_sums(int D) const { return orient ? 2 : D; }
 };
-int shell_msd_block(ta_ctx* ctx, const ShellMsd& m, const Slab& slab, const LifeSums& s, int64_t b, int64_t nb, const int* ids) {
+// ids: the block's observed items; rows, hm, per_frame (orient): the block's index rows and the boxes on the device
+int shell_msd_block(ta_ctx* ctx, const ShellMsd& m, const Slab& slab, const LifeSums& s, int64_t b, int64_t nb, const int* ids,
+                    const int* rows, const double* hm, bool per_frame) {
     hipStream_t st = slab.st;
-    const int G = ta::shell_msd_groups(ctx->n_cu, (long)nb, (long)m.L);
+    const int G = ta::shell_msd_groups(ctx->n_cu, (long)nb, (long)m.L), chunk = ta::shell_msd_chunk((long)ctx->opt_shell_msd_chunk);
     unsigned long long* words = (unsigned long long*)ctx->shell_words.p;
     TA_LAUNCH(ctx, "k_shell_bits", st, ta::launch_shell_bits(ctx->n_cu, s.Z, (long)s.pitch, (long)s.T, (long)nb, words, st));
-    TA_LAUNCH(ctx, "k_shell_msd", st,
-              ta::launch_shell_msd(slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, slab.D, ids, (long)nb, words, m.condition,
-                                   (long)m.L, ta::shell_msd_chunk((long)ctx->opt_shell_msd_chunk), G, ctx->shell_part.p, st));
+    if (m.orient)
+        TA_LAUNCH(ctx, "k_shell_orient", st,
+                  ta::launch_shell_orient(slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, slab.D, m.orient->mode, rows, (long)nb,
+                                          hm, per_frame, words, m.condition, (long)m.L, chunk, G, ctx->shell_part.p, st));
+    else
+        TA_LAUNCH(ctx, "k_shell_msd", st,
+                  ta::launch_shell_msd(slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, slab.D, ids, (long)nb, words, m.condition,
+                                       (long)m.L, chunk, G, ctx->shell_part.p, st));
     TA_LAUNCH(ctx, "k_shell_fold", st,
-              ta::launch_shell_fold(ctx->shell_part.p, G, (long)m.L, slab.D, b == 0, m.d_sums, (long long*)m.d_count, st));
+              ta::launch_shell_fold(ctx->shell_part.p, G, (long)m.L, m.n_sums(slab.D), b == 0, m.d_sums, (long long*)m.d_count, st));
     return TA_OK;
 }
 int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, double* d_ci, int64_t* d_runs, double* d_nb,
@@ -2313,6 +2329,7 @@ int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, double
     const int64_t* lag0 = (const int64_t*)ctx->shell_tab.dev.p;
     const auto [hm, ida, idb] = pair_tail((const double*)(lag0 + 1), p.box, p);
     const int* lab = idb + p.pitch_b;
+    const int* rows = lab + 2 * ((Qc + 1) / 2);  // (ta_shell_orient*: the index rows behind the Qc zero labels)
     const int64_t pitch_q = (Qc + VHD_TILE_B - 1) / VHD_TILE_B * VHD_TILE_B, words = (T + 63) / 64;
     const size_t per = sizeof(double) * (size_t)D * (size_t)(p.pitch_a + pitch_q);  // a gathered frame
     const int64_t fit = std::max<int64_t>(1, (int64_t)(kVhdBudget / (64 * per)));
@@ -2321,7 +2338,8 @@ int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, double
     double* ga = (double*)ctx->vhd_scr.p;
     if (msd && (msd->d_sums || msd->d_count)) {
         TA_CHECK(ensure(ctx, ctx->shell_words, sizeof(uint64_t) * (size_t)Qc * (size_t)words));
-        TA_CHECK(ensure(ctx, ctx->shell_part, ta::shell_msd_part_bytes(ta::shell_msd_groups(ctx->n_cu, (long)Qc, (long)msd->L), (long)msd->L, D)));
+        TA_CHECK(ensure(ctx, ctx->shell_part,
+                        ta::shell_msd_part_bytes(ta::shell_msd_groups(ctx->n_cu, (long)Qc, (long)msd->L), (long)msd->L, msd->n_sums(D))));
     } else {
         msd = nullptr;
     }
@@ -2341,7 +2359,7 @@ int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, double
                                                p.filter() ? 2.0 : 1.0, s.Z, st));
         }
         TA_CHECK(life_sums_block(ctx, s, b, nb, p.filter(), p.gap, lab));
-        if (msd) TA_CHECK(shell_msd_block(ctx, *msd, slab, s, b, nb, idb + q0));
+        if (msd) TA_CHECK(shell_msd_block(ctx, *msd, slab, s, b, nb, idb + q0, rows + (msd->orient ? orient_row_len(msd->orient->mode) * q0 : 0), hm, p.box.per_frame));
     }
     return life_sums_end(ctx, s);
 }
@@ -2354,13 +2372,16 @@ int shell_launch(ta_ctx* ctx, int fft, const ShellPlan& p, double* d_ci, int64_t
         ctx, nullptr, stream, no_args,
         [&](const Slab& s) -> int {
             const int64_t Qc = shell_block(ctx, p.n_b, s.pitch);
-            const size_t n = 1 + pair_tail_size(p.box, p) + ((size_t)Qc + 1) / 2;
+            const ShellOrient* orient = msd ? msd->orient : nullptr;
+            const size_t n_lab = 1 + pair_tail_size(p.box, p) + ((size_t)Qc + 1) / 2;
+            const size_t n_rows = orient ? (size_t)p.n_b * orient_row_len(orient->mode) : 0, n = n_lab + (n_rows + 1) / 2;
             double* h = nullptr;
             TA_CHECK(ctx->shell_tab.begin(ctx, sizeof(double) * n, (void**)&h));
             memset(h, 0, sizeof(double) * n);  // (the zero lag in front, the zero labels behind)
             pair_tail_pack(h + 1, p.box, p);
+            if (orient) memcpy(h + n_lab, orient->h_index, sizeof(int32_t) * n_rows);
             if (out) {
-                const size_t n_msd = msd ? (size_t)(msd->L + 1) * (size_t)(p.D + 1) : (size_t)s.T;
+                const size_t n_msd = msd ? (size_t)(msd->L + 1) * (size_t)(msd->n_sums(p.D) + 1) : (size_t)s.T;
                 TA_CHECK(ensure(ctx, ctx->pair_out, sizeof(double) * (n_msd + 2 * (size_t)s.T + 1)));
                 *out = (double*)ctx->pair_out.p;
             }
@@ -2369,8 +2390,8 @@ int shell_launch(ta_ctx* ctx, int fft, const ShellPlan& p, double* d_ci, int64_t
         [&](const Slab& s) {
             if (msd && out) {
                 double* o = *out;
-                const size_t n1 = (size_t)(msd->L + 1) * (size_t)p.D, n2 = (size_t)msd->L + 1;
-                const ShellMsd m{msd->condition, msd->L, msd->d_sums ? o : nullptr, msd->d_count ? (int64_t*)(o + n1) : nullptr};
+                const size_t n1 = (size_t)(msd->L + 1) * (size_t)msd->n_sums(p.D), n2 = (size_t)msd->L + 1;
+                const ShellMsd m{msd->condition, msd->L, msd->d_sums ? o : nullptr, msd->d_count ? (int64_t*)(o + n1) : nullptr, msd->orient};
                 return shell_pm(ctx, false, s, p, nullptr, d_runs ? (int64_t*)(o + n1 + n2) : nullptr, d_nb ? o + n1 + n2 + s.T + 1 : nullptr, &m);
             }
             if (!out) return shell_pm(ctx, fft != 0, s, p, d_ci, d_runs, d_nb, msd);
@@ -2380,15 +2401,45 @@ int shell_launch(ta_ctx* ctx, int fft, const ShellPlan& p, double* d_ci, int64_t
 }
 
 // the argument checks of ta_shell_msd*: shell_plan's, and the condition and max_lag against the staged frames and the cap
-int shell_msd_plan(ta_ctx* ctx, int condition, int64_t max_lag, const ShellArgs& a, bool any_out, ShellPlan* p) {
-    const std::string who = "shell_msd: ";
+int shell_msd_plan(ta_ctx* ctx, int condition, int64_t max_lag, const ShellArgs& a, bool any_out, ShellPlan* p, const char* name = "shell_msd") {
+    const std::string who = std::string(name) + ": ";
     if (condition != ta::SHELL_CONTINUOUS && condition != ta::SHELL_ENDPOINTS)
         return fail(ctx, TA_E_INVALID, who + "condition must be 0 (continuous) or 1 (endpoints)");
-    TA_CHECK(shell_plan(ctx, 0, a, any_out, p, "shell_msd", "sums, count, runs and nb"));
+    TA_CHECK(shell_plan(ctx, 0, a, any_out, p, name, "sums, count, runs and nb"));
     if (max_lag < 0 || max_lag > p->T - 1)
         return fail(ctx, TA_E_INVALID, who + "max_lag must be 0 ... n_frames - 1 = " + std::to_string(p->T - 1));
     if (max_lag > ta::kShellMsdMaxLag)
         return fail(ctx, TA_E_INVALID, who + "max_lag must be at most " + std::to_string(ta::kShellMsdMaxLag) + " (eight passes of 256 lags)");
+    return TA_OK;
+}
+
+// the argument checks of ta_shell_orient*: the mode and the anchor column, shell_msd_plan's, three staged columns and the
+// box on x, y, z, ta_orient's checks of the index rows, and every row's anchor against the observed items
+int shell_orient_plan(ta_ctx* ctx, int condition, int64_t max_lag, const ShellOrient& o, const ShellArgs& a, bool any_out, ShellPlan* p) {
+    const std::string who = "shell_orient: ";
+    if (o.mode < ORIENT_BOND || o.mode > ORIENT_NORMAL)
+        return fail(ctx, TA_E_INVALID, who + "mode must be TA_ORIENT_BOND (0), TA_ORIENT_BISECTOR (1) or TA_ORIENT_NORMAL (2)");
+    const int K = orient_row_len(o.mode);
+    if (o.anchor < 0 || o.anchor >= K) return fail(ctx, TA_E_INVALID, who + "anchor must be a column of the index rows, 0 ... " + std::to_string(K - 1));
+    if (!o.h_index) return fail(ctx, TA_E_INVALID, who + "the index table is NULL");
+    TA_CHECK(shell_msd_plan(ctx, condition, max_lag, a, any_out, p, "shell_orient"));
+    if (p->D != 3) return fail(ctx, TA_E_INVALID, who + "the position slab must hold three columns per atom (dim = " + std::to_string(p->D) + ")");
+    if (a.h_dims && !(a.axes[0] == 0 && a.axes[1] == 1 && a.axes[2] == 2))
+        return fail(ctx, TA_E_INVALID, who + "the box needs the three columns x, y, z (axes {0, 1, 2})");
+    if (p->A * 3 >= (int64_t)1 << 31 || p->n_b * 6 >= (int64_t)1 << 31)
+        return fail(ctx, TA_E_INVALID, who + "n_atoms * 3 and n_vectors * 6 must be below 2^31");
+    for (int64_t n = 0; n < p->n_b; ++n) {
+        const int32_t* r = o.h_index + n * K;
+        for (int j = 0; j < K; ++j)
+            if (r[j] < 0 || r[j] >= p->A)
+                return fail(ctx, TA_E_INVALID, who + "index " + std::to_string(r[j]) + " of vector " + std::to_string(n) +
+                                                   " is outside 0 ... n_atoms - 1");
+        if (r[0] == r[1] || (K == 3 && (r[0] == r[2] || r[1] == r[2])))
+            return fail(ctx, TA_E_INVALID, who + "vector " + std::to_string(n) + " names an atom twice");
+        if (r[o.anchor] != p->idb[(size_t)n])
+            return fail(ctx, TA_E_INVALID, who + "the anchor of vector " + std::to_string(n) + " (atom " + std::to_string(r[o.anchor]) +
+                                               ") is not observed item " + std::to_string(n) + " (atom " + std::to_string(p->idb[(size_t)n]) + ")");
+    }
     return TA_OK;
 }
 
@@ -3358,6 +3409,24 @@ int ta_shell_msd_staged(ta_ctx* ctx, int condition, int64_t max_lag, int64_t n_a
     });
 }
 
+// The shell-resolved reorientation on the staged slab 0; the index rows, the index lists and the box are HOST arrays, the
+// outputs on the device
+int ta_shell_orient_staged(ta_ctx* ctx, int condition, int64_t max_lag, int mode, int anchor, const int32_t* h_index, int64_t n_a,
+                           const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes,
+                           double r_cut, double r_break, int gap, double* d_sums, int64_t* d_count, int64_t* d_runs, double* d_nb,
+                           void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
+    const ShellOrient o{mode, anchor, h_index};
+    ShellPlan plan;
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(shell_orient_plan(ctx, condition, max_lag, o, a, d_sums || d_count || d_runs || d_nb, &plan));
+    const ShellMsd m{condition, max_lag, d_sums, d_count, &o};
+    return shell_launch(ctx, 0, plan, nullptr, d_runs, d_nb, stream, nullptr, &m);
+    });
+}
+
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
     return ta::guarded(fail, ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
@@ -4269,6 +4338,27 @@ int ta_shell_residence(ta_ctx* ctx, int fft, int64_t n_a, const int64_t* h_idx_a
     TA_CHECK(shell_launch(ctx, fft, p, h_ci, h_runs, h_nb, ctx->stream, &d_out));
     const size_t T = (size_t)ctx->st_T;  // (int64 counts travel as 8-byte elements)
     return host_finish(ctx, {{h_ci, d_out, T}, {(double*)h_runs, d_out + T, T + 1}, {h_nb, d_out + 2 * T + 1, T}});
+    });
+}
+
+int ta_shell_orient(ta_ctx* ctx, int condition, int64_t max_lag, int mode, int anchor, const int32_t* h_index, int64_t n_a,
+                    const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes, double r_cut,
+                    double r_break, int gap, double* h_sums, int64_t* h_count, int64_t* h_runs, double* h_nb) {
+    return host_call(ctx, [&]() -> int {
+    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
+    const ShellOrient o{mode, anchor, h_index};
+    ShellPlan p;
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(shell_orient_plan(ctx, condition, max_lag, o, a, h_sums || h_count || h_runs || h_nb, &p));
+    if (ctx->is_cpu)
+        return cpu_rc(ctx, ta::cpu::shell_orient(cpu_state(ctx), condition, max_lag, mode, h_index, p.n_a, p.ida.data(), p.n_b, p.idb.data(),
+                                                 p.box.data(), p.box.per_frame, p.cuts, p.gap, h_sums, h_count, h_runs, h_nb));
+    double* d_out = nullptr;
+    const ShellMsd m{condition, max_lag, h_sums, h_count, &o};  // (which outputs are asked for: shell_launch points them into d_out)
+    TA_CHECK(shell_launch(ctx, 0, p, nullptr, h_runs, h_nb, ctx->stream, &d_out, &m));
+    const size_t T = (size_t)ctx->st_T, n1 = (size_t)(max_lag + 1) * 2, n2 = (size_t)max_lag + 1;  // (int64 as 8-byte elements)
+    return host_finish(ctx, {{h_sums, d_out, n1}, {(double*)h_count, d_out + n1, n2}, {(double*)h_runs, d_out + n1 + n2, T + 1},
+                             {h_nb, d_out + n1 + n2 + T + 1, T}});
     });
 }
 

@@ -44,6 +44,7 @@
 #include "bond_math.hpp"
 #include "pair_math.hpp"
 #include "shell_msd_math.hpp"
+#include "shell_orient_math.hpp"
 #include "unwrap_box.hpp"
 #include "vanhove_distinct_math.hpp"
 #include "vanhove_math.hpp"
@@ -1223,17 +1224,18 @@ int shell_residence_t(const State& s, bool fft, int64_t n_a, const int32_t* ida,
     });
 }
 
-// ta_shell_msd: shell_residence_t's series g of every observed item (runs, nb by lifetime_sums), and behind each item's fill its
-// gated squared displacements over the lags 0 ... L (shell_msd_math.hpp: the same term, fma(d, d, acc), and the same gates as
-// k_shell_msd): a plain loop over the origins inside, left(s) from one walk down the frames.  A thread adds into sums and
-// counts of its own; the threads' sums are added in thread order (exact inputs: any order gives the same bits).
-template <class E, int D, bool PERIODIC>
-int shell_msd_t(const State& s, int condition, int64_t L, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
-                bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs, double* nb) {
+// The gated lag sums behind shell_residence_t's series g of every observed item (runs, nb by lifetime_sums), for ta_shell_msd
+// and ta_shell_orient: behind each item's fill its NS sums over the lags 0 ... L with shell_msd_math.hpp's gates, as
+// shell_gate_walk: a plain loop over the origins inside, left(s) from one walk down the frames.  item(n, thread) prepares item
+// n and returns its term(acc, t, t + k), which adds one term onto the NS sums acc.  A thread adds into sums and counts of its
+// own; the threads' sums are added in thread order (exact inputs: any order gives the same bits).
+template <class E, int D, bool PERIODIC, int NS, class Item>
+int shell_gated_sums(const State& s, int condition, int64_t L, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
+                     bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs, double* nb, Item item) {
     const int64_t T = s.T, A = s.A, nw = (T + 63) / 64;
     const int nth = s.threads > 0 ? s.threads : 1;
     const E* x = static_cast<const E*>(s.slabs[0]);
-    const size_t n1 = (size_t)(L + 1) * D, n2 = (size_t)L + 1;
+    const size_t n1 = (size_t)(L + 1) * NS, n2 = (size_t)L + 1;
     std::vector<uint64_t> S;
     std::vector<double> acc;
     std::vector<int64_t> cnt, left;
@@ -1254,15 +1256,14 @@ int shell_msd_t(const State& s, int condition, int64_t L, int64_t n_a, const int
         auto inside = [&](int64_t t) { return (w[t >> 6] >> (t & 63)) & 1; };
         lf[T] = 0;
         for (int64_t t = T - 1; t >= 0; --t) lf[t] = inside(t) ? lf[t + 1] + 1 : 0;
-        const E* xq = x + (size_t)idb[n] * D;
+        auto term = item(n, th);
         for (int64_t t = 0; t < T; ++t) {
             if (!inside(t)) continue;
             const int64_t k_end = condition == SHELL_CONTINUOUS ? std::min(lf[t], L + 1) : std::min(T - t, L + 1);
             for (int64_t k = 0; k < k_end; ++k) {
                 if (condition == SHELL_ENDPOINTS && !inside(t + k)) continue;
                 ++a_n[k];
-                for (int d = 0; d < D; ++d)
-                    a_s[k * D + d] = shell_msd_add(a_s[k * D + d], (double)xq[(size_t)t * A * D + d], (double)xq[(size_t)(t + k) * A * D + d]);
+                term(a_s + k * NS, t, t + k);
             }
         }
     });
@@ -1278,6 +1279,56 @@ int shell_msd_t(const State& s, int condition, int64_t L, int64_t n_a, const int
         count[i] = v;
     }
     return TA_OK;
+}
+
+// ta_shell_msd: the term is shell_msd_add per axis, fma(d, d, acc), as k_shell_msd's
+template <class E, int D, bool PERIODIC>
+int shell_msd_t(const State& s, int condition, int64_t L, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
+                bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs, double* nb) {
+    const int64_t A = s.A;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    return shell_gated_sums<E, D, PERIODIC, D>(s, condition, L, n_a, ida, n_b, idb, hm, per_frame, cuts, gap, sums, count, runs, nb,
+                                               [&](int64_t n, int) {
+                                                   const E* xq = x + (size_t)idb[n] * D;
+                                                   return [=](double* acc, int64_t t, int64_t t2) {
+                                                       for (int d = 0; d < D; ++d)
+                                                           acc[d] = shell_msd_add(acc[d], (double)xq[(size_t)t * A * D + d], (double)xq[(size_t)t2 * A * D + d]);
+                                                   };
+                                               });
+}
+
+// ta_shell_orient: u of the item's vector in every frame by orient_math.hpp's sequence with the distance pass's box, kept per
+// thread; the term is shell_orient_math.hpp's, as k_shell_orient's
+template <class E, bool PERIODIC, int MODE>
+int shell_orient_t(const State& s, int condition, int64_t L, const int32_t* index, int64_t n_a, const int32_t* ida, int64_t n_b,
+                   const int32_t* idb, const double* hm, bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count,
+                   int64_t* runs, double* nb) {
+    const int64_t T = s.T, A = s.A;
+    constexpr int K = MODE == ORIENT_BOND ? 2 : 3;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    std::vector<double> U;
+    try {
+        if (sums || count) U.assign((size_t)(s.threads > 0 ? s.threads : 1) * (size_t)T * 3, 0.0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    return shell_gated_sums<E, 3, PERIODIC, 2>(s, condition, L, n_a, ida, n_b, idb, hm, per_frame, cuts, gap, sums, count, runs, nb,
+                                               [&](int64_t n, int th) {
+        double* u = U.data() + (size_t)th * (size_t)T * 3;
+        const int32_t* row = index + n * K;
+        for (int64_t t = 0; t < T; ++t) {
+            double at[3][3] = {};
+            for (int j = 0; j < K; ++j)
+                for (int d = 0; d < 3; ++d) at[j][d] = (double)x[((size_t)t * A + (size_t)row[j]) * 3 + d];
+            OrientBox bx{};
+            if (PERIODIC) bx = shell_orient_box(hm + (per_frame ? t * 6 : 0));
+            shell_orient_unit<MODE, PERIODIC>(at[0], at[1], at[2], bx, *reinterpret_cast<double(*)[3]>(u + 3 * t));
+        }
+        return [=](double* acc, int64_t t, int64_t t2) {
+            const double *a = u + 3 * t, *b = u + 3 * t2;
+            shell_orient_add(acc[0], acc[1], shell_orient_dot(a[0], a[1], a[2], b[0], b[1], b[2]));
+        };
+    });
 }
 
 int pair_find(const State& s, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, bool same, int64_t stride,
@@ -1301,6 +1352,23 @@ int shell_msd(const State& s, int condition, int64_t max_lag, int64_t n_a, const
     TA_PAIR_DISPATCH(shell_msd_t, s, condition, max_lag, n_a, ida, n_b, idb, hm, per_frame, cuts, gap, sums, count, runs, nb);
 }
 #undef TA_PAIR_DISPATCH
+int shell_orient(const State& s, int condition, int64_t max_lag, int mode, const int32_t* index, int64_t n_a, const int32_t* ida, int64_t n_b,
+                 const int32_t* idb, const double* hm, bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs,
+                 double* nb) {
+#define TA_SO_ARGS s, condition, max_lag, index, n_a, ida, n_b, idb, hm, per_frame, cuts, gap, sums, count, runs, nb
+#define TA_SO_MODE(E, P)                                                                 \
+    return mode == ORIENT_BOND       ? shell_orient_t<E, P, ORIENT_BOND>(TA_SO_ARGS)     \
+           : mode == ORIENT_BISECTOR ? shell_orient_t<E, P, ORIENT_BISECTOR>(TA_SO_ARGS) \
+                                     : shell_orient_t<E, P, ORIENT_NORMAL>(TA_SO_ARGS)
+    if (s.dtype == TA_F32) {
+        if (hm) TA_SO_MODE(float, true);
+        TA_SO_MODE(float, false);
+    }
+    if (hm) TA_SO_MODE(double, true);
+    TA_SO_MODE(double, false);
+#undef TA_SO_MODE
+#undef TA_SO_ARGS
+}
 
 template <class E>
 int compound_t(const State& s, int64_t C, const int64_t* off, const int32_t* members, const double* w, const double* u,

@@ -117,6 +117,12 @@ int shell_residence(const State& s, bool fft, int64_t n_a, const int32_t* ida, i
 // k_shell_msd: the same term and gates); any output may be NULL.  OpenMP over observed items.
 int shell_msd(const State& s, int condition, int64_t max_lag, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb,
               const double* hm, bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs, double* nb);
+// ta_shell_orient: shell_msd's gated sums with shell_orient_math.hpp's term in place of the squared displacement: sums
+// (max_lag + 1, 2) = (sum c, sum c c), c = u(t) . u(t + k), u the unit vector of index row n (orient_row_len(mode) atoms of slab 0,
+// dim 3; orient_math.hpp's sequence with hm as the image step's box), gated by the series of observed item n, the row's anchor
+int shell_orient(const State& s, int condition, int64_t max_lag, int mode, const int32_t* index, int64_t n_a, const int32_t* ida, int64_t n_b,
+                 const int32_t* idb, const double* hm, bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs,
+                 double* nb);
 // ta_compound: out (n_frames, n_compounds, dim) float64 = sum_{i in [offsets[c], offsets[c + 1])} w_i x[t, members[i], d] -
 // g_c F[t, d] of slab 0 (g_c = sum_i w_i, F = sum_a u_a x[t, a, d]; frame_weights NULL: no such term; weights NULL: all 1),
 // the sum in member order (the first product, then fma), parallel over compounds; arguments checked by the caller

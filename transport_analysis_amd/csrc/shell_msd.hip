@@ -5,22 +5,10 @@
 //   k_shell_bits                a wave per destination pair of Z at a time, as k_pair_runs: lane l reads frame 64 j + l, the
 //                               ballots are the two items' 64-frame words of g, stored packed (ceil(T / 64) words per item):
 //                               Z is read ONCE, everything behind works on 1 / 64 of its bytes.
-//   k_shell_msd<E, D, COND>     grid (G, passes).  Workgroup (x, y) owns the 256 lags [256 y, 256 y + 256), one per thread, and
-//                               the items x, x + G, ... of the block, one at a time, in chunks of C origin frames (C a
-//                               multiple of 64).  Per (item, chunk): the words of the chunk and of the lagged frames behind it
-//                               go to LDS; a chunk without a frame inside is left at once (a workgroup-uniform branch: with
-//                               sparse residence most of the work); the item's D columns of the frames [c0 + 256 y,
-//                               c0 + 256 y + C + 256) are read through PmAtom in the slab's own element type and kept in LDS
-//                               in that type; "continuous": wave 0 walks the words from the last down and leaves left(s), the
-//                               frames from s on to the first frame outside.  Then per 64-frame word of origins (skipped
-//                               where zero): lane i of every wave reads origin 64 j + i's columns from the slab, and per SET
-//                               bit i of the word (a scalar loop, its trip count the same for every lane) the origin comes
-//                               out of lane i by v_readlane, the lagged frame out of LDS (consecutive lanes, consecutive
-//                               addresses), widened, and fma(d, d, acc) runs under the gate: "continuous" lag < left(s), with
-//                               origins whose run ends below the pass's first lag skipped for the whole workgroup;
-//                               "endpoints" bit i of the thread's window of g at its lag, whose popcount against the
-//                               origins' word is that lag's count.  A thread's D sums and its count stay in registers over
-//                               all items of the workgroup and are stored once: the partial rows [G][256 passes].
+//   k_shell_msd<E, D, COND>     shell_gate_walk (shell_gate.hpp: the chunks, the words in LDS, the two gates, the partial rows)
+//                               with the item's D columns as its Source, read through PmAtom in the slab's own element type
+//                               and kept in LDS in that type, and fma(d, d, acc) per axis as its Term.  k_shell_orient
+//                               (shell_orient.hip) is the walk's other instantiation.
 //   k_shell_fold                the G partial rows added in row order (the counts as integers), into the outputs (the first
 //                               block of observed items) or onto them (the blocks behind it: block order).
 // No atomics, no float adds whose order depends on timing: repeat runs give the same bits.  Every loop's trip count depends on
@@ -31,12 +19,11 @@
 #include <type_traits>
 
 #include "pm_read.hpp"
+#include "shell_gate.hpp"
 #include "shell_msd_math.hpp"
 
 namespace ta {
 namespace {
-
-constexpr int kSmLags = kPmThreads;  // lags per pass: one per thread
 
 // Z: the 0/1 block (n_units destination pairs of `pitch` rows).  words: n_items rows of nw = ceil(T / 64) words.
 __global__ void __launch_bounds__(kPmThreads)
@@ -58,99 +45,42 @@ __global__ void __launch_bounds__(kPmThreads)
     }
 }
 
-__device__ __forceinline__ unsigned long long sm_uniform(unsigned long long v) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return ((unsigned long long)hi << 32) | lo;
-}
-// lane i's value (i wave-uniform), widened
-__device__ __forceinline__ double sm_from_lane(double v, int i) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), i), __builtin_amdgcn_readlane(__double2loint(v), i));
-}
-__device__ __forceinline__ double sm_from_lane(float v, int i) {
-    return (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i));
-}
+// The walk's Source of the MSD: the item's D columns, read through PmAtom::row and kept in the slab's own element type
+template <class E, int D>
+struct ShellMsdSource {
+    static constexpr int NV = D;
+    using Kept = E;
+    PmAtom<E, D> atom;
+    __device__ __forceinline__ void load(long t, double (&v)[D]) const {
+        double r[3];
+        atom.row(t, r);
+#pragma unroll
+        for (int d = 0; d < D; ++d) v[d] = r[d];
+    }
+};
+// ... and its Term: shell_msd_add per axis
+template <int D>
+struct ShellMsdTerm {
+    static constexpr int NS = D;
+    template <class A, class B>
+    static __device__ __forceinline__ void add(double (&acc)[D], bool gate, A&& origin, B&& lagged) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const double a = origin(d), b = lagged(d);
+            if (gate) acc[d] = shell_msd_add(acc[d], a, b);
+        }
+    }
+};
 
-// x: the staged slab; ids: the block's observed items (atoms of the slab); words: k_shell_bits' rows; C: origins per chunk;
-// part_s [G][256 passes][D], part_n [G][256 passes].  Dynamic LDS: (C + 256 y_max + 256) / 64 words | C ints | D (C + 256) E.
+// x: the staged slab; ids: the block's observed items (atoms of the slab); the rest as shell_gate_walk's (shell_gate.hpp)
 template <class E, int D, int COND>
 __global__ void __launch_bounds__(kPmThreads)
     k_shell_msd(const E* __restrict__ x, long pitch, long T, const int* __restrict__ ids, long n_items,
                 const unsigned long long* __restrict__ words, long nw, int C, double* __restrict__ part_s,
                 unsigned long long* __restrict__ part_n) {
-    extern __shared__ unsigned long long sm_lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const long k0 = (long)blockIdx.y * kSmLags, lag = k0 + tid;
-    const int n_ww = (int)((C + k0) / 64) + 4, n_ow = C / 64, n_x = C + kSmLags;
-    unsigned long long* wd = sm_lds;                                                      // n_ww words from frame c0 on
-    int* left = reinterpret_cast<int*>(sm_lds + ((C + (long)(gridDim.y - 1) * kSmLags) / 64 + 4));  // C
-    E* xs = reinterpret_cast<E*>(left + C);                                               // [D][n_x] from frame c0 + k0 on
-    double acc[D] = {};
-    unsigned long long cnt = 0;
-    for (long q = blockIdx.x; q < n_items; q += gridDim.x) {
-        const unsigned long long* wq = words + q * nw;
-        const PmAtom<E, D> atom(x, pitch, (unsigned)ids[q]);
-        for (long c0 = 0; c0 + k0 < T; c0 += C) {
-            __syncthreads();  // (the chunk before has been read)
-            if (tid < n_ww) wd[tid] = c0 / 64 + tid < nw ? wq[c0 / 64 + tid] : 0ull;
-            __syncthreads();
-            unsigned long long any = 0;
-            for (int j = 0; j < n_ow; ++j) any |= wd[j];
-            if (!sm_uniform(any)) continue;  // (the same words for every thread)
-            for (int i = tid; i < n_x; i += kPmThreads) {
-                const long t = c0 + k0 + i;
-                double v[3];
-                atom.row(t < T ? t : 0, v);
-#pragma unroll
-                for (int d = 0; d < D; ++d) xs[d * n_x + i] = (E)v[d];
-            }
-            if (COND == SHELL_CONTINUOUS && tid < 64) {
-                long long behind = c0 + 64L * n_ww;  // (frames behind the words: no lag of this pass reaches them)
-                for (int w = n_ww - 1; w >= 0; --w) {
-                    const unsigned long long m = wd[w];
-                    if (w < n_ow) left[64 * w + lane] = (int)shell_left(m, lane, c0 + 64L * w, behind);
-                    behind = shell_left_carry(m, c0 + 64L * w, behind);
-                }
-            }
-            __syncthreads();
-            for (int j = 0; j < n_ow; ++j) {
-                const unsigned long long m = sm_uniform(wd[j]);
-                if (!m) continue;
-                const long s = c0 + 64L * j + lane;
-                double o[3];
-                atom.row(s < T ? s : 0, o);
-                E xo[D];
-#pragma unroll
-                for (int d = 0; d < D; ++d) xo[d] = (E)o[d];
-                unsigned long long gates = 0;
-                if (COND == SHELL_ENDPOINTS) {
-                    const long rel = 64L * j + lag;
-                    gates = m & shell_window(wd[rel >> 6], wd[(rel >> 6) + 1], (int)(rel & 63));
-                    cnt += __popcll(gates);
-                }
-                for (unsigned long long mm = m; mm; mm &= mm - 1) {
-                    const int i = __builtin_ctzll(mm);
-                    bool gate;
-                    if (COND == SHELL_CONTINUOUS) {
-                        const int lf = __builtin_amdgcn_readfirstlane(left[64 * j + i]);
-                        if (lf <= k0) continue;  // (the run ends below this pass's lags)
-                        gate = lag < lf;
-                        cnt += gate;
-                    } else {
-                        gate = (gates >> i) & 1ull;
-                    }
-#pragma unroll
-                    for (int d = 0; d < D; ++d) {
-                        const double a = sm_from_lane(xo[d], i), b = (double)xs[d * n_x + 64 * j + i + tid];
-                        if (gate) acc[d] = shell_msd_add(acc[d], a, b);
-                    }
-                }
-            }
-        }
-    }
-    const size_t row = (size_t)blockIdx.x * ((size_t)gridDim.y * kSmLags) + (size_t)lag;
-#pragma unroll
-    for (int d = 0; d < D; ++d) part_s[row * D + d] = acc[d];
-    part_n[row] = cnt;
+    shell_gate_walk<COND, ShellMsdTerm<D>>(T, n_items, words, nw, C, part_s, part_n, [&](long q) {
+        return ShellMsdSource<E, D>{PmAtom<E, D>(x, pitch, (unsigned)ids[q])};
+    });
 }
 
 // sums (L + 1, D), count (L + 1): the G partial rows (Lp lags each) added in row order; first: stored, otherwise added on
@@ -168,10 +98,6 @@ __global__ void __launch_bounds__(kPmThreads)
         for (int g = 0; g < G; ++g) acc += part_n[(size_t)g * Lp + i];
         count[i] = (first ? 0 : count[i]) + (long long)acc;
     }
-}
-
-size_t sm_lds_bytes(int C, int n_pass, int D, bool f32) {
-    return 8 * (size_t)((C + (n_pass - 1) * kSmLags) / 64 + 4) + 4 * (size_t)C + (size_t)D * (C + kSmLags) * (f32 ? 4 : 8);
 }
 
 }  // namespace
@@ -204,7 +130,7 @@ hipError_t launch_shell_msd(const void* x, bool f32, long pitch, long T, long n_
         chunk < 64 || chunk > 1024 || chunk % 64 || G < 1 || G > n_items || (condition != SHELL_CONTINUOUS && condition != SHELL_ENDPOINTS) ||
         !x || !ids || !words || !part)
         return hipErrorInvalidValue;
-    const size_t lds = sm_lds_bytes(chunk, (int)n_pass, D, f32);
+    const size_t lds = shell_gate_lds_bytes(chunk, (int)n_pass, D, f32 ? 4 : 8);
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     double* part_s = (double*)part;
     unsigned long long* part_n = (unsigned long long*)(part_s + (size_t)G * (size_t)(n_pass * kSmLags) * D);

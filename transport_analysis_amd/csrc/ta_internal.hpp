@@ -522,6 +522,14 @@ hipError_t launch_shell_msd(const void* x, bool f32, long pitch, long T, long n_
                             hipStream_t st);
 hipError_t launch_shell_fold(const void* part, int G, long max_lag, int D, bool first, double* sums, long long* count, hipStream_t st);
 
+// shell_orient.hip: the shell-resolved reorientation of one block of observed items, between launch_shell_bits and
+// launch_shell_fold (D = 2) and with launch_shell_msd's words, lags, chunk, G and part (two sums per lag).  index: the block's
+// n_items rows of orient_row_len(mode) atoms of the slab x (dim 3), one per observed item (the vector's anchor), device int32;
+// hm: NULL or the distance pass's boxes (H[3], M[3] per box; per_frame: one per frame), the image step's orthorhombic box
+hipError_t launch_shell_orient(const void* x, bool f32, long pitch, long T, long n_atoms, int D, int mode, const int* index, long n_items,
+                               const double* hm, bool per_frame, const unsigned long long* words, int condition, long max_lag, int chunk,
+                               int G, void* part, hipStream_t st);
+
 // unwrap.hip: NoJump unwrapping of a float64 pair-major slab in place (rows < T; an unpaired column's partner untouched),
 // box table of unwrap_box.hpp on the device (tpitch rows per entry; a constant box: element 0)
 hipError_t launch_unwrap(double* slab, long pitch, long T, long n_atoms, int D, const int* axes, bool triclinic,

@@ -80,6 +80,7 @@ class PairLifetime(CollectiveAnalysis):
     _by_particle_message = ("PairLifetime has no per-particle result: the correlations are sums over all pairs "
                             "(by_particle=True is not supported)")
     _n_at = 2  # items per row of the list, results.<_result_keys[0]>
+    _staged_with = None  # universe indices staged along with the two groups (set by a subclass before __init__)
     _result_keys = ("pairs", "times", "n_bonded", "coordination", "run_lengths", "intermittent", "continuous",
                     "tau_intermittent", "tau_continuous", "mean_run")
 
@@ -137,6 +138,8 @@ class PairLifetime(CollectiveAnalysis):
             raise ValueError("atomgroup and atomgroup_b overlap but differ: they must be the same group or disjoint (a pair "
                              "list counts every pair once)")
         union = np.union1d(ix_a, ix_b)
+        if self._staged_with is not None:  # (atoms that are no items but are read with them: ShellOrientation's vectors)
+            union = np.union1d(union, self._staged_with)
         # (the group itself where it already is the sorted union: its frames are then read without a gather)
         own = np.asarray(atomgroup.ix if hasattr(atomgroup, "ix") else atomgroup.indices)
         staged = atomgroup if np.array_equal(union, own) else atomgroup.universe.atoms[union]
