@@ -1235,6 +1235,11 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      min(n, KC)); the results do not depend on it;
  *   "partial_chunk" n : wavevectors per launch of ta_partial_density*'s pass (0, the default: KC, the count of the tile
  *                      that serves the call's species; n >= 1: min(n, KC)); the results do not depend on it;
+ *   "partial_cross_chunk" n : wavevectors per batch of the cross term of ta_partial_density* and ta_partial_cross (0, the
+ *                      default: as many as keep the batch's workspaces under 1 GiB, at least 1; n >= 1: min(n, that count)).
+ *                      A batch is ONE by-particle evaluation of its n S^2 pseudo-particles.  With fft = 0, and with an even
+ *                      S^2, the results do not depend on it; with fft = 1 and an odd S^2 other pseudo-particles share a
+ *                      transform in another batching and the results agree within the FFT path's bound;
  *   "vanhove_chunk" n : lags per pass of ta_vanhove* (0, the default: as many as fit 64 KiB of LDS; n >= 1: min(n, n_lags,
  *                      that count)); the results do not depend on it;
  *   "overlap_chunk" n : lags per launch of ta_overlap* (0, the default: floor(S / n_cutoffs), S of ta_overlap_tile; n >= 1:

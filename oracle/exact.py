@@ -415,6 +415,26 @@ def current_exact(x, v, w, q):
     return np.stack([np.einsum("ktn,tnd->ktd", c, wv), np.einsum("ktn,tnd->ktd", s, wv)], axis=3)
 
 
+def partial_exact(x, w, labels, S, q):
+    """The exact integers behind ta_partial_density at quarter-turn phases, for integer positions x (T, A, D), integer
+    weights w (None: ones), labels in 0 ... S - 1 and turns q (K, D): (density (K, S, T, 2) int64 = sum_{n in a} w_n (cos,
+    sin) -- a label nobody carries: zeros --, numerators (K, T, S^2) int64 of the autocorrelations of each wavevector's S^2
+    pseudo-particles in slab order: pseudo-particle i S + j is rho_i (i == j), rho_i + rho_j (i < j), rho_i - rho_j (i > j),
+    as k_onsager_combos lays them out).  Over T - k: cross_aa = num[a S + a], cross_ab = 1/4 (num[a S + b] - num[b S + a])
+    for a < b."""
+    c, s = quarter_cs(x, q)
+    wi = np.ones(c.shape[2], dtype=np.int64) if w is None else _as_int(w)
+    labels = np.asarray(labels)
+    K, T, _ = c.shape
+    rho = np.zeros((K, S, T, 2), dtype=np.int64)
+    for a in range(S):
+        sel = np.flatnonzero(labels == a)
+        rho[:, a, :, 0] = c[:, :, sel] @ wi[sel]
+        rho[:, a, :, 1] = s[:, :, sel] @ wi[sel]
+    num = np.stack([pair_acf_num(pseudo_particles(rho[j])) for j in range(K)]) if K else np.zeros((0, T, S * S), dtype=np.int64)
+    return rho, num
+
+
 def axis_current_num(cur, axis):
     """(long numerators (T,), transverse numerators by component (T, D)) of one wavevector's integer current (T, D, 2) when
     the wavevector has ONE non-zero component `axis`: k^ = +-e_axis exactly, jL = +-current[axis], jT[d] = current[d] for

@@ -1,5 +1,6 @@
 """The analysis classes on the HIP path, GPU only: IntermediateScattering, CurrentCorrelation, VanHoveSelf, VanHoveDistinct,
-PairLifetime, HydrogenBondLifetime, OrientationalCorrelation and DynamicSusceptibility through StagedAnalysis._prepare,
+PairLifetime, HydrogenBondLifetime, OrientationalCorrelation, DynamicSusceptibility and PartialScattering (and, staged in
+pieces, ShellResidence, ShellMSD and ShellOrientation) through StagedAnalysis._prepare,
 _single_frame and _conclude -- pinned slabs filled by ta_stage_frame, stage_commit in pieces, "stage_device_f32" as
 _set_options asks for it, the unwrap and ta_compound before the call, the host-facing entry and _store.
 
@@ -8,7 +9,7 @@ _set_options asks for it, the unwrap and ta_compound before the call, the host-f
      printed figures.  Every run of a class in this module is watched (the fixture `watched`): with float32 staging the
      device slabs hold the staged float32 values AS float32 and no widening kernel ran in the call.  One case per class is
      staged in pieces of 32, 32 and 1 frames: the same bits as in one commit.
-  B  the four collective classes on devices=[0, 0] (and one on three members for two atoms), under distributed=True with
+  B  the five collective classes on devices=[0, 0] (and one on three members for two atoms), under distributed=True with
      two gloo ranks on the one GPU and more ranks than atoms, and with one nccl (RCCL) rank: every result against the
      reference over ALL atoms at the single-device bar, the integers equal to the single-device run's."""
 import ctypes
@@ -22,7 +23,11 @@ import test_current_correlation
 import test_orientation
 import test_overlap
 import test_pair_lifetime
+import test_partial_scattering as test_partial  # (test_partial_scattering is a test of this module)
 import test_scattering
+import test_shell_msd
+import test_shell_orientation
+import test_shell_residence
 import test_vanhove
 import test_vanhove_distinct
 from transport_analysis_amd import _base, _lib
@@ -30,9 +35,10 @@ from transport_analysis_amd import _base, _lib
 pytestmark = pytest.mark.gpu
 
 STAGING = [pytest.param(np.float32, id="stage32"), pytest.param(np.float64, id="stage64")]
-COLLECTIVE = [test_scattering, test_current_correlation, test_vanhove, test_overlap]
-MODULE_IDS = ["scattering", "current", "vanhove_self", "overlap"]
-ATOMS = {test_scattering: 13, test_current_correlation: 33, test_vanhove: 13, test_overlap: 13}  # odd: the blocks differ
+COLLECTIVE = [test_scattering, test_current_correlation, test_vanhove, test_overlap, test_partial]
+MODULE_IDS = ["scattering", "current", "vanhove_self", "overlap", "partial_scattering"]
+ATOMS = {test_scattering: 13, test_current_correlation: 33, test_vanhove: 13, test_overlap: 13,
+         test_partial: 33}  # odd: the blocks differ
 
 
 def device_slab_bits(c, slab, dtype):
@@ -143,6 +149,18 @@ def test_dynamic_susceptibility(dtype, watched):
     saw(watched, "DynamicSusceptibility", dtype)
 
 
+@pytest.mark.parametrize("dtype", STAGING)
+def test_partial_scattering(dtype, watched):
+    """the shells of the box against IntermediateScattering on the same placement, fft True and False; one species; total()
+    and the normalisations; weights and labels by attribute name; compound= with one label per compound"""
+    test_partial.class_partials_add_up_to_intermediate_scattering(**on_gpu(dtype))
+    test_partial.class_one_species_is_intermediate_scattering(**on_gpu(dtype))
+    test_partial.class_total_and_the_normalisations(**on_gpu(dtype))
+    test_partial.class_weights_and_attribute_names(**on_gpu(dtype))
+    test_partial.class_compound_with_per_compound_labels(**on_gpu(dtype))
+    saw(watched, "PartialScattering", dtype)
+
+
 _cpu_class = {}
 
 
@@ -225,7 +243,8 @@ def test_orientational_correlation_minimum_image(dims, moving, mode, dtype, watc
 def piece_cases():
     """{class name: a function that builds the class on 65 frames on device 0}"""
     from transport_analysis_amd import (CurrentCorrelation, DynamicSusceptibility, HydrogenBondLifetime, IntermediateScattering,
-                                        OrientationalCorrelation, VanHoveDistinct, VanHoveSelf)
+                                        OrientationalCorrelation, PartialScattering, ShellMSD, ShellOrientation, ShellResidence,
+                                        VanHoveDistinct, VanHoveSelf)
     from transport_analysis_amd._mini_mda import ArrayUniverse
 
     def scattering():
@@ -265,8 +284,29 @@ def piece_cases():
         x, lags, _, _, _ = test_overlap.ref.case(65, 13, 3)
         return DynamicSusceptibility(ArrayUniverse(positions=x).atoms, lags, cutoff=test_overlap.ref.CUTOFFS, device=0)
 
+    def partial_scattering():
+        x, w, lab, k = test_partial.ref.case(65, 33, 3, 3, 3)[:4]
+        return PartialScattering(ArrayUniverse(positions=x).atoms, k, species=lab, weights=w, device=0)
+
+    def shell_cuts(cuts, dims):
+        return dict(r_cut=cuts["r_cut"], r_break=cuts["r_break"], intermittency=1, periodic=dims is not None, device=0)
+
+    def shell_residence():
+        x, a, b, dims, axes, cuts = test_shell_residence.ref.case(65, 6, 30, 3, "disjoint", True, 1)[:6]
+        u = test_shell_residence.universe(x, dims, axes)
+        return ShellResidence(u.atoms[a], u.atoms[b], fft=False, **shell_cuts(cuts, dims))
+
+    def shell_msd():
+        x, a, b, dims, axes, cuts = test_shell_msd.mref.case(65, 6, 30, 3, "disjoint", True, 1, 20)[:6]
+        u = test_shell_residence.universe(x, dims, axes)
+        return ShellMSD(u.atoms[a], u.atoms[b], max_lag=20, **shell_cuts(cuts, dims))
+
+    def shell_orientation():
+        _, reference, group, vectors, cuts = test_shell_orientation.class_case("bond", 0, True, n_frames=65)[:5]
+        return ShellOrientation(reference, group, vectors, mode="bond", anchor=0, max_lag=30, **shell_cuts(cuts, True))
+
     return {f.__name__: f for f in (scattering, current, vanhove_self, vanhove_distinct, pair_lifetime, hydrogen_bonds, orientation,
-                                    susceptibility)}
+                                    susceptibility, partial_scattering, shell_residence, shell_msd, shell_orientation)}
 
 
 def same_bits(a, b):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import partial_ref as ref
+import placement
 from transport_analysis_amd import IntermediateScattering, PartialScattering, _lib
 from transport_analysis_amd._mini_mda import ArrayUniverse
 
@@ -252,13 +253,15 @@ def universe(T=50, A=12, box=None, seed=11):
     return ArrayUniverse(positions=x, **kw), x
 
 
-def test_class_partials_add_up_to_intermediate_scattering():
+def class_partials_add_up_to_intermediate_scattering(**place):
+    """the body of test_class_partials_add_up_to_intermediate_scattering under the placement keywords `place`
+    (test_classes_gpu.py runs the class bodies on the GPU)"""
     T, A = 50, 12
     u, x = universe(T, A, box=[15, 15, 15, 90, 90, 90])
     lab = np.array(list("ABBCABBCABBA"))
     for fft in (True, False):
-        r = PartialScattering(u.atoms, species=lab, q=[0.5, 0.9], dq=0.2, max_vectors=4, fft=fft, device="cpu").run()
-        s = IntermediateScattering(u.atoms, q=[0.5, 0.9], dq=0.2, max_vectors=4, fft=fft, device="cpu").run().results
+        r = PartialScattering(u.atoms, species=lab, q=[0.5, 0.9], dq=0.2, max_vectors=4, fft=fft, **place).run()
+        s = IntermediateScattering(u.atoms, q=[0.5, 0.9], dq=0.2, max_vectors=4, fft=fft, **place).run().results
         res = r.results
         K = res.kvectors.shape[0]
         assert list(res.species) == ["A", "B", "C"] and list(res.species_counts) == [4, 6, 2]
@@ -277,25 +280,33 @@ def test_class_partials_add_up_to_intermediate_scattering():
             r.bhatia_thornton()
 
 
-def test_class_one_species_is_intermediate_scattering():
+def test_class_partials_add_up_to_intermediate_scattering():
+    class_partials_add_up_to_intermediate_scattering(device="cpu")
+
+
+def class_one_species_is_intermediate_scattering(**place):
     T, A = 50, 12
     u, x = universe(T, A)
     k = np.array([[1.0, 0.0, 0.0], [0.6, 0.8, 0.0]])
     x32 = x.astype(np.float32).astype(np.float64)
-    r = PartialScattering(u.atoms, k, species=np.zeros(A, dtype=int), device="cpu").run().results
-    s = IntermediateScattering(u.atoms, k, device="cpu").run().results
+    r = PartialScattering(u.atoms, k, species=np.zeros(A, dtype=int), **place).run().results
+    s = IntermediateScattering(u.atoms, k, **place).run().results
     bar = ref.density_bar(x32, None, np.zeros(A, dtype=np.int32), 1, k)[0]
     assert np.max(np.abs(r.density[:, 0] - s.density)) <= 2 * bar
     assert np.max(np.abs(r.f_partial[:, :, 0, 0] - s.f)) <= 1e-10 * np.max(np.abs(s.f[0]))
     assert np.array_equal(r.shell, np.arange(2))
 
 
-def test_class_total_and_the_normalisations():
+def test_class_one_species_is_intermediate_scattering():
+    class_one_species_is_intermediate_scattering(device="cpu")
+
+
+def class_total_and_the_normalisations(**place):
     T, A = 50, 12
     u, x = universe(T, A)
     k = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.6, 0.8, 0.0]])
     lab = np.arange(A) % 2
-    r = PartialScattering(u.atoms, k, species=lab, fft=False, device="cpu").run()
+    r = PartialScattering(u.atoms, k, species=lab, fft=False, **place).run()
     res = r.results
     b = np.array([0.5, -2.0])
     lags = ref.lag_sample(T)
@@ -321,13 +332,17 @@ def test_class_total_and_the_normalisations():
     # a species label that no atom carries cannot arise from labels; an empty species comes from index order only: NaN rule
     r.results.species_counts = np.array([12, 0])
     assert np.all(np.isnan(r.ashcroft_langreth()[..., 1, 1]) | np.isinf(r.ashcroft_langreth()[..., 1, 1]))
-    fresh = PartialScattering(u.atoms, k, species=lab, device="cpu")
+    fresh = PartialScattering(u.atoms, k, species=lab, **place)
     for call in (fresh.total, fresh.ashcroft_langreth, fresh.bhatia_thornton):
         with pytest.raises(RuntimeError, match="must be run"):
             call()
 
 
-def test_class_weights_and_attribute_names():
+def test_class_total_and_the_normalisations():
+    class_total_and_the_normalisations(device="cpu")
+
+
+def class_weights_and_attribute_names(**place):
     T, A = 40, 12
     rng = np.random.default_rng(3)
     x = np.cumsum(rng.normal(scale=0.2, size=(T, A, 3)), axis=0) + 20
@@ -336,12 +351,16 @@ def test_class_weights_and_attribute_names():
     u.atoms.types = types  # species by the name of a per-atom attribute of the group
     k = np.array([[1.0, 0.0, 0.0]])
     w = ref.weights(A, 2)
-    r = PartialScattering(u.atoms, k, species="types", weights=w, device="cpu").run().results
+    r = PartialScattering(u.atoms, k, species="types", weights=w, **place).run().results
     assert list(r.species) == ["Cl", "Na"]
     x32 = x.astype(np.float32).astype(np.float64)
     lab = np.where(types == "Cl", 0, 1).astype(np.int32)
     want = ref.density_of(x32, w, lab, 2, k)
     assert np.all(np.max(np.abs(r.density - want), axis=(0, 2, 3)) <= ref.density_bar(x32, w, lab, 2, k))
+
+
+def test_class_weights_and_attribute_names():
+    class_weights_and_attribute_names(device="cpu")
 
 
 def test_class_refusals():
@@ -366,7 +385,7 @@ def test_class_refusals():
         PartialScattering(u.atoms, species=lab, q=1.0, dq=0.2, device="cpu").run()
 
 
-def test_class_compound_with_per_compound_labels():
+def class_compound_with_per_compound_labels(**place):
     """molecules of three atoms: the partials of their centres of mass, one label per compound, against the class run on the
     centres themselves"""
     T, A = 30, 12
@@ -376,7 +395,7 @@ def test_class_compound_with_per_compound_labels():
     mol = np.arange(A) // 3
     k = np.array([[1.0, 0.0, 0.0], [0.6, 0.8, 0.0]])
     lab = np.array([0, 1, 1, 0])
-    r = PartialScattering(ArrayUniverse(positions=x, masses=m).atoms, k, species=lab, compound=mol, fft=False, device="cpu").run().results
+    r = PartialScattering(ArrayUniverse(positions=x, masses=m).atoms, k, species=lab, compound=mol, fft=False, **place).run().results
     wn = m / np.bincount(mol, weights=m)[mol]
     com = np.stack([(x[:, mol == c] * wn[mol == c][None, :, None]).sum(axis=1) for c in range(4)], axis=1)
     assert r.density.shape == (2, 2, T, 2) and list(r.species_counts) == [2, 2]
@@ -386,9 +405,14 @@ def test_class_compound_with_per_compound_labels():
     assert np.max(np.abs(r.f_partial_by_kvector[0] - d0)) <= 1e-10 * np.max(np.abs(d0))
 
 
+def test_class_compound_with_per_compound_labels():
+    class_compound_with_per_compound_labels(device="cpu")
+
+
 # ---- the class on several ranks: distributed=True -----------------------------------------------------------------------
 PLACED_T = 65
 INTEGER_KEYS = ()  # (nothing here is an integer)
+placement.PORTS.setdefault(__name__, 52000)  # (this module's first port, beside the other classes': test_classes_gpu.py too)
 
 
 def placed_case(A):
@@ -423,7 +447,4 @@ def test_class_distributed_two_gloo_ranks_cpu_backend(tmp_path, A):
     and contributes zeros (_no_moments).  The densities are summed over the ranks BEFORE the cross term (ta_partial_cross)."""
     import sys
 
-    import placement
-
-    placement.PORTS.setdefault(__name__, 52000)  # (this module's first port, beside the other classes')
     placement.check_ranks(sys.modules[__name__], A, 2, "cpu", tmp_path, dict(device="cpu"))

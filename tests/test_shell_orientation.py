@@ -146,8 +146,8 @@ def test_degenerate_vector(mode):
 
 
 # ---- the class ------------------------------------------------------------------------------------------------------------------
-def class_case(mode, anchor, boxed, kind="disjoint", L=30):
-    x, a, b, rows, dims, axes, cuts, g, want, runs, nb = oref.case(40, 6, 30, kind, boxed, 1, L, mode, anchor)
+def class_case(mode, anchor, boxed, kind="disjoint", L=30, n_frames=40):
+    x, a, b, rows, dims, axes, cuts, g, want, runs, nb = oref.case(n_frames, 6, 30, kind, boxed, 1, L, mode, anchor)
     u = ArrayUniverse(positions=x, dimensions=dims)
     anchors = a if b is None else b
     # the followed group: the anchors and their partners, in an order of its own; vectors are positions within it

@@ -126,6 +126,7 @@ private:
     X(scatter_chunk, 0, opt_check_scatter_chunk) /* wavevectors per pass of ta_scatter* (0: as many as fit kScatterBudget) */ \
     X(kcurrent_chunk, 0, opt_check_kcurrent_chunk) /* wavevectors per launch of k_kcurrent (0: the tile's own count) */     \
     X(partial_chunk, 0, opt_check_partial_chunk) /* wavevectors per launch of k_species_density (0: the tile's own count) */ \
+    X(partial_cross_chunk, 0, opt_check_partial_cross_chunk) /* wavevectors per batch of partial_cross (0: as many as fit kPartialCrossBudget) */ \
     X(vanhove_chunk, 0, opt_check_vanhove_chunk) /* lags per pass of ta_vanhove* (0: as many as fit a workgroup's LDS) */ \
     X(overlap_chunk, 0, opt_check_overlap_chunk) /* lags per launch of ta_overlap* (0: as many as the kernel's tile holds) */ \
     X(vanhove_distinct_chunk, 0, opt_check_vanhove_distinct_chunk) /* lags per pass of ta_vanhove_distinct* (0: as many as fit kVhdBudget) */ \
@@ -1564,12 +1565,14 @@ int partial_plan(ta_ctx* ctx, int K, const double* h_kvecs, int D, const double*
 // cross (K, T, S, S) of the densities (K, S, T, 2) at d_density: a complex density is a species sum with dim 2, so wavevector
 // j's block is the (S, T, 2) sums coll_cross takes, and its S^2 pseudo-particles rho_a, rho_a + rho_b, rho_a - rho_b are S^2
 // whole pairs.  Per chunk of Kx wavevectors -- as many as keep the Onsager workspaces under kPartialCrossBudget, which bounds
-// memory and nothing else: a particle's autocorrelation does not depend on its neighbours -- k_onsager_combos per wavevector,
-// ONE by-particle evaluation of the chunk's Kx S^2 particles by the VACF's dispatch, and the finish.
+// memory and nothing else: a particle's autocorrelation does not depend on its neighbours; "partial_cross_chunk" n: min(n,
+// that count) -- k_onsager_combos per wavevector, ONE by-particle evaluation of the chunk's Kx S^2 particles by the VACF's
+// dispatch, and the finish.
 int partial_cross(ta_ctx* ctx, bool fft, const double* d_density, int K, int S, int64_t T, double* d_cross, hipStream_t st) {
     const int64_t P1 = (int64_t)S * S, pitch = pm_pitch(T);
     const size_t per_k = pm_bytes(T, 2 * P1) + sizeof(double) * (size_t)(T * P1);
-    const int Kx = (int)std::max<size_t>(1, std::min<size_t>((size_t)K, kPartialCrossBudget / per_k));
+    const int Kfit = (int)std::max<size_t>(1, std::min<size_t>((size_t)K, kPartialCrossBudget / per_k));
+    const int Kx = ctx->opt_partial_cross_chunk > 0 ? (int)std::min<int64_t>(ctx->opt_partial_cross_chunk, Kfit) : Kfit;
     TA_CHECK(ensure(ctx, ctx->ons_pm, pm_bytes(T, 2 * P1 * Kx)));
     TA_CHECK(ensure(ctx, ctx->ons_bp, sizeof(double) * (size_t)(T * P1 * Kx + T) + sizeof(int) * TA_ONSAGER_MAX_SPECIES * (size_t)Kx));
     double* pm = (double*)ctx->ons_pm.p;
@@ -2526,6 +2529,9 @@ int opt_check_kcurrent_chunk(ta_ctx* ctx, int64_t value) {
 }
 int opt_check_partial_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "partial_chunk: 0 (the tile's count) or the wavevectors per launch");
+}
+int opt_check_partial_cross_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "partial_cross_chunk: 0 (automatic) or the wavevectors per batch");
 }
 int opt_check_scatter_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "scatter_chunk: 0 (automatic) or the wavevectors per pass");
