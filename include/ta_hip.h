@@ -484,6 +484,38 @@ int ta_overlap(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_cutoffs, co
 /* the (lag, cutoff) slots S of one k_overlap launch, a compile-time tile of the library */
 int ta_overlap_tile(int *slots);
 
+/* ta_overlap_density : the density of the overlap field of the positions in slab 0 per time origin (FourPointStructureFactor):
+ *              the sum whose variance over origins is the four-point structure factor S_4(k, t).  With T frames, N atoms, D
+ *              staged columns, n_k wavevectors h_kvecs (n_k, D) in rad per length unit (1 <= n_k <= TA_SCATTER_MAX_K; k = 0
+ *              is allowed), n_lags lags under ta_vanhove's rules and n_cutoffs cutoffs under ta_overlap's:
+ *                r2, a2[c]  = exactly ta_overlap's (strict <; a float32 slab widened first; a NaN r2 counts nothing)
+ *                (cos, sin) = exactly ta_partial_density's phase of x[t0], the ORIGIN frame: q = k / 2 pi on the host, u by
+ *                             product-then-fma, r = u - rint(u), sincospi(2 r)
+ *                h_w[(((j * n_cutoffs + c) * n_lags + l) * T + t0) * 2 + (0, 1)] = sum_{n: r2 < a2[c]} (cos, sin)
+ *                             for t0 < T - tau_l,  (+0.0, +0.0) for t0 >= T - tau_l          float64, every element written
+ *              NOTHING is divided and there are no weights.  The update is a select (an atom outside adds nothing, no 0 NaN
+ *              arises).  With k = 0 the real part equals ta_overlap's Q exactly and the imaginary part is 0.  W adds up over
+ *              atoms -- shards, group members, ranks --, |W|^2 does not: a variance over origins is to be taken AFTER that sum.
+ *              A call with n_k * n_cutoffs * n_lags * T > 2^26 is refused: the output would pass 1 GiB.  That limit is a choice.
+ *              The pass k_overlap_density reads the slab in the element type it has, with k_overlap's reads, once per launch
+ *              of KC wavevectors and Lc lags: the phase depends on the origin frame only, so one sincospi per (atom, origin
+ *              frame, wavevector) serves every (lag, cutoff) slot of the launch.  A thread keeps one complex sum per (slot,
+ *              wavevector, origin frame of its own) in registers across its atoms; the sums leave as partials per group of
+ *              atoms, added in a fixed order by k_overlap_density_sum: no atomics, and the groups depend on the slab and
+ *              the device only, so the bits are the same from run to run and for every chunk.  Lc = floor(SL / n_cutoffs)
+ *              with SL, KC of the kernel's tile (ta_overlap_density_tile), at most n_lags; option "overlap_density_chunk"
+ *              n >= 1 forces min(n, n_lags, that count).  ta_trim releases the partials and the host-facing calls' output.
+ *              NULL h_kvecs, n_k outside 1 ... TA_SCATTER_MAX_K, a non-finite component, then ta_overlap's checks of the
+ *              lags and cutoffs, a NULL output, the 2^26 bound (all checked before anything is allocated or written, under
+ *              the prefix "overlap_density: "): TA_E_INVALID; nothing staged: TA_E_STATE; n_atoms * dim must be below 2^31.
+ *              CPU backend: the same r2, a2 and phase expression; OpenMP over the (lag, origin) pairs, each a plain sum in
+ *              atom order: the bits do not depend on the number of threads.  Timings: k_overlap_density is the main kernel. */
+int ta_overlap_density(ta_ctx *ctx, int n_k, const double *h_kvecs, int n_lags, const int64_t *h_lags, int n_cutoffs,
+                       const double *h_cutoffs, double *h_w);
+/* the (lag, cutoff) slots SL and the wavevectors KC of one k_overlap_density launch and the origin frames per thread (a
+ * workgroup covers 256 frames of them), a compile-time tile of the library */
+int ta_overlap_density_tile(int *slots, int *kc, int *frames);
+
 /* ta_vanhove_distinct : the distinct part of the van Hove function of the positions in slab 0 (VanHoveDistinct): the
  *              histogram of the distances between item a_p at an origin frame and item b_q a lag later, over ORDERED pairs
  *              of different items.  With T frames, D staged columns:
@@ -1002,6 +1034,12 @@ int ta_vanhove_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_bins
 int ta_overlap_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int n_cutoffs, const double *h_cutoffs, int64_t *d_q,
                       void *stream);
 
+/* h_kvecs, h_lags, h_cutoffs: HOST arrays, as for ta_overlap_density (they size the launches; checked before anything is
+ * written); d_w (n_k, n_cutoffs, n_lags, n_frames, 2) float64 on the device; slab 0 (the positions) is read in the element
+ * type it has.  Asynchronous on `stream`; there is no frame-major (_dev) entry */
+int ta_overlap_density_staged(ta_ctx *ctx, int n_k, const double *h_kvecs, int n_lags, const int64_t *h_lags, int n_cutoffs,
+                              const double *h_cutoffs, double *d_w, void *stream);
+
 /* every list and the box: HOST arrays, as for ta_vanhove_distinct (they size the launches; checked before anything is
  * written); d_counts (n_lags, n_bins + 1) int64: a device array; slab 0 is read in the element type it has */
 int ta_vanhove_distinct_staged(ta_ctx *ctx, int n_lags, const int64_t *h_lags, int64_t origin_stride, int64_t n_a,
@@ -1126,6 +1164,10 @@ int ta_group_vanhove(ta_group *g, int n_lags, const int64_t *h_lags, int n_bins,
 /* ta_group_overlap: ta_overlap on every member with the same lags and cutoffs (checked first): the members' Q are SUMMED on
  * the host as int64 -- the per-origin counts add up over atoms, their squares do not.                                */
 int ta_group_overlap(ta_group *g, int n_lags, const int64_t *h_lags, int n_cutoffs, const double *h_cutoffs, int64_t *h_q);
+/* ta_group_overlap_density: ta_overlap_density on every member with the same wavevectors, lags and cutoffs (checked first):
+ * the members' W are SUMMED on the host in member order as float64 -- the per-origin sums add up over atoms, |W|^2 does not. */
+int ta_group_overlap_density(ta_group *g, int n_k, const double *h_kvecs, int n_lags, const int64_t *h_lags, int n_cutoffs,
+                             const double *h_cutoffs, double *h_w);
 /* ta_group_unwrap: ta_unwrap on every member's block of slab `slab` (declared with ta_unwrap above) */
 int ta_group_unwrap(ta_group *g, int slab, const double *h_dimensions, const int *axes); /* every member's block */
 
@@ -1244,6 +1286,8 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      that count)); the results do not depend on it;
  *   "overlap_chunk" n : lags per launch of ta_overlap* (0, the default: floor(S / n_cutoffs), S of ta_overlap_tile; n >= 1:
  *                      min(n, n_lags, that count)); the results do not depend on it;
+ *   "overlap_density_chunk" n : lags per launch of ta_overlap_density* (0, the default: floor(SL / n_cutoffs), SL of
+ *                      ta_overlap_density_tile; n >= 1: min(n, n_lags, that count)); the results do not depend on it bit for bit;
  *   "vanhove_distinct_chunk" n : lags per pass of ta_vanhove_distinct* (0, the default: as many as fit 4 GiB of gathered
  *                      scratch, at least 1; n >= 1: min(n, n_lags)); the results do not depend on it;
  *   "pair_chunk" n : candidate pairs per block of ta_pair_lifetime* (0, the default: as many as fit 32 GiB of indicator

@@ -4,7 +4,8 @@ transport-analysis API (VelocityAutocorr, ViscosityHelfand), MDAnalysis' Einstei
 IntermediateScattering, with their species-resolved partials F_ab(k, t) and S_ab(k), PartialScattering, and their real-space partners, the self van Hove function G_s(r, t) with the non-Gaussian parameter,
 VanHoveSelf, and the distinct van Hove function G_d(r, t) with the radial distribution function g(r), VanHoveDistinct, and
 the longitudinal and transverse current correlation functions C_L(k, t) and C_T(k, t), CurrentCorrelation, and the
-self-overlap Q(t) with the four-point susceptibility chi_4(t), DynamicSusceptibility, and the rotational correlation functions
+self-overlap Q(t) with the four-point susceptibility chi_4(t), DynamicSusceptibility, and the four-point structure factor
+S_4(k, t) of the overlap field, FourPointStructureFactor, and the rotational correlation functions
 C_1(t), C_2(t) of molecule-fixed unit vectors with their dipole sum, OrientationalCorrelation, and the intermittent and
 continuous pair population correlation functions with the lifetimes of ion pairs and solvation contacts, PairLifetime, and
 of hydrogen bonds with a donor-hydrogen-acceptor angle criterion, HydrogenBondLifetime, and the residence times of atoms in
@@ -24,6 +25,7 @@ from .current_correlation import CurrentCorrelation  # noqa: F401
 from .vanhove import VanHoveSelf, log_lags  # noqa: F401
 from .vanhove_distinct import VanHoveDistinct  # noqa: F401
 from .susceptibility import DynamicSusceptibility  # noqa: F401
+from .four_point import FourPointStructureFactor  # noqa: F401
 from .orientation import OrientationalCorrelation, group_indices  # noqa: F401
 from .pair_lifetime import PairLifetime  # noqa: F401
 from .hbond_lifetime import HydrogenBondLifetime  # noqa: F401

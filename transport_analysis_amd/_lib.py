@@ -48,6 +48,8 @@ _KCURRENT = _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp)  # (handle, fft, n_k, h
 _PARTIAL = _int(_vp, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp)
 _VANHOVE = _int(_vp, _ci, _vp, _ci, _dbl, _vp, _vp)  # (handle, n_lags, h_lags, n_bins, dr, h_counts, h_moments)
 _OVERLAP = _int(_vp, _ci, _vp, _ci, _vp, _vp)  # (handle, n_lags, h_lags, n_cutoffs, h_cutoffs, h_q)
+# (handle, n_k, h_kvecs, n_lags, h_lags, n_cutoffs, h_cutoffs, h_w)
+_OVERLAP_DENSITY = _int(_vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp)
 
 #: every symbol include/ta_hip.h declares -> (result type, argument types): the one table EXPORTS and lib() are made of
 _API = {
@@ -89,6 +91,8 @@ _API = {
     "ta_vanhove_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _ci, _dbl, _vp, _vp, _vp),
     "ta_overlap": _OVERLAP, "ta_overlap_tile": _int(_P(_ci)), "ta_overlap_staged": _int(_vp, _ci, _vp, _ci, _vp, _vp, _vp),
     "ta_overlap_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _vp, _ci, _vp, _vp, _vp),
+    "ta_overlap_density": _OVERLAP_DENSITY, "ta_overlap_density_tile": _int(_P(_ci), _P(_ci), _P(_ci)),
+    "ta_overlap_density_staged": _int(_vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp),
     # (handle, n_lags, h_lags, origin_stride, n_a, h_idx_a, n_b, h_idx_b, h_dimensions, axes, n_bins, dr, counts[, stream])
     "ta_vanhove_distinct": _int(_vp, _ci, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _dbl, _vp),
     "ta_pair_find": _int(_vp, _i64, _vp, _i64, _vp, _vp, _vp, _dbl, _i64, _vp),
@@ -132,6 +136,7 @@ _API = {
     "ta_group_scatter": _SCATTER, "ta_group_kcurrent": _KCURRENT, "ta_group_partial_density": _PARTIAL,
     "ta_group_vanhove": _VANHOVE,
     "ta_group_overlap": _OVERLAP,
+    "ta_group_overlap_density": _OVERLAP_DENSITY,
 }
 EXPORTS = tuple(_API)
 
@@ -235,6 +240,15 @@ def overlap_tile():
     slots = ctypes.c_int()
     lib().ta_overlap_tile(ctypes.byref(slots))
     return slots.value
+
+
+def overlap_density_tile():
+    """{"SL", "KC", "F"}: the (lag, cutoff) slots and the wavevectors of one k_overlap_density launch -- floor(SL / n_cutoffs)
+    lags and KC wavevectors share a launch -- and the origin frames per thread (a workgroup covers 256 F frames),
+    ta_overlap_density_tile"""
+    sl, kc, f = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    lib().ta_overlap_density_tile(ctypes.byref(sl), ctypes.byref(kc), ctypes.byref(f))
+    return {"SL": sl.value, "KC": kc.value, "F": f.value}
 
 
 def _ptr(a):
@@ -630,6 +644,24 @@ class _Staged:
         self._call("overlap", L, _ptr(lg), C, _ptr(a), _ptr(q))
         return q
 
+    def overlap_density(self, kvectors, lags, cutoffs):
+        """Density of the overlap field per time origin of slab 0 (the positions), ta_overlap_density: for `kvectors` (n_k,
+        dim) in rad per length unit (k = 0 allowed), the integer frame `lags` and the `cutoffs` a_c of `overlap` the
+        complex128 array W (n_k, n_cutoffs, n_lags, n_frames) = sum over the atoms with |x(t0 + lag) - x(t0)| < a_c of
+        exp(i k . x(t0)), zeros at t0 >= n_frames - lag; nothing is divided.  A group: the members' W are summed (|W|^2
+        and a variance over origins come after that sum)."""
+        T, D = (self.shape[0], self.shape[2]) if self.shape is not None else (0, 0)
+        if D:
+            k, K = self._kvectors(kvectors, D)
+        else:  # unstaged: the library reports it
+            k = np.ascontiguousarray(kvectors, dtype=np.float64)
+            K = int(k.shape[0]) if k.ndim else 0
+        lg, L = self._lags(lags)
+        a, C = self._cutoffs(cutoffs)
+        w = np.empty((K, C, L, T, 2), dtype=np.float64)
+        self._call("overlap_density", K, _ptr(k), L, _ptr(lg), C, _ptr(a), _ptr(w))
+        return w.view(np.complex128)[..., 0]
+
     def unwrap(self, slab, dimensions, axes):
         """Undo periodic wrapping of staged slab `slab` in place (MDAnalysis' NoJump, ta_unwrap; a group: on every
         member's block of the slab): `dimensions` the (n_frames, 6) boxes [a, b, c, alpha, beta, gamma] of the staged
@@ -911,6 +943,14 @@ class Context(_Staged):
         lg, L = self._lags(lags)
         a, C = self._cutoffs(cutoffs)
         self._call("overlap_staged", L, _ptr(lg), C, _ptr(a), d_q or None, stream or None)
+
+    def overlap_density_staged(self, kvectors, lags, cutoffs, d_w, stream=0):
+        """`kvectors`, `lags`, `cutoffs`: HOST arrays (checked by the library before anything is written); d_w (n_k,
+        n_cutoffs, n_lags, n_frames, 2) float64 on the device"""
+        k, K = self._kvectors(kvectors, self._staged_shape()[2])
+        lg, L = self._lags(lags)
+        a, C = self._cutoffs(cutoffs)
+        self._call("overlap_density_staged", K, _ptr(k), L, _ptr(lg), C, _ptr(a), d_w or None, stream or None)
 
     def _vhd_args(self, lags, origin_stride, idx_a, idx_b, dimensions, axes, n_bins, dr):
         """the argument tuple ta_vanhove_distinct* share, and the arrays it points into (to be kept until the call is over)"""

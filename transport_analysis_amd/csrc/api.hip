@@ -129,6 +129,7 @@ private:
     X(partial_cross_chunk, 0, opt_check_partial_cross_chunk) /* wavevectors per batch of partial_cross (0: as many as fit kPartialCrossBudget) */ \
     X(vanhove_chunk, 0, opt_check_vanhove_chunk) /* lags per pass of ta_vanhove* (0: as many as fit a workgroup's LDS) */ \
     X(overlap_chunk, 0, opt_check_overlap_chunk) /* lags per launch of ta_overlap* (0: as many as the kernel's tile holds) */ \
+    X(overlap_density_chunk, 0, opt_check_overlap_density_chunk) /* lags per launch of ta_overlap_density* (0: as many as the kernel's tile holds) */ \
     X(vanhove_distinct_chunk, 0, opt_check_vanhove_distinct_chunk) /* lags per pass of ta_vanhove_distinct* (0: as many as fit kVhdBudget) */ \
     X(pair_chunk, 0, opt_check_pair_chunk) /* candidate pairs per block of ta_pair_lifetime* (0: as many as fit kPairBudget) */ \
     X(pair_find_chunk, 0, opt_check_pair_find_chunk) /* searched frames per pass of ta_pair_find (0: as many as fit kVhdBudget) */ \
@@ -206,6 +207,11 @@ struct ta_ctx {
     // caller's array, so the only buffer is the output of host-facing calls (up to 1 GiB: trimmed)
     HostTable ov_tab{workspaces, tables};
     DevBuf ov_out{workspaces, kTrimmed};
+    // overlap field's density per origin (overlap_density_pm): the lags (int64) with the squared cutoffs and the wavevectors
+    // in turns behind them, the partial sums of one launch (trimmed; its size does not depend on the call's lists), the
+    // output of host-facing calls (up to 1 GiB: trimmed)
+    HostTable od_tab{workspaces, tables};
+    DevBuf od_part{workspaces, kTrimmed}, od_out{workspaces, kTrimmed};
     // distinct van Hove function (vhd_pm): the table (lags, squared edges, box entries, padded index lists), the gathered
     // frame-major scratch GA | GB and the uint64 histogram (trimmed), the output of host-facing calls
     HostTable vhd_tab{workspaces, tables};
@@ -1692,6 +1698,53 @@ int overlap_pm(ta_ctx* ctx, const Slab& slab, int L, int C, int64_t* d_q) {
     return call_end(ctx, st);
 }
 
+// ---- overlap field's density per origin (overlap_density.hip) ----------------------------------------------------------
+constexpr size_t kOdBudget = (size_t)1 << 30;  // k_overlap_density's partial-sum buffer, as kPartialBudget (a choice)
+
+// the table's tail: the squared cutoffs a2[c] = fl(a_c a_c), then the wavevectors in turns (q = k / 2 pi)
+int overlap_density_plan(ta_ctx* ctx, int K, const double* h_kvecs, int L, const int64_t* h_lags, int C, const double* h_cutoffs,
+                         int64_t A, int D, hipStream_t st) {
+    return lag_table_plan(
+        ctx, ctx->od_tab, "overlap_density: ", L, h_lags, (size_t)C + (size_t)K * D,
+        [&](double* tail) {
+            vh_cutoffs2(C, h_cutoffs, tail);
+            for (size_t i = 0; i < (size_t)K * D; ++i) tail[C + i] = phase_turns(h_kvecs[i]);
+        },
+        A, D, st);
+}
+
+// One call on a pair-major position slab of either element type, read as it is (the caller has opened the call's bracket, it
+// is closed here; overlap_density_plan has queued the table).  Per chunk of at most KC wavevectors and Lc lags (Lc C <= the
+// tile's slots; "overlap_density_chunk" n: min(n, L, that count)) ONE k_overlap_density launch and the fixed-order sum of
+// its partials into its corner of d_w (K, C, L, T, 2): every element is written, those at t0 >= T - tau as the +0.0 nothing
+// was added to.  The atom groups depend on the slab and the device only: the same bits for every chunk size.  ev[1] / ev[2]
+// bracket the (last) launch.
+int overlap_density_pm(ta_ctx* ctx, const Slab& s, int K, int L, int C, double* d_w) {
+    hipStream_t st = s.st;
+    int SL = 1, KC = 1, F = 2;
+    overlap_density_tile(&SL, &KC, &F);
+    const int Lc = lag_chunk(ctx->opt_overlap_density_chunk, L, std::max(1, SL / C));
+    const int G = overlap_density_parts(ctx->n_cu, (long)s.pitch, (long)s.A, kOdBudget);
+    TA_CHECK(ensure(ctx, ctx->od_part, (size_t)G * SL * KC * (size_t)s.T * 16));
+    double* part = (double*)ctx->od_part.p;
+    const int64_t* d_lags = (const int64_t*)ctx->od_tab.dev.p;
+    const double* d_a2 = (const double*)ctx->od_tab.dev.p + L;
+    const double* d_q = d_a2 + C;
+    for (int j0 = 0; j0 < K; j0 += KC) {
+        const int kc = std::min(KC, K - j0);
+        for (int l0 = 0; l0 < L; l0 += Lc) {
+            const int lc = std::min(Lc, L - l0);
+            TA_LAUNCH_MAIN(ctx, "k_overlap_density", st,
+                           launch_overlap_density(s.pm, s.f32, (long)s.pitch, (long)s.T, (long)s.A, s.D, d_lags, l0, lc, L, d_a2, C,
+                                                  d_q + (size_t)j0 * s.D, kc, part, G, st));
+            TA_LAUNCH(ctx, "k_overlap_density_sum", st,
+                      launch_overlap_density_sum(part, G, (long)s.T, lc, C, L, kc,
+                                                 d_w + (((size_t)j0 * C) * L + l0) * (size_t)s.T * 2, st));
+        }
+    }
+    return call_end(ctx, st);
+}
+
 // ---- distinct van Hove function (vanhove_distinct.hip) --------------------------------------------------------------
 constexpr size_t kVhdBudget = (size_t)4 << 30;  // the gathered scratch of one pass (a choice, not a measurement)
 
@@ -2554,6 +2607,9 @@ int opt_check_shell_msd_chunk(ta_ctx* ctx, int64_t value) {
 int opt_check_overlap_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "overlap_chunk: 0 (automatic) or the lags per launch");
 }
+int opt_check_overlap_density_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "overlap_density_chunk: 0 (automatic) or the lags per launch");
+}
 int opt_check_vanhove_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "vanhove_chunk: 0 (automatic) or the lags per pass");
 }
@@ -3347,6 +3403,23 @@ int ta_overlap_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_cuto
     });
 }
 
+// Overlap field's density per origin: the staged slab 0 holds the positions, read in its own element type (never widened);
+// the wavevectors, lags and cutoffs are HOST arrays: they size the launches, and overlap_density_plan runs before the call
+// is opened; there is no frame-major entry
+int ta_overlap_density_staged(ta_ctx* ctx, int n_k, const double* h_kvecs, int n_lags, const int64_t* h_lags, int n_cutoffs,
+                              const double* h_cutoffs, double* d_w, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    return slab_entry(
+        ctx, nullptr, stream,
+        [&] {
+            return check_overlap_density(fail, ctx, n_k, h_kvecs, ctx->st_nslabs ? ctx->st_D : 0, n_lags, h_lags, n_cutoffs, h_cutoffs,
+                                         ctx->st_nslabs ? ctx->st_T : 0, d_w != nullptr);
+        },
+        [&](const Slab& s) { return overlap_density_plan(ctx, n_k, h_kvecs, n_lags, h_lags, n_cutoffs, h_cutoffs, s.A, s.D, s.st); },
+        [&](const Slab& s) { return overlap_density_pm(ctx, s, n_k, n_lags, n_cutoffs, d_w); });
+    });
+}
+
 // Distinct van Hove function on the staged slab 0, read in its own element type; every list is a HOST array
 int ta_vanhove_distinct_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int64_t origin_stride, int64_t n_a,
                                const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes,
@@ -3815,6 +3888,24 @@ int overlap_launch(ta_ctx* ctx, int L, const int64_t* h_lags, int C, const doubl
     return TA_OK;
 }
 
+// Overlap-density share of a host-facing call, queued on ctx->stream and not waited for: the wavevectors, lags and cutoffs
+// (checked by the caller) uploaded, W (K, C, L, T, 2) left on the device in *d_out
+int overlap_density_launch(ta_ctx* ctx, int K, const double* h_kvecs, int L, const int64_t* h_lags, int C, const double* h_cutoffs,
+                           double** d_out) {
+    double* out = nullptr;
+    TA_CHECK(slab_entry(
+        ctx, nullptr, ctx->stream, no_args,
+        [&](const Slab& s) -> int {
+            TA_CHECK(overlap_density_plan(ctx, K, h_kvecs, L, h_lags, C, h_cutoffs, s.A, s.D, ctx->stream));
+            TA_CHECK(ensure(ctx, ctx->od_out, sizeof(double) * 2 * (size_t)K * (size_t)C * (size_t)L * (size_t)s.T));
+            out = (double*)ctx->od_out.p;
+            return TA_OK;
+        },
+        [&](const Slab& s) { return overlap_density_pm(ctx, s, K, L, C, out); }));
+    *d_out = out;
+    return TA_OK;
+}
+
 // The collective part (K, T) of a host (K, T, 2) density (ta_scatter_collective)
 int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int K, int64_t T, double* h_coll) {
     const size_t KT = (size_t)K * T;
@@ -4238,6 +4329,32 @@ int ta_overlap(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_cutoffs, co
 
 int ta_overlap_tile(int* slots) {
     if (slots) *slots = ta::overlap_slots();
+    return TA_OK;
+}
+
+int ta_overlap_density(ta_ctx* ctx, int n_k, const double* h_kvecs, int n_lags, const int64_t* h_lags, int n_cutoffs,
+                       const double* h_cutoffs, double* h_w) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(check_overlap_density(fail, ctx, n_k, h_kvecs, ctx->st_nslabs ? ctx->st_D : 0, n_lags, h_lags, n_cutoffs, h_cutoffs,
+                                   ctx->st_nslabs ? ctx->st_T : 0, h_w != nullptr));
+    TA_CHECK(check_staged(ctx));
+    if (ctx->is_cpu) {
+        TA_CHECK(check_cols(ctx, "overlap_density: ", ctx->st_A, ctx->st_D));
+        return cpu_rc(ctx, ta::cpu::overlap_density(cpu_state(ctx), n_k, h_kvecs, n_lags, h_lags, n_cutoffs, h_cutoffs, h_w));
+    }
+    double* d_out = nullptr;
+    TA_CHECK(ta::overlap_density_launch(ctx, n_k, h_kvecs, n_lags, h_lags, n_cutoffs, h_cutoffs, &d_out));
+    return host_finish(ctx, {{h_w, d_out, 2 * (size_t)n_k * (size_t)n_cutoffs * (size_t)n_lags * (size_t)ctx->st_T}});
+    });
+}
+
+int ta_overlap_density_tile(int* slots, int* kc, int* frames) {
+    int a = 0, b = 0, c = 0;
+    ta::overlap_density_tile(&a, &b, &c);
+    if (slots) *slots = a;
+    if (kc) *kc = b;
+    if (frames) *frames = c;
     return TA_OK;
 }
 

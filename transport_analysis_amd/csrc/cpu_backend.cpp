@@ -913,6 +913,100 @@ int overlap(const State& s, int L, const int64_t* lags, int C, const double* cut
     return s.dtype == TA_F32 ? overlap_e<float>(s, L, lags, C, cutoffs, q) : overlap_e<double>(s, L, lags, C, cutoffs, q);
 }
 
+// (cos, sin)(pi y), |y| <= 1, as sincospi gives it on the device to within an ulp: the half turns are folded away exactly
+// first (|y| = n / 2 + f, |f| <= 1 / 4), so the quarter turns come out as exact 0 and +-1
+inline void od_sincospi(double y, double* sn, double* cs) {
+    const double ay = std::fabs(y);
+    const double n = std::nearbyint(2.0 * ay);  // 0, 1 or 2
+    const double f = 3.141592653589793238463 * (ay - 0.5 * n);
+    const double sf = std::sin(f), cf = std::cos(f);
+    double s_, c_;
+    if (n == 0.0) s_ = sf, c_ = cf;
+    else if (n == 1.0) s_ = cf, c_ = -sf;
+    else s_ = -sf, c_ = -cf;
+    *sn = y < 0.0 ? -s_ : s_;
+    *cs = c_;
+}
+
+// The overlap field's density per origin.  As overlap_t: a thread that owns (l, t0) streams the two frames' atoms in atom
+// order and writes its K C sums -- no two threads share an element of w, and nothing depends on the thread count.  The
+// phase is phase_math.hpp's expression (q = k / 2 pi, u by product-then-fma, r = u - rint(u), sincospi(2 r)) of the ORIGIN
+// frame, r2 and a2 are vanhove_math.hpp's, the update is a select.  Wavevectors in blocks of kOdBlock keep the sums on the stack.
+constexpr int kOdBlock = 16;
+
+template <class E, int D>
+int overlap_density_t(const State& s, int K, const double* kvecs, int L, const int64_t* lags, int C, const double* cutoffs,
+                      double* w) {
+    const int64_t T = s.T, A = s.A;
+    const E* x = static_cast<const E*>(s.slabs[0]);
+    const int nth = s.threads > 0 ? s.threads : 1;
+    double a2[TA_OVERLAP_MAX_CUTOFFS];
+    vh_cutoffs2(C, cutoffs, a2);
+    std::vector<double> q;
+    try {
+        q.assign((size_t)K * 3, 0.0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    for (int j = 0; j < K; ++j)
+        for (int d = 0; d < D; ++d) q[(size_t)j * 3 + d] = kvecs[(size_t)j * D + d] / 6.283185307179586476925;
+    std::fill(w, w + 2 * (size_t)K * C * L * T, 0.0);
+    for (int j0 = 0; j0 < K; j0 += kOdBlock) {
+        const int kb = std::min(kOdBlock, K - j0);
+#pragma omp parallel for num_threads(nth) schedule(static) collapse(2)
+        for (int l = 0; l < L; ++l) {
+            for (int64_t t = 0; t < T; ++t) {
+                const int64_t tau = lags[l];
+                if (t + tau >= T) continue;
+                double re[kOdBlock][TA_OVERLAP_MAX_CUTOFFS] = {}, im[kOdBlock][TA_OVERLAP_MAX_CUTOFFS] = {};
+                const E* x0 = x + (size_t)t * A * D;
+                const E* x1 = x + (size_t)(t + tau) * A * D;
+                for (int64_t n = 0; n < A; ++n) {
+                    double a[3] = {0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
+                    for (int d = 0; d < D; ++d) {
+                        a[d] = (double)x0[n * D + d];
+                        b[d] = (double)x1[n * D + d];
+                    }
+                    const double r2 = vh_r2<D>(a, b);
+                    if (!(r2 < a2[C - 1])) continue;  // (the cutoffs increase: outside the largest is outside all)
+                    for (int jl = 0; jl < kb; ++jl) {
+                        const double* qj = q.data() + (size_t)(j0 + jl) * 3;
+                        double u = qj[0] * a[0];
+                        if (D > 1) u = std::fma(qj[1], a[1], u);
+                        if (D > 2) u = std::fma(qj[2], a[2], u);
+                        const double r = u - std::nearbyint(u);
+                        double sn, cs;
+                        od_sincospi(2.0 * r, &sn, &cs);
+                        for (int c = 0; c < C; ++c) {
+                            const bool inside = r2 < a2[c];
+                            re[jl][c] = inside ? re[jl][c] + cs : re[jl][c];
+                            im[jl][c] = inside ? im[jl][c] + sn : im[jl][c];
+                        }
+                    }
+                }
+                for (int jl = 0; jl < kb; ++jl)
+                    for (int c = 0; c < C; ++c) {
+                        double* o = w + ((((size_t)(j0 + jl) * C + c) * L + l) * T + t) * 2;
+                        o[0] = re[jl][c], o[1] = im[jl][c];
+                    }
+            }
+        }
+    }
+    return TA_OK;
+}
+
+template <class E>
+int overlap_density_e(const State& s, int K, const double* kvecs, int L, const int64_t* lags, int C, const double* cutoffs, double* w) {
+    if (s.D == 1) return overlap_density_t<E, 1>(s, K, kvecs, L, lags, C, cutoffs, w);
+    if (s.D == 2) return overlap_density_t<E, 2>(s, K, kvecs, L, lags, C, cutoffs, w);
+    return overlap_density_t<E, 3>(s, K, kvecs, L, lags, C, cutoffs, w);
+}
+
+int overlap_density(const State& s, int K, const double* kvecs, int L, const int64_t* lags, int C, const double* cutoffs, double* w) {
+    return s.dtype == TA_F32 ? overlap_density_e<float>(s, K, kvecs, L, lags, C, cutoffs, w)
+                             : overlap_density_e<double>(s, K, kvecs, L, lags, C, cutoffs, w);
+}
+
 // fn(E(), D, PERIODIC) as template arguments for the staged element type, dim and box
 #define TA_PAIR_DISPATCH(fn, ...)                                                                                  \
     do {                                                                                                           \

@@ -84,6 +84,10 @@ int vanhove(const State& s, int L, const int64_t* lags, int B, double dr, int64_
 // overlap.hip: q (C, L, T) int64, zeros at t0 >= T - lag.  OpenMP over the (lag, origin) pairs, each counted over all atoms by
 // one thread: no per-thread copies of q, and nothing depends on the number of threads.
 int overlap(const State& s, int L, const int64_t* lags, int C, const double* cutoffs, int64_t* q);
+// ta_overlap_density: the overlap field's density per origin of slab 0 for K wavevectors, L lags and C cutoffs, with the r2 and
+// a2 of ta_overlap and overlap_density.hip's phase expression of the origin frame: w (K, C, L, T, 2), +0.0 at t0 >= T - lag.
+// OpenMP over the (lag, origin) pairs, each a plain sum in atom order: nothing depends on the number of threads.
+int overlap_density(const State& s, int K, const double* kvecs, int L, const int64_t* lags, int C, const double* cutoffs, double* w);
 // ta_vanhove_distinct: the distinct van Hove histogram of slab 0 with vanhove_distinct_math.hpp's arithmetic, as
 // vanhove_distinct.hip: counts (L, B + 1) int64 over the ordered pairs (ida[p], idb[q]), ida[p] != idb[q], of the origins
 // t = stride o and the lags with t + lag < n_frames (OpenMP over (origin, a-tile), a histogram per thread, added at the end).

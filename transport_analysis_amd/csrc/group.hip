@@ -794,6 +794,23 @@ int ta_group_overlap(ta_group* g, int n_lags, const int64_t* h_lags, int n_cutof
     });
 }
 
+// Overlap field's density per origin: every member's W of its atoms for the same wavevectors, lags and cutoffs, added on the
+// host in member order as float64 (W adds up over atoms; |W|^2 and a variance over origins are the caller's, after this sum)
+int ta_group_overlap_density(ta_group* g, int n_k, const double* h_kvecs, int n_lags, const int64_t* h_lags, int n_cutoffs,
+                             const double* h_cutoffs, double* h_w) {
+    return group_call(g, [&]() -> int {
+    TAG_CHECK(check_group(g));
+    TAG_CHECK(check_overlap_density(gfail, g, n_k, h_kvecs, g->T ? g->D : 0, n_lags, h_lags, n_cutoffs, h_cutoffs, g->T, h_w != nullptr));
+    TAG_CHECK(check_staged(g));
+    const size_t nw = 2 * (size_t)n_k * (size_t)n_cutoffs * (size_t)n_lags * (size_t)g->T;
+    std::vector<int> who;
+    TAG_CHECK(sum_members(g, who, "overlap densities", {{0, nw, h_w}}, [&](int i, double** d) {
+        return overlap_density_launch(g->ctx[i], n_k, h_kvecs, n_lags, h_lags, n_cutoffs, h_cutoffs, d);
+    }));
+    return TA_OK;
+    });
+}
+
 // Unwrap: every member's block of slab `slab` with the same box table, queued on all devices, then waited for
 int ta_group_unwrap(ta_group* g, int slab, const double* h_dimensions, const int* axes) {
     return group_call(g, [&]() -> int {

@@ -26,13 +26,6 @@ namespace {
 constexpr int kOvSlots = 8;
 static_assert(kOvSlots >= TA_OVERLAP_MAX_CUTOFFS, "one lag's cutoffs share a launch");
 
-// r2 of one pair, NaN (which no cutoff counts) for a pair whose lagged frame is at or past T
-template <int D>
-__device__ __forceinline__ double ov_r2(bool live, const double (&x0)[3], const double (&x1)[3]) {
-    const double r2 = vh_r2<D>(x0, x1);
-    return live ? r2 : __builtin_nan("");
-}
-
 // Workgroup (bx, g) as k_vanhove's: origin frames [1024 bx, 1024 bx + 1024), atoms g, g + G, ... (G = gridDim.y); the atom's
 // columns at the thread's kPmFrames origin frames stay in registers across the launch's lags, and the lagged rows are read
 // as k_vanhove reads them, by pm_lagged (pm_read.hpp; a pair with t + tau >= T reads row 0 and counts nothing).

@@ -2,7 +2,7 @@
 //   pm_frame                      every kernel that walks frames: k_species_sum (species_sum.hip) and all of the following
 //   PmAtom, pm_load               k_species_sort (species_self.hip), k_compound (compound.hip), k_phase (scatter.hip), k_kcurrent
 //                                 (kcurrent.hip, PmAtom::load), k_orient (orient.hip), k_vanhove (vanhove.hip), k_overlap (overlap.hip)
-//   pm_lagged                     k_vanhove, k_overlap: row t + tau of the same atom
+//   pm_lagged                     k_vanhove, k_overlap, k_overlap_density (overlap_density.hip): row t + tau of the same atom
 //   PmAtom::row                   pm_lagged's odd float32 lag and float64 rows, k_vhd_gather (vanhove_distinct.hip)
 //   pm_store_row                  k_species_sort, k_compound, k_orient
 //   pm_unit_grid                  the launchers of the kernels that walk units
@@ -81,12 +81,14 @@ struct PmAtom {
     }
 };
 
-// The D columns of one atom in the thread's frames ...
-template <class E, int D>
-__device__ __forceinline__ void pm_load(const PmAtom<E, D>& a, long T, long tb, double (&col)[kPmFrames][3]) {
+// The D columns of one atom in the thread's F frames (kPmFrames, or the 2 of k_overlap_density: a workgroup then starts at
+// a multiple of 256 F) ...
+template <class E, int D, int F = kPmFrames>
+__device__ __forceinline__ void pm_load(const PmAtom<E, D>& a, long T, long tb, double (&col)[F][3]) {
     constexpr bool kF32 = PmAtom<E, D>::kF32;
+    static_assert(F % 2 == 0, "a float32 load is two frames");
 #pragma unroll
-    for (int f = 0; f < kPmFrames; f += kF32 ? 2 : 1) {
+    for (int f = 0; f < F; f += kF32 ? 2 : 1) {
         const long t = pm_frame<kF32>(tb, f);  // (float32: even)
         a.load(t < T ? (kF32 ? t / 2 : t) : 0, col[f], col[kF32 ? f + 1 : f]);
     }
@@ -98,17 +100,18 @@ __device__ __forceinline__ void pm_load0(const PmAtom<E, D>& a, double (&col0)[3
     a.load(0, col0, unused);
 }
 
-// Row t + tau of the same atom for the thread's kPmFrames origin frames t = pm_frame(tb, f): fn(f, live, row) per frame, in
+// Row t + tau of the same atom for the thread's F (default kPmFrames) origin frames t = pm_frame(tb, f): fn(f, live, row) per frame, in
 // frame order.  A float64 row is one 16-byte load at any t; two float32 rows share a 16-byte load when tau is even (origin
 // frames 2 m, 2 m + 1 -> rows 2 m + tau, 2 m + tau + 1), an odd tau takes 8-byte loads.  A row at or past T reads row 0 and is
 // not live: nothing is read at or past row T, but the second half of a float32 load at row T - 1 of an odd T, which lies
 // inside the pitch.
-template <class E, int D, class Fn>
+template <int F = kPmFrames, class E, int D, class Fn>
 __device__ __forceinline__ void pm_lagged(const PmAtom<E, D>& a, long T, long tb, long tau, Fn&& fn) {
     constexpr bool kF32 = PmAtom<E, D>::kF32;
+    static_assert(F % 2 == 0, "a float32 load is two frames");
     if (kF32 && (tau & 1) == 0) {
 #pragma unroll
-        for (int f = 0; f < kPmFrames; f += 2) {
+        for (int f = 0; f < F; f += 2) {
             const long t2 = pm_frame<kF32>(tb, f) + tau;  // (even)
             double lo[3], hi[3];
             a.load(t2 < T ? t2 / 2 : 0, lo, hi);
@@ -117,7 +120,7 @@ __device__ __forceinline__ void pm_lagged(const PmAtom<E, D>& a, long T, long tb
         }
     } else {
 #pragma unroll
-        for (int f = 0; f < kPmFrames; ++f) {
+        for (int f = 0; f < F; ++f) {
             const long t2 = pm_frame<kF32>(tb, f) + tau;
             double lo[3];
             a.row(t2 < T ? t2 : 0, lo);

@@ -211,11 +211,11 @@ static int check_vanhove(Fail fail, Owner* owner, int n_lags, const int64_t* h_l
 // valid after host_wait
 int vanhove_launch(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, double dr, bool counts, bool moments, void** d_out);
 // the argument checks of ta_overlap* (context or group: the same messages for both), all of them before anything is written.
-// T: the frames (0: not known, nothing staged -- the caller reports that next)
+// T: the frames (0: not known, nothing staged -- the caller reports that next).  check_overlap_lists: the lags, the cutoffs and
+// the output under the family's message prefix `p`, shared with ta_overlap_density*
 template <class Fail, class Owner>
-static int check_overlap(Fail fail, Owner* owner, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs,
-                         int64_t T, bool any_output) {
-    const std::string p = "overlap: ";
+static int check_overlap_lists(Fail fail, Owner* owner, const std::string& p, int n_lags, const int64_t* h_lags, int n_cutoffs,
+                               const double* h_cutoffs, int64_t T, bool any_output) {
     if (!h_lags) return fail(owner, TA_E_INVALID, p + "lags are NULL");
     if (n_lags < 1 || n_lags > TA_VANHOVE_MAX_LAGS)
         return fail(owner, TA_E_INVALID, p + "n_lags must be 1 ... " + std::to_string(TA_VANHOVE_MAX_LAGS));
@@ -228,12 +228,42 @@ static int check_overlap(Fail fail, Owner* owner, int n_lags, const int64_t* h_l
         if (c && !(a > h_cutoffs[c - 1])) return fail(owner, TA_E_INVALID, p + "the cutoffs must be strictly increasing");
     }
     if (!any_output) return fail(owner, TA_E_INVALID, p + "the output is NULL");
-    if (const int rc = check_vanhove_lags(fail, owner, p, n_lags, h_lags, T)) return rc;
+    return check_vanhove_lags(fail, owner, p, n_lags, h_lags, T);
+}
+template <class Fail, class Owner>
+static int check_overlap(Fail fail, Owner* owner, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs,
+                         int64_t T, bool any_output) {
+    const std::string p = "overlap: ";
+    if (const int rc = check_overlap_lists(fail, owner, p, n_lags, h_lags, n_cutoffs, h_cutoffs, T, any_output)) return rc;
     if ((int64_t)n_cutoffs * n_lags * T > (int64_t)1 << 27)
         return fail(owner, TA_E_INVALID, p + "n_cutoffs * n_lags * n_frames = " + std::to_string((int64_t)n_cutoffs * n_lags * T) +
                                              " exceeds 2^27 (1 GiB of output): fewer lags or cutoffs per call");
     return TA_OK;
 }
+// the argument checks of ta_overlap_density* (context or group: the same messages for both), all of them before anything is
+// allocated or written: the wavevectors as ta_partial_density's, then ta_overlap's lists under this family's prefix, the
+// output and its size.  T, D: the frames and the components per wavevector (0: not known, nothing staged -- the caller
+// reports that next)
+template <class Fail, class Owner>
+static int check_overlap_density(Fail fail, Owner* owner, int n_k, const double* h_kvecs, int D, int n_lags, const int64_t* h_lags,
+                                 int n_cutoffs, const double* h_cutoffs, int64_t T, bool any_output) {
+    const std::string p = "overlap_density: ";
+    if (!h_kvecs) return fail(owner, TA_E_INVALID, p + "wavevectors are NULL");
+    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(owner, TA_E_INVALID, p + "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
+    for (int64_t i = 0; i < (int64_t)n_k * D; ++i)
+        if (!(h_kvecs[i] - h_kvecs[i] == 0.0))
+            return fail(owner, TA_E_INVALID, p + "wavevector " + std::to_string(i / D) + " has a non-finite component");
+    if (const int rc = check_overlap_lists(fail, owner, p, n_lags, h_lags, n_cutoffs, h_cutoffs, T, any_output)) return rc;
+    const int64_t n_out = (int64_t)n_k * n_cutoffs * n_lags * T;  // (<= 2^12 2^2 2^10 T)
+    if (n_out > (int64_t)1 << 26)
+        return fail(owner, TA_E_INVALID, p + "n_k * n_cutoffs * n_lags * n_frames = " + std::to_string(n_out) +
+                                             " exceeds 2^26 (1 GiB of output): fewer wavevectors, lags or cutoffs per call");
+    return TA_OK;
+}
+// api.hip, for group.hip: one context's ta_overlap_density share (its staged slab 0, the call's wavevectors, lags and
+// cutoffs, checked by the caller), queued: *d_out = W (n_k, n_cutoffs, n_lags, n_frames, 2), valid after host_wait
+int overlap_density_launch(ta_ctx* ctx, int n_k, const double* h_kvecs, int n_lags, const int64_t* h_lags, int n_cutoffs,
+                           const double* h_cutoffs, double** d_out);
 // api.hip, for group.hip: one context's ta_overlap share (its staged slab 0, the call's lags and cutoffs, checked by the
 // caller), queued: *d_out = Q (n_cutoffs, n_lags, n_frames) int64, valid after host_wait
 int overlap_launch(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs, int64_t** d_out);
@@ -439,6 +469,20 @@ hipError_t launch_vanhove(int n_cu, const void* x, bool f32, long pitch, long T,
 int overlap_slots();
 hipError_t launch_overlap(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, const int64_t* lags, int l0,
                           int Lc, int L, const double* a2, int C, unsigned long long* q, hipStream_t st);
+
+// overlap_density.hip: the overlap field's density per origin of a pair-major slab of float64 or (f32) float32 elements, read
+// as it is, for the lags [l0, l0 + Lc) of L (device array `lags`), C cutoffs with squared values a2 (device) and kc <= KC
+// wavevectors q (kc, D) (device, turns per length unit): partial [n_parts][kc][Lc C][T] (re, im) sums over the atoms g, g +
+// n_parts, ... (written in full; n_parts from overlap_density_parts, which depends on the slab and the device only).
+// sum: w[jl, c, l, t] (the launch's corner of W (K, C, L, T, 2)) = the parts added in k_sum_partials' order.
+// overlap_density_tile: the (lag, cutoff) slots SL, the wavevectors KC and the frames per thread of the one tile.
+void overlap_density_tile(int* slots, int* kc, int* frames);
+int overlap_density_parts(int n_cu, long pitch, long n_atoms, size_t budget);
+hipError_t launch_overlap_density(const void* x, bool f32, long pitch, long T, long n_atoms, int D, const int64_t* lags, int l0,
+                                  int Lc, int L, const double* a2, int C, const double* q, int kc, double* partial, int n_parts,
+                                  hipStream_t st);
+hipError_t launch_overlap_density_sum(const double* partial, int n_parts, long T, int Lc, int C, int L, int kc, double* w,
+                                      hipStream_t st);
 
 // vanhove_distinct.hip: the distinct van Hove histogram in two passes.  The item pitches of the scratch and of the padded
 // index lists (ids; -1: padding) are multiples of the pair kernel's tiles.  n_orig = ceil(T / stride): the origins of lag 0,

@@ -44,6 +44,14 @@ TA_VH_HD double vh_r2(const double (&a)[3], const double (&b)[3]) {
     return r2;
 }
 
+// r2 of one pair as k_overlap (overlap.hip) and k_overlap_density (overlap_density.hip) take it: NaN (which no cutoff counts)
+// for a pair whose lagged frame is at or past T
+template <int D>
+TA_VH_HD double ov_r2(bool live, const double (&x0)[3], const double (&x1)[3]) {
+    const double r2 = vh_r2<D>(x0, x1);
+    return live ? r2 : __builtin_nan("");
+}
+
 // A float32 guess (r2 >= 0, so it is >= 0; capped at B, which a NaN becomes too), stepped down and up against the table:
 // the result is the bin of the definition whatever the guess was.  A NaN r2 compares false both ways from B: the overflow bin.
 TA_VH_HD int vh_bin(double r2, const double* e, int B, float inv_dr) {
