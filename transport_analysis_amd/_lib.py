@@ -1025,27 +1025,34 @@ class Context(_Staged):
         n_frames - tau; runs (n_frames + 1,) int64 = the histogram of the lengths of the runs of bonded frames; nb
         (n_frames,) = the bonded pairs per frame), None for one not asked for.  One context only: a device group has no
         such call."""
-        return self._life("pair_lifetime", self._pair_args, (fft, pairs, r_cut, dimensions, axes), ci, runs, nb)
+        return self._life("pair_lifetime", self._life_outs(ci, runs, nb), self._pair_args(fft, pairs, r_cut, dimensions, axes))
 
     def pair_lifetime_staged(self, fft, r_cut, pairs=None, *, dimensions=None, axes=None, d_ci=0, d_runs=0, d_nb=0, stream=0):
         """`pairs`, `dimensions`: HOST arrays (checked by the library before anything is written); d_ci (n_frames,), d_runs
         (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
-        self._life_staged("pair_lifetime_staged", self._pair_args(fft, pairs, r_cut, dimensions, axes), d_ci, d_runs, d_nb, stream)
+        self._life_staged("pair_lifetime_staged", self._pair_args(fft, pairs, r_cut, dimensions, axes), (d_ci, d_runs, d_nb), stream)
 
-    def _life(self, name, make_args, given, ci, runs, nb):
-        """what pair_lifetime and bond_lifetime share: the outputs asked for allocated, the call, (ci, runs, nb)"""
+    def _life_outs(self, ci, runs, nb):
+        """the outputs (asked for, shape, dtype) of the three-output calls"""
         T = self._staged_shape()[0]
-        args, keep = make_args(*given)
-        o_ci = np.empty(T, dtype=np.float64) if ci else None
-        o_runs = np.empty(T + 1, dtype=np.int64) if runs else None
-        o_nb = np.empty(T, dtype=np.float64) if nb else None
-        self._call(name, *args, _ptr(o_ci), _ptr(o_runs), _ptr(o_nb))
-        del keep
-        return o_ci, o_runs, o_nb
+        return (ci, T, np.float64), (runs, T + 1, np.int64), (nb, T, np.float64)
 
-    def _life_staged(self, name, args_keep, d_ci, d_runs, d_nb, stream):
+    def _gated_outs(self, max_lag, n_sums, sums, count, runs, nb):
+        """the outputs (asked for, shape, dtype) of shell_msd and shell_orient: n_sums sums per lag"""
+        L = max(int(max_lag), 0)
+        return ((sums, (L + 1, n_sums), np.float64), (count, L + 1, np.int64)) + self._life_outs(False, runs, nb)[1:]
+
+    def _life(self, name, outs, args_keep):
+        """what the pair, bond and shell calls share: the outputs asked for allocated, the call, the tuple of them"""
         args, keep = args_keep
-        self._call(name, *args, d_ci or None, d_runs or None, d_nb or None, stream or None)
+        res = tuple(np.empty(shape, dtype=dtype) if want else None for want, shape, dtype in outs)
+        self._call(name, *args, *(_ptr(o) for o in res))
+        del keep
+        return res
+
+    def _life_staged(self, name, args_keep, d_outs, stream):
+        args, keep = args_keep
+        self._call(name, *args, *(d or None for d in d_outs), stream or None)
         del keep
 
     def _bond_args(self, fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes):
@@ -1068,14 +1075,15 @@ class Context(_Staged):
         hydrogen, acceptor) of staged item ids; a bond forms below `r_cut` with (triplets) the cosine of the D-H-A angle at most
         `cos_cut`, lasts while below `r_break` / `cos_break` (None: the form values), and absences of up to `gap` frames (0 ...
         63) between bonded frames are filled.  One context only: a device group has no such call."""
-        return self._life("bond_lifetime", self._bond_args, (fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes), ci, runs, nb)
+        return self._life("bond_lifetime", self._life_outs(ci, runs, nb),
+                          self._bond_args(fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes))
 
     def bond_lifetime_staged(self, fft, atoms, r_cut, *, r_break=None, cos_cut=0.0, cos_break=None, gap=0, dimensions=None, axes=None,
                              d_ci=0, d_runs=0, d_nb=0, stream=0):
         """`atoms`, `dimensions`: HOST arrays (checked by the library before anything is written); d_ci (n_frames,), d_runs
         (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
         self._life_staged("bond_lifetime_staged", self._bond_args(fft, atoms, r_cut, r_break, cos_cut, cos_break, gap, dimensions, axes),
-                          d_ci, d_runs, d_nb, stream)
+                          (d_ci, d_runs, d_nb), stream)
 
     def _shell_args(self, fft, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes):
         """the argument tuple ta_shell_residence* share, and the arrays it points into (to be kept until the call is over)"""
@@ -1091,14 +1099,15 @@ class Context(_Staged):
         closer than `r_cut`, stays inside while some is closer than `r_break` (None: r_cut), and absences of up to `gap` frames
         (0 ... 63) between frames inside are filled.  The lists: strictly increasing item indices, the same list or disjoint
         ones.  One context only: a device group has no such call."""
-        return self._life("shell_residence", self._shell_args, (fft, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes), ci, runs, nb)
+        return self._life("shell_residence", self._life_outs(ci, runs, nb),
+                          self._shell_args(fft, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes))
 
     def shell_residence_staged(self, fft, r_cut, *, r_break=None, gap=0, idx_a=None, idx_b=None, dimensions=None, axes=None,
                                d_ci=0, d_runs=0, d_nb=0, stream=0):
         """the lists and `dimensions`: HOST arrays (checked by the library before anything is written); d_ci (n_frames,), d_runs
         (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
         self._life_staged("shell_residence_staged", self._shell_args(fft, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes),
-                          d_ci, d_runs, d_nb, stream)
+                          (d_ci, d_runs, d_nb), stream)
 
     def _shell_msd_args(self, condition, max_lag, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes):
         """the argument tuple ta_shell_msd* share, and the arrays it points into (to be kept until the call is over)"""
@@ -1115,24 +1124,16 @@ class Context(_Staged):
         of the reference items `idx_a` under `condition`: "continuous" (inside in every frame from the origin to the lag) or
         "endpoints" (inside at both ends); the shell, `runs` and `nb` as shell_residence's.  The positions must be unwrapped.
         One context only: a device group has no such call."""
-        T, _, D = self._staged_shape()
-        args, keep = self._shell_msd_args(condition, max_lag, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
-        L = max(int(max_lag), 0)
-        o_sums = np.empty((L + 1, D), dtype=np.float64) if sums else None
-        o_count = np.empty(L + 1, dtype=np.int64) if count else None
-        o_runs = np.empty(T + 1, dtype=np.int64) if runs else None
-        o_nb = np.empty(T, dtype=np.float64) if nb else None
-        self._call("shell_msd", *args, _ptr(o_sums), _ptr(o_count), _ptr(o_runs), _ptr(o_nb))
-        del keep
-        return o_sums, o_count, o_runs, o_nb
+        D = self._staged_shape()[2]
+        args_keep = self._shell_msd_args(condition, max_lag, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
+        return self._life("shell_msd", self._gated_outs(max_lag, D, sums, count, runs, nb), args_keep)
 
     def shell_msd_staged(self, condition, max_lag, r_cut, *, r_break=None, gap=0, idx_a=None, idx_b=None, dimensions=None,
                          axes=None, d_sums=0, d_count=0, d_runs=0, d_nb=0, stream=0):
         """the lists and `dimensions`: HOST arrays (checked by the library before anything is written); d_sums (max_lag + 1,
         dim), d_count (max_lag + 1,) int64, d_runs (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
-        args, keep = self._shell_msd_args(condition, max_lag, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
-        self._call("shell_msd_staged", *args, d_sums or None, d_count or None, d_runs or None, d_nb or None, stream or None)
-        del keep
+        self._life_staged("shell_msd_staged", self._shell_msd_args(condition, max_lag, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes),
+                          (d_sums, d_count, d_runs, d_nb), stream)
 
     def _shell_orient_args(self, condition, max_lag, index, mode, anchor, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes):
         """the argument tuple ta_shell_orient* share, and the arrays it points into (to be kept until the call is over)"""
@@ -1151,24 +1152,17 @@ class Context(_Staged):
         by the shell series of its anchor atom, column `anchor` of its row; `idx_b` must list the anchors row by row (None:
         the anchors are the reference list `idx_a` itself).  `dimensions` serves the distance pass and the vectors' image
         step.  One context only: a device group has no such call."""
-        T = self._staged_shape()[0]
-        args, keep = self._shell_orient_args(condition, max_lag, index, mode, anchor, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
-        L = max(int(max_lag), 0)
-        o_sums = np.empty((L + 1, 2), dtype=np.float64) if sums else None
-        o_count = np.empty(L + 1, dtype=np.int64) if count else None
-        o_runs = np.empty(T + 1, dtype=np.int64) if runs else None
-        o_nb = np.empty(T, dtype=np.float64) if nb else None
-        self._call("shell_orient", *args, _ptr(o_sums), _ptr(o_count), _ptr(o_runs), _ptr(o_nb))
-        del keep
-        return o_sums, o_count, o_runs, o_nb
+        self._staged_shape()  # (nothing staged is reported before anything about the arguments)
+        args_keep = self._shell_orient_args(condition, max_lag, index, mode, anchor, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
+        return self._life("shell_orient", self._gated_outs(max_lag, 2, sums, count, runs, nb), args_keep)
 
     def shell_orient_staged(self, condition, max_lag, index, mode, r_cut, *, anchor=0, r_break=None, gap=0, idx_a=None, idx_b=None,
                             dimensions=None, axes=None, d_sums=0, d_count=0, d_runs=0, d_nb=0, stream=0):
         """`index`, the lists and `dimensions`: HOST arrays (checked by the library before anything is written); d_sums
         (max_lag + 1, 2), d_count (max_lag + 1,) int64, d_runs (n_frames + 1,) int64, d_nb (n_frames,) on the device"""
-        args, keep = self._shell_orient_args(condition, max_lag, index, mode, anchor, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes)
-        self._call("shell_orient_staged", *args, d_sums or None, d_count or None, d_runs or None, d_nb or None, stream or None)
-        del keep
+        self._life_staged("shell_orient_staged",
+                          self._shell_orient_args(condition, max_lag, index, mode, anchor, r_cut, r_break, gap, idx_a, idx_b, dimensions, axes),
+                          (d_sums, d_count, d_runs, d_nb), stream)
 
     def _orient_args(self, fft, index, mode, dimensions, weights):
         """the argument tuple ta_orient* share, and the arrays it points into (to be kept until the call is over)"""

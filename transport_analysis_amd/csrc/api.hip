@@ -2071,6 +2071,46 @@ int pair_find_launch(ta_ctx* ctx, const PairFindPlan& p) {
         [&](const Slab& s) { return pair_find_pm(ctx, s, p); });
 }
 
+// The outputs of a lifetime or shell call as the caller gave them, on the device (the staged entries) or on the host: lags is
+// ci of the three-output calls and sums of the gated ones (ta_shell_msd*, ta_shell_orient*), which alone have count.  NULL:
+// not asked for.
+struct LifePtrs {
+    double* lags;
+    int64_t* count;
+    int64_t* runs;
+    double* nb;
+    bool any() const { return lags || count || runs || nb; }
+};
+// Where a host-facing call's results lie in ctx->pair_out, in 8-byte elements (int64 counts travel as doubles): segment i
+// is [off[i], off[i + 1]), in LifePtrs' order.  ci (T) | runs (T + 1) | nb (T) of the three-output calls (n_sums 0: no
+// count), sums ((L + 1) n_sums) | count (L + 1) | runs | nb of the gated ones.
+struct LifeOut {
+    size_t off[5] = {};
+    // the device outputs of those asked for in `want`, in the buffer at `base`
+    LifePtrs at(double* base, const LifePtrs& want) const {
+        return {want.lags ? base + off[0] : nullptr, want.count ? (int64_t*)(base + off[1]) : nullptr,
+                want.runs ? (int64_t*)(base + off[2]) : nullptr, want.nb ? base + off[3] : nullptr};
+    }
+};
+LifeOut life_out(int64_t T, int64_t L = 0, int n_sums = 0) {
+    const size_t len[4] = {n_sums ? (size_t)(L + 1) * (size_t)n_sums : (size_t)T, n_sums ? (size_t)L + 1 : 0, (size_t)T + 1, (size_t)T};
+    LifeOut o;
+    for (int i = 0; i < 4; ++i) o.off[i + 1] = o.off[i] + len[i];
+    return o;
+}
+// the context's output buffer for a host-facing call (before the call is opened)
+int life_out_buffer(ta_ctx* ctx, const LifeOut& o, double** out) {
+    TA_CHECK(ensure(ctx, ctx->pair_out, sizeof(double) * o.off[4]));
+    *out = (double*)ctx->pair_out.p;
+    return TA_OK;
+}
+// the tail of a host-facing call: the results at d_out copied into those of `h` asked for
+int life_finish(ta_ctx* ctx, const LifeOut& o, const LifePtrs& h, const double* d_out) {
+    double* const dst[4] = {h.lags, (double*)h.count, (double*)h.runs, h.nb};
+    auto seg = [&](int i) { return HostCopy{dst[i], d_out + o.off[i], o.off[i + 1] - o.off[i]}; };
+    return host_finish(ctx, {seg(0), seg(1), seg(2), seg(3)});
+}
+
 // What ta_bond_lifetime* add to a lifetime call: items per row, the break criterion, the gap tolerance
 struct BondArgs {
     int n_at;
@@ -2090,7 +2130,7 @@ struct PairLifePlan {
     ta::BondCuts cuts{};
     // the level block needs k_pair_filter: a gap to close, or a break criterion apart from the form criterion
     bool filter() const { return gap > 0 || cuts.rb2 != cuts.rc2 || (n_at == 3 && cuts.cb2 != cuts.c2); }
-    size_t list_doubles() const { return h_pairs ? ((size_t)n_at * (size_t)P + 1) / 2 : 0; }  // the int32 rows in the table
+    LifeOut out;
 };
 int bond_rows(ta_ctx* ctx, const std::string& who, int64_t n_bonds, int n_at, const int32_t* h_atoms, int64_t A) {
     if (n_bonds < 1 || n_bonds >= (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, who + "n_bonds must be 1 ... 2^30 - 1");
@@ -2155,6 +2195,7 @@ int pair_life_plan(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs
         if (ctx->pair_n == 0) return fail(ctx, TA_E_STATE, who + "the found pair list is empty");
         p->P = ctx->pair_n;
     }
+    p->out = life_out(T);
     if (!h_dims) return TA_OK;
     TA_CHECK(image_box(ctx, who, h_dims, axes, T, ctx->st_D, &p->box));
     return half_box(ctx, who, bond ? "r_break" : "r_cut", bond ? bond->r_break : r_cut, p->box, ctx->st_D, 1);
@@ -2164,6 +2205,17 @@ int pair_life_plan(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs
 int64_t pair_block(const ta_ctx* ctx, int64_t P, int64_t pitch) {
     const int64_t fit = std::max<int64_t>(2, 2 * (int64_t)(kPairBudget / ((size_t)pitch * 16)));
     return std::min<int64_t>(P, ctx->opt_pair_chunk > 0 ? ctx->opt_pair_chunk : fit);
+}
+// The table of a lifetime call, hm | pairs (the int32 rows of an explicit list) | Pc zero labels: the pairs per block, where
+// the parts begin and the whole, in doubles
+struct PairTab {
+    int64_t Pc;
+    size_t pairs, lab, n;
+};
+PairTab pair_tab_layout(const ta_ctx* ctx, const PairLifePlan& p, int64_t pitch) {
+    const int64_t Pc = pair_block(ctx, p.P, pitch);
+    const size_t pairs = p.box.hm.size(), lab = pairs + (p.h_pairs ? ((size_t)p.n_at * (size_t)p.P + 1) / 2 : 0);
+    return {Pc, pairs, lab, lab + ((size_t)Pc + 1) / 2};
 }
 
 // One lifetime call on the staged position slab of either element type, read as it is (the caller has opened the call's
@@ -2227,16 +2279,17 @@ int life_sums_end(ta_ctx* ctx, const LifeSums& s) {
     return call_end(ctx, st);
 }
 
-int pair_life_pm(ta_ctx* ctx, bool fft, const Slab& slab, const PairLifePlan& p, double* d_ci, int64_t* d_runs, double* d_nb) {
+int pair_life_pm(ta_ctx* ctx, bool fft, const Slab& slab, const PairLifePlan& p, const LifePtrs& d) {
     hipStream_t st = slab.st;
     const int64_t T = slab.T, pitch = slab.pitch, P = p.P;
-    const int64_t Pc = pair_block(ctx, P, pitch);
+    const PairTab t = pair_tab_layout(ctx, p, pitch);
+    const int64_t Pc = t.Pc;
     const double* tab = (const double*)ctx->pair_tab.dev.p;
     const double* hm = p.box.n_box ? tab : nullptr;
-    const int* pairs = p.h_pairs ? (const int*)(tab + p.box.hm.size()) : (const int*)ctx->pair_list.p;
-    const int* lab = (const int*)(tab + p.box.hm.size() + p.list_doubles());
+    const int* pairs = p.h_pairs ? (const int*)(tab + t.pairs) : (const int*)ctx->pair_list.p;
+    const int* lab = (const int*)(tab + t.lab);
     LifeSums s;
-    TA_CHECK(life_sums_begin(ctx, fft, slab, P, Pc, d_ci, d_runs, d_nb, &s));
+    TA_CHECK(life_sums_begin(ctx, fft, slab, P, Pc, d.lags, d.runs, d.nb, &s));
     for (int64_t b = 0; b < s.n_blocks; ++b) {
         const int64_t p0 = b * Pc, pb = std::min(Pc, P - p0);
         if (p.bond)
@@ -2252,35 +2305,29 @@ int pair_life_pm(ta_ctx* ctx, bool fft, const Slab& slab, const PairLifePlan& p,
     return life_sums_end(ctx, s);
 }
 
-// ta_pair_lifetime_staged and the device half of ta_pair_lifetime (out != NULL: the context's own output buffer ci (T) |
-// runs (T + 1) | nb (T) takes the place of the d_* pointers, which then only say what is asked for)
-int pair_life_launch(ta_ctx* ctx, int fft, const PairLifePlan& p, double* d_ci, int64_t* d_runs, double* d_nb, void* stream, double** out) {
+// ta_pair_lifetime_staged and the device half of ta_pair_lifetime (out != NULL: the context's own output buffer, laid out by
+// p.out, takes the place of the pointers of d, which then only say what is asked for)
+int pair_life_launch(ta_ctx* ctx, int fft, const PairLifePlan& p, const LifePtrs& d, void* stream, double** out) {
     return slab_entry(
         ctx, nullptr, stream, no_args,
         [&](const Slab& s) -> int {
-            const int64_t Pc = pair_block(ctx, p.P, s.pitch);
-            const size_t n = p.box.hm.size() + p.list_doubles() + ((size_t)Pc + 1) / 2;
+            const PairTab t = pair_tab_layout(ctx, p, s.pitch);
             double* h = nullptr;
-            TA_CHECK(ctx->pair_tab.begin(ctx, sizeof(double) * n, (void**)&h));
-            memset(h, 0, sizeof(double) * n);
+            TA_CHECK(ctx->pair_tab.begin(ctx, sizeof(double) * t.n, (void**)&h));
+            memset(h, 0, sizeof(double) * t.n);
             if (!p.box.hm.empty()) memcpy(h, p.box.hm.data(), sizeof(double) * p.box.hm.size());
-            if (p.h_pairs) memcpy(h + p.box.hm.size(), p.h_pairs, sizeof(int32_t) * (size_t)p.n_at * (size_t)p.P);
-            if (out) {
-                TA_CHECK(ensure(ctx, ctx->pair_out, sizeof(double) * (3 * (size_t)s.T + 1)));
-                *out = (double*)ctx->pair_out.p;
-            }
+            if (p.h_pairs) memcpy(h + t.pairs, p.h_pairs, sizeof(int32_t) * (size_t)p.n_at * (size_t)p.P);
+            if (out) TA_CHECK(life_out_buffer(ctx, p.out, out));
             return ctx->pair_tab.send(ctx, s.st);
         },
-        [&](const Slab& s) {
-            if (!out) return pair_life_pm(ctx, fft != 0, s, p, d_ci, d_runs, d_nb);
-            double* o = *out;
-            return pair_life_pm(ctx, fft != 0, s, p, d_ci ? o : nullptr, d_runs ? (int64_t*)(o + s.T) : nullptr,
-                                d_nb ? o + 2 * s.T + 1 : nullptr);
-        });
+        [&](const Slab& s) { return pair_life_pm(ctx, fft != 0, s, p, out ? p.out.at(*out, d) : d); });
 }
 
 // ---- shell residence times: the level of an observed item against a group of reference items (shell.hip) ------------
-// The caller's arguments of ta_shell_residence*, as they came
+// The three kinds of call: the residence sums alone (ta_shell_residence*), or in ci's place the gated sums over the lags
+// 0 ... max_lag of squared displacements (ta_shell_msd*) or of the unit vectors' products (ta_shell_orient*)
+enum ShellKind { SHELL_RESIDENCE, SHELL_MSD, SHELL_ORIENT };
+// The caller's arguments, as they came; behind gap those of the gated kinds, and behind max_lag those of ta_shell_orient* alone
 struct ShellArgs {
     int64_t n_a, n_b;
     const int64_t *h_idx_a, *h_idx_b;
@@ -2288,22 +2335,51 @@ struct ShellArgs {
     const int* axes;
     double r_cut, r_break;
     int gap;
+    int condition = 0;
+    int64_t max_lag = 0;
+    int mode = 0, anchor = 0;
+    const int32_t* h_index = nullptr;
 };
 // The host side of one call (both kinds of context): a = the reference items, b = the observed ones, one series per b-item.
 // The b list carries one more tile of padding than item_lists gives it: a block of observed items is read from its first
-// item on, a whole number of tiles long.
+// item on, a whole number of tiles long.  n_sums: the gated sums per lag (0: SHELL_RESIDENCE, D: SHELL_MSD, 2:
+// SHELL_ORIENT); row_len: the atoms per index row of h_index, one row per observed item (0 but for SHELL_ORIENT).
 struct ShellPlan : ItemLists {
+    ShellKind kind = SHELL_RESIDENCE;
     int D = 0, gap = 0;
     int64_t T = 0, A = 0;
     ta::BondCuts cuts{};
     PairBox box;
+    int condition = 0, n_sums = 0, mode = 0, row_len = 0;
+    int64_t L = 0;
+    const int32_t* h_index = nullptr;
+    LifeOut out;
     bool filter() const { return gap > 0 || cuts.rb2 != cuts.rc2; }
+    // what the CPU backend's three calls share
+    ta::cpu::ShellItems cpu() const { return {n_a, ida.data(), n_b, idb.data(), box.data(), box.per_frame, &cuts, gap}; }
 };
-int shell_plan(ta_ctx* ctx, int fft, const ShellArgs& a, bool any_out, ShellPlan* p, const char* name = "shell_residence",
-               const char* outputs = "ci, runs and nb") {
+// The argument checks of a call of `kind`, in the order the entries have always made them: what the gated kinds check before
+// anything else (the mode, the anchor column and the index table; the condition), what every kind checks, and what the gated
+// kinds check against the staged shape (max_lag against the frames and the cap; three staged columns and the box on x, y, z,
+// ta_orient's checks of the index rows, and every row's anchor against the observed items)
+int shell_plan(ta_ctx* ctx, ShellKind kind, int fft, const ShellArgs& a, bool any_out, ShellPlan* p) {
+    const char* name = kind == SHELL_RESIDENCE ? "shell_residence" : kind == SHELL_MSD ? "shell_msd" : "shell_orient";
     const std::string who = std::string(name) + ": ";
+    p->kind = kind;
+    if (kind == SHELL_ORIENT) {
+        if (a.mode < ORIENT_BOND || a.mode > ORIENT_NORMAL)
+            return fail(ctx, TA_E_INVALID, who + "mode must be TA_ORIENT_BOND (0), TA_ORIENT_BISECTOR (1) or TA_ORIENT_NORMAL (2)");
+        p->mode = a.mode, p->row_len = orient_row_len(a.mode), p->h_index = a.h_index;
+        if (a.anchor < 0 || a.anchor >= p->row_len)
+            return fail(ctx, TA_E_INVALID, who + "anchor must be a column of the index rows, 0 ... " + std::to_string(p->row_len - 1));
+        if (!a.h_index) return fail(ctx, TA_E_INVALID, who + "the index table is NULL");
+    }
+    if (kind != SHELL_RESIDENCE && a.condition != ta::SHELL_CONTINUOUS && a.condition != ta::SHELL_ENDPOINTS)
+        return fail(ctx, TA_E_INVALID, who + "condition must be 0 (continuous) or 1 (endpoints)");
+
     TA_CHECK(check_fft(ctx, fft));
-    if (!any_out) return fail(ctx, TA_E_INVALID, who + "the " + outputs + " outputs are all NULL");
+    if (!any_out)
+        return fail(ctx, TA_E_INVALID, who + "the " + (kind == SHELL_RESIDENCE ? "ci, runs and nb" : "sums, count, runs and nb") + " outputs are all NULL");
     if (a.h_idx_a && a.n_a < 1) return fail(ctx, TA_E_INVALID, who + "n_a must be >= 1");
     if (a.h_idx_b && a.n_b < 1) return fail(ctx, TA_E_INVALID, who + "n_b must be >= 1");
     TA_CHECK(pair_cut_args(ctx, who, a.r_cut, a.h_dims, a.axes));
@@ -2322,9 +2398,39 @@ int shell_plan(ta_ctx* ctx, int fft, const ShellArgs& a, bool any_out, ShellPlan
     if (p->n_b >= (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, who + "n_b must be below 2^30");
     p->pitch_b += VHD_TILE_B;
     p->idb.resize((size_t)p->pitch_b, -1);
-    if (!a.h_dims) return TA_OK;
-    TA_CHECK(image_box(ctx, who, a.h_dims, a.axes, T, D, &p->box));
-    return half_box(ctx, who, "r_break", a.r_break, p->box, D, 1);
+    if (a.h_dims) {
+        TA_CHECK(image_box(ctx, who, a.h_dims, a.axes, T, D, &p->box));
+        TA_CHECK(half_box(ctx, who, "r_break", a.r_break, p->box, D, 1));
+    }
+
+    if (kind != SHELL_RESIDENCE) {
+        if (a.max_lag < 0 || a.max_lag > T - 1)
+            return fail(ctx, TA_E_INVALID, who + "max_lag must be 0 ... n_frames - 1 = " + std::to_string(T - 1));
+        if (a.max_lag > ta::kShellMsdMaxLag)
+            return fail(ctx, TA_E_INVALID, who + "max_lag must be at most " + std::to_string(ta::kShellMsdMaxLag) + " (eight passes of 256 lags)");
+        p->condition = a.condition, p->L = a.max_lag, p->n_sums = kind == SHELL_ORIENT ? 2 : D;
+    }
+    p->out = life_out(T, p->L, p->n_sums);
+    if (kind != SHELL_ORIENT) return TA_OK;
+    if (D != 3) return fail(ctx, TA_E_INVALID, who + "the position slab must hold three columns per atom (dim = " + std::to_string(D) + ")");
+    if (a.h_dims && !(a.axes[0] == 0 && a.axes[1] == 1 && a.axes[2] == 2))
+        return fail(ctx, TA_E_INVALID, who + "the box needs the three columns x, y, z (axes {0, 1, 2})");
+    if (A * 3 >= (int64_t)1 << 31 || p->n_b * 6 >= (int64_t)1 << 31)
+        return fail(ctx, TA_E_INVALID, who + "n_atoms * 3 and n_vectors * 6 must be below 2^31");
+    const int K = p->row_len;
+    for (int64_t n = 0; n < p->n_b; ++n) {
+        const int32_t* r = a.h_index + n * K;
+        for (int j = 0; j < K; ++j)
+            if (r[j] < 0 || r[j] >= A)
+                return fail(ctx, TA_E_INVALID, who + "index " + std::to_string(r[j]) + " of vector " + std::to_string(n) +
+                                                   " is outside 0 ... n_atoms - 1");
+        if (r[0] == r[1] || (K == 3 && (r[0] == r[2] || r[1] == r[2])))
+            return fail(ctx, TA_E_INVALID, who + "vector " + std::to_string(n) + " names an atom twice");
+        if (r[a.anchor] != p->idb[(size_t)n])
+            return fail(ctx, TA_E_INVALID, who + "the anchor of vector " + std::to_string(n) + " (atom " + std::to_string(r[a.anchor]) +
+                                               ") is not observed item " + std::to_string(n) + " (atom " + std::to_string(p->idb[(size_t)n]) + ")");
+    }
+    return TA_OK;
 }
 
 // the observed items per block: pair_block's count of series; a block behind the first starts at an even item
@@ -2332,75 +2438,72 @@ int64_t shell_block(const ta_ctx* ctx, int64_t n_b, int64_t pitch) {
     const int64_t Qc = pair_block(ctx, n_b, pitch);
     return Qc < n_b ? std::max<int64_t>(2, Qc & ~(int64_t)1) : Qc;
 }
+// The table of a call, zero lag | hm | ida | idb (pair_tail_*) | Qc zero labels | index rows (n_b rows of row_len int32): the
+// observed items per block, where the parts begin and the whole, in doubles
+struct ShellTab {
+    int64_t Qc;
+    size_t tail, lab, rows, n;
+};
+ShellTab shell_tab_layout(const ta_ctx* ctx, const ShellPlan& p, int64_t pitch) {
+    const int64_t Qc = shell_block(ctx, p.n_b, pitch);
+    const size_t tail = 1, lab = tail + pair_tail_size(p.box, p), rows = lab + ((size_t)Qc + 1) / 2;
+    return {Qc, tail, lab, rows, rows + ((size_t)p.n_b * (size_t)p.row_len + 1) / 2};
+}
 
 // One call on the staged position slab of either element type (the caller has opened the call's bracket, it is closed here;
-// the table zero lag | hm | ida | idb | zero labels has been queued).  Per block of observed items: per chunk of whole
-// 64-frame words one k_vhd_gather launch at lag 0, stride 1 (the reference items and the block's observed items, read in the
-// slab's own element type) and one k_shell_series launch, which writes the chunk's rows of the level block Z; then
-// life_sums_block, pair_life_pm's passes.  Neither chunking changes a bit: every row of Z has one writer whatever the chunk,
-// and the blocks' rows are added as pair_life_pm's.  ev[1] / ev[2] bracket the (last) k_shell_series launch, unless a
-// lag-sum evaluation after it records its own main kernel.
-// msd (ta_shell_msd*, otherwise NULL): behind a block's filter k_shell_bits packs its series, k_shell_msd (shell_msd.hip) adds
-// up the gated squared displacements of the block's items over the lags 0 ... L and k_shell_fold adds the workgroups' partial
-// rows in row order onto sums and count: the blocks in block order.
-// orient (ta_shell_orient*, otherwise NULL): k_shell_orient (shell_orient.hip) stands in k_shell_msd's place, the walk over the
-// unit vectors of the block's index rows (one per observed item, its anchor; the table carries them behind the zero labels)
-// with the distance pass's boxes for the image step; two sums per lag in place of D.
-struct ShellOrient {
-    int mode, anchor;
-    const int32_t* h_index;
-};
-struct ShellMsd {
-    int condition;
-    int64_t L;
-    double* d_sums;
-    int64_t* d_count;
-    const ShellOrient* orient = nullptr;
-    int n_sums(int D) const { return orient ? 2 : D; }
-};
-// ids: the block's observed items; rows, hm, per_frame (orient): the block's index rows and the boxes on the device
-int shell_msd_block(ta_ctx* ctx, const ShellMsd& m, const Slab& slab, const LifeSums& s, int64_t b, int64_t nb, const int* ids,
-                    const int* rows, const double* hm, bool per_frame) {
+// the table has been queued).  Per block of observed items: per chunk of whole 64-frame words one k_vhd_gather launch at
+// lag 0, stride 1 (the reference items and the block's observed items, read in the slab's own element type) and one
+// k_shell_series launch, which writes the chunk's rows of the level block Z; then life_sums_block, pair_life_pm's passes.
+// Neither chunking changes a bit: every row of Z has one writer whatever the chunk, and the blocks' rows are added as
+// pair_life_pm's.  ev[1] / ev[2] bracket the (last) k_shell_series launch, unless a lag-sum evaluation after it records its
+// own main kernel.
+// A gated call (p.n_sums; no ci) with sums or count asked for: behind a block's filter k_shell_bits packs its series,
+// k_shell_msd (shell_msd.hip) adds up the gated squared displacements of the block's items over the lags 0 ... L and
+// k_shell_fold adds the workgroups' partial rows in row order onto sums and count: the blocks in block order.
+// SHELL_ORIENT: k_shell_orient (shell_orient.hip) stands in k_shell_msd's place, the walk over the unit vectors of the block's
+// index rows (one per observed item, its anchor) with the distance pass's boxes for the image step; two sums per lag.
+// ids: the block's observed items; rows, hm (SHELL_ORIENT): the block's index rows and the boxes on the device
+int shell_gated_block(ta_ctx* ctx, const ShellPlan& p, const Slab& slab, const LifeSums& s, int64_t b, int64_t nb, const int* ids,
+                      const int* rows, const double* hm, const LifePtrs& d) {
     hipStream_t st = slab.st;
-    const int G = ta::shell_msd_groups(ctx->n_cu, (long)nb, (long)m.L), chunk = ta::shell_msd_chunk((long)ctx->opt_shell_msd_chunk);
+    const int G = ta::shell_msd_groups(ctx->n_cu, (long)nb, (long)p.L), chunk = ta::shell_msd_chunk((long)ctx->opt_shell_msd_chunk);
     unsigned long long* words = (unsigned long long*)ctx->shell_words.p;
     TA_LAUNCH(ctx, "k_shell_bits", st, ta::launch_shell_bits(ctx->n_cu, s.Z, (long)s.pitch, (long)s.T, (long)nb, words, st));
-    if (m.orient)
+    if (p.kind == SHELL_ORIENT)
         TA_LAUNCH(ctx, "k_shell_orient", st,
-                  ta::launch_shell_orient(slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, slab.D, m.orient->mode, rows, (long)nb,
-                                          hm, per_frame, words, m.condition, (long)m.L, chunk, G, ctx->shell_part.p, st));
+                  ta::launch_shell_orient(slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, slab.D, p.mode, rows, (long)nb, hm,
+                                          p.box.per_frame, words, p.condition, (long)p.L, chunk, G, ctx->shell_part.p, st));
     else
         TA_LAUNCH(ctx, "k_shell_msd", st,
-                  ta::launch_shell_msd(slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, slab.D, ids, (long)nb, words, m.condition,
-                                       (long)m.L, chunk, G, ctx->shell_part.p, st));
+                  ta::launch_shell_msd(slab.pm, slab.f32, (long)slab.pitch, (long)slab.T, (long)slab.A, slab.D, ids, (long)nb, words,
+                                       p.condition, (long)p.L, chunk, G, ctx->shell_part.p, st));
     TA_LAUNCH(ctx, "k_shell_fold", st,
-              ta::launch_shell_fold(ctx->shell_part.p, G, (long)m.L, m.n_sums(slab.D), b == 0, m.d_sums, (long long*)m.d_count, st));
+              ta::launch_shell_fold(ctx->shell_part.p, G, (long)p.L, p.n_sums, b == 0, d.lags, (long long*)d.count, st));
     return TA_OK;
 }
-int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, double* d_ci, int64_t* d_runs, double* d_nb,
-             const ShellMsd* msd = nullptr) {
+int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, const LifePtrs& d) {
     hipStream_t st = slab.st;
     const int D = p.D;
-    const int64_t T = slab.T, pitch = slab.pitch, N = p.n_b, Qc = shell_block(ctx, N, pitch);
-    const int64_t* lag0 = (const int64_t*)ctx->shell_tab.dev.p;
-    const auto [hm, ida, idb] = pair_tail((const double*)(lag0 + 1), p.box, p);
-    const int* lab = idb + p.pitch_b;
-    const int* rows = lab + 2 * ((Qc + 1) / 2);  // (ta_shell_orient*: the index rows behind the Qc zero labels)
+    const ShellTab t = shell_tab_layout(ctx, p, slab.pitch);
+    const int64_t T = slab.T, pitch = slab.pitch, N = p.n_b, Qc = t.Qc;
+    const double* tab = (const double*)ctx->shell_tab.dev.p;
+    const int64_t* lag0 = (const int64_t*)tab;
+    const auto [hm, ida, idb] = pair_tail(tab + t.tail, p.box, p);
+    const int *lab = (const int*)(tab + t.lab), *rows = (const int*)(tab + t.rows);
     const int64_t pitch_q = (Qc + VHD_TILE_B - 1) / VHD_TILE_B * VHD_TILE_B, words = (T + 63) / 64;
     const size_t per = sizeof(double) * (size_t)D * (size_t)(p.pitch_a + pitch_q);  // a gathered frame
     const int64_t fit = std::max<int64_t>(1, (int64_t)(kVhdBudget / (64 * per)));
     const int64_t wc = std::min<int64_t>({words, 65535, ctx->opt_shell_chunk > 0 ? ctx->opt_shell_chunk : fit});
     TA_CHECK(ensure(ctx, ctx->vhd_scr, (size_t)std::min(T, 64 * wc) * per));
     double* ga = (double*)ctx->vhd_scr.p;
-    if (msd && (msd->d_sums || msd->d_count)) {
+    const bool gated = p.n_sums && (d.lags || d.count);
+    if (gated) {
         TA_CHECK(ensure(ctx, ctx->shell_words, sizeof(uint64_t) * (size_t)Qc * (size_t)words));
         TA_CHECK(ensure(ctx, ctx->shell_part,
-                        ta::shell_msd_part_bytes(ta::shell_msd_groups(ctx->n_cu, (long)Qc, (long)msd->L), (long)msd->L, msd->n_sums(D))));
-    } else {
-        msd = nullptr;
+                        ta::shell_msd_part_bytes(ta::shell_msd_groups(ctx->n_cu, (long)Qc, (long)p.L), (long)p.L, p.n_sums)));
     }
     LifeSums s;
-    TA_CHECK(life_sums_begin(ctx, fft, slab, N, Qc, d_ci, d_runs, d_nb, &s));
+    TA_CHECK(life_sums_begin(ctx, fft, slab, N, Qc, p.n_sums ? nullptr : d.lags, d.runs, d.nb, &s));
     for (int64_t b = 0; b < s.n_blocks; ++b) {
         const int64_t q0 = b * Qc, nb = std::min(Qc, N - q0), pitch_b = (nb + VHD_TILE_B - 1) / VHD_TILE_B * VHD_TILE_B;
         for (int64_t w0 = 0; w0 < words; w0 += wc) {
@@ -2415,88 +2518,26 @@ int shell_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ShellPlan& p, double
                                                p.filter() ? 2.0 : 1.0, s.Z, st));
         }
         TA_CHECK(life_sums_block(ctx, s, b, nb, p.filter(), p.gap, lab));
-        if (msd) TA_CHECK(shell_msd_block(ctx, *msd, slab, s, b, nb, idb + q0, rows + (msd->orient ? orient_row_len(msd->orient->mode) * q0 : 0), hm, p.box.per_frame));
+        if (gated) TA_CHECK(shell_gated_block(ctx, p, slab, s, b, nb, idb + q0, rows + p.row_len * q0, hm, d));
     }
     return life_sums_end(ctx, s);
 }
 
-// ta_shell_residence_staged and the device half of ta_shell_residence (out as pair_life_launch's).  msd (ta_shell_msd*): no ci;
-// the context's own output buffer is then sums ((L + 1) D) | count (L + 1) | runs (T + 1) | nb (T)
-int shell_launch(ta_ctx* ctx, int fft, const ShellPlan& p, double* d_ci, int64_t* d_runs, double* d_nb, void* stream, double** out,
-                 const ShellMsd* msd = nullptr) {
+// The staged entries and the device half of the host-facing ones (out as pair_life_launch's)
+int shell_launch(ta_ctx* ctx, int fft, const ShellPlan& p, const LifePtrs& d, void* stream, double** out) {
     return slab_entry(
         ctx, nullptr, stream, no_args,
         [&](const Slab& s) -> int {
-            const int64_t Qc = shell_block(ctx, p.n_b, s.pitch);
-            const ShellOrient* orient = msd ? msd->orient : nullptr;
-            const size_t n_lab = 1 + pair_tail_size(p.box, p) + ((size_t)Qc + 1) / 2;
-            const size_t n_rows = orient ? (size_t)p.n_b * orient_row_len(orient->mode) : 0, n = n_lab + (n_rows + 1) / 2;
+            const ShellTab t = shell_tab_layout(ctx, p, s.pitch);
             double* h = nullptr;
-            TA_CHECK(ctx->shell_tab.begin(ctx, sizeof(double) * n, (void**)&h));
-            memset(h, 0, sizeof(double) * n);  // (the zero lag in front, the zero labels behind)
-            pair_tail_pack(h + 1, p.box, p);
-            if (orient) memcpy(h + n_lab, orient->h_index, sizeof(int32_t) * n_rows);
-            if (out) {
-                const size_t n_msd = msd ? (size_t)(msd->L + 1) * (size_t)(msd->n_sums(p.D) + 1) : (size_t)s.T;
-                TA_CHECK(ensure(ctx, ctx->pair_out, sizeof(double) * (n_msd + 2 * (size_t)s.T + 1)));
-                *out = (double*)ctx->pair_out.p;
-            }
+            TA_CHECK(ctx->shell_tab.begin(ctx, sizeof(double) * t.n, (void**)&h));
+            memset(h, 0, sizeof(double) * t.n);  // (the zero lag in front, the zero labels)
+            pair_tail_pack(h + t.tail, p.box, p);
+            std::copy_n(p.h_index, (size_t)p.n_b * (size_t)p.row_len, (int32_t*)(h + t.rows));
+            if (out) TA_CHECK(life_out_buffer(ctx, p.out, out));
             return ctx->shell_tab.send(ctx, s.st);
         },
-        [&](const Slab& s) {
-            if (msd && out) {
-                double* o = *out;
-                const size_t n1 = (size_t)(msd->L + 1) * (size_t)msd->n_sums(p.D), n2 = (size_t)msd->L + 1;
-                const ShellMsd m{msd->condition, msd->L, msd->d_sums ? o : nullptr, msd->d_count ? (int64_t*)(o + n1) : nullptr, msd->orient};
-                return shell_pm(ctx, false, s, p, nullptr, d_runs ? (int64_t*)(o + n1 + n2) : nullptr, d_nb ? o + n1 + n2 + s.T + 1 : nullptr, &m);
-            }
-            if (!out) return shell_pm(ctx, fft != 0, s, p, d_ci, d_runs, d_nb, msd);
-            double* o = *out;
-            return shell_pm(ctx, fft != 0, s, p, d_ci ? o : nullptr, d_runs ? (int64_t*)(o + s.T) : nullptr, d_nb ? o + 2 * s.T + 1 : nullptr);
-        });
-}
-
-// the argument checks of ta_shell_msd*: shell_plan's, and the condition and max_lag against the staged frames and the cap
-int shell_msd_plan(ta_ctx* ctx, int condition, int64_t max_lag, const ShellArgs& a, bool any_out, ShellPlan* p, const char* name = "shell_msd") {
-    const std::string who = std::string(name) + ": ";
-    if (condition != ta::SHELL_CONTINUOUS && condition != ta::SHELL_ENDPOINTS)
-        return fail(ctx, TA_E_INVALID, who + "condition must be 0 (continuous) or 1 (endpoints)");
-    TA_CHECK(shell_plan(ctx, 0, a, any_out, p, name, "sums, count, runs and nb"));
-    if (max_lag < 0 || max_lag > p->T - 1)
-        return fail(ctx, TA_E_INVALID, who + "max_lag must be 0 ... n_frames - 1 = " + std::to_string(p->T - 1));
-    if (max_lag > ta::kShellMsdMaxLag)
-        return fail(ctx, TA_E_INVALID, who + "max_lag must be at most " + std::to_string(ta::kShellMsdMaxLag) + " (eight passes of 256 lags)");
-    return TA_OK;
-}
-
-// the argument checks of ta_shell_orient*: the mode and the anchor column, shell_msd_plan's, three staged columns and the
-// box on x, y, z, ta_orient's checks of the index rows, and every row's anchor against the observed items
-int shell_orient_plan(ta_ctx* ctx, int condition, int64_t max_lag, const ShellOrient& o, const ShellArgs& a, bool any_out, ShellPlan* p) {
-    const std::string who = "shell_orient: ";
-    if (o.mode < ORIENT_BOND || o.mode > ORIENT_NORMAL)
-        return fail(ctx, TA_E_INVALID, who + "mode must be TA_ORIENT_BOND (0), TA_ORIENT_BISECTOR (1) or TA_ORIENT_NORMAL (2)");
-    const int K = orient_row_len(o.mode);
-    if (o.anchor < 0 || o.anchor >= K) return fail(ctx, TA_E_INVALID, who + "anchor must be a column of the index rows, 0 ... " + std::to_string(K - 1));
-    if (!o.h_index) return fail(ctx, TA_E_INVALID, who + "the index table is NULL");
-    TA_CHECK(shell_msd_plan(ctx, condition, max_lag, a, any_out, p, "shell_orient"));
-    if (p->D != 3) return fail(ctx, TA_E_INVALID, who + "the position slab must hold three columns per atom (dim = " + std::to_string(p->D) + ")");
-    if (a.h_dims && !(a.axes[0] == 0 && a.axes[1] == 1 && a.axes[2] == 2))
-        return fail(ctx, TA_E_INVALID, who + "the box needs the three columns x, y, z (axes {0, 1, 2})");
-    if (p->A * 3 >= (int64_t)1 << 31 || p->n_b * 6 >= (int64_t)1 << 31)
-        return fail(ctx, TA_E_INVALID, who + "n_atoms * 3 and n_vectors * 6 must be below 2^31");
-    for (int64_t n = 0; n < p->n_b; ++n) {
-        const int32_t* r = o.h_index + n * K;
-        for (int j = 0; j < K; ++j)
-            if (r[j] < 0 || r[j] >= p->A)
-                return fail(ctx, TA_E_INVALID, who + "index " + std::to_string(r[j]) + " of vector " + std::to_string(n) +
-                                                   " is outside 0 ... n_atoms - 1");
-        if (r[0] == r[1] || (K == 3 && (r[0] == r[2] || r[1] == r[2])))
-            return fail(ctx, TA_E_INVALID, who + "vector " + std::to_string(n) + " names an atom twice");
-        if (r[o.anchor] != p->idb[(size_t)n])
-            return fail(ctx, TA_E_INVALID, who + "the anchor of vector " + std::to_string(n) + " (atom " + std::to_string(r[o.anchor]) +
-                                               ") is not observed item " + std::to_string(n) + " (atom " + std::to_string(p->idb[(size_t)n]) + ")");
-    }
-    return TA_OK;
+        [&](const Slab& s) { return shell_pm(ctx, fft != 0, s, p, out ? p.out.at(*out, d) : d); });
 }
 
 // ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
@@ -2539,6 +2580,13 @@ int cpu_stage_alloc(ta_ctx* ctx, int64_t n_frames, int64_t n_atoms, int dim, int
 
 // the tail of every CPU branch: the backend's return code (0, or TA_E_NOMEM) as the entry's
 int cpu_rc(ta_ctx* ctx, int rc) { return rc ? fail(ctx, rc, "CPU backend: out of host memory") : TA_OK; }
+
+int cpu_shell(ta_ctx* ctx, bool fft, const ShellPlan& p, const LifePtrs& h) {
+    const ta::cpu::State s = cpu_state(ctx);
+    return cpu_rc(ctx, p.kind == SHELL_RESIDENCE ? ta::cpu::shell_residence(s, fft, p.cpu(), h.lags, h.runs, h.nb)
+                       : p.kind == SHELL_MSD     ? ta::cpu::shell_msd(s, p.condition, p.L, p.cpu(), h.lags, h.count, h.runs, h.nb)
+                                                 : ta::cpu::shell_orient(s, p.condition, p.L, p.mode, p.h_index, p.cpu(), h.lags, h.count, h.runs, h.nb));
+}
 
 // the mean over atoms of a lag-indexed sum (velocityautocorr.py:214,237; viscosity.py:233)
 void atom_mean(const ta_ctx* ctx, double* h_ts) {
@@ -3439,71 +3487,56 @@ int ta_vanhove_distinct_staged(ta_ctx* ctx, int n_lags, const int64_t* h_lags, i
 // Pair lifetimes on the staged slab 0, read in its own element type; the pair list and the box are HOST arrays.  Bond
 // lifetimes (bond != NULL) take the same path with k_bond_series (and k_pair_filter where needed)
 static int life_staged(ta_ctx* ctx, int fft, int64_t n_rows, const int32_t* h_rows, const double* h_dimensions, const int* axes, double r_cut,
-                       const BondArgs* bond, double* d_ci, int64_t* d_runs, double* d_nb, void* stream) {
+                       const BondArgs* bond, const LifePtrs& d, void* stream) {
     return ta::guarded(fail, ctx, [&]() -> int {
     PairLifePlan plan;
     TA_CHECK(need_ctx(ctx));
     TA_NO_CPU(ctx);
-    TA_CHECK(pair_life_plan(ctx, fft, n_rows, h_rows, h_dimensions, axes, r_cut, d_ci || d_runs || d_nb, &plan, bond));
-    return pair_life_launch(ctx, fft, plan, d_ci, d_runs, d_nb, stream, nullptr);
+    TA_CHECK(pair_life_plan(ctx, fft, n_rows, h_rows, h_dimensions, axes, r_cut, d.any(), &plan, bond));
+    return pair_life_launch(ctx, fft, plan, d, stream, nullptr);
     });
 }
 int ta_pair_lifetime_staged(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs, const double* h_dimensions, const int* axes,
                             double r_cut, double* d_ci, int64_t* d_runs, double* d_nb, void* stream) {
-    return life_staged(ctx, fft, n_pairs, h_pairs, h_dimensions, axes, r_cut, nullptr, d_ci, d_runs, d_nb, stream);
+    return life_staged(ctx, fft, n_pairs, h_pairs, h_dimensions, axes, r_cut, nullptr, {d_ci, nullptr, d_runs, d_nb}, stream);
 }
 int ta_bond_lifetime_staged(ta_ctx* ctx, int fft, int64_t n_bonds, int n_at, const int32_t* h_atoms, const double* h_dimensions,
                             const int* axes, double r_cut, double r_break, double cos_cut, double cos_break, int gap, double* d_ci,
                             int64_t* d_runs, double* d_nb, void* stream) {
     const BondArgs bond{n_at, r_break, cos_cut, cos_break, gap};
-    return life_staged(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, &bond, d_ci, d_runs, d_nb, stream);
+    return life_staged(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, &bond, {d_ci, nullptr, d_runs, d_nb}, stream);
 }
 
-// Shell residence times on the staged slab 0, read in its own element type; the index lists and the box are HOST arrays
+// The shell calls on the staged slab 0, read in its own element type; the index lists, the box and (ta_shell_orient_staged)
+// the index rows are HOST arrays, the outputs on the device
+static int shell_staged(ta_ctx* ctx, ShellKind kind, int fft, const ShellArgs& a, const LifePtrs& d, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    ShellPlan plan;
+    TA_CHECK(need_ctx(ctx));
+    TA_NO_CPU(ctx);
+    TA_CHECK(shell_plan(ctx, kind, fft, a, d.any(), &plan));
+    return shell_launch(ctx, fft, plan, d, stream, nullptr);
+    });
+}
 int ta_shell_residence_staged(ta_ctx* ctx, int fft, int64_t n_a, const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b,
                               const double* h_dimensions, const int* axes, double r_cut, double r_break, int gap, double* d_ci,
                               int64_t* d_runs, double* d_nb, void* stream) {
-    return ta::guarded(fail, ctx, [&]() -> int {
-    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
-    ShellPlan plan;
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(shell_plan(ctx, fft, a, d_ci || d_runs || d_nb, &plan));
-    return shell_launch(ctx, fft, plan, d_ci, d_runs, d_nb, stream, nullptr);
-    });
+    return shell_staged(ctx, SHELL_RESIDENCE, fft, {n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap},
+                        {d_ci, nullptr, d_runs, d_nb}, stream);
 }
-
-// The shell-resolved MSD on the staged slab 0; the index lists and the box are HOST arrays, the outputs on the device
 int ta_shell_msd_staged(ta_ctx* ctx, int condition, int64_t max_lag, int64_t n_a, const int64_t* h_idx_a, int64_t n_b,
                         const int64_t* h_idx_b, const double* h_dimensions, const int* axes, double r_cut, double r_break, int gap,
                         double* d_sums, int64_t* d_count, int64_t* d_runs, double* d_nb, void* stream) {
-    return ta::guarded(fail, ctx, [&]() -> int {
-    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
-    ShellPlan plan;
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(shell_msd_plan(ctx, condition, max_lag, a, d_sums || d_count || d_runs || d_nb, &plan));
-    const ShellMsd m{condition, max_lag, d_sums, d_count};
-    return shell_launch(ctx, 0, plan, nullptr, d_runs, d_nb, stream, nullptr, &m);
-    });
+    return shell_staged(ctx, SHELL_MSD, 0, {n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap, condition, max_lag},
+                        {d_sums, d_count, d_runs, d_nb}, stream);
 }
-
-// The shell-resolved reorientation on the staged slab 0; the index rows, the index lists and the box are HOST arrays, the
-// outputs on the device
 int ta_shell_orient_staged(ta_ctx* ctx, int condition, int64_t max_lag, int mode, int anchor, const int32_t* h_index, int64_t n_a,
                            const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes,
                            double r_cut, double r_break, int gap, double* d_sums, int64_t* d_count, int64_t* d_runs, double* d_nb,
                            void* stream) {
-    return ta::guarded(fail, ctx, [&]() -> int {
-    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
-    const ShellOrient o{mode, anchor, h_index};
-    ShellPlan plan;
-    TA_CHECK(need_ctx(ctx));
-    TA_NO_CPU(ctx);
-    TA_CHECK(shell_orient_plan(ctx, condition, max_lag, o, a, d_sums || d_count || d_runs || d_nb, &plan));
-    const ShellMsd m{condition, max_lag, d_sums, d_count, &o};
-    return shell_launch(ctx, 0, plan, nullptr, d_runs, d_nb, stream, nullptr, &m);
-    });
+    return shell_staged(ctx, SHELL_ORIENT, 0,
+                        {n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap, condition, max_lag, mode, anchor, h_index},
+                        {d_sums, d_count, d_runs, d_nb}, stream);
 }
 
 int ta_last_timing(ta_ctx* ctx, float* total_ms, float* main_kernel_ms) {
@@ -4419,90 +4452,62 @@ int ta_pair_find_read(ta_ctx* ctx, int64_t capacity, int32_t* h_pairs) {
 
 // ta_pair_lifetime and (bond != NULL) ta_bond_lifetime: the plan, the CPU backend or the device half, the outputs copied back
 static int life_host(ta_ctx* ctx, int fft, int64_t n_rows, const int32_t* h_rows, const double* h_dimensions, const int* axes, double r_cut,
-                     const BondArgs* bond, double* h_ci, int64_t* h_runs, double* h_nb) {
+                     const BondArgs* bond, const LifePtrs& h) {
     return host_call(ctx, [&]() -> int {
     PairLifePlan p;
     TA_CHECK(need_ctx(ctx));
-    TA_CHECK(pair_life_plan(ctx, fft, n_rows, h_rows, h_dimensions, axes, r_cut, h_ci || h_runs || h_nb, &p, bond));
+    TA_CHECK(pair_life_plan(ctx, fft, n_rows, h_rows, h_dimensions, axes, r_cut, h.any(), &p, bond));
     if (ctx->is_cpu && bond)
         return cpu_rc(ctx, ta::cpu::bond_lifetime(cpu_state(ctx), fft != 0, p.P, p.n_at, h_rows, p.box.data(), p.box.per_frame, p.cuts, p.gap,
-                                                  h_ci, h_runs, h_nb));
+                                                  h.lags, h.runs, h.nb));
     if (ctx->is_cpu)
         return cpu_rc(ctx, ta::cpu::pair_lifetime(cpu_state(ctx), fft != 0, p.P, h_rows ? h_rows : ctx->pair_host.data(), p.box.data(),
-                                                  p.box.per_frame, p.rc2, h_ci, h_runs, h_nb));
+                                                  p.box.per_frame, p.rc2, h.lags, h.runs, h.nb));
     double* d_out = nullptr;
-    TA_CHECK(pair_life_launch(ctx, fft, p, h_ci, h_runs, h_nb, ctx->stream, &d_out));
-    const size_t T = (size_t)ctx->st_T;  // (int64 counts travel as 8-byte elements)
-    return host_finish(ctx, {{h_ci, d_out, T}, {(double*)h_runs, d_out + T, T + 1}, {h_nb, d_out + 2 * T + 1, T}});
+    TA_CHECK(pair_life_launch(ctx, fft, p, h, ctx->stream, &d_out));
+    return life_finish(ctx, p.out, h, d_out);
     });
 }
 int ta_pair_lifetime(ta_ctx* ctx, int fft, int64_t n_pairs, const int32_t* h_pairs, const double* h_dimensions, const int* axes,
                      double r_cut, double* h_ci, int64_t* h_runs, double* h_nb) {
-    return life_host(ctx, fft, n_pairs, h_pairs, h_dimensions, axes, r_cut, nullptr, h_ci, h_runs, h_nb);
+    return life_host(ctx, fft, n_pairs, h_pairs, h_dimensions, axes, r_cut, nullptr, {h_ci, nullptr, h_runs, h_nb});
 }
 int ta_bond_lifetime(ta_ctx* ctx, int fft, int64_t n_bonds, int n_at, const int32_t* h_atoms, const double* h_dimensions, const int* axes,
                      double r_cut, double r_break, double cos_cut, double cos_break, int gap, double* h_ci, int64_t* h_runs, double* h_nb) {
     const BondArgs bond{n_at, r_break, cos_cut, cos_break, gap};
-    return life_host(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, &bond, h_ci, h_runs, h_nb);
+    return life_host(ctx, fft, n_bonds, h_atoms, h_dimensions, axes, r_cut, &bond, {h_ci, nullptr, h_runs, h_nb});
 }
 
+// ta_shell_residence, ta_shell_msd and ta_shell_orient: the plan, the CPU backend or the device half, the outputs copied back
+static int shell_host(ta_ctx* ctx, ShellKind kind, int fft, const ShellArgs& a, const LifePtrs& h) {
+    return host_call(ctx, [&]() -> int {
+    ShellPlan p;
+    TA_CHECK(need_ctx(ctx));
+    TA_CHECK(shell_plan(ctx, kind, fft, a, h.any(), &p));
+    if (ctx->is_cpu) return cpu_shell(ctx, fft != 0, p, h);
+    double* d_out = nullptr;
+    TA_CHECK(shell_launch(ctx, fft, p, h, ctx->stream, &d_out));
+    return life_finish(ctx, p.out, h, d_out);
+    });
+}
 int ta_shell_residence(ta_ctx* ctx, int fft, int64_t n_a, const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b,
                        const double* h_dimensions, const int* axes, double r_cut, double r_break, int gap, double* h_ci, int64_t* h_runs,
                        double* h_nb) {
-    return host_call(ctx, [&]() -> int {
-    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
-    ShellPlan p;
-    TA_CHECK(need_ctx(ctx));
-    TA_CHECK(shell_plan(ctx, fft, a, h_ci || h_runs || h_nb, &p));
-    if (ctx->is_cpu)
-        return cpu_rc(ctx, ta::cpu::shell_residence(cpu_state(ctx), fft != 0, p.n_a, p.ida.data(), p.n_b, p.idb.data(), p.box.data(),
-                                                    p.box.per_frame, p.cuts, p.gap, h_ci, h_runs, h_nb));
-    double* d_out = nullptr;
-    TA_CHECK(shell_launch(ctx, fft, p, h_ci, h_runs, h_nb, ctx->stream, &d_out));
-    const size_t T = (size_t)ctx->st_T;  // (int64 counts travel as 8-byte elements)
-    return host_finish(ctx, {{h_ci, d_out, T}, {(double*)h_runs, d_out + T, T + 1}, {h_nb, d_out + 2 * T + 1, T}});
-    });
+    return shell_host(ctx, SHELL_RESIDENCE, fft, {n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap},
+                      {h_ci, nullptr, h_runs, h_nb});
 }
-
-int ta_shell_orient(ta_ctx* ctx, int condition, int64_t max_lag, int mode, int anchor, const int32_t* h_index, int64_t n_a,
-                    const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes, double r_cut,
-                    double r_break, int gap, double* h_sums, int64_t* h_count, int64_t* h_runs, double* h_nb) {
-    return host_call(ctx, [&]() -> int {
-    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
-    const ShellOrient o{mode, anchor, h_index};
-    ShellPlan p;
-    TA_CHECK(need_ctx(ctx));
-    TA_CHECK(shell_orient_plan(ctx, condition, max_lag, o, a, h_sums || h_count || h_runs || h_nb, &p));
-    if (ctx->is_cpu)
-        return cpu_rc(ctx, ta::cpu::shell_orient(cpu_state(ctx), condition, max_lag, mode, h_index, p.n_a, p.ida.data(), p.n_b, p.idb.data(),
-                                                 p.box.data(), p.box.per_frame, p.cuts, p.gap, h_sums, h_count, h_runs, h_nb));
-    double* d_out = nullptr;
-    const ShellMsd m{condition, max_lag, h_sums, h_count, &o};  // (which outputs are asked for: shell_launch points them into d_out)
-    TA_CHECK(shell_launch(ctx, 0, p, nullptr, h_runs, h_nb, ctx->stream, &d_out, &m));
-    const size_t T = (size_t)ctx->st_T, n1 = (size_t)(max_lag + 1) * 2, n2 = (size_t)max_lag + 1;  // (int64 as 8-byte elements)
-    return host_finish(ctx, {{h_sums, d_out, n1}, {(double*)h_count, d_out + n1, n2}, {(double*)h_runs, d_out + n1 + n2, T + 1},
-                             {h_nb, d_out + n1 + n2 + T + 1, T}});
-    });
-}
-
 int ta_shell_msd(ta_ctx* ctx, int condition, int64_t max_lag, int64_t n_a, const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b,
                  const double* h_dimensions, const int* axes, double r_cut, double r_break, int gap, double* h_sums, int64_t* h_count,
                  int64_t* h_runs, double* h_nb) {
-    return host_call(ctx, [&]() -> int {
-    const ShellArgs a{n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap};
-    ShellPlan p;
-    TA_CHECK(need_ctx(ctx));
-    TA_CHECK(shell_msd_plan(ctx, condition, max_lag, a, h_sums || h_count || h_runs || h_nb, &p));
-    if (ctx->is_cpu)
-        return cpu_rc(ctx, ta::cpu::shell_msd(cpu_state(ctx), condition, max_lag, p.n_a, p.ida.data(), p.n_b, p.idb.data(), p.box.data(),
-                                              p.box.per_frame, p.cuts, p.gap, h_sums, h_count, h_runs, h_nb));
-    double* d_out = nullptr;
-    const ShellMsd m{condition, max_lag, h_sums, h_count};  // (which outputs are asked for: shell_launch points them into d_out)
-    TA_CHECK(shell_launch(ctx, 0, p, nullptr, h_runs, h_nb, ctx->stream, &d_out, &m));
-    const size_t T = (size_t)ctx->st_T, n1 = (size_t)(max_lag + 1) * (size_t)p.D, n2 = (size_t)max_lag + 1;  // (int64 as 8-byte elements)
-    return host_finish(ctx, {{h_sums, d_out, n1}, {(double*)h_count, d_out + n1, n2}, {(double*)h_runs, d_out + n1 + n2, T + 1},
-                             {h_nb, d_out + n1 + n2 + T + 1, T}});
-    });
+    return shell_host(ctx, SHELL_MSD, 0, {n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap, condition, max_lag},
+                      {h_sums, h_count, h_runs, h_nb});
+}
+int ta_shell_orient(ta_ctx* ctx, int condition, int64_t max_lag, int mode, int anchor, const int32_t* h_index, int64_t n_a,
+                    const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes, double r_cut,
+                    double r_break, int gap, double* h_sums, int64_t* h_count, int64_t* h_runs, double* h_nb) {
+    return shell_host(ctx, SHELL_ORIENT, 0,
+                      {n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap, condition, max_lag, mode, anchor, h_index},
+                      {h_sums, h_count, h_runs, h_nb});
 }
 
 // The host slabs of a context go away (ta_compound: they hold atoms, the staged slab no longer does)

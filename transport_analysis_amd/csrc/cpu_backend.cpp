@@ -1437,19 +1437,21 @@ int bond_lifetime(const State& s, bool fft, int64_t P, int n_at, const int32_t* 
                   const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb) {
     TA_PAIR_DISPATCH(bond_lifetime_t, s, fft, P, n_at, atoms, hm, per_frame, cuts, gap, ci, runs, nb);
 }
-int shell_residence(const State& s, bool fft, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
-                    bool per_frame, const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb) {
-    TA_PAIR_DISPATCH(shell_residence_t, s, fft, n_a, ida, n_b, idb, hm, per_frame, cuts, gap, ci, runs, nb);
+// (the templates take the shared arguments of a shell call one by one)
+#define TA_SHELL_ITEMS c.n_a, c.ida, c.n_b, c.idb, c.hm, c.per_frame, *c.cuts, c.gap
+int shell_residence(const State& s, bool fft, const ShellItems& c, double* ci, int64_t* runs, double* nb) {
+    const double* hm = c.hm;
+    TA_PAIR_DISPATCH(shell_residence_t, s, fft, TA_SHELL_ITEMS, ci, runs, nb);
 }
-int shell_msd(const State& s, int condition, int64_t max_lag, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb,
-              const double* hm, bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs, double* nb) {
-    TA_PAIR_DISPATCH(shell_msd_t, s, condition, max_lag, n_a, ida, n_b, idb, hm, per_frame, cuts, gap, sums, count, runs, nb);
+int shell_msd(const State& s, int condition, int64_t max_lag, const ShellItems& c, double* sums, int64_t* count, int64_t* runs, double* nb) {
+    const double* hm = c.hm;
+    TA_PAIR_DISPATCH(shell_msd_t, s, condition, max_lag, TA_SHELL_ITEMS, sums, count, runs, nb);
 }
 #undef TA_PAIR_DISPATCH
-int shell_orient(const State& s, int condition, int64_t max_lag, int mode, const int32_t* index, int64_t n_a, const int32_t* ida, int64_t n_b,
-                 const int32_t* idb, const double* hm, bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs,
-                 double* nb) {
-#define TA_SO_ARGS s, condition, max_lag, index, n_a, ida, n_b, idb, hm, per_frame, cuts, gap, sums, count, runs, nb
+int shell_orient(const State& s, int condition, int64_t max_lag, int mode, const int32_t* index, const ShellItems& c, double* sums,
+                 int64_t* count, int64_t* runs, double* nb) {
+    const double* hm = c.hm;
+#define TA_SO_ARGS s, condition, max_lag, index, TA_SHELL_ITEMS, sums, count, runs, nb
 #define TA_SO_MODE(E, P)                                                                 \
     return mode == ORIENT_BOND       ? shell_orient_t<E, P, ORIENT_BOND>(TA_SO_ARGS)     \
            : mode == ORIENT_BISECTOR ? shell_orient_t<E, P, ORIENT_BISECTOR>(TA_SO_ARGS) \
@@ -1462,6 +1464,7 @@ int shell_orient(const State& s, int condition, int64_t max_lag, int mode, const
     TA_SO_MODE(double, false);
 #undef TA_SO_MODE
 #undef TA_SO_ARGS
+#undef TA_SHELL_ITEMS
 }
 
 template <class E>

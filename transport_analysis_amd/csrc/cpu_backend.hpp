@@ -111,22 +111,31 @@ int pair_lifetime(const State& s, bool fft, int64_t P, const int32_t* pairs, con
 // level, hysteresis and closing of absences of up to `gap` frames on the packed words, as k_bond_series and k_pair_filter
 int bond_lifetime(const State& s, bool fft, int64_t P, int n_at, const int32_t* atoms, const double* hm, bool per_frame,
                   const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb);
+// What the three shell calls share: the reference items ida and the observed items idb, hm and per_frame as
+// vanhove_distinct's, the squared form and break radii (cuts->rc2, cuts->rb2) and the tolerated absence in frames
+struct ShellItems {
+    int64_t n_a;
+    const int32_t* ida;
+    int64_t n_b;
+    const int32_t* idb;
+    const double* hm;
+    bool per_frame;
+    const BondCuts* cuts;
+    int gap;
+};
 // ta_shell_residence: the same three sums of the n_b series of the observed items idb against ALL reference items ida (one
 // with the observed item's own id does not count): bond_math.hpp's shell_level of "some reference item closer than
 // sqrt(rc2)" / "... sqrt(rb2)", then bond_lifetime's filters, as k_shell_series and k_pair_filter.  OpenMP over observed items.
-int shell_residence(const State& s, bool fft, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb, const double* hm,
-                    bool per_frame, const BondCuts& cuts, int gap, double* ci, int64_t* runs, double* nb);
+int shell_residence(const State& s, bool fft, const ShellItems& c, double* ci, int64_t* runs, double* nb);
 // ta_shell_msd: shell_residence's series g, its runs and nb, and sums (max_lag + 1, D), count (max_lag + 1): the squared
 // displacements of the observed items over the lags 0 ... max_lag, gated by g under `condition` (shell_msd_math.hpp, as
 // k_shell_msd: the same term and gates); any output may be NULL.  OpenMP over observed items.
-int shell_msd(const State& s, int condition, int64_t max_lag, int64_t n_a, const int32_t* ida, int64_t n_b, const int32_t* idb,
-              const double* hm, bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs, double* nb);
+int shell_msd(const State& s, int condition, int64_t max_lag, const ShellItems& c, double* sums, int64_t* count, int64_t* runs, double* nb);
 // ta_shell_orient: shell_msd's gated sums with shell_orient_math.hpp's term in place of the squared displacement: sums
 // (max_lag + 1, 2) = (sum c, sum c c), c = u(t) . u(t + k), u the unit vector of index row n (orient_row_len(mode) atoms of slab 0,
 // dim 3; orient_math.hpp's sequence with hm as the image step's box), gated by the series of observed item n, the row's anchor
-int shell_orient(const State& s, int condition, int64_t max_lag, int mode, const int32_t* index, int64_t n_a, const int32_t* ida, int64_t n_b,
-                 const int32_t* idb, const double* hm, bool per_frame, const BondCuts& cuts, int gap, double* sums, int64_t* count, int64_t* runs,
-                 double* nb);
+int shell_orient(const State& s, int condition, int64_t max_lag, int mode, const int32_t* index, const ShellItems& c, double* sums,
+                 int64_t* count, int64_t* runs, double* nb);
 // ta_compound: out (n_frames, n_compounds, dim) float64 = sum_{i in [offsets[c], offsets[c + 1])} w_i x[t, members[i], d] -
 // g_c F[t, d] of slab 0 (g_c = sum_i w_i, F = sum_a u_a x[t, a, d]; frame_weights NULL: no such term; weights NULL: all 1),
 // the sum in member order (the first product, then fma), parallel over compounds; arguments checked by the caller

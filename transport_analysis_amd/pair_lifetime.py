@@ -213,21 +213,28 @@ class PairLifetime(CollectiveAnalysis):
     def _correlate(self, fft, sums):
         return None  # the sums are the result: there is no correlation step
 
+    def _run_sums(self, n_in, run_lengths):
+        """(n0, cc, mean_run) of the bonded (inside) counts per frame and the run-length histogram: n0[tau] = sum_{t < T - tau}
+        n_in[t], cc[tau] = sum_{l > tau} run_lengths[l] (l - tau), suffix sums in int64; the mean run length times dt"""
+        T = self.n_frames
+        n0 = np.cumsum(n_in)[::-1].copy()
+        ell = np.arange(T + 1, dtype=np.int64)
+        s0 = np.cumsum(run_lengths[::-1])[::-1]          # s0[k] = sum_{l >= k} runs[l]
+        s1 = np.cumsum((ell * run_lengths)[::-1])[::-1]  # s1[k] = sum_{l >= k} l runs[l]
+        cc = s1[1:] - ell[:T] * s0[1:]
+        n_runs = int(run_lengths.sum())
+        dt = float(self.times[1] - self.times[0]) if T > 1 else 0.0
+        return n0, cc, float(s1[0]) / n_runs * dt if n_runs else float("nan")
+
     def _store(self, sums, _):
         ci, runs, nb, staged = sums
-        r, T = self.results, self.n_frames
+        r = self.results
         setattr(r, self._result_keys[0], self._union[np.asarray(staged, dtype=np.int64)].reshape(-1, self._n_at))
         r.times = self.lag_times()
         r.n_bonded = np.rint(nb).astype(np.int64)
         r.coordination = float(np.mean(r.n_bonded / float(self.n_a)))
         r.run_lengths = np.asarray(runs, dtype=np.int64)
-        # n0[tau] = sum_{t < T - tau} n_bonded[t];  cc[tau] = sum_{l > tau} run_lengths[l] (l - tau): suffix sums in int64
-        n0 = np.cumsum(r.n_bonded)[::-1].copy()
-        ell = np.arange(T + 1, dtype=np.int64)
-        s0 = np.cumsum(r.run_lengths[::-1])[::-1]          # s0[k] = sum_{l >= k} runs[l]
-        s1 = np.cumsum((ell * r.run_lengths)[::-1])[::-1]  # s1[k] = sum_{l >= k} l runs[l]
-        tau = ell[:T]
-        cc = s1[1:] - tau * s0[1:]
+        n0, cc, r.mean_run = self._run_sums(r.n_bonded, r.run_lengths)
         if not r.n_bonded.any():
             warnings.warn(f"{type(self).__name__}: no pair is bonded in any frame; the correlation functions are nan", UserWarning,
                           stacklevel=4)
@@ -236,6 +243,3 @@ class PairLifetime(CollectiveAnalysis):
             r.continuous = cc / n0.astype(np.float64)
         r.tau_intermittent = _trapezoid(r.intermittent, r.times)
         r.tau_continuous = _trapezoid(r.continuous, r.times)
-        n_runs = int(r.run_lengths.sum())
-        dt = float(self.times[1] - self.times[0]) if T > 1 else 0.0
-        r.mean_run = float(s1[0]) / n_runs * dt if n_runs else float("nan")

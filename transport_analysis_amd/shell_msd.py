@@ -8,18 +8,12 @@ displacements over the lags 0 ... ``max_lag``, every term gated by bits of g, re
 """
 from __future__ import annotations
 
-import warnings
-
 import numpy as np
 
-from ._lib import SHELL_CONDITIONS
-from .shell_residence import ShellResidence
-
-#: the library's cap on ``max_lag`` (eight passes of 256 lags)
-MAX_LAG_CAP = 2047
+from .shell_residence import MAX_LAG_CAP, _GatedShell  # noqa: F401  (MAX_LAG_CAP: this module's name for it stays)
 
 
-class ShellMSD(ShellResidence):
+class ShellMSD(_GatedShell):
     r"""MSD of the observed atoms while they are in the shell of a reference group.
 
     .. math:: MSD_j(\tau) = \frac{\sum_q \sum_{t < T - \tau} w_q(t, \tau) (x_{q,j}(t + \tau) - x_{q,j}(t))^2}
@@ -63,20 +57,13 @@ class ShellMSD(ShellResidence):
     _by_particle_message = ("ShellMSD has no per-particle result: the sums run over all observed atoms "
                             "(by_particle=True is not supported)")
     _result_keys = ("times", "count", "msd_axes", "msd", "n_inside", "mean_inside", "run_lengths", "survival")
+    _nothing_inside = "no observed atom is inside the shell in any frame; the MSD is nan"
 
     def __init__(self, reference, observed=None, *, r_cut, r_break=None, intermittency=0, max_lag=None, condition="continuous",
                  unwrap=False, periodic=True, dim_type="xyz", **kwargs):
-        if "fft" in kwargs:
-            raise TypeError("ShellMSD does not take fft=: the gate is a product over the frames between origin and lag, "
-                            "there is no FFT form")
-        if condition not in SHELL_CONDITIONS:
-            raise ValueError(f"condition must be one of {sorted(SHELL_CONDITIONS)}, got {condition!r}")
-        if max_lag is not None:
-            if int(max_lag) != max_lag or max_lag < 0:
-                raise ValueError(f"max_lag must be an integer >= 0, got {max_lag}")
-            if max_lag > MAX_LAG_CAP:
-                raise ValueError(f"max_lag must be at most {MAX_LAG_CAP}, got {max_lag}")
-            max_lag = int(max_lag)
+        self._refuse_fft(kwargs)
+        self._check_condition(condition)
+        max_lag = self._check_max_lag(max_lag)
         super().__init__(reference, observed, r_cut=r_cut, r_break=r_break, intermittency=intermittency, periodic=periodic,
                          fft=False, dim_type=dim_type, **kwargs)
         self.max_lag, self.condition = max_lag, condition
@@ -86,12 +73,6 @@ class ShellMSD(ShellResidence):
         # float32 staging stays float32 on the device: the kernels read it as it is (the unwrap pass works on float64 slabs)
         self._ctx.set_option("stage_device_f32", int(dtype == np.float32 and not self._unwrap))
 
-    def _prepare(self):
-        if self.max_lag is not None and self.max_lag > self.n_frames - 1:
-            raise ValueError(f"max_lag = {self.max_lag} needs more than the {self.n_frames} analysed frames")
-        self._max_lag = min(self.n_frames - 1, 1024) if self.max_lag is None else self.max_lag
-        super()._prepare()
-
     def _moments(self, fft, lo, hi, correlate):
         all_a = self.n_a == self.n_particles
         out = self._ctx.shell_msd(self.condition, self._max_lag, self.r_cut, r_break=self.r_break, gap=self.intermittency,
@@ -100,17 +81,7 @@ class ShellMSD(ShellResidence):
         return out, None
 
     def _store(self, sums, _):
-        S, count, runs, nb = sums
-        r, L = self.results, self._max_lag
-        r.times = self.lag_times()[:L + 1]
-        r.count = np.asarray(count, dtype=np.int64)
-        r.n_inside = np.rint(nb).astype(np.int64)
-        r.mean_inside = float(np.mean(r.n_inside))
-        r.run_lengths = np.asarray(runs, dtype=np.int64)
-        n0 = np.cumsum(r.n_inside)[::-1][:L + 1].astype(np.float64)
-        if not r.n_inside.any():
-            warnings.warn("ShellMSD: no observed atom is inside the shell in any frame; the MSD is nan", UserWarning, stacklevel=4)
+        S, r = self._store_gated(sums), self.results
         with np.errstate(divide="ignore", invalid="ignore"):
-            r.msd_axes = np.where(r.count[:, None] > 0, np.asarray(S, dtype=np.float64) / r.count[:, None], np.nan)
-            r.survival = r.count / n0
+            r.msd_axes = np.where(r.count[:, None] > 0, S / r.count[:, None], np.nan)
         r.msd = r.msd_axes.sum(axis=1)

@@ -10,17 +10,14 @@ backend's twin (the same arithmetic); a GPU context never falls back to it.
 """
 from __future__ import annotations
 
-import warnings
-
 import numpy as np
 
-from ._lib import ORIENT_MODES, SHELL_CONDITIONS
+from ._lib import ORIENT_MODES
 from .pair_lifetime import _trapezoid
-from .shell_msd import MAX_LAG_CAP
-from .shell_residence import ShellResidence
+from .shell_residence import _GatedShell
 
 
-class ShellOrientation(ShellResidence):
+class ShellOrientation(_GatedShell):
     r"""C_1 and C_2 of molecule-fixed unit vectors while their molecule is in the shell of a reference group.
 
     .. math:: C_1(\tau) = \frac{\sum_n \sum_{t < T - \tau} w_n(t, \tau)\, c}{N(\tau)}, \qquad
@@ -72,24 +69,17 @@ class ShellOrientation(ShellResidence):
     _by_particle_message = ("ShellOrientation has no per-particle result: the sums run over all vectors "
                             "(by_particle=True is not supported)")
     _result_keys = ("times", "count", "c1", "c2", "n_inside", "mean_inside", "run_lengths", "survival", "tau_1", "tau_2")
+    _nothing_inside = "no anchor atom is inside the shell in any frame; the correlation functions are nan"
 
     def __init__(self, reference, atomgroup, vectors, *, mode="bond", anchor=0, r_cut, r_break=None, intermittency=0, max_lag=None,
                  condition="continuous", periodic=True, dim_type="xyz", **kwargs):
-        if "fft" in kwargs:
-            raise TypeError("ShellOrientation does not take fft=: the gate is a product over the frames between origin and lag, "
-                            "there is no FFT form")
+        self._refuse_fft(kwargs)
         if dim_type != "xyz":
             raise ValueError(f"ShellOrientation needs dim_type='xyz' (a unit vector has three components), got {dim_type!r}")
-        if condition not in SHELL_CONDITIONS:
-            raise ValueError(f"condition must be one of {sorted(SHELL_CONDITIONS)}, got {condition!r}")
+        self._check_condition(condition)
         if mode not in ORIENT_MODES:
             raise ValueError(f"mode: {mode!r}, expected one of {sorted(ORIENT_MODES)}")
-        if max_lag is not None:
-            if int(max_lag) != max_lag or max_lag < 0:
-                raise ValueError(f"max_lag must be an integer >= 0, got {max_lag}")
-            if max_lag > MAX_LAG_CAP:
-                raise ValueError(f"max_lag must be at most {MAX_LAG_CAP}, got {max_lag}")
-            max_lag = int(max_lag)
+        max_lag = self._check_max_lag(max_lag)
         width = 2 if mode == "bond" else 3
         if int(anchor) != anchor or not 0 <= anchor < width:
             raise ValueError(f"anchor must be a column of vectors, 0 ... {width - 1}, got {anchor}")
@@ -116,12 +106,6 @@ class ShellOrientation(ShellResidence):
         rows = np.searchsorted(self._union, atoms)
         self.vectors = np.ascontiguousarray(rows[np.argsort(rows[:, self.anchor], kind="stable")], dtype=np.int32)
 
-    def _prepare(self):
-        if self.max_lag is not None and self.max_lag > self.n_frames - 1:
-            raise ValueError(f"max_lag = {self.max_lag} needs more than the {self.n_frames} analysed frames")
-        self._max_lag = min(self.n_frames - 1, 1024) if self.max_lag is None else self.max_lag
-        super()._prepare()
-
     def _moments(self, fft, lo, hi, correlate):
         all_a = self.n_a == self.n_particles
         out = self._ctx.shell_orient(self.condition, self._max_lag, self.vectors, self.mode, self.r_cut, anchor=self.anchor,
@@ -130,21 +114,9 @@ class ShellOrientation(ShellResidence):
         return out, None
 
     def _store(self, sums, _):
-        S, count, runs, nb = sums
-        r, L = self.results, self._max_lag
-        r.times = self.lag_times()[:L + 1]
-        r.count = np.asarray(count, dtype=np.int64)
-        r.n_inside = np.rint(nb).astype(np.int64)
-        r.mean_inside = float(np.mean(r.n_inside))
-        r.run_lengths = np.asarray(runs, dtype=np.int64)
-        n0 = np.cumsum(r.n_inside)[::-1][:L + 1].astype(np.float64)
-        if not r.n_inside.any():
-            warnings.warn("ShellOrientation: no anchor atom is inside the shell in any frame; the correlation functions are nan",
-                          UserWarning, stacklevel=4)
-        S = np.asarray(S, dtype=np.float64)
+        S, r = self._store_gated(sums), self.results
         with np.errstate(divide="ignore", invalid="ignore"):
             r.c1 = np.where(r.count > 0, S[:, 0] / r.count, np.nan)
             r.c2 = np.where(r.count > 0, (3.0 * S[:, 1] / r.count - 1.0) / 2.0, np.nan)
-            r.survival = r.count / n0
         r.tau_1 = _trapezoid(r.c1, r.times)
         r.tau_2 = _trapezoid(r.c2, r.times)

@@ -19,8 +19,12 @@ import warnings
 
 import numpy as np
 
+from ._lib import SHELL_CONDITIONS
 from .pair_lifetime import PairLifetime, _trapezoid
 from .vanhove_distinct import _sorted_ix
+
+#: the library's cap on ``max_lag`` of the gated sums (eight passes of 256 lags)
+MAX_LAG_CAP = 2047
 
 
 class ShellResidence(PairLifetime):
@@ -91,17 +95,12 @@ class ShellResidence(PairLifetime):
 
     def _store(self, sums, _):
         ci, runs, nb = sums
-        r, T = self.results, self.n_frames
+        r = self.results
         r.times = self.lag_times()
         r.n_inside = np.rint(nb).astype(np.int64)
         r.mean_inside = float(np.mean(r.n_inside))
         r.run_lengths = np.asarray(runs, dtype=np.int64)
-        # n0[tau] = sum_{t < T - tau} n_inside[t];  cc[tau] = sum_{l > tau} run_lengths[l] (l - tau): suffix sums in int64
-        n0 = np.cumsum(r.n_inside)[::-1].copy()
-        ell = np.arange(T + 1, dtype=np.int64)
-        s0 = np.cumsum(r.run_lengths[::-1])[::-1]
-        s1 = np.cumsum((ell * r.run_lengths)[::-1])[::-1]
-        cc = s1[1:] - ell[:T] * s0[1:]
+        n0, cc, r.mean_run = self._run_sums(r.n_inside, r.run_lengths)
         if not r.n_inside.any():
             warnings.warn("ShellResidence: no observed atom is inside the shell in any frame; the residence functions are nan",
                           UserWarning, stacklevel=4)
@@ -110,6 +109,53 @@ class ShellResidence(PairLifetime):
             r.survival = cc / n0.astype(np.float64)
         r.tau_intermittent = _trapezoid(r.intermittent, r.times)
         r.tau_residence = _trapezoid(r.survival, r.times)
-        n_runs = int(r.run_lengths.sum())
-        dt = float(self.times[1] - self.times[0]) if T > 1 else 0.0
-        r.mean_run = float(s1[0]) / n_runs * dt if n_runs else float("nan")
+
+
+class _GatedShell(ShellResidence):
+    """What ShellMSD and ShellOrientation share: sums over the lags 0 ... ``max_lag`` whose terms are gated by the shell series
+    under ``condition``, in the place of ShellResidence's lag sums."""
+
+    _nothing_inside = None  # the warning where no series is ever inside, behind "<class name>: "
+
+    def _refuse_fft(self, kwargs):
+        if "fft" in kwargs:
+            raise TypeError(f"{type(self).__name__} does not take fft=: the gate is a product over the frames between origin and lag, "
+                            "there is no FFT form")
+
+    @staticmethod
+    def _check_condition(condition):
+        if condition not in SHELL_CONDITIONS:
+            raise ValueError(f"condition must be one of {sorted(SHELL_CONDITIONS)}, got {condition!r}")
+
+    @staticmethod
+    def _check_max_lag(max_lag):
+        """max_lag as an int, or None"""
+        if max_lag is None:
+            return None
+        if int(max_lag) != max_lag or max_lag < 0:
+            raise ValueError(f"max_lag must be an integer >= 0, got {max_lag}")
+        if max_lag > MAX_LAG_CAP:
+            raise ValueError(f"max_lag must be at most {MAX_LAG_CAP}, got {max_lag}")
+        return int(max_lag)
+
+    def _prepare(self):
+        if self.max_lag is not None and self.max_lag > self.n_frames - 1:
+            raise ValueError(f"max_lag = {self.max_lag} needs more than the {self.n_frames} analysed frames")
+        self._max_lag = min(self.n_frames - 1, 1024) if self.max_lag is None else self.max_lag
+        super()._prepare()
+
+    def _store_gated(self, sums):
+        """times, count, n_inside, mean_inside, run_lengths and survival of the results; returns the gated sums (L + 1, n)"""
+        S, count, runs, nb = sums
+        r, L = self.results, self._max_lag
+        r.times = self.lag_times()[:L + 1]
+        r.count = np.asarray(count, dtype=np.int64)
+        r.n_inside = np.rint(nb).astype(np.int64)
+        r.mean_inside = float(np.mean(r.n_inside))
+        r.run_lengths = np.asarray(runs, dtype=np.int64)
+        n0 = np.cumsum(r.n_inside)[::-1][:L + 1].astype(np.float64)
+        if not r.n_inside.any():  # (one frame further from the caller than a warning of _store's own)
+            warnings.warn(f"{type(self).__name__}: {self._nothing_inside}", UserWarning, stacklevel=5)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r.survival = r.count / n0
+        return np.asarray(S, dtype=np.float64)
