@@ -1,15 +1,17 @@
-"""The ranks of the collective classes' placement tests: IntermediateScattering, CurrentCorrelation, VanHoveSelf and
-DynamicSusceptibility under distributed=True, each rank a fresh child process with its own process group.
+"""The ranks of the collective classes' placement tests: IntermediateScattering, CurrentCorrelation, VanHoveSelf,
+DynamicSusceptibility, PartialScattering and FourPointStructureFactor under distributed=True, each rank a fresh child
+process with its own process group.
 
-A class's test module (test_scattering, test_current_correlation, test_vanhove, test_overlap) gives
+A class's test module (test_scattering, test_current_correlation, test_vanhove, test_overlap, test_partial_scattering,
+test_overlap_density) gives
 
     placed_results(A, **place)   the class run on its case of A atoms with the placement keywords: {name: array}
     check_placed(out, A, what)   those arrays against the reference over ALL atoms, at the bar of the single-device test
     INTEGER_KEYS                 the results that are integers: equal to the single-process run's
 
-and ranks() runs placed_results(A, distributed=True) in `world` children.  The CPU halves (device="cpu", gloo) are unmarked
-tests of those modules; the GPU halves (gloo with two ranks on one GPU, nccl = RCCL with one rank) are in
-test_classes_gpu.py."""
+and ranks() runs placed_results(A, distributed=True) in `world` children.  The CPU halves (device="cpu", gloo; for
+FourPointStructureFactor also "cpu-env": $TA_AMD_DEVICE=cpu and no device= keyword) are unmarked tests of those modules;
+the GPU halves (gloo with two ranks on one GPU, nccl = RCCL with one rank) are in test_classes_gpu.py."""
 import importlib
 import os
 
@@ -17,7 +19,7 @@ import numpy as np
 
 #: first port of each module's groups (test_gpu_dist.py's derivation: + pid % 2000 + A, here + 100 per kind of group)
 PORTS = {"test_scattering": 42000, "test_current_correlation": 44500, "test_vanhove": 47000, "test_overlap": 49500}
-KINDS = {"cpu": 0, "gloo": 100, "nccl": 200}
+KINDS = {"cpu": 0, "gloo": 100, "nccl": 200, "cpu-env": 300}
 
 
 def record_ranges(out, results):
@@ -34,6 +36,10 @@ def _rank(rank, world, port, kind, module, A, out_dir):
     place = {"distributed": True}
     if kind == "cpu":
         place["device"] = "cpu"
+        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    elif kind == "cpu-env":
+        os.environ.pop("LOCAL_RANK", None)
+        os.environ["TA_AMD_DEVICE"] = "cpu"  # no device= keyword: dist.default_device() reads the variable
         dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
     elif kind == "gloo":
         os.environ.pop("LOCAL_RANK", None)

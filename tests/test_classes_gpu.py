@@ -1,6 +1,6 @@
 """The analysis classes on the HIP path, GPU only: IntermediateScattering, CurrentCorrelation, VanHoveSelf, VanHoveDistinct,
-PairLifetime, HydrogenBondLifetime, OrientationalCorrelation, DynamicSusceptibility and PartialScattering (and, staged in
-pieces, ShellResidence, ShellMSD and ShellOrientation) through StagedAnalysis._prepare,
+PairLifetime, HydrogenBondLifetime, OrientationalCorrelation, DynamicSusceptibility, PartialScattering and
+FourPointStructureFactor (and, staged in pieces, ShellResidence, ShellMSD and ShellOrientation) through StagedAnalysis._prepare,
 _single_frame and _conclude -- pinned slabs filled by ta_stage_frame, stage_commit in pieces, "stage_device_f32" as
 _set_options asks for it, the unwrap and ta_compound before the call, the host-facing entry and _store.
 
@@ -9,7 +9,7 @@ _set_options asks for it, the unwrap and ta_compound before the call, the host-f
      printed figures.  Every run of a class in this module is watched (the fixture `watched`): with float32 staging the
      device slabs hold the staged float32 values AS float32 and no widening kernel ran in the call.  One case per class is
      staged in pieces of 32, 32 and 1 frames: the same bits as in one commit.
-  B  the five collective classes on devices=[0, 0] (and one on three members for two atoms), under distributed=True with
+  B  the six collective classes on devices=[0, 0] (and on three members of which the first is empty), under distributed=True with
      two gloo ranks on the one GPU and more ranks than atoms, and with one nccl (RCCL) rank: every result against the
      reference over ALL atoms at the single-device bar, the integers equal to the single-device run's."""
 import ctypes
@@ -22,6 +22,7 @@ import test_bond_lifetime
 import test_current_correlation
 import test_orientation
 import test_overlap
+import test_overlap_density
 import test_pair_lifetime
 import test_partial_scattering as test_partial  # (test_partial_scattering is a test of this module)
 import test_scattering
@@ -35,10 +36,10 @@ from transport_analysis_amd import _base, _lib
 pytestmark = pytest.mark.gpu
 
 STAGING = [pytest.param(np.float32, id="stage32"), pytest.param(np.float64, id="stage64")]
-COLLECTIVE = [test_scattering, test_current_correlation, test_vanhove, test_overlap, test_partial]
-MODULE_IDS = ["scattering", "current", "vanhove_self", "overlap", "partial_scattering"]
+COLLECTIVE = [test_scattering, test_current_correlation, test_vanhove, test_overlap, test_partial, test_overlap_density]
+MODULE_IDS = ["scattering", "current", "vanhove_self", "overlap", "partial_scattering", "four_point"]
 ATOMS = {test_scattering: 13, test_current_correlation: 33, test_vanhove: 13, test_overlap: 13,
-         test_partial: 33}  # odd: the blocks differ
+         test_partial: 33, test_overlap_density: 13}  # odd: the blocks differ
 
 
 def device_slab_bits(c, slab, dtype):
@@ -161,6 +162,19 @@ def test_partial_scattering(dtype, watched):
     saw(watched, "PartialScattering", dtype)
 
 
+@pytest.mark.parametrize("dtype", STAGING)
+def test_four_point_structure_factor(dtype, watched):
+    """explicit wavevectors in d = 1, 2, 3 with the k = 0 row against DynamicSusceptibility on the same placement, a scalar
+    cutoff and lags=None, float32 positions, q= / dq= of the box at frame 0 with and without unwrap=True (ta_unwrap, then the
+    kernel on float64 slabs), compound= with and without the barycentric frame (ta_compound, then the kernel on its slab)"""
+    test_overlap_density.class_against_reference(**on_gpu(dtype))
+    test_overlap_density.class_scalar_cutoff_and_default_lags(**on_gpu(dtype))
+    test_overlap_density.class_float32_staging_is_the_same(**on_gpu(dtype))
+    test_overlap_density.class_box_shells_and_unwrap(**on_gpu(dtype))
+    test_overlap_density.compounds_with_dyadic_weights(**on_gpu(dtype))
+    saw(watched, "FourPointStructureFactor", dtype)
+
+
 _cpu_class = {}
 
 
@@ -242,9 +256,9 @@ def test_orientational_correlation_minimum_image(dims, moving, mode, dtype, watc
 # ---- staging in pieces --------------------------------------------------------------------------------------------------------
 def piece_cases():
     """{class name: a function that builds the class on 65 frames on device 0}"""
-    from transport_analysis_amd import (CurrentCorrelation, DynamicSusceptibility, HydrogenBondLifetime, IntermediateScattering,
-                                        OrientationalCorrelation, PartialScattering, ShellMSD, ShellOrientation, ShellResidence,
-                                        VanHoveDistinct, VanHoveSelf)
+    from transport_analysis_amd import (CurrentCorrelation, DynamicSusceptibility, FourPointStructureFactor, HydrogenBondLifetime,
+                                        IntermediateScattering, OrientationalCorrelation, PartialScattering, ShellMSD,
+                                        ShellOrientation, ShellResidence, VanHoveDistinct, VanHoveSelf)
     from transport_analysis_amd._mini_mda import ArrayUniverse
 
     def scattering():
@@ -288,6 +302,10 @@ def piece_cases():
         x, w, lab, k = test_partial.ref.case(65, 33, 3, 3, 3)[:4]
         return PartialScattering(ArrayUniverse(positions=x).atoms, k, species=lab, weights=w, device=0)
 
+    def four_point():
+        x, k, lags = test_overlap_density.ref.case(65, 13, 3)[:3]
+        return FourPointStructureFactor(ArrayUniverse(positions=x).atoms, k, lags, cutoff=test_overlap_density.ref.CUTOFFS, device=0)
+
     def shell_cuts(cuts, dims):
         return dict(r_cut=cuts["r_cut"], r_break=cuts["r_break"], intermittency=1, periodic=dims is not None, device=0)
 
@@ -306,7 +324,8 @@ def piece_cases():
         return ShellOrientation(reference, group, vectors, mode="bond", anchor=0, max_lag=30, **shell_cuts(cuts, True))
 
     return {f.__name__: f for f in (scattering, current, vanhove_self, vanhove_distinct, pair_lifetime, hydrogen_bonds, orientation,
-                                    susceptibility, partial_scattering, shell_residence, shell_msd, shell_orientation)}
+                                    susceptibility, partial_scattering, four_point, shell_residence, shell_msd,
+                                    shell_orientation)}
 
 
 def same_bits(a, b):
@@ -358,11 +377,24 @@ def test_two_members_on_one_device(mod, watched):
     assert len(watched) >= 3  # (the single run and both members)
 
 
-def test_three_members_two_atoms_one_member_empty(watched):
-    out = test_vanhove.placed_results(2, devices=[0, 0, 0])
-    assert out["device_ranges"].tolist() == [[0, 0], [0, 1], [1, 2]]
-    test_vanhove.check_placed(out, 2, "devices=[0, 0, 0]")
-    assert np.array_equal(out["counts"], test_vanhove.placed_results(2, device=0)["counts"])
+#: the fewest atoms a module's case can be built with (partial_ref's three species need three)
+FEWEST_ATOMS = {test_partial: 3}
+
+
+@pytest.mark.parametrize("mod", COLLECTIVE, ids=MODULE_IDS)
+def test_three_members_two_atoms_one_member_empty(mod, watched):
+    """A atoms on A + 1 members (two on devices=[0, 0, 0]; PartialScattering three on four): the FIRST member holds none, the
+    others one atom each with its own slice of the per-atom weights and labels"""
+    A = FEWEST_ATOMS.get(mod, 2)
+    out = mod.placed_results(A, devices=[0] * (A + 1))
+    assert out["device_ranges"].tolist() == [[0, 0]] + [[i, i + 1] for i in range(A)]
+    mod.check_placed(out, A, f"devices={[0] * (A + 1)}")
+    single = mod.placed_results(A, device=0)
+    for key in mod.INTEGER_KEYS:
+        assert out[key].dtype == np.int64 and np.array_equal(out[key], single[key]), key
+    if mod is test_vanhove:
+        assert out["device_ranges"].tolist() == [[0, 0], [0, 1], [1, 2]]
+        assert np.array_equal(out["counts"], single["counts"])
 
 
 @pytest.mark.parametrize("more_ranks_than_atoms", [False, True], ids=["odd", "one-atom"])

@@ -1,17 +1,25 @@
 """The overlap field's density per origin and S_4 (ta_overlap_density*, FourPointStructureFactor) on the CPU backend
 (Context("cpu"), device="cpu"): the C-ABI and every error return, closed forms, the long-double reference of
 overlap_density_ref (within its bar), shards, threads and the class.  (The one return that needs a slab of 2^31 columns,
-n_atoms dim >= 2^31, is not reached here.)"""
+n_atoms dim >= 2^31, is not reached here.)  The class tests' bodies take the placement keywords: test_classes_gpu.py calls
+them with device=0, and placed_results / check_placed (placement.py) are the class on device groups and across ranks --
+here two gloo ranks on the CPU backend, chosen by device="cpu" and by $TA_AMD_DEVICE=cpu."""
 import ctypes
+import functools
+import sys
 
 import numpy as np
 import pytest
 
 import overlap_density_ref as ref
+import placement
+import test_exact_overlap_density as exact_density
+from oracle import exact
 from test_vanhove import wrapped_walk
 from transport_analysis_amd import DynamicSusceptibility, FourPointStructureFactor, _lib, log_lags
 from transport_analysis_amd._base import UpdatingAtomGroup
 from transport_analysis_amd._mini_mda import ArrayUniverse
+from transport_analysis_amd.scattering import kvectors_from_box
 
 LD = np.longdouble
 TWO_PI = 6.283185307179586476925
@@ -293,10 +301,10 @@ def test_class_against_reference():
     class_against_reference(device="cpu")
 
 
-def test_class_scalar_cutoff_and_default_lags():
+def class_scalar_cutoff_and_default_lags(**place):
     case = ref.case(200, 13, 3)
     x, k = case[:2]
-    r = FourPointStructureFactor(ArrayUniverse(positions=x).atoms, k, cutoff=1.5, device="cpu").run().results
+    r = FourPointStructureFactor(ArrayUniverse(positions=x).atoms, k, cutoff=1.5, **place).run().results
     lags = log_lags(200)
     assert np.array_equal(r.lags, lags)
     assert r.w_by_origin.shape == (5, 1, len(lags), 200) and r.s4.shape == (5, 1, len(lags))
@@ -304,21 +312,29 @@ def test_class_scalar_cutoff_and_default_lags():
     ref.assert_w(r.w_by_origin, (x, k, lags, W, Q, ref.bar(x, k, Q)), what="scalar cutoff")
 
 
-def test_class_float32_staging_is_the_same():
+def test_class_scalar_cutoff_and_default_lags():
+    class_scalar_cutoff_and_default_lags(device="cpu")
+
+
+def class_float32_staging_is_the_same(**place):
     case = ref.case(65, 13, 3)
     x, k, lags = case[:3]
-    r = FourPointStructureFactor(ArrayUniverse(positions=x.astype(np.float32)).atoms, k, lags, cutoff=ref.CUTOFFS, device="cpu").run().results
+    r = FourPointStructureFactor(ArrayUniverse(positions=x.astype(np.float32)).atoms, k, lags, cutoff=ref.CUTOFFS, **place).run().results
     ref.assert_w(r.w_by_origin, case, what="float32 staging")
 
 
-def test_class_box_shells_and_unwrap():
+def test_class_float32_staging_is_the_same():
+    class_float32_staging_is_the_same(device="cpu")
+
+
+def class_box_shells_and_unwrap(**place):
     """q= on the box of a wrapped walk: the shell's vectors are commensurate, so the PHASE does not care about wrapping, but the
     DISPLACEMENT does: unwrap=True on the wrapped walk gives the unwrapped walk's W, and leaving it out does not.  s4 is the
     mean of s4_by_kvector over a shell's vectors."""
     walk, wrapped, box = wrapped_walk()
     dims = [*box, 90, 90, 90]
     lags = ref.lag_sample(120)
-    kw = dict(q=(0.55, 0.8), dq=0.3, cutoff=(0.5, 1.5, 4.0), device="cpu")
+    kw = dict(q=(0.55, 0.8), dq=0.3, cutoff=(0.5, 1.5, 4.0), **place)
     a = FourPointStructureFactor(ArrayUniverse(positions=walk, dimensions=dims).atoms, None, lags, **kw).run().results
     b = FourPointStructureFactor(ArrayUniverse(positions=wrapped, dimensions=dims).atoms, None, lags, unwrap=True, **kw).run().results
     w = FourPointStructureFactor(ArrayUniverse(positions=wrapped, dimensions=dims).atoms, None, lags, **kw).run().results
@@ -338,14 +354,18 @@ def test_class_box_shells_and_unwrap():
     assert "unwrap=True" in FourPointStructureFactor.__doc__ and "DISPLACEMENT" in FourPointStructureFactor.__doc__
 
 
-def test_compounds_with_dyadic_weights():
+def test_class_box_shells_and_unwrap():
+    class_box_shells_and_unwrap(device="cpu")
+
+
+def compounds_with_dyadic_weights(**place):
     """16 atoms of equal mass in molecules of 4: the weights 1/4 and 1/16 are dyadic, so the centres (and the centres in the
     barycentric frame) stay on a grid and the indicator is exact; N is the number of compounds"""
     x, k, lags = ref.case(65, 16, 3)[:3]
     mol = np.arange(16) // 4
     u = ArrayUniverse(positions=x, masses=np.full(16, 2.0))
     centres = x.reshape(65, 4, 4, 3).mean(axis=2)
-    kw = dict(cutoff=ref.CUTOFFS, device="cpu")
+    kw = dict(cutoff=ref.CUTOFFS, **place)
     for frame, pos in ((None, centres), ("barycentric", centres - x.mean(axis=1)[:, None, :])):
         extra = {} if frame is None else {"reference_frame": frame}
         r = FourPointStructureFactor(u.atoms, k, lags, compound=mol, **extra, **kw).run().results
@@ -354,6 +374,10 @@ def test_compounds_with_dyadic_weights():
         s4, _ = s4_of(W, lags, 4)
         ok = r.n_origins >= 2
         assert rel_err(r.s4_by_kvector[:, :, ok], s4[:, :, ok]) <= 1e-12  # N is 4
+
+
+def test_compounds_with_dyadic_weights():
+    compounds_with_dyadic_weights(device="cpu")
 
 
 def test_class_refusals():
@@ -392,3 +416,146 @@ def test_class_refusals():
     doc = FourPointStructureFactor.__doc__
     assert "ensemble-dependent" in doc and "origins are correlated" in doc
     assert not hasattr(FourPointStructureFactor, "fit") and "No fit" in doc
+
+
+# ---- the class on several devices and ranks: devices=[...], distributed=True ------------------------------------------------
+PLACED_T = 65
+INTEGER_KEYS = ("exact_w", "exact_q", "box_shell")
+placement.PORTS.setdefault(__name__, 54500)  # (this module's first port, beside the other classes': test_classes_gpu.py too)
+EXACT_SEED = 11
+BOX_KW = dict(q=(0.55, 0.8), dq=0.3, cutoff=(0.5, 1.5, 4.0))
+
+
+@functools.lru_cache(maxsize=None)
+def placed_case(A):
+    """the grid walk of A atoms as overlap_density_ref.case would give it, without that function's 0 < Q_e < N (one atom
+    cannot have it): (x, k, lags, W, Q, bar), computed once"""
+    x = ref.scatter_ref.walk(PLACED_T, A, 3, 1)
+    k, lags = ref.wavevectors(5, 3), ref.lag_sample(PLACED_T)
+    assert not np.any(k[-1]) and np.all(np.any(k[:-1], axis=1))
+    W, Q = ref.reference(x, k, lags, ref.CUTOFFS)
+    return x, k, lags, W, Q, ref.bar(x, k, Q)
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(A):
+    """(x, k, lags, W int64 (K, C, L, T, 2)): integer walks and quarter-turn phases, W a Gaussian integer in every entry"""
+    x = exact.int_walk(PLACED_T, A, 3, 1, EXACT_SEED)
+    lags = exact_density.LAGS[exact_density.LAGS < PLACED_T]
+    W, _, _ = exact_density.exact_w(x, exact_density.QUARTER_Q, lags, exact_density.CUTOFFS)
+    return x, exact.quarter_wavevectors(exact_density.QUARTER_Q), lags, W
+
+
+@functools.lru_cache(maxsize=None)
+def box_case():
+    """test_vanhove.wrapped_walk()'s nine atoms: (walk, wrapped, dims, k, shell, lags, W, Q, bar) with the shells' vectors
+    of the constant box and the reference on the UNWRAPPED walk"""
+    walk, wrapped, box = wrapped_walk()
+    dims = [*box, 90, 90, 90]
+    k, shell = kvectors_from_box(dims, BOX_KW["q"], BOX_KW["dq"])
+    m = k * box / TWO_PI  # commensurate: whole numbers of periods along every edge, in both shells
+    assert np.allclose(m, np.rint(m), atol=1e-12) and set(shell) == {0, 1} and k.shape[0] > 2
+    lags = ref.lag_sample(walk.shape[0])
+    W, Q = ref.reference(walk, k, lags, BOX_KW["cutoff"])
+    return walk, wrapped, dims, k, shell, lags, W, Q, ref.bar(walk, k, Q)
+
+
+def placed_results(A, **place):
+    """FourPointStructureFactor under the placement keywords `place`: {name: array} (placement.py) of three runs --
+    (a) the grid walk of A atoms, (b) the exact integer case of A atoms, with DynamicSusceptibility's Q under the same
+    placement, and for A > 1 (c) the nine wrapped atoms with the wavevectors of the box and unwrap=True, and the unwrapped
+    ones in per-frame boxes of which only frame 0 is that box (the wavevectors are frame 0's on every rank and member)"""
+    from placement import record_ranges
+
+    out = {}
+    x, k, lags = placed_case(A)[:3]
+    r = FourPointStructureFactor(ArrayUniverse(positions=x).atoms, k, lags, cutoff=ref.CUTOFFS, **place).run().results
+    record_ranges(out, r)
+    out.update(w=ref.as_parts(r.w_by_origin), s4=r.s4_by_kvector, s4_uncentred=r.s4_uncentred_by_kvector, n_origins=r.n_origins)
+    x, k, lags, _ = exact_case(A)
+    u = ArrayUniverse(positions=x)
+    got = ref.as_parts(FourPointStructureFactor(u.atoms, k, lags, cutoff=exact_density.CUTOFFS, **place).run().results.w_by_origin)
+    assert np.array_equal(got, np.rint(got))  # whole numbers, whatever they are: nothing is lost in the int64
+    out["exact_w"] = got.astype(np.int64)
+    out["exact_q"] = DynamicSusceptibility(u.atoms, lags, cutoff=exact_density.CUTOFFS, **place).run().results.overlap_by_origin
+    out["box_shell"] = np.zeros(0, dtype=np.int64)
+    if A > 1:
+        walk, wrapped, dims, _, _, lags = box_case()[:6]
+        r = FourPointStructureFactor(ArrayUniverse(positions=wrapped, dimensions=dims).atoms, None, lags, unwrap=True, **BOX_KW,
+                                     **place).run().results
+        out.update(box_k=r.kvectors, box_shell=r.shell, box_w=ref.as_parts(r.w_by_origin))
+        moving = np.tile(np.array(dims, dtype=np.float64), (len(walk), 1))
+        moving[1:, :2] = moving[0, 1::-1]  # (the edges along x and y change places: other vectors, as many per shell)
+        r =FourPointStructureFactor(ArrayUniverse(positions=walk, dimensions=moving).atoms, None, lags[:2], **BOX_KW,
+                                     **place).run().results
+        out.update(first_box_k=r.kvectors, first_box_shell=r.shell)
+    return out
+
+
+def check_placed(out, A, what):
+    """placed_results against the references over ALL atoms.  (a) W within overlap_density_ref's bar and A u_r, the one
+    re-association of the blocks' sums (test_overlap_density_shapes.py's allowance for a group); S_4 and the uncentred one
+    within 1e-12 relative of s4_of(reference W) (test_class_against_reference's bar): the blocks' W are added before
+    anything is squared; NaN exactly where a lag has fewer than two origins.  (b) W EQUAL to exact_w's integers, its k = 0
+    row DynamicSusceptibility's Q.  (c) the wavevectors and shells those of frame 0's box, W of the wrapped atoms with
+    unwrap=True within the bar of the reference on the unwrapped walk."""
+    case = placed_case(A)
+    lags, W = case[2], case[3]
+    ref.assert_w(out["w"], case, what=what, extra_bar=A * ref.U_R)
+    s4, unc = s4_of(W, lags, A)
+    assert np.array_equal(out["n_origins"], PLACED_T - lags)
+    ok = out["n_origins"] >= 2
+    assert ok.sum() == len(lags) - 1  # lag T - 1: one origin
+    err_s, err_u = rel_err(out["s4"][:, :, ok], s4[:, :, ok]), rel_err(out["s4_uncentred"], unc)
+    print(f"    {what}: s4 {err_s:.2e}, uncentred {err_u:.2e} relative")
+    assert err_s <= 1e-12 and err_u <= 1e-12
+    assert np.array_equal(np.isnan(out["s4"]), np.broadcast_to(~ok, out["s4"].shape)) and not np.isnan(out["s4_uncentred"]).any()
+    x, k, lags, W = exact_case(A)
+    bad = int(np.count_nonzero(out["exact_w"] != W))
+    print(f"    {what}: exact W, {bad} of {W.size} components differ (sum |W| {int(np.abs(W).sum())})")
+    assert out["exact_w"].dtype == np.int64 and out["exact_w"].shape == W.shape and bad == 0
+    K0 = exact_density.K0
+    assert np.array_equal(out["exact_w"][K0, ..., 0], out["exact_q"]) and not out["exact_w"][K0, ..., 1].any()
+    assert out["exact_q"].dtype == np.int64 and out["exact_q"][:, 0, :].min() == A  # lag 0: every atom overlaps itself
+    if A > 1:
+        walk, _, _, k, shell, lags, W, Q, b = box_case()
+        for key in ("box_k", "first_box_k"):
+            assert np.array_equal(out[key], k), key
+        assert np.array_equal(out["box_shell"], shell) and np.array_equal(out["first_box_shell"], shell)
+        ref.assert_w(out["box_w"], (walk, k, lags, W, Q, b), what=f"{what} box, unwrap", extra_bar=walk.shape[1] * ref.U_R)
+    else:
+        assert out["box_shell"].size == 0
+
+
+@pytest.mark.parametrize("A", [13, 1])
+def test_class_distributed_two_gloo_ranks_cpu_backend(tmp_path, A):
+    """A = 13: the ranks hold 6 and 7 atoms (and 4 and 5 of the nine wrapped ones); A = 1: rank 0 holds no atom and contributes
+    zeros (_no_moments).  W travels through the all-reduce as float64 (..., 2) and is squared only after it: the S_4 of the
+    two blocks' own W would not add up to the reference's (k = 0, test_overlap_density_shapes.py's threshold)."""
+    placement.check_ranks(sys.modules[__name__], A, 2, "cpu", tmp_path, dict(device="cpu"))
+    if A > 1:
+        x, k, lags, W = placed_case(A)[:4]
+        ok = (PLACED_T - lags) >= 2
+        s4, _ = s4_of(W, lags, A)
+        halves = [s4_of(ref.reference(x[:, lo:hi], k, lags, ref.CUTOFFS)[0], lags, A)[0] for lo, hi in ((0, A // 2), (A // 2, A))]
+        assert float(np.max(np.abs((halves[0] + halves[1])[-1][:, ok] - s4[-1][:, ok]))) > 1e-3  # (what summing variances would give)
+
+
+def test_class_distributed_with_the_cpu_backend_from_the_environment(tmp_path):
+    """the ranks set $TA_AMD_DEVICE=cpu and give no device=: dist.default_device() hands the CPU backend on as
+    _lib.device_index does (it used to be int("cpu")).  The same checks as with device="cpu"."""
+    placement.check_ranks(sys.modules[__name__], 13, 2, "cpu-env", tmp_path, dict(device="cpu"))
+
+
+def test_default_device_and_a_cpu_backend_under_nccl(monkeypatch):
+    from transport_analysis_amd import dist as tad
+
+    monkeypatch.setenv("TA_AMD_DEVICE", "cpu")
+    assert tad.default_device() == _lib.DEVICE_CPU == _lib.device_index(tad.default_device())
+    monkeypatch.setattr(tad, "uses_device_reduce", lambda: True)
+    with pytest.raises(ValueError, match="selects the CPU backend, but the process group's backend is nccl"):
+        tad.default_device()
+    with pytest.raises(ValueError, match="selects the CPU backend, but the process group's backend is nccl"):
+        tad.check_backend(_lib.DEVICE_CPU, 'device="cpu"')
+    monkeypatch.setenv("TA_AMD_DEVICE", "3")
+    assert tad.default_device() == 3 == tad.check_backend(3, "device=3")

@@ -372,9 +372,10 @@ class StagedAnalysis(AnalysisBase):
         self._source = self._group  # whose arrays a frame is read from
         self._rccl = False  # the lag sums stay on the GPU through the reduce
         if self._distributed:
-            from .dist import shard_of_this_rank, uses_device_reduce
+            from .dist import check_backend, shard_of_this_rank, uses_device_reduce
 
             _, _, self._lo, self._hi = shard_of_this_rank(self.n_particles)
+            check_backend(self._device, 'device="cpu"')
             self.results.particle_range = (self._lo, self._hi)
             # this rank's block only: the trajectory gathers hi - lo atoms per frame, not all of them
             self._source = self._group[self._lo:self._hi]

@@ -72,13 +72,17 @@ def shard_of_this_rank(n_atoms):
 
 
 def default_device():
-    """GPU index of the calling rank: $TA_AMD_DEVICE, else $LOCAL_RANK (torchrun: one process per
-    GPU), else torch's current device when a process group is up, else 0."""
+    """Device of the calling rank, as ``_lib.device_index`` gives it: $TA_AMD_DEVICE (a GPU index, or "cpu" for the opt-in
+    CPU backend: ``_lib.DEVICE_CPU``), else $LOCAL_RANK (torchrun: one process per GPU), else torch's current device when a
+    process group is up, else 0."""
     import os
 
-    for key in ("TA_AMD_DEVICE", "LOCAL_RANK"):
-        if os.environ.get(key, "") != "":
-            return int(os.environ[key])
+    from . import _lib
+
+    if os.environ.get("TA_AMD_DEVICE", "") != "":
+        return check_backend(_lib.device_index(os.environ["TA_AMD_DEVICE"]), "$TA_AMD_DEVICE=" + os.environ["TA_AMD_DEVICE"])
+    if os.environ.get("LOCAL_RANK", "") != "":
+        return int(os.environ["LOCAL_RANK"])
     try:
         import torch
         import torch.distributed as dist
@@ -95,6 +99,17 @@ def uses_device_reduce():
     import torch.distributed as dist
 
     return dist.is_available() and dist.is_initialized() and dist.get_backend() == "nccl"
+
+
+def check_backend(device, asked_by):
+    """`device` (``_lib.device_index``'s value) if the process group can reduce what it computes: the CPU backend's sums are
+    host arrays, which nccl (RCCL) does not reduce -- a ValueError that says so, `asked_by` naming who chose the device."""
+    from . import _lib
+
+    if device == _lib.DEVICE_CPU and uses_device_reduce():
+        raise ValueError(f"{asked_by} selects the CPU backend, but the process group's backend is nccl, which reduces device "
+                         "tensors only: initialise the group with gloo, or give a GPU index")
+    return device
 
 
 def staged_timeseries_on_device(launch, n_frames, n_local, n_atoms_total, device, by_particle=False):
