@@ -337,6 +337,12 @@ int check_fft(ta_ctx* ctx, int fft) { return fft == 0 || fft == 1 ? TA_OK : fail
 int check_dtype(ta_ctx* ctx, int dtype) {
     return dtype == TA_F32 || dtype == TA_F64 ? TA_OK : fail(ctx, TA_E_INVALID, "bad dtype");
 }
+// the shape of host sums handed to a correlator (dim NULL: sums without that axis)
+int check_sums_shape(ta_ctx* ctx, int64_t n_frames, const int* dim = nullptr) {
+    if (n_frames < 1 || n_frames > (int64_t)1 << 30 || (dim && (*dim < 1 || *dim > 3)))
+        return fail(ctx, TA_E_INVALID, std::string("need 1 <= n_frames <= 2^30") + (dim ? ", 1 <= dim <= 3" : ""));
+    return TA_OK;
+}
 int check_shape(ta_ctx* ctx, int64_t T, int64_t A, int D, int64_t ld_row) {
     TA_CHECK(need_ctx(ctx));
     if (T < 1 || A < 1 || D < 1 || D > 3)
@@ -356,6 +362,29 @@ int ensure(ta_ctx* ctx, DevBuf& b, size_t bytes) {
     if (bytes == 0) bytes = 16;
     TA_HIP_TRY(ctx, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
+    return TA_OK;
+}
+
+// A host-facing call's output buffer `b`, sized by the call's layout (before the call is opened) ...
+template <class E>  // (double, or int64_t where the call's only segment holds counts)
+int out_buffer(ta_ctx* ctx, DevBuf& b, const OutLayout& o, E** out) {
+    static_assert(sizeof(E) == 8);
+    TA_CHECK(ensure(ctx, b, sizeof(E) * o.total()));
+    *out = (E*)b.p;
+    return TA_OK;
+}
+// ... and the call's tail: the segments at d_out copied into the caller's arrays `h`, in segment order (NULL, or left out at
+// the end: not asked for), then everything the call queued waited for
+int out_finish(ta_ctx* ctx, const OutLayout& o, const double* d_out, std::initializer_list<void*> h) {
+    HostCopy c[OutLayout::kMax] = {};
+    int i = 0;
+    for (void* p : h) c[i] = {(double*)p, d_out + o.off[i], o.len(i)}, ++i;
+    return host_finish(ctx, {c[0], c[1], c[2], c[3]});
+}
+
+// host sums queued for upload into segment i of a call's layout (the correlators of host sums)
+int upload_segment(ta_ctx* ctx, const OutLayout& o, double* out, int i, const double* h, hipStream_t st) {
+    TA_HIP_TRY(ctx, hipMemcpyAsync(o.at(out, i), h, sizeof(double) * o.len(i), hipMemcpyHostToDevice, st));
     return TA_OK;
 }
 
@@ -1423,7 +1452,7 @@ int orient_pm(ta_ctx* ctx, bool fft, const Slab& slab, const OrientPlan& p, doub
 }
 
 // ta_orient_dev / ta_orient_staged (dev NULL) and the device half of ta_orient (out != NULL: the context's own output
-// buffer c1 (T) | c2 (T) | total (T, 3) | coll (T) takes the place of the d_* pointers, which then only say what is asked for)
+// buffer, laid out by orient_out, takes the place of the d_* pointers, which then only say what is asked for)
 int orient_entry(ta_ctx* ctx, const DevSrc* dev, int fft, int mode, int64_t N, const int32_t* h_index, const double* h_dims,
                  const double* h_w, double* d_c1, double* d_c2, double* d_total, double* d_coll, void* stream, double** out) {
     const OrientArgs a{fft, mode, N, h_index, h_dims, h_w, d_c1 != nullptr, d_c2 != nullptr, d_total != nullptr, d_coll != nullptr};
@@ -1437,17 +1466,13 @@ int orient_entry(ta_ctx* ctx, const DevSrc* dev, int fft, int mode, int64_t N, c
         },
         [&](const Slab& s) -> int {
             TA_CHECK(orient_plan(ctx, a, box, s.st, &plan));
-            if (out) {
-                TA_CHECK(ensure(ctx, ctx->orient_out, sizeof(double) * (size_t)s.T * 6));
-                *out = (double*)ctx->orient_out.p;
-            }
+            if (out) TA_CHECK(out_buffer(ctx, ctx->orient_out, orient_out(s.T), out));
             return TA_OK;
         },
         [&](const Slab& s) {
             if (!out) return orient_pm(ctx, fft != 0, s, plan, d_c1, d_c2, d_total, d_coll);
-            double* o = *out;
-            return orient_pm(ctx, fft != 0, s, plan, a.c1 ? o : nullptr, a.c2 ? o + s.T : nullptr, a.total ? o + 2 * s.T : nullptr,
-                             a.coll ? o + 5 * s.T : nullptr);
+            const OutLayout o = orient_out(s.T);
+            return orient_pm(ctx, fft != 0, s, plan, o.at(*out, 0, a.c1), o.at(*out, 1, a.c2), o.at(*out, 2, a.total), o.at(*out, 3, a.coll));
         });
 }
 
@@ -1941,10 +1966,7 @@ int vhd_launch(ta_ctx* ctx, const VhdPlan& plan, const int64_t* h_lags, double d
         ctx, nullptr, stream, no_args,
         [&](const Slab& s) -> int {
             TA_CHECK(vhd_upload(ctx, plan, h_lags, dr, s.st));
-            if (!d_counts) {
-                TA_CHECK(ensure(ctx, ctx->vhd_out, sizeof(int64_t) * (size_t)plan.L * (size_t)(plan.B + 1)));
-                d_counts = (int64_t*)ctx->vhd_out.p;
-            }
+            if (!d_counts) TA_CHECK(out_buffer(ctx, ctx->vhd_out, vhd_out(plan.L, plan.B), &d_counts));
             if (d_out) *d_out = d_counts;
             return TA_OK;
         },
@@ -2081,34 +2103,18 @@ struct LifePtrs {
     double* nb;
     bool any() const { return lags || count || runs || nb; }
 };
-// Where a host-facing call's results lie in ctx->pair_out, in 8-byte elements (int64 counts travel as doubles): segment i
-// is [off[i], off[i + 1]), in LifePtrs' order.  ci (T) | runs (T + 1) | nb (T) of the three-output calls (n_sums 0: no
-// count), sums ((L + 1) n_sums) | count (L + 1) | runs | nb of the gated ones.
-struct LifeOut {
-    size_t off[5] = {};
-    // the device outputs of those asked for in `want`, in the buffer at `base`
-    LifePtrs at(double* base, const LifePtrs& want) const {
-        return {want.lags ? base + off[0] : nullptr, want.count ? (int64_t*)(base + off[1]) : nullptr,
-                want.runs ? (int64_t*)(base + off[2]) : nullptr, want.nb ? base + off[3] : nullptr};
-    }
-};
-LifeOut life_out(int64_t T, int64_t L = 0, int n_sums = 0) {
-    const size_t len[4] = {n_sums ? (size_t)(L + 1) * (size_t)n_sums : (size_t)T, n_sums ? (size_t)L + 1 : 0, (size_t)T + 1, (size_t)T};
-    LifeOut o;
-    for (int i = 0; i < 4; ++i) o.off[i + 1] = o.off[i] + len[i];
-    return o;
+// Where a host-facing call's results lie in ctx->pair_out, in LifePtrs' order: ci (T) | no count | runs (T + 1) | nb (T) of
+// the three-output calls (n_sums 0), sums ((L + 1) n_sums) | count (L + 1) | runs | nb of the gated ones.
+OutLayout life_out(int64_t T, int64_t L = 0, int n_sums = 0) {
+    return {n_sums ? out_n(L + 1, n_sums) : out_n(T), n_sums ? out_n(L + 1) : 0, out_n(T + 1), out_n(T)};
 }
-// the context's output buffer for a host-facing call (before the call is opened)
-int life_out_buffer(ta_ctx* ctx, const LifeOut& o, double** out) {
-    TA_CHECK(ensure(ctx, ctx->pair_out, sizeof(double) * o.off[4]));
-    *out = (double*)ctx->pair_out.p;
-    return TA_OK;
+// the device outputs of those asked for in `want`, in the buffer at `base`
+LifePtrs life_at(const OutLayout& o, double* base, const LifePtrs& want) {
+    return {o.at(base, 0, want.lags), (int64_t*)o.at(base, 1, want.count), (int64_t*)o.at(base, 2, want.runs), o.at(base, 3, want.nb)};
 }
 // the tail of a host-facing call: the results at d_out copied into those of `h` asked for
-int life_finish(ta_ctx* ctx, const LifeOut& o, const LifePtrs& h, const double* d_out) {
-    double* const dst[4] = {h.lags, (double*)h.count, (double*)h.runs, h.nb};
-    auto seg = [&](int i) { return HostCopy{dst[i], d_out + o.off[i], o.off[i + 1] - o.off[i]}; };
-    return host_finish(ctx, {seg(0), seg(1), seg(2), seg(3)});
+int life_finish(ta_ctx* ctx, const OutLayout& o, const LifePtrs& h, const double* d_out) {
+    return out_finish(ctx, o, d_out, {h.lags, h.count, h.runs, h.nb});
 }
 
 // What ta_bond_lifetime* add to a lifetime call: items per row, the break criterion, the gap tolerance
@@ -2130,7 +2136,7 @@ struct PairLifePlan {
     ta::BondCuts cuts{};
     // the level block needs k_pair_filter: a gap to close, or a break criterion apart from the form criterion
     bool filter() const { return gap > 0 || cuts.rb2 != cuts.rc2 || (n_at == 3 && cuts.cb2 != cuts.c2); }
-    LifeOut out;
+    OutLayout out;
 };
 int bond_rows(ta_ctx* ctx, const std::string& who, int64_t n_bonds, int n_at, const int32_t* h_atoms, int64_t A) {
     if (n_bonds < 1 || n_bonds >= (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, who + "n_bonds must be 1 ... 2^30 - 1");
@@ -2317,10 +2323,10 @@ int pair_life_launch(ta_ctx* ctx, int fft, const PairLifePlan& p, const LifePtrs
             memset(h, 0, sizeof(double) * t.n);
             if (!p.box.hm.empty()) memcpy(h, p.box.hm.data(), sizeof(double) * p.box.hm.size());
             if (p.h_pairs) memcpy(h + t.pairs, p.h_pairs, sizeof(int32_t) * (size_t)p.n_at * (size_t)p.P);
-            if (out) TA_CHECK(life_out_buffer(ctx, p.out, out));
+            if (out) TA_CHECK(out_buffer(ctx, ctx->pair_out, p.out, out));
             return ctx->pair_tab.send(ctx, s.st);
         },
-        [&](const Slab& s) { return pair_life_pm(ctx, fft != 0, s, p, out ? p.out.at(*out, d) : d); });
+        [&](const Slab& s) { return pair_life_pm(ctx, fft != 0, s, p, out ? life_at(p.out, *out, d) : d); });
 }
 
 // ---- shell residence times: the level of an observed item against a group of reference items (shell.hip) ------------
@@ -2353,7 +2359,7 @@ struct ShellPlan : ItemLists {
     int condition = 0, n_sums = 0, mode = 0, row_len = 0;
     int64_t L = 0;
     const int32_t* h_index = nullptr;
-    LifeOut out;
+    OutLayout out;
     bool filter() const { return gap > 0 || cuts.rb2 != cuts.rc2; }
     // what the CPU backend's three calls share
     ta::cpu::ShellItems cpu() const { return {n_a, ida.data(), n_b, idb.data(), box.data(), box.per_frame, &cuts, gap}; }
@@ -2534,10 +2540,10 @@ int shell_launch(ta_ctx* ctx, int fft, const ShellPlan& p, const LifePtrs& d, vo
             memset(h, 0, sizeof(double) * t.n);  // (the zero lag in front, the zero labels)
             pair_tail_pack(h + t.tail, p.box, p);
             std::copy_n(p.h_index, (size_t)p.n_b * (size_t)p.row_len, (int32_t*)(h + t.rows));
-            if (out) TA_CHECK(life_out_buffer(ctx, p.out, out));
+            if (out) TA_CHECK(out_buffer(ctx, ctx->pair_out, p.out, out));
             return ctx->shell_tab.send(ctx, s.st);
         },
-        [&](const Slab& s) { return shell_pm(ctx, fft != 0, s, p, out ? p.out.at(*out, d) : d); });
+        [&](const Slab& s) { return shell_pm(ctx, fft != 0, s, p, out ? life_at(p.out, *out, d) : d); });
 }
 
 // ---- the staged shape, and the CPU backend's side of the entry points ----------------------------------------------
@@ -3740,67 +3746,61 @@ int host_launch(ta_ctx* ctx, int which, const double* h_masses, double scale, do
 }
 
 // Conductivity share of a host-facing call, queued on ctx->stream and not waited for: charges (this context's atoms)
-// uploaded, the moment (and with self the self lag sum, with coll Phi) left on the device in *d_out: (T, D) moment,
-// then T values of Phi, then T of the self term.
+// uploaded, the moment (and with self the self lag sum, with coll Phi) left on the device in *d_out, laid out by cond_out
 int cond_launch(ta_ctx* ctx, int fft, const double* h_q, bool coll, bool self, double** d_out) {
-    double* out = nullptr;
-    TA_CHECK(slab_entry(
+    return slab_entry(
         ctx, nullptr, ctx->stream, no_args,
         [&](const Slab& s) -> int {
             TA_CHECK(ensure(ctx, ctx->cond_q, sizeof(double) * s.A));
-            TA_CHECK(ensure(ctx, ctx->cond_out, sizeof(double) * (size_t)s.T * (s.D + 2)));
-            out = (double*)ctx->cond_out.p;
+            TA_CHECK(out_buffer(ctx, ctx->cond_out, cond_out(s.T, s.D), d_out));
             TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->cond_q.p, h_q, sizeof(double) * s.A, hipMemcpyHostToDevice, ctx->stream));
             return TA_OK;
         },
         [&](const Slab& s) {
-            return cond_pm(ctx, fft != 0, s, (const double*)ctx->cond_q.p, out, coll ? out + s.T * s.D : nullptr,
-                           self ? out + s.T * (s.D + 1) : nullptr);
-        }));
-    *d_out = out;
-    return TA_OK;
+            const OutLayout o = cond_out(s.T, s.D);
+            return cond_pm(ctx, fft != 0, s, (const double*)ctx->cond_q.p, o.at(*d_out, 0), o.at(*d_out, 1, coll), o.at(*d_out, 2, self));
+        });
 }
 
 // Phi of a host (T, D) moment on this context's device, blocking (the group's collective after its members' sums)
 int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T, int D, double* h_coll) {
+    const OutLayout o = cond_out(T, D);
+    double* out = nullptr;
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    TA_CHECK(ensure(ctx, ctx->cond_out, sizeof(double) * (size_t)T * (D + 2)));
-    double* out = (double*)ctx->cond_out.p;
-    TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_moment, sizeof(double) * T * D, hipMemcpyHostToDevice, ctx->stream));
-    TA_CHECK(cond_collective(ctx, fft != 0, out, T, D, out + T * D, ctx->stream));
-    return host_finish(ctx, {{h_coll, out + T * D, (size_t)T}});
+    TA_CHECK(out_buffer(ctx, ctx->cond_out, o, &out));
+    TA_CHECK(upload_segment(ctx, o, out, 0, h_moment, ctx->stream));
+    TA_CHECK(cond_collective(ctx, fft != 0, o.at(out, 0), T, D, o.at(out, 1), ctx->stream));
+    return out_finish(ctx, o, out, {nullptr, h_coll});
 }
 
 // Moments' / currents' share of a host-facing call, queued on ctx->stream and not waited for: the labels and weights (this
-// context's atoms, labels already checked) uploaded, the (S, T, D) sums and with cross the (T, S, S) cross term behind
-// them left on the device in *d_out (the Onsager buffers serve both quantities: one call at a time uses them).
+// context's atoms, labels already checked) uploaded, the sums and with cross the cross term left on the device in *d_out,
+// laid out by coll_out (the Onsager buffers serve both quantities: one call at a time uses them).
 int coll_launch(ta_ctx* ctx, int kind, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out) {
-    double* out = nullptr;
-    TA_CHECK(slab_entry(
+    return slab_entry(
         ctx, nullptr, ctx->stream, no_args,
         [&](const Slab& s) -> int {
             TA_CHECK(ensure(ctx, ctx->ons_lab, sizeof(int32_t) * s.A));
             if (h_w) TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * s.A));
-            TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)s.T * S * (s.D + S)));
-            out = (double*)ctx->ons_out.p;
+            TA_CHECK(out_buffer(ctx, ctx->ons_out, coll_out(S, s.T, s.D), d_out));
             TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_lab.p, h_species, sizeof(int32_t) * s.A, hipMemcpyHostToDevice, ctx->stream));
             if (h_w) TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_w.p, h_w, sizeof(double) * s.A, hipMemcpyHostToDevice, ctx->stream));
             return TA_OK;
         },
         [&](const Slab& s) {
+            const OutLayout o = coll_out(S, s.T, s.D);
             return coll_pm(ctx, kCollective[kind], fft != 0, s, S, (const int32_t*)ctx->ons_lab.p,
-                           h_w ? (const double*)ctx->ons_w.p : nullptr, out, cross ? out + (size_t)S * s.T * s.D : nullptr);
-        }));
-    *d_out = out;
-    return TA_OK;
+                           h_w ? (const double*)ctx->ons_w.p : nullptr, o.at(*d_out, 0), o.at(*d_out, 1, cross));
+        });
 }
 
 // A correlation of host sums on this context's device, blocking, as a compute call of its own (the *_cross and
 // *_collective entries; a group's ONE evaluation after its members' sums).  Needs no staged slab.  upload(st): the
-// workspaces ensured, the sums queued for upload; body(st): the correlation, inside the call's bracket (no dominant
-// kernel of its own, unless the correlator records one); back(), back2(): the one or two copies to the host.
+// workspaces ensured, the sums queued for upload into their segment of the call's layout; body(st): the correlation,
+// inside the call's bracket (no dominant kernel of its own, unless the correlator records one).  The caller's out_finish
+// copies the correlation's segments to the host.
 template <class Upload, class Body>
-int host_sums_run(ta_ctx* ctx, Upload&& upload, Body&& body) {
+int host_sums_call(ta_ctx* ctx, Upload&& upload, Body&& body) {
     TA_HIP_TRY(ctx, hipSetDevice(ctx->device));
     TA_CHECK(ctx->commits.flush());
     hipStream_t st = ctx->stream;
@@ -3811,36 +3811,23 @@ int host_sums_run(ta_ctx* ctx, Upload&& upload, Body&& body) {
     TA_CHECK(body(st));
     return call_end(ctx, st);
 }
-template <class Upload, class Body, class Back>
-int host_sums_call(ta_ctx* ctx, Upload&& upload, Body&& body, Back&& back) {
-    TA_CHECK(host_sums_run(ctx, upload, body));
-    return host_finish(ctx, {back()});
-}
-template <class Upload, class Body, class Back, class Back2>
-int host_sums_call(ta_ctx* ctx, Upload&& upload, Body&& body, Back&& back, Back2&& back2) {
-    TA_CHECK(host_sums_run(ctx, upload, body));
-    return host_finish(ctx, {back(), back2()});
-}
-
-// The cross term (T, S, S) of host (S, T, D) sums (ta_onsager_cross, ta_current_cross)
+// The cross term of host sums (ta_onsager_cross, ta_current_cross)
 int coll_cross_host(ta_ctx* ctx, int kind, int fft, const double* h_sums, int S, int64_t T, int D, double* h_cross) {
-    const size_t n_sums = (size_t)S * T * D;
+    const OutLayout o = coll_out(S, T, D);
     double* out = nullptr;
-    return host_sums_call(
+    TA_CHECK(host_sums_call(
         ctx,
         [&](hipStream_t st) -> int {
-            TA_CHECK(ensure(ctx, ctx->ons_out, sizeof(double) * (size_t)T * S * (D + S)));
-            out = (double*)ctx->ons_out.p;
-            TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_sums, sizeof(double) * n_sums, hipMemcpyHostToDevice, st));
-            return TA_OK;
+            TA_CHECK(out_buffer(ctx, ctx->ons_out, o, &out));
+            return upload_segment(ctx, o, out, 0, h_sums, st);
         },
-        [&](hipStream_t st) { return coll_cross(ctx, kCollective[kind], fft != 0, out, S, T, D, out + n_sums, st); },
-        [&] { return HostCopy{h_cross, out + n_sums, (size_t)T * S * S}; });
+        [&](hipStream_t st) { return coll_cross(ctx, kCollective[kind], fft != 0, o.at(out, 0), S, T, D, o.at(out, 1), st); }));
+    return out_finish(ctx, o, out, {nullptr, h_cross});
 }
 
 // Self-term share of a host-facing call, queued on ctx->stream and not waited for: the labels (this context's atoms)
-// checked and sorted, the weights uploaded (the Onsager weight buffer: one call at a time uses it), the (S, T) lag sums
-// left on the device in *d_out; h_counts (S) or NULL: this context's atoms per species.
+// checked and sorted, the weights uploaded (the Onsager weight buffer: one call at a time uses it), the lag sums left on
+// the device in *d_out (self_out); h_counts (S) or NULL: this context's atoms per species.
 int self_launch(ta_ctx* ctx, int quantity, int fft, int S, const int32_t* h_species, const double* h_w, int64_t* h_counts,
                 double** d_out) {
     SortPlan plan;
@@ -3849,193 +3836,151 @@ int self_launch(ta_ctx* ctx, int quantity, int fft, int S, const int32_t* h_spec
         [&](const Slab& s) -> int {
             TA_CHECK(self_plan(ctx, S, h_species, s.A, s.D, ctx->stream, &plan));
             if (h_w) TA_CHECK(ensure(ctx, ctx->ons_w, sizeof(double) * s.A));
-            TA_CHECK(ensure(ctx, ctx->self_out, sizeof(double) * (size_t)s.T * S));
+            TA_CHECK(out_buffer(ctx, ctx->self_out, self_out(S, s.T), d_out));
             if (h_w) TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->ons_w.p, h_w, sizeof(double) * s.A, hipMemcpyHostToDevice, ctx->stream));
             return TA_OK;
         },
-        [&](const Slab& s) {
-            return species_self_pm(ctx, quantity, fft != 0, s, plan, h_w ? (const double*)ctx->ons_w.p : nullptr,
-                                   (double*)ctx->self_out.p);
-        }));
+        [&](const Slab& s) { return species_self_pm(ctx, quantity, fft != 0, s, plan, h_w ? (const double*)ctx->ons_w.p : nullptr, *d_out); }));
     if (h_counts)
         for (int s = 0; s < S; ++s) h_counts[s] = plan.count[s];
-    *d_out = (double*)ctx->self_out.p;
     return TA_OK;
 }
 
 // Scattering share of a host-facing call, queued on ctx->stream and not waited for: the wavevectors (checked by the
-// caller) uploaded, self (K, T), then the density (K, T, 2), then coll (K, T) left on the device in *d_out (the ones asked for)
+// caller) uploaded, the outputs asked for left on the device in *d_out, laid out by scatter_out
 int scatter_launch(ta_ctx* ctx, int fft, int K, const double* h_kvecs, bool self, bool density, bool coll, double** d_out) {
-    double* out = nullptr;
-    TA_CHECK(slab_entry(
+    return slab_entry(
         ctx, nullptr, ctx->stream, no_args,
         [&](const Slab& s) -> int {
             TA_CHECK(scatter_plan(ctx, K, h_kvecs, s.A, s.D, ctx->stream));
-            TA_CHECK(ensure(ctx, ctx->scatter_out, sizeof(double) * (size_t)K * s.T * 4));
-            out = (double*)ctx->scatter_out.p;
-            return TA_OK;
+            return out_buffer(ctx, ctx->scatter_out, scatter_out(K, s.T), d_out);
         },
         [&](const Slab& s) {
-            const size_t KT = (size_t)K * s.T;
-            return scatter_pm(ctx, fft != 0, s, K, self ? out : nullptr, density ? out + KT : nullptr, coll ? out + 3 * KT : nullptr);
-        }));
-    *d_out = out;
-    return TA_OK;
+            const OutLayout o = scatter_out(K, s.T);
+            return scatter_pm(ctx, fft != 0, s, K, o.at(*d_out, 0, self), o.at(*d_out, 1, density), o.at(*d_out, 2, coll));
+        });
 }
 
 // Van Hove share of a host-facing call, queued on ctx->stream and not waited for: the lags and bins (checked by the caller)
-// uploaded, counts (L, B + 1) int64, then moments (L, 2) left on the device in *d_out (the ones asked for)
-int vanhove_launch(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, bool counts, bool moments, void** d_out) {
-    char* out = nullptr;
-    const size_t n_counts = (size_t)L * (size_t)(B + 1);
-    TA_CHECK(slab_entry(
+// uploaded, the outputs asked for left on the device in *d_out, laid out by vanhove_out
+int vanhove_launch(ta_ctx* ctx, int L, const int64_t* h_lags, int B, double dr, bool counts, bool moments, double** d_out) {
+    const OutLayout o = vanhove_out(L, B);
+    return slab_entry(
         ctx, nullptr, ctx->stream, no_args,
         [&](const Slab& s) -> int {
             TA_CHECK(vanhove_plan(ctx, L, h_lags, B, dr, s.A, s.D, ctx->stream));
-            TA_CHECK(ensure(ctx, ctx->vh_out, sizeof(int64_t) * n_counts + sizeof(double) * 2 * (size_t)L));
-            out = (char*)ctx->vh_out.p;
-            return TA_OK;
+            return out_buffer(ctx, ctx->vh_out, o, d_out);
         },
-        [&](const Slab& s) {
-            return vanhove_pm(ctx, s, L, B, dr, counts ? (int64_t*)out : nullptr,
-                              moments ? (double*)(out + sizeof(int64_t) * n_counts) : nullptr);
-        }));
-    *d_out = out;
-    return TA_OK;
+        [&](const Slab& s) { return vanhove_pm(ctx, s, L, B, dr, (int64_t*)o.at(*d_out, 0, counts), o.at(*d_out, 1, moments)); });
 }
 
 // Overlap share of a host-facing call, queued on ctx->stream and not waited for: the lags and cutoffs (checked by the caller)
-// uploaded, Q (C, L, T) int64 left on the device in *d_out
-int overlap_launch(ta_ctx* ctx, int L, const int64_t* h_lags, int C, const double* h_cutoffs, int64_t** d_out) {
-    int64_t* out = nullptr;
-    TA_CHECK(slab_entry(
+// uploaded, Q left on the device in *d_out (overlap_out)
+int overlap_launch(ta_ctx* ctx, int L, const int64_t* h_lags, int C, const double* h_cutoffs, double** d_out) {
+    return slab_entry(
         ctx, nullptr, ctx->stream, no_args,
         [&](const Slab& s) -> int {
             TA_CHECK(overlap_plan(ctx, L, h_lags, C, h_cutoffs, s.A, s.D, ctx->stream));
-            TA_CHECK(ensure(ctx, ctx->ov_out, sizeof(int64_t) * (size_t)C * (size_t)L * (size_t)s.T));
-            out = (int64_t*)ctx->ov_out.p;
-            return TA_OK;
+            return out_buffer(ctx, ctx->ov_out, overlap_out(C, L, s.T), d_out);
         },
-        [&](const Slab& s) { return overlap_pm(ctx, s, L, C, out); }));
-    *d_out = out;
-    return TA_OK;
+        [&](const Slab& s) { return overlap_pm(ctx, s, L, C, (int64_t*)*d_out); });
 }
 
 // Overlap-density share of a host-facing call, queued on ctx->stream and not waited for: the wavevectors, lags and cutoffs
-// (checked by the caller) uploaded, W (K, C, L, T, 2) left on the device in *d_out
+// (checked by the caller) uploaded, W left on the device in *d_out (overlap_density_out)
 int overlap_density_launch(ta_ctx* ctx, int K, const double* h_kvecs, int L, const int64_t* h_lags, int C, const double* h_cutoffs,
                            double** d_out) {
-    double* out = nullptr;
-    TA_CHECK(slab_entry(
+    return slab_entry(
         ctx, nullptr, ctx->stream, no_args,
         [&](const Slab& s) -> int {
             TA_CHECK(overlap_density_plan(ctx, K, h_kvecs, L, h_lags, C, h_cutoffs, s.A, s.D, ctx->stream));
-            TA_CHECK(ensure(ctx, ctx->od_out, sizeof(double) * 2 * (size_t)K * (size_t)C * (size_t)L * (size_t)s.T));
-            out = (double*)ctx->od_out.p;
-            return TA_OK;
+            return out_buffer(ctx, ctx->od_out, overlap_density_out(K, C, L, s.T), d_out);
         },
-        [&](const Slab& s) { return overlap_density_pm(ctx, s, K, L, C, out); }));
-    *d_out = out;
-    return TA_OK;
+        [&](const Slab& s) { return overlap_density_pm(ctx, s, K, L, C, *d_out); });
 }
 
 // The collective part (K, T) of a host (K, T, 2) density (ta_scatter_collective)
 int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int K, int64_t T, double* h_coll) {
-    const size_t KT = (size_t)K * T;
+    const OutLayout o = scatter_out(K, T);
     double* out = nullptr;
-    return host_sums_call(
+    TA_CHECK(host_sums_call(
         ctx,
         [&](hipStream_t st) -> int {
-            TA_CHECK(ensure(ctx, ctx->scatter_out, sizeof(double) * KT * 4));
+            TA_CHECK(out_buffer(ctx, ctx->scatter_out, o, &out));
             TA_CHECK(ensure(ctx, ctx->scatter_work, scatter_work_bytes(T, K, false)));
-            out = (double*)ctx->scatter_out.p;
-            TA_HIP_TRY(ctx, hipMemcpyAsync(out + KT, h_density, sizeof(double) * KT * 2, hipMemcpyHostToDevice, st));
-            return TA_OK;
+            return upload_segment(ctx, o, out, 1, h_density, st);
         },
-        [&](hipStream_t st) { return scatter_collective(ctx, fft != 0, out + KT, K, T, out + 3 * KT, st); },
-        [&] { return HostCopy{h_coll, out + 3 * KT, KT}; });
+        [&](hipStream_t st) { return scatter_collective(ctx, fft != 0, o.at(out, 1), K, T, o.at(out, 2), st); }));
+    return out_finish(ctx, o, out, {nullptr, nullptr, h_coll});
 }
 
 // Current-correlation share of a host-facing call, queued on ctx->stream and not waited for: the table (wavevectors, checked
-// by the caller, and this context's atoms' weights) uploaded, the current (K, T, D, 2), then (correlate) long (K, T) and trans
-// (K, T) left on the device in *d_out
+// by the caller, and this context's atoms' weights) uploaded, the current and (correlate) long and trans left on the device in
+// *d_out, laid out by kcurrent_out
 int kcurrent_launch(ta_ctx* ctx, int fft, int K, const double* h_kvecs, const double* h_w, bool correlate, double** d_out) {
-    double* out = nullptr;
-    TA_CHECK(slab_entry(
+    return slab_entry(
         ctx, nullptr, ctx->stream, [&] { return kcurrent_slabs(ctx); },
         [&](const Slab& s) -> int {
             TA_CHECK(kcurrent_plan(ctx, K, h_kvecs, s.D, h_w, s.A, ctx->stream));
-            TA_CHECK(ensure(ctx, ctx->kcur_out, sizeof(double) * (size_t)K * s.T * (2 * s.D + 2)));
-            out = (double*)ctx->kcur_out.p;
-            return TA_OK;
+            return out_buffer(ctx, ctx->kcur_out, kcurrent_out(K, s.T, s.D), d_out);
         },
         [&](const Slab& s) {
-            const size_t KT = (size_t)K * s.T, n_cur = KT * s.D * 2;
+            const OutLayout o = kcurrent_out(K, s.T, s.D);
             const double* d_w = h_w ? (const double*)ctx->kcur_tab.dev.p + 2 * (size_t)K * s.D : nullptr;
-            return kcurrent_pm(ctx, fft != 0, s, K, d_w, out, correlate ? out + n_cur : nullptr, correlate ? out + n_cur + KT : nullptr);
-        }));
-    *d_out = out;
-    return TA_OK;
+            return kcurrent_pm(ctx, fft != 0, s, K, d_w, o.at(*d_out, 0), o.at(*d_out, 1, correlate), o.at(*d_out, 2, correlate));
+        });
 }
 
-// long and trans (K, T) of a host (K, T, D, 2) current (ta_kcurrent_correlate)
+// long and trans of a host current (ta_kcurrent_correlate)
 int kcurrent_correlate_host(ta_ctx* ctx, int fft, const double* h_current, int K, const double* h_kvecs, int64_t T, int D,
                             double* h_long, double* h_trans) {
-    const size_t KT = (size_t)K * T, n_cur = KT * D * 2;
+    const OutLayout o = kcurrent_out(K, T, D);
     double* out = nullptr;
-    return host_sums_call(
+    TA_CHECK(host_sums_call(
         ctx,
         [&](hipStream_t st) -> int {
-            TA_CHECK(ensure(ctx, ctx->kcur_out, sizeof(double) * KT * (2 * D + 2)));
+            TA_CHECK(out_buffer(ctx, ctx->kcur_out, o, &out));
             TA_CHECK(ensure(ctx, ctx->kcur_work, kcurrent_work_bytes(T, K, D, false)));
             TA_CHECK(kcurrent_plan(ctx, K, h_kvecs, D, nullptr, 0, st));
-            out = (double*)ctx->kcur_out.p;
-            TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_current, sizeof(double) * n_cur, hipMemcpyHostToDevice, st));
-            return TA_OK;
+            return upload_segment(ctx, o, out, 0, h_current, st);
         },
-        [&](hipStream_t st) { return kcurrent_correlation(ctx, fft != 0, out, K, T, D, out + n_cur, out + n_cur + KT, st); },
-        [&] { return HostCopy{h_long, out + n_cur, KT}; }, [&] { return HostCopy{h_trans, out + n_cur + KT, KT}; });
+        [&](hipStream_t st) { return kcurrent_correlation(ctx, fft != 0, o.at(out, 0), K, T, D, o.at(out, 1), o.at(out, 2), st); }));
+    return out_finish(ctx, o, out, {nullptr, h_long, h_trans});
 }
 
 // Partial-density share of a host-facing call, queued on ctx->stream and not waited for: the table (wavevectors, checked by
-// the caller, and this context's atoms' weights) and the labels (checked by the caller) uploaded, the density (K, S, T, 2),
-// then (cross) the cross term (K, T, S, S) left on the device in *d_out
+// the caller, and this context's atoms' weights) and the labels (checked by the caller) uploaded, the density and (cross) the
+// cross term left on the device in *d_out, laid out by partial_out
 int partial_launch(ta_ctx* ctx, int fft, int K, const double* h_kvecs, int S, const int32_t* h_species, const double* h_w,
                    bool cross, double** d_out) {
-    double* out = nullptr;
-    TA_CHECK(slab_entry(
+    return slab_entry(
         ctx, nullptr, ctx->stream, [&] { return partial_slab(ctx); },
         [&](const Slab& s) -> int {
             TA_CHECK(partial_plan(ctx, K, h_kvecs, s.D, h_w, s.A, ctx->stream));
             TA_CHECK(ensure(ctx, ctx->psd_lab, sizeof(int32_t) * (size_t)s.A));
-            TA_CHECK(ensure(ctx, ctx->psd_out, sizeof(double) * (size_t)K * s.T * S * (2 + S)));
-            out = (double*)ctx->psd_out.p;
+            TA_CHECK(out_buffer(ctx, ctx->psd_out, partial_out(K, S, s.T), d_out));
             TA_HIP_TRY(ctx, hipMemcpyAsync(ctx->psd_lab.p, h_species, sizeof(int32_t) * s.A, hipMemcpyHostToDevice, ctx->stream));
             return TA_OK;
         },
         [&](const Slab& s) {
+            const OutLayout o = partial_out(K, S, s.T);
             const double* d_w = h_w ? (const double*)ctx->psd_tab.dev.p + (size_t)K * s.D : nullptr;
-            return partial_pm(ctx, fft != 0, s, K, S, (const int32_t*)ctx->psd_lab.p, d_w, out,
-                              cross ? out + (size_t)K * S * s.T * 2 : nullptr);
-        }));
-    *d_out = out;
-    return TA_OK;
+            return partial_pm(ctx, fft != 0, s, K, S, (const int32_t*)ctx->psd_lab.p, d_w, o.at(*d_out, 0), o.at(*d_out, 1, cross));
+        });
 }
 
-// The cross term (K, T, S, S) of a host (K, S, T, 2) density (ta_partial_cross)
+// The cross term of a host density (ta_partial_cross)
 int partial_cross_host(ta_ctx* ctx, int fft, const double* h_density, int K, int S, int64_t T, double* h_cross) {
-    const size_t n_den = (size_t)K * S * T * 2;
+    const OutLayout o = partial_out(K, S, T);
     double* out = nullptr;
-    return host_sums_call(
+    TA_CHECK(host_sums_call(
         ctx,
         [&](hipStream_t st) -> int {
-            TA_CHECK(ensure(ctx, ctx->psd_out, sizeof(double) * (size_t)K * T * S * (2 + S)));
-            out = (double*)ctx->psd_out.p;
-            TA_HIP_TRY(ctx, hipMemcpyAsync(out, h_density, sizeof(double) * n_den, hipMemcpyHostToDevice, st));
-            return TA_OK;
+            TA_CHECK(out_buffer(ctx, ctx->psd_out, o, &out));
+            return upload_segment(ctx, o, out, 0, h_density, st);
         },
-        [&](hipStream_t st) { return partial_cross(ctx, fft != 0, out, K, S, T, out + n_den, st); },
-        [&] { return HostCopy{h_cross, out + n_den, (size_t)K * T * S * S}; });
+        [&](hipStream_t st) { return partial_cross(ctx, fft != 0, o.at(out, 0), K, S, T, o.at(out, 1), st); }));
+    return out_finish(ctx, o, out, {nullptr, h_cross});
 }
 
 // One context's unwrap of staged slab `slab` (ta_unwrap, ta_group_unwrap), queued on ctx->stream behind the queued commits
@@ -4130,8 +4075,7 @@ int ta_conductivity(ta_ctx* ctx, int fft, const double* h_charges, double* h_mom
     if (ctx->is_cpu) return cpu_conductivity(ctx, fft != 0, h_charges, h_moment, h_collective, h_self_lagsum);
     double* d_out = nullptr;
     TA_CHECK(ta::cond_launch(ctx, fft, h_charges, h_collective != nullptr, h_self_lagsum != nullptr, &d_out));
-    const size_t T = (size_t)ctx->st_T, D = (size_t)ctx->st_D;
-    return host_finish(ctx, {{h_moment, d_out, T * D}, {h_collective, d_out + T * D, T}, {h_self_lagsum, d_out + T * (D + 1), T}});
+    return out_finish(ctx, cond_out(ctx->st_T, ctx->st_D), d_out, {h_moment, h_collective, h_self_lagsum});
     });
 }
 
@@ -4147,8 +4091,7 @@ static int coll_host(ta_ctx* ctx, int kind, int fft, int n_species, const int32_
     if (ctx->is_cpu) return cpu_rc(ctx, q.cpu(cpu_state(ctx), fft != 0, n_species, h_species, h_weights, h_sums, h_cross));
     double* d_out = nullptr;
     TA_CHECK(ta::coll_launch(ctx, kind, fft, n_species, h_species, h_weights, h_cross != nullptr, &d_out));
-    const size_t T = (size_t)ctx->st_T, D = (size_t)ctx->st_D, S = (size_t)n_species;
-    return host_finish(ctx, {{h_sums, d_out, S * T * D}, {h_cross, d_out + S * T * D, T * S * S}});
+    return out_finish(ctx, coll_out(n_species, ctx->st_T, ctx->st_D), d_out, {h_sums, h_cross});
     });
 }
 static int coll_cross_call(ta_ctx* ctx, int kind, int fft, const double* h_sums, int n_species, int64_t n_frames, int dim,
@@ -4159,8 +4102,7 @@ static int coll_cross_call(ta_ctx* ctx, int kind, int fft, const double* h_sums,
     TA_CHECK(check_fft(ctx, fft));
     TA_CHECK(check_species_count(fail, ctx, n_species));
     if (!h_sums || !h_cross) return fail(ctx, TA_E_INVALID, std::string(q.noun) + " or cross output is NULL");
-    if (n_frames < 1 || dim < 1 || dim > 3 || n_frames > (int64_t)1 << 30)
-        return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30, 1 <= dim <= 3");
+    TA_CHECK(check_sums_shape(ctx, n_frames, &dim));
     if (ctx->is_cpu) return cpu_rc(ctx, q.cpu_cross(ctx->cpu_threads, fft != 0, h_sums, n_species, n_frames, dim, h_cross));
     return ta::coll_cross_host(ctx, kind, fft, h_sums, n_species, n_frames, dim, h_cross);
     });
@@ -4193,7 +4135,7 @@ int ta_species_self(ta_ctx* ctx, int quantity, int fft, int n_species, const int
     }
     double* d_out = nullptr;
     TA_CHECK(ta::self_launch(ctx, quantity, fft, n_species, h_species, h_weights, h_counts, &d_out));
-    return host_finish(ctx, {{h_self, d_out, (size_t)n_species * (size_t)ctx->st_T}});
+    return out_finish(ctx, self_out(n_species, ctx->st_T), d_out, {h_self});
     });
 }
 
@@ -4205,8 +4147,7 @@ int ta_scatter(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, double* h_s
     if (ctx->is_cpu) return cpu_rc(ctx, ta::cpu::scatter(cpu_state(ctx), fft != 0, n_k, h_kvecs, h_self, h_density, h_coll));
     double* d_out = nullptr;
     TA_CHECK(ta::scatter_launch(ctx, fft, n_k, h_kvecs, h_self != nullptr, h_density != nullptr, h_coll != nullptr, &d_out));
-    const size_t KT = (size_t)n_k * (size_t)ctx->st_T;
-    return host_finish(ctx, {{h_self, d_out, KT}, {h_density, d_out + KT, 2 * KT}, {h_coll, d_out + 3 * KT, KT}});
+    return out_finish(ctx, scatter_out(n_k, ctx->st_T), d_out, {h_self, h_density, h_coll});
     });
 }
 
@@ -4230,8 +4171,7 @@ int ta_orient(ta_ctx* ctx, int fft, int mode, int64_t n_vectors, const int32_t* 
     double* d_out = nullptr;
     TA_CHECK(orient_entry(ctx, nullptr, fft, mode, n_vectors, h_index, h_dimensions, h_weights, h_c1, h_c2, h_total, h_coll, ctx->stream,
                           &d_out));
-    const size_t T = (size_t)ctx->st_T;
-    return host_finish(ctx, {{h_c1, d_out, T}, {h_c2, d_out + T, T}, {h_total, d_out + 2 * T, 3 * T}, {h_coll, d_out + 5 * T, T}});
+    return out_finish(ctx, orient_out(ctx->st_T), d_out, {h_c1, h_c2, h_total, h_coll});
     });
 }
 
@@ -4240,8 +4180,8 @@ int ta_scatter_collective(ta_ctx* ctx, int fft, const double* h_density, int n_k
     TA_CHECK(need_ctx(ctx));
     TA_CHECK(check_fft(ctx, fft));
     if (!h_density || !h_coll) return fail(ctx, TA_E_INVALID, "density or collective output is NULL");
-    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(ctx, TA_E_INVALID, "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
-    if (n_frames < 1 || n_frames > (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30");
+    TA_CHECK(check_n_k(fail, ctx, n_k));
+    TA_CHECK(check_sums_shape(ctx, n_frames));
     if (ctx->is_cpu) return cpu_rc(ctx, ta::cpu::scatter_collective(ctx->cpu_threads, fft != 0, h_density, n_k, n_frames, h_coll));
     return ta::scatter_collective_host(ctx, fft, h_density, n_k, n_frames, h_coll);
     });
@@ -4256,8 +4196,7 @@ int ta_kcurrent(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, const doub
         return cpu_rc(ctx, ta::cpu::kcurrent(cpu_state(ctx), fft != 0, n_k, h_kvecs, h_weights, h_current, h_long, h_trans));
     double* d_out = nullptr;
     TA_CHECK(ta::kcurrent_launch(ctx, fft, n_k, h_kvecs, h_weights, h_long || h_trans, &d_out));
-    const size_t KT = (size_t)n_k * (size_t)ctx->st_T, n_cur = KT * (size_t)ctx->st_D * 2;
-    return host_finish(ctx, {{h_current, d_out, n_cur}, {h_long, d_out + n_cur, KT}, {h_trans, d_out + n_cur + KT, KT}});
+    return out_finish(ctx, kcurrent_out(n_k, ctx->st_T, ctx->st_D), d_out, {h_current, h_long, h_trans});
     });
 }
 
@@ -4265,8 +4204,7 @@ int ta_kcurrent_correlate(ta_ctx* ctx, int fft, const double* h_current, int n_k
                           double* h_long, double* h_trans) {
     return host_call(ctx, [&]() -> int {
     TA_CHECK(need_ctx(ctx));
-    if (n_frames < 1 || dim < 1 || dim > 3 || n_frames > (int64_t)1 << 30)
-        return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30, 1 <= dim <= 3");
+    TA_CHECK(check_sums_shape(ctx, n_frames, &dim));
     if (!h_current) return fail(ctx, TA_E_INVALID, "current is NULL");
     TA_CHECK(check_kcurrent(fail, ctx, fft, n_k, h_kvecs, dim, h_long || h_trans));
     if (ctx->is_cpu)
@@ -4296,9 +4234,7 @@ int ta_partial_density(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, int
                                                     h_cross));
     double* d_out = nullptr;
     TA_CHECK(ta::partial_launch(ctx, fft, n_k, h_kvecs, n_species, h_species, h_weights, h_cross != nullptr, &d_out));
-    const size_t n_den = (size_t)n_k * (size_t)n_species * (size_t)ctx->st_T * 2;
-    return host_finish(ctx, {{h_density, d_out, n_den},
-                             {h_cross, d_out + n_den, (size_t)n_k * (size_t)ctx->st_T * (size_t)n_species * (size_t)n_species}});
+    return out_finish(ctx, partial_out(n_k, n_species, ctx->st_T), d_out, {h_density, h_cross});
     });
 }
 
@@ -4308,8 +4244,8 @@ int ta_partial_cross(ta_ctx* ctx, int fft, const double* h_density, int n_k, int
     TA_CHECK(check_fft(ctx, fft));
     TA_CHECK(check_species_count(fail, ctx, n_species));
     if (!h_density || !h_cross) return fail(ctx, TA_E_INVALID, "partial density or cross output is NULL");
-    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(ctx, TA_E_INVALID, "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
-    if (n_frames < 1 || n_frames > (int64_t)1 << 30) return fail(ctx, TA_E_INVALID, "need 1 <= n_frames <= 2^30");
+    TA_CHECK(check_n_k(fail, ctx, n_k));
+    TA_CHECK(check_sums_shape(ctx, n_frames));
     if (ctx->is_cpu)
         return cpu_rc(ctx, ta::cpu::partial_cross(ctx->cpu_threads, fft != 0, h_density, n_k, n_species, n_frames, h_cross));
     return ta::partial_cross_host(ctx, fft, h_density, n_k, n_species, n_frames, h_cross);
@@ -4336,11 +4272,9 @@ int ta_vanhove(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, doubl
         TA_CHECK(check_cols(ctx, "vanhove: ", ctx->st_A, ctx->st_D));
         return cpu_rc(ctx, ta::cpu::vanhove(cpu_state(ctx), n_lags, h_lags, n_bins, dr, h_counts, h_moments));
     }
-    void* d_out = nullptr;
+    double* d_out = nullptr;
     TA_CHECK(ta::vanhove_launch(ctx, n_lags, h_lags, n_bins, dr, h_counts != nullptr, h_moments != nullptr, &d_out));
-    const size_t n_counts = (size_t)n_lags * (size_t)(n_bins + 1);  // (int64 counts travel as 8-byte elements)
-    return host_finish(ctx, {{(double*)h_counts, (const double*)d_out, n_counts},
-                             {h_moments, (const double*)d_out + n_counts, 2 * (size_t)n_lags}});
+    return out_finish(ctx, vanhove_out(n_lags, n_bins), d_out, {h_counts, h_moments});
     });
 }
 
@@ -4353,10 +4287,9 @@ int ta_overlap(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_cutoffs, co
         TA_CHECK(check_cols(ctx, "overlap: ", ctx->st_A, ctx->st_D));
         return cpu_rc(ctx, ta::cpu::overlap(cpu_state(ctx), n_lags, h_lags, n_cutoffs, h_cutoffs, h_q));
     }
-    int64_t* d_out = nullptr;
+    double* d_out = nullptr;
     TA_CHECK(ta::overlap_launch(ctx, n_lags, h_lags, n_cutoffs, h_cutoffs, &d_out));
-    const size_t n_q = (size_t)n_cutoffs * (size_t)n_lags * (size_t)ctx->st_T;  // (int64 counts travel as 8-byte elements)
-    return host_finish(ctx, {{(double*)h_q, (const double*)d_out, n_q}});
+    return out_finish(ctx, overlap_out(n_cutoffs, n_lags, ctx->st_T), d_out, {h_q});
     });
 }
 
@@ -4378,7 +4311,7 @@ int ta_overlap_density(ta_ctx* ctx, int n_k, const double* h_kvecs, int n_lags, 
     }
     double* d_out = nullptr;
     TA_CHECK(ta::overlap_density_launch(ctx, n_k, h_kvecs, n_lags, h_lags, n_cutoffs, h_cutoffs, &d_out));
-    return host_finish(ctx, {{h_w, d_out, 2 * (size_t)n_k * (size_t)n_cutoffs * (size_t)n_lags * (size_t)ctx->st_T}});
+    return out_finish(ctx, overlap_density_out(n_k, n_cutoffs, n_lags, ctx->st_T), d_out, {h_w});
     });
 }
 
@@ -4406,7 +4339,7 @@ int ta_vanhove_distinct(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int64_t 
                                                      p.box.data(), p.box.per_frame, n_bins, dr, h_counts));
     int64_t* d_out = nullptr;
     TA_CHECK(vhd_launch(ctx, p, h_lags, dr, nullptr, ctx->stream, &d_out));
-    return host_finish(ctx, {{(double*)h_counts, (const double*)d_out, (size_t)n_lags * (size_t)(n_bins + 1)}});  // (8-byte elements)
+    return out_finish(ctx, vhd_out(n_lags, n_bins), (const double*)d_out, {h_counts});
     });
 }
 

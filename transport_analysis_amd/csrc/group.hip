@@ -315,13 +315,13 @@ int drained(ta_group* g, const std::vector<int>& who, int rc) {
 }
 
 // The sum over members of what each leaves on its device.  launch(i, &d) queues member i's share and returns its device
-// result, an array of 8-byte elements; of that result every part (n elements at offset off, float64 or int64; h NULL:
-// skipped) is copied into a host vector of the member's own.  A copy's HIP error is the group's own failure ("<what> copy:
-// ..."); any failure drains the members first.  Then every member is waited for, each part's h zeroed and the members'
-// values added in member order, int64 parts as int64 (who: the members called).
+// result, laid out by the call's `out` (ta_internal.hpp); of that result every part -- part j is segment j of the layout,
+// float64 or int64; h NULL, or left out at the end: skipped -- is copied into a host vector of the member's own.  A copy's
+// HIP error is the group's own failure ("<what> copy: ..."); any failure drains the members first.  Then every member is
+// waited for, each part's h zeroed and the members' values added in member order, int64 parts as int64 (who: the members
+// called).
 struct MemberPart {
     enum Kind { F64, I64 };
-    size_t off, n;
     void* h;
     Kind kind = F64;
 };
@@ -330,38 +330,46 @@ union MemberWord {  // (the copies fill it bytewise)
     int64_t i;
 };
 template <class Launch>
-int sum_members(ta_group* g, std::vector<int>& who, const char* what, std::initializer_list<MemberPart> parts, Launch&& launch) {
+int sum_members(ta_group* g, std::vector<int>& who, const char* what, const OutLayout& out, std::initializer_list<MemberPart> parts,
+                Launch&& launch) {
     std::vector<std::vector<MemberWord>> got(g->ctx.size());
+    // fn(part, j) for every part asked for, j its segment
+    auto each = [&](auto&& fn) {
+        int j = 0;
+        for (const MemberPart& p : parts) {
+            if (p.h) fn(p, j);
+            ++j;
+        }
+    };
     size_t total = 0;
-    for (const MemberPart& p : parts) total += p.h ? p.n : 0;
+    each([&](const MemberPart&, int j) { total += out.len(j); });
     hipError_t he = hipSuccess;
     int rc = for_members(g, &who, [&](int i) {
         double* d = nullptr;
         if (const int r = launch(i, &d)) return r;
         got[i].resize(total);  // (once: copies into it are in flight from here on)
         MemberWord* dst = got[i].data();
-        for (const MemberPart& p : parts) {
-            if (!p.h || he != hipSuccess) continue;
-            he = hipMemcpyAsync(dst, d + p.off, sizeof(double) * p.n, hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
-            dst += p.n;
-        }
+        each([&](const MemberPart&, int j) {
+            if (he != hipSuccess) return;
+            he = hipMemcpyAsync(dst, out.at(d, j), sizeof(double) * out.len(j), hipMemcpyDeviceToHost, ctx_stream(g->ctx[i]));
+            dst += out.len(j);
+        });
         return he == hipSuccess ? TA_OK : TA_E_HIP;
     });
     if (he != hipSuccess) rc = gfail(g, TA_E_HIP, std::string(what) + " copy: " + hipGetErrorString(he));
     if (rc) return drained(g, who, rc);
     if ((rc = wait_members(g, who))) return rc;
-    for (const MemberPart& p : parts)
-        if (p.h) memset(p.h, 0, sizeof(double) * p.n);  // (+0.0 and 0)
+    each([&](const MemberPart& p, int j) { memset(p.h, 0, sizeof(double) * out.len(j)); });  // (+0.0 and 0)
     for (int i : who) {
         const MemberWord* src = got[i].data();
-        for (const MemberPart& p : parts) {
-            if (!p.h) continue;
+        each([&](const MemberPart& p, int j) {
+            const size_t n = out.len(j);
             if (p.kind == MemberPart::I64)
-                for (size_t k = 0; k < p.n; ++k) ((int64_t*)p.h)[k] += src[k].i;
+                for (size_t k = 0; k < n; ++k) ((int64_t*)p.h)[k] += src[k].i;
             else
-                for (size_t k = 0; k < p.n; ++k) ((double*)p.h)[k] += src[k].f;
-            src += p.n;
-        }
+                for (size_t k = 0; k < n; ++k) ((double*)p.h)[k] += src[k].f;
+            src += n;
+        });
     }
     return TA_OK;
 }
@@ -619,9 +627,8 @@ int ta_group_conductivity(ta_group* g, int fft, const double* h_charges, double*
     TAG_CHECK(check_fft(g, fft));
     if (!h_charges || !h_moment || !h_collective) return gfail(g, TA_E_INVALID, "charges, moment or collective is NULL");
     TAG_CHECK(check_staged(g));
-    const size_t T = (size_t)g->T, D = (size_t)g->D;
     std::vector<int> who;
-    TAG_CHECK(sum_members(g, who, "moment", {{0, T * D, h_moment}, {T * (D + 1), T, h_self_lagsum}}, [&](int i, double** d) {
+    TAG_CHECK(sum_members(g, who, "moment", cond_out(g->T, g->D), {{h_moment}, {nullptr}, {h_self_lagsum}}, [&](int i, double** d) {
         return cond_launch(g->ctx[i], fft, h_charges + g->lo[i], false, h_self_lagsum != nullptr, d);
     }));
     if (const int rc = cond_collective_host(g->ctx[who[0]], fft, h_moment, g->T, g->D, h_collective)) return mfail(g, who[0], rc);
@@ -642,7 +649,7 @@ static int group_collective(ta_group* g, int kind, const char* noun, int fft, in
     TAG_CHECK(check_staged(g));
     TAG_CHECK(check_labels(gfail, g, h_species, g->A, n_species));
     std::vector<int> who;
-    TAG_CHECK(sum_members(g, who, noun, {{0, (size_t)n_species * g->T * g->D, h_sums}}, [&](int i, double** d) {
+    TAG_CHECK(sum_members(g, who, noun, coll_out(n_species, g->T, g->D), {{h_sums}}, [&](int i, double** d) {
         return coll_launch(g->ctx[i], kind, fft, n_species, h_species + g->lo[i], h_weights ? h_weights + g->lo[i] : nullptr, false, d);
     }));
     if (h_cross)
@@ -674,7 +681,7 @@ int ta_group_species_self(ta_group* g, int quantity, int fft, int n_species, con
     TAG_CHECK(check_labels(gfail, g, h_species, g->A, n_species));
     std::vector<std::vector<int64_t>> cnt(g->ctx.size());
     std::vector<int> who;
-    TAG_CHECK(sum_members(g, who, "self terms", {{0, (size_t)n_species * g->T, h_self}}, [&](int i, double** d) {
+    TAG_CHECK(sum_members(g, who, "self terms", self_out(n_species, g->T), {{h_self}}, [&](int i, double** d) {
         cnt[i].assign(n_species, 0);
         return self_launch(g->ctx[i], quantity, fft, n_species, h_species + g->lo[i], h_weights ? h_weights + g->lo[i] : nullptr,
                            cnt[i].data(), d);
@@ -696,12 +703,12 @@ int ta_group_scatter(ta_group* g, int fft, int n_k, const double* h_kvecs, doubl
     TAG_CHECK(check_group(g));
     TAG_CHECK(check_kvecs(gfail, g, fft, n_k, h_kvecs, g->T ? g->D : 0, h_self || h_density || h_coll));
     TAG_CHECK(check_staged(g));
-    const size_t KT = (size_t)n_k * g->T;
+    const OutLayout out = scatter_out(n_k, g->T);
     std::vector<double> own;
-    if (h_coll && !h_density) own.resize(2 * KT);
+    if (h_coll && !h_density) own.resize(out.len(1));
     double* dens = h_density ? h_density : h_coll ? own.data() : nullptr;
     std::vector<int> who;
-    TAG_CHECK(sum_members(g, who, "scattering sums", {{0, KT, h_self}, {KT, 2 * KT, dens}}, [&](int i, double** d) {
+    TAG_CHECK(sum_members(g, who, "scattering sums", out, {{h_self}, {dens}}, [&](int i, double** d) {
         return scatter_launch(g->ctx[i], fft, n_k, h_kvecs, h_self != nullptr, dens != nullptr, false, d);
     }));
     if (h_coll)
@@ -719,12 +726,12 @@ int ta_group_kcurrent(ta_group* g, int fft, int n_k, const double* h_kvecs, cons
     TAG_CHECK(check_group(g));
     TAG_CHECK(check_kcurrent(gfail, g, fft, n_k, h_kvecs, g->T ? g->D : 0, h_current || h_long || h_trans));
     TAG_CHECK(check_staged(g));
-    const size_t n_cur = (size_t)n_k * g->T * g->D * 2;
+    const OutLayout out = kcurrent_out(n_k, g->T, g->D);
     std::vector<double> own;
-    if (!h_current) own.resize(n_cur);
+    if (!h_current) own.resize(out.len(0));
     double* cur = h_current ? h_current : own.data();
     std::vector<int> who;
-    TAG_CHECK(sum_members(g, who, "currents", {{0, n_cur, cur}}, [&](int i, double** d) {
+    TAG_CHECK(sum_members(g, who, "currents", out, {{cur}}, [&](int i, double** d) {
         return kcurrent_launch(g->ctx[i], fft, n_k, h_kvecs, h_weights ? h_weights + g->lo[i] : nullptr, false, d);
     }));
     if (h_long || h_trans)
@@ -744,9 +751,8 @@ int ta_group_partial_density(ta_group* g, int fft, int n_k, const double* h_kvec
     TAG_CHECK(check_partial(gfail, g, fft, n_k, h_kvecs, g->T ? g->D : 0, n_species, h_species, h_density));
     TAG_CHECK(check_staged(g));
     TAG_CHECK(check_labels(gfail, g, h_species, g->A, n_species));
-    const size_t n_den = (size_t)n_k * n_species * g->T * 2;
     std::vector<int> who;
-    TAG_CHECK(sum_members(g, who, "partial densities", {{0, n_den, h_density}}, [&](int i, double** d) {
+    TAG_CHECK(sum_members(g, who, "partial densities", partial_out(n_k, n_species, g->T), {{h_density}}, [&](int i, double** d) {
         return partial_launch(g->ctx[i], fft, n_k, h_kvecs, n_species, h_species + g->lo[i],
                               h_weights ? h_weights + g->lo[i] : nullptr, false, d);
     }));
@@ -763,13 +769,9 @@ int ta_group_vanhove(ta_group* g, int n_lags, const int64_t* h_lags, int n_bins,
     TAG_CHECK(check_group(g));
     TAG_CHECK(check_vanhove(gfail, g, n_lags, h_lags, n_bins, dr, g->T, h_counts || h_moments));
     TAG_CHECK(check_staged(g));
-    const size_t nc = (size_t)n_lags * (size_t)(n_bins + 1), nm = 2 * (size_t)n_lags;
     std::vector<int> who;
-    TAG_CHECK(sum_members(g, who, "van Hove sums", {{0, nc, h_counts, MemberPart::I64}, {nc, nm, h_moments}}, [&](int i, double** d) {
-        void* out = nullptr;
-        const int rc = vanhove_launch(g->ctx[i], n_lags, h_lags, n_bins, dr, h_counts != nullptr, h_moments != nullptr, &out);
-        *d = (double*)out;
-        return rc;
+    TAG_CHECK(sum_members(g, who, "van Hove sums", vanhove_out(n_lags, n_bins), {{h_counts, MemberPart::I64}, {h_moments}}, [&](int i, double** d) {
+        return vanhove_launch(g->ctx[i], n_lags, h_lags, n_bins, dr, h_counts != nullptr, h_moments != nullptr, d);
     }));
     return TA_OK;
     });
@@ -782,13 +784,9 @@ int ta_group_overlap(ta_group* g, int n_lags, const int64_t* h_lags, int n_cutof
     TAG_CHECK(check_group(g));
     TAG_CHECK(check_overlap(gfail, g, n_lags, h_lags, n_cutoffs, h_cutoffs, g->T, h_q != nullptr));
     TAG_CHECK(check_staged(g));
-    const size_t nq = (size_t)n_cutoffs * (size_t)n_lags * (size_t)g->T;
     std::vector<int> who;
-    TAG_CHECK(sum_members(g, who, "overlap counts", {{0, nq, h_q, MemberPart::I64}}, [&](int i, double** d) {
-        int64_t* out = nullptr;
-        const int rc = overlap_launch(g->ctx[i], n_lags, h_lags, n_cutoffs, h_cutoffs, &out);
-        *d = (double*)out;
-        return rc;
+    TAG_CHECK(sum_members(g, who, "overlap counts", overlap_out(n_cutoffs, n_lags, g->T), {{h_q, MemberPart::I64}}, [&](int i, double** d) {
+        return overlap_launch(g->ctx[i], n_lags, h_lags, n_cutoffs, h_cutoffs, d);
     }));
     return TA_OK;
     });
@@ -802,9 +800,8 @@ int ta_group_overlap_density(ta_group* g, int n_k, const double* h_kvecs, int n_
     TAG_CHECK(check_group(g));
     TAG_CHECK(check_overlap_density(gfail, g, n_k, h_kvecs, g->T ? g->D : 0, n_lags, h_lags, n_cutoffs, h_cutoffs, g->T, h_w != nullptr));
     TAG_CHECK(check_staged(g));
-    const size_t nw = 2 * (size_t)n_k * (size_t)n_cutoffs * (size_t)n_lags * (size_t)g->T;
     std::vector<int> who;
-    TAG_CHECK(sum_members(g, who, "overlap densities", {{0, nw, h_w}}, [&](int i, double** d) {
+    TAG_CHECK(sum_members(g, who, "overlap densities", overlap_density_out(n_k, n_cutoffs, n_lags, g->T), {{h_w}}, [&](int i, double** d) {
         return overlap_density_launch(g->ctx[i], n_k, h_kvecs, n_lags, h_lags, n_cutoffs, h_cutoffs, d);
     }));
     return TA_OK;

@@ -72,16 +72,61 @@ struct HostCopy {
     size_t n;
 };
 int host_finish(ta_ctx* ctx, std::initializer_list<HostCopy> copies);
+
+// Where a host-facing call's results lie in the context's output buffer for that call, in 8-byte elements (int64 counts
+// travel as doubles): segment i is [off[i], off[i + 1]), off[n] the buffer's size.  One function per call below lays its
+// segments out, and every consumer asks it: the launch half for the buffer's size and the device outputs (at), the blocking
+// entry for the copies back (api.hip's out_finish), the correlators of host sums for their slices, the group for the parts
+// it sums over its members (group.hip's sum_members).  The comment on each function is the one record of that call's order.
+struct OutLayout {
+    static constexpr int kMax = 4;
+    int n = 0;
+    size_t off[kMax + 1] = {};
+    OutLayout() = default;
+    OutLayout(std::initializer_list<size_t> len) {
+        for (size_t l : len) off[n + 1] = off[n] + l, ++n;
+    }
+    size_t total() const { return off[n]; }
+    size_t len(int i) const { return off[i + 1] - off[i]; }
+    // segment i of the buffer at `base`, or NULL where it is not wanted
+    double* at(double* base, int i, bool want = true) const { return want ? base + off[i] : nullptr; }
+};
+inline size_t out_n(int64_t a, int64_t b = 1, int64_t c = 1, int64_t d = 1, int64_t e = 1) {
+    return (size_t)a * (size_t)b * (size_t)c * (size_t)d * (size_t)e;
+}
+// ta_conductivity: moment (T, D) | Phi (T) | self lag sum (T)
+inline OutLayout cond_out(int64_t T, int D) { return {out_n(T, D), out_n(T), out_n(T)}; }
+// ta_onsager / ta_current: sums (S, T, D) | cross term (T, S, S)
+inline OutLayout coll_out(int S, int64_t T, int D) { return {out_n(S, T, D), out_n(T, S, S)}; }
+// ta_species_self: self lag sums (S, T)
+inline OutLayout self_out(int S, int64_t T) { return {out_n(S, T)}; }
+// ta_scatter: self (K, T) | density (K, T, 2) | coll (K, T)
+inline OutLayout scatter_out(int K, int64_t T) { return {out_n(K, T), out_n(K, T, 2), out_n(K, T)}; }
+// ta_orient: c1 (T) | c2 (T) | total (T, 3) | coll (T)
+inline OutLayout orient_out(int64_t T) { return {out_n(T), out_n(T), out_n(T, 3), out_n(T)}; }
+// ta_kcurrent: current (K, T, D, 2) | long (K, T) | trans (K, T)
+inline OutLayout kcurrent_out(int K, int64_t T, int D) { return {out_n(K, T, D, 2), out_n(K, T), out_n(K, T)}; }
+// ta_partial_density: density (K, S, T, 2) | cross term (K, T, S, S)
+inline OutLayout partial_out(int K, int S, int64_t T) { return {out_n(K, S, T, 2), out_n(K, T, S, S)}; }
+// ta_vanhove: counts (L, B + 1) int64 | moments (L, 2)
+inline OutLayout vanhove_out(int L, int B) { return {out_n(L, B + 1), out_n(L, 2)}; }
+// ta_overlap: Q (C, L, T) int64
+inline OutLayout overlap_out(int C, int L, int64_t T) { return {out_n(C, L, T)}; }
+// ta_overlap_density: W (K, C, L, T, 2)
+inline OutLayout overlap_density_out(int K, int C, int L, int64_t T) { return {out_n(K, C, L, T, 2)}; }
+// ta_vanhove_distinct: counts (L, B + 1) int64
+inline OutLayout vhd_out(int L, int B) { return {out_n(L, B + 1)}; }
+
 // api.hip, for group.hip: one context's conductivity share (ta_conductivity on its staged slab 0 with its atoms' charges
-// h_q), queued: *d_out = the (n_frames, dim) moment, then Phi (coll), then the self lag sum (self), valid after
-// host_wait; and Phi of a host (n_frames, dim) moment on the context's device, blocking
+// h_q), queued: *d_out = cond_out's segments (Phi with coll, the self lag sum with self), valid after host_wait; and Phi
+// of a host (n_frames, dim) moment on the context's device, blocking
 int cond_launch(ta_ctx* ctx, int fft, const double* h_q, bool coll, bool self, double** d_out);
 int cond_collective_host(ta_ctx* ctx, int fft, const double* h_moment, int64_t T, int D, double* h_coll);
 // api.hip, for group.hip: the two species-collective quantities, Onsager moments (ta_onsager*) and Green-Kubo currents
 // (ta_current*), share one host path (api.hip's Collective table, indexed by `kind`).  One context's share (its staged
-// slab 0 with its atoms' labels h_species and weights h_w or NULL, n_species the call's), queued: *d_out = the (n_species,
-// n_frames, dim) sums, valid after host_wait; and the cross term (n_frames, S, S) of host sums (S, n_frames, dim) on the
-// context's device, blocking
+// slab 0 with its atoms' labels h_species and weights h_w or NULL, n_species the call's), queued: *d_out = coll_out's
+// segments (the cross term with cross), valid after host_wait; and the cross term of host sums on the context's device,
+// blocking
 enum CollKind { COLL_MOMENTS = 0, COLL_CURRENTS = 1 };
 int coll_launch(ta_ctx* ctx, int kind, int fft, int S, const int32_t* h_species, const double* h_w, bool cross, double** d_out);
 int coll_cross_host(ta_ctx* ctx, int kind, int fft, const double* h_sums, int S, int64_t T, int D, double* h_cross);
@@ -102,10 +147,16 @@ static int check_labels(Fail fail, Owner* owner, const int32_t* h_species, int64
     return TA_OK;
 }
 // api.hip, for group.hip: one context's ta_species_self share (its staged slab 0 with its atoms' labels and weights, the
-// call's n_species; labels checked here), queued: *d_out = the (n_species, n_frames) self lag sums, valid after host_wait;
-// h_counts (n_species) or NULL: its atoms per species
+// call's n_species; labels checked here), queued: *d_out = self_out's segment, valid after host_wait; h_counts (n_species)
+// or NULL: its atoms per species
 int self_launch(ta_ctx* ctx, int quantity, int fft, int S, const int32_t* h_species, const double* h_w, int64_t* h_counts,
                 double** d_out);
+// "[<prefix>]n_k must be 1 ... TA_SCATTER_MAX_K", for every call that takes wavevectors
+template <class Fail, class Owner>
+static int check_n_k(Fail fail, Owner* owner, int n_k, const std::string& p = "") {
+    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(owner, TA_E_INVALID, p + "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
+    return TA_OK;
+}
 // the wavevector checks of ta_scatter* on a context (fail, ctx) or a group (gfail, g): the same messages for both.  D: the
 // components per wavevector (0: not known, nothing staged -- the caller reports that next)
 template <class Fail, class Owner>
@@ -113,15 +164,15 @@ static int check_kvecs(Fail fail, Owner* owner, int fft, int n_k, const double* 
     if (fft != 0 && fft != 1) return fail(owner, TA_E_INVALID, "fft must be 0 or 1");
     if (!any_output) return fail(owner, TA_E_INVALID, "scatter: the self, density and collective outputs are all NULL");
     if (!h_kvecs) return fail(owner, TA_E_INVALID, "wavevectors are NULL");
-    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(owner, TA_E_INVALID, "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
+    if (const int rc = check_n_k(fail, owner, n_k)) return rc;
     for (int64_t i = 0; i < (int64_t)n_k * D; ++i)
         if (!(h_kvecs[i] - h_kvecs[i] == 0.0))
             return fail(owner, TA_E_INVALID, "wavevector " + std::to_string(i / D) + " has a non-finite component");
     return TA_OK;
 }
 // api.hip, for group.hip: one context's ta_scatter share (its staged slab 0, the call's wavevectors, checked by the caller),
-// queued: *d_out = self (n_k, n_frames), then the density (n_k, n_frames, 2), then coll (n_k, n_frames) -- the ones asked
-// for are valid after host_wait; and the collective part of a host density on the context's device, blocking
+// queued: *d_out = scatter_out's segments -- the ones asked for are valid after host_wait; and the collective part of a
+// host density on the context's device, blocking
 int scatter_launch(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, bool self, bool density, bool coll, double** d_out);
 int scatter_collective_host(ta_ctx* ctx, int fft, const double* h_density, int n_k, int64_t T, double* h_coll);
 // the argument checks of ta_kcurrent* on a context (fail, ctx) or a group (gfail, g): the same messages for both.  D: the
@@ -131,7 +182,7 @@ static int check_kcurrent(Fail fail, Owner* owner, int fft, int n_k, const doubl
     if (fft != 0 && fft != 1) return fail(owner, TA_E_INVALID, "fft must be 0 or 1");
     if (!any_output) return fail(owner, TA_E_INVALID, "kcurrent: the current, longitudinal and transverse outputs are all NULL");
     if (!h_kvecs) return fail(owner, TA_E_INVALID, "wavevectors are NULL");
-    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(owner, TA_E_INVALID, "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
+    if (const int rc = check_n_k(fail, owner, n_k)) return rc;
     for (int j = 0; j < n_k && D > 0; ++j) {
         for (int d = 0; d < D; ++d) {
             const double c = h_kvecs[(int64_t)j * D + d];
@@ -145,9 +196,8 @@ static int check_kcurrent(Fail fail, Owner* owner, int fft, int n_k, const doubl
     return TA_OK;
 }
 // api.hip, for group.hip: one context's ta_kcurrent share (its staged slabs 0 and 1, the call's wavevectors, checked by the
-// caller, its atoms' weights h_w or NULL), queued: *d_out = the current (n_k, n_frames, dim, 2), then (correlate) long
-// (n_k, n_frames) and trans (n_k, n_frames), valid after host_wait; and the two correlations of a host current on the
-// context's device, blocking
+// caller, its atoms' weights h_w or NULL), queued: *d_out = kcurrent_out's segments (long and trans with correlate), valid
+// after host_wait; and the two correlations of a host current on the context's device, blocking
 int kcurrent_launch(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, const double* h_w, bool correlate, double** d_out);
 int kcurrent_correlate_host(ta_ctx* ctx, int fft, const double* h_current, int n_k, const double* h_kvecs, int64_t T, int D,
                             double* h_long, double* h_trans);
@@ -160,7 +210,7 @@ static int check_partial(Fail fail, Owner* owner, int fft, int n_k, const double
     if (fft != 0 && fft != 1) return fail(owner, TA_E_INVALID, "fft must be 0 or 1");
     if (const int rc = check_species_count(fail, owner, S)) return rc;
     if (!h_kvecs) return fail(owner, TA_E_INVALID, "wavevectors are NULL");
-    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(owner, TA_E_INVALID, "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
+    if (const int rc = check_n_k(fail, owner, n_k)) return rc;
     for (int64_t i = 0; i < (int64_t)n_k * D; ++i)
         if (!(h_kvecs[i] - h_kvecs[i] == 0.0))
             return fail(owner, TA_E_INVALID, "wavevector " + std::to_string(i / D) + " has a non-finite component");
@@ -169,9 +219,9 @@ static int check_partial(Fail fail, Owner* owner, int fft, int n_k, const double
     return TA_OK;
 }
 // api.hip, for group.hip: one context's ta_partial_density share (its staged slab 0, the call's wavevectors, checked by the
-// caller, its atoms' labels h_species (checked by the caller) and weights h_w or NULL), queued: *d_out = the density (n_k,
-// n_species, n_frames, 2), then (cross) the cross term (n_k, n_frames, S, S), valid after host_wait; and the cross term of a
-// host density on the context's device, blocking
+// caller, its atoms' labels h_species (checked by the caller) and weights h_w or NULL), queued: *d_out = partial_out's
+// segments (the cross term with cross), valid after host_wait; and the cross term of a host density on the context's
+// device, blocking
 int partial_launch(ta_ctx* ctx, int fft, int n_k, const double* h_kvecs, int S, const int32_t* h_species, const double* h_w,
                    bool cross, double** d_out);
 int partial_cross_host(ta_ctx* ctx, int fft, const double* h_density, int n_k, int S, int64_t T, double* h_cross);
@@ -207,9 +257,8 @@ static int check_vanhove(Fail fail, Owner* owner, int n_lags, const int64_t* h_l
     return check_vanhove_lags(fail, owner, "vanhove: ", n_lags, h_lags, T);
 }
 // api.hip, for group.hip: one context's ta_vanhove share (its staged slab 0, the call's lags and bins, checked by the
-// caller), queued: *d_out = counts (n_lags, n_bins + 1) int64, then moments (n_lags, 2) float64 -- the ones asked for are
-// valid after host_wait
-int vanhove_launch(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, double dr, bool counts, bool moments, void** d_out);
+// caller), queued: *d_out = vanhove_out's segments -- the ones asked for are valid after host_wait
+int vanhove_launch(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_bins, double dr, bool counts, bool moments, double** d_out);
 // the argument checks of ta_overlap* (context or group: the same messages for both), all of them before anything is written.
 // T: the frames (0: not known, nothing staged -- the caller reports that next).  check_overlap_lists: the lags, the cutoffs and
 // the output under the family's message prefix `p`, shared with ta_overlap_density*
@@ -249,7 +298,7 @@ static int check_overlap_density(Fail fail, Owner* owner, int n_k, const double*
                                  int n_cutoffs, const double* h_cutoffs, int64_t T, bool any_output) {
     const std::string p = "overlap_density: ";
     if (!h_kvecs) return fail(owner, TA_E_INVALID, p + "wavevectors are NULL");
-    if (n_k < 1 || n_k > TA_SCATTER_MAX_K) return fail(owner, TA_E_INVALID, p + "n_k must be 1 ... " + std::to_string(TA_SCATTER_MAX_K));
+    if (const int rc = check_n_k(fail, owner, n_k, p)) return rc;
     for (int64_t i = 0; i < (int64_t)n_k * D; ++i)
         if (!(h_kvecs[i] - h_kvecs[i] == 0.0))
             return fail(owner, TA_E_INVALID, p + "wavevector " + std::to_string(i / D) + " has a non-finite component");
@@ -261,12 +310,12 @@ static int check_overlap_density(Fail fail, Owner* owner, int n_k, const double*
     return TA_OK;
 }
 // api.hip, for group.hip: one context's ta_overlap_density share (its staged slab 0, the call's wavevectors, lags and
-// cutoffs, checked by the caller), queued: *d_out = W (n_k, n_cutoffs, n_lags, n_frames, 2), valid after host_wait
+// cutoffs, checked by the caller), queued: *d_out = overlap_density_out's segment, valid after host_wait
 int overlap_density_launch(ta_ctx* ctx, int n_k, const double* h_kvecs, int n_lags, const int64_t* h_lags, int n_cutoffs,
                            const double* h_cutoffs, double** d_out);
 // api.hip, for group.hip: one context's ta_overlap share (its staged slab 0, the call's lags and cutoffs, checked by the
-// caller), queued: *d_out = Q (n_cutoffs, n_lags, n_frames) int64, valid after host_wait
-int overlap_launch(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs, int64_t** d_out);
+// caller), queued: *d_out = overlap_out's segment, valid after host_wait
+int overlap_launch(ta_ctx* ctx, int n_lags, const int64_t* h_lags, int n_cutoffs, const double* h_cutoffs, double** d_out);
 // api.hip, for group.hip: one context's ta_unwrap queued on its stream (box.tab must stay valid until host_wait)
 int unwrap_launch(ta_ctx* ctx, int slab, const BoxTable& box, const int* axes);
 hipStream_t ctx_stream(ta_ctx* ctx);
