@@ -68,7 +68,7 @@ extern "C" {
 
 /* ta_ctx_create(TA_DEVICE_CPU, ...): the OPT-IN CPU backend behind the same symbols (csrc/cpu_backend.cpp, C++/OpenMP,
  * SURVEY.md section 8(b)): host slabs only, ta_stage_alloc / ta_stage_frame / ta_stage_commit (a no-op) / ta_vacf_fft /
- * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_pair_find / ta_pair_find_read / ta_pair_lifetime / ta_bond_lifetime / ta_shell_residence / ta_shell_msd / ta_shell_orient / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
+ * ta_vacf_direct / ta_helfand_msd / ta_msd / ta_conductivity / ta_onsager / ta_onsager_cross / ta_current / ta_current_cross / ta_species_self / ta_orient / ta_chain_modes / ta_pair_find / ta_pair_find_read / ta_pair_lifetime / ta_bond_lifetime / ta_shell_residence / ta_shell_msd / ta_shell_orient / ta_unwrap / ta_compound / ta_stage_synth (into the host slab) / ta_set_option ("cpu_threads") / ta_stage_free /
  * ta_trim work as documented below and
  * compute on the host cores; every device-facing call (ta_stage_alloc_device, *_dev, *_staged, ta_stage_commit_dev,
  * timings, ta_group_*) returns TA_E_UNSUPPORTED.  It is never chosen on the caller's behalf: every other
@@ -158,7 +158,8 @@ int ta_stage_synth(ta_ctx *ctx, int slab, uint64_t seed, int64_t col_offset, int
  * member entry, 12 per compound) and, with frame weights, the (n_frames, dim) weighted mean and its partial sums (the
  * ta_onsager workspace); for ta_orient* the block of the orientation columns (3 * n_vectors * pitch * 16 bytes, shared by
  * the two ranks), the pair-major copy of the total (and the (n_frames, 3) total itself when it is not asked for) and the
- * sum's partial sums (the ta_onsager workspace);
+ * sum's partial sums (the ta_onsager workspace); for ta_chain_modes* the blocks of one batch of modes (3 * n_chains * pitch * 8
+ * bytes per mode);
  * the labels, weights and outputs of host-facing calls are kept.                                                                                                            */
 int ta_trim(ta_ctx *ctx);
 
@@ -867,6 +868,59 @@ int ta_shell_orient(ta_ctx *ctx, int condition, int64_t max_lag, int mode, int a
 int ta_orient(ta_ctx *ctx, int fft, int mode, int64_t n_vectors, const int32_t *h_index, const double *h_dimensions,
               const double *h_weights, double *h_c1, double *h_c2, double *h_total, double *h_coll);
 
+/* ta_chain_modes : autocorrelations of linear functionals of whole chains of the positions in slab 0 (RouseModes: the Rouse
+ *              normal modes X_p, the end-to-end vector), three staged columns per atom.  Chain c is row c of h_members
+ *              (n_chains, chain_len) int32, row-major: chain_len = N >= 2 atoms (beads) of slab 0 in backbone order, pairwise
+ *              distinct within the row and in [0, n_atoms); chains may share atoms.  h_coeff (n_modes, N) float64, row-major,
+ *              is all the call knows about the functionals.  Per frame t:
+ *                s_1 = 0,   s_n = s_{n-1} + img(x[t, m_n] - x[t, m_{n-1}])            n = 2 ... N
+ *                Y_q(c, t) = sum_{n = 2 ... N} h_coeff[q * N + n - 1] * s_n           q = 0 ... n_modes - 1
+ *                h_acf[q * T + tau] = 1/(T - tau) sum_{t < T - tau} sum_c Y_q(c, t) . Y_q(c, t + tau)
+ *              s is the chain made whole relative to its first bead; h_coeff[q * N + 0] is read and checked but multiplies
+ *              s_1 = 0.  A row of coefficients that sums to zero is therefore the same functional of the absolute positions,
+ *              without any unwrapping: cos(p pi (n - 1/2) / N) / N is the Rouse mode X_p = 1/N sum_n r_n cos(p pi (n - 1/2) / N),
+ *              p = 1 ... N - 1, and the unit row e_N the end-to-end vector r_N - r_1.  Lag 0 is kept.  NOTHING is divided by
+ *              n_chains (RouseModes does that).  h_acf adds up over disjoint chain lists.
+ *              Arithmetic (csrc/chain_math.hpp; the CPU backend runs the same sequence).  img is ta_orient's difference
+ *              (csrc/orient_math.hpp, orient_diff): x[m_n] - x[m_{n-1}] in float64 (a float32 slab: widened first), and with
+ *              h_dimensions (n_frames, 6) as for ta_unwrap (NULL: nothing is reduced) ONE sequential image step per axis, z,
+ *              then y, then x, with the box of frame t, bit for bit the step documented under ta_orient: an orthorhombic box
+ *              given as a triclinic table of the same H gives the same bits, per-frame boxes (NPT) are followed, and it is
+ *              the MINIMUM image while every bond is shorter than half the smallest box width, whichever periodic images
+ *              the beads are.  Then s_j = s_j + d_j, a plain add, and per mode acc_j = fma(coeff, s_j, acc_j) from acc = 0,
+ *              in bead order.
+ *              Error bound per component of Y_q, with e = 2^-53, from that sequence.  A bond d: one rounding of the raw
+ *              difference and, with a box, one rounding per image step it goes through, each of an intermediate no larger
+ *              than the raw difference: within (1 + 3 R) e b, b the longest bond and R = the largest raw |x_b - x_a|
+ *              component over b (0 without a box; about the box length over the bond length for wrapped chains).  s_n: n - 1
+ *              bonds and n - 2 roundings of partial sums no larger than the chain's extent S = max_n |s_n| <= (N - 1) b, so
+ *              within ((1 + 3 R) b + S) (N - 1) e.  Y_q: N - 1 fmas, each one rounding of a partial sum bounded by
+ *              A_q S, A_q = sum_n |coeff[q][n]|: every component of Y_q is within (N - 1) e (2 S + (1 + 3 R) b) A_q of the
+ *              exact functional of the staged values -- a few thousand e times the chain's extent for chains of a hundred
+ *              beads, far inside the lag sums' bar.  acf: the library's usual 1e-10 of the series' maximum.
+ *              The pass k_chain_modes reads the slab in the element type it has (a float32 device slab as float32, widened
+ *              in registers; never widened first) and walks every chain once for up to M modes, M of ta_chain_modes_tile:
+ *              a call takes ceil(B / M) passes per batch of B modes, each a read of the slab.  A pass writes one float64
+ *              pair-major block per mode, n_chains pseudo-atoms of dim 3 holding Y_q, rows n_frames ... pitch - 1 zeros
+ *              (no atomics, one writer per element: the same bits from run to run); each row of h_acf is ONE lag-sum
+ *              evaluation of ta_vacf_fft (fft = 1) / ta_vacf_direct (fft = 0) on its block.  A batch is as many modes as
+ *              keep the blocks (3 n_chains pitch 8 bytes each) under 2 GiB, at least one (TA_E_NOMEM when that does not
+ *              fit); option "chain_modes_chunk".  A mode's result does not depend on the batch or the pass it was in, bit
+ *              for bit.  ta_trim releases the blocks.  The staged slab is not changed.
+ *              fft other than 0 / 1, n_chains < 1, chain_len < 2, n_modes < 1, a NULL h_members, h_coeff or output, dim != 3,
+ *              n_atoms * 3 or n_modes * n_chains * 3 at or above 2^31, a member out of range, an atom twice in a chain, a
+ *              non-finite coefficient, a box ta_unwrap's table rejects (all checked before anything is written):
+ *              TA_E_INVALID; nothing staged: TA_E_STATE.  CPU backend: the same arithmetic, OpenMP over chains, one
+ *              frame-major array per mode and its VACF routines.  There is no *_dev entry and no ta_group_* form: a chain's
+ *              atoms would have to share a shard.  Cross-correlations between modes and per-chain results are not formed.
+ *              Timings: the (last) pass is the main kernel unless an evaluation after it records its own
+ *              (ta_kernel_timeline names it k_chain_modes, once per pass).
+ * ta_chain_modes_tile: *modes = M, the modes one pass of k_chain_modes serves, *frames = the frames per thread (a workgroup
+ *              covers 256 of them); either may be NULL.                                                                  */
+int ta_chain_modes(ta_ctx *ctx, int fft, int64_t n_chains, int64_t chain_len, const int32_t *h_members, int n_modes,
+                   const double *h_coeff, const double *h_dimensions, double *h_acf);
+int ta_chain_modes_tile(int *modes, int *frames);
+
 /* ---- periodic unwrapping of a staged position slab ---------------------------------------------------------------
  * ta_unwrap: undo periodic wrapping of staging slab `slab` in place (MDAnalysis' NoJump), over the staged frames
  * in order.  h_dimensions: (n_frames, 6) float64 rows [a, b, c, alpha, beta, gamma] (A, degrees; ts.dimensions).
@@ -1014,6 +1068,12 @@ int ta_scatter_staged(ta_ctx *ctx, int fft, int n_k, const double *h_kvecs, doub
 /* h_index, h_dimensions, h_weights: HOST arrays, as for ta_orient_dev; slab 0 (the positions) is read in the element type it has */
 int ta_orient_staged(ta_ctx *ctx, int fft, int mode, int64_t n_vectors, const int32_t *h_index, const double *h_dimensions,
                      const double *h_weights, double *d_c1, double *d_c2, double *d_total, double *d_coll, void *stream);
+
+/* h_members, h_coeff, h_dimensions: HOST arrays, as for ta_chain_modes (checked before anything is written); d_acf (n_modes,
+ * n_frames) on the device; asynchronous on `stream`, as ta_orient_staged; slab 0 (the positions) is read in the element type
+ * it has */
+int ta_chain_modes_staged(ta_ctx *ctx, int fft, int64_t n_chains, int64_t chain_len, const int32_t *h_members, int n_modes,
+                          const double *h_coeff, const double *h_dimensions, double *d_acf, void *stream);
 
 /* h_kvecs: HOST wavevectors, d_weights: device weights (n_atoms) or NULL, as ta_conductivity_staged's charges; slab 0 (the
  * velocities) and slab 1 (the positions) are read in the element type they have; each output may be NULL, not all three */
@@ -1282,6 +1342,8 @@ int ta_fft_plan_info(int64_t n_frames, int64_t *m_out, int *n_threads, int *n_st
  *                      A batch is ONE by-particle evaluation of its n S^2 pseudo-particles.  With fft = 0, and with an even
  *                      S^2, the results do not depend on it; with fft = 1 and an odd S^2 other pseudo-particles share a
  *                      transform in another batching and the results agree within the FFT path's bound;
+ *   "chain_modes_chunk" n : modes per batch of ta_chain_modes* (0, the default: as many as keep the batch's blocks under
+ *                      2 GiB, at least 1; n >= 1: min(n, that count)); the results do not depend on it bit for bit;
  *   "vanhove_chunk" n : lags per pass of ta_vanhove* (0, the default: as many as fit 64 KiB of LDS; n >= 1: min(n, n_lags,
  *                      that count)); the results do not depend on it;
  *   "overlap_chunk" n : lags per launch of ta_overlap* (0, the default: floor(S / n_cutoffs), S of ta_overlap_tile; n >= 1:

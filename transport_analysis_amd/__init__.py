@@ -10,7 +10,8 @@ C_1(t), C_2(t) of molecule-fixed unit vectors with their dipole sum, Orientation
 continuous pair population correlation functions with the lifetimes of ion pairs and solvation contacts, PairLifetime, and
 of hydrogen bonds with a donor-hydrogen-acceptor angle criterion, HydrogenBondLifetime, and the residence times of atoms in
 the solvation shell of a whole group, ShellResidence, with the mean squared displacement of the atoms while they stay in that
-shell, ShellMSD, and the reorientation of their molecules while they stay there, ShellOrientation."""
+shell, ShellMSD, and the reorientation of their molecules while they stay there, ShellOrientation, and the autocorrelations
+of the Rouse normal modes and of the end-to-end vector of chains, RouseModes."""
 __version__ = "0.1.0"
 
 from .velocityautocorr import VelocityAutocorr  # noqa: F401
@@ -32,3 +33,4 @@ from .hbond_lifetime import HydrogenBondLifetime  # noqa: F401
 from .shell_residence import ShellResidence  # noqa: F401
 from .shell_msd import ShellMSD  # noqa: F401
 from .shell_orientation import ShellOrientation  # noqa: F401
+from .rouse import RouseModes  # noqa: F401

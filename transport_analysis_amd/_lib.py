@@ -81,6 +81,9 @@ _API = {
     "ta_orient": _int(_vp, _ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp),
     "ta_orient_dev": _int(_vp, _vp, _i64, _i64, _ci, _i64, _ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp),
     "ta_orient_staged": _int(_vp, _ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp),
+    "ta_chain_modes": _int(_vp, _ci, _i64, _i64, _vp, _ci, _vp, _vp, _vp),
+    "ta_chain_modes_staged": _int(_vp, _ci, _i64, _i64, _vp, _ci, _vp, _vp, _vp, _vp),
+    "ta_chain_modes_tile": _int(_P(_ci), _P(_ci)),
     "ta_kcurrent": _KCURRENT, "ta_kcurrent_correlate": _int(_vp, _ci, _vp, _ci, _vp, _i64, _ci, _vp, _vp),
     "ta_kcurrent_tile": _int(_P(_ci), _P(_ci), _P(_ci)),
     "ta_kcurrent_staged": _int(_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp),
@@ -249,6 +252,14 @@ def overlap_density_tile():
     sl, kc, f = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     lib().ta_overlap_density_tile(ctypes.byref(sl), ctypes.byref(kc), ctypes.byref(f))
     return {"SL": sl.value, "KC": kc.value, "F": f.value}
+
+
+def chain_modes_tile():
+    """{"modes", "frames"}: the modes one k_chain_modes launch serves and the frames per thread (a workgroup covers 256 of
+    them), ta_chain_modes_tile"""
+    m, f = ctypes.c_int(), ctypes.c_int()
+    lib().ta_chain_modes_tile(ctypes.byref(m), ctypes.byref(f))
+    return {"modes": m.value, "frames": f.value}
 
 
 def _ptr(a):
@@ -1218,6 +1229,44 @@ class Context(_Staged):
         """`index`, `dimensions`, `weights`: HOST arrays (checked by the library before anything is written)"""
         args, keep = self._orient_args(fft, index, mode, dimensions, weights)
         self._call("orient_staged", *args, d_c1 or None, d_c2 or None, d_total or None, d_coll or None, stream or None)
+        del keep
+
+    def _chain_args(self, fft, members, coeff, dimensions):
+        """the argument tuple ta_chain_modes* share, and the arrays it points into (to be kept until the call is over)"""
+        mem = np.ascontiguousarray(members)
+        if mem.ndim != 2 or not np.issubdtype(mem.dtype, np.integer):
+            raise ValueError(f"members: shape {mem.shape} and dtype {mem.dtype}, expected an integer (n_chains, chain_len) array")
+        if mem.size and (mem.min() < -2**31 or mem.max() >= 2**31):
+            raise ValueError("members: entries must fit int32")
+        mem = np.ascontiguousarray(mem, dtype=np.int32)
+        co = np.ascontiguousarray(coeff, dtype=np.float64)
+        if co.ndim != 2 or co.shape[1] != mem.shape[1]:
+            raise ValueError(f"coeff: shape {co.shape}, expected (n_modes, {mem.shape[1]}) (one coefficient per bead)")
+        dims = None
+        if dimensions is not None:
+            dims = np.ascontiguousarray(dimensions, dtype=np.float64)
+            if self.shape is not None and dims.shape != (self.shape[0], 6):
+                raise ValueError(f"dimensions: shape {dims.shape}, expected ({self.shape[0]}, 6) (one box per staged frame)")
+        return (int(fft), int(mem.shape[0]), int(mem.shape[1]), _ptr(mem), int(co.shape[0]), _ptr(co), _ptr(dims)), (mem, co, dims)
+
+    def chain_modes(self, fft, members, coeff, dimensions=None):
+        """Autocorrelations of linear functionals of whole chains of slab 0 (the positions, three columns per atom),
+        ta_chain_modes: `members` (n_chains, chain_len) atoms in backbone order, `coeff` (n_modes, chain_len) one row per
+        functional of the chain made whole bead by bead (relative to its first bead), `dimensions` the (n_frames, 6) boxes of
+        the staged frames for the image step (None: nothing is reduced): acf (n_modes, n_frames), the sum over chains, not
+        divided by their number.  One context only: a device group has no such call."""
+        T = self._staged_shape()[0]
+        args, keep = self._chain_args(fft, members, coeff, dimensions)
+        acf = np.empty((args[4], T), dtype=np.float64)
+        self._call("chain_modes", *args, _ptr(acf))
+        del keep
+        return acf
+
+    def chain_modes_staged(self, fft, members, coeff, dimensions=None, d_acf=0, stream=0):
+        """`members`, `coeff`, `dimensions`: HOST arrays (checked by the library before anything is written); d_acf (n_modes,
+        n_frames) on the device"""
+        args, keep = self._chain_args(fft, members, coeff, dimensions)
+        self._call("chain_modes_staged", *args, d_acf or None, stream or None)
         del keep
 
     # -- timing ----------------------------------------------------------

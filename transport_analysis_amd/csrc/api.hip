@@ -23,6 +23,7 @@
 #include "cpu_backend.hpp"
 #include "direct_kernels.hpp"
 #include "kcurrent_math.hpp"
+#include "chain_math.hpp"
 #include "orient_math.hpp"
 #include "pair_math.hpp"
 #include "phase_math.hpp"
@@ -127,6 +128,7 @@ private:
     X(kcurrent_chunk, 0, opt_check_kcurrent_chunk) /* wavevectors per launch of k_kcurrent (0: the tile's own count) */     \
     X(partial_chunk, 0, opt_check_partial_chunk) /* wavevectors per launch of k_species_density (0: the tile's own count) */ \
     X(partial_cross_chunk, 0, opt_check_partial_cross_chunk) /* wavevectors per batch of partial_cross (0: as many as fit kPartialCrossBudget) */ \
+    X(chain_modes_chunk, 0, opt_check_chain_modes_chunk) /* functionals per batch of ta_chain_modes* (0: as many as fit kChainBudget) */ \
     X(vanhove_chunk, 0, opt_check_vanhove_chunk) /* lags per pass of ta_vanhove* (0: as many as fit a workgroup's LDS) */ \
     X(overlap_chunk, 0, opt_check_overlap_chunk) /* lags per launch of ta_overlap* (0: as many as the kernel's tile holds) */ \
     X(overlap_density_chunk, 0, opt_check_overlap_density_chunk) /* lags per launch of ta_overlap_density* (0: as many as the kernel's tile holds) */ \
@@ -188,6 +190,10 @@ struct ta_ctx {
     // ask for it), the table (box rows, weights, index rows, zero labels), the outputs of host-facing calls
     DevBuf orient_z{workspaces, kTrimmed}, orient_work{workspaces, kTrimmed}, orient_out{workspaces, kKept};
     HostTable orient_tab{workspaces, tables};
+    // chain normal modes (chain_pm): the blocks of one batch of functionals (3 n_chains pitch 8 bytes each; trimmed), the
+    // table (box rows, coefficients, members), the output of host-facing calls
+    DevBuf chain_z{workspaces, kTrimmed}, chain_out{workspaces, kKept};
+    HostTable chain_tab{workspaces, tables};
     // current correlation functions (kcurrent_pm): the partial sums of one chunk of wavevectors (trimmed; its size does not
     // depend on their number), the pair-major slab of the pseudo-atoms jL, jT with their by-particle lag sums (and the current
     // itself when the caller does not ask for it), the wavevectors in turns with the unit vectors (and a host call's weights)
@@ -1476,6 +1482,129 @@ int orient_entry(ta_ctx* ctx, const DevSrc* dev, int fft, int mode, int64_t N, c
         });
 }
 
+// ---- chain normal modes (chain_modes.hip) ---------------------------------------------------------------------------
+// The budget of the blocks of one batch of functionals (3 n_chains pitch 8 bytes each): a choice, not a measurement.  It
+// bounds memory and nothing else: a functional's lag sum does not depend on its neighbours in the batch.
+constexpr size_t kChainBudget = (size_t)2 << 30;
+
+// The caller's arguments of ta_chain_modes*, as they came
+struct ChainArgs {
+    int fft;
+    int64_t C, N;  // chains, beads per chain
+    const int32_t* h_members;
+    int Q;
+    const double *h_coeff, *h_dims;
+    const void* out;
+};
+
+// Every check of ta_chain_modes* (both kinds of context), all of them before anything is written.  With h_dims the box table
+// (unwrap_box.hpp; per-frame rows padded to the pitch) is left in *box.
+int chain_check(ta_ctx* ctx, const ChainArgs& a, BoxTable* box) {
+    const std::string p = "chain_modes: ";
+    TA_CHECK(check_fft(ctx, a.fft));
+    if (a.C < 1) return fail(ctx, TA_E_INVALID, p + "n_chains must be >= 1");
+    if (a.N < 2) return fail(ctx, TA_E_INVALID, p + "chain_len must be >= 2");
+    if (a.Q < 1) return fail(ctx, TA_E_INVALID, p + "n_modes must be >= 1");
+    if (!a.h_members) return fail(ctx, TA_E_INVALID, p + "the member table is NULL");
+    if (!a.h_coeff) return fail(ctx, TA_E_INVALID, p + "the coefficient matrix is NULL");
+    if (!a.out) return fail(ctx, TA_E_INVALID, p + "the acf output is NULL");
+    TA_CHECK(check_staged(ctx));
+    const int64_t T = ctx->st_T, A = ctx->st_A;
+    if (ctx->st_D != 3)
+        return fail(ctx, TA_E_INVALID, p + "the position slab must hold three columns per atom (dim = " + std::to_string(ctx->st_D) + ")");
+    if (A * 3 >= (int64_t)1 << 31 || a.N >= (int64_t)1 << 31 || a.C >= (int64_t)1 << 31 || (int64_t)a.Q * a.C * 3 >= (int64_t)1 << 31)
+        return fail(ctx, TA_E_INVALID, p + "n_atoms * 3 and n_modes * n_chains * 3 must be below 2^31");
+    std::vector<int32_t> row((size_t)a.N);
+    for (int64_t c = 0; c < a.C; ++c) {
+        const int32_t* r = a.h_members + c * a.N;
+        for (int64_t n = 0; n < a.N; ++n)
+            if (r[n] < 0 || r[n] >= A)
+                return fail(ctx, TA_E_INVALID, p + "member " + std::to_string(r[n]) + " of chain " + std::to_string(c) +
+                                                   " is outside 0 ... n_atoms - 1");
+        row.assign(r, r + a.N);
+        std::sort(row.begin(), row.end());
+        if (std::adjacent_find(row.begin(), row.end()) != row.end())
+            return fail(ctx, TA_E_INVALID, p + "chain " + std::to_string(c) + " names an atom twice");
+    }
+    for (int64_t i = 0; i < (int64_t)a.Q * a.N; ++i)
+        if (!(a.h_coeff[i] - a.h_coeff[i] == 0.0))
+            return fail(ctx, TA_E_INVALID, p + "coefficient " + std::to_string(i % a.N) + " of mode " + std::to_string(i / a.N) + " is not finite");
+    if (a.h_dims) {
+        const int axes[3] = {0, 1, 2};
+        const std::string why = box_table(a.h_dims, T, 3, axes, 8, box);
+        if (!why.empty()) return fail(ctx, TA_E_INVALID, p + why);
+    }
+    return TA_OK;
+}
+
+// The host half of one call, before it is opened: the table -- box rows (orient_box_rows) | coefficients (Q, N) | members
+// (C, N) int32 -- queued for upload on `st`.  Nothing on the device has been written when this fails.
+struct ChainPlan {
+    int64_t C = 0, N = 0, tpitch = 0;  // tpitch 0: no box
+    int Q = 0;
+    size_t n_box() const { return (size_t)kOrientBoxRows * (size_t)tpitch; }
+};
+int chain_plan(ta_ctx* ctx, const ChainArgs& a, const BoxTable& box, hipStream_t st, ChainPlan* p) {
+    p->C = a.C, p->N = a.N, p->Q = a.Q, p->tpitch = a.h_dims ? box.tpitch : 0;
+    const size_t n_coeff = (size_t)a.Q * (size_t)a.N, n_member = (size_t)a.C * (size_t)a.N;
+    const size_t n = p->n_box() + n_coeff + (n_member + 1) / 2;
+    double* h = nullptr;
+    TA_CHECK(ctx->chain_tab.begin(ctx, sizeof(double) * n, (void**)&h));
+    memset(h, 0, sizeof(double) * n);
+    if (a.h_dims) orient_box_rows(box, h);
+    h += p->n_box();
+    memcpy(h, a.h_coeff, sizeof(double) * n_coeff);
+    memcpy(h + n_coeff, a.h_members, sizeof(int32_t) * n_member);
+    return ctx->chain_tab.send(ctx, st);
+}
+
+// One call on the pair-major position slab of either element type, read as it is (the caller has opened the call's bracket,
+// it is closed here; chain_plan has queued the table).  Per batch of B functionals -- as many as keep their blocks under
+// kChainBudget, at least one; "chain_modes_chunk" n: min(n, that count) -- ceil(B / tile modes) passes, each a read of the
+// slab, write the batch's blocks, then ONE VACF lag-sum evaluation per functional on its block is its row of d_acf (Q, T).
+// A functional's block and evaluation do not depend on the batch or the launch it was in: the same bits for every chunk.
+// ev[1] / ev[2] bracket the (last) pass, unless an evaluation after it records its own.
+int chain_pm(ta_ctx* ctx, bool fft, const Slab& slab, const ChainPlan& p, double* d_acf) {
+    const int64_t pitch = slab.pitch, T = slab.T;
+    hipStream_t st = slab.st;
+    int MC = 1, F = 2;
+    chain_modes_tile(&MC, &F);
+    const size_t block = (size_t)((3 * p.C + 1) / 2) * (size_t)pitch * 2;  // doubles per functional
+    const int fit = (int)std::max<size_t>(1, std::min<size_t>((size_t)p.Q, kChainBudget / (block * sizeof(double))));
+    const int B = ctx->opt_chain_modes_chunk > 0 ? (int)std::min<int64_t>(ctx->opt_chain_modes_chunk, fit) : fit;
+    TA_CHECK(ensure(ctx, ctx->chain_z, block * sizeof(double) * (size_t)B));
+    double* Z = (double*)ctx->chain_z.p;
+    const double* tab = (const double*)ctx->chain_tab.dev.p;
+    const double* box = p.tpitch ? tab : nullptr;
+    const double* coeff = tab + p.n_box();
+    const int* member = (const int*)(coeff + (size_t)p.Q * (size_t)p.N);
+    for (int q0 = 0; q0 < p.Q; q0 += B) {
+        const int nb = std::min(B, p.Q - q0);
+        for (int l0 = 0; l0 < nb; l0 += MC)
+            TA_LAUNCH_MAIN(ctx, "k_chain_modes", st,
+                           launch_chain_modes(ctx->n_cu, slab.pm, slab.f32, (long)pitch, (long)T, (long)slab.A, slab.D, (long)p.C, (int)p.N,
+                                              member, coeff + (size_t)(q0 + l0) * (size_t)p.N, std::min(MC, nb - l0), box, (long)p.tpitch,
+                                              Z + (size_t)l0 * block, st));
+        for (int b = 0; b < nb; ++b)
+            TA_CHECK(acf_impl(ctx, fft, Z + (size_t)b * block, pitch, T, p.C, 3, d_acf + (size_t)(q0 + b) * (size_t)T, nullptr, 0, st));
+    }
+    return call_end(ctx, st);
+}
+
+// ta_chain_modes_staged and the device half of ta_chain_modes (out != NULL: the context's own output buffer takes d_acf's place)
+int chain_entry(ta_ctx* ctx, const ChainArgs& a, double* d_acf, void* stream, double** out) {
+    BoxTable box;
+    ChainPlan plan;
+    return slab_entry(
+        ctx, nullptr, stream, [&] { return chain_check(ctx, a, &box); },
+        [&](const Slab& s) -> int {
+            TA_CHECK(chain_plan(ctx, a, box, s.st, &plan));
+            if (out) TA_CHECK(out_buffer(ctx, ctx->chain_out, chain_modes_out(a.Q, s.T), out));
+            return TA_OK;
+        },
+        [&](const Slab& s) { return chain_pm(ctx, a.fft != 0, s, plan, out ? *out : d_acf); });
+}
+
 // ---- current correlation functions (kcurrent.hip) -------------------------------------------------------------------
 // The budget of k_kcurrent's partial-sum buffer: G KC pitch D 16 bytes bound its atom groups G.  A choice, not a
 // measurement: the headline shape (10000 x 100000 x 3) asks for ~100 groups = 0.2 GB next to its 48 GB of slabs; the cap
@@ -2640,6 +2769,9 @@ int opt_check_partial_chunk(ta_ctx* ctx, int64_t value) {
 int opt_check_partial_cross_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "partial_cross_chunk: 0 (automatic) or the wavevectors per batch");
 }
+int opt_check_chain_modes_chunk(ta_ctx* ctx, int64_t value) {
+    return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "chain_modes_chunk: 0 (automatic) or the modes per batch");
+}
 int opt_check_scatter_chunk(ta_ctx* ctx, int64_t value) {
     return value >= 0 ? TA_OK : fail(ctx, TA_E_INVALID, "scatter_chunk: 0 (automatic) or the wavevectors per pass");
 }
@@ -3536,6 +3668,14 @@ int ta_shell_msd_staged(ta_ctx* ctx, int condition, int64_t max_lag, int64_t n_a
     return shell_staged(ctx, SHELL_MSD, 0, {n_a, n_b, h_idx_a, h_idx_b, h_dimensions, axes, r_cut, r_break, gap, condition, max_lag},
                         {d_sums, d_count, d_runs, d_nb}, stream);
 }
+int ta_chain_modes_staged(ta_ctx* ctx, int fft, int64_t n_chains, int64_t chain_len, const int32_t* h_members, int n_modes,
+                           const double* h_coeff, const double* h_dimensions, double* d_acf, void* stream) {
+    return ta::guarded(fail, ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    return chain_entry(ctx, ChainArgs{fft, n_chains, chain_len, h_members, n_modes, h_coeff, h_dimensions, d_acf}, d_acf, stream, nullptr);
+    });
+}
+
 int ta_shell_orient_staged(ta_ctx* ctx, int condition, int64_t max_lag, int mode, int anchor, const int32_t* h_index, int64_t n_a,
                            const int64_t* h_idx_a, int64_t n_b, const int64_t* h_idx_b, const double* h_dimensions, const int* axes,
                            double r_cut, double r_break, int gap, double* d_sums, int64_t* d_count, int64_t* d_runs, double* d_nb,
@@ -4173,6 +4313,36 @@ int ta_orient(ta_ctx* ctx, int fft, int mode, int64_t n_vectors, const int32_t* 
                           &d_out));
     return out_finish(ctx, orient_out(ctx->st_T), d_out, {h_c1, h_c2, h_total, h_coll});
     });
+}
+
+int ta_chain_modes(ta_ctx* ctx, int fft, int64_t n_chains, int64_t chain_len, const int32_t* h_members, int n_modes,
+                   const double* h_coeff, const double* h_dimensions, double* h_acf) {
+    return host_call(ctx, [&]() -> int {
+    TA_CHECK(need_ctx(ctx));
+    const ChainArgs a{fft, n_chains, chain_len, h_members, n_modes, h_coeff, h_dimensions, h_acf};
+    if (ctx->is_cpu) {
+        BoxTable box;
+        TA_CHECK(chain_check(ctx, a, &box));
+        std::vector<double> rows;
+        if (h_dimensions) {
+            rows.resize((size_t)kOrientBoxRows * (size_t)box.tpitch);
+            orient_box_rows(box, rows.data());
+        }
+        return cpu_rc(ctx, ta::cpu::chain_modes(cpu_state(ctx), fft != 0, n_chains, chain_len, h_members, n_modes, h_coeff,
+                                                h_dimensions ? rows.data() : nullptr, box.tpitch, h_acf));
+    }
+    double* d_out = nullptr;
+    TA_CHECK(chain_entry(ctx, a, nullptr, ctx->stream, &d_out));
+    return out_finish(ctx, chain_modes_out(n_modes, ctx->st_T), d_out, {h_acf});
+    });
+}
+
+int ta_chain_modes_tile(int* modes, int* frames) {
+    int a = 0, b = 0;
+    ta::chain_modes_tile(&a, &b);
+    if (modes) *modes = a;
+    if (frames) *frames = b;
+    return TA_OK;
 }
 
 int ta_scatter_collective(ta_ctx* ctx, int fft, const double* h_density, int n_k, int64_t n_frames, double* h_coll) {

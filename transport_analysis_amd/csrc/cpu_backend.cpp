@@ -40,6 +40,7 @@
 #include "../../include/ta_hip.h"
 #include "cpu_backend.hpp"
 #include "kcurrent_math.hpp"
+#include "chain_math.hpp"
 #include "orient_math.hpp"
 #include "bond_math.hpp"
 #include "pair_math.hpp"
@@ -685,6 +686,62 @@ int orient(const State& s, bool fft, int mode, int64_t N, const int32_t* index, 
     if (coll) {
         std::vector<double> m(tot, tot + (size_t)T * 3);  // (the evaluation may not write to the caller's total)
         if (int rc = acf(1, m.data(), coll)) return rc;
+    }
+    return TA_OK;
+}
+
+// y (Q, T, C, 3): functional q of chain c in frame t, by chain_math.hpp's sequence in bead order
+template <class E, bool PERIODIC>
+static void chain_frames(const State& s, int64_t C, int64_t N, const int32_t* members, int Q, const double* coeff, const double* box,
+                         int64_t tpitch, double* y) {
+    const int64_t T = s.T, A = s.A;
+    const void* slab = s.slabs[0];
+#pragma omp parallel for num_threads(s.threads) schedule(static)
+    for (int64_t c = 0; c < C; ++c) {
+        const int32_t* row = members + c * N;
+        std::vector<double> acc((size_t)Q * 3);
+        for (int64_t t = 0; t < T; ++t) {
+            OrientBox bx{};
+            if (PERIODIC) {
+                const double* b = box + (tpitch == 1 ? 0 : t);
+                bx = OrientBox{b[0], b[tpitch], b[2 * tpitch], b[3 * tpitch], b[4 * tpitch], b[5 * tpitch], b[6 * tpitch], b[7 * tpitch],
+                               b[8 * tpitch]};
+            }
+            std::fill(acc.begin(), acc.end(), 0.0);
+            double prev[3], cur[3], sum[3] = {0.0, 0.0, 0.0};
+            for (int d = 0; d < 3; ++d) prev[d] = elem<E>(slab, ((size_t)t * A + (size_t)row[0]) * 3 + d);
+            for (int64_t n = 1; n < N; ++n) {
+                for (int d = 0; d < 3; ++d) cur[d] = elem<E>(slab, ((size_t)t * A + (size_t)row[n]) * 3 + d);
+                chain_step<PERIODIC>(prev, cur, bx, sum);
+                for (int q = 0; q < Q; ++q) chain_term(coeff[(size_t)q * N + n], sum, *reinterpret_cast<double(*)[3]>(&acc[(size_t)q * 3]));
+                for (int d = 0; d < 3; ++d) prev[d] = cur[d];
+            }
+            for (int q = 0; q < Q; ++q)
+                for (int d = 0; d < 3; ++d) y[(((size_t)q * T + t) * C + c) * 3 + d] = acc[(size_t)q * 3 + d];
+        }
+    }
+}
+
+int chain_modes(const State& s, bool fft, int64_t C, int64_t N, const int32_t* members, int Q, const double* coeff, const double* box,
+                int64_t tpitch, double* acf) {
+    const int64_t T = s.T;
+    std::vector<double> y;
+    try {
+        y.assign((size_t)Q * T * C * 3, 0.0);
+    } catch (const std::bad_alloc&) {
+        return TA_E_NOMEM;
+    }
+    if (s.dtype == TA_F32) {
+        if (box) chain_frames<float, true>(s, C, N, members, Q, coeff, box, tpitch, y.data());
+        else chain_frames<float, false>(s, C, N, members, Q, coeff, box, tpitch, y.data());
+    } else {
+        if (box) chain_frames<double, true>(s, C, N, members, Q, coeff, box, tpitch, y.data());
+        else chain_frames<double, false>(s, C, N, members, Q, coeff, box, tpitch, y.data());
+    }
+    for (int q = 0; q < Q; ++q) {
+        const State v = f64_slab(s.threads, T, C, 3, y.data() + (size_t)q * T * C * 3);
+        double* out = acf + (size_t)q * T;
+        if (int rc = fft ? vacf_fft(v, out, nullptr) : vacf_direct(v, out, nullptr)) return rc;
     }
     return TA_OK;
 }

@@ -58,6 +58,11 @@ int scatter_collective(int threads, bool fft, const double* density, int K, int6
 // (H00 H10 H11 H20 H21 H22 M00 M11 M22) of tpitch doubles (tpitch 1: one constant box); arguments checked by the caller
 int orient(const State& s, bool fft, int mode, int64_t N, const int32_t* index, const double* box, int64_t tpitch, const double* w,
            double* c1, double* c2, double* total, double* coll);
+// ta_chain_modes: Q linear functionals (coeff (Q, N)) of C chains (members (C, N) atoms of slab 0, dim 3, in backbone order) with
+// chain_math.hpp's sequence, as chain_modes.hip: OpenMP over chains, one frame-major (n_frames, C, 3) array per functional;
+// acf (Q, n_frames) = their vacf_fft / vacf_direct lag sums, one evaluation per functional.  box, tpitch: as orient's
+int chain_modes(const State& s, bool fft, int64_t C, int64_t N, const int32_t* members, int Q, const double* coeff, const double* box,
+                int64_t tpitch, double* acf);
 // ta_kcurrent: the k-space current of slab 0 (the velocities) and slab 1 (the positions) for K wavevectors kvecs (K, dim), with
 // kcurrent.hip's arithmetic (the phase as scatter(); w_n v by a product, then one fma with the cosine and one with the sine):
 // current (K, n_frames, dim, 2) = the plain sum in atom order (w NULL: all 1), lon / trans (K, n_frames) = kcurrent_correlate

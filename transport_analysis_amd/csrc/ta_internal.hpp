@@ -104,6 +104,8 @@ inline OutLayout self_out(int S, int64_t T) { return {out_n(S, T)}; }
 inline OutLayout scatter_out(int K, int64_t T) { return {out_n(K, T), out_n(K, T, 2), out_n(K, T)}; }
 // ta_orient: c1 (T) | c2 (T) | total (T, 3) | coll (T)
 inline OutLayout orient_out(int64_t T) { return {out_n(T), out_n(T), out_n(T, 3), out_n(T)}; }
+// ta_chain_modes: acf (Q, T)
+inline OutLayout chain_modes_out(int Q, int64_t T) { return {out_n(Q, T)}; }
 // ta_kcurrent: current (K, T, D, 2) | long (K, T) | trans (K, T)
 inline OutLayout kcurrent_out(int K, int64_t T, int D) { return {out_n(K, T, D, 2), out_n(K, T), out_n(K, T)}; }
 // ta_partial_density: density (K, S, T, 2) | cross term (K, T, S, S)
@@ -469,6 +471,17 @@ hipError_t launch_scatter_transpose(const double* bp, long T, long K, double* ou
 // of kOrientBoxRows rows of tpitch doubles (tpitch 1: one constant box; else one box per frame, tpitch >= T)
 hipError_t launch_orient(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, int mode, int rank,
                          long n_vectors, const int* index, const double* box, long tpitch, double* Z, hipStream_t st);
+
+// chain_modes.hip: the blocks of n_q <= tile modes linear functionals (coeff (n_q, chain_len), device float64) of n_chains
+// chains (member (n_chains, chain_len), device int32: atoms of the slab in backbone order) of a pair-major slab of float64 or
+// (f32) float32 elements with D = 3, read as it is (chain_math.hpp: the chain made whole bead by bead).  Z: n_q float64
+// pair-major blocks behind each other, each n_chains pseudo-atoms of dim 3 = ceil(3 n_chains / 2) pairs of `pitch` rows, rows
+// T ... pitch - 1 and the phantom column zeros.  box: as launch_orient's.  chain_modes_tile: the modes per launch and the
+// frames per thread of the one tile (a workgroup covers 256 frames of them).
+hipError_t launch_chain_modes(int n_cu, const void* x, bool f32, long pitch, long T, long n_atoms, int D, long n_chains, int chain_len,
+                              const int* member, const double* coeff, int n_q, const double* box, long tpitch, double* Z,
+                              hipStream_t st);
+void chain_modes_tile(int* modes, int* frames);
 
 // kcurrent.hip: the k-space current of kc <= KC wavevectors q (kc, D) (device array, turns per length unit) from the pair-major
 // slabs v (velocities) and x (positions) of float64 or (f32) float32 elements, both read as they are, in one pass: partial
